@@ -12,7 +12,12 @@ GPU (seed 1000*4 + k).  One step = one Forward fill over
   --mode rolling: RollingOutputForwardMatrix semantics (`boss --loglike`), log-likelihood only, ~0 algorithmic bytes.
   --scaling weak (default): --pairs pairs PER GPU;  strong: --pairs pairs in total, dealt to the ranks by cell count.
 
-Prints ONE JSON line (rank 0).  Besides the contract's keys it carries `roofline`, `cpu_baseline` and, at N = 1, `extra`:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps of the headline and prints the line: the
+contract's keys and the `roofline` of those steps (no recorded constants).  --dump-outputs DIR writes what the last timed step
+returned (DIR/loglike.npy: one float64 log-likelihood per pair, in pair order over all ranks).
+
+--full adds everything else, as a plain run did before: the recorded constants (`roofline.traffic` / `issue`, checked by kernel
+hash), `cpu_baseline` and, at N = 1, `extra`:
 the other modes of the path on the BASELINE configs they are quoted on (config 3: Forward-Backward counts on protpsw,
 config 2: Viterbi + traceback on dnapsw, config 1: cold-start latency of one 50-aa pair), each with its own roofline
 block; the other two modes of the HEADLINE machine on config 4's own shape (`viterbi4`: one traceback byte per cell,
@@ -174,9 +179,11 @@ def parse_args(argv=None):
     ap.add_argument("--inlen", type=int, default=487)
     ap.add_argument("--outlen", type=int, default=10000)
     ap.add_argument("--preset", default="psw2dna")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra (non-headline) measurements")
-    ap.add_argument("--extra-em-only", action="store_true", help="of the extras, only the EM iteration with its all-reduce (needs a rank group: N > 1 or MB_BENCH_FORCE_COMM=1)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: recorded constants, the cpu_baseline leg and the extra (non-headline) measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra (non-headline) measurements")
+    ap.add_argument("--extra-em-only", action="store_true", help="with --full: of the extras, only the EM iteration with its all-reduce (needs a rank group: N > 1 or MB_BENCH_FORCE_COMM=1)")
     ap.add_argument("--write-kernel-sha", metavar="FILE", help="write the hashes of this run's generated kernel sources (profiles/<tag>_kernel_sha.json: what recorded PMC / issue figures are checked against)")
     ap.add_argument("--dropin-only", action="store_true", help="only extra.dropin (the reference's call sites through the C++ classes); prints that block")
     ap.add_argument("--quick", action="store_true", help="with --dropin-only: small batches")
@@ -617,6 +624,32 @@ def extra_dropin(capi, np, quick=False):
     return out
 
 
+DUMP_CAP_BYTES = 64 << 20      # --dump-outputs writes at most this much; a larger array is cut to a fixed, seeded sample
+
+
+def dump_outputs(out_dir, grp, rank, world, mine, ll):
+    """--dump-outputs: the log-likelihoods of the last timed step, one float64 per pair in global pair order (every rank's
+    shard gathered on rank 0), as out_dir/loglike.npy.  Collective at N > 1: every rank calls it."""
+    import numpy as np
+    ll = np.asarray(ll, np.float64)
+    if world > 1:
+        n = int(grp.all_reduce_float(float(len(mine)), "max"))
+        pad = [0.0] * (n - len(mine))
+        rows = grp.all_gather_floats([float(len(mine))] + [float(k) for k in mine] + pad + [float(v) for v in ll] + pad)
+        full = np.full(sum(int(r[0]) for r in rows), np.nan)
+        for r in rows:
+            c = int(r[0])
+            full[np.asarray(r[1:1 + c], np.int64)] = r[1 + n:1 + n + c]
+        ll = full
+    if rank != 0:
+        return
+    cap = DUMP_CAP_BYTES // ll.itemsize
+    if ll.size > cap:
+        ll = ll[np.sort(np.random.default_rng(0).choice(ll.size, cap, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loglike.npy"), ll)
+
+
 def main():
     args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -649,7 +682,7 @@ def main():
 
     capi.set_device(local_rank)
     global DUMP_DIR
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and (args.full or args.write_kernel_sha or args.dropin_only):
         import tempfile
         DUMP_DIR = tempfile.mkdtemp(prefix="mb_bench_kernels_")
         dump_kernels_as(args.preset)
@@ -706,6 +739,8 @@ def main():
         dt = grp.all_reduce_float(dt, "max")
         total_cells = grp.all_reduce_float(float(cells_rank), "sum")
     value = total_cells * args.steps / dt / 1e9
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, grp, rank, world, mine, ll)
 
     extra = {}
     if world > 1:
@@ -736,7 +771,7 @@ def main():
             "config 2-4 (batches of pairs, this line)": "weak scaling 1.0 per GPU by construction: every rank fills its own pairs, no data-path collective; strong scaling of 256 pairs over 8 GPUs leaves 32 pairs per GPU, whose tile wavefront still fills 256 CUs (672 live tiles per launch)",
             "config 3 (--train)": "one all-reduce of nTransitions + 1 doubles (3.6 KB) per EM iteration: latency only",
             "config 5 (64 sequences x 50 kb over 8 GPUs)": "STRONG scaling ceiling 1.0-1.3x for the 5 063-state machine (measured on one GPU, extra.config5.eight_per_gpu of the N = 1 line: 64 sequences against 8; round 6 with the generated sweeps: Forward 1.27, Viterbi 1.06, --align 1.04): a one-tape lattice is serial along its columns, a sequence is k <= 8 workgroups and its period a latency chain of 5 rounds (DESIGN.md 4.4), so 8 sequences per GPU take almost as long as 64 on one GPU; only a batch of more sequences than CUs scales.  The whole fn3 profile (21 761 states, ring beyond one CU's LDS) does scale with workgroups per sequence: 64 -> 16 -> 4 sequences x 3 kb take 30 -> 18 -> 15 ms (Viterbi fill)"}
-    if grp and not args.no_extra:
+    if grp and args.full and not args.no_extra:
         # the ONE collective of the path (--train): E-step on this rank's shard of config 3, then the all-reduce of
         # nTransitions + 1 doubles over RCCL (xGMI)
         mp = Machine.fromFile(os.path.join(ROOT, "tests", "golden", "preset", "protpsw.json"))
@@ -759,7 +794,7 @@ def main():
                                  "ms_per_iteration": round(d1 * 1e3, 3), "allreduce_ms": round(tr * 1e3, 3), "n_ranks_seen": int(round(seen)),
                                  "value": round(world * bp.cells() / d1 / 1e9, 2), "unit": "G lattice-cells/s over all ranks",
                                  "symbol_count_invariant": nsym / (world * per * 400)}
-    if world == 1 and rank == 0 and not args.no_extra and not args.extra_em_only:
+    if world == 1 and rank == 0 and args.full and not args.no_extra and not args.extra_em_only:
         other = capi.MB_ROLLING if flags == capi.MB_MATERIALISE else capi.MB_MATERIALISE
         _, d1 = timed(lambda: batch.forward(other), label="headline.other_mode")
         extra["rolling_gcells_per_gpu" if other == capi.MB_ROLLING else "materialised_gcells_per_gpu"] = round(cells_rank / d1 / 1e9, 3)
@@ -775,7 +810,7 @@ def main():
             extra["rolling_note"] = "boss --loglike mode: no matrix in HBM, bound by vector instruction issue (fp64 add/max, v_exp_f32/v_log_f32), not by HBM; the HBM fraction is not meaningful for it"
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:      # the CPU leg runs at N = 1 only (the other ranks would idle behind it)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:      # the CPU leg runs at N = 1 only (the other ranks would idle behind it)
         from concurrent.futures import ThreadPoolExecutor
         from oracle import oracle   # checker / baseline only: never on the product path
         om = oracle.OracleMachine(em)
@@ -814,7 +849,7 @@ def main():
                "sample": "%d pairs (one per host core, concurrently) of %d aa x %d nt on %s (%.1f s wall), RollingOutputForwardMatrix restatement oracle/mb_oracle.c, table logsumexp"
                          % (cores, args.inlen, sample_out, args.preset, d2)}
 
-    if rank == 0 and world == 1 and not args.no_extra and not args.extra_em_only:
+    if rank == 0 and world == 1 and args.full and not args.no_extra and not args.extra_em_only:
         extra.update(extra_single_gpu(capi, np, HBM_PEAK_GBS))
         try:
             extra["train"] = extra_train(capi, np)
@@ -847,15 +882,15 @@ def main():
         # library stream around the launch sequence; launches are back to back, gaps < 1 us in the rocprof trace)
         ach = BYTES_PER_CELL * cells_rank * args.steps / (dev_ms / 1e3) / 1e9 if (dev_ms > 0 and flags == capi.MB_MATERIALISE) else 0.0
         traffic = None
-        traffic_src = None
-        pmc = recorded(PROFILE_TAG + "_pmc_hbm.json")      # HBM bytes per launch from the committed PMC passes: a recorded constant, valid for the default workload and the kernel it was measured on
+        traffic_src = None if args.full else "recorded constants are quoted with --full"
+        pmc = recorded(PROFILE_TAG + "_pmc_hbm.json") if args.full else None      # HBM bytes per launch from the committed PMC passes: a recorded constant, valid for the default workload and the kernel it was measured on
         if pmc and pmc.get("kernel") == kernel and pmc.get("cells_per_step") == cells_rank and flags == capi.MB_MATERIALISE:
             if kernels_unchanged("traffic:headline", ["psw2dna.sum.mat.fwd.clos"]):
                 traffic = round(pmc["hbm_bytes_per_cell"] * cells_rank * args.steps / max(launches, 1))
                 traffic_src = "profiles/%s_pmc_hbm.json (rocprofv3 --pmc WRITE_SIZE / FETCH_SIZE passes of this command; recorded -- kernel source verified unchanged by hash)" % PROFILE_TAG
             else:
                 traffic_src = REFUSED.get("traffic:headline")
-        elif flags == capi.MB_MATERIALISE:
+        elif flags == capi.MB_MATERIALISE and args.full:
             traffic_src = "no PMC passes recorded for this workload (profiles/%s_pmc_hbm.json)" % PROFILE_TAG
         out = {
             "metric": "Giga DP-cells/sec (Forward) on composed protpsw machine",
@@ -875,12 +910,13 @@ def main():
                          "avg_launch_us": round(dev_ms * 1e3 / max(launches, 1), 2),
                          "device_ms_per_step": round(dev_ms / args.steps, 3),
                          "issue": valu_issue(["psw2dna.sum.mat.fwd.clos.hip" if flags == capi.MB_MATERIALISE else "psw2dna.sum.roll.fwd.clos.hip"],
-                                             cells_rank * args.steps / max(dev_ms / 1e3, 1e-9)) if args.preset == "psw2dna" else None},
+                                             cells_rank * args.steps / max(dev_ms / 1e3, 1e-9)) if args.full and args.preset == "psw2dna" else None},
             "cpu_baseline": cpu,
             "loglike_checksum": float(np.sum(ll)),      # this rank's (rank 0); all ranks: extra.checks.loglike_checksum_all_ranks
-            "recorded_constants": {"tag": PROFILE_TAG, "refused": dict(REFUSED), "kernel_sha": kernel_sha_now()},
             "extra": extra,
         }
+        if args.full:
+            out["recorded_constants"] = {"tag": PROFILE_TAG, "refused": dict(REFUSED), "kernel_sha": kernel_sha_now()}
         if extra:
             # wall clock beside device time for every timed mode, and the modes where the two differ
             extra["timings"] = {"unit": "[wall ms, device ms] per call", **TIMINGS}
@@ -906,7 +942,7 @@ def main():
         print(json.dumps(out))
         sys.stdout.flush()
     failed = rank == 0 and world > 1 and not (extra.get("checks") or {}).get("ok", False)
-    if grp and not args.no_extra and world > 1 and rank == 0 and (extra.get("em_iteration") or {}).get("n_ranks_seen") != world:
+    if grp and args.full and not args.no_extra and world > 1 and rank == 0 and (extra.get("em_iteration") or {}).get("n_ranks_seen") != world:
         failed = True
     if grp:
         grp.close()

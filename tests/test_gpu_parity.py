@@ -2213,7 +2213,7 @@ def test_bench_two_ranks_dry_run(capi, scaling):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "6", "--outlen", "700",
-                        "--scaling", scaling], capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
+                        "--scaling", scaling, "--full"], capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                        # rank 0 prints the one JSON line
@@ -2252,7 +2252,7 @@ def test_bench_eight_ranks_dry_run(capi, scaling, tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MB_MEM_FRACTION"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--pairs", "4" if scaling == "weak" else "12", "--outlen", "1000",
-                        "--scaling", scaling], capture_output=True, text=True, cwd=ROOT, env=env, timeout=1200)
+                        "--scaling", scaling, "--full"], capture_output=True, text=True, cwd=ROOT, env=env, timeout=1200)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -2296,7 +2296,7 @@ def test_bench_one_rank_rccl_communicator(capi):
     """The RCCL route of bench.py / boss.py (shard.RankGroup: unique id on rank 0 -> broadcast over gloo -> mb_comm_init ->
     mb_allreduce_counts on the library's own HIP runtime and stream, torch never on the GPU) with the one-rank communicator a
     one-GPU box can form: bootstrap, the EM leg's collective, teardown -- in a process of its own, as a host uses it."""
-    d = _bench_json(["--steps", "1", "--warmup", "1", "--pairs", "4", "--outlen", "500", "--no-cpu", "--extra-em-only"], {"MB_BENCH_FORCE_COMM": "1"})
+    d = _bench_json(["--steps", "1", "--warmup", "1", "--pairs", "4", "--outlen", "500", "--full", "--no-cpu", "--extra-em-only"], {"MB_BENCH_FORCE_COMM": "1"})
     em = d["extra"]["em_iteration"]
     assert d["n_gpus"] == 1 and em["n_ranks_seen"] == 1 and "RCCL through the C-ABI" in em["workload"]
     assert abs(em["symbol_count_invariant"] - 1.0) < 1e-4
@@ -2310,7 +2310,7 @@ def test_bench_two_ranks_over_rccl(capi, backend):
     over BOTH ranks' pairs."""
     if capi.device_count() < 2:
         pytest.skip("needs two GPUs")
-    d = _bench_json(["--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "6", "--outlen", "700"], {"MB_BENCH_BACKEND": backend})
+    d = _bench_json(["--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "6", "--outlen", "700", "--full"], {"MB_BENCH_BACKEND": backend})
     assert d["n_gpus"] == 2 and d["config"]["cells_per_gpu_per_step"] * 2 == 12 * 488 * 701 * 271
     assert sum(r["cells_per_step"] for r in d["extra"]["per_rank"]) == 12 * 488 * 701 * 271
     em = d["extra"]["em_iteration"]
