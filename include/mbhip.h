@@ -212,6 +212,12 @@ int mb_debug_jit_source(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_
                         const uint32_t *dst, const uint16_t *inTok, const uint16_t *outTok, const double *logWeight,
                         int mode, int backward, int closure, int G, const char *path);
 
+/* The plan of the persistent-strip form of the pipelined Forward (host only): strips of C columns, pair p in matrix slot p % nSlots.
+ * Writes the tickets as (pair, strip) int32 pairs in the order workgroups take them, and per pair (slot, strips of that slot that
+ * must have finished before the pair starts); returns the number of tickets, -1 on error. */
+int64_t mb_debug_persist_plan(int64_t nPairs, const int32_t *inLen, const int32_t *outLen, int32_t C, int64_t nSlots, int32_t *tickets,
+                              int64_t maxTickets, int32_t *wait);
+
 /* The same for the small-machine family (machines of <= 16 states: lane = column, states in registers); mode 0 = sum
  * semiring, 1 = max with fp64 cells, 2 = max with one traceback byte per cell, 3 = Forward fused with posterior counts;
  * mode + 32 writes the PROGRAM the generator unrolls instead: 20 int32 (magic 0x534D5031, S, nIn, nOut, backward, seed and end

@@ -1314,8 +1314,13 @@ static int run_fill_loglike(mb_batch *b, int mode, int flags, double *loglike) {
     else if ((long long)(g_ws[0].bytes / 8) < b->maxPairCells) { set_error("a single DP matrix exceeds the device memory budget"); rc = 1; }
     else {
       tm.start();
-      rc = medium_forward_pipelined(m, f->fwdSum, f->geoFS, b->pairs, b->d_in, b->d_out, pool, (long long)(g_ws[0].bytes / 8), d_ll, g_stream);
-      g_last_kernel = medium_jit_ready(f->fwdSum, MB_FORWARD, MED_MAT_FULL) ? "k_medium_jit" : "k_medium_tile<0>";
+      rc = medium_forward_pipelined(m, f->fwdSum, f->geoFS, b->pairs, b->d_in, b->d_out, pool, (long long)(g_ws[0].bytes / 8), d_ll, g_stream, !m->mediumPersistOff);
+      if (rc == 2) {      // a persistent strip waited longer than MB_MEDIUM_PERSIST_TIMEOUT_S: latched off for this machine, the call runs again launch by launch
+        m->mediumPersistOff = true;
+        fprintf(stderr, "[mbhip] WARNING: a persistent strip of the pipelined Forward waited longer than MB_MEDIUM_PERSIST_TIMEOUT_S for another strip (is the device shared?): the call is run again launch by launch, and so are this machine's later calls\n");
+        rc = medium_forward_pipelined(m, f->fwdSum, f->geoFS, b->pairs, b->d_in, b->d_out, pool, (long long)(g_ws[0].bytes / 8), d_ll, g_stream, false);
+      }
+      g_last_kernel = (medium_jit_ready(f->fwdSum, MB_FORWARD, MED_MAT_FULL) || medium_jit_ready(f->fwdSum, MB_FORWARD, MED_MAT_PERSIST)) ? "k_medium_jit" : "k_medium_tile<0>";
       g_last_ms += tm.stop();
     }
   } else {
@@ -1738,6 +1743,20 @@ int mb_fill(mb_machine *m, int mode, const int32_t *in, int64_t inLen, const int
   return mb_fill_env(m, mode, in, inLen, out, outLen, startState, nullptr, nullptr, cellsOut);
 }
 
+// ---- introspection: the persistent-strip plan of a batch (host only): tickets (pair, strip) and per pair (slot, strips to wait for) ----
+int64_t mb_debug_persist_plan(int64_t nPairs, const int32_t *inLen, const int32_t *outLen, int32_t C, int64_t nSlots, int32_t *tickets, int64_t maxTickets, int32_t *wait) {
+  ApiLock lock;
+  if (nPairs < 0 || C < 1 || nSlots < 1 || (nPairs > 0 && (!inLen || !outLen || !wait))) { set_error("mb_debug_persist_plan: bad argument"); return -1; }
+  std::vector<PairDesc> pairs((size_t)nPairs);
+  for (int64_t p = 0; p < nPairs; ++p) { pairs[p].inLen = inLen[p]; pairs[p].outLen = outLen[p]; }
+  std::vector<int2> tk, w;
+  medium_persist_plan(pairs, C, nSlots, tk, w);
+  if ((int64_t)tk.size() > maxTickets || (!tickets && !tk.empty())) { set_error("mb_debug_persist_plan: ticket buffer too small"); return -1; }
+  for (size_t k = 0; k < tk.size(); ++k) { tickets[2 * k] = tk[k].x; tickets[2 * k + 1] = tk[k].y; }
+  for (size_t p = 0; p < w.size(); ++p) { wait[2 * p] = w[p].x; wait[2 * p + 1] = w[p].y; }
+  return (int64_t)tk.size();
+}
+
 // ---- introspection: generated source of the run-time specialised tile kernel (host only, no device needed) ------
 int mb_debug_jit_source(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_t nTrans, const uint32_t *src, const uint32_t *dst,
                         const uint16_t *inTok, const uint16_t *outTok, const double *logWeight, int mode, int backward, int closure,
@@ -1753,8 +1772,8 @@ int mb_debug_jit_source(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_
   std::string err;
   if (!compile_machine(&m, &err)) { set_error(err); return 1; }
   // mode: MB_FORWARD sum, MB_VITERBI max, 3 count, 4 max with traceback bytes; + 16: tiles without a matrix (MED_MAT_ROLL; implied by 4);
-  // + 32: the PROGRAM instead of the source (see below)
-  const int matKind = ((mode & 16) || (mode & 15) == MED_MODE_TB) ? MED_MAT_ROLL : MED_MAT_FULL;
+  // + 32: the PROGRAM instead of the source (see below); + 128: the persistent-strip matrix kernel (MED_MAT_PERSIST, sum only)
+  const int matKind = (mode & 128) ? MED_MAT_PERSIST : (((mode & 16) || (mode & 15) == MED_MODE_TB) ? MED_MAT_ROLL : MED_MAT_FULL);
   const bool dumpProgram = (mode & 32) != 0;
   const bool compactRing = (mode & 64) != 0;      // + 64: the matrix-free kernel with the COMPACT ring (as many wavefronts as its LDS allows, at most 12)
   mode &= 15;
@@ -1799,7 +1818,7 @@ int mb_debug_jit_source(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_
     if (!ok) { set_error("mb_debug_jit_source: short write"); return 1; }
     return 0;
   }
-  if (matKind == MED_MAT_ROLL) geo.haloSteps = 0;
+  if (matKind != MED_MAT_FULL) geo.haloSteps = 0;
   if (compactRing) {
     if (matKind != MED_MAT_ROLL || P.recC.empty()) { set_error("mb_debug_jit_source: no compact ring for this kernel kind"); return 1; }
     geo.compact = true; geo.haloSteps = 0;
@@ -1809,6 +1828,7 @@ int mb_debug_jit_source(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_
     }
   }
   if (mode == MED_MODE_TB && !medium_tb_eligible(&m, P)) { set_error("machine does not qualify for traceback bytes on the tiled family"); return 1; }
+  if (matKind == MED_MAT_PERSIST && mode != MB_FORWARD) { set_error("mb_debug_jit_source: the persistent-strip kernel is a sum kernel"); return 1; }
   const std::string code = medium_jit_source(&m, P, geo, mode == MED_MODE_COUNT ? MED_MODE_COUNT : (mode == MED_MODE_TB ? MED_MODE_TB : (mode == MB_VITERBI ? MB_VITERBI : MB_FORWARD)), matKind);
   FILE *f = fopen(path, "w");
   if (!f) { set_error("mb_debug_jit_source: cannot open output file"); return 1; }

@@ -67,6 +67,9 @@ struct mb_machine {
   int *d_levFOff = nullptr, *d_levFState = nullptr, *d_levBOff = nullptr, *d_levBState = nullptr;
   mb::DevMachine dev{};
   void *fast = nullptr;   // kernel-family specific compiled tables (owned; see mb_fast_*.hip)
+  // latched: a persistent-strip sweep of this machine waited in vain once (a shared device?) -- launch by launch from then on.  Kept
+  // here, not with the compiled tables, so that a weight update (which rebuilds them) does not clear it
+  bool mediumPersistOff = false;
 };
 
 namespace mb {

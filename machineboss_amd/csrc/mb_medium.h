@@ -13,8 +13,10 @@ constexpr int MED_MODE_COUNT = 3;   // internal kernel mode: Forward fill (sum) 
 constexpr int MED_MODE_TB = 4;      // internal kernel mode: Viterbi fill (max) that keeps ONE traceback byte per cell instead of the fp64 cell
 // what a tile kernel keeps in HBM (JMAT of the specialised kernel): MED_MAT_NONE = one workgroup sweeps a whole strip, halo
 // columns only; MED_MAT_FULL = tiles + the fp64 matrix; MED_MAT_ROLL = tiles without a matrix (halo columns of the few
-// states other strips read + a boundary record per strip): traceback-byte Viterbi, count sweep, log-likelihood-only Forward
-enum { MED_MAT_NONE = 0, MED_MAT_FULL = 1, MED_MAT_ROLL = 2 };
+// states other strips read + a boundary record per strip): traceback-byte Viterbi, count sweep, log-likelihood-only Forward;
+// MED_MAT_PERSIST = the fp64 matrix written by PERSISTENT STRIPS (one workgroup sweeps whole strips taken by ticket, the halo
+// states handed over through a per-strip halo column: medium_forward_pipelined)
+enum { MED_MAT_NONE = 0, MED_MAT_FULL = 1, MED_MAT_ROLL = 2, MED_MAT_PERSIST = 3 };
 constexpr int MED_GEOM_LEVELS = 5;  // strip widths a program is specialised for: its widest, halved 0..4 times
 
 // One candidate of one lane: 16 bytes, fetched with a single global_load_dwordx4.
@@ -124,9 +126,9 @@ struct MedProgram {
   int *d_desc = nullptr;
   MedRec *d_rec = nullptr, *d_ldsImage = nullptr;
   MedProgDev dev{};
-  // [(3 * medium_jit_index(mode) + matKind) * 2 + env][MedGeom::level]: sum / max / count / traceback bytes, MED_MAT_*, and the strip
+  // [(4 * medium_jit_index(mode) + matKind) * 2 + env][MedGeom::level]: sum / max / count / traceback bytes, MED_MAT_*, and the strip
   // width (level h = the program's widest strip halved h times; narrow strips for short input sequences)
-  MedJit jit[24 * MED_GEOM_LEVELS];       // ... x restricted envelopes (MedGeom::env)
+  MedJit jit[32 * MED_GEOM_LEVELS];       // ... x restricted envelopes (MedGeom::env)
 };
 
 // haloSteps > 0: the materialised kernel loads the halo supercells of a whole tile (at most haloSteps steps) into LDS in
@@ -197,7 +199,7 @@ int medium_fill_materialised(const mb_machine *m, MedProgram &P, const MedGeom &
                              double *d_pool, hipStream_t st, const MedEnv &env = MedEnv());
 // run-time specialisation (mb_medium_jit.cpp): returns false if hiprtc is unavailable or the program does not qualify
 bool medium_jit_get(const mb_machine *m, MedProgram &P, const MedGeom &geo, int mode, int matKind, bool allowReplan = true);
-inline int medium_jit_slot(int mode, int matKind, int level, bool env = false) { return ((3 * medium_jit_index(mode) + matKind) * 2 + (env ? 1 : 0)) * MED_GEOM_LEVELS + level; }
+inline int medium_jit_slot(int mode, int matKind, int level, bool env = false) { return ((4 * medium_jit_index(mode) + matKind) * 2 + (env ? 1 : 0)) * MED_GEOM_LEVELS + level; }
 inline int medium_compact_len(const MedProgram &P) { return ((int)P.haloStates.size() + 2) & ~1; }      // halo states + the -inf entry, even
 // geometry of a matrix-free sweep: the compact ring's (tried once per kernel kind: its kernel must compile into the registers its
 // wavefront count leaves, without touching the program's placement) or the plain one
@@ -209,9 +211,14 @@ inline bool medium_jit_ready(const MedProgram &P, int mode, int matKind) {
 // strip width for a batch (narrower strips for short input sequences)
 MedGeom medium_pick_geometry(const MedProgram &P, const MedGeom &geo, const std::vector<PairDesc> &pairs, bool materialise);
 void medium_jit_free(MedProgram &P);
+// persist: the persistent-strip form may be used (MB_MEDIUM_PERSIST); returns 2 -- nothing kept, no error set -- when one of its bounded
+// waits ran out: the caller latches the form off for the machine and calls again with persist = false
 int medium_forward_pipelined(const mb_machine *m, MedProgram &P, const MedGeom &geo, const std::vector<PairDesc> &pairs,
                              const int *d_in, const int *d_out, double *d_pool, long long poolCells, double *d_loglike,
-                             hipStream_t st);
+                             hipStream_t st, bool persist = false);
+// the persistent-strip plan of a batch (host only): tickets in (pair, strip) order, per pair its matrix slot and the strips of that
+// slot that must have finished before it starts -- what a ticket waits for is always a LOWER ticket
+void medium_persist_plan(const std::vector<PairDesc> &pairs, int C, long long nSlots, std::vector<int2> &tickets, std::vector<int2> &wait);
 int medium_forward_rolling(const mb_machine *m, MedProgram &P, const MedGeom &geo, const PairDesc *d_pairs,
                            const std::vector<PairDesc> &pairs, const int *d_in, const int *d_out, double *d_colHalo,
                            const long long *d_haloBase, double *d_loglike, hipStream_t st);

@@ -54,6 +54,11 @@ struct MedTileArgs {
   double *bound;                  // tile-boundary records: the ring state a block hands to the next block of its strip
   const long long *boundBase;     // per pair offset (doubles)
   unsigned char *tb;              // Viterbi traceback bytes (MED_MODE_TB), medium_tb_stride(S) per supercell, PairDesc::cellBase = byte offset
+  // persistent strips (MED_MAT_PERSIST, specialised kernel only): colHalo / haloBase hold the halo columns, `tiles` the tickets
+  unsigned *psync;                // [0] ticket counter, [1] error word, [2 + slot] strips finished in each matrix slot
+  const int2 *pwait;              // per pair: (matrix slot, strips of that slot that finish before the pair starts)
+  long long ptimeout;             // bound of every wait, wall-clock ticks (100 MHz)
+  int ntickets, ppad;
 };
 
 #define MED_L2E 1.44269504088896f
@@ -1404,13 +1409,82 @@ int medium_counts_rolling(const mb_machine *m, MedProgram &P, const MedGeom &geo
   return rc;
 }
 
+void medium_persist_plan(const std::vector<PairDesc> &pairs, int C, long long nSlots, std::vector<int2> &tickets, std::vector<int2> &wait) {
+  tickets.clear(); wait.assign(pairs.size(), make_int2(0, 0));
+  std::vector<int> done((size_t)std::max<long long>(nSlots, 1), 0);      // strips dealt to each slot so far
+  for (size_t p = 0; p < pairs.size(); ++p) {
+    const int slot = (int)(p % (size_t)std::max<long long>(nSlots, 1)), NA = (pairs[p].inLen + C) / C;
+    wait[p] = make_int2(slot, done[slot]);
+    done[slot] += NA;
+    for (int a = 0; a < NA; ++a) tickets.push_back(make_int2((int)p, a));
+  }
+}
+
+// PERSISTENT STRIPS (MB_MEDIUM_PERSIST: 0 off, 1 on, default on wherever the halo columns fit).  The launch-by-launch pipeline below
+// runs ~1 300 launches of 128-step tiles for config 4a; every launch pays a tile prologue (ring preload from the matrix, LDS fill,
+// record image) and a drain, and the pipeline ramps over ~30 launches per pair (485 -> 459 ms per step).  Here
+// ONE grid takes the strips by ticket and sweeps each whole (the generated kernel of MED_MAT_PERSIST, see
+// mb_medium_jit.cpp): one prologue per strip, a strip lags its left neighbour by C + JPAHEAD steps, and the halo states come through
+// a compact halo column instead of the whole supercell read back from the matrix.  Matrix slots keep their meaning: pair p takes slot
+// p % nSlots once every strip of the slot's previous pairs has finished.  Same step body, same cells: bit-identical log-likelihoods.
+// Returns -1 when the form does not apply (nothing launched), 2 when a wait ran out (nothing kept), else 0 / 1.
+static int forward_persistent(const mb_machine *m, MedProgram &P, const MedGeom &geo, const std::vector<PairDesc> &pairsIn, long long slotCells,
+                              const int *d_in, const int *d_out, double *d_pool, long long poolCells, double *d_loglike, hipStream_t st) {
+  const long long n = (long long)pairsIn.size();
+  const int C = geo.C, H = std::max<int>((int)P.haloStates.size(), 1);
+  int maxIn = 0, maxOut = 0;
+  for (const PairDesc &pd : pairsIn) { maxIn = std::max(maxIn, pd.inLen); maxOut = std::max(maxOut, pd.outLen); }
+  // the halo columns of a slot ([NA][outLen + 1][H] doubles of its pair) come out of the same budget, behind the matrices
+  const long long slotHalo = (long long)((maxIn + C) / C) * (maxOut + 1) * H;
+  const long long nSlots = std::min<long long>(poolCells / (slotCells + slotHalo), n);
+  if (nSlots < 1 || !medium_jit_get(m, P, geo, MB_FORWARD, MED_MAT_PERSIST, /*allowReplan=*/false)) return -1;
+  const MedJit &J = P.jit[medium_jit_slot(MB_FORWARD, MED_MAT_PERSIST, geo.level, false)];
+  std::vector<int2> tickets, wait;
+  medium_persist_plan(pairsIn, C, nSlots, tickets, wait);
+  if (tickets.size() > 0x7fffffffull) return -1;
+  std::vector<PairDesc> pairs = pairsIn;
+  std::vector<long long> haloBase(n);
+  for (long long p = 0; p < n; ++p) { pairs[p].launch0 = 0; pairs[p].cellBase = wait[p].x * slotCells; haloBase[p] = wait[p].x * slotHalo; }
+  double *d_halo = d_pool + nSlots * slotCells;
+  PairDesc *d_pairs = nullptr; int2 *d_tk = nullptr, *d_wait = nullptr; long long *d_hb = nullptr; unsigned *d_sync = nullptr;
+  int rc = 0;
+  unsigned err = 0;
+  do {
+    if (!hip_ok(sm_alloc((void **)&d_pairs, n * sizeof(PairDesc)), "hipMalloc(pairs)") || !hip_ok(sm_alloc((void **)&d_tk, tickets.size() * sizeof(int2)), "hipMalloc(tickets)") ||
+        !hip_ok(sm_alloc((void **)&d_wait, n * sizeof(int2)), "hipMalloc(slot waits)") || !hip_ok(sm_alloc((void **)&d_hb, n * sizeof(long long)), "hipMalloc(halo bases)") ||
+        !hip_ok(sm_alloc((void **)&d_sync, (2 + nSlots) * sizeof(unsigned)), "hipMalloc(strip counters)")) { rc = 1; break; }
+    if (h2d_large(d_pairs, pairs.data(), n * sizeof(PairDesc)) || h2d_large(d_tk, tickets.data(), tickets.size() * sizeof(int2)) ||
+        h2d_large(d_wait, wait.data(), n * sizeof(int2)) || h2d_large(d_hb, haloBase.data(), n * sizeof(long long))) { rc = 1; break; }
+    if (!hip_ok(hipMemsetAsync(d_sync, 0, (2 + nSlots) * sizeof(unsigned), st), "memset(strip counters)") ||
+        !hip_ok(hipMemsetAsync(d_halo, 0xFF, (size_t)(nSlots * slotHalo) * sizeof(double), st), "memset(halo sentinel)")) { rc = 1; break; }
+    MedProgDev dev = P.dev;
+    dev.ldsImageRecs = (int)P.ldsImageIdx.size();
+    MedTileArgs A{};
+    A.pairs = d_pairs; A.inTok = d_in; A.outTok = d_out; A.pool = d_pool; A.colHalo = d_halo; A.haloBase = d_hb;
+    A.loglike = d_loglike; A.tiles = d_tk; A.C = C; A.TS = maxOut + C + 1; A.rev = P.backward ? 1 : 0; A.materialise = 1; A.det = g_deterministic ? 1 : 0;
+    A.psync = d_sync; A.pwait = d_wait; A.ntickets = (int)tickets.size();
+    A.ptimeout = (long long)std::max(1, env_int_m("MB_MEDIUM_PERSIST_TIMEOUT_S", 20)) * 100000000ll;
+    if (const int us = env_int_m("MB_MEDIUM_PERSIST_TIMEOUT_US", 0)) A.ptimeout = (long long)std::max(us, 1) * 100ll;      // (the tests' way to a time-out)
+    // one workgroup per strip; a workgroup takes its ticket when it starts (whatever its blockIdx), so it waits only for started ones
+    const long long grid = (long long)tickets.size();
+    ++g_last_launches;
+    if (!launch_jit(J, dim3((unsigned)grid), dim3(geo.waves * 64), st, dev, A)) { set_error("persistent strips: launch of the run-time specialised kernel failed"); rc = 1; break; }
+    if (!hip_ok(hipGetLastError(), "persistent strips launch") || !hip_ok(hipMemcpyAsync(&err, d_sync + 1, sizeof(err), hipMemcpyDeviceToHost, st), "strip status") ||
+        !hip_ok(hipStreamSynchronize(st), "persistent strips kernel")) { rc = 1; break; }
+    if (err) rc = 2;
+  } while (0);
+  (void)hipStreamSynchronize(st);      // (buffers are freed only once nothing uses them, on every path)
+  sm_free(d_pairs); sm_free(d_tk); sm_free(d_wait); sm_free(d_hb); sm_free(d_sync);
+  return rc;
+}
+
 // Materialised Forward over a whole batch when only the log-likelihoods are kept (ForwardMatrix(...).logLike()):
 // a continuous pipeline.  Pair p starts at launch launch0[p]; a new pair is admitted as soon as the wavefront has
 // room for its strips (target: one resident workgroup per CU) and a matrix slot is free, so the chip stays full
 // across pair boundaries instead of draining at every sub-batch.  Matrix slots are recycled in stream order.
 int medium_forward_pipelined(const mb_machine *m, MedProgram &P, const MedGeom &geoIn, const std::vector<PairDesc> &pairsIn,
                              const int *d_in, const int *d_out, double *d_pool, long long poolCells, double *d_loglike,
-                             hipStream_t st) {
+                             hipStream_t st, bool persist) {
   const long long n = (long long)pairsIn.size();
   if (n == 0) return 0;
   const MedGeom geo = medium_pick_geometry(P, geoIn, pairsIn, true);
@@ -1425,6 +1499,10 @@ int medium_forward_pipelined(const mb_machine *m, MedProgram &P, const MedGeom &
   const size_t ldsPerWg = std::max<size_t>(medium_jit_lds_bytes(P, geo), 1024);
   const int wgPerCU = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((160 * 1024) / ldsPerWg, 32 / std::max(geo.waves, 1)), 8));
   const int target = 256 * wgPerCU;
+  if (persist && env_int_m("MB_MEDIUM_PERSIST", -1) != 0) {
+    const int rc = forward_persistent(m, P, geo, pairsIn, slotCells, d_in, d_out, d_pool, poolCells, d_loglike, st);
+    if (rc != -1) return rc;
+  }
   std::vector<PairDesc> pairs = pairsIn;
   std::vector<int> life(n), NAp(n), NBp(n);
   for (long long p = 0; p < n; ++p) {

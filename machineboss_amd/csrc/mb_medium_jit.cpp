@@ -76,6 +76,125 @@ static size_t lds_payload_bytes(const MedProgram &P, const MedGeom &geo, int mod
   return (ring_bytes(P, geo) + P.ldsImageIdx.size() * sizeof(MedRec) + tok_bytes(P, geo) + count_bytes(P, geo) + halo_bytes(P, geo) + tb_bytes(P, geo, mode) + 15) & ~(size_t)15;
 }
 size_t medium_jit_lds_bytes(const MedProgram &P, const MedGeom &geo, int mode) { return lds_payload_bytes(P, geo, mode) + 128; }
+// persistent strips (MED_MAT_PERSIST): halo rows of the strip to the left staged ahead, JPAHEAD + 1 rows of JNHP states behind the rest
+static int persist_ahead() { return std::max(1, std::min(env_int("MB_MEDIUM_PERSIST_AHEAD", 16), 256)); }
+static size_t persist_stage_bytes(const MedProgram &P) { return (size_t)(persist_ahead() + 1) * std::max<size_t>(P.haloStates.size(), 1) * sizeof(double); }
+
+// PERSISTENT STRIPS: the matrix kernel (JMAT 1) with the text below at the skeleton's /*@P...@*/ markers (empty for every other kind, whose
+// source stays byte for byte what it was).  A workgroup takes a ticket when it starts -- strips in (pair, strip) order -- and sweeps that
+// strip whole (one tile of A.TS > outLen + C steps, block 0).  It waits for LOWER tickets only -- the strip to its left, the pairs that
+// held its matrix slot before -- whose holders have started and are resident, so nothing depends on the order in which the dispatcher
+// starts workgroups or on how many fit the device at once.  (A loop over tickets in a grid of resident workgroups was measured to cost
+// the psw2dna kernel 60 VGPRs and 16 spilled ones: what the compiler hoists out of it; a new workgroup per strip costs a dispatch.)  The
+// halo states of column C - 1 go to a halo column per strip ([outLen + 1][JNHP], the pair's matrix slot) with agent-scope stores; the
+// strip to the right reads row t + 1 + JPAHEAD at step t with an agent-scope load, repeats while it reads as the sentinel (all ones: a
+// NaN no cell holds), puts the sentinel back and keeps the row in LDS until step t + JPAHEAD moves it into column 0 of the ring.  Nothing
+// reads the matrix back.  Every wait is bounded (A.ptimeout); one that runs out sets the error word and the whole grid drains.
+static const char *kPersistDefs = R"MBP(#define JPERS 1
+#define HALO_EMPTY (~0ull)
+__device__ __forceinline__ unsigned long long jp_ld(const double *p) { return __hip_atomic_load((const unsigned long long *)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void jp_st(double *p, unsigned long long b) { __hip_atomic_store((unsigned long long *)p, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ bool jp_failed(unsigned *err) { return __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u; }
+__device__ __forceinline__ void jp_fail(unsigned *err) { __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// the value at p, once it no longer reads as the sentinel (b: what a load issued earlier returned)
+__device__ __forceinline__ double jp_wait(const double *p, unsigned long long b, unsigned *err, long long timeoutTicks) {
+  if (b != HALO_EMPTY) return __longlong_as_double((long long)b);
+  const long long t0 = (long long)wall_clock64();
+  for (;;) {
+    b = jp_ld(p);
+    if (b != HALO_EMPTY) return __longlong_as_double((long long)b);
+    if (jp_failed(err)) return -__builtin_inf();
+    if ((long long)wall_clock64() - t0 > timeoutTicks) { jp_fail(err); return -__builtin_inf(); }
+    __builtin_amdgcn_s_sleep(1);
+  }
+}
+)MBP";
+static const char *kPersistArgs = R"MBP(  unsigned *psync;              // JPERS: [0] ticket counter, [1] error word, [2 + slot] strips finished in matrix slot `slot`
+  const int2 *pwait;            // JPERS: per pair (matrix slot, strips of that slot that finish before the pair starts)
+  long long ptimeout;           // JPERS: bound of every wait (wall-clock ticks, 100 MHz)
+  int ntickets, ppad;
+)MBP";
+static const char *kPersistOpen = R"MBP(  int *jpWord = (int *)((char *)lds + JFLAGOFF);      // JPERS: the ticket of this workgroup, taken when it starts
+  if (tid == 0) {
+    int tk = (int)__hip_atomic_fetch_add(A.psync, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tk < A.ntickets) {      // every strip of the pairs that held this matrix slot before has finished
+      const int2 w = A.pwait[A.tiles[tk].x];
+      const long long t0w = (long long)wall_clock64();
+      while (__hip_atomic_load(A.psync + 2 + w.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)w.y) {
+        if (jp_failed(A.psync + 1)) break;
+        if ((long long)wall_clock64() - t0w > A.ptimeout) { jp_fail(A.psync + 1); break; }
+        __builtin_amdgcn_s_sleep(2);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    }
+    if (jp_failed(A.psync + 1)) tk = A.ntickets;      // a wait ran out somewhere: drain
+    jpWord[0] = tk;
+  }
+  __syncthreads();
+  const int jpTicket = jpWord[0];
+  if (jpTicket >= A.ntickets) return;
+)MBP";
+static const char *kPersistTile = R"MBP(  { const int2 tl = A.tiles[jpTicket]; pairIdx = tl.x; a = tl.y; }      // JPERS: the ticket's (pair, strip), swept whole: block 0
+)MBP";
+static const char *kPersistPro = R"MBP(  // JPERS: halo columns of this pair's matrix slot -- the one the strip to the left writes, this strip's own -- and the staged rows
+  const long long jpHsz = (long long)(outLen + 1) * JNHP;
+  double *jpIn = A.colHalo + A.haloBase[pairIdx] + (long long)max(a - 1, 0) * jpHsz;
+  double *jpOut = A.colHalo + A.haloBase[pairIdx] + (long long)a * jpHsz;
+  double *jpStage = (double *)((char *)lds + JPSTAGEOFF);      // row o at (o % (JPAHEAD + 1)) * JNHP
+  int jpHS[JNHR], jpOS[JPOUTR];      // ring offsets of the halo states this thread moves in / this lane stores out
+#pragma unroll
+  for (int k = 0; k < JNHR; ++k) jpHS[k] = JHSTATE(min(tid + k * NT, JNHP - 1));
+#pragma unroll
+  for (int k = 0; k < JPOUTR; ++k) jpOS[k] = JHSTATE(min(q + k * LPG, JNHP - 1));
+  if (i0 > 0) {
+    for (int r = 0; r <= min(JPAHEAD, outLen); ++r) {
+#pragma unroll
+      for (int k = 0; k < JNHR; ++k) {
+        if (tid + k * NT < JNH) {
+          double *hp = jpIn + (long long)r * JNHP + tid + k * NT;
+          const double v = jp_wait(hp, jp_ld(hp), A.psync + 1, A.ptimeout);
+          jp_st(hp, HALO_EMPTY);
+          jpStage[r * JNHP + tid + k * NT] = v;
+          if (r == 0) ring(NS - 1, 0)[jpHS[k]] = v;      // column 0 at step -1: output position 0
+        }
+      }
+    }
+  }
+)MBP";
+static const char *kPersistLoad = R"MBP(#elif JPERS
+    unsigned long long jpv[JNHR];      // JPERS: row t + 1 + JPAHEAD of the left halo column (unconditional, clamped: as the halo supercell above)
+#pragma unroll
+    for (int k = 0; k < JNHR; ++k) jpv[k] = jp_ld(jpIn + (long long)min(t + 1 + JPAHEAD, outLen) * JNHP + min(tid + k * NT, JNHP - 1));
+)MBP";
+static const char *kPersistHalo = R"MBP(#elif JPERS
+    if (i0 > 0) {      // JPERS: row t + 1 + JPAHEAD into the stage (waiting while it reads as the sentinel), row t + 1 into column 0
+      const int jr = t + 1 + JPAHEAD;
+#pragma unroll
+      for (int k = 0; k < JNHR; ++k) {
+        const int idx = tid + k * NT;
+        if (idx < JNH) {
+          if (jr <= outLen) {
+            double *hp = jpIn + (long long)jr * JNHP + idx;
+            const double v = jp_wait(hp, jpv[k], A.psync + 1, A.ptimeout);
+            jp_st(hp, HALO_EMPTY);
+            jpStage[(jr % (JPAHEAD + 1)) * JNHP + idx] = v;
+          }
+          if (wantHalo) ring(slotCur, 0)[jpHS[k]] = jpStage[((t + 1) % (JPAHEAD + 1)) * JNHP + idx];
+        }
+      }
+    }
+)MBP";
+static const char *kPersistStore = R"MBP(      if (c == C - 1 && a + 1 < NA) {      // JPERS: this row's halo states, for the strip to the right
+#pragma unroll
+        for (int k = 0; k < JPOUTR; ++k)
+          if (q + k * LPG < JNH) jp_st(jpOut + (long long)o * JNHP + q + k * LPG, (unsigned long long)__double_as_longlong(cur[jpOS[k]]));
+      }
+)MBP";
+static const char *kPersistClose = R"MBP(  // JPERS: the strip's cells and halo rows are written (and the halo rows it read hold the sentinel again) before its slot's count says so
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  __syncthreads();
+  if (tid == 0) (void)__hip_atomic_fetch_add(A.psync + 2 + A.pwait[pairIdx].x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+)MBP";
 
 // Traceback bytes: code = table << 6 | index of the candidate in its table's list, so a state may have at most 64
 // candidates per table (any machine with a larger fan-in keeps the fp64 Viterbi matrix); a silent self-loop on state 0 --
@@ -171,13 +290,13 @@ std::string medium_jit_source(const mb_machine *m, const MedProgram &P, const Me
   std::ostringstream defs, pre, body, post, flat;
   const int S = m->S;
   const bool counting = mode == MED_MODE_COUNT && !P.flatCount, tbmode = mode == MED_MODE_TB, maxmode = mode == MB_VITERBI || tbmode;
-  const bool materialise = matKind == MED_MAT_FULL;
+  const bool materialise = matKind == MED_MAT_FULL, persist = matKind == MED_MAT_PERSIST;
   const int threads = geo.waves * 64;
   defs << "#define JS " << S << "\n#define JSPAD " << P.Spad << "\n#define JNS " << P.NS << "\n#define JG " << P.G
        << "\n#define JC " << geo.C << "\n#define JWAVES " << geo.waves << "\n#define JMODE " << (maxmode ? 1 : (mode == MED_MODE_COUNT ? 2 : 0))
        << "\n#define JSTORE2 " << env_int("MB_JIT_STORE2", (S % 2 == 0 && P.LPG <= 8) ? 1 : 0)
        << "\n#define JSTORENT " << env_int("MB_JIT_STORENT", 0)
-       << "\n#define JENV " << (geo.env ? 1 : 0) << "\n#define JMAT " << matKind << "\n#define JTB " << (tbmode ? 1 : 0) << "\n#define JTBS " << tb_lds_stride(P) << "\n#define JSB " << medium_tb_stride(S)
+       << "\n#define JENV " << (geo.env ? 1 : 0) << "\n#define JMAT " << (persist ? 1 : matKind) << "\n#define JTB " << (tbmode ? 1 : 0) << "\n#define JTBS " << tb_lds_stride(P) << "\n#define JSB " << medium_tb_stride(S)
        << "\n#define JNH " << P.haloStates.size() << "\n#define JNHP " << std::max<size_t>(P.haloStates.size(), 1)
        << "\n#define JNHR " << std::max<size_t>((P.haloStates.size() + threads - 1) / threads, 1) << "\n#define JHALOT " << (materialise ? geo.haloSteps : 0)
        // NEIGHBOUR SYNCHRONISATION instead of a workgroup barrier per step (tiles without a matrix whose halo rows one wavefront moves):
@@ -195,6 +314,9 @@ std::string medium_jit_source(const mb_machine *m, const MedProgram &P, const Me
        << "\n#define JLDSRECS " << (long long)P.ldsImageIdx.size() << "\n#define JTOKW " << P.tokWindow
        << "\n#define JTOKN " << (P.tokWindow + geo.C - 1 + threads - 1) / threads
        << "\n#define JDUMMYOFF " << P.dummyOff << "\n#define JHALO " << (S + threads - 1) / threads << "\n";
+  if (persist)
+    defs << kPersistDefs << "#define JPAHEAD " << persist_ahead() << "\n#define JPSTAGEOFF " << lds_payload_bytes(P, geo, mode) + 128
+         << "\n#define JPOUTR " << (std::max<size_t>(P.haloStates.size(), 1) + P.LPG - 1) / P.LPG << "\n";
   defs << "__device__ const int jHaloState[] = {";   // states whose values cross a strip boundary (halo rows of JMAT == 2)
   for (size_t k = 0; k < std::max<size_t>(P.haloStates.size(), 1); ++k) defs << (k ? "," : "") << (k < P.haloStates.size() ? P.haloStates[k] : 0);
   defs << "};\n#define JHSTATE(k) jHaloState[k]\n";
@@ -399,6 +521,9 @@ std::string medium_jit_source(const mb_machine *m, const MedProgram &P, const Me
   replace("/*@BODY@*/", body.str());
   replace("/*@FLAT@*/", flat.str());
   replace("/*@POST@*/", post.str());
+  const std::pair<const char *, const char *> pmarks[] = {{"/*@PARGS@*/", kPersistArgs}, {"/*@POPEN@*/", kPersistOpen}, {"/*@PNOREAD@*/", " && !JPERS"}, {"/*@PTILE@*/", kPersistTile}, {"/*@PBLOCK@*/", " && !JPERS"},
+      {"/*@PPRO@*/", kPersistPro}, {"/*@PLOAD@*/", kPersistLoad}, {"/*@PHALO@*/", kPersistHalo}, {"/*@PSTORE@*/", kPersistStore}, {"/*@PCLOSE@*/", kPersistClose}};
+  for (const auto &pm : pmarks) replace(pm.first, persist ? pm.second : "");
   return src;
 }
 
@@ -422,14 +547,14 @@ bool medium_jit_get(const mb_machine *m, MedProgram &P, const MedGeom &geoIn, in
   std::string code, src;
   bool fromCache = false;
   for (int attempt = 0; attempt < 8; ++attempt) {
-    J.ldsBytes = medium_jit_lds_bytes(P, geo, mode);
+    J.ldsBytes = medium_jit_lds_bytes(P, geo, mode) + (matKind == MED_MAT_PERSIST ? persist_stage_bytes(P) : 0);
     if (J.ldsBytes > 160 * 1024) {
       if (opt_env("MB_MEDIUM_JIT_VERBOSE")) fprintf(stderr, "[mbhip] jit (mode %d, matrix kind %d): %zu bytes of LDS at register budget %d -- ahead-of-time kernel\n", mode, matKind, (size_t)J.ldsBytes, P.regBudget);
       return false;
     }
     src = medium_jit_source(m, P, geo, mode, matKind);
     if (const char *dump = opt_env("MB_MEDIUM_JIT_DUMP")) {
-      if (FILE *f = fopen((std::string(dump) + (mode == MB_VITERBI ? ".vit" : (mode == MED_MODE_COUNT ? ".cnt" : (mode == MED_MODE_TB ? ".tb" : ".sum"))) + (materialise ? ".mat" : (matKind == MED_MAT_ROLL ? ".tiles" : ".roll")) + (P.backward ? ".bwd" : ".fwd") + (P.closure ? ".clos" : ".exact") + ".hip").c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
+      if (FILE *f = fopen((std::string(dump) + (mode == MB_VITERBI ? ".vit" : (mode == MED_MODE_COUNT ? ".cnt" : (mode == MED_MODE_TB ? ".tb" : ".sum"))) + (materialise ? ".mat" : (matKind == MED_MAT_ROLL ? ".tiles" : (matKind == MED_MAT_PERSIST ? ".pers" : ".roll"))) + (P.backward ? ".bwd" : ".fwd") + (P.closure ? ".clos" : ".exact") + ".hip").c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
     }
     std::string log;
     if (!jit_compile(src, "mb_medium_jit.hip", code, &log, &fromCache)) {

@@ -44,7 +44,7 @@ struct MedTileArgs {
   double *bound;                // JMAT == 2: tile-boundary records (ring state a block hands to the next block of its strip)
   const long long *boundBase;   //            per pair offset (doubles); strip a's record follows at a * (JNS - 1) * JC * JS
   unsigned char *tb;            // JTB: Viterbi traceback bytes, JSB per supercell, reference order; PairDesc::cellBase = byte offset
-};
+/*@PARGS@*/};
 // JMAT: 0 = one workgroup sweeps a whole strip, no matrix (halo columns in colHalo); 1 = tiles, matrix in `pool` (the ring
 // state of a tile's first steps and the halo supercells are read back from it); 2 = tiles WITHOUT a matrix: halo columns
 // (JNH states per row: the sources of input-consuming transitions) in colHalo, one column per strip, and the ring state at
@@ -208,15 +208,15 @@ extern "C" __global__ __launch_bounds__(JWAVES * 64) void k_medium_jit(MedProgDe
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int g = lane / LPG, q = lane - g * LPG;
   const int jdet = A.det; (void)jdet;
-  int pairIdx, a;
+/*@POPEN@*/  int pairIdx, a;
   bool prevDead = false;      // JMAT == 2 with envelopes: the block before this one holds no cell of the envelope and did not run
   if (JTILES) { const int2 tl = A.tiles[A.tileBase + blockIdx.x]; pairIdx = tl.x; a = tl.y & 0x3fffffff; prevDead = (tl.y >> 30) & 1; }
   else { pairIdx = blockIdx.x; a = A.launch; }
-  (void)prevDead;
+/*@PTILE@*/  (void)prevDead;
   const PairDesc pd = A.pairs[pairIdx];
   const int inLen = pd.inLen, outLen = pd.outLen;
   const long long I = inLen + 1;
-  const int b = JTILES ? A.launch - pd.launch0 - 2 * a : 0;
+  const int b = JTILES/*@PBLOCK@*/ ? A.launch - pd.launch0 - 2 * a : 0;
   const int NA = (inLen + C) / C;
   const int T = outLen + C;
   if (a >= NA || b < 0 || (long long)b * A.TS >= T) return;
@@ -371,7 +371,7 @@ extern "C" __global__ __launch_bounds__(JWAVES * 64) void k_medium_jit(MedProgDe
       const int cc = col - 1, ci = i0 + cc, co = tp - cc;
       if (ci < 0 || ci > inLen || co < 0 || co > outLen) continue;
       const double *src = nullptr;
-      if (JMAT == 1) src = cellPtr(ci, co);
+      if (JMAT == 1/*@PNOREAD@*/) src = cellPtr(ci, co);
       else if (JMAT == 0 && cc == -1) src = haloIn + (long long)co * S;
       if (src) ring(slot, col)[j] = src[j];
     }
@@ -393,7 +393,7 @@ extern "C" __global__ __launch_bounds__(JWAVES * 64) void k_medium_jit(MedProgDe
 #endif
   }
 #endif
-  __syncthreads();
+/*@PPRO@*/  __syncthreads();
 
   cdesc_t desc = (cdesc_t)P.desc;
   grec_t grec = (grec_t)P.rec;
@@ -496,7 +496,7 @@ extern "C" __global__ __launch_bounds__(JWAVES * 64) void k_medium_jit(MedProgDe
 #pragma unroll
       for (int k = 0; k < JNHR; ++k) hvc[k] = hs[JHSTATE(min(tid + k * NT, JNHP - 1))];
     }
-#elif JHALOT == 0
+/*@PLOAD@*/#elif JHALOT == 0
     double hv[JHALO];
     {
       const int hi = i0 > 0 ? i0 - 1 : 0, ho = min(t + 1, outLen);
@@ -578,7 +578,7 @@ extern "C" __global__ __launch_bounds__(JWAVES * 64) void k_medium_jit(MedProgDe
 #pragma unroll
       for (int k = 0; k < JNHR; ++k) if (tid + k * NT < JNH) hd[tid + k * NT] = hvc[k];
     }
-#else
+/*@PHALO@*/#else
     if (wantHalo) {
       double *hd = ring(slotCur, 0);
 #pragma unroll
@@ -599,7 +599,7 @@ extern "C" __global__ __launch_bounds__(JWAVES * 64) void k_medium_jit(MedProgDe
         double *dstp = cellPtr(i, o);
         med_copy_out(dstp, cur, q);
       }
-#elif JMAT == 0
+/*@PSTORE@*/#elif JMAT == 0
       if (c == C - 1) med_copy_out(haloOut + (long long)o * S, cur, q);
 #else
       if (c == C - 1 && a + 1 < NA)
@@ -677,6 +677,6 @@ extern "C" __global__ __launch_bounds__(JWAVES * 64) void k_medium_jit(MedProgDe
     if (x != 0.0) (void)__hip_atomic_fetch_add(A.counts + tr, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 #endif
-}
+/*@PCLOSE@*/}
 )MBJIT";
 }  // namespace mb
