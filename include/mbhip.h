@@ -141,6 +141,27 @@ int mb_fill(mb_machine *m, int mode, const int32_t *in, int64_t inLen, const int
 int mb_fill_env(mb_machine *m, int mode, const int32_t *in, int64_t inLen, const int32_t *out, int64_t outLen,
                 int32_t startState, const int32_t *envStart, const int32_t *envEnd, double *cellsOut);
 
+/* ---- profile tapes: a machine with an empty input tape against soft output sequences -------------------------------------
+ * `--recognize-csv` (target/boss.cpp:606-611, src/csv.cpp:8-18): the semantics of compose(M, transpose(CSVProfile::machine()))
+ * scored with empty tapes (src/machine.cpp:794-850, 1053-1085), swept natively over the (rows + 1) x 2 x nStates lattice
+ * (docs/profile_tapes.md).  Profile k = rows rowOff[k]..rowOff[k+1); row r = logP[r*(nOutTok+1) ...], column 0 = the blank (the
+ * row is consumed, the machine does not move), column t = the log weight of output token t; -inf allowed, NaN / +inf rejected.
+ * Transitions that read input never fire.  Viterbi keeps the first maximum: the blank first, then emitting edges in `incoming`
+ * order; after the silent moves, "no move" first, then silent edges in `incoming` order.  Paths are the machine's global edge
+ * ids, start -> end, with the row at which each edge fired (pathRow may be NULL); a profile whose score is -inf gets an empty
+ * path.  Counts follow mb_batch_counts (a -inf profile adds nothing) and are the same bits from call to call in either mode of
+ * MB_DETERMINISTIC.  Materialised lattices: cells[((row*2) + layer)*nStates + state], layer 0 = arrived at the row, layer 1 =
+ * after the silent moves; mb_profile_fill: cellsOut[(nRows+1)*2*nStates], mode MB_FORWARD / MB_VITERBI / MB_BACKWARD. */
+typedef struct mb_profiles mb_profiles;
+mb_profiles *mb_profiles_create(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff);
+void mb_profiles_destroy(mb_profiles *p);
+int mb_profiles_forward(mb_profiles *p, int flags /* MB_ROLLING | MB_MATERIALISE */, double *loglike);
+int64_t mb_profile_path_bound(const mb_machine *m, int64_t nRows);
+int mb_profiles_viterbi(mb_profiles *p, double *loglike, int64_t *pathOff, uint32_t *pathEdges,
+                        int32_t *pathRow /* row at which each edge fired */, int64_t pathCap);
+int mb_profiles_counts(mb_profiles *p, double *counts, double *loglikeSum, double *loglike);
+int mb_profile_fill(mb_machine *m, int mode, const double *logP, int64_t nRows, double *cellsOut);
+
 /* ---- convenience wrappers over host buffers (create batch, run, destroy) ----------------------------------
  * forwardLogLike / viterbiLogLike+viterbiAlign / forwardBackwardCounts of src/api.h:20-34.                   */
 int mb_forward_batch(mb_machine *m, int64_t nPairs, const int32_t *inTok, const int64_t *inOff,

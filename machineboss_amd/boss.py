@@ -3,6 +3,7 @@
     python -m machineboss_amd.boss MACHINE.json [--preset NAME] [-P params.json] [-F funcs.json] [-N constraints.json]
            [-D seqpairs.json] [--input-chars S] [--output-chars S] [--input-fasta F] [--output-fasta F]
            [--input-json F] [--output-json F] [--use-defaults] [-L] [-V] [-A] [-C] [-T] [-R width]
+           [--generate-json F] [--recognize-csv F]
 
 Restates the data-handling and inference section of /root/reference/target/boss.cpp:716-847 -- how sequences are
 collected into pairs, how parameters are assembled, and the exact output text of --loglike / --viterbi / --align /
@@ -10,6 +11,10 @@ collected into pairs, how parameters are assembled, and the exact output text of
 machine-expression language of its command line is reduced to what assembles the benchmark machines: several
 transducer files / presets on one command line are COMPOSED (algebra.py = Machine::compose); the other operators
 (concatenate, union, Kleene closures, ...) are not here.
+
+``--recognize-csv FILE`` puts a profile (a soft output sequence, src/csv.cpp) behind the machines.  The reference composes
+it as an (L+1)-state recogniser; here the composed left part, which must have an empty input alphabet, is scored natively
+against the profile (profile.py, mb_profile.hip) with -L, -V or -C, and prints what the reference prints.
 
 Numbers print like C++ `ostream << double` (6 significant digits, target/boss.cpp:794-807 via src/jsonio.h:14-22),
 parameters with 15 (src/weight.cpp:483).  Work is batched: all pairs go through one device call per mode; with
@@ -124,6 +129,8 @@ def buildParser() -> argparse.ArgumentParser:
     ap.add_argument("--hmmer-multihit", help="Plan7 generator with the J loop")
     ap.add_argument("--generate-chars", help="compose a generator of this sequence in front of the machine(s)")
     ap.add_argument("--recognize-chars", help="compose a recogniser of this sequence behind the machine(s)")
+    ap.add_argument("--generate-json", help="compose a generator of the sequence in this JSON file ({name, sequence}) in front of the machine(s)")
+    ap.add_argument("--recognize-csv", help="score the machine(s) against this CSV profile (rightmost; with -L, -V or -C)")
     ap.add_argument("-P", "--params", action="append", default=[])
     ap.add_argument("-F", "--functions", action="append", default=[])
     ap.add_argument("-N", "--constraints", action="append", default=[])
@@ -161,6 +168,9 @@ def loadMachine(args) -> Machine:
             machines.insert(0, build(HmmerModel.fromFile(path)))
     if args.generate_chars is not None:       # leftmost: a generator of the sequence (target/boss.cpp:362-364)
         machines.insert(0, generator(list(args.generate_chars), args.generate_chars))
+    if args.generate_json is not None:        # leftmost, like --generate-chars (target/boss.cpp:355-357)
+        j = json.load(open(args.generate_json))
+        machines.insert(0, generator(list(j["sequence"]), j.get("name", "")))
     if args.recognize_chars is not None:      # rightmost: a recogniser of the sequence (target/boss.cpp:384-386)
         machines.append(recognizer(list(args.recognize_chars), args.recognize_chars))
     if not machines:
@@ -248,9 +258,55 @@ def _gather_in_order(local: List[Any], n: int, rank: int, world: int, owned: Opt
     return out
 
 
+def runProfile(args, out) -> int:
+    """--recognize-csv: the machines left of the profile, composed, against the profile tape (-L / -V / -C)."""
+    from . import capi, dp
+    from .profile import Profile
+    if args.align or args.train:
+        raise MachineError("--recognize-csv supports -L, -V and -C")
+    if not (args.loglike or args.viterbi or args.counts):
+        raise MachineError("--recognize-csv needs -L, -V or -C")
+    if args.recognize_chars is not None or args.data or args.input_chars is not None or args.output_chars is not None or \
+            args.input_fasta or args.output_fasta or args.input_json or args.output_json:
+        raise MachineError("--recognize-csv takes no other sequence data")
+    if _dist() is not None and _dist().get_world_size() > 1:
+        raise MachineError("--recognize-csv runs on one rank")
+    machine = loadMachine(args)
+    if machine.inputAlphabet():
+        raise MachineError("--recognize-csv needs a machine with an empty input alphabet (compose a generator in front); input alphabet: %s"
+                           % ",".join(machine.inputAlphabet()))
+    if not os.path.exists(args.recognize_csv):
+        raise MachineError("CSV file not found")
+    profile = Profile.fromCsv(args.recognize_csv)
+    params: Dict[str, Any] = {}
+    for f in args.functions:
+        params.update(json.load(open(f)))
+    for f in args.params:
+        params.update(json.load(open(f)))
+    for k, v in machine.getParamDefs(args.use_defaults).items():
+        params.setdefault(k, v)
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    dm = capi.DeviceMachine(ev)
+    prof = capi.DeviceProfiles(dm, [profile.logRows(ev)])
+    if args.loglike:
+        out.write('[["","",%s]]\n' % fmt(prof.forward(capi.MB_ROLLING)[0]))
+    if args.counts:
+        counts = dp.MachineCounts(ev)
+        _, s, _ = prof.counts(counts._flat)
+        counts.loglike += s
+        pc = counts.paramCounts(machine, params)
+        out.write("{" + ",".join('"%s":%s' % (escaped(k), "%g" % pc[k]) for k in sorted(pc)) + "}\n")
+    if args.viterbi:
+        out.write('[["","",%s]]\n' % fmt(prof.viterbi(paths=False)[0][0]))
+    prof.close(); dm.close()
+    return 0
+
+
 def run(argv: Optional[List[str]] = None, out=None) -> int:
     out = out or sys.stdout
     args = buildParser().parse_args(argv)
+    if args.recognize_csv is not None:
+        return runProfile(args, out)
     machine = loadMachine(args)
     inference = args.loglike or args.viterbi or args.align or args.counts or args.train
     data = collectData(args, machine, inference)

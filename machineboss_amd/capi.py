@@ -28,6 +28,8 @@ EXPORTS = [
     "mb_jit_stats", "mb_alloc_stats", "mb_machine_sweep_ops", "mb_set_option", "mb_get_option", "mb_log_sum_exp", "mb_log_sum_exp_n", "mb_log_inner_product",
     "mb_batch_set_envelopes", "mb_fill_env",
     "mb_comm_unique_id", "mb_comm_init", "mb_comm_destroy", "mb_allreduce_counts",
+    "mb_profiles_create", "mb_profiles_destroy", "mb_profiles_forward", "mb_profile_path_bound", "mb_profiles_viterbi",
+    "mb_profiles_counts", "mb_profile_fill",
 ]
 
 _lib = None
@@ -100,6 +102,14 @@ def load():
     L.mb_comm_init.argtypes = [C.c_char_p, C.c_int, C.c_int]; L.mb_comm_init.restype = vp
     L.mb_comm_destroy.argtypes = [vp]; L.mb_comm_destroy.restype = None
     L.mb_allreduce_counts.argtypes = [vp, dp, C.c_size_t, dp]
+    L.mb_profiles_create.restype = vp
+    L.mb_profiles_create.argtypes = [vp, C.c_int64, dp, i64p]
+    L.mb_profiles_destroy.argtypes = [vp]; L.mb_profiles_destroy.restype = None
+    L.mb_profiles_forward.argtypes = [vp, C.c_int, dp]
+    L.mb_profile_path_bound.argtypes = [vp, C.c_int64]; L.mb_profile_path_bound.restype = C.c_int64
+    L.mb_profiles_viterbi.argtypes = [vp, dp, i64p, u32p, i32p, C.c_int64]
+    L.mb_profiles_counts.argtypes = [vp, dp, dp, dp]
+    L.mb_profile_fill.argtypes = [vp, C.c_int, dp, C.c_int64, dp]
     _lib = L
     return L
 
@@ -513,3 +523,67 @@ class DeviceBatch:
         ll = np.empty(self.nPairs, np.float64)
         _check(load().mb_batch_counts(self.h, _p(counts, C.c_double), C.byref(s), _p(ll, C.c_double)))
         return counts, s.value, ll
+
+
+class DeviceProfiles:
+    """Device-resident batch of profile tapes (mb_profiles*) for a machine with an empty input tape: per profile a
+    [rows, nOutTok + 1] array of log weights, column 0 = the blank (profile.Profile.logRows)."""
+
+    def __init__(self, dm: DeviceMachine, profiles):
+        self.dm = dm
+        rows = [np.asarray(p, np.float64).reshape(-1, dm.em.nOutTok + 1) for p in profiles]
+        self.nProfiles = len(rows)
+        self.rowOff = np.zeros(self.nProfiles + 1, np.int64)
+        for k, r in enumerate(rows):
+            self.rowOff[k + 1] = self.rowOff[k] + len(r)
+        self.logP = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((1, dm.em.nOutTok + 1)), np.float64)
+        L = load()
+        self.h = L.mb_profiles_create(dm.h, self.nProfiles, _p(self.logP, C.c_double), _p(self.rowOff, C.c_int64))
+        if not self.h:
+            raise MbError(L.mb_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            try:
+                _lib.mb_profiles_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    __del__ = close
+
+    def forward(self, flags: int = MB_ROLLING) -> np.ndarray:
+        ll = np.empty(self.nProfiles, np.float64)
+        _check(load().mb_profiles_forward(self.h, flags, _p(ll, C.c_double)))
+        return ll
+
+    def viterbi(self, paths: bool = True):
+        """Returns (loglike, pathOff, pathEdges, pathRow); the last three are None without paths."""
+        ll = np.empty(self.nProfiles, np.float64)
+        if not paths:
+            _check(load().mb_profiles_viterbi(self.h, _p(ll, C.c_double), None, None, None, 0))
+            return ll, None, None, None
+        L = load()
+        cap = int(sum(L.mb_profile_path_bound(self.dm.h, int(n)) for n in np.diff(self.rowOff)))
+        off = np.zeros(self.nProfiles + 1, np.int64)
+        edges = np.empty(max(cap, 1), np.uint32); rows = np.empty(max(cap, 1), np.int32)
+        _check(L.mb_profiles_viterbi(self.h, _p(ll, C.c_double), _p(off, C.c_int64), _p(edges, C.c_uint32), _p(rows, C.c_int32), cap))
+        return ll, off, edges[:off[-1]].copy(), rows[:off[-1]].copy()
+
+    def counts(self, counts: Optional[np.ndarray] = None):
+        """Returns (counts[nTrans], loglikeSum, loglike[nProfiles]); accumulates into ``counts`` if given."""
+        if counts is None:
+            counts = np.zeros(self.dm.nTrans, np.float64)
+        assert counts.dtype == np.float64 and counts.shape == (self.dm.nTrans,) and counts.flags.c_contiguous
+        s = C.c_double(0.0)
+        ll = np.empty(self.nProfiles, np.float64)
+        _check(load().mb_profiles_counts(self.h, _p(counts, C.c_double), C.byref(s), _p(ll, C.c_double)))
+        return counts, s.value, ll
+
+
+def profile_fill(dm: DeviceMachine, mode: int, logP) -> np.ndarray:
+    """One profile's lattice [rows + 1, 2, nStates] (layer 0 = arrived at the row, 1 = after the silent moves)."""
+    P = np.ascontiguousarray(np.asarray(logP, np.float64).reshape(-1, dm.em.nOutTok + 1))
+    cells = np.empty((len(P) + 1, 2, dm.nStates), np.float64)
+    _check(load().mb_profile_fill(dm.h, mode, _p(P, C.c_double), len(P), _p(cells, C.c_double)))
+    return cells

@@ -15,6 +15,7 @@
 #include "mb_internal.h"
 #include "mb_jit.h"
 #include "mb_medium.h"
+#include "mb_profile.h"
 #include "mb_small.h"
 #include "mb_usage.h"
 #include "mb_wide.h"
@@ -2089,6 +2090,292 @@ int mb_counts_batch(mb_machine *m, int64_t nPairs, const int32_t *inTok, const i
   if (!b) return 1;
   const int rc = mb_batch_counts(b, counts, loglikeSum, loglike);
   mb_batch_destroy(b);
+  return rc;
+}
+
+}  // extern "C"
+
+// ---- profile tapes (mb_profile.hip, docs/profile_tapes.md) ------------------------------------------------------------------
+namespace mb {
+
+static bool profile_values_ok(const double *v, long long n) {
+  for (long long k = 0; k < n; ++k)
+    if (std::isnan(v[k]) || v[k] == INFINITY) { set_error("profile weight " + std::to_string(k) + " is NaN or +infinity (log weights: -inf allowed)"); return false; }
+  return true;
+}
+
+// Split the profiles into chunks whose device memory (bytesPer(profile k)) fits the budget; even-sized like plan_chunks.
+static bool profile_chunks(const mb_profiles *p, const std::function<double(long long)> &bytesPer, std::vector<Chunk> &out) {
+  const double budget = (double)budget_bytes();
+  double total = 0.0;
+  for (long long k = 0; k < p->n; ++k) {
+    const double b = bytesPer(k);
+    if (b > budget) { set_error("one profile's DP lattice (" + std::to_string((long long)b) + " bytes) exceeds the device memory budget"); return false; }
+    total += b;
+  }
+  const double nChunks = std::max(1.0, std::ceil(total / budget));
+  const double share = std::min(budget, total / nChunks * 1.05);
+  long long p0 = 0;
+  double acc = 0.0;
+  for (long long k = 0; k < p->n; ++k) {
+    const double b = bytesPer(k);
+    if (k > p0 && (acc + b > budget || (acc >= share && acc + b > share) || k - p0 >= (1 << 30))) { out.push_back({p0, k, 0}); p0 = k; acc = 0.0; }
+    acc += b;
+  }
+  if (p->n > p0) out.push_back({p0, p->n, 0});
+  return true;
+}
+
+// descriptors of profiles [p0, p1): lattices and traceback slots packed from 0; returns the pool doubles and path entries
+static int profile_descs(const mb_profiles *p, long long p0, long long p1, ProfDesc **d_out, long long *cells, long long *paths) {
+  std::vector<ProfDesc> h((size_t)(p1 - p0));
+  long long c = 0, t = 0;
+  for (long long k = p0; k < p1; ++k) {
+    ProfDesc &d = h[(size_t)(k - p0)];
+    d.rowBase = p->rowOff[k]; d.nRows = (int)(p->rowOff[k + 1] - p->rowOff[k]); d.cellBase = c; d.pathBase = t; d.pad = 0;
+    c += profile_cells(p->m->S, d.nRows);
+    t += profile_path_bound(p->m->nLevF, d.nRows);
+  }
+  if (cells) *cells = c;
+  if (paths) *paths = t;
+  MB_HIP(sm_alloc((void **)d_out, std::max<size_t>(h.size(), 1) * sizeof(ProfDesc)));
+  if (!h.empty() && (!hip_ok(hipMemcpyAsync(*d_out, h.data(), h.size() * sizeof(ProfDesc), hipMemcpyHostToDevice, g_stream), "H2D profile descriptors") ||
+                     !hip_ok(hipStreamSynchronize(g_stream), "H2D profile descriptors"))) { sm_free(*d_out); *d_out = nullptr; return 1; }
+  return 0;
+}
+
+static int profile_scratch(const mb_machine *m, long long n, double **scratch) {
+  *scratch = nullptr;
+  if (profile_lds_bytes(m->S) || n == 0) return 0;
+  *scratch = (double *)ws_get(1, (size_t)n * 3 * m->S * sizeof(double));
+  return *scratch ? 0 : 1;
+}
+
+// Forward (MB_FORWARD) or Viterbi scores without paths (MB_VITERBI); mat: through the materialised lattice
+static int profiles_scores(mb_profiles *p, int mode, bool mat, double *loglike) {
+  const mb_machine *m = p->m;
+  const double rollBytes = profile_lds_bytes(m->S) ? 0.0 : 24.0 * m->S;
+  std::vector<Chunk> chunks;
+  if (!profile_chunks(p, [&](long long k) { return mat ? 8.0 * profile_cells(m->S, p->rowOff[k + 1] - p->rowOff[k]) : rollBytes; }, chunks)) return 1;
+  double *d_ll = nullptr;
+  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
+  int rc = 0;
+  Timer tm;
+  for (const Chunk &c : chunks) {
+    ProfDesc *d = nullptr;
+    long long cells = 0;
+    if ((rc = profile_descs(p, c.p0, c.p1, &d, &cells, nullptr))) break;
+    const long long np = c.p1 - c.p0;
+    double *pool = nullptr, *scratch = nullptr;
+    if (mat) { pool = (double *)ws_get(0, (size_t)std::max<long long>(cells, 1) * sizeof(double)); if (!pool) rc = 1; }
+    else rc = profile_scratch(m, np, &scratch);
+    if (!rc) {
+      tm.start();
+      rc = launch_profile_fwd(m, mode, mat, d, (int)np, p->d_logP, pool, scratch, d_ll + c.p0, g_stream);
+      g_last_ms += tm.stop();
+      ++g_last_launches;
+    }
+    if (rc) quiesce_streams();
+    sm_free(d);
+    if (rc) break;
+  }
+  if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  sm_free(d_ll);
+  g_last_kernel = mode == MB_VITERBI ? (mat ? "k_profile_fwd<max,mat>" : "k_profile_fwd<max,rolling>") : (mat ? "k_profile_fwd<sum,mat>" : "k_profile_fwd<sum,rolling>");
+  return rc;
+}
+
+}  // namespace mb
+
+extern "C" {
+
+mb_profiles *mb_profiles_create(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff) {
+  ApiGuard guard;
+  if (!m || nProfiles < 0 || (nProfiles > 0 && !rowOff)) { set_error("null argument"); return nullptr; }
+  if (ensure_init()) return nullptr;
+  mb_profiles *p = new mb_profiles();
+  p->m = m; p->n = nProfiles;
+  p->rowOff.assign((size_t)nProfiles + 1, 0);
+  for (long long k = 0; k < nProfiles; ++k) {
+    const long long len = rowOff[k + 1] - rowOff[k];
+    if (len < 0 || len > 0x3fffffff) { set_error("bad profile row offsets"); delete p; return nullptr; }
+    p->rowOff[(size_t)k + 1] = p->rowOff[(size_t)k] + len;
+  }
+  p->totalRows = p->rowOff.back();
+  const long long C = m->nOut + 1, nv = p->totalRows * C;
+  const double *v0 = logP ? logP + (nProfiles ? rowOff[0] * C : 0) : nullptr;
+  if (nv && !v0) { set_error("null argument"); delete p; return nullptr; }
+  if (!profile_values_ok(v0, nv)) { delete p; return nullptr; }
+  if (!hip_ok(hipMalloc((void **)&p->d_logP, (size_t)std::max<long long>(nv, 1) * sizeof(double)), "hipMalloc(profiles)")) { delete p; return nullptr; }
+  if (nv && h2d_large(p->d_logP, v0, (size_t)nv * sizeof(double))) { mb_profiles_destroy(p); return nullptr; }
+  if (!hip_ok(hipStreamSynchronize(g_stream), "H2D profiles")) { mb_profiles_destroy(p); return nullptr; }
+  return p;
+}
+
+void mb_profiles_destroy(mb_profiles *p) {
+  ApiGuard guard;
+  if (!p) return;
+  if (p->d_logP) (void)hipFree(p->d_logP);
+  delete p;
+}
+
+int mb_profiles_forward(mb_profiles *p, int flags, double *loglike) {
+  ApiGuard guard;
+  if (!p || (!loglike && p->n)) { set_error("null argument"); return 1; }
+  if (flags != MB_ROLLING && flags != MB_MATERIALISE) { set_error("unknown flags"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  return profiles_scores(p, MB_FORWARD, flags == MB_MATERIALISE, loglike);
+}
+
+int64_t mb_profile_path_bound(const mb_machine *m, int64_t nRows) {
+  if (!m || nRows < 0) return 0;
+  return profile_path_bound(m->nLevF, nRows);
+}
+
+int mb_profiles_viterbi(mb_profiles *p, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow, int64_t pathCap) {
+  ApiGuard guard;
+  if (!p || (!loglike && p->n)) { set_error("null argument"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  if (!pathEdges || !pathOff) return profiles_scores(p, MB_VITERBI, false, loglike);
+  const mb_machine *m = p->m;
+  std::vector<Chunk> chunks;
+  auto bytes = [&](long long k) { const long long L = p->rowOff[k + 1] - p->rowOff[k]; return 8.0 * profile_cells(m->S, L) + 8.0 * profile_path_bound(m->nLevF, L); };
+  if (!profile_chunks(p, bytes, chunks)) return 1;
+  double *d_ll = nullptr;
+  long long *d_len = nullptr;
+  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
+  if (!hip_ok(sm_alloc((void **)&d_len, std::max<long long>(p->n, 1) * sizeof(long long)), "hipMalloc(path lengths)")) { sm_free(d_ll); return 1; }
+  int rc = 0;
+  Timer tm;
+  long long written = 0;
+  pathOff[0] = 0;
+  std::vector<long long> len;
+  std::vector<uint32_t> he;
+  std::vector<int32_t> hr;
+  for (const Chunk &c : chunks) {
+    ProfDesc *d = nullptr;
+    long long cells = 0, paths = 0;
+    if ((rc = profile_descs(p, c.p0, c.p1, &d, &cells, &paths))) break;
+    const long long np = c.p1 - c.p0;
+    double *pool = (double *)ws_get(0, (size_t)std::max<long long>(cells, 1) * sizeof(double));
+    uint32_t *d_e = (uint32_t *)ws_get(3, (size_t)std::max<long long>(paths, 1) * sizeof(uint32_t));
+    int32_t *d_r = (int32_t *)ws_get(4, (size_t)std::max<long long>(paths, 1) * sizeof(int32_t));
+    if (!pool || !d_e || !d_r) rc = 1;
+    if (!rc) {
+      tm.start();
+      rc = launch_profile_fwd(m, MB_VITERBI, true, d, (int)np, p->d_logP, pool, nullptr, d_ll + c.p0, g_stream);
+      if (!rc) rc = launch_profile_traceback(m, d, (int)np, p->d_logP, pool, d_e, d_r, d_len + c.p0, g_stream);
+      g_last_ms += tm.stop();
+      ++g_last_launches;
+    }
+    len.resize((size_t)np); he.resize((size_t)std::max<long long>(paths, 1)); hr.resize(he.size());
+    if (!rc && !hip_ok(hipMemcpy(len.data(), d_len + c.p0, np * sizeof(long long), hipMemcpyDeviceToHost), "D2H path lengths")) rc = 1;
+    if (!rc && paths && (d2h_large(he.data(), d_e, paths * sizeof(uint32_t)) || (pathRow && d2h_large(hr.data(), d_r, paths * sizeof(int32_t))))) rc = 1;
+    long long base = 0;
+    for (long long k = 0; k < np && !rc; ++k) {
+      const long long L = p->rowOff[c.p0 + k + 1] - p->rowOff[c.p0 + k];
+      long long n = len[(size_t)k];
+      if (n == -1) n = 0;   // no finite path: an empty one (the reference refuses to trace it)
+      else if (n < 0) { set_error(n == -2 ? "profile traceback overflowed its bound" : "profile traceback found no matching candidate"); rc = 1; break; }
+      if (written + n > pathCap) { set_error("pathCap too small for the Viterbi paths"); rc = 1; break; }
+      std::memcpy(pathEdges + written, he.data() + base, (size_t)n * sizeof(uint32_t));
+      if (pathRow) std::memcpy(pathRow + written, hr.data() + base, (size_t)n * sizeof(int32_t));
+      written += n;
+      pathOff[c.p0 + k + 1] = written;
+      base += profile_path_bound(m->nLevF, L);
+    }
+    if (rc) quiesce_streams();
+    sm_free(d);
+    if (rc) break;
+  }
+  if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  sm_free(d_ll); sm_free(d_len);
+  g_last_kernel = "k_profile_fwd<max,mat>";
+  return rc;
+}
+
+int mb_profiles_counts(mb_profiles *p, double *counts, double *loglikeSum, double *loglike) {
+  ApiGuard guard;
+  if (!p || !counts) { set_error("null argument"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  const mb_machine *m = p->m;
+  const long long nT = m->nTrans;
+  const double rollBytes = profile_lds_bytes(m->S) ? 0.0 : 24.0 * m->S;
+  std::vector<Chunk> chunks;
+  auto bytes = [&](long long k) { return 8.0 * profile_cells(m->S, p->rowOff[k + 1] - p->rowOff[k]) + 8.0 * nT + rollBytes; };
+  if (!profile_chunks(p, bytes, chunks)) return 1;
+  double *d_ll = nullptr, *d_bll = nullptr, *d_cc = nullptr;
+  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
+  if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
+      !hip_ok(sm_alloc((void **)&d_cc, std::max<long long>(nT, 1) * sizeof(double)), "hipMalloc(counts)")) { sm_free(d_ll); sm_free(d_bll); sm_free(d_cc); return 1; }
+  int rc = 0;
+  Timer tm;
+  std::vector<double> total((size_t)nT, 0.0), hc((size_t)nT);
+  for (const Chunk &c : chunks) {
+    ProfDesc *d = nullptr;
+    long long cells = 0;
+    if ((rc = profile_descs(p, c.p0, c.p1, &d, &cells, nullptr))) break;
+    const long long np = c.p1 - c.p0;
+    double *pool = (double *)ws_get(0, (size_t)std::max<long long>(cells, 1) * sizeof(double));
+    double *part = (double *)ws_get(2, (size_t)std::max<long long>(np * nT, 1) * sizeof(double));
+    double *scratch = nullptr;
+    if (!pool || !part || profile_scratch(m, np, &scratch)) rc = 1;
+    if (!rc) {
+      tm.start();
+      rc = launch_profile_fwd(m, MB_FORWARD, true, d, (int)np, p->d_logP, pool, nullptr, d_ll + c.p0, g_stream);
+      if (!rc && nT) rc = hip_ok(hipMemsetAsync(part, 0, (size_t)np * nT * sizeof(double), g_stream), "memset(counts)") ? 0 : 1;
+      if (!rc) rc = launch_profile_bwd(m, false, d, (int)np, p->d_logP, nullptr, pool, scratch, d_bll + c.p0, part, nT, g_stream);
+      if (!rc) rc = launch_profile_sum_counts(part, (int)np, nT, d_cc, g_stream);
+      g_last_ms += tm.stop();
+      ++g_last_launches;
+    }
+    if (!rc && nT && !hip_ok(hipMemcpy(hc.data(), d_cc, nT * sizeof(double), hipMemcpyDeviceToHost), "D2H counts")) rc = 1;
+    if (!rc) for (long long e = 0; e < nT; ++e) total[(size_t)e] += hc[(size_t)e];
+    if (rc) quiesce_streams();
+    sm_free(d);
+    if (rc) break;
+  }
+  std::vector<double> hll((size_t)p->n);
+  if (!rc && p->n && !hip_ok(hipMemcpy(hll.data(), d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  sm_free(d_ll); sm_free(d_bll); sm_free(d_cc);
+  g_last_kernel = "k_profile_bwd<counts>";
+  if (rc) return rc;
+  for (long long e = 0; e < nT; ++e) counts[e] += total[(size_t)e];
+  double s = 0.0;
+  for (long long k = 0; k < p->n; ++k) { s += hll[(size_t)k]; if (loglike) loglike[k] = hll[(size_t)k]; }
+  if (loglikeSum) *loglikeSum += s;
+  return 0;
+}
+
+int mb_profile_fill(mb_machine *m, int mode, const double *logP, int64_t nRows, double *cellsOut) {
+  ApiGuard guard;
+  if (!m || !cellsOut || nRows < 0 || (nRows && !logP)) { set_error("null argument"); return 1; }
+  if (mode != MB_FORWARD && mode != MB_VITERBI && mode != MB_BACKWARD) { set_error("unknown fill mode"); return 1; }
+  if (ensure_init()) return 1;
+  g_last_ms = 0.0; g_last_launches = 0;
+  const int64_t off[2] = {0, nRows};
+  mb_profiles *p = mb_profiles_create(m, 1, logP, off);
+  if (!p) return 1;
+  ProfDesc *d = nullptr;
+  long long cells = 0;
+  int rc = profile_descs(p, 0, 1, &d, &cells, nullptr);
+  double *d_ll = nullptr;
+  if (!rc && !hip_ok(sm_alloc((void **)&d_ll, sizeof(double)), "hipMalloc(loglike)")) rc = 1;
+  double *pool = rc ? nullptr : (double *)ws_get(0, (size_t)cells * sizeof(double));
+  if (!rc && !pool) rc = 1;
+  if (!rc) {
+    Timer tm;
+    tm.start();
+    rc = mode == MB_BACKWARD ? launch_profile_bwd(m, true, d, 1, p->d_logP, pool, nullptr, nullptr, d_ll, nullptr, 0, g_stream)
+                             : launch_profile_fwd(m, mode, true, d, 1, p->d_logP, pool, nullptr, d_ll, g_stream);
+    g_last_ms += tm.stop();
+    g_last_launches = 1;
+  }
+  if (!rc) rc = d2h_large(cellsOut, pool, (size_t)cells * sizeof(double));
+  if (rc) quiesce_streams();
+  sm_free(d); sm_free(d_ll);
+  mb_profiles_destroy(p);
+  g_last_kernel = mode == MB_BACKWARD ? "k_profile_bwd<mat>" : (mode == MB_VITERBI ? "k_profile_fwd<max,mat>" : "k_profile_fwd<sum,mat>");
   return rc;
 }
 

@@ -1,0 +1,203 @@
+"""CPU tests of profile tapes (machineboss_amd/profile.py): the CSV reader, the numpy restatement of the profile recurrence against
+the composition compose(M, transpose(CSVProfile::machine())) scored by the oracle with empty tapes, counts against finite
+differences, and the reference's --recognize-csv goldens (Makefile test-csv-tiny*, test-nanopore*)."""
+import json
+import math
+
+import numpy as np
+import pytest
+
+from conftest import golden_path, load_json
+from randmachine import random_machine
+from machineboss_amd import algebra
+from machineboss_amd.evalmachine import EvaluatedMachine
+from machineboss_amd.machine import Machine, MachineError, MachineState, MachineTransition
+from machineboss_amd.profile import Profile, ProfileDP, table_log_sum_exp
+
+
+def _csv(tmp_path, text):
+    p = tmp_path / "p.csv"
+    p.write_bytes(text.encode())
+    return Profile.fromCsv(str(p))
+
+
+def _machine_of(em):
+    """An EvaluatedMachine (randmachine) as a Machine with numeric weights, transitions in global-id order."""
+    m = Machine()
+    for _ in range(em.nStates):
+        m.state.append(MachineState())
+    isym, osym = em.inputTokenizer.tok2sym, em.outputTokenizer.tok2sym
+    for e in range(em.nTransitions):
+        m.state[int(em.src[e])].trans.append(MachineTransition(dest=int(em.dst[e]), inp=isym[em.inTok[e]] if em.inTok[e] else "",
+                                                                out=osym[em.outTok[e]] if em.outTok[e] else "", weight=float(np.exp(em.logWeight[e]))))
+    return m
+
+
+def _generator_json(name):
+    j = load_json("io", name)
+    return algebra.generator(list(j["sequence"]), j.get("name", ""))
+
+
+# ---- CSV reading (src/csv.cpp:48-72, src/util.cpp:71-85) ---------------------------------------------------------------------
+def test_csv_trailing_comma_and_runs_of_commas(tmp_path):
+    p = _csv(tmp_path, "A,,C,G,T,\n.1,,.2,.3,.4,.5\n")
+    assert p.header == ["A", "C", "G", "T"]
+    assert p.row == [[pytest.approx(.1), pytest.approx(.2), pytest.approx(.3), pytest.approx(.4), pytest.approx(.5)]]
+
+
+def test_csv_float32_rounding(tmp_path):
+    p = _csv(tmp_path, "A\n0.1,0.3\n")
+    assert p.row[0][0] == float(np.float32(0.1)) and p.row[0][0] != 0.1
+    assert p.row[0][1] == float(np.float32(0.3))
+
+
+def test_csv_no_blank_short_rows_all_blank(tmp_path):
+    p = _csv(tmp_path, "a,b\n.5,.5\n.25\n0,0,1\n\n,,\n")
+    assert len(p) == 3                       # empty lines and lines of separators only are no rows
+    em = EvaluatedMachine.fromMachine(algebra.generator(["a", "b"], "g"), {}, useDefaults=True)
+    P = p.logRows(em)
+    assert P.shape == (3, 3)
+    assert P[0, 0] == -math.inf              # no blank column: weight 0
+    assert P[0, 1] == math.log(.5) and P[0, 2] == math.log(.5)
+    assert P[1, 1] == math.log(.25) and P[1, 2] == -math.inf and P[1, 0] == -math.inf   # short row
+    assert P[2, 0] == 0.0 and P[2, 1] == -math.inf   # all blank
+
+
+def test_csv_columns_beyond_blank_and_foreign_symbols(tmp_path):
+    p = _csv(tmp_path, "x,a\n.5,.25,.125,9\n")
+    em = EvaluatedMachine.fromMachine(algebra.generator(["a", "c"], "g"), {}, useDefaults=True)
+    P = p.logRows(em)                         # tokens: 1 = a, 2 = c
+    assert P[0, 0] == math.log(.125)          # column len(header) = the blank; column 3 ignored
+    assert P[0, 1] == math.log(.25)           # "x" is not in the alphabet: dropped
+    assert P[0, 2] == -math.inf               # "c" is not in the header
+
+
+def test_csv_stof_leading_number(tmp_path):
+    p = _csv(tmp_path, "A\n 2.5e-1xyz,1\r\n")
+    assert p.row == [[0.25, 1.0]]
+    with pytest.raises(MachineError):
+        _csv(tmp_path, "A\nabc\n")
+
+
+def test_table_log_sum_exp_cutoff():
+    assert table_log_sum_exp(0.0, -10.5) == 0.0
+    assert abs(table_log_sum_exp(0.0, 0.0) - math.log(2)) < 1e-9
+    assert table_log_sum_exp(-math.inf, -math.inf) == -math.inf
+
+
+# ---- the restatement against the composed machine -----------------------------------------------------------------------------
+def _random_profile(rng, em, L):
+    syms = em.outputTokenizer.tok2sym[1:]
+    header = list(syms) + ["zz"]
+    rng.shuffle(header)
+    rows = []
+    for _ in range(L):
+        v = rng.uniform(0.05, 1.0, len(header) + 1)
+        v[rng.rand(len(v)) < 0.2] = 0.0
+        rows.append([float(np.float32(x)) for x in v[:rng.randint(len(header) - 1, len(header) + 2)]])
+    return Profile(header, rows)
+
+
+@pytest.mark.parametrize("seed", range(30))
+def test_restatement_equals_composition(oracle_mod, seed):
+    rng = np.random.RandomState(1000 + seed)
+    S = int(rng.randint(1, 9))
+    em0 = random_machine(S, 0, int(rng.randint(1, 4)), 500 + seed)
+    M = _machine_of(em0)
+    em = EvaluatedMachine.fromMachine(M, {}, useDefaults=True)
+    dp = ProfileDP(em)
+    prof = _random_profile(rng, em, int(rng.randint(0, 41)))
+    P = prof.logRows(em)
+    comp = algebra.compose(M, prof.recogniserMachine(), True, False)   # parallel transitions kept apart: Viterbi is per edge
+    ec = EvaluatedMachine.fromMachine(comp, {}, useDefaults=True)
+    om = oracle_mod.OracleMachine(ec)
+    exact = om.loglike([], [], oracle_mod.SUM_EXACT)
+    got = dp.forward(P)[0]
+    if exact == -math.inf:
+        assert got == -math.inf
+    else:
+        assert abs(got - exact) <= 1e-9 * max(1.0, abs(exact)), (got, exact)
+        assert abs(dp.backward(P)[0] - exact) <= 1e-9 * max(1.0, abs(exact))
+        table = om.loglike([], [], oracle_mod.SUM_TABLE)
+        assert abs(dp.forward(P, "table")[0] - table) <= 1e-6 * max(1.0, abs(table))
+    vit = om.viterbi([], [])[-1, -1, -1]
+    v, edges, rows = dp.viterbi(P)
+    assert (v == -math.inf and vit == -math.inf) or abs(v - vit) <= 1e-12 * max(1.0, abs(vit)), (v, vit)
+    if v > -math.inf:   # the path's weight is the score, its rows ascend and it emits at most one symbol per row
+        w = sum(em.logWeight[e] for e in edges) + sum(P[r, em.outTok[e]] for e, r in zip(edges, rows) if em.outTok[e])
+        emitted = [r for e, r in zip(edges, rows) if em.outTok[e]]
+        w += sum(P[r, 0] for r in sorted(set(range(len(P))) - set(emitted)))
+        assert abs(w - v) <= 1e-9 * max(1.0, abs(v))
+        assert list(rows) == sorted(rows) and len(emitted) == len(set(emitted))
+        assert int(em.src[edges[0]]) == 0 if len(edges) else True
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_counts_are_forward_derivatives(seed):
+    rng = np.random.RandomState(77 + seed)
+    em = random_machine(int(rng.randint(2, 7)), 0, 2, 900 + seed)
+    dp = ProfileDP(em)
+    P = _random_profile(rng, em, int(rng.randint(1, 12))).logRows(em)
+    c, ll = dp.counts(P)
+    if ll == -math.inf:
+        assert not c.any()
+        return
+    h = 1e-5
+    for t in range(em.nTransitions):
+        if em.inTok[t] or em.logWeight[t] == -math.inf:
+            continue
+        lw = em.logWeight.copy(); lw[t] += h
+        up = ProfileDP(em.withLogWeights(lw)).forward(P)[0]
+        lw[t] -= 2 * h
+        dn = ProfileDP(em.withLogWeights(lw)).forward(P)[0]
+        assert abs((up - dn) / (2 * h) - c[t]) <= 1e-6 + 1e-5 * abs(c[t]), (t, (up - dn) / (2 * h), c[t])
+
+
+# ---- the reference's goldens (Makefile:362-375) ---------------------------------------------------------------------------------
+GOLDENS = [("tiny_uc.json", None, "tiny_uc.csv", "tiny_uc"), ("tiny_lc.json", None, "tiny_uc.csv", "tiny_uc_fail"),
+           ("empty.json", None, "tiny_uc.csv", "tiny_empty"), ("nanopore_test_seq.json", None, "nanopore_test.csv", "nanopore_test"),
+           ("nanopore_test_seq.json", "acgt_wild.json", "nanopore_test.csv", "nanopore_test_prefix")]
+
+
+@pytest.mark.parametrize("seq,concat,csv,expect", GOLDENS)
+def test_reference_goldens(seq, concat, csv, expect):
+    M = _generator_json(seq)
+    if concat:
+        M = algebra.concatenate(M, Machine.fromFile(golden_path("machine", concat)))
+    em = EvaluatedMachine.fromMachine(M, {}, useDefaults=True)
+    P = Profile.fromCsv(golden_path("csv", csv)).logRows(em)
+    want = load_json("expect", expect + ".json")[0][0]
+    want = -math.inf if want == "-Infinity" else float(want)
+    dp = ProfileDP(em)
+    exact, table = dp.forward(P)[0], dp.forward(P, "table")[0]
+    if want == -math.inf:
+        assert exact == -math.inf and table == -math.inf
+        return
+    assert abs(table - want) <= 2e-4, (table, want)
+    assert abs(exact - want) <= 1e-4 * abs(want), (exact, want)
+
+
+def test_tiny_goldens_by_hand():
+    em = EvaluatedMachine.fromMachine(_generator_json("tiny_uc.json"), {}, useDefaults=True)
+    P = Profile.fromCsv(golden_path("csv", "tiny_uc.csv")).logRows(em)
+    f32 = lambda x: float(np.float32(x))
+    assert abs(ProfileDP(em).forward(P)[0] - math.log(4 * f32(.1) * f32(.6) ** 3)) < 1e-12
+    em0 = EvaluatedMachine.fromMachine(_generator_json("empty.json"), {}, useDefaults=True)
+    assert abs(ProfileDP(em0).forward(Profile.fromCsv(golden_path("csv", "tiny_uc.csv")).logRows(em0))[0] - 4 * math.log(f32(.6))) < 1e-12
+
+
+def test_bitnoise_profile_equals_token_golden():
+    """seq101 . bitnoise against prof001.csv (a one-hot profile of 001) = expect/101-bitnoise-001.json."""
+    M = algebra.compose(_generator_json("seq101.json"), Machine.fromFile(golden_path("machine", "bitnoise.json")))
+    params = load_json("io", "params.json")
+    em = EvaluatedMachine.fromMachine(M, params)
+    P = Profile.fromCsv(golden_path("csv", "prof001.csv")).logRows(em)
+    want = float(load_json("expect", "101-bitnoise-001.json")[0][0])
+    assert abs(ProfileDP(em).forward(P)[0] - want) <= 1e-4 * abs(want)
+
+
+def test_recogniser_machine_shape():
+    p = Profile.fromCsv(golden_path("csv", "tiny_uc.csv"))
+    r = p.recogniserMachine()
+    assert len(r.state) == 5 and r.inputAlphabet() == ["A", "C", "G", "T"] and not r.outputAlphabet()
+    assert [t.inp for t in r.state[0].trans] == ["A", "C", "G", "T", ""]
