@@ -5,7 +5,10 @@ import numpy as np
 from machineboss_amd.evalmachine import EvaluatedMachine, Tokenizer
 
 
-def random_machine(S, nIn, nOut, seed, density=2.0, silent_density=1.2, dup=True, allow_inf=False):
+def random_machine(S, nIn, nOut, seed, density=2.0, silent_density=1.2, dup=True, allow_inf=False, backbone=0.7, to_end=0.0):
+    """backbone: the chance of a silent s -> s+1 edge (each one adds a silent level; 0 keeps the levels few).  to_end: the chance
+    of an extra emitting edge s -> S-1 (from a second generator), which keeps the end state reachable without the backbone.  Every
+    keyword leaves the default call's random draws where they were: it returns the same machine whatever is added here."""
     rng = np.random.RandomState(seed)
     edges = []  # (src, dst, it, ot, logw)
     for s in range(S):
@@ -21,8 +24,11 @@ def random_machine(S, nIn, nOut, seed, density=2.0, silent_density=1.2, dup=True
         for _ in range(ns):
             if s + 1 < S:
                 edges.append((s, rng.randint(s + 1, S), 0, 0, float(np.log(rng.uniform(0.05, 1.0)))))
-        if s + 1 < S and rng.rand() < 0.7:   # keep the end state reachable through a silent backbone
+        if s + 1 < S and rng.rand() < backbone:   # keep the end state reachable through a silent backbone
             edges.append((s, s + 1, 0, 0, float(np.log(rng.uniform(0.2, 1.0)))))
+    if to_end > 0 and nOut:
+        rng2 = np.random.RandomState(seed + 7919)
+        edges += [(s, S - 1, 0, int(rng2.randint(1, nOut + 1)), float(np.log(rng2.uniform(0.05, 1.0)))) for s in range(S) if rng2.rand() < to_end]
     if dup and edges:
         for _ in range(max(1, len(edges) // 10)):
             e = edges[rng.randint(len(edges))]
@@ -95,3 +101,45 @@ def plain_hmm(S, fan, nOut, seed):
     off = np.cumsum(off)
     tidx = (np.arange(n) - off[src]).astype(np.uint32)
     return EvaluatedMachine(S, Tokenizer([]), Tokenizer([chr(97 + k) for k in range(nOut)]), src, dst, it, ot, tidx, lw, off, [None] * S)
+
+
+QUANT = (0.0, float(np.log(0.5)), float(np.log(0.25)), -np.inf)
+
+
+def quantised_machine(S, nIn, nOut, seed, p_inf=0.1):
+    """Log weights from QUANT only, so Viterbi candidates tie: every emitting edge has a duplicate of the same weight (parallel
+    edges), emitting edges into one state come from several sources with different tokens, silent edges of weight 0 or log 1/2.
+    With nIn > 0 some edges read input (and never fire against a profile)."""
+    rng = np.random.RandomState(seed)
+    q = lambda: QUANT[3] if rng.rand() < p_inf else QUANT[rng.randint(3)]
+    edges = []
+    for s in range(S):
+        for _ in range(rng.randint(1, 4)):
+            d, ot, w = rng.randint(0, S), rng.randint(1, nOut + 1) if nOut else 0, q()
+            if ot:
+                edges.append((s, d, 0, ot, w))
+                if rng.rand() < 0.5:
+                    edges.append((s, d, 0, ot, w))                          # a parallel edge of equal weight
+            if nIn:
+                edges.append((s, d, rng.randint(1, nIn + 1), ot if rng.rand() < 0.5 else 0, q()))
+        if s + 1 < S:
+            edges.append((s, s + 1 + rng.randint(min(3, S - s - 1)), 0, 0, QUANT[rng.randint(2)]))
+    edges.sort(key=lambda e: e[0])
+    n = len(edges)
+    src = np.array([e[0] for e in edges], np.uint32); dst = np.array([e[1] for e in edges], np.uint32)
+    it = np.array([e[2] for e in edges], np.uint16); ot = np.array([e[3] for e in edges], np.uint16)
+    lw = np.array([e[4] for e in edges], np.float64)
+    off = np.zeros(S + 1, np.int64)
+    for s in src:
+        off[s + 1] += 1
+    off = np.cumsum(off)
+    tidx = (np.arange(n) - off[src]).astype(np.uint32)
+    return EvaluatedMachine(S, Tokenizer([chr(65 + k) for k in range(nIn)]), Tokenizer([chr(97 + k) for k in range(nOut)]),
+                            src, dst, it, ot, tidx, lw, off, [None] * S)
+
+
+def quantised_profile(rng, nOut, L, p_inf=0.15):
+    """[L, nOut + 1] log weights from QUANT: blank and symbol columns often equal."""
+    P = np.array(QUANT[:3])[rng.randint(0, 3, (L, nOut + 1))]
+    P[rng.rand(L, nOut + 1) < p_inf] = -np.inf
+    return P

@@ -10,11 +10,11 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, golden_path, load_json
+from profhelpers import _check_all, _close, _profiles
 from randmachine import random_machine
 from machineboss_amd import algebra, capi
 from machineboss_amd.evalmachine import EvaluatedMachine
 from machineboss_amd.machine import Machine
-from machineboss_amd.profile import ProfileDP
 
 pytestmark = pytest.mark.gpu
 
@@ -27,58 +27,6 @@ def device():
     yield
     capi.set_memory_budget(0)
     capi.set_option("MB_DETERMINISTIC", None)
-
-
-def _profiles(em, lengths, seed, zeros=0.2):
-    rng = np.random.RandomState(seed)
-    out = []
-    for L in lengths:
-        P = np.log(rng.uniform(0.02, 1.0, (L, em.nOutTok + 1)))
-        P[rng.rand(L, em.nOutTok + 1) < zeros] = -np.inf
-        out.append(P)
-    return out
-
-
-def _close(a, b, rel):
-    a, b = np.asarray(a), np.asarray(b)
-    both_inf = (a == -np.inf) & (b == -np.inf)
-    with np.errstate(invalid="ignore"):
-        return bool(np.all(both_inf | (np.abs(a - b) <= rel * np.maximum(1.0, np.abs(b)))))
-
-
-def _check_all(em, profs, fill=True):
-    dm = capi.DeviceMachine(em)
-    dp = ProfileDP(em)
-    dev = capi.DeviceProfiles(dm, profs)
-    ref = [dp.forward(P) for P in profs]
-    want = np.array([r[0] for r in ref])
-    assert _close(dev.forward(capi.MB_ROLLING), want, 1e-9)
-    assert _close(dev.forward(capi.MB_MATERIALISE), want, 1e-9)
-    v, off, edges, rows = dev.viterbi()
-    v0, _, _, _ = dev.viterbi(paths=False)
-    for k, P in enumerate(profs):
-        rv, re_, rr = dp.viterbi(P)
-        assert v[k] == rv and v0[k] == rv, (k, v[k], rv)
-        assert np.array_equal(edges[off[k]:off[k + 1]], re_) and np.array_equal(rows[off[k]:off[k + 1]], rr), k
-    c, s, ll = dev.counts()
-    rc = np.zeros(em.nTransitions)
-    for P in profs:
-        rc += dp.counts(P)[0]
-    assert _close(ll, want, 1e-9)
-    assert np.allclose(c, rc, rtol=1e-6, atol=1e-9), np.abs(c - rc).max()
-    assert s == pytest.approx(float(np.sum(want)), rel=1e-9) if np.all(want > -np.inf) else True
-    if fill:
-        k = int(np.argmax([len(q) for q in profs]))
-        P, (_, N, W) = profs[k], ref[k]
-        F = capi.profile_fill(dm, capi.MB_FORWARD, P)
-        assert _close(F[:, 0], N, 1e-9) and _close(F[:, 1], W, 1e-9)
-        _, Nv, Wv = dp.forward(P, "max")
-        V = capi.profile_fill(dm, capi.MB_VITERBI, P)
-        assert np.array_equal(V[:, 0], Nv) and np.array_equal(V[:, 1], Wv)
-        _, NB, WB = dp.backward(P)
-        B = capi.profile_fill(dm, capi.MB_BACKWARD, P)
-        assert _close(B[:, 0], NB, 1e-9) and _close(B[:, 1], WB, 1e-9)
-    return dm, dev, c
 
 
 @pytest.mark.parametrize("S,nOut,seed", [(8, 2, 1), (8, 4, 2), (300, 4, 3), (2000, 4, 4)])

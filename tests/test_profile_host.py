@@ -1,6 +1,7 @@
 """CPU tests of profile tapes (machineboss_amd/profile.py): the CSV reader, the numpy restatement of the profile recurrence against
 the composition compose(M, transpose(CSVProfile::machine())) scored by the oracle with empty tapes, counts against finite
 differences, and the reference's --recognize-csv goldens (Makefile test-csv-tiny*, test-nanopore*)."""
+import hashlib
 import json
 import math
 
@@ -8,7 +9,8 @@ import numpy as np
 import pytest
 
 from conftest import golden_path, load_json
-from randmachine import random_machine
+from profhelpers import _machine_of, tie_census
+from randmachine import quantised_machine, quantised_profile, random_machine
 from machineboss_amd import algebra
 from machineboss_amd.evalmachine import EvaluatedMachine
 from machineboss_amd.machine import Machine, MachineError, MachineState, MachineTransition
@@ -19,18 +21,6 @@ def _csv(tmp_path, text):
     p = tmp_path / "p.csv"
     p.write_bytes(text.encode())
     return Profile.fromCsv(str(p))
-
-
-def _machine_of(em):
-    """An EvaluatedMachine (randmachine) as a Machine with numeric weights, transitions in global-id order."""
-    m = Machine()
-    for _ in range(em.nStates):
-        m.state.append(MachineState())
-    isym, osym = em.inputTokenizer.tok2sym, em.outputTokenizer.tok2sym
-    for e in range(em.nTransitions):
-        m.state[int(em.src[e])].trans.append(MachineTransition(dest=int(em.dst[e]), inp=isym[em.inTok[e]] if em.inTok[e] else "",
-                                                                out=osym[em.outTok[e]] if em.outTok[e] else "", weight=float(np.exp(em.logWeight[e]))))
-    return m
 
 
 def _generator_json(name):
@@ -98,16 +88,31 @@ def _random_profile(rng, em, L):
     return Profile(header, rows)
 
 
-@pytest.mark.parametrize("seed", range(30))
+def _quantised_csv(rng, em, L):
+    """A profile of weights 1, 1/2, 1/4 and 0 (quantised_profile) as a CSV profile: symbols in token order, then the blank."""
+    P = quantised_profile(rng, em.nOutTok, L)
+    return Profile(em.outputTokenizer.tok2sym[1:], np.exp(np.roll(P, -1, axis=1)).tolist())
+
+
+@pytest.mark.parametrize("seed", range(50))
 def test_restatement_equals_composition(oracle_mod, seed):
+    """Seeds 0-29: random machines and profiles; 30-39: quantised weights (Viterbi ties); 40-49: machines with an input alphabet,
+    whose input-reading transitions never fire against the empty input tape."""
     rng = np.random.RandomState(1000 + seed)
     S = int(rng.randint(1, 9))
-    em0 = random_machine(S, 0, int(rng.randint(1, 4)), 500 + seed)
+    if seed < 30:
+        em0 = random_machine(S, 0, int(rng.randint(1, 4)), 500 + seed)
+    elif seed < 40:
+        em0 = quantised_machine(S, 0, int(rng.randint(1, 4)), 500 + seed)
+    else:
+        em0 = random_machine(S, int(rng.randint(1, 4)), int(rng.randint(1, 4)), 500 + seed)
     M = _machine_of(em0)
     em = EvaluatedMachine.fromMachine(M, {}, useDefaults=True)
     dp = ProfileDP(em)
-    prof = _random_profile(rng, em, int(rng.randint(0, 41)))
+    prof = (_random_profile if seed < 30 or seed >= 40 else _quantised_csv)(rng, em, int(rng.randint(0, 41)))
     P = prof.logRows(em)
+    if 30 <= seed < 40:
+        assert set(np.unique(P)) <= {0.0, math.log(.5), math.log(.25), -math.inf}
     comp = algebra.compose(M, prof.recogniserMachine(), True, False)   # parallel transitions kept apart: Viterbi is per edge
     ec = EvaluatedMachine.fromMachine(comp, {}, useDefaults=True)
     om = oracle_mod.OracleMachine(ec)
@@ -201,3 +206,31 @@ def test_recogniser_machine_shape():
     r = p.recogniserMachine()
     assert len(r.state) == 5 and r.inputAlphabet() == ["A", "C", "G", "T"] and not r.outputAlphabet()
     assert [t.inp for t in r.state[0].trans] == ["A", "C", "G", "T", ""]
+
+
+# ---- the test machines themselves ------------------------------------------------------------------------------------------------
+def _digest(em):
+    h = hashlib.sha256()
+    for a in (em.src, em.dst, em.inTok, em.outTok, em.logWeight, em.transIndex, em.transOffset):
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()[:16]
+
+
+def test_random_machine_default_stream_unchanged():
+    """Keywords added to random_machine must not move its random draws: every parity test depends on these machines."""
+    assert _digest(random_machine(8, 0, 2, 1)) == "8151d34a70a38ab4"
+    assert _digest(random_machine(300, 0, 4, 3)) == "6f7ae7d87437ea7b"
+    assert _digest(random_machine(7000, 0, 3, 11, density=1.0, silent_density=0.3)) == "f0670239b55c597a"
+    assert _digest(random_machine(40, 2, 3, 5)) == "01fcbaf6e4e78544"
+
+
+def test_quantised_restatement_has_ties():
+    """The quantised machines give the traceback many equal candidates of every kind (what the device tie tests rely on)."""
+    tot = {"blank": 0, "emit": 0, "stay": 0, "silent": 0}
+    for seed in range(4):
+        em = quantised_machine(12, 0, 3, seed)
+        dp, rng = ProfileDP(em), np.random.RandomState(seed)
+        for L in (5, 20, 40):
+            for k, n in tie_census(dp, quantised_profile(rng, 3, L)).items():
+                tot[k] += n
+    assert tot["blank"] >= 10 and tot["emit"] >= 40 and tot["stay"] >= 10, tot
