@@ -162,6 +162,29 @@ int mb_profiles_viterbi(mb_profiles *p, double *loglike, int64_t *pathOff, uint3
 int mb_profiles_counts(mb_profiles *p, double *counts, double *loglikeSum, double *loglike);
 int mb_profile_fill(mb_machine *m, int mode, const double *logP, int64_t nRows, double *cellsOut);
 
+/* ---- prefix search: imputing the input tape (--prefix-decode / --prefix-encode / --random-encode) -------------------------------
+ * The node fill of the reference's PrefixTree (src/ctc.cpp:25-88) on the device, the tree and its heap on the host
+ * (docs/decoding.md).  An mb_prefix holds nSeq searches (output sequence k = outTok[outOff[k]..outOff[k+1]), tokens 1..nOutTok)
+ * and a pool of maxNodes node lattices of (maxOutLen + 1) x 2 x nStates doubles, taken from the library's workspace under the
+ * memory budget (mb_set_memory_budget); it never grows: a fill that finds the pool full fails and changes nothing.
+ * logSumInTrans is R = log((I - N)^-1), nStates x nStates row-major, N summing exp(w) over the transitions with empty output
+ * (EvaluatedMachine::logSumInTrans, src/eval.cpp:146-184); -inf allowed, NaN / +inf rejected.
+ * mb_prefix_root fills the root of search `seq`; mb_prefix_extend fills n children in ONE launch: entry i is the child of node
+ * parent[i] (a live node of search seq[i]) by input token inTok[i] (1..nInTok).  Both return node handles (slot numbers) and,
+ * per node, logSeqProb = log P(x, y) and logPrefixProb = log P(y | an input starting with x).  mb_prefix_release hands slots back.
+ * Node lattices: cells[((j*2) + layer)*nStates + state], j = 0..outLen of the node's search, layer 0 = seq, layer 1 = prefix.
+ * A fill gives the same bits from call to call. */
+typedef struct mb_prefix mb_prefix;
+mb_prefix *mb_prefix_create(mb_machine *m, int64_t nSeq, const int32_t *outTok, const int64_t *outOff,
+                            const double *logSumInTrans, int64_t maxNodes);
+void mb_prefix_destroy(mb_prefix *p);
+int mb_prefix_root(mb_prefix *p, int64_t seq, int64_t *nodeOut, double *logSeqProb, double *logPrefixProb);
+int mb_prefix_extend(mb_prefix *p, int64_t n, const int64_t *seq, const int64_t *parent, const int32_t *inTok,
+                     int64_t *childOut, double *logSeqProb, double *logPrefixProb);
+int mb_prefix_release(mb_prefix *p, int64_t n, const int64_t *node);
+int64_t mb_prefix_free_nodes(const mb_prefix *p);
+int mb_prefix_node_cells(mb_prefix *p, int64_t node, double *cellsOut);
+
 /* ---- convenience wrappers over host buffers (create batch, run, destroy) ----------------------------------
  * forwardLogLike / viterbiLogLike+viterbiAlign / forwardBackwardCounts of src/api.h:20-34.                   */
 int mb_forward_batch(mb_machine *m, int64_t nPairs, const int32_t *inTok, const int64_t *inOff,
@@ -200,6 +223,7 @@ double mb_log_inner_product(const double *v1, const double *v2, const double *v3
 int mb_set_kernel(int which);
 /* Bytes of device memory the library may use for DP matrices (default: 80 % of free HBM). */
 int mb_set_memory_budget(size_t bytes);
+size_t mb_memory_budget(void);   /* what the pools of one call may take now: the explicit budget, else a share of the device (0: no device) */
 /* The library keeps its matrix pools allocated between calls (grow-only); this frees them. */
 int mb_release_workspace(void);
 /* What the matrix pools cost this process so far: device allocations and releases of pool slots, slots evicted to make room,

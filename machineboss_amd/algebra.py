@@ -18,6 +18,7 @@ unitindel-unitindel.json).
 from __future__ import annotations
 
 import json
+import math
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
 from .machine import Constraints, Machine, MachineError, MachineState, MachineTransition
@@ -372,17 +373,22 @@ def padWithNullStates(m: Machine) -> Machine:
     return result if hasNullPaddingStates(result) else concatenate(result, dummy)
 
 
-def advanceSort(m: Machine) -> Machine:
-    """src/machine.cpp:1245-1378 with countBackTransitions = nSilentBackTransitions, mustAdvance = isSilent."""
+def nEmptyOutputBackTransitions(m: Machine) -> int:
+    return sum(1 for s in range(1, len(m.state)) for t in m.state[s].trans if t.outputEmpty() and t.dest <= s)
+
+
+def advanceSort(m: Machine, nBackTransitions=nSilentBackTransitions, mustAdvance=MachineTransition.isSilent) -> Machine:
+    """src/machine.cpp:1245-1378; the defaults (countBackTransitions = nSilentBackTransitions, mustAdvance = isSilent) are
+    Machine::advanceSort(), decodeSort passes the non-outputting pair."""
     n = len(m.state)
-    before = nSilentBackTransitions(m)
+    before = nBackTransitions(m)
     if not before:
         return m
     silIn: List[List[int]] = [[] for _ in range(n)]; silOut: List[List[int]] = [[] for _ in range(n)]
     nIn = [0] * n; nOut = [0] * n
     for s in range(1, n - 1):
         for t in m.state[s].trans:
-            if t.isSilent() and t.dest != s and t.dest != n - 1 and t.dest != 0:
+            if mustAdvance(t) and t.dest != s and t.dest != n - 1 and t.dest != 0:
                 silOut[s].append(t.dest); silIn[t.dest].append(s); nOut[s] += 1; nIn[t.dest] += 1
     key = lambda a: (nIn[a], nIn[a] - nOut[a], a)      # the std::set comparator
     order: List[int] = []
@@ -415,15 +421,15 @@ def advanceSort(m: Machine) -> Machine:
             ns = MachineState(); ns.name = m.state[s].name
             ns.trans = [_copyTrans(t, old2new[t.dest]) for t in m.state[s].trans]
             result.state.append(ns)
-    after = nSilentBackTransitions(result)
+    after = nBackTransitions(result)
     if after >= before and changed:
         result = m
     if after and not hasNullPaddingStates(m):
         withDummy = padWithNullStates(m)
         if not hasNullPaddingStates(withDummy):
             raise MachineError("Dummy machine does not look like a dummy, triggering infinite dummification loop")
-        sortedWithDummy = advanceSort(withDummy)
-        if nSilentBackTransitions(sortedWithDummy) < after:
+        sortedWithDummy = advanceSort(withDummy, nBackTransitions, mustAdvance)
+        if nBackTransitions(sortedWithDummy) < after:
             result = sortedWithDummy
     return result
 
@@ -629,3 +635,51 @@ def config4bMachine(presetDir: str) -> Machine:
     d = P("dnapsw")
     d.cons = Constraints()
     return compose(compose(P("protpsw"), P("translate")), d)
+
+
+# ---- decoding (target/boss.cpp:850-921) ------------------------------------------------------------------------------------
+def transpose(m: Machine) -> Machine:
+    """Machine::transpose (src/machine.cpp:1892-1898): input and output labels swapped -- encoding is decoding of the transpose."""
+    r = _copyMachine(m)
+    for ms in r.state:
+        for t in ms.trans:
+            t.inp, t.out = t.out, t.inp
+    return r
+
+
+def silenceInput(m: Machine) -> Machine:
+    """Machine::silenceInput (src/machine.cpp:629-635): the same states and transitions with every input label cleared."""
+    r = _copyMachine(m)
+    for ms in r.state:
+        for t in ms.trans:
+            t.inp = ""
+    return r
+
+
+def decodeSort(m: Machine) -> Machine:
+    """Machine::decodeSort (src/machine.cpp:1232-1234): advanceSort over the non-outputting transitions."""
+    return advanceSort(m, nEmptyOutputBackTransitions, MachineTransition.outputEmpty)
+
+
+def decodePath(path, m: Machine, params=None) -> List[str]:
+    """EvaluatedMachine::decode (src/eval.cpp:204-216): the input symbols along a path through the input-silenced copy of ``m``
+    (the same state order): per step source -> dest with output ``out``, the input token of the heaviest such transition of ``m``
+    (bestOutgoingToken, src/eval.cpp:13-24: tokens ascending, then destination order, a strictly greater weight replaces)."""
+    from .evalmachine import EvaluatedMachine
+    ev = EvaluatedMachine.fromMachine(m, params)
+    order = ev.outgoingOrder()
+    best: Dict[tuple, int] = {}
+    bestW: Dict[tuple, float] = {}
+    for e in order:
+        k = (int(ev.src[e]), int(ev.dst[e]), int(ev.outTok[e]))
+        w = float(ev.logWeight[e])
+        if w > bestW.get(k, -math.inf):
+            bestW[k] = w; best[k] = int(ev.inTok[e])
+    out: List[str] = []
+    s = m.startState()
+    for t in path.trans:
+        tok = best.get((s, t.dest, ev.outputTokenizer.sym2tok[t.out]), 0)
+        if tok:
+            out.append(ev.inputTokenizer.tok2sym[tok])
+        s = t.dest
+    return out

@@ -4,6 +4,8 @@
            [-D seqpairs.json] [--input-chars S] [--output-chars S] [--input-fasta F] [--output-fasta F]
            [--input-json F] [--output-json F] [--use-defaults] [-L] [-V] [-A] [-C] [-T] [-R width]
            [--generate-json F] [--recognize-csv F]
+           [--prefix-decode] [--prefix-encode] [--prefix-backtrack N] [--viterbi-decode] [--viterbi-encode]
+           [--random-encode] [--seed N] [--decode-backend device|numpy] [--decode-nodes N]
 
 Restates the data-handling and inference section of /root/reference/target/boss.cpp:716-847 -- how sequences are
 collected into pairs, how parameters are assembled, and the exact output text of --loglike / --viterbi / --align /
@@ -15,6 +17,11 @@ transducer files / presets on one command line are COMPOSED (algebra.py = Machin
 ``--recognize-csv FILE`` puts a profile (a soft output sequence, src/csv.cpp) behind the machines.  The reference composes
 it as an (L+1)-state recogniser; here the composed left part, which must have an empty input alphabet, is scored natively
 against the profile (profile.py, mb_profile.hip) with -L, -V or -C, and prints what the reference prints.
+
+``--prefix-decode`` imputes the most likely INPUT for each given output by the reference's prefix search (src/ctc.cpp), its
+node fills on the device (prefixtree.py, mb_prefix.hip, docs/decoding.md); ``--prefix-encode`` the most likely OUTPUT for each
+given input (the same search on the transposed machine), ``--random-encode`` samples one; ``--viterbi-decode / --viterbi-encode``
+read the answer off the Viterbi path of the input-silenced machine (target/boss.cpp:850-921).  All print a SeqPairList.
 
 Numbers print like C++ `ostream << double` (6 significant digits, target/boss.cpp:794-807 via src/jsonio.h:14-22),
 parameters with 15 (src/weight.cpp:483).  Work is batched: all pairs go through one device call per mode; with
@@ -122,7 +129,7 @@ def seqPairFromPath(m: Machine, path, inputName: str, outputName: str) -> SeqPai
 def buildParser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="boss", description=__doc__.split("\n\n")[0])
     ap.add_argument("machine", nargs="*", help="transducer JSON file")
-    ap.add_argument("--preset", action="append", default=[], help="preset name (dnapsw, protpsw, psw2dna, translate); repeatable")
+    ap.add_argument("--preset", action="append", default=[], help="preset name (dnapsw, protpsw, psw2dna, translate, hamming74); repeatable")
     ap.add_argument("-H", "--hmmer", help="generator from a HMMER3 model file, local alignment mode (target/boss.cpp:574-579); leftmost")
     ap.add_argument("--hmmer-global", help="the same in global alignment mode")
     ap.add_argument("--hmmer-plan7", help="Plan7 generator (single hit, N/C flanks)")
@@ -145,6 +152,16 @@ def buildParser() -> argparse.ArgumentParser:
     ap.add_argument("-C", "--counts", action="store_true")
     ap.add_argument("-T", "--train", action="store_true")
     ap.add_argument("-R", "--wiggle-room", type=int)
+    ap.add_argument("--prefix-decode", action="store_true", help="most likely input for each output, by prefix search")
+    ap.add_argument("--prefix-encode", action="store_true", help="most likely output for each input, by prefix search")
+    ap.add_argument("--prefix-backtrack", type=int, help="purge open prefixes more than N symbols shorter than the longest")
+    ap.add_argument("--viterbi-decode", action="store_true", help="input of the Viterbi path for each output")
+    ap.add_argument("--viterbi-encode", action="store_true", help="output of the Viterbi path for each input")
+    ap.add_argument("--random-encode", action="store_true", help="sample an output for each input")
+    ap.add_argument("--seed", type=int, help="random number seed")
+    ap.add_argument("--decode-backend", choices=("device", "numpy"), default=os.environ.get("MB_DECODE_BACKEND") or "device",
+                    help="who fills the search lattices: the HIP kernels (default) or the numpy restatement")
+    ap.add_argument("--decode-nodes", type=int, help="size of the node pool of a prefix search (lattices of 2 (L+1) S doubles)")
     return ap
 
 
@@ -178,7 +195,7 @@ def loadMachine(args) -> Machine:
     return composeAll(machines)
 
 
-def collectData(args, machine: Machine, inferenceRequested: bool) -> List[SeqPair]:
+def collectData(args, machine: Machine, inferenceRequested: bool, encoding: bool = False, decoding: bool = False) -> List[SeqPair]:
     """target/boss.cpp:716-773."""
     data: List[SeqPair] = []
     for f in args.data:
@@ -198,9 +215,9 @@ def collectData(args, machine: Machine, inferenceRequested: bool) -> List[SeqPai
     if args.output_json:
         j = json.load(open(args.output_json)); outSeqs.append((j.get("name", ""), list(j["sequence"])))
     inputEmpty, outputEmpty = not machine.inputAlphabet(), not machine.outputAlphabet()
-    if not inSeqs and inputEmpty and ((outputEmpty and inferenceRequested) or outSeqs):
+    if not inSeqs and ((inputEmpty and ((outputEmpty and inferenceRequested) or outSeqs)) or encoding or decoding):
         inSeqs.append(("", []))
-    if not outSeqs and inSeqs and outputEmpty:
+    if not outSeqs and ((inSeqs and outputEmpty) or encoding):
         outSeqs.append(("", []))
     for iname, iseq in inSeqs:
         for oname, oseq in outSeqs:
@@ -302,14 +319,109 @@ def runProfile(args, out) -> int:
     return 0
 
 
+def _viterbiInputs(backend: str, silent: Machine, decodeTrans: Machine, params, outputs: List[List[str]]) -> List[List[str]]:
+    """--viterbi-decode / --viterbi-encode (target/boss.cpp:869-873, 904-907): the Viterbi path of the input-silenced machine for
+    each output, then the input symbols of the heaviest matching transitions of the machine itself (algebra.decodePath).  The
+    device backend is the existing Viterbi-with-paths entry point; the numpy one scores the silenced machine, a generator,
+    against the output as a one-hot profile (profile.ProfileDP), which takes the same first maximum."""
+    from . import dp
+    from .algebra import decodePath
+    ev = EvaluatedMachine.fromMachine(silent, params)
+    if not all(ev.outputTokenizer.canTokenize(o) for o in outputs):
+        raise MachineError("Can't do traceback: no finite-weight paths")
+    if backend == "numpy":
+        import numpy as np
+        from .profile import ProfileDP
+        pdp = ProfileDP(ev)
+        paths = []
+        for o in outputs:
+            P = np.full((len(o), ev.nOutTok + 1), -math.inf)
+            P[np.arange(len(o)), ev.outputTokenizer.tokenize(o)] = 0.0
+            v, edges, _ = pdp.viterbi(P)
+            paths.append(dp.edgesToPath(ev, silent, edges) if v > -math.inf else None)
+    else:
+        paths = [p for _, p in dp.viterbiBatch(ev, silent, [SeqPair([], o, "", "") for o in outputs])]
+    if any(p is None for p in paths):
+        raise MachineError("Can't do traceback: no finite-weight paths")
+    return [decodePath(p, decodeTrans, params) for p in paths]
+
+
+def encodingMachine(machine: Machine, viterbi: bool = False) -> Machine:
+    """The machine whose DECODING is the encoding of ``machine`` (target/boss.cpp:854-855)."""
+    from . import algebra
+    trans = algebra.advancingMachine(algebra.advanceSort(algebra.transpose(machine)))
+    return algebra.decodeSort(trans) if viterbi else trans
+
+
+def viterbiEncode(machine: Machine, inputs: List[List[str]], backend: str = "device", params=None) -> List[List[str]]:
+    """--viterbi-encode as a function: the output of the Viterbi path for each input symbol sequence."""
+    from . import algebra
+    trans = encodingMachine(machine, True)
+    return _viterbiInputs(backend, algebra.silenceInput(trans), trans, machine.getParamDefs(True) if params is None else params, inputs)
+
+
+def _canonical(mt) -> float:
+    """uniform_real_distribution<double>(0, 1) over a 32-bit generator: two draws, low word first."""
+    lo = mt(); hi = mt()
+    return min((lo + hi * 4294967296.0) / 18446744073709551616.0, 1.0 - 2.0 ** -53)
+
+
+def runCoding(args, machine: Machine, params, data: List[SeqPair], emit) -> None:
+    """The encode and decode sections of target/boss.cpp:850-921."""
+    from . import algebra, prefixtree
+    from .dp import Mt19937
+    maxBacktrack = args.prefix_backtrack if args.prefix_backtrack is not None else prefixtree.NO_BACKTRACK_LIMIT
+    encoding = args.prefix_encode or args.viterbi_encode or args.random_encode
+    decoding = args.prefix_decode or args.viterbi_decode
+
+    def impute(trans: Machine, viterbi: bool, sample: bool, outputs: List[List[str]]) -> List[List[str]]:
+        if viterbi:
+            return _viterbiInputs(args.decode_backend, algebra.silenceInput(trans), trans, params, outputs)
+        ev = EvaluatedMachine.fromMachine(trans, params)
+        if not sample:
+            return prefixtree.decodeBatch(ev, outputs, maxBacktrack, args.decode_backend, args.decode_nodes)[0]
+        import time
+        seed = args.seed if args.seed is not None else int(time.time())
+        res = []
+        for o in outputs:
+            mt = Mt19937(seed)                     # makeRnd() per sequence pair (target/boss.cpp:877): every pair starts from the seed
+            tree = prefixtree.PrefixTree.forOutput(ev, o, maxBacktrack, args.decode_backend, args.decode_nodes)
+            try:
+                res.append(tree.sampleSeq(lambda: _canonical(mt)))
+            finally:
+                tree.close()
+        return res
+
+    if encoding:
+        if not data:
+            raise MachineError("To encode an output sequence, please specify an input sequence file")
+        for sp in data:
+            if sp.output:
+                raise MachineError("You cannot specify output sequences when encoding; the goal of encoding is to generate %s output for a given input"
+                                   % ("random" if args.random_encode else "the most likely"))
+        trans = encodingMachine(machine, args.viterbi_encode)      # encoding is decoding of the transpose
+        enc = impute(trans, args.viterbi_encode, args.random_encode, [sp.input for sp in data])
+        emit("[" + ",\n ".join(seqPairJson(SeqPair(sp.input, e, sp.inputName, "output")) for sp, e in zip(data, enc)) + "]\n")
+    if decoding:
+        if not data:
+            raise MachineError("To decode an input sequence, please specify an output sequence file")
+        for sp in data:
+            if sp.input:
+                raise MachineError("You cannot specify input sequences when decoding; the goal of decoding is to impute the most likely input for a given output")
+        dec = impute(machine, args.viterbi_decode, False, [sp.output for sp in data])
+        emit("[" + ",\n ".join(seqPairJson(SeqPair(d, sp.output, "input", sp.outputName)) for sp, d in zip(data, dec)) + "]\n")
+
+
 def run(argv: Optional[List[str]] = None, out=None) -> int:
     out = out or sys.stdout
     args = buildParser().parse_args(argv)
     if args.recognize_csv is not None:
         return runProfile(args, out)
     machine = loadMachine(args)
-    inference = args.loglike or args.viterbi or args.align or args.counts or args.train
-    data = collectData(args, machine, inference)
+    encoding = args.prefix_encode or args.viterbi_encode or args.random_encode
+    decoding = args.prefix_decode or args.viterbi_decode
+    inference = args.loglike or args.viterbi or args.align or args.counts or args.train or encoding or decoding
+    data = collectData(args, machine, inference, encoding, decoding)
     gotData = bool(data)
     noIO = not machine.inputAlphabet() and not machine.outputAlphabet()
     if gotData and not inference:
@@ -374,6 +486,11 @@ def run(argv: Optional[List[str]] = None, out=None) -> int:
         if args.align:
             aligned = [seqPairFromPath(machine, p, sp.inputName, sp.outputName) for sp, (v, p) in zip(data, res) if p is not None]
             emit("[" + ",\n ".join(seqPairJson(sp) for sp in aligned) + "]\n")
+
+    if encoding or decoding:
+        if world > 1:
+            raise MachineError("encoding and decoding run on one rank")
+        runCoding(args, machine, params, data, emit)
     return 0
 
 

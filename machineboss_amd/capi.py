@@ -24,12 +24,14 @@ EXPORTS = [
     "mb_machine_n_levels", "mb_machine_edge_order",
     "mb_batch_create", "mb_batch_destroy", "mb_batch_cells", "mb_batch_forward", "mb_viterbi_path_bound",
     "mb_batch_viterbi", "mb_batch_counts", "mb_fill", "mb_forward_batch", "mb_viterbi_batch", "mb_counts_batch",
-    "mb_set_kernel", "mb_set_memory_budget", "mb_release_workspace", "mb_debug_jit_source", "mb_debug_persist_plan", "mb_debug_small_source", "mb_debug_wide_retimed", "mb_debug_wide_parts", "mb_debug_wide_jit",
+    "mb_set_kernel", "mb_set_memory_budget", "mb_memory_budget", "mb_release_workspace", "mb_debug_jit_source", "mb_debug_persist_plan", "mb_debug_small_source", "mb_debug_wide_retimed", "mb_debug_wide_parts", "mb_debug_wide_jit",
     "mb_jit_stats", "mb_alloc_stats", "mb_machine_sweep_ops", "mb_set_option", "mb_get_option", "mb_log_sum_exp", "mb_log_sum_exp_n", "mb_log_inner_product",
     "mb_batch_set_envelopes", "mb_fill_env",
     "mb_comm_unique_id", "mb_comm_init", "mb_comm_destroy", "mb_allreduce_counts",
     "mb_profiles_create", "mb_profiles_destroy", "mb_profiles_forward", "mb_profile_path_bound", "mb_profiles_viterbi",
     "mb_profiles_counts", "mb_profile_fill",
+    "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
+    "mb_prefix_node_cells",
 ]
 
 _lib = None
@@ -78,6 +80,7 @@ def load():
     L.mb_counts_batch.argtypes = [vp, C.c_int64, i32p, i64p, i32p, i64p, dp, dp, dp]
     L.mb_set_kernel.argtypes = [C.c_int]
     L.mb_set_memory_budget.argtypes = [C.c_size_t]
+    L.mb_memory_budget.restype = C.c_size_t
     L.mb_batch_set_envelopes.argtypes = [vp, i64p, i32p, i32p]
     L.mb_fill_env.argtypes = [vp, C.c_int, i32p, C.c_int64, i32p, C.c_int64, C.c_int32, i32p, i32p, dp]
     L.mb_debug_jit_source.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, u32p, u32p, u16p, u16p, dp,
@@ -110,6 +113,14 @@ def load():
     L.mb_profiles_viterbi.argtypes = [vp, dp, i64p, u32p, i32p, C.c_int64]
     L.mb_profiles_counts.argtypes = [vp, dp, dp, dp]
     L.mb_profile_fill.argtypes = [vp, C.c_int, dp, C.c_int64, dp]
+    L.mb_prefix_create.restype = vp
+    L.mb_prefix_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, C.c_int64]
+    L.mb_prefix_destroy.argtypes = [vp]; L.mb_prefix_destroy.restype = None
+    L.mb_prefix_root.argtypes = [vp, C.c_int64, i64p, dp, dp]
+    L.mb_prefix_extend.argtypes = [vp, C.c_int64, i64p, i64p, i32p, i64p, dp, dp]
+    L.mb_prefix_release.argtypes = [vp, C.c_int64, i64p]
+    L.mb_prefix_free_nodes.argtypes = [vp]; L.mb_prefix_free_nodes.restype = C.c_int64
+    L.mb_prefix_node_cells.argtypes = [vp, C.c_int64, dp]
     _lib = L
     return L
 
@@ -137,6 +148,11 @@ def set_kernel(which: int):
 
 def set_memory_budget(nbytes: int):
     _check(load().mb_set_memory_budget(nbytes))
+
+
+def memory_budget() -> int:
+    """Bytes the pools of one call may take now (the explicit budget, else a share of the device)."""
+    return int(load().mb_memory_budget())
 
 
 def release_workspace():
@@ -587,3 +603,65 @@ def profile_fill(dm: DeviceMachine, mode: int, logP) -> np.ndarray:
     cells = np.empty((len(P) + 1, 2, dm.nStates), np.float64)
     _check(load().mb_profile_fill(dm.h, mode, _p(P, C.c_double), len(P), _p(cells, C.c_double)))
     return cells
+
+
+class DevicePrefix:
+    """Device-resident node lattices of prefix searches (mb_prefix*): ``outputs`` is one token sequence per search, ``logR`` the
+    machine's log((I - N)^-1) (prefixtree.logSumInTrans), ``maxNodes`` the fixed size of the node pool.  The tree is the caller's:
+    nodes are slot numbers (prefixtree.PrefixTree, docs/decoding.md)."""
+
+    def __init__(self, dm: DeviceMachine, outputs, logR, maxNodes: int):
+        self.dm = dm
+        outs = [np.asarray(o, np.int32).reshape(-1) for o in outputs]
+        self.nSeq = len(outs)
+        self.outOff = np.zeros(self.nSeq + 1, np.int64)
+        for k, o in enumerate(outs):
+            self.outOff[k + 1] = self.outOff[k] + len(o)
+        self.outTok = np.ascontiguousarray(np.concatenate(outs + [np.zeros(1, np.int32)]), np.int32)
+        R = np.ascontiguousarray(logR, np.float64)
+        assert R.shape == (dm.nStates, dm.nStates)
+        L = load()
+        self.h = L.mb_prefix_create(dm.h, self.nSeq, _p(self.outTok, C.c_int32), _p(self.outOff, C.c_int64), _p(R, C.c_double), int(maxNodes))
+        if not self.h:
+            raise MbError(L.mb_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            try:
+                _lib.mb_prefix_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    __del__ = close
+
+    def root(self, seq: int = 0) -> Tuple[int, float, float]:
+        """(node, logSeqProb, logPrefixProb) of the root of search ``seq``."""
+        n = C.c_int64(-1); a = C.c_double(); b = C.c_double()
+        _check(load().mb_prefix_root(self.h, int(seq), C.byref(n), C.byref(a), C.byref(b)))
+        return n.value, a.value, b.value
+
+    def extend(self, seq, parent, inTok) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """One launch: child i of node parent[i] (search seq[i]) by input token inTok[i]; (nodes, logSeqProb, logPrefixProb)."""
+        sq = np.ascontiguousarray(seq, np.int64); pa = np.ascontiguousarray(parent, np.int64); tk = np.ascontiguousarray(inTok, np.int32)
+        n = len(sq)
+        assert len(pa) == n and len(tk) == n
+        ch = np.empty(n, np.int64); a = np.empty(n, np.float64); b = np.empty(n, np.float64)
+        _check(load().mb_prefix_extend(self.h, n, _p(sq, C.c_int64), _p(pa, C.c_int64), _p(tk, C.c_int32), _p(ch, C.c_int64),
+                                       _p(a, C.c_double), _p(b, C.c_double)))
+        return ch, a, b
+
+    def release(self, nodes) -> None:
+        nd = np.ascontiguousarray(nodes, np.int64)
+        if len(nd):
+            _check(load().mb_prefix_release(self.h, len(nd), _p(nd, C.c_int64)))
+
+    def free_nodes(self) -> int:
+        return load().mb_prefix_free_nodes(self.h)
+
+    def node_cells(self, node: int, seq: int) -> np.ndarray:
+        """The node's lattice [outLen + 1, 2, nStates] (layer 0 = seq, 1 = prefix); ``seq`` is the node's search (for the shape)."""
+        L = int(self.outOff[seq + 1] - self.outOff[seq])
+        cells = np.empty((L + 1, 2, self.dm.nStates), np.float64)
+        _check(load().mb_prefix_node_cells(self.h, int(node), _p(cells, C.c_double)))
+        return cells

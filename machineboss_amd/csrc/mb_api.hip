@@ -15,6 +15,7 @@
 #include "mb_internal.h"
 #include "mb_jit.h"
 #include "mb_medium.h"
+#include "mb_prefix.h"
 #include "mb_profile.h"
 #include "mb_small.h"
 #include "mb_usage.h"
@@ -88,11 +89,13 @@ static int ensure_init() {
 
 // Grow-only device workspaces, kept across calls so that steady-state batch calls do no hipMalloc/hipFree
 // (a 200 GB hipMalloc costs far more than the kernels it feeds).  Slot 0/1: matrix pools, 2: halo columns.
-struct Workspace { void *p = nullptr; size_t bytes = 0; bool pinned = false; };
+struct Workspace { void *p = nullptr; size_t bytes = 0; bool pinned = false; bool held = false; };   // held: a live object owns the slot (prefix node pool)
 static const int WS_SLOTS = 16;
-static Workspace g_ws[WS_SLOTS];   // 0/1 matrix pools, 2 halo columns, 3..7 Viterbi path buffers, 8.. small-machine family
+static Workspace g_ws[WS_SLOTS];   // 0/1 matrix pools, 2 halo columns, 3..7 Viterbi path buffers, 8.. small-machine family, 15 prefix node pool
 
 static size_t cached_bytes() { size_t t = 0; for (const Workspace &w : g_ws) t += w.bytes; return t; }
+// what a call may take back from the cache: a held slot belongs to a live object
+static size_t reclaimable_bytes() { size_t t = 0; for (const Workspace &w : g_ws) if (!w.held) t += w.bytes; return t; }
 
 // A slot handed out during the current API call is pinned until the next call begins; growing one slot may release every
 // unpinned one (a Viterbi batch that needs 80 % of HBM in slot 0 must be able to reclaim the Backward pool a previous
@@ -113,7 +116,7 @@ static void ws_free_slot(Workspace &w) {
 static void ws_release_unpinned(int except) {
   for (int k = 0; k < WS_SLOTS; ++k) {
     Workspace &w = g_ws[k];
-    if (k == except || w.pinned || !w.p) continue;
+    if (k == except || w.pinned || w.held || !w.p) continue;
     ws_free_slot(w); ++g_alloc.evictions;
   }
 }
@@ -245,7 +248,7 @@ int h2d_large(void *dstDev, const void *src, size_t bytes) {
 }
 
 static void ws_release() {
-  for (Workspace &w : g_ws) ws_free_slot(w);
+  for (Workspace &w : g_ws) if (!w.held) ws_free_slot(w);
   for (SmallBlock &b : g_smallFree) (void)hipFree(b.p);
   g_smallFree.clear();
   for (int k = 0; k < 2; ++k) if (g_pinned[k]) { (void)hipHostFree(g_pinned[k]); g_pinned[k] = nullptr; }
@@ -272,7 +275,7 @@ size_t budget_bytes() {
   static double stickyFrac = 0.0;
   double frac = 0.90;
   if (const char *e = opt_env("MB_MEM_FRACTION")) { const double f = atof(e); if (f > 0.0 && f <= 0.95) frac = f; }
-  const size_t cur = (size_t)((double)(freeB + cached_bytes()) * frac);
+  const size_t cur = (size_t)((double)(freeB + reclaimable_bytes()) * frac);
   if (!sticky || frac != stickyFrac || cur < sticky || cur > sticky + sticky / 8 || !env_flag_default("MB_POOL_STICKY", 1)) { sticky = cur; stickyFrac = frac; }
   return sticky;
 }
@@ -945,6 +948,12 @@ int mb_set_kernel(int which) {
 }
 
 int mb_set_memory_budget(size_t bytes) { g_mem_budget = bytes; return 0; }
+
+size_t mb_memory_budget(void) {
+  ApiLock lock;
+  if (ensure_init()) return 0;
+  return budget_bytes();
+}
 
 int mb_release_workspace(void) {
   ApiGuard guard;
@@ -2377,6 +2386,189 @@ int mb_profile_fill(mb_machine *m, int mode, const double *logP, int64_t nRows, 
   mb_profiles_destroy(p);
   g_last_kernel = mode == MB_BACKWARD ? "k_profile_bwd<mat>" : (mode == MB_VITERBI ? "k_profile_fwd<max,mat>" : "k_profile_fwd<sum,mat>");
   return rc;
+}
+
+// ---- prefix search: node fills on the device, the tree on the host (mb_prefix.hip, docs/decoding.md) --------------------------
+static const int WS_PREFIX_POOL = 15;
+
+static void prefix_free(mb_prefix *p) {
+  sm_free(p->d_out); sm_free(p->d_rOff); sm_free(p->d_rIdx); sm_free(p->d_rVal);   // (cached by size class: steady cycles allocate nothing)
+  if (p->pool) {
+    if (p->poolIsWorkspace) g_ws[WS_PREFIX_POOL].held = false;      // the memory stays cached for the next search
+    else { (void)hipFree(p->pool); ++g_alloc.frees; }
+  }
+  delete p;
+}
+
+mb_prefix *mb_prefix_create(mb_machine *m, int64_t nSeq, const int32_t *outTok, const int64_t *outOff, const double *logSumInTrans,
+                            int64_t maxNodes) {
+  ApiGuard guard;
+  if (!m || nSeq < 1 || !outOff || !logSumInTrans || maxNodes < 1) { set_error("null argument"); return nullptr; }
+  if (ensure_init()) return nullptr;
+  if (m->S > PREFIX_MAX_STATES) { set_error("prefix search: more than " + std::to_string(PREFIX_MAX_STATES) + " states"); return nullptr; }
+  mb_prefix *p = new mb_prefix();
+  p->m = m; p->nSeq = nSeq; p->maxNodes = maxNodes;
+  p->outOff.resize(nSeq + 1);
+  for (int64_t k = 0; k <= nSeq; ++k) p->outOff[k] = outOff[k] - outOff[0];
+  for (int64_t k = 0; k < nSeq; ++k) {
+    const long long len = p->outOff[k + 1] - p->outOff[k];
+    if (len < 0 || len > 0x3fffffff) { set_error("bad output offsets"); delete p; return nullptr; }
+    p->maxOutLen = std::max(p->maxOutLen, len);
+  }
+  const long long nTok = p->outOff[nSeq];
+  const int32_t *tok = outTok ? outTok + outOff[0] : nullptr;
+  if (nTok && !tok) { set_error("null argument"); delete p; return nullptr; }
+  for (long long k = 0; k < nTok; ++k)
+    if (tok[k] < 1 || tok[k] > m->nOut) { set_error("output token " + std::to_string(tok[k]) + " outside the alphabet"); delete p; return nullptr; }
+  // R by column, -inf entries dropped; NaN or +inf is a caller's error
+  const int S = m->S;
+  std::vector<long long> rOff(S + 1, 0);
+  std::vector<int> rIdx; std::vector<double> rVal;
+  for (int s = 0; s < S; ++s) {
+    for (int q = 0; q < S; ++q) {
+      const double v = logSumInTrans[(size_t)q * S + s];
+      if (std::isnan(v) || v == INFINITY) { set_error("logSumInTrans holds NaN or +infinity"); delete p; return nullptr; }
+      if (v > -INFINITY) { rIdx.push_back(q); rVal.push_back(v); }
+    }
+    rOff[s + 1] = (long long)rIdx.size();
+  }
+  p->slotDoubles = prefix_slot_doubles(S, p->maxOutLen);
+  const double poolBytes = (double)maxNodes * (double)p->slotDoubles * 8.0;
+  const double rBytes = 12.0 * (double)rIdx.size() + 8.0 * (S + 1) + 4.0 * (double)nTok;   // R by column and the tokens count too
+  if (poolBytes + rBytes > (double)budget_bytes()) {
+    set_error("prefix search: " + std::to_string(maxNodes) + " node lattices of " + std::to_string(p->slotDoubles * 8) + " bytes and " +
+              std::to_string((long long)rBytes) + " bytes of tables exceed the device memory budget (" + std::to_string(budget_bytes()) +
+              " bytes): ask for fewer nodes (--decode-nodes)");
+    delete p; return nullptr;
+  }
+  bool ok = hip_ok(sm_alloc((void **)&p->d_out, (size_t)std::max<long long>(nTok, 1) * sizeof(int)), "hipMalloc(prefix tokens)") &&
+            hip_ok(sm_alloc((void **)&p->d_rOff, rOff.size() * sizeof(long long)), "hipMalloc(prefix R)") &&
+            hip_ok(sm_alloc((void **)&p->d_rIdx, std::max<size_t>(rIdx.size(), 1) * sizeof(int)), "hipMalloc(prefix R)") &&
+            hip_ok(sm_alloc((void **)&p->d_rVal, std::max<size_t>(rVal.size(), 1) * sizeof(double)), "hipMalloc(prefix R)");
+  ok = ok && (!nTok || hip_ok(hipMemcpy(p->d_out, tok, (size_t)nTok * sizeof(int), hipMemcpyHostToDevice), "H2D prefix tokens")) &&
+       hip_ok(hipMemcpy(p->d_rOff, rOff.data(), rOff.size() * sizeof(long long), hipMemcpyHostToDevice), "H2D prefix R") &&
+       (rIdx.empty() || (hip_ok(hipMemcpy(p->d_rIdx, rIdx.data(), rIdx.size() * sizeof(int), hipMemcpyHostToDevice), "H2D prefix R") &&
+                         hip_ok(hipMemcpy(p->d_rVal, rVal.data(), rVal.size() * sizeof(double), hipMemcpyHostToDevice), "H2D prefix R")));
+  if (ok) {
+    // the node pool: the library's cached workspace when no other live search holds it (steady create / destroy cycles allocate
+    // nothing), else an allocation of this object
+    Workspace &w = g_ws[WS_PREFIX_POOL];
+    if (!w.held) {
+      p->pool = (double *)ws_get(WS_PREFIX_POOL, (size_t)poolBytes);
+      if (p->pool) { w.held = true; p->poolIsWorkspace = true; }
+      ok = p->pool != nullptr;
+    } else {
+      ok = hip_ok(hipMalloc((void **)&p->pool, std::max<size_t>((size_t)poolBytes, 256)), "hipMalloc(prefix node pool)");
+      if (ok) { ++g_alloc.allocs; g_alloc.bytes += (size_t)poolBytes; } else p->pool = nullptr;
+    }
+  }
+  if (!ok) { prefix_free(p); return nullptr; }
+  p->slotSeq.assign((size_t)maxNodes, -1);
+  p->freeSlots.resize((size_t)maxNodes);
+  for (int64_t k = 0; k < maxNodes; ++k) p->freeSlots[(size_t)k] = maxNodes - 1 - k;   // slot 0 goes out first
+  return p;
+}
+
+void mb_prefix_destroy(mb_prefix *p) {
+  if (!p) return;
+  ApiGuard guard;
+  quiesce_streams();
+  prefix_free(p);
+}
+
+// One launch for n fills.  parent[i] < 0: entry i is the root of search seq[i] (inTok ignored).
+static int prefix_fill(mb_prefix *p, int64_t n, const int64_t *seq, const int64_t *parent, const int32_t *inTok, int64_t *childOut,
+                       double *logSeqProb, double *logPrefixProb) {
+  if (n == 0) return 0;
+  if (n > 0x7fffffff) { set_error("too many fills in one call"); return 1; }
+  const mb_machine *m = p->m;
+  for (int64_t i = 0; i < n; ++i) {
+    if (seq[i] < 0 || seq[i] >= p->nSeq) { set_error("prefix fill " + std::to_string(i) + ": no such search"); return 1; }
+    if (parent[i] >= 0) {
+      if (parent[i] >= p->maxNodes || p->slotSeq[(size_t)parent[i]] != seq[i]) { set_error("prefix fill " + std::to_string(i) + ": parent is not a live node of that search"); return 1; }
+      if (inTok[i] < 1 || inTok[i] > m->nIn) { set_error("prefix fill " + std::to_string(i) + ": input token outside the alphabet"); return 1; }
+    }
+  }
+  if ((int64_t)p->freeSlots.size() < n) {
+    set_error("prefix node pool is full (" + std::to_string(p->maxNodes) + " nodes, " + std::to_string(p->freeSlots.size()) + " free, " + std::to_string(n) + " wanted)");
+    return 1;
+  }
+  std::vector<PrefixDesc> h((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    const long long slot = p->freeSlots[p->freeSlots.size() - 1 - (size_t)i];
+    childOut[i] = slot;
+    PrefixDesc &d = h[(size_t)i];
+    d.parentBase = parent[i] >= 0 ? parent[i] * p->slotDoubles : -1;
+    d.childBase = slot * p->slotDoubles;
+    d.outBase = p->outOff[(size_t)seq[i]];
+    d.outLen = (int)(p->outOff[(size_t)seq[i] + 1] - p->outOff[(size_t)seq[i]]);
+    d.inTok = parent[i] >= 0 ? inTok[i] : 0;
+  }
+  PrefixDesc *d_desc = nullptr; double *d_res = nullptr;
+  MB_HIP(sm_alloc((void **)&d_desc, h.size() * sizeof(PrefixDesc)));
+  if (!hip_ok(sm_alloc((void **)&d_res, (size_t)n * 2 * sizeof(double)), "hipMalloc(prefix results)")) { sm_free(d_desc); return 1; }
+  std::vector<double> res((size_t)n * 2);
+  int rc = hip_ok(hipMemcpyAsync(d_desc, h.data(), h.size() * sizeof(PrefixDesc), hipMemcpyHostToDevice, g_stream), "H2D prefix descriptors") ? 0 : 1;
+  if (!rc) {
+    Timer tm;
+    tm.start();
+    const PrefixR R{p->d_rOff, p->d_rIdx, p->d_rVal};
+    rc = launch_prefix_fill(m, R, d_desc, (int)n, p->d_out, p->pool, d_res, g_stream);
+    g_last_ms += tm.stop();
+    g_last_launches = 1;
+  }
+  if (!rc && !hip_ok(hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(double), hipMemcpyDeviceToHost, g_stream), "D2H prefix results")) rc = 1;
+  if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "k_prefix_fill")) rc = 1;
+  if (rc) quiesce_streams();
+  sm_free(d_desc); sm_free(d_res);
+  g_last_kernel = "k_prefix_fill";
+  if (rc) return rc;
+  for (int64_t i = 0; i < n; ++i) {
+    p->slotSeq[(size_t)childOut[i]] = seq[i];
+    logSeqProb[i] = res[2 * (size_t)i]; logPrefixProb[i] = res[2 * (size_t)i + 1];
+  }
+  p->freeSlots.resize(p->freeSlots.size() - (size_t)n);
+  return 0;
+}
+
+int mb_prefix_root(mb_prefix *p, int64_t seq, int64_t *nodeOut, double *logSeqProb, double *logPrefixProb) {
+  ApiGuard guard;
+  if (!p || !nodeOut || !logSeqProb || !logPrefixProb) { set_error("null argument"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  const int64_t none = -1;
+  return prefix_fill(p, 1, &seq, &none, nullptr, nodeOut, logSeqProb, logPrefixProb);
+}
+
+int mb_prefix_extend(mb_prefix *p, int64_t n, const int64_t *seq, const int64_t *parent, const int32_t *inTok, int64_t *childOut,
+                     double *logSeqProb, double *logPrefixProb) {
+  ApiGuard guard;
+  if (!p || n < 0 || (n && (!seq || !parent || !inTok || !childOut || !logSeqProb || !logPrefixProb))) { set_error("null argument"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  for (int64_t i = 0; i < n; ++i)
+    if (parent[i] < 0) { set_error("prefix fill " + std::to_string(i) + ": parent is not a live node of that search"); return 1; }
+  return prefix_fill(p, n, seq, parent, inTok, childOut, logSeqProb, logPrefixProb);
+}
+
+int mb_prefix_release(mb_prefix *p, int64_t n, const int64_t *node) {
+  ApiGuard guard;
+  if (!p || n < 0 || (n && !node)) { set_error("null argument"); return 1; }
+  for (int64_t i = 0; i < n; ++i) {
+    if (node[i] < 0 || node[i] >= p->maxNodes || p->slotSeq[(size_t)node[i]] < 0) { set_error("prefix release: node " + std::to_string(node[i]) + " is not live"); return 1; }
+    for (int64_t k = 0; k < i; ++k) if (node[k] == node[i]) { set_error("prefix release: node " + std::to_string(node[i]) + " is listed twice"); return 1; }
+  }
+  for (int64_t i = 0; i < n; ++i) { p->slotSeq[(size_t)node[i]] = -1; p->freeSlots.push_back(node[i]); }
+  return 0;
+}
+
+int64_t mb_prefix_free_nodes(const mb_prefix *p) { return p ? (int64_t)p->freeSlots.size() : 0; }
+
+int mb_prefix_node_cells(mb_prefix *p, int64_t node, double *cellsOut) {
+  ApiGuard guard;
+  if (!p || !cellsOut) { set_error("null argument"); return 1; }
+  if (node < 0 || node >= p->maxNodes || p->slotSeq[(size_t)node] < 0) { set_error("prefix node " + std::to_string(node) + " is not live"); return 1; }
+  const long long k = p->slotSeq[(size_t)node];
+  const long long cells = prefix_slot_doubles(p->m->S, p->outOff[(size_t)k + 1] - p->outOff[(size_t)k]);
+  return d2h_large(cellsOut, p->pool + node * p->slotDoubles, (size_t)cells * sizeof(double));
 }
 
 }  // extern "C"

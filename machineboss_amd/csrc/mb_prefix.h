@@ -1,0 +1,50 @@
+// mb_prefix.h -- prefix-tree node fills (src/ctc.cpp:25-88 PrefixTree::Node::fill), docs/decoding.md.
+//
+// A node is an input prefix x[1..n] of one search (one output sequence y[1..L]); its lattice is (L+1) rows x 2 layers x S states:
+// layer 0 (seq) = Forward likelihood of the pair (x, y[1..j]) ending in the state, layer 1 (prefix) = likelihood of y[1..j] given
+// any input that starts with x.  Cells live at cells[((j*2)+layer)*S + d] inside the node's slot of the pool.  The device owns the
+// lattices; the tree (who is whose parent, which slots are live, the heap) is the host's.
+#pragma once
+#include <vector>
+
+#include "mb_internal.h"
+
+namespace mb {
+
+struct PrefixDesc {
+  long long parentBase;   // offset (doubles) of the parent's slot in the pool, -1: this node is a root
+  long long childBase;    // offset of the slot to fill
+  long long outBase;      // first output token of the node's search in the token array
+  int outLen;
+  int inTok;              // the node's own input token (1..nIn), 0 for a root
+};
+
+// R = log((I - N)^-1) by COLUMN: entries rOff[s]..rOff[s+1] are the finite R[p][s], p ascending (rIdx = p, rVal = R[p][s])
+struct PrefixR {
+  const long long *rOff;
+  const int *rIdx;
+  const double *rVal;
+};
+
+inline long long prefix_slot_doubles(int S, long long maxOutLen) { return 2 * (maxOutLen + 1) * (long long)S; }
+// the V row of a workgroup lives in LDS: S doubles
+constexpr int PREFIX_MAX_STATES = 160 * 1024 / 8;
+
+int launch_prefix_fill(const mb_machine *m, const PrefixR &R, const PrefixDesc *d, int n, const int *outTok, double *pool,
+                       double *result /* [2n]: logSeqProb, logPrefixProb per entry */, hipStream_t st);
+
+}  // namespace mb
+
+struct mb_prefix {
+  mb_machine *m = nullptr;
+  long long nSeq = 0, maxNodes = 0, slotDoubles = 0, maxOutLen = 0;
+  std::vector<long long> outOff;     // [nSeq+1], rebased to 0
+  int *d_out = nullptr;              // output tokens of every search
+  long long *d_rOff = nullptr;       // R by column (PrefixR)
+  int *d_rIdx = nullptr;
+  double *d_rVal = nullptr;
+  double *pool = nullptr;            // maxNodes slots of slotDoubles
+  bool poolIsWorkspace = false;      // the pool is the library's cached node-pool workspace (else an allocation of this object)
+  std::vector<long long> freeSlots;  // stack of free slots
+  std::vector<long long> slotSeq;    // [maxNodes]: search of a live slot, -1 = free
+};
