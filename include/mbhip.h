@@ -184,6 +184,13 @@ int mb_prefix_extend(mb_prefix *p, int64_t n, const int64_t *seq, const int64_t 
 int mb_prefix_release(mb_prefix *p, int64_t n, const int64_t *node);
 int64_t mb_prefix_free_nodes(const mb_prefix *p);
 int mb_prefix_node_cells(mb_prefix *p, int64_t node, double *cellsOut);
+/* The same searches against PROFILES (soft outputs) in place of token strings: search k decodes rows rowOff[k]..rowOff[k+1] of
+ * logP, rows of nOutTok + 1 log weights with column 0 the blank (the layout of mb_profiles_create; -inf allowed, NaN / +inf
+ * rejected).  The answers are those of the token search on compose(machine, profile recogniser) with an empty output, swept
+ * natively over the profile's rows (docs/decoding.md).  Every other mb_prefix_* call works on the returned object unchanged;
+ * a node's lattice is cells[((r*2) + layer)*nStates + state], r = 0..rows, layer 0 = Forward, layer 1 = prefix. */
+mb_prefix *mb_prefix_create_profiles(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff,
+                                     const double *logSumInTrans, int64_t maxNodes);
 
 /* ---- convenience wrappers over host buffers (create batch, run, destroy) ----------------------------------
  * forwardLogLike / viterbiLogLike+viterbiAlign / forwardBackwardCounts of src/api.h:20-34.                   */

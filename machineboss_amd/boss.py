@@ -3,7 +3,7 @@
     python -m machineboss_amd.boss MACHINE.json [--preset NAME] [-P params.json] [-F funcs.json] [-N constraints.json]
            [-D seqpairs.json] [--input-chars S] [--output-chars S] [--input-fasta F] [--output-fasta F]
            [--input-json F] [--output-json F] [--use-defaults] [-L] [-V] [-A] [-C] [-T] [-R width]
-           [--generate-json F] [--recognize-csv F]
+           [--generate-json F] [--recognize-csv F [--prefix-decode] [--viterbi-decode]]
            [--prefix-decode] [--prefix-encode] [--prefix-backtrack N] [--viterbi-decode] [--viterbi-encode]
            [--random-encode] [--seed N] [--decode-backend device|numpy] [--decode-nodes N]
 
@@ -16,7 +16,9 @@ transducer files / presets on one command line are COMPOSED (algebra.py = Machin
 
 ``--recognize-csv FILE`` puts a profile (a soft output sequence, src/csv.cpp) behind the machines.  The reference composes
 it as an (L+1)-state recogniser; here the composed left part, which must have an empty input alphabet, is scored natively
-against the profile (profile.py, mb_profile.hip) with -L, -V or -C, and prints what the reference prints.
+against the profile (profile.py, mb_profile.hip) with -L, -V or -C, and prints what the reference prints.  With
+``--prefix-decode`` or ``--viterbi-decode`` the left part keeps its input alphabet and the most likely INPUT given the profile is
+imputed (prefixtree.ProfilePrefixDP, k_prefix_fill_profile in mb_prefix.hip; docs/decoding.md).
 
 ``--prefix-decode`` imputes the most likely INPUT for each given output by the reference's prefix search (src/ctc.cpp), its
 node fills on the device (prefixtree.py, mb_prefix.hip, docs/decoding.md); ``--prefix-encode`` the most likely OUTPUT for each
@@ -137,7 +139,7 @@ def buildParser() -> argparse.ArgumentParser:
     ap.add_argument("--generate-chars", help="compose a generator of this sequence in front of the machine(s)")
     ap.add_argument("--recognize-chars", help="compose a recogniser of this sequence behind the machine(s)")
     ap.add_argument("--generate-json", help="compose a generator of the sequence in this JSON file ({name, sequence}) in front of the machine(s)")
-    ap.add_argument("--recognize-csv", help="score the machine(s) against this CSV profile (rightmost; with -L, -V or -C)")
+    ap.add_argument("--recognize-csv", help="score the machine(s) against this CSV profile (rightmost; with -L, -V or -C), or decode it (--prefix-decode, --viterbi-decode)")
     ap.add_argument("-P", "--params", action="append", default=[])
     ap.add_argument("-F", "--functions", action="append", default=[])
     ap.add_argument("-N", "--constraints", action="append", default=[])
@@ -275,10 +277,79 @@ def _gather_in_order(local: List[Any], n: int, rank: int, world: int, owned: Opt
     return out
 
 
+def _profileParams(args, machine: Machine) -> Dict[str, Any]:
+    params: Dict[str, Any] = {}
+    for f in args.functions:
+        params.update(json.load(open(f)))
+    for f in args.params:
+        params.update(json.load(open(f)))
+    for k, v in machine.getParamDefs(args.use_defaults).items():
+        params.setdefault(k, v)
+    return params
+
+
+def runProfileDecode(args, out) -> int:
+    """--recognize-csv with --prefix-decode / --viterbi-decode: the most likely input of the machines left of the profile given
+    the profile.  Prints what the reference prints for the composed machine, whose output tape is empty."""
+    from . import algebra, prefixtree
+    from .profile import Profile
+    if args.prefix_encode or args.viterbi_encode or args.random_encode:
+        raise MachineError("--recognize-csv cannot be encoded: the profile is an output; use --prefix-decode or --viterbi-decode")
+    if args.loglike or args.viterbi or args.counts or args.align or args.train:
+        raise MachineError("--recognize-csv decodes (--prefix-decode, --viterbi-decode) or scores (-L, -V, -C), not both in one run")
+    if args.recognize_chars is not None or args.data or args.input_chars is not None or args.output_chars is not None or \
+            args.input_fasta or args.output_fasta or args.input_json or args.output_json:
+        raise MachineError("--recognize-csv takes no other sequence data: the profile is the output to decode")
+    if _dist() is not None and _dist().get_world_size() > 1:
+        raise MachineError("--recognize-csv runs on one rank")
+    machine = loadMachine(args)
+    if not os.path.exists(args.recognize_csv):
+        raise MachineError("CSV file not found")
+    profile = Profile.fromCsv(args.recognize_csv)
+    params = _profileParams(args, machine)
+    decoded: List[List[str]] = []
+    if args.prefix_decode:
+        maxBacktrack = args.prefix_backtrack if args.prefix_backtrack is not None else prefixtree.NO_BACKTRACK_LIMIT
+        ev = EvaluatedMachine.fromMachine(machine, params)
+        decoded.append(prefixtree.decodeBatch(ev, None, maxBacktrack, args.decode_backend, args.decode_nodes, profiles=[profile])[0][0])
+    if args.viterbi_decode:
+        decoded.append(viterbiDecodeProfile(machine, profile, args.decode_backend, params))
+    for d in decoded:
+        out.write("[" + seqPairJson(SeqPair(d, [], "input", "")) + "]\n")
+    return 0
+
+
+def viterbiDecodeProfile(machine: Machine, profile, backend: str = "device", params=None) -> List[str]:
+    """--viterbi-decode against a profile: the Viterbi path of the input-silenced machine through the profile (the existing
+    profile Viterbi with paths), then the input symbols of the heaviest matching transitions of the machine itself."""
+    from . import algebra, dp
+    params = machine.getParamDefs(True) if params is None else params
+    silent = algebra.silenceInput(machine)
+    ev = EvaluatedMachine.fromMachine(silent, params)
+    P = profile.logRows(ev) if hasattr(profile, "logRows") else profile
+    if backend == "numpy":
+        from .profile import ProfileDP
+        v, edges, _ = ProfileDP(ev).viterbi(P)
+    else:
+        from . import capi
+        dm = capi.DeviceMachine(ev)
+        prof = capi.DeviceProfiles(dm, [P])
+        try:
+            ll, off, e, _ = prof.viterbi(paths=True)
+        finally:
+            prof.close(); dm.close()
+        v, edges = float(ll[0]), e[off[0]:off[1]]
+    if not v > -math.inf:
+        raise MachineError("Can't do traceback: no finite-weight paths")
+    return algebra.decodePath(dp.edgesToPath(ev, silent, edges), machine, params)
+
+
 def runProfile(args, out) -> int:
     """--recognize-csv: the machines left of the profile, composed, against the profile tape (-L / -V / -C)."""
     from . import capi, dp
     from .profile import Profile
+    if args.prefix_decode or args.viterbi_decode or args.prefix_encode or args.viterbi_encode or args.random_encode:
+        return runProfileDecode(args, out)
     if args.align or args.train:
         raise MachineError("--recognize-csv supports -L, -V and -C")
     if not (args.loglike or args.viterbi or args.counts):
@@ -295,13 +366,7 @@ def runProfile(args, out) -> int:
     if not os.path.exists(args.recognize_csv):
         raise MachineError("CSV file not found")
     profile = Profile.fromCsv(args.recognize_csv)
-    params: Dict[str, Any] = {}
-    for f in args.functions:
-        params.update(json.load(open(f)))
-    for f in args.params:
-        params.update(json.load(open(f)))
-    for k, v in machine.getParamDefs(args.use_defaults).items():
-        params.setdefault(k, v)
+    params = _profileParams(args, machine)
     ev = EvaluatedMachine.fromMachine(machine, params)
     dm = capi.DeviceMachine(ev)
     prof = capi.DeviceProfiles(dm, [profile.logRows(ev)])

@@ -31,7 +31,7 @@ EXPORTS = [
     "mb_profiles_create", "mb_profiles_destroy", "mb_profiles_forward", "mb_profile_path_bound", "mb_profiles_viterbi",
     "mb_profiles_counts", "mb_profile_fill",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
-    "mb_prefix_node_cells",
+    "mb_prefix_node_cells", "mb_prefix_create_profiles",
 ]
 
 _lib = None
@@ -115,6 +115,8 @@ def load():
     L.mb_profile_fill.argtypes = [vp, C.c_int, dp, C.c_int64, dp]
     L.mb_prefix_create.restype = vp
     L.mb_prefix_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, C.c_int64]
+    L.mb_prefix_create_profiles.restype = vp
+    L.mb_prefix_create_profiles.argtypes = [vp, C.c_int64, dp, i64p, dp, C.c_int64]
     L.mb_prefix_destroy.argtypes = [vp]; L.mb_prefix_destroy.restype = None
     L.mb_prefix_root.argtypes = [vp, C.c_int64, i64p, dp, dp]
     L.mb_prefix_extend.argtypes = [vp, C.c_int64, i64p, i64p, i32p, i64p, dp, dp]
@@ -608,20 +610,28 @@ def profile_fill(dm: DeviceMachine, mode: int, logP) -> np.ndarray:
 class DevicePrefix:
     """Device-resident node lattices of prefix searches (mb_prefix*): ``outputs`` is one token sequence per search, ``logR`` the
     machine's log((I - N)^-1) (prefixtree.logSumInTrans), ``maxNodes`` the fixed size of the node pool.  The tree is the caller's:
-    nodes are slot numbers (prefixtree.PrefixTree, docs/decoding.md)."""
+    nodes are slot numbers (prefixtree.PrefixTree, docs/decoding.md).  With ``profiles`` -- per search a [rows, nOutTok + 1] array
+    of log weights, column 0 the blank (profile.Profile.logRows) -- the searches decode soft outputs and ``outputs`` is not read."""
 
-    def __init__(self, dm: DeviceMachine, outputs, logR, maxNodes: int):
+    def __init__(self, dm: DeviceMachine, outputs, logR, maxNodes: int, profiles=None):
         self.dm = dm
-        outs = [np.asarray(o, np.int32).reshape(-1) for o in outputs]
+        if profiles is not None:
+            outs = [np.asarray(p, np.float64).reshape(-1, dm.em.nOutTok + 1) for p in profiles]
+        else:
+            outs = [np.asarray(o, np.int32).reshape(-1) for o in outputs]
         self.nSeq = len(outs)
-        self.outOff = np.zeros(self.nSeq + 1, np.int64)
+        self.outOff = np.zeros(self.nSeq + 1, np.int64)          # tokens, or rows
         for k, o in enumerate(outs):
             self.outOff[k + 1] = self.outOff[k] + len(o)
-        self.outTok = np.ascontiguousarray(np.concatenate(outs + [np.zeros(1, np.int32)]), np.int32)
         R = np.ascontiguousarray(logR, np.float64)
         assert R.shape == (dm.nStates, dm.nStates)
         L = load()
-        self.h = L.mb_prefix_create(dm.h, self.nSeq, _p(self.outTok, C.c_int32), _p(self.outOff, C.c_int64), _p(R, C.c_double), int(maxNodes))
+        if profiles is not None:
+            self.logP = np.ascontiguousarray(np.concatenate(outs + [np.zeros((1, dm.em.nOutTok + 1))]), np.float64)
+            self.h = L.mb_prefix_create_profiles(dm.h, self.nSeq, _p(self.logP, C.c_double), _p(self.outOff, C.c_int64), _p(R, C.c_double), int(maxNodes))
+        else:
+            self.outTok = np.ascontiguousarray(np.concatenate(outs + [np.zeros(1, np.int32)]), np.int32)
+            self.h = L.mb_prefix_create(dm.h, self.nSeq, _p(self.outTok, C.c_int32), _p(self.outOff, C.c_int64), _p(R, C.c_double), int(maxNodes))
         if not self.h:
             raise MbError(L.mb_last_error().decode())
 

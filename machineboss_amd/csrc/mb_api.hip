@@ -2392,7 +2392,7 @@ int mb_profile_fill(mb_machine *m, int mode, const double *logP, int64_t nRows, 
 static const int WS_PREFIX_POOL = 15;
 
 static void prefix_free(mb_prefix *p) {
-  sm_free(p->d_out); sm_free(p->d_rOff); sm_free(p->d_rIdx); sm_free(p->d_rVal);   // (cached by size class: steady cycles allocate nothing)
+  sm_free(p->d_out); sm_free(p->d_logP); sm_free(p->d_rOff); sm_free(p->d_rIdx); sm_free(p->d_rVal);   // (cached by size class: steady cycles allocate nothing)
   if (p->pool) {
     if (p->poolIsWorkspace) g_ws[WS_PREFIX_POOL].held = false;      // the memory stays cached for the next search
     else { (void)hipFree(p->pool); ++g_alloc.frees; }
@@ -2400,9 +2400,10 @@ static void prefix_free(mb_prefix *p) {
   delete p;
 }
 
-mb_prefix *mb_prefix_create(mb_machine *m, int64_t nSeq, const int32_t *outTok, const int64_t *outOff, const double *logSumInTrans,
-                            int64_t maxNodes) {
-  ApiGuard guard;
+// The searches of one object decode either token strings (outTok) or profiles (profile = true: logP, rows of nOutTok + 1 log
+// weights, outOff counting rows); everything else -- R, the pool, the free list -- is the same.
+static mb_prefix *prefix_create(mb_machine *m, int64_t nSeq, bool profile, const int32_t *outTok, const double *logP, const int64_t *outOff,
+                                const double *logSumInTrans, int64_t maxNodes) {
   if (!m || nSeq < 1 || !outOff || !logSumInTrans || maxNodes < 1) { set_error("null argument"); return nullptr; }
   if (ensure_init()) return nullptr;
   if (m->S > PREFIX_MAX_STATES) { set_error("prefix search: more than " + std::to_string(PREFIX_MAX_STATES) + " states"); return nullptr; }
@@ -2415,11 +2416,16 @@ mb_prefix *mb_prefix_create(mb_machine *m, int64_t nSeq, const int32_t *outTok, 
     if (len < 0 || len > 0x3fffffff) { set_error("bad output offsets"); delete p; return nullptr; }
     p->maxOutLen = std::max(p->maxOutLen, len);
   }
-  const long long nTok = p->outOff[nSeq];
+  const long long nTok = profile ? 0 : p->outOff[nSeq];
   const int32_t *tok = outTok ? outTok + outOff[0] : nullptr;
   if (nTok && !tok) { set_error("null argument"); delete p; return nullptr; }
   for (long long k = 0; k < nTok; ++k)
     if (tok[k] < 1 || tok[k] > m->nOut) { set_error("output token " + std::to_string(tok[k]) + " outside the alphabet"); delete p; return nullptr; }
+  const long long nVal = profile ? p->outOff[nSeq] * (m->nOut + 1) : 0;
+  const double *val = logP ? logP + outOff[0] * (m->nOut + 1) : nullptr;
+  if (nVal && !val) { set_error("null argument"); delete p; return nullptr; }
+  if (!profile_values_ok(val, nVal)) { delete p; return nullptr; }
+  p->profile = profile;
   // R by column, -inf entries dropped; NaN or +inf is a caller's error
   const int S = m->S;
   std::vector<long long> rOff(S + 1, 0);
@@ -2434,7 +2440,7 @@ mb_prefix *mb_prefix_create(mb_machine *m, int64_t nSeq, const int32_t *outTok, 
   }
   p->slotDoubles = prefix_slot_doubles(S, p->maxOutLen);
   const double poolBytes = (double)maxNodes * (double)p->slotDoubles * 8.0;
-  const double rBytes = 12.0 * (double)rIdx.size() + 8.0 * (S + 1) + 4.0 * (double)nTok;   // R by column and the tokens count too
+  const double rBytes = 12.0 * (double)rIdx.size() + 8.0 * (S + 1) + 4.0 * (double)nTok + 8.0 * (double)nVal;   // R by column and the tokens (profile rows) count too
   if (poolBytes + rBytes > (double)budget_bytes()) {
     set_error("prefix search: " + std::to_string(maxNodes) + " node lattices of " + std::to_string(p->slotDoubles * 8) + " bytes and " +
               std::to_string((long long)rBytes) + " bytes of tables exceed the device memory budget (" + std::to_string(budget_bytes()) +
@@ -2445,6 +2451,8 @@ mb_prefix *mb_prefix_create(mb_machine *m, int64_t nSeq, const int32_t *outTok, 
             hip_ok(sm_alloc((void **)&p->d_rOff, rOff.size() * sizeof(long long)), "hipMalloc(prefix R)") &&
             hip_ok(sm_alloc((void **)&p->d_rIdx, std::max<size_t>(rIdx.size(), 1) * sizeof(int)), "hipMalloc(prefix R)") &&
             hip_ok(sm_alloc((void **)&p->d_rVal, std::max<size_t>(rVal.size(), 1) * sizeof(double)), "hipMalloc(prefix R)");
+  ok = ok && (!profile || hip_ok(sm_alloc((void **)&p->d_logP, (size_t)std::max<long long>(nVal, 1) * sizeof(double)), "hipMalloc(prefix profiles)"));
+  ok = ok && (!nVal || (!h2d_large(p->d_logP, val, (size_t)nVal * sizeof(double)) && hip_ok(hipStreamSynchronize(g_stream), "H2D prefix profiles")));
   ok = ok && (!nTok || hip_ok(hipMemcpy(p->d_out, tok, (size_t)nTok * sizeof(int), hipMemcpyHostToDevice), "H2D prefix tokens")) &&
        hip_ok(hipMemcpy(p->d_rOff, rOff.data(), rOff.size() * sizeof(long long), hipMemcpyHostToDevice), "H2D prefix R") &&
        (rIdx.empty() || (hip_ok(hipMemcpy(p->d_rIdx, rIdx.data(), rIdx.size() * sizeof(int), hipMemcpyHostToDevice), "H2D prefix R") &&
@@ -2467,6 +2475,18 @@ mb_prefix *mb_prefix_create(mb_machine *m, int64_t nSeq, const int32_t *outTok, 
   p->freeSlots.resize((size_t)maxNodes);
   for (int64_t k = 0; k < maxNodes; ++k) p->freeSlots[(size_t)k] = maxNodes - 1 - k;   // slot 0 goes out first
   return p;
+}
+
+mb_prefix *mb_prefix_create(mb_machine *m, int64_t nSeq, const int32_t *outTok, const int64_t *outOff, const double *logSumInTrans,
+                            int64_t maxNodes) {
+  ApiGuard guard;
+  return prefix_create(m, nSeq, false, outTok, nullptr, outOff, logSumInTrans, maxNodes);
+}
+
+mb_prefix *mb_prefix_create_profiles(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff, const double *logSumInTrans,
+                                     int64_t maxNodes) {
+  ApiGuard guard;
+  return prefix_create(m, nProfiles, true, nullptr, logP, rowOff, logSumInTrans, maxNodes);
 }
 
 void mb_prefix_destroy(mb_prefix *p) {
@@ -2513,15 +2533,16 @@ static int prefix_fill(mb_prefix *p, int64_t n, const int64_t *seq, const int64_
     Timer tm;
     tm.start();
     const PrefixR R{p->d_rOff, p->d_rIdx, p->d_rVal};
-    rc = launch_prefix_fill(m, R, d_desc, (int)n, p->d_out, p->pool, d_res, g_stream);
+    rc = p->profile ? launch_prefix_fill_profile(m, R, d_desc, (int)n, p->d_logP, p->pool, d_res, g_stream)
+                    : launch_prefix_fill(m, R, d_desc, (int)n, p->d_out, p->pool, d_res, g_stream);
     g_last_ms += tm.stop();
     g_last_launches = 1;
   }
   if (!rc && !hip_ok(hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(double), hipMemcpyDeviceToHost, g_stream), "D2H prefix results")) rc = 1;
-  if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "k_prefix_fill")) rc = 1;
+  if (!rc && !hip_ok(hipStreamSynchronize(g_stream), p->profile ? "k_prefix_fill_profile" : "k_prefix_fill")) rc = 1;
   if (rc) quiesce_streams();
   sm_free(d_desc); sm_free(d_res);
-  g_last_kernel = "k_prefix_fill";
+  g_last_kernel = p->profile ? "k_prefix_fill_profile" : "k_prefix_fill";
   if (rc) return rc;
   for (int64_t i = 0; i < n; ++i) {
     p->slotSeq[(size_t)childOut[i]] = seq[i];

@@ -14,8 +14,8 @@ namespace mb {
 struct PrefixDesc {
   long long parentBase;   // offset (doubles) of the parent's slot in the pool, -1: this node is a root
   long long childBase;    // offset of the slot to fill
-  long long outBase;      // first output token of the node's search in the token array
-  int outLen;
+  long long outBase;      // first output token of the node's search in the token array (profile searches: its first row)
+  int outLen;             // number of output tokens (rows)
   int inTok;              // the node's own input token (1..nIn), 0 for a root
 };
 
@@ -29,9 +29,14 @@ struct PrefixR {
 inline long long prefix_slot_doubles(int S, long long maxOutLen) { return 2 * (maxOutLen + 1) * (long long)S; }
 // the V row of a workgroup lives in LDS: S doubles
 constexpr int PREFIX_MAX_STATES = 160 * 1024 / 8;
+// against profiles N[r-1], Xn[r-1] and the row's nOut + 1 weights sit beside it: 3 S + nOut + 1 doubles
+constexpr size_t PREFIX_PROFILE_MAX_LDS = 160 * 1024;
 
 int launch_prefix_fill(const mb_machine *m, const PrefixR &R, const PrefixDesc *d, int n, const int *outTok, double *pool,
                        double *result /* [2n]: logSeqProb, logPrefixProb per entry */, hipStream_t st);
+// the same against profiles: logP holds rows of nOut + 1 log weights (column 0 the blank), outBase / outLen of a descriptor count rows
+int launch_prefix_fill_profile(const mb_machine *m, const PrefixR &R, const PrefixDesc *d, int n, const double *logP, double *pool,
+                               double *result, hipStream_t st);
 
 }  // namespace mb
 
@@ -40,6 +45,8 @@ struct mb_prefix {
   long long nSeq = 0, maxNodes = 0, slotDoubles = 0, maxOutLen = 0;
   std::vector<long long> outOff;     // [nSeq+1], rebased to 0
   int *d_out = nullptr;              // output tokens of every search
+  bool profile = false;              // the searches decode profiles: outOff counts rows of d_logP, d_out is unused
+  double *d_logP = nullptr;          // [rows][nOut + 1] log weights of every search's profile, column 0 the blank
   long long *d_rOff = nullptr;       // R by column (PrefixR)
   int *d_rIdx = nullptr;
   double *d_rVal = nullptr;

@@ -113,4 +113,113 @@ int launch_prefix_fill(const mb_machine *m, const PrefixR &R, const PrefixDesc *
   return hip_ok(hipGetLastError(), "k_prefix_fill") ? 0 : 1;
 }
 
+// The same node against a PROFILE P[0..L) (rows of nOut + 1 log weights, column 0 the blank) in place of y: the token search on
+// compose(M, profile recogniser) with an empty output, swept over rows r = 0..L and M's own states (docs/decoding.md).  As in
+// k_profile_fwd a row has two stages: N, the mass that has arrived at the row -- only there may the blank fire -- and W, the
+// mass after M's output-less moves; the composition fixes that order (the recogniser waits), so a blank and an output-less move
+// are not counted in both orders.
+//
+//   An[r][d] = [root, r = 0, d = 0] (+) sum_{t: s->d, in = a, out = o} Pa.W[r-1][s] + w_t + P[r-1][o]
+//   Aw[r][d] = sum_{t: s->d, in = a, out = eps} Pa.W[r][s] + w_t
+//   N[r][d]  = An[r][d] (+) (N[r-1][d] + P[r-1][0]) (+) sum_{t: s->d, in = eps, out = o} W[r-1][s] + w_t + P[r-1][o]
+//   W[r][d]  = Aw[r][d] (+) N[r][d] (+) sum_{silent t: s->d, s < d} W[r][s] + w_t
+//   Xn[r][d] = An[r][d] (+) (Xn[r-1][d] + P[r-1][0]) (+) sum_{t: s->d, any in, out = o} Y[r-1][s] + w_t + P[r-1][o]
+//   X[r][d]  = Aw[r][d] (+) Xn[r][d]
+//   Y[r][s]  = logsum_p X[r][p] + R[p][s];   logSeqProb = W[L][S-1],  logPrefixProb = Y[L][S-1]
+//
+// Layer 0 of a slot is W, layer 1 is X.  The phases of a row are those of k_prefix_fill: the Y product into LDS, the middle phase,
+// the silent levels.  N and Xn are read by the next row only, and only by the lane that wrote them: they live in LDS beside Y
+// (3 S doubles in all) and are not stored.  The row's nOut + 1 weights go into LDS while the product runs, one load each per row;
+// a symbol of weight -inf is skipped as a whole (the branch is uniform over the workgroup).  The terms of a cell keep one order
+// -- the node's own symbol, the blank, then the edges by output symbol -- so a fill gives the same bits from run to run.
+__global__ __launch_bounds__(PX_THREADS) void k_prefix_fill_profile(DevMachine m, PrefixR R, const PrefixDesc *__restrict__ descs,
+                                                                    const double *__restrict__ logP, double *pool, double *__restrict__ result) {
+  extern __shared__ double px_V[];             // Y[r-1], N[r-1], Xn[r-1] (S doubles each), then the row's weights (nOut + 1)
+  const PrefixDesc nd = descs[blockIdx.x];
+  const int S = m.S, K = m.K, C = m.nOut + 1, L = nd.outLen, a = nd.inTok;
+  double *px_N = px_V + S, *px_Xn = px_N + S, *px_P = px_Xn + S;
+  const bool root = nd.parentBase < 0;
+  const double *par = root ? nullptr : pool + nd.parentBase;
+  double *cells = pool + nd.childBase;
+  const double *P = logP + nd.outBase * C;
+  for (int r = 0; r <= L; ++r) {
+    double *W = cells + (long long)r * 2 * S, *X = W + S;
+    const double *Wprev = W - 2 * S, *Xprev = W - S;       // (read for r > 0 only)
+    if (r) {
+      for (int c = threadIdx.x; c < C; c += blockDim.x) px_P[c] = P[(long long)(r - 1) * C + c];
+      for (int s = threadIdx.x; s < S; s += blockDim.x) px_V[s] = px_column(R, s, Xprev);
+      __syncthreads();
+    }
+    for (int d = threadIdx.x; d < S; d += blockDim.x) {
+      const int row0 = d * K;
+      double An = (root && r == 0 && d == 0) ? 0.0 : -INFINITY, Aw = -INFINITY;
+      if (!root) {
+        const double *pq = par + (long long)r * 2 * S;
+        for (int e = m.inOff[row0 + a * C], e1 = m.inOff[row0 + a * C + 1]; e < e1; ++e) Aw = lse2_exact(Aw, pq[m.inSrc[e]] + m.inW[e]);
+        if (r) {
+          pq -= 2 * S;
+          for (int o = 1; o < C; ++o) {
+            const double po = px_P[o];
+            if (!(po > -INFINITY)) continue;
+            for (int e = m.inOff[row0 + a * C + o], e1 = m.inOff[row0 + a * C + o + 1]; e < e1; ++e) An = lse2_exact(An, (pq[m.inSrc[e]] + m.inW[e]) + po);
+          }
+        }
+      }
+      double pre = An, acc = An;                           // Xn and N
+      if (r) {
+        const double blank = px_P[0];
+        acc = lse2_exact(acc, px_N[d] + blank);
+        pre = lse2_exact(pre, px_Xn[d] + blank);
+        for (int o = 1; o < C; ++o) {
+          const double po = px_P[o];
+          if (!(po > -INFINITY)) continue;
+          for (int e = m.inOff[row0 + o], e1 = m.inOff[row0 + o + 1]; e < e1; ++e) acc = lse2_exact(acc, (Wprev[m.inSrc[e]] + m.inW[e]) + po);
+          for (int i = 0; i <= m.nIn; ++i)
+            for (int e = m.inOff[row0 + i * C + o], e1 = m.inOff[row0 + i * C + o + 1]; e < e1; ++e) pre = lse2_exact(pre, (px_V[m.inSrc[e]] + m.inW[e]) + po);
+        }
+      }
+      px_N[d] = acc;                                       // (this lane's own entries: nobody else reads them)
+      px_Xn[d] = pre;
+      X[d] = lse2_exact(Aw, pre);
+      W[d] = lse2_exact(Aw, acc);
+    }
+    __syncthreads();
+    for (int lev = 1; lev < m.nLevF; ++lev) {          // level 0 has no silent edge coming in: its cells are final
+      const int l0 = m.levFOff[lev], ns = m.levFOff[lev + 1] - l0;
+      for (int k = threadIdx.x; k < ns; k += blockDim.x) {
+        const int q = m.levFState[l0 + k];
+        double acc = W[q];
+        for (int e = m.inOff[q * K], e1 = m.inOff[q * K + 1]; e < e1; ++e) {
+          const int s = (int)m.inSrc[e];
+          if (s >= q) continue;                         // as the token sweeps: a silent self-loop never fires
+          acc = lse2_exact(acc, W[s] + m.inW[e]);
+        }
+        W[q] = acc;
+      }
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x == 0) {
+    const double *last = cells + (long long)L * 2 * S;
+    result[2 * blockIdx.x] = last[S - 1];
+    result[2 * blockIdx.x + 1] = px_column(R, S - 1, last + S);      // Y[L][S-1]: the only column of the last product that is needed
+  }
+}
+
+int launch_prefix_fill_profile(const mb_machine *m, const PrefixR &R, const PrefixDesc *d, int n, const double *logP, double *pool,
+                               double *result, hipStream_t st) {
+  if (n <= 0) return 0;
+  const size_t lds = ((size_t)3 * m->S + m->nOut + 1) * sizeof(double);
+  static size_t ldsAllowed = 64 * 1024;      // as launch_prefix_fill: asked for once, and only when a machine needs it
+  if (lds > ldsAllowed) {
+    if (lds > PREFIX_PROFILE_MAX_LDS) { set_error("prefix search against profiles: 3 x states + output symbols doubles exceed the LDS of a workgroup (about 6 800 states)"); return 1; }
+    if (!hip_ok(hipFuncSetAttribute((const void *)&k_prefix_fill_profile, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PREFIX_PROFILE_MAX_LDS),
+                "k_prefix_fill_profile: raising the LDS limit for a machine of more than 2 700 states")) return 1;
+    ldsAllowed = PREFIX_PROFILE_MAX_LDS;
+  }
+  const int threads = std::min(PX_THREADS, std::max(64, (m->S + 63) / 64 * 64));
+  k_prefix_fill_profile<<<dim3(n), dim3(threads), lds, st>>>(m->dev, R, d, logP, pool, result);
+  return hip_ok(hipGetLastError(), "k_prefix_fill_profile") ? 0 : 1;
+}
+
 }  // namespace mb

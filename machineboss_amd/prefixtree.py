@@ -124,13 +124,83 @@ class PrefixDP:
         return cells, float(cells[L, 0, S - 1]), lpp
 
 
+class ProfilePrefixDP(PrefixDP):
+    """The node fill against a PROFILE (rows of output-symbol log weights plus a blank, profile.Profile.logRows) in place of the
+    output string: the prefix search on compose(M, profile recogniser) with an empty output, swept natively over rows r = 0..L
+    and M's own S states (docs/decoding.md, "Decoding against a profile").  As in profile.ProfileDP a row has two stages: N, the
+    mass that has ARRIVED at the row (only there may the blank fire), and W, the mass after M's output-less moves -- the order the
+    composition fixes, so that a blank and an output-less move of M are not counted in both orders:
+
+        An[r][d] = [root, r = 0, d = 0] (+) sum_{t: s->d, in = a, out = o} Pa.W[r-1][s] + w_t + P[r-1][o]
+        Aw[r][d] = sum_{t: s->d, in = a, out = eps} Pa.W[r][s] + w_t
+        N[r][d]  = An[r][d] (+) (N[r-1][d] + P[r-1][0]) (+) sum_{t: s->d, in = eps, out = o} W[r-1][s] + w_t + P[r-1][o]
+        W[r][d]  = Aw[r][d] (+) N[r][d] (+) sum_{silent t: s->d, s < d} W[r][s] + w_t
+        Xn[r][d] = An[r][d] (+) (Xn[r-1][d] + P[r-1][0]) (+) sum_{t: s->d, any in, out = o} Y[r-1][s] + w_t + P[r-1][o]
+        X[r][d]  = Aw[r][d] (+) Xn[r][d]
+        Y[r][s]  = logsum_p X[r][p] + R[p][s]
+        logSeqProb = W[L][S-1],     logPrefixProb = Y[L][S-1]
+
+    ``fill(P, parentCells, a)`` -> (cells[L+1][2][S], logSeqProb, logPrefixProb); layer 0 = W, layer 1 = X."""
+
+    def __init__(self, em: EvaluatedMachine, logR: Optional[np.ndarray] = None):
+        super().__init__(em, logR)
+        none = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0), np.zeros(0, np.int64))
+
+        def emitting(sel):
+            parts = [self._by[k] + (np.full(len(self._by[k][0]), k[1], np.int64),) for k in sorted(self._by) if k[1] > 0 and sel(k[0])]
+            return tuple(np.concatenate(c) for c in zip(*parts)) if parts else none
+        self._emitIn = [emitting(lambda i, a=a: i == a) for a in range(em.nInTok + 1)]      # [a]: in = a, out = o > 0 (src, dst, w, o)
+        self._emitAny = emitting(lambda i: True)
+        self._all = np.arange(self.S, dtype=np.int64)
+
+    def fill(self, P, parent: Optional[np.ndarray] = None, a: int = 0) -> Tuple[np.ndarray, float, float]:
+        P = np.asarray(P, np.float64).reshape(-1, self.em.nOutTok + 1)
+        if np.isnan(P).any() or (P == math.inf).any():
+            raise MachineError("profile weight is NaN or +infinity")
+        L, S = len(P), self.S
+        cells = np.full((L + 1, 2, S), _NEG)
+        Y = N = Xn = np.full(S, _NEG)
+        for r in range(L + 1):
+            Pr = P[r - 1] if r else None
+            An, Aw = np.full(S, _NEG), np.full(S, _NEG)
+            if parent is None:
+                if r == 0:
+                    An[0] = 0.0
+            else:
+                s, d, w = self._edges(a, 0)
+                Aw = _lse_fold(Aw, d, parent[r, 0][s] + w)
+                if r:
+                    s, d, w, o = self._emitIn[a]
+                    An = _lse_fold(An, d, (parent[r - 1, 0][s] + w) + Pr[o])
+            if r:
+                s, d, w, o = self._emitIn[0]
+                N = _lse_fold(An, np.concatenate([self._all, d]), np.concatenate([N + Pr[0], (cells[r - 1, 0][s] + w) + Pr[o]]))
+                s, d, w, o = self._emitAny
+                Xn = _lse_fold(An, np.concatenate([self._all, d]), np.concatenate([Xn + Pr[0], (Y[s] + w) + Pr[o]]))
+            else:
+                N = Xn = An
+            sq, px = _lse_fold(Aw, self._all, N), _lse_fold(Aw, self._all, Xn)
+            if self._levels:
+                s, d, w = self._by[(0, 0)]
+                for lvl in self._levels:
+                    sq = _lse_fold(sq, d[lvl], sq[s[lvl]] + w[lvl])
+            cells[r, 0], cells[r, 1] = sq, px
+            Y = self.columnSums(px)
+        return cells, float(cells[L, 0, S - 1]), float(Y[S - 1])
+
+
 # ---- backends: who keeps the lattices ----------------------------------------------------------------------------------------
 class NumpyNodes:
-    """Node lattices on the host, filled by PrefixDP; the same interface and the same fixed pool size as the device backend."""
+    """Node lattices on the host, filled by PrefixDP (token outputs) or ProfilePrefixDP (``profiles``: one [rows, nOutTok + 1]
+    array of log weights per search); the same interface and the same fixed pool size as the device backend."""
 
-    def __init__(self, em: EvaluatedMachine, outputs: Sequence[Sequence[int]], logR: np.ndarray, maxNodes: int):
-        self.dp = PrefixDP(em, logR)
-        self.outputs = [np.asarray(o, np.int64) for o in outputs]
+    def __init__(self, em: EvaluatedMachine, outputs: Optional[Sequence[Sequence[int]]], logR: np.ndarray, maxNodes: int, profiles=None):
+        if profiles is not None:
+            self.dp = ProfilePrefixDP(em, logR)
+            self.outputs = [np.asarray(p, np.float64).reshape(-1, em.nOutTok + 1) for p in profiles]
+        else:
+            self.dp = PrefixDP(em, logR)
+            self.outputs = [np.asarray(o, np.int64) for o in outputs]
         self.maxNodes = int(maxNodes)
         self.cells: Dict[int, np.ndarray] = {}
         self._free = list(range(self.maxNodes - 1, -1, -1))
@@ -167,14 +237,19 @@ class NumpyNodes:
         self.cells.clear()
 
 
-def makeNodes(em: EvaluatedMachine, outputs, backend: str = "device", maxNodes: Optional[int] = None, logR: Optional[np.ndarray] = None):
+def makeNodes(em: EvaluatedMachine, outputs=None, backend: str = "device", maxNodes: Optional[int] = None, logR: Optional[np.ndarray] = None,
+              profiles=None):
     """The lattice store of ``len(outputs)`` searches: "numpy" (host, PrefixDP) or "device" (capi.DevicePrefix, mb_prefix.hip).
+    With ``profiles`` (one [rows, nOutTok + 1] array of log weights per search, column 0 the blank) the searches decode soft
+    outputs and ``outputs`` is not read.
     ``maxNodes`` None: DEFAULT_MAX_NODES per search, on the device no more than half the memory budget holds (a slot is
     2 (maxL + 1) S doubles, so long outputs on large machines get fewer); a number is taken as it is and fails if it does not fit."""
     R = logSumInTrans(em) if logR is None else logR
+    if profiles is not None:
+        outputs = [np.asarray(p, np.float64).reshape(-1, em.nOutTok + 1) for p in profiles]     # (only their lengths are read below)
     want = DEFAULT_MAX_NODES * max(1, len(outputs)) if maxNodes is None else int(maxNodes)
     if backend == "numpy":
-        return NumpyNodes(em, outputs, R, want)
+        return NumpyNodes(em, outputs, R, want, profiles)
     if backend != "device":
         raise MachineError("unknown prefix search backend %s" % backend)
     from . import capi, dp
@@ -182,7 +257,7 @@ def makeNodes(em: EvaluatedMachine, outputs, backend: str = "device", maxNodes: 
     if maxNodes is None:
         slot = 16 * (max([len(o) for o in outputs] + [0]) + 1) * em.nStates
         want = max(len(outputs) * (em.nInTok + 1), min(want, capi.memory_budget() // 2 // slot))
-    return capi.DevicePrefix(dm, outputs, R, want)
+    return capi.DevicePrefix(dm, outputs, R, want, profiles)
 
 
 # ---- std::push_heap / pop_heap / make_heap as libstdc++ orders them: which of two equal prefixes comes out first is theirs -------
@@ -244,6 +319,10 @@ class _Node:
 _less = lambda x, y: x.logPrefixProb < y.logPrefixProb
 
 
+def _logRows(em: EvaluatedMachine, profile) -> np.ndarray:
+    return profile.logRows(em) if hasattr(profile, "logRows") else np.asarray(profile, np.float64).reshape(-1, em.nOutTok + 1)
+
+
 class PrefixTree:
     """One search (src/ctc.cpp:112-395) over a lattice store.  The order of operations is the reference's and decides ties:
     children are made for input tokens 1..nIn in order, a child enters the heap only if its prefix probability exceeds the best
@@ -267,6 +346,14 @@ class PrefixTree:
                   maxNodes: Optional[int] = None) -> "PrefixTree":
         """PrefixTree(machine, outSym, maxBacktrack): a search with a lattice store of its own."""
         t = cls(em, makeNodes(em, [em.outputTokenizer.tokenize(list(outSym))], backend, maxNodes), 0, maxBacktrack, owner=True)
+        t.start()
+        return t
+
+    @classmethod
+    def forProfile(cls, em: EvaluatedMachine, profile, maxBacktrack: int = NO_BACKTRACK_LIMIT, backend: str = "device",
+                   maxNodes: Optional[int] = None) -> "PrefixTree":
+        """A search for the most likely input given a PROFILE: a profile.Profile, or its [rows, nOutTok + 1] log-weight table."""
+        t = cls(em, makeNodes(em, None, backend, maxNodes, profiles=[_logRows(em, profile)]), 0, maxBacktrack, owner=True)
         t.start()
         return t
 
@@ -397,13 +484,18 @@ class PrefixTree:
         return self.em.inputTokenizer.detokenize(self.sampleTokSeq(rng))
 
 
-def decodeBatch(em: EvaluatedMachine, outputs: Sequence[Sequence[str]], maxBacktrack: int = NO_BACKTRACK_LIMIT, backend: str = "device",
-                maxNodes: Optional[int] = None) -> Tuple[List[List[str]], List[PrefixTree]]:
+def decodeBatch(em: EvaluatedMachine, outputs: Optional[Sequence[Sequence[str]]], maxBacktrack: int = NO_BACKTRACK_LIMIT, backend: str = "device",
+                maxNodes: Optional[int] = None, profiles=None) -> Tuple[List[List[str]], List[PrefixTree]]:
     """doPrefixSearch for every output at once, in lock step: per round every unfinished search names the prefix it extends, and
     ONE ``extend`` (one device launch) fills the children of all of them.  A search sees exactly the fills, in the order, that it
-    would see alone, so its answer and its node count are those of a single search.  Returns (decoded inputs, the searches)."""
-    toks = [em.outputTokenizer.tokenize(list(o)) for o in outputs]
-    nodes = makeNodes(em, toks, backend, maxNodes)
+    would see alone, so its answer and its node count are those of a single search.  Returns (decoded inputs, the searches).
+    ``profiles`` (profile.Profile objects or log-weight tables) in place of ``outputs`` decodes soft outputs."""
+    if profiles is not None:
+        toks = [_logRows(em, p) for p in profiles]
+        nodes = makeNodes(em, None, backend, maxNodes, profiles=toks)
+    else:
+        toks = [em.outputTokenizer.tokenize(list(o)) for o in outputs]
+        nodes = makeNodes(em, toks, backend, maxNodes)
     trees = [PrefixTree(em, nodes, k, maxBacktrack) for k in range(len(toks))]
     try:
         for t in trees:

@@ -12,7 +12,13 @@ The share of a fill spent in the V product: build a second library with the prod
     MB_BUILD_EXTRA_FLAGS=-DMB_PREFIX_SKIP_PRODUCT python -m machineboss_amd.build --force   (then keep that libmbhip.so under another name)
     MBHIP_LIBRARY=that.so python scripts/bench_decode.py --no-numpy --no-search
 
-and compare device_ms; its cells are meaningless, only its time is read."""
+and compare device_ms; its cells are meaningless, only its time is read.
+
+    python scripts/bench_decode.py --profile [--out profiles/decode_profile_bench.json]
+
+fills the roots' children against PROFILES instead (k_prefix_fill_profile): soft versions of the same outputs, 0.86 on the encoded
+symbol, 0.04 on the others and 0.02 on the blank, each jittered by up to a tenth.  Beside it the same launches through the token
+kernel on the arg-max string of each profile, for a cost per row side by side."""
 import argparse
 import json
 import os
@@ -39,8 +45,70 @@ def outputs(m, n, L, seed=1):
     return outs[:n]
 
 
+def soften(em, toks, seed=2):
+    rng = np.random.RandomState(seed)
+    profs = []
+    for y in toks:
+        W = np.full((len(y), em.nOutTok + 1), 0.04)
+        W[:, 0] = 0.02
+        W[np.arange(len(y)), np.asarray(y, np.int64)] = 0.86
+        profs.append(np.log(W * rng.uniform(0.9, 1.1, W.shape)))
+    return profs
+
+
+def time_children(dev, B, nIn):
+    """Best of three launches that fill the nIn children of every search's root: (device ms, wall ms)."""
+    roots = [dev.root(k)[0] for k in range(B)]
+    seq = [k for k in range(B) for _ in range(nIn)]
+    par = [roots[k] for k in range(B) for _ in range(nIn)]
+    tok = [t for _ in range(B) for t in range(1, nIn + 1)]
+    ch, _, _ = dev.extend(seq, par, tok)                  # warm-up
+    dev.release(ch)
+    best_ms, best_wall = 1e30, 1e30
+    for _ in range(3):
+        t0 = time.perf_counter()
+        ch, _, _ = dev.extend(seq, par, tok)
+        best_wall = min(best_wall, (time.perf_counter() - t0) * 1e3)
+        best_ms = min(best_ms, capi.last_device_ms())
+        dev.release(ch)
+    return best_ms, best_wall
+
+
+def profile_rows(args, m, em, dm, R):
+    S, nIn = em.nStates, em.nInTok
+    rows = []
+    for L in [int(x) for x in args.lengths.split(",")]:
+        for B in [int(x) for x in args.batches.split(",")]:
+            toks = [em.outputTokenizer.tokenize(o) for o in outputs(m, B, L)]
+            profs = soften(em, toks)
+            hard = [np.argmax(p[:, 1:], axis=1) + 1 for p in profs]
+            dev = capi.DevicePrefix(dm, None, R, B * (1 + 3 * nIn), profs)
+            p_ms, p_wall = time_children(dev, B, nIn)
+            dev.close()
+            dev = capi.DevicePrefix(dm, hard, R, B * (1 + 3 * nIn))
+            t_ms, t_wall = time_children(dev, B, nIn)
+            dev.close()
+            fills = B * nIn
+            row = {"L": L, "searches": B, "fills_per_launch": fills, "profile_device_ms": round(p_ms, 3), "profile_wall_ms": round(p_wall, 3),
+                   "profile_us_per_row": round(p_ms * 1e3 / (L + 1), 2), "profile_fills_per_s": round(fills / (p_ms * 1e-3), 1),
+                   "token_device_ms": round(t_ms, 3), "token_us_per_row": round(t_ms * 1e3 / (L + 1), 2),
+                   "profile_vs_token": round(p_ms / t_ms, 2)}
+            if not args.no_numpy:
+                dp = prefixtree.ProfilePrefixDP(em, R)
+                root = dp.fill(profs[0])[0]
+                t0 = time.perf_counter()
+                for t in range(1, nIn + 1):
+                    dp.fill(profs[0], root, t)
+                row["numpy_ms_per_fill"] = round((time.perf_counter() - t0) * 1e3 / nIn, 2)
+                row["speedup_vs_numpy"] = round(row["numpy_ms_per_fill"] * fills / p_ms, 1)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--profile", action="store_true", help="fills against profiles (k_prefix_fill_profile) beside the token kernel")
     ap.add_argument("--out")
     ap.add_argument("--lengths", default="200,2000")
     ap.add_argument("--batches", default="1,64")
@@ -53,7 +121,9 @@ def main():
     R = prefixtree.logSumInTrans(em)
     dm = capi.DeviceMachine(em)
     rows = []
-    for L in [int(x) for x in args.lengths.split(",")]:
+    if args.profile:
+        rows = profile_rows(args, m, em, dm, R)
+    for L in [] if args.profile else [int(x) for x in args.lengths.split(",")]:
         for B in [int(x) for x in args.batches.split(",")]:
             outs = outputs(m, B, L)
             toks = [em.outputTokenizer.tokenize(o) for o in outs]
