@@ -162,6 +162,22 @@ int mb_profiles_viterbi(mb_profiles *p, double *loglike, int64_t *pathOff, uint3
 int mb_profiles_counts(mb_profiles *p, double *counts, double *loglikeSum, double *loglike);
 int mb_profile_fill(mb_machine *m, int mode, const double *logP, int64_t nRows, double *cellsOut);
 
+/* CTC-merged profiles (`--recognize-merge-csv`, src/csv.cpp:20-46): the semantics of compose(M, transpose(CSVProfile::mergingMachine()))
+ * with empty tapes -- a column repeated in consecutive rows is one symbol, and only a blank separates two equal symbols -- swept
+ * natively over (rows + 1) x 2 x (nCols + 1) planes x nStates (docs/profile_tapes.md, "Merged (CTC) profiles").  Row r =
+ * logP[r*(nCols+1) ...]: column 0 the blank, column c = 1..nCols the log weight of a CSV column whose output token is colTok[c-1]
+ * (1..nOutTok; two columns may share a token and stay two columns).  One column map per batch.  Plane 0 = the last row took the
+ * blank (or no row yet), plane c = the last row took column c.  mb_profiles_forward / _viterbi / _counts / _destroy and
+ * mb_profile_path_bound work on the returned object unchanged; blank and repeat rows are not path edges.  Viterbi keeps the first
+ * maximum: after the silent moves "no move", then silent edges in `incoming` order; into plane 0 the planes ascending; into plane c
+ * the repeat, then the emitting edges of colTok[c-1] in `incoming` order, each from the lowest plane k != c attaining its maximum; at
+ * the end the planes ascending.  Materialised lattices: cells[(((row*2) + layer)*(nCols+1) + plane)*nStates + state];
+ * mb_profile_fill_merged: cellsOut[(nRows+1)*2*(nCols+1)*nStates].  nCols < 1, a token outside 1..nOutTok, NaN / +inf: an error. */
+mb_profiles *mb_profiles_create_merged(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff,
+                                       int32_t nCols, const int32_t *colTok);
+int mb_profile_fill_merged(mb_machine *m, int mode, const double *logP, int64_t nRows, int32_t nCols, const int32_t *colTok,
+                           double *cellsOut);
+
 /* ---- prefix search: imputing the input tape (--prefix-decode / --prefix-encode / --random-encode) -------------------------------
  * The node fill of the reference's PrefixTree (src/ctc.cpp:25-88) on the device, the tree and its heap on the host
  * (docs/decoding.md).  An mb_prefix holds nSeq searches (output sequence k = outTok[outOff[k]..outOff[k+1]), tokens 1..nOutTok)

@@ -3,7 +3,7 @@
     python -m machineboss_amd.boss MACHINE.json [--preset NAME] [-P params.json] [-F funcs.json] [-N constraints.json]
            [-D seqpairs.json] [--input-chars S] [--output-chars S] [--input-fasta F] [--output-fasta F]
            [--input-json F] [--output-json F] [--use-defaults] [-L] [-V] [-A] [-C] [-T] [-R width]
-           [--generate-json F] [--recognize-csv F [--prefix-decode] [--viterbi-decode]]
+           [--generate-json F] [--recognize-csv F [--prefix-decode] [--viterbi-decode]] [--recognize-merge-csv F [--viterbi-decode]]
            [--prefix-decode] [--prefix-encode] [--prefix-backtrack N] [--viterbi-decode] [--viterbi-encode]
            [--random-encode] [--seed N] [--decode-backend device|numpy] [--decode-nodes N]
 
@@ -19,6 +19,9 @@ it as an (L+1)-state recogniser; here the composed left part, which must have an
 against the profile (profile.py, mb_profile.hip) with -L, -V or -C, and prints what the reference prints.  With
 ``--prefix-decode`` or ``--viterbi-decode`` the left part keeps its input alphabet and the most likely INPUT given the profile is
 imputed (prefixtree.ProfilePrefixDP, k_prefix_fill_profile in mb_prefix.hip; docs/decoding.md).
+``--recognize-merge-csv FILE`` reads the same file as a CTC profile (CSVProfile::mergingMachine, src/csv.cpp:20-46): a symbol
+repeated in consecutive rows is one symbol, and only a blank separates two equal symbols.  It goes wherever ``--recognize-csv``
+goes except with ``--prefix-decode`` (profile.MergedProfileDP, mb_profile_merge.hip; docs/profile_tapes.md).
 
 ``--prefix-decode`` imputes the most likely INPUT for each given output by the reference's prefix search (src/ctc.cpp), its
 node fills on the device (prefixtree.py, mb_prefix.hip, docs/decoding.md); ``--prefix-encode`` the most likely OUTPUT for each
@@ -140,6 +143,7 @@ def buildParser() -> argparse.ArgumentParser:
     ap.add_argument("--recognize-chars", help="compose a recogniser of this sequence behind the machine(s)")
     ap.add_argument("--generate-json", help="compose a generator of the sequence in this JSON file ({name, sequence}) in front of the machine(s)")
     ap.add_argument("--recognize-csv", help="score the machine(s) against this CSV profile (rightmost; with -L, -V or -C), or decode it (--prefix-decode, --viterbi-decode)")
+    ap.add_argument("--recognize-merge-csv", help="the same against a CTC profile: a symbol repeated in consecutive rows is one symbol, and only a blank separates two equal symbols (not with --prefix-decode)")
     ap.add_argument("-P", "--params", action="append", default=[])
     ap.add_argument("-F", "--functions", action="append", default=[])
     ap.add_argument("-N", "--constraints", action="append", default=[])
@@ -302,6 +306,8 @@ def runProfileDecode(args, out) -> int:
         raise MachineError("--recognize-csv takes no other sequence data: the profile is the output to decode")
     if _dist() is not None and _dist().get_world_size() > 1:
         raise MachineError("--recognize-csv runs on one rank")
+    if args.merge and args.prefix_decode:
+        raise MachineError("--recognize-merge-csv cannot be prefix-decoded: there is no merged prefix fill; use --viterbi-decode")
     machine = loadMachine(args)
     if not os.path.exists(args.recognize_csv):
         raise MachineError("CSV file not found")
@@ -313,27 +319,32 @@ def runProfileDecode(args, out) -> int:
         ev = EvaluatedMachine.fromMachine(machine, params)
         decoded.append(prefixtree.decodeBatch(ev, None, maxBacktrack, args.decode_backend, args.decode_nodes, profiles=[profile])[0][0])
     if args.viterbi_decode:
-        decoded.append(viterbiDecodeProfile(machine, profile, args.decode_backend, params))
+        decoded.append(viterbiDecodeProfile(machine, profile, args.decode_backend, params, args.merge))
     for d in decoded:
         out.write("[" + seqPairJson(SeqPair(d, [], "input", "")) + "]\n")
     return 0
 
 
-def viterbiDecodeProfile(machine: Machine, profile, backend: str = "device", params=None) -> List[str]:
+def viterbiDecodeProfile(machine: Machine, profile, backend: str = "device", params=None, merge: bool = False) -> List[str]:
     """--viterbi-decode against a profile: the Viterbi path of the input-silenced machine through the profile (the existing
-    profile Viterbi with paths), then the input symbols of the heaviest matching transitions of the machine itself."""
+    profile Viterbi with paths), then the input symbols of the heaviest matching transitions of the machine itself.  ``merge``:
+    the profile is CTC-merged (--recognize-merge-csv; a Profile, or a pair (logP, colTok) as Profile.mergeRows returns)."""
     from . import algebra, dp
     params = machine.getParamDefs(True) if params is None else params
     silent = algebra.silenceInput(machine)
     ev = EvaluatedMachine.fromMachine(silent, params)
-    P = profile.logRows(ev) if hasattr(profile, "logRows") else profile
+    colTok = None
+    if merge:
+        P, colTok = _mergedRows(profile, ev) if hasattr(profile, "mergeRows") else profile
+    else:
+        P = profile.logRows(ev) if hasattr(profile, "logRows") else profile
     if backend == "numpy":
-        from .profile import ProfileDP
-        v, edges, _ = ProfileDP(ev).viterbi(P)
+        from .profile import MergedProfileDP, ProfileDP
+        v, edges, _ = (MergedProfileDP(ev, colTok) if merge else ProfileDP(ev)).viterbi(P)
     else:
         from . import capi
         dm = capi.DeviceMachine(ev)
-        prof = capi.DeviceProfiles(dm, [P])
+        prof = capi.DeviceProfiles(dm, [P], colTok)
         try:
             ll, off, e, _ = prof.viterbi(paths=True)
         finally:
@@ -344,10 +355,26 @@ def viterbiDecodeProfile(machine: Machine, profile, backend: str = "device", par
     return algebra.decodePath(dp.edgesToPath(ev, silent, edges), machine, params)
 
 
+def _mergedRows(profile, ev):
+    """Profile.mergeRows for the device: (logP, colTok) with at least one column.  A header none of whose symbols the machine
+    emits leaves only the blank; a column of weight 0 for the machine's first token says the same."""
+    import numpy as np
+    P, colTok = profile.mergeRows(ev)
+    if len(colTok) == 0 and ev.nOutTok:
+        P, colTok = np.concatenate([P, np.full((len(P), 1), -math.inf)], axis=1), np.array([1], np.int32)
+    return P, colTok
+
+
 def runProfile(args, out) -> int:
-    """--recognize-csv: the machines left of the profile, composed, against the profile tape (-L / -V / -C)."""
+    """--recognize-csv / --recognize-merge-csv: the machines left of the profile, composed, against the profile tape (-L / -V /
+    -C).  With --decode-backend numpy a merged profile is swept by the numpy restatement (profile.MergedProfileDP)."""
     from . import capi, dp
     from .profile import Profile
+    args.merge = args.recognize_merge_csv is not None
+    if args.merge:
+        if args.recognize_csv is not None:
+            raise MachineError("--recognize-csv and --recognize-merge-csv cannot be combined: the profile is one file, read one way")
+        args.recognize_csv = args.recognize_merge_csv
     if args.prefix_decode or args.viterbi_decode or args.prefix_encode or args.viterbi_encode or args.random_encode:
         return runProfileDecode(args, out)
     if args.align or args.train:
@@ -368,8 +395,16 @@ def runProfile(args, out) -> int:
     profile = Profile.fromCsv(args.recognize_csv)
     params = _profileParams(args, machine)
     ev = EvaluatedMachine.fromMachine(machine, params)
+    if args.merge and not ev.nOutTok:
+        raise MachineError("--recognize-merge-csv needs a machine with an output alphabet")
+    if args.merge and args.decode_backend == "numpy":
+        return _runMergedNumpy(args, out, machine, params, ev, profile)
     dm = capi.DeviceMachine(ev)
-    prof = capi.DeviceProfiles(dm, [profile.logRows(ev)])
+    if args.merge:
+        P, colTok = _mergedRows(profile, ev)
+        prof = capi.DeviceProfiles(dm, [P], colTok)
+    else:
+        prof = capi.DeviceProfiles(dm, [profile.logRows(ev)])
     if args.loglike:
         out.write('[["","",%s]]\n' % fmt(prof.forward(capi.MB_ROLLING)[0]))
     if args.counts:
@@ -381,6 +416,26 @@ def runProfile(args, out) -> int:
     if args.viterbi:
         out.write('[["","",%s]]\n' % fmt(prof.viterbi(paths=False)[0][0]))
     prof.close(); dm.close()
+    return 0
+
+
+def _runMergedNumpy(args, out, machine: Machine, params, ev, profile) -> int:
+    """-L / -C / -V of a merged profile through the numpy restatement, printed as runProfile prints the device's."""
+    from . import dp
+    from .profile import MergedProfileDP
+    P, colTok = profile.mergeRows(ev)
+    mdp = MergedProfileDP(ev, colTok)
+    if args.loglike:
+        out.write('[["","",%s]]\n' % fmt(mdp.forward(P)[0]))
+    if args.counts:
+        counts = dp.MachineCounts(ev)
+        c, ll = mdp.counts(P)
+        counts._flat += c
+        counts.loglike += ll
+        pc = counts.paramCounts(machine, params)
+        out.write("{" + ",".join('"%s":%s' % (escaped(k), "%g" % pc[k]) for k in sorted(pc)) + "}\n")
+    if args.viterbi:
+        out.write('[["","",%s]]\n' % fmt(mdp.forward(P, "max")[0]))
     return 0
 
 
@@ -480,7 +535,7 @@ def runCoding(args, machine: Machine, params, data: List[SeqPair], emit) -> None
 def run(argv: Optional[List[str]] = None, out=None) -> int:
     out = out or sys.stdout
     args = buildParser().parse_args(argv)
-    if args.recognize_csv is not None:
+    if args.recognize_csv is not None or args.recognize_merge_csv is not None:
         return runProfile(args, out)
     machine = loadMachine(args)
     encoding = args.prefix_encode or args.viterbi_encode or args.random_encode

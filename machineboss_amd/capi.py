@@ -29,7 +29,7 @@ EXPORTS = [
     "mb_batch_set_envelopes", "mb_fill_env",
     "mb_comm_unique_id", "mb_comm_init", "mb_comm_destroy", "mb_allreduce_counts",
     "mb_profiles_create", "mb_profiles_destroy", "mb_profiles_forward", "mb_profile_path_bound", "mb_profiles_viterbi",
-    "mb_profiles_counts", "mb_profile_fill",
+    "mb_profiles_counts", "mb_profile_fill", "mb_profiles_create_merged", "mb_profile_fill_merged",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
     "mb_prefix_node_cells", "mb_prefix_create_profiles",
 ]
@@ -113,6 +113,9 @@ def load():
     L.mb_profiles_viterbi.argtypes = [vp, dp, i64p, u32p, i32p, C.c_int64]
     L.mb_profiles_counts.argtypes = [vp, dp, dp, dp]
     L.mb_profile_fill.argtypes = [vp, C.c_int, dp, C.c_int64, dp]
+    L.mb_profiles_create_merged.restype = vp
+    L.mb_profiles_create_merged.argtypes = [vp, C.c_int64, dp, i64p, C.c_int32, i32p]
+    L.mb_profile_fill_merged.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_int32, i32p, dp]
     L.mb_prefix_create.restype = vp
     L.mb_prefix_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, C.c_int64]
     L.mb_prefix_create_profiles.restype = vp
@@ -545,18 +548,26 @@ class DeviceBatch:
 
 class DeviceProfiles:
     """Device-resident batch of profile tapes (mb_profiles*) for a machine with an empty input tape: per profile a
-    [rows, nOutTok + 1] array of log weights, column 0 = the blank (profile.Profile.logRows)."""
+    [rows, nOutTok + 1] array of log weights, column 0 = the blank (profile.Profile.logRows).  With ``colTok`` the profiles are
+    CTC-merged (mb_profiles_create_merged): per profile a [rows, nCols + 1] array, column 0 the blank and column c a CSV column
+    whose output token is colTok[c - 1] (profile.Profile.mergeRows); every method works the same."""
 
-    def __init__(self, dm: DeviceMachine, profiles):
+    def __init__(self, dm: DeviceMachine, profiles, colTok=None):
         self.dm = dm
-        rows = [np.asarray(p, np.float64).reshape(-1, dm.em.nOutTok + 1) for p in profiles]
+        self.colTok = None if colTok is None else np.ascontiguousarray(np.asarray(colTok).reshape(-1), np.int32)
+        width = dm.em.nOutTok + 1 if colTok is None else len(self.colTok) + 1
+        rows = [np.asarray(p, np.float64).reshape(-1, width) for p in profiles]
         self.nProfiles = len(rows)
         self.rowOff = np.zeros(self.nProfiles + 1, np.int64)
         for k, r in enumerate(rows):
             self.rowOff[k + 1] = self.rowOff[k] + len(r)
-        self.logP = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((1, dm.em.nOutTok + 1)), np.float64)
+        self.logP = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((1, width)), np.float64)
         L = load()
-        self.h = L.mb_profiles_create(dm.h, self.nProfiles, _p(self.logP, C.c_double), _p(self.rowOff, C.c_int64))
+        if colTok is None:
+            self.h = L.mb_profiles_create(dm.h, self.nProfiles, _p(self.logP, C.c_double), _p(self.rowOff, C.c_int64))
+        else:
+            self.h = L.mb_profiles_create_merged(dm.h, self.nProfiles, _p(self.logP, C.c_double), _p(self.rowOff, C.c_int64),
+                                                 len(self.colTok), _p(self.colTok, C.c_int32))
         if not self.h:
             raise MbError(L.mb_last_error().decode())
 
@@ -604,6 +615,16 @@ def profile_fill(dm: DeviceMachine, mode: int, logP) -> np.ndarray:
     P = np.ascontiguousarray(np.asarray(logP, np.float64).reshape(-1, dm.em.nOutTok + 1))
     cells = np.empty((len(P) + 1, 2, dm.nStates), np.float64)
     _check(load().mb_profile_fill(dm.h, mode, _p(P, C.c_double), len(P), _p(cells, C.c_double)))
+    return cells
+
+
+def profile_fill_merged(dm: DeviceMachine, mode: int, logP, colTok) -> np.ndarray:
+    """One merged profile's lattice [rows + 1, 2, nCols + 1, nStates] (layer 0 = arrived at the row, 1 = after the silent moves;
+    plane 0 = the last row took the blank, plane c = it took column c)."""
+    ct = np.ascontiguousarray(np.asarray(colTok).reshape(-1), np.int32)
+    P = np.ascontiguousarray(np.asarray(logP, np.float64).reshape(-1, len(ct) + 1))
+    cells = np.empty((len(P) + 1, 2, len(ct) + 1, dm.nStates), np.float64)
+    _check(load().mb_profile_fill_merged(dm.h, mode, _p(P, C.c_double), len(P), len(ct), _p(ct, C.c_int32), _p(cells, C.c_double)))
     return cells
 
 

@@ -17,6 +17,7 @@
 #include "mb_medium.h"
 #include "mb_prefix.h"
 #include "mb_profile.h"
+#include "mb_profile_merge.h"
 #include "mb_small.h"
 #include "mb_usage.h"
 #include "mb_wide.h"
@@ -2135,6 +2136,38 @@ static bool profile_chunks(const mb_profiles *p, const std::function<double(long
   return true;
 }
 
+// Plain and CTC-merged profiles (p->nCols > 0, mb_profile_merge.hip) share the entry points below: the merged lattice has nCols + 1
+// planes of the plain one, its own kernels and its own rolling state.
+static long long pf_planes(const mb_profiles *p) { return p->nCols ? p->nCols + 1 : 1; }
+static long long pf_width(const mb_profiles *p) { return p->nCols ? p->nCols + 1 : p->m->nOut + 1; }   // doubles of a row
+static long long pf_cells(const mb_profiles *p, long long nRows) { return profile_cells(p->m->S, nRows) * pf_planes(p); }
+static MergeMap pf_map(const mb_profiles *p) { return MergeMap{p->nCols, p->d_colTok}; }
+// doubles of global scratch a workgroup of the Forward / Viterbi (mat: materialised) or of the rolling Backward sweep needs (0: LDS)
+static long long pf_fwd_scratch(const mb_profiles *p, bool mat) {
+  const int S = p->m->S;
+  if (!p->nCols) return mat || profile_lds_bytes(S) ? 0 : 3LL * S;
+  return profile_merge_fwd_lds(S, p->nCols, mat) ? 0 : profile_merge_ring(S, p->nCols);
+}
+static long long pf_bwd_scratch(const mb_profiles *p) {
+  const int S = p->m->S;
+  if (!p->nCols) return profile_lds_bytes(S) ? 0 : 3LL * S;
+  return profile_merge_bwd_lds(S, p->nCols) ? 0 : profile_merge_ring(S, p->nCols);
+}
+static int pf_fwd(const mb_profiles *p, int mode, bool mat, const ProfDesc *d, int n, double *pool, double *scratch, double *loglike) {
+  return p->nCols ? launch_profile_merge_fwd(p->m, pf_map(p), mode, mat, d, n, p->d_logP, pool, scratch, loglike, g_stream)
+                  : launch_profile_fwd(p->m, mode, mat, d, n, p->d_logP, pool, scratch, loglike, g_stream);
+}
+static int pf_bwd(const mb_profiles *p, bool mat, const ProfDesc *d, int n, double *pool, const double *fwdPool, double *scratch,
+                  double *loglike, double *part, long long nTrans) {
+  return p->nCols ? launch_profile_merge_bwd(p->m, pf_map(p), mat, d, n, p->d_logP, pool, fwdPool, scratch, loglike, part, nTrans, g_stream)
+                  : launch_profile_bwd(p->m, mat, d, n, p->d_logP, pool, fwdPool, scratch, loglike, part, nTrans, g_stream);
+}
+static int pf_traceback(const mb_profiles *p, const ProfDesc *d, int n, const double *pool, uint32_t *edges, int32_t *rows, long long *len) {
+  return p->nCols ? launch_profile_merge_traceback(p->m, pf_map(p), d, n, p->d_logP, pool, edges, rows, len, g_stream)
+                  : launch_profile_traceback(p->m, d, n, p->d_logP, pool, edges, rows, len, g_stream);
+}
+static const char *pf_name(const mb_profiles *p, const char *plain, const char *merged) { return p->nCols ? merged : plain; }
+
 // descriptors of profiles [p0, p1): lattices and traceback slots packed from 0; returns the pool doubles and path entries
 static int profile_descs(const mb_profiles *p, long long p0, long long p1, ProfDesc **d_out, long long *cells, long long *paths) {
   std::vector<ProfDesc> h((size_t)(p1 - p0));
@@ -2142,7 +2175,7 @@ static int profile_descs(const mb_profiles *p, long long p0, long long p1, ProfD
   for (long long k = p0; k < p1; ++k) {
     ProfDesc &d = h[(size_t)(k - p0)];
     d.rowBase = p->rowOff[k]; d.nRows = (int)(p->rowOff[k + 1] - p->rowOff[k]); d.cellBase = c; d.pathBase = t; d.pad = 0;
-    c += profile_cells(p->m->S, d.nRows);
+    c += pf_cells(p, d.nRows);
     t += profile_path_bound(p->m->nLevF, d.nRows);
   }
   if (cells) *cells = c;
@@ -2153,19 +2186,18 @@ static int profile_descs(const mb_profiles *p, long long p0, long long p1, ProfD
   return 0;
 }
 
-static int profile_scratch(const mb_machine *m, long long n, double **scratch) {
+static int profile_scratch(long long perGroup, long long n, double **scratch) {
   *scratch = nullptr;
-  if (profile_lds_bytes(m->S) || n == 0) return 0;
-  *scratch = (double *)ws_get(1, (size_t)n * 3 * m->S * sizeof(double));
+  if (!perGroup || n == 0) return 0;
+  *scratch = (double *)ws_get(1, (size_t)n * perGroup * sizeof(double));
   return *scratch ? 0 : 1;
 }
 
 // Forward (MB_FORWARD) or Viterbi scores without paths (MB_VITERBI); mat: through the materialised lattice
 static int profiles_scores(mb_profiles *p, int mode, bool mat, double *loglike) {
-  const mb_machine *m = p->m;
-  const double rollBytes = profile_lds_bytes(m->S) ? 0.0 : 24.0 * m->S;
+  const double rollBytes = 8.0 * pf_fwd_scratch(p, mat);
   std::vector<Chunk> chunks;
-  if (!profile_chunks(p, [&](long long k) { return mat ? 8.0 * profile_cells(m->S, p->rowOff[k + 1] - p->rowOff[k]) : rollBytes; }, chunks)) return 1;
+  if (!profile_chunks(p, [&](long long k) { return (mat ? 8.0 * pf_cells(p, p->rowOff[k + 1] - p->rowOff[k]) : 0.0) + rollBytes; }, chunks)) return 1;
   double *d_ll = nullptr;
   MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
   int rc = 0;
@@ -2177,10 +2209,10 @@ static int profiles_scores(mb_profiles *p, int mode, bool mat, double *loglike) 
     const long long np = c.p1 - c.p0;
     double *pool = nullptr, *scratch = nullptr;
     if (mat) { pool = (double *)ws_get(0, (size_t)std::max<long long>(cells, 1) * sizeof(double)); if (!pool) rc = 1; }
-    else rc = profile_scratch(m, np, &scratch);
+    if (!rc) rc = profile_scratch(pf_fwd_scratch(p, mat), np, &scratch);
     if (!rc) {
       tm.start();
-      rc = launch_profile_fwd(m, mode, mat, d, (int)np, p->d_logP, pool, scratch, d_ll + c.p0, g_stream);
+      rc = pf_fwd(p, mode, mat, d, (int)np, pool, scratch, d_ll + c.p0);
       g_last_ms += tm.stop();
       ++g_last_launches;
     }
@@ -2190,7 +2222,8 @@ static int profiles_scores(mb_profiles *p, int mode, bool mat, double *loglike) 
   }
   if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
   sm_free(d_ll);
-  g_last_kernel = mode == MB_VITERBI ? (mat ? "k_profile_fwd<max,mat>" : "k_profile_fwd<max,rolling>") : (mat ? "k_profile_fwd<sum,mat>" : "k_profile_fwd<sum,rolling>");
+  g_last_kernel = mode == MB_VITERBI ? (mat ? pf_name(p, "k_profile_fwd<max,mat>", "k_profile_merge_fwd<max,mat>") : pf_name(p, "k_profile_fwd<max,rolling>", "k_profile_merge_fwd<max,rolling>"))
+                                     : (mat ? pf_name(p, "k_profile_fwd<sum,mat>", "k_profile_merge_fwd<sum,mat>") : pf_name(p, "k_profile_fwd<sum,rolling>", "k_profile_merge_fwd<sum,rolling>"));
   return rc;
 }
 
@@ -2198,12 +2231,12 @@ static int profiles_scores(mb_profiles *p, int mode, bool mat, double *loglike) 
 
 extern "C" {
 
-mb_profiles *mb_profiles_create(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff) {
-  ApiGuard guard;
+// nCols = 0: plain profiles, rows of nOutTok + 1 doubles; nCols > 0: merged, rows of nCols + 1 doubles and the column map colTok
+static mb_profiles *profiles_create(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff, int nCols, const int32_t *colTok) {
   if (!m || nProfiles < 0 || (nProfiles > 0 && !rowOff)) { set_error("null argument"); return nullptr; }
   if (ensure_init()) return nullptr;
   mb_profiles *p = new mb_profiles();
-  p->m = m; p->n = nProfiles;
+  p->m = m; p->n = nProfiles; p->nCols = nCols;
   p->rowOff.assign((size_t)nProfiles + 1, 0);
   for (long long k = 0; k < nProfiles; ++k) {
     const long long len = rowOff[k + 1] - rowOff[k];
@@ -2211,20 +2244,43 @@ mb_profiles *mb_profiles_create(mb_machine *m, int64_t nProfiles, const double *
     p->rowOff[(size_t)k + 1] = p->rowOff[(size_t)k] + len;
   }
   p->totalRows = p->rowOff.back();
-  const long long C = m->nOut + 1, nv = p->totalRows * C;
+  const long long C = nCols ? nCols + 1 : m->nOut + 1, nv = p->totalRows * C;
   const double *v0 = logP ? logP + (nProfiles ? rowOff[0] * C : 0) : nullptr;
   if (nv && !v0) { set_error("null argument"); delete p; return nullptr; }
   if (!profile_values_ok(v0, nv)) { delete p; return nullptr; }
   if (!hip_ok(hipMalloc((void **)&p->d_logP, (size_t)std::max<long long>(nv, 1) * sizeof(double)), "hipMalloc(profiles)")) { delete p; return nullptr; }
+  if (nCols && (!hip_ok(hipMalloc((void **)&p->d_colTok, (size_t)nCols * sizeof(int)), "hipMalloc(profile columns)") ||
+                !hip_ok(hipMemcpyAsync(p->d_colTok, colTok, (size_t)nCols * sizeof(int), hipMemcpyHostToDevice, g_stream), "H2D profile columns"))) { mb_profiles_destroy(p); return nullptr; }
   if (nv && h2d_large(p->d_logP, v0, (size_t)nv * sizeof(double))) { mb_profiles_destroy(p); return nullptr; }
   if (!hip_ok(hipStreamSynchronize(g_stream), "H2D profiles")) { mb_profiles_destroy(p); return nullptr; }
   return p;
+}
+
+static bool merge_map_ok(const mb_machine *m, int32_t nCols, const int32_t *colTok) {
+  if (!m) { set_error("null argument"); return false; }
+  if (nCols < 1 || nCols > 0xffff) { set_error("merged profiles need 1..65535 columns"); return false; }
+  if (!colTok) { set_error("null argument"); return false; }
+  for (int c = 0; c < nCols; ++c)
+    if (colTok[c] < 1 || colTok[c] > m->nOut) { set_error("column " + std::to_string(c + 1) + ": token " + std::to_string(colTok[c]) + " is outside 1..nOutTok"); return false; }
+  return true;
+}
+
+mb_profiles *mb_profiles_create(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff) {
+  ApiGuard guard;
+  return profiles_create(m, nProfiles, logP, rowOff, 0, nullptr);
+}
+
+mb_profiles *mb_profiles_create_merged(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff, int32_t nCols, const int32_t *colTok) {
+  ApiGuard guard;
+  if (!merge_map_ok(m, nCols, colTok)) return nullptr;
+  return profiles_create(m, nProfiles, logP, rowOff, nCols, colTok);
 }
 
 void mb_profiles_destroy(mb_profiles *p) {
   ApiGuard guard;
   if (!p) return;
   if (p->d_logP) (void)hipFree(p->d_logP);
+  if (p->d_colTok) (void)hipFree(p->d_colTok);
   delete p;
 }
 
@@ -2248,7 +2304,8 @@ int mb_profiles_viterbi(mb_profiles *p, double *loglike, int64_t *pathOff, uint3
   if (!pathEdges || !pathOff) return profiles_scores(p, MB_VITERBI, false, loglike);
   const mb_machine *m = p->m;
   std::vector<Chunk> chunks;
-  auto bytes = [&](long long k) { const long long L = p->rowOff[k + 1] - p->rowOff[k]; return 8.0 * profile_cells(m->S, L) + 8.0 * profile_path_bound(m->nLevF, L); };
+  const long long vScratch = pf_fwd_scratch(p, true);
+  auto bytes = [&](long long k) { const long long L = p->rowOff[k + 1] - p->rowOff[k]; return 8.0 * pf_cells(p, L) + 8.0 * profile_path_bound(m->nLevF, L) + 8.0 * vScratch; };
   if (!profile_chunks(p, bytes, chunks)) return 1;
   double *d_ll = nullptr;
   long long *d_len = nullptr;
@@ -2269,11 +2326,12 @@ int mb_profiles_viterbi(mb_profiles *p, double *loglike, int64_t *pathOff, uint3
     double *pool = (double *)ws_get(0, (size_t)std::max<long long>(cells, 1) * sizeof(double));
     uint32_t *d_e = (uint32_t *)ws_get(3, (size_t)std::max<long long>(paths, 1) * sizeof(uint32_t));
     int32_t *d_r = (int32_t *)ws_get(4, (size_t)std::max<long long>(paths, 1) * sizeof(int32_t));
-    if (!pool || !d_e || !d_r) rc = 1;
+    double *scratch = nullptr;
+    if (!pool || !d_e || !d_r || profile_scratch(vScratch, np, &scratch)) rc = 1;
     if (!rc) {
       tm.start();
-      rc = launch_profile_fwd(m, MB_VITERBI, true, d, (int)np, p->d_logP, pool, nullptr, d_ll + c.p0, g_stream);
-      if (!rc) rc = launch_profile_traceback(m, d, (int)np, p->d_logP, pool, d_e, d_r, d_len + c.p0, g_stream);
+      rc = pf_fwd(p, MB_VITERBI, true, d, (int)np, pool, scratch, d_ll + c.p0);
+      if (!rc) rc = pf_traceback(p, d, (int)np, pool, d_e, d_r, d_len + c.p0);
       g_last_ms += tm.stop();
       ++g_last_launches;
     }
@@ -2299,7 +2357,7 @@ int mb_profiles_viterbi(mb_profiles *p, double *loglike, int64_t *pathOff, uint3
   }
   if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
   sm_free(d_ll); sm_free(d_len);
-  g_last_kernel = "k_profile_fwd<max,mat>";
+  g_last_kernel = pf_name(p, "k_profile_fwd<max,mat>", "k_profile_merge_fwd<max,mat>");
   return rc;
 }
 
@@ -2309,9 +2367,9 @@ int mb_profiles_counts(mb_profiles *p, double *counts, double *loglikeSum, doubl
   g_last_ms = 0.0; g_last_launches = 0;
   const mb_machine *m = p->m;
   const long long nT = m->nTrans;
-  const double rollBytes = profile_lds_bytes(m->S) ? 0.0 : 24.0 * m->S;
+  const long long PL = pf_planes(p), cScratch = std::max(pf_fwd_scratch(p, true), pf_bwd_scratch(p));   // one buffer serves both sweeps
   std::vector<Chunk> chunks;
-  auto bytes = [&](long long k) { return 8.0 * profile_cells(m->S, p->rowOff[k + 1] - p->rowOff[k]) + 8.0 * nT + rollBytes; };
+  auto bytes = [&](long long k) { return 8.0 * pf_cells(p, p->rowOff[k + 1] - p->rowOff[k]) + 8.0 * nT * PL + 8.0 * cScratch; };
   if (!profile_chunks(p, bytes, chunks)) return 1;
   double *d_ll = nullptr, *d_bll = nullptr, *d_cc = nullptr;
   MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
@@ -2326,15 +2384,16 @@ int mb_profiles_counts(mb_profiles *p, double *counts, double *loglikeSum, doubl
     if ((rc = profile_descs(p, c.p0, c.p1, &d, &cells, nullptr))) break;
     const long long np = c.p1 - c.p0;
     double *pool = (double *)ws_get(0, (size_t)std::max<long long>(cells, 1) * sizeof(double));
-    double *part = (double *)ws_get(2, (size_t)std::max<long long>(np * nT, 1) * sizeof(double));
+    double *part = (double *)ws_get(2, (size_t)std::max<long long>(np * PL * nT, 1) * sizeof(double));
     double *scratch = nullptr;
-    if (!pool || !part || profile_scratch(m, np, &scratch)) rc = 1;
+    if (!pool || !part || profile_scratch(cScratch, np, &scratch)) rc = 1;
+    if (!rc && np * PL > 0x7fffffff) { set_error("too many profile planes in one chunk"); rc = 1; }
     if (!rc) {
       tm.start();
-      rc = launch_profile_fwd(m, MB_FORWARD, true, d, (int)np, p->d_logP, pool, nullptr, d_ll + c.p0, g_stream);
-      if (!rc && nT) rc = hip_ok(hipMemsetAsync(part, 0, (size_t)np * nT * sizeof(double), g_stream), "memset(counts)") ? 0 : 1;
-      if (!rc) rc = launch_profile_bwd(m, false, d, (int)np, p->d_logP, nullptr, pool, scratch, d_bll + c.p0, part, nT, g_stream);
-      if (!rc) rc = launch_profile_sum_counts(part, (int)np, nT, d_cc, g_stream);
+      rc = pf_fwd(p, MB_FORWARD, true, d, (int)np, pool, scratch, d_ll + c.p0);
+      if (!rc && nT) rc = hip_ok(hipMemsetAsync(part, 0, (size_t)np * PL * nT * sizeof(double), g_stream), "memset(counts)") ? 0 : 1;
+      if (!rc) rc = pf_bwd(p, false, d, (int)np, nullptr, pool, scratch, d_bll + c.p0, part, nT);
+      if (!rc) rc = launch_profile_sum_counts(part, (int)(np * PL), nT, d_cc, g_stream);   // merged: over profiles, then planes
       g_last_ms += tm.stop();
       ++g_last_launches;
     }
@@ -2347,7 +2406,7 @@ int mb_profiles_counts(mb_profiles *p, double *counts, double *loglikeSum, doubl
   std::vector<double> hll((size_t)p->n);
   if (!rc && p->n && !hip_ok(hipMemcpy(hll.data(), d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
   sm_free(d_ll); sm_free(d_bll); sm_free(d_cc);
-  g_last_kernel = "k_profile_bwd<counts>";
+  g_last_kernel = pf_name(p, "k_profile_bwd<counts>", "k_profile_merge_bwd<counts>");
   if (rc) return rc;
   for (long long e = 0; e < nT; ++e) counts[e] += total[(size_t)e];
   double s = 0.0;
@@ -2356,36 +2415,48 @@ int mb_profiles_counts(mb_profiles *p, double *counts, double *loglikeSum, doubl
   return 0;
 }
 
-int mb_profile_fill(mb_machine *m, int mode, const double *logP, int64_t nRows, double *cellsOut) {
-  ApiGuard guard;
+static int profile_fill(mb_machine *m, int mode, const double *logP, int64_t nRows, int nCols, const int32_t *colTok, double *cellsOut) {
   if (!m || !cellsOut || nRows < 0 || (nRows && !logP)) { set_error("null argument"); return 1; }
   if (mode != MB_FORWARD && mode != MB_VITERBI && mode != MB_BACKWARD) { set_error("unknown fill mode"); return 1; }
   if (ensure_init()) return 1;
   g_last_ms = 0.0; g_last_launches = 0;
   const int64_t off[2] = {0, nRows};
-  mb_profiles *p = mb_profiles_create(m, 1, logP, off);
+  mb_profiles *p = profiles_create(m, 1, logP, off, nCols, colTok);
   if (!p) return 1;
   ProfDesc *d = nullptr;
   long long cells = 0;
   int rc = profile_descs(p, 0, 1, &d, &cells, nullptr);
-  double *d_ll = nullptr;
+  double *d_ll = nullptr, *scratch = nullptr;
   if (!rc && !hip_ok(sm_alloc((void **)&d_ll, sizeof(double)), "hipMalloc(loglike)")) rc = 1;
   double *pool = rc ? nullptr : (double *)ws_get(0, (size_t)cells * sizeof(double));
   if (!rc && !pool) rc = 1;
+  if (!rc && mode != MB_BACKWARD) rc = profile_scratch(pf_fwd_scratch(p, true), 1, &scratch);
   if (!rc) {
     Timer tm;
     tm.start();
-    rc = mode == MB_BACKWARD ? launch_profile_bwd(m, true, d, 1, p->d_logP, pool, nullptr, nullptr, d_ll, nullptr, 0, g_stream)
-                             : launch_profile_fwd(m, mode, true, d, 1, p->d_logP, pool, nullptr, d_ll, g_stream);
+    rc = mode == MB_BACKWARD ? pf_bwd(p, true, d, 1, pool, nullptr, nullptr, d_ll, nullptr, 0)
+                             : pf_fwd(p, mode, true, d, 1, pool, scratch, d_ll);
     g_last_ms += tm.stop();
     g_last_launches = 1;
   }
   if (!rc) rc = d2h_large(cellsOut, pool, (size_t)cells * sizeof(double));
   if (rc) quiesce_streams();
   sm_free(d); sm_free(d_ll);
+  g_last_kernel = mode == MB_BACKWARD ? pf_name(p, "k_profile_bwd<mat>", "k_profile_merge_bwd<mat>")
+                                      : (mode == MB_VITERBI ? pf_name(p, "k_profile_fwd<max,mat>", "k_profile_merge_fwd<max,mat>") : pf_name(p, "k_profile_fwd<sum,mat>", "k_profile_merge_fwd<sum,mat>"));
   mb_profiles_destroy(p);
-  g_last_kernel = mode == MB_BACKWARD ? "k_profile_bwd<mat>" : (mode == MB_VITERBI ? "k_profile_fwd<max,mat>" : "k_profile_fwd<sum,mat>");
   return rc;
+}
+
+int mb_profile_fill(mb_machine *m, int mode, const double *logP, int64_t nRows, double *cellsOut) {
+  ApiGuard guard;
+  return profile_fill(m, mode, logP, nRows, 0, nullptr, cellsOut);
+}
+
+int mb_profile_fill_merged(mb_machine *m, int mode, const double *logP, int64_t nRows, int32_t nCols, const int32_t *colTok, double *cellsOut) {
+  ApiGuard guard;
+  if (!merge_map_ok(m, nCols, colTok)) return 1;
+  return profile_fill(m, mode, logP, nRows, nCols, colTok, cellsOut);
 }
 
 // ---- prefix search: node fills on the device, the tree on the host (mb_prefix.hip, docs/decoding.md) --------------------------

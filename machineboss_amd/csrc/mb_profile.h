@@ -38,5 +38,7 @@ struct mb_profiles {
   mb_machine *m = nullptr;
   long long n = 0, totalRows = 0;
   std::vector<long long> rowOff;   // [n+1], rebased to 0
-  double *d_logP = nullptr;        // [totalRows * (nOut+1)]
+  double *d_logP = nullptr;        // [totalRows * (nOut+1)]; merged: [totalRows * (nCols+1)]
+  int nCols = 0;                   // > 0: CTC-merged profiles (mb_profile_merge.h), rows of nCols + 1 doubles
+  int *d_colTok = nullptr;         // [nCols] output token of each column
 };

@@ -12,6 +12,9 @@ recurrence -- the yardstick of the device sweeps:
     loglike   = W[L][S-1]
 
 (+) is log-sum-exp (Forward) or max (Viterbi).  P[r][0] is the blank: the row is consumed and the machine does not move.
+
+CTC-merged profiles (``--recognize-merge-csv``, src/csv.cpp:20-46; mb_profile_merge.hip) have the recogniser
+(Profile.mergingMachine), the row table (Profile.mergeRows) and the yardstick (MergedProfileDP) here too.
 """
 from __future__ import annotations
 
@@ -101,6 +104,57 @@ class Profile:
         for ms in m.state:
             ms.trans = [MachineTransition(dest=t.dest, inp=t.out, out=t.inp, weight=t.weight) for t in ms.trans]
         return m
+
+    def mergingMachine(self) -> Machine:
+        """CSVProfile::mergingMachine (src/csv.cpp:20-46): the profile as a CTC generator.  State (pos, tok) = "row pos - 1 took
+        column tok" (tok = len(header): the blank); a row that repeats the last column, or takes the blank, emits nothing.  All
+        columns of the last row lead to the one end state: (L - 1)(nCols + 1) + 2 states for L >= 1 rows."""
+        if not self.header:
+            raise MachineError("Need header to build mergingMachine from CSVProfile")
+        nCols, nRows = len(self.header), len(self.row)
+
+        def index(pos: int, tok: int) -> int:
+            return 0 if pos == 0 else (pos - 1) * (nCols + 1) + (0 if pos == nRows else tok) + 1
+        m = Machine()
+        for _ in range(index(nRows, 0) + 1):
+            m.state.append(MachineState())
+        for pos in range(1, nRows):
+            for tok in range(nCols + 1):
+                m.state[index(pos, tok)].name = [pos, "" if tok == nCols else self.header[tok]]
+        m.state[0].name = "START"
+        m.state[-1].name = "END"
+        for pos, row in enumerate(self.row):
+            for col in range(min(len(row), nCols + 1)):
+                dest = index(pos + 1, col)
+                for tok in range((nCols if pos else 0) + 1):
+                    emit = "" if (col == tok and pos > 0) or col == nCols else self.header[col]
+                    m.state[index(pos, tok)].trans.append(MachineTransition(dest=dest, inp="", out=emit, weight=row[col]))
+        return m
+
+    def mergingRecogniserMachine(self) -> Machine:
+        """CSVProfile::mergingMachine().transpose() -- what ``--recognize-merge-csv`` composes onto the model."""
+        m = self.mergingMachine()
+        for ms in m.state:
+            ms.trans = [MachineTransition(dest=t.dest, inp=t.out, out=t.inp, weight=t.weight) for t in ms.trans]
+        return m
+
+    def mergeRows(self, em: EvaluatedMachine) -> Tuple[np.ndarray, np.ndarray]:
+        """(logP[rows, nCols + 1], colTok[nCols]) for the merged (CTC) sweeps: the header columns whose symbol is in the machine's
+        output alphabet, in header order, as columns 1..nCols with colTok[c - 1] their output token; column 0 the blank (header
+        column len(header)).  A symbol that heads two columns gives two columns (they do not merge with each other); short rows
+        weigh 0; columns beyond the blank are ignored."""
+        if not self.header:
+            raise MachineError("Need header to build mergingMachine from CSVProfile")
+        tok = {s: t for t, s in enumerate(em.outputTokenizer.tok2sym) if t}
+        cols = [len(self.header)] + [c for c, h in enumerate(self.header) if h in tok]
+        P = np.empty((len(self.row), len(cols)), np.float64)
+        for r, row in enumerate(self.row):
+            for k, c in enumerate(cols):
+                v = row[c] if c < len(row) else 0.0
+                if v < 0 or math.isnan(v):
+                    raise MachineError("Profile row %d: weight %g is not a probability" % (r, v))
+                P[r, k] = math.log(v) if v > 0 else -math.inf
+        return P, np.array([tok[self.header[c]] for c in cols[1:]], np.int32)
 
 
 # ---- the numpy restatement -------------------------------------------------------------------------------------------------
@@ -289,4 +343,174 @@ class ProfileDP:
                 k = next(k for k in self.inEmit[q] if (W[r - 1, self.eS[k]] + self.eW[k]) + Pr[self.eO[k]] == cur)
                 r -= 1
                 edges.append(int(self.eId[k])); rows.append(r); q = int(self.eS[k]); layer = 1
+        return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32)
+
+
+def _red_planes(A: np.ndarray, mx: bool) -> np.ndarray:
+    """(+) over axis 0 of A[planes, S]: max, or the exact (max-shifted) log-sum-exp."""
+    m = A.max(axis=0)
+    if mx:
+        return m
+    fin = m > _NEG
+    ms = np.where(fin, m, 0.0)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        return np.where(fin, ms + np.log(np.exp(A - ms).sum(axis=0)), _NEG)
+
+
+class MergedProfileDP(ProfileDP):
+    """The merged (CTC) profile recurrence in numpy -- the yardstick of mb_profile_merge.hip (docs/profile_tapes.md, "Merged (CTC)
+    profiles"): the semantics of compose(M, transpose(CSVProfile::mergingMachine())) with empty tapes.  Beside the S states of M
+    the lattice has a "last column seen" axis of nCols + 1 planes: plane 0 = the last row took the blank (or no row yet), plane c
+    = the last row took column c, whose output token is colTok[c - 1]:
+
+        N[0][0][q]   = [q == 0], every other plane -inf
+        W[r][p][q]   = N[r][p][q] (+) sum_{silent t: s->q, s < q} W[r][p][s] + w_t
+        N[r+1][0][q] = (+)_p (N[r][p][q] + P[r][0])
+        N[r+1][c][q] = (N[r][c][q] + P[r][c]) (+) sum_{t: s->q, in = eps, out = colTok[c]} (X[r][c][s] + w_t) + P[r][c]
+        X[r][c][s]   = (+)_{k != c} W[r][k][s]
+        loglike      = (+)_p W[L][p][S-1]
+
+    Viterbi keeps the first maximum: W takes "no move" first, then silent edges in `incoming` order; N[.][0] the planes ascending;
+    N[.][c] the repeat first, then emitting edges in `incoming` order, each from the lowest plane k != c that attains X; the end
+    the planes ascending.  Lattices are [L + 1, nCols + 1, S]."""
+
+    def __init__(self, em: EvaluatedMachine, colTok: Sequence[int]):
+        super().__init__(em)
+        self.colTok = np.asarray(colTok, np.int64).reshape(-1)
+        if len(self.colTok) and (self.colTok.min() < 1 or self.colTok.max() > em.nOutTok):
+            raise MachineError("column token outside 1..nOutTok")
+        self.nCols = len(self.colTok)
+        self.PL = self.nCols + 1
+        # per column, the emitting edges of its token (positions in the `incoming`-ordered emitting list)
+        self.colSel = [np.nonzero(self.eO == t)[0] for t in self.colTok]
+
+    def _check(self, P) -> np.ndarray:
+        P = np.asarray(P, np.float64).reshape(-1, self.PL)
+        if np.isnan(P).any() or (P == math.inf).any():
+            raise MachineError("profile weight is NaN or +infinity")
+        return P
+
+    def _others(self, c: int) -> List[int]:
+        return [k for k in range(self.PL) if k != c]
+
+    def forward(self, P, mode: str = "exact") -> Tuple[float, np.ndarray, np.ndarray]:
+        """(loglike, N[L+1][nCols+1][S], W[L+1][nCols+1][S]); mode "exact" or "max"."""
+        P = self._check(P)
+        mx = mode == "max"
+        fold = _max_fold if mx else _lse_fold
+        L, S, PL = len(P), self.S, self.PL
+        N = np.full((L + 1, PL, S), _NEG); W = np.full((L + 1, PL, S), _NEG)
+        N[0, 0, 0] = 0.0
+        for r in range(L + 1):
+            if r:
+                Pr, Np, Wp = P[r - 1], N[r - 1], W[r - 1]
+                N[r, 0] = _red_planes(Np + Pr[0], mx)
+                for c in range(1, PL):
+                    X = _red_planes(Wp[self._others(c)], mx)
+                    sel = self.colSel[c - 1]
+                    N[r, c] = fold(Np[c] + Pr[c], self.eD[sel], (X[self.eS[sel]] + self.eW[sel]) + Pr[c])
+            for p in range(PL):
+                w = N[r, p].copy()
+                for lv in self.fLevels:
+                    w = fold(w, self.sD[lv], w[self.sS[lv]] + self.sW[lv])
+                W[r, p] = w
+        return float(_red_planes(W[L, :, S - 1:S], mx)[0]), N, W
+
+    def backward(self, P) -> Tuple[float, np.ndarray, np.ndarray]:
+        """(loglike, NB[L+1][nCols+1][S], WB[L+1][nCols+1][S]), exact log-sum-exp; loglike = NB[0][0][0]."""
+        P = self._check(P)
+        L, S, PL = len(P), self.S, self.PL
+        NB = np.full((L + 1, PL, S), _NEG); WB = np.full((L + 1, PL, S), _NEG)
+        for r in range(L, -1, -1):
+            for k in range(PL):
+                base = np.full(S, _NEG)
+                if r == L:
+                    base[S - 1] = 0.0
+                else:
+                    for c in range(1, PL):
+                        if c != k:
+                            sel = self.colSel[c - 1]
+                            base = _lse_fold(base, self.eS[sel], (self.eW[sel] + P[r][c]) + NB[r + 1][c][self.eD[sel]])
+                for lv in self.bLevels:
+                    base = _lse_fold(base, self.sS[lv], base[self.sD[lv]] + self.sW[lv])
+                WB[r, k] = base
+                if r < L:
+                    terms = [base, P[r][0] + NB[r + 1][0]] + ([P[r][k] + NB[r + 1][k]] if k else [])
+                    NB[r, k] = _red_planes(np.stack(terms), False)
+                else:
+                    NB[r, k] = base
+        return float(NB[0, 0, 0]), NB, WB
+
+    def counts(self, P) -> Tuple[np.ndarray, float]:
+        """(posterior expected use of every transition, Forward loglike); nothing for a -inf profile."""
+        P = self._check(P)
+        ll, _, WF = self.forward(P)
+        out = np.zeros(self.em.nTransitions)
+        if not ll > _NEG:
+            return out, ll
+        _, NB, WB = self.backward(P)
+        with np.errstate(invalid="ignore"):
+            for r in range(len(P) + 1):
+                for k in range(self.PL):
+                    f = WF[r, k] - ll
+                    if r < len(P):
+                        for c in range(1, self.PL):
+                            if c != k:
+                                sel = self.colSel[c - 1]
+                                np.add.at(out, self.eId[sel], np.exp(f[self.eS[sel]] + ((self.eW[sel] + P[r][c]) + NB[r + 1][c][self.eD[sel]])))
+                    np.add.at(out, self.sId, np.exp(f[self.sS] + (WB[r, k][self.sD] + self.sW)))
+        return out, ll
+
+    def viterbi(self, P, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray]:
+        """(score, global edge ids start -> end, row at which each fired); the first maximum in the fill's candidate order.  Blank
+        and repeat rows are not edges.  ``census``: counts, by the candidate taken ("blank" / "repeat" / "emit" at an N cell,
+        "stay" / "silent" at a W cell, "plane" for an emitting edge whose X has two attaining planes, "end"), the steps at which
+        two or more candidates equal the cell."""
+        P = self._check(P)
+        v, N, W = self.forward(P, "max")
+        edges: List[int] = []; rows: List[int] = []
+        if not v > _NEG:
+            return v, np.zeros(0, np.uint32), np.zeros(0, np.int32)
+
+        def tie(kind: str, n: int):
+            if census is not None and n > 1:
+                census[kind] = census.get(kind, 0) + 1
+        r, q, layer = len(P), self.S - 1, 1
+        ends = [p for p in range(self.PL) if W[r, p, q] == v]
+        tie("end", len(ends))
+        p = ends[0]
+        while True:
+            if layer == 1:
+                cur = W[r, p, q]
+                cand = [N[r, p, q] == cur] + [W[r, p, self.sS[k]] + self.sW[k] == cur for k in self.inSil[q]]
+                tie("stay" if cand[0] else "silent", sum(cand))
+                if cand[0]:
+                    layer = 0
+                    continue
+                k = self.inSil[q][cand.index(True, 1) - 1]
+                edges.append(int(self.sId[k])); rows.append(r); q = int(self.sS[k])
+            else:
+                if r == 0:
+                    assert q == 0 and p == 0
+                    break
+                Pr, cur = P[r - 1], N[r, p, q]
+                if p == 0:
+                    cand = [N[r - 1, k, q] + Pr[0] == cur for k in range(self.PL)]
+                    tie("blank", sum(cand))
+                    p = cand.index(True)
+                    r -= 1
+                    continue
+                oth = self._others(p)
+                ks = [k for k in self.inEmit[q] if self.eO[k] == self.colTok[p - 1]]
+                X = [max(W[r - 1, o, self.eS[k]] for o in oth) for k in ks]
+                cand = [N[r - 1, p, q] + Pr[p] == cur] + [(x + self.eW[k]) + Pr[p] == cur for k, x in zip(ks, X)]
+                tie("repeat" if cand[0] else "emit", sum(cand))
+                r -= 1
+                if cand[0]:
+                    continue
+                j = cand.index(True, 1) - 1
+                k = ks[j]
+                src = [o for o in oth if W[r, o, self.eS[k]] == X[j]]
+                tie("plane", len(src))
+                edges.append(int(self.eId[k])); rows.append(r); q = int(self.eS[k]); p = src[0]; layer = 1
         return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32)
