@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_path, load_json
+import mergehelpers as mh
 from mergehelpers import merged_path_weight, random_merge_profile
 from profhelpers import _machine_of
 from randmachine import quantised_machine, random_machine
@@ -252,3 +253,79 @@ def test_cli_rejections():
         boss.run(base + ["--recognize-merge-csv", CSV], io.StringIO())
     with pytest.raises(MachineError, match="no other sequence data"):
         boss.run(base + ["--recognize-merge-csv", CSV, "-L", "--output-chars", "A"], io.StringIO())
+
+
+# ---- the inputs of the GPU edge suite ------------------------------------------------------------------------------------------------
+def _finite(em, colTok, profs):
+    mdp = MergedProfileDP(em, colTok)
+    return np.array([mdp.forward(P)[0] > -math.inf for P in profs])
+
+
+def test_edge_suite_inputs_are_live():
+    """test_profile_merge_edges_gpu.py asserts, from the restatement, that its inputs score finite, tie and split into chunks as its
+    cases need; the same builders of mergehelpers.py are held to the same conditions here, so the seeds are verified without a GPU.
+    (Backward and counts from 1 024 planes on are computed by the restatement nowhere.)"""
+    for nCols, S in mh.LANE_CASES:
+        em, colTok, profs = mh.lane_case(nCols, S)
+        assert len(colTok) == nCols and em.nStates == S and 1 <= min(colTok) and max(colTok) <= 3
+        assert max(len(P) for P in profs) <= (23 if nCols + 1 <= 66 else 3)
+        assert int(em.silentLevels().max(initial=0)) + 1 <= 16
+        assert _finite(em, colTok, profs).sum() >= 3, (nCols, S)
+    assert max(nc + 1 for nc, _ in mh.LANE_CASES) > mh.PM_THREADS
+    for S in mh.LDS_CASES:
+        em, colTok, profs = mh.lds_case(S)
+        assert 1 < int(em.silentLevels().max(initial=0)) + 1 <= 16
+        assert _finite(em, colTok, profs).sum() >= 2, S
+    for nIn, nOut in mh.ALPHABET_CASES:
+        em, colTok, profs = mh.alphabet_case(nIn, nOut)
+        assert np.sum(em.inTok != 0) >= 10 and np.sum((em.inTok != 0) & (em.outTok != 0)) >= 1
+        assert _finite(em, colTok, profs).sum() >= 3, (nIn, nOut)
+        em, colTok, hot, seqs = mh.alphabet_one_hot_case(nIn, nOut)
+        f = _finite(em, colTok, hot)
+        assert f[:6].sum() >= 4 and f[6:].all(), (nIn, nOut, f)
+        mdp = MergedProfileDP(em, colTok)
+        assert mdp.forward(hot[-3])[0] == pytest.approx(mdp.forward(hot[-2])[0], rel=1e-12) != pytest.approx(mdp.forward(hot[-1])[0], rel=1e-6)
+    for name, (em, colTok, profs) in mh.column_map_cases().items():
+        assert _finite(em, colTok, profs).sum() >= 3, name
+    for name, (em, colTok, profs) in mh.degenerate_cases().items():
+        f = _finite(em, colTok, profs)
+        assert f.sum() >= (2 if name == "noblank" else 3), (name, f)
+        assert name != "infrow" or (not f[1] and not f[4])
+    em, colTok, P = mh.all_blank_case()
+    assert MergedProfileDP(em, colTok).forward(np.zeros((0, len(colTok) + 1)))[0] > -math.inf
+    # ties: every kind at least 5 times (the counts in the GPU test's docstring)
+    tot = {}
+    for em, colTok, profs in mh.tie_cases():
+        assert len(profs) > 64
+        mdp = MergedProfileDP(em, colTok)
+        for P in profs:
+            mdp.viterbi(P, tot)
+    assert all(tot.get(kind, 0) >= 5 for kind in mh.TIE_KINDS), tot
+    print("tie census", tot)
+    # batches: at least half finite and some -inf (Viterbi is finite where Forward is), and a budget that cuts >= 3 unequal chunks
+    for S, n, maxL in mh.BATCH_CASES:
+        em, colTok, profs = mh.batch_case(S, n, maxL)
+        levels = int(em.silentLevels().max(initial=0)) + 1
+        assert levels <= 16
+        mdp = MergedProfileDP(em, colTok)
+        fin = np.array([mdp.forward(P, "max")[0] > -math.inf for P in profs])
+        assert fin.sum() >= n // 2 and not fin.all()
+        cb, vb = mh.batch_bytes(em, 4, profs, levels)
+        budget = int(sum(cb) / 3.5)
+        assert budget >= max(cb) * 1.2 and budget >= max(vb) * 1.2
+        for b in (cb, vb):
+            chunks = mh.greedy_chunks(b, budget)
+            assert len(chunks) >= 3 and len({p1 - p0 for p0, p1 in chunks}) >= 2, chunks
+    # long profiles: the 300-row cuts of the derivative check and the shortest whole profile score finite
+    for with_input in (False, True):
+        em, colTok, profs = mh.long_case(with_input)
+        assert (np.sum(em.inTok != 0) > 0) == with_input and int(em.silentLevels().max(initial=0)) + 1 <= 16
+        assert _finite(em, colTok, [P[:300] for P in profs] + profs[:1]).all()
+    em, colTok, P = mh.long_restatement_case()
+    assert _finite(em, colTok, [P]).all()
+    for which in ("generator", "random"):
+        for zeros in (False, True):
+            M, em, prof = mh.composed_case(which, zeros)
+            P, colTok = prof.mergeRows(em)
+            assert len(set(colTok)) < len(colTok) and (P == -math.inf).any() == zeros
+            assert _finite(em, colTok, [P]).all(), (which, zeros)
