@@ -207,6 +207,15 @@ int mb_prefix_node_cells(mb_prefix *p, int64_t node, double *cellsOut);
  * a node's lattice is cells[((r*2) + layer)*nStates + state], r = 0..rows, layer 0 = Forward, layer 1 = prefix. */
 mb_prefix *mb_prefix_create_profiles(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff,
                                      const double *logSumInTrans, int64_t maxNodes);
+/* The same against CTC-MERGED profiles (the layout of mb_profiles_create_merged): rows of nCols + 1 log weights, column 0 the
+ * blank, column c the CSV column whose output token is colTok[c - 1] (1..nOutTok); a batch has one column map.  The answers are
+ * those of the token search on compose(machine, merging recogniser) with an empty output.  A node's lattice has nCols + 1 planes:
+ * cells[(((r*2) + layer)*(nCols+1) + plane)*nStates + state], plane 0 = the last row took the blank (or no row yet), plane c = it
+ * took column c; a slot is 2 (maxRows + 1)(nCols + 1) nStates doubles, which mb_prefix_node_cells copies.  Errors: nCols < 1, a
+ * token outside 1..nOutTok, NaN / +inf, a pool over the memory budget, and a machine whose working set
+ * ((6 nCols + 5) nStates + nCols + 1 doubles) exceeds the 160 KiB of LDS of a workgroup. */
+mb_prefix *mb_prefix_create_merged(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff, int32_t nCols,
+                                   const int32_t *colTok, const double *logSumInTrans, int64_t maxNodes);
 
 /* ---- convenience wrappers over host buffers (create batch, run, destroy) ----------------------------------
  * forwardLogLike / viterbiLogLike+viterbiAlign / forwardBackwardCounts of src/api.h:20-34.                   */

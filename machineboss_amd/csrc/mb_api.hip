@@ -2463,7 +2463,7 @@ int mb_profile_fill_merged(mb_machine *m, int mode, const double *logP, int64_t 
 static const int WS_PREFIX_POOL = 15;
 
 static void prefix_free(mb_prefix *p) {
-  sm_free(p->d_out); sm_free(p->d_logP); sm_free(p->d_rOff); sm_free(p->d_rIdx); sm_free(p->d_rVal);   // (cached by size class: steady cycles allocate nothing)
+  sm_free(p->d_out); sm_free(p->d_logP); sm_free(p->d_colTok); sm_free(p->d_rOff); sm_free(p->d_rIdx); sm_free(p->d_rVal);   // (cached by size class: steady cycles allocate nothing)
   if (p->pool) {
     if (p->poolIsWorkspace) g_ws[WS_PREFIX_POOL].held = false;      // the memory stays cached for the next search
     else { (void)hipFree(p->pool); ++g_alloc.frees; }
@@ -2472,9 +2472,10 @@ static void prefix_free(mb_prefix *p) {
 }
 
 // The searches of one object decode either token strings (outTok) or profiles (profile = true: logP, rows of nOutTok + 1 log
-// weights, outOff counting rows); everything else -- R, the pool, the free list -- is the same.
+// weights, outOff counting rows) or CTC-merged profiles (nCols > 0: rows of nCols + 1 log weights, nCols + 1 planes per slot,
+// mb_prefix_merge.hip); everything else -- R, the pool, the free list -- is the same.
 static mb_prefix *prefix_create(mb_machine *m, int64_t nSeq, bool profile, const int32_t *outTok, const double *logP, const int64_t *outOff,
-                                const double *logSumInTrans, int64_t maxNodes) {
+                                const double *logSumInTrans, int64_t maxNodes, int32_t nCols = 0, const int32_t *colTok = nullptr) {
   if (!m || nSeq < 1 || !outOff || !logSumInTrans || maxNodes < 1) { set_error("null argument"); return nullptr; }
   if (ensure_init()) return nullptr;
   if (m->S > PREFIX_MAX_STATES) { set_error("prefix search: more than " + std::to_string(PREFIX_MAX_STATES) + " states"); return nullptr; }
@@ -2492,11 +2493,13 @@ static mb_prefix *prefix_create(mb_machine *m, int64_t nSeq, bool profile, const
   if (nTok && !tok) { set_error("null argument"); delete p; return nullptr; }
   for (long long k = 0; k < nTok; ++k)
     if (tok[k] < 1 || tok[k] > m->nOut) { set_error("output token " + std::to_string(tok[k]) + " outside the alphabet"); delete p; return nullptr; }
-  const long long nVal = profile ? p->outOff[nSeq] * (m->nOut + 1) : 0;
-  const double *val = logP ? logP + outOff[0] * (m->nOut + 1) : nullptr;
+  const long long width = nCols ? nCols + 1 : m->nOut + 1;      // doubles of a profile row
+  const long long nVal = profile ? p->outOff[nSeq] * width : 0;
+  const double *val = logP ? logP + outOff[0] * width : nullptr;
   if (nVal && !val) { set_error("null argument"); delete p; return nullptr; }
   if (!profile_values_ok(val, nVal)) { delete p; return nullptr; }
   p->profile = profile;
+  p->nCols = nCols;
   // R by column, -inf entries dropped; NaN or +inf is a caller's error
   const int S = m->S;
   std::vector<long long> rOff(S + 1, 0);
@@ -2509,7 +2512,12 @@ static mb_prefix *prefix_create(mb_machine *m, int64_t nSeq, bool profile, const
     }
     rOff[s + 1] = (long long)rIdx.size();
   }
-  p->slotDoubles = prefix_slot_doubles(S, p->maxOutLen);
+  p->slotDoubles = nCols ? merged_prefix_slot_doubles(S, nCols, p->maxOutLen) : prefix_slot_doubles(S, p->maxOutLen);
+  if (nCols && !merged_prefix_lds_fits(S, nCols)) {
+    set_error("prefix search against merged profiles: ((6 nCols + 5) x states + nCols + 1) doubles exceed the LDS of a workgroup (160 KiB; " +
+              std::to_string(S) + " states, " + std::to_string(nCols) + " columns)");
+    delete p; return nullptr;
+  }
   const double poolBytes = (double)maxNodes * (double)p->slotDoubles * 8.0;
   const double rBytes = 12.0 * (double)rIdx.size() + 8.0 * (S + 1) + 4.0 * (double)nTok + 8.0 * (double)nVal;   // R by column and the tokens (profile rows) count too
   if (poolBytes + rBytes > (double)budget_bytes()) {
@@ -2523,6 +2531,8 @@ static mb_prefix *prefix_create(mb_machine *m, int64_t nSeq, bool profile, const
             hip_ok(sm_alloc((void **)&p->d_rIdx, std::max<size_t>(rIdx.size(), 1) * sizeof(int)), "hipMalloc(prefix R)") &&
             hip_ok(sm_alloc((void **)&p->d_rVal, std::max<size_t>(rVal.size(), 1) * sizeof(double)), "hipMalloc(prefix R)");
   ok = ok && (!profile || hip_ok(sm_alloc((void **)&p->d_logP, (size_t)std::max<long long>(nVal, 1) * sizeof(double)), "hipMalloc(prefix profiles)"));
+  ok = ok && (!nCols || (hip_ok(sm_alloc((void **)&p->d_colTok, (size_t)nCols * sizeof(int)), "hipMalloc(prefix columns)") &&
+                         hip_ok(hipMemcpy(p->d_colTok, colTok, (size_t)nCols * sizeof(int), hipMemcpyHostToDevice), "H2D prefix columns")));
   ok = ok && (!nVal || (!h2d_large(p->d_logP, val, (size_t)nVal * sizeof(double)) && hip_ok(hipStreamSynchronize(g_stream), "H2D prefix profiles")));
   ok = ok && (!nTok || hip_ok(hipMemcpy(p->d_out, tok, (size_t)nTok * sizeof(int), hipMemcpyHostToDevice), "H2D prefix tokens")) &&
        hip_ok(hipMemcpy(p->d_rOff, rOff.data(), rOff.size() * sizeof(long long), hipMemcpyHostToDevice), "H2D prefix R") &&
@@ -2558,6 +2568,13 @@ mb_prefix *mb_prefix_create_profiles(mb_machine *m, int64_t nProfiles, const dou
                                      int64_t maxNodes) {
   ApiGuard guard;
   return prefix_create(m, nProfiles, true, nullptr, logP, rowOff, logSumInTrans, maxNodes);
+}
+
+mb_prefix *mb_prefix_create_merged(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff, int32_t nCols,
+                                   const int32_t *colTok, const double *logSumInTrans, int64_t maxNodes) {
+  ApiGuard guard;
+  if (!merge_map_ok(m, nCols, colTok)) return nullptr;
+  return prefix_create(m, nProfiles, true, nullptr, logP, rowOff, logSumInTrans, maxNodes, nCols, colTok);
 }
 
 void mb_prefix_destroy(mb_prefix *p) {
@@ -2604,16 +2621,18 @@ static int prefix_fill(mb_prefix *p, int64_t n, const int64_t *seq, const int64_
     Timer tm;
     tm.start();
     const PrefixR R{p->d_rOff, p->d_rIdx, p->d_rVal};
-    rc = p->profile ? launch_prefix_fill_profile(m, R, d_desc, (int)n, p->d_logP, p->pool, d_res, g_stream)
-                    : launch_prefix_fill(m, R, d_desc, (int)n, p->d_out, p->pool, d_res, g_stream);
+    rc = p->nCols    ? launch_prefix_fill_merged(m, R, p->nCols, p->d_colTok, d_desc, (int)n, p->d_logP, p->pool, d_res, g_stream)
+         : p->profile ? launch_prefix_fill_profile(m, R, d_desc, (int)n, p->d_logP, p->pool, d_res, g_stream)
+                      : launch_prefix_fill(m, R, d_desc, (int)n, p->d_out, p->pool, d_res, g_stream);
     g_last_ms += tm.stop();
     g_last_launches = 1;
   }
   if (!rc && !hip_ok(hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(double), hipMemcpyDeviceToHost, g_stream), "D2H prefix results")) rc = 1;
-  if (!rc && !hip_ok(hipStreamSynchronize(g_stream), p->profile ? "k_prefix_fill_profile" : "k_prefix_fill")) rc = 1;
+  const char *kernel = p->nCols ? "k_prefix_fill_merged" : p->profile ? "k_prefix_fill_profile" : "k_prefix_fill";
+  if (!rc && !hip_ok(hipStreamSynchronize(g_stream), kernel)) rc = 1;
   if (rc) quiesce_streams();
   sm_free(d_desc); sm_free(d_res);
-  g_last_kernel = p->profile ? "k_prefix_fill_profile" : "k_prefix_fill";
+  g_last_kernel = kernel;
   if (rc) return rc;
   for (int64_t i = 0; i < n; ++i) {
     p->slotSeq[(size_t)childOut[i]] = seq[i];
@@ -2659,7 +2678,7 @@ int mb_prefix_node_cells(mb_prefix *p, int64_t node, double *cellsOut) {
   if (!p || !cellsOut) { set_error("null argument"); return 1; }
   if (node < 0 || node >= p->maxNodes || p->slotSeq[(size_t)node] < 0) { set_error("prefix node " + std::to_string(node) + " is not live"); return 1; }
   const long long k = p->slotSeq[(size_t)node];
-  const long long cells = prefix_slot_doubles(p->m->S, p->outOff[(size_t)k + 1] - p->outOff[(size_t)k]);
+  const long long cells = prefix_slot_doubles(p->m->S, p->outOff[(size_t)k + 1] - p->outOff[(size_t)k]) * (p->nCols ? p->nCols + 1 : 1);
   return d2h_large(cellsOut, p->pool + node * p->slotDoubles, (size_t)cells * sizeof(double));
 }
 

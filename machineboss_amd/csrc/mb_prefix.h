@@ -31,12 +31,22 @@ inline long long prefix_slot_doubles(int S, long long maxOutLen) { return 2 * (m
 constexpr int PREFIX_MAX_STATES = 160 * 1024 / 8;
 // against profiles N[r-1], Xn[r-1] and the row's nOut + 1 weights sit beside it: 3 S + nOut + 1 doubles
 constexpr size_t PREFIX_PROFILE_MAX_LDS = 160 * 1024;
+// against CTC-merged profiles (mb_prefix_merge.hip) a node has nCols + 1 planes of the plain lattice, and a workgroup keeps in LDS
+// Y[r-1], N[r-1] and Xn[r-1] (nCols + 1 planes of S each), the three exclusion vectors (nCols planes of S each), the two blank sums
+// (S each) and the row's nCols + 1 weights: (6 nCols + 5) S + nCols + 1 doubles, at most PREFIX_PROFILE_MAX_LDS bytes
+inline long long merged_prefix_lds_doubles(int S, int nCols) { return (6LL * nCols + 5) * S + nCols + 1; }
+inline bool merged_prefix_lds_fits(int S, int nCols) { return (unsigned long long)merged_prefix_lds_doubles(S, nCols) * sizeof(double) <= PREFIX_PROFILE_MAX_LDS; }
+inline long long merged_prefix_slot_doubles(int S, int nCols, long long maxOutLen) { return prefix_slot_doubles(S, maxOutLen) * (nCols + 1); }
 
 int launch_prefix_fill(const mb_machine *m, const PrefixR &R, const PrefixDesc *d, int n, const int *outTok, double *pool,
                        double *result /* [2n]: logSeqProb, logPrefixProb per entry */, hipStream_t st);
 // the same against profiles: logP holds rows of nOut + 1 log weights (column 0 the blank), outBase / outLen of a descriptor count rows
 int launch_prefix_fill_profile(const mb_machine *m, const PrefixR &R, const PrefixDesc *d, int n, const double *logP, double *pool,
                                double *result, hipStream_t st);
+// the same against CTC-merged profiles: rows of nCols + 1 log weights (column 0 the blank, column c of output token colTok[c - 1], a
+// device array), slots of merged_prefix_slot_doubles laid out as cells[(((r*2) + layer)*(nCols+1) + p)*S + q]
+int launch_prefix_fill_merged(const mb_machine *m, const PrefixR &R, int nCols, const int *colTok, const PrefixDesc *d, int n,
+                              const double *logP, double *pool, double *result, hipStream_t st);
 
 }  // namespace mb
 
@@ -47,6 +57,8 @@ struct mb_prefix {
   int *d_out = nullptr;              // output tokens of every search
   bool profile = false;              // the searches decode profiles: outOff counts rows of d_logP, d_out is unused
   double *d_logP = nullptr;          // [rows][nOut + 1] log weights of every search's profile, column 0 the blank
+  int nCols = 0;                     // > 0: the profiles are CTC-merged (mb_prefix_merge.hip): rows of nCols + 1 doubles, nCols + 1 planes per slot
+  int *d_colTok = nullptr;           // [nCols] output token of each column
   long long *d_rOff = nullptr;       // R by column (PrefixR)
   int *d_rIdx = nullptr;
   double *d_rVal = nullptr;

@@ -28,7 +28,7 @@ import numpy as np
 
 from .evalmachine import EvaluatedMachine
 from .machine import MachineError
-from .profile import _lse_fold
+from .profile import _lse_fold, _red_planes
 
 _NEG = -math.inf
 NO_BACKTRACK_LIMIT = (1 << 63) - 1      # numeric_limits<long>::max(), target/boss.cpp:851
@@ -189,13 +189,104 @@ class ProfilePrefixDP(PrefixDP):
         return cells, float(cells[L, 0, S - 1]), float(Y[S - 1])
 
 
+class MergedProfilePrefixDP(PrefixDP):
+    """The node fill against a CTC-MERGED profile (profile.Profile.mergeRows: rows of nCols + 1 log weights, column 0 the blank,
+    column c the CSV column whose output token is colTok[c - 1]): the prefix search on compose(M, merging recogniser) with an
+    empty output (docs/decoding.md, "Decoding against a merged profile").  A node gains the "last column seen" axis of
+    profile.MergedProfileDP -- plane 0 = blank or no row yet, plane c = the last row took column c -- and keeps the two stages
+    of ProfilePrefixDP: the blank and the repeat read the ARRIVED stage (N, Xn), never W or X.  With excl_c(V)[s] the sum of
+    V[k][s] over the planes k != c:
+
+        An[r][0][d] = [root, r = 0, d = 0]
+        An[r][c][d] = sum_{t: s->d, in = a, out = colTok[c]} excl_c(Pa.W[r-1])[s] + w_t + P[r-1][c]
+        Aw[r][p][d] = sum_{t: s->d, in = a, out = eps} Pa.W[r][p][s] + w_t
+        N[r][0][d]  = An[r][0][d] (+) (+)_p (N[r-1][p][d] + P[r-1][0])
+        N[r][c][d]  = An[r][c][d] (+) (N[r-1][c][d] + P[r-1][c]) (+) sum_{t: in = eps, out = colTok[c]} excl_c(W[r-1])[s] + w_t + P[r-1][c]
+        W[r][p][d]  = Aw[r][p][d] (+) N[r][p][d] (+) sum_{silent t: s->d, s < d} W[r][p][s] + w_t
+        Xn[r][0][d] = An[r][0][d] (+) (+)_p (Xn[r-1][p][d] + P[r-1][0])
+        Xn[r][c][d] = An[r][c][d] (+) (Xn[r-1][c][d] + P[r-1][c]) (+) sum_{t: any in, out = colTok[c]} excl_c(Y[r-1])[s] + w_t + P[r-1][c]
+        X[r][p][d]  = Aw[r][p][d] (+) Xn[r][p][d]
+        Y[r][p][s]  = logsum_q X[r][p][q] + R[q][s]
+        logSeqProb  = (+)_p W[L][p][S-1],     logPrefixProb = (+)_p Y[L][p][S-1]
+
+    ``fill(P, parentCells, a)`` -> (cells[L+1][2][nCols+1][S], logSeqProb, logPrefixProb); layer 0 = W, layer 1 = X."""
+
+    def __init__(self, em: EvaluatedMachine, colTok: Sequence[int], logR: Optional[np.ndarray] = None):
+        super().__init__(em, logR)
+        self.colTok = np.asarray(colTok, np.int64).reshape(-1)
+        if len(self.colTok) and (self.colTok.min() < 1 or self.colTok.max() > em.nOutTok):
+            raise MachineError("column token outside 1..nOutTok")
+        self.nCols = len(self.colTok)
+        self.PL = self.nCols + 1
+        self._all = np.arange(self.S, dtype=np.int64)
+
+    def _excl(self, V: np.ndarray) -> np.ndarray:
+        """[nCols, S]: row c - 1 is the sum of the planes of V other than c."""
+        out = np.full((self.nCols, self.S), _NEG)
+        for c in range(1, self.PL):
+            out[c - 1] = _red_planes(V[[k for k in range(self.PL) if k != c]], False)
+        return out
+
+    def fill(self, P, parent: Optional[np.ndarray] = None, a: int = 0) -> Tuple[np.ndarray, float, float]:
+        P = np.asarray(P, np.float64).reshape(-1, self.PL)
+        if np.isnan(P).any() or (P == math.inf).any():
+            raise MachineError("profile weight is NaN or +infinity")
+        L, S, PL = len(P), self.S, self.PL
+        cells = np.full((L + 1, 2, PL, S), _NEG)
+        N = Xn = Y = np.full((PL, S), _NEG)
+        for r in range(L + 1):
+            An, Aw = np.full((PL, S), _NEG), np.full((PL, S), _NEG)
+            if parent is None:
+                if r == 0:
+                    An[0, 0] = 0.0
+            else:
+                s, d, w = self._edges(a, 0)
+                for p in range(PL):
+                    Aw[p] = _lse_fold(Aw[p], d, parent[r, 0, p][s] + w)
+                if r:
+                    ex = self._excl(parent[r - 1, 0])
+                    for c in range(1, PL):
+                        s, d, w = self._edges(a, int(self.colTok[c - 1]))
+                        An[c] = _lse_fold(An[c], d, (ex[c - 1][s] + w) + P[r - 1][c])
+            if r:
+                Pr = P[r - 1]
+                exW, exY = self._excl(cells[r - 1, 0]), self._excl(Y)
+                Nn, Xnn = np.empty((PL, S)), np.empty((PL, S))
+                Nn[0] = _red_planes(np.concatenate([An[:1], N + Pr[0]]), False)
+                Xnn[0] = _red_planes(np.concatenate([An[:1], Xn + Pr[0]]), False)
+                for c in range(1, PL):
+                    tok = int(self.colTok[c - 1])
+                    s, d, w = self._edges(0, tok)
+                    Nn[c] = _lse_fold(An[c], np.concatenate([self._all, d]), np.concatenate([N[c] + Pr[c], (exW[c - 1][s] + w) + Pr[c]]))
+                    s, d, w = self._anyIn[tok]
+                    Xnn[c] = _lse_fold(An[c], np.concatenate([self._all, d]), np.concatenate([Xn[c] + Pr[c], (exY[c - 1][s] + w) + Pr[c]]))
+                N, Xn = Nn, Xnn
+            else:
+                N = Xn = An
+            Y = np.empty((PL, S))
+            for p in range(PL):
+                sq, px = _lse_fold(Aw[p], self._all, N[p]), _lse_fold(Aw[p], self._all, Xn[p])
+                if self._levels:
+                    s, d, w = self._by[(0, 0)]
+                    for lvl in self._levels:
+                        sq = _lse_fold(sq, d[lvl], sq[s[lvl]] + w[lvl])
+                cells[r, 0, p], cells[r, 1, p] = sq, px
+                Y[p] = self.columnSums(px)
+        return cells, float(_red_planes(cells[L, 0, :, S - 1:S], False)[0]), float(_red_planes(Y[:, S - 1:S], False)[0])
+
+
 # ---- backends: who keeps the lattices ----------------------------------------------------------------------------------------
 class NumpyNodes:
     """Node lattices on the host, filled by PrefixDP (token outputs) or ProfilePrefixDP (``profiles``: one [rows, nOutTok + 1]
-    array of log weights per search); the same interface and the same fixed pool size as the device backend."""
+    array of log weights per search) or, with ``colTok``, MergedProfilePrefixDP ([rows, nCols + 1] arrays); the same interface and
+    the same fixed pool size as the device backend."""
 
-    def __init__(self, em: EvaluatedMachine, outputs: Optional[Sequence[Sequence[int]]], logR: np.ndarray, maxNodes: int, profiles=None):
-        if profiles is not None:
+    def __init__(self, em: EvaluatedMachine, outputs: Optional[Sequence[Sequence[int]]], logR: np.ndarray, maxNodes: int, profiles=None,
+                 colTok=None):
+        if colTok is not None:
+            self.dp = MergedProfilePrefixDP(em, colTok, logR)
+            self.outputs = [np.asarray(p, np.float64).reshape(-1, self.dp.PL) for p in profiles]
+        elif profiles is not None:
             self.dp = ProfilePrefixDP(em, logR)
             self.outputs = [np.asarray(p, np.float64).reshape(-1, em.nOutTok + 1) for p in profiles]
         else:
@@ -238,26 +329,30 @@ class NumpyNodes:
 
 
 def makeNodes(em: EvaluatedMachine, outputs=None, backend: str = "device", maxNodes: Optional[int] = None, logR: Optional[np.ndarray] = None,
-              profiles=None):
+              profiles=None, colTok=None):
     """The lattice store of ``len(outputs)`` searches: "numpy" (host, PrefixDP) or "device" (capi.DevicePrefix, mb_prefix.hip).
     With ``profiles`` (one [rows, nOutTok + 1] array of log weights per search, column 0 the blank) the searches decode soft
-    outputs and ``outputs`` is not read.
+    outputs and ``outputs`` is not read; with ``colTok`` as well the profiles are CTC-merged: [rows, nCols + 1] tables and the
+    column map of profile.Profile.mergeRows (a slot then has nCols + 1 planes).
     ``maxNodes`` None: DEFAULT_MAX_NODES per search, on the device no more than half the memory budget holds (a slot is
     2 (maxL + 1) S doubles, so long outputs on large machines get fewer); a number is taken as it is and fails if it does not fit."""
     R = logSumInTrans(em) if logR is None else logR
+    if colTok is not None and profiles is None:
+        raise MachineError("a column map needs profiles")
+    planes = 1 if colTok is None else len(np.asarray(colTok).reshape(-1)) + 1
     if profiles is not None:
-        outputs = [np.asarray(p, np.float64).reshape(-1, em.nOutTok + 1) for p in profiles]     # (only their lengths are read below)
+        outputs = [np.asarray(p, np.float64).reshape(-1, em.nOutTok + 1 if colTok is None else planes) for p in profiles]     # (only their lengths are read below)
     want = DEFAULT_MAX_NODES * max(1, len(outputs)) if maxNodes is None else int(maxNodes)
     if backend == "numpy":
-        return NumpyNodes(em, outputs, R, want, profiles)
+        return NumpyNodes(em, outputs, R, want, profiles, colTok)
     if backend != "device":
         raise MachineError("unknown prefix search backend %s" % backend)
     from . import capi, dp
     dm = dp._device_machine(em)
     if maxNodes is None:
-        slot = 16 * (max([len(o) for o in outputs] + [0]) + 1) * em.nStates
+        slot = 16 * (max([len(o) for o in outputs] + [0]) + 1) * em.nStates * planes
         want = max(len(outputs) * (em.nInTok + 1), min(want, capi.memory_budget() // 2 // slot))
-    return capi.DevicePrefix(dm, outputs, R, want, profiles)
+    return capi.DevicePrefix(dm, outputs, R, want, profiles, colTok)
 
 
 # ---- std::push_heap / pop_heap / make_heap as libstdc++ orders them: which of two equal prefixes comes out first is theirs -------
@@ -319,8 +414,17 @@ class _Node:
 _less = lambda x, y: x.logPrefixProb < y.logPrefixProb
 
 
-def _logRows(em: EvaluatedMachine, profile) -> np.ndarray:
-    return profile.logRows(em) if hasattr(profile, "logRows") else np.asarray(profile, np.float64).reshape(-1, em.nOutTok + 1)
+def _logRows(em: EvaluatedMachine, profile, colTok=None) -> np.ndarray:
+    """The table of a profile: logRows, or with a column map the table of mergeRows (whose map must be that one)."""
+    if colTok is None:
+        return profile.logRows(em) if hasattr(profile, "logRows") else np.asarray(profile, np.float64).reshape(-1, em.nOutTok + 1)
+    colTok = np.asarray(colTok).reshape(-1)
+    if not hasattr(profile, "mergeRows"):
+        return np.asarray(profile, np.float64).reshape(-1, len(colTok) + 1)
+    P, ct = profile.mergeRows(em)
+    if not np.array_equal(ct, colTok):
+        raise MachineError("the profile's columns are not the column map of the batch")
+    return P
 
 
 class PrefixTree:
@@ -351,9 +455,10 @@ class PrefixTree:
 
     @classmethod
     def forProfile(cls, em: EvaluatedMachine, profile, maxBacktrack: int = NO_BACKTRACK_LIMIT, backend: str = "device",
-                   maxNodes: Optional[int] = None) -> "PrefixTree":
-        """A search for the most likely input given a PROFILE: a profile.Profile, or its [rows, nOutTok + 1] log-weight table."""
-        t = cls(em, makeNodes(em, None, backend, maxNodes, profiles=[_logRows(em, profile)]), 0, maxBacktrack, owner=True)
+                   maxNodes: Optional[int] = None, colTok=None) -> "PrefixTree":
+        """A search for the most likely input given a PROFILE: a profile.Profile, or its [rows, nOutTok + 1] log-weight table.
+        With ``colTok`` the profile is CTC-merged: a Profile read through mergeRows, or its [rows, nCols + 1] table."""
+        t = cls(em, makeNodes(em, None, backend, maxNodes, profiles=[_logRows(em, profile, colTok)], colTok=colTok), 0, maxBacktrack, owner=True)
         t.start()
         return t
 
@@ -485,14 +590,15 @@ class PrefixTree:
 
 
 def decodeBatch(em: EvaluatedMachine, outputs: Optional[Sequence[Sequence[str]]], maxBacktrack: int = NO_BACKTRACK_LIMIT, backend: str = "device",
-                maxNodes: Optional[int] = None, profiles=None) -> Tuple[List[List[str]], List[PrefixTree]]:
+                maxNodes: Optional[int] = None, profiles=None, colTok=None) -> Tuple[List[List[str]], List[PrefixTree]]:
     """doPrefixSearch for every output at once, in lock step: per round every unfinished search names the prefix it extends, and
     ONE ``extend`` (one device launch) fills the children of all of them.  A search sees exactly the fills, in the order, that it
     would see alone, so its answer and its node count are those of a single search.  Returns (decoded inputs, the searches).
-    ``profiles`` (profile.Profile objects or log-weight tables) in place of ``outputs`` decodes soft outputs."""
+    ``profiles`` (profile.Profile objects or log-weight tables) in place of ``outputs`` decodes soft outputs; with ``colTok`` they are
+    CTC-merged profiles (mergeRows tables, or Profile objects read through mergeRows) under that one column map."""
     if profiles is not None:
-        toks = [_logRows(em, p) for p in profiles]
-        nodes = makeNodes(em, None, backend, maxNodes, profiles=toks)
+        toks = [_logRows(em, p, colTok) for p in profiles]
+        nodes = makeNodes(em, None, backend, maxNodes, profiles=toks, colTok=colTok)
     else:
         toks = [em.outputTokenizer.tokenize(list(o)) for o in outputs]
         nodes = makeNodes(em, toks, backend, maxNodes)

@@ -18,7 +18,12 @@ and compare device_ms; its cells are meaningless, only its time is read.
 
 fills the roots' children against PROFILES instead (k_prefix_fill_profile): soft versions of the same outputs, 0.86 on the encoded
 symbol, 0.04 on the others and 0.02 on the blank, each jittered by up to a tenth.  Beside it the same launches through the token
-kernel on the arg-max string of each profile, for a cost per row side by side."""
+kernel on the arg-max string of each profile, for a cost per row side by side.
+
+    python scripts/bench_decode.py --merged [--out profiles/decode_merge_bench.json]
+
+fills the roots' children against the same rows read as CTC-MERGED profiles (k_prefix_fill_merged, nCols = 4: one column per output
+symbol) beside the plain profile fill on the same rows.  The figure is merged / plain at the same shape, from one session."""
 import argparse
 import json
 import os
@@ -106,9 +111,33 @@ def profile_rows(args, m, em, dm, R):
     return rows
 
 
+def merged_rows(args, m, em, dm, R):
+    nIn = em.nInTok
+    colTok = list(range(1, em.nOutTok + 1))
+    rows = []
+    for L in [int(x) for x in args.lengths.split(",")]:
+        for B in [int(x) for x in args.batches.split(",")]:
+            profs = soften(em, [em.outputTokenizer.tokenize(o) for o in outputs(m, B, L)])
+            dev = capi.DevicePrefix(dm, None, R, B * (1 + 3 * nIn), profs, colTok)
+            g_ms, g_wall = time_children(dev, B, nIn)
+            dev.close()
+            dev = capi.DevicePrefix(dm, None, R, B * (1 + 3 * nIn), profs)
+            p_ms, p_wall = time_children(dev, B, nIn)
+            dev.close()
+            fills = B * nIn
+            row = {"L": L, "searches": B, "nCols": len(colTok), "fills_per_launch": fills, "merged_device_ms": round(g_ms, 3),
+                   "merged_wall_ms": round(g_wall, 3), "merged_us_per_row": round(g_ms * 1e3 / (L + 1), 2),
+                   "merged_fills_per_s": round(fills / (g_ms * 1e-3), 1), "plain_device_ms": round(p_ms, 3),
+                   "plain_us_per_row": round(p_ms * 1e3 / (L + 1), 2), "merged_vs_plain": round(g_ms / p_ms, 2)}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", action="store_true", help="fills against profiles (k_prefix_fill_profile) beside the token kernel")
+    ap.add_argument("--merged", action="store_true", help="fills against CTC-merged profiles (k_prefix_fill_merged) beside the plain profile fill")
     ap.add_argument("--out")
     ap.add_argument("--lengths", default="200,2000")
     ap.add_argument("--batches", default="1,64")
@@ -123,7 +152,9 @@ def main():
     rows = []
     if args.profile:
         rows = profile_rows(args, m, em, dm, R)
-    for L in [] if args.profile else [int(x) for x in args.lengths.split(",")]:
+    elif args.merged:
+        rows = merged_rows(args, m, em, dm, R)
+    for L in [] if args.profile or args.merged else [int(x) for x in args.lengths.split(",")]:
         for B in [int(x) for x in args.batches.split(",")]:
             outs = outputs(m, B, L)
             toks = [em.outputTokenizer.tokenize(o) for o in outs]
