@@ -85,3 +85,57 @@ def profile_fills(em, P, paths, logR=None):
     for p in sorted(paths, key=len):
         out[p] = dp.fill(P) if not p else dp.fill(P, out[p[:-1]][0], p[-1])
     return out
+
+
+# ---- the edge suite (test_prefix_edges_gpu.py, test_prefix_host.py::test_edge_suite_inputs_are_live) --------------------------------
+def edge_profile(S, nOut, L=33):
+    """The profile of the case of prefixhelpers.EDGE_CASES with S states."""
+    return random_profile(np.random.RandomState(S + L), L, nOut)
+
+
+def lds_profile_states(nOut, ldsBytes):
+    """The largest S with 3 S + nOut + 1 doubles within ``ldsBytes`` (what k_prefix_fill_profile keeps in LDS)."""
+    return (ldsBytes // 8 - (nOut + 1)) // 3
+
+
+def lds_profile(S, nOut, L=4):
+    return random_profile(np.random.RandomState(S), L, nOut, pZero=0.0)
+
+
+def batch_profiles(nOut=5, lengths=tuple(range(10))):
+    return [random_profile(np.random.RandomState(20 + L), L, nOut) for L in lengths]
+
+
+def far_column_profile():
+    """Two rows that read mostly a, then mostly b (prefixhelpers.far_column_case)."""
+    return np.log(np.array([[0.1, 0.8, 0.1], [0.1, 0.1, 0.8]]))
+
+
+SPARSE_SEED = 0
+DEAD_ROW = 16
+
+
+def sparse_profile(L, nOut, seed=SPARSE_SEED):
+    """About a third of the symbol weights are -inf, and the blank of about a third of the rows."""
+    rng = np.random.RandomState(seed)
+    w = rng.uniform(0.05, 1.0, (L, nOut + 1))
+    with np.errstate(divide="ignore"):
+        return np.log(np.where(rng.rand(L, nOut + 1) < 1.0 / 3.0, 0.0, w))
+
+
+def dead_row_profile(L, nOut, seed=1):
+    """A dense profile whose row DEAD_ROW is -inf throughout: nothing passes it."""
+    P = random_profile(np.random.RandomState(seed), L, nOut, pZero=0.0)
+    P[DEAD_ROW] = -np.inf
+    return P
+
+
+def twin_profiles(em, outs, sharp=0.8):
+    """Soft versions of output strings: ``sharp`` on the symbol, the rest spread over the other symbols and the blank."""
+    profs = []
+    for o in outs:
+        y = em.outputTokenizer.tokenize(list(o))
+        W = np.full((len(y), em.nOutTok + 1), (1.0 - sharp) / em.nOutTok)
+        W[np.arange(len(y)), y] = sharp
+        profs.append(np.log(W))
+    return profs

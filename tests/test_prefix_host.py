@@ -232,3 +232,125 @@ def test_decode_helpers_of_the_algebra(machines):
     assert not s.inputAlphabet() and s.outputAlphabet() == m.outputAlphabet() and m.inputAlphabet()
     d = algebra.decodeSort(algebra.advancingMachine(algebra.advanceSort(t)))
     assert d.nStates() >= m.nStates() and algebra.nEmptyOutputBackTransitions(d) <= algebra.nEmptyOutputBackTransitions(t)
+
+
+def _family_refs(dp, y, nIn):
+    from prefixhelpers import family_paths
+    out = {}
+    for p in family_paths(nIn):
+        out[p] = dp.fill(y) if not p else dp.fill(y, out[p[:-1]][0], p[-1])
+    return out
+
+
+def _live_family(ref, floor, tag):
+    """Every result finite, at least ``floor`` of each layer finite."""
+    for p, (cells, lsp, lpp) in ref.items():
+        assert np.isfinite(lsp) and np.isfinite(lpp), (tag, p, lsp, lpp)
+    for layer in (0, 1):
+        fin = sum(int(np.isfinite(c[:, layer]).sum()) for c, _, _ in ref.values())
+        assert fin >= floor * sum(c[:, layer].size for c, _, _ in ref.values()), (tag, layer, fin)
+
+
+def test_edge_suite_inputs_are_live():
+    """tests/test_prefix_edges_gpu.py asserts, from the yardsticks, that its inputs are finite, dead, far down or tied where its cases
+    need them to be; the same builders of prefixhelpers.py and profileprefixhelpers.py are held to the same conditions here, so the
+    seeds are verified without a GPU."""
+    import prefixhelpers as ph
+    import profileprefixhelpers as pph
+    # 1. alphabets and lanes: every result finite, half of each layer finite, with both yardsticks
+    for S, nIn, nOut, lv in ph.EDGE_CASES:
+        em, y = ph.edge_case(S, nIn, nOut, lv)
+        assert em.nStates == S and em.nInTok == nIn and em.nOutTok == nOut and len(y) == ph.EDGE_L
+        assert (int(em.silentLevels().max()) > 0) == lv
+        R = prefixtree.logSumInTrans(em)
+        _live_family(_family_refs(prefixtree.PrefixDP(em, R), y, nIn), 0.5, ("token", S, nIn, nOut, lv))
+        _live_family(_family_refs(prefixtree.ProfilePrefixDP(em, R), pph.edge_profile(S, nOut), nIn), 0.5, ("profile", S, nIn, nOut, lv))
+    assert {c[0] for c in ph.EDGE_CASES} == {1, 2, 63, 64, 65, 1024, 1025}
+    for S in (1, 2, 63, 64, 65, 1025):
+        here = [c for c in ph.EDGE_CASES if c[0] == S]
+        assert {c[3] for c in here} == ({False} if S == 1 else {True, False}), S
+    for ab in ph.EDGE_ALPHABETS:
+        assert {c[3] for c in ph.EDGE_CASES if c[1:3] == ab} == {True, False}
+    assert all(c in ph.EDGE_CASES for c in ph.WITNESS_CASES)
+    # 2. the LDS marks: the child's two results are finite
+    for S in ph.LDS_TOKEN_STATES:
+        em, R, y = ph.lds_token_case(S)
+        dp = prefixtree.PrefixDP(em, R)
+        root = dp.fill(y)
+        child = dp.fill(y, root[0], 1)
+        assert all(np.isfinite(v) for v in root[1:] + child[1:]), (S, root[1:], child[1:])
+    assert ph.LDS_TOKEN_STATES == (64 * 1024 // 8, 64 * 1024 // 8 + 1)
+    for lds in (64 * 1024, 160 * 1024):
+        S0 = pph.lds_profile_states(2, lds)
+        assert (3 * S0 + 3) * 8 <= lds < (3 * (S0 + 1) + 3) * 8
+        for S in (S0, S0 + 1)[:2 if lds == 64 * 1024 else 1]:
+            em = ph.lds_machine(S)
+            dp = prefixtree.ProfilePrefixDP(em, ph.banded_R(S))
+            P = pph.lds_profile(S, 2)
+            root = dp.fill(P)
+            child = dp.fill(P, root[0], 1)
+            assert all(np.isfinite(v) for v in root[1:] + child[1:]), (S, root[1:], child[1:])
+    # 3. batches: every root of two symbols or rows and more is finite
+    em, ys = ph.batch_case()
+    assert (em.nStates, em.nInTok, em.nOutTok) == (40, 3, 5) and [len(y) for y in ys] == list(range(10)) and int(em.silentLevels().max()) > 0
+    R = prefixtree.logSumInTrans(em)
+    dp, pdp = prefixtree.PrefixDP(em, R), prefixtree.ProfilePrefixDP(em, R)
+    profs = pph.batch_profiles()
+    assert [len(P) for P in profs] == list(range(10))
+    for y, P in zip(ys, profs):
+        assert len(y) < 2 or (np.isfinite(dp.fill(y)[1]) and np.isfinite(pdp.fill(P)[1])), len(y)
+    # 4. the far column
+    em, R, y = ph.far_column_case()
+    s, fed = ph.COLUMN_STATE, ph.COLUMN_FED
+    for kind, dp, out in (("token", prefixtree.PrefixDP(em, R), y), ("profile", prefixtree.ProfilePrefixDP(em, R), pph.far_column_profile())):
+        for p, (cells, lsp, lpp) in _family_refs(dp, out, em.nInTok).items():
+            row = cells[1, 1]
+            V = dp.columnSums(row)
+            terms = row[:, None] + R
+            assert np.isfinite(V[s]) and np.isfinite(terms.max()) and terms[:, s].max() <= terms.max() - 800, (kind, p)
+            assert math.exp(V[s] - terms.max()) == 0.0                          # what a linear product under one maximum would keep of it
+            assert np.isfinite(cells[2, 1, fed]) and np.isfinite(lpp), (kind, p)
+            # the cell is fed through V[s] alone: one edge on b, times the row's weight of b against a profile
+            into = [(int(q), float(w)) for q, d, o, w in zip(em.src, em.dst, em.outTok, em.logWeight) if d == fed and o == 2]
+            assert {q for q, _ in into} == {s}
+            extra = 0.0 if kind == "token" else float(out[1][2])
+            want = np.logaddexp.reduce([V[s] + w + extra for _, w in into])
+            assert abs(cells[2, 1, fed] - want) <= 1e-12 * abs(want), (kind, p, cells[2, 1, fed], want)
+            assert lpp == pytest.approx(cells[2, 1, fed], rel=1e-12)          # and the node's prefix probability reads nothing else
+    # 5. sparse profiles
+    em, _ = ph.edge_case(65, 3, 5, True)
+    R = prefixtree.logSumInTrans(em)
+    pdp = prefixtree.ProfilePrefixDP(em, R)
+    P = pph.sparse_profile(ph.EDGE_L, 5)
+    assert 0.25 <= np.isneginf(P[:, 1:]).mean() <= 0.42 and 0.2 <= np.isneginf(P[:, 0]).mean() <= 0.45
+    _live_family(_family_refs(pdp, P, 3), 0.5, "sparse")
+    P = pph.dead_row_profile(ph.EDGE_L, 5)
+    assert np.isneginf(P[pph.DEAD_ROW]).all() and np.isfinite(np.delete(P, pph.DEAD_ROW, 0)).all()
+    for p, (cells, lsp, lpp) in _family_refs(pdp, P, 3).items():
+        assert lsp == -math.inf and lpp == -math.inf and np.isneginf(cells[pph.DEAD_ROW + 1:]).all(), p
+        assert np.isfinite(cells[pph.DEAD_ROW]).mean() >= 0.5, p
+    y = ph.edge_case(65, 3, 5, True)[1]
+    hot = pph.hard_profile(y, 5)
+    assert np.isneginf(hot[:, 0]).all() and (np.isfinite(hot).sum(axis=1) == 1).all()
+    _live_family(_family_refs(pdp, hot, 3), 0.5, "one-hot")
+    # 6. twins and ties: the best input of every search holds a twin symbol, and on the quantised machine children tie exactly
+    for quantised in (False, True):
+        em = ph.twin_machine(ph.TWIN_STATES, ph.TWIN_SEED, quantised)
+        e = [t for t in ph.machine_edges(em) if t[2] in (1, 2)]
+        assert e and [t[:2] + t[3:] for t in e if t[2] == 1] == [t[:2] + t[3:] for t in e if t[2] == 2]
+        assert [t[:2] + t[3:] for t in ph.machine_edges(em) if t[2] == 3] != [t[:2] + t[3:] for t in e if t[2] == 1]
+        assert int(em.silentLevels().max()) > 0
+        if quantised:
+            k = em.logWeight / math.log(0.5)
+            assert np.abs(k - np.round(k)).max() < 1e-12
+        outs = ph.twin_outputs(em, ph.TWIN_SEARCHES, ph.TWIN_L, ph.TWIN_SEED)
+        for kw in (dict(outputs=outs), dict(outputs=None, profiles=pph.twin_profiles(em, outs, 0.5 if quantised else 0.8))):
+            seqs, trees = prefixtree.decodeBatch(em, kw["outputs"], backend="numpy", profiles=kw.get("profiles"))
+            assert all(set(sq) & {"A", "B"} for sq in seqs), seqs
+            print("twin searches", quantised, seqs, [t.nFills for t in trees])
+            assert max(t.nFills for t in trees) <= 2000
+    # 7. the silent self-loop
+    em, y = ph.self_loop_case()
+    loops = [t for t in ph.machine_edges(em) if t[2] == 0 and t[3] == 0 and t[0] == t[1]]
+    assert len(loops) == 1 and loops[0][0] == 0 and int(em.silentLevels().max()) > 0
+    _live_family(_family_refs(prefixtree.PrefixDP(em), y, 3), 0.5, "self-loop")
