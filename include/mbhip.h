@@ -178,6 +178,34 @@ mb_profiles *mb_profiles_create_merged(mb_machine *m, int64_t nProfiles, const d
 int mb_profile_fill_merged(mb_machine *m, int mode, const double *logP, int64_t nRows, int32_t nCols, const int32_t *colTok,
                            double *cellsOut);
 
+/* Pairs: a known input sequence against a profile (`--recognize-csv` beside --input-chars / --input-fasta / --input-json): the
+ * semantics of compose(M, transpose(CSVProfile::machine())) on input x[1..I] with an empty output, for a machine WITH an input
+ * alphabet, swept natively over (I + 1) x (rows + 1) x 2 x nStates along anti-diagonals (docs/profile_tapes.md, "Pairs: an input
+ * sequence against a profile").  Pair k = input tokens inTok[inOff[k]..inOff[k+1]) (1..nInTok) and rows rowOff[k]..rowOff[k+1) of
+ * logP (rows as mb_profiles_create).  Layer 0 (N) = arrived at (i, row), where alone the blank may fire; layer 1 (W) = after the
+ * machine's output-less moves there (input-only edges from (i-1, row), then the silent levels).  Viterbi keeps the first maximum:
+ * into N the blank, then the match edges (in = x_i, an output) in `incoming` order, then the output-only edges in `incoming` order;
+ * into W "no move", then the input-only edges, then the silent edges, each in `incoming` order.  Paths are the machine's global edge
+ * ids, start -> end; pathRow (may be NULL) is the row an emitting edge consumed, for an output-less edge the number of rows consumed
+ * before it; the input position follows by counting the input-consuming edges.  A pair whose score is -inf gets an empty path and
+ * adds nothing to the counts; blank rows are not edges.  pathCap must hold the sum of mb_profile_pair_path_bound over the pairs
+ * (I + L + (I + L + 1) * (silent levels)).  Counts with MB_DETERMINISTIC=1 go through 64-bit fixed point and are the same bits from
+ * call to call.  Materialised lattices: cells[(((i*(nRows+1)) + row)*2 + layer)*nStates + state]; mb_profile_pair_fill:
+ * cellsOut[(nIn+1)*(nRows+1)*2*nStates], mode MB_FORWARD / MB_VITERBI / MB_BACKWARD (Backward: layer 0 = from the arrived stage).
+ * Errors, before anything is launched: a token outside 1..nInTok (any token, for a machine without inputs), NaN / +inf weights, a
+ * pathCap below the bound, a lattice beyond the memory budget on its own.  An input the machine cannot read scores -inf. */
+typedef struct mb_profile_pairs mb_profile_pairs;
+mb_profile_pairs *mb_profile_pairs_create(mb_machine *m, int64_t nPairs, const int32_t *inTok, const int64_t *inOff,
+                                          const double *logP, const int64_t *rowOff);
+void mb_profile_pairs_destroy(mb_profile_pairs *p);
+int mb_profile_pairs_forward(mb_profile_pairs *p, int flags /* MB_ROLLING | MB_MATERIALISE */, double *loglike);
+int64_t mb_profile_pair_path_bound(const mb_machine *m, int64_t nIn, int64_t nRows);
+int mb_profile_pairs_viterbi(mb_profile_pairs *p, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow,
+                             int64_t pathCap);
+int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglikeSum, double *loglike);
+int mb_profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows,
+                         double *cellsOut);
+
 /* ---- prefix search: imputing the input tape (--prefix-decode / --prefix-encode / --random-encode) -------------------------------
  * The node fill of the reference's PrefixTree (src/ctc.cpp:25-88) on the device, the tree and its heap on the host
  * (docs/decoding.md).  An mb_prefix holds nSeq searches (output sequence k = outTok[outOff[k]..outOff[k+1]), tokens 1..nOutTok)

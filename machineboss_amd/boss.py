@@ -399,12 +399,18 @@ def runProfile(args, out) -> int:
         raise MachineError("--recognize-csv supports -L, -V and -C")
     if not (args.loglike or args.viterbi or args.counts):
         raise MachineError("--recognize-csv needs -L, -V or -C")
-    if args.recognize_chars is not None or args.data or args.input_chars is not None or args.output_chars is not None or \
-            args.input_fasta or args.output_fasta or args.input_json or args.output_json:
+    if args.recognize_chars is not None or args.data or args.output_chars is not None or args.output_fasta or args.output_json:
         raise MachineError("--recognize-csv takes no other sequence data")
+    hasInput = args.input_chars is not None or bool(args.input_fasta) or bool(args.input_json)
+    if hasInput and args.merge:
+        raise MachineError("--recognize-merge-csv takes no input sequence: two-tape sweeps take plain profiles (--recognize-csv)")
     if _dist() is not None and _dist().get_world_size() > 1:
         raise MachineError("--recognize-csv runs on one rank")
     machine = loadMachine(args)
+    if hasInput:
+        if not machine.inputAlphabet():
+            raise MachineError("--recognize-csv takes no other sequence data: the machine has no input alphabet to read an input sequence")
+        return _runProfilePairs(args, out, machine)
     if machine.inputAlphabet():
         raise MachineError("--recognize-csv needs a machine with an empty input alphabet (compose a generator in front); input alphabet: %s"
                            % ",".join(machine.inputAlphabet()))
@@ -434,6 +440,65 @@ def runProfile(args, out) -> int:
     if args.viterbi:
         out.write('[["","",%s]]\n' % fmt(prof.viterbi(paths=False)[0][0]))
     prof.close(); dm.close()
+    return 0
+
+
+def _runProfilePairs(args, out, machine: Machine) -> int:
+    """--recognize-csv beside --input-chars / --input-fasta / --input-json on a machine with an input alphabet: every input
+    sequence is one pair with the profile (docs/profile_tapes.md, "Pairs"), all pairs in one batch.  -L and -V print one
+    [input name, "", score] per pair, -C the counts summed over the pairs.  --decode-backend numpy: profile.PairProfileDP."""
+    import numpy as np
+    from . import dp
+    from .profile import PairProfileDP, Profile
+    if not os.path.exists(args.recognize_csv):
+        raise MachineError("CSV file not found")
+    profile = Profile.fromCsv(args.recognize_csv)
+    params = _profileParams(args, machine)
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    inSeqs: List[Tuple[str, List[str]]] = []
+    if args.input_fasta:
+        inSeqs += [(n, list(s)) for n, s in readFasta(args.input_fasta)]
+    if args.input_chars is not None:
+        inSeqs.append((args.input_chars, list(args.input_chars)))
+    if args.input_json:
+        j = json.load(open(args.input_json)); inSeqs.append((j.get("name", ""), list(j["sequence"])))
+    # as the --loglike loop (dp.loglikeBatch): a sequence that cannot be tokenised scores -inf and adds nothing to the counts
+    ok = [ev.inputTokenizer.canTokenize(seq) for _, seq in inSeqs]
+    xs = [np.asarray(ev.inputTokenizer.tokenize(seq), np.int64).reshape(-1) for (_, seq), k in zip(inSeqs, ok) if k]
+    P = profile.logRows(ev)
+    counts = dp.MachineCounts(ev)
+    if args.decode_backend == "numpy":
+        pdp = PairProfileDP(ev)
+        fwd = [pdp.forward(x, P)[0] for x in xs] if args.loglike else None
+        if args.counts:
+            for x in xs:
+                c, ll = pdp.counts(x, P)
+                counts._flat += c
+                counts.loglike += ll
+        vit = [pdp.forward(x, P, "max")[0] for x in xs] if args.viterbi else None
+    else:
+        from . import capi
+        dm = capi.DeviceMachine(ev)
+        pairs = capi.DeviceProfilePairs(dm, xs, [P] * len(xs))
+        try:
+            fwd = pairs.forward(capi.MB_ROLLING) if args.loglike else None
+            if args.counts:
+                _, s, _ = pairs.counts(counts._flat)
+                counts.loglike += s
+            vit = pairs.viterbi(paths=False)[0] if args.viterbi else None
+        finally:
+            pairs.close(); dm.close()
+
+    def scores(v):
+        it = iter(v)
+        return "[" + ",".join('["%s","",%s]' % (escaped(n), fmt(float(next(it)) if k else -math.inf)) for (n, _), k in zip(inSeqs, ok)) + "]\n"
+    if args.loglike:
+        out.write(scores(fwd))
+    if args.counts:
+        pc = counts.paramCounts(machine, params)
+        out.write("{" + ",".join('"%s":%s' % (escaped(k), "%g" % pc[k]) for k in sorted(pc)) + "}\n")
+    if args.viterbi:
+        out.write(scores(vit))
     return 0
 
 

@@ -30,6 +30,8 @@ EXPORTS = [
     "mb_comm_unique_id", "mb_comm_init", "mb_comm_destroy", "mb_allreduce_counts",
     "mb_profiles_create", "mb_profiles_destroy", "mb_profiles_forward", "mb_profile_path_bound", "mb_profiles_viterbi",
     "mb_profiles_counts", "mb_profile_fill", "mb_profiles_create_merged", "mb_profile_fill_merged",
+    "mb_profile_pairs_create", "mb_profile_pairs_destroy", "mb_profile_pairs_forward", "mb_profile_pair_path_bound",
+    "mb_profile_pairs_viterbi", "mb_profile_pairs_counts", "mb_profile_pair_fill",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
     "mb_prefix_node_cells", "mb_prefix_create_profiles", "mb_prefix_create_merged",
 ]
@@ -116,6 +118,14 @@ def load():
     L.mb_profiles_create_merged.restype = vp
     L.mb_profiles_create_merged.argtypes = [vp, C.c_int64, dp, i64p, C.c_int32, i32p]
     L.mb_profile_fill_merged.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_int32, i32p, dp]
+    L.mb_profile_pairs_create.restype = vp
+    L.mb_profile_pairs_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, i64p]
+    L.mb_profile_pairs_destroy.argtypes = [vp]; L.mb_profile_pairs_destroy.restype = None
+    L.mb_profile_pairs_forward.argtypes = [vp, C.c_int, dp]
+    L.mb_profile_pair_path_bound.argtypes = [vp, C.c_int64, C.c_int64]; L.mb_profile_pair_path_bound.restype = C.c_int64
+    L.mb_profile_pairs_viterbi.argtypes = [vp, dp, i64p, u32p, i32p, C.c_int64]
+    L.mb_profile_pairs_counts.argtypes = [vp, dp, dp, dp]
+    L.mb_profile_pair_fill.argtypes = [vp, C.c_int, i32p, C.c_int64, dp, C.c_int64, dp]
     L.mb_prefix_create.restype = vp
     L.mb_prefix_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, C.c_int64]
     L.mb_prefix_create_profiles.restype = vp
@@ -627,6 +637,83 @@ def profile_fill_merged(dm: DeviceMachine, mode: int, logP, colTok) -> np.ndarra
     P = np.ascontiguousarray(np.asarray(logP, np.float64).reshape(-1, len(ct) + 1))
     cells = np.empty((len(P) + 1, 2, len(ct) + 1, dm.nStates), np.float64)
     _check(load().mb_profile_fill_merged(dm.h, mode, _p(P, C.c_double), len(P), len(ct), _p(ct, C.c_int32), _p(cells, C.c_double)))
+    return cells
+
+
+class DeviceProfilePairs:
+    """Device-resident batch of (input sequence, profile) pairs (mb_profile_pairs*) for a machine with an input alphabet: pair k is
+    the token sequence ``inputs[k]`` (1..nInTok) against the [rows, nOutTok + 1] log weights ``profiles[k]``, column 0 = the blank
+    (profile.Profile.logRows).  The yardstick is profile.PairProfileDP (docs/profile_tapes.md, "Pairs")."""
+
+    def __init__(self, dm: DeviceMachine, inputs, profiles):
+        self.dm = dm
+        width = dm.em.nOutTok + 1
+        rows = [np.asarray(p, np.float64).reshape(-1, width) for p in profiles]
+        xs = [np.asarray(x, np.int64).reshape(-1) for x in inputs]
+        if len(xs) != len(rows):
+            raise ValueError("as many input sequences as profiles, please")
+        self.nPairs = len(rows)
+        self.rowOff = np.zeros(self.nPairs + 1, np.int64); self.inOff = np.zeros(self.nPairs + 1, np.int64)
+        for k, (x, r) in enumerate(zip(xs, rows)):
+            self.rowOff[k + 1] = self.rowOff[k] + len(r)
+            self.inOff[k + 1] = self.inOff[k] + len(x)
+        self.logP = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((1, width)), np.float64)
+        self.inTok = np.ascontiguousarray(np.concatenate(xs + [np.zeros(1, np.int64)]), np.int32)
+        L = load()
+        self.h = L.mb_profile_pairs_create(dm.h, self.nPairs, _p(self.inTok, C.c_int32), _p(self.inOff, C.c_int64),
+                                           _p(self.logP, C.c_double), _p(self.rowOff, C.c_int64))
+        if not self.h:
+            raise MbError(L.mb_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            try:
+                _lib.mb_profile_pairs_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    __del__ = close
+
+    def path_cap(self) -> int:
+        L = load()
+        return int(sum(L.mb_profile_pair_path_bound(self.dm.h, int(i), int(r)) for i, r in zip(np.diff(self.inOff), np.diff(self.rowOff))))
+
+    def forward(self, flags: int = MB_ROLLING) -> np.ndarray:
+        ll = np.empty(self.nPairs, np.float64)
+        _check(load().mb_profile_pairs_forward(self.h, flags, _p(ll, C.c_double)))
+        return ll
+
+    def viterbi(self, paths: bool = True, cap: Optional[int] = None):
+        """Returns (loglike, pathOff, pathEdges, pathRow); the last three are None without paths.  ``cap``: the size of the path
+        buffers (default: the sum of the pairs' path bounds, which is what the library asks for)."""
+        ll = np.empty(self.nPairs, np.float64)
+        if not paths:
+            _check(load().mb_profile_pairs_viterbi(self.h, _p(ll, C.c_double), None, None, None, 0))
+            return ll, None, None, None
+        cap = self.path_cap() if cap is None else int(cap)
+        off = np.zeros(self.nPairs + 1, np.int64)
+        edges = np.empty(max(cap, 1), np.uint32); rows = np.empty(max(cap, 1), np.int32)
+        _check(load().mb_profile_pairs_viterbi(self.h, _p(ll, C.c_double), _p(off, C.c_int64), _p(edges, C.c_uint32), _p(rows, C.c_int32), cap))
+        return ll, off, edges[:off[-1]].copy(), rows[:off[-1]].copy()
+
+    def counts(self, counts: Optional[np.ndarray] = None):
+        """Returns (counts[nTrans], loglikeSum, loglike[nPairs]); accumulates into ``counts`` if given."""
+        if counts is None:
+            counts = np.zeros(self.dm.nTrans, np.float64)
+        assert counts.dtype == np.float64 and counts.shape == (self.dm.nTrans,) and counts.flags.c_contiguous
+        s = C.c_double(0.0)
+        ll = np.empty(self.nPairs, np.float64)
+        _check(load().mb_profile_pairs_counts(self.h, _p(counts, C.c_double), C.byref(s), _p(ll, C.c_double)))
+        return counts, s.value, ll
+
+
+def profile_pair_fill(dm: DeviceMachine, mode: int, x, logP) -> np.ndarray:
+    """One pair's lattice [len(x) + 1, rows + 1, 2, nStates] (layer 0 = arrived at (i, row), 1 = after the output-less moves)."""
+    P = np.ascontiguousarray(np.asarray(logP, np.float64).reshape(-1, dm.em.nOutTok + 1))
+    xs = np.ascontiguousarray(np.asarray(x, np.int64).reshape(-1), np.int32)
+    cells = np.empty((len(xs) + 1, len(P) + 1, 2, dm.nStates), np.float64)
+    _check(load().mb_profile_pair_fill(dm.h, mode, _p(xs, C.c_int32), len(xs), _p(P, C.c_double), len(P), _p(cells, C.c_double)))
     return cells
 
 

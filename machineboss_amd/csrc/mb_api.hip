@@ -18,6 +18,7 @@
 #include "mb_prefix.h"
 #include "mb_profile.h"
 #include "mb_profile_merge.h"
+#include "mb_profile_pair.h"
 #include "mb_small.h"
 #include "mb_usage.h"
 #include "mb_wide.h"
@@ -2457,6 +2458,302 @@ int mb_profile_fill_merged(mb_machine *m, int mode, const double *logP, int64_t 
   ApiGuard guard;
   if (!merge_map_ok(m, nCols, colTok)) return 1;
   return profile_fill(m, mode, logP, nRows, nCols, colTok, cellsOut);
+}
+
+// ---- two-tape profile sweeps: an input sequence against a profile (mb_profile_pair.hip, docs/profile_tapes.md "Pairs") ----------
+// Split the pairs into chunks whose device memory (bytesPer(pair k)) fits the budget; even-sized like profile_chunks.
+static bool pair_profile_chunks(const mb_profile_pairs *p, const std::function<double(long long)> &bytesPer, std::vector<Chunk> &out) {
+  const double budget = (double)budget_bytes();
+  double total = 0.0;
+  for (long long k = 0; k < p->n; ++k) {
+    const double b = bytesPer(k);
+    if (b > budget) { set_error("one pair's DP lattice (" + std::to_string((long long)b) + " bytes) exceeds the device memory budget"); return false; }
+    total += b;
+  }
+  const double nChunks = std::max(1.0, std::ceil(total / budget));
+  const double share = std::min(budget, total / nChunks * 1.05);
+  long long p0 = 0;
+  double acc = 0.0;
+  for (long long k = 0; k < p->n; ++k) {
+    const double b = bytesPer(k);
+    if (k > p0 && (acc + b > budget || (acc >= share && acc + b > share) || k - p0 >= (1 << 30))) { out.push_back({p0, k, 0}); p0 = k; acc = 0.0; }
+    acc += b;
+  }
+  if (p->n > p0) out.push_back({p0, p->n, 0});
+  return true;
+}
+
+static long long pp_in(const mb_profile_pairs *p, long long k) { return p->inOff[k + 1] - p->inOff[k]; }
+static long long pp_rows(const mb_profile_pairs *p, long long k) { return p->rowOff[k + 1] - p->rowOff[k]; }
+static double pp_cell_bytes(const mb_profile_pairs *p, long long k) { return 8.0 * (double)profile_pair_cells(p->m->S, pp_in(p, k), pp_rows(p, k)); }
+// bytes of global scratch the rolling sweep of pair k needs (0: its ring is in LDS)
+static double pp_ring_bytes(const mb_profile_pairs *p, long long k) {
+  return profile_pair_lds_bytes(p->m->S, pp_in(p, k), pp_rows(p, k)) ? 0.0 : 8.0 * (double)profile_pair_ring(p->m->S, pp_in(p, k), pp_rows(p, k));
+}
+
+struct PairProfPlan { PairProfDesc *d = nullptr; long long cells = 0, paths = 0, ring = 0, maxItems = 0; size_t lds = 0; };
+
+// descriptors of pairs [p0, p1): lattices, traceback slots and scratch rings packed from 0
+static int pair_profile_descs(const mb_profile_pairs *p, long long p0, long long p1, bool rolling, PairProfPlan &pl) {
+  std::vector<PairProfDesc> h((size_t)(p1 - p0));
+  const int S = p->m->S;
+  for (long long k = p0; k < p1; ++k) {
+    PairProfDesc &d = h[(size_t)(k - p0)];
+    const long long I = pp_in(p, k), L = pp_rows(p, k);
+    d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)I; d.nRows = (int)L;
+    d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = -1;
+    pl.cells += profile_pair_cells(S, I, L);
+    pl.paths += profile_pair_path_bound(p->m->nLevF, I, L);
+    pl.maxItems = std::max(pl.maxItems, (std::min(I, L) + 1) * S);
+    if (rolling) {
+      const size_t lds = profile_pair_lds_bytes(S, I, L);
+      if (lds) pl.lds = std::max(pl.lds, lds);
+      else { d.ringBase = pl.ring; pl.ring += profile_pair_ring(S, I, L); }
+    }
+  }
+  MB_HIP(sm_alloc((void **)&pl.d, std::max<size_t>(h.size(), 1) * sizeof(PairProfDesc)));
+  if (!h.empty() && (!hip_ok(hipMemcpyAsync(pl.d, h.data(), h.size() * sizeof(PairProfDesc), hipMemcpyHostToDevice, g_stream), "H2D pair descriptors") ||
+                     !hip_ok(hipStreamSynchronize(g_stream), "H2D pair descriptors"))) { sm_free(pl.d); pl.d = nullptr; return 1; }
+  return 0;
+}
+
+// Forward (MB_FORWARD) or Viterbi scores without paths (MB_VITERBI); mat: through the materialised lattice
+static int pair_profile_scores(mb_profile_pairs *p, int mode, bool mat, double *loglike) {
+  std::vector<Chunk> chunks;
+  if (!pair_profile_chunks(p, [&](long long k) { return mat ? pp_cell_bytes(p, k) : pp_ring_bytes(p, k); }, chunks)) return 1;
+  double *d_ll = nullptr;
+  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
+  int rc = 0;
+  Timer tm;
+  for (const Chunk &c : chunks) {
+    PairProfPlan pl;
+    if ((rc = pair_profile_descs(p, c.p0, c.p1, !mat, pl))) break;
+    double *pool = nullptr, *scratch = nullptr;
+    if (mat) { pool = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double)); if (!pool) rc = 1; }
+    else if (pl.ring) { scratch = (double *)ws_get(1, (size_t)pl.ring * sizeof(double)); if (!scratch) rc = 1; }
+    if (!rc) {
+      tm.start();
+      rc = launch_profile_pair_fwd(p->m, mode, mat, pl.d, (int)(c.p1 - c.p0), pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, d_ll + c.p0, g_stream);
+      g_last_ms += tm.stop();
+      ++g_last_launches;
+    }
+    if (rc) quiesce_streams();
+    sm_free(pl.d);
+    if (rc) break;
+  }
+  if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  sm_free(d_ll);
+  g_last_kernel = mode == MB_VITERBI ? (mat ? "k_profile_pair_fwd<max,mat>" : "k_profile_pair_fwd<max,rolling>")
+                                     : (mat ? "k_profile_pair_fwd<sum,mat>" : "k_profile_pair_fwd<sum,rolling>");
+  return rc;
+}
+
+mb_profile_pairs *mb_profile_pairs_create(mb_machine *m, int64_t nPairs, const int32_t *inTok, const int64_t *inOff, const double *logP, const int64_t *rowOff) {
+  ApiGuard guard;
+  if (!m || nPairs < 0 || (nPairs > 0 && (!rowOff || !inOff))) { set_error("null argument"); return nullptr; }
+  if (ensure_init()) return nullptr;
+  mb_profile_pairs *p = new mb_profile_pairs();
+  p->m = m; p->n = nPairs;
+  p->rowOff.assign((size_t)nPairs + 1, 0); p->inOff.assign((size_t)nPairs + 1, 0);
+  for (long long k = 0; k < nPairs; ++k) {
+    const long long L = rowOff[k + 1] - rowOff[k], I = inOff[k + 1] - inOff[k];
+    if (L < 0 || L > 0x3fffffff || I < 0 || I > 0x3fffffff) { set_error("bad pair offsets"); delete p; return nullptr; }
+    if ((double)(std::min(I, L) + 1) * m->S > 2147483647.0) { set_error("pair " + std::to_string(k) + ": an anti-diagonal of the lattice has more than 2^31 cells"); delete p; return nullptr; }
+    p->rowOff[(size_t)k + 1] = p->rowOff[(size_t)k] + L;
+    p->inOff[(size_t)k + 1] = p->inOff[(size_t)k] + I;
+  }
+  p->totalRows = p->rowOff.back(); p->totalIn = p->inOff.back();
+  const long long C = m->nOut + 1, nv = p->totalRows * C;
+  const double *v0 = logP ? logP + (nPairs ? rowOff[0] * C : 0) : nullptr;
+  const int32_t *x0 = inTok ? inTok + (nPairs ? inOff[0] : 0) : nullptr;
+  if ((nv && !v0) || (p->totalIn && !x0)) { set_error("null argument"); delete p; return nullptr; }
+  for (long long k = 0; k < p->totalIn; ++k)
+    if (x0[k] < 1 || x0[k] > m->nIn) {
+      set_error("input token " + std::to_string(x0[k]) + " at position " + std::to_string(k) + " is outside 1..nInTok (" + std::to_string(m->nIn) + ")");
+      delete p; return nullptr;
+    }
+  if (!profile_values_ok(v0, nv)) { delete p; return nullptr; }
+  if (!hip_ok(hipMalloc((void **)&p->d_logP, (size_t)std::max<long long>(nv, 1) * sizeof(double)), "hipMalloc(pair profiles)") ||
+      !hip_ok(hipMalloc((void **)&p->d_in, (size_t)std::max<long long>(p->totalIn, 1) * sizeof(int)), "hipMalloc(pair inputs)")) { mb_profile_pairs_destroy(p); return nullptr; }
+  if (nv && h2d_large(p->d_logP, v0, (size_t)nv * sizeof(double))) { mb_profile_pairs_destroy(p); return nullptr; }
+  if (p->totalIn && h2d_large(p->d_in, x0, (size_t)p->totalIn * sizeof(int))) { mb_profile_pairs_destroy(p); return nullptr; }
+  if (!hip_ok(hipStreamSynchronize(g_stream), "H2D pairs")) { mb_profile_pairs_destroy(p); return nullptr; }
+  return p;
+}
+
+void mb_profile_pairs_destroy(mb_profile_pairs *p) {
+  ApiGuard guard;
+  if (!p) return;
+  if (p->d_logP) (void)hipFree(p->d_logP);
+  if (p->d_in) (void)hipFree(p->d_in);
+  delete p;
+}
+
+int mb_profile_pairs_forward(mb_profile_pairs *p, int flags, double *loglike) {
+  ApiGuard guard;
+  if (!p || (!loglike && p->n)) { set_error("null argument"); return 1; }
+  if (flags != MB_ROLLING && flags != MB_MATERIALISE) { set_error("unknown flags"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  return pair_profile_scores(p, MB_FORWARD, flags == MB_MATERIALISE, loglike);
+}
+
+int64_t mb_profile_pair_path_bound(const mb_machine *m, int64_t nIn, int64_t nRows) {
+  if (!m || nIn < 0 || nRows < 0) return 0;
+  return profile_pair_path_bound(m->nLevF, nIn, nRows);
+}
+
+int mb_profile_pairs_viterbi(mb_profile_pairs *p, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow, int64_t pathCap) {
+  ApiGuard guard;
+  if (!p || (!loglike && p->n)) { set_error("null argument"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  if (!pathEdges || !pathOff) return pair_profile_scores(p, MB_VITERBI, false, loglike);
+  const mb_machine *m = p->m;
+  long long need = 0;
+  for (long long k = 0; k < p->n; ++k) need += profile_pair_path_bound(m->nLevF, pp_in(p, k), pp_rows(p, k));
+  if (pathCap < need) { set_error("pathCap too small for the Viterbi paths: " + std::to_string((long long)pathCap) + " entries, the path bounds of the pairs sum to " + std::to_string(need)); return 1; }
+  std::vector<Chunk> chunks;
+  auto bytes = [&](long long k) { return pp_cell_bytes(p, k) + 8.0 * profile_pair_path_bound(m->nLevF, pp_in(p, k), pp_rows(p, k)); };
+  if (!pair_profile_chunks(p, bytes, chunks)) return 1;
+  double *d_ll = nullptr;
+  long long *d_len = nullptr;
+  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
+  if (!hip_ok(sm_alloc((void **)&d_len, std::max<long long>(p->n, 1) * sizeof(long long)), "hipMalloc(path lengths)")) { sm_free(d_ll); return 1; }
+  int rc = 0;
+  Timer tm;
+  long long written = 0;
+  pathOff[0] = 0;
+  std::vector<long long> len;
+  std::vector<uint32_t> he;
+  std::vector<int32_t> hr;
+  for (const Chunk &c : chunks) {
+    PairProfPlan pl;
+    if ((rc = pair_profile_descs(p, c.p0, c.p1, false, pl))) break;
+    const long long np = c.p1 - c.p0, paths = pl.paths;
+    double *pool = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
+    uint32_t *d_e = (uint32_t *)ws_get(3, (size_t)std::max<long long>(paths, 1) * sizeof(uint32_t));
+    int32_t *d_r = (int32_t *)ws_get(4, (size_t)std::max<long long>(paths, 1) * sizeof(int32_t));
+    if (!pool || !d_e || !d_r) rc = 1;
+    if (!rc) {
+      tm.start();
+      rc = launch_profile_pair_fwd(m, MB_VITERBI, true, pl.d, (int)np, 0, pl.maxItems, p->d_in, p->d_logP, pool, nullptr, d_ll + c.p0, g_stream);
+      if (!rc) rc = launch_profile_pair_traceback(m, pl.d, (int)np, p->d_in, p->d_logP, pool, d_e, d_r, d_len + c.p0, g_stream);
+      g_last_ms += tm.stop();
+      ++g_last_launches;
+    }
+    len.resize((size_t)np); he.resize((size_t)std::max<long long>(paths, 1)); hr.resize(he.size());
+    if (!rc && !hip_ok(hipMemcpy(len.data(), d_len + c.p0, np * sizeof(long long), hipMemcpyDeviceToHost), "D2H path lengths")) rc = 1;
+    if (!rc && paths && (d2h_large(he.data(), d_e, paths * sizeof(uint32_t)) || (pathRow && d2h_large(hr.data(), d_r, paths * sizeof(int32_t))))) rc = 1;
+    long long base = 0;
+    for (long long k = 0; k < np && !rc; ++k) {
+      long long n = len[(size_t)k];
+      if (n == -1) n = 0;   // no finite path: an empty one, as mb_profiles_viterbi
+      else if (n < 0) { set_error(n == -2 ? "pair traceback overflowed its bound" : "pair traceback found no matching candidate"); rc = 1; break; }
+      std::memcpy(pathEdges + written, he.data() + base, (size_t)n * sizeof(uint32_t));
+      if (pathRow) std::memcpy(pathRow + written, hr.data() + base, (size_t)n * sizeof(int32_t));
+      written += n;
+      pathOff[c.p0 + k + 1] = written;
+      base += profile_pair_path_bound(m->nLevF, pp_in(p, c.p0 + k), pp_rows(p, c.p0 + k));
+    }
+    if (rc) quiesce_streams();
+    sm_free(pl.d);
+    if (rc) break;
+  }
+  if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  sm_free(d_ll); sm_free(d_len);
+  g_last_kernel = "k_profile_pair_fwd<max,mat>";
+  return rc;
+}
+
+int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglikeSum, double *loglike) {
+  ApiGuard guard;
+  if (!p || !counts) { set_error("null argument"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
+  const mb_machine *m = p->m;
+  const long long nT = m->nTrans;
+  std::vector<Chunk> chunks;
+  if (!pair_profile_chunks(p, [&](long long k) { return 2.0 * pp_cell_bytes(p, k); }, chunks)) return 1;   // the Forward and the Backward lattice
+  double *d_ll = nullptr, *d_bll = nullptr, *d_cc = nullptr;
+  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
+  if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
+      !hip_ok(sm_alloc((void **)&d_cc, std::max<long long>(nT, 1) * sizeof(double)), "hipMalloc(counts)")) { sm_free(d_ll); sm_free(d_bll); sm_free(d_cc); return 1; }
+  int rc = 0;
+  Timer tm;
+  std::vector<double> total((size_t)nT, 0.0), hc((size_t)nT);
+  for (const Chunk &c : chunks) {
+    PairProfPlan pl;
+    if ((rc = pair_profile_descs(p, c.p0, c.p1, false, pl))) break;
+    const long long np = c.p1 - c.p0;
+    double *fwd = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
+    double *bwd = (double *)ws_get(1, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
+    if (!fwd || !bwd) rc = 1;
+    long long maxCells = 0;
+    for (long long k = c.p0; k < c.p1; ++k) maxCells = std::max(maxCells, profile_pair_cells(m->S, pp_in(p, k), pp_rows(p, k)) / 2);
+    const int groups = (int)std::min<long long>(256, std::max<long long>(1, (maxCells + 2047) / 2048));
+    if (!rc && np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); rc = 1; }
+    if (!rc) {
+      tm.start();
+      rc = launch_profile_pair_fwd(m, MB_FORWARD, true, pl.d, (int)np, 0, pl.maxItems, p->d_in, p->d_logP, fwd, nullptr, d_ll + c.p0, g_stream);
+      if (!rc) rc = launch_profile_pair_bwd(m, pl.d, (int)np, pl.maxItems, p->d_in, p->d_logP, bwd, d_bll + c.p0, g_stream);
+      if (!rc && nT) rc = hip_ok(hipMemsetAsync(d_cc, 0, (size_t)nT * sizeof(double), g_stream), "memset(counts)") ? 0 : 1;
+      if (!rc) rc = launch_profile_pair_counts(m, pl.d, (int)np, groups, p->d_in, p->d_logP, fwd, bwd, d_cc, g_stream);
+      g_last_ms += tm.stop();
+      ++g_last_launches;
+    }
+    if (!rc && nT && !hip_ok(hipMemcpy(hc.data(), d_cc, nT * sizeof(double), hipMemcpyDeviceToHost), "D2H counts")) rc = 1;
+    if (!rc && g_deterministic)
+      for (long long e = 0; e < nT && !rc; ++e) {      // fixed point, 2^-36
+        unsigned long long u; std::memcpy(&u, &hc[(size_t)e], 8);
+        if (!det_to_double(u, hc[(size_t)e])) { set_error("MB_DETERMINISTIC: a posterior count left the fixed-point range (6.7e7 per transition and call): split the batch or use the floating-point mode"); rc = 1; }
+      }
+    if (!rc) for (long long e = 0; e < nT; ++e) total[(size_t)e] += hc[(size_t)e];
+    if (rc) quiesce_streams();
+    sm_free(pl.d);
+    if (rc) break;
+  }
+  std::vector<double> hll((size_t)p->n);
+  if (!rc && p->n && !hip_ok(hipMemcpy(hll.data(), d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  sm_free(d_ll); sm_free(d_bll); sm_free(d_cc);
+  g_last_kernel = "k_profile_pair_counts";
+  if (rc) return rc;
+  for (long long e = 0; e < nT; ++e) counts[e] += total[(size_t)e];
+  double s = 0.0;
+  for (long long k = 0; k < p->n; ++k) { s += hll[(size_t)k]; if (loglike) loglike[k] = hll[(size_t)k]; }
+  if (loglikeSum) *loglikeSum += s;
+  return 0;
+}
+
+int mb_profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, double *cellsOut) {
+  ApiGuard guard;
+  if (!m || !cellsOut || nRows < 0 || nIn < 0 || (nRows && !logP) || (nIn && !inTok)) { set_error("null argument"); return 1; }
+  if (mode != MB_FORWARD && mode != MB_VITERBI && mode != MB_BACKWARD) { set_error("unknown fill mode"); return 1; }
+  if (ensure_init()) return 1;
+  g_last_ms = 0.0; g_last_launches = 0;
+  const int64_t rOff[2] = {0, nRows}, iOff[2] = {0, nIn};
+  mb_profile_pairs *p = mb_profile_pairs_create(m, 1, inTok, iOff, logP, rOff);
+  if (!p) return 1;
+  std::vector<Chunk> chunks;
+  if (!pair_profile_chunks(p, [&](long long k) { return pp_cell_bytes(p, k); }, chunks)) { mb_profile_pairs_destroy(p); return 1; }
+  PairProfPlan pl;
+  int rc = pair_profile_descs(p, 0, 1, false, pl);
+  double *d_ll = nullptr;
+  if (!rc && !hip_ok(sm_alloc((void **)&d_ll, sizeof(double)), "hipMalloc(loglike)")) rc = 1;
+  double *pool = rc ? nullptr : (double *)ws_get(0, (size_t)pl.cells * sizeof(double));
+  if (!rc && !pool) rc = 1;
+  if (!rc) {
+    Timer tm;
+    tm.start();
+    rc = mode == MB_BACKWARD ? launch_profile_pair_bwd(m, pl.d, 1, pl.maxItems, p->d_in, p->d_logP, pool, d_ll, g_stream)
+                             : launch_profile_pair_fwd(m, mode, true, pl.d, 1, 0, pl.maxItems, p->d_in, p->d_logP, pool, nullptr, d_ll, g_stream);
+    g_last_ms += tm.stop();
+    g_last_launches = 1;
+  }
+  if (!rc) rc = d2h_large(cellsOut, pool, (size_t)pl.cells * sizeof(double));
+  if (rc) quiesce_streams();
+  sm_free(pl.d); sm_free(d_ll);
+  g_last_kernel = mode == MB_BACKWARD ? "k_profile_pair_bwd" : (mode == MB_VITERBI ? "k_profile_pair_fwd<max,mat>" : "k_profile_pair_fwd<sum,mat>");
+  mb_profile_pairs_destroy(p);
+  return rc;
 }
 
 // ---- prefix search: node fills on the device, the tree on the host (mb_prefix.hip, docs/decoding.md) --------------------------

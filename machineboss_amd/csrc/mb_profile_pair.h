@@ -1,0 +1,53 @@
+// mb_profile_pair.h -- two-tape profile sweeps: a machine with an input alphabet, a known input sequence x[1..I] and a profile of L
+// rows as the soft output (docs/profile_tapes.md, "Pairs: an input sequence against a profile").
+//
+// Lattice of one pair: (I+1) input positions x (L+1) rows x 2 layers x S states.  Layer 0 (N) = "arrived at (i, r)", layer 1 (W) =
+// "after the machine's output-less moves there"; materialised cells live at cells[(((i*(L+1)) + r)*2 + layer)*S + q].
+#pragma once
+#include <algorithm>
+#include <vector>
+
+#include "mb_internal.h"
+
+namespace mb {
+
+struct PairProfDesc {
+  long long inBase;     // first input token of this pair in the batch's token array
+  long long rowBase;    // first row of this pair's profile in the batch's row table (rows of nOut+1 doubles, column 0 = blank)
+  long long cellBase;   // offset (doubles) of this pair's lattice in a matrix pool
+  long long pathBase;   // offset of this pair's slot in the traceback buffers
+  long long ringBase;   // rolling sweeps: offset (doubles) of this pair's ring in the global scratch buffer, -1 = the ring is in LDS
+  int nIn, nRows;
+};
+
+inline long long profile_pair_cells(int S, long long nIn, long long nRows) { return (nIn + 1) * (nRows + 1) * 2 * (long long)S; }
+// traceback slot: at most nIn input-consuming and nRows output-only edges, and nLevF - 1 silent edges at each of the at most
+// nIn + nRows + 1 cells a path visits
+inline long long profile_pair_path_bound(int nLevF, long long nIn, long long nRows) {
+  return nIn + nRows + (nIn + nRows + 1) * (long long)(nLevF - 1);
+}
+// the rolling ring: three anti-diagonals of both layers, each of min(I, L) + 1 cells
+inline long long profile_pair_ring(int S, long long nIn, long long nRows) { return 3 * 2 * (std::min(nIn, nRows) + 1) * (long long)S; }
+// dynamic LDS of a pair's ring when it fits (0: a slice of the global scratch buffer)
+size_t profile_pair_lds_bytes(int S, long long nIn, long long nRows);
+
+// lds: the dynamic LDS of the launch (the largest ring among the pairs whose ringBase is -1)
+int launch_profile_pair_fwd(const mb_machine *m, int mode, bool mat, const PairProfDesc *d, int n, size_t lds, long long maxItems,
+                            const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st);
+int launch_profile_pair_bwd(const mb_machine *m, const PairProfDesc *d, int n, long long maxItems, const int *inTok, const double *logP,
+                            double *pool, double *loglike, hipStream_t st);
+// counts[nTrans] += posteriors of the n pairs (fwdPool / bwdPool: their materialised lattices); det: 64-bit fixed point at 2^-36
+int launch_profile_pair_counts(const mb_machine *m, const PairProfDesc *d, int n, int groupsPerPair, const int *inTok, const double *logP,
+                               const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
+int launch_profile_pair_traceback(const mb_machine *m, const PairProfDesc *d, int n, const int *inTok, const double *logP,
+                                  const double *pool, uint32_t *edges, int32_t *rows, long long *len, hipStream_t st);
+
+}  // namespace mb
+
+struct mb_profile_pairs {
+  mb_machine *m = nullptr;
+  long long n = 0, totalRows = 0, totalIn = 0;
+  std::vector<long long> rowOff, inOff;   // [n+1], rebased to 0
+  double *d_logP = nullptr;               // [totalRows * (nOut+1)]
+  int *d_in = nullptr;                    // [totalIn]
+};

@@ -514,3 +514,178 @@ class MergedProfileDP(ProfileDP):
                 tie("plane", len(src))
                 edges.append(int(self.eId[k])); rows.append(r); q = int(self.eS[k]); p = src[0]; layer = 1
         return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32)
+
+
+class PairProfileDP(ProfileDP):
+    """A machine WITH an input alphabet on a known input sequence x[1..I] against a profile of L rows, in numpy -- the yardstick of
+    mb_profile_pair.hip (docs/profile_tapes.md, "Pairs: an input sequence against a profile"): the semantics of
+    compose(M, transpose(CSVProfile::machine())) run on input x with an empty output.  N = "arrived at (i, r)", W = "after M's
+    output-less moves there":
+
+        N[i][r][d] = [i = 0, r = 0, d = 0]
+                     (+) N[i][r-1][d] + P[r-1][0]                                              (blank; r > 0)
+                     (+) sum_{t: s->d, in = x_i, out = o}  W[i-1][r-1][s] + w_t + P[r-1][o]      (match;  i > 0, r > 0)
+                     (+) sum_{t: s->d, in = eps, out = o}  W[i][r-1][s]   + w_t + P[r-1][o]      (output-only; r > 0)
+        W[i][r][d] = N[i][r][d]
+                     (+) sum_{t: s->d, in = x_i, out = eps} W[i-1][r][s] + w_t                   (input-only; i > 0)
+                     (+) sum_{silent t: s->d, s < d}        W[i][r][s]   + w_t                   (silent levels)
+        loglike    = W[I][L][S-1]
+
+    The blank reads N, never W (the waiting-machine order of docs/decoding.md).  Viterbi keeps the FIRST maximum -- N: the blank,
+    then match edges in `incoming` order, then output-only edges in `incoming` order; W: "no move" (N), then input-only edges in
+    `incoming` order, then silent edges in `incoming` order.  Every method takes (x, P): x the input tokens (1..nInTok), P the
+    [L, nOutTok + 1] log weights of Profile.logRows.  Lattices are [I + 1, L + 1, S]."""
+
+    def __init__(self, em: EvaluatedMachine):
+        super().__init__(em)
+        order = em.incomingOrder()
+        it, ot, src, dst = em.inTok[order], em.outTok[order], em.src[order].astype(np.int64), em.dst[order].astype(np.int64)
+
+        def table(sel):
+            return order[sel], src[sel], dst[sel], em.logWeight[order[sel]], ot[sel].astype(np.int64)
+        # [a]: (edge id, src, dst, w, out token) of the edges reading input token a, in `incoming` order; [0] unused
+        self.match = [table((it == a) & (ot > 0)) for a in range(em.nInTok + 1)]
+        self.ins = [table((it == a) & (ot == 0)) for a in range(em.nInTok + 1)]
+        self._all = np.arange(self.S, dtype=np.int64)
+
+    def _checkPair(self, x, P) -> Tuple[np.ndarray, np.ndarray]:
+        x = np.asarray(x, np.int64).reshape(-1)
+        if len(x) and (x.min() < 1 or x.max() > self.em.nInTok):
+            raise MachineError("input token outside 1..nInTok")
+        return x, self._check(P)
+
+    def forward(self, x, P, mode: str = "exact") -> Tuple[float, np.ndarray, np.ndarray]:
+        """(loglike, N[I+1][L+1][S], W[I+1][L+1][S]); mode "exact" or "max"."""
+        x, P = self._checkPair(x, P)
+        fold = _max_fold if mode == "max" else _lse_fold
+        I, L, S = len(x), len(P), self.S
+        N = np.full((I + 1, L + 1, S), _NEG); W = np.full((I + 1, L + 1, S), _NEG)
+        for i in range(I + 1):
+            for r in range(L + 1):
+                base = np.full(S, _NEG)
+                if i == 0 and r == 0:
+                    base[0] = 0.0
+                if r:
+                    Pr = P[r - 1]
+                    idx, vals = [self._all], [N[i, r - 1] + Pr[0]]
+                    if i:
+                        _, s, d, w, o = self.match[x[i - 1]]
+                        idx.append(d); vals.append((W[i - 1, r - 1][s] + w) + Pr[o])
+                    idx.append(self.eD); vals.append((W[i, r - 1][self.eS] + self.eW) + Pr[self.eO])
+                    base = fold(base, np.concatenate(idx), np.concatenate(vals))
+                N[i, r] = base
+                w_ = base
+                if i:
+                    _, s, d, w, _o = self.ins[x[i - 1]]
+                    w_ = fold(w_, d, W[i - 1, r][s] + w)
+                else:
+                    w_ = w_.copy()
+                for lv in self.fLevels:
+                    w_ = fold(w_, self.sD[lv], w_[self.sS[lv]] + self.sW[lv])
+                W[i, r] = w_
+        return float(W[I, L, S - 1]), N, W
+
+    def backward(self, x, P) -> Tuple[float, np.ndarray, np.ndarray]:
+        """(loglike, NB[I+1][L+1][S], WB[I+1][L+1][S]), exact log-sum-exp; loglike = NB[0][0][0].  WB[i][r][s] is the mass from
+        the waiting stage of (i, r, s) to the end, NB from the arrived stage: NB = WB (+) (P[r][0] + NB[i][r+1])."""
+        x, P = self._checkPair(x, P)
+        I, L, S = len(x), len(P), self.S
+        NB = np.full((I + 1, L + 1, S), _NEG); WB = np.full((I + 1, L + 1, S), _NEG)
+        for i in range(I, -1, -1):
+            for r in range(L, -1, -1):
+                base = np.full(S, _NEG)
+                if i == I and r == L:
+                    base[S - 1] = 0.0
+                if r < L:
+                    if i < I:
+                        _, s, d, w, o = self.match[x[i]]
+                        base = _lse_fold(base, s, (w + P[r][o]) + NB[i + 1, r + 1][d])
+                    base = _lse_fold(base, self.eS, (self.eW + P[r][self.eO]) + NB[i, r + 1][self.eD])
+                if i < I:
+                    _, s, d, w, _o = self.ins[x[i]]
+                    base = _lse_fold(base, s, WB[i + 1, r][d] + w)
+                for lv in self.bLevels:
+                    base = _lse_fold(base, self.sS[lv], base[self.sD[lv]] + self.sW[lv])
+                WB[i, r] = base
+                NB[i, r] = np.logaddexp(base, P[r][0] + NB[i, r + 1]) if r < L else base
+        return float(NB[0, 0, 0]), NB, WB
+
+    def counts(self, x, P, blanks: Optional[list] = None) -> Tuple[np.ndarray, float]:
+        """(posterior expected use of every transition, Forward loglike); nothing for a -inf pair.  Blank rows are not edges;
+        ``blanks`` (a list) receives their posterior mass, summed over the lattice."""
+        x, P = self._checkPair(x, P)
+        ll, NF, WF = self.forward(x, P)
+        out = np.zeros(self.em.nTransitions)
+        if not ll > _NEG:
+            return out, ll
+        _, NB, WB = self.backward(x, P)
+        I, L = len(x), len(P)
+        blank = 0.0
+        with np.errstate(invalid="ignore"):
+            for i in range(I + 1):
+                for r in range(L + 1):
+                    f = WF[i, r] - ll
+                    if r < L:
+                        if i < I:
+                            e, s, d, w, o = self.match[x[i]]
+                            np.add.at(out, e, np.exp(f[s] + ((w + P[r][o]) + NB[i + 1, r + 1][d])))
+                        np.add.at(out, self.eId, np.exp(f[self.eS] + ((self.eW + P[r][self.eO]) + NB[i, r + 1][self.eD])))
+                        b = (NF[i, r] - ll) + (P[r][0] + NB[i, r + 1])
+                        blank += float(np.exp(b[b > _NEG]).sum())
+                    if i < I:
+                        e, s, d, w, _o = self.ins[x[i]]
+                        np.add.at(out, e, np.exp(f[s] + (WB[i + 1, r][d] + w)))
+                    np.add.at(out, self.sId, np.exp(f[self.sS] + (WB[i, r][self.sD] + self.sW)))
+        if blanks is not None:
+            blanks.append(blank)
+        return out, ll
+
+    def viterbi(self, x, P, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray]:
+        """(score, global edge ids start -> end, row at which each fired); the first maximum in the fill's candidate order.  The
+        row of an emitting edge is the row it consumed, of an output-less edge the number of rows consumed before it; the input
+        position follows by counting the input-consuming edges.  ``census``: per step at which two or more candidates equal the
+        cell, a count under the tuple of the kinds that tie, in candidate order ("blank", "match", "emit" at an N cell; "stay",
+        "ins", "silent" at a W cell)."""
+        x, P = self._checkPair(x, P)
+        v, N, W = self.forward(x, P, "max")
+        edges: List[int] = []; rows: List[int] = []
+        if not v > _NEG:
+            return v, np.zeros(0, np.uint32), np.zeros(0, np.int32)
+        i, r, q, layer = len(x), len(P), self.S - 1, 1
+        while True:
+            cand = []          # (kind, edge id or -1, source state, attains the cell)
+            if layer == 1:
+                cur = W[i, r, q]
+                cand.append(("stay", -1, q, N[i, r, q] == cur))
+                if i:
+                    e, s, d, w, _o = self.ins[x[i - 1]]
+                    cand += [("ins", int(e[k]), int(s[k]), W[i - 1, r, s[k]] + w[k] == cur) for k in np.nonzero(d == q)[0]]
+                cand += [("silent", int(self.sId[k]), int(self.sS[k]), W[i, r, self.sS[k]] + self.sW[k] == cur) for k in self.inSil[q]]
+            else:
+                if r == 0:
+                    assert i == 0 and q == 0
+                    break
+                Pr, cur = P[r - 1], N[i, r, q]
+                cand.append(("blank", -1, q, N[i, r - 1, q] + Pr[0] == cur))
+                if i:
+                    e, s, d, w, o = self.match[x[i - 1]]
+                    cand += [("match", int(e[k]), int(s[k]), (W[i - 1, r - 1, s[k]] + w[k]) + Pr[o[k]] == cur) for k in np.nonzero(d == q)[0]]
+                cand += [("emit", int(self.eId[k]), int(self.eS[k]), (W[i, r - 1, self.eS[k]] + self.eW[k]) + Pr[self.eO[k]] == cur)
+                         for k in self.inEmit[q]]
+            hits = [c for c in cand if c[3]]
+            if census is not None and len(hits) > 1:
+                kinds = tuple(dict.fromkeys(c[0] for c in hits))
+                census[kinds] = census.get(kinds, 0) + 1
+            kind, e, s, _ = hits[0]
+            if kind == "stay":
+                layer = 0
+            elif kind == "blank":
+                r -= 1
+            elif kind in ("ins", "silent"):
+                edges.append(e); rows.append(r); q = s
+                i -= kind == "ins"
+            else:
+                r -= 1
+                edges.append(e); rows.append(r); q = s; layer = 1
+                i -= kind == "match"
+        return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32)
