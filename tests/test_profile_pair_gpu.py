@@ -32,67 +32,8 @@ def device():
     capi.set_option("MB_DETERMINISTIC", None)
 
 
-WORST = {}
-
-
-def _note(what, got, want):
-    WORST[what] = max(WORST.get(what, 0.0), log_dev(got, want))
-    print("worst deviation so far, %s: %.3g" % (what, WORST[what]))
-
-
-def _reference(dp, x, P):
-    ll, N, W = dp.forward(x, P)
-    _, NB, WB = dp.backward(x, P)
-    v, VN, VW = dp.forward(x, P, "max")
-    return dict(ll=ll, fwd=np.stack([N, W], axis=2), bwd=np.stack([NB, WB], axis=2), v=v, vit=np.stack([VN, VW], axis=2),
-                path=dp.viterbi(x, P)[1:], counts=dp.counts(x, P)[0])
-
-
-def _check_machine(em, pairs, fill=True, live=None):
-    """Everything the device computes for the pairs of one machine, in one batch, against the restatement."""
-    dp = PairProfileDP(em)
-    refs = [_reference(dp, x, P) for x, P in pairs]
-    dm = capi.DeviceMachine(em)
-    dev = capi.DeviceProfilePairs(dm, [x for x, _ in pairs], [P for _, P in pairs])
-    try:
-        want = np.array([r["ll"] for r in refs])
-        for flags in (capi.MB_ROLLING, capi.MB_MATERIALISE):
-            got = dev.forward(flags)
-            _note("forward", got, want)
-            assert logs_close(got, want), (flags, got, want)
-        wv = np.array([r["v"] for r in refs])
-        assert logs_close(dev.viterbi(paths=False)[0], wv, 1e-12)
-        v, off, edges, rows = dev.viterbi()
-        assert logs_close(v, wv, 1e-12), (v, wv)
-        for k, r in enumerate(refs):
-            assert np.array_equal(edges[off[k]:off[k + 1]], r["path"][0]) and np.array_equal(rows[off[k]:off[k + 1]], r["path"][1]), k
-        c, s, ll = dev.counts()
-        wc = np.sum([r["counts"] for r in refs], axis=0)
-        big = wc >= 1e-3
-        WORST["counts"] = max(WORST.get("counts", 0.0), float(np.max(np.abs(c[big] - wc[big]) / wc[big], initial=0.0)))
-        WORST["small counts"] = max(WORST.get("small counts", 0.0), float(np.max(np.abs(c[~big] - wc[~big]), initial=0.0)))
-        print("worst deviation so far, counts: %.3g relative, %.3g absolute below 1e-3" % (WORST["counts"], WORST["small counts"]))
-        assert counts_close(c, wc), np.abs(c - wc).max()
-        assert logs_close(ll, want) and (s == -math.inf if (want == -math.inf).any() else abs(s - want.sum()) <= 1e-9 * max(1.0, abs(want.sum())))
-        if fill:
-            for (x, P), r in zip(pairs, refs):
-                for mode, key in ((capi.MB_FORWARD, "fwd"), (capi.MB_BACKWARD, "bwd")):
-                    got = capi.profile_pair_fill(dm, mode, x, P)
-                    _note("cells", got, r[key])
-                    assert logs_close(got, r[key]), (mode, len(x), len(P))
-                    if live is not None:
-                        live["cells"] += int(np.isfinite(r[key]).sum()); live["all"] += r[key].size
-                assert logs_close(capi.profile_pair_fill(dm, capi.MB_VITERBI, x, P), r["vit"], 1e-12), (len(x), len(P))
-        if live is not None:
-            live["ll"] += list(want > -math.inf)
-    finally:
-        dev.close(); dm.close()
-    return refs
-
-
-def _assert_live(live):
-    assert np.mean(live["ll"]) >= 0.9, np.mean(live["ll"])
-    assert live["all"] == 0 or live["cells"] >= 0.5 * live["all"], (live["cells"], live["all"])
+WORST = ph.WORST
+_note, _check_machine, _assert_live = ph.note, ph.check_machine, ph.assert_live      # (shared with test_profile_pair_edges_gpu.py)
 
 
 @pytest.mark.parametrize("S,nIn,nOut", ph.SUITE_CASES)

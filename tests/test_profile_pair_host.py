@@ -165,18 +165,8 @@ def test_no_input_equals_profile_dp(seed):
     assert logs_close([va], [vb], 1e-12) and np.array_equal(ea, eb) and np.array_equal(ra, rb)
 
 
-HALF = math.log(0.5)
-
-
-def _tie_machine():
-    """Weights that are multiples of log 0.5.  Two routes 0 -> 3 tie at every step:
-    N ties: the blank against a match (0 -> 0 reading a, emitting A, at weight 1 beside a blank of weight 1 ... see the census);
-    W ties: staying against an input-only self-loop, an input-only edge against a silent one."""
-    from prefixhelpers import machine_from_edges
-    edges = [(0, 0, 1, 1, 0.0), (0, 0, 0, 1, 0.0), (0, 0, 1, 0, 0.0), (0, 1, 1, 0, HALF), (0, 1, 0, 0, HALF), (1, 1, 1, 1, 0.0),
-             (1, 1, 0, 1, 0.0), (1, 1, 1, 0, 0.0), (1, 2, 0, 0, HALF), (1, 2, 1, 0, HALF), (2, 3, 0, 0, 0.0), (2, 2, 1, 1, 0.0),
-             (2, 2, 0, 1, 0.0), (2, 2, 1, 0, 0.0), (3, 3, 1, 0, 0.0), (3, 3, 1, 1, 0.0), (3, 3, 0, 1, 0.0)]
-    return machine_from_edges(4, 1, 1, edges)
+HALF = ph.HALF
+_tie_machine = ph.tie_machine          # (the GPU edge suite runs the same machine on the device)
 
 
 def test_tie_census():
@@ -325,3 +315,43 @@ def test_pair_suite_inputs_are_live():
     em, pairs = ph.sparse_case()                       # a dead-input case: held only to being neither all dead nor all live
     lls = [PairProfileDP(em).forward(x, P)[0] > -math.inf for x, P in pairs]
     assert any(lls), lls
+
+
+def test_pair_edge_suite_inputs_are_live():
+    """test_profile_pair_edges_gpu.py asserts the same two conditions per case; its builders are held to them here.  Cases that
+    compare scores, paths or counts but no cells are held to the likelihoods alone."""
+    def both(cases):
+        ll, cells = _live(cases)
+        assert ll >= 0.9 and cells >= 0.5, (ll, cells)
+
+    def scores(cases):
+        assert _live(cases)[0] >= 0.9
+    for levels in (True, False):
+        for I, L in ph.RING_SHAPES:
+            scores([ph.ring_case(I, L, levels)])
+    em, pairs = ph.mixed_case()
+    scores([(em,) + p for p in pairs])
+    em, pairs = ph.packed_case()
+    scores([(em,) + p for p in pairs])
+    em, pairs, dead = ph.big_counts_case()
+    assert em.nTransitions > 8192 and PairProfileDP(em).forward(*dead)[0] == -math.inf
+    scores([(em,) + p for p in pairs])
+    em, pairs = ph.flat_counts_case()
+    assert em.nTransitions > 8192
+    scores([(em,) + p for p in pairs])
+    em = ph.tie_machine()
+    both([(em,) + p for p in ph.tie_pairs()])
+    both(ph.hand_tie_cases())
+    em, pairs = ph.twin_case()
+    both([(em,) + p for p in pairs])
+    em, pairs = ph.chain_case()
+    scores([(em,) + p for p in pairs])
+    for I, L in ph.FLAT_SHAPES:
+        em, pairs = ph.flat_diagonals_case(I, L)
+        both([(em,) + p for p in pairs])
+    for nIn, nOut in ph.SMALL_ALPHABETS:
+        both([(em,) + p for em, pairs in ph.alphabet_case(nIn, nOut) for p in pairs])
+    em, pairs = ph.pair_self_loop_case()
+    both([(em,) + p for p in pairs])
+    em, x, P, Pfar = ph.far_case()
+    both([(em, x, Pfar)])
