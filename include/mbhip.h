@@ -206,6 +206,23 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
 int mb_profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows,
                          double *cellsOut);
 
+/* Pairs against CTC-merged profiles: a known input sequence against the rows of `--recognize-merge-csv` -- the semantics of
+ * compose(M, transpose(CSVProfile::mergingMachine())) on input x[1..I] with an empty output, swept natively over
+ * (I + 1) x (rows + 1) x 2 x (nCols + 1) x nStates along anti-diagonals (mb_profile_pair_merge.hip; docs/profile_tapes.md, "Pairs
+ * against a merged profile").  Rows hold nCols + 1 doubles and the batch has one column map, as mb_profiles_create_merged; plane 0 =
+ * the last row took the blank (or no row yet), plane c = the last row took column c.  mb_profile_pairs_forward / _viterbi / _counts /
+ * _destroy and mb_profile_pair_path_bound work on the merged object unchanged.  Viterbi keeps the first maximum: into N[..][0] the
+ * planes ascending; into N[..][c] the repeat, then the match edges, then the output-only edges of colTok[c] in `incoming` order, each
+ * from the lowest plane other than c that attains its exclusion vector; into W "no move", then the input-only edges, then the silent
+ * edges; at the end the planes ascending.  Blank and repeat rows are not edges.  Materialised lattices:
+ * cells[((((i*(nRows+1)) + row)*2 + layer)*(nCols+1) + plane)*nStates + state]; mb_profile_pair_fill_merged:
+ * cellsOut[(nIn+1)*(nRows+1)*2*(nCols+1)*nStates].  Errors, before anything is launched: nCols < 1, a colTok outside 1..nOutTok, an
+ * input token outside 1..nInTok, NaN / +inf weights, a pathCap below the bound, a lattice beyond the memory budget on its own. */
+mb_profile_pairs *mb_profile_pairs_create_merged(mb_machine *m, int64_t nPairs, const int32_t *inTok, const int64_t *inOff,
+                                                 const double *logP, const int64_t *rowOff, int32_t nCols, const int32_t *colTok);
+int mb_profile_pair_fill_merged(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows,
+                                int32_t nCols, const int32_t *colTok, double *cellsOut);
+
 /* ---- prefix search: imputing the input tape (--prefix-decode / --prefix-encode / --random-encode) -------------------------------
  * The node fill of the reference's PrefixTree (src/ctc.cpp:25-88) on the device, the tree and its heap on the host
  * (docs/decoding.md).  An mb_prefix holds nSeq searches (output sequence k = outTok[outOff[k]..outOff[k+1]), tokens 1..nOutTok)

@@ -443,18 +443,64 @@ def runProfile(args, out) -> int:
     return 0
 
 
+def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device", params=None, merge: bool = False,
+                      loglike: bool = True, viterbi: bool = False, counts: bool = False):
+    """Every input sequence (a list of symbols) as one pair with ``profile`` (a profile.Profile), all pairs in one batch, on a
+    machine with an input alphabet (docs/profile_tapes.md, "Pairs" and "Pairs against a merged profile").  ``merge``: the profile
+    is read CTC-merged, as --recognize-merge-csv reads it.  ``backend``: "device" (capi.DeviceProfilePairs) or "numpy"
+    (profile.PairProfileDP / PairMergedProfileDP).  Returns (scores, paramCounts): scores["loglike"] and scores["viterbi"] hold one
+    float per input, or None where not asked for -- a sequence that cannot be tokenised scores -inf and adds nothing to the counts,
+    as the --loglike loop (dp.loglikeBatch); paramCounts is the posterior count of every parameter summed over the pairs, or None."""
+    import numpy as np
+    from . import dp
+    from .profile import PairMergedProfileDP, PairProfileDP
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    if merge and not ev.nOutTok:
+        raise MachineError("--recognize-merge-csv needs a machine with an output alphabet")
+    ok = [ev.inputTokenizer.canTokenize(seq) for seq in inputs]
+    xs = [np.asarray(ev.inputTokenizer.tokenize(seq), np.int64).reshape(-1) for seq, k in zip(inputs, ok) if k]
+    P, colTok = _mergedRows(profile, ev) if merge else (profile.logRows(ev), None)
+    acc = dp.MachineCounts(ev)
+    fwd = vit = None
+    if backend == "numpy":
+        pdp = PairMergedProfileDP(ev, colTok) if merge else PairProfileDP(ev)
+        fwd = [pdp.forward(x, P)[0] for x in xs] if loglike else None
+        if counts:
+            for x in xs:
+                c, ll = pdp.counts(x, P)
+                acc._flat += c
+                acc.loglike += ll
+        vit = [pdp.forward(x, P, "max")[0] for x in xs] if viterbi else None
+    else:
+        from . import capi
+        dm = capi.DeviceMachine(ev)
+        pairs = capi.DeviceProfilePairs(dm, xs, [P] * len(xs), colTok) if merge else capi.DeviceProfilePairs(dm, xs, [P] * len(xs))
+        try:
+            fwd = pairs.forward(capi.MB_ROLLING) if loglike else None
+            if counts:
+                _, s, _ = pairs.counts(acc._flat)
+                acc.loglike += s
+            vit = pairs.viterbi(paths=False)[0] if viterbi else None
+        finally:
+            pairs.close(); dm.close()
+
+    def spread(v):
+        if v is None:
+            return None
+        it = iter(v)
+        return [float(next(it)) if k else -math.inf for k in ok]
+    return {"loglike": spread(fwd), "viterbi": spread(vit)}, (acc.paramCounts(machine, params) if counts else None)
+
+
 def _runProfilePairs(args, out, machine: Machine) -> int:
     """--recognize-csv beside --input-chars / --input-fasta / --input-json on a machine with an input alphabet: every input
     sequence is one pair with the profile (docs/profile_tapes.md, "Pairs"), all pairs in one batch.  -L and -V print one
     [input name, "", score] per pair, -C the counts summed over the pairs.  --decode-backend numpy: profile.PairProfileDP."""
-    import numpy as np
-    from . import dp
-    from .profile import PairProfileDP, Profile
+    from .profile import Profile
     if not os.path.exists(args.recognize_csv):
         raise MachineError("CSV file not found")
     profile = Profile.fromCsv(args.recognize_csv)
     params = _profileParams(args, machine)
-    ev = EvaluatedMachine.fromMachine(machine, params)
     inSeqs: List[Tuple[str, List[str]]] = []
     if args.input_fasta:
         inSeqs += [(n, list(s)) for n, s in readFasta(args.input_fasta)]
@@ -462,43 +508,17 @@ def _runProfilePairs(args, out, machine: Machine) -> int:
         inSeqs.append((args.input_chars, list(args.input_chars)))
     if args.input_json:
         j = json.load(open(args.input_json)); inSeqs.append((j.get("name", ""), list(j["sequence"])))
-    # as the --loglike loop (dp.loglikeBatch): a sequence that cannot be tokenised scores -inf and adds nothing to the counts
-    ok = [ev.inputTokenizer.canTokenize(seq) for _, seq in inSeqs]
-    xs = [np.asarray(ev.inputTokenizer.tokenize(seq), np.int64).reshape(-1) for (_, seq), k in zip(inSeqs, ok) if k]
-    P = profile.logRows(ev)
-    counts = dp.MachineCounts(ev)
-    if args.decode_backend == "numpy":
-        pdp = PairProfileDP(ev)
-        fwd = [pdp.forward(x, P)[0] for x in xs] if args.loglike else None
-        if args.counts:
-            for x in xs:
-                c, ll = pdp.counts(x, P)
-                counts._flat += c
-                counts.loglike += ll
-        vit = [pdp.forward(x, P, "max")[0] for x in xs] if args.viterbi else None
-    else:
-        from . import capi
-        dm = capi.DeviceMachine(ev)
-        pairs = capi.DeviceProfilePairs(dm, xs, [P] * len(xs))
-        try:
-            fwd = pairs.forward(capi.MB_ROLLING) if args.loglike else None
-            if args.counts:
-                _, s, _ = pairs.counts(counts._flat)
-                counts.loglike += s
-            vit = pairs.viterbi(paths=False)[0] if args.viterbi else None
-        finally:
-            pairs.close(); dm.close()
+    sc, pc = scoreProfilePairs(machine, [seq for _, seq in inSeqs], profile, backend="numpy" if args.decode_backend == "numpy" else "device",
+                               params=params, loglike=bool(args.loglike), viterbi=bool(args.viterbi), counts=bool(args.counts))
 
     def scores(v):
-        it = iter(v)
-        return "[" + ",".join('["%s","",%s]' % (escaped(n), fmt(float(next(it)) if k else -math.inf)) for (n, _), k in zip(inSeqs, ok)) + "]\n"
+        return "[" + ",".join('["%s","",%s]' % (escaped(n), fmt(x)) for (n, _), x in zip(inSeqs, v)) + "]\n"
     if args.loglike:
-        out.write(scores(fwd))
+        out.write(scores(sc["loglike"]))
     if args.counts:
-        pc = counts.paramCounts(machine, params)
         out.write("{" + ",".join('"%s":%s' % (escaped(k), "%g" % pc[k]) for k in sorted(pc)) + "}\n")
     if args.viterbi:
-        out.write(scores(vit))
+        out.write(scores(sc["viterbi"]))
     return 0
 
 

@@ -32,6 +32,7 @@ EXPORTS = [
     "mb_profiles_counts", "mb_profile_fill", "mb_profiles_create_merged", "mb_profile_fill_merged",
     "mb_profile_pairs_create", "mb_profile_pairs_destroy", "mb_profile_pairs_forward", "mb_profile_pair_path_bound",
     "mb_profile_pairs_viterbi", "mb_profile_pairs_counts", "mb_profile_pair_fill",
+    "mb_profile_pairs_create_merged", "mb_profile_pair_fill_merged",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
     "mb_prefix_node_cells", "mb_prefix_create_profiles", "mb_prefix_create_merged",
 ]
@@ -126,6 +127,9 @@ def load():
     L.mb_profile_pairs_viterbi.argtypes = [vp, dp, i64p, u32p, i32p, C.c_int64]
     L.mb_profile_pairs_counts.argtypes = [vp, dp, dp, dp]
     L.mb_profile_pair_fill.argtypes = [vp, C.c_int, i32p, C.c_int64, dp, C.c_int64, dp]
+    L.mb_profile_pairs_create_merged.restype = vp
+    L.mb_profile_pairs_create_merged.argtypes = [vp, C.c_int64, i32p, i64p, dp, i64p, C.c_int32, i32p]
+    L.mb_profile_pair_fill_merged.argtypes = [vp, C.c_int, i32p, C.c_int64, dp, C.c_int64, C.c_int32, i32p, dp]
     L.mb_prefix_create.restype = vp
     L.mb_prefix_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, C.c_int64]
     L.mb_prefix_create_profiles.restype = vp
@@ -643,11 +647,15 @@ def profile_fill_merged(dm: DeviceMachine, mode: int, logP, colTok) -> np.ndarra
 class DeviceProfilePairs:
     """Device-resident batch of (input sequence, profile) pairs (mb_profile_pairs*) for a machine with an input alphabet: pair k is
     the token sequence ``inputs[k]`` (1..nInTok) against the [rows, nOutTok + 1] log weights ``profiles[k]``, column 0 = the blank
-    (profile.Profile.logRows).  The yardstick is profile.PairProfileDP (docs/profile_tapes.md, "Pairs")."""
+    (profile.Profile.logRows).  The yardstick is profile.PairProfileDP (docs/profile_tapes.md, "Pairs").  With ``colTok`` the
+    profiles are CTC-merged (mb_profile_pairs_create_merged): per pair a [rows, nCols + 1] array, column 0 the blank and column c a
+    CSV column whose output token is colTok[c - 1] (profile.Profile.mergeRows); every method works the same and the yardstick is
+    profile.PairMergedProfileDP."""
 
-    def __init__(self, dm: DeviceMachine, inputs, profiles):
+    def __init__(self, dm: DeviceMachine, inputs, profiles, colTok=None):
         self.dm = dm
-        width = dm.em.nOutTok + 1
+        self.colTok = None if colTok is None else np.ascontiguousarray(np.asarray(colTok).reshape(-1), np.int32)
+        width = dm.em.nOutTok + 1 if colTok is None else len(self.colTok) + 1
         rows = [np.asarray(p, np.float64).reshape(-1, width) for p in profiles]
         xs = [np.asarray(x, np.int64).reshape(-1) for x in inputs]
         if len(xs) != len(rows):
@@ -660,8 +668,13 @@ class DeviceProfilePairs:
         self.logP = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((1, width)), np.float64)
         self.inTok = np.ascontiguousarray(np.concatenate(xs + [np.zeros(1, np.int64)]), np.int32)
         L = load()
-        self.h = L.mb_profile_pairs_create(dm.h, self.nPairs, _p(self.inTok, C.c_int32), _p(self.inOff, C.c_int64),
-                                           _p(self.logP, C.c_double), _p(self.rowOff, C.c_int64))
+        if colTok is None:
+            self.h = L.mb_profile_pairs_create(dm.h, self.nPairs, _p(self.inTok, C.c_int32), _p(self.inOff, C.c_int64),
+                                               _p(self.logP, C.c_double), _p(self.rowOff, C.c_int64))
+        else:
+            self.h = L.mb_profile_pairs_create_merged(dm.h, self.nPairs, _p(self.inTok, C.c_int32), _p(self.inOff, C.c_int64),
+                                                      _p(self.logP, C.c_double), _p(self.rowOff, C.c_int64), len(self.colTok),
+                                                      _p(self.colTok, C.c_int32))
         if not self.h:
             raise MbError(L.mb_last_error().decode())
 
@@ -714,6 +727,18 @@ def profile_pair_fill(dm: DeviceMachine, mode: int, x, logP) -> np.ndarray:
     xs = np.ascontiguousarray(np.asarray(x, np.int64).reshape(-1), np.int32)
     cells = np.empty((len(xs) + 1, len(P) + 1, 2, dm.nStates), np.float64)
     _check(load().mb_profile_pair_fill(dm.h, mode, _p(xs, C.c_int32), len(xs), _p(P, C.c_double), len(P), _p(cells, C.c_double)))
+    return cells
+
+
+def profile_pair_fill_merged(dm: DeviceMachine, mode: int, x, logP, colTok) -> np.ndarray:
+    """One pair's lattice against a merged profile, [len(x) + 1, rows + 1, 2, nCols + 1, nStates] (layer 0 = arrived at (i, row),
+    1 = after the output-less moves; plane 0 = the last row took the blank, plane c = it took column c)."""
+    ct = np.ascontiguousarray(np.asarray(colTok).reshape(-1), np.int32)
+    P = np.ascontiguousarray(np.asarray(logP, np.float64).reshape(-1, len(ct) + 1))
+    xs = np.ascontiguousarray(np.asarray(x, np.int64).reshape(-1), np.int32)
+    cells = np.empty((len(xs) + 1, len(P) + 1, 2, len(ct) + 1, dm.nStates), np.float64)
+    _check(load().mb_profile_pair_fill_merged(dm.h, mode, _p(xs, C.c_int32), len(xs), _p(P, C.c_double), len(P), len(ct),
+                                              _p(ct, C.c_int32), _p(cells, C.c_double)))
     return cells
 
 

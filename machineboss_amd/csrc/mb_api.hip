@@ -19,6 +19,7 @@
 #include "mb_profile.h"
 #include "mb_profile_merge.h"
 #include "mb_profile_pair.h"
+#include "mb_profile_pair_merge.h"
 #include "mb_small.h"
 #include "mb_usage.h"
 #include "mb_wide.h"
@@ -2485,11 +2486,22 @@ static bool pair_profile_chunks(const mb_profile_pairs *p, const std::function<d
 
 static long long pp_in(const mb_profile_pairs *p, long long k) { return p->inOff[k + 1] - p->inOff[k]; }
 static long long pp_rows(const mb_profile_pairs *p, long long k) { return p->rowOff[k + 1] - p->rowOff[k]; }
-static double pp_cell_bytes(const mb_profile_pairs *p, long long k) { return 8.0 * (double)profile_pair_cells(p->m->S, pp_in(p, k), pp_rows(p, k)); }
-// bytes of global scratch the rolling sweep of pair k needs (0: its ring is in LDS)
-static double pp_ring_bytes(const mb_profile_pairs *p, long long k) {
-  return profile_pair_lds_bytes(p->m->S, pp_in(p, k), pp_rows(p, k)) ? 0.0 : 8.0 * (double)profile_pair_ring(p->m->S, pp_in(p, k), pp_rows(p, k));
+static double pp_cell_bytes(const mb_profile_pairs *p, long long k) { return 8.0 * (double)profile_pair_cells(p->m->S, pp_in(p, k), pp_rows(p, k)) * (p->nCols + 1); }
+// The ring of pair k's sweep and its dynamic LDS (0: a slice of the global scratch buffer).  Plain profiles: the rolling sweep alone
+// has one.  Merged: the materialised sweeps keep their exclusion vectors in one too (mb_profile_pair_merge.h).
+static long long pp_ring(const mb_profile_pairs *p, long long k, bool rolling) {
+  if (p->nCols) return profile_pair_merge_ring(p->m->S, p->nCols, pp_in(p, k), pp_rows(p, k), !rolling);
+  return rolling ? profile_pair_ring(p->m->S, pp_in(p, k), pp_rows(p, k)) : 0;
 }
+static size_t pp_ring_lds(const mb_profile_pairs *p, long long k, bool rolling) {
+  if (p->nCols) return profile_pair_merge_lds_bytes(p->m->S, p->nCols, pp_in(p, k), pp_rows(p, k), !rolling);
+  return rolling ? profile_pair_lds_bytes(p->m->S, pp_in(p, k), pp_rows(p, k)) : 0;
+}
+// bytes of global scratch the sweep of pair k needs (0: its ring is in LDS, or it has none)
+static double pp_ring_bytes(const mb_profile_pairs *p, long long k, bool rolling) {
+  return pp_ring_lds(p, k, rolling) ? 0.0 : 8.0 * (double)pp_ring(p, k, rolling);
+}
+static MergeMap pp_map(const mb_profile_pairs *p) { return MergeMap{p->nCols, p->d_colTok}; }
 
 struct PairProfPlan { PairProfDesc *d = nullptr; long long cells = 0, paths = 0, ring = 0, maxItems = 0; size_t lds = 0; };
 
@@ -2502,13 +2514,13 @@ static int pair_profile_descs(const mb_profile_pairs *p, long long p0, long long
     const long long I = pp_in(p, k), L = pp_rows(p, k);
     d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)I; d.nRows = (int)L;
     d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = -1;
-    pl.cells += profile_pair_cells(S, I, L);
+    pl.cells += profile_pair_cells(S, I, L) * (p->nCols + 1);
     pl.paths += profile_pair_path_bound(p->m->nLevF, I, L);
-    pl.maxItems = std::max(pl.maxItems, (std::min(I, L) + 1) * S);
-    if (rolling) {
-      const size_t lds = profile_pair_lds_bytes(S, I, L);
+    pl.maxItems = std::max(pl.maxItems, (std::min(I, L) + 1) * S * (p->nCols + 1));
+    if (pp_ring(p, k, rolling)) {
+      const size_t lds = pp_ring_lds(p, k, rolling);
       if (lds) pl.lds = std::max(pl.lds, lds);
-      else { d.ringBase = pl.ring; pl.ring += profile_pair_ring(S, I, L); }
+      else { d.ringBase = pl.ring; pl.ring += pp_ring(p, k, rolling); }
     }
   }
   MB_HIP(sm_alloc((void **)&pl.d, std::max<size_t>(h.size(), 1) * sizeof(PairProfDesc)));
@@ -2517,10 +2529,33 @@ static int pair_profile_descs(const mb_profile_pairs *p, long long p0, long long
   return 0;
 }
 
+// The one place where the plain and the merged kernels part: the launches of a chunk and the names they report.
+static int pp_launch_fwd(const mb_profile_pairs *p, int mode, bool mat, const PairProfPlan &pl, long long n, double *pool, double *scratch, double *ll) {
+  if (p->nCols) return launch_profile_pair_merge_fwd(p->m, pp_map(p), mode, mat, pl.d, (int)n, pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, ll, g_stream);
+  return launch_profile_pair_fwd(p->m, mode, mat, pl.d, (int)n, mat ? 0 : pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, mat ? nullptr : scratch, ll, g_stream);
+}
+static int pp_launch_bwd(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, double *pool, double *scratch, double *ll) {
+  if (p->nCols) return launch_profile_pair_merge_bwd(p->m, pp_map(p), pl.d, (int)n, pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, ll, g_stream);
+  return launch_profile_pair_bwd(p->m, pl.d, (int)n, pl.maxItems, p->d_in, p->d_logP, pool, ll, g_stream);
+}
+static int pp_launch_traceback(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, const double *pool, uint32_t *e, int32_t *r, long long *len) {
+  if (p->nCols) return launch_profile_pair_merge_traceback(p->m, pp_map(p), pl.d, (int)n, p->d_in, p->d_logP, pool, e, r, len, g_stream);
+  return launch_profile_pair_traceback(p->m, pl.d, (int)n, p->d_in, p->d_logP, pool, e, r, len, g_stream);
+}
+static int pp_launch_counts(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, int groups, const double *fwd, const double *bwd, double *cc) {
+  if (p->nCols) return launch_profile_pair_merge_counts(p->m, pp_map(p), pl.d, (int)n, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
+  return launch_profile_pair_counts(p->m, pl.d, (int)n, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
+}
+static const char *pp_fwd_name(const mb_profile_pairs *p, int mode, bool mat) {
+  static const char *const names[2][2][2] = {{{"k_profile_pair_fwd<sum,rolling>", "k_profile_pair_fwd<sum,mat>"}, {"k_profile_pair_fwd<max,rolling>", "k_profile_pair_fwd<max,mat>"}},
+                                             {{"k_profile_pair_merge_fwd<sum,rolling>", "k_profile_pair_merge_fwd<sum,mat>"}, {"k_profile_pair_merge_fwd<max,rolling>", "k_profile_pair_merge_fwd<max,mat>"}}};
+  return names[p->nCols ? 1 : 0][mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
+}
+
 // Forward (MB_FORWARD) or Viterbi scores without paths (MB_VITERBI); mat: through the materialised lattice
 static int pair_profile_scores(mb_profile_pairs *p, int mode, bool mat, double *loglike) {
   std::vector<Chunk> chunks;
-  if (!pair_profile_chunks(p, [&](long long k) { return mat ? pp_cell_bytes(p, k) : pp_ring_bytes(p, k); }, chunks)) return 1;
+  if (!pair_profile_chunks(p, [&](long long k) { return (mat ? pp_cell_bytes(p, k) : 0.0) + pp_ring_bytes(p, k, !mat); }, chunks)) return 1;
   double *d_ll = nullptr;
   MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
   int rc = 0;
@@ -2530,10 +2565,10 @@ static int pair_profile_scores(mb_profile_pairs *p, int mode, bool mat, double *
     if ((rc = pair_profile_descs(p, c.p0, c.p1, !mat, pl))) break;
     double *pool = nullptr, *scratch = nullptr;
     if (mat) { pool = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double)); if (!pool) rc = 1; }
-    else if (pl.ring) { scratch = (double *)ws_get(1, (size_t)pl.ring * sizeof(double)); if (!scratch) rc = 1; }
+    if (!rc && pl.ring) { scratch = (double *)ws_get(1, (size_t)pl.ring * sizeof(double)); if (!scratch) rc = 1; }
     if (!rc) {
       tm.start();
-      rc = launch_profile_pair_fwd(p->m, mode, mat, pl.d, (int)(c.p1 - c.p0), pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, d_ll + c.p0, g_stream);
+      rc = pp_launch_fwd(p, mode, mat, pl, c.p1 - c.p0, pool, scratch, d_ll + c.p0);
       g_last_ms += tm.stop();
       ++g_last_launches;
     }
@@ -2543,27 +2578,27 @@ static int pair_profile_scores(mb_profile_pairs *p, int mode, bool mat, double *
   }
   if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
   sm_free(d_ll);
-  g_last_kernel = mode == MB_VITERBI ? (mat ? "k_profile_pair_fwd<max,mat>" : "k_profile_pair_fwd<max,rolling>")
-                                     : (mat ? "k_profile_pair_fwd<sum,mat>" : "k_profile_pair_fwd<sum,rolling>");
+  g_last_kernel = pp_fwd_name(p, mode, mat);
   return rc;
 }
 
-mb_profile_pairs *mb_profile_pairs_create(mb_machine *m, int64_t nPairs, const int32_t *inTok, const int64_t *inOff, const double *logP, const int64_t *rowOff) {
-  ApiGuard guard;
+// nCols > 0: CTC-merged profiles, rows of nCols + 1 doubles and the column map colTok (checked by the caller)
+static mb_profile_pairs *profile_pairs_create(mb_machine *m, int64_t nPairs, const int32_t *inTok, const int64_t *inOff, const double *logP,
+                                              const int64_t *rowOff, int32_t nCols, const int32_t *colTok) {
   if (!m || nPairs < 0 || (nPairs > 0 && (!rowOff || !inOff))) { set_error("null argument"); return nullptr; }
   if (ensure_init()) return nullptr;
   mb_profile_pairs *p = new mb_profile_pairs();
-  p->m = m; p->n = nPairs;
+  p->m = m; p->n = nPairs; p->nCols = nCols;
   p->rowOff.assign((size_t)nPairs + 1, 0); p->inOff.assign((size_t)nPairs + 1, 0);
   for (long long k = 0; k < nPairs; ++k) {
     const long long L = rowOff[k + 1] - rowOff[k], I = inOff[k + 1] - inOff[k];
     if (L < 0 || L > 0x3fffffff || I < 0 || I > 0x3fffffff) { set_error("bad pair offsets"); delete p; return nullptr; }
-    if ((double)(std::min(I, L) + 1) * m->S > 2147483647.0) { set_error("pair " + std::to_string(k) + ": an anti-diagonal of the lattice has more than 2^31 cells"); delete p; return nullptr; }
+    if ((double)(std::min(I, L) + 1) * m->S * (nCols + 1) > 2147483647.0) { set_error("pair " + std::to_string(k) + ": an anti-diagonal of the lattice has more than 2^31 cells"); delete p; return nullptr; }
     p->rowOff[(size_t)k + 1] = p->rowOff[(size_t)k] + L;
     p->inOff[(size_t)k + 1] = p->inOff[(size_t)k] + I;
   }
   p->totalRows = p->rowOff.back(); p->totalIn = p->inOff.back();
-  const long long C = m->nOut + 1, nv = p->totalRows * C;
+  const long long C = nCols ? nCols + 1 : m->nOut + 1, nv = p->totalRows * C;
   const double *v0 = logP ? logP + (nPairs ? rowOff[0] * C : 0) : nullptr;
   const int32_t *x0 = inTok ? inTok + (nPairs ? inOff[0] : 0) : nullptr;
   if ((nv && !v0) || (p->totalIn && !x0)) { set_error("null argument"); delete p; return nullptr; }
@@ -2577,8 +2612,22 @@ mb_profile_pairs *mb_profile_pairs_create(mb_machine *m, int64_t nPairs, const i
       !hip_ok(hipMalloc((void **)&p->d_in, (size_t)std::max<long long>(p->totalIn, 1) * sizeof(int)), "hipMalloc(pair inputs)")) { mb_profile_pairs_destroy(p); return nullptr; }
   if (nv && h2d_large(p->d_logP, v0, (size_t)nv * sizeof(double))) { mb_profile_pairs_destroy(p); return nullptr; }
   if (p->totalIn && h2d_large(p->d_in, x0, (size_t)p->totalIn * sizeof(int))) { mb_profile_pairs_destroy(p); return nullptr; }
+  if (nCols && (!hip_ok(hipMalloc((void **)&p->d_colTok, (size_t)nCols * sizeof(int)), "hipMalloc(column map)") ||
+                !hip_ok(hipMemcpyAsync(p->d_colTok, colTok, (size_t)nCols * sizeof(int), hipMemcpyHostToDevice, g_stream), "H2D column map"))) { mb_profile_pairs_destroy(p); return nullptr; }
   if (!hip_ok(hipStreamSynchronize(g_stream), "H2D pairs")) { mb_profile_pairs_destroy(p); return nullptr; }
   return p;
+}
+
+mb_profile_pairs *mb_profile_pairs_create(mb_machine *m, int64_t nPairs, const int32_t *inTok, const int64_t *inOff, const double *logP, const int64_t *rowOff) {
+  ApiGuard guard;
+  return profile_pairs_create(m, nPairs, inTok, inOff, logP, rowOff, 0, nullptr);
+}
+
+mb_profile_pairs *mb_profile_pairs_create_merged(mb_machine *m, int64_t nPairs, const int32_t *inTok, const int64_t *inOff, const double *logP,
+                                                 const int64_t *rowOff, int32_t nCols, const int32_t *colTok) {
+  ApiGuard guard;
+  if (!merge_map_ok(m, nCols, colTok)) return nullptr;
+  return profile_pairs_create(m, nPairs, inTok, inOff, logP, rowOff, nCols, colTok);
 }
 
 void mb_profile_pairs_destroy(mb_profile_pairs *p) {
@@ -2586,6 +2635,7 @@ void mb_profile_pairs_destroy(mb_profile_pairs *p) {
   if (!p) return;
   if (p->d_logP) (void)hipFree(p->d_logP);
   if (p->d_in) (void)hipFree(p->d_in);
+  if (p->d_colTok) (void)hipFree(p->d_colTok);
   delete p;
 }
 
@@ -2612,7 +2662,7 @@ int mb_profile_pairs_viterbi(mb_profile_pairs *p, double *loglike, int64_t *path
   for (long long k = 0; k < p->n; ++k) need += profile_pair_path_bound(m->nLevF, pp_in(p, k), pp_rows(p, k));
   if (pathCap < need) { set_error("pathCap too small for the Viterbi paths: " + std::to_string((long long)pathCap) + " entries, the path bounds of the pairs sum to " + std::to_string(need)); return 1; }
   std::vector<Chunk> chunks;
-  auto bytes = [&](long long k) { return pp_cell_bytes(p, k) + 8.0 * profile_pair_path_bound(m->nLevF, pp_in(p, k), pp_rows(p, k)); };
+  auto bytes = [&](long long k) { return pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false) + 8.0 * profile_pair_path_bound(m->nLevF, pp_in(p, k), pp_rows(p, k)); };
   if (!pair_profile_chunks(p, bytes, chunks)) return 1;
   double *d_ll = nullptr;
   long long *d_len = nullptr;
@@ -2632,11 +2682,12 @@ int mb_profile_pairs_viterbi(mb_profile_pairs *p, double *loglike, int64_t *path
     double *pool = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
     uint32_t *d_e = (uint32_t *)ws_get(3, (size_t)std::max<long long>(paths, 1) * sizeof(uint32_t));
     int32_t *d_r = (int32_t *)ws_get(4, (size_t)std::max<long long>(paths, 1) * sizeof(int32_t));
-    if (!pool || !d_e || !d_r) rc = 1;
+    double *scratch = pl.ring ? (double *)ws_get(1, (size_t)pl.ring * sizeof(double)) : nullptr;
+    if (!pool || !d_e || !d_r || (pl.ring && !scratch)) rc = 1;
     if (!rc) {
       tm.start();
-      rc = launch_profile_pair_fwd(m, MB_VITERBI, true, pl.d, (int)np, 0, pl.maxItems, p->d_in, p->d_logP, pool, nullptr, d_ll + c.p0, g_stream);
-      if (!rc) rc = launch_profile_pair_traceback(m, pl.d, (int)np, p->d_in, p->d_logP, pool, d_e, d_r, d_len + c.p0, g_stream);
+      rc = pp_launch_fwd(p, MB_VITERBI, true, pl, np, pool, scratch, d_ll + c.p0);
+      if (!rc) rc = pp_launch_traceback(p, pl, np, pool, d_e, d_r, d_len + c.p0);
       g_last_ms += tm.stop();
       ++g_last_launches;
     }
@@ -2660,7 +2711,7 @@ int mb_profile_pairs_viterbi(mb_profile_pairs *p, double *loglike, int64_t *path
   }
   if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
   sm_free(d_ll); sm_free(d_len);
-  g_last_kernel = "k_profile_pair_fwd<max,mat>";
+  g_last_kernel = pp_fwd_name(p, MB_VITERBI, true);
   return rc;
 }
 
@@ -2672,7 +2723,7 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
   const mb_machine *m = p->m;
   const long long nT = m->nTrans;
   std::vector<Chunk> chunks;
-  if (!pair_profile_chunks(p, [&](long long k) { return 2.0 * pp_cell_bytes(p, k); }, chunks)) return 1;   // the Forward and the Backward lattice
+  if (!pair_profile_chunks(p, [&](long long k) { return 2.0 * pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false); }, chunks)) return 1;   // the Forward and the Backward lattice
   double *d_ll = nullptr, *d_bll = nullptr, *d_cc = nullptr;
   MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
   if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
@@ -2686,17 +2737,18 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
     const long long np = c.p1 - c.p0;
     double *fwd = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
     double *bwd = (double *)ws_get(1, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
-    if (!fwd || !bwd) rc = 1;
+    double *scratch = pl.ring ? (double *)ws_get(2, (size_t)pl.ring * sizeof(double)) : nullptr;
+    if (!fwd || !bwd || (pl.ring && !scratch)) rc = 1;
     long long maxCells = 0;
-    for (long long k = c.p0; k < c.p1; ++k) maxCells = std::max(maxCells, profile_pair_cells(m->S, pp_in(p, k), pp_rows(p, k)) / 2);
+    for (long long k = c.p0; k < c.p1; ++k) maxCells = std::max(maxCells, profile_pair_cells(m->S, pp_in(p, k), pp_rows(p, k)) / 2 * (p->nCols + 1));
     const int groups = (int)std::min<long long>(256, std::max<long long>(1, (maxCells + 2047) / 2048));
     if (!rc && np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); rc = 1; }
     if (!rc) {
       tm.start();
-      rc = launch_profile_pair_fwd(m, MB_FORWARD, true, pl.d, (int)np, 0, pl.maxItems, p->d_in, p->d_logP, fwd, nullptr, d_ll + c.p0, g_stream);
-      if (!rc) rc = launch_profile_pair_bwd(m, pl.d, (int)np, pl.maxItems, p->d_in, p->d_logP, bwd, d_bll + c.p0, g_stream);
+      rc = pp_launch_fwd(p, MB_FORWARD, true, pl, np, fwd, scratch, d_ll + c.p0);      // (merged: the Backward's ring follows the Forward's on the stream, one scratch buffer serves both)
+      if (!rc) rc = pp_launch_bwd(p, pl, np, bwd, scratch, d_bll + c.p0);
       if (!rc && nT) rc = hip_ok(hipMemsetAsync(d_cc, 0, (size_t)nT * sizeof(double), g_stream), "memset(counts)") ? 0 : 1;
-      if (!rc) rc = launch_profile_pair_counts(m, pl.d, (int)np, groups, p->d_in, p->d_logP, fwd, bwd, d_cc, g_stream);
+      if (!rc) rc = pp_launch_counts(p, pl, np, groups, fwd, bwd, d_cc);
       g_last_ms += tm.stop();
       ++g_last_launches;
     }
@@ -2714,7 +2766,7 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
   std::vector<double> hll((size_t)p->n);
   if (!rc && p->n && !hip_ok(hipMemcpy(hll.data(), d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
   sm_free(d_ll); sm_free(d_bll); sm_free(d_cc);
-  g_last_kernel = "k_profile_pair_counts";
+  g_last_kernel = p->nCols ? "k_profile_pair_merge_counts" : "k_profile_pair_counts";
   if (rc) return rc;
   for (long long e = 0; e < nT; ++e) counts[e] += total[(size_t)e];
   double s = 0.0;
@@ -2723,37 +2775,50 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
   return 0;
 }
 
-int mb_profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, double *cellsOut) {
-  ApiGuard guard;
+static int profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, int32_t nCols,
+                             const int32_t *colTok, double *cellsOut) {
   if (!m || !cellsOut || nRows < 0 || nIn < 0 || (nRows && !logP) || (nIn && !inTok)) { set_error("null argument"); return 1; }
   if (mode != MB_FORWARD && mode != MB_VITERBI && mode != MB_BACKWARD) { set_error("unknown fill mode"); return 1; }
   if (ensure_init()) return 1;
   g_last_ms = 0.0; g_last_launches = 0;
   const int64_t rOff[2] = {0, nRows}, iOff[2] = {0, nIn};
-  mb_profile_pairs *p = mb_profile_pairs_create(m, 1, inTok, iOff, logP, rOff);
+  mb_profile_pairs *p = profile_pairs_create(m, 1, inTok, iOff, logP, rOff, nCols, colTok);
   if (!p) return 1;
   std::vector<Chunk> chunks;
-  if (!pair_profile_chunks(p, [&](long long k) { return pp_cell_bytes(p, k); }, chunks)) { mb_profile_pairs_destroy(p); return 1; }
+  if (!pair_profile_chunks(p, [&](long long k) { return pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false); }, chunks)) { mb_profile_pairs_destroy(p); return 1; }
   PairProfPlan pl;
   int rc = pair_profile_descs(p, 0, 1, false, pl);
   double *d_ll = nullptr;
   if (!rc && !hip_ok(sm_alloc((void **)&d_ll, sizeof(double)), "hipMalloc(loglike)")) rc = 1;
   double *pool = rc ? nullptr : (double *)ws_get(0, (size_t)pl.cells * sizeof(double));
   if (!rc && !pool) rc = 1;
+  double *scratch = !rc && pl.ring ? (double *)ws_get(1, (size_t)pl.ring * sizeof(double)) : nullptr;
+  if (!rc && pl.ring && !scratch) rc = 1;
   if (!rc) {
     Timer tm;
     tm.start();
-    rc = mode == MB_BACKWARD ? launch_profile_pair_bwd(m, pl.d, 1, pl.maxItems, p->d_in, p->d_logP, pool, d_ll, g_stream)
-                             : launch_profile_pair_fwd(m, mode, true, pl.d, 1, 0, pl.maxItems, p->d_in, p->d_logP, pool, nullptr, d_ll, g_stream);
+    rc = mode == MB_BACKWARD ? pp_launch_bwd(p, pl, 1, pool, scratch, d_ll) : pp_launch_fwd(p, mode, true, pl, 1, pool, scratch, d_ll);
     g_last_ms += tm.stop();
     g_last_launches = 1;
   }
   if (!rc) rc = d2h_large(cellsOut, pool, (size_t)pl.cells * sizeof(double));
   if (rc) quiesce_streams();
   sm_free(pl.d); sm_free(d_ll);
-  g_last_kernel = mode == MB_BACKWARD ? "k_profile_pair_bwd" : (mode == MB_VITERBI ? "k_profile_pair_fwd<max,mat>" : "k_profile_pair_fwd<sum,mat>");
+  g_last_kernel = mode == MB_BACKWARD ? (nCols ? "k_profile_pair_merge_bwd" : "k_profile_pair_bwd") : pp_fwd_name(p, mode, true);
   mb_profile_pairs_destroy(p);
   return rc;
+}
+
+int mb_profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, double *cellsOut) {
+  ApiGuard guard;
+  return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, 0, nullptr, cellsOut);
+}
+
+int mb_profile_pair_fill_merged(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, int32_t nCols,
+                                const int32_t *colTok, double *cellsOut) {
+  ApiGuard guard;
+  if (!merge_map_ok(m, nCols, colTok)) return 1;
+  return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, nCols, colTok, cellsOut);
 }
 
 // ---- prefix search: node fills on the device, the tree on the host (mb_prefix.hip, docs/decoding.md) --------------------------

@@ -48,6 +48,8 @@ struct mb_profile_pairs {
   mb_machine *m = nullptr;
   long long n = 0, totalRows = 0, totalIn = 0;
   std::vector<long long> rowOff, inOff;   // [n+1], rebased to 0
-  double *d_logP = nullptr;               // [totalRows * (nOut+1)]
+  double *d_logP = nullptr;               // [totalRows * (nOut+1)]; merged: [totalRows * (nCols+1)]
   int *d_in = nullptr;                    // [totalIn]
+  int nCols = 0;                          // > 0: CTC-merged profiles (mb_profile_pair_merge.h)
+  int *d_colTok = nullptr;                // [nCols] output token of column c at [c - 1]
 };

@@ -1,0 +1,493 @@
+// mb_profile_pair_merge.hip -- Forward / Backward / Viterbi / posterior counts of a machine WITH an input alphabet, run on a known
+// input sequence x[1..I] against a CTC-MERGED profile of L rows: the semantics of compose(M, transpose(CSVProfile::mergingMachine()))
+// on input x with an empty output, restated in docs/profile_tapes.md ("Pairs against a merged profile"):
+//
+//   X[i][r][c][s] = (+)_{k != c} W[i][r][k][s]                                                          (the exclusion vector)
+//   N[i][r][0][d] = [i = 0, r = 0, d = 0]  (+)  (+)_p (N[i][r-1][p][d] + P[r-1][0])                      (blank; r > 0)
+//   N[i][r][c][d] = (N[i][r-1][c][d] + P[r-1][c])                                                        (repeat; r > 0)
+//                   (+) sum_{t: s->d, in = x_i, out = colTok[c]} X[i-1][r-1][c][s] + w_t + P[r-1][c]      (match; i > 0, r > 0)
+//                   (+) sum_{t: s->d, in = eps, out = colTok[c]} X[i][r-1][c][s]   + w_t + P[r-1][c]      (output-only; r > 0)
+//   W[i][r][p][d] = N[i][r][p][d]
+//                   (+) sum_{t: s->d, in = x_i, out = eps} W[i-1][r][p][s] + w_t                          (input-only; same plane)
+//                   (+) sum_{silent t: s->d, s < d}        W[i][r][p][s]   + w_t                          (silent levels, per plane)
+//   loglike       = (+)_p W[I][L][p][S-1]
+//
+// The anti-diagonal sweep of mb_profile_pair.hip with the plane axis and the exclusion vector of mb_profile_merge.hip.  One
+// workgroup per pair; the work items of a diagonal are (cell, plane, state) and the lanes stride over them.  Per diagonal: one phase
+// for N and the non-silent part of W and a barrier, one barrier per silent level, and one phase and barrier that forms X, so that no
+// edge loop runs over planes -- (I + L + 1)(nLevF + 1) barriers per pair.  The rolling sweeps keep a ring of three diagonals of N, W
+// and X, 3 (3 nCols + 2)(min(I, L) + 1) S doubles, in LDS when that fits 160 KiB, else in the pair's slice of a global scratch
+// buffer; the materialised ones keep only X there.  Cells are fp64, the sums the exact log-sum-exp.
+#include <algorithm>
+
+#include "mb_device_math.h"
+#include "mb_profile_pair_merge.h"
+
+namespace mb {
+
+template <int MODE>
+__device__ __forceinline__ double ppm_red(double a, double b) { return MODE == MB_VITERBI ? dmax(a, b) : lse2_exact(a, b); }
+
+static constexpr int PPM_THREADS = 1024;
+static constexpr size_t PPM_LDS_MAX = 160 * 1024;
+static constexpr int PPM_COUNTS_LDS_MAX = 8192;
+
+size_t profile_pair_merge_lds_bytes(int S, int nCols, long long nIn, long long nRows, bool mat) {
+  const double b = (double)profile_pair_merge_ring(S, nCols, nIn, nRows, mat) * sizeof(double);
+  return b <= (double)PPM_LDS_MAX ? (size_t)b : 0;
+}
+
+// Where cell (i, r) lives.  nw(i, r, layer): its N (layer 0) or W (layer 1), nCols + 1 planes of S states -- the materialised
+// lattice, or the ring (diagonal (i + r) mod 3, the cell by its coordinate on the short side of the lattice).  xv(i, r): its
+// exclusion vectors, column c at (c - 1) * S -- always in the ring, beside N and W when rolling.
+template <bool MAT>
+struct PairMergeLattice {
+  double *cells, *ring;
+  int S, PL, L, M, byI;
+  __device__ __forceinline__ long long slot(int i, int r) const { return (long long)((i + r) % 3) * M + (byI ? i : r); }
+  __device__ __forceinline__ double *nw(int i, int r, int layer) const {
+    if (MAT) return cells + ((((long long)i * (L + 1)) + r) * 2 + layer) * PL * S;
+    return ring + (slot(i, r) * (3 * PL - 1) + layer * PL) * S;
+  }
+  __device__ __forceinline__ double *xv(int i, int r) const {
+    if (MAT) return ring + slot(i, r) * (PL - 1) * S;
+    return ring + (slot(i, r) * (3 * PL - 1) + 2 * PL) * S;
+  }
+};
+
+// Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every N and W cell into pool (layout of mb_profile_pair_merge.h)
+// and only X in the ring, else rolling.  Viterbi keeps the FIRST maximum: N[.][.][0] takes the planes ascending; N[.][.][c] the
+// repeat first, then the match edges in `incoming` order, then the output-only edges in `incoming` order; W takes N (no move)
+// first, then the input-only edges, then the silent edges, each in `incoming` order; X and the end the planes ascending -- the
+// order k_profile_pair_merge_traceback re-enumerates.
+template <int MODE, bool MAT>
+__global__ __launch_bounds__(PPM_THREADS) void k_profile_pair_merge_fwd(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+                                                                        const int *__restrict__ inTok, const double *__restrict__ logP,
+                                                                        double *pool, double *scratch, double *__restrict__ loglike) {
+  extern __shared__ double ppm_sh[];
+  const PairProfDesc pd = descs[blockIdx.x];
+  const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
+  const int *x = inTok + pd.inBase;
+  const double *P = logP + pd.rowBase * PL;
+  const PairMergeLattice<MAT> lat{MAT ? pool + pd.cellBase : nullptr, pd.ringBase < 0 ? ppm_sh : scratch + pd.ringBase, S, PL, L,
+                                  min(I, L) + 1, I <= L};
+  const int PS = PL * S;
+  for (int d = 0; d <= I + L; ++d) {
+    const int ilo = max(0, d - L), nCells = min(I, d) - ilo + 1;
+    const int nItems = nCells * PS;
+    for (int it = threadIdx.x; it < nItems; it += blockDim.x) {
+      const int c = it / PS, pq = it - c * PS, p = pq / S, q = pq - p * S, i = ilo + c, r = d - i;
+      const int xRow = i > 0 ? q * K + x[i - 1] * C : 0;     // CSR rows q*K + key(x_i, o), o = 0..nOut: contiguous
+      double acc = (d == 0 && pq == 0) ? 0.0 : -INFINITY;
+      if (r > 0) {
+        const double w = P[(long long)(r - 1) * PL + p];
+        const double *Np = lat.nw(i, r - 1, 0);
+        if (p == 0) {
+          acc = Np[q] + w;
+          for (int k = 1; k < PL; ++k) acc = ppm_red<MODE>(acc, Np[k * S + q] + w);
+        } else if (w > -INFINITY) {                          // (a column the row rules out is skipped as a whole)
+          const int tok = mm.colTok[p - 1];
+          acc = Np[p * S + q] + w;
+          if (i > 0) {
+            const double *Xd = lat.xv(i - 1, r - 1) + (p - 1) * S;
+            const int a1 = m.inOff[xRow + tok + 1];
+            for (int a = m.inOff[xRow + tok]; a < a1; ++a) acc = ppm_red<MODE>(acc, (Xd[m.inSrc[a]] + m.inW[a]) + w);
+          }
+          const double *Xu = lat.xv(i, r - 1) + (p - 1) * S;
+          const int a1 = m.inOff[q * K + tok + 1];
+          for (int a = m.inOff[q * K + tok]; a < a1; ++a) acc = ppm_red<MODE>(acc, (Xu[m.inSrc[a]] + m.inW[a]) + w);
+        }
+      }
+      lat.nw(i, r, 0)[pq] = acc;
+      if (i > 0) {
+        const double *Wl = lat.nw(i - 1, r, 1) + p * S;
+        const int a1 = m.inOff[xRow + 1];
+        for (int a = m.inOff[xRow]; a < a1; ++a) acc = ppm_red<MODE>(acc, Wl[m.inSrc[a]] + m.inW[a]);
+      }
+      lat.nw(i, r, 1)[pq] = acc;
+    }
+    __syncthreads();
+    for (int lev = 1; lev < m.nLevF; ++lev) {      // (level 0 has no silent edge coming in: its W is complete)
+      const int l0 = m.levFOff[lev], ns = m.levFOff[lev + 1] - l0;
+      const int PN = PL * ns, nLevItems = nCells * PN;
+      for (int it = threadIdx.x; it < nLevItems; it += blockDim.x) {
+        const int c = it / PN, pj = it - c * PN, p = pj / ns, q = m.levFState[l0 + (pj - p * ns)], i = ilo + c;
+        double *Wc = lat.nw(i, d - i, 1) + p * S;
+        double acc = Wc[q];
+        const int a1 = m.inOff[q * K + 1];
+        for (int a = m.inOff[q * K]; a < a1; ++a) {
+          const int s = (int)m.inSrc[a];
+          if (s >= q) continue;                       // as the token sweeps: a silent self-loop never fires
+          acc = ppm_red<MODE>(acc, Wc[s] + m.inW[a]);
+        }
+        Wc[q] = acc;
+      }
+      __syncthreads();
+    }
+    if (d < I + L) {
+      const int XS = nC * S, nXItems = nCells * XS;
+      for (int it = threadIdx.x; it < nXItems; it += blockDim.x) {
+        const int c = it / XS, cs = it - c * XS, col = cs / S + 1, s = cs - (col - 1) * S, i = ilo + c;
+        const double *Wc = lat.nw(i, d - i, 1) + s;
+        double acc = Wc[0];                             // plane 0 is never the excluded one
+        for (int k = 1; k < PL; ++k)
+          if (k != col) acc = ppm_red<MODE>(acc, Wc[k * S]);
+        lat.xv(i, d - i)[cs] = acc;
+      }
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x == 0) {
+    const double *We = lat.nw(I, L, 1) + S - 1;
+    double acc = We[0];
+    for (int p = 1; p < PL; ++p) acc = ppm_red<MODE>(acc, We[p * S]);
+    loglike[blockIdx.x] = acc;
+  }
+}
+
+// Materialised Backward sweep, layer 0 = NB ("from the arrived stage"), layer 1 = WB ("from the waiting stage"):
+//   T[i][r][c][s]  = sum_{t: s->d, in = x_{i+1}, out = colTok[c]} (w_t + P[r][c]) + NB[i+1][r+1][c][d]     (i < I, r < L)
+//                    (+) sum_{t: s->d, in = eps, out = colTok[c]} (w_t + P[r][c]) + NB[i][r+1][c][d]       (r < L)
+//   WB[i][r][k][s] = [i = I, r = L, s = S-1]  (+)  (+)_{c != k} T[i][r][c][s]
+//                    (+) sum_{t: in = x_{i+1}, out = eps} w_t + WB[i+1][r][k][d]                           (i < I)
+//                    (+) sum_{silent t, s < d}            w_t + WB[i][r][k][d]
+//   NB[i][r][k][s] = WB[i][r][k][s] (+) (P[r][0] + NB[i][r+1][0][s]) (+) [k >= 1](P[r][k] + NB[i][r+1][k][s])   (r < L)
+//   loglike        = NB[0][0][0][0]
+// Anti-diagonals from I + L down.  T, everything that leaves (i, r, s) through column c, is formed once per diagonal over (cell,
+// column, state) -- the mirror of the Forward's X -- so the edge loops do not run over planes; it lives in the ring (one diagonal of
+// it, the cell by its place on the diagonal).  A state's WB is final once its backward level has run; the item that finishes it
+// writes its NB.
+__global__ __launch_bounds__(PPM_THREADS) void k_profile_pair_merge_bwd(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+                                                                        const int *__restrict__ inTok, const double *__restrict__ logP,
+                                                                        double *pool, double *scratch, double *__restrict__ loglike) {
+  extern __shared__ double ppm_sh[];
+  const PairProfDesc pd = descs[blockIdx.x];
+  const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
+  const int *x = inTok + pd.inBase;
+  const double *P = logP + pd.rowBase * PL;
+  const PairMergeLattice<true> lat{pool + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  double *T = pd.ringBase < 0 ? ppm_sh : scratch + pd.ringBase;       // T[(cell on the diagonal * nCols + c - 1) * S + s]
+  const int PS = PL * S, XS = nC * S;
+  for (int d = I + L; d >= 0; --d) {
+    const int ilo = max(0, d - L), nCells = min(I, d) - ilo + 1;
+    if (d < I + L) {
+      const int nTItems = nCells * XS;
+      for (int it = threadIdx.x; it < nTItems; it += blockDim.x) {
+        const int c = it / XS, cs = it - c * XS, col = cs / S + 1, s = cs - (col - 1) * S, i = ilo + c, r = d - i;
+        double v = -INFINITY;
+        if (r < L) {
+          const double pc = P[(long long)r * PL + col];
+          if (pc > -INFINITY) {
+            const int tok = mm.colTok[col - 1];
+            if (i < I) {
+              const double *Nd = lat.nw(i + 1, r + 1, 0) + col * S;
+              const int xRow = s * K + x[i] * C;
+              const int a1 = m.outOff[xRow + tok + 1];
+              for (int a = m.outOff[xRow + tok]; a < a1; ++a) v = lse2_exact(v, (m.outW[a] + pc) + Nd[m.outDst[a]]);
+            }
+            const double *Nu = lat.nw(i, r + 1, 0) + col * S;
+            const int a1 = m.outOff[s * K + tok + 1];
+            for (int a = m.outOff[s * K + tok]; a < a1; ++a) v = lse2_exact(v, (m.outW[a] + pc) + Nu[m.outDst[a]]);
+          }
+        }
+        T[it] = v;
+      }
+      __syncthreads();
+    }
+    const int nItems = nCells * PS;
+    for (int it = threadIdx.x; it < nItems; it += blockDim.x) {
+      const int c = it / PS, ks = it - c * PS, k = ks / S, s = ks - k * S, i = ilo + c, r = d - i;
+      double v = (d == I + L && s == S - 1) ? 0.0 : -INFINITY;
+      if (r < L) {
+        const double *Tc = T + (long long)c * XS + s;
+        for (int col = 1; col < PL; ++col)
+          if (col != k) v = lse2_exact(v, Tc[(col - 1) * S]);
+      }
+      if (i < I) {
+        const double *Wl = lat.nw(i + 1, r, 1) + k * S;
+        const int xRow = s * K + x[i] * C;
+        const int a1 = m.outOff[xRow + 1];
+        for (int a = m.outOff[xRow]; a < a1; ++a) v = lse2_exact(v, Wl[m.outDst[a]] + m.outW[a]);
+      }
+      lat.nw(i, r, 1)[ks] = v;
+      if (r < L) {
+        const double *Nn = lat.nw(i, r + 1, 0), *Pr = P + (long long)r * PL;
+        v = lse2_exact(v, Pr[0] + Nn[s]);
+        if (k) v = lse2_exact(v, Pr[k] + Nn[ks]);
+      }
+      lat.nw(i, r, 0)[ks] = v;
+    }
+    __syncthreads();
+    for (int lev = 1; lev < m.nLevB; ++lev) {
+      const int l0 = m.levBOff[lev], ns = m.levBOff[lev + 1] - l0;
+      const int PN = PL * ns, nLevItems = nCells * PN;
+      for (int it = threadIdx.x; it < nLevItems; it += blockDim.x) {
+        const int c = it / PN, kj = it - c * PN, k = kj / ns, s = m.levBState[l0 + (kj - k * ns)], i = ilo + c, r = d - i;
+        double *Wc = lat.nw(i, r, 1) + k * S;
+        double v = Wc[s];
+        const int a1 = m.outOff[s * K + 1];
+        for (int a = m.outOff[s * K]; a < a1; ++a) {
+          const int t = (int)m.outDst[a];
+          if (t <= s) continue;
+          v = lse2_exact(v, Wc[t] + m.outW[a]);
+        }
+        Wc[s] = v;
+        if (r < L) {
+          const double *Nn = lat.nw(i, r + 1, 0), *Pr = P + (long long)r * PL;
+          v = lse2_exact(v, Pr[0] + Nn[s]);
+          if (k) v = lse2_exact(v, Pr[k] + Nn[k * S + s]);
+        }
+        lat.nw(i, r, 0)[k * S + s] = v;
+      }
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x == 0) loglike[blockIdx.x] = lat.nw(0, 0, 0)[0];
+}
+
+// Posterior counts.  With both lattices in memory every (cell, plane, edge) term is independent:
+//   count[t] += exp(W_F[i][r][k][s] - LL + term_t), term_t the edge's summand of WB[i][r][k][s] above (through T for the emitting
+//   edges: every column c != k),
+// so the sweep is a flat grid over (pair, group of the pair, (cell, plane, state)).  Per-workgroup partial counts are kept in LDS when
+// the transition table is small and flushed once with atomics; det: both tables hold 64-bit fixed point at 2^-36 (mb_internal.h) --
+// integer adds commute, so the counts are the same bits from call to call.  A pair whose likelihood is -inf adds nothing.
+__global__ __launch_bounds__(256) void k_profile_pair_merge_counts(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+                                                                   int groupsPerPair, const int *__restrict__ inTok,
+                                                                   const double *__restrict__ logP, const double *__restrict__ fwdPool,
+                                                                   const double *__restrict__ bwdPool, long long nTrans,
+                                                                   double *__restrict__ counts, int det) {
+  __shared__ double lcount[PPM_COUNTS_LDS_MAX];
+  const bool useLds = nTrans <= PPM_COUNTS_LDS_MAX;
+  if (useLds) {
+    for (int e = threadIdx.x; e < nTrans; e += blockDim.x) lcount[e] = 0.0;
+    __syncthreads();
+  }
+  const int pair = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
+  const PairProfDesc pd = descs[pair];
+  const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
+  const int *x = inTok + pd.inBase;
+  const double *P = logP + pd.rowBase * PL;
+  const PairMergeLattice<true> F{const_cast<double *>(fwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0},
+      B{const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  double LL;
+  {
+    const double *We = F.nw(I, L, 1) + S - 1;
+    LL = We[0];
+    for (int p = 1; p < PL; ++p) LL = lse2_exact(LL, We[p * S]);
+  }
+  double *tab = useLds ? lcount : counts;
+  auto add = [&](uint32_t e, double c) {
+    if (c != 0.0) {
+      if (det) atomicAdd((unsigned long long *)tab + e, (unsigned long long)fmin(fmax(c * 68719476736.0 + 0.5, 0.0), 4611686018427387904.0));
+      else atomicAdd(&tab[e], c);
+    }
+  };
+  if (LL > -INFINITY) {
+    const long long PS = (long long)PL * S, nItems = (long long)(I + 1) * (L + 1) * PS;
+    for (long long idx = (long long)group * blockDim.x + threadIdx.x; idx < nItems; idx += (long long)groupsPerPair * blockDim.x) {
+      const long long cell = idx / PS;
+      const int ks = (int)(idx - cell * PS), k = ks / S, s = ks - k * S, i = (int)(cell / (L + 1)), r = (int)(cell - (long long)i * (L + 1));
+      const double f = F.nw(i, r, 1)[ks] - LL;
+      if (!(f > -INFINITY)) continue;
+      const int xRow = i < I ? s * K + x[i] * C : 0;
+      if (r < L) {
+        const double *Pr = P + (long long)r * PL;
+        for (int col = 1; col < PL; ++col) {
+          const double pc = Pr[col];
+          if (col == k || !(pc > -INFINITY)) continue;
+          const int tok = mm.colTok[col - 1];
+          if (i < I) {
+            const double *Nd = B.nw(i + 1, r + 1, 0) + col * S;
+            const int a1 = m.outOff[xRow + tok + 1];
+            for (int a = m.outOff[xRow + tok]; a < a1; ++a) add(m.outEid[a], exp(f + ((m.outW[a] + pc) + Nd[m.outDst[a]])));
+          }
+          const double *Nu = B.nw(i, r + 1, 0) + col * S;
+          const int a1 = m.outOff[s * K + tok + 1];
+          for (int a = m.outOff[s * K + tok]; a < a1; ++a) add(m.outEid[a], exp(f + ((m.outW[a] + pc) + Nu[m.outDst[a]])));
+        }
+      }
+      if (i < I) {
+        const double *Wl = B.nw(i + 1, r, 1) + k * S;
+        const int a1 = m.outOff[xRow + 1];
+        for (int a = m.outOff[xRow]; a < a1; ++a) add(m.outEid[a], exp(f + (Wl[m.outDst[a]] + m.outW[a])));
+      }
+      const double *Wc = B.nw(i, r, 1) + k * S;
+      const int a1 = m.outOff[s * K + 1];
+      for (int a = m.outOff[s * K]; a < a1; ++a) {
+        const int t = (int)m.outDst[a];
+        if (t <= s) continue;
+        add(m.outEid[a], exp(f + (Wc[t] + m.outW[a])));
+      }
+    }
+  }
+  if (useLds) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < nTrans; e += blockDim.x)
+      if (det ? ((const unsigned long long *)lcount)[e] != 0ull : lcount[e] != 0.0) {
+        if (det) atomicAdd((unsigned long long *)counts + e, ((const unsigned long long *)lcount)[e]);
+        else atomicAdd(&counts[e], lcount[e]);
+      }
+  }
+}
+
+// Viterbi traceback over a materialised max lattice, one lane per pair: from the first plane that attains the score at
+// W[I][L][.][S-1] back to N[0][0][0][0], taking at every cell the first candidate (in the fill's order) whose value equals the cell;
+// an emitting edge comes from the lowest plane k != c whose W equals the edge's X.  Blank and repeat rows are not edges.  Edges go
+// start -> end into the pair's slot (profile_pair_path_bound entries) with the row each fired at, as k_profile_pair_traceback.
+// len = -1: no finite path, -2: the slot was too small, -3: no candidate matched (a corrupt matrix).
+__global__ void k_profile_pair_merge_traceback(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs, int n,
+                                               const int *__restrict__ inTok, const double *__restrict__ logP,
+                                               const double *__restrict__ pool, uint32_t *edges, int32_t *rows, long long *len) {
+  const int pair = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pair >= n) return;
+  const PairProfDesc pd = descs[pair];
+  const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
+  const int *x = inTok + pd.inBase;
+  const double *P = logP + pd.rowBase * PL;
+  const PairMergeLattice<true> lat{const_cast<double *>(pool) + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  uint32_t *pe = edges + pd.pathBase;
+  int32_t *pr = rows + pd.pathBase;
+  int i = I, r = L, q = S - 1, layer = 1, p = 0;
+  const long long cap = I + L + (long long)(I + L + 1) * (m.nLevF - 1);
+  long long cnt = 0;
+  {
+    const double *We = lat.nw(I, L, 1) + q;
+    double best = We[0];
+    for (int k = 1; k < PL; ++k)
+      if (best < We[k * S]) { best = We[k * S]; p = k; }
+    if (!(best > -INFINITY)) { len[pair] = -1; return; }
+  }
+  for (;;) {
+    const int xRow = i > 0 ? q * K + x[i - 1] * C : 0;
+    int a = 0, found = -1, ni = i;
+    if (layer == 1) {
+      const double *W = lat.nw(i, r, 1) + p * S;
+      const double cur = W[q];
+      if (lat.nw(i, r, 0)[p * S + q] == cur) { layer = 0; continue; }
+      if (i > 0) {
+        const double *Wl = lat.nw(i - 1, r, 1) + p * S;
+        a = m.inOff[xRow];
+        for (const int a1 = m.inOff[xRow + 1]; a < a1; ++a)
+          if (Wl[m.inSrc[a]] + m.inW[a] == cur) { found = (int)m.inSrc[a]; ni = i - 1; break; }
+      }
+      if (found < 0) {
+        a = m.inOff[q * K];
+        for (const int a1 = m.inOff[q * K + 1]; a < a1; ++a) {
+          const int s = (int)m.inSrc[a];
+          if (s < q && W[s] + m.inW[a] == cur) { found = s; break; }
+        }
+      }
+      if (found < 0) { len[pair] = -3; return; }
+      if (cnt >= cap) { len[pair] = -2; return; }
+      pe[cnt] = m.inEid[a]; pr[cnt] = r; ++cnt;
+      i = ni; q = found;
+    } else {
+      if (r == 0) { if (i != 0 || q != 0 || p != 0) { len[pair] = -3; return; } break; }
+      const double *Np = lat.nw(i, r - 1, 0);
+      const double cur = lat.nw(i, r, 0)[p * S + q], w = P[(long long)(r - 1) * PL + p];
+      if (p == 0) {
+        int k = 0;
+        while (k < PL && !(Np[k * S + q] + w == cur)) ++k;
+        if (k == PL) { len[pair] = -3; return; }
+        p = k; --r;
+        continue;
+      }
+      if (Np[p * S + q] + w == cur) { --r; continue; }
+      const int tok = mm.colTok[p - 1];
+      int from = -1;
+      // the edge's X and the lowest plane that attains it
+      auto excl = [&](const double *Wv, int s, int &kx) {
+        double xs = Wv[s];
+        kx = 0;
+        for (int k = 1; k < PL; ++k)
+          if (k != p && xs < Wv[k * S + s]) { xs = Wv[k * S + s]; kx = k; }
+        return xs;
+      };
+      if (i > 0) {
+        const double *Wd = lat.nw(i - 1, r - 1, 1);
+        a = m.inOff[xRow + tok];
+        for (const int a1 = m.inOff[xRow + tok + 1]; a < a1; ++a) {
+          int kx;
+          const double xs = excl(Wd, (int)m.inSrc[a], kx);
+          if ((xs + m.inW[a]) + w == cur) { found = (int)m.inSrc[a]; from = kx; ni = i - 1; break; }
+        }
+      }
+      if (found < 0) {
+        const double *Wu = lat.nw(i, r - 1, 1);
+        a = m.inOff[q * K + tok];
+        for (const int a1 = m.inOff[q * K + tok + 1]; a < a1; ++a) {
+          int kx;
+          const double xs = excl(Wu, (int)m.inSrc[a], kx);
+          if ((xs + m.inW[a]) + w == cur) { found = (int)m.inSrc[a]; from = kx; break; }
+        }
+      }
+      if (found < 0) { len[pair] = -3; return; }
+      if (cnt >= cap) { len[pair] = -2; return; }
+      --r;
+      pe[cnt] = m.inEid[a]; pr[cnt] = r; ++cnt;
+      i = ni; q = found; p = from; layer = 1;
+    }
+  }
+  for (long long u = 0, v = cnt - 1; u < v; ++u, --v) {
+    const uint32_t e = pe[u]; pe[u] = pe[v]; pe[v] = e;
+    const int32_t w = pr[u]; pr[u] = pr[v]; pr[v] = w;
+  }
+  len[pair] = cnt;
+}
+
+static int ppm_threads(long long maxItems) { return (int)std::min<long long>(PPM_THREADS, std::max<long long>(64, (maxItems + 63) / 64 * 64)); }
+
+// beyond the default 64 KiB the kernels must be told; asked for once, and only when a ring needs it
+static bool ppm_allow_lds(size_t lds) {
+  static size_t ldsAllowed = 64 * 1024;
+  if (lds <= ldsAllowed) return true;
+  const void *ks[] = {(const void *)&k_profile_pair_merge_fwd<MB_FORWARD, false>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, false>,
+                      (const void *)&k_profile_pair_merge_fwd<MB_FORWARD, true>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, true>,
+                      (const void *)&k_profile_pair_merge_bwd};
+  for (const void *k : ks)
+    if (!hip_ok(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPM_LDS_MAX), "k_profile_pair_merge: raising the LDS limit")) return false;
+  ldsAllowed = PPM_LDS_MAX;
+  return true;
+}
+
+int launch_profile_pair_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const PairProfDesc *d, int n, size_t lds,
+                                  long long maxItems, const int *inTok, const double *logP, double *pool, double *scratch,
+                                  double *loglike, hipStream_t st) {
+  if (n <= 0) return 0;
+  if (!ppm_allow_lds(lds)) return 1;
+  const dim3 g(n), b(ppm_threads(maxItems));
+  if (mode == MB_VITERBI) {
+    if (mat) k_profile_pair_merge_fwd<MB_VITERBI, true><<<g, b, lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
+    else k_profile_pair_merge_fwd<MB_VITERBI, false><<<g, b, lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
+  } else {
+    if (mat) k_profile_pair_merge_fwd<MB_FORWARD, true><<<g, b, lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
+    else k_profile_pair_merge_fwd<MB_FORWARD, false><<<g, b, lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
+  }
+  return hip_ok(hipGetLastError(), "k_profile_pair_merge_fwd") ? 0 : 1;
+}
+
+int launch_profile_pair_merge_bwd(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, size_t lds, long long maxItems,
+                                  const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  if (n <= 0) return 0;
+  if (!ppm_allow_lds(lds)) return 1;
+  k_profile_pair_merge_bwd<<<dim3(n), dim3(ppm_threads(maxItems)), lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
+  return hip_ok(hipGetLastError(), "k_profile_pair_merge_bwd") ? 0 : 1;
+}
+
+int launch_profile_pair_merge_counts(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, int groupsPerPair, const int *inTok,
+                                     const double *logP, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
+  if (n <= 0 || m->nTrans <= 0) return 0;
+  k_profile_pair_merge_counts<<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(
+      m->dev, mm, d, groupsPerPair, inTok, logP, fwdPool, bwdPool, m->nTrans, counts, g_deterministic ? 1 : 0);
+  return hip_ok(hipGetLastError(), "k_profile_pair_merge_counts") ? 0 : 1;
+}
+
+int launch_profile_pair_merge_traceback(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, const int *inTok,
+                                        const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len,
+                                        hipStream_t st) {
+  if (n <= 0) return 0;
+  k_profile_pair_merge_traceback<<<(n + 63) / 64, 64, 0, st>>>(m->dev, mm, d, n, inTok, logP, pool, edges, rows, len);
+  return hip_ok(hipGetLastError(), "k_profile_pair_merge_traceback") ? 0 : 1;
+}
+
+}  // namespace mb

@@ -689,3 +689,245 @@ class PairProfileDP(ProfileDP):
                 edges.append(e); rows.append(r); q = s; layer = 1
                 i -= kind == "match"
         return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32)
+
+
+def _excl_planes(A: np.ndarray, mx: bool) -> np.ndarray:
+    """out[k] = (+)_{j != k} A[j] over axis 0 of A[planes, ...], every k at once: a prefix and a suffix reduction joined, planes + 1
+    vector operations instead of planes^2 (one plane: all -inf).  Pairwise max or exact pairwise log-sum-exp."""
+    op = np.maximum if mx else np.logaddexp
+    out = np.full(A.shape, _NEG)
+    if len(A) > 1:
+        pre, suf = op.accumulate(A, axis=0), op.accumulate(A[::-1], axis=0)[::-1]
+        out[1:] = pre[:-1]
+        out[:-1] = op(out[:-1], suf[1:])
+    return out
+
+
+class PairMergedProfileDP(PairProfileDP):
+    """A machine WITH an input alphabet on a known input sequence x[1..I] against a CTC-MERGED profile of L rows, in numpy -- the
+    yardstick of mb_profile_pair_merge.hip (docs/profile_tapes.md, "Pairs against a merged profile"): the semantics of
+    compose(M, transpose(CSVProfile::mergingMachine())) run on input x with an empty output.  The lattice of PairProfileDP with the
+    plane axis of MergedProfileDP: plane 0 = the last row took the blank (or no row yet), plane c = the last row took column c, whose
+    output token is colTok[c - 1].  N = "arrived", W = "after M's output-less moves", X the exclusion vector:
+
+        X[i][r][c][s] = (+)_{k != c} W[i][r][k][s]
+        N[i][r][0][d] = [i = 0, r = 0, d = 0]  (+)  (+)_p (N[i][r-1][p][d] + P[r-1][0])                    (blank; r > 0)
+        N[i][r][c][d] = (N[i][r-1][c][d] + P[r-1][c])                                                      (repeat; r > 0)
+                        (+) sum_{t: s->d, in = x_i, out = colTok[c]} X[i-1][r-1][c][s] + w_t + P[r-1][c]    (match; i > 0, r > 0)
+                        (+) sum_{t: s->d, in = eps, out = colTok[c]} X[i][r-1][c][s]   + w_t + P[r-1][c]    (output-only; r > 0)
+        W[i][r][p][d] = N[i][r][p][d]
+                        (+) sum_{t: s->d, in = x_i, out = eps} W[i-1][r][p][s] + w_t                        (input-only; same plane)
+                        (+) sum_{silent t: s->d, s < d}        W[i][r][p][s]   + w_t                        (silent levels, per plane)
+        loglike       = (+)_p W[I][L][p][S-1]
+
+    The blank and the repeat read N, never W.  Viterbi keeps the FIRST maximum -- N[.][.][0]: planes ascending; N[.][.][c]: the
+    repeat, then match edges in `incoming` order, then output-only edges in `incoming` order, each from the lowest plane k != c
+    that attains its X; W: "no move", then input-only edges, then silent edges, each in `incoming` order; the end: planes
+    ascending.  Every method takes (x, P): P the [L, nCols + 1] log weights of Profile.mergeRows.  Lattices are
+    [I + 1, L + 1, nCols + 1, S]."""
+
+    def __init__(self, em: EvaluatedMachine, colTok: Sequence[int]):
+        super().__init__(em)
+        self.colTok = np.asarray(colTok, np.int64).reshape(-1)
+        self.nCols = len(self.colTok)
+        if self.nCols < 1:
+            raise MachineError("merged profiles need at least one column")
+        if self.colTok.min() < 1 or self.colTok.max() > em.nOutTok:
+            raise MachineError("column token outside 1..nOutTok")
+        self.PL = self.nCols + 1
+
+        def by_column(tab):
+            """(edge id, src, dst, w, column) of the edges of ``tab`` whose token heads a column: column-major, `incoming` order within"""
+            e, s, d, w, o = tab
+            sel = [np.nonzero(o == t)[0] for t in self.colTok]
+            col = np.concatenate([np.full(len(k), c + 1, np.int64) for c, k in enumerate(sel)])
+            k = np.concatenate(sel).astype(np.int64)
+            return e[k], s[k], d[k], w[k], col
+        self.matchCol = [by_column(t) for t in self.match]
+        self.emitCol = by_column((self.eId, self.eS, self.eD, self.eW, self.eO))
+
+    def _check(self, P) -> np.ndarray:
+        P = np.asarray(P, np.float64).reshape(-1, self.PL)
+        if np.isnan(P).any() or (P == math.inf).any():
+            raise MachineError("profile weight is NaN or +infinity")
+        return P
+
+    def _planes(self, fold, base: np.ndarray, d: np.ndarray, vals: np.ndarray) -> np.ndarray:
+        """fold over (plane, state) at once: vals[PL, n] into base[PL, S] at column d[n] of every plane"""
+        S = self.S
+        idx = (np.arange(self.PL)[:, None] * S + d[None, :]).ravel()
+        return fold(base.ravel(), idx, vals.ravel()).reshape(self.PL, S)
+
+    def forward(self, x, P, mode: str = "exact") -> Tuple[float, np.ndarray, np.ndarray]:
+        """(loglike, N[I+1][L+1][nCols+1][S], W[I+1][L+1][nCols+1][S]); mode "exact" or "max"."""
+        return self._sweep(x, P, mode)[:3]
+
+    def _sweep(self, x, P, mode: str):
+        """forward() and the exclusion vectors X[I+1][L+1][nCols+1][S] (plane 0 of X is not read)"""
+        x, P = self._checkPair(x, P)
+        mx = mode == "max"
+        fold = _max_fold if mx else _lse_fold
+        I, L, S, PL = len(x), len(P), self.S, self.PL
+        N = np.full((I + 1, L + 1, PL, S), _NEG); W = np.full((I + 1, L + 1, PL, S), _NEG)
+        X = np.full((I + 1, L + 1, PL, S), _NEG)
+        for i in range(I + 1):
+            for r in range(L + 1):
+                base = np.full((PL, S), _NEG)
+                if i == 0 and r == 0:
+                    base[0, 0] = 0.0
+                if r:
+                    Pr = P[r - 1]
+                    base[0] = _red_planes(N[i, r - 1] + Pr[0], mx)
+                    flat = (N[i, r - 1] + Pr[:, None]).ravel()
+                    flat[:S] = base[0]
+                    idx, vals = [], []
+                    if i:
+                        _, s, d, w, c = self.matchCol[x[i - 1]]
+                        idx.append(c * S + d); vals.append((X[i - 1, r - 1][c, s] + w) + Pr[c])
+                    _, s, d, w, c = self.emitCol
+                    idx.append(c * S + d); vals.append((X[i, r - 1][c, s] + w) + Pr[c])
+                    base = fold(flat, np.concatenate(idx), np.concatenate(vals)).reshape(PL, S)
+                N[i, r] = base
+                w_ = base.copy()
+                if i:
+                    _, s, d, w, _o = self.ins[x[i - 1]]
+                    w_ = self._planes(fold, w_, d, W[i - 1, r][:, s] + w)
+                for lv in self.fLevels:
+                    w_ = self._planes(fold, w_, self.sD[lv], w_[:, self.sS[lv]] + self.sW[lv])
+                W[i, r] = w_
+                X[i, r] = _excl_planes(w_, mx)
+        return float(_red_planes(W[I, L, :, S - 1:S], mx)[0]), N, W, X
+
+    def backward(self, x, P) -> Tuple[float, np.ndarray, np.ndarray]:
+        """(loglike, NB[I+1][L+1][nCols+1][S], WB[I+1][L+1][nCols+1][S]), exact log-sum-exp; loglike = NB[0][0][0][0]."""
+        x, P = self._checkPair(x, P)
+        I, L, S, PL = len(x), len(P), self.S, self.PL
+        NB = np.full((I + 1, L + 1, PL, S), _NEG); WB = np.full((I + 1, L + 1, PL, S), _NEG)
+        for i in range(I, -1, -1):
+            for r in range(L, -1, -1):
+                base = np.full((PL, S), _NEG)
+                if r < L:
+                    # T[c][s]: everything that leaves s through column c; WB[k] takes the columns other than k
+                    idx, vals = [], []
+                    if i < I:
+                        _, s, d, w, c = self.matchCol[x[i]]
+                        idx.append(c * S + s); vals.append((w + P[r][c]) + NB[i + 1, r + 1][c, d])
+                    _, s, d, w, c = self.emitCol
+                    idx.append(c * S + s); vals.append((w + P[r][c]) + NB[i, r + 1][c, d])
+                    T = _lse_fold(np.full(PL * S, _NEG), np.concatenate(idx), np.concatenate(vals)).reshape(PL, S)
+                    base = _excl_planes(T, False)
+                if i == I and r == L:
+                    base[:, S - 1] = 0.0
+                if i < I:
+                    _, s, d, w, _o = self.ins[x[i]]
+                    base = self._planes(_lse_fold, base, s, WB[i + 1, r][:, d] + w)
+                for lv in self.bLevels:
+                    base = self._planes(_lse_fold, base, self.sS[lv], base[:, self.sD[lv]] + self.sW[lv])
+                WB[i, r] = base
+                if r < L:
+                    nb = np.logaddexp(base, P[r][0] + NB[i, r + 1][0])
+                    nb[1:] = np.logaddexp(nb[1:], P[r][1:, None] + NB[i, r + 1][1:])
+                    NB[i, r] = nb
+                else:
+                    NB[i, r] = base
+        return float(NB[0, 0, 0, 0]), NB, WB
+
+    def counts(self, x, P, blanks: Optional[list] = None) -> Tuple[np.ndarray, float]:
+        """(posterior expected use of every transition, Forward loglike); nothing for a -inf pair.  Blank and repeat rows are not
+        edges; ``blanks`` (a list) receives their posterior mass, summed over the lattice."""
+        x, P = self._checkPair(x, P)
+        ll, NF, WF, XF = self._sweep(x, P, "exact")
+        out = np.zeros(self.em.nTransitions)
+        if not ll > _NEG:
+            return out, ll
+        _, NB, WB = self.backward(x, P)
+        I, L = len(x), len(P)
+        blank = 0.0
+        with np.errstate(invalid="ignore"):
+            for i in range(I + 1):
+                for r in range(L + 1):
+                    f, fx = WF[i, r] - ll, XF[i, r] - ll
+                    if r < L:
+                        if i < I:
+                            e, s, d, w, c = self.matchCol[x[i]]
+                            np.add.at(out, e, np.exp(fx[c, s] + ((w + P[r][c]) + NB[i + 1, r + 1][c, d])))
+                        e, s, d, w, c = self.emitCol
+                        np.add.at(out, e, np.exp(fx[c, s] + ((w + P[r][c]) + NB[i, r + 1][c, d])))
+                        n = NF[i, r] - ll
+                        b = np.concatenate([(n + (P[r][0] + NB[i, r + 1][0])).ravel(), (n[1:] + (P[r][1:, None] + NB[i, r + 1][1:])).ravel()])
+                        blank += float(np.exp(b[b > _NEG]).sum())
+                    if i < I:
+                        e, s, d, w, _o = self.ins[x[i]]
+                        np.add.at(out, e, np.exp(f[:, s] + (WB[i + 1, r][:, d] + w)).sum(axis=0))
+                    np.add.at(out, self.sId, np.exp(f[:, self.sS] + (WB[i, r][:, self.sD] + self.sW)).sum(axis=0))
+        if blanks is not None:
+            blanks.append(blank)
+        return out, ll
+
+    def viterbi(self, x, P, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray]:
+        """(score, global edge ids start -> end, row at which each fired); the first maximum in the fill's candidate order.  Rows as
+        PairProfileDP.viterbi; blank and repeat rows are not edges.  ``census`` counts, by the candidate taken, the steps at which
+        two or more candidates equal the cell: "end"; "stay" / "input" / "silent" at a W cell; "blank" at N[.][.][0]; "repeat" /
+        "match" / "emit" at N[.][.][c]; "plane" for an emitting edge whose X two planes attain."""
+        x, P = self._checkPair(x, P)
+        v, N, W = self.forward(x, P, "max")
+        edges: List[int] = []; rows: List[int] = []
+        if not v > _NEG:
+            return v, np.zeros(0, np.uint32), np.zeros(0, np.int32)
+
+        def tie(kind: str, n: int):
+            if census is not None and n > 1:
+                census[kind] = census.get(kind, 0) + 1
+        i, r, q, layer = len(x), len(P), self.S - 1, 1
+        ends = [p for p in range(self.PL) if W[i, r, p, q] == v]
+        tie("end", len(ends))
+        p = ends[0]
+        while True:
+            cand = []          # (kind, edge id or -1, source state, input position of the source, attains the cell)
+            if layer == 1:
+                cur = W[i, r, p, q]
+                cand.append(("stay", -1, q, i, N[i, r, p, q] == cur))
+                if i:
+                    e, s, d, w, _o = self.ins[x[i - 1]]
+                    cand += [("input", int(e[k]), int(s[k]), i - 1, W[i - 1, r, p, s[k]] + w[k] == cur) for k in np.nonzero(d == q)[0]]
+                cand += [("silent", int(self.sId[k]), int(self.sS[k]), i, W[i, r, p, self.sS[k]] + self.sW[k] == cur) for k in self.inSil[q]]
+                hits = [c for c in cand if c[4]]
+                kind, e, s, ni, _ = hits[0]
+                tie(kind, len(hits))
+                if kind == "stay":
+                    layer = 0
+                else:
+                    edges.append(e); rows.append(r); q = s; i = ni
+                continue
+            if r == 0:
+                assert i == 0 and q == 0 and p == 0
+                break
+            Pr, cur = P[r - 1], N[i, r, p, q]
+            if p == 0:
+                hit = [N[i, r - 1, k, q] + Pr[0] == cur for k in range(self.PL)]
+                tie("blank", sum(hit))
+                p = hit.index(True)
+                r -= 1
+                continue
+            oth = [k for k in range(self.PL) if k != p]
+            tok = self.colTok[p - 1]
+            cand.append(("repeat", -1, q, i, None, N[i, r - 1, p, q] + Pr[p] == cur))
+            if i:
+                e, s, d, w, o = self.match[x[i - 1]]
+                for k in np.nonzero((d == q) & (o == tok))[0]:
+                    xv = max(W[i - 1, r - 1, o_, s[k]] for o_ in oth)
+                    cand.append(("match", int(e[k]), int(s[k]), i - 1, xv, (xv + w[k]) + Pr[p] == cur))
+            for k in self.inEmit[q]:
+                if self.eO[k] == tok:
+                    xv = max(W[i, r - 1, o_, self.eS[k]] for o_ in oth)
+                    cand.append(("emit", int(self.eId[k]), int(self.eS[k]), i, xv, (xv + self.eW[k]) + Pr[p] == cur))
+            hits = [c for c in cand if c[5]]
+            kind, e, s, ni, xv, _ = hits[0]
+            tie(kind, len(hits))
+            r -= 1
+            if kind == "repeat":
+                continue
+            src = [k for k in oth if W[ni, r, k, s] == xv]
+            tie("plane", len(src))
+            edges.append(e); rows.append(r); q = s; i = ni; p = src[0]; layer = 1
+        return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32)
