@@ -206,6 +206,22 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
 int mb_profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows,
                          double *cellsOut);
 
+/* Pairs under an envelope (docs/profile_tapes.md, "Pairs under an envelope"): per row r = 0..rows the half-open interval
+ * [inStart[r], inEnd[r]) of input positions whose cells exist, both layers of every other cell -inf -- Envelope::inStart / inEnd in
+ * the orientation of mb_batch_set_envelopes.  Pair k owns rows envOff[k]..envOff[k+1]: rows_k + 1 of them, or none (full: the pair
+ * runs the sweeps above, in a launch of their own when the batch holds both kinds).  envOff == NULL clears every envelope.  The
+ * sweeps visit the envelope cells alone; materialised lattices are compact, cells[((off[r] + i - inStart[r])*2 + layer)*nStates +
+ * state] with off[r] the cells of the rows before r, and mb_profile_pairs_cells is the doubles of all of them (the memory budget
+ * chunks by it).  mb_profile_pair_fill_env hands back the full rectangle of mb_profile_pair_fill with -inf outside; both pointers
+ * NULL = no envelope.  Errors, before anything is launched (the pairs are then left without envelopes): "Envelope/sequence mismatch"
+ * (a row count other than rows + 1, inEnd > nIn + 1, inStart < 0 or > inEnd), "Envelope is not connected" (the rule of
+ * Envelope::connected; (0, 0) and (nIn, rows) lie inside), "Envelope is not monotone" (inStart or inEnd decreases from a row to the
+ * next), "envelopes take plain profiles" (a merged pairs object). */
+int mb_profile_pairs_set_envelopes(mb_profile_pairs *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd);
+int mb_profile_pair_fill_env(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows,
+                             const int32_t *envStart, const int32_t *envEnd, double *cellsOut);
+int64_t mb_profile_pairs_cells(const mb_profile_pairs *p);   /* doubles of all materialised lattices under the current envelopes */
+
 /* Pairs against CTC-merged profiles: a known input sequence against the rows of `--recognize-merge-csv` -- the semantics of
  * compose(M, transpose(CSVProfile::mergingMachine())) on input x[1..I] with an empty output, swept natively over
  * (I + 1) x (rows + 1) x 2 x (nCols + 1) x nStates along anti-diagonals (mb_profile_pair_merge.hip; docs/profile_tapes.md, "Pairs

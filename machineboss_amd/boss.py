@@ -3,7 +3,8 @@
     python -m machineboss_amd.boss MACHINE.json [--preset NAME] [-P params.json] [-F funcs.json] [-N constraints.json]
            [-D seqpairs.json] [--input-chars S] [--output-chars S] [--input-fasta F] [--output-fasta F]
            [--input-json F] [--output-json F] [--use-defaults] [-L] [-V] [-A] [-C] [-T] [-R width]
-           [--generate-json F] [--recognize-csv F [--prefix-decode] [--viterbi-decode]] [--recognize-merge-csv F [--viterbi-decode]]
+           [--generate-json F] [--recognize-csv F [--prefix-decode] [--viterbi-decode] [--profile-band N]]
+           [--recognize-merge-csv F [--viterbi-decode]]
            [--prefix-decode] [--prefix-encode] [--prefix-backtrack N] [--viterbi-decode] [--viterbi-encode]
            [--random-encode] [--seed N] [--decode-backend device|numpy] [--decode-nodes N]
 
@@ -144,6 +145,7 @@ def buildParser() -> argparse.ArgumentParser:
     ap.add_argument("--recognize-chars", help="compose a recogniser of this sequence behind the machine(s)")
     ap.add_argument("--generate-json", help="compose a generator of the sequence in this JSON file ({name, sequence}) in front of the machine(s)")
     ap.add_argument("--recognize-csv", help="score the machine(s) against this CSV profile (rightmost; with -L, -V or -C), or decode it (--prefix-decode, --viterbi-decode)")
+    ap.add_argument("--profile-band", type=int, metavar="N", help="with --recognize-csv beside an input sequence: sweep each pair under a band of half-width N around the diagonal (seqpair.Envelope.band)")
     ap.add_argument("--recognize-merge-csv", help="the same against a CTC profile: a symbol repeated in consecutive rows is one symbol, and only a blank separates two equal symbols (not with --prefix-decode)")
     ap.add_argument("-P", "--params", action="append", default=[])
     ap.add_argument("-F", "--functions", action="append", default=[])
@@ -411,6 +413,8 @@ def runProfile(args, out) -> int:
         if not machine.inputAlphabet():
             raise MachineError("--recognize-csv takes no other sequence data: the machine has no input alphabet to read an input sequence")
         return _runProfilePairs(args, out, machine)
+    if args.profile_band is not None:
+        raise MachineError(_BAND_ONLY)
     if machine.inputAlphabet():
         raise MachineError("--recognize-csv needs a machine with an empty input alphabet (compose a generator in front); input alphabet: %s"
                            % ",".join(machine.inputAlphabet()))
@@ -444,25 +448,40 @@ def runProfile(args, out) -> int:
 
 
 def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device", params=None, merge: bool = False,
-                      loglike: bool = True, viterbi: bool = False, counts: bool = False):
+                      loglike: bool = True, viterbi: bool = False, counts: bool = False, band: Optional[int] = None):
     """Every input sequence (a list of symbols) as one pair with ``profile`` (a profile.Profile), all pairs in one batch, on a
     machine with an input alphabet (docs/profile_tapes.md, "Pairs" and "Pairs against a merged profile").  ``merge``: the profile
     is read CTC-merged, as --recognize-merge-csv reads it.  ``backend``: "device" (capi.DeviceProfilePairs) or "numpy"
     (profile.PairProfileDP / PairMergedProfileDP).  Returns (scores, paramCounts): scores["loglike"] and scores["viterbi"] hold one
     float per input, or None where not asked for -- a sequence that cannot be tokenised scores -inf and adds nothing to the counts,
-    as the --loglike loop (dp.loglikeBatch); paramCounts is the posterior count of every parameter summed over the pairs, or None."""
+    as the --loglike loop (dp.loglikeBatch); paramCounts is the posterior count of every parameter summed over the pairs, or None.
+    ``band``: every tokenisable input is swept under seqpair.Envelope.band(len(x), len(profile), band) (docs/profile_tapes.md,
+    "Pairs under an envelope"); plain profiles only."""
     import numpy as np
     from . import dp
     from .profile import PairMergedProfileDP, PairProfileDP
+    from .seqpair import Envelope
     ev = EvaluatedMachine.fromMachine(machine, params)
     if merge and not ev.nOutTok:
         raise MachineError("--recognize-merge-csv needs a machine with an output alphabet")
+    if band is not None and merge:
+        raise MachineError("envelopes take plain profiles")
     ok = [ev.inputTokenizer.canTokenize(seq) for seq in inputs]
     xs = [np.asarray(ev.inputTokenizer.tokenize(seq), np.int64).reshape(-1) for seq, k in zip(inputs, ok) if k]
     P, colTok = _mergedRows(profile, ev) if merge else (profile.logRows(ev), None)
     acc = dp.MachineCounts(ev)
     fwd = vit = None
-    if backend == "numpy":
+    envs = None if band is None else [Envelope.band(len(x), len(P), int(band)) for x in xs]
+    if backend == "numpy" and envs is not None:
+        pdp = PairProfileDP(ev)
+        fwd = [pdp.forward(x, P, env=e)[0] for x, e in zip(xs, envs)] if loglike else None
+        if counts:
+            for x, e in zip(xs, envs):
+                c, ll = pdp.counts(x, P, env=e)
+                acc._flat += c
+                acc.loglike += ll
+        vit = [pdp.forward(x, P, "max", env=e)[0] for x, e in zip(xs, envs)] if viterbi else None
+    elif backend == "numpy":
         pdp = PairMergedProfileDP(ev, colTok) if merge else PairProfileDP(ev)
         fwd = [pdp.forward(x, P)[0] for x in xs] if loglike else None
         if counts:
@@ -476,6 +495,8 @@ def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device"
         dm = capi.DeviceMachine(ev)
         pairs = capi.DeviceProfilePairs(dm, xs, [P] * len(xs), colTok) if merge else capi.DeviceProfilePairs(dm, xs, [P] * len(xs))
         try:
+            if envs is not None:
+                pairs.set_envelopes(envs)
             fwd = pairs.forward(capi.MB_ROLLING) if loglike else None
             if counts:
                 _, s, _ = pairs.counts(acc._flat)
@@ -509,7 +530,8 @@ def _runProfilePairs(args, out, machine: Machine) -> int:
     if args.input_json:
         j = json.load(open(args.input_json)); inSeqs.append((j.get("name", ""), list(j["sequence"])))
     sc, pc = scoreProfilePairs(machine, [seq for _, seq in inSeqs], profile, backend="numpy" if args.decode_backend == "numpy" else "device",
-                               params=params, loglike=bool(args.loglike), viterbi=bool(args.viterbi), counts=bool(args.counts))
+                               params=params, loglike=bool(args.loglike), viterbi=bool(args.viterbi), counts=bool(args.counts),
+                               band=args.profile_band)
 
     def scores(v):
         return "[" + ",".join('["%s","",%s]' % (escaped(n), fmt(x)) for (n, _), x in zip(inSeqs, v)) + "]\n"
@@ -635,9 +657,18 @@ def runCoding(args, machine: Machine, params, data: List[SeqPair], emit) -> None
         emit("[" + ",\n ".join(seqPairJson(SeqPair(d, sp.output, "input", sp.outputName)) for sp, d in zip(data, dec)) + "]\n")
 
 
+_BAND_ONLY = "--profile-band goes with --recognize-csv beside an input sequence (--input-chars, --input-fasta, --input-json) and -L, -V or -C, nowhere else"
+
+
 def run(argv: Optional[List[str]] = None, out=None) -> int:
     out = out or sys.stdout
     args = buildParser().parse_args(argv)
+    if args.profile_band is not None:
+        decode = args.prefix_decode or args.viterbi_decode or args.prefix_encode or args.viterbi_encode or args.random_encode
+        if args.recognize_csv is None or args.recognize_merge_csv is not None or decode:
+            raise MachineError(_BAND_ONLY)
+        if args.profile_band < 0:
+            raise MachineError("--profile-band takes a half-width of 0 or more")
     if args.recognize_csv is not None or args.recognize_merge_csv is not None:
         return runProfile(args, out)
     machine = loadMachine(args)

@@ -33,6 +33,7 @@ EXPORTS = [
     "mb_profile_pairs_create", "mb_profile_pairs_destroy", "mb_profile_pairs_forward", "mb_profile_pair_path_bound",
     "mb_profile_pairs_viterbi", "mb_profile_pairs_counts", "mb_profile_pair_fill",
     "mb_profile_pairs_create_merged", "mb_profile_pair_fill_merged",
+    "mb_profile_pairs_set_envelopes", "mb_profile_pair_fill_env", "mb_profile_pairs_cells",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
     "mb_prefix_node_cells", "mb_prefix_create_profiles", "mb_prefix_create_merged",
 ]
@@ -130,6 +131,9 @@ def load():
     L.mb_profile_pairs_create_merged.restype = vp
     L.mb_profile_pairs_create_merged.argtypes = [vp, C.c_int64, i32p, i64p, dp, i64p, C.c_int32, i32p]
     L.mb_profile_pair_fill_merged.argtypes = [vp, C.c_int, i32p, C.c_int64, dp, C.c_int64, C.c_int32, i32p, dp]
+    L.mb_profile_pairs_set_envelopes.argtypes = [vp, i64p, i32p, i32p]
+    L.mb_profile_pair_fill_env.argtypes = [vp, C.c_int, i32p, C.c_int64, dp, C.c_int64, i32p, i32p, dp]
+    L.mb_profile_pairs_cells.argtypes = [vp]; L.mb_profile_pairs_cells.restype = C.c_int64
     L.mb_prefix_create.restype = vp
     L.mb_prefix_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, C.c_int64]
     L.mb_prefix_create_profiles.restype = vp
@@ -692,6 +696,32 @@ class DeviceProfilePairs:
         L = load()
         return int(sum(L.mb_profile_pair_path_bound(self.dm.h, int(i), int(r)) for i, r in zip(np.diff(self.inOff), np.diff(self.rowOff))))
 
+    def set_envelopes(self, envs):
+        """envs: per pair None (full: the pair keeps the sweeps over the whole rectangle), a seqpair.Envelope or an (inStart,
+        inEnd) pair of rows + 1 entries each; ``None`` instead of a list clears every envelope (docs/profile_tapes.md, "Pairs
+        under an envelope")."""
+        if envs is None:
+            _check(load().mb_profile_pairs_set_envelopes(self.h, None, None, None))
+            return
+        envs = list(envs)
+        if len(envs) != self.nPairs:
+            raise ValueError("one envelope (or None) per pair, please")
+        off = np.zeros(self.nPairs + 1, np.int64)
+        st, en = [], []
+        for k, e in enumerate(envs):
+            n = 0
+            if e is not None:
+                a, b = _env_rows(e)
+                st.append(a); en.append(b); n = len(a)
+            off[k + 1] = off[k] + n
+        cat = lambda xs: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros(1, np.int32), np.int32)
+        a, b = cat(st), cat(en)
+        _check(load().mb_profile_pairs_set_envelopes(self.h, _p(off, C.c_int64), _p(a, C.c_int32), _p(b, C.c_int32)))
+
+    def cells(self) -> int:
+        """Doubles of the materialised lattices of all pairs under the current envelopes."""
+        return int(load().mb_profile_pairs_cells(self.h))
+
     def forward(self, flags: int = MB_ROLLING) -> np.ndarray:
         ll = np.empty(self.nPairs, np.float64)
         _check(load().mb_profile_pairs_forward(self.h, flags, _p(ll, C.c_double)))
@@ -721,12 +751,29 @@ class DeviceProfilePairs:
         return counts, s.value, ll
 
 
-def profile_pair_fill(dm: DeviceMachine, mode: int, x, logP) -> np.ndarray:
-    """One pair's lattice [len(x) + 1, rows + 1, 2, nStates] (layer 0 = arrived at (i, row), 1 = after the output-less moves)."""
+def _env_rows(env):
+    """(inStart, inEnd) as int32 arrays from a seqpair.Envelope or a pair of sequences."""
+    a, b = (env.inStart, env.inEnd) if hasattr(env, "inStart") else env
+    a = np.ascontiguousarray(np.asarray(a).reshape(-1), np.int32); b = np.ascontiguousarray(np.asarray(b).reshape(-1), np.int32)
+    if len(a) != len(b):
+        raise ValueError("inStart and inEnd of an envelope have one entry per row each")
+    return a, b
+
+
+def profile_pair_fill(dm: DeviceMachine, mode: int, x, logP, env=None) -> np.ndarray:
+    """One pair's lattice [len(x) + 1, rows + 1, 2, nStates] (layer 0 = arrived at (i, row), 1 = after the output-less moves).
+    ``env``: a seqpair.Envelope or (inStart, inEnd); the cells outside it are -inf in both layers."""
     P = np.ascontiguousarray(np.asarray(logP, np.float64).reshape(-1, dm.em.nOutTok + 1))
     xs = np.ascontiguousarray(np.asarray(x, np.int64).reshape(-1), np.int32)
     cells = np.empty((len(xs) + 1, len(P) + 1, 2, dm.nStates), np.float64)
-    _check(load().mb_profile_pair_fill(dm.h, mode, _p(xs, C.c_int32), len(xs), _p(P, C.c_double), len(P), _p(cells, C.c_double)))
+    if env is None:
+        _check(load().mb_profile_pair_fill(dm.h, mode, _p(xs, C.c_int32), len(xs), _p(P, C.c_double), len(P), _p(cells, C.c_double)))
+        return cells
+    a, b = _env_rows(env)
+    if len(a) != len(P) + 1:
+        raise MbError("Envelope/sequence mismatch")
+    _check(load().mb_profile_pair_fill_env(dm.h, mode, _p(xs, C.c_int32), len(xs), _p(P, C.c_double), len(P), _p(a, C.c_int32),
+                                           _p(b, C.c_int32), _p(cells, C.c_double)))
     return cells
 
 

@@ -19,6 +19,7 @@
 #include "mb_profile.h"
 #include "mb_profile_merge.h"
 #include "mb_profile_pair.h"
+#include "mb_profile_pair_env.h"
 #include "mb_profile_pair_merge.h"
 #include "mb_small.h"
 #include "mb_usage.h"
@@ -2486,15 +2487,23 @@ static bool pair_profile_chunks(const mb_profile_pairs *p, const std::function<d
 
 static long long pp_in(const mb_profile_pairs *p, long long k) { return p->inOff[k + 1] - p->inOff[k]; }
 static long long pp_rows(const mb_profile_pairs *p, long long k) { return p->rowOff[k + 1] - p->rowOff[k]; }
-static double pp_cell_bytes(const mb_profile_pairs *p, long long k) { return 8.0 * (double)profile_pair_cells(p->m->S, pp_in(p, k), pp_rows(p, k)) * (p->nCols + 1); }
+static bool pp_env(const mb_profile_pairs *p, long long k) { return p->hasEnv && p->envBase[(size_t)k] >= 0; }
+// doubles of pair k's materialised lattice: the rectangle, or the compact lattice of its envelope
+static long long pp_cells(const mb_profile_pairs *p, long long k) {
+  if (pp_env(p, k)) return p->envCells[(size_t)k] * 2 * (long long)p->m->S;
+  return profile_pair_cells(p->m->S, pp_in(p, k), pp_rows(p, k)) * (p->nCols + 1);
+}
+static double pp_cell_bytes(const mb_profile_pairs *p, long long k) { return 8.0 * (double)pp_cells(p, k); }
 // The ring of pair k's sweep and its dynamic LDS (0: a slice of the global scratch buffer).  Plain profiles: the rolling sweep alone
 // has one.  Merged: the materialised sweeps keep their exclusion vectors in one too (mb_profile_pair_merge.h).
 static long long pp_ring(const mb_profile_pairs *p, long long k, bool rolling) {
   if (p->nCols) return profile_pair_merge_ring(p->m->S, p->nCols, pp_in(p, k), pp_rows(p, k), !rolling);
+  if (pp_env(p, k)) return rolling ? profile_pair_env_ring(p->m->S, p->envM[(size_t)k]) : 0;
   return rolling ? profile_pair_ring(p->m->S, pp_in(p, k), pp_rows(p, k)) : 0;
 }
 static size_t pp_ring_lds(const mb_profile_pairs *p, long long k, bool rolling) {
   if (p->nCols) return profile_pair_merge_lds_bytes(p->m->S, p->nCols, pp_in(p, k), pp_rows(p, k), !rolling);
+  if (pp_env(p, k)) return rolling ? profile_pair_env_lds_bytes(p->m->S, p->envM[(size_t)k]) : 0;
   return rolling ? profile_pair_lds_bytes(p->m->S, pp_in(p, k), pp_rows(p, k)) : 0;
 }
 // bytes of global scratch the sweep of pair k needs (0: its ring is in LDS, or it has none)
@@ -2503,54 +2512,107 @@ static double pp_ring_bytes(const mb_profile_pairs *p, long long k, bool rolling
 }
 static MergeMap pp_map(const mb_profile_pairs *p) { return MergeMap{p->nCols, p->d_colTok}; }
 
-struct PairProfPlan { PairProfDesc *d = nullptr; long long cells = 0, paths = 0, ring = 0, maxItems = 0; size_t lds = 0; };
+// Pairs with an envelope go to the kernels of mb_profile_pair_env.hip in a launch of their own: a chunk's pairs without one come
+// first in its per-pair outputs (log-likelihoods, path lengths), then the pairs with one; slot[k - p0] is where pair k landed.
+struct PairProfPlan {
+  PairProfDesc *d = nullptr; PairEnvDesc *e = nullptr;
+  long long cells = 0, paths = 0, ring = 0, maxItems = 0, maxItemsEnv = 0, nPlain = 0, nEnv = 0;
+  size_t lds = 0, ldsEnv = 0;
+  std::vector<long long> slot;
+};
+static void pp_plan_free(PairProfPlan &pl) { sm_free(pl.d); sm_free(pl.e); pl.d = nullptr; pl.e = nullptr; }
 
 // descriptors of pairs [p0, p1): lattices, traceback slots and scratch rings packed from 0
 static int pair_profile_descs(const mb_profile_pairs *p, long long p0, long long p1, bool rolling, PairProfPlan &pl) {
-  std::vector<PairProfDesc> h((size_t)(p1 - p0));
+  std::vector<PairProfDesc> h;
+  std::vector<PairEnvDesc> he;
+  std::vector<long long> envPairs;
   const int S = p->m->S;
+  pl.slot.assign((size_t)(p1 - p0), 0);
   for (long long k = p0; k < p1; ++k) {
-    PairProfDesc &d = h[(size_t)(k - p0)];
     const long long I = pp_in(p, k), L = pp_rows(p, k);
-    d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)I; d.nRows = (int)L;
-    d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = -1;
-    pl.cells += profile_pair_cells(S, I, L) * (p->nCols + 1);
-    pl.paths += profile_pair_path_bound(p->m->nLevF, I, L);
-    pl.maxItems = std::max(pl.maxItems, (std::min(I, L) + 1) * S * (p->nCols + 1));
+    long long ringBase = -1;
     if (pp_ring(p, k, rolling)) {
       const size_t lds = pp_ring_lds(p, k, rolling);
-      if (lds) pl.lds = std::max(pl.lds, lds);
-      else { d.ringBase = pl.ring; pl.ring += pp_ring(p, k, rolling); }
+      if (lds) { if (pp_env(p, k)) pl.ldsEnv = std::max(pl.ldsEnv, lds); else pl.lds = std::max(pl.lds, lds); }
+      else { ringBase = pl.ring; pl.ring += pp_ring(p, k, rolling); }
     }
+    if (pp_env(p, k)) {
+      PairEnvDesc d;
+      d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)I; d.nRows = (int)L;
+      d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = ringBase;
+      d.envBase = p->envBase[(size_t)k]; d.diagBase = p->diagBase[(size_t)k]; d.nCells = p->envCells[(size_t)k]; d.M = p->envM[(size_t)k];
+      pl.maxItemsEnv = std::max(pl.maxItemsEnv, (long long)d.M * S);
+      he.push_back(d); envPairs.push_back(k);
+    } else {
+      PairProfDesc d;
+      d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)I; d.nRows = (int)L;
+      d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = ringBase;
+      pl.maxItems = std::max(pl.maxItems, (std::min(I, L) + 1) * S * (p->nCols + 1));
+      pl.slot[(size_t)(k - p0)] = (long long)h.size();
+      h.push_back(d);
+    }
+    pl.cells += pp_cells(p, k);
+    pl.paths += profile_pair_path_bound(p->m->nLevF, I, L);
   }
+  pl.nPlain = (long long)h.size(); pl.nEnv = (long long)he.size();
+  for (size_t j = 0; j < envPairs.size(); ++j) pl.slot[(size_t)(envPairs[j] - p0)] = pl.nPlain + (long long)j;
   MB_HIP(sm_alloc((void **)&pl.d, std::max<size_t>(h.size(), 1) * sizeof(PairProfDesc)));
-  if (!h.empty() && (!hip_ok(hipMemcpyAsync(pl.d, h.data(), h.size() * sizeof(PairProfDesc), hipMemcpyHostToDevice, g_stream), "H2D pair descriptors") ||
-                     !hip_ok(hipStreamSynchronize(g_stream), "H2D pair descriptors"))) { sm_free(pl.d); pl.d = nullptr; return 1; }
+  if (!hip_ok(sm_alloc((void **)&pl.e, std::max<size_t>(he.size(), 1) * sizeof(PairEnvDesc)), "hipMalloc(pair descriptors)")) { pp_plan_free(pl); return 1; }
+  if ((!h.empty() && !hip_ok(hipMemcpyAsync(pl.d, h.data(), h.size() * sizeof(PairProfDesc), hipMemcpyHostToDevice, g_stream), "H2D pair descriptors")) ||
+      (!he.empty() && !hip_ok(hipMemcpyAsync(pl.e, he.data(), he.size() * sizeof(PairEnvDesc), hipMemcpyHostToDevice, g_stream), "H2D pair descriptors")) ||
+      !hip_ok(hipStreamSynchronize(g_stream), "H2D pair descriptors")) { pp_plan_free(pl); return 1; }
+  return 0;
+}
+static PairEnvTables pp_tables(const mb_profile_pairs *p) { return PairEnvTables{p->d_envStart, p->d_envEnd, p->d_envOff, p->d_diagLo, p->d_diagCnt}; }
+// per-pair device results (each chunk in the order of its plan's slots; at[k] = the entry of pair k) into dst[0..n)
+struct PairWhere {
+  std::vector<long long> at; bool permuted = false;
+  void add(long long p0, const PairProfPlan &pl) {
+    for (long long s : pl.slot) at.push_back(p0 + s);
+    permuted = permuted || pl.nEnv;
+  }
+};
+static int pp_fetch(double *dst, const double *d_src, long long n, const PairWhere &w, const char *what) {
+  if (n <= 0) return 0;
+  if (!w.permuted) return hip_ok(hipMemcpy(dst, d_src, (size_t)n * sizeof(double), hipMemcpyDeviceToHost), what) ? 0 : 1;
+  std::vector<double> tmp((size_t)n);
+  if (!hip_ok(hipMemcpy(tmp.data(), d_src, tmp.size() * sizeof(double), hipMemcpyDeviceToHost), what)) return 1;
+  for (long long k = 0; k < n; ++k) dst[k] = tmp[(size_t)w.at[(size_t)k]];
   return 0;
 }
 
 // The one place where the plain and the merged kernels part: the launches of a chunk and the names they report.
 static int pp_launch_fwd(const mb_profile_pairs *p, int mode, bool mat, const PairProfPlan &pl, long long n, double *pool, double *scratch, double *ll) {
   if (p->nCols) return launch_profile_pair_merge_fwd(p->m, pp_map(p), mode, mat, pl.d, (int)n, pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, ll, g_stream);
-  return launch_profile_pair_fwd(p->m, mode, mat, pl.d, (int)n, mat ? 0 : pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, mat ? nullptr : scratch, ll, g_stream);
+  if (launch_profile_pair_fwd(p->m, mode, mat, pl.d, (int)pl.nPlain, mat ? 0 : pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, mat ? nullptr : scratch, ll, g_stream)) return 1;
+  return launch_profile_pair_env_fwd(p->m, mode, mat, pl.e, pp_tables(p), (int)pl.nEnv, mat ? 0 : pl.ldsEnv, pl.maxItemsEnv, p->d_in, p->d_logP, pool,
+                                     mat ? nullptr : scratch, ll + pl.nPlain, g_stream);
 }
 static int pp_launch_bwd(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, double *pool, double *scratch, double *ll) {
   if (p->nCols) return launch_profile_pair_merge_bwd(p->m, pp_map(p), pl.d, (int)n, pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, ll, g_stream);
-  return launch_profile_pair_bwd(p->m, pl.d, (int)n, pl.maxItems, p->d_in, p->d_logP, pool, ll, g_stream);
+  if (launch_profile_pair_bwd(p->m, pl.d, (int)pl.nPlain, pl.maxItems, p->d_in, p->d_logP, pool, ll, g_stream)) return 1;
+  return launch_profile_pair_env_bwd(p->m, pl.e, pp_tables(p), (int)pl.nEnv, pl.maxItemsEnv, p->d_in, p->d_logP, pool, ll + pl.nPlain, g_stream);
 }
 static int pp_launch_traceback(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, const double *pool, uint32_t *e, int32_t *r, long long *len) {
   if (p->nCols) return launch_profile_pair_merge_traceback(p->m, pp_map(p), pl.d, (int)n, p->d_in, p->d_logP, pool, e, r, len, g_stream);
-  return launch_profile_pair_traceback(p->m, pl.d, (int)n, p->d_in, p->d_logP, pool, e, r, len, g_stream);
+  if (launch_profile_pair_traceback(p->m, pl.d, (int)pl.nPlain, p->d_in, p->d_logP, pool, e, r, len, g_stream)) return 1;
+  return launch_profile_pair_env_traceback(p->m, pl.e, pp_tables(p), (int)pl.nEnv, p->d_in, p->d_logP, pool, e, r, len + pl.nPlain, g_stream);
 }
 static int pp_launch_counts(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, int groups, const double *fwd, const double *bwd, double *cc) {
   if (p->nCols) return launch_profile_pair_merge_counts(p->m, pp_map(p), pl.d, (int)n, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
-  return launch_profile_pair_counts(p->m, pl.d, (int)n, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
+  if (launch_profile_pair_counts(p->m, pl.d, (int)pl.nPlain, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream)) return 1;
+  return launch_profile_pair_env_counts(p->m, pl.e, pp_tables(p), (int)pl.nEnv, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
 }
 static const char *pp_fwd_name(const mb_profile_pairs *p, int mode, bool mat) {
   static const char *const names[2][2][2] = {{{"k_profile_pair_fwd<sum,rolling>", "k_profile_pair_fwd<sum,mat>"}, {"k_profile_pair_fwd<max,rolling>", "k_profile_pair_fwd<max,mat>"}},
                                              {{"k_profile_pair_merge_fwd<sum,rolling>", "k_profile_pair_merge_fwd<sum,mat>"}, {"k_profile_pair_merge_fwd<max,rolling>", "k_profile_pair_merge_fwd<max,mat>"}}};
+  static const char *const envNames[2][2] = {{"k_profile_pair_env_fwd<sum,rolling>", "k_profile_pair_env_fwd<sum,mat>"}, {"k_profile_pair_env_fwd<max,rolling>", "k_profile_pair_env_fwd<max,mat>"}};
+  if (p->hasEnv) return envNames[mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];      // (a batch that mixes both kinds reports the envelope kernel)
   return names[p->nCols ? 1 : 0][mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
 }
+// launches of a chunk: one per kind of pair it holds
+static int pp_chunk_launches(const PairProfPlan &pl) { return pl.nEnv && pl.nPlain ? 2 : 1; }
 
 // Forward (MB_FORWARD) or Viterbi scores without paths (MB_VITERBI); mat: through the materialised lattice
 static int pair_profile_scores(mb_profile_pairs *p, int mode, bool mat, double *loglike) {
@@ -2560,9 +2622,11 @@ static int pair_profile_scores(mb_profile_pairs *p, int mode, bool mat, double *
   MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
   int rc = 0;
   Timer tm;
+  PairWhere where;
   for (const Chunk &c : chunks) {
     PairProfPlan pl;
     if ((rc = pair_profile_descs(p, c.p0, c.p1, !mat, pl))) break;
+    where.add(c.p0, pl);
     double *pool = nullptr, *scratch = nullptr;
     if (mat) { pool = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double)); if (!pool) rc = 1; }
     if (!rc && pl.ring) { scratch = (double *)ws_get(1, (size_t)pl.ring * sizeof(double)); if (!scratch) rc = 1; }
@@ -2570,16 +2634,81 @@ static int pair_profile_scores(mb_profile_pairs *p, int mode, bool mat, double *
       tm.start();
       rc = pp_launch_fwd(p, mode, mat, pl, c.p1 - c.p0, pool, scratch, d_ll + c.p0);
       g_last_ms += tm.stop();
-      ++g_last_launches;
+      g_last_launches += pp_chunk_launches(pl);
     }
     if (rc) quiesce_streams();
-    sm_free(pl.d);
+    pp_plan_free(pl);
     if (rc) break;
   }
-  if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  if (!rc && pp_fetch(loglike, d_ll, p->n, where, "D2H loglike")) rc = 1;
   sm_free(d_ll);
   g_last_kernel = pp_fwd_name(p, mode, mat);
   return rc;
+}
+
+// ---- envelopes of the pairs (mb_profile_pair_env.hip, docs/profile_tapes.md "Pairs under an envelope") ----
+static void pp_env_free(mb_profile_pairs *p) {
+  if (p->d_envStart) (void)hipFree(p->d_envStart);
+  if (p->d_envEnd) (void)hipFree(p->d_envEnd);
+  if (p->d_envOff) (void)hipFree(p->d_envOff);
+  if (p->d_diagLo) (void)hipFree(p->d_diagLo);
+  if (p->d_diagCnt) (void)hipFree(p->d_diagCnt);
+  p->d_envStart = p->d_envEnd = p->d_diagLo = p->d_diagCnt = nullptr; p->d_envOff = nullptr;
+  p->hasEnv = false;
+  p->envBase.clear(); p->diagBase.clear(); p->envCells.clear(); p->envM.clear(); p->h_envStart.clear(); p->h_envEnd.clear();
+}
+
+// Checks as mb_batch_set_envelopes (fits, connected) and, new here, that neither bound decreases from one row to the next: the
+// sweeps rest on the envelope cells of an anti-diagonal being consecutive.  A rejected call leaves the pairs without envelopes.
+static int profile_pairs_set_envelopes(mb_profile_pairs *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
+  pp_env_free(p);
+  if (!envOff) return 0;
+  const long long total = envOff[p->n] - envOff[0];
+  if (total && p->nCols) { set_error("envelopes take plain profiles"); return 1; }
+  if (total && (!inStart || !inEnd)) { set_error("null argument"); return 1; }
+  std::vector<long long> envBase((size_t)p->n, -1), diagBase((size_t)p->n, -1), envCells((size_t)p->n, 0), hOff;
+  std::vector<int> envM((size_t)p->n, 0), hSt, hEn, hLo, hCnt;
+  for (long long k = 0; k < p->n; ++k) {
+    const long long rows = envOff[k + 1] - envOff[k], I = pp_in(p, k), L = pp_rows(p, k);
+    if (rows == 0) continue;   // full: the pair keeps the sweeps of mb_profile_pair.hip
+    if (rows != L + 1) { set_error("Envelope/sequence mismatch"); return 1; }
+    const int32_t *st = inStart + envOff[k], *en = inEnd + envOff[k];
+    for (long long y = 0; y < rows; ++y)
+      if (st[y] < 0 || en[y] > I + 1 || st[y] > en[y]) { set_error("Envelope/sequence mismatch"); return 1; }
+    bool conn = env_overlapping(st[0], en[0], 0, 1);
+    for (long long y = 1; conn && y < rows; ++y) conn = env_overlapping(st[y - 1], (long long)en[y - 1] + 1, st[y], en[y]);
+    conn = conn && env_overlapping(st[rows - 1], en[rows - 1], I, I + 1);
+    if (!conn) { set_error("Envelope is not connected"); return 1; }
+    for (long long y = 1; y < rows; ++y)
+      if (st[y] < st[y - 1] || en[y] < en[y - 1]) { set_error("Envelope is not monotone"); return 1; }
+    envBase[(size_t)k] = (long long)hSt.size(); diagBase[(size_t)k] = (long long)hLo.size();
+    const size_t d0 = hLo.size();
+    hLo.resize(d0 + (size_t)(I + L + 1), 0); hCnt.resize(d0 + (size_t)(I + L + 1), 0);
+    long long cells = 0;
+    for (long long y = 0; y < rows; ++y) {
+      hSt.push_back(st[y]); hEn.push_back(en[y]); hOff.push_back(cells);
+      cells += en[y] - st[y];
+      // row y puts one cell on each of the diagonals st[y] + y .. en[y] - 1 + y; the rows go upwards, so on a diagonal every
+      // later row holds a smaller i than the rows before it: the last one written is the diagonal's first i
+      for (long long i = st[y]; i < en[y]; ++i) { hLo[d0 + (size_t)(i + y)] = (int)i; ++hCnt[d0 + (size_t)(i + y)]; }
+    }
+    envCells[(size_t)k] = cells;
+    int M = 1;
+    for (size_t d = d0; d < hLo.size(); ++d) M = std::max(M, hCnt[d]);
+    envM[(size_t)k] = M;
+  }
+  if (hSt.empty()) return 0;
+  if (ensure_init()) return 1;
+  auto up = [&](void **dst, const void *src, size_t bytes) {
+    return hip_ok(hipMalloc(dst, std::max<size_t>(bytes, 8)), "hipMalloc(pair envelopes)") && h2d_large(*dst, src, bytes) == 0;
+  };
+  if (!up((void **)&p->d_envStart, hSt.data(), hSt.size() * sizeof(int)) || !up((void **)&p->d_envEnd, hEn.data(), hEn.size() * sizeof(int)) ||
+      !up((void **)&p->d_envOff, hOff.data(), hOff.size() * sizeof(long long)) || !up((void **)&p->d_diagLo, hLo.data(), hLo.size() * sizeof(int)) ||
+      !up((void **)&p->d_diagCnt, hCnt.data(), hCnt.size() * sizeof(int)) || !hip_ok(hipStreamSynchronize(g_stream), "H2D pair envelopes")) { pp_env_free(p); return 1; }
+  p->envBase.swap(envBase); p->diagBase.swap(diagBase); p->envCells.swap(envCells); p->envM.swap(envM);
+  p->h_envStart.swap(hSt); p->h_envEnd.swap(hEn);
+  p->hasEnv = true;
+  return 0;
 }
 
 // nCols > 0: CTC-merged profiles, rows of nCols + 1 doubles and the column map colTok (checked by the caller)
@@ -2636,7 +2765,21 @@ void mb_profile_pairs_destroy(mb_profile_pairs *p) {
   if (p->d_logP) (void)hipFree(p->d_logP);
   if (p->d_in) (void)hipFree(p->d_in);
   if (p->d_colTok) (void)hipFree(p->d_colTok);
+  pp_env_free(p);
   delete p;
+}
+
+int mb_profile_pairs_set_envelopes(mb_profile_pairs *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
+  ApiGuard guard;
+  if (!p) { set_error("null argument"); return 1; }
+  return profile_pairs_set_envelopes(p, envOff, inStart, inEnd);
+}
+
+int64_t mb_profile_pairs_cells(const mb_profile_pairs *p) {
+  if (!p) return 0;
+  long long c = 0;
+  for (long long k = 0; k < p->n; ++k) c += pp_cells(p, k);
+  return c;
 }
 
 int mb_profile_pairs_forward(mb_profile_pairs *p, int flags, double *loglike) {
@@ -2675,9 +2818,11 @@ int mb_profile_pairs_viterbi(mb_profile_pairs *p, double *loglike, int64_t *path
   std::vector<long long> len;
   std::vector<uint32_t> he;
   std::vector<int32_t> hr;
+  PairWhere where;
   for (const Chunk &c : chunks) {
     PairProfPlan pl;
     if ((rc = pair_profile_descs(p, c.p0, c.p1, false, pl))) break;
+    where.add(c.p0, pl);
     const long long np = c.p1 - c.p0, paths = pl.paths;
     double *pool = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
     uint32_t *d_e = (uint32_t *)ws_get(3, (size_t)std::max<long long>(paths, 1) * sizeof(uint32_t));
@@ -2689,14 +2834,14 @@ int mb_profile_pairs_viterbi(mb_profile_pairs *p, double *loglike, int64_t *path
       rc = pp_launch_fwd(p, MB_VITERBI, true, pl, np, pool, scratch, d_ll + c.p0);
       if (!rc) rc = pp_launch_traceback(p, pl, np, pool, d_e, d_r, d_len + c.p0);
       g_last_ms += tm.stop();
-      ++g_last_launches;
+      g_last_launches += pp_chunk_launches(pl);
     }
     len.resize((size_t)np); he.resize((size_t)std::max<long long>(paths, 1)); hr.resize(he.size());
     if (!rc && !hip_ok(hipMemcpy(len.data(), d_len + c.p0, np * sizeof(long long), hipMemcpyDeviceToHost), "D2H path lengths")) rc = 1;
     if (!rc && paths && (d2h_large(he.data(), d_e, paths * sizeof(uint32_t)) || (pathRow && d2h_large(hr.data(), d_r, paths * sizeof(int32_t))))) rc = 1;
     long long base = 0;
     for (long long k = 0; k < np && !rc; ++k) {
-      long long n = len[(size_t)k];
+      long long n = len[(size_t)pl.slot[(size_t)k]];
       if (n == -1) n = 0;   // no finite path: an empty one, as mb_profiles_viterbi
       else if (n < 0) { set_error(n == -2 ? "pair traceback overflowed its bound" : "pair traceback found no matching candidate"); rc = 1; break; }
       std::memcpy(pathEdges + written, he.data() + base, (size_t)n * sizeof(uint32_t));
@@ -2706,10 +2851,10 @@ int mb_profile_pairs_viterbi(mb_profile_pairs *p, double *loglike, int64_t *path
       base += profile_pair_path_bound(m->nLevF, pp_in(p, c.p0 + k), pp_rows(p, c.p0 + k));
     }
     if (rc) quiesce_streams();
-    sm_free(pl.d);
+    pp_plan_free(pl);
     if (rc) break;
   }
-  if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  if (!rc && pp_fetch(loglike, d_ll, p->n, where, "D2H loglike")) rc = 1;
   sm_free(d_ll); sm_free(d_len);
   g_last_kernel = pp_fwd_name(p, MB_VITERBI, true);
   return rc;
@@ -2731,16 +2876,18 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
   int rc = 0;
   Timer tm;
   std::vector<double> total((size_t)nT, 0.0), hc((size_t)nT);
+  PairWhere where;
   for (const Chunk &c : chunks) {
     PairProfPlan pl;
     if ((rc = pair_profile_descs(p, c.p0, c.p1, false, pl))) break;
+    where.add(c.p0, pl);
     const long long np = c.p1 - c.p0;
     double *fwd = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
     double *bwd = (double *)ws_get(1, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
     double *scratch = pl.ring ? (double *)ws_get(2, (size_t)pl.ring * sizeof(double)) : nullptr;
     if (!fwd || !bwd || (pl.ring && !scratch)) rc = 1;
     long long maxCells = 0;
-    for (long long k = c.p0; k < c.p1; ++k) maxCells = std::max(maxCells, profile_pair_cells(m->S, pp_in(p, k), pp_rows(p, k)) / 2 * (p->nCols + 1));
+    for (long long k = c.p0; k < c.p1; ++k) maxCells = std::max(maxCells, pp_cells(p, k) / 2);
     const int groups = (int)std::min<long long>(256, std::max<long long>(1, (maxCells + 2047) / 2048));
     if (!rc && np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); rc = 1; }
     if (!rc) {
@@ -2750,7 +2897,7 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
       if (!rc && nT) rc = hip_ok(hipMemsetAsync(d_cc, 0, (size_t)nT * sizeof(double), g_stream), "memset(counts)") ? 0 : 1;
       if (!rc) rc = pp_launch_counts(p, pl, np, groups, fwd, bwd, d_cc);
       g_last_ms += tm.stop();
-      ++g_last_launches;
+      g_last_launches += pp_chunk_launches(pl);
     }
     if (!rc && nT && !hip_ok(hipMemcpy(hc.data(), d_cc, nT * sizeof(double), hipMemcpyDeviceToHost), "D2H counts")) rc = 1;
     if (!rc && g_deterministic)
@@ -2760,13 +2907,13 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
       }
     if (!rc) for (long long e = 0; e < nT; ++e) total[(size_t)e] += hc[(size_t)e];
     if (rc) quiesce_streams();
-    sm_free(pl.d);
+    pp_plan_free(pl);
     if (rc) break;
   }
   std::vector<double> hll((size_t)p->n);
-  if (!rc && p->n && !hip_ok(hipMemcpy(hll.data(), d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  if (!rc && pp_fetch(hll.data(), d_ll, p->n, where, "D2H loglike")) rc = 1;
   sm_free(d_ll); sm_free(d_bll); sm_free(d_cc);
-  g_last_kernel = p->nCols ? "k_profile_pair_merge_counts" : "k_profile_pair_counts";
+  g_last_kernel = p->nCols ? "k_profile_pair_merge_counts" : (p->hasEnv ? "k_profile_pair_env_counts" : "k_profile_pair_counts");
   if (rc) return rc;
   for (long long e = 0; e < nT; ++e) counts[e] += total[(size_t)e];
   double s = 0.0;
@@ -2776,7 +2923,7 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
 }
 
 static int profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, int32_t nCols,
-                             const int32_t *colTok, double *cellsOut) {
+                             const int32_t *colTok, const int32_t *envStart, const int32_t *envEnd, double *cellsOut) {
   if (!m || !cellsOut || nRows < 0 || nIn < 0 || (nRows && !logP) || (nIn && !inTok)) { set_error("null argument"); return 1; }
   if (mode != MB_FORWARD && mode != MB_VITERBI && mode != MB_BACKWARD) { set_error("unknown fill mode"); return 1; }
   if (ensure_init()) return 1;
@@ -2784,6 +2931,11 @@ static int profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int6
   const int64_t rOff[2] = {0, nRows}, iOff[2] = {0, nIn};
   mb_profile_pairs *p = profile_pairs_create(m, 1, inTok, iOff, logP, rOff, nCols, colTok);
   if (!p) return 1;
+  const bool env = envStart && envEnd;
+  if (env) {
+    const int64_t eOff[2] = {0, nRows + 1};
+    if (profile_pairs_set_envelopes(p, eOff, envStart, envEnd)) { mb_profile_pairs_destroy(p); return 1; }
+  }
   std::vector<Chunk> chunks;
   if (!pair_profile_chunks(p, [&](long long k) { return pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false); }, chunks)) { mb_profile_pairs_destroy(p); return 1; }
   PairProfPlan pl;
@@ -2801,24 +2953,41 @@ static int profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int6
     g_last_ms += tm.stop();
     g_last_launches = 1;
   }
-  if (!rc) rc = d2h_large(cellsOut, pool, (size_t)pl.cells * sizeof(double));
+  if (!rc && !env) rc = d2h_large(cellsOut, pool, (size_t)pl.cells * sizeof(double));
+  if (!rc && env) {      // the compact lattice into the full rectangle, -inf outside the envelope
+    std::vector<double> compact((size_t)pl.cells);
+    rc = d2h_large(compact.data(), pool, compact.size() * sizeof(double));
+    const size_t cellD = 2 * (size_t)m->S;
+    if (!rc) std::fill(cellsOut, cellsOut + (size_t)(nIn + 1) * (size_t)(nRows + 1) * cellD, -INFINITY);
+    size_t at = 0;
+    for (int64_t r = 0; !rc && r <= nRows; ++r)
+      for (int64_t i = envStart[r]; i < envEnd[r]; ++i, at += cellD)
+        std::memcpy(cellsOut + ((size_t)i * (size_t)(nRows + 1) + (size_t)r) * cellD, compact.data() + at, cellD * sizeof(double));
+  }
   if (rc) quiesce_streams();
-  sm_free(pl.d); sm_free(d_ll);
-  g_last_kernel = mode == MB_BACKWARD ? (nCols ? "k_profile_pair_merge_bwd" : "k_profile_pair_bwd") : pp_fwd_name(p, mode, true);
+  pp_plan_free(pl); sm_free(d_ll);
+  g_last_kernel = mode == MB_BACKWARD ? (nCols ? "k_profile_pair_merge_bwd" : (env ? "k_profile_pair_env_bwd" : "k_profile_pair_bwd")) : pp_fwd_name(p, mode, true);
   mb_profile_pairs_destroy(p);
   return rc;
 }
 
 int mb_profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, double *cellsOut) {
   ApiGuard guard;
-  return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, 0, nullptr, cellsOut);
+  return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, 0, nullptr, nullptr, nullptr, cellsOut);
+}
+
+int mb_profile_pair_fill_env(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows,
+                             const int32_t *envStart, const int32_t *envEnd, double *cellsOut) {
+  ApiGuard guard;
+  if ((envStart == nullptr) != (envEnd == nullptr)) { set_error("null argument"); return 1; }
+  return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, 0, nullptr, envStart, envEnd, cellsOut);
 }
 
 int mb_profile_pair_fill_merged(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, int32_t nCols,
                                 const int32_t *colTok, double *cellsOut) {
   ApiGuard guard;
   if (!merge_map_ok(m, nCols, colTok)) return 1;
-  return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, nCols, colTok, cellsOut);
+  return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, nCols, colTok, nullptr, nullptr, cellsOut);
 }
 
 // ---- prefix search: node fills on the device, the tree on the host (mb_prefix.hip, docs/decoding.md) --------------------------

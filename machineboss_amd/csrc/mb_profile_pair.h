@@ -52,4 +52,11 @@ struct mb_profile_pairs {
   int *d_in = nullptr;                    // [totalIn]
   int nCols = 0;                          // > 0: CTC-merged profiles (mb_profile_pair_merge.h)
   int *d_colTok = nullptr;                // [nCols] output token of column c at [c - 1]
+  // envelopes (mb_profile_pairs_set_envelopes, mb_profile_pair_env.h): the pairs with envBase >= 0 run the envelope kernels
+  bool hasEnv = false;
+  std::vector<long long> envBase, diagBase, envCells;   // [n]: first envelope row / first diagonal entry (-1: full), envelope cells
+  std::vector<int> envM;                                // [n]: the largest cell count of a diagonal
+  std::vector<int> h_envStart, h_envEnd;                // the rows of the pairs that have an envelope, packed
+  int *d_envStart = nullptr, *d_envEnd = nullptr, *d_diagLo = nullptr, *d_diagCnt = nullptr;
+  long long *d_envOff = nullptr;
 };

@@ -1,0 +1,46 @@
+// mb_profile_pair_env.h -- the two-tape profile sweeps of mb_profile_pair.h under an ENVELOPE (docs/profile_tapes.md, "Pairs under
+// an envelope"): per row r = 0..L the half-open interval [inStart[r], inEnd[r]) of input positions whose cells exist; both layers of
+// every other cell are -inf.  inStart and inEnd never decrease from one row to the next, so the envelope cells of an anti-diagonal
+// are a run of consecutive i.
+//
+// Materialised lattices are COMPACT: cells[((off[r] + i - inStart[r]) * 2 + layer) * S + q], off[r] = the cells of the rows < r.
+#pragma once
+#include "mb_profile_pair.h"
+
+namespace mb {
+
+struct PairEnvDesc {
+  long long inBase, rowBase;   // as PairProfDesc
+  long long cellBase;          // offset (doubles) of this pair's compact lattice in a matrix pool
+  long long pathBase;          // offset of this pair's slot in the traceback buffers
+  long long ringBase;          // rolling sweeps: offset (doubles) of this pair's ring in the global scratch buffer, -1 = LDS
+  long long envBase;           // first of this pair's nRows + 1 entries in envStart / envEnd / envOff
+  long long diagBase;          // first of this pair's nIn + nRows + 1 entries in diagLo / diagCnt
+  long long nCells;            // envelope cells of the pair (off[nRows + 1])
+  int nIn, nRows;
+  int M;                       // the largest cell count of any anti-diagonal of the pair
+};
+
+// device arrays of a batch's envelopes (rows of the pairs that have one, packed)
+struct PairEnvTables {
+  const int *envStart, *envEnd;   // [rows]
+  const long long *envOff;        // [rows] compact index of the first cell of each row, per pair from 0
+  const int *diagLo, *diagCnt;    // [diagonals] first i and cell count of each anti-diagonal
+};
+
+// the rolling ring: three anti-diagonals of both layers, each of M cells; a cell lives at i mod M
+inline long long profile_pair_env_ring(int S, long long M) { return 3 * 2 * M * (long long)S; }
+// dynamic LDS of the ring when it fits (0: a slice of the global scratch buffer)
+size_t profile_pair_env_lds_bytes(int S, long long M);
+
+int launch_profile_pair_env_fwd(const mb_machine *m, int mode, bool mat, const PairEnvDesc *d, PairEnvTables t, int n, size_t lds,
+                                long long maxItems, const int *inTok, const double *logP, double *pool, double *scratch, double *loglike,
+                                hipStream_t st);
+int launch_profile_pair_env_bwd(const mb_machine *m, const PairEnvDesc *d, PairEnvTables t, int n, long long maxItems, const int *inTok,
+                                const double *logP, double *pool, double *loglike, hipStream_t st);
+int launch_profile_pair_env_counts(const mb_machine *m, const PairEnvDesc *d, PairEnvTables t, int n, int groupsPerPair, const int *inTok,
+                                   const double *logP, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
+int launch_profile_pair_env_traceback(const mb_machine *m, const PairEnvDesc *d, PairEnvTables t, int n, const int *inTok,
+                                      const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len, hipStream_t st);
+
+}  // namespace mb

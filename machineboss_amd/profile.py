@@ -26,6 +26,7 @@ import numpy as np
 
 from .evalmachine import EvaluatedMachine
 from .machine import Machine, MachineError, MachineState, MachineTransition
+from .seqpair import Envelope
 
 _STOF = re.compile(r"[ \t\n\v\f\r]*([+-]?(?:inf(?:inity)?|nan|(?:\d+\.?\d*|\.\d+)(?:[eE][+-]?\d+)?))", re.I)
 
@@ -534,7 +535,11 @@ class PairProfileDP(ProfileDP):
     The blank reads N, never W (the waiting-machine order of docs/decoding.md).  Viterbi keeps the FIRST maximum -- N: the blank,
     then match edges in `incoming` order, then output-only edges in `incoming` order; W: "no move" (N), then input-only edges in
     `incoming` order, then silent edges in `incoming` order.  Every method takes (x, P): x the input tokens (1..nInTok), P the
-    [L, nOutTok + 1] log weights of Profile.logRows.  Lattices are [I + 1, L + 1, S]."""
+    [L, nOutTok + 1] log weights of Profile.logRows.  Lattices are [I + 1, L + 1, S].
+
+    ``env`` (forward, backward, counts, viterbi): a seqpair.Envelope or an (inStart, inEnd) pair -- row r holds the input positions
+    inStart[r] <= i < inEnd[r]; both layers of every other cell are -inf (docs/profile_tapes.md, "Pairs under an envelope").  The
+    sweeps visit the envelope cells alone.  Without it not one operation differs."""
 
     def __init__(self, em: EvaluatedMachine):
         super().__init__(em)
@@ -554,14 +559,36 @@ class PairProfileDP(ProfileDP):
             raise MachineError("input token outside 1..nInTok")
         return x, self._check(P)
 
-    def forward(self, x, P, mode: str = "exact") -> Tuple[float, np.ndarray, np.ndarray]:
+    @staticmethod
+    def envelopeRows(env, I: int, L: int):
+        """Per input position i the rows r of the envelope cells (i, r), ascending; None without an envelope.  Raises what
+        mb_profile_pairs_set_envelopes rejects: a mismatch, an envelope that is not connected or not monotone."""
+        if env is None:
+            return None
+        st, en = (env.inStart, env.inEnd) if hasattr(env, "inStart") else env
+        st = [int(v) for v in st]; en = [int(v) for v in en]
+        if len(st) != L + 1 or len(en) != L + 1 or any(a < 0 or b > I + 1 or a > b for a, b in zip(st, en)):
+            raise MachineError("Envelope/sequence mismatch")
+        e = Envelope(); e.inLen, e.outLen, e.inStart, e.inEnd = I, L, st, en
+        if not e.connected():
+            raise MachineError("Envelope is not connected")
+        if not e.monotone():
+            raise MachineError("Envelope is not monotone")
+        rows: List[List[int]] = [[] for _ in range(I + 1)]
+        for r in range(L + 1):
+            for i in range(st[r], en[r]):
+                rows[i].append(r)
+        return rows
+
+    def forward(self, x, P, mode: str = "exact", env=None) -> Tuple[float, np.ndarray, np.ndarray]:
         """(loglike, N[I+1][L+1][S], W[I+1][L+1][S]); mode "exact" or "max"."""
         x, P = self._checkPair(x, P)
         fold = _max_fold if mode == "max" else _lse_fold
         I, L, S = len(x), len(P), self.S
         N = np.full((I + 1, L + 1, S), _NEG); W = np.full((I + 1, L + 1, S), _NEG)
+        inside = self.envelopeRows(env, I, L)
         for i in range(I + 1):
-            for r in range(L + 1):
+            for r in (range(L + 1) if inside is None else inside[i]):      # (a cell outside stays -inf and is read as such)
                 base = np.full(S, _NEG)
                 if i == 0 and r == 0:
                     base[0] = 0.0
@@ -585,14 +612,15 @@ class PairProfileDP(ProfileDP):
                 W[i, r] = w_
         return float(W[I, L, S - 1]), N, W
 
-    def backward(self, x, P) -> Tuple[float, np.ndarray, np.ndarray]:
+    def backward(self, x, P, env=None) -> Tuple[float, np.ndarray, np.ndarray]:
         """(loglike, NB[I+1][L+1][S], WB[I+1][L+1][S]), exact log-sum-exp; loglike = NB[0][0][0].  WB[i][r][s] is the mass from
         the waiting stage of (i, r, s) to the end, NB from the arrived stage: NB = WB (+) (P[r][0] + NB[i][r+1])."""
         x, P = self._checkPair(x, P)
         I, L, S = len(x), len(P), self.S
         NB = np.full((I + 1, L + 1, S), _NEG); WB = np.full((I + 1, L + 1, S), _NEG)
+        inside = self.envelopeRows(env, I, L)
         for i in range(I, -1, -1):
-            for r in range(L, -1, -1):
+            for r in (range(L, -1, -1) if inside is None else reversed(inside[i])):
                 base = np.full(S, _NEG)
                 if i == I and r == L:
                     base[S - 1] = 0.0
@@ -610,20 +638,21 @@ class PairProfileDP(ProfileDP):
                 NB[i, r] = np.logaddexp(base, P[r][0] + NB[i, r + 1]) if r < L else base
         return float(NB[0, 0, 0]), NB, WB
 
-    def counts(self, x, P, blanks: Optional[list] = None) -> Tuple[np.ndarray, float]:
+    def counts(self, x, P, blanks: Optional[list] = None, env=None) -> Tuple[np.ndarray, float]:
         """(posterior expected use of every transition, Forward loglike); nothing for a -inf pair.  Blank rows are not edges;
         ``blanks`` (a list) receives their posterior mass, summed over the lattice."""
         x, P = self._checkPair(x, P)
-        ll, NF, WF = self.forward(x, P)
+        ll, NF, WF = self.forward(x, P) if env is None else self.forward(x, P, env=env)
         out = np.zeros(self.em.nTransitions)
         if not ll > _NEG:
             return out, ll
-        _, NB, WB = self.backward(x, P)
+        _, NB, WB = self.backward(x, P) if env is None else self.backward(x, P, env=env)
         I, L = len(x), len(P)
+        inside = self.envelopeRows(env, I, L)
         blank = 0.0
         with np.errstate(invalid="ignore"):
             for i in range(I + 1):
-                for r in range(L + 1):
+                for r in (range(L + 1) if inside is None else inside[i]):
                     f = WF[i, r] - ll
                     if r < L:
                         if i < I:
@@ -640,14 +669,16 @@ class PairProfileDP(ProfileDP):
             blanks.append(blank)
         return out, ll
 
-    def viterbi(self, x, P, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray]:
+    def viterbi(self, x, P, census: Optional[dict] = None, env=None) -> Tuple[float, np.ndarray, np.ndarray]:
         """(score, global edge ids start -> end, row at which each fired); the first maximum in the fill's candidate order.  The
         row of an emitting edge is the row it consumed, of an output-less edge the number of rows consumed before it; the input
         position follows by counting the input-consuming edges.  ``census``: per step at which two or more candidates equal the
         cell, a count under the tuple of the kinds that tie, in candidate order ("blank", "match", "emit" at an N cell; "stay",
-        "ins", "silent" at a W cell)."""
+        "ins", "silent" at a W cell).  Under ``env`` a candidate whose source cell lies outside the envelope is -inf and loses; the
+        census counts, under ("outside", kind), the steps that had such a candidate of that kind."""
         x, P = self._checkPair(x, P)
-        v, N, W = self.forward(x, P, "max")
+        v, N, W = self.forward(x, P, "max") if env is None else self.forward(x, P, "max", env=env)
+        inside = self.envelopeRows(env, len(x), len(P))
         edges: List[int] = []; rows: List[int] = []
         if not v > _NEG:
             return v, np.zeros(0, np.uint32), np.zeros(0, np.int32)
@@ -673,6 +704,12 @@ class PairProfileDP(ProfileDP):
                 cand += [("emit", int(self.eId[k]), int(self.eS[k]), (W[i, r - 1, self.eS[k]] + self.eW[k]) + Pr[self.eO[k]] == cur)
                          for k in self.inEmit[q]]
             hits = [c for c in cand if c[3]]
+            if census is not None and inside is not None:
+                back = {"ins": (1, 0), "blank": (0, 1), "emit": (0, 1), "match": (1, 1)}
+                for kind in dict.fromkeys(c[0] for c in cand if c[0] in back):
+                    si, sr = i - back[kind][0], r - back[kind][1]
+                    if sr not in inside[si]:
+                        census[("outside", kind)] = census.get(("outside", kind), 0) + 1
             if census is not None and len(hits) > 1:
                 kinds = tuple(dict.fromkeys(c[0] for c in hits))
                 census[kinds] = census.get(kinds, 0) + 1

@@ -163,3 +163,26 @@ class Envelope:
     @classmethod
     def pathAreaEnvelope(cls, path: Sequence[Tuple[str, str]], width: int) -> "Envelope":
         e = cls(); e.initPathArea(path, width); return e
+
+    def monotone(self) -> bool:
+        """Neither inStart nor inEnd decreases from one row to the next: then the cells of an anti-diagonal x + y = d are a run
+        of consecutive x (the two-tape profile sweeps rest on it).  The full, path and path-area forms all are."""
+        return all(self.inStart[y - 1] <= self.inStart[y] and self.inEnd[y - 1] <= self.inEnd[y] for y in range(1, len(self.inStart)))
+
+    @classmethod
+    def band(cls, inLen: int, outLen: int, width: int) -> "Envelope":
+        """A band of half-width ``width`` around the line from (0, 0) to (inLen, outLen): row y is centred on
+        c = round(y * inLen / outLen) and holds max(0, c - width) .. min(inLen, c + width).  With outLen == 0 the line lies in
+        the one row there is: it starts from the centre 0 and runs to inLen, whatever the width.  Raises "Envelope is not
+        connected" where the width cannot bridge the slope."""
+        e = cls()
+        e.inLen, e.outLen = int(inLen), int(outLen)
+        e.inStart, e.inEnd = [], []
+        for y in range(e.outLen + 1):
+            c = (2 * y * e.inLen + e.outLen) // (2 * e.outLen) if e.outLen else 0      # round half up, in integers
+            e.inStart.append(max(0, c - width)); e.inEnd.append(min(e.inLen, c + width) + 1)
+        if not e.outLen:
+            e.inEnd[0] = e.inLen + 1
+        if width < 0 or not e.connected():
+            raise MachineError("Envelope is not connected")
+        return e

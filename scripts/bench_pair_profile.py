@@ -7,6 +7,11 @@ over A, C, G, T + blank, 1 and 64 pairs, at I = L = 200 and at I = L = 2 000.  T
            inputs: I launches of a row-serial fill, every pair of the batch in each
 
     python scripts/bench_pair_profile.py [--quick] [--chained-large] [--out profiles/pair_profile_bench.json]
+    python scripts/bench_pair_profile.py --band [W ...] [--quick] [--out profiles/pair_profile_band_bench.json]
+
+--band (docs/profile_tapes.md, "Pairs under an envelope"): the same shapes under seqpair.Envelope.band of half-width W (default 15
+and 63) -- forward(MB_ROLLING) under the band beside the full sweep of the same pairs in the same process, and counts() under the
+band; nothing is chained.
 
 Times are wall clock around synchronised calls, after one warm-up call; the repetitions of each are in the output.  --quick: the
 small shape only (a rehearsal).  The chained route at I = L = 2 000 is 2 000 launches of 2 001 serial rows each -- minutes per call --
@@ -55,12 +60,46 @@ def chained(dm, logR, xs, profs):
         px.close()
 
 
+def band_runs(args, em, dm, out):
+    from machineboss_amd.seqpair import Envelope
+    shapes = [(200, 1, 5), (200, 64, 5)] + ([] if args.quick else [(2000, 1, 2), (2000, 64, 2)])
+    for size, n, reps in shapes:
+        rng = np.random.RandomState(size + n)
+        xs = [rng.randint(1, em.nInTok + 1, size=size).astype(np.int32) for _ in range(n)]
+        profs = [np.log(rng.dirichlet([0.3] * (em.nOutTok + 1), size).astype(np.float32).astype(np.float64) + 1e-6) for _ in range(n)]
+        dev = capi.DeviceProfilePairs(dm, xs, profs)
+        full, tf = timed(lambda: dev.forward(capi.MB_ROLLING), reps)
+        for w in args.band:
+            env = Envelope.band(size, size, w)
+            dev.set_envelopes([env] * n)
+            ll, tb = timed(lambda: dev.forward(capi.MB_ROLLING), reps)
+            kernel = capi.last_kernel_name()
+            (_, _, llc), tc = timed(lambda: dev.counts(), 1)
+            run = {"I": size, "L": size, "pairs": n, "band": w, "full_forward_rolling_s": round(tf, 6), "band_forward_rolling_s": round(tb, 6),
+                   "full_over_band": round(tf / tb, 2), "band_counts_s": round(tc, 6), "reps": reps, "kernel": kernel,
+                   "lattice_doubles": dev.cells(), "finite": int(np.isfinite(ll).sum()), "loglike_0": float(ll[0]), "full_loglike_0": float(full[0]),
+                   "counts_loglike_equal": bool(np.array_equal(ll, llc))}
+            dev.set_envelopes(None)
+            out["runs"].append(run)
+            print(json.dumps(run), flush=True)
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(out, f, indent=1, sort_keys=True)
+                f.write("\n")
+        dev.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--chained-large", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pair_profile_bench.json"))
+    ap.add_argument("--band", type=int, nargs="*", metavar="W", help="sweep under bands of these half-widths (default 15 63) beside the full sweep")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.band is not None and not args.band:
+        args.band = [15, 63]
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "pair_profile_band_bench.json" if args.band else "pair_profile_bench.json")
     if capi.device_count() == 0:
         sys.exit("no GPU visible")
     capi.set_device(0)
@@ -69,6 +108,10 @@ def main():
     logR = prefixtree.logSumInTrans(em)
     dm = capi.DeviceMachine(em)
     out = {"machine": "dnastore4", "states": em.nStates, "input_tokens": em.nInTok, "silent_levels": dm.n_levels(), "runs": []}
+    if args.band:
+        band_runs(args, em, dm, out)
+        dm.close()
+        return
     shapes = [(200, 1, 5, 2), (200, 64, 5, 2)] + ([] if args.quick else [(2000, 1, 2, 1), (2000, 64, 2, 1)])
     for size, n, repsPairs, repsChained in shapes:
         rng = np.random.RandomState(size + n)
