@@ -2512,7 +2512,7 @@ static double pp_ring_bytes(const mb_profile_pairs *p, long long k, bool rolling
 }
 static MergeMap pp_map(const mb_profile_pairs *p) { return MergeMap{p->nCols, p->d_colTok}; }
 
-// Pairs with an envelope go to the kernels of mb_profile_pair_env.hip in a launch of their own: a chunk's pairs without one come
+// Pairs with an envelope go to the kernels' envelope geometry in a launch of their own: a chunk's pairs without one come
 // first in its per-pair outputs (log-likelihoods, path lengths), then the pairs with one; slot[k - p0] is where pair k landed.
 struct PairProfPlan {
   PairProfDesc *d = nullptr; PairEnvDesc *e = nullptr;
@@ -2537,17 +2537,14 @@ static int pair_profile_descs(const mb_profile_pairs *p, long long p0, long long
       if (lds) { if (pp_env(p, k)) pl.ldsEnv = std::max(pl.ldsEnv, lds); else pl.lds = std::max(pl.lds, lds); }
       else { ringBase = pl.ring; pl.ring += pp_ring(p, k, rolling); }
     }
+    PairEnvDesc d;      // (a full pair keeps its PairProfDesc part)
+    d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)I; d.nRows = (int)L;
+    d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = ringBase;
     if (pp_env(p, k)) {
-      PairEnvDesc d;
-      d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)I; d.nRows = (int)L;
-      d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = ringBase;
       d.envBase = p->envBase[(size_t)k]; d.diagBase = p->diagBase[(size_t)k]; d.nCells = p->envCells[(size_t)k]; d.M = p->envM[(size_t)k];
       pl.maxItemsEnv = std::max(pl.maxItemsEnv, (long long)d.M * S);
       he.push_back(d); envPairs.push_back(k);
     } else {
-      PairProfDesc d;
-      d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)I; d.nRows = (int)L;
-      d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = ringBase;
       pl.maxItems = std::max(pl.maxItems, (std::min(I, L) + 1) * S * (p->nCols + 1));
       pl.slot[(size_t)(k - p0)] = (long long)h.size();
       h.push_back(d);
@@ -2564,7 +2561,7 @@ static int pair_profile_descs(const mb_profile_pairs *p, long long p0, long long
       !hip_ok(hipStreamSynchronize(g_stream), "H2D pair descriptors")) { pp_plan_free(pl); return 1; }
   return 0;
 }
-static PairEnvTables pp_tables(const mb_profile_pairs *p) { return PairEnvTables{p->d_envStart, p->d_envEnd, p->d_envOff, p->d_diagLo, p->d_diagCnt}; }
+static PairEnvTables pp_env_tables(const mb_profile_pairs *p) { return PairEnvTables{p->d_envStart, p->d_envEnd, p->d_envOff, p->d_diagLo, p->d_diagCnt}; }
 // per-pair device results (each chunk in the order of its plan's slots; at[k] = the entry of pair k) into dst[0..n)
 struct PairWhere {
   std::vector<long long> at; bool permuted = false;
@@ -2582,27 +2579,28 @@ static int pp_fetch(double *dst, const double *d_src, long long n, const PairWhe
   return 0;
 }
 
-// The one place where the plain and the merged kernels part: the launches of a chunk and the names they report.
+// The one place where the plain and the merged kernels part: the launches of a chunk and the names they report.  The plain kernels
+// take the chunk's full pairs, then its pairs under an envelope, through the two overloads of one launcher.
 static int pp_launch_fwd(const mb_profile_pairs *p, int mode, bool mat, const PairProfPlan &pl, long long n, double *pool, double *scratch, double *ll) {
   if (p->nCols) return launch_profile_pair_merge_fwd(p->m, pp_map(p), mode, mat, pl.d, (int)n, pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, ll, g_stream);
   if (launch_profile_pair_fwd(p->m, mode, mat, pl.d, (int)pl.nPlain, mat ? 0 : pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, mat ? nullptr : scratch, ll, g_stream)) return 1;
-  return launch_profile_pair_env_fwd(p->m, mode, mat, pl.e, pp_tables(p), (int)pl.nEnv, mat ? 0 : pl.ldsEnv, pl.maxItemsEnv, p->d_in, p->d_logP, pool,
-                                     mat ? nullptr : scratch, ll + pl.nPlain, g_stream);
+  return launch_profile_pair_fwd(p->m, mode, mat, pl.e, pp_env_tables(p), (int)pl.nEnv, mat ? 0 : pl.ldsEnv, pl.maxItemsEnv, p->d_in, p->d_logP, pool,
+                                 mat ? nullptr : scratch, ll + pl.nPlain, g_stream);
 }
 static int pp_launch_bwd(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, double *pool, double *scratch, double *ll) {
   if (p->nCols) return launch_profile_pair_merge_bwd(p->m, pp_map(p), pl.d, (int)n, pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, ll, g_stream);
   if (launch_profile_pair_bwd(p->m, pl.d, (int)pl.nPlain, pl.maxItems, p->d_in, p->d_logP, pool, ll, g_stream)) return 1;
-  return launch_profile_pair_env_bwd(p->m, pl.e, pp_tables(p), (int)pl.nEnv, pl.maxItemsEnv, p->d_in, p->d_logP, pool, ll + pl.nPlain, g_stream);
+  return launch_profile_pair_bwd(p->m, pl.e, pp_env_tables(p), (int)pl.nEnv, pl.maxItemsEnv, p->d_in, p->d_logP, pool, ll + pl.nPlain, g_stream);
 }
 static int pp_launch_traceback(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, const double *pool, uint32_t *e, int32_t *r, long long *len) {
   if (p->nCols) return launch_profile_pair_merge_traceback(p->m, pp_map(p), pl.d, (int)n, p->d_in, p->d_logP, pool, e, r, len, g_stream);
   if (launch_profile_pair_traceback(p->m, pl.d, (int)pl.nPlain, p->d_in, p->d_logP, pool, e, r, len, g_stream)) return 1;
-  return launch_profile_pair_env_traceback(p->m, pl.e, pp_tables(p), (int)pl.nEnv, p->d_in, p->d_logP, pool, e, r, len + pl.nPlain, g_stream);
+  return launch_profile_pair_traceback(p->m, pl.e, pp_env_tables(p), (int)pl.nEnv, p->d_in, p->d_logP, pool, e, r, len + pl.nPlain, g_stream);
 }
 static int pp_launch_counts(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, int groups, const double *fwd, const double *bwd, double *cc) {
   if (p->nCols) return launch_profile_pair_merge_counts(p->m, pp_map(p), pl.d, (int)n, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
   if (launch_profile_pair_counts(p->m, pl.d, (int)pl.nPlain, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream)) return 1;
-  return launch_profile_pair_env_counts(p->m, pl.e, pp_tables(p), (int)pl.nEnv, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
+  return launch_profile_pair_counts(p->m, pl.e, pp_env_tables(p), (int)pl.nEnv, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
 }
 static const char *pp_fwd_name(const mb_profile_pairs *p, int mode, bool mat) {
   static const char *const names[2][2][2] = {{{"k_profile_pair_fwd<sum,rolling>", "k_profile_pair_fwd<sum,mat>"}, {"k_profile_pair_fwd<max,rolling>", "k_profile_pair_fwd<max,mat>"}},
@@ -2646,7 +2644,7 @@ static int pair_profile_scores(mb_profile_pairs *p, int mode, bool mat, double *
   return rc;
 }
 
-// ---- envelopes of the pairs (mb_profile_pair_env.hip, docs/profile_tapes.md "Pairs under an envelope") ----
+// ---- envelopes of the pairs (mb_profile_pair_env.h, docs/profile_tapes.md "Pairs under an envelope") ----
 static void pp_env_free(mb_profile_pairs *p) {
   if (p->d_envStart) (void)hipFree(p->d_envStart);
   if (p->d_envEnd) (void)hipFree(p->d_envEnd);
@@ -2670,7 +2668,7 @@ static int profile_pairs_set_envelopes(mb_profile_pairs *p, const int64_t *envOf
   std::vector<int> envM((size_t)p->n, 0), hSt, hEn, hLo, hCnt;
   for (long long k = 0; k < p->n; ++k) {
     const long long rows = envOff[k + 1] - envOff[k], I = pp_in(p, k), L = pp_rows(p, k);
-    if (rows == 0) continue;   // full: the pair keeps the sweeps of mb_profile_pair.hip
+    if (rows == 0) continue;   // full: the pair keeps the full geometry of mb_profile_pair.hip
     if (rows != L + 1) { set_error("Envelope/sequence mismatch"); return 1; }
     const int32_t *st = inStart + envOff[k], *en = inEnd + envOff[k];
     for (long long y = 0; y < rows; ++y)

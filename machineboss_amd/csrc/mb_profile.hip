@@ -12,31 +12,23 @@
 // W) in LDS when they fit (24 S bytes: about 6 800 states in 160 KiB), else in a per-workgroup slice of a global scratch buffer.
 // Cells are fp64 and the sums use the exact log-sum-exp (the counts of long profiles need it).  Transitions that read input never
 // fire: the input tape is empty.
-#include <algorithm>
-
-#include "mb_device_math.h"
 #include "mb_profile.h"
+#include "mb_profile_common.h"
 
 namespace mb {
 
-template <int MODE>
-__device__ __forceinline__ double pf_red(double a, double b) { return MODE == MB_VITERBI ? dmax(a, b) : lse2_exact(a, b); }
-
-static constexpr int PF_THREADS = 1024;
-static constexpr size_t PF_LDS_MAX = 160 * 1024;
-
 size_t profile_lds_bytes(int S) {
   const size_t b = (size_t)3 * S * sizeof(double);
-  return b <= PF_LDS_MAX ? b : 0;
+  return b <= SWEEP_LDS_MAX ? b : 0;
 }
 
 // Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every cell into pool (layout of mb_profile.h), else rolling.
 // Viterbi keeps the FIRST maximum: N takes the blank candidate first, then the emitting edges in `incoming` order; W takes N
 // (no move) first, then the silent edges in `incoming` order -- the order k_profile_traceback re-enumerates.
 template <int MODE, bool MAT>
-__global__ __launch_bounds__(PF_THREADS) void k_profile_fwd(DevMachine m, const ProfDesc *__restrict__ descs,
-                                                            const double *__restrict__ logP, double *pool, double *scratch,
-                                                            int useLds, double *__restrict__ loglike) {
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_fwd(DevMachine m, const ProfDesc *__restrict__ descs,
+                                                               const double *__restrict__ logP, double *pool, double *scratch,
+                                                               int useLds, double *__restrict__ loglike) {
   extern __shared__ double pf_sh[];
   const ProfDesc pd = descs[blockIdx.x];
   const int S = m.S, K = m.K, C = m.nOut + 1, L = pd.nRows;
@@ -57,7 +49,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_profile_fwd(DevMachine m, const 
         double acc = Np[q] + blank;
         const int a1 = m.inOff[q * K + C];            // CSR rows q*K + key(0, o), o = 1..nOut: contiguous
         for (int a = m.inOff[q * K + 1]; a < a1; ++a)
-          acc = pf_red<MODE>(acc, (Wp[m.inSrc[a]] + m.inW[a]) + Pr[m.eOutTok[m.inEid[a]]]);
+          acc = red<MODE>(acc, (Wp[m.inSrc[a]] + m.inW[a]) + Pr[m.eOutTok[m.inEid[a]]]);
         Nc[q] = acc;
       }
     }
@@ -71,7 +63,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_profile_fwd(DevMachine m, const 
         for (int a = m.inOff[q * K]; a < a1; ++a) {
           const int s = (int)m.inSrc[a];
           if (s >= q) continue;                       // as the token sweeps: a silent self-loop never fires
-          acc = pf_red<MODE>(acc, Wc[s] + m.inW[a]);
+          acc = red<MODE>(acc, Wc[s] + m.inW[a]);
         }
         Wc[q] = acc;
       }
@@ -89,10 +81,10 @@ __global__ __launch_bounds__(PF_THREADS) void k_profile_fwd(DevMachine m, const 
 // with LL the Forward likelihood.  An edge belongs to one source state and a state to one lane (its place in its level), so each
 // accumulator has one writer and sees its rows in a fixed order: the counts are the same bits from run to run.
 template <bool MAT>
-__global__ __launch_bounds__(PF_THREADS) void k_profile_bwd(DevMachine m, const ProfDesc *__restrict__ descs,
-                                                            const double *__restrict__ logP, double *pool,
-                                                            const double *__restrict__ fwdPool, double *scratch, int useLds,
-                                                            double *__restrict__ loglike, double *part, long long nTrans) {
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_bwd(DevMachine m, const ProfDesc *__restrict__ descs,
+                                                               const double *__restrict__ logP, double *pool,
+                                                               const double *__restrict__ fwdPool, double *scratch, int useLds,
+                                                               double *__restrict__ loglike, double *part, long long nTrans) {
   extern __shared__ double pf_sh[];
   const ProfDesc pd = descs[blockIdx.x];
   const int S = m.S, K = m.K, C = m.nOut + 1, L = pd.nRows;
@@ -210,12 +202,10 @@ static void pf_set_lds_attr() {
   static bool done = false;
   if (done) return;
   done = true;
-  (void)hipFuncSetAttribute((const void *)&k_profile_fwd<MB_FORWARD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF_LDS_MAX);
-  (void)hipFuncSetAttribute((const void *)&k_profile_fwd<MB_VITERBI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF_LDS_MAX);
-  (void)hipFuncSetAttribute((const void *)&k_profile_bwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PF_LDS_MAX);
+  (void)hipFuncSetAttribute((const void *)&k_profile_fwd<MB_FORWARD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX);
+  (void)hipFuncSetAttribute((const void *)&k_profile_fwd<MB_VITERBI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX);
+  (void)hipFuncSetAttribute((const void *)&k_profile_bwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX);
 }
-
-static int pf_threads(int S) { return std::min(PF_THREADS, std::max(64, (S + 63) / 64 * 64)); }
 
 int launch_profile_fwd(const mb_machine *m, int mode, bool mat, const ProfDesc *d, int n, const double *logP, double *pool,
                        double *scratch, double *loglike, hipStream_t st) {
@@ -223,7 +213,7 @@ int launch_profile_fwd(const mb_machine *m, int mode, bool mat, const ProfDesc *
   pf_set_lds_attr();
   const size_t lds = mat ? 0 : profile_lds_bytes(m->S);
   const int useLds = lds > 0;
-  const dim3 g(n), b(pf_threads(m->S));
+  const dim3 g(n), b(sweep_threads(m->S));
   if (mode == MB_VITERBI) {
     if (mat) k_profile_fwd<MB_VITERBI, true><<<g, b, 0, st>>>(m->dev, d, logP, pool, scratch, 0, loglike);
     else k_profile_fwd<MB_VITERBI, false><<<g, b, lds, st>>>(m->dev, d, logP, pool, scratch, useLds, loglike);
@@ -239,7 +229,7 @@ int launch_profile_bwd(const mb_machine *m, bool mat, const ProfDesc *d, int n, 
   if (n <= 0) return 0;
   pf_set_lds_attr();
   const size_t lds = mat ? 0 : profile_lds_bytes(m->S);
-  const dim3 g(n), b(pf_threads(m->S));
+  const dim3 g(n), b(sweep_threads(m->S));
   if (mat) k_profile_bwd<true><<<g, b, 0, st>>>(m->dev, d, logP, pool, fwdPool, scratch, 0, loglike, part, nTrans);
   else k_profile_bwd<false><<<g, b, lds, st>>>(m->dev, d, logP, pool, fwdPool, scratch, lds > 0, loglike, part, nTrans);
   return hip_ok(hipGetLastError(), "k_profile_bwd") ? 0 : 1;

@@ -1,0 +1,57 @@
+// mb_profile_common.h -- what the profile sweeps share (mb_profile.hip, mb_profile_merge.hip, mb_profile_pair.hip,
+// mb_profile_pair_merge.hip): the reduction of a sweep's mode, the LDS a ring may take, the lanes of a workgroup, and the
+// accumulator of the posterior counts.  Device code: included by .hip files only.
+#pragma once
+#include <algorithm>
+
+#include "mb_device_math.h"
+#include "mb_internal.h"
+
+namespace mb {
+
+static constexpr int SWEEP_THREADS = 1024;
+static constexpr size_t SWEEP_LDS_MAX = 160 * 1024;      // a ring lives in LDS while it fits, else in global scratch
+static constexpr int COUNTS_LDS_MAX = 8192;             // transitions a workgroup's LDS accumulators hold
+
+template <int MODE>
+__device__ __forceinline__ double red(double a, double b) { return MODE == MB_VITERBI ? dmax(a, b) : lse2_exact(a, b); }
+
+// lanes of a workgroup whose busiest phase has maxItems work items: whole wavefronts, at least one
+inline int sweep_threads(long long maxItems) { return (int)std::min<long long>(SWEEP_THREADS, std::max<long long>(64, (maxItems + 63) / 64 * 64)); }
+
+// Posterior counts of one workgroup.  Partial counts are kept in the workgroup's LDS table (lds[COUNTS_LDS_MAX]) when the
+// transition table is small and flushed once with atomics; beyond, every term goes to the global table.  det: both tables hold
+// 64-bit fixed point at 2^-36 (mb_internal.h) -- integer adds commute, so the counts are the same bits from call to call.
+struct CountsAcc {
+  double *lds, *counts, *tab;
+  long long nTrans;
+  int det;
+  bool useLds;
+  // every lane of the workgroup: zeroes the LDS table
+  __device__ __forceinline__ CountsAcc(double *lds, double *counts, long long nTrans, int det)
+      : lds(lds), counts(counts), nTrans(nTrans), det(det), useLds(nTrans <= COUNTS_LDS_MAX) {
+    if (useLds) {
+      for (int e = threadIdx.x; e < nTrans; e += blockDim.x) lds[e] = 0.0;
+      __syncthreads();
+    }
+    tab = useLds ? lds : counts;
+  }
+  __device__ __forceinline__ void add(uint32_t e, double c) const {
+    if (c != 0.0) {
+      if (det) atomicAdd((unsigned long long *)tab + e, (unsigned long long)fmin(fmax(c * MB_DET_GLOBAL_SCALE + 0.5, 0.0), 4611686018427387904.0));
+      else atomicAdd(&tab[e], c);
+    }
+  }
+  // every lane of the workgroup, after its last add
+  __device__ __forceinline__ void flush() const {
+    if (!useLds) return;
+    __syncthreads();
+    for (int e = threadIdx.x; e < nTrans; e += blockDim.x)
+      if (det ? ((const unsigned long long *)lds)[e] != 0ull : lds[e] != 0.0) {
+        if (det) atomicAdd((unsigned long long *)counts + e, ((const unsigned long long *)lds)[e]);
+        else atomicAdd(&counts[e], lds[e]);
+      }
+  }
+};
+
+}  // namespace mb

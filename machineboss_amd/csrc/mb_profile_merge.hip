@@ -13,22 +13,14 @@
 // are split into groups, one per plane, and the lanes of a group run over the states (of a silent level).  Per row: one emission
 // phase and a barrier, one barrier per silent level -- the barriers of the plain sweep, with nCols + 1 times the work between them --
 // and one more phase and barrier for X, so that no edge loop runs over planes.  Cells are fp64, sums the exact log-sum-exp.
-#include <algorithm>
-
-#include "mb_device_math.h"
+#include "mb_profile_common.h"
 #include "mb_profile_merge.h"
 
 namespace mb {
 
-template <int MODE>
-__device__ __forceinline__ double pm_red(double a, double b) { return MODE == MB_VITERBI ? dmax(a, b) : lse2_exact(a, b); }
-
-static constexpr int PM_THREADS = 1024;
-static constexpr size_t PM_LDS_MAX = 160 * 1024;
-
 static size_t pm_fit(long long doubles) {
   const unsigned long long b = (unsigned long long)doubles * sizeof(double);
-  return b <= PM_LDS_MAX ? (size_t)b : 0;
+  return b <= SWEEP_LDS_MAX ? (size_t)b : 0;
 }
 size_t profile_merge_fwd_lds(int S, int nCols, bool mat) { return pm_fit(mat ? (long long)nCols * S : profile_merge_ring(S, nCols)); }
 size_t profile_merge_bwd_lds(int S, int nCols) { return pm_fit(3LL * (nCols + 1) * S); }
@@ -51,9 +43,9 @@ __device__ __forceinline__ PmLanes pm_lanes(int planes) {
 // order; N[.][0] the planes ascending; N[.][c] the repeat first, then the emitting edges of colTok[c] in `incoming` order; X and the
 // end the planes ascending -- the order k_profile_merge_traceback re-enumerates.
 template <int MODE, bool MAT>
-__global__ __launch_bounds__(PM_THREADS) void k_profile_merge_fwd(DevMachine m, MergeMap mm, const ProfDesc *__restrict__ descs,
-                                                                  const double *__restrict__ logP, double *pool, double *scratch,
-                                                                  int useLds, double *__restrict__ loglike) {
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_merge_fwd(DevMachine m, MergeMap mm, const ProfDesc *__restrict__ descs,
+                                                                     const double *__restrict__ logP, double *pool, double *scratch,
+                                                                     int useLds, double *__restrict__ loglike) {
   extern __shared__ double pm_sh[];
   const ProfDesc pd = descs[blockIdx.x];
   const int S = m.S, K = m.K, nC = mm.nCols, PL = nC + 1, L = pd.nRows;
@@ -78,7 +70,7 @@ __global__ __launch_bounds__(PM_THREADS) void k_profile_merge_fwd(DevMachine m, 
         if (p == 0) {
           for (int q = ln.ln; q < S; q += ln.LPP) {
             double acc = Np[q] + w;
-            for (int k = 1; k < PL; ++k) acc = pm_red<MODE>(acc, Np[(long long)k * S + q] + w);
+            for (int k = 1; k < PL; ++k) acc = red<MODE>(acc, Np[(long long)k * S + q] + w);
             Nc[q] = acc;
           }
         } else {
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(PM_THREADS) void k_profile_merge_fwd(DevMachine m, 
           for (int q = ln.ln; q < S; q += ln.LPP) {
             double acc = Np[(long long)p * S + q] + w;
             const int a1 = m.inOff[q * K + tok + 1];
-            for (int a = m.inOff[q * K + tok]; a < a1; ++a) acc = pm_red<MODE>(acc, (Xc[m.inSrc[a]] + m.inW[a]) + w);
+            for (int a = m.inOff[q * K + tok]; a < a1; ++a) acc = red<MODE>(acc, (Xc[m.inSrc[a]] + m.inW[a]) + w);
             Nc[(long long)p * S + q] = acc;
           }
         }
@@ -106,7 +98,7 @@ __global__ __launch_bounds__(PM_THREADS) void k_profile_merge_fwd(DevMachine m, 
           for (int a = m.inOff[q * K]; a < a1; ++a) {
             const int s = (int)m.inSrc[a];
             if (s >= q) continue;                         // as the plain sweep: a silent self-loop never fires
-            acc = pm_red<MODE>(acc, Wq[s] + m.inW[a]);
+            acc = red<MODE>(acc, Wq[s] + m.inW[a]);
           }
           Wq[q] = acc;
         }
@@ -119,7 +111,7 @@ __global__ __launch_bounds__(PM_THREADS) void k_profile_merge_fwd(DevMachine m, 
         for (int s = ln.ln; s < S; s += ln.LPP) {
           double acc = Wc[s];                             // plane 0 is never the excluded one
           for (int k = 1; k < PL; ++k)
-            if (k != c) acc = pm_red<MODE>(acc, Wc[(long long)k * S + s]);
+            if (k != c) acc = red<MODE>(acc, Wc[(long long)k * S + s]);
           Xc[s] = acc;
         }
       }
@@ -128,7 +120,7 @@ __global__ __launch_bounds__(PM_THREADS) void k_profile_merge_fwd(DevMachine m, 
   }
   if (threadIdx.x == 0) {
     double acc = Wc[S - 1];
-    for (int p = 1; p < PL; ++p) acc = pm_red<MODE>(acc, Wc[(long long)p * S + S - 1]);
+    for (int p = 1; p < PL; ++p) acc = red<MODE>(acc, Wc[(long long)p * S + S - 1]);
     loglike[blockIdx.x] = acc;
   }
 }
@@ -141,10 +133,10 @@ __global__ __launch_bounds__(PM_THREADS) void k_profile_merge_fwd(DevMachine m, 
 // posteriors of the terms above with W_F[r][k][s] - LL in front.  An accumulator belongs to one plane and one source state, hence to
 // one lane, which sees its rows and columns in a fixed order: the counts are the same bits from run to run.
 template <bool MAT>
-__global__ __launch_bounds__(PM_THREADS) void k_profile_merge_bwd(DevMachine m, MergeMap mm, const ProfDesc *__restrict__ descs,
-                                                                  const double *__restrict__ logP, double *pool,
-                                                                  const double *__restrict__ fwdPool, double *scratch, int useLds,
-                                                                  double *__restrict__ loglike, double *part, long long nTrans) {
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_merge_bwd(DevMachine m, MergeMap mm, const ProfDesc *__restrict__ descs,
+                                                                     const double *__restrict__ logP, double *pool,
+                                                                     const double *__restrict__ fwdPool, double *scratch, int useLds,
+                                                                     double *__restrict__ loglike, double *part, long long nTrans) {
   extern __shared__ double pm_sh[];
   const ProfDesc pd = descs[blockIdx.x];
   const int S = m.S, K = m.K, nC = mm.nCols, PL = nC + 1, L = pd.nRows;
@@ -299,18 +291,15 @@ static void pm_set_lds_attr() {
   static bool done = false;
   if (done) return;
   done = true;
-  (void)hipFuncSetAttribute((const void *)&k_profile_merge_fwd<MB_FORWARD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PM_LDS_MAX);
-  (void)hipFuncSetAttribute((const void *)&k_profile_merge_fwd<MB_VITERBI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PM_LDS_MAX);
-  (void)hipFuncSetAttribute((const void *)&k_profile_merge_fwd<MB_FORWARD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PM_LDS_MAX);
-  (void)hipFuncSetAttribute((const void *)&k_profile_merge_fwd<MB_VITERBI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PM_LDS_MAX);
-  (void)hipFuncSetAttribute((const void *)&k_profile_merge_bwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PM_LDS_MAX);
+  (void)hipFuncSetAttribute((const void *)&k_profile_merge_fwd<MB_FORWARD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX);
+  (void)hipFuncSetAttribute((const void *)&k_profile_merge_fwd<MB_VITERBI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX);
+  (void)hipFuncSetAttribute((const void *)&k_profile_merge_fwd<MB_FORWARD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX);
+  (void)hipFuncSetAttribute((const void *)&k_profile_merge_fwd<MB_VITERBI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX);
+  (void)hipFuncSetAttribute((const void *)&k_profile_merge_bwd<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX);
 }
 
 // one lane per (plane, state) pair up to the workgroup's 1 024
-static int pm_threads(int S, int nCols) {
-  const long long items = (long long)(nCols + 1) * S;
-  return (int)std::min<long long>(PM_THREADS, std::max<long long>(64, (items + 63) / 64 * 64));
-}
+static int pm_threads(int S, int nCols) { return sweep_threads((long long)(nCols + 1) * S); }
 
 int launch_profile_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const ProfDesc *d, int n, const double *logP,
                              double *pool, double *scratch, double *loglike, hipStream_t st) {

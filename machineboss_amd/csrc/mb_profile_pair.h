@@ -31,16 +31,17 @@ inline long long profile_pair_ring(int S, long long nIn, long long nRows) { retu
 // dynamic LDS of a pair's ring when it fits (0: a slice of the global scratch buffer)
 size_t profile_pair_lds_bytes(int S, long long nIn, long long nRows);
 
+// The launchers, one per sweep, over full rectangles; mb_profile_pair_env.h declares their overloads for pairs under an envelope.
 // lds: the dynamic LDS of the launch (the largest ring among the pairs whose ringBase is -1)
-int launch_profile_pair_fwd(const mb_machine *m, int mode, bool mat, const PairProfDesc *d, int n, size_t lds, long long maxItems,
-                            const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st);
-int launch_profile_pair_bwd(const mb_machine *m, const PairProfDesc *d, int n, long long maxItems, const int *inTok, const double *logP,
-                            double *pool, double *loglike, hipStream_t st);
+int launch_profile_pair_fwd(const mb_machine *m, int mode, bool mat, const PairProfDesc *d, int n, size_t lds, long long maxItems, const int *inTok,
+                            const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st);
+int launch_profile_pair_bwd(const mb_machine *m, const PairProfDesc *d, int n, long long maxItems, const int *inTok, const double *logP, double *pool,
+                            double *loglike, hipStream_t st);
 // counts[nTrans] += posteriors of the n pairs (fwdPool / bwdPool: their materialised lattices); det: 64-bit fixed point at 2^-36
 int launch_profile_pair_counts(const mb_machine *m, const PairProfDesc *d, int n, int groupsPerPair, const int *inTok, const double *logP,
                                const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
-int launch_profile_pair_traceback(const mb_machine *m, const PairProfDesc *d, int n, const int *inTok, const double *logP,
-                                  const double *pool, uint32_t *edges, int32_t *rows, long long *len, hipStream_t st);
+int launch_profile_pair_traceback(const mb_machine *m, const PairProfDesc *d, int n, const int *inTok, const double *logP, const double *pool,
+                                  uint32_t *edges, int32_t *rows, long long *len, hipStream_t st);
 
 }  // namespace mb
 

@@ -16,53 +16,103 @@
 // diagonal: one phase for N and the non-silent part of W and one barrier, then one barrier per silent level -- (I + L + 1) nLevF
 // barriers per pair.  The rolling sweeps keep a ring of three diagonals of both layers, 3 * 2 * (min(I, L) + 1) * S doubles, in LDS
 // when that fits 160 KiB, else in the pair's slice of a global scratch buffer.  Cells are fp64, the sums the exact log-sum-exp.
-#include <algorithm>
-
-#include "mb_device_math.h"
-#include "mb_profile_pair.h"
+//
+// Every kernel is written once over a GEOMETRY, which says which cells exist and where they live: FullGeom, the whole rectangle, or
+// EnvGeom, the cells of an envelope (docs/profile_tapes.md, "Pairs under an envelope").  Both layers of a cell outside the envelope
+// are -inf, so a neighbour outside is not read; the recurrence, the candidate order and the sums are the same text for both.
+#include "mb_profile_common.h"
+#include "mb_profile_pair_env.h"
 
 namespace mb {
 
-template <int MODE>
-__device__ __forceinline__ double pp_red(double a, double b) { return MODE == MB_VITERBI ? dmax(a, b) : lse2_exact(a, b); }
-
-static constexpr int PP_THREADS = 1024;
-static constexpr size_t PP_LDS_MAX = 160 * 1024;
-static constexpr int PP_COUNTS_LDS_MAX = 8192;
-
 size_t profile_pair_lds_bytes(int S, long long nIn, long long nRows) {
   const double b = (double)profile_pair_ring(S, nIn, nRows) * sizeof(double);
-  return b <= (double)PP_LDS_MAX ? (size_t)b : 0;
+  return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
+}
+size_t profile_pair_env_lds_bytes(int S, long long M) {
+  const double b = (double)profile_pair_env_ring(S, M) * sizeof(double);
+  return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
 }
 
-// Where the layers of cell (i, r) live: the materialised lattice, or the ring (diagonal (i + r) mod 3, the cell by its coordinate on
-// the short side of the lattice).
+struct NoPairTables {};      // what the full geometry needs beside a pair's descriptor
+
+// The whole rectangle.  MAT: the materialised lattice of mb_profile_pair.h at base, else the ring (diagonal (i + r) mod 3, the cell
+// by its coordinate on the short side of the lattice).
 template <bool MAT>
-struct PairLattice {
+struct FullGeom {
+  using Desc = PairProfDesc;
+  using Tables = NoPairTables;
+  static constexpr bool ENV = false;
   double *base;
-  int S, L, M, byI;
+  int S, I, L, M, byI;
+  __device__ __forceinline__ FullGeom(const Desc &pd, Tables, double *base, int S)
+      : base(base), S(S), I(pd.nIn), L(pd.nRows), M(min(pd.nIn, pd.nRows) + 1), byI(pd.nIn <= pd.nRows) {}
+  // the cells of diagonal d: i = ilo .. ilo + nCells - 1
+  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = max(0, d - L); nCells = min(I, d) - ilo + 1; }
+  // asked of neighbours the caller has already bounded to the rectangle
+  static constexpr __device__ __forceinline__ bool inside(int, int) { return true; }
   __device__ __forceinline__ double *at(int i, int r, int layer) const {
     if (MAT) return base + ((((long long)i * (L + 1)) + r) * 2 + layer) * S;
     return base + ((((long long)((i + r) % 3) * M) + (byI ? i : r)) * 2 + layer) * S;
   }
+  // counts: the cells of the pair and the c-th of them
+  __device__ __forceinline__ long long cells() const { return (long long)(I + 1) * (L + 1); }
+  __device__ __forceinline__ void cell(long long c, int &i, int &r) const { i = (int)(c / (L + 1)); r = (int)(c - (long long)i * (L + 1)); }
 };
 
-// Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every cell into pool (layout of mb_profile_pair.h), else rolling.
+// The cells of an envelope (mb_profile_pair_env.h).  Its bounds never decrease from row to row, so the cells of diagonal d are the
+// run i = diagLo[d] .. diagLo[d] + diagCnt[d] - 1 (the host uploads both).  MAT: the compact lattice at base, else the ring
+// (diagonal (i + r) mod 3, the cell at i mod M, M the largest diagCnt of the pair: the cells of a diagonal have consecutive i and
+// number at most M, so no two share a slot).
+template <bool MAT>
+struct EnvGeom {
+  using Desc = PairEnvDesc;
+  using Tables = PairEnvTables;
+  static constexpr bool ENV = true;
+  double *base;
+  const int *st, *en;         // the pair's envelope rows
+  const long long *off;       // compact index of the first cell of each row
+  const int *dLo, *dCnt;
+  long long nCells;
+  int S, L, M;
+  __device__ __forceinline__ EnvGeom(const Desc &pd, const Tables &t, double *base, int S)
+      : base(base), st(t.envStart + pd.envBase), en(t.envEnd + pd.envBase), off(t.envOff + pd.envBase),
+        dLo(t.diagLo + pd.diagBase), dCnt(t.diagCnt + pd.diagBase), nCells(pd.nCells), S(S), L(pd.nRows), M(pd.M) {}
+  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = dLo[d]; nCells = dCnt[d]; }
+  // r in -1..L+1, i in -1..I+1
+  __device__ __forceinline__ bool inside(int i, int r) const { return r >= 0 && r <= L && i >= st[r] && i < en[r]; }
+  __device__ __forceinline__ double *at(int i, int r, int layer) const {
+    if (MAT) return base + ((off[r] + (i - st[r])) * 2 + layer) * S;
+    return base + ((((long long)((i + r) % 3) * M) + (i % M)) * 2 + layer) * S;
+  }
+  __device__ __forceinline__ long long cells() const { return nCells; }
+  __device__ __forceinline__ void cell(long long c, int &i, int &r) const {
+    int lo = 0, hi = L;                        // the last row whose offset is <= c: rows behind it start past the cell
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (off[mid] <= c) lo = mid; else hi = mid - 1;
+    }
+    r = lo; i = st[r] + (int)(c - off[r]);
+  }
+};
+
+// Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every cell into pool (the geometry's layout), else rolling.
 // Viterbi keeps the FIRST maximum: N takes the blank first, then the match edges in `incoming` order, then the output-only edges in
 // `incoming` order; W takes N (no move) first, then the input-only edges, then the silent edges, each in `incoming` order -- the
 // order k_profile_pair_traceback re-enumerates.
-template <int MODE, bool MAT>
-__global__ __launch_bounds__(PP_THREADS) void k_profile_pair_fwd(DevMachine m, const PairProfDesc *__restrict__ descs,
-                                                                 const int *__restrict__ inTok, const double *__restrict__ logP,
-                                                                 double *pool, double *scratch, double *__restrict__ loglike) {
+template <int MODE, bool MAT, template <bool> class Geom>
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_fwd(DevMachine m, const typename Geom<MAT>::Desc *__restrict__ descs, typename Geom<MAT>::Tables t,
+                                                                    const int *__restrict__ inTok, const double *__restrict__ logP,
+                                                                    double *pool, double *scratch, double *__restrict__ loglike) {
   extern __shared__ double pp_sh[];
-  const PairProfDesc pd = descs[blockIdx.x];
+  const auto pd = descs[blockIdx.x];
   const int S = m.S, K = m.K, C = m.nOut + 1, I = pd.nIn, L = pd.nRows;
   const int *x = inTok + pd.inBase;
   const double *P = logP + pd.rowBase * C;
-  const PairLattice<MAT> lat{MAT ? pool + pd.cellBase : (pd.ringBase < 0 ? pp_sh : scratch + pd.ringBase), S, L, min(I, L) + 1, I <= L};
+  const Geom<MAT> lat(pd, t, MAT ? pool + pd.cellBase : (pd.ringBase < 0 ? pp_sh : scratch + pd.ringBase), S);
   for (int d = 0; d <= I + L; ++d) {
-    const int ilo = max(0, d - L), nCells = min(I, d) - ilo + 1;
+    int ilo, nCells;
+    lat.diag(d, ilo, nCells);
     const int nItems = nCells * S;
     for (int it = threadIdx.x; it < nItems; it += blockDim.x) {
       const int c = it / S, q = it - c * S, i = ilo + c, r = d - i;
@@ -70,25 +120,28 @@ __global__ __launch_bounds__(PP_THREADS) void k_profile_pair_fwd(DevMachine m, c
       double acc;
       if (r > 0) {
         const double *Pr = P + (long long)(r - 1) * C;
-        acc = lat.at(i, r - 1, 0)[q] + Pr[0];
-        if (i > 0) {
+        const bool up = lat.inside(i, r - 1);
+        acc = up ? lat.at(i, r - 1, 0)[q] + Pr[0] : -INFINITY;
+        if (i > 0 && lat.inside(i - 1, r - 1)) {
           const double *Wd = lat.at(i - 1, r - 1, 1);
           const int a1 = m.inOff[xRow + C];
           for (int a = m.inOff[xRow + 1]; a < a1; ++a)
-            acc = pp_red<MODE>(acc, (Wd[m.inSrc[a]] + m.inW[a]) + Pr[m.eOutTok[m.inEid[a]]]);
+            acc = red<MODE>(acc, (Wd[m.inSrc[a]] + m.inW[a]) + Pr[m.eOutTok[m.inEid[a]]]);
         }
-        const double *Wu = lat.at(i, r - 1, 1);
-        const int a1 = m.inOff[q * K + C];
-        for (int a = m.inOff[q * K + 1]; a < a1; ++a)
-          acc = pp_red<MODE>(acc, (Wu[m.inSrc[a]] + m.inW[a]) + Pr[m.eOutTok[m.inEid[a]]]);
+        if (up) {
+          const double *Wu = lat.at(i, r - 1, 1);
+          const int a1 = m.inOff[q * K + C];
+          for (int a = m.inOff[q * K + 1]; a < a1; ++a)
+            acc = red<MODE>(acc, (Wu[m.inSrc[a]] + m.inW[a]) + Pr[m.eOutTok[m.inEid[a]]]);
+        }
       } else {
         acc = (i == 0 && q == 0) ? 0.0 : -INFINITY;
       }
       lat.at(i, r, 0)[q] = acc;
-      if (i > 0) {
+      if (i > 0 && lat.inside(i - 1, r)) {
         const double *Wl = lat.at(i - 1, r, 1);
         const int a1 = m.inOff[xRow + 1];
-        for (int a = m.inOff[xRow]; a < a1; ++a) acc = pp_red<MODE>(acc, Wl[m.inSrc[a]] + m.inW[a]);
+        for (int a = m.inOff[xRow]; a < a1; ++a) acc = red<MODE>(acc, Wl[m.inSrc[a]] + m.inW[a]);
       }
       lat.at(i, r, 1)[q] = acc;
     }
@@ -104,14 +157,14 @@ __global__ __launch_bounds__(PP_THREADS) void k_profile_pair_fwd(DevMachine m, c
         for (int a = m.inOff[q * K]; a < a1; ++a) {
           const int s = (int)m.inSrc[a];
           if (s >= q) continue;                       // as the token sweeps: a silent self-loop never fires
-          acc = pp_red<MODE>(acc, Wc[s] + m.inW[a]);
+          acc = red<MODE>(acc, Wc[s] + m.inW[a]);
         }
         Wc[q] = acc;
       }
       __syncthreads();
     }
   }
-  if (threadIdx.x == 0) loglike[blockIdx.x] = lat.at(I, L, 1)[S - 1];
+  if (threadIdx.x == 0) loglike[blockIdx.x] = lat.at(I, L, 1)[S - 1];      // (an envelope is connected: (0, 0) and (I, L) are inside)
 }
 
 // Materialised Backward sweep, layer 0 = NB ("from the arrived stage"), layer 1 = WB ("from the waiting stage"):
@@ -122,41 +175,47 @@ __global__ __launch_bounds__(PP_THREADS) void k_profile_pair_fwd(DevMachine m, c
 //                 (+) sum_{silent t: s->d, s < d}            w_t + WB[i][r][d]
 //   NB[i][r][s] = WB[i][r][s] (+) (P[r][0] + NB[i][r+1][s])   (r < L);   loglike = NB[0][0][0]
 // Anti-diagonals from I + L down.  A state's WB is final once its backward level has run; the item that finishes it writes its NB.
-__global__ __launch_bounds__(PP_THREADS) void k_profile_pair_bwd(DevMachine m, const PairProfDesc *__restrict__ descs,
-                                                                 const int *__restrict__ inTok, const double *__restrict__ logP,
-                                                                 double *pool, double *__restrict__ loglike) {
-  const PairProfDesc pd = descs[blockIdx.x];
+// A successor cell outside the geometry contributes nothing.
+template <template <bool> class Geom>
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_bwd(DevMachine m, const typename Geom<true>::Desc *__restrict__ descs, typename Geom<true>::Tables t,
+                                                                    const int *__restrict__ inTok, const double *__restrict__ logP,
+                                                                    double *pool, double *__restrict__ loglike) {
+  const auto pd = descs[blockIdx.x];
   const int S = m.S, K = m.K, C = m.nOut + 1, I = pd.nIn, L = pd.nRows;
   const int *x = inTok + pd.inBase;
   const double *P = logP + pd.rowBase * C;
-  const PairLattice<true> lat{pool + pd.cellBase, S, L, 0, 0};
+  const Geom<true> lat(pd, t, pool + pd.cellBase, S);
   for (int d = I + L; d >= 0; --d) {
-    const int ilo = max(0, d - L), nCells = min(I, d) - ilo + 1;
+    int ilo, nCells;
+    lat.diag(d, ilo, nCells);
     const int nItems = nCells * S;
     for (int it = threadIdx.x; it < nItems; it += blockDim.x) {
       const int c = it / S, s = it - c * S, i = ilo + c, r = d - i;
       const int xRow = i < I ? s * K + x[i] * C : 0;
       const double *Pr = P + (long long)r * C;
+      const bool down = r < L && lat.inside(i, r + 1);
       double v = (i == I && r == L && s == S - 1) ? 0.0 : -INFINITY;
       if (r < L) {
-        if (i < I) {
+        if (i < I && lat.inside(i + 1, r + 1)) {
           const double *Nd = lat.at(i + 1, r + 1, 0);
           const int a1 = m.outOff[xRow + C];
           for (int a = m.outOff[xRow + 1]; a < a1; ++a)
             v = lse2_exact(v, (m.outW[a] + Pr[m.eOutTok[m.outEid[a]]]) + Nd[m.outDst[a]]);
         }
-        const double *Nu = lat.at(i, r + 1, 0);
-        const int a1 = m.outOff[s * K + C];
-        for (int a = m.outOff[s * K + 1]; a < a1; ++a)
-          v = lse2_exact(v, (m.outW[a] + Pr[m.eOutTok[m.outEid[a]]]) + Nu[m.outDst[a]]);
+        if (down) {
+          const double *Nu = lat.at(i, r + 1, 0);
+          const int a1 = m.outOff[s * K + C];
+          for (int a = m.outOff[s * K + 1]; a < a1; ++a)
+            v = lse2_exact(v, (m.outW[a] + Pr[m.eOutTok[m.outEid[a]]]) + Nu[m.outDst[a]]);
+        }
       }
-      if (i < I) {
+      if (i < I && lat.inside(i + 1, r)) {
         const double *Wl = lat.at(i + 1, r, 1);
         const int a1 = m.outOff[xRow + 1];
         for (int a = m.outOff[xRow]; a < a1; ++a) v = lse2_exact(v, Wl[m.outDst[a]] + m.outW[a]);
       }
       lat.at(i, r, 1)[s] = v;
-      lat.at(i, r, 0)[s] = r < L ? lse2_exact(v, Pr[0] + lat.at(i, r + 1, 0)[s]) : v;
+      lat.at(i, r, 0)[s] = down ? lse2_exact(v, Pr[0] + lat.at(i, r + 1, 0)[s]) : v;
     }
     __syncthreads();
     for (int lev = 1; lev < m.nLevB; ++lev) {
@@ -173,7 +232,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_profile_pair_bwd(DevMachine m, c
           v = lse2_exact(v, Wc[t] + m.outW[a]);
         }
         Wc[s] = v;
-        lat.at(i, r, 0)[s] = r < L ? lse2_exact(v, P[(long long)r * C] + lat.at(i, r + 1, 0)[s]) : v;
+        lat.at(i, r, 0)[s] = (r < L && lat.inside(i, r + 1)) ? lse2_exact(v, P[(long long)r * C] + lat.at(i, r + 1, 0)[s]) : v;
       }
       __syncthreads();
     }
@@ -183,92 +242,80 @@ __global__ __launch_bounds__(PP_THREADS) void k_profile_pair_bwd(DevMachine m, c
 
 // Posterior counts.  With both lattices in memory every (cell, edge) term is independent:
 //   count[t] += exp(W_F[i][r][s] - LL + term_t), term_t the edge's summand of WB[i][r][s] above,
-// so the sweep is a flat grid over (pair, group of the pair, (cell, state)).  Per-workgroup partial counts are kept in LDS when the
-// transition table is small and flushed once with atomics; det: both tables hold 64-bit fixed point at 2^-36 (mb_internal.h) --
-// integer adds commute, so the counts are the same bits from call to call.  A pair whose likelihood is -inf adds nothing.
-__global__ __launch_bounds__(256) void k_profile_pair_counts(DevMachine m, const PairProfDesc *__restrict__ descs, int groupsPerPair,
+// so the sweep is a flat grid over (pair, group of the pair, (cell, state)), accumulated by CountsAcc (mb_profile_common.h).  A pair
+// whose likelihood is -inf adds nothing.
+template <template <bool> class Geom>
+__global__ __launch_bounds__(256) void k_profile_pair_counts(DevMachine m, const typename Geom<true>::Desc *__restrict__ descs, typename Geom<true>::Tables t, int groupsPerPair,
                                                              const int *__restrict__ inTok, const double *__restrict__ logP,
                                                              const double *__restrict__ fwdPool, const double *__restrict__ bwdPool,
                                                              long long nTrans, double *__restrict__ counts, int det) {
-  __shared__ double lcount[PP_COUNTS_LDS_MAX];
-  const bool useLds = nTrans <= PP_COUNTS_LDS_MAX;
-  if (useLds) {
-    for (int e = threadIdx.x; e < nTrans; e += blockDim.x) lcount[e] = 0.0;
-    __syncthreads();
-  }
+  __shared__ double lcount[COUNTS_LDS_MAX];
+  const CountsAcc acc(lcount, counts, nTrans, det);
   const int k = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
-  const PairProfDesc pd = descs[k];
+  const auto pd = descs[k];
   const int S = m.S, K = m.K, C = m.nOut + 1, I = pd.nIn, L = pd.nRows;
   const int *x = inTok + pd.inBase;
   const double *P = logP + pd.rowBase * C;
-  const PairLattice<true> F{const_cast<double *>(fwdPool) + pd.cellBase, S, L, 0, 0}, B{const_cast<double *>(bwdPool) + pd.cellBase, S, L, 0, 0};
+  const Geom<true> F(pd, t, const_cast<double *>(fwdPool) + pd.cellBase, S), B(pd, t, const_cast<double *>(bwdPool) + pd.cellBase, S);
   const double LL = F.at(I, L, 1)[S - 1];
-  double *tab = useLds ? lcount : counts;
-  auto add = [&](uint32_t e, double c) {
-    if (c != 0.0) {
-      if (det) atomicAdd((unsigned long long *)tab + e, (unsigned long long)fmin(fmax(c * 68719476736.0 + 0.5, 0.0), 4611686018427387904.0));
-      else atomicAdd(&tab[e], c);
-    }
-  };
   if (LL > -INFINITY) {
-    const long long nItems = (long long)(I + 1) * (L + 1) * S;
+    const long long nItems = F.cells() * S;
     for (long long idx = (long long)group * blockDim.x + threadIdx.x; idx < nItems; idx += (long long)groupsPerPair * blockDim.x) {
       const long long cell = idx / S;
-      const int s = (int)(idx - cell * S), i = (int)(cell / (L + 1)), r = (int)(cell - (long long)i * (L + 1));
+      const int s = (int)(idx - cell * S);
+      int i, r;
+      F.cell(cell, i, r);
       const double f = F.at(i, r, 1)[s] - LL;
       if (!(f > -INFINITY)) continue;
       const int xRow = i < I ? s * K + x[i] * C : 0;
       const double *Pr = P + (long long)r * C;
       if (r < L) {
-        if (i < I) {
+        if (i < I && B.inside(i + 1, r + 1)) {
           const double *Nd = B.at(i + 1, r + 1, 0);
           const int a1 = m.outOff[xRow + C];
           for (int a = m.outOff[xRow + 1]; a < a1; ++a)
-            add(m.outEid[a], exp(f + ((m.outW[a] + Pr[m.eOutTok[m.outEid[a]]]) + Nd[m.outDst[a]])));
+            acc.add(m.outEid[a], exp(f + ((m.outW[a] + Pr[m.eOutTok[m.outEid[a]]]) + Nd[m.outDst[a]])));
         }
-        const double *Nu = B.at(i, r + 1, 0);
-        const int a1 = m.outOff[s * K + C];
-        for (int a = m.outOff[s * K + 1]; a < a1; ++a)
-          add(m.outEid[a], exp(f + ((m.outW[a] + Pr[m.eOutTok[m.outEid[a]]]) + Nu[m.outDst[a]])));
+        if (B.inside(i, r + 1)) {
+          const double *Nu = B.at(i, r + 1, 0);
+          const int a1 = m.outOff[s * K + C];
+          for (int a = m.outOff[s * K + 1]; a < a1; ++a)
+            acc.add(m.outEid[a], exp(f + ((m.outW[a] + Pr[m.eOutTok[m.outEid[a]]]) + Nu[m.outDst[a]])));
+        }
       }
-      if (i < I) {
+      if (i < I && B.inside(i + 1, r)) {
         const double *Wl = B.at(i + 1, r, 1);
         const int a1 = m.outOff[xRow + 1];
-        for (int a = m.outOff[xRow]; a < a1; ++a) add(m.outEid[a], exp(f + (Wl[m.outDst[a]] + m.outW[a])));
+        for (int a = m.outOff[xRow]; a < a1; ++a) acc.add(m.outEid[a], exp(f + (Wl[m.outDst[a]] + m.outW[a])));
       }
       const double *Wc = B.at(i, r, 1);
       const int a1 = m.outOff[s * K + 1];
       for (int a = m.outOff[s * K]; a < a1; ++a) {
         const int t = (int)m.outDst[a];
         if (t <= s) continue;
-        add(m.outEid[a], exp(f + (Wc[t] + m.outW[a])));
+        acc.add(m.outEid[a], exp(f + (Wc[t] + m.outW[a])));
       }
     }
   }
-  if (useLds) {
-    __syncthreads();
-    for (int e = threadIdx.x; e < nTrans; e += blockDim.x)
-      if (det ? ((const unsigned long long *)lcount)[e] != 0ull : lcount[e] != 0.0) {
-        if (det) atomicAdd((unsigned long long *)counts + e, ((const unsigned long long *)lcount)[e]);
-        else atomicAdd(&counts[e], lcount[e]);
-      }
-  }
+  acc.flush();
 }
 
 // Viterbi traceback over a materialised max lattice, one lane per pair: from W[I][L][S-1] back to N[0][0][0], taking at every cell
 // the first candidate (in the fill's order) whose value equals the cell.  Edges go start -> end into the pair's slot
 // (profile_pair_path_bound entries) with the row each fired at: an emitting edge the row it consumed, an output-less edge the number
 // of rows consumed before it.  len = -1: no finite path, -2: the slot was too small, -3: no candidate matched (a corrupt matrix).
-__global__ void k_profile_pair_traceback(DevMachine m, const PairProfDesc *__restrict__ descs, int n, const int *__restrict__ inTok,
+// A candidate whose source cell lies outside the geometry is left out: it is -inf, and the cells on the path are finite.
+template <template <bool> class Geom>
+__global__ void k_profile_pair_traceback(DevMachine m, const typename Geom<true>::Desc *__restrict__ descs, typename Geom<true>::Tables t, int n, const int *__restrict__ inTok,
                                          const double *__restrict__ logP, const double *__restrict__ pool, uint32_t *edges,
                                          int32_t *rows, long long *len) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
-  const PairProfDesc pd = descs[k];
+  const auto pd = descs[k];
   const int S = m.S, K = m.K, C = m.nOut + 1, I = pd.nIn, L = pd.nRows;
   const int *x = inTok + pd.inBase;
   const double *P = logP + pd.rowBase * C;
-  const PairLattice<true> lat{const_cast<double *>(pool) + pd.cellBase, S, L, 0, 0};
+  const Geom<true> lat(pd, t, const_cast<double *>(pool) + pd.cellBase, S);
   uint32_t *pe = edges + pd.pathBase;
   int32_t *pr = rows + pd.pathBase;
   int i = I, r = L, q = S - 1, layer = 1;
@@ -283,7 +330,7 @@ __global__ void k_profile_pair_traceback(DevMachine m, const PairProfDesc *__res
       const double cur = W[q];
       if (lat.at(i, r, 0)[q] == cur) { layer = 0; continue; }
       int ni = i;
-      if (i > 0) {
+      if (i > 0 && lat.inside(i - 1, r)) {
         const double *Wl = lat.at(i - 1, r, 1);
         a = m.inOff[xRow];
         for (const int a1 = m.inOff[xRow + 1]; a < a1; ++a)
@@ -304,15 +351,16 @@ __global__ void k_profile_pair_traceback(DevMachine m, const PairProfDesc *__res
       if (r == 0) { if (i != 0 || q != 0) { len[k] = -3; return; } break; }
       const double *Pr = P + (long long)(r - 1) * C;
       const double cur = lat.at(i, r, 0)[q];
-      if (lat.at(i, r - 1, 0)[q] + Pr[0] == cur) { --r; continue; }
+      const bool up = lat.inside(i, r - 1);
+      if (up && lat.at(i, r - 1, 0)[q] + Pr[0] == cur) { --r; continue; }
       int ni = i;
-      if (i > 0) {
+      if (i > 0 && lat.inside(i - 1, r - 1)) {
         const double *Wd = lat.at(i - 1, r - 1, 1);
         a = m.inOff[xRow + 1];
         for (const int a1 = m.inOff[xRow + C]; a < a1; ++a)
           if ((Wd[m.inSrc[a]] + m.inW[a]) + Pr[m.eOutTok[m.inEid[a]]] == cur) { found = (int)m.inSrc[a]; ni = i - 1; break; }
       }
-      if (found < 0) {
+      if (found < 0 && up) {
         const double *Wu = lat.at(i, r - 1, 1);
         a = m.inOff[q * K + 1];
         for (const int a1 = m.inOff[q * K + C]; a < a1; ++a)
@@ -332,51 +380,86 @@ __global__ void k_profile_pair_traceback(DevMachine m, const PairProfDesc *__res
   len[k] = cnt;
 }
 
-static int pp_threads(long long maxItems) { return (int)std::min<long long>(PP_THREADS, std::max<long long>(64, (maxItems + 63) / 64 * 64)); }
-
-int launch_profile_pair_fwd(const mb_machine *m, int mode, bool mat, const PairProfDesc *d, int n, size_t lds, long long maxItems,
-                            const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st) {
+// The launchers: each sweep once over a geometry, and the two overloads of the headers that name one.
+template <template <bool> class Geom>
+static int pair_fwd(const mb_machine *m, int mode, bool mat, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, size_t lds, long long maxItems,
+                    const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  constexpr bool ENV = Geom<true>::ENV;
   if (n <= 0) return 0;
   if (mat) lds = 0;
   static size_t ldsAllowed = 64 * 1024;      // beyond the default the kernels must be told; asked for once, and only when a ring needs it
   if (lds > ldsAllowed) {
-    if (!hip_ok(hipFuncSetAttribute((const void *)&k_profile_pair_fwd<MB_FORWARD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PP_LDS_MAX),
-                "k_profile_pair_fwd: raising the LDS limit") ||
-        !hip_ok(hipFuncSetAttribute((const void *)&k_profile_pair_fwd<MB_VITERBI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PP_LDS_MAX),
-                "k_profile_pair_fwd: raising the LDS limit")) return 1;
-    ldsAllowed = PP_LDS_MAX;
+    const char *what = ENV ? "k_profile_pair_env_fwd: raising the LDS limit" : "k_profile_pair_fwd: raising the LDS limit";
+    if (!hip_ok(hipFuncSetAttribute((const void *)&k_profile_pair_fwd<MB_FORWARD, false, Geom>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what) ||
+        !hip_ok(hipFuncSetAttribute((const void *)&k_profile_pair_fwd<MB_VITERBI, false, Geom>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what)) return 1;
+    ldsAllowed = SWEEP_LDS_MAX;
   }
-  const dim3 g(n), b(pp_threads(maxItems));
+  const dim3 g(n), b(sweep_threads(maxItems));
   if (mode == MB_VITERBI) {
-    if (mat) k_profile_pair_fwd<MB_VITERBI, true><<<g, b, 0, st>>>(m->dev, d, inTok, logP, pool, scratch, loglike);
-    else k_profile_pair_fwd<MB_VITERBI, false><<<g, b, lds, st>>>(m->dev, d, inTok, logP, pool, scratch, loglike);
+    if (mat) k_profile_pair_fwd<MB_VITERBI, true, Geom><<<g, b, 0, st>>>(m->dev, d, t, inTok, logP, pool, scratch, loglike);
+    else k_profile_pair_fwd<MB_VITERBI, false, Geom><<<g, b, lds, st>>>(m->dev, d, t, inTok, logP, pool, scratch, loglike);
   } else {
-    if (mat) k_profile_pair_fwd<MB_FORWARD, true><<<g, b, 0, st>>>(m->dev, d, inTok, logP, pool, scratch, loglike);
-    else k_profile_pair_fwd<MB_FORWARD, false><<<g, b, lds, st>>>(m->dev, d, inTok, logP, pool, scratch, loglike);
+    if (mat) k_profile_pair_fwd<MB_FORWARD, true, Geom><<<g, b, 0, st>>>(m->dev, d, t, inTok, logP, pool, scratch, loglike);
+    else k_profile_pair_fwd<MB_FORWARD, false, Geom><<<g, b, lds, st>>>(m->dev, d, t, inTok, logP, pool, scratch, loglike);
   }
-  return hip_ok(hipGetLastError(), "k_profile_pair_fwd") ? 0 : 1;
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_pair_env_fwd" : "k_profile_pair_fwd") ? 0 : 1;
+}
+int launch_profile_pair_fwd(const mb_machine *m, int mode, bool mat, const PairProfDesc *d, int n, size_t lds, long long maxItems, const int *inTok,
+                            const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  return pair_fwd<FullGeom>(m, mode, mat, d, {}, n, lds, maxItems, inTok, logP, pool, scratch, loglike, st);
+}
+int launch_profile_pair_fwd(const mb_machine *m, int mode, bool mat, const PairEnvDesc *d, const PairEnvTables &t, int n, size_t lds, long long maxItems,
+                            const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  return pair_fwd<EnvGeom>(m, mode, mat, d, t, n, lds, maxItems, inTok, logP, pool, scratch, loglike, st);
 }
 
-int launch_profile_pair_bwd(const mb_machine *m, const PairProfDesc *d, int n, long long maxItems, const int *inTok, const double *logP,
-                            double *pool, double *loglike, hipStream_t st) {
+template <template <bool> class Geom>
+static int pair_bwd(const mb_machine *m, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, long long maxItems, const int *inTok,
+                    const double *logP, double *pool, double *loglike, hipStream_t st) {
   if (n <= 0) return 0;
-  k_profile_pair_bwd<<<dim3(n), dim3(pp_threads(maxItems)), 0, st>>>(m->dev, d, inTok, logP, pool, loglike);
-  return hip_ok(hipGetLastError(), "k_profile_pair_bwd") ? 0 : 1;
+  k_profile_pair_bwd<Geom><<<dim3(n), dim3(sweep_threads(maxItems)), 0, st>>>(m->dev, d, t, inTok, logP, pool, loglike);
+  return hip_ok(hipGetLastError(), Geom<true>::ENV ? "k_profile_pair_env_bwd" : "k_profile_pair_bwd") ? 0 : 1;
+}
+int launch_profile_pair_bwd(const mb_machine *m, const PairProfDesc *d, int n, long long maxItems, const int *inTok, const double *logP, double *pool,
+                            double *loglike, hipStream_t st) {
+  return pair_bwd<FullGeom>(m, d, {}, n, maxItems, inTok, logP, pool, loglike, st);
+}
+int launch_profile_pair_bwd(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, long long maxItems, const int *inTok, const double *logP,
+                            double *pool, double *loglike, hipStream_t st) {
+  return pair_bwd<EnvGeom>(m, d, t, n, maxItems, inTok, logP, pool, loglike, st);
 }
 
+template <template <bool> class Geom>
+static int pair_counts(const mb_machine *m, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, int groupsPerPair, const int *inTok,
+                       const double *logP, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
+  if (n <= 0 || m->nTrans <= 0) return 0;
+  k_profile_pair_counts<Geom><<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(m->dev, d, t, groupsPerPair, inTok, logP, fwdPool, bwdPool, m->nTrans, counts,
+                                                                                                 g_deterministic ? 1 : 0);
+  return hip_ok(hipGetLastError(), Geom<true>::ENV ? "k_profile_pair_env_counts" : "k_profile_pair_counts") ? 0 : 1;
+}
 int launch_profile_pair_counts(const mb_machine *m, const PairProfDesc *d, int n, int groupsPerPair, const int *inTok, const double *logP,
                                const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
-  if (n <= 0 || m->nTrans <= 0) return 0;
-  k_profile_pair_counts<<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(m->dev, d, groupsPerPair, inTok, logP, fwdPool, bwdPool,
-                                                                                               m->nTrans, counts, g_deterministic ? 1 : 0);
-  return hip_ok(hipGetLastError(), "k_profile_pair_counts") ? 0 : 1;
+  return pair_counts<FullGeom>(m, d, {}, n, groupsPerPair, inTok, logP, fwdPool, bwdPool, counts, st);
+}
+int launch_profile_pair_counts(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, int groupsPerPair, const int *inTok, const double *logP,
+                               const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
+  return pair_counts<EnvGeom>(m, d, t, n, groupsPerPair, inTok, logP, fwdPool, bwdPool, counts, st);
 }
 
-int launch_profile_pair_traceback(const mb_machine *m, const PairProfDesc *d, int n, const int *inTok, const double *logP,
-                                  const double *pool, uint32_t *edges, int32_t *rows, long long *len, hipStream_t st) {
+template <template <bool> class Geom>
+static int pair_traceback(const mb_machine *m, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, const int *inTok, const double *logP,
+                          const double *pool, uint32_t *edges, int32_t *rows, long long *len, hipStream_t st) {
   if (n <= 0) return 0;
-  k_profile_pair_traceback<<<(n + 63) / 64, 64, 0, st>>>(m->dev, d, n, inTok, logP, pool, edges, rows, len);
-  return hip_ok(hipGetLastError(), "k_profile_pair_traceback") ? 0 : 1;
+  k_profile_pair_traceback<Geom><<<(n + 63) / 64, 64, 0, st>>>(m->dev, d, t, n, inTok, logP, pool, edges, rows, len);
+  return hip_ok(hipGetLastError(), Geom<true>::ENV ? "k_profile_pair_env_traceback" : "k_profile_pair_traceback") ? 0 : 1;
+}
+int launch_profile_pair_traceback(const mb_machine *m, const PairProfDesc *d, int n, const int *inTok, const double *logP, const double *pool,
+                                  uint32_t *edges, int32_t *rows, long long *len, hipStream_t st) {
+  return pair_traceback<FullGeom>(m, d, {}, n, inTok, logP, pool, edges, rows, len, st);
+}
+int launch_profile_pair_traceback(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, const int *inTok, const double *logP, const double *pool,
+                                  uint32_t *edges, int32_t *rows, long long *len, hipStream_t st) {
+  return pair_traceback<EnvGeom>(m, d, t, n, inTok, logP, pool, edges, rows, len, st);
 }
 
 }  // namespace mb

@@ -9,15 +9,11 @@
 
 namespace mb {
 
-struct PairEnvDesc {
-  long long inBase, rowBase;   // as PairProfDesc
-  long long cellBase;          // offset (doubles) of this pair's compact lattice in a matrix pool
-  long long pathBase;          // offset of this pair's slot in the traceback buffers
-  long long ringBase;          // rolling sweeps: offset (doubles) of this pair's ring in the global scratch buffer, -1 = LDS
+// a pair's descriptor and what its envelope adds
+struct PairEnvDesc : PairProfDesc {      // cellBase: of this pair's compact lattice
   long long envBase;           // first of this pair's nRows + 1 entries in envStart / envEnd / envOff
   long long diagBase;          // first of this pair's nIn + nRows + 1 entries in diagLo / diagCnt
   long long nCells;            // envelope cells of the pair (off[nRows + 1])
-  int nIn, nRows;
   int M;                       // the largest cell count of any anti-diagonal of the pair
 };
 
@@ -33,14 +29,15 @@ inline long long profile_pair_env_ring(int S, long long M) { return 3 * 2 * M * 
 // dynamic LDS of the ring when it fits (0: a slice of the global scratch buffer)
 size_t profile_pair_env_lds_bytes(int S, long long M);
 
-int launch_profile_pair_env_fwd(const mb_machine *m, int mode, bool mat, const PairEnvDesc *d, PairEnvTables t, int n, size_t lds,
-                                long long maxItems, const int *inTok, const double *logP, double *pool, double *scratch, double *loglike,
-                                hipStream_t st);
-int launch_profile_pair_env_bwd(const mb_machine *m, const PairEnvDesc *d, PairEnvTables t, int n, long long maxItems, const int *inTok,
-                                const double *logP, double *pool, double *loglike, hipStream_t st);
-int launch_profile_pair_env_counts(const mb_machine *m, const PairEnvDesc *d, PairEnvTables t, int n, int groupsPerPair, const int *inTok,
-                                   const double *logP, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
-int launch_profile_pair_env_traceback(const mb_machine *m, const PairEnvDesc *d, PairEnvTables t, int n, const int *inTok,
-                                      const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len, hipStream_t st);
+
+// the launchers of mb_profile_pair.h over pairs under an envelope (lds, maxItems: of the envelope rings)
+int launch_profile_pair_fwd(const mb_machine *m, int mode, bool mat, const PairEnvDesc *d, const PairEnvTables &t, int n, size_t lds, long long maxItems,
+                            const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st);
+int launch_profile_pair_bwd(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, long long maxItems, const int *inTok, const double *logP,
+                            double *pool, double *loglike, hipStream_t st);
+int launch_profile_pair_counts(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, int groupsPerPair, const int *inTok, const double *logP,
+                               const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
+int launch_profile_pair_traceback(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, const int *inTok, const double *logP, const double *pool,
+                                  uint32_t *edges, int32_t *rows, long long *len, hipStream_t st);
 
 }  // namespace mb

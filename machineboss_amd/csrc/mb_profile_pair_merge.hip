@@ -18,23 +18,14 @@
 // edge loop runs over planes -- (I + L + 1)(nLevF + 1) barriers per pair.  The rolling sweeps keep a ring of three diagonals of N, W
 // and X, 3 (3 nCols + 2)(min(I, L) + 1) S doubles, in LDS when that fits 160 KiB, else in the pair's slice of a global scratch
 // buffer; the materialised ones keep only X there.  Cells are fp64, the sums the exact log-sum-exp.
-#include <algorithm>
-
-#include "mb_device_math.h"
+#include "mb_profile_common.h"
 #include "mb_profile_pair_merge.h"
 
 namespace mb {
 
-template <int MODE>
-__device__ __forceinline__ double ppm_red(double a, double b) { return MODE == MB_VITERBI ? dmax(a, b) : lse2_exact(a, b); }
-
-static constexpr int PPM_THREADS = 1024;
-static constexpr size_t PPM_LDS_MAX = 160 * 1024;
-static constexpr int PPM_COUNTS_LDS_MAX = 8192;
-
 size_t profile_pair_merge_lds_bytes(int S, int nCols, long long nIn, long long nRows, bool mat) {
   const double b = (double)profile_pair_merge_ring(S, nCols, nIn, nRows, mat) * sizeof(double);
-  return b <= (double)PPM_LDS_MAX ? (size_t)b : 0;
+  return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
 }
 
 // Where cell (i, r) lives.  nw(i, r, layer): its N (layer 0) or W (layer 1), nCols + 1 planes of S states -- the materialised
@@ -61,9 +52,9 @@ struct PairMergeLattice {
 // first, then the input-only edges, then the silent edges, each in `incoming` order; X and the end the planes ascending -- the
 // order k_profile_pair_merge_traceback re-enumerates.
 template <int MODE, bool MAT>
-__global__ __launch_bounds__(PPM_THREADS) void k_profile_pair_merge_fwd(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
-                                                                        const int *__restrict__ inTok, const double *__restrict__ logP,
-                                                                        double *pool, double *scratch, double *__restrict__ loglike) {
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_fwd(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+                                                                          const int *__restrict__ inTok, const double *__restrict__ logP,
+                                                                          double *pool, double *scratch, double *__restrict__ loglike) {
   extern __shared__ double ppm_sh[];
   const PairProfDesc pd = descs[blockIdx.x];
   const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
@@ -84,25 +75,25 @@ __global__ __launch_bounds__(PPM_THREADS) void k_profile_pair_merge_fwd(DevMachi
         const double *Np = lat.nw(i, r - 1, 0);
         if (p == 0) {
           acc = Np[q] + w;
-          for (int k = 1; k < PL; ++k) acc = ppm_red<MODE>(acc, Np[k * S + q] + w);
+          for (int k = 1; k < PL; ++k) acc = red<MODE>(acc, Np[k * S + q] + w);
         } else if (w > -INFINITY) {                          // (a column the row rules out is skipped as a whole)
           const int tok = mm.colTok[p - 1];
           acc = Np[p * S + q] + w;
           if (i > 0) {
             const double *Xd = lat.xv(i - 1, r - 1) + (p - 1) * S;
             const int a1 = m.inOff[xRow + tok + 1];
-            for (int a = m.inOff[xRow + tok]; a < a1; ++a) acc = ppm_red<MODE>(acc, (Xd[m.inSrc[a]] + m.inW[a]) + w);
+            for (int a = m.inOff[xRow + tok]; a < a1; ++a) acc = red<MODE>(acc, (Xd[m.inSrc[a]] + m.inW[a]) + w);
           }
           const double *Xu = lat.xv(i, r - 1) + (p - 1) * S;
           const int a1 = m.inOff[q * K + tok + 1];
-          for (int a = m.inOff[q * K + tok]; a < a1; ++a) acc = ppm_red<MODE>(acc, (Xu[m.inSrc[a]] + m.inW[a]) + w);
+          for (int a = m.inOff[q * K + tok]; a < a1; ++a) acc = red<MODE>(acc, (Xu[m.inSrc[a]] + m.inW[a]) + w);
         }
       }
       lat.nw(i, r, 0)[pq] = acc;
       if (i > 0) {
         const double *Wl = lat.nw(i - 1, r, 1) + p * S;
         const int a1 = m.inOff[xRow + 1];
-        for (int a = m.inOff[xRow]; a < a1; ++a) acc = ppm_red<MODE>(acc, Wl[m.inSrc[a]] + m.inW[a]);
+        for (int a = m.inOff[xRow]; a < a1; ++a) acc = red<MODE>(acc, Wl[m.inSrc[a]] + m.inW[a]);
       }
       lat.nw(i, r, 1)[pq] = acc;
     }
@@ -118,7 +109,7 @@ __global__ __launch_bounds__(PPM_THREADS) void k_profile_pair_merge_fwd(DevMachi
         for (int a = m.inOff[q * K]; a < a1; ++a) {
           const int s = (int)m.inSrc[a];
           if (s >= q) continue;                       // as the token sweeps: a silent self-loop never fires
-          acc = ppm_red<MODE>(acc, Wc[s] + m.inW[a]);
+          acc = red<MODE>(acc, Wc[s] + m.inW[a]);
         }
         Wc[q] = acc;
       }
@@ -131,7 +122,7 @@ __global__ __launch_bounds__(PPM_THREADS) void k_profile_pair_merge_fwd(DevMachi
         const double *Wc = lat.nw(i, d - i, 1) + s;
         double acc = Wc[0];                             // plane 0 is never the excluded one
         for (int k = 1; k < PL; ++k)
-          if (k != col) acc = ppm_red<MODE>(acc, Wc[k * S]);
+          if (k != col) acc = red<MODE>(acc, Wc[k * S]);
         lat.xv(i, d - i)[cs] = acc;
       }
       __syncthreads();
@@ -140,7 +131,7 @@ __global__ __launch_bounds__(PPM_THREADS) void k_profile_pair_merge_fwd(DevMachi
   if (threadIdx.x == 0) {
     const double *We = lat.nw(I, L, 1) + S - 1;
     double acc = We[0];
-    for (int p = 1; p < PL; ++p) acc = ppm_red<MODE>(acc, We[p * S]);
+    for (int p = 1; p < PL; ++p) acc = red<MODE>(acc, We[p * S]);
     loglike[blockIdx.x] = acc;
   }
 }
@@ -157,9 +148,9 @@ __global__ __launch_bounds__(PPM_THREADS) void k_profile_pair_merge_fwd(DevMachi
 // column, state) -- the mirror of the Forward's X -- so the edge loops do not run over planes; it lives in the ring (one diagonal of
 // it, the cell by its place on the diagonal).  A state's WB is final once its backward level has run; the item that finishes it
 // writes its NB.
-__global__ __launch_bounds__(PPM_THREADS) void k_profile_pair_merge_bwd(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
-                                                                        const int *__restrict__ inTok, const double *__restrict__ logP,
-                                                                        double *pool, double *scratch, double *__restrict__ loglike) {
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_bwd(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+                                                                          const int *__restrict__ inTok, const double *__restrict__ logP,
+                                                                          double *pool, double *scratch, double *__restrict__ loglike) {
   extern __shared__ double ppm_sh[];
   const PairProfDesc pd = descs[blockIdx.x];
   const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
@@ -248,20 +239,15 @@ __global__ __launch_bounds__(PPM_THREADS) void k_profile_pair_merge_bwd(DevMachi
 // Posterior counts.  With both lattices in memory every (cell, plane, edge) term is independent:
 //   count[t] += exp(W_F[i][r][k][s] - LL + term_t), term_t the edge's summand of WB[i][r][k][s] above (through T for the emitting
 //   edges: every column c != k),
-// so the sweep is a flat grid over (pair, group of the pair, (cell, plane, state)).  Per-workgroup partial counts are kept in LDS when
-// the transition table is small and flushed once with atomics; det: both tables hold 64-bit fixed point at 2^-36 (mb_internal.h) --
-// integer adds commute, so the counts are the same bits from call to call.  A pair whose likelihood is -inf adds nothing.
+// so the sweep is a flat grid over (pair, group of the pair, (cell, plane, state)), accumulated by CountsAcc (mb_profile_common.h).
+// A pair whose likelihood is -inf adds nothing.
 __global__ __launch_bounds__(256) void k_profile_pair_merge_counts(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
                                                                    int groupsPerPair, const int *__restrict__ inTok,
                                                                    const double *__restrict__ logP, const double *__restrict__ fwdPool,
                                                                    const double *__restrict__ bwdPool, long long nTrans,
                                                                    double *__restrict__ counts, int det) {
-  __shared__ double lcount[PPM_COUNTS_LDS_MAX];
-  const bool useLds = nTrans <= PPM_COUNTS_LDS_MAX;
-  if (useLds) {
-    for (int e = threadIdx.x; e < nTrans; e += blockDim.x) lcount[e] = 0.0;
-    __syncthreads();
-  }
+  __shared__ double lcount[COUNTS_LDS_MAX];
+  const CountsAcc acc(lcount, counts, nTrans, det);
   const int pair = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
   const PairProfDesc pd = descs[pair];
   const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
@@ -275,13 +261,6 @@ __global__ __launch_bounds__(256) void k_profile_pair_merge_counts(DevMachine m,
     LL = We[0];
     for (int p = 1; p < PL; ++p) LL = lse2_exact(LL, We[p * S]);
   }
-  double *tab = useLds ? lcount : counts;
-  auto add = [&](uint32_t e, double c) {
-    if (c != 0.0) {
-      if (det) atomicAdd((unsigned long long *)tab + e, (unsigned long long)fmin(fmax(c * 68719476736.0 + 0.5, 0.0), 4611686018427387904.0));
-      else atomicAdd(&tab[e], c);
-    }
-  };
   if (LL > -INFINITY) {
     const long long PS = (long long)PL * S, nItems = (long long)(I + 1) * (L + 1) * PS;
     for (long long idx = (long long)group * blockDim.x + threadIdx.x; idx < nItems; idx += (long long)groupsPerPair * blockDim.x) {
@@ -299,35 +278,28 @@ __global__ __launch_bounds__(256) void k_profile_pair_merge_counts(DevMachine m,
           if (i < I) {
             const double *Nd = B.nw(i + 1, r + 1, 0) + col * S;
             const int a1 = m.outOff[xRow + tok + 1];
-            for (int a = m.outOff[xRow + tok]; a < a1; ++a) add(m.outEid[a], exp(f + ((m.outW[a] + pc) + Nd[m.outDst[a]])));
+            for (int a = m.outOff[xRow + tok]; a < a1; ++a) acc.add(m.outEid[a], exp(f + ((m.outW[a] + pc) + Nd[m.outDst[a]])));
           }
           const double *Nu = B.nw(i, r + 1, 0) + col * S;
           const int a1 = m.outOff[s * K + tok + 1];
-          for (int a = m.outOff[s * K + tok]; a < a1; ++a) add(m.outEid[a], exp(f + ((m.outW[a] + pc) + Nu[m.outDst[a]])));
+          for (int a = m.outOff[s * K + tok]; a < a1; ++a) acc.add(m.outEid[a], exp(f + ((m.outW[a] + pc) + Nu[m.outDst[a]])));
         }
       }
       if (i < I) {
         const double *Wl = B.nw(i + 1, r, 1) + k * S;
         const int a1 = m.outOff[xRow + 1];
-        for (int a = m.outOff[xRow]; a < a1; ++a) add(m.outEid[a], exp(f + (Wl[m.outDst[a]] + m.outW[a])));
+        for (int a = m.outOff[xRow]; a < a1; ++a) acc.add(m.outEid[a], exp(f + (Wl[m.outDst[a]] + m.outW[a])));
       }
       const double *Wc = B.nw(i, r, 1) + k * S;
       const int a1 = m.outOff[s * K + 1];
       for (int a = m.outOff[s * K]; a < a1; ++a) {
         const int t = (int)m.outDst[a];
         if (t <= s) continue;
-        add(m.outEid[a], exp(f + (Wc[t] + m.outW[a])));
+        acc.add(m.outEid[a], exp(f + (Wc[t] + m.outW[a])));
       }
     }
   }
-  if (useLds) {
-    __syncthreads();
-    for (int e = threadIdx.x; e < nTrans; e += blockDim.x)
-      if (det ? ((const unsigned long long *)lcount)[e] != 0ull : lcount[e] != 0.0) {
-        if (det) atomicAdd((unsigned long long *)counts + e, ((const unsigned long long *)lcount)[e]);
-        else atomicAdd(&counts[e], lcount[e]);
-      }
-  }
+  acc.flush();
 }
 
 // Viterbi traceback over a materialised max lattice, one lane per pair: from the first plane that attains the score at
@@ -435,8 +407,6 @@ __global__ void k_profile_pair_merge_traceback(DevMachine m, MergeMap mm, const 
   len[pair] = cnt;
 }
 
-static int ppm_threads(long long maxItems) { return (int)std::min<long long>(PPM_THREADS, std::max<long long>(64, (maxItems + 63) / 64 * 64)); }
-
 // beyond the default 64 KiB the kernels must be told; asked for once, and only when a ring needs it
 static bool ppm_allow_lds(size_t lds) {
   static size_t ldsAllowed = 64 * 1024;
@@ -445,8 +415,8 @@ static bool ppm_allow_lds(size_t lds) {
                       (const void *)&k_profile_pair_merge_fwd<MB_FORWARD, true>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, true>,
                       (const void *)&k_profile_pair_merge_bwd};
   for (const void *k : ks)
-    if (!hip_ok(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PPM_LDS_MAX), "k_profile_pair_merge: raising the LDS limit")) return false;
-  ldsAllowed = PPM_LDS_MAX;
+    if (!hip_ok(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), "k_profile_pair_merge: raising the LDS limit")) return false;
+  ldsAllowed = SWEEP_LDS_MAX;
   return true;
 }
 
@@ -455,7 +425,7 @@ int launch_profile_pair_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bo
                                   double *loglike, hipStream_t st) {
   if (n <= 0) return 0;
   if (!ppm_allow_lds(lds)) return 1;
-  const dim3 g(n), b(ppm_threads(maxItems));
+  const dim3 g(n), b(sweep_threads(maxItems));
   if (mode == MB_VITERBI) {
     if (mat) k_profile_pair_merge_fwd<MB_VITERBI, true><<<g, b, lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
     else k_profile_pair_merge_fwd<MB_VITERBI, false><<<g, b, lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
@@ -470,7 +440,7 @@ int launch_profile_pair_merge_bwd(const mb_machine *m, MergeMap mm, const PairPr
                                   const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st) {
   if (n <= 0) return 0;
   if (!ppm_allow_lds(lds)) return 1;
-  k_profile_pair_merge_bwd<<<dim3(n), dim3(ppm_threads(maxItems)), lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
+  k_profile_pair_merge_bwd<<<dim3(n), dim3(sweep_threads(maxItems)), lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
   return hip_ok(hipGetLastError(), "k_profile_pair_merge_bwd") ? 0 : 1;
 }
 

@@ -1,4 +1,4 @@
-"""GPU tests of the two-tape profile sweeps under an envelope (mb_profile_pair_env.hip; docs/profile_tapes.md, "Pairs under an
+"""GPU tests of the two-tape profile sweeps under an envelope (mb_profile_pair.hip, EnvGeom; docs/profile_tapes.md, "Pairs under an
 envelope").  The reference is profile.PairProfileDP(env=...) and the bounds are those of pairprofilehelpers: log values 1e-9 relative
 to max(1, |value|) with -inf exact; counts >= 1e-3 at 1e-6 relative, smaller ones at 1e-9 + 1e-6 x count; Viterbi scores and cells
 at 1e-12; paths and rows equal.  test_profile_pair_env_host.py holds the same builders to their liveness conditions on the CPU."""
