@@ -239,6 +239,34 @@ mb_profile_pairs *mb_profile_pairs_create_merged(mb_machine *m, int64_t nPairs, 
 int mb_profile_pair_fill_merged(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows,
                                 int32_t nCols, const int32_t *colTok, double *cellsOut);
 
+/* Pairs of profiles (`--generate-csv A.csv` beside `--recognize-csv B.csv`): a machine WITH an input alphabet between an input
+ * profile and an output profile -- the semantics of compose(A.machine(), compose(M, transpose(B.machine()))) with both tapes empty,
+ * swept natively over (K + 1) x (rows + 1) x 3 x nStates along anti-diagonals (mb_profile_two.hip; docs/profile_tapes.md, "Pairs
+ * of profiles").  Pair k = rows inOff[k]..inOff[k+1) of logA (rows of nInTok + 1 doubles, column 0 = the blank, column a = input
+ * token a) and rows rowOff[k]..rowOff[k+1) of logB (rows as mb_profiles_create).  Layer 0 (N) = arrived at (i, row), where alone
+ * the output blank may fire; layer 1 (W) = after the machine's output-less moves there; layer 2 (Z) = committed to wait for the next
+ * input row, where alone the input blank may fire and from which alone the input-reading edges leave.  Viterbi keeps the first
+ * maximum: into N the output blank, then the match edges, then the output-only edges; into W "no move", then the input-only edges,
+ * then the silent edges; into Z "W", then the input blank; edges of a kind in `incoming` order (input token ascending, then output
+ * token).  Paths are the machine's global edge ids, start -> end; pathRow (may be NULL) is the output row an emitting edge
+ * consumed, for an output-less edge the number of output rows consumed before it; pathInRow (may be NULL) is the same on the input
+ * tape -- input blanks advance it without an edge.  A pair whose score is -inf gets an empty path and adds nothing to the counts;
+ * blanks on either tape are not edges.  pathCap must hold the sum of mb_profile_pair_path_bound(m, K, rows) over the pairs.  Counts
+ * with MB_DETERMINISTIC=1 go through 64-bit fixed point and are the same bits from call to call.  Materialised lattices:
+ * cells[(((i*(nRows+1)) + row)*3 + layer)*nStates + state]; mb_profile_two_fill: cellsOut[(nIn+1)*(nRows+1)*3*nStates], mode
+ * MB_FORWARD / MB_VITERBI / MB_BACKWARD (Backward: layer 0 = from the arrived stage, 2 = from the committed stage).  There are no
+ * envelopes and no CTC-merged form.  Errors, before anything is launched: "two-profile sweeps need a machine with an input
+ * alphabet", NaN / +inf weights in either table, a pathCap below the bound, a lattice beyond the memory budget on its own. */
+typedef struct mb_profile_twos mb_profile_twos;
+mb_profile_twos *mb_profile_twos_create(mb_machine *m, int64_t nPairs, const double *logA, const int64_t *inOff, const double *logB,
+                                        const int64_t *rowOff);
+void mb_profile_twos_destroy(mb_profile_twos *p);
+int mb_profile_twos_forward(mb_profile_twos *p, int flags /* MB_ROLLING | MB_MATERIALISE */, double *loglike);
+int mb_profile_twos_viterbi(mb_profile_twos *p, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow,
+                            int32_t *pathInRow, int64_t pathCap);
+int mb_profile_twos_counts(mb_profile_twos *p, double *counts, double *loglikeSum, double *loglike);
+int mb_profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, double *cellsOut);
+
 /* ---- prefix search: imputing the input tape (--prefix-decode / --prefix-encode / --random-encode) -------------------------------
  * The node fill of the reference's PrefixTree (src/ctc.cpp:25-88) on the device, the tree and its heap on the host
  * (docs/decoding.md).  An mb_prefix holds nSeq searches (output sequence k = outTok[outOff[k]..outOff[k+1]), tokens 1..nOutTok)

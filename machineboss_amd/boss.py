@@ -3,7 +3,7 @@
     python -m machineboss_amd.boss MACHINE.json [--preset NAME] [-P params.json] [-F funcs.json] [-N constraints.json]
            [-D seqpairs.json] [--input-chars S] [--output-chars S] [--input-fasta F] [--output-fasta F]
            [--input-json F] [--output-json F] [--use-defaults] [-L] [-V] [-A] [-C] [-T] [-R width]
-           [--generate-json F] [--recognize-csv F [--prefix-decode] [--viterbi-decode] [--profile-band N]]
+           [--generate-json F] [--generate-csv F] [--recognize-csv F [--prefix-decode] [--viterbi-decode] [--profile-band N]]
            [--recognize-merge-csv F [--viterbi-decode]]
            [--prefix-decode] [--prefix-encode] [--prefix-backtrack N] [--viterbi-decode] [--viterbi-encode]
            [--random-encode] [--seed N] [--decode-backend device|numpy] [--decode-nodes N]
@@ -24,6 +24,10 @@ imputed (prefixtree.ProfilePrefixDP, k_prefix_fill_profile in mb_prefix.hip; doc
 repeated in consecutive rows is one symbol, and only a blank separates two equal symbols.  It goes wherever ``--recognize-csv``
 goes except with ``--prefix-decode`` (profile.MergedProfileDP, mb_profile_merge.hip; docs/profile_tapes.md); the prefix search
 against a merged profile is ``prefixDecodeProfile(..., merge=True)`` (k_prefix_fill_merged, docs/decoding.md).
+
+``--generate-csv A.csv`` beside ``--recognize-csv B.csv`` (with -L, -V or -C) scores a machine that keeps its input alphabet
+between two profiles, A the soft input and B the soft output, without composing A's generator in front (profile.TwoProfileDP,
+mb_profile_two.hip; docs/profile_tapes.md, "Pairs of profiles"); ``scoreTwoProfiles`` is the same for a batch of input profiles.
 
 ``--prefix-decode`` imputes the most likely INPUT for each given output by the reference's prefix search (src/ctc.cpp), its
 node fills on the device (prefixtree.py, mb_prefix.hip, docs/decoding.md); ``--prefix-encode`` the most likely OUTPUT for each
@@ -144,6 +148,7 @@ def buildParser() -> argparse.ArgumentParser:
     ap.add_argument("--generate-chars", help="compose a generator of this sequence in front of the machine(s)")
     ap.add_argument("--recognize-chars", help="compose a recogniser of this sequence behind the machine(s)")
     ap.add_argument("--generate-json", help="compose a generator of the sequence in this JSON file ({name, sequence}) in front of the machine(s)")
+    ap.add_argument("--generate-csv", help="beside --recognize-csv with -L, -V or -C: score the machine(s) between this CSV profile as the soft input and that one as the soft output")
     ap.add_argument("--recognize-csv", help="score the machine(s) against this CSV profile (rightmost; with -L, -V or -C), or decode it (--prefix-decode, --viterbi-decode)")
     ap.add_argument("--profile-band", type=int, metavar="N", help="with --recognize-csv beside an input sequence: sweep each pair under a band of half-width N around the diagonal (seqpair.Envelope.band)")
     ap.add_argument("--recognize-merge-csv", help="the same against a CTC profile: a symbol repeated in consecutive rows is one symbol, and only a blank separates two equal symbols (not with --prefix-decode)")
@@ -413,6 +418,8 @@ def runProfile(args, out) -> int:
         if not machine.inputAlphabet():
             raise MachineError("--recognize-csv takes no other sequence data: the machine has no input alphabet to read an input sequence")
         return _runProfilePairs(args, out, machine)
+    if args.generate_csv is not None:
+        return _runTwoProfiles(args, out, machine)
     if args.profile_band is not None:
         raise MachineError(_BAND_ONLY)
     if machine.inputAlphabet():
@@ -544,6 +551,71 @@ def _runProfilePairs(args, out, machine: Machine) -> int:
     return 0
 
 
+def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "device", params=None,
+                     loglike: bool = True, viterbi: bool = False, counts: bool = False):
+    """Every input profile (a profile.Profile, read against the machine's input alphabet) as one pair with ``outProfile`` (a
+    profile.Profile, read against its output alphabet), all pairs in one batch, on a machine with an input alphabet
+    (docs/profile_tapes.md, "Pairs of profiles").  ``backend``: "device" (capi.DeviceProfileTwos) or "numpy"
+    (profile.TwoProfileDP).  Returns what scoreProfilePairs returns: (scores, paramCounts), scores["loglike"] and
+    scores["viterbi"] one float per input profile, or None where not asked for; paramCounts the posterior count of every parameter
+    summed over the pairs, or None."""
+    from . import dp
+    from .profile import TwoProfileDP
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    if not ev.nInTok:
+        raise MachineError("two-profile sweeps need a machine with an input alphabet")
+    As = [a.logRowsIn(ev) for a in inProfiles]
+    B = outProfile.logRows(ev)
+    acc = dp.MachineCounts(ev)
+    fwd = vit = None
+    if backend == "numpy":
+        tdp = TwoProfileDP(ev)
+        fwd = [tdp.forward(A, B)[0] for A in As] if loglike else None
+        if counts:
+            for A in As:
+                c, ll = tdp.counts(A, B)
+                acc._flat += c
+                acc.loglike += ll
+        vit = [tdp.forward(A, B, "max")[0] for A in As] if viterbi else None
+    else:
+        from . import capi
+        dm = capi.DeviceMachine(ev)
+        twos = capi.DeviceProfileTwos(dm, As, [B] * len(As))
+        try:
+            fwd = twos.forward(capi.MB_ROLLING) if loglike else None
+            if counts:
+                _, s, _ = twos.counts(acc._flat)
+                acc.loglike += s
+            vit = twos.viterbi(paths=False)[0] if viterbi else None
+        finally:
+            twos.close(); dm.close()
+
+    def floats(v):
+        return None if v is None else [float(x) for x in v]
+    return {"loglike": floats(fwd), "viterbi": floats(vit)}, (acc.paramCounts(machine, params) if counts else None)
+
+
+def _runTwoProfiles(args, out, machine: Machine) -> int:
+    """--generate-csv beside --recognize-csv on a machine with an input alphabet: one pair of profiles (docs/profile_tapes.md,
+    "Pairs of profiles").  -L and -V print [the --generate-csv argument, "", score], -C the counts.  --decode-backend numpy:
+    profile.TwoProfileDP."""
+    from .profile import Profile
+    if not machine.inputAlphabet():
+        raise MachineError("two-profile sweeps need a machine with an input alphabet")
+    if not os.path.exists(args.generate_csv) or not os.path.exists(args.recognize_csv):
+        raise MachineError("CSV file not found")
+    sc, pc = scoreTwoProfiles(machine, [Profile.fromCsv(args.generate_csv)], Profile.fromCsv(args.recognize_csv),
+                              backend="numpy" if args.decode_backend == "numpy" else "device", params=_profileParams(args, machine),
+                              loglike=bool(args.loglike), viterbi=bool(args.viterbi), counts=bool(args.counts))
+    if args.loglike:
+        out.write('[["%s","",%s]]\n' % (escaped(args.generate_csv), fmt(sc["loglike"][0])))
+    if args.counts:
+        out.write("{" + ",".join('"%s":%s' % (escaped(k), "%g" % pc[k]) for k in sorted(pc)) + "}\n")
+    if args.viterbi:
+        out.write('[["%s","",%s]]\n' % (escaped(args.generate_csv), fmt(sc["viterbi"][0])))
+    return 0
+
+
 def _runMergedNumpy(args, out, machine: Machine, params, ev, profile) -> int:
     """-L / -C / -V of a merged profile through the numpy restatement, printed as runProfile prints the device's."""
     from . import dp
@@ -657,12 +729,19 @@ def runCoding(args, machine: Machine, params, data: List[SeqPair], emit) -> None
         emit("[" + ",\n ".join(seqPairJson(SeqPair(d, sp.output, "input", sp.outputName)) for sp, d in zip(data, dec)) + "]\n")
 
 
+_GENERATE_ONLY = ("--generate-csv goes with --recognize-csv and -L, -V or -C on a machine with an input alphabet, nowhere else: not with "
+                  "--recognize-merge-csv, an input sequence, the decode options or --profile-band")
 _BAND_ONLY = "--profile-band goes with --recognize-csv beside an input sequence (--input-chars, --input-fasta, --input-json) and -L, -V or -C, nowhere else"
 
 
 def run(argv: Optional[List[str]] = None, out=None) -> int:
     out = out or sys.stdout
     args = buildParser().parse_args(argv)
+    if args.generate_csv is not None:
+        decode = args.prefix_decode or args.viterbi_decode or args.prefix_encode or args.viterbi_encode or args.random_encode
+        hasInput = args.input_chars is not None or bool(args.input_fasta) or bool(args.input_json)
+        if args.recognize_csv is None or args.recognize_merge_csv is not None or hasInput or decode or args.profile_band is not None:
+            raise MachineError(_GENERATE_ONLY)
     if args.profile_band is not None:
         decode = args.prefix_decode or args.viterbi_decode or args.prefix_encode or args.viterbi_encode or args.random_encode
         if args.recognize_csv is None or args.recognize_merge_csv is not None or decode:

@@ -34,6 +34,8 @@ EXPORTS = [
     "mb_profile_pairs_viterbi", "mb_profile_pairs_counts", "mb_profile_pair_fill",
     "mb_profile_pairs_create_merged", "mb_profile_pair_fill_merged",
     "mb_profile_pairs_set_envelopes", "mb_profile_pair_fill_env", "mb_profile_pairs_cells",
+    "mb_profile_twos_create", "mb_profile_twos_destroy", "mb_profile_twos_forward", "mb_profile_twos_viterbi", "mb_profile_twos_counts",
+    "mb_profile_two_fill",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
     "mb_prefix_node_cells", "mb_prefix_create_profiles", "mb_prefix_create_merged",
 ]
@@ -134,6 +136,13 @@ def load():
     L.mb_profile_pairs_set_envelopes.argtypes = [vp, i64p, i32p, i32p]
     L.mb_profile_pair_fill_env.argtypes = [vp, C.c_int, i32p, C.c_int64, dp, C.c_int64, i32p, i32p, dp]
     L.mb_profile_pairs_cells.argtypes = [vp]; L.mb_profile_pairs_cells.restype = C.c_int64
+    L.mb_profile_twos_create.restype = vp
+    L.mb_profile_twos_create.argtypes = [vp, C.c_int64, dp, i64p, dp, i64p]
+    L.mb_profile_twos_destroy.argtypes = [vp]; L.mb_profile_twos_destroy.restype = None
+    L.mb_profile_twos_forward.argtypes = [vp, C.c_int, dp]
+    L.mb_profile_twos_viterbi.argtypes = [vp, dp, i64p, u32p, i32p, i32p, C.c_int64]
+    L.mb_profile_twos_counts.argtypes = [vp, dp, dp, dp]
+    L.mb_profile_two_fill.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, dp]
     L.mb_prefix_create.restype = vp
     L.mb_prefix_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, C.c_int64]
     L.mb_prefix_create_profiles.restype = vp
@@ -786,6 +795,86 @@ def profile_pair_fill_merged(dm: DeviceMachine, mode: int, x, logP, colTok) -> n
     cells = np.empty((len(xs) + 1, len(P) + 1, 2, len(ct) + 1, dm.nStates), np.float64)
     _check(load().mb_profile_pair_fill_merged(dm.h, mode, _p(xs, C.c_int32), len(xs), _p(P, C.c_double), len(P), len(ct),
                                               _p(ct, C.c_int32), _p(cells, C.c_double)))
+    return cells
+
+
+class DeviceProfileTwos:
+    """Device-resident batch of (input profile, output profile) pairs (mb_profile_twos*) for a machine with an input alphabet: pair k
+    is the [rows, nInTok + 1] log weights ``inProfiles[k]`` (profile.Profile.logRowsIn) against the [rows, nOutTok + 1] log weights
+    ``outProfiles[k]`` (profile.Profile.logRows), column 0 of either the blank.  The yardstick is profile.TwoProfileDP
+    (docs/profile_tapes.md, "Pairs of profiles")."""
+
+    def __init__(self, dm: DeviceMachine, inProfiles, outProfiles):
+        self.dm = dm
+        wa, wb = dm.em.nInTok + 1, dm.em.nOutTok + 1
+        As = [np.asarray(p, np.float64).reshape(-1, wa) for p in inProfiles]
+        Bs = [np.asarray(p, np.float64).reshape(-1, wb) for p in outProfiles]
+        if len(As) != len(Bs):
+            raise ValueError("as many input profiles as output profiles, please")
+        self.nPairs = len(As)
+        self.rowOff = np.zeros(self.nPairs + 1, np.int64); self.inOff = np.zeros(self.nPairs + 1, np.int64)
+        for k, (a, b) in enumerate(zip(As, Bs)):
+            self.inOff[k + 1] = self.inOff[k] + len(a)
+            self.rowOff[k + 1] = self.rowOff[k] + len(b)
+        self.logA = np.ascontiguousarray(np.concatenate(As + [np.zeros((1, wa))]), np.float64)
+        self.logB = np.ascontiguousarray(np.concatenate(Bs + [np.zeros((1, wb))]), np.float64)
+        L = load()
+        self.h = L.mb_profile_twos_create(dm.h, self.nPairs, _p(self.logA, C.c_double), _p(self.inOff, C.c_int64),
+                                          _p(self.logB, C.c_double), _p(self.rowOff, C.c_int64))
+        if not self.h:
+            raise MbError(L.mb_last_error().decode())
+
+    def close(self):
+        if getattr(self, "h", None) and _lib is not None:
+            try:
+                _lib.mb_profile_twos_destroy(self.h)
+            except Exception:
+                pass
+            self.h = None
+
+    __del__ = close
+
+    def path_cap(self) -> int:
+        L = load()
+        return int(sum(L.mb_profile_pair_path_bound(self.dm.h, int(i), int(r)) for i, r in zip(np.diff(self.inOff), np.diff(self.rowOff))))
+
+    def forward(self, flags: int = MB_ROLLING) -> np.ndarray:
+        ll = np.empty(self.nPairs, np.float64)
+        _check(load().mb_profile_twos_forward(self.h, flags, _p(ll, C.c_double)))
+        return ll
+
+    def viterbi(self, paths: bool = True, cap: Optional[int] = None):
+        """Returns (loglike, pathOff, pathEdges, pathRow, pathInRow); the last four are None without paths.  ``cap``: the size of
+        the path buffers (default: the sum of the pairs' path bounds, which is what the library asks for)."""
+        ll = np.empty(self.nPairs, np.float64)
+        if not paths:
+            _check(load().mb_profile_twos_viterbi(self.h, _p(ll, C.c_double), None, None, None, None, 0))
+            return ll, None, None, None, None
+        cap = self.path_cap() if cap is None else int(cap)
+        off = np.zeros(self.nPairs + 1, np.int64)
+        edges = np.empty(max(cap, 1), np.uint32); rows = np.empty(max(cap, 1), np.int32); ins = np.empty(max(cap, 1), np.int32)
+        _check(load().mb_profile_twos_viterbi(self.h, _p(ll, C.c_double), _p(off, C.c_int64), _p(edges, C.c_uint32), _p(rows, C.c_int32),
+                                              _p(ins, C.c_int32), cap))
+        return ll, off, edges[:off[-1]].copy(), rows[:off[-1]].copy(), ins[:off[-1]].copy()
+
+    def counts(self, counts: Optional[np.ndarray] = None):
+        """Returns (counts[nTrans], loglikeSum, loglike[nPairs]); accumulates into ``counts`` if given."""
+        if counts is None:
+            counts = np.zeros(self.dm.nTrans, np.float64)
+        assert counts.dtype == np.float64 and counts.shape == (self.dm.nTrans,) and counts.flags.c_contiguous
+        s = C.c_double(0.0)
+        ll = np.empty(self.nPairs, np.float64)
+        _check(load().mb_profile_twos_counts(self.h, _p(counts, C.c_double), C.byref(s), _p(ll, C.c_double)))
+        return counts, s.value, ll
+
+
+def profile_two_fill(dm: DeviceMachine, mode: int, logA, logB) -> np.ndarray:
+    """One pair's lattice [rows of A + 1, rows of B + 1, 3, nStates] (layer 0 = arrived at (i, row), 1 = after the output-less
+    moves, 2 = committed to wait for the next input row)."""
+    A = np.ascontiguousarray(np.asarray(logA, np.float64).reshape(-1, dm.em.nInTok + 1))
+    B = np.ascontiguousarray(np.asarray(logB, np.float64).reshape(-1, dm.em.nOutTok + 1))
+    cells = np.empty((len(A) + 1, len(B) + 1, 3, dm.nStates), np.float64)
+    _check(load().mb_profile_two_fill(dm.h, mode, _p(A, C.c_double), len(A), _p(B, C.c_double), len(B), _p(cells, C.c_double)))
     return cells
 
 

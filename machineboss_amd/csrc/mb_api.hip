@@ -21,6 +21,7 @@
 #include "mb_profile_pair.h"
 #include "mb_profile_pair_env.h"
 #include "mb_profile_pair_merge.h"
+#include "mb_profile_two.h"
 #include "mb_small.h"
 #include "mb_usage.h"
 #include "mb_wide.h"
@@ -2464,10 +2465,10 @@ int mb_profile_fill_merged(mb_machine *m, int mode, const double *logP, int64_t 
 
 // ---- two-tape profile sweeps: an input sequence against a profile (mb_profile_pair.hip, docs/profile_tapes.md "Pairs") ----------
 // Split the pairs into chunks whose device memory (bytesPer(pair k)) fits the budget; even-sized like profile_chunks.
-static bool pair_profile_chunks(const mb_profile_pairs *p, const std::function<double(long long)> &bytesPer, std::vector<Chunk> &out) {
+static bool lattice_chunks(long long n, const std::function<double(long long)> &bytesPer, std::vector<Chunk> &out) {
   const double budget = (double)budget_bytes();
   double total = 0.0;
-  for (long long k = 0; k < p->n; ++k) {
+  for (long long k = 0; k < n; ++k) {
     const double b = bytesPer(k);
     if (b > budget) { set_error("one pair's DP lattice (" + std::to_string((long long)b) + " bytes) exceeds the device memory budget"); return false; }
     total += b;
@@ -2476,14 +2477,16 @@ static bool pair_profile_chunks(const mb_profile_pairs *p, const std::function<d
   const double share = std::min(budget, total / nChunks * 1.05);
   long long p0 = 0;
   double acc = 0.0;
-  for (long long k = 0; k < p->n; ++k) {
+  for (long long k = 0; k < n; ++k) {
     const double b = bytesPer(k);
     if (k > p0 && (acc + b > budget || (acc >= share && acc + b > share) || k - p0 >= (1 << 30))) { out.push_back({p0, k, 0}); p0 = k; acc = 0.0; }
     acc += b;
   }
-  if (p->n > p0) out.push_back({p0, p->n, 0});
+  if (n > p0) out.push_back({p0, n, 0});
   return true;
 }
+
+static bool pair_profile_chunks(const mb_profile_pairs *p, const std::function<double(long long)> &bytesPer, std::vector<Chunk> &out) { return lattice_chunks(p->n, bytesPer, out); }
 
 static long long pp_in(const mb_profile_pairs *p, long long k) { return p->inOff[k + 1] - p->inOff[k]; }
 static long long pp_rows(const mb_profile_pairs *p, long long k) { return p->rowOff[k + 1] - p->rowOff[k]; }
@@ -2986,6 +2989,281 @@ int mb_profile_pair_fill_merged(mb_machine *m, int mode, const int32_t *inTok, i
   ApiGuard guard;
   if (!merge_map_ok(m, nCols, colTok)) return 1;
   return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, nCols, colTok, nullptr, nullptr, cellsOut);
+}
+
+// ---- two-profile sweeps: an input profile against an output profile (mb_profile_two.hip, docs/profile_tapes.md "Pairs of profiles") --
+static long long pt_in(const mb_profile_twos *p, long long k) { return p->inOff[k + 1] - p->inOff[k]; }
+static long long pt_rows(const mb_profile_twos *p, long long k) { return p->rowOff[k + 1] - p->rowOff[k]; }
+static double pt_cell_bytes(const mb_profile_twos *p, long long k) { return 8.0 * (double)profile_two_cells(p->m->S, pt_in(p, k), pt_rows(p, k)); }
+// bytes of global scratch the rolling sweep of pair k needs (0: its ring is in LDS)
+static double pt_ring_bytes(const mb_profile_twos *p, long long k) {
+  return profile_two_lds_bytes(p->m->S, pt_in(p, k), pt_rows(p, k)) ? 0.0 : 8.0 * (double)profile_two_ring(p->m->S, pt_in(p, k), pt_rows(p, k));
+}
+static long long pt_path_bound(const mb_profile_twos *p, long long k) { return profile_pair_path_bound(p->m->nLevF, pt_in(p, k), pt_rows(p, k)); }
+
+struct TwoProfPlan {
+  PairProfDesc *d = nullptr;
+  long long cells = 0, paths = 0, ring = 0, maxItems = 0;
+  size_t lds = 0;
+};
+static void pt_plan_free(TwoProfPlan &pl) { sm_free(pl.d); pl.d = nullptr; }
+
+// descriptors of pairs [p0, p1): lattices, traceback slots and (rolling) scratch rings packed from 0
+static int two_profile_descs(const mb_profile_twos *p, long long p0, long long p1, bool rolling, TwoProfPlan &pl) {
+  std::vector<PairProfDesc> h;
+  const int S = p->m->S;
+  for (long long k = p0; k < p1; ++k) {
+    const long long K = pt_in(p, k), L = pt_rows(p, k);
+    PairProfDesc d;
+    d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)K; d.nRows = (int)L;
+    d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = -1;
+    if (rolling) {
+      const size_t lds = profile_two_lds_bytes(S, K, L);
+      if (lds) pl.lds = std::max(pl.lds, lds);
+      else { d.ringBase = pl.ring; pl.ring += profile_two_ring(S, K, L); }
+    }
+    pl.maxItems = std::max(pl.maxItems, (std::min(K, L) + 1) * S);
+    pl.cells += profile_two_cells(S, K, L);
+    pl.paths += pt_path_bound(p, k);
+    h.push_back(d);
+  }
+  MB_HIP(sm_alloc((void **)&pl.d, std::max<size_t>(h.size(), 1) * sizeof(PairProfDesc)));
+  if ((!h.empty() && !hip_ok(hipMemcpyAsync(pl.d, h.data(), h.size() * sizeof(PairProfDesc), hipMemcpyHostToDevice, g_stream), "H2D pair descriptors")) ||
+      !hip_ok(hipStreamSynchronize(g_stream), "H2D pair descriptors")) { pt_plan_free(pl); return 1; }
+  return 0;
+}
+
+static const char *pt_fwd_name(int mode, bool mat) {
+  static const char *const names[2][2] = {{"k_profile_two_fwd<sum,rolling>", "k_profile_two_fwd<sum,mat>"}, {"k_profile_two_fwd<max,rolling>", "k_profile_two_fwd<max,mat>"}};
+  return names[mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
+}
+
+// Forward (MB_FORWARD) or Viterbi scores without paths (MB_VITERBI); mat: through the materialised lattice
+static int two_profile_scores(mb_profile_twos *p, int mode, bool mat, double *loglike) {
+  std::vector<Chunk> chunks;
+  if (!lattice_chunks(p->n, [&](long long k) { return mat ? pt_cell_bytes(p, k) : pt_ring_bytes(p, k); }, chunks)) return 1;
+  double *d_ll = nullptr;
+  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
+  int rc = 0;
+  Timer tm;
+  for (const Chunk &c : chunks) {
+    TwoProfPlan pl;
+    if ((rc = two_profile_descs(p, c.p0, c.p1, !mat, pl))) break;
+    double *pool = nullptr, *scratch = nullptr;
+    if (mat) { pool = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double)); if (!pool) rc = 1; }
+    if (!rc && pl.ring) { scratch = (double *)ws_get(1, (size_t)pl.ring * sizeof(double)); if (!scratch) rc = 1; }
+    if (!rc) {
+      tm.start();
+      rc = launch_profile_two_fwd(p->m, mode, mat, pl.d, (int)(c.p1 - c.p0), pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, scratch, d_ll + c.p0, g_stream);
+      g_last_ms += tm.stop();
+      g_last_launches += 1;
+    }
+    if (rc) quiesce_streams();
+    pt_plan_free(pl);
+    if (rc) break;
+  }
+  if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  sm_free(d_ll);
+  g_last_kernel = pt_fwd_name(mode, mat);
+  return rc;
+}
+
+mb_profile_twos *mb_profile_twos_create(mb_machine *m, int64_t nPairs, const double *logA, const int64_t *inOff, const double *logB, const int64_t *rowOff) {
+  ApiGuard guard;
+  if (!m || nPairs < 0 || (nPairs > 0 && (!rowOff || !inOff))) { set_error("null argument"); return nullptr; }
+  if (!m->nIn) { set_error("two-profile sweeps need a machine with an input alphabet"); return nullptr; }
+  if (ensure_init()) return nullptr;
+  mb_profile_twos *p = new mb_profile_twos();
+  p->m = m; p->n = nPairs;
+  p->rowOff.assign((size_t)nPairs + 1, 0); p->inOff.assign((size_t)nPairs + 1, 0);
+  for (long long k = 0; k < nPairs; ++k) {
+    const long long L = rowOff[k + 1] - rowOff[k], K = inOff[k + 1] - inOff[k];
+    if (L < 0 || L > 0x3fffffff || K < 0 || K > 0x3fffffff) { set_error("bad pair offsets"); delete p; return nullptr; }
+    if ((double)(std::min(K, L) + 1) * m->S > 2147483647.0) { set_error("pair " + std::to_string(k) + ": an anti-diagonal of the lattice has more than 2^31 cells"); delete p; return nullptr; }
+    p->rowOff[(size_t)k + 1] = p->rowOff[(size_t)k] + L;
+    p->inOff[(size_t)k + 1] = p->inOff[(size_t)k] + K;
+  }
+  p->totalRows = p->rowOff.back(); p->totalIn = p->inOff.back();
+  const long long C = m->nOut + 1, CA = m->nIn + 1, nb = p->totalRows * C, na = p->totalIn * CA;
+  const double *b0 = logB ? logB + (nPairs ? rowOff[0] * C : 0) : nullptr;
+  const double *a0 = logA ? logA + (nPairs ? inOff[0] * CA : 0) : nullptr;
+  if ((nb && !b0) || (na && !a0)) { set_error("null argument"); delete p; return nullptr; }
+  if (!profile_values_ok(a0, na) || !profile_values_ok(b0, nb)) { delete p; return nullptr; }
+  if (!hip_ok(hipMalloc((void **)&p->d_logB, (size_t)std::max<long long>(nb, 1) * sizeof(double)), "hipMalloc(output profiles)") ||
+      !hip_ok(hipMalloc((void **)&p->d_logA, (size_t)std::max<long long>(na, 1) * sizeof(double)), "hipMalloc(input profiles)")) { mb_profile_twos_destroy(p); return nullptr; }
+  if ((nb && h2d_large(p->d_logB, b0, (size_t)nb * sizeof(double))) || (na && h2d_large(p->d_logA, a0, (size_t)na * sizeof(double))) ||
+      !hip_ok(hipStreamSynchronize(g_stream), "H2D profiles")) { mb_profile_twos_destroy(p); return nullptr; }
+  return p;
+}
+
+void mb_profile_twos_destroy(mb_profile_twos *p) {
+  ApiGuard guard;
+  if (!p) return;
+  if (p->d_logA) (void)hipFree(p->d_logA);
+  if (p->d_logB) (void)hipFree(p->d_logB);
+  delete p;
+}
+
+int mb_profile_twos_forward(mb_profile_twos *p, int flags, double *loglike) {
+  ApiGuard guard;
+  if (!p || (!loglike && p->n)) { set_error("null argument"); return 1; }
+  if (flags != MB_ROLLING && flags != MB_MATERIALISE) { set_error("unknown flags"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  return two_profile_scores(p, MB_FORWARD, flags == MB_MATERIALISE, loglike);
+}
+
+int mb_profile_twos_viterbi(mb_profile_twos *p, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow, int32_t *pathInRow, int64_t pathCap) {
+  ApiGuard guard;
+  if (!p || (!loglike && p->n)) { set_error("null argument"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  if (!pathEdges || !pathOff) return two_profile_scores(p, MB_VITERBI, false, loglike);
+  long long need = 0;
+  for (long long k = 0; k < p->n; ++k) need += pt_path_bound(p, k);
+  if (pathCap < need) { set_error("pathCap too small for the Viterbi paths: " + std::to_string((long long)pathCap) + " entries, the path bounds of the pairs sum to " + std::to_string(need)); return 1; }
+  std::vector<Chunk> chunks;
+  if (!lattice_chunks(p->n, [&](long long k) { return pt_cell_bytes(p, k) + 12.0 * pt_path_bound(p, k); }, chunks)) return 1;
+  double *d_ll = nullptr;
+  long long *d_len = nullptr;
+  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
+  if (!hip_ok(sm_alloc((void **)&d_len, std::max<long long>(p->n, 1) * sizeof(long long)), "hipMalloc(path lengths)")) { sm_free(d_ll); return 1; }
+  int rc = 0;
+  Timer tm;
+  long long written = 0;
+  pathOff[0] = 0;
+  std::vector<long long> len;
+  std::vector<uint32_t> he;
+  std::vector<int32_t> hr, hi;
+  for (const Chunk &c : chunks) {
+    TwoProfPlan pl;
+    if ((rc = two_profile_descs(p, c.p0, c.p1, false, pl))) break;
+    const long long np = c.p1 - c.p0, paths = pl.paths;
+    double *pool = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
+    uint32_t *d_e = (uint32_t *)ws_get(3, (size_t)std::max<long long>(paths, 1) * sizeof(uint32_t));
+    int32_t *d_r = (int32_t *)ws_get(4, (size_t)std::max<long long>(paths, 1) * sizeof(int32_t));
+    int32_t *d_i = (int32_t *)ws_get(5, (size_t)std::max<long long>(paths, 1) * sizeof(int32_t));
+    if (!pool || !d_e || !d_r || !d_i) rc = 1;
+    if (!rc) {
+      tm.start();
+      rc = launch_profile_two_fwd(p->m, MB_VITERBI, true, pl.d, (int)np, 0, pl.maxItems, p->d_logA, p->d_logB, pool, nullptr, d_ll + c.p0, g_stream);
+      if (!rc) rc = launch_profile_two_traceback(p->m, pl.d, (int)np, p->d_logA, p->d_logB, pool, d_e, d_r, d_i, d_len + c.p0, g_stream);
+      g_last_ms += tm.stop();
+      g_last_launches += 1;
+    }
+    len.resize((size_t)np); he.resize((size_t)std::max<long long>(paths, 1)); hr.resize(he.size()); hi.resize(he.size());
+    if (!rc && !hip_ok(hipMemcpy(len.data(), d_len + c.p0, np * sizeof(long long), hipMemcpyDeviceToHost), "D2H path lengths")) rc = 1;
+    if (!rc && paths && (d2h_large(he.data(), d_e, paths * sizeof(uint32_t)) || (pathRow && d2h_large(hr.data(), d_r, paths * sizeof(int32_t))) ||
+                         (pathInRow && d2h_large(hi.data(), d_i, paths * sizeof(int32_t))))) rc = 1;
+    long long base = 0;
+    for (long long k = 0; k < np && !rc; ++k) {
+      long long n = len[(size_t)k];
+      if (n == -1) n = 0;   // no finite path: an empty one, as mb_profile_pairs_viterbi
+      else if (n < 0) { set_error(n == -2 ? "pair traceback overflowed its bound" : "pair traceback found no matching candidate"); rc = 1; break; }
+      std::memcpy(pathEdges + written, he.data() + base, (size_t)n * sizeof(uint32_t));
+      if (pathRow) std::memcpy(pathRow + written, hr.data() + base, (size_t)n * sizeof(int32_t));
+      if (pathInRow) std::memcpy(pathInRow + written, hi.data() + base, (size_t)n * sizeof(int32_t));
+      written += n;
+      pathOff[c.p0 + k + 1] = written;
+      base += pt_path_bound(p, c.p0 + k);
+    }
+    if (rc) quiesce_streams();
+    pt_plan_free(pl);
+    if (rc) break;
+  }
+  if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  sm_free(d_ll); sm_free(d_len);
+  g_last_kernel = pt_fwd_name(MB_VITERBI, true);
+  return rc;
+}
+
+int mb_profile_twos_counts(mb_profile_twos *p, double *counts, double *loglikeSum, double *loglike) {
+  ApiGuard guard;
+  if (!p || !counts) { set_error("null argument"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
+  const mb_machine *m = p->m;
+  const long long nT = m->nTrans;
+  std::vector<Chunk> chunks;
+  if (!lattice_chunks(p->n, [&](long long k) { return 2.0 * pt_cell_bytes(p, k); }, chunks)) return 1;   // the Forward and the Backward lattice
+  double *d_ll = nullptr, *d_bll = nullptr, *d_cc = nullptr;
+  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
+  if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
+      !hip_ok(sm_alloc((void **)&d_cc, std::max<long long>(nT, 1) * sizeof(double)), "hipMalloc(counts)")) { sm_free(d_ll); sm_free(d_bll); sm_free(d_cc); return 1; }
+  int rc = 0;
+  Timer tm;
+  std::vector<double> total((size_t)nT, 0.0), hc((size_t)nT);
+  for (const Chunk &c : chunks) {
+    TwoProfPlan pl;
+    if ((rc = two_profile_descs(p, c.p0, c.p1, false, pl))) break;
+    const long long np = c.p1 - c.p0;
+    double *fwd = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
+    double *bwd = (double *)ws_get(1, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
+    if (!fwd || !bwd) rc = 1;
+    long long maxCells = 0;
+    for (long long k = c.p0; k < c.p1; ++k) maxCells = std::max(maxCells, profile_two_cells(m->S, pt_in(p, k), pt_rows(p, k)) / 3);
+    const int groups = (int)std::min<long long>(256, std::max<long long>(1, (maxCells + 2047) / 2048));
+    if (!rc && np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); rc = 1; }
+    if (!rc) {
+      tm.start();
+      rc = launch_profile_two_fwd(m, MB_FORWARD, true, pl.d, (int)np, 0, pl.maxItems, p->d_logA, p->d_logB, fwd, nullptr, d_ll + c.p0, g_stream);
+      if (!rc) rc = launch_profile_two_bwd(m, pl.d, (int)np, pl.maxItems, p->d_logA, p->d_logB, bwd, d_bll + c.p0, g_stream);
+      if (!rc && nT) rc = hip_ok(hipMemsetAsync(d_cc, 0, (size_t)nT * sizeof(double), g_stream), "memset(counts)") ? 0 : 1;
+      if (!rc) rc = launch_profile_two_counts(m, pl.d, (int)np, groups, p->d_logA, p->d_logB, fwd, bwd, d_cc, g_stream);
+      g_last_ms += tm.stop();
+      g_last_launches += 1;
+    }
+    if (!rc && nT && !hip_ok(hipMemcpy(hc.data(), d_cc, nT * sizeof(double), hipMemcpyDeviceToHost), "D2H counts")) rc = 1;
+    if (!rc && g_deterministic)
+      for (long long e = 0; e < nT && !rc; ++e) {      // fixed point, 2^-36
+        unsigned long long u; std::memcpy(&u, &hc[(size_t)e], 8);
+        if (!det_to_double(u, hc[(size_t)e])) { set_error("MB_DETERMINISTIC: a posterior count left the fixed-point range (6.7e7 per transition and call): split the batch or use the floating-point mode"); rc = 1; }
+      }
+    if (!rc) for (long long e = 0; e < nT; ++e) total[(size_t)e] += hc[(size_t)e];
+    if (rc) quiesce_streams();
+    pt_plan_free(pl);
+    if (rc) break;
+  }
+  std::vector<double> hll((size_t)p->n);
+  if (!rc && p->n && !hip_ok(hipMemcpy(hll.data(), d_ll, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  sm_free(d_ll); sm_free(d_bll); sm_free(d_cc);
+  g_last_kernel = "k_profile_two_counts";
+  if (rc) return rc;
+  for (long long e = 0; e < nT; ++e) counts[e] += total[(size_t)e];
+  double s = 0.0;
+  for (long long k = 0; k < p->n; ++k) { s += hll[(size_t)k]; if (loglike) loglike[k] = hll[(size_t)k]; }
+  if (loglikeSum) *loglikeSum += s;
+  return 0;
+}
+
+int mb_profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, double *cellsOut) {
+  ApiGuard guard;
+  if (!m || !cellsOut || nRows < 0 || nIn < 0 || (nRows && !logB) || (nIn && !logA)) { set_error("null argument"); return 1; }
+  if (mode != MB_FORWARD && mode != MB_VITERBI && mode != MB_BACKWARD) { set_error("unknown fill mode"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  const int64_t rOff[2] = {0, nRows}, iOff[2] = {0, nIn};
+  mb_profile_twos *p = mb_profile_twos_create(m, 1, logA, iOff, logB, rOff);
+  if (!p) return 1;
+  std::vector<Chunk> chunks;
+  if (!lattice_chunks(1, [&](long long k) { return pt_cell_bytes(p, k); }, chunks)) { mb_profile_twos_destroy(p); return 1; }
+  TwoProfPlan pl;
+  int rc = two_profile_descs(p, 0, 1, false, pl);
+  double *d_ll = nullptr;
+  if (!rc && !hip_ok(sm_alloc((void **)&d_ll, sizeof(double)), "hipMalloc(loglike)")) rc = 1;
+  double *pool = rc ? nullptr : (double *)ws_get(0, (size_t)pl.cells * sizeof(double));
+  if (!rc && !pool) rc = 1;
+  if (!rc) {
+    Timer tm;
+    tm.start();
+    rc = mode == MB_BACKWARD ? launch_profile_two_bwd(m, pl.d, 1, pl.maxItems, p->d_logA, p->d_logB, pool, d_ll, g_stream)
+                             : launch_profile_two_fwd(m, mode, true, pl.d, 1, 0, pl.maxItems, p->d_logA, p->d_logB, pool, nullptr, d_ll, g_stream);
+    g_last_ms += tm.stop();
+    g_last_launches = 1;
+  }
+  if (!rc) rc = d2h_large(cellsOut, pool, (size_t)pl.cells * sizeof(double));
+  if (rc) quiesce_streams();
+  pt_plan_free(pl); sm_free(d_ll);
+  g_last_kernel = mode == MB_BACKWARD ? "k_profile_two_bwd" : pt_fwd_name(mode, true);
+  mb_profile_twos_destroy(p);
+  return rc;
 }
 
 // ---- prefix search: node fills on the device, the tree on the host (mb_prefix.hip, docs/decoding.md) --------------------------

@@ -1,0 +1,41 @@
+// mb_profile_two.h -- two-profile sweeps: a machine with an input alphabet between an input profile of K rows (the generator of
+// `--generate-csv`) and an output profile of L rows (docs/profile_tapes.md, "Pairs of profiles").
+//
+// Lattice of one pair: (K+1) input rows x (L+1) output rows x 3 layers x S states.  Layer 0 (N) = "arrived at (i, r)", layer 1 (W) =
+// "after the machine's output-less moves there", layer 2 (Z) = "committed to wait for the next input row"; materialised cells live
+// at cells[(((i*(L+1)) + r)*3 + layer)*S + q].  A pair is described by a PairProfDesc whose inBase is the first row of its input
+// profile in the batch's input row table (rows of nIn+1 doubles, column 0 = blank) and nIn the number of those rows.
+#pragma once
+#include <algorithm>
+#include <vector>
+
+#include "mb_profile_pair.h"
+
+namespace mb {
+
+inline long long profile_two_cells(int S, long long nIn, long long nRows) { return (nIn + 1) * (nRows + 1) * 3 * (long long)S; }
+// the rolling ring: three anti-diagonals of three layers, each of min(K, L) + 1 cells
+inline long long profile_two_ring(int S, long long nIn, long long nRows) { return 3 * 3 * (std::min(nIn, nRows) + 1) * (long long)S; }
+// dynamic LDS of a pair's ring when it fits (0: a slice of the global scratch buffer)
+size_t profile_two_lds_bytes(int S, long long nIn, long long nRows);
+
+// lds: the dynamic LDS of the launch (the largest ring among the pairs whose ringBase is -1)
+int launch_profile_two_fwd(const mb_machine *m, int mode, bool mat, const PairProfDesc *d, int n, size_t lds, long long maxItems, const double *logA,
+                           const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st);
+int launch_profile_two_bwd(const mb_machine *m, const PairProfDesc *d, int n, long long maxItems, const double *logA, const double *logB, double *pool,
+                           double *loglike, hipStream_t st);
+// counts[nTrans] += posteriors of the n pairs (fwdPool / bwdPool: their materialised lattices); det: 64-bit fixed point at 2^-36
+int launch_profile_two_counts(const mb_machine *m, const PairProfDesc *d, int n, int groupsPerPair, const double *logA, const double *logB,
+                              const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
+int launch_profile_two_traceback(const mb_machine *m, const PairProfDesc *d, int n, const double *logA, const double *logB, const double *pool,
+                                 uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, hipStream_t st);
+
+}  // namespace mb
+
+struct mb_profile_twos {
+  mb_machine *m = nullptr;
+  long long n = 0, totalRows = 0, totalIn = 0;
+  std::vector<long long> rowOff, inOff;   // [n+1], rebased to 0: rows of the output / the input profiles
+  double *d_logB = nullptr;               // [totalRows * (nOut+1)]
+  double *d_logA = nullptr;               // [totalIn * (nIn+1)]
+};

@@ -1,0 +1,409 @@
+// mb_profile_two.hip -- Forward / Backward / Viterbi / posterior counts of a machine WITH an input alphabet between two PROFILE tapes:
+// an input profile A of K rows (the generator of `--generate-csv`) and an output profile B of L rows (`--recognize-csv`) -- the
+// semantics of compose(A.machine(), compose(M, transpose(B.machine()))) with both tapes empty, restated in docs/profile_tapes.md
+// ("Pairs of profiles"):
+//
+//   N[i][r][d] = [i = 0, r = 0, d = 0]
+//                (+) N[i][r-1][d] + B[r-1][0]                                                          (output blank; r > 0)
+//                (+) sum_{t: s->d, in = a, out = o}   ((Z[i-1][r-1][s] + w_t) + A[i-1][a]) + B[r-1][o]   (match; i > 0, r > 0)
+//                (+) sum_{t: s->d, in = eps, out = o} (W[i][r-1][s] + w_t) + B[r-1][o]                   (output-only; r > 0)
+//   W[i][r][d] = N[i][r][d]
+//                (+) sum_{t: s->d, in = a, out = eps} (Z[i-1][r][s] + w_t) + A[i-1][a]                   (input-only; i > 0)
+//                (+) sum_{silent t: s->d, s < d}      W[i][r][s] + w_t                                   (silent levels)
+//   Z[i][r][d] = W[i][r][d] (+) Z[i-1][r][d] + A[i-1][0]                                                 (input blank; i > 0)
+//   loglike    = Z[K][L][S-1]
+//
+// The generator moves only while the machine waits, so after an input blank only input-reading edges follow: Z feeds the match and
+// the input-only edges alone.  The sweep is the one of mb_profile_pair.hip -- one workgroup per pair along the anti-diagonals i + r,
+// the work items of a diagonal (cell, state) -- with the edge loops over ALL input tokens (for a destination q the CSR rows
+// q*K + a*C + o, a = 1..nIn: they are contiguous from q*K + C to (q + 1)*K) and a third layer.  Z of a state is written by the item
+// that finishes its W: the first phase writes it from the W it has, and the phase of the state's silent level writes it again from
+// the finished W -- nothing reads Z before the diagonal's last barrier, so the barriers stay at (K + L + 1) nLevF per pair.  The
+// rolling sweeps keep a ring of three diagonals of three layers, 3 * 3 * (min(K, L) + 1) * S doubles, in LDS when that fits 160 KiB,
+// else in the pair's slice of a global scratch buffer.  Cells are fp64, the sums the exact log-sum-exp.
+#include "mb_profile_common.h"
+#include "mb_profile_two.h"
+
+namespace mb {
+
+size_t profile_two_lds_bytes(int S, long long nIn, long long nRows) {
+  const double b = (double)profile_two_ring(S, nIn, nRows) * sizeof(double);
+  return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
+}
+
+// Where the cells of a pair live.  MAT: the materialised lattice of mb_profile_two.h at base, else the ring (diagonal (i + r) mod 3,
+// the cell by its coordinate on the short side of the lattice).
+template <bool MAT>
+struct TwoGeom {
+  double *base;
+  int S, K, L, M, byI;
+  __device__ __forceinline__ TwoGeom(const PairProfDesc &pd, double *base, int S)
+      : base(base), S(S), K(pd.nIn), L(pd.nRows), M(min(pd.nIn, pd.nRows) + 1), byI(pd.nIn <= pd.nRows) {}
+  // the cells of diagonal d: i = ilo .. ilo + nCells - 1
+  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = max(0, d - L); nCells = min(K, d) - ilo + 1; }
+  __device__ __forceinline__ double *at(int i, int r, int layer) const {
+    if (MAT) return base + ((((long long)i * (L + 1)) + r) * 3 + layer) * S;
+    return base + ((((long long)((i + r) % 3) * M) + (byI ? i : r)) * 3 + layer) * S;
+  }
+  __device__ __forceinline__ long long cells() const { return (long long)(K + 1) * (L + 1); }
+  __device__ __forceinline__ void cell(long long c, int &i, int &r) const { i = (int)(c / (L + 1)); r = (int)(c - (long long)i * (L + 1)); }
+};
+
+// Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every cell into pool, else rolling.  Viterbi keeps the FIRST
+// maximum: N takes the output blank first, then the match edges, then the output-only edges; W takes N (no move) first, then the
+// input-only edges, then the silent edges; Z takes W first, then the input blank; edges of a kind in `incoming` order (input token
+// ascending, then output token) -- the order k_profile_two_traceback re-enumerates.
+template <int MODE, bool MAT>
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_fwd(DevMachine m, const PairProfDesc *__restrict__ descs, const double *__restrict__ logA,
+                                                                   const double *__restrict__ logB, double *pool, double *scratch, double *__restrict__ loglike) {
+  extern __shared__ double pt_sh[];
+  const PairProfDesc pd = descs[blockIdx.x];
+  const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, K = pd.nIn, L = pd.nRows;
+  const double *A = logA + pd.inBase * CA;
+  const double *B = logB + pd.rowBase * C;
+  const TwoGeom<MAT> lat(pd, MAT ? pool + pd.cellBase : (pd.ringBase < 0 ? pt_sh : scratch + pd.ringBase), S);
+  for (int d = 0; d <= K + L; ++d) {
+    int ilo, nCells;
+    lat.diag(d, ilo, nCells);
+    const int nItems = nCells * S;
+    for (int it = threadIdx.x; it < nItems; it += blockDim.x) {
+      const int c = it / S, q = it - c * S, i = ilo + c, r = d - i;
+      const double *Ai = A + (long long)max(i - 1, 0) * CA;      // row i - 1; read when i > 0
+      double acc;
+      if (r > 0) {
+        const double *Br = B + (long long)(r - 1) * C;
+        acc = lat.at(i, r - 1, 0)[q] + Br[0];
+        if (i > 0) {
+          const double *Zd = lat.at(i - 1, r - 1, 2);
+          for (int a = 1; a <= m.nIn; ++a) {
+            const int row = q * KK + a * C;
+            const double wa = Ai[a];
+            const int e1 = m.inOff[row + C];
+            for (int e = m.inOff[row + 1]; e < e1; ++e)
+              acc = red<MODE>(acc, ((Zd[m.inSrc[e]] + m.inW[e]) + wa) + Br[m.eOutTok[m.inEid[e]]]);
+          }
+        }
+        const double *Wu = lat.at(i, r - 1, 1);
+        const int e1 = m.inOff[q * KK + C];
+        for (int e = m.inOff[q * KK + 1]; e < e1; ++e)
+          acc = red<MODE>(acc, (Wu[m.inSrc[e]] + m.inW[e]) + Br[m.eOutTok[m.inEid[e]]]);
+      } else {
+        acc = (i == 0 && q == 0) ? 0.0 : -INFINITY;
+      }
+      lat.at(i, r, 0)[q] = acc;
+      if (i > 0) {
+        const double *Zl = lat.at(i - 1, r, 2);
+        for (int a = 1; a <= m.nIn; ++a) {
+          const int row = q * KK + a * C;
+          const double wa = Ai[a];
+          const int e1 = m.inOff[row + 1];
+          for (int e = m.inOff[row]; e < e1; ++e) acc = red<MODE>(acc, (Zl[m.inSrc[e]] + m.inW[e]) + wa);
+        }
+        lat.at(i, r, 1)[q] = acc;
+        lat.at(i, r, 2)[q] = red<MODE>(acc, Zl[q] + Ai[0]);
+      } else {
+        lat.at(i, r, 1)[q] = acc;
+        lat.at(i, r, 2)[q] = acc;
+      }
+    }
+    __syncthreads();
+    for (int lev = 1; lev < m.nLevF; ++lev) {      // (level 0 has no silent edge coming in: its W and Z are complete)
+      const int l0 = m.levFOff[lev], ns = m.levFOff[lev + 1] - l0;
+      const int nLevItems = nCells * ns;
+      for (int it = threadIdx.x; it < nLevItems; it += blockDim.x) {
+        const int c = it / ns, q = m.levFState[l0 + (it - c * ns)], i = ilo + c, r = d - i;
+        double *Wc = lat.at(i, r, 1);
+        double acc = Wc[q];
+        const int e1 = m.inOff[q * KK + 1];
+        for (int e = m.inOff[q * KK]; e < e1; ++e) {
+          const int s = (int)m.inSrc[e];
+          if (s >= q) continue;                       // as the token sweeps: a silent self-loop never fires
+          acc = red<MODE>(acc, Wc[s] + m.inW[e]);
+        }
+        Wc[q] = acc;
+        lat.at(i, r, 2)[q] = i > 0 ? red<MODE>(acc, lat.at(i - 1, r, 2)[q] + A[(long long)(i - 1) * CA]) : acc;
+      }
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x == 0) loglike[blockIdx.x] = lat.at(K, L, 2)[S - 1];
+}
+
+// Materialised Backward sweep, layer 0 = NB ("from the arrived stage"), 1 = WB ("from the waiting stage"), 2 = ZB ("from the
+// committed stage"):
+//   ZB[i][r][s] = [i = K, r = L, s = S-1]
+//                 (+) A[i][0] + ZB[i+1][r][s]                                                    (i < K)
+//                 (+) sum_{t: s->d, in = a, out = o}   ((w_t + A[i][a]) + B[r][o]) + NB[i+1][r+1][d]   (i < K, r < L)
+//                 (+) sum_{t: s->d, in = a, out = eps} (w_t + A[i][a]) + WB[i+1][r][d]                 (i < K)
+//   WB[i][r][s] = ZB[i][r][s]
+//                 (+) sum_{t: s->d, in = eps, out = o} (w_t + B[r][o]) + NB[i][r+1][d]                 (r < L)
+//                 (+) sum_{silent t: s->d, s < d}      w_t + WB[i][r][d]
+//   NB[i][r][s] = WB[i][r][s] (+) (B[r][0] + NB[i][r+1][s])   (r < L);   loglike = NB[0][0][0]
+// Anti-diagonals from K + L down.  A state's WB is final once its backward level has run; the item that finishes it writes its NB.
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_bwd(DevMachine m, const PairProfDesc *__restrict__ descs, const double *__restrict__ logA,
+                                                                   const double *__restrict__ logB, double *pool, double *__restrict__ loglike) {
+  const PairProfDesc pd = descs[blockIdx.x];
+  const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, K = pd.nIn, L = pd.nRows;
+  const double *A = logA + pd.inBase * CA;
+  const double *B = logB + pd.rowBase * C;
+  const TwoGeom<true> lat(pd, pool + pd.cellBase, S);
+  for (int d = K + L; d >= 0; --d) {
+    int ilo, nCells;
+    lat.diag(d, ilo, nCells);
+    const int nItems = nCells * S;
+    for (int it = threadIdx.x; it < nItems; it += blockDim.x) {
+      const int c = it / S, s = it - c * S, i = ilo + c, r = d - i;
+      const double *Ai = A + (long long)i * CA;      // read when i < K
+      const double *Br = B + (long long)r * C;       // read when r < L
+      double v = (i == K && r == L && s == S - 1) ? 0.0 : -INFINITY;
+      if (i < K) {
+        v = lse2_exact(v, Ai[0] + lat.at(i + 1, r, 2)[s]);
+        if (r < L) {
+          const double *Nd = lat.at(i + 1, r + 1, 0);
+          for (int a = 1; a <= m.nIn; ++a) {
+            const int row = s * KK + a * C;
+            const double wa = Ai[a];
+            const int e1 = m.outOff[row + C];
+            for (int e = m.outOff[row + 1]; e < e1; ++e)
+              v = lse2_exact(v, ((m.outW[e] + wa) + Br[m.eOutTok[m.outEid[e]]]) + Nd[m.outDst[e]]);
+          }
+        }
+        const double *Wl = lat.at(i + 1, r, 1);
+        for (int a = 1; a <= m.nIn; ++a) {
+          const int row = s * KK + a * C;
+          const double wa = Ai[a];
+          const int e1 = m.outOff[row + 1];
+          for (int e = m.outOff[row]; e < e1; ++e) v = lse2_exact(v, (m.outW[e] + wa) + Wl[m.outDst[e]]);
+        }
+      }
+      lat.at(i, r, 2)[s] = v;
+      if (r < L) {
+        const double *Nu = lat.at(i, r + 1, 0);
+        const int e1 = m.outOff[s * KK + C];
+        for (int e = m.outOff[s * KK + 1]; e < e1; ++e)
+          v = lse2_exact(v, (m.outW[e] + Br[m.eOutTok[m.outEid[e]]]) + Nu[m.outDst[e]]);
+      }
+      lat.at(i, r, 1)[s] = v;
+      lat.at(i, r, 0)[s] = r < L ? lse2_exact(v, Br[0] + lat.at(i, r + 1, 0)[s]) : v;
+    }
+    __syncthreads();
+    for (int lev = 1; lev < m.nLevB; ++lev) {
+      const int l0 = m.levBOff[lev], ns = m.levBOff[lev + 1] - l0;
+      const int nLevItems = nCells * ns;
+      for (int it = threadIdx.x; it < nLevItems; it += blockDim.x) {
+        const int c = it / ns, s = m.levBState[l0 + (it - c * ns)], i = ilo + c, r = d - i;
+        double *Wc = lat.at(i, r, 1);
+        double v = Wc[s];
+        const int e1 = m.outOff[s * KK + 1];
+        for (int e = m.outOff[s * KK]; e < e1; ++e) {
+          const int t = (int)m.outDst[e];
+          if (t <= s) continue;
+          v = lse2_exact(v, Wc[t] + m.outW[e]);
+        }
+        Wc[s] = v;
+        lat.at(i, r, 0)[s] = r < L ? lse2_exact(v, B[(long long)r * C] + lat.at(i, r + 1, 0)[s]) : v;
+      }
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x == 0) loglike[blockIdx.x] = lat.at(0, 0, 0)[0];
+}
+
+// Posterior counts.  With both lattices in memory every (cell, edge) term is independent:
+//   count[t] += exp(F[i][r][s] - LL + term_t), term_t the edge's summand of ZB (read from Z_F) or WB (read from W_F) above,
+// so the sweep is a flat grid over (pair, group of the pair, (cell, state)), accumulated by CountsAcc (mb_profile_common.h).  A pair
+// whose likelihood is -inf adds nothing; the blanks of either tape are not edges.
+__global__ __launch_bounds__(256) void k_profile_two_counts(DevMachine m, const PairProfDesc *__restrict__ descs, int groupsPerPair, const double *__restrict__ logA,
+                                                            const double *__restrict__ logB, const double *__restrict__ fwdPool,
+                                                            const double *__restrict__ bwdPool, long long nTrans, double *__restrict__ counts, int det) {
+  __shared__ double lcount[COUNTS_LDS_MAX];
+  const CountsAcc acc(lcount, counts, nTrans, det);
+  const int k = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
+  const PairProfDesc pd = descs[k];
+  const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, K = pd.nIn, L = pd.nRows;
+  const double *A = logA + pd.inBase * CA;
+  const double *B = logB + pd.rowBase * C;
+  const TwoGeom<true> F(pd, const_cast<double *>(fwdPool) + pd.cellBase, S), Bk(pd, const_cast<double *>(bwdPool) + pd.cellBase, S);
+  const double LL = F.at(K, L, 2)[S - 1];
+  if (LL > -INFINITY) {
+    const long long nItems = F.cells() * S;
+    for (long long idx = (long long)group * blockDim.x + threadIdx.x; idx < nItems; idx += (long long)groupsPerPair * blockDim.x) {
+      const long long cell = idx / S;
+      const int s = (int)(idx - cell * S);
+      int i, r;
+      F.cell(cell, i, r);
+      const double f = F.at(i, r, 1)[s] - LL, z = F.at(i, r, 2)[s] - LL;
+      if (!(z > -INFINITY)) continue;                 // (Z holds W: a dead Z is a dead W)
+      const double *Ai = A + (long long)i * CA;
+      const double *Br = B + (long long)r * C;
+      if (i < K) {
+        const double *Wl = Bk.at(i + 1, r, 1);
+        for (int a = 1; a <= m.nIn; ++a) {
+          const int row = s * KK + a * C;
+          const double wa = Ai[a];
+          if (r < L) {
+            const double *Nd = Bk.at(i + 1, r + 1, 0);
+            const int e1 = m.outOff[row + C];
+            for (int e = m.outOff[row + 1]; e < e1; ++e)
+              acc.add(m.outEid[e], exp(z + (((m.outW[e] + wa) + Br[m.eOutTok[m.outEid[e]]]) + Nd[m.outDst[e]])));
+          }
+          const int e1 = m.outOff[row + 1];
+          for (int e = m.outOff[row]; e < e1; ++e) acc.add(m.outEid[e], exp(z + ((m.outW[e] + wa) + Wl[m.outDst[e]])));
+        }
+      }
+      if (!(f > -INFINITY)) continue;
+      if (r < L) {
+        const double *Nu = Bk.at(i, r + 1, 0);
+        const int e1 = m.outOff[s * KK + C];
+        for (int e = m.outOff[s * KK + 1]; e < e1; ++e)
+          acc.add(m.outEid[e], exp(f + ((m.outW[e] + Br[m.eOutTok[m.outEid[e]]]) + Nu[m.outDst[e]])));
+      }
+      const double *Wc = Bk.at(i, r, 1);
+      const int e1 = m.outOff[s * KK + 1];
+      for (int e = m.outOff[s * KK]; e < e1; ++e) {
+        const int t = (int)m.outDst[e];
+        if (t <= s) continue;
+        acc.add(m.outEid[e], exp(f + (Wc[t] + m.outW[e])));
+      }
+    }
+  }
+  acc.flush();
+}
+
+// Viterbi traceback over a materialised max lattice, one lane per pair: from Z[K][L][S-1] back to N[0][0][0], taking at every cell
+// the first candidate (in the fill's order) whose value equals the cell.  Edges go start -> end into the pair's slot
+// (profile_pair_path_bound entries) with both coordinates at which each fired: an emitting edge the output row it consumed, an
+// output-less edge the number of output rows consumed before it, and the same on the input tape.  len = -1: no finite path, -2: the
+// slot was too small, -3: no candidate matched (a corrupt matrix).
+__global__ void k_profile_two_traceback(DevMachine m, const PairProfDesc *__restrict__ descs, int n, const double *__restrict__ logA,
+                                        const double *__restrict__ logB, const double *__restrict__ pool, uint32_t *edges, int32_t *rows,
+                                        int32_t *inRows, long long *len) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const PairProfDesc pd = descs[k];
+  const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, K = pd.nIn, L = pd.nRows;
+  const double *A = logA + pd.inBase * CA;
+  const double *B = logB + pd.rowBase * C;
+  const TwoGeom<true> lat(pd, const_cast<double *>(pool) + pd.cellBase, S);
+  uint32_t *pe = edges + pd.pathBase;
+  int32_t *pr = rows + pd.pathBase, *pi = inRows + pd.pathBase;
+  int i = K, r = L, q = S - 1, layer = 2;
+  const long long cap = K + L + (long long)(K + L + 1) * (m.nLevF - 1);
+  long long cnt = 0;
+  if (!(lat.at(i, r, 2)[q] > -INFINITY)) { len[k] = -1; return; }
+  for (;;) {
+    const double *Ai = A + (long long)max(i - 1, 0) * CA;      // row i - 1; read when i > 0
+    int e = 0, found = -1;
+    if (layer == 2) {
+      const double cur = lat.at(i, r, 2)[q];
+      if (lat.at(i, r, 1)[q] == cur) { layer = 1; continue; }
+      if (i > 0 && lat.at(i - 1, r, 2)[q] + Ai[0] == cur) { --i; continue; }
+      len[k] = -3; return;
+    } else if (layer == 1) {
+      const double *W = lat.at(i, r, 1);
+      const double cur = W[q];
+      if (lat.at(i, r, 0)[q] == cur) { layer = 0; continue; }
+      int ni = i, nl = 1;
+      if (i > 0) {
+        const double *Zl = lat.at(i - 1, r, 2);
+        for (int a = 1; a <= m.nIn && found < 0; ++a) {
+          const int row = q * KK + a * C;
+          const double wa = Ai[a];
+          e = m.inOff[row];
+          for (const int e1 = m.inOff[row + 1]; e < e1; ++e)
+            if ((Zl[m.inSrc[e]] + m.inW[e]) + wa == cur) { found = (int)m.inSrc[e]; ni = i - 1; nl = 2; break; }
+        }
+      }
+      if (found < 0) {
+        e = m.inOff[q * KK];
+        for (const int e1 = m.inOff[q * KK + 1]; e < e1; ++e) {
+          const int s = (int)m.inSrc[e];
+          if (s < q && W[s] + m.inW[e] == cur) { found = s; break; }
+        }
+      }
+      if (found < 0) { len[k] = -3; return; }
+      if (cnt >= cap) { len[k] = -2; return; }
+      pe[cnt] = m.inEid[e]; pr[cnt] = r; pi[cnt] = ni; ++cnt;
+      i = ni; q = found; layer = nl;
+    } else {
+      if (r == 0) { if (i != 0 || q != 0) { len[k] = -3; return; } break; }
+      const double *Br = B + (long long)(r - 1) * C;
+      const double cur = lat.at(i, r, 0)[q];
+      if (lat.at(i, r - 1, 0)[q] + Br[0] == cur) { --r; continue; }
+      int ni = i, nl = 1;
+      if (i > 0) {
+        const double *Zd = lat.at(i - 1, r - 1, 2);
+        for (int a = 1; a <= m.nIn && found < 0; ++a) {
+          const int row = q * KK + a * C;
+          const double wa = Ai[a];
+          e = m.inOff[row + 1];
+          for (const int e1 = m.inOff[row + C]; e < e1; ++e)
+            if (((Zd[m.inSrc[e]] + m.inW[e]) + wa) + Br[m.eOutTok[m.inEid[e]]] == cur) { found = (int)m.inSrc[e]; ni = i - 1; nl = 2; break; }
+        }
+      }
+      if (found < 0) {
+        const double *Wu = lat.at(i, r - 1, 1);
+        e = m.inOff[q * KK + 1];
+        for (const int e1 = m.inOff[q * KK + C]; e < e1; ++e)
+          if ((Wu[m.inSrc[e]] + m.inW[e]) + Br[m.eOutTok[m.inEid[e]]] == cur) { found = (int)m.inSrc[e]; break; }
+      }
+      if (found < 0) { len[k] = -3; return; }
+      if (cnt >= cap) { len[k] = -2; return; }
+      --r;
+      pe[cnt] = m.inEid[e]; pr[cnt] = r; pi[cnt] = ni; ++cnt;
+      i = ni; q = found; layer = nl;
+    }
+  }
+  for (long long u = 0, v = cnt - 1; u < v; ++u, --v) {
+    const uint32_t e = pe[u]; pe[u] = pe[v]; pe[v] = e;
+    const int32_t w = pr[u]; pr[u] = pr[v]; pr[v] = w;
+    const int32_t x = pi[u]; pi[u] = pi[v]; pi[v] = x;
+  }
+  len[k] = cnt;
+}
+
+int launch_profile_two_fwd(const mb_machine *m, int mode, bool mat, const PairProfDesc *d, int n, size_t lds, long long maxItems, const double *logA,
+                           const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  if (n <= 0) return 0;
+  if (mat) lds = 0;
+  static size_t ldsAllowed = 64 * 1024;      // beyond the default the kernels must be told; asked for once, and only when a ring needs it
+  if (lds > ldsAllowed) {
+    const char *what = "k_profile_two_fwd: raising the LDS limit";
+    if (!hip_ok(hipFuncSetAttribute((const void *)&k_profile_two_fwd<MB_FORWARD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what) ||
+        !hip_ok(hipFuncSetAttribute((const void *)&k_profile_two_fwd<MB_VITERBI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what)) return 1;
+    ldsAllowed = SWEEP_LDS_MAX;
+  }
+  const dim3 g(n), b(sweep_threads(maxItems));
+  if (mode == MB_VITERBI) {
+    if (mat) k_profile_two_fwd<MB_VITERBI, true><<<g, b, 0, st>>>(m->dev, d, logA, logB, pool, scratch, loglike);
+    else k_profile_two_fwd<MB_VITERBI, false><<<g, b, lds, st>>>(m->dev, d, logA, logB, pool, scratch, loglike);
+  } else {
+    if (mat) k_profile_two_fwd<MB_FORWARD, true><<<g, b, 0, st>>>(m->dev, d, logA, logB, pool, scratch, loglike);
+    else k_profile_two_fwd<MB_FORWARD, false><<<g, b, lds, st>>>(m->dev, d, logA, logB, pool, scratch, loglike);
+  }
+  return hip_ok(hipGetLastError(), "k_profile_two_fwd") ? 0 : 1;
+}
+
+int launch_profile_two_bwd(const mb_machine *m, const PairProfDesc *d, int n, long long maxItems, const double *logA, const double *logB, double *pool,
+                           double *loglike, hipStream_t st) {
+  if (n <= 0) return 0;
+  k_profile_two_bwd<<<dim3(n), dim3(sweep_threads(maxItems)), 0, st>>>(m->dev, d, logA, logB, pool, loglike);
+  return hip_ok(hipGetLastError(), "k_profile_two_bwd") ? 0 : 1;
+}
+
+int launch_profile_two_counts(const mb_machine *m, const PairProfDesc *d, int n, int groupsPerPair, const double *logA, const double *logB,
+                              const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
+  if (n <= 0 || m->nTrans <= 0) return 0;
+  k_profile_two_counts<<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(m->dev, d, groupsPerPair, logA, logB, fwdPool, bwdPool, m->nTrans, counts,
+                                                                                         g_deterministic ? 1 : 0);
+  return hip_ok(hipGetLastError(), "k_profile_two_counts") ? 0 : 1;
+}
+
+int launch_profile_two_traceback(const mb_machine *m, const PairProfDesc *d, int n, const double *logA, const double *logB, const double *pool,
+                                 uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, hipStream_t st) {
+  if (n <= 0) return 0;
+  k_profile_two_traceback<<<(n + 63) / 64, 64, 0, st>>>(m->dev, d, n, logA, logB, pool, edges, rows, inRows, len);
+  return hip_ok(hipGetLastError(), "k_profile_two_traceback") ? 0 : 1;
+}
+
+}  // namespace mb

@@ -76,7 +76,9 @@ class Profile:
         """[rows, nOutTok + 1] log weights in the machine's output alphabet: column 0 the blank (header column len(header);
         0 if the row is shorter), column t the output token t (the sum over header columns of that symbol; 0 if none or the row
         is shorter).  Header symbols outside the alphabet are dropped; columns beyond the blank are ignored."""
-        syms = em.outputTokenizer.tok2sym
+        return self._logRows(em.outputTokenizer.tok2sym)
+
+    def _logRows(self, syms: Sequence[str]) -> np.ndarray:
         cols: List[List[int]] = [[len(self.header)]] + [[c for c, h in enumerate(self.header) if h == syms[t]] for t in range(1, len(syms))]
         P = np.empty((len(self.row), len(cols)), np.float64)
         for r, row in enumerate(self.row):
@@ -86,6 +88,11 @@ class Profile:
                     raise MachineError("Profile row %d: weight %g is not a probability" % (r, v))
                 P[r, t] = math.log(v) if v > 0 else -math.inf
         return P
+
+    def logRowsIn(self, em: EvaluatedMachine) -> np.ndarray:
+        """[rows, nInTok + 1] log weights in the machine's INPUT alphabet, by the rules of logRows: the profile as the generator
+        of ``--generate-csv`` (docs/profile_tapes.md, "Pairs of profiles").  Column 0 is the blank."""
+        return self._logRows(em.inputTokenizer.tok2sym)
 
     def machine(self) -> Machine:
         """CSVProfile::machine (src/csv.cpp:8-18): the profile as a generator of L+1 states."""
@@ -968,3 +975,199 @@ class PairMergedProfileDP(PairProfileDP):
             tie("plane", len(src))
             edges.append(e); rows.append(r); q = s; i = ni; p = src[0]; layer = 1
         return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32)
+
+
+class TwoProfileDP(PairProfileDP):
+    """A machine WITH an input alphabet between two profiles, in numpy -- the yardstick of mb_profile_two.hip
+    (docs/profile_tapes.md, "Pairs of profiles"): the semantics of compose(A.machine(), compose(M, B.recogniserMachine())) with both
+    tapes empty.  A[i][0..nInTok] are the log rows of the input profile (K rows, Profile.logRowsIn), B[r][0..nOutTok] those of the
+    output profile (L rows, Profile.logRows); column 0 of either is its blank.  N = "arrived at (i, r)", W = "after M's output-less
+    moves there", Z = "committed to wait for the next input row":
+
+        N[i][r][d] = [i = 0, r = 0, d = 0]
+                     (+) N[i][r-1][d] + B[r-1][0]                                                          (output blank; r > 0)
+                     (+) sum_{t: s->d, in = a, out = o}   ((Z[i-1][r-1][s] + w_t) + A[i-1][a]) + B[r-1][o]   (match; i, r > 0)
+                     (+) sum_{t: s->d, in = eps, out = o} (W[i][r-1][s] + w_t) + B[r-1][o]                   (output-only; r > 0)
+        W[i][r][d] = N[i][r][d]
+                     (+) sum_{t: s->d, in = a, out = eps} (Z[i-1][r][s] + w_t) + A[i-1][a]                   (input-only; i > 0)
+                     (+) sum_{silent t: s->d, s < d}      W[i][r][s] + w_t                                   (silent levels)
+        Z[i][r][d] = W[i][r][d] (+) Z[i-1][r][d] + A[i-1][0]                                                 (input blank; i > 0)
+        loglike    = Z[K][L][S-1]
+
+    The generator moves only while M waits, so M's output-only and silent moves at an input position come before the input blank
+    there: after a blank only input-reading edges follow (Z feeds the match and the input-only edges alone).  The output blank reads
+    N, never W.  Viterbi keeps the FIRST maximum -- N: the output blank, then the match edges, then the output-only edges; W: "no
+    move", then the input-only edges, then the silent edges; Z: W, then the input blank; edges of a kind in `incoming` order, which
+    is ascending input token first, then ascending output token.  Lattices are [K + 1, L + 1, S]."""
+
+    def __init__(self, em: EvaluatedMachine):
+        super().__init__(em)
+        order = em.incomingOrder()
+        it, ot, src, dst = em.inTok[order], em.outTok[order], em.src[order].astype(np.int64), em.dst[order].astype(np.int64)
+
+        def table(sel):
+            return order[sel], src[sel], dst[sel], em.logWeight[order[sel]], it[sel].astype(np.int64), ot[sel].astype(np.int64)
+        # (edge id, src, dst, w, in token, out token) of the edges that read input, in `incoming` order
+        self.mAll = table((it > 0) & (ot > 0))
+        self.iAll = table((it > 0) & (ot == 0))
+
+    def _checkTwo(self, A, B) -> Tuple[np.ndarray, np.ndarray]:
+        if not self.em.nInTok:
+            raise MachineError("two-profile sweeps need a machine with an input alphabet")
+        A = np.asarray(A, np.float64).reshape(-1, self.em.nInTok + 1)
+        if np.isnan(A).any() or (A == math.inf).any():
+            raise MachineError("profile weight is NaN or +infinity")
+        return A, self._check(B)
+
+    def forward(self, A, B, mode: str = "exact") -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
+        """(loglike, N, W, Z), each [K+1][L+1][S]; mode "exact" or "max"."""
+        A, B = self._checkTwo(A, B)
+        fold = _max_fold if mode == "max" else _lse_fold
+        K, L, S = len(A), len(B), self.S
+        N = np.full((K + 1, L + 1, S), _NEG); W = np.full((K + 1, L + 1, S), _NEG); Z = np.full((K + 1, L + 1, S), _NEG)
+        _, mS, mD, mW, mA, mO = self.mAll
+        _, iS, iD, iW, iA, _ = self.iAll
+        for i in range(K + 1):
+            for r in range(L + 1):
+                base = np.full(S, _NEG)
+                if i == 0 and r == 0:
+                    base[0] = 0.0
+                if r:
+                    Br = B[r - 1]
+                    idx, vals = [self._all], [N[i, r - 1] + Br[0]]
+                    if i:
+                        idx.append(mD); vals.append(((Z[i - 1, r - 1][mS] + mW) + A[i - 1][mA]) + Br[mO])
+                    idx.append(self.eD); vals.append((W[i, r - 1][self.eS] + self.eW) + Br[self.eO])
+                    base = fold(base, np.concatenate(idx), np.concatenate(vals))
+                N[i, r] = base
+                w_ = fold(base, iD, (Z[i - 1, r][iS] + iW) + A[i - 1][iA]) if i else base.copy()
+                for lv in self.fLevels:
+                    w_ = fold(w_, self.sD[lv], w_[self.sS[lv]] + self.sW[lv])
+                W[i, r] = w_
+                Z[i, r] = fold(w_, self._all, Z[i - 1, r] + A[i - 1][0]) if i else w_
+        return float(Z[K, L, S - 1]), N, W, Z
+
+    def backward(self, A, B) -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
+        """(loglike, NB, WB, ZB), exact log-sum-exp; loglike = NB[0][0][0].  ZB[i][r][s] is the mass from the committed stage of
+        (i, r, s) to the end, WB from the waiting stage, NB from the arrived stage."""
+        A, B = self._checkTwo(A, B)
+        K, L, S = len(A), len(B), self.S
+        NB = np.full((K + 1, L + 1, S), _NEG); WB = np.full((K + 1, L + 1, S), _NEG); ZB = np.full((K + 1, L + 1, S), _NEG)
+        _, mS, mD, mW, mA, mO = self.mAll
+        _, iS, iD, iW, iA, _ = self.iAll
+        for i in range(K, -1, -1):
+            for r in range(L, -1, -1):
+                base = np.full(S, _NEG)
+                if i == K and r == L:
+                    base[S - 1] = 0.0
+                if i < K:
+                    base = _lse_fold(base, self._all, A[i][0] + ZB[i + 1, r])
+                    if r < L:
+                        base = _lse_fold(base, mS, ((mW + A[i][mA]) + B[r][mO]) + NB[i + 1, r + 1][mD])
+                    base = _lse_fold(base, iS, (iW + A[i][iA]) + WB[i + 1, r][iD])
+                ZB[i, r] = base
+                if r < L:
+                    base = _lse_fold(base, self.eS, (self.eW + B[r][self.eO]) + NB[i, r + 1][self.eD])
+                for lv in self.bLevels:
+                    base = _lse_fold(base, self.sS[lv], base[self.sD[lv]] + self.sW[lv])
+                WB[i, r] = base
+                NB[i, r] = np.logaddexp(base, B[r][0] + NB[i, r + 1]) if r < L else base
+        return float(NB[0, 0, 0]), NB, WB, ZB
+
+    def counts(self, A, B, blanks: Optional[list] = None) -> Tuple[np.ndarray, float]:
+        """(posterior expected use of every transition, Forward loglike); nothing for a -inf pair.  Blanks are not edges;
+        ``blanks`` (a list) receives (mass of the output blanks, mass of the input blanks), summed over the lattice."""
+        A, B = self._checkTwo(A, B)
+        ll, NF, WF, ZF = self.forward(A, B)
+        out = np.zeros(self.em.nTransitions)
+        if not ll > _NEG:
+            return out, ll
+        _, NB, WB, ZB = self.backward(A, B)
+        K, L = len(A), len(B)
+        mE, mS, mD, mW, mA, mO = self.mAll
+        iE, iS, iD, iW, iA, _ = self.iAll
+        outBlank = inBlank = 0.0
+
+        def mass(b):
+            return float(np.exp(b[b > _NEG]).sum())
+        with np.errstate(invalid="ignore"):
+            for i in range(K + 1):
+                for r in range(L + 1):
+                    f, z = WF[i, r] - ll, ZF[i, r] - ll
+                    if r < L:
+                        if i < K:
+                            np.add.at(out, mE, np.exp(z[mS] + (((mW + A[i][mA]) + B[r][mO]) + NB[i + 1, r + 1][mD])))
+                        np.add.at(out, self.eId, np.exp(f[self.eS] + ((self.eW + B[r][self.eO]) + NB[i, r + 1][self.eD])))
+                        outBlank += mass((NF[i, r] - ll) + (B[r][0] + NB[i, r + 1]))
+                    if i < K:
+                        np.add.at(out, iE, np.exp(z[iS] + ((iW + A[i][iA]) + WB[i + 1, r][iD])))
+                        inBlank += mass(z + (A[i][0] + ZB[i + 1, r]))
+                    np.add.at(out, self.sId, np.exp(f[self.sS] + (WB[i, r][self.sD] + self.sW)))
+        if blanks is not None:
+            blanks.append((outBlank, inBlank))
+        return out, ll
+
+    def viterbi(self, A, B, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
+        """(score, global edge ids start -> end, output row, input row at which each fired); the first maximum in the fill's
+        candidate order.  The output row of an emitting edge is the row it consumed, of an output-less edge the number of rows
+        consumed before it; the input row likewise on the input tape -- input blanks advance it without an edge, so it does not
+        follow from counting edges.  ``census``: per step at which two or more candidates equal the cell, a count under the tuple
+        of the kinds that tie, in candidate order ("blank", "match", "emit" at an N cell; "stay", "ins", "silent" at a W cell;
+        "wait", "inblank" at a Z cell)."""
+        A, B = self._checkTwo(A, B)
+        v, N, W, Z = self.forward(A, B, "max")
+        edges: List[int] = []; rows: List[int] = []; ins: List[int] = []
+        if not v > _NEG:
+            return v, np.zeros(0, np.uint32), np.zeros(0, np.int32), np.zeros(0, np.int32)
+        mE, mS, mD, mW, mA, mO = self.mAll
+        iE, iS, iD, iW, iA, _ = self.iAll
+        i, r, q, layer = len(A), len(B), self.S - 1, 2
+        while True:
+            cand = []          # (kind, edge id or -1, source state, attains the cell)
+            if layer == 2:
+                cur = Z[i, r, q]
+                cand.append(("wait", -1, q, W[i, r, q] == cur))
+                if i:
+                    cand.append(("inblank", -1, q, Z[i - 1, r, q] + A[i - 1][0] == cur))
+            elif layer == 1:
+                cur = W[i, r, q]
+                cand.append(("stay", -1, q, N[i, r, q] == cur))
+                if i:
+                    cand += [("ins", int(iE[k]), int(iS[k]), (Z[i - 1, r, iS[k]] + iW[k]) + A[i - 1][iA[k]] == cur) for k in np.nonzero(iD == q)[0]]
+                cand += [("silent", int(self.sId[k]), int(self.sS[k]), W[i, r, self.sS[k]] + self.sW[k] == cur) for k in self.inSil[q]]
+            else:
+                if r == 0:
+                    assert i == 0 and q == 0
+                    break
+                Br, cur = B[r - 1], N[i, r, q]
+                cand.append(("blank", -1, q, N[i, r - 1, q] + Br[0] == cur))
+                if i:
+                    cand += [("match", int(mE[k]), int(mS[k]), ((Z[i - 1, r - 1, mS[k]] + mW[k]) + A[i - 1][mA[k]]) + Br[mO[k]] == cur)
+                             for k in np.nonzero(mD == q)[0]]
+                cand += [("emit", int(self.eId[k]), int(self.eS[k]), (W[i, r - 1, self.eS[k]] + self.eW[k]) + Br[self.eO[k]] == cur)
+                         for k in self.inEmit[q]]
+            hits = [c for c in cand if c[3]]
+            if census is not None and len(hits) > 1:
+                kinds = tuple(dict.fromkeys(c[0] for c in hits))
+                census[kinds] = census.get(kinds, 0) + 1
+            kind, e, s, _ = hits[0]
+            if kind == "wait":
+                layer = 1
+            elif kind == "inblank":
+                i -= 1
+            elif kind == "stay":
+                layer = 0
+            elif kind == "blank":
+                r -= 1
+            elif kind == "silent":
+                edges.append(e); rows.append(r); ins.append(i); q = s
+            elif kind == "ins":
+                i -= 1
+                edges.append(e); rows.append(r); ins.append(i); q = s; layer = 2
+            elif kind == "emit":
+                r -= 1
+                edges.append(e); rows.append(r); ins.append(i); q = s; layer = 1
+            else:
+                r -= 1; i -= 1
+                edges.append(e); rows.append(r); ins.append(i); q = s; layer = 2
+        return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32), np.array(ins[::-1], np.int32)
