@@ -222,6 +222,20 @@ int mb_profile_pair_fill_env(mb_machine *m, int mode, const int32_t *inTok, int6
                              const int32_t *envStart, const int32_t *envEnd, double *cellsOut);
 int64_t mb_profile_pairs_cells(const mb_profile_pairs *p);   /* doubles of all materialised lattices under the current envelopes */
 
+/* Row posteriors of the pairs (docs/profile_tapes.md, "Row posteriors"): post[(rowOff[k] - rowOff[0] + r)*(nOutTok+1) + o] = the
+ * posterior probability that row r of pair k's profile was consumed as output token o (column 0: as the blank), which is the
+ * gradient of the pair's log-likelihood in logP at that entry.  post has the layout of the row table and is overwritten.  Every row
+ * of a pair with a finite likelihood sums to 1; a pair whose likelihood is -inf gets zeros, an entry whose weight is -inf is exactly
+ * 0, and the column sums of a pair are the mb_profile_pairs_counts of the transitions that write the column's token, added up.
+ * Pairs under an envelope are summed over its cells.  With MB_DETERMINISTIC=1 the sums go through 64-bit fixed point at 2^-36 and
+ * are the same bits from call to call, alone or in a batch, chunked or not.  mb_profile_pairs_set_rows replaces the whole row table
+ * (same shapes, checked as mb_profile_pairs_create checks it; a refused table leaves the old one in effect), launches nothing and
+ * leaves the envelopes in place: a training loop re-uses the object.  Both refuse a merged pairs object before anything is launched:
+ * "row posteriors take plain profiles". */
+int mb_profile_pairs_row_posteriors(mb_profile_pairs *p, double *post /* [sum rows][nOutTok+1], overwritten */,
+                                    double *loglike /* [nPairs] or NULL */);
+int mb_profile_pairs_set_rows(mb_profile_pairs *p, const double *logP);
+
 /* Pairs against CTC-merged profiles: a known input sequence against the rows of `--recognize-merge-csv` -- the semantics of
  * compose(M, transpose(CSVProfile::mergingMachine())) on input x[1..I] with an empty output, swept natively over
  * (I + 1) x (rows + 1) x 2 x (nCols + 1) x nStates along anti-diagonals (mb_profile_pair_merge.hip; docs/profile_tapes.md, "Pairs

@@ -151,6 +151,7 @@ def buildParser() -> argparse.ArgumentParser:
     ap.add_argument("--generate-csv", help="beside --recognize-csv with -L, -V or -C: score the machine(s) between this CSV profile as the soft input and that one as the soft output")
     ap.add_argument("--recognize-csv", help="score the machine(s) against this CSV profile (rightmost; with -L, -V or -C), or decode it (--prefix-decode, --viterbi-decode)")
     ap.add_argument("--profile-band", type=int, metavar="N", help="with --recognize-csv beside an input sequence: sweep each pair under a band of half-width N around the diagonal (seqpair.Envelope.band)")
+    ap.add_argument("--profile-posteriors", action="store_true", help="with --recognize-csv beside an input sequence: per pair the posterior probability that each row of the profile was consumed as each output symbol, column 0 the blank (the gradient of the log-likelihood in the profile)")
     ap.add_argument("--recognize-merge-csv", help="the same against a CTC profile: a symbol repeated in consecutive rows is one symbol, and only a blank separates two equal symbols (not with --prefix-decode)")
     ap.add_argument("-P", "--params", action="append", default=[])
     ap.add_argument("-F", "--functions", action="append", default=[])
@@ -404,7 +405,7 @@ def runProfile(args, out) -> int:
         return runProfileDecode(args, out)
     if args.align or args.train:
         raise MachineError("--recognize-csv supports -L, -V and -C")
-    if not (args.loglike or args.viterbi or args.counts):
+    if not (args.loglike or args.viterbi or args.counts or args.profile_posteriors):
         raise MachineError("--recognize-csv needs -L, -V or -C")
     if args.recognize_chars is not None or args.data or args.output_chars is not None or args.output_fasta or args.output_json:
         raise MachineError("--recognize-csv takes no other sequence data")
@@ -418,6 +419,8 @@ def runProfile(args, out) -> int:
         if not machine.inputAlphabet():
             raise MachineError("--recognize-csv takes no other sequence data: the machine has no input alphabet to read an input sequence")
         return _runProfilePairs(args, out, machine)
+    if args.profile_posteriors:
+        raise MachineError(_POSTERIORS_ONLY)
     if args.generate_csv is not None:
         return _runTwoProfiles(args, out, machine)
     if args.profile_band is not None:
@@ -455,7 +458,8 @@ def runProfile(args, out) -> int:
 
 
 def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device", params=None, merge: bool = False,
-                      loglike: bool = True, viterbi: bool = False, counts: bool = False, band: Optional[int] = None):
+                      loglike: bool = True, viterbi: bool = False, counts: bool = False, band: Optional[int] = None,
+                      posteriors: bool = False):
     """Every input sequence (a list of symbols) as one pair with ``profile`` (a profile.Profile), all pairs in one batch, on a
     machine with an input alphabet (docs/profile_tapes.md, "Pairs" and "Pairs against a merged profile").  ``merge``: the profile
     is read CTC-merged, as --recognize-merge-csv reads it.  ``backend``: "device" (capi.DeviceProfilePairs) or "numpy"
@@ -463,7 +467,10 @@ def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device"
     float per input, or None where not asked for -- a sequence that cannot be tokenised scores -inf and adds nothing to the counts,
     as the --loglike loop (dp.loglikeBatch); paramCounts is the posterior count of every parameter summed over the pairs, or None.
     ``band``: every tokenisable input is swept under seqpair.Envelope.band(len(x), len(profile), band) (docs/profile_tapes.md,
-    "Pairs under an envelope"); plain profiles only."""
+    "Pairs under an envelope"); plain profiles only.  ``posteriors``: scores["posteriors"] holds one [rows, nOutTok + 1] array per
+    input, the posterior probability that each row was consumed as each output token (column 0: as the blank; docs/profile_tapes.md,
+    "Row posteriors") -- zeros for an input that cannot be tokenised or scores -inf; plain profiles only; the key is absent when not
+    asked for."""
     import numpy as np
     from . import dp
     from .profile import PairMergedProfileDP, PairProfileDP
@@ -473,11 +480,13 @@ def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device"
         raise MachineError("--recognize-merge-csv needs a machine with an output alphabet")
     if band is not None and merge:
         raise MachineError("envelopes take plain profiles")
+    if posteriors and merge:
+        raise MachineError("row posteriors take plain profiles")
     ok = [ev.inputTokenizer.canTokenize(seq) for seq in inputs]
     xs = [np.asarray(ev.inputTokenizer.tokenize(seq), np.int64).reshape(-1) for seq, k in zip(inputs, ok) if k]
     P, colTok = _mergedRows(profile, ev) if merge else (profile.logRows(ev), None)
     acc = dp.MachineCounts(ev)
-    fwd = vit = None
+    fwd = vit = post = None
     envs = None if band is None else [Envelope.band(len(x), len(P), int(band)) for x in xs]
     if backend == "numpy" and envs is not None:
         pdp = PairProfileDP(ev)
@@ -488,6 +497,7 @@ def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device"
                 acc._flat += c
                 acc.loglike += ll
         vit = [pdp.forward(x, P, "max", env=e)[0] for x, e in zip(xs, envs)] if viterbi else None
+        post = [pdp.rowPosteriors(x, P, env=e)[0] for x, e in zip(xs, envs)] if posteriors else None
     elif backend == "numpy":
         pdp = PairMergedProfileDP(ev, colTok) if merge else PairProfileDP(ev)
         fwd = [pdp.forward(x, P)[0] for x in xs] if loglike else None
@@ -497,6 +507,7 @@ def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device"
                 acc._flat += c
                 acc.loglike += ll
         vit = [pdp.forward(x, P, "max")[0] for x in xs] if viterbi else None
+        post = [pdp.rowPosteriors(x, P)[0] for x in xs] if posteriors else None
     else:
         from . import capi
         dm = capi.DeviceMachine(ev)
@@ -509,6 +520,9 @@ def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device"
                 _, s, _ = pairs.counts(acc._flat)
                 acc.loglike += s
             vit = pairs.viterbi(paths=False)[0] if viterbi else None
+            if posteriors:
+                flat = pairs.row_posteriors()[0]
+                post = [flat[k * len(P):(k + 1) * len(P)] for k in range(len(xs))]
         finally:
             pairs.close(); dm.close()
 
@@ -517,7 +531,11 @@ def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device"
             return None
         it = iter(v)
         return [float(next(it)) if k else -math.inf for k in ok]
-    return {"loglike": spread(fwd), "viterbi": spread(vit)}, (acc.paramCounts(machine, params) if counts else None)
+    scores = {"loglike": spread(fwd), "viterbi": spread(vit)}
+    if posteriors:
+        it = iter(post)
+        scores["posteriors"] = [np.array(next(it)) if k else np.zeros(P.shape) for k in ok]
+    return scores, (acc.paramCounts(machine, params) if counts else None)
 
 
 def _runProfilePairs(args, out, machine: Machine) -> int:
@@ -538,7 +556,7 @@ def _runProfilePairs(args, out, machine: Machine) -> int:
         j = json.load(open(args.input_json)); inSeqs.append((j.get("name", ""), list(j["sequence"])))
     sc, pc = scoreProfilePairs(machine, [seq for _, seq in inSeqs], profile, backend="numpy" if args.decode_backend == "numpy" else "device",
                                params=params, loglike=bool(args.loglike), viterbi=bool(args.viterbi), counts=bool(args.counts),
-                               band=args.profile_band)
+                               band=args.profile_band, posteriors=bool(args.profile_posteriors))
 
     def scores(v):
         return "[" + ",".join('["%s","",%s]' % (escaped(n), fmt(x)) for (n, _), x in zip(inSeqs, v)) + "]\n"
@@ -548,6 +566,9 @@ def _runProfilePairs(args, out, machine: Machine) -> int:
         out.write("{" + ",".join('"%s":%s' % (escaped(k), "%g" % pc[k]) for k in sorted(pc)) + "}\n")
     if args.viterbi:
         out.write(scores(sc["viterbi"]))
+    if args.profile_posteriors:
+        rows = lambda a: "[" + ",".join("[" + ",".join(fmt(float(v)) for v in row) + "]" for row in a) + "]"
+        out.write("[" + ",".join('["%s","",%s]' % (escaped(n), rows(a)) for (n, _), a in zip(inSeqs, sc["posteriors"])) + "]\n")
     return 0
 
 
@@ -731,6 +752,7 @@ def runCoding(args, machine: Machine, params, data: List[SeqPair], emit) -> None
 
 _GENERATE_ONLY = ("--generate-csv goes with --recognize-csv and -L, -V or -C on a machine with an input alphabet, nowhere else: not with "
                   "--recognize-merge-csv, an input sequence, the decode options or --profile-band")
+_POSTERIORS_ONLY = "--profile-posteriors goes with --recognize-csv beside an input sequence (--input-chars, --input-fasta, --input-json), nowhere else"
 _BAND_ONLY = "--profile-band goes with --recognize-csv beside an input sequence (--input-chars, --input-fasta, --input-json) and -L, -V or -C, nowhere else"
 
 
@@ -748,6 +770,10 @@ def run(argv: Optional[List[str]] = None, out=None) -> int:
             raise MachineError(_BAND_ONLY)
         if args.profile_band < 0:
             raise MachineError("--profile-band takes a half-width of 0 or more")
+    if args.profile_posteriors:
+        decode = args.prefix_decode or args.viterbi_decode or args.prefix_encode or args.viterbi_encode or args.random_encode
+        if (args.recognize_csv is None and args.recognize_merge_csv is None) or decode:
+            raise MachineError(_POSTERIORS_ONLY)
     if args.recognize_csv is not None or args.recognize_merge_csv is not None:
         return runProfile(args, out)
     machine = loadMachine(args)

@@ -34,6 +34,7 @@ EXPORTS = [
     "mb_profile_pairs_viterbi", "mb_profile_pairs_counts", "mb_profile_pair_fill",
     "mb_profile_pairs_create_merged", "mb_profile_pair_fill_merged",
     "mb_profile_pairs_set_envelopes", "mb_profile_pair_fill_env", "mb_profile_pairs_cells",
+    "mb_profile_pairs_row_posteriors", "mb_profile_pairs_set_rows",
     "mb_profile_twos_create", "mb_profile_twos_destroy", "mb_profile_twos_forward", "mb_profile_twos_viterbi", "mb_profile_twos_counts",
     "mb_profile_two_fill",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
@@ -136,6 +137,8 @@ def load():
     L.mb_profile_pairs_set_envelopes.argtypes = [vp, i64p, i32p, i32p]
     L.mb_profile_pair_fill_env.argtypes = [vp, C.c_int, i32p, C.c_int64, dp, C.c_int64, i32p, i32p, dp]
     L.mb_profile_pairs_cells.argtypes = [vp]; L.mb_profile_pairs_cells.restype = C.c_int64
+    L.mb_profile_pairs_row_posteriors.argtypes = [vp, dp, dp]
+    L.mb_profile_pairs_set_rows.argtypes = [vp, dp]
     L.mb_profile_twos_create.restype = vp
     L.mb_profile_twos_create.argtypes = [vp, C.c_int64, dp, i64p, dp, i64p]
     L.mb_profile_twos_destroy.argtypes = [vp]; L.mb_profile_twos_destroy.restype = None
@@ -758,6 +761,26 @@ class DeviceProfilePairs:
         ll = np.empty(self.nPairs, np.float64)
         _check(load().mb_profile_pairs_counts(self.h, _p(counts, C.c_double), C.byref(s), _p(ll, C.c_double)))
         return counts, s.value, ll
+
+    def row_posteriors(self):
+        """Returns (post[sumRows, nOutTok + 1], loglike[nPairs]): post[rowOff[k] + r][o] is the posterior probability that row r of
+        pair k was consumed as output token o (column 0: as the blank), the gradient of loglike[k] in that entry of the profile;
+        zeros for a pair whose likelihood is -inf (docs/profile_tapes.md, "Row posteriors").  Plain profiles only."""
+        post = np.zeros((int(self.rowOff[-1]), self.logP.shape[1]), np.float64)
+        ll = np.empty(self.nPairs, np.float64)
+        _check(load().mb_profile_pairs_row_posteriors(self.h, _p(post, C.c_double), _p(ll, C.c_double)))
+        return post, ll
+
+    def set_profiles(self, profiles):
+        """New rows for every pair, of the shapes the object was created with; the inputs and the envelopes stay.  A refused
+        table (NaN, +inf) leaves the old rows in effect."""
+        width = self.logP.shape[1]
+        rows = [np.asarray(q, np.float64).reshape(-1, width) for q in profiles]
+        if len(rows) != self.nPairs or any(len(r) != n for r, n in zip(rows, np.diff(self.rowOff))):
+            raise ValueError("one profile per pair with the rows it was created with, please")
+        logP = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((1, width)), np.float64)
+        _check(load().mb_profile_pairs_set_rows(self.h, _p(logP, C.c_double)))
+        self.logP = logP
 
 
 def _env_rows(env):

@@ -2923,6 +2923,86 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
   return 0;
 }
 
+// the LDS table of k_profile_pair_rowpost in doubles; MB_ROWPOST_TABLE makes it smaller (the rows-per-block and wide-row paths at small shapes)
+static int pp_rowpost_table() { return std::max(1, std::min(env_int("MB_ROWPOST_TABLE", ROWPOST_LDS_MAX), ROWPOST_LDS_MAX)); }
+static int pp_launch_rowpost(const mb_profile_pairs *p, const PairProfPlan &pl, int groups, int tabMax, const double *fwd, const double *bwd, double *post) {
+  if (launch_profile_pair_rowpost(p->m, pl.d, (int)pl.nPlain, groups, tabMax, p->d_in, p->d_logP, fwd, bwd, post, g_stream)) return 1;
+  return launch_profile_pair_rowpost(p->m, pl.e, pp_env_tables(p), (int)pl.nEnv, groups, tabMax, p->d_in, p->d_logP, fwd, bwd, post, g_stream);
+}
+
+int mb_profile_pairs_row_posteriors(mb_profile_pairs *p, double *post, double *loglike) {
+  ApiGuard guard;
+  if (!p || (!post && p->totalRows)) { set_error("null argument"); return 1; }
+  if (p->nCols) { set_error("row posteriors take plain profiles"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
+  const mb_machine *m = p->m;
+  const long long C = m->nOut + 1, nv = p->totalRows * C;
+  const int tabMax = pp_rowpost_table();
+  std::vector<Chunk> chunks;
+  auto bytes = [&](long long k) { return 2.0 * pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false) + 8.0 * (double)(pp_rows(p, k) * C); };   // both lattices and the pair's bins
+  if (!pair_profile_chunks(p, bytes, chunks)) return 1;
+  double *d_ll = nullptr, *d_bll = nullptr, *d_post = nullptr;
+  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
+  if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
+      !hip_ok(sm_alloc((void **)&d_post, std::max<long long>(nv, 1) * sizeof(double)), "hipMalloc(row posteriors)")) { sm_free(d_ll); sm_free(d_bll); sm_free(d_post); return 1; }
+  int rc = 0;
+  Timer tm;
+  PairWhere where;
+  for (const Chunk &c : chunks) {
+    PairProfPlan pl;
+    if ((rc = pair_profile_descs(p, c.p0, c.p1, false, pl))) break;
+    where.add(c.p0, pl);
+    const long long np = c.p1 - c.p0;
+    double *fwd = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
+    double *bwd = (double *)ws_get(1, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
+    if (!fwd || !bwd) rc = 1;
+    long long groups = 1;      // the row blocks of the pair that has most (a group past a pair's last block has nothing to do)
+    for (long long k = c.p0; k < c.p1; ++k) {
+      const long long L = pp_rows(p, k), R = profile_pair_rowpost_rows(pp_cells(p, k) / (2 * (long long)m->S), m->S, (int)L, (int)C, tabMax);
+      groups = std::max(groups, (L + R - 1) / R);
+    }
+    groups = std::min<long long>(groups, 1024);
+    if (!rc && np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); rc = 1; }
+    if (!rc) {
+      tm.start();
+      rc = pp_launch_fwd(p, MB_FORWARD, true, pl, np, fwd, nullptr, d_ll + c.p0);
+      if (!rc) rc = pp_launch_bwd(p, pl, np, bwd, nullptr, d_bll + c.p0);
+      if (!rc) rc = pp_launch_rowpost(p, pl, (int)groups, tabMax, fwd, bwd, d_post);
+      g_last_ms += tm.stop();
+      g_last_launches += pp_chunk_launches(pl);
+    }
+    if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "row posteriors")) rc = 1;      // (the next chunk takes the lattices over)
+    if (rc) quiesce_streams();
+    pp_plan_free(pl);
+    if (rc) break;
+  }
+  if (!rc && nv && d2h_large(post, d_post, (size_t)nv * sizeof(double))) rc = 1;
+  if (!rc && g_deterministic)
+    for (long long e = 0; e < nv && !rc; ++e) {      // fixed point, 2^-36 (a posterior is at most 1: far inside the range)
+      unsigned long long u; std::memcpy(&u, &post[e], 8);
+      if (!det_to_double(u, post[e])) { set_error("MB_DETERMINISTIC: a row posterior left the fixed-point range"); rc = 1; }
+    }
+  std::vector<double> hll((size_t)p->n);
+  if (!rc && pp_fetch(hll.data(), d_ll, p->n, where, "D2H loglike")) rc = 1;
+  sm_free(d_ll); sm_free(d_bll); sm_free(d_post);
+  g_last_kernel = p->hasEnv ? "k_profile_pair_env_rowpost" : "k_profile_pair_rowpost";
+  if (rc) return rc;
+  if (loglike) for (long long k = 0; k < p->n; ++k) loglike[k] = hll[(size_t)k];
+  return 0;
+}
+
+int mb_profile_pairs_set_rows(mb_profile_pairs *p, const double *logP) {
+  ApiGuard guard;
+  if (!p) { set_error("null argument"); return 1; }
+  if (p->nCols) { set_error("row posteriors take plain profiles"); return 1; }
+  const long long nv = p->totalRows * (p->m->nOut + 1);
+  if (nv && !logP) { set_error("null argument"); return 1; }
+  if (!profile_values_ok(logP, nv)) return 1;
+  if (nv && h2d_large(p->d_logP, logP, (size_t)nv * sizeof(double))) return 1;
+  return hip_ok(hipStreamSynchronize(g_stream), "H2D pair profiles") ? 0 : 1;
+}
+
 static int profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, int32_t nCols,
                              const int32_t *colTok, const int32_t *envStart, const int32_t *envEnd, double *cellsOut) {
   if (!m || !cellsOut || nRows < 0 || nIn < 0 || (nRows && !logP) || (nIn && !inTok)) { set_error("null argument"); return 1; }

@@ -31,6 +31,20 @@ inline long long profile_pair_ring(int S, long long nIn, long long nRows) { retu
 // dynamic LDS of a pair's ring when it fits (0: a slice of the global scratch buffer)
 size_t profile_pair_lds_bytes(int S, long long nIn, long long nRows);
 
+// Row posteriors (k_profile_pair_rowpost): a workgroup of ROWPOST_THREADS lanes owns blocks of whole rows and keeps their bins, rows of
+// the block x C doubles, in an LDS table of at most tabMax <= ROWPOST_LDS_MAX doubles.  The rows of a block: enough for about
+// ROWPOST_ITEMS (cell, state) items, as many as the table holds at the most; 1 where a single row does not fit it (its bins are then
+// summed in global memory).  cells: of the pair's lattice, the rectangle or its envelope.
+static constexpr int ROWPOST_THREADS = 256;
+static constexpr int ROWPOST_LDS_MAX = 4096;
+static constexpr int ROWPOST_ITEMS = 8192;
+__host__ __device__ inline int profile_pair_rowpost_rows(long long cells, int S, int L, int C, int tabMax) {
+  if (L <= 0 || C > tabMax) return 1;
+  const long long perRow = cells * S / (L + 1) > 1 ? cells * S / (L + 1) : 1, want = (ROWPOST_ITEMS + perRow - 1) / perRow;
+  const long long rows = want < tabMax / C ? want : tabMax / C;
+  return (int)(rows < L ? rows : L);
+}
+
 // The launchers, one per sweep, over full rectangles; mb_profile_pair_env.h declares their overloads for pairs under an envelope.
 // lds: the dynamic LDS of the launch (the largest ring among the pairs whose ringBase is -1)
 int launch_profile_pair_fwd(const mb_machine *m, int mode, bool mat, const PairProfDesc *d, int n, size_t lds, long long maxItems, const int *inTok,
@@ -42,6 +56,10 @@ int launch_profile_pair_counts(const mb_machine *m, const PairProfDesc *d, int n
                                const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
 int launch_profile_pair_traceback(const mb_machine *m, const PairProfDesc *d, int n, const int *inTok, const double *logP, const double *pool,
                                   uint32_t *edges, int32_t *rows, long long *len, hipStream_t st);
+// post[(rowBase + r) * C + o] = the row posteriors of the n pairs, every bin of every row written (nothing to clear); groupsPerPair:
+// at least the row blocks of the pair that has most; det: post holds 64-bit fixed point at 2^-36
+int launch_profile_pair_rowpost(const mb_machine *m, const PairProfDesc *d, int n, int groupsPerPair, int tabMax, const int *inTok, const double *logP,
+                                const double *fwdPool, const double *bwdPool, double *post, hipStream_t st);
 
 }  // namespace mb
 

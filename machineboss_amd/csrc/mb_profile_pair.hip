@@ -58,6 +58,9 @@ struct FullGeom {
   // counts: the cells of the pair and the c-th of them
   __device__ __forceinline__ long long cells() const { return (long long)(I + 1) * (L + 1); }
   __device__ __forceinline__ void cell(long long c, int &i, int &r) const { i = (int)(c / (L + 1)); r = (int)(c - (long long)i * (L + 1)); }
+  // row posteriors: the cells counted row by row (row r holds the cells rowFirst(r) .. rowFirst(r + 1) - 1, by ascending i)
+  __device__ __forceinline__ long long rowFirst(int r) const { return (long long)r * (I + 1); }
+  __device__ __forceinline__ void rowCell(long long c, int &i, int &r) const { r = (int)(c / (I + 1)); i = (int)(c - (long long)r * (I + 1)); }
 };
 
 // The cells of an envelope (mb_profile_pair_env.h).  Its bounds never decrease from row to row, so the cells of diagonal d are the
@@ -94,6 +97,9 @@ struct EnvGeom {
     }
     r = lo; i = st[r] + (int)(c - off[r]);
   }
+  // (the compact index already counts row by row; r <= L)
+  __device__ __forceinline__ long long rowFirst(int r) const { return off[r]; }
+  __device__ __forceinline__ void rowCell(long long c, int &i, int &r) const { cell(c, i, r); }
 };
 
 // Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every cell into pool (the geometry's layout), else rolling.
@@ -300,6 +306,107 @@ __global__ __launch_bounds__(256) void k_profile_pair_counts(DevMachine m, const
   acc.flush();
 }
 
+// Row posteriors: post[(rowBase + r) * C + o] = the posterior probability that row r of the pair's profile was consumed as column o
+// (0: the blank), the gradient of the log-likelihood in P[r][o] (docs/profile_tapes.md, "Row posteriors"):
+//   post[r][0] = sum_i sum_s exp((N_F[i][r][s] - LL) + (P[r][0] + NB[i][r+1][s]))
+//   post[r][o] = the emitting terms of k_profile_pair_counts above, binned by (row, output token) instead of by transition.
+// The bins are few and the lanes of a wavefront are consecutive states of a cell, so nothing is added per term.  The work items are
+// (row, cell of the row, state) in that order and a workgroup owns whole rows: blocks of profile_pair_rowpost_rows rows, dealt round
+// robin to the pair's groups.  A lane sums its terms of one column in a register, in CSR order; where all 64 lanes of the wavefront
+// hold items of one row the lane sums are reduced across the lanes and one lane adds the result to the workgroup's LDS table (rows
+// of the block x C), else (a row seam, the tail of the block) every lane adds its own.  The table is then stored: every bin has one
+// writing workgroup, so there is no global atomic and nothing to clear beforehand.  A row of more than tabMax columns is summed in
+// its global bins instead, cleared by the workgroup that owns it.  A pair whose likelihood is -inf gets zeros.
+// det: a lane sum is turned into 64-bit fixed point at 2^-36 (mb_internal.h) before it meets another, and integers are reduced and
+// added; post then holds the integers.
+__device__ __forceinline__ void rowpost_add(double *tab, int bin, double v, bool whole, int lane, int det) {
+  if (det) {
+    unsigned long long u = (unsigned long long)fmin(fmax(v * MB_DET_GLOBAL_SCALE + 0.5, 0.0), 4611686018427387904.0);
+    if (whole) {
+      for (int w = 32; w > 0; w >>= 1) u += __shfl_xor(u, w);
+      if (lane != 0) u = 0ull;
+    }
+    if (u != 0ull) atomicAdd((unsigned long long *)tab + bin, u);
+  } else {
+    if (whole) {
+      for (int w = 32; w > 0; w >>= 1) v += __shfl_xor(v, w);
+      if (lane != 0) v = 0.0;
+    }
+    if (v != 0.0) atomicAdd(&tab[bin], v);
+  }
+}
+
+template <template <bool> class Geom>
+__global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_rowpost(DevMachine m, const typename Geom<true>::Desc *__restrict__ descs, typename Geom<true>::Tables t, int groupsPerPair,
+                                                                          const int *__restrict__ inTok, const double *__restrict__ logP,
+                                                                          const double *__restrict__ fwdPool, const double *__restrict__ bwdPool,
+                                                                          double *post, int tabMax, int det) {
+  __shared__ double ltab[ROWPOST_LDS_MAX];
+  const int k = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
+  const auto pd = descs[k];
+  const int S = m.S, K = m.K, C = m.nOut + 1, I = pd.nIn, L = pd.nRows;
+  if (L == 0) return;
+  const int *x = inTok + pd.inBase;
+  const double *P = logP + pd.rowBase * C;
+  const Geom<true> F(pd, t, const_cast<double *>(fwdPool) + pd.cellBase, S), B(pd, t, const_cast<double *>(bwdPool) + pd.cellBase, S);
+  const double LL = F.at(I, L, 1)[S - 1];
+  const int R = profile_pair_rowpost_rows(F.cells(), S, L, C, tabMax);
+  const bool useLds = C <= tabMax;
+  const int lane = threadIdx.x & 63;
+  for (long long rb = (long long)group * R; rb < L; rb += (long long)groupsPerPair * R) {
+    const int r0 = (int)rb, r1 = (int)min((long long)L, rb + R), nBins = (r1 - r0) * C;
+    double *out = post + (pd.rowBase + r0) * C;
+    double *tab = useLds ? ltab : out;
+    for (int e = threadIdx.x; e < nBins; e += blockDim.x) tab[e] = 0.0;      // (the fixed point's zero has the same bits)
+    if (!useLds) __threadfence();
+    __syncthreads();
+    if (LL > -INFINITY) {
+      const long long c0 = F.rowFirst(r0), nItems = (F.rowFirst(r1) - c0) * S;
+      for (long long base = threadIdx.x - lane; base < nItems; base += blockDim.x) {      // (a wavefront stays whole in here)
+        const long long idx = base + lane;
+        const bool valid = idx < nItems;
+        int i = 0, r = r0, s = 0;
+        double f = -INFINITY, n = -INFINITY;
+        if (valid) {
+          const long long cell = idx / S;
+          s = (int)(idx - cell * S);
+          F.rowCell(c0 + cell, i, r);
+          f = F.at(i, r, 1)[s] - LL;
+          n = F.at(i, r, 0)[s] - LL;
+        }
+        const bool whole = __all(valid && r == __shfl(r, 0));
+        const bool up = valid && B.inside(i, r + 1), across = valid && i < I && B.inside(i + 1, r + 1);
+        const double *Pr = P + (long long)r * C;
+        const double *Nu = up ? B.at(i, r + 1, 0) : nullptr, *Nd = across ? B.at(i + 1, r + 1, 0) : nullptr;
+        const int sRow = s * K, xRow = across ? sRow + x[i] * C : 0;
+        const bool fLive = f > -INFINITY;
+        const int bin0 = (r - r0) * C;
+        rowpost_add(tab, bin0, (up && n > -INFINITY) ? exp(n + (Pr[0] + Nu[s])) : 0.0, whole, lane, det);
+        for (int o = 1; o < C; ++o) {      // the out-edges of (s, input token) that write o are one CSR row
+          double v = 0.0;
+          if (fLive) {
+            const double po = Pr[o];
+            if (across) {
+              const int a1 = m.outOff[xRow + o + 1];
+              for (int a = m.outOff[xRow + o]; a < a1; ++a) v += exp(f + ((m.outW[a] + po) + Nd[m.outDst[a]]));
+            }
+            if (up) {
+              const int a1 = m.outOff[sRow + o + 1];
+              for (int a = m.outOff[sRow + o]; a < a1; ++a) v += exp(f + ((m.outW[a] + po) + Nu[m.outDst[a]]));
+            }
+          }
+          rowpost_add(tab, bin0 + o, v, whole, lane, det);
+        }
+      }
+    }
+    __syncthreads();
+    if (useLds) {
+      for (int e = threadIdx.x; e < nBins; e += blockDim.x) out[e] = tab[e];
+      __syncthreads();
+    }
+  }
+}
+
 // Viterbi traceback over a materialised max lattice, one lane per pair: from W[I][L][S-1] back to N[0][0][0], taking at every cell
 // the first candidate (in the fill's order) whose value equals the cell.  Edges go start -> end into the pair's slot
 // (profile_pair_path_bound entries) with the row each fired at: an emitting edge the row it consumed, an output-less edge the number
@@ -444,6 +551,23 @@ int launch_profile_pair_counts(const mb_machine *m, const PairProfDesc *d, int n
 int launch_profile_pair_counts(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, int groupsPerPair, const int *inTok, const double *logP,
                                const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
   return pair_counts<EnvGeom>(m, d, t, n, groupsPerPair, inTok, logP, fwdPool, bwdPool, counts, st);
+}
+
+template <template <bool> class Geom>
+static int pair_rowpost(const mb_machine *m, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, int groupsPerPair, int tabMax, const int *inTok,
+                        const double *logP, const double *fwdPool, const double *bwdPool, double *post, hipStream_t st) {
+  if (n <= 0) return 0;
+  k_profile_pair_rowpost<Geom><<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(ROWPOST_THREADS), 0, st>>>(m->dev, d, t, groupsPerPair, inTok, logP, fwdPool, bwdPool, post, tabMax,
+                                                                                                              g_deterministic ? 1 : 0);
+  return hip_ok(hipGetLastError(), Geom<true>::ENV ? "k_profile_pair_env_rowpost" : "k_profile_pair_rowpost") ? 0 : 1;
+}
+int launch_profile_pair_rowpost(const mb_machine *m, const PairProfDesc *d, int n, int groupsPerPair, int tabMax, const int *inTok, const double *logP,
+                                const double *fwdPool, const double *bwdPool, double *post, hipStream_t st) {
+  return pair_rowpost<FullGeom>(m, d, {}, n, groupsPerPair, tabMax, inTok, logP, fwdPool, bwdPool, post, st);
+}
+int launch_profile_pair_rowpost(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, int groupsPerPair, int tabMax, const int *inTok,
+                                const double *logP, const double *fwdPool, const double *bwdPool, double *post, hipStream_t st) {
+  return pair_rowpost<EnvGeom>(m, d, t, n, groupsPerPair, tabMax, inTok, logP, fwdPool, bwdPool, post, st);
 }
 
 template <template <bool> class Geom>

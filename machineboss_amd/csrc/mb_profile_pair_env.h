@@ -37,6 +37,8 @@ int launch_profile_pair_bwd(const mb_machine *m, const PairEnvDesc *d, const Pai
                             double *pool, double *loglike, hipStream_t st);
 int launch_profile_pair_counts(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, int groupsPerPair, const int *inTok, const double *logP,
                                const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
+int launch_profile_pair_rowpost(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, int groupsPerPair, int tabMax, const int *inTok,
+                                const double *logP, const double *fwdPool, const double *bwdPool, double *post, hipStream_t st);
 int launch_profile_pair_traceback(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, const int *inTok, const double *logP, const double *pool,
                                   uint32_t *edges, int32_t *rows, long long *len, hipStream_t st);
 

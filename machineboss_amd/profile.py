@@ -676,6 +676,35 @@ class PairProfileDP(ProfileDP):
             blanks.append(blank)
         return out, ll
 
+    def rowPosteriors(self, x, P, env=None) -> Tuple[np.ndarray, float]:
+        """(post[L, nOutTok + 1], Forward loglike): post[r][o] is the posterior probability that row r was consumed as output token
+        o (column 0: as the blank) -- the emitting terms of counts() and its blank term, binned by (row, column) instead of by
+        transition, which is the gradient of loglike in P[r][o] (docs/profile_tapes.md, "Row posteriors").  Every row sums to 1;
+        zeros for a -inf pair; exactly 0 where P[r][o] is -inf."""
+        x, P = self._checkPair(x, P)
+        ll, NF, WF = self.forward(x, P) if env is None else self.forward(x, P, env=env)
+        I, L = len(x), len(P)
+        post = np.zeros((L, self.em.nOutTok + 1))
+        if not ll > _NEG:
+            return post, ll
+        _, NB, WB = self.backward(x, P) if env is None else self.backward(x, P, env=env)
+        inside = self.envelopeRows(env, I, L)
+        with np.errstate(invalid="ignore"):
+            for i in range(I + 1):
+                for r in (range(L) if inside is None else inside[i]):
+                    if r == L:
+                        continue
+                    f = WF[i, r] - ll
+                    b = (NF[i, r] - ll) + (P[r][0] + NB[i, r + 1])
+                    post[r, 0] += float(np.exp(b[b > _NEG]).sum())
+                    if i < I:
+                        _, s, d, w, o = self.match[x[i]]
+                        t = f[s] + ((w + P[r][o]) + NB[i + 1, r + 1][d])
+                        np.add.at(post[r], o[t > _NEG], np.exp(t[t > _NEG]))
+                    t = f[self.eS] + ((self.eW + P[r][self.eO]) + NB[i, r + 1][self.eD])
+                    np.add.at(post[r], np.asarray(self.eO)[t > _NEG], np.exp(t[t > _NEG]))
+        return post, ll
+
     def viterbi(self, x, P, census: Optional[dict] = None, env=None) -> Tuple[float, np.ndarray, np.ndarray]:
         """(score, global edge ids start -> end, row at which each fired); the first maximum in the fill's candidate order.  The
         row of an emitting edge is the row it consumed, of an output-less edge the number of rows consumed before it; the input
