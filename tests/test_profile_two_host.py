@@ -304,3 +304,46 @@ def test_two_suite_inputs_are_live():
     em, A, B, Afar, Bfar = th.far_case()
     ll, far = TwoProfileDP(em).forward(A, B)[0], TwoProfileDP(em).forward(Afar, Bfar)[0]
     assert ll > -math.inf and abs(far - (ll + 18 * th.FAR_SHIFT)) <= 1e-9 * abs(far)
+
+
+def test_two_edge_inputs_are_live():
+    """test_profile_two_edges_gpu.py: the group rule of mb_profile_twos_counts restated (a workgroup per 2 048 (cell, state) items of
+    the largest lattice of a launch) and the shapes on either side of its marks; every transition of the group cases with a
+    positive count, so that an item left out cannot hide in a zero; the chunking of the budgets restated, with the dead pair and
+    (0, 0) inside a chunk; and nine in ten of the 126 live pairs of the traceback case with a path."""
+    S = th.GROUP_S
+    items = [S * (K + 1) * (L + 1) for K, L in th.GROUP_SHAPES]
+    assert items == [2040, 2050, 2050, 4205, 10240, 10400, 10400, 20800] and S % 2 == 1
+    assert [th.count_groups(S, [s]) for s in th.GROUP_SHAPES] == list(th.GROUP_COUNTS) and th.GROUP_COUNTS[:4] == (1, 2, 2, 3)
+    assert th.GROUP_COUNTS[4:] == (5, 6, 6, 11) and 4205 % (3 * 256) == 256 + 109          # the last stride: group 0, a part of group 1
+    assert th.count_groups(S, th.GROUP_RAGGED) == 11 and all(th.count_groups(S, [s]) == 1 for s in th.GROUP_RAGGED[1:])
+    assert th.count_groups(1, [(0, 0)]) == 1 and th.count_groups(700, [(3, 4)]) == 7 and th.count_groups(8, [(999, 999)]) == 256
+    em, singles, ragged, dead = th.group_case()
+    dp = TwoProfileDP(em)
+    assert np.array_equal(ragged[0][0], singles[-1][0]) and np.array_equal(ragged[0][1], singles[-1][1])
+    for A, B in singles:
+        c, ll = dp.counts(A, B)
+        assert ll > -math.inf and (c > 0).all(), (len(A), len(B), ll, c.min())
+    assert all(dp.forward(A, B)[0] > -math.inf for A, B in ragged[1:]) and dp.forward(*dead)[0] == -math.inf
+    em, pairs = th.split_case()
+    dp = TwoProfileDP(em)
+    lls = [dp.forward(A, B)[0] > -math.inf for A, B in pairs]
+    assert [(len(A), len(B)) for A, B in pairs] == list(th.SPLIT_SHAPES) and lls == [k != th.SPLIT_DEAD for k in range(len(pairs))], lls
+    assert all(len(dp.viterbi(A, B)[1]) > 0 for k, (A, B) in enumerate(pairs) if k != th.SPLIT_DEAD)
+    bounds = [th.path_bound(len(dp.fLevels), K, L) for K, L in th.SPLIT_SHAPES]
+    for sizes, slack in (([th.count_bytes(th.SPLIT_S, K, L) for K, L in th.SPLIT_SHAPES], 4096),
+                         ([th.path_bytes(th.SPLIT_S, K, L, b) for (K, L), b in zip(th.SPLIT_SHAPES, bounds)], 1024)):
+        chunks = th.lattice_chunks(sizes, 2 * max(sizes) + slack)
+        assert len(chunks) >= 3 and chunks[0][0] == 0 and chunks[-1][1] == len(sizes) and all(a[1] == b[0] for a, b in zip(chunks, chunks[1:]))
+        assert all(sum(sizes[p0:p1]) <= 2 * max(sizes) + slack for p0, p1 in chunks)
+        for inside in (th.SPLIT_DEAD, th.SPLIT_SHAPES.index((0, 0))):
+            assert any(p0 < inside < p1 - 1 for p0, p1 in chunks), (inside, chunks)
+    em, pairs = th.chain_case()
+    sizes = [th.path_bytes(th.CHAIN_S, len(A), len(B), th.path_bound(th.CHAIN_S - 1, len(A), len(B))) for A, B in pairs] * 2
+    assert len(th.lattice_chunks(sizes, 2 * max(sizes) + 1024)) >= 3
+    em, pairs = th.seam_case()
+    dp = TwoProfileDP(em)
+    lls = [dp.forward(A, B, "max")[0] > -math.inf for A, B in pairs]
+    assert len(pairs) == 129 and th.SEAM_DEAD == (63, 64, 128) and not any(lls[k] for k in th.SEAM_DEAD)
+    assert np.mean(np.delete(lls, th.SEAM_DEAD)) >= 0.9, np.mean(np.delete(lls, th.SEAM_DEAD))
+    assert [(len(A), len(B)) for k, (A, B) in enumerate(pairs) if k not in th.SEAM_DEAD][:6] == list(th.SEAM_SHAPES)

@@ -1,5 +1,5 @@
 """Machines, profiles, bounds and the device-against-restatement comparison of the two-profile tests (test_profile_two_host.py,
-test_profile_two_gpu.py; not a test module).  The bounds are those of pairprofilehelpers."""
+test_profile_two_gpu.py, test_profile_two_edges_gpu.py; not a test module).  The bounds are those of pairprofilehelpers."""
 import math
 
 import numpy as np
@@ -208,6 +208,120 @@ def chain_case():
         A, B = two_input(np.random.RandomState(500 + k), em, K, L, pInf=0.0)
         A = A.copy(); B = B.copy(); A[:, 0] = -np.inf; B[:, 0] = -np.inf
         pairs.append((A, B))
+    return em, pairs
+
+
+# ---- where the host splits a call (test_profile_two_edges_gpu.py; held to its liveness conditions without a GPU by
+# test_profile_two_host.py::test_two_edge_inputs_are_live) ---------------------------------------------------------------------------
+COUNT_GROUP_ITEMS = 2048                          # (cell, state) items of the largest lattice per count workgroup of a pair
+COUNT_GROUPS_MAX = 256
+
+
+def count_groups(S, shapes):
+    """Workgroups per pair of one counts launch, as mb_profile_twos_counts has it: one per 2 048 items of the largest lattice of
+    the launch, an item a state of a cell -- S (K + 1)(L + 1) of them --, at least one and at most 256."""
+    items = max(S * (K + 1) * (L + 1) for K, L in shapes)
+    return min(COUNT_GROUPS_MAX, max(1, -(-items // COUNT_GROUP_ITEMS)))
+
+
+def lattice_chunks(sizes, budget):
+    """[(p0, p1)]: lattice_chunks of mb_api.hip restated -- chunks of at most ``budget`` bytes, evened out to within a twentieth."""
+    total = float(sum(sizes))
+    n = max(1.0, math.ceil(total / budget))
+    share = min(float(budget), total / n * 1.05)
+    out, p0, acc = [], 0, 0.0
+    for k, b in enumerate(sizes):
+        if k > p0 and (acc + b > budget or (acc >= share and acc + b > share)):
+            out.append((p0, k)); p0, acc = k, 0.0
+        acc += b
+    return out + ([(p0, len(sizes))] if len(sizes) > p0 else [])
+
+
+def dead_pair(rng, em, K, L, row):
+    """A pair whose output profile has one row all -inf: likelihood -inf, an empty path, no counts."""
+    A, B = two_input(rng, em, K, L, pInf=0.0)
+    B = B.copy(); B[row] = -np.inf
+    return A, B
+
+
+GROUP_S = 5
+# 2 040 items: one group (409 cells, the last count below 2 048 / 5, is prime); 2 050: two, the short side found by i and by r;
+# 4 205: three, and the sixth stride of 768 stops at item 365 -- group 0 whole, group 1 in part, group 2 not at all; then
+# 10 240 = 5 x 2 048 against 10 400: the last lattice of five groups and the first of six, by i and by r; 20 800: eleven
+GROUP_SHAPES = ((23, 16), (9, 40), (40, 9), (28, 28), (31, 63), (31, 64), (64, 31), (63, 64))
+GROUP_COUNTS = (1, 2, 2, 3, 5, 6, 6, 11)
+GROUP_RAGGED = ((63, 64), (2, 3), (0, 0), (0, 5), (5, 0))
+
+
+def group_machine():
+    return pair_machine(GROUP_S, 5, True, 2, 3)
+
+
+def group_pair(em, K, L):
+    return two_input(np.random.RandomState(7000 + 100 * K + L), em, K, L, pInf=0.0)
+
+
+def group_case():
+    """(em, one pair per shape of GROUP_SHAPES, the ragged batch, a dead pair): an odd S, so that a stride of 256 lanes does not end
+    on a cell; the first pair of the ragged batch is the last of the shapes."""
+    em = group_machine()
+    return em, [group_pair(em, K, L) for K, L in GROUP_SHAPES], [group_pair(em, K, L) for K, L in GROUP_RAGGED], dead_pair(np.random.RandomState(7999), em, 5, 6, 2)
+
+
+def fixed_counts_close(got, want, cells):
+    """counts_close with the error of MB_DETERMINISTIC's fixed point added: ``cells`` adds to a transition at most, each rounded to
+    the nearest 2^-36."""
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    return bool(np.all(np.abs(got - want) <= np.where(want >= 1e-3, 0.0, 1e-9) + 1e-6 * want + cells * 2.0 ** -37))
+
+
+SPLIT_S = 8
+SPLIT_SHAPES = ((9, 9), (2, 5), (0, 0), (7, 9), (0, 4), (6, 7), (9, 6), (4, 0), (5, 2), (9, 9))
+SPLIT_DEAD = 5                                     # the (6, 7) pair
+
+
+def split_machine():
+    return pair_machine(SPLIT_S, 108, True, 2, 3)
+
+
+def split_case():
+    """(em, pairs): ten ragged pairs on the levelled machine of 8 states, the fifth of them dead."""
+    em = split_machine()
+    pairs = [two_input(np.random.RandomState(8000 + 100 * k + 10 * K + L), em, K, L, pInf=0.0) for k, (K, L) in enumerate(SPLIT_SHAPES)]
+    pairs[SPLIT_DEAD] = dead_pair(np.random.RandomState(8999), em, *SPLIT_SHAPES[SPLIT_DEAD], 3)
+    return em, pairs
+
+
+def count_bytes(S, K, L):
+    """What lattice_chunks is told a pair costs mb_profile_twos_counts: the Forward and the Backward lattice."""
+    return 2 * 8 * 3 * S * (K + 1) * (L + 1)
+
+
+def path_bytes(S, K, L, bound):
+    """And mb_profile_twos_viterbi: the max lattice and a traceback slot of ``bound`` entries in three arrays of four bytes."""
+    return 8 * 3 * S * (K + 1) * (L + 1) + 12 * bound
+
+
+def path_bound(nLevels, K, L):
+    """The size of a traceback slot: K + L edges that read or write, and between them runs of at most ``nLevels`` silent ones."""
+    return K + L + (K + L + 1) * nLevels
+
+
+SEAM_PAIRS = 129
+SEAM_DEAD = (63, 64, 128)                          # the last lane of block 0, the first of block 1, the only one of block 2
+SEAM_SHAPES = SUITE_SHAPES[:-1]
+
+
+def seam_case():
+    """(em, pairs): 129 pairs on the machine of split_case, the shapes of the suite below (9, 9) in turn, a tenth of the weights
+    -inf; three dead pairs at the seams of the traceback's blocks of 64 lanes."""
+    em = split_machine()
+    pairs = []
+    for k in range(SEAM_PAIRS):
+        K, L = SEAM_SHAPES[k % len(SEAM_SHAPES)]
+        pairs.append(two_input(np.random.RandomState(9000 + k), em, K, L, pInf=0.1))
+    for k in SEAM_DEAD:
+        pairs[k] = dead_pair(np.random.RandomState(9000 + k), em, 3, 4, 1)
     return em, pairs
 
 
