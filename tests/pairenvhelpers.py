@@ -6,6 +6,7 @@ import math
 import numpy as np
 
 import pairprofilehelpers as ph
+from mergehelpers import greedy_chunks
 from pairprofilehelpers import counts_close, logs_close, pair_input, pair_machine
 from machineboss_amd.machine import MachineError
 from machineboss_amd.seqpair import Envelope
@@ -267,3 +268,211 @@ def check_env_batch(em, triples, fill=False, live=None):
     finally:
         dev.close(); dm.close()
     return refs
+
+
+# ---- a call that mixes plain and enveloped pairs (test_profile_pair_mixed_gpu.py; held to its conditions without a GPU by
+# test_profile_pair_env_host.py) ---------------------------------------------------------------------------------------------------------
+# pair_profile_descs (mb_api.hip) launches a chunk's plain pairs first and its enveloped pairs second and writes the per-pair outputs
+# in that order: slot = rank among the chunk's plain pairs, or nPlain + rank among its enveloped ones.
+MIXED_STATES = (8, 65)
+MIXED_SEED = {8: 208, 65: 265}
+# (I, L, envelope or None, dead): enveloped first and plain last, so that slot order differs from pair order at both ends
+MIXED_SPEC = ((9, 9, "band0", False), (20, 14, None, False), (0, 0, "full", False), (0, 0, None, False), (18, 14, None, False),
+              (5, 6, None, True), (0, 6, None, False), (20, 14, "full", False), (12, 12, "band1", False), (6, 6, "stairs", False),
+              (8, 7, "band2", True), (6, 0, "full", False), (19, 13, None, False), (20, 14, "area", False), (0, 5, "full", False),
+              (4, 0, None, False), (11, 8, "full", False), (10, 13, "band2", False), (9, 4, None, False), (3, 8, None, False))
+MIXED_DEAD = tuple(k for k, s in enumerate(MIXED_SPEC) if s[3])
+
+
+def named_envelope(kind, rng, I, L):
+    if kind is None:
+        return None
+    if kind == "full":
+        return full(I, L)
+    if kind == "stairs":
+        return staircase(I, L)
+    if kind == "area":
+        return Envelope.pathAreaEnvelope(random_alignment(rng, I, L), 2)
+    return Envelope.band(I, L, int(kind[4:]))
+
+
+def mixed_case(S):
+    """(em, [(x, P, env or None)]): MIXED_SPEC on the machine of S states with silent levels; a dead pair has its middle row all -inf."""
+    em = pair_machine(S, MIXED_SEED[S], True, 2, 3)
+    triples = []
+    for k, (I, L, kind, dead) in enumerate(MIXED_SPEC):
+        rng = np.random.RandomState(7000 * S + 100 * k + 10 * I + L)
+        x, P = pair_input(rng, em, I, L)
+        if dead:
+            P = P.copy(); P[L // 2] = -np.inf
+        triples.append((x, P, named_envelope(kind, rng, I, L)))
+    return em, triples
+
+
+def mixed_states(triples):
+    """The envelope states of section 4, in order: all plain, the mix, every pair enveloped (full for the plain ones), the mix with
+    plain and enveloped swapped (a formerly plain pair under band(3), or the full envelope where its slope needs more), none."""
+    envs = [t[2] for t in triples]
+    swapped = []
+    for x, P, env in triples:
+        if env is not None:
+            swapped.append(None)
+            continue
+        try:
+            swapped.append(Envelope.band(len(x), len(P), 3))
+        except MachineError:
+            swapped.append(full(len(x), len(P)))
+    return [("plain", [None] * len(envs)), ("mixed", envs), ("all", [e if e is not None else full(len(x), len(P)) for (x, P, _), e in zip(triples, envs)]),
+            ("swapped", swapped), ("cleared", None)]
+
+
+def slots(envs):
+    """slot[k] of PairProfPlan for one chunk whose pairs have these envelopes."""
+    nPlain = sum(e is None for e in envs)
+    out, p, e = [], 0, 0
+    for env in envs:
+        if env is None:
+            out.append(p); p += 1
+        else:
+            out.append(nPlain + e); e += 1
+    return out
+
+
+LDS_MAX = 160 * 1024
+CALLS = ("forward", "viterbi", "counts", "posteriors", "rolling")
+
+
+def silent_levels(em):
+    """nLevF - 1 of the device's machine: the silent levels of the restatement."""
+    from machineboss_amd.profile import PairProfileDP
+    return len(PairProfileDP(em).fLevels)
+
+
+def lattice_doubles(S, x, P, env):
+    """pp_cells: the rectangle's two layers, or those of the compact lattice of the envelope."""
+    return 2 * S * (n_cells(env) if env is not None else (len(x) + 1) * (len(P) + 1))
+
+
+def path_bound(nLevels, I, L):
+    """profile_pair_path_bound with nLevels = nLevF - 1."""
+    return I + L + (I + L + 1) * nLevels
+
+
+def scratch_ring_bytes(S, x, P, env):
+    """pp_ring_bytes of the rolling sweeps: 0 where the ring lies in LDS."""
+    b = 48 * S * (diag_max(env) if env is not None else min(len(x), len(P)) + 1)
+    return 0 if b <= LDS_MAX else b
+
+
+def call_bytes(call, em, triples, nLevels=None):
+    """What each call of mb_api.hip tells lattice_chunks a pair costs: the lattice for materialised Forward, the traceback slot on
+    top of it for Viterbi with paths, two lattices for counts, the pair's bins beside them for row posteriors, the scratch ring
+    alone for the rolling sweeps."""
+    S, C = em.nStates, em.nOutTok + 1
+    nLevels = silent_levels(em) if nLevels is None and call == "viterbi" else nLevels
+    out = []
+    for x, P, env in triples:
+        cells = 8 * lattice_doubles(S, x, P, env)
+        out.append({"forward": cells, "viterbi": cells + 8 * path_bound(nLevels or 0, len(x), len(P)), "counts": 2 * cells,
+                    "posteriors": 2 * cells + 8 * len(P) * C, "rolling": scratch_ring_bytes(S, x, P, env)}[call])
+    return out
+
+
+def chunk_kinds(chunks, envs):
+    """Per chunk "P" (plain pairs only), "E" (enveloped only), "PE" (mixed, its first pair plain) or "EP"."""
+    out = []
+    for p0, p1 in chunks:
+        kinds = ["E" if e is not None else "P" for e in envs[p0:p1]]
+        out.append(kinds[0] if len(set(kinds)) == 1 else kinds[0] + ("E" if kinds[0] == "P" else "P"))
+    return out
+
+
+def chunk_launches(chunks, envs):
+    """pp_chunk_launches summed: two for a chunk that holds both kinds."""
+    return sum(2 if len(k) == 2 else 1 for k in chunk_kinds(chunks, envs))
+
+
+# The budget of the chunked calls of the mixed batch, in units of the largest pair's bytes under that call (at or above 1.2, below
+# which a pair alone may be refused): five chunks for each of the four calls at S = 8 and at S = 65 -- pairs 0-3 (mixed, the first
+# enveloped), 4-6 (plain), 7-11 (enveloped), 12-13 (mixed, the first plain), 14-19 (mixed, the first enveloped)
+MIXED_BUDGET_FACTOR = 1.8
+MIXED_CHUNKS = [(0, 4), (4, 7), (7, 12), (12, 14), (14, 20)]
+MIXED_CHUNK_KINDS = ["EP", "P", "E", "PE", "EP"]
+
+
+def mixed_budget(call, em, triples):
+    return int(MIXED_BUDGET_FACTOR * max(call_bytes(call, em, triples)))
+
+
+# ---- rolling sweeps in chunks: scratch rings at S = 300 ----------------------------------------------------------------------------
+ROLL_SHAPE = (12, 14)                    # a ring of 48 * 13 * 300 = 187 200 bytes, plain or under band(12) (M = 13): past 160 KiB
+ROLL_ORDER = "EpPPeEEEePPp"              # E, P: (12, 14) with a scratch ring; e, p: (3, 3), ring in LDS, no bytes: they ride along
+ROLL_CHUNKS = ("EP", "PE", "EE", "PP")   # of the ring-bearing pairs, under a budget of 2.5 rings
+
+
+def roll_case():
+    """(em, triples): pack_case's machine; eight pairs at (12, 14) in the order E P P E E E P P and two small pairs of each kind."""
+    em = pair_machine(PACK[0], 301, True, 2, 3)
+    triples = []
+    for k, c in enumerate(ROLL_ORDER):
+        I, L = ROLL_SHAPE if c in "EP" else (3, 3)
+        x, P = pair_input(np.random.RandomState(3300 + k), em, I, L)
+        triples.append((x, P, Envelope.band(I, L, 12 if c == "E" else 1) if c in "Ee" else None))
+    return em, triples
+
+
+ROLL_BUDGET = 5 * 187200 // 2
+
+
+# ---- the traceback past one block of 64 lanes, in each of the two launches of a call ----------------------------------------------------
+SEAM_PLAIN, SEAM_ENV = 129, 65
+SEAM_DEAD_PLAIN, SEAM_DEAD_ENV = (63, 64, 128), (63, 64)      # by slot within the launch
+SEAM_SHAPES = ((0, 0), (0, 3), (3, 0), (1, 1), (2, 4), (4, 2), (4, 4), (3, 3))
+
+
+def seam_case():
+    """(em, triples): 194 pairs at S = 8 with levels, two plain pairs then an enveloped one, 64 times, then one of each; the
+    envelopes in turn from envelopes() of the shape; dead pairs at the seams of both launches' blocks."""
+    em = pair_machine(8, 208, True, 2, 3)
+    kinds = "PPE" * 64 + "EP"
+    triples, nP, nE = [], 0, 0
+    for k, c in enumerate(kinds):
+        I, L = SEAM_SHAPES[k % len(SEAM_SHAPES)]
+        dead = (nP in SEAM_DEAD_PLAIN) if c == "P" else (nE in SEAM_DEAD_ENV)
+        if dead:
+            I, L = 3, 4
+        rng = np.random.RandomState(9100 + k)
+        x, P = pair_input(rng, em, I, L)
+        if dead:
+            P = P.copy(); P[1] = -np.inf
+        env = None
+        if c == "E":
+            es = envelopes(rng, I, L)
+            env = es[nE % len(es)][1]
+        triples.append((x, P, env))
+        nP += c == "P"; nE += c == "E"
+    return em, triples
+
+
+def seam_prefix(triples, n):
+    """The indices of the pairs whose slot within their launch is below n."""
+    out, nP, nE = [], 0, 0
+    for k, t in enumerate(triples):
+        if (nE if t[2] is not None else nP) < n:
+            out.append(k)
+        nP += t[2] is None; nE += t[2] is not None
+    return out
+
+
+# ---- row posteriors past 1 024 row blocks ---------------------------------------------------------------------------------------------------
+WRAP_SHAPE = (1, 1100)
+WRAP_GROUPS = 1024                       # the cap of mb_profile_pairs_row_posteriors on a pair's workgroups
+
+
+def wrap_case():
+    """(em, x, P, Pdead): S = 2 with levels, nOut = 3 (C = 4), one input symbol against 1 100 rows; the dead profile has row 1 050,
+    past the first pass of the row-block loop, all -inf."""
+    em = pair_machine(2, 222, True, 2, 3)
+    x, P = pair_input(np.random.RandomState(1100), em, *WRAP_SHAPE)
+    Pd = P.copy(); Pd[1050] = -np.inf
+    return em, x, P, Pd

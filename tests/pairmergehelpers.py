@@ -211,3 +211,24 @@ def check_machine(em, colTok, pairs, fill=True, live=None):
     finally:
         dev.close(); dm.close()
     return refs
+
+
+# ---- the traceback past one block of 64 lanes (test_profile_pair_mixed_gpu.py) -------------------------------------------------------------
+SEAM_PAIRS = 129
+SEAM_DEAD = (63, 64, 128)                        # the last lane of block 0, the first of block 1, the only one of block 2
+SEAM_COLTOK = (1, 2)
+SEAM_SHAPES = ((0, 0), (0, 3), (3, 0), (1, 1), (2, 3), (3, 2), (3, 3))
+
+
+def seam_case():
+    """(em, colTok, pairs): 129 pairs at S = 8 with levels against merged profiles of two columns, the shapes in turn; three dead
+    pairs (a row all -inf) at the seams of k_profile_pair_merge_traceback's blocks."""
+    em = pair_machine(8, 208, True, 2, 3)
+    pairs = []
+    for k in range(SEAM_PAIRS):
+        I, L = (3, 3) if k in SEAM_DEAD else SEAM_SHAPES[k % len(SEAM_SHAPES)]
+        x, P = merged_input(np.random.RandomState(9200 + k), em, 2, I, L, zeros=0.1)
+        if k in SEAM_DEAD:
+            P[1] = -np.inf
+        pairs.append((x, P))
+    return em, SEAM_COLTOK, pairs

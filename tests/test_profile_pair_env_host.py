@@ -219,6 +219,112 @@ def test_tie_batch_shows_every_tie_with_a_loser_outside():
         assert census.get(("outside", kind), 0) >= 1, census
 
 
+# ---- the inputs of test_profile_pair_mixed_gpu.py: one call over plain and enveloped pairs ----------------------------------------------
+def _envs(triples):
+    return [t[2] for t in triples]
+
+
+@pytest.mark.parametrize("S", eh.MIXED_STATES)
+def test_mixed_batch_composition_and_liveness(S):
+    """mixed_case: an enveloped pair first and a plain one last; bands of width 0, 1 and 2, a path-area envelope, a staircase whose
+    rows are single cells and full envelopes; (0, 0), no rows, no input and a dead pair of each kind; shapes up to (20, 14).  All
+    but the two dead pairs have a finite likelihood and, where I + L > 0, a path."""
+    em, triples = eh.mixed_case(S)
+    spec = eh.MIXED_SPEC
+    envs = _envs(triples)
+    assert len(triples) == len(spec) >= 12 and em.nStates == S and eh.silent_levels(em) >= 1
+    assert envs[0] is not None and envs[-1] is None
+    sl = eh.slots(envs)
+    assert sorted(sl) == list(range(len(sl))) and sl[0] == sum(e is None for e in envs) and sl[-1] == sl[0] - 1
+    kinds = "".join("E" if e is not None else "P" for e in envs)
+    assert "PP" in kinds and "EE" in kinds and "PEP" in kinds and "EPE" in kinds      # (the two kinds alternate irregularly)
+    assert {s[2] for s in spec} == {None, "band0", "band1", "band2", "area", "stairs", "full"}
+    for (x, P, env), (I, L, kind, dead) in zip(triples, spec):
+        assert (len(x), len(P)) == (I, L) and (env is None) == (kind is None)
+        if env is not None:
+            assert env.connected() and env.monotone() and len(env.inStart) == L + 1
+    stairs = triples[[s[2] for s in spec].index("stairs")][2]
+    assert all(b - a == 1 for a, b in zip(stairs.inStart, stairs.inEnd))
+    area = [t[2] for t, s in zip(triples, spec) if s[2] == "area"][0]
+    assert not area.isFull() and eh.n_cells(area) > 20 + 14 + 1
+    for kind in (False, True):      # plain, enveloped
+        mine = [(s[0], s[1]) for s in spec if (s[2] is not None) == kind and not s[3]]
+        assert (0, 0) in mine and any(I > 0 and L == 0 for I, L in mine) and any(I == 0 and L > 0 for I, L in mine)
+        assert sum(1 for s in spec if (s[2] is not None) == kind and s[3]) == 1
+    assert max(s[0] for s in spec) == 20 and max(s[1] for s in spec) == 14
+    dp = PairProfileDP(em)
+    lls = np.array([dp.forward(x, P, env=env)[0] for x, P, env in triples])
+    assert _live(lls) >= 0.85, _live(lls)
+    assert [k for k, v in enumerate(lls) if v == -math.inf] == list(eh.MIXED_DEAD)
+    for k, (x, P, env) in enumerate(triples):
+        v, edges, rows = dp.viterbi(x, P, env=env)
+        assert (len(edges) > 0) == (k not in eh.MIXED_DEAD) or len(x) + len(P) == 0, k
+    for name, state in eh.mixed_states(triples):
+        assert state is None or len(state) == len(triples)
+    swapped = dict(eh.mixed_states(triples))["swapped"]
+    assert all((a is None) != (b is None) for a, b in zip(envs, swapped))
+
+
+@pytest.mark.parametrize("S", eh.MIXED_STATES)
+def test_mixed_batch_chunks_hold_every_kind_of_chunk(S):
+    """Under 1.8 x the largest pair's bytes each of the four materialised calls cuts the batch into the same five chunks, by the
+    restated chunk rule over the restated bytes: a mixed chunk whose first pair is enveloped, a plain one, an enveloped one, a
+    mixed one whose first pair is plain, and a mixed one again."""
+    em, triples = eh.mixed_case(S)
+    envs = _envs(triples)
+    assert eh.MIXED_BUDGET_FACTOR >= 1.2
+    for call in eh.CALLS[:4]:
+        b = eh.call_bytes(call, em, triples)
+        assert all(v > 0 for v in b)
+        chunks = eh.greedy_chunks(b, eh.mixed_budget(call, em, triples))
+        assert chunks == eh.MIXED_CHUNKS and len(chunks) >= 4, (call, chunks)
+        assert eh.chunk_kinds(chunks, envs) == eh.MIXED_CHUNK_KINDS and set(eh.MIXED_CHUNK_KINDS) == {"P", "E", "PE", "EP"}
+        assert eh.chunk_launches(chunks, envs) == 8
+        live = [k for k in range(len(triples)) if k not in eh.MIXED_DEAD]
+        sub = [triples[k] for k in live]
+        assert len(eh.greedy_chunks(eh.call_bytes(call, em, sub), eh.mixed_budget(call, em, sub))) >= 4
+    assert eh.call_bytes("rolling", em, triples) == [0] * len(triples)      # every ring in LDS: the rolling sweeps do not chunk here
+
+
+def test_rolling_chunks_of_the_scratch_rings():
+    """roll_case: eight rings of 187 200 bytes, plain (48 x 13 x 300) and under band(12) (M = 13), past 160 KiB and so in scratch;
+    four small pairs whose rings lie in LDS cost nothing and ride in the chunk they fall in.  A budget of 2.5 rings cuts the
+    ring-bearing pairs into (E, P), (P, E), (E, E), (P, P); the last two chunks hold one kind only, small pairs included."""
+    em, triples = eh.roll_case()
+    envs = _envs(triples)
+    b = eh.call_bytes("rolling", em, triples)
+    assert em.nStates == 300 and [v for v in b if v] == [187200] * 8 and 187200 > eh.LDS_MAX
+    assert [eh.diag_max(e) for e, c in zip(envs, eh.ROLL_ORDER) if c == "E"] == [13] * 4
+    assert ["E" if e is not None else "P" for e in envs] == [c.upper() for c in eh.ROLL_ORDER]
+    chunks = eh.greedy_chunks(b, eh.ROLL_BUDGET)
+    assert chunks == [(0, 3), (3, 6), (6, 9), (9, 12)]
+    rings = ["".join(c for c in eh.ROLL_ORDER[p0:p1] if c in "EP") for p0, p1 in chunks]
+    assert tuple(rings) == eh.ROLL_CHUNKS
+    assert eh.chunk_kinds(chunks, envs) == ["EP", "PE", "E", "P"] and eh.chunk_launches(chunks, envs) == 6
+    dp = PairProfileDP(em)
+    assert all(dp.forward(x, P, env=env)[0] > -math.inf for x, P, env in triples)
+
+
+def test_seam_batch_puts_dead_pairs_at_the_block_seams_of_both_launches():
+    """seam_case: 129 plain and 65 enveloped pairs interleaved; by slot within their launch the dead pairs are 63, 64 and 128 of the
+    plain launch and 63 and 64 of the enveloped one; every other pair has a path."""
+    em, triples = eh.seam_case()
+    envs = _envs(triples)
+    assert sum(e is None for e in envs) == eh.SEAM_PLAIN == 129 and sum(e is not None for e in envs) == eh.SEAM_ENV == 65
+    assert max(max(len(x), len(P)) for x, P, _ in triples) <= 4
+    sl = eh.slots(envs)
+    dp = PairProfileDP(em)
+    dead = sorted(sl[k] for k, (x, P, env) in enumerate(triples) if dp.forward(x, P, "max", env=env)[0] == -math.inf)
+    assert dead == sorted(eh.SEAM_DEAD_PLAIN + tuple(129 + s for s in eh.SEAM_DEAD_ENV))
+    assert len(eh.seam_prefix(triples, 64)) == 128 and len(eh.seam_prefix(triples, 65)) == 130
+    for n in (64, 65):
+        sub = [envs[k] for k in eh.seam_prefix(triples, n)]
+        assert sum(e is None for e in sub) == sum(e is not None for e in sub) == n
+    kinds = {kind for k, (x, P, env) in enumerate(triples) if env is not None
+             for kind, e in eh.envelopes(np.random.RandomState(0), len(x), len(P)) if (e.inStart, e.inEnd) == (env.inStart, env.inEnd)}
+    assert {"full", "band0", "stairs"} <= kinds
+
+
 # ---- the command line ---------------------------------------------------------------------------------------------------------------------
 CSV = os.path.join(HERE, "golden", "csv", "tiny_uc.csv")
 DNASTORE = os.path.join(HERE, "golden", "machine", "dnastore4.json")

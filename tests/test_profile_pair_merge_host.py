@@ -231,3 +231,15 @@ def test_edge_suite_inputs_are_live():
         dp = PairMergedProfileDP(em, colTok)
         fin = [dp.forward(x, P)[0] > -math.inf for x, P in pairs]
         assert sum(fin) >= len(fin) - 1, name
+
+
+def test_merged_seam_batch_is_live_but_at_the_seams():
+    """seam_case of test_profile_pair_mixed_gpu.py: 129 pairs at shapes up to (3, 3) against two columns; the pairs at 63, 64 and
+    128 -- the seams of the traceback's blocks of 64 lanes -- are dead and every other pair has a Viterbi path."""
+    em, colTok, pairs = pm.seam_case()
+    assert len(pairs) == pm.SEAM_PAIRS == 129 and pm.SEAM_DEAD == (63, 64, 128) and len(colTok) == 2 and em.nStates == 8
+    assert max(max(len(x), len(P)) for x, P in pairs) <= 3
+    dp = PairMergedProfileDP(em, colTok)
+    for k, (x, P) in enumerate(pairs):
+        v, edges, rows = dp.viterbi(x, P)
+        assert (v == -math.inf) == (k in pm.SEAM_DEAD) and (len(edges) == 0) == (k in pm.SEAM_DEAD), k

@@ -119,6 +119,35 @@ def test_row_posteriors_are_the_gradient_of_forward(band):
     assert n >= 50
 
 
+def test_wrap_case_has_more_row_blocks_than_a_pair_has_workgroups():
+    """wrap_case of test_profile_pair_mixed_gpu.py: (1, 1 100) at S = 2, C = 4.  With a table of 4 doubles a block is one row
+    (profile_pair_rowpost_rows: tabMax / C), with 2 a row does not fit it and a block is one row as well: 1 100 blocks for the
+    1 024 workgroups a pair gets at the most, so 76 workgroups take a second block.  The default table holds 1 024 rows: two blocks.
+    The restatement's rows sum to 1 under no envelope, the full one and the staircase; the dead profile has no likelihood."""
+    import pairenvhelpers as eh
+    em, x, P, Pdead = eh.wrap_case()
+    I, L = eh.WRAP_SHAPE
+    C = em.nOutTok + 1
+    assert (len(x), len(P), em.nStates, C) == (1, 1100, 2, 4) and eh.silent_levels(em) >= 1
+
+    def rows_per_block(cells, tabMax):      # profile_pair_rowpost_rows (mb_profile_pair.h)
+        if C > tabMax:
+            return 1
+        perRow = max(1, cells * em.nStates // (L + 1))
+        return min(-(-8192 // perRow), tabMax // C, L)
+    for cells in ((I + 1) * (L + 1), eh.n_cells(eh.staircase(I, L))):
+        assert rows_per_block(cells, 4) == rows_per_block(cells, 2) == 1 and L > eh.WRAP_GROUPS
+        assert -(-L // rows_per_block(cells, 4096)) == 2
+    stairs = eh.staircase(I, L)
+    assert all(b - a == 1 for a, b in zip(stairs.inStart, stairs.inEnd))
+    dp = _dp(em)
+    for env in (None, eh.full(I, L), stairs):
+        post, ll = dp.rowPosteriors(x, P, env=env)
+        assert ll > -math.inf and post.shape == (L, C) and np.abs(post.sum(axis=1) - 1.0).max() <= 1e-9 and (post[1024:] > 0).any()
+    post, ll = dp.rowPosteriors(x, Pdead)
+    assert ll == -math.inf and not post.any()
+
+
 def _torch_pairs():
     """Two small pairs on one machine with finite entries, a ragged rowOff, the second under a band."""
     em = pair_machine(8, 108, True, 2, 3)
