@@ -281,6 +281,21 @@ int mb_profile_twos_viterbi(mb_profile_twos *p, double *loglike, int64_t *pathOf
 int mb_profile_twos_counts(mb_profile_twos *p, double *counts, double *loglikeSum, double *loglike);
 int mb_profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, double *cellsOut);
 
+/* Row posteriors of the pairs of profiles (docs/profile_tapes.md, "Row posteriors of pairs of profiles"):
+ * postB[(rowOff[k] - rowOff[0] + r)*(nOutTok+1) + o] = the posterior probability that output row r of pair k was consumed as output
+ * token o, postA[(inOff[k] - inOff[0] + i)*(nInTok+1) + a] = that input row i was consumed as input token a (column 0 of either: as
+ * its blank) -- the gradients of the pair's log-likelihood in logB and in logA at those entries.  Either table has the layout of its
+ * row table and is overwritten; either may be NULL, and its kernel is then not launched.  Every row of a pair with a finite
+ * likelihood sums to 1; a pair whose likelihood is -inf gets zeros in both tables, an entry whose weight is -inf is exactly 0, and
+ * the column sums of a pair are the mb_profile_twos_counts of the transitions that write (postB) or read (postA) the column's token,
+ * added up.  With MB_DETERMINISTIC=1 the sums go through 64-bit fixed point at 2^-36 and are the same bits from call to call, alone
+ * or in a batch, chunked or not.  mb_profile_twos_set_rows replaces the input row table, the output row table or both (NULL: keep;
+ * same shapes, checked as mb_profile_twos_create checks them; a refused table leaves both old tables in effect) and launches
+ * nothing: a training loop re-uses the object. */
+int mb_profile_twos_row_posteriors(mb_profile_twos *p, double *postA /* [sum K][nInTok+1], may be NULL */,
+                                   double *postB /* [sum rows][nOutTok+1], may be NULL */, double *loglike /* [nPairs], may be NULL */);
+int mb_profile_twos_set_rows(mb_profile_twos *p, const double *logA /* NULL: keep */, const double *logB /* NULL: keep */);
+
 /* ---- prefix search: imputing the input tape (--prefix-decode / --prefix-encode / --random-encode) -------------------------------
  * The node fill of the reference's PrefixTree (src/ctc.cpp:25-88) on the device, the tree and its heap on the host
  * (docs/decoding.md).  An mb_prefix holds nSeq searches (output sequence k = outTok[outOff[k]..outOff[k+1]), tokens 1..nOutTok)

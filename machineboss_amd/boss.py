@@ -25,7 +25,7 @@ repeated in consecutive rows is one symbol, and only a blank separates two equal
 goes except with ``--prefix-decode`` (profile.MergedProfileDP, mb_profile_merge.hip; docs/profile_tapes.md); the prefix search
 against a merged profile is ``prefixDecodeProfile(..., merge=True)`` (k_prefix_fill_merged, docs/decoding.md).
 
-``--generate-csv A.csv`` beside ``--recognize-csv B.csv`` (with -L, -V or -C) scores a machine that keeps its input alphabet
+``--generate-csv A.csv`` beside ``--recognize-csv B.csv`` (with -L, -V, -C or --profile-posteriors) scores a machine that keeps its input alphabet
 between two profiles, A the soft input and B the soft output, without composing A's generator in front (profile.TwoProfileDP,
 mb_profile_two.hip; docs/profile_tapes.md, "Pairs of profiles"); ``scoreTwoProfiles`` is the same for a batch of input profiles.
 
@@ -148,10 +148,10 @@ def buildParser() -> argparse.ArgumentParser:
     ap.add_argument("--generate-chars", help="compose a generator of this sequence in front of the machine(s)")
     ap.add_argument("--recognize-chars", help="compose a recogniser of this sequence behind the machine(s)")
     ap.add_argument("--generate-json", help="compose a generator of the sequence in this JSON file ({name, sequence}) in front of the machine(s)")
-    ap.add_argument("--generate-csv", help="beside --recognize-csv with -L, -V or -C: score the machine(s) between this CSV profile as the soft input and that one as the soft output")
+    ap.add_argument("--generate-csv", help="beside --recognize-csv with -L, -V, -C or --profile-posteriors: score the machine(s) between this CSV profile as the soft input and that one as the soft output")
     ap.add_argument("--recognize-csv", help="score the machine(s) against this CSV profile (rightmost; with -L, -V or -C), or decode it (--prefix-decode, --viterbi-decode)")
     ap.add_argument("--profile-band", type=int, metavar="N", help="with --recognize-csv beside an input sequence: sweep each pair under a band of half-width N around the diagonal (seqpair.Envelope.band)")
-    ap.add_argument("--profile-posteriors", action="store_true", help="with --recognize-csv beside an input sequence: per pair the posterior probability that each row of the profile was consumed as each output symbol, column 0 the blank (the gradient of the log-likelihood in the profile)")
+    ap.add_argument("--profile-posteriors", action="store_true", help="with --recognize-csv beside an input sequence: per pair the posterior probability that each row of the profile was consumed as each output symbol, column 0 the blank (the gradient of the log-likelihood in the profile); beside --generate-csv: the same for the rows of both profiles")
     ap.add_argument("--recognize-merge-csv", help="the same against a CTC profile: a symbol repeated in consecutive rows is one symbol, and only a blank separates two equal symbols (not with --prefix-decode)")
     ap.add_argument("-P", "--params", action="append", default=[])
     ap.add_argument("-F", "--functions", action="append", default=[])
@@ -419,10 +419,10 @@ def runProfile(args, out) -> int:
         if not machine.inputAlphabet():
             raise MachineError("--recognize-csv takes no other sequence data: the machine has no input alphabet to read an input sequence")
         return _runProfilePairs(args, out, machine)
-    if args.profile_posteriors:
-        raise MachineError(_POSTERIORS_ONLY)
     if args.generate_csv is not None:
         return _runTwoProfiles(args, out, machine)
+    if args.profile_posteriors:
+        raise MachineError(_POSTERIORS_ONLY)
     if args.profile_band is not None:
         raise MachineError(_BAND_ONLY)
     if machine.inputAlphabet():
@@ -573,13 +573,17 @@ def _runProfilePairs(args, out, machine: Machine) -> int:
 
 
 def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "device", params=None,
-                     loglike: bool = True, viterbi: bool = False, counts: bool = False):
+                     loglike: bool = True, viterbi: bool = False, counts: bool = False, posteriors: bool = False):
     """Every input profile (a profile.Profile, read against the machine's input alphabet) as one pair with ``outProfile`` (a
     profile.Profile, read against its output alphabet), all pairs in one batch, on a machine with an input alphabet
     (docs/profile_tapes.md, "Pairs of profiles").  ``backend``: "device" (capi.DeviceProfileTwos) or "numpy"
     (profile.TwoProfileDP).  Returns what scoreProfilePairs returns: (scores, paramCounts), scores["loglike"] and
     scores["viterbi"] one float per input profile, or None where not asked for; paramCounts the posterior count of every parameter
-    summed over the pairs, or None."""
+    summed over the pairs, or None.  ``posteriors``: scores["posteriors"] holds one (postA[K, nInTok + 1], postB[L, nOutTok + 1]) per
+    input profile, the posterior probability that each row of either tape was consumed as each of its tokens (column 0: as the
+    blank; docs/profile_tapes.md, "Row posteriors of pairs of profiles") -- zeros for a pair that scores -inf; the key is absent
+    when not asked for."""
+    import numpy as np
     from . import dp
     from .profile import TwoProfileDP
     ev = EvaluatedMachine.fromMachine(machine, params)
@@ -588,7 +592,7 @@ def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "d
     As = [a.logRowsIn(ev) for a in inProfiles]
     B = outProfile.logRows(ev)
     acc = dp.MachineCounts(ev)
-    fwd = vit = None
+    fwd = vit = post = None
     if backend == "numpy":
         tdp = TwoProfileDP(ev)
         fwd = [tdp.forward(A, B)[0] for A in As] if loglike else None
@@ -598,6 +602,7 @@ def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "d
                 acc._flat += c
                 acc.loglike += ll
         vit = [tdp.forward(A, B, "max")[0] for A in As] if viterbi else None
+        post = [tdp.rowPosteriors(A, B)[:2] for A in As] if posteriors else None
     else:
         from . import capi
         dm = capi.DeviceMachine(ev)
@@ -608,17 +613,24 @@ def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "d
                 _, s, _ = twos.counts(acc._flat)
                 acc.loglike += s
             vit = twos.viterbi(paths=False)[0] if viterbi else None
+            if posteriors:
+                pa, pb, _ = twos.row_posteriors()
+                post = [(np.array(pa[twos.inOff[k]:twos.inOff[k + 1]]), np.array(pb[k * len(B):(k + 1) * len(B)])) for k in range(len(As))]
         finally:
             twos.close(); dm.close()
 
     def floats(v):
         return None if v is None else [float(x) for x in v]
-    return {"loglike": floats(fwd), "viterbi": floats(vit)}, (acc.paramCounts(machine, params) if counts else None)
+    scores = {"loglike": floats(fwd), "viterbi": floats(vit)}
+    if posteriors:
+        scores["posteriors"] = post
+    return scores, (acc.paramCounts(machine, params) if counts else None)
 
 
 def _runTwoProfiles(args, out, machine: Machine) -> int:
     """--generate-csv beside --recognize-csv on a machine with an input alphabet: one pair of profiles (docs/profile_tapes.md,
-    "Pairs of profiles").  -L and -V print [the --generate-csv argument, "", score], -C the counts.  --decode-backend numpy:
+    "Pairs of profiles").  -L and -V print [the --generate-csv argument, "", score], -C the counts, --profile-posteriors after them
+    [the --generate-csv argument, "", {"input": the K rows of postA, "output": the L rows of postB}].  --decode-backend numpy:
     profile.TwoProfileDP."""
     from .profile import Profile
     if not machine.inputAlphabet():
@@ -627,13 +639,18 @@ def _runTwoProfiles(args, out, machine: Machine) -> int:
         raise MachineError("CSV file not found")
     sc, pc = scoreTwoProfiles(machine, [Profile.fromCsv(args.generate_csv)], Profile.fromCsv(args.recognize_csv),
                               backend="numpy" if args.decode_backend == "numpy" else "device", params=_profileParams(args, machine),
-                              loglike=bool(args.loglike), viterbi=bool(args.viterbi), counts=bool(args.counts))
+                              loglike=bool(args.loglike), viterbi=bool(args.viterbi), counts=bool(args.counts),
+                              posteriors=bool(args.profile_posteriors))
     if args.loglike:
         out.write('[["%s","",%s]]\n' % (escaped(args.generate_csv), fmt(sc["loglike"][0])))
     if args.counts:
         out.write("{" + ",".join('"%s":%s' % (escaped(k), "%g" % pc[k]) for k in sorted(pc)) + "}\n")
     if args.viterbi:
         out.write('[["%s","",%s]]\n' % (escaped(args.generate_csv), fmt(sc["viterbi"][0])))
+    if args.profile_posteriors:
+        rows = lambda a: "[" + ",".join("[" + ",".join(fmt(float(v)) for v in row) + "]" for row in a) + "]"
+        pa, pb = sc["posteriors"][0]
+        out.write('[["%s","",{"input":%s,"output":%s}]]\n' % (escaped(args.generate_csv), rows(pa), rows(pb)))
     return 0
 
 
@@ -751,8 +768,8 @@ def runCoding(args, machine: Machine, params, data: List[SeqPair], emit) -> None
 
 
 _GENERATE_ONLY = ("--generate-csv goes with --recognize-csv and -L, -V or -C on a machine with an input alphabet, nowhere else: not with "
-                  "--recognize-merge-csv, an input sequence, the decode options or --profile-band")
-_POSTERIORS_ONLY = "--profile-posteriors goes with --recognize-csv beside an input sequence (--input-chars, --input-fasta, --input-json), nowhere else"
+                  "--recognize-merge-csv, an input sequence, the decode options or --profile-band; --profile-posteriors may stand beside or instead of -L, -V and -C")
+_POSTERIORS_ONLY = "--profile-posteriors goes with --recognize-csv beside an input sequence (--input-chars, --input-fasta, --input-json) or beside --generate-csv, nowhere else"
 _BAND_ONLY = "--profile-band goes with --recognize-csv beside an input sequence (--input-chars, --input-fasta, --input-json) and -L, -V or -C, nowhere else"
 
 

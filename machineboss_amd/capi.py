@@ -36,6 +36,7 @@ EXPORTS = [
     "mb_profile_pairs_set_envelopes", "mb_profile_pair_fill_env", "mb_profile_pairs_cells",
     "mb_profile_pairs_row_posteriors", "mb_profile_pairs_set_rows",
     "mb_profile_twos_create", "mb_profile_twos_destroy", "mb_profile_twos_forward", "mb_profile_twos_viterbi", "mb_profile_twos_counts",
+    "mb_profile_twos_row_posteriors", "mb_profile_twos_set_rows",
     "mb_profile_two_fill",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
     "mb_prefix_node_cells", "mb_prefix_create_profiles", "mb_prefix_create_merged",
@@ -145,6 +146,8 @@ def load():
     L.mb_profile_twos_forward.argtypes = [vp, C.c_int, dp]
     L.mb_profile_twos_viterbi.argtypes = [vp, dp, i64p, u32p, i32p, i32p, C.c_int64]
     L.mb_profile_twos_counts.argtypes = [vp, dp, dp, dp]
+    L.mb_profile_twos_row_posteriors.argtypes = [vp, dp, dp, dp]
+    L.mb_profile_twos_set_rows.argtypes = [vp, dp, dp]
     L.mb_profile_two_fill.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, dp]
     L.mb_prefix_create.restype = vp
     L.mb_prefix_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, C.c_int64]
@@ -889,6 +892,35 @@ class DeviceProfileTwos:
         ll = np.empty(self.nPairs, np.float64)
         _check(load().mb_profile_twos_counts(self.h, _p(counts, C.c_double), C.byref(s), _p(ll, C.c_double)))
         return counts, s.value, ll
+
+    def row_posteriors(self, inputs: bool = True, outputs: bool = True):
+        """Returns (postA[sumK, nInTok + 1], postB[sumRows, nOutTok + 1], loglike[nPairs]): postB[rowOff[k] + r][o] is the posterior
+        probability that output row r of pair k was consumed as output token o, postA[inOff[k] + i][a] that input row i was
+        consumed as input token a (column 0 of either: as its blank) -- the gradients of loglike[k] in those entries of the two
+        profiles; zeros for a pair whose likelihood is -inf (docs/profile_tapes.md, "Row posteriors of pairs of profiles").
+        ``inputs=False`` / ``outputs=False``: that table is None and its kernel is not launched."""
+        postA = np.zeros((int(self.inOff[-1]), self.logA.shape[1]), np.float64) if inputs else None
+        postB = np.zeros((int(self.rowOff[-1]), self.logB.shape[1]), np.float64) if outputs else None
+        ll = np.empty(self.nPairs, np.float64)
+        _check(load().mb_profile_twos_row_posteriors(self.h, _p(postA, C.c_double), _p(postB, C.c_double), _p(ll, C.c_double)))
+        return postA, postB, ll
+
+    def set_profiles(self, inProfiles=None, outProfiles=None):
+        """New rows for every pair on the input tape, the output tape or both (None: keep), of the shapes the object was created
+        with.  A refused table (NaN, +inf) leaves both old tables in effect."""
+        def table(profiles, old, off):
+            if profiles is None:
+                return None
+            rows = [np.asarray(q, np.float64).reshape(-1, old.shape[1]) for q in profiles]
+            if len(rows) != self.nPairs or any(len(r) != n for r, n in zip(rows, np.diff(off))):
+                raise ValueError("one profile per pair with the rows it was created with, please")
+            return np.ascontiguousarray(np.concatenate(rows + [np.zeros((1, old.shape[1]))]), np.float64)
+        logA, logB = table(inProfiles, self.logA, self.inOff), table(outProfiles, self.logB, self.rowOff)
+        _check(load().mb_profile_twos_set_rows(self.h, _p(logA, C.c_double), _p(logB, C.c_double)))
+        if logA is not None:
+            self.logA = logA
+        if logB is not None:
+            self.logB = logB
 
 
 def profile_two_fill(dm: DeviceMachine, mode: int, logA, logB) -> np.ndarray:

@@ -3314,6 +3314,89 @@ int mb_profile_twos_counts(mb_profile_twos *p, double *counts, double *loglikeSu
   return 0;
 }
 
+// the line blocks of k_profile_two_rowpost on one axis of the pair that has most among [p0, p1), 1 024 at the most
+static long long pt_rowpost_groups(const mb_profile_twos *p, long long p0, long long p1, int axis, int tabMax) {
+  const int S = p->m->S;
+  const long long NC = (axis ? p->m->nIn : p->m->nOut) + 1;
+  long long groups = 1;
+  for (long long k = p0; k < p1; ++k) {
+    const long long K = pt_in(p, k), L = pt_rows(p, k), NL = axis ? K : L;
+    const long long R = profile_pair_rowpost_rows((K + 1) * (L + 1), S, (int)NL, (int)NC, tabMax);
+    groups = std::max(groups, (NL + R - 1) / R);
+  }
+  return std::min<long long>(groups, 1024);
+}
+
+int mb_profile_twos_row_posteriors(mb_profile_twos *p, double *postA, double *postB, double *loglike) {
+  ApiGuard guard;
+  if (!p) { set_error("null argument"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
+  const mb_machine *m = p->m;
+  const long long C = m->nOut + 1, CA = m->nIn + 1, nb = postB ? p->totalRows * C : 0, na = postA ? p->totalIn * CA : 0;
+  const int tabMax = pp_rowpost_table();
+  std::vector<Chunk> chunks;
+  auto bytes = [&](long long k) { return 2.0 * pt_cell_bytes(p, k) + 8.0 * (double)(pt_rows(p, k) * C + pt_in(p, k) * CA); };   // both lattices and the pair's bins of both tables
+  if (!lattice_chunks(p->n, bytes, chunks)) return 1;
+  double *d_ll = nullptr, *d_bll = nullptr, *d_pa = nullptr, *d_pb = nullptr;
+  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
+  if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
+      !hip_ok(sm_alloc((void **)&d_pa, std::max<long long>(na, 1) * sizeof(double)), "hipMalloc(row posteriors)") ||
+      !hip_ok(sm_alloc((void **)&d_pb, std::max<long long>(nb, 1) * sizeof(double)), "hipMalloc(row posteriors)")) { sm_free(d_ll); sm_free(d_bll); sm_free(d_pa); sm_free(d_pb); return 1; }
+  int rc = 0;
+  Timer tm;
+  for (const Chunk &c : chunks) {
+    TwoProfPlan pl;
+    if ((rc = two_profile_descs(p, c.p0, c.p1, false, pl))) break;
+    const long long np = c.p1 - c.p0;
+    double *fwd = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
+    double *bwd = (double *)ws_get(1, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
+    if (!fwd || !bwd) rc = 1;
+    const long long groupsB = pt_rowpost_groups(p, c.p0, c.p1, 0, tabMax), groupsA = pt_rowpost_groups(p, c.p0, c.p1, 1, tabMax);
+    if (!rc && np * std::max(groupsA, groupsB) > 0x7fffffff) { set_error("too many pairs in one chunk"); rc = 1; }
+    if (!rc) {
+      tm.start();
+      rc = launch_profile_two_fwd(m, MB_FORWARD, true, pl.d, (int)np, 0, pl.maxItems, p->d_logA, p->d_logB, fwd, nullptr, d_ll + c.p0, g_stream);
+      if (!rc) rc = launch_profile_two_bwd(m, pl.d, (int)np, pl.maxItems, p->d_logA, p->d_logB, bwd, d_bll + c.p0, g_stream);
+      if (!rc && postB) rc = launch_profile_two_rowpost(m, 0, pl.d, (int)np, (int)groupsB, tabMax, p->d_logA, p->d_logB, fwd, bwd, d_pb, g_stream);
+      if (!rc && postA) rc = launch_profile_two_rowpost(m, 1, pl.d, (int)np, (int)groupsA, tabMax, p->d_logA, p->d_logB, fwd, bwd, d_pa, g_stream);
+      g_last_ms += tm.stop();
+      g_last_launches += 1;
+    }
+    if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "row posteriors")) rc = 1;      // (the next chunk takes the lattices over)
+    if (rc) quiesce_streams();
+    pt_plan_free(pl);
+    if (rc) break;
+  }
+  if (!rc && na && d2h_large(postA, d_pa, (size_t)na * sizeof(double))) rc = 1;
+  if (!rc && nb && d2h_large(postB, d_pb, (size_t)nb * sizeof(double))) rc = 1;
+  if (!rc && g_deterministic)
+    for (int t = 0; t < 2 && !rc; ++t) {      // fixed point, 2^-36 (a posterior is at most 1: far inside the range)
+      double *post = t ? postB : postA;
+      const long long nv = t ? nb : na;
+      for (long long e = 0; e < nv && !rc; ++e) {
+        unsigned long long u; std::memcpy(&u, &post[e], 8);
+        if (!det_to_double(u, post[e])) { set_error("MB_DETERMINISTIC: a posterior count left the fixed-point range (6.7e7 per transition and call): split the batch or use the floating-point mode"); rc = 1; }
+      }
+    }
+  std::vector<double> hll((size_t)p->n);
+  if (!rc && p->n && !hip_ok(hipMemcpy(hll.data(), d_ll, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  sm_free(d_ll); sm_free(d_bll); sm_free(d_pa); sm_free(d_pb);
+  g_last_kernel = "k_profile_two_rowpost";
+  if (rc) return rc;
+  if (loglike) for (long long k = 0; k < p->n; ++k) loglike[k] = hll[(size_t)k];
+  return 0;
+}
+
+int mb_profile_twos_set_rows(mb_profile_twos *p, const double *logA, const double *logB) {
+  ApiGuard guard;
+  if (!p) { set_error("null argument"); return 1; }
+  const long long na = logA ? p->totalIn * (p->m->nIn + 1) : 0, nb = logB ? p->totalRows * (p->m->nOut + 1) : 0;
+  if (!profile_values_ok(logA, na) || !profile_values_ok(logB, nb)) return 1;      // (before either copy: a refused table leaves both in effect)
+  if ((na && h2d_large(p->d_logA, logA, (size_t)na * sizeof(double))) || (nb && h2d_large(p->d_logB, logB, (size_t)nb * sizeof(double)))) return 1;
+  return hip_ok(hipStreamSynchronize(g_stream), "H2D profiles") ? 0 : 1;
+}
+
 int mb_profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, double *cellsOut) {
   ApiGuard guard;
   if (!m || !cellsOut || nRows < 0 || nIn < 0 || (nRows && !logB) || (nIn && !logA)) { set_error("null argument"); return 1; }

@@ -1,6 +1,6 @@
 // mb_profile_common.h -- what the profile sweeps share (mb_profile.hip, mb_profile_merge.hip, mb_profile_pair.hip,
-// mb_profile_pair_merge.hip): the reduction of a sweep's mode, the LDS a ring may take, the lanes of a workgroup, and the
-// accumulator of the posterior counts.  Device code: included by .hip files only.
+// mb_profile_pair_merge.hip, mb_profile_two.hip): the reduction of a sweep's mode, the LDS a ring may take, the lanes of a workgroup, the
+// accumulator of the posterior counts and the add of the row posteriors.  Device code: included by .hip files only.
 #pragma once
 #include <algorithm>
 
@@ -53,5 +53,25 @@ struct CountsAcc {
       }
   }
 };
+
+// One lane sum into bin `bin` of a row-posterior table (k_profile_pair_rowpost, k_profile_two_rowpost), every lane of the wavefront
+// together.  whole: all 64 lanes hold items of one line, so the sums are reduced across the lanes and lane 0 alone adds; else every
+// lane adds its own.  det: the lane sum becomes 64-bit fixed point at 2^-36 (mb_internal.h) before it meets another.
+__device__ __forceinline__ void rowpost_add(double *tab, int bin, double v, bool whole, int lane, int det) {
+  if (det) {
+    unsigned long long u = (unsigned long long)fmin(fmax(v * MB_DET_GLOBAL_SCALE + 0.5, 0.0), 4611686018427387904.0);
+    if (whole) {
+      for (int w = 32; w > 0; w >>= 1) u += __shfl_xor(u, w);
+      if (lane != 0) u = 0ull;
+    }
+    if (u != 0ull) atomicAdd((unsigned long long *)tab + bin, u);
+  } else {
+    if (whole) {
+      for (int w = 32; w > 0; w >>= 1) v += __shfl_xor(v, w);
+      if (lane != 0) v = 0.0;
+    }
+    if (v != 0.0) atomicAdd(&tab[bin], v);
+  }
+}
 
 }  // namespace mb

@@ -318,24 +318,7 @@ __global__ __launch_bounds__(256) void k_profile_pair_counts(DevMachine m, const
 // writing workgroup, so there is no global atomic and nothing to clear beforehand.  A row of more than tabMax columns is summed in
 // its global bins instead, cleared by the workgroup that owns it.  A pair whose likelihood is -inf gets zeros.
 // det: a lane sum is turned into 64-bit fixed point at 2^-36 (mb_internal.h) before it meets another, and integers are reduced and
-// added; post then holds the integers.
-__device__ __forceinline__ void rowpost_add(double *tab, int bin, double v, bool whole, int lane, int det) {
-  if (det) {
-    unsigned long long u = (unsigned long long)fmin(fmax(v * MB_DET_GLOBAL_SCALE + 0.5, 0.0), 4611686018427387904.0);
-    if (whole) {
-      for (int w = 32; w > 0; w >>= 1) u += __shfl_xor(u, w);
-      if (lane != 0) u = 0ull;
-    }
-    if (u != 0ull) atomicAdd((unsigned long long *)tab + bin, u);
-  } else {
-    if (whole) {
-      for (int w = 32; w > 0; w >>= 1) v += __shfl_xor(v, w);
-      if (lane != 0) v = 0.0;
-    }
-    if (v != 0.0) atomicAdd(&tab[bin], v);
-  }
-}
-
+// added (rowpost_add, mb_profile_common.h); post then holds the integers.
 template <template <bool> class Geom>
 __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_rowpost(DevMachine m, const typename Geom<true>::Desc *__restrict__ descs, typename Geom<true>::Tables t, int groupsPerPair,
                                                                           const int *__restrict__ inTok, const double *__restrict__ logP,

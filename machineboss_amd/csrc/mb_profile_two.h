@@ -27,6 +27,11 @@ int launch_profile_two_bwd(const mb_machine *m, const PairProfDesc *d, int n, lo
 // counts[nTrans] += posteriors of the n pairs (fwdPool / bwdPool: their materialised lattices); det: 64-bit fixed point at 2^-36
 int launch_profile_two_counts(const mb_machine *m, const PairProfDesc *d, int n, int groupsPerPair, const double *logA, const double *logB,
                               const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
+// post = the row posteriors of the n pairs on one tape, every bin of every line written (nothing to clear).  axis 0: the output rows,
+// post[(rowBase + r) * (nOut+1) + o]; axis 1: the input rows, post[(inBase + i) * (nIn+1) + a].  groupsPerPair: at least the line blocks
+// (profile_pair_rowpost_rows over the axis) of the pair that has most, 1 024 at the most; det: post holds 64-bit fixed point at 2^-36
+int launch_profile_two_rowpost(const mb_machine *m, int axis, const PairProfDesc *d, int n, int groupsPerPair, int tabMax, const double *logA,
+                               const double *logB, const double *fwdPool, const double *bwdPool, double *post, hipStream_t st);
 int launch_profile_two_traceback(const mb_machine *m, const PairProfDesc *d, int n, const double *logA, const double *logB, const double *pool,
                                  uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, hipStream_t st);
 

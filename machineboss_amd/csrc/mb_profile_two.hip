@@ -1,4 +1,4 @@
-// mb_profile_two.hip -- Forward / Backward / Viterbi / posterior counts of a machine WITH an input alphabet between two PROFILE tapes:
+// mb_profile_two.hip -- Forward / Backward / Viterbi / posterior counts / row posteriors of a machine WITH an input alphabet between two PROFILE tapes:
 // an input profile A of K rows (the generator of `--generate-csv`) and an output profile B of L rows (`--recognize-csv`) -- the
 // semantics of compose(A.machine(), compose(M, transpose(B.machine()))) with both tapes empty, restated in docs/profile_tapes.md
 // ("Pairs of profiles"):
@@ -270,6 +270,116 @@ __global__ __launch_bounds__(256) void k_profile_two_counts(DevMachine m, const 
   acc.flush();
 }
 
+// Row posteriors of both tapes (docs/profile_tapes.md, "Row posteriors of pairs of profiles"): the terms of k_profile_two_counts and
+// the two blank masses, binned by (line, column) instead of by transition.  AXIS 0 bins output rows -- post[(rowBase + r) * C + o] is
+// the gradient of the log-likelihood in B[r][o]:
+//   post[r][0] = sum_i sum_s exp((N_F[i][r][s] - LL) + (B[r][0] + NB[i][r+1][s]))
+//   post[r][o] = the match terms (read from Z_F) and the output-only terms (read from W_F) whose edge writes o
+// AXIS 1 bins input rows -- post[(inBase + i) * CA + a] is the gradient in A[i][a]:
+//   post[i][0] = sum_r sum_s exp((Z_F[i][r][s] - LL) + (A[i][0] + ZB[i+1][r][s]))
+//   post[i][a] = the input-only and the match terms (both read from Z_F) whose edge reads a
+// The scheme is the one of k_profile_pair_rowpost: the work items are (line, cell of the line, state) in that order -- over the full
+// rectangle both orders are a division -- and a workgroup owns whole lines, blocks of profile_pair_rowpost_rows lines dealt round
+// robin to the pair's groups.  A lane sums its terms of one column in a register, in CSR order (axis 0, column o: the rows
+// s*K + a*C + o for a = 1..nIn, then s*K + o; axis 1, column a: the rows s*K + a*C + o for o = 0..nOut); rowpost_add reduces the lane
+// sums of a wavefront that lies in one line and adds to the workgroup's LDS table, which is then stored: every bin has one writing
+// workgroup, so there is no global atomic and nothing to clear beforehand.  A line of more than tabMax columns is summed in its
+// global bins instead, cleared by the workgroup that owns it.  A pair whose likelihood is -inf gets zeros.  det: post holds 64-bit
+// fixed point at 2^-36.
+template <int AXIS>
+__global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_rowpost(DevMachine m, const PairProfDesc *__restrict__ descs, int groupsPerPair,
+                                                                         const double *__restrict__ logA, const double *__restrict__ logB,
+                                                                         const double *__restrict__ fwdPool, const double *__restrict__ bwdPool,
+                                                                         double *post, int tabMax, int det) {
+  __shared__ double ltab[ROWPOST_LDS_MAX];
+  const int k = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
+  const PairProfDesc pd = descs[k];
+  const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, K = pd.nIn, L = pd.nRows;
+  const int NL = AXIS ? K : L, NC = AXIS ? CA : C, per = (AXIS ? L : K) + 1;      // lines, bins of a line, cells of a line
+  if (NL == 0) return;
+  const double *A = logA + pd.inBase * CA;
+  const double *B = logB + pd.rowBase * C;
+  const TwoGeom<true> F(pd, const_cast<double *>(fwdPool) + pd.cellBase, S), Bk(pd, const_cast<double *>(bwdPool) + pd.cellBase, S);
+  const double LL = F.at(K, L, 2)[S - 1];
+  const int R = profile_pair_rowpost_rows(F.cells(), S, NL, NC, tabMax);
+  const bool useLds = NC <= tabMax;
+  const int lane = threadIdx.x & 63;
+  for (long long lb = (long long)group * R; lb < NL; lb += (long long)groupsPerPair * R) {
+    const int l0 = (int)lb, l1 = (int)min((long long)NL, lb + R), nBins = (l1 - l0) * NC;
+    double *out = post + ((AXIS ? pd.inBase : pd.rowBase) + l0) * NC;
+    double *tab = useLds ? ltab : out;
+    for (int e = threadIdx.x; e < nBins; e += blockDim.x) tab[e] = 0.0;      // (the fixed point's zero has the same bits)
+    if (!useLds) __threadfence();
+    __syncthreads();
+    if (LL > -INFINITY) {
+      const long long nItems = (long long)(l1 - l0) * per * S;
+      for (long long base = threadIdx.x - lane; base < nItems; base += blockDim.x) {      // (a wavefront stays whole in here)
+        const long long idx = base + lane;
+        const bool valid = idx < nItems;
+        int line = l0, j = 0, s = 0;
+        if (valid) {
+          const long long cell = idx / S;
+          s = (int)(idx - cell * S);
+          line = l0 + (int)(cell / per);
+          j = (int)(cell - (long long)(line - l0) * per);
+        }
+        const int i = AXIS ? line : j, r = AXIS ? j : line;
+        const double z = valid ? F.at(i, r, 2)[s] - LL : -INFINITY;
+        const bool whole = __all(valid && line == __shfl(line, 0));
+        const bool diag = valid && i < K && r < L;      // (the line's own coordinate is inside: r < L on axis 0, i < K on axis 1)
+        const double *Ai = A + (long long)i * CA;        // read when i < K
+        const double *Br = B + (long long)r * C;         // read when r < L
+        const double *Nd = diag ? Bk.at(i + 1, r + 1, 0) : nullptr;
+        const int sRow = s * KK, bin0 = (line - l0) * NC;
+        if (AXIS == 0) {
+          const double f = valid ? F.at(i, r, 1)[s] - LL : -INFINITY, n = valid ? F.at(i, r, 0)[s] - LL : -INFINITY;
+          const double *Nu = Bk.at(i, r + 1, 0);
+          const bool zLive = diag && z > -INFINITY, fLive = f > -INFINITY;
+          rowpost_add(tab, bin0, n > -INFINITY ? exp(n + (Br[0] + Nu[s])) : 0.0, whole, lane, det);
+          for (int o = 1; o < C; ++o) {      // the out-edges of (s, a) that write o are one CSR row
+            double v = 0.0;
+            const double po = Br[o];
+            if (zLive)
+              for (int a = 1; a <= m.nIn; ++a) {
+                const int row = sRow + a * C + o;
+                const double wa = Ai[a];
+                const int e1 = m.outOff[row + 1];
+                for (int e = m.outOff[row]; e < e1; ++e) v += exp(z + (((m.outW[e] + wa) + po) + Nd[m.outDst[e]]));
+              }
+            if (fLive) {
+              const int e1 = m.outOff[sRow + o + 1];
+              for (int e = m.outOff[sRow + o]; e < e1; ++e) v += exp(f + ((m.outW[e] + po) + Nu[m.outDst[e]]));
+            }
+            rowpost_add(tab, bin0 + o, v, whole, lane, det);
+          }
+        } else {
+          const double *Zl = Bk.at(i + 1, r, 2), *Wl = Bk.at(i + 1, r, 1);
+          const bool zLive = z > -INFINITY;
+          rowpost_add(tab, bin0, zLive ? exp(z + (Ai[0] + Zl[s])) : 0.0, whole, lane, det);
+          for (int a = 1; a < CA; ++a) {      // the out-edges of s that read a: the input-only row, then the rows of the output tokens
+            double v = 0.0;
+            if (zLive) {
+              const int row = sRow + a * C;
+              const double wa = Ai[a];
+              int e = m.outOff[row];
+              for (const int e1 = m.outOff[row + 1]; e < e1; ++e) v += exp(z + ((m.outW[e] + wa) + Wl[m.outDst[e]]));
+              if (diag)
+                for (const int e1 = m.outOff[row + C]; e < e1; ++e)
+                  v += exp(z + (((m.outW[e] + wa) + Br[m.eOutTok[m.outEid[e]]]) + Nd[m.outDst[e]]));
+            }
+            rowpost_add(tab, bin0 + a, v, whole, lane, det);
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (useLds) {
+      for (int e = threadIdx.x; e < nBins; e += blockDim.x) out[e] = tab[e];
+      __syncthreads();
+    }
+  }
+}
+
 // Viterbi traceback over a materialised max lattice, one lane per pair: from Z[K][L][S-1] back to N[0][0][0], taking at every cell
 // the first candidate (in the fill's order) whose value equals the cell.  Edges go start -> end into the pair's slot
 // (profile_pair_path_bound entries) with both coordinates at which each fired: an emitting edge the output row it consumed, an
@@ -397,6 +507,16 @@ int launch_profile_two_counts(const mb_machine *m, const PairProfDesc *d, int n,
   k_profile_two_counts<<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(m->dev, d, groupsPerPair, logA, logB, fwdPool, bwdPool, m->nTrans, counts,
                                                                                          g_deterministic ? 1 : 0);
   return hip_ok(hipGetLastError(), "k_profile_two_counts") ? 0 : 1;
+}
+
+int launch_profile_two_rowpost(const mb_machine *m, int axis, const PairProfDesc *d, int n, int groupsPerPair, int tabMax, const double *logA,
+                               const double *logB, const double *fwdPool, const double *bwdPool, double *post, hipStream_t st) {
+  if (n <= 0) return 0;
+  const dim3 g((unsigned)((long long)n * groupsPerPair)), b(ROWPOST_THREADS);
+  const int det = g_deterministic ? 1 : 0;
+  if (axis) k_profile_two_rowpost<1><<<g, b, 0, st>>>(m->dev, d, groupsPerPair, logA, logB, fwdPool, bwdPool, post, tabMax, det);
+  else k_profile_two_rowpost<0><<<g, b, 0, st>>>(m->dev, d, groupsPerPair, logA, logB, fwdPool, bwdPool, post, tabMax, det);
+  return hip_ok(hipGetLastError(), "k_profile_two_rowpost") ? 0 : 1;
 }
 
 int launch_profile_two_traceback(const mb_machine *m, const PairProfDesc *d, int n, const double *logA, const double *logB, const double *pool,

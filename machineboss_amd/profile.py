@@ -1136,6 +1136,44 @@ class TwoProfileDP(PairProfileDP):
             blanks.append((outBlank, inBlank))
         return out, ll
 
+    def rowPosteriors(self, A, B) -> Tuple[np.ndarray, np.ndarray, float]:
+        """(postA[K, nInTok + 1], postB[L, nOutTok + 1], Forward loglike): postB[r][o] is the posterior probability that output
+        row r was consumed as output token o, postA[i][a] that input row i was consumed as input token a (column 0 of either: as
+        its blank) -- the terms of counts() and its two blank masses, binned by (row, column) of either tape instead of by
+        transition, which are the gradients of loglike in B[r][o] and in A[i][a] (docs/profile_tapes.md, "Row posteriors of pairs
+        of profiles").  Every row of either table sums to 1; zeros for a -inf pair; exactly 0 where the weight is -inf."""
+        A, B = self._checkTwo(A, B)
+        ll, NF, WF, ZF = self.forward(A, B)
+        K, L = len(A), len(B)
+        postA = np.zeros((K, self.em.nInTok + 1)); postB = np.zeros((L, self.em.nOutTok + 1))
+        if not ll > _NEG:
+            return postA, postB, ll
+        _, NB, WB, ZB = self.backward(A, B)
+        _, mS, mD, mW, mA, mO = self.mAll
+        _, iS, iD, iW, iA, _ = self.iAll
+        eO = np.asarray(self.eO)
+
+        def mass(b):
+            return float(np.exp(b[b > _NEG]).sum())
+        with np.errstate(invalid="ignore"):
+            for i in range(K + 1):
+                for r in range(L + 1):
+                    f, z = WF[i, r] - ll, ZF[i, r] - ll
+                    if r < L:
+                        if i < K:
+                            t = z[mS] + (((mW + A[i][mA]) + B[r][mO]) + NB[i + 1, r + 1][mD])
+                            live = t > _NEG
+                            np.add.at(postB[r], mO[live], np.exp(t[live]))
+                            np.add.at(postA[i], mA[live], np.exp(t[live]))
+                        t = f[self.eS] + ((self.eW + B[r][eO]) + NB[i, r + 1][self.eD])
+                        np.add.at(postB[r], eO[t > _NEG], np.exp(t[t > _NEG]))
+                        postB[r, 0] += mass((NF[i, r] - ll) + (B[r][0] + NB[i, r + 1]))
+                    if i < K:
+                        t = z[iS] + ((iW + A[i][iA]) + WB[i + 1, r][iD])
+                        np.add.at(postA[i], iA[t > _NEG], np.exp(t[t > _NEG]))
+                        postA[i, 0] += mass(z + (A[i][0] + ZB[i + 1, r]))
+        return postA, postB, ll
+
     def viterbi(self, A, B, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
         """(score, global edge ids start -> end, output row, input row at which each fired); the first maximum in the fill's
         candidate order.  The output row of an emitting edge is the row it consumed, of an output-less edge the number of rows

@@ -1,5 +1,6 @@
 """The log-likelihood of (input sequence, profile) pairs as a differentiable function of the profiles, for PyTorch: a CTC-style loss
-with a transducer (an error or channel model) between the truth and the frames (docs/profile_tapes.md, "Row posteriors").
+with a transducer (an error or channel model) between the truth and the frames (docs/profile_tapes.md, "Row posteriors"); and of
+(input profile, output profile) pairs as a differentiable function of both (two_profile_loglike).
 
 The gradient of a pair's log-likelihood in its profile is the pair's row posteriors, so forward is one row_posteriors() call and
 backward multiplies what it kept.  The machine's weights are constants here; their gradient is the posterior counts
@@ -75,3 +76,75 @@ def pair_profile_loglike(machine_or_dm, inputs, logP, rowOff, envs=None, backend
         raise ValueError("one envelope (or None) per pair, please")
     inputs = [np.asarray(x, np.int64).reshape(-1) for x in inputs]
     return _PairProfileLoglike.apply(logP, machine_or_dm, inputs, rowOff, envs, backend)
+
+
+def _two_row_posteriors(machine_or_dm, A, inOff, B, rowOff, wantA, wantB, backend):
+    """(postA[sumK, CA] or None, postB[sumRows, C] or None, loglike[nPairs]) in numpy, on the device or by the numpy yardstick."""
+    n = len(rowOff) - 1
+    As = [A[inOff[k]:inOff[k + 1]] for k in range(n)]
+    Bs = [B[rowOff[k]:rowOff[k + 1]] for k in range(n)]
+    if backend == "numpy":
+        from .profile import TwoProfileDP
+        em = getattr(machine_or_dm, "em", machine_or_dm)
+        dp = TwoProfileDP(em)
+        postA, postB = np.zeros(A.shape, np.float64), np.zeros(B.shape, np.float64)
+        ll = np.empty(n, np.float64)
+        for k in range(n):
+            postA[inOff[k]:inOff[k + 1]], postB[rowOff[k]:rowOff[k + 1]], ll[k] = dp.rowPosteriors(As[k], Bs[k])
+        return (postA if wantA else None), (postB if wantB else None), ll
+    if backend != "device":
+        raise ValueError('backend is "device" or "numpy"')
+    from . import capi
+    own = not isinstance(machine_or_dm, capi.DeviceMachine)
+    dm = capi.DeviceMachine(machine_or_dm) if own else machine_or_dm
+    twos = capi.DeviceProfileTwos(dm, As, Bs)
+    try:
+        return twos.row_posteriors(inputs=wantA, outputs=wantB)
+    finally:
+        twos.close()
+        if own:
+            dm.close()
+
+
+class _TwoProfileLoglike(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logA, logB, machine_or_dm, inOff, rowOff, backend):
+        A = np.ascontiguousarray(logA.detach().cpu().numpy(), np.float64)
+        B = np.ascontiguousarray(logB.detach().cpu().numpy(), np.float64)
+        wantA, wantB = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        postA, postB, ll = _two_row_posteriors(machine_or_dm, A, inOff, B, rowOff, wantA, wantB, backend)
+        ctx.inOff, ctx.rowOff = inOff, rowOff
+        ctx.save_for_backward(None if postA is None else torch.from_numpy(postA).to(logA.device),
+                              None if postB is None else torch.from_numpy(postB).to(logB.device))
+        return torch.from_numpy(ll).to(logB.device)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        def grad(post, off):
+            if post is None:
+                return None
+            rows = torch.as_tensor(np.diff(off), device=post.device)
+            return torch.repeat_interleave(grad_out.to(device=post.device, dtype=post.dtype), rows).unsqueeze(1) * post
+        postA, postB = ctx.saved_tensors
+        return grad(postA, ctx.inOff), grad(postB, ctx.rowOff), None, None, None, None
+
+
+def two_profile_loglike(machine_or_dm, logA, inOff, logB, rowOff, backend="device"):
+    """tensor[nPairs] of log-likelihoods: pair k is the rows inOff[k]..inOff[k + 1] of ``logA``, a float64 [sumK, nInTok + 1] tensor
+    of log weights on the input tape, against the rows rowOff[k]..rowOff[k + 1] of ``logB``, a float64 [sumRows, nOutTok + 1] tensor
+    on the output tape; column 0 of either is its blank (docs/profile_tapes.md, "Row posteriors of pairs of profiles").
+    Differentiable in both tables: the gradient is grad_out[k] times the row posteriors of pair k on that tape, zeros for a pair
+    that scores -inf, computed only for the tables that require one.  ``machine_or_dm``: an EvaluatedMachine or a
+    capi.DeviceMachine (kept open for the caller).  ``backend``: "device" (one capi.DeviceProfileTwos.row_posteriors() call) or
+    "numpy" (profile.TwoProfileDP.rowPosteriors, no GPU needed).  Tensors go through host memory, as pair_profile_loglike's do."""
+    if logA.dtype != torch.float64 or logA.dim() != 2:
+        raise ValueError("logA is a float64 [sumK, nInTok + 1] tensor")
+    if logB.dtype != torch.float64 or logB.dim() != 2:
+        raise ValueError("logB is a float64 [sumRows, nOutTok + 1] tensor")
+    inOff = np.asarray(inOff, np.int64).reshape(-1)
+    rowOff = np.asarray(rowOff, np.int64).reshape(-1)
+    if len(inOff) < 1 or inOff[0] != 0 or inOff[-1] != logA.shape[0] or (np.diff(inOff) < 0).any():
+        raise ValueError("inOff has one entry per pair and one more, from 0 up to the rows of logA")
+    if len(rowOff) != len(inOff) or rowOff[0] != 0 or rowOff[-1] != logB.shape[0] or (np.diff(rowOff) < 0).any():
+        raise ValueError("rowOff has one entry per pair and one more, from 0 up to the rows of logB")
+    return _TwoProfileLoglike.apply(logA, logB, machine_or_dm, inOff, rowOff, backend)
