@@ -1,5 +1,5 @@
-"""Shared helpers of the tests of decoding against a CTC-merged profile (test_prefix_merge_host.py, test_prefix_merge_gpu.py; not a
-test module): the composite compose(M, merging recogniser) with a map from its states to the cells of the native lattice, the node
+"""Shared helpers of the tests of decoding against a CTC-merged profile (test_prefix_merge_host.py, test_prefix_merge_gpu.py,
+test_prefix_merge_edges_gpu.py; not a test module): the composite compose(M, merging recogniser) with a map from its states to the cells of the native lattice, the node
 families of both fills, and the deterministic inputs of the device cases.  The seeds were searched on the CPU so that the
 conditions the cases state (finite results, populated layers) hold under the numpy restatement alone."""
 import dataclasses
@@ -246,3 +246,106 @@ def lds_case(S):
     """(em, colTok, P) at nCols = 4, 3 rows, for the machines at the LDS limit."""
     em = device_machine(S, 3, S)
     return em, [1, 2, 3, 1], live_rows(np.random.RandomState(S), 4, 3, zeros=0.1)
+
+
+# ---- the edge suite of the merged fill (test_prefix_merge_edges_gpu.py; held to its liveness conditions without a GPU by
+# test_prefix_merge_host.py::test_edge_suite_inputs_are_live) -------------------------------------------------------------------------
+# (nCols, S, L).  PL = nCols + 1 planes: from 513 on a lane serves one plane alone (LPP = 1) and the lanes past PL idle; 1 024 planes
+# fill the workgroup exactly; from 1 025 on a lane owns several planes in every phase.  The last two need 104.7 and 152.4 KiB of LDS.
+PLANE_CASES = [(600, 1, 3), (1023, 1, 3), (1024, 1, 3), (1030, 2, 3), (1500, 2, 2)]
+SHORT_FAMILY = [(), (1,), (1, 2)]          # the root, one child, one grandchild: where the yardstick takes a second per node
+
+
+def plane_paths(nCols):
+    """The family compared at ``nCols`` columns: the whole one up to 1 024 planes, SHORT_FAMILY beyond."""
+    return family_paths(2) if nCols < 1024 else SHORT_FAMILY
+
+
+# (S, nIn, nOut, levels): the strides C = nOut + 1 and K = (nIn + 1)(nOut + 1) from alphabets of different sizes
+ALPHABET_CASES = [(1, 1, 1, False), (2, 1, 4, True), (63, 3, 5, True), (64, 5, 3, False), (65, 3, 5, True), (65, 5, 3, False)]
+EDGE_ROWS = 33
+DEAD_ROW = 16
+
+
+def alphabet_case(S, nIn, nOut, levels):
+    """(em, colTok, P): 2 nOut - 1 columns on the tokens in turn, so all but the last token have two columns; 33 rows without
+    -inf."""
+    em = populated_machine(S, 100 + S, levels, nIn, nOut)
+    nCols = 2 * nOut - 1
+    return em, [1 + c % nOut for c in range(nCols)], live_rows(np.random.RandomState(S + EDGE_ROWS), nCols, EDGE_ROWS, zeros=0.0)
+
+
+def batch_machine():
+    """S = 40, silent levels, nIn = 3, nOut = 5: the machine of the dead-weight and the batch cases."""
+    return populated_machine(40, 7, True, 3, 5)
+
+
+DEAD_COLTOK = [1, 2, 3, 4, 5, 1, 3]
+
+
+def sparse_rows():
+    """33 rows over DEAD_COLTOK, each weight -inf with probability one third, the blank included: rows with a dead blank skip the
+    blank sums, and bN / bXn, eP / eW / eY stay from an earlier row where a column is dead."""
+    rng = np.random.RandomState(0)
+    w = rng.uniform(0.05, 1.0, (EDGE_ROWS, len(DEAD_COLTOK) + 1))
+    with np.errstate(divide="ignore"):
+        return np.log(np.where(rng.rand(*w.shape) < 1.0 / 3.0, 0.0, w))
+
+
+def dead_row_rows():
+    """33 rows over DEAD_COLTOK without -inf, but row DEAD_ROW -inf throughout: nothing passes it."""
+    P = live_rows(np.random.RandomState(1), len(DEAD_COLTOK), EDGE_ROWS, zeros=0.0)
+    P[DEAD_ROW] = -np.inf
+    return P
+
+
+def dead_blank_case():
+    """lane_case(65, 2, 6) with the blank of every row -inf: the group of plane 0 never forms a blank sum."""
+    em, colTok, P = lane_case(65, 2, 6)
+    P[:, 0] = -np.inf
+    return em, colTok, P
+
+
+def far_column_rows():
+    """Two rows over colTok = [1, 2] that read mostly a, then mostly b (prefixhelpers.far_column_case)."""
+    return np.log(np.array([[0.05, 0.9, 0.05], [0.05, 0.05, 0.9]]))
+
+
+TWIN_COLTOK = [1, 2, 1]
+# A quantised sharp row: 2^0 on its column, 2^-6 elsewhere; two output tokens per profile.  Searched on the CPU: the numpy searches
+# take 121 to 145 fills each (three tokens, or 2^-1 against 2^-4, take 500 to 4 000 on this machine, whose weights are flat).
+QUANT_BITS, QUANT_TOKENS = (0, 6), 2
+
+
+def twin_merged_profiles(em, quantised):
+    """Four sharp merged profiles over TWIN_COLTOK that read as output strings of prefixhelpers.twin_outputs.  ``quantised``:
+    every weight is a multiple of log 0.5, as the weights of the quantised twin machine are, so that different paths tie exactly."""
+    import prefixhelpers as ph
+    rng = np.random.RandomState(ph.TWIN_SEED)
+    profs = []
+    for o in ph.twin_outputs(em, ph.TWIN_SEARCHES, QUANT_TOKENS if quantised else ph.TWIN_L, ph.TWIN_SEED):
+        P = sharp_merged_profile(rng, em.outputTokenizer.tokenize(list(o)), TWIN_COLTOK, sharp=0.8)
+        if quantised:
+            P = np.where(P == P.max(), QUANT_BITS[0], QUANT_BITS[1]) * np.log(0.5)
+        profs.append(P)
+    return profs
+
+
+SELF_LOOP_COLTOK = [1, 2, 3, 4, 5, 2]
+
+
+def self_loop_rows():
+    return live_rows(np.random.RandomState(8), len(SELF_LOOP_COLTOK), 12, zeros=0.1)
+
+
+BATCH_COLTOK = [1, 2, 3, 4, 5, 2, 4]
+BATCH_LENGTHS = tuple(range(10))
+
+
+def batch_rows():
+    """One table per search, of 0, 1, ..., 9 rows."""
+    return [live_rows(np.random.RandomState(20 + L), len(BATCH_COLTOK), L, zeros=0.05) for L in BATCH_LENGTHS]
+
+
+MANY_FILLS = (300, 600)          # (S, children in one extend): 69 640 B of LDS, two workgroups per CU, more fills than are resident
+LDS_MARK_STATES = (282, 283, 706)          # nCols = 4: 65 464 B (within 64 KiB), 65 696 B (the opt-in), 163 832 B (the limit)

@@ -173,3 +173,90 @@ def test_cli_spelling_is_still_rejected():
     with pytest.raises(MachineError, match="cannot be prefix-decoded"):
         boss.run(["tests/golden/machine/dnastore4.json", "--use-defaults", "--recognize-merge-csv", "tests/golden/csv/tiny_uc.csv",
                   "--prefix-decode", "--decode-backend", "numpy"], io.StringIO())
+
+
+def _live(ref, floor, tag):
+    """Every result finite, at least ``floor`` of each layer finite."""
+    for p, (cells, lsp, lpp) in ref.items():
+        assert np.isfinite(lsp) and np.isfinite(lpp), (tag, p, lsp, lpp)
+    for layer in (0, 1):
+        fin = sum(int(np.isfinite(c[:, layer]).sum()) for c, _, _ in ref.values())
+        assert fin >= floor * sum(c[:, layer].size for c, _, _ in ref.values()), (tag, layer, fin)
+
+
+def test_edge_suite_inputs_are_live():
+    """tests/test_prefix_merge_edges_gpu.py asserts, from the yardstick, that its inputs are finite, dead, far down or tied where its
+    cases need them to be; the same builders of mergeprefixhelpers.py are held to the same conditions here, so the seeds are
+    verified without a GPU and nothing there passes on -inf = -inf."""
+    import math
+    import prefixhelpers as ph
+    # 1. many planes: every result finite, half of each layer
+    assert [c[0] + 1 for c in mph.PLANE_CASES] == [601, 1024, 1025, 1031, 1501]
+    for nCols, S, L in mph.PLANE_CASES:
+        em, colTok, P = mph.lane_case(nCols, S, L)
+        assert em.nStates == S and P.shape == (L, nCols + 1) and colTok == [1 + c % 3 for c in range(nCols)]
+        paths = mph.plane_paths(nCols)
+        assert len(paths) == (5 if nCols < 1024 else 3) and max(len(p) for p in paths) == 2
+        _live(mph.merged_fills(em, P, colTok, paths), 0.5, ("planes", nCols, S, L))
+    # 2. alphabets: every result finite, three quarters of each layer
+    for S, nIn, nOut, lv in mph.ALPHABET_CASES:
+        em, colTok, P = mph.alphabet_case(S, nIn, nOut, lv)
+        assert (em.nStates, em.nInTok, em.nOutTok) == (S, nIn, nOut) and (int(em.silentLevels().max()) > 0) == lv
+        assert colTok == [1 + c % nOut for c in range(2 * nOut - 1)] and P.shape == (33, 2 * nOut) and np.isfinite(P).all()
+        _live(mph.merged_fills(em, P, colTok, family_paths(nIn)), 0.75, ("alphabets", S, nIn, nOut, lv))
+    # 3. dead weights
+    em = mph.batch_machine()
+    assert (em.nStates, em.nInTok, em.nOutTok) == (40, 3, 5) and int(em.silentLevels().max()) > 0
+    P = mph.sparse_rows()
+    dead = np.isneginf(P[:, 0])
+    assert dead.sum() == 12 and (dead[:-1] & ~dead[1:]).any() and not np.isneginf(P).all(axis=1).any()
+    assert 0.3 <= np.isneginf(P).mean() <= 0.4
+    _live(mph.merged_fills(em, P, mph.DEAD_COLTOK, family_paths(3)), 0.5, "a third dead")
+    P = mph.dead_row_rows()
+    assert np.isneginf(P[mph.DEAD_ROW]).all() and np.isfinite(np.delete(P, mph.DEAD_ROW, 0)).all()
+    for p, (cells, lsp, lpp) in mph.merged_fills(em, P, mph.DEAD_COLTOK, family_paths(3)).items():
+        assert lsp == -math.inf and lpp == -math.inf and np.isneginf(cells[mph.DEAD_ROW + 1:]).all(), p
+        assert np.isfinite(cells[:mph.DEAD_ROW + 1]).mean() >= 0.5 and np.isfinite(cells[mph.DEAD_ROW]).mean() >= 0.5, p
+    em, colTok, P = mph.dead_blank_case()
+    assert P.shape == (6, 66) and em.nStates == 2 and np.isneginf(P[:, 0]).all()
+    _live(mph.merged_fills(em, P, colTok, family_paths(2)), 0.5, "every blank dead")
+    # 4. the far column: every prefix probability is finite, and below what a linear product under the row maximum can hold
+    em, R, _ = ph.far_column_case()
+    ref = mph.merged_fills(em, mph.far_column_rows(), [1, 2], family_paths(2), R)
+    assert all(np.isfinite(v[2]) and v[2] < -850 for v in ref.values()), [v[2] for v in ref.values()]
+    assert ref[()][2] == pytest.approx(-851.127, abs=1e-3)
+    # 5. twins and ties: the yardstick's twins are the same bits, every best input holds a twin symbol, the searches are short
+    for quantised in (False, True):
+        em = ph.twin_machine(ph.TWIN_STATES, ph.TWIN_SEED, quantised)
+        profs = mph.twin_merged_profiles(em, quantised)
+        assert len(profs) == 4
+        if quantised:
+            for k in [em.logWeight / math.log(0.5)] + [P / math.log(0.5) for P in profs]:
+                assert np.abs(k - np.round(k)).max() < 1e-12
+        ref = mph.merged_fills(em, profs[0], mph.TWIN_COLTOK, [(), (1,), (2,), (3,), (2, 1), (2, 2), (2, 3)])
+        for a, b, c in (((1,), (2,), (3,)), ((2, 1), (2, 2), (2, 3))):
+            assert ref[a][0].tobytes() == ref[b][0].tobytes() and ref[a][1:] == ref[b][1:]
+            assert ref[a][0].tobytes() != ref[c][0].tobytes() and np.isfinite(ref[a][2])
+        seqs, trees = prefixtree.decodeBatch(em, None, backend="numpy", profiles=profs, colTok=mph.TWIN_COLTOK)
+        assert all(set(sq) & {"A", "B"} for sq in seqs), seqs
+        print("merged twin searches", quantised, seqs, [t.nFills for t in trees])
+        assert max(t.nFills for t in trees) < 300
+    # 6. the silent self-loop
+    em, _ = ph.self_loop_case()
+    loops = [t for t in ph.machine_edges(em) if t[2] == 0 and t[3] == 0 and t[0] == t[1]]
+    assert len(loops) == 1 and loops[0][0] == 0 and int(em.silentLevels().max()) > 0
+    P = mph.self_loop_rows()
+    assert P.shape == (12, len(mph.SELF_LOOP_COLTOK) + 1)
+    _live(mph.merged_fills(em, P, mph.SELF_LOOP_COLTOK, family_paths(3)), 0.5, "self-loop")
+    # 7. lengths 0 to 9: the root and the three children of every search are finite
+    em, profs = mph.batch_machine(), mph.batch_rows()
+    assert [P.shape for P in profs] == [(L, len(mph.BATCH_COLTOK) + 1) for L in range(10)]
+    for P in profs:
+        ref = mph.merged_fills(em, P, mph.BATCH_COLTOK, [(), (1,), (2,), (3,)])
+        assert all(np.isfinite(v[1]) and np.isfinite(v[2]) for v in ref.values()), len(P)
+    # 8. and 9. the many fills and the LDS marks: the root and the children compared are finite
+    for S, toks in [(mph.MANY_FILLS[0], (1, 2))] + [(S, (1,)) for S in mph.LDS_MARK_STATES]:
+        em, colTok, P = mph.lds_case(S)
+        assert em.nStates == S and len(colTok) == 4 and len(P) == 3
+        ref = mph.merged_fills(em, P, colTok, [()] + [(t,) for t in toks])
+        assert all(np.isfinite(v[1]) and np.isfinite(v[2]) for v in ref.values()), S
