@@ -178,6 +178,22 @@ mb_profiles *mb_profiles_create_merged(mb_machine *m, int64_t nProfiles, const d
 int mb_profile_fill_merged(mb_machine *m, int mode, const double *logP, int64_t nRows, int32_t nCols, const int32_t *colTok,
                            double *cellsOut);
 
+/* Row posteriors of one-tape profiles, plain and merged (docs/profile_tapes.md, "Row posteriors of one-tape profiles"):
+ * post[(rowOff[k] - rowOff[0] + r)*width + x], width = nOutTok + 1 (plain) or nCols + 1 (merged), = the posterior probability that
+ * row r of profile k was consumed as column x (0: the blank), which is the gradient of the profile's log-likelihood in logP at that
+ * entry.  For merged profiles column c holds both ways a row takes it: repeating the previous row's column and a fresh emission of
+ * colTok[c-1]; with a linear-chain generator the likelihood is minus the CTC loss and post its gradient in the frames.  post has the
+ * layout of the row table and is overwritten.  Every row of a profile with a finite likelihood sums to 1; a profile whose likelihood
+ * is -inf gets zeros, an entry whose weight is -inf is exactly 0, and the column sums of a plain profile are the mb_profiles_counts
+ * of the transitions that write the column's token, added up.  The call runs the materialised Forward and Backward sweeps and one
+ * flat kernel over all rows (k_profile_rowpost); it chunks under the memory budget by two lattices per profile, and one profile whose
+ * two lattices exceed the budget is an error before anything is launched.  With MB_DETERMINISTIC=1 the sums go through 64-bit fixed
+ * point at 2^-36 and are the same bits from call to call, alone or in a batch, chunked or not.  mb_profiles_set_rows replaces the
+ * whole row table (same shapes, checked as mb_profiles_create / _create_merged check it; a refused table leaves the old one in
+ * effect) and launches nothing: a training loop re-uses the object. */
+int mb_profiles_row_posteriors(mb_profiles *p, double *post /* [sum rows][width], overwritten */, double *loglike /* [nProfiles] or NULL */);
+int mb_profiles_set_rows(mb_profiles *p, const double *logP);
+
 /* Pairs: a known input sequence against a profile (`--recognize-csv` beside --input-chars / --input-fasta / --input-json): the
  * semantics of compose(M, transpose(CSVProfile::machine())) on input x[1..I] with an empty output, for a machine WITH an input
  * alphabet, swept natively over (I + 1) x (rows + 1) x 2 x nStates along anti-diagonals (docs/profile_tapes.md, "Pairs: an input

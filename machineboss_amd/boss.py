@@ -24,6 +24,8 @@ imputed (prefixtree.ProfilePrefixDP, k_prefix_fill_profile in mb_prefix.hip; doc
 repeated in consecutive rows is one symbol, and only a blank separates two equal symbols.  It goes wherever ``--recognize-csv``
 goes except with ``--prefix-decode`` (profile.MergedProfileDP, mb_profile_merge.hip; docs/profile_tapes.md); the prefix search
 against a merged profile is ``prefixDecodeProfile(..., merge=True)`` (k_prefix_fill_merged, docs/decoding.md).
+``--profile-posteriors`` beside either, alone or after -L, -V and -C, prints the gradient of the log-likelihood in the profile's
+rows (``profilePosteriors``, k_profile_rowpost in mb_profile_post.hip; docs/profile_tapes.md, "Row posteriors of one-tape profiles").
 
 ``--generate-csv A.csv`` beside ``--recognize-csv B.csv`` (with -L, -V, -C or --profile-posteriors) scores a machine that keeps its input alphabet
 between two profiles, A the soft input and B the soft output, without composing A's generator in front (profile.TwoProfileDP,
@@ -151,7 +153,7 @@ def buildParser() -> argparse.ArgumentParser:
     ap.add_argument("--generate-csv", help="beside --recognize-csv with -L, -V, -C or --profile-posteriors: score the machine(s) between this CSV profile as the soft input and that one as the soft output")
     ap.add_argument("--recognize-csv", help="score the machine(s) against this CSV profile (rightmost; with -L, -V or -C), or decode it (--prefix-decode, --viterbi-decode)")
     ap.add_argument("--profile-band", type=int, metavar="N", help="with --recognize-csv beside an input sequence: sweep each pair under a band of half-width N around the diagonal (seqpair.Envelope.band)")
-    ap.add_argument("--profile-posteriors", action="store_true", help="with --recognize-csv beside an input sequence: per pair the posterior probability that each row of the profile was consumed as each output symbol, column 0 the blank (the gradient of the log-likelihood in the profile); beside --generate-csv: the same for the rows of both profiles")
+    ap.add_argument("--profile-posteriors", action="store_true", help="with --recognize-csv beside an input sequence: per pair the posterior probability that each row of the profile was consumed as each output symbol, column 0 the blank (the gradient of the log-likelihood in the profile); beside --generate-csv: the same for the rows of both profiles; with --recognize-csv or --recognize-merge-csv alone on a machine with an empty input alphabet: the same for the one profile (merged: per CSV column)")
     ap.add_argument("--recognize-merge-csv", help="the same against a CTC profile: a symbol repeated in consecutive rows is one symbol, and only a blank separates two equal symbols (not with --prefix-decode)")
     ap.add_argument("-P", "--params", action="append", default=[])
     ap.add_argument("-F", "--functions", action="append", default=[])
@@ -393,7 +395,8 @@ def _mergedRows(profile, ev):
 
 def runProfile(args, out) -> int:
     """--recognize-csv / --recognize-merge-csv: the machines left of the profile, composed, against the profile tape (-L / -V /
-    -C).  With --decode-backend numpy a merged profile is swept by the numpy restatement (profile.MergedProfileDP)."""
+    -C, and --profile-posteriors after them or alone: [["","",rows]], profilePosteriors).  With --decode-backend numpy a merged
+    profile is swept by the numpy restatement (profile.MergedProfileDP), and the posteriors of either kind by the yardstick."""
     from . import capi, dp
     from .profile import Profile
     args.merge = args.recognize_merge_csv is not None
@@ -421,7 +424,7 @@ def runProfile(args, out) -> int:
         return _runProfilePairs(args, out, machine)
     if args.generate_csv is not None:
         return _runTwoProfiles(args, out, machine)
-    if args.profile_posteriors:
+    if args.profile_posteriors and machine.inputAlphabet():
         raise MachineError(_POSTERIORS_ONLY)
     if args.profile_band is not None:
         raise MachineError(_BAND_ONLY)
@@ -437,24 +440,72 @@ def runProfile(args, out) -> int:
         raise MachineError("--recognize-merge-csv needs a machine with an output alphabet")
     if args.merge and args.decode_backend == "numpy":
         return _runMergedNumpy(args, out, machine, params, ev, profile)
-    dm = capi.DeviceMachine(ev)
-    if args.merge:
-        P, colTok = _mergedRows(profile, ev)
-        prof = capi.DeviceProfiles(dm, [P], colTok)
-    else:
-        prof = capi.DeviceProfiles(dm, [profile.logRows(ev)])
-    if args.loglike:
-        out.write('[["","",%s]]\n' % fmt(prof.forward(capi.MB_ROLLING)[0]))
-    if args.counts:
-        counts = dp.MachineCounts(ev)
-        _, s, _ = prof.counts(counts._flat)
-        counts.loglike += s
-        pc = counts.paramCounts(machine, params)
-        out.write("{" + ",".join('"%s":%s' % (escaped(k), "%g" % pc[k]) for k in sorted(pc)) + "}\n")
-    if args.viterbi:
-        out.write('[["","",%s]]\n' % fmt(prof.viterbi(paths=False)[0][0]))
-    prof.close(); dm.close()
+    numpyPost = args.profile_posteriors and args.decode_backend == "numpy"      # the yardstick: no device object for it
+    if args.loglike or args.counts or args.viterbi or (args.profile_posteriors and not numpyPost):
+        dm = capi.DeviceMachine(ev)
+        if args.merge:
+            P, colTok = _mergedRows(profile, ev)
+            prof = capi.DeviceProfiles(dm, [P], colTok)
+        else:
+            prof = capi.DeviceProfiles(dm, [profile.logRows(ev)])
+        if args.loglike:
+            out.write('[["","",%s]]\n' % fmt(prof.forward(capi.MB_ROLLING)[0]))
+        if args.counts:
+            counts = dp.MachineCounts(ev)
+            _, s, _ = prof.counts(counts._flat)
+            counts.loglike += s
+            pc = counts.paramCounts(machine, params)
+            out.write("{" + ",".join('"%s":%s' % (escaped(k), "%g" % pc[k]) for k in sorted(pc)) + "}\n")
+        if args.viterbi:
+            out.write('[["","",%s]]\n' % fmt(prof.viterbi(paths=False)[0][0]))
+        if args.profile_posteriors and not numpyPost:
+            _writeProfilePosteriors(out, prof.row_posteriors()[0])
+        prof.close(); dm.close()
+    if numpyPost:
+        _writeProfilePosteriors(out, profilePosteriors(machine, profile, "numpy", params)[0])
     return 0
+
+
+def _writeProfilePosteriors(out, post) -> None:
+    out.write('[["","",[' + ",".join("[" + ",".join(fmt(float(v)) for v in row) + "]" for row in post) + "]]]\n")
+
+
+def profilePosteriors(machine: Machine, profile, backend: str = "device", params=None, merge: bool = False):
+    """--profile-posteriors of a one-tape profile: (post[L, width], loglike) of a machine with an empty input alphabet against the
+    profile, post[r][x] the posterior probability that row r was consumed as column x (0: the blank), the gradient of loglike in
+    the profile's log weights (docs/profile_tapes.md, "Row posteriors of one-tape profiles"); zeros for a profile that scores
+    -inf.  ``profile``: a Profile, or its rows (merged: a pair (logP, colTok) as Profile.mergeRows returns).  ``merge``: the
+    profile is CTC-merged and width = nCols + 1, else width = nOutTok + 1.  ``backend``: "device" (capi.DeviceProfiles) or "numpy"
+    (profile.ProfileDP / MergedProfileDP)."""
+    params = machine.getParamDefs(True) if params is None else params
+    if machine.inputAlphabet():
+        raise MachineError("--recognize-csv needs a machine with an empty input alphabet (compose a generator in front); input alphabet: %s"
+                           % ",".join(machine.inputAlphabet()))
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    colTok = None
+    if merge:
+        if not ev.nOutTok:
+            raise MachineError("--recognize-merge-csv needs a machine with an output alphabet")
+        P, colTok = _mergedRows(profile, ev) if hasattr(profile, "mergeRows") else profile
+    else:
+        P = profile.logRows(ev) if hasattr(profile, "logRows") else profile
+    if backend == "numpy":
+        from .profile import MergedProfileDP, ProfileDP
+        post, ll = (MergedProfileDP(ev, colTok) if merge else ProfileDP(ev)).rowPosteriors(P)
+        return post, float(ll)
+    if backend != "device":
+        raise MachineError('backend is "device" or "numpy"')
+    from . import capi
+    dm = capi.DeviceMachine(ev)
+    prof = None
+    try:
+        prof = capi.DeviceProfiles(dm, [P], colTok)
+        post, ll = prof.row_posteriors()
+    finally:
+        if prof is not None:
+            prof.close()
+        dm.close()
+    return post, float(ll[0])
 
 
 def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device", params=None, merge: bool = False,
@@ -671,6 +722,8 @@ def _runMergedNumpy(args, out, machine: Machine, params, ev, profile) -> int:
         out.write("{" + ",".join('"%s":%s' % (escaped(k), "%g" % pc[k]) for k in sorted(pc)) + "}\n")
     if args.viterbi:
         out.write('[["","",%s]]\n' % fmt(mdp.forward(P, "max")[0]))
+    if args.profile_posteriors:
+        _writeProfilePosteriors(out, profilePosteriors(machine, profile, "numpy", params, merge=True)[0])
     return 0
 
 
@@ -769,7 +822,8 @@ def runCoding(args, machine: Machine, params, data: List[SeqPair], emit) -> None
 
 _GENERATE_ONLY = ("--generate-csv goes with --recognize-csv and -L, -V or -C on a machine with an input alphabet, nowhere else: not with "
                   "--recognize-merge-csv, an input sequence, the decode options or --profile-band; --profile-posteriors may stand beside or instead of -L, -V and -C")
-_POSTERIORS_ONLY = "--profile-posteriors goes with --recognize-csv beside an input sequence (--input-chars, --input-fasta, --input-json) or beside --generate-csv, nowhere else"
+_POSTERIORS_ONLY = ("--profile-posteriors goes with --recognize-csv beside an input sequence (--input-chars, --input-fasta, --input-json) or beside --generate-csv, "
+                    "or with --recognize-csv / --recognize-merge-csv alone on a machine with an empty input alphabet, nowhere else")
 _BAND_ONLY = "--profile-band goes with --recognize-csv beside an input sequence (--input-chars, --input-fasta, --input-json) and -L, -V or -C, nowhere else"
 
 

@@ -30,6 +30,7 @@ EXPORTS = [
     "mb_comm_unique_id", "mb_comm_init", "mb_comm_destroy", "mb_allreduce_counts",
     "mb_profiles_create", "mb_profiles_destroy", "mb_profiles_forward", "mb_profile_path_bound", "mb_profiles_viterbi",
     "mb_profiles_counts", "mb_profile_fill", "mb_profiles_create_merged", "mb_profile_fill_merged",
+    "mb_profiles_row_posteriors", "mb_profiles_set_rows",
     "mb_profile_pairs_create", "mb_profile_pairs_destroy", "mb_profile_pairs_forward", "mb_profile_pair_path_bound",
     "mb_profile_pairs_viterbi", "mb_profile_pairs_counts", "mb_profile_pair_fill",
     "mb_profile_pairs_create_merged", "mb_profile_pair_fill_merged",
@@ -124,6 +125,8 @@ def load():
     L.mb_profiles_create_merged.restype = vp
     L.mb_profiles_create_merged.argtypes = [vp, C.c_int64, dp, i64p, C.c_int32, i32p]
     L.mb_profile_fill_merged.argtypes = [vp, C.c_int, dp, C.c_int64, C.c_int32, i32p, dp]
+    L.mb_profiles_row_posteriors.argtypes = [vp, dp, dp]
+    L.mb_profiles_set_rows.argtypes = [vp, dp]
     L.mb_profile_pairs_create.restype = vp
     L.mb_profile_pairs_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, i64p]
     L.mb_profile_pairs_destroy.argtypes = [vp]; L.mb_profile_pairs_destroy.restype = None
@@ -643,6 +646,27 @@ class DeviceProfiles:
         ll = np.empty(self.nProfiles, np.float64)
         _check(load().mb_profiles_counts(self.h, _p(counts, C.c_double), C.byref(s), _p(ll, C.c_double)))
         return counts, s.value, ll
+
+    def row_posteriors(self):
+        """Returns (post[sumRows, width], loglike[nProfiles]), width = nOutTok + 1 or, merged, nCols + 1: post[rowOff[k] + r][x] is
+        the posterior probability that row r of profile k was consumed as column x (0: the blank), the gradient of loglike[k] in
+        that entry of the profile; zeros for a profile whose likelihood is -inf (docs/profile_tapes.md, "Row posteriors of
+        one-tape profiles").  Plain and merged profiles alike."""
+        post = np.zeros((int(self.rowOff[-1]), self.logP.shape[1]), np.float64)
+        ll = np.empty(self.nProfiles, np.float64)
+        _check(load().mb_profiles_row_posteriors(self.h, _p(post, C.c_double), _p(ll, C.c_double)))
+        return post, ll
+
+    def set_profiles(self, profiles):
+        """New rows for every profile, of the shapes the object was created with.  A refused table (NaN, +inf) leaves the old rows
+        in effect."""
+        width = self.logP.shape[1]
+        rows = [np.asarray(q, np.float64).reshape(-1, width) for q in profiles]
+        if len(rows) != self.nProfiles or any(len(r) != n for r, n in zip(rows, np.diff(self.rowOff))):
+            raise ValueError("one profile per profile of the object with the rows it was created with, please")
+        logP = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((1, width)), np.float64)
+        _check(load().mb_profiles_set_rows(self.h, _p(logP, C.c_double)))
+        self.logP = logP
 
 
 def profile_fill(dm: DeviceMachine, mode: int, logP) -> np.ndarray:

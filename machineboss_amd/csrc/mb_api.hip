@@ -21,6 +21,7 @@
 #include "mb_profile_pair.h"
 #include "mb_profile_pair_env.h"
 #include "mb_profile_pair_merge.h"
+#include "mb_profile_post.h"
 #include "mb_profile_two.h"
 #include "mb_small.h"
 #include "mb_usage.h"
@@ -2417,6 +2418,82 @@ int mb_profiles_counts(mb_profiles *p, double *counts, double *loglikeSum, doubl
   for (long long k = 0; k < p->n; ++k) { s += hll[(size_t)k]; if (loglike) loglike[k] = hll[(size_t)k]; }
   if (loglikeSum) *loglikeSum += s;
   return 0;
+}
+
+static int pp_rowpost_table();   // (below, beside the pair sweeps: the LDS table under MB_ROWPOST_TABLE)
+
+// Row posteriors of plain and merged profiles: the materialised Forward, the materialised Backward and the flat k_profile_rowpost
+// over both lattices (mb_profile_post.hip).  The lattices take slots 0 and 1, the Forward's scratch slot 2.
+int mb_profiles_row_posteriors(mb_profiles *p, double *post, double *loglike) {
+  ApiGuard guard;
+  if (!p || (!post && p->totalRows)) { set_error("null argument"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
+  const mb_machine *m = p->m;
+  const long long PL = pf_planes(p), C = pf_width(p), nv = p->totalRows * C, fScratch = pf_fwd_scratch(p, true);
+  const int tabMax = pp_rowpost_table();
+  std::vector<Chunk> chunks;
+  auto rowsOf = [&](long long k) { return p->rowOff[k + 1] - p->rowOff[k]; };
+  auto bytes = [&](long long k) { return 2.0 * 8.0 * pf_cells(p, rowsOf(k)) + 8.0 * (double)(rowsOf(k) * C) + 8.0 * fScratch; };   // both lattices, the bins, the sweeps' scratch
+  if (!profile_chunks(p, bytes, chunks)) return 1;
+  double *d_ll = nullptr, *d_bll = nullptr, *d_post = nullptr;
+  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
+  if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
+      !hip_ok(sm_alloc((void **)&d_post, std::max<long long>(nv, 1) * sizeof(double)), "hipMalloc(row posteriors)")) { sm_free(d_ll); sm_free(d_bll); sm_free(d_post); return 1; }
+  int rc = 0;
+  Timer tm;
+  for (const Chunk &c : chunks) {
+    ProfDesc *d = nullptr;
+    long long cells = 0;
+    if ((rc = profile_descs(p, c.p0, c.p1, &d, &cells, nullptr))) break;
+    const long long np = c.p1 - c.p0;
+    double *fwd = (double *)ws_get(0, (size_t)std::max<long long>(cells, 1) * sizeof(double));
+    double *bwd = (double *)ws_get(1, (size_t)std::max<long long>(cells, 1) * sizeof(double));
+    double *scratch = fScratch && np ? (double *)ws_get(2, (size_t)(np * fScratch) * sizeof(double)) : nullptr;
+    if (!fwd || !bwd || (fScratch && np && !scratch)) rc = 1;
+    long long groups = 1;      // the row blocks of the profile that has most (a group past a profile's last block has nothing to do)
+    for (long long k = c.p0; k < c.p1; ++k) {
+      const long long L = rowsOf(k), R = profile_rowpost_rows(m->S, (int)PL, L, (int)C, tabMax);
+      groups = std::max(groups, (L + R - 1) / R);
+    }
+    groups = std::min<long long>(groups, 1024);
+    if (!rc && np * groups > 0x7fffffff) { set_error("too many profiles in one chunk"); rc = 1; }
+    if (!rc) {
+      tm.start();
+      rc = pf_fwd(p, MB_FORWARD, true, d, (int)np, fwd, scratch, d_ll + c.p0);
+      if (!rc) rc = pf_bwd(p, true, d, (int)np, bwd, nullptr, nullptr, d_bll + c.p0, nullptr, 0);
+      if (!rc) rc = launch_profile_rowpost(m, pf_map(p), d, (int)np, (int)groups, tabMax, p->d_logP, fwd, bwd, d_ll + c.p0, d_post, g_stream);
+      g_last_ms += tm.stop();
+      ++g_last_launches;
+    }
+    if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "row posteriors")) rc = 1;      // (the next chunk takes the lattices over)
+    if (rc) quiesce_streams();
+    sm_free(d);
+    if (rc) break;
+  }
+  if (!rc && nv && d2h_large(post, d_post, (size_t)nv * sizeof(double))) rc = 1;
+  if (!rc && g_deterministic)
+    for (long long e = 0; e < nv && !rc; ++e) {      // fixed point, 2^-36 (a posterior is at most 1: far inside the range)
+      unsigned long long u; std::memcpy(&u, &post[e], 8);
+      if (!det_to_double(u, post[e])) { set_error("MB_DETERMINISTIC: a row posterior left the fixed-point range"); rc = 1; }
+    }
+  std::vector<double> hll((size_t)p->n);
+  if (!rc && p->n && !hip_ok(hipMemcpy(hll.data(), d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
+  sm_free(d_ll); sm_free(d_bll); sm_free(d_post);
+  g_last_kernel = pf_name(p, "k_profile_rowpost", "k_profile_merge_rowpost");
+  if (rc) return rc;
+  if (loglike) for (long long k = 0; k < p->n; ++k) loglike[k] = hll[(size_t)k];
+  return 0;
+}
+
+int mb_profiles_set_rows(mb_profiles *p, const double *logP) {
+  ApiGuard guard;
+  if (!p) { set_error("null argument"); return 1; }
+  const long long nv = p->totalRows * pf_width(p);
+  if (nv && !logP) { set_error("null argument"); return 1; }
+  if (!profile_values_ok(logP, nv)) return 1;
+  if (nv && h2d_large(p->d_logP, logP, (size_t)nv * sizeof(double))) return 1;
+  return hip_ok(hipStreamSynchronize(g_stream), "H2D profiles") ? 0 : 1;
 }
 
 static int profile_fill(mb_machine *m, int mode, const double *logP, int64_t nRows, int nCols, const int32_t *colTok, double *cellsOut) {

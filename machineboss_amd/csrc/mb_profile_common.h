@@ -1,5 +1,5 @@
 // mb_profile_common.h -- what the profile sweeps share (mb_profile.hip, mb_profile_merge.hip, mb_profile_pair.hip,
-// mb_profile_pair_merge.hip, mb_profile_two.hip): the reduction of a sweep's mode, the LDS a ring may take, the lanes of a workgroup, the
+// mb_profile_pair_merge.hip, mb_profile_two.hip, mb_profile_post.hip): the reduction of a sweep's mode, the LDS a ring may take, the lanes of a workgroup, the
 // accumulator of the posterior counts and the add of the row posteriors.  Device code: included by .hip files only.
 #pragma once
 #include <algorithm>
@@ -54,7 +54,7 @@ struct CountsAcc {
   }
 };
 
-// One lane sum into bin `bin` of a row-posterior table (k_profile_pair_rowpost, k_profile_two_rowpost), every lane of the wavefront
+// One lane sum into bin `bin` of a row-posterior table (k_profile_pair_rowpost, k_profile_two_rowpost, k_profile_rowpost), every lane of the wavefront
 // together.  whole: all 64 lanes hold items of one line, so the sums are reduced across the lanes and lane 0 alone adds; else every
 // lane adds its own.  det: the lane sum becomes 64-bit fixed point at 2^-36 (mb_internal.h) before it meets another.
 __device__ __forceinline__ void rowpost_add(double *tab, int bin, double v, bool whole, int lane, int det) {

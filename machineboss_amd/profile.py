@@ -324,6 +324,25 @@ class ProfileDP:
                 np.add.at(out, self.sId, np.exp(f[self.sS] + (WB[r][self.sD] + self.sW)))
         return out, ll
 
+    def rowPosteriors(self, P) -> Tuple[np.ndarray, float]:
+        """(post[L, nOutTok + 1], Forward loglike): post[r][o] is the posterior probability that row r was consumed as output token
+        o (column 0: as the blank) -- the emitting terms of counts() and the blank term of backward(), binned by (row, column),
+        which is the gradient of loglike in P[r][o] (docs/profile_tapes.md, "Row posteriors of one-tape profiles").  Every row
+        sums to 1; zeros for a -inf profile; exactly 0 where P[r][o] is -inf."""
+        P = self._check(P)
+        ll, NF, WF = self.forward(P)
+        post = np.zeros((len(P), self.em.nOutTok + 1))
+        if not ll > _NEG:
+            return post, ll
+        _, NB, _ = self.backward(P)
+        with np.errstate(invalid="ignore"):
+            for r in range(len(P)):
+                b = (NF[r] - ll) + (P[r][0] + NB[r + 1])
+                post[r, 0] = float(np.exp(b[b > _NEG]).sum())
+                t = (WF[r] - ll)[self.eS] + ((self.eW + P[r][self.eO]) + NB[r + 1][self.eD])
+                np.add.at(post[r], self.eO[t > _NEG], np.exp(t[t > _NEG]))
+        return post, ll
+
     def viterbi(self, P) -> Tuple[float, np.ndarray, np.ndarray]:
         """(score, global edge ids start -> end, row at which each fired); the first maximum in the fill's candidate order."""
         P = self._check(P)
@@ -468,6 +487,39 @@ class MergedProfileDP(ProfileDP):
                                 np.add.at(out, self.eId[sel], np.exp(f[self.eS[sel]] + ((self.eW[sel] + P[r][c]) + NB[r + 1][c][self.eD[sel]])))
                     np.add.at(out, self.sId, np.exp(f[self.sS] + (WB[r, k][self.sD] + self.sW)))
         return out, ll
+
+    def rowPosteriors(self, P, repeats: Optional[list] = None) -> Tuple[np.ndarray, float]:
+        """(post[L, nCols + 1], Forward loglike): post[r][c] is the posterior probability that row r was consumed as column c
+        (column 0: as the blank), the gradient of loglike in P[r][c] (docs/profile_tapes.md, "Row posteriors of one-tape
+        profiles"): the blank out of every plane, and for a column its repeat (plane c stays) plus the fresh emissions of
+        colTok[c - 1] out of every plane k != c -- the emitting terms of counts().  ``repeats``, if a list, receives the
+        [L, nCols + 1] repeat part, so that post - repeats sums per token to the counts.  Every row sums to 1; zeros for a -inf
+        profile; exactly 0 where P[r][c] is -inf."""
+        P = self._check(P)
+        ll, NF, WF = self.forward(P)
+        L, PL = len(P), self.PL
+        post = np.zeros((L, PL)); rep = np.zeros((L, PL))
+        if repeats is not None:
+            repeats.append(rep)
+        if not ll > _NEG:
+            return post, ll
+        _, NB, _ = self.backward(P)
+        with np.errstate(invalid="ignore"):
+            for r in range(L):
+                for k in range(PL):
+                    n, f = NF[r, k] - ll, WF[r, k] - ll
+                    b = n + (P[r][0] + NB[r + 1][0])
+                    post[r, 0] += float(np.exp(b[b > _NEG]).sum())
+                    if k:
+                        b = n + (P[r][k] + NB[r + 1][k])
+                        rep[r, k] = float(np.exp(b[b > _NEG]).sum())
+                    for c in range(1, PL):
+                        if c != k:
+                            sel = self.colSel[c - 1]
+                            t = f[self.eS[sel]] + ((self.eW[sel] + P[r][c]) + NB[r + 1][c][self.eD[sel]])
+                            post[r, c] += float(np.exp(t[t > _NEG]).sum())
+        post += rep
+        return post, ll
 
     def viterbi(self, P, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray]:
         """(score, global edge ids start -> end, row at which each fired); the first maximum in the fill's candidate order.  Blank

@@ -1,6 +1,7 @@
 """The log-likelihood of (input sequence, profile) pairs as a differentiable function of the profiles, for PyTorch: a CTC-style loss
 with a transducer (an error or channel model) between the truth and the frames (docs/profile_tapes.md, "Row posteriors"); and of
-(input profile, output profile) pairs as a differentiable function of both (two_profile_loglike).
+(input profile, output profile) pairs as a differentiable function of both (two_profile_loglike); and of one-tape profiles scored
+by a generator (profile_loglike), which with CTC-merged profiles is the CTC loss proper, constrained to the generator's language.
 
 The gradient of a pair's log-likelihood in its profile is the pair's row posteriors, so forward is one row_posteriors() call and
 backward multiplies what it kept.  The machine's weights are constants here; their gradient is the posterior counts
@@ -148,3 +149,71 @@ def two_profile_loglike(machine_or_dm, logA, inOff, logB, rowOff, backend="devic
     if len(rowOff) != len(inOff) or rowOff[0] != 0 or rowOff[-1] != logB.shape[0] or (np.diff(rowOff) < 0).any():
         raise ValueError("rowOff has one entry per pair and one more, from 0 up to the rows of logB")
     return _TwoProfileLoglike.apply(logA, logB, machine_or_dm, inOff, rowOff, backend)
+
+
+def _one_row_posteriors(machine_or_dm, P, rowOff, colTok, backend):
+    """(post[sumRows, width], loglike[nProfiles]) in numpy, on the device or by the numpy yardstick."""
+    n = len(rowOff) - 1
+    profiles = [P[rowOff[k]:rowOff[k + 1]] for k in range(n)]
+    if backend == "numpy":
+        from .profile import MergedProfileDP, ProfileDP
+        em = getattr(machine_or_dm, "em", machine_or_dm)
+        dp = ProfileDP(em) if colTok is None else MergedProfileDP(em, colTok)
+        post = np.zeros(P.shape, np.float64)
+        ll = np.empty(n, np.float64)
+        for k in range(n):
+            post[rowOff[k]:rowOff[k + 1]], ll[k] = dp.rowPosteriors(profiles[k])
+        return post, ll
+    if backend != "device":
+        raise ValueError('backend is "device" or "numpy"')
+    from . import capi
+    own = not isinstance(machine_or_dm, capi.DeviceMachine)
+    dm = capi.DeviceMachine(machine_or_dm) if own else machine_or_dm
+    prof = None
+    try:
+        prof = capi.DeviceProfiles(dm, profiles, colTok)
+        return prof.row_posteriors()
+    finally:
+        if prof is not None:
+            prof.close()
+        if own:
+            dm.close()
+
+
+class _ProfileLoglike(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logP, machine_or_dm, rowOff, colTok, backend):
+        P = np.ascontiguousarray(logP.detach().cpu().numpy(), np.float64)
+        post, ll = _one_row_posteriors(machine_or_dm, P, rowOff, colTok, backend)
+        ctx.rowOff = rowOff
+        ctx.save_for_backward(torch.from_numpy(post).to(logP.device))
+        return torch.from_numpy(ll).to(logP.device)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        post, = ctx.saved_tensors
+        rows = torch.as_tensor(np.diff(ctx.rowOff), device=post.device)
+        return torch.repeat_interleave(grad_out.to(post.dtype), rows).unsqueeze(1) * post, None, None, None, None
+
+
+def profile_loglike(machine_or_dm, logP, rowOff, colTok=None, backend="device"):
+    """tensor[nProfiles] of log-likelihoods of a machine with an empty input alphabet (a generator) against one-tape profiles:
+    profile k is the rows rowOff[k]..rowOff[k + 1] of ``logP``, a float64 [sumRows, nOutTok + 1] tensor of log weights with column 0
+    the blank; with ``colTok`` the profiles are CTC-merged and logP is [sumRows, nCols + 1], column c a frame's log weight of the
+    output token colTok[c - 1] (docs/profile_tapes.md, "Row posteriors of one-tape profiles").  With algebra.generator(y) as the
+    machine and merged profiles the result is -ctc_loss(logP, y, reduction="sum") per profile; with a lexicon, a language model
+    or a profile HMM it is the CTC likelihood of that generator's language.  Differentiable in ``logP``: the gradient is
+    grad_out[k] times the row posteriors of profile k, zeros for a profile that scores -inf (like zero_infinity of a CTC loss).
+    ``machine_or_dm``: an EvaluatedMachine or a capi.DeviceMachine (kept open for the caller).  ``backend``: "device" (one
+    capi.DeviceProfiles.row_posteriors() call) or "numpy" (profile.ProfileDP / MergedProfileDP.rowPosteriors, no GPU needed).
+    Tensors go through host memory, as pair_profile_loglike's do."""
+    if logP.dtype != torch.float64 or logP.dim() != 2:
+        raise ValueError("logP is a float64 [sumRows, nOutTok + 1] (merged: [sumRows, nCols + 1]) tensor")
+    rowOff = np.asarray(rowOff, np.int64).reshape(-1)
+    if len(rowOff) < 1 or rowOff[0] != 0 or rowOff[-1] != logP.shape[0] or (np.diff(rowOff) < 0).any():
+        raise ValueError("rowOff has one entry per profile and one more, from 0 up to the rows of logP")
+    if colTok is not None:
+        colTok = np.asarray(colTok, np.int64).reshape(-1)
+        if logP.shape[1] != len(colTok) + 1:
+            raise ValueError("merged profiles: logP has one column per entry of colTok and the blank in front")
+    return _ProfileLoglike.apply(logP, machine_or_dm, rowOff, colTok, backend)
