@@ -12,17 +12,11 @@
 #include <string>
 #include <vector>
 
+#include "mb_api_internal.h"
 #include "mb_internal.h"
 #include "mb_jit.h"
 #include "mb_medium.h"
 #include "mb_prefix.h"
-#include "mb_profile.h"
-#include "mb_profile_merge.h"
-#include "mb_profile_pair.h"
-#include "mb_profile_pair_env.h"
-#include "mb_profile_pair_merge.h"
-#include "mb_profile_post.h"
-#include "mb_profile_two.h"
 #include "mb_small.h"
 #include "mb_usage.h"
 #include "mb_wide.h"
@@ -66,11 +60,8 @@ bool hip_ok(hipError_t e, const char *what) {
 static std::recursive_mutex g_api_mutex;
 static int g_api_depth = 0;
 static void ws_begin_call();
-struct ApiGuard {
-  std::lock_guard<std::recursive_mutex> lk;
-  ApiGuard() : lk(g_api_mutex) { if (g_api_depth++ == 0) ws_begin_call(); }
-  ~ApiGuard() { --g_api_depth; }
-};
+ApiGuard::ApiGuard() { g_api_mutex.lock(); if (g_api_depth++ == 0) ws_begin_call(); }
+ApiGuard::~ApiGuard() { --g_api_depth; g_api_mutex.unlock(); }
 // the same lock without the "a new call begins" bookkeeping: option and introspection entry points (they touch the environment /
 // the planners' process-wide state, which guarded calls of other threads read)
 struct ApiLock {
@@ -80,7 +71,7 @@ struct ApiLock {
 bool g_deterministic = false;
 static int g_device = -1;   // device the library's stream and workspaces live on
 
-static int ensure_init() {
+int ensure_init() {
   if (g_init) return 0;
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
@@ -209,7 +200,7 @@ void sm_free(void *p) {
 // path array; the staged copy runs at the PCIe rate and overlaps the host-side memcpy of chunk k with the DMA of k+1.
 static void *g_pinned[2] = {nullptr, nullptr};
 static const size_t PINNED_CHUNK = (size_t)8 << 20;
-static int d2h_large(void *dst, const void *srcDev, size_t bytes) {
+int d2h_large(void *dst, const void *srcDev, size_t bytes) {
   if (bytes < ((size_t)1 << 20)) {
     if (!hip_ok(hipMemcpyAsync(dst, srcDev, bytes, hipMemcpyDeviceToHost, g_stream), "D2H")) return 1;
     return hip_ok(hipStreamSynchronize(g_stream), "D2H") ? 0 : 1;
@@ -309,7 +300,7 @@ static hipStream_t second_stream() {
 }
 
 // an error path is about to release what launched kernels may still read: wait for both streams (their own errors are not news here)
-static void quiesce_streams() {
+void quiesce_streams() {
   if (hipStream_t s2 = second_stream()) (void)hipStreamSynchronize(s2);
   (void)hipStreamSynchronize(g_stream);
   (void)hipGetLastError();
@@ -324,24 +315,7 @@ static int device_cus() {
   return cus;
 }
 
-struct Timer {
-  hipEvent_t a = nullptr, b = nullptr;
-  bool ok = false;
-  Timer() { ok = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess; }
-  ~Timer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  void start() { if (ok) (void)hipEventRecord(a, g_stream); }
-  double stop() {
-    if (!ok) return 0.0;
-    (void)hipEventRecord(b, g_stream);
-    (void)hipEventSynchronize(b);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, a, b);
-    return ms;
-  }
-};
-
 // Split [0,nPairs) into chunks whose matrices (nMatrices per pair, doubles) fit the budget.
-struct Chunk { long long p0, p1, cells; };
 static bool plan_chunks(const mb_batch *b, int nMatrices, std::vector<Chunk> &out, double bytesPerCell = 0.0) {
   const size_t budget = budget_bytes();
   long long maxCells = bytesPerCell > 0.0 ? (long long)((double)budget / bytesPerCell) : (long long)(budget / (8ull * nMatrices));
@@ -414,7 +388,7 @@ struct FastState {
   SmallProgram smF, smB;
 };
 
-static int env_int(const char *name, int dflt) {
+int env_int(const char *name, int dflt) {
   const char *v = opt_env(name);
   return v && *v ? atoi(v) : dflt;
 }
@@ -1145,7 +1119,6 @@ void mb_batch_destroy(mb_batch *b) {
 int64_t mb_batch_cells(const mb_batch *b) { return b ? b->totalCells : 0; }
 
 // Envelope::fits / connected as DPMatrix::alloc asserts them (src/dpmatrix.defs.h:31-32, src/seqpair.cpp:184-193)
-static bool env_overlapping(long long s1, long long e1, long long s2, long long e2) { return !(s1 >= e2 || s2 >= e1); }
 
 int mb_batch_set_envelopes(mb_batch *b, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
   ApiGuard guard;
@@ -2105,1404 +2078,6 @@ int mb_counts_batch(mb_machine *m, int64_t nPairs, const int32_t *inTok, const i
   if (!b) return 1;
   const int rc = mb_batch_counts(b, counts, loglikeSum, loglike);
   mb_batch_destroy(b);
-  return rc;
-}
-
-}  // extern "C"
-
-// ---- profile tapes (mb_profile.hip, docs/profile_tapes.md) ------------------------------------------------------------------
-namespace mb {
-
-static bool profile_values_ok(const double *v, long long n) {
-  for (long long k = 0; k < n; ++k)
-    if (std::isnan(v[k]) || v[k] == INFINITY) { set_error("profile weight " + std::to_string(k) + " is NaN or +infinity (log weights: -inf allowed)"); return false; }
-  return true;
-}
-
-// Split the profiles into chunks whose device memory (bytesPer(profile k)) fits the budget; even-sized like plan_chunks.
-static bool profile_chunks(const mb_profiles *p, const std::function<double(long long)> &bytesPer, std::vector<Chunk> &out) {
-  const double budget = (double)budget_bytes();
-  double total = 0.0;
-  for (long long k = 0; k < p->n; ++k) {
-    const double b = bytesPer(k);
-    if (b > budget) { set_error("one profile's DP lattice (" + std::to_string((long long)b) + " bytes) exceeds the device memory budget"); return false; }
-    total += b;
-  }
-  const double nChunks = std::max(1.0, std::ceil(total / budget));
-  const double share = std::min(budget, total / nChunks * 1.05);
-  long long p0 = 0;
-  double acc = 0.0;
-  for (long long k = 0; k < p->n; ++k) {
-    const double b = bytesPer(k);
-    if (k > p0 && (acc + b > budget || (acc >= share && acc + b > share) || k - p0 >= (1 << 30))) { out.push_back({p0, k, 0}); p0 = k; acc = 0.0; }
-    acc += b;
-  }
-  if (p->n > p0) out.push_back({p0, p->n, 0});
-  return true;
-}
-
-// Plain and CTC-merged profiles (p->nCols > 0, mb_profile_merge.hip) share the entry points below: the merged lattice has nCols + 1
-// planes of the plain one, its own kernels and its own rolling state.
-static long long pf_planes(const mb_profiles *p) { return p->nCols ? p->nCols + 1 : 1; }
-static long long pf_width(const mb_profiles *p) { return p->nCols ? p->nCols + 1 : p->m->nOut + 1; }   // doubles of a row
-static long long pf_cells(const mb_profiles *p, long long nRows) { return profile_cells(p->m->S, nRows) * pf_planes(p); }
-static MergeMap pf_map(const mb_profiles *p) { return MergeMap{p->nCols, p->d_colTok}; }
-// doubles of global scratch a workgroup of the Forward / Viterbi (mat: materialised) or of the rolling Backward sweep needs (0: LDS)
-static long long pf_fwd_scratch(const mb_profiles *p, bool mat) {
-  const int S = p->m->S;
-  if (!p->nCols) return mat || profile_lds_bytes(S) ? 0 : 3LL * S;
-  return profile_merge_fwd_lds(S, p->nCols, mat) ? 0 : profile_merge_ring(S, p->nCols);
-}
-static long long pf_bwd_scratch(const mb_profiles *p) {
-  const int S = p->m->S;
-  if (!p->nCols) return profile_lds_bytes(S) ? 0 : 3LL * S;
-  return profile_merge_bwd_lds(S, p->nCols) ? 0 : profile_merge_ring(S, p->nCols);
-}
-static int pf_fwd(const mb_profiles *p, int mode, bool mat, const ProfDesc *d, int n, double *pool, double *scratch, double *loglike) {
-  return p->nCols ? launch_profile_merge_fwd(p->m, pf_map(p), mode, mat, d, n, p->d_logP, pool, scratch, loglike, g_stream)
-                  : launch_profile_fwd(p->m, mode, mat, d, n, p->d_logP, pool, scratch, loglike, g_stream);
-}
-static int pf_bwd(const mb_profiles *p, bool mat, const ProfDesc *d, int n, double *pool, const double *fwdPool, double *scratch,
-                  double *loglike, double *part, long long nTrans) {
-  return p->nCols ? launch_profile_merge_bwd(p->m, pf_map(p), mat, d, n, p->d_logP, pool, fwdPool, scratch, loglike, part, nTrans, g_stream)
-                  : launch_profile_bwd(p->m, mat, d, n, p->d_logP, pool, fwdPool, scratch, loglike, part, nTrans, g_stream);
-}
-static int pf_traceback(const mb_profiles *p, const ProfDesc *d, int n, const double *pool, uint32_t *edges, int32_t *rows, long long *len) {
-  return p->nCols ? launch_profile_merge_traceback(p->m, pf_map(p), d, n, p->d_logP, pool, edges, rows, len, g_stream)
-                  : launch_profile_traceback(p->m, d, n, p->d_logP, pool, edges, rows, len, g_stream);
-}
-static const char *pf_name(const mb_profiles *p, const char *plain, const char *merged) { return p->nCols ? merged : plain; }
-
-// descriptors of profiles [p0, p1): lattices and traceback slots packed from 0; returns the pool doubles and path entries
-static int profile_descs(const mb_profiles *p, long long p0, long long p1, ProfDesc **d_out, long long *cells, long long *paths) {
-  std::vector<ProfDesc> h((size_t)(p1 - p0));
-  long long c = 0, t = 0;
-  for (long long k = p0; k < p1; ++k) {
-    ProfDesc &d = h[(size_t)(k - p0)];
-    d.rowBase = p->rowOff[k]; d.nRows = (int)(p->rowOff[k + 1] - p->rowOff[k]); d.cellBase = c; d.pathBase = t; d.pad = 0;
-    c += pf_cells(p, d.nRows);
-    t += profile_path_bound(p->m->nLevF, d.nRows);
-  }
-  if (cells) *cells = c;
-  if (paths) *paths = t;
-  MB_HIP(sm_alloc((void **)d_out, std::max<size_t>(h.size(), 1) * sizeof(ProfDesc)));
-  if (!h.empty() && (!hip_ok(hipMemcpyAsync(*d_out, h.data(), h.size() * sizeof(ProfDesc), hipMemcpyHostToDevice, g_stream), "H2D profile descriptors") ||
-                     !hip_ok(hipStreamSynchronize(g_stream), "H2D profile descriptors"))) { sm_free(*d_out); *d_out = nullptr; return 1; }
-  return 0;
-}
-
-static int profile_scratch(long long perGroup, long long n, double **scratch) {
-  *scratch = nullptr;
-  if (!perGroup || n == 0) return 0;
-  *scratch = (double *)ws_get(1, (size_t)n * perGroup * sizeof(double));
-  return *scratch ? 0 : 1;
-}
-
-// Forward (MB_FORWARD) or Viterbi scores without paths (MB_VITERBI); mat: through the materialised lattice
-static int profiles_scores(mb_profiles *p, int mode, bool mat, double *loglike) {
-  const double rollBytes = 8.0 * pf_fwd_scratch(p, mat);
-  std::vector<Chunk> chunks;
-  if (!profile_chunks(p, [&](long long k) { return (mat ? 8.0 * pf_cells(p, p->rowOff[k + 1] - p->rowOff[k]) : 0.0) + rollBytes; }, chunks)) return 1;
-  double *d_ll = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
-  int rc = 0;
-  Timer tm;
-  for (const Chunk &c : chunks) {
-    ProfDesc *d = nullptr;
-    long long cells = 0;
-    if ((rc = profile_descs(p, c.p0, c.p1, &d, &cells, nullptr))) break;
-    const long long np = c.p1 - c.p0;
-    double *pool = nullptr, *scratch = nullptr;
-    if (mat) { pool = (double *)ws_get(0, (size_t)std::max<long long>(cells, 1) * sizeof(double)); if (!pool) rc = 1; }
-    if (!rc) rc = profile_scratch(pf_fwd_scratch(p, mat), np, &scratch);
-    if (!rc) {
-      tm.start();
-      rc = pf_fwd(p, mode, mat, d, (int)np, pool, scratch, d_ll + c.p0);
-      g_last_ms += tm.stop();
-      ++g_last_launches;
-    }
-    if (rc) quiesce_streams();
-    sm_free(d);
-    if (rc) break;
-  }
-  if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
-  sm_free(d_ll);
-  g_last_kernel = mode == MB_VITERBI ? (mat ? pf_name(p, "k_profile_fwd<max,mat>", "k_profile_merge_fwd<max,mat>") : pf_name(p, "k_profile_fwd<max,rolling>", "k_profile_merge_fwd<max,rolling>"))
-                                     : (mat ? pf_name(p, "k_profile_fwd<sum,mat>", "k_profile_merge_fwd<sum,mat>") : pf_name(p, "k_profile_fwd<sum,rolling>", "k_profile_merge_fwd<sum,rolling>"));
-  return rc;
-}
-
-}  // namespace mb
-
-extern "C" {
-
-// nCols = 0: plain profiles, rows of nOutTok + 1 doubles; nCols > 0: merged, rows of nCols + 1 doubles and the column map colTok
-static mb_profiles *profiles_create(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff, int nCols, const int32_t *colTok) {
-  if (!m || nProfiles < 0 || (nProfiles > 0 && !rowOff)) { set_error("null argument"); return nullptr; }
-  if (ensure_init()) return nullptr;
-  mb_profiles *p = new mb_profiles();
-  p->m = m; p->n = nProfiles; p->nCols = nCols;
-  p->rowOff.assign((size_t)nProfiles + 1, 0);
-  for (long long k = 0; k < nProfiles; ++k) {
-    const long long len = rowOff[k + 1] - rowOff[k];
-    if (len < 0 || len > 0x3fffffff) { set_error("bad profile row offsets"); delete p; return nullptr; }
-    p->rowOff[(size_t)k + 1] = p->rowOff[(size_t)k] + len;
-  }
-  p->totalRows = p->rowOff.back();
-  const long long C = nCols ? nCols + 1 : m->nOut + 1, nv = p->totalRows * C;
-  const double *v0 = logP ? logP + (nProfiles ? rowOff[0] * C : 0) : nullptr;
-  if (nv && !v0) { set_error("null argument"); delete p; return nullptr; }
-  if (!profile_values_ok(v0, nv)) { delete p; return nullptr; }
-  if (!hip_ok(hipMalloc((void **)&p->d_logP, (size_t)std::max<long long>(nv, 1) * sizeof(double)), "hipMalloc(profiles)")) { delete p; return nullptr; }
-  if (nCols && (!hip_ok(hipMalloc((void **)&p->d_colTok, (size_t)nCols * sizeof(int)), "hipMalloc(profile columns)") ||
-                !hip_ok(hipMemcpyAsync(p->d_colTok, colTok, (size_t)nCols * sizeof(int), hipMemcpyHostToDevice, g_stream), "H2D profile columns"))) { mb_profiles_destroy(p); return nullptr; }
-  if (nv && h2d_large(p->d_logP, v0, (size_t)nv * sizeof(double))) { mb_profiles_destroy(p); return nullptr; }
-  if (!hip_ok(hipStreamSynchronize(g_stream), "H2D profiles")) { mb_profiles_destroy(p); return nullptr; }
-  return p;
-}
-
-static bool merge_map_ok(const mb_machine *m, int32_t nCols, const int32_t *colTok) {
-  if (!m) { set_error("null argument"); return false; }
-  if (nCols < 1 || nCols > 0xffff) { set_error("merged profiles need 1..65535 columns"); return false; }
-  if (!colTok) { set_error("null argument"); return false; }
-  for (int c = 0; c < nCols; ++c)
-    if (colTok[c] < 1 || colTok[c] > m->nOut) { set_error("column " + std::to_string(c + 1) + ": token " + std::to_string(colTok[c]) + " is outside 1..nOutTok"); return false; }
-  return true;
-}
-
-mb_profiles *mb_profiles_create(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff) {
-  ApiGuard guard;
-  return profiles_create(m, nProfiles, logP, rowOff, 0, nullptr);
-}
-
-mb_profiles *mb_profiles_create_merged(mb_machine *m, int64_t nProfiles, const double *logP, const int64_t *rowOff, int32_t nCols, const int32_t *colTok) {
-  ApiGuard guard;
-  if (!merge_map_ok(m, nCols, colTok)) return nullptr;
-  return profiles_create(m, nProfiles, logP, rowOff, nCols, colTok);
-}
-
-void mb_profiles_destroy(mb_profiles *p) {
-  ApiGuard guard;
-  if (!p) return;
-  if (p->d_logP) (void)hipFree(p->d_logP);
-  if (p->d_colTok) (void)hipFree(p->d_colTok);
-  delete p;
-}
-
-int mb_profiles_forward(mb_profiles *p, int flags, double *loglike) {
-  ApiGuard guard;
-  if (!p || (!loglike && p->n)) { set_error("null argument"); return 1; }
-  if (flags != MB_ROLLING && flags != MB_MATERIALISE) { set_error("unknown flags"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  return profiles_scores(p, MB_FORWARD, flags == MB_MATERIALISE, loglike);
-}
-
-int64_t mb_profile_path_bound(const mb_machine *m, int64_t nRows) {
-  if (!m || nRows < 0) return 0;
-  return profile_path_bound(m->nLevF, nRows);
-}
-
-int mb_profiles_viterbi(mb_profiles *p, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow, int64_t pathCap) {
-  ApiGuard guard;
-  if (!p || (!loglike && p->n)) { set_error("null argument"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  if (!pathEdges || !pathOff) return profiles_scores(p, MB_VITERBI, false, loglike);
-  const mb_machine *m = p->m;
-  std::vector<Chunk> chunks;
-  const long long vScratch = pf_fwd_scratch(p, true);
-  auto bytes = [&](long long k) { const long long L = p->rowOff[k + 1] - p->rowOff[k]; return 8.0 * pf_cells(p, L) + 8.0 * profile_path_bound(m->nLevF, L) + 8.0 * vScratch; };
-  if (!profile_chunks(p, bytes, chunks)) return 1;
-  double *d_ll = nullptr;
-  long long *d_len = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
-  if (!hip_ok(sm_alloc((void **)&d_len, std::max<long long>(p->n, 1) * sizeof(long long)), "hipMalloc(path lengths)")) { sm_free(d_ll); return 1; }
-  int rc = 0;
-  Timer tm;
-  long long written = 0;
-  pathOff[0] = 0;
-  std::vector<long long> len;
-  std::vector<uint32_t> he;
-  std::vector<int32_t> hr;
-  for (const Chunk &c : chunks) {
-    ProfDesc *d = nullptr;
-    long long cells = 0, paths = 0;
-    if ((rc = profile_descs(p, c.p0, c.p1, &d, &cells, &paths))) break;
-    const long long np = c.p1 - c.p0;
-    double *pool = (double *)ws_get(0, (size_t)std::max<long long>(cells, 1) * sizeof(double));
-    uint32_t *d_e = (uint32_t *)ws_get(3, (size_t)std::max<long long>(paths, 1) * sizeof(uint32_t));
-    int32_t *d_r = (int32_t *)ws_get(4, (size_t)std::max<long long>(paths, 1) * sizeof(int32_t));
-    double *scratch = nullptr;
-    if (!pool || !d_e || !d_r || profile_scratch(vScratch, np, &scratch)) rc = 1;
-    if (!rc) {
-      tm.start();
-      rc = pf_fwd(p, MB_VITERBI, true, d, (int)np, pool, scratch, d_ll + c.p0);
-      if (!rc) rc = pf_traceback(p, d, (int)np, pool, d_e, d_r, d_len + c.p0);
-      g_last_ms += tm.stop();
-      ++g_last_launches;
-    }
-    len.resize((size_t)np); he.resize((size_t)std::max<long long>(paths, 1)); hr.resize(he.size());
-    if (!rc && !hip_ok(hipMemcpy(len.data(), d_len + c.p0, np * sizeof(long long), hipMemcpyDeviceToHost), "D2H path lengths")) rc = 1;
-    if (!rc && paths && (d2h_large(he.data(), d_e, paths * sizeof(uint32_t)) || (pathRow && d2h_large(hr.data(), d_r, paths * sizeof(int32_t))))) rc = 1;
-    long long base = 0;
-    for (long long k = 0; k < np && !rc; ++k) {
-      const long long L = p->rowOff[c.p0 + k + 1] - p->rowOff[c.p0 + k];
-      long long n = len[(size_t)k];
-      if (n == -1) n = 0;   // no finite path: an empty one (the reference refuses to trace it)
-      else if (n < 0) { set_error(n == -2 ? "profile traceback overflowed its bound" : "profile traceback found no matching candidate"); rc = 1; break; }
-      if (written + n > pathCap) { set_error("pathCap too small for the Viterbi paths"); rc = 1; break; }
-      std::memcpy(pathEdges + written, he.data() + base, (size_t)n * sizeof(uint32_t));
-      if (pathRow) std::memcpy(pathRow + written, hr.data() + base, (size_t)n * sizeof(int32_t));
-      written += n;
-      pathOff[c.p0 + k + 1] = written;
-      base += profile_path_bound(m->nLevF, L);
-    }
-    if (rc) quiesce_streams();
-    sm_free(d);
-    if (rc) break;
-  }
-  if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
-  sm_free(d_ll); sm_free(d_len);
-  g_last_kernel = pf_name(p, "k_profile_fwd<max,mat>", "k_profile_merge_fwd<max,mat>");
-  return rc;
-}
-
-int mb_profiles_counts(mb_profiles *p, double *counts, double *loglikeSum, double *loglike) {
-  ApiGuard guard;
-  if (!p || !counts) { set_error("null argument"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  const mb_machine *m = p->m;
-  const long long nT = m->nTrans;
-  const long long PL = pf_planes(p), cScratch = std::max(pf_fwd_scratch(p, true), pf_bwd_scratch(p));   // one buffer serves both sweeps
-  std::vector<Chunk> chunks;
-  auto bytes = [&](long long k) { return 8.0 * pf_cells(p, p->rowOff[k + 1] - p->rowOff[k]) + 8.0 * nT * PL + 8.0 * cScratch; };
-  if (!profile_chunks(p, bytes, chunks)) return 1;
-  double *d_ll = nullptr, *d_bll = nullptr, *d_cc = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
-  if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
-      !hip_ok(sm_alloc((void **)&d_cc, std::max<long long>(nT, 1) * sizeof(double)), "hipMalloc(counts)")) { sm_free(d_ll); sm_free(d_bll); sm_free(d_cc); return 1; }
-  int rc = 0;
-  Timer tm;
-  std::vector<double> total((size_t)nT, 0.0), hc((size_t)nT);
-  for (const Chunk &c : chunks) {
-    ProfDesc *d = nullptr;
-    long long cells = 0;
-    if ((rc = profile_descs(p, c.p0, c.p1, &d, &cells, nullptr))) break;
-    const long long np = c.p1 - c.p0;
-    double *pool = (double *)ws_get(0, (size_t)std::max<long long>(cells, 1) * sizeof(double));
-    double *part = (double *)ws_get(2, (size_t)std::max<long long>(np * PL * nT, 1) * sizeof(double));
-    double *scratch = nullptr;
-    if (!pool || !part || profile_scratch(cScratch, np, &scratch)) rc = 1;
-    if (!rc && np * PL > 0x7fffffff) { set_error("too many profile planes in one chunk"); rc = 1; }
-    if (!rc) {
-      tm.start();
-      rc = pf_fwd(p, MB_FORWARD, true, d, (int)np, pool, scratch, d_ll + c.p0);
-      if (!rc && nT) rc = hip_ok(hipMemsetAsync(part, 0, (size_t)np * PL * nT * sizeof(double), g_stream), "memset(counts)") ? 0 : 1;
-      if (!rc) rc = pf_bwd(p, false, d, (int)np, nullptr, pool, scratch, d_bll + c.p0, part, nT);
-      if (!rc) rc = launch_profile_sum_counts(part, (int)(np * PL), nT, d_cc, g_stream);   // merged: over profiles, then planes
-      g_last_ms += tm.stop();
-      ++g_last_launches;
-    }
-    if (!rc && nT && !hip_ok(hipMemcpy(hc.data(), d_cc, nT * sizeof(double), hipMemcpyDeviceToHost), "D2H counts")) rc = 1;
-    if (!rc) for (long long e = 0; e < nT; ++e) total[(size_t)e] += hc[(size_t)e];
-    if (rc) quiesce_streams();
-    sm_free(d);
-    if (rc) break;
-  }
-  std::vector<double> hll((size_t)p->n);
-  if (!rc && p->n && !hip_ok(hipMemcpy(hll.data(), d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
-  sm_free(d_ll); sm_free(d_bll); sm_free(d_cc);
-  g_last_kernel = pf_name(p, "k_profile_bwd<counts>", "k_profile_merge_bwd<counts>");
-  if (rc) return rc;
-  for (long long e = 0; e < nT; ++e) counts[e] += total[(size_t)e];
-  double s = 0.0;
-  for (long long k = 0; k < p->n; ++k) { s += hll[(size_t)k]; if (loglike) loglike[k] = hll[(size_t)k]; }
-  if (loglikeSum) *loglikeSum += s;
-  return 0;
-}
-
-static int pp_rowpost_table();   // (below, beside the pair sweeps: the LDS table under MB_ROWPOST_TABLE)
-
-// Row posteriors of plain and merged profiles: the materialised Forward, the materialised Backward and the flat k_profile_rowpost
-// over both lattices (mb_profile_post.hip).  The lattices take slots 0 and 1, the Forward's scratch slot 2.
-int mb_profiles_row_posteriors(mb_profiles *p, double *post, double *loglike) {
-  ApiGuard guard;
-  if (!p || (!post && p->totalRows)) { set_error("null argument"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
-  const mb_machine *m = p->m;
-  const long long PL = pf_planes(p), C = pf_width(p), nv = p->totalRows * C, fScratch = pf_fwd_scratch(p, true);
-  const int tabMax = pp_rowpost_table();
-  std::vector<Chunk> chunks;
-  auto rowsOf = [&](long long k) { return p->rowOff[k + 1] - p->rowOff[k]; };
-  auto bytes = [&](long long k) { return 2.0 * 8.0 * pf_cells(p, rowsOf(k)) + 8.0 * (double)(rowsOf(k) * C) + 8.0 * fScratch; };   // both lattices, the bins, the sweeps' scratch
-  if (!profile_chunks(p, bytes, chunks)) return 1;
-  double *d_ll = nullptr, *d_bll = nullptr, *d_post = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
-  if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
-      !hip_ok(sm_alloc((void **)&d_post, std::max<long long>(nv, 1) * sizeof(double)), "hipMalloc(row posteriors)")) { sm_free(d_ll); sm_free(d_bll); sm_free(d_post); return 1; }
-  int rc = 0;
-  Timer tm;
-  for (const Chunk &c : chunks) {
-    ProfDesc *d = nullptr;
-    long long cells = 0;
-    if ((rc = profile_descs(p, c.p0, c.p1, &d, &cells, nullptr))) break;
-    const long long np = c.p1 - c.p0;
-    double *fwd = (double *)ws_get(0, (size_t)std::max<long long>(cells, 1) * sizeof(double));
-    double *bwd = (double *)ws_get(1, (size_t)std::max<long long>(cells, 1) * sizeof(double));
-    double *scratch = fScratch && np ? (double *)ws_get(2, (size_t)(np * fScratch) * sizeof(double)) : nullptr;
-    if (!fwd || !bwd || (fScratch && np && !scratch)) rc = 1;
-    long long groups = 1;      // the row blocks of the profile that has most (a group past a profile's last block has nothing to do)
-    for (long long k = c.p0; k < c.p1; ++k) {
-      const long long L = rowsOf(k), R = profile_rowpost_rows(m->S, (int)PL, L, (int)C, tabMax);
-      groups = std::max(groups, (L + R - 1) / R);
-    }
-    groups = std::min<long long>(groups, 1024);
-    if (!rc && np * groups > 0x7fffffff) { set_error("too many profiles in one chunk"); rc = 1; }
-    if (!rc) {
-      tm.start();
-      rc = pf_fwd(p, MB_FORWARD, true, d, (int)np, fwd, scratch, d_ll + c.p0);
-      if (!rc) rc = pf_bwd(p, true, d, (int)np, bwd, nullptr, nullptr, d_bll + c.p0, nullptr, 0);
-      if (!rc) rc = launch_profile_rowpost(m, pf_map(p), d, (int)np, (int)groups, tabMax, p->d_logP, fwd, bwd, d_ll + c.p0, d_post, g_stream);
-      g_last_ms += tm.stop();
-      ++g_last_launches;
-    }
-    if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "row posteriors")) rc = 1;      // (the next chunk takes the lattices over)
-    if (rc) quiesce_streams();
-    sm_free(d);
-    if (rc) break;
-  }
-  if (!rc && nv && d2h_large(post, d_post, (size_t)nv * sizeof(double))) rc = 1;
-  if (!rc && g_deterministic)
-    for (long long e = 0; e < nv && !rc; ++e) {      // fixed point, 2^-36 (a posterior is at most 1: far inside the range)
-      unsigned long long u; std::memcpy(&u, &post[e], 8);
-      if (!det_to_double(u, post[e])) { set_error("MB_DETERMINISTIC: a row posterior left the fixed-point range"); rc = 1; }
-    }
-  std::vector<double> hll((size_t)p->n);
-  if (!rc && p->n && !hip_ok(hipMemcpy(hll.data(), d_ll, p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
-  sm_free(d_ll); sm_free(d_bll); sm_free(d_post);
-  g_last_kernel = pf_name(p, "k_profile_rowpost", "k_profile_merge_rowpost");
-  if (rc) return rc;
-  if (loglike) for (long long k = 0; k < p->n; ++k) loglike[k] = hll[(size_t)k];
-  return 0;
-}
-
-int mb_profiles_set_rows(mb_profiles *p, const double *logP) {
-  ApiGuard guard;
-  if (!p) { set_error("null argument"); return 1; }
-  const long long nv = p->totalRows * pf_width(p);
-  if (nv && !logP) { set_error("null argument"); return 1; }
-  if (!profile_values_ok(logP, nv)) return 1;
-  if (nv && h2d_large(p->d_logP, logP, (size_t)nv * sizeof(double))) return 1;
-  return hip_ok(hipStreamSynchronize(g_stream), "H2D profiles") ? 0 : 1;
-}
-
-static int profile_fill(mb_machine *m, int mode, const double *logP, int64_t nRows, int nCols, const int32_t *colTok, double *cellsOut) {
-  if (!m || !cellsOut || nRows < 0 || (nRows && !logP)) { set_error("null argument"); return 1; }
-  if (mode != MB_FORWARD && mode != MB_VITERBI && mode != MB_BACKWARD) { set_error("unknown fill mode"); return 1; }
-  if (ensure_init()) return 1;
-  g_last_ms = 0.0; g_last_launches = 0;
-  const int64_t off[2] = {0, nRows};
-  mb_profiles *p = profiles_create(m, 1, logP, off, nCols, colTok);
-  if (!p) return 1;
-  ProfDesc *d = nullptr;
-  long long cells = 0;
-  int rc = profile_descs(p, 0, 1, &d, &cells, nullptr);
-  double *d_ll = nullptr, *scratch = nullptr;
-  if (!rc && !hip_ok(sm_alloc((void **)&d_ll, sizeof(double)), "hipMalloc(loglike)")) rc = 1;
-  double *pool = rc ? nullptr : (double *)ws_get(0, (size_t)cells * sizeof(double));
-  if (!rc && !pool) rc = 1;
-  if (!rc && mode != MB_BACKWARD) rc = profile_scratch(pf_fwd_scratch(p, true), 1, &scratch);
-  if (!rc) {
-    Timer tm;
-    tm.start();
-    rc = mode == MB_BACKWARD ? pf_bwd(p, true, d, 1, pool, nullptr, nullptr, d_ll, nullptr, 0)
-                             : pf_fwd(p, mode, true, d, 1, pool, scratch, d_ll);
-    g_last_ms += tm.stop();
-    g_last_launches = 1;
-  }
-  if (!rc) rc = d2h_large(cellsOut, pool, (size_t)cells * sizeof(double));
-  if (rc) quiesce_streams();
-  sm_free(d); sm_free(d_ll);
-  g_last_kernel = mode == MB_BACKWARD ? pf_name(p, "k_profile_bwd<mat>", "k_profile_merge_bwd<mat>")
-                                      : (mode == MB_VITERBI ? pf_name(p, "k_profile_fwd<max,mat>", "k_profile_merge_fwd<max,mat>") : pf_name(p, "k_profile_fwd<sum,mat>", "k_profile_merge_fwd<sum,mat>"));
-  mb_profiles_destroy(p);
-  return rc;
-}
-
-int mb_profile_fill(mb_machine *m, int mode, const double *logP, int64_t nRows, double *cellsOut) {
-  ApiGuard guard;
-  return profile_fill(m, mode, logP, nRows, 0, nullptr, cellsOut);
-}
-
-int mb_profile_fill_merged(mb_machine *m, int mode, const double *logP, int64_t nRows, int32_t nCols, const int32_t *colTok, double *cellsOut) {
-  ApiGuard guard;
-  if (!merge_map_ok(m, nCols, colTok)) return 1;
-  return profile_fill(m, mode, logP, nRows, nCols, colTok, cellsOut);
-}
-
-// ---- two-tape profile sweeps: an input sequence against a profile (mb_profile_pair.hip, docs/profile_tapes.md "Pairs") ----------
-// Split the pairs into chunks whose device memory (bytesPer(pair k)) fits the budget; even-sized like profile_chunks.
-static bool lattice_chunks(long long n, const std::function<double(long long)> &bytesPer, std::vector<Chunk> &out) {
-  const double budget = (double)budget_bytes();
-  double total = 0.0;
-  for (long long k = 0; k < n; ++k) {
-    const double b = bytesPer(k);
-    if (b > budget) { set_error("one pair's DP lattice (" + std::to_string((long long)b) + " bytes) exceeds the device memory budget"); return false; }
-    total += b;
-  }
-  const double nChunks = std::max(1.0, std::ceil(total / budget));
-  const double share = std::min(budget, total / nChunks * 1.05);
-  long long p0 = 0;
-  double acc = 0.0;
-  for (long long k = 0; k < n; ++k) {
-    const double b = bytesPer(k);
-    if (k > p0 && (acc + b > budget || (acc >= share && acc + b > share) || k - p0 >= (1 << 30))) { out.push_back({p0, k, 0}); p0 = k; acc = 0.0; }
-    acc += b;
-  }
-  if (n > p0) out.push_back({p0, n, 0});
-  return true;
-}
-
-static bool pair_profile_chunks(const mb_profile_pairs *p, const std::function<double(long long)> &bytesPer, std::vector<Chunk> &out) { return lattice_chunks(p->n, bytesPer, out); }
-
-static long long pp_in(const mb_profile_pairs *p, long long k) { return p->inOff[k + 1] - p->inOff[k]; }
-static long long pp_rows(const mb_profile_pairs *p, long long k) { return p->rowOff[k + 1] - p->rowOff[k]; }
-static bool pp_env(const mb_profile_pairs *p, long long k) { return p->hasEnv && p->envBase[(size_t)k] >= 0; }
-// doubles of pair k's materialised lattice: the rectangle, or the compact lattice of its envelope
-static long long pp_cells(const mb_profile_pairs *p, long long k) {
-  if (pp_env(p, k)) return p->envCells[(size_t)k] * 2 * (long long)p->m->S;
-  return profile_pair_cells(p->m->S, pp_in(p, k), pp_rows(p, k)) * (p->nCols + 1);
-}
-static double pp_cell_bytes(const mb_profile_pairs *p, long long k) { return 8.0 * (double)pp_cells(p, k); }
-// The ring of pair k's sweep and its dynamic LDS (0: a slice of the global scratch buffer).  Plain profiles: the rolling sweep alone
-// has one.  Merged: the materialised sweeps keep their exclusion vectors in one too (mb_profile_pair_merge.h).
-static long long pp_ring(const mb_profile_pairs *p, long long k, bool rolling) {
-  if (p->nCols) return profile_pair_merge_ring(p->m->S, p->nCols, pp_in(p, k), pp_rows(p, k), !rolling);
-  if (pp_env(p, k)) return rolling ? profile_pair_env_ring(p->m->S, p->envM[(size_t)k]) : 0;
-  return rolling ? profile_pair_ring(p->m->S, pp_in(p, k), pp_rows(p, k)) : 0;
-}
-static size_t pp_ring_lds(const mb_profile_pairs *p, long long k, bool rolling) {
-  if (p->nCols) return profile_pair_merge_lds_bytes(p->m->S, p->nCols, pp_in(p, k), pp_rows(p, k), !rolling);
-  if (pp_env(p, k)) return rolling ? profile_pair_env_lds_bytes(p->m->S, p->envM[(size_t)k]) : 0;
-  return rolling ? profile_pair_lds_bytes(p->m->S, pp_in(p, k), pp_rows(p, k)) : 0;
-}
-// bytes of global scratch the sweep of pair k needs (0: its ring is in LDS, or it has none)
-static double pp_ring_bytes(const mb_profile_pairs *p, long long k, bool rolling) {
-  return pp_ring_lds(p, k, rolling) ? 0.0 : 8.0 * (double)pp_ring(p, k, rolling);
-}
-static MergeMap pp_map(const mb_profile_pairs *p) { return MergeMap{p->nCols, p->d_colTok}; }
-
-// Pairs with an envelope go to the kernels' envelope geometry in a launch of their own: a chunk's pairs without one come
-// first in its per-pair outputs (log-likelihoods, path lengths), then the pairs with one; slot[k - p0] is where pair k landed.
-struct PairProfPlan {
-  PairProfDesc *d = nullptr; PairEnvDesc *e = nullptr;
-  long long cells = 0, paths = 0, ring = 0, maxItems = 0, maxItemsEnv = 0, nPlain = 0, nEnv = 0;
-  size_t lds = 0, ldsEnv = 0;
-  std::vector<long long> slot;
-};
-static void pp_plan_free(PairProfPlan &pl) { sm_free(pl.d); sm_free(pl.e); pl.d = nullptr; pl.e = nullptr; }
-
-// descriptors of pairs [p0, p1): lattices, traceback slots and scratch rings packed from 0
-static int pair_profile_descs(const mb_profile_pairs *p, long long p0, long long p1, bool rolling, PairProfPlan &pl) {
-  std::vector<PairProfDesc> h;
-  std::vector<PairEnvDesc> he;
-  std::vector<long long> envPairs;
-  const int S = p->m->S;
-  pl.slot.assign((size_t)(p1 - p0), 0);
-  for (long long k = p0; k < p1; ++k) {
-    const long long I = pp_in(p, k), L = pp_rows(p, k);
-    long long ringBase = -1;
-    if (pp_ring(p, k, rolling)) {
-      const size_t lds = pp_ring_lds(p, k, rolling);
-      if (lds) { if (pp_env(p, k)) pl.ldsEnv = std::max(pl.ldsEnv, lds); else pl.lds = std::max(pl.lds, lds); }
-      else { ringBase = pl.ring; pl.ring += pp_ring(p, k, rolling); }
-    }
-    PairEnvDesc d;      // (a full pair keeps its PairProfDesc part)
-    d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)I; d.nRows = (int)L;
-    d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = ringBase;
-    if (pp_env(p, k)) {
-      d.envBase = p->envBase[(size_t)k]; d.diagBase = p->diagBase[(size_t)k]; d.nCells = p->envCells[(size_t)k]; d.M = p->envM[(size_t)k];
-      pl.maxItemsEnv = std::max(pl.maxItemsEnv, (long long)d.M * S);
-      he.push_back(d); envPairs.push_back(k);
-    } else {
-      pl.maxItems = std::max(pl.maxItems, (std::min(I, L) + 1) * S * (p->nCols + 1));
-      pl.slot[(size_t)(k - p0)] = (long long)h.size();
-      h.push_back(d);
-    }
-    pl.cells += pp_cells(p, k);
-    pl.paths += profile_pair_path_bound(p->m->nLevF, I, L);
-  }
-  pl.nPlain = (long long)h.size(); pl.nEnv = (long long)he.size();
-  for (size_t j = 0; j < envPairs.size(); ++j) pl.slot[(size_t)(envPairs[j] - p0)] = pl.nPlain + (long long)j;
-  MB_HIP(sm_alloc((void **)&pl.d, std::max<size_t>(h.size(), 1) * sizeof(PairProfDesc)));
-  if (!hip_ok(sm_alloc((void **)&pl.e, std::max<size_t>(he.size(), 1) * sizeof(PairEnvDesc)), "hipMalloc(pair descriptors)")) { pp_plan_free(pl); return 1; }
-  if ((!h.empty() && !hip_ok(hipMemcpyAsync(pl.d, h.data(), h.size() * sizeof(PairProfDesc), hipMemcpyHostToDevice, g_stream), "H2D pair descriptors")) ||
-      (!he.empty() && !hip_ok(hipMemcpyAsync(pl.e, he.data(), he.size() * sizeof(PairEnvDesc), hipMemcpyHostToDevice, g_stream), "H2D pair descriptors")) ||
-      !hip_ok(hipStreamSynchronize(g_stream), "H2D pair descriptors")) { pp_plan_free(pl); return 1; }
-  return 0;
-}
-static PairEnvTables pp_env_tables(const mb_profile_pairs *p) { return PairEnvTables{p->d_envStart, p->d_envEnd, p->d_envOff, p->d_diagLo, p->d_diagCnt}; }
-// per-pair device results (each chunk in the order of its plan's slots; at[k] = the entry of pair k) into dst[0..n)
-struct PairWhere {
-  std::vector<long long> at; bool permuted = false;
-  void add(long long p0, const PairProfPlan &pl) {
-    for (long long s : pl.slot) at.push_back(p0 + s);
-    permuted = permuted || pl.nEnv;
-  }
-};
-static int pp_fetch(double *dst, const double *d_src, long long n, const PairWhere &w, const char *what) {
-  if (n <= 0) return 0;
-  if (!w.permuted) return hip_ok(hipMemcpy(dst, d_src, (size_t)n * sizeof(double), hipMemcpyDeviceToHost), what) ? 0 : 1;
-  std::vector<double> tmp((size_t)n);
-  if (!hip_ok(hipMemcpy(tmp.data(), d_src, tmp.size() * sizeof(double), hipMemcpyDeviceToHost), what)) return 1;
-  for (long long k = 0; k < n; ++k) dst[k] = tmp[(size_t)w.at[(size_t)k]];
-  return 0;
-}
-
-// The one place where the plain and the merged kernels part: the launches of a chunk and the names they report.  The plain kernels
-// take the chunk's full pairs, then its pairs under an envelope, through the two overloads of one launcher.
-static int pp_launch_fwd(const mb_profile_pairs *p, int mode, bool mat, const PairProfPlan &pl, long long n, double *pool, double *scratch, double *ll) {
-  if (p->nCols) return launch_profile_pair_merge_fwd(p->m, pp_map(p), mode, mat, pl.d, (int)n, pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, ll, g_stream);
-  if (launch_profile_pair_fwd(p->m, mode, mat, pl.d, (int)pl.nPlain, mat ? 0 : pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, mat ? nullptr : scratch, ll, g_stream)) return 1;
-  return launch_profile_pair_fwd(p->m, mode, mat, pl.e, pp_env_tables(p), (int)pl.nEnv, mat ? 0 : pl.ldsEnv, pl.maxItemsEnv, p->d_in, p->d_logP, pool,
-                                 mat ? nullptr : scratch, ll + pl.nPlain, g_stream);
-}
-static int pp_launch_bwd(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, double *pool, double *scratch, double *ll) {
-  if (p->nCols) return launch_profile_pair_merge_bwd(p->m, pp_map(p), pl.d, (int)n, pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, ll, g_stream);
-  if (launch_profile_pair_bwd(p->m, pl.d, (int)pl.nPlain, pl.maxItems, p->d_in, p->d_logP, pool, ll, g_stream)) return 1;
-  return launch_profile_pair_bwd(p->m, pl.e, pp_env_tables(p), (int)pl.nEnv, pl.maxItemsEnv, p->d_in, p->d_logP, pool, ll + pl.nPlain, g_stream);
-}
-static int pp_launch_traceback(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, const double *pool, uint32_t *e, int32_t *r, long long *len) {
-  if (p->nCols) return launch_profile_pair_merge_traceback(p->m, pp_map(p), pl.d, (int)n, p->d_in, p->d_logP, pool, e, r, len, g_stream);
-  if (launch_profile_pair_traceback(p->m, pl.d, (int)pl.nPlain, p->d_in, p->d_logP, pool, e, r, len, g_stream)) return 1;
-  return launch_profile_pair_traceback(p->m, pl.e, pp_env_tables(p), (int)pl.nEnv, p->d_in, p->d_logP, pool, e, r, len + pl.nPlain, g_stream);
-}
-static int pp_launch_counts(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, int groups, const double *fwd, const double *bwd, double *cc) {
-  if (p->nCols) return launch_profile_pair_merge_counts(p->m, pp_map(p), pl.d, (int)n, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
-  if (launch_profile_pair_counts(p->m, pl.d, (int)pl.nPlain, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream)) return 1;
-  return launch_profile_pair_counts(p->m, pl.e, pp_env_tables(p), (int)pl.nEnv, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
-}
-static const char *pp_fwd_name(const mb_profile_pairs *p, int mode, bool mat) {
-  static const char *const names[2][2][2] = {{{"k_profile_pair_fwd<sum,rolling>", "k_profile_pair_fwd<sum,mat>"}, {"k_profile_pair_fwd<max,rolling>", "k_profile_pair_fwd<max,mat>"}},
-                                             {{"k_profile_pair_merge_fwd<sum,rolling>", "k_profile_pair_merge_fwd<sum,mat>"}, {"k_profile_pair_merge_fwd<max,rolling>", "k_profile_pair_merge_fwd<max,mat>"}}};
-  static const char *const envNames[2][2] = {{"k_profile_pair_env_fwd<sum,rolling>", "k_profile_pair_env_fwd<sum,mat>"}, {"k_profile_pair_env_fwd<max,rolling>", "k_profile_pair_env_fwd<max,mat>"}};
-  if (p->hasEnv) return envNames[mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];      // (a batch that mixes both kinds reports the envelope kernel)
-  return names[p->nCols ? 1 : 0][mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
-}
-// launches of a chunk: one per kind of pair it holds
-static int pp_chunk_launches(const PairProfPlan &pl) { return pl.nEnv && pl.nPlain ? 2 : 1; }
-
-// Forward (MB_FORWARD) or Viterbi scores without paths (MB_VITERBI); mat: through the materialised lattice
-static int pair_profile_scores(mb_profile_pairs *p, int mode, bool mat, double *loglike) {
-  std::vector<Chunk> chunks;
-  if (!pair_profile_chunks(p, [&](long long k) { return (mat ? pp_cell_bytes(p, k) : 0.0) + pp_ring_bytes(p, k, !mat); }, chunks)) return 1;
-  double *d_ll = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
-  int rc = 0;
-  Timer tm;
-  PairWhere where;
-  for (const Chunk &c : chunks) {
-    PairProfPlan pl;
-    if ((rc = pair_profile_descs(p, c.p0, c.p1, !mat, pl))) break;
-    where.add(c.p0, pl);
-    double *pool = nullptr, *scratch = nullptr;
-    if (mat) { pool = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double)); if (!pool) rc = 1; }
-    if (!rc && pl.ring) { scratch = (double *)ws_get(1, (size_t)pl.ring * sizeof(double)); if (!scratch) rc = 1; }
-    if (!rc) {
-      tm.start();
-      rc = pp_launch_fwd(p, mode, mat, pl, c.p1 - c.p0, pool, scratch, d_ll + c.p0);
-      g_last_ms += tm.stop();
-      g_last_launches += pp_chunk_launches(pl);
-    }
-    if (rc) quiesce_streams();
-    pp_plan_free(pl);
-    if (rc) break;
-  }
-  if (!rc && pp_fetch(loglike, d_ll, p->n, where, "D2H loglike")) rc = 1;
-  sm_free(d_ll);
-  g_last_kernel = pp_fwd_name(p, mode, mat);
-  return rc;
-}
-
-// ---- envelopes of the pairs (mb_profile_pair_env.h, docs/profile_tapes.md "Pairs under an envelope") ----
-static void pp_env_free(mb_profile_pairs *p) {
-  if (p->d_envStart) (void)hipFree(p->d_envStart);
-  if (p->d_envEnd) (void)hipFree(p->d_envEnd);
-  if (p->d_envOff) (void)hipFree(p->d_envOff);
-  if (p->d_diagLo) (void)hipFree(p->d_diagLo);
-  if (p->d_diagCnt) (void)hipFree(p->d_diagCnt);
-  p->d_envStart = p->d_envEnd = p->d_diagLo = p->d_diagCnt = nullptr; p->d_envOff = nullptr;
-  p->hasEnv = false;
-  p->envBase.clear(); p->diagBase.clear(); p->envCells.clear(); p->envM.clear(); p->h_envStart.clear(); p->h_envEnd.clear();
-}
-
-// Checks as mb_batch_set_envelopes (fits, connected) and, new here, that neither bound decreases from one row to the next: the
-// sweeps rest on the envelope cells of an anti-diagonal being consecutive.  A rejected call leaves the pairs without envelopes.
-static int profile_pairs_set_envelopes(mb_profile_pairs *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
-  pp_env_free(p);
-  if (!envOff) return 0;
-  const long long total = envOff[p->n] - envOff[0];
-  if (total && p->nCols) { set_error("envelopes take plain profiles"); return 1; }
-  if (total && (!inStart || !inEnd)) { set_error("null argument"); return 1; }
-  std::vector<long long> envBase((size_t)p->n, -1), diagBase((size_t)p->n, -1), envCells((size_t)p->n, 0), hOff;
-  std::vector<int> envM((size_t)p->n, 0), hSt, hEn, hLo, hCnt;
-  for (long long k = 0; k < p->n; ++k) {
-    const long long rows = envOff[k + 1] - envOff[k], I = pp_in(p, k), L = pp_rows(p, k);
-    if (rows == 0) continue;   // full: the pair keeps the full geometry of mb_profile_pair.hip
-    if (rows != L + 1) { set_error("Envelope/sequence mismatch"); return 1; }
-    const int32_t *st = inStart + envOff[k], *en = inEnd + envOff[k];
-    for (long long y = 0; y < rows; ++y)
-      if (st[y] < 0 || en[y] > I + 1 || st[y] > en[y]) { set_error("Envelope/sequence mismatch"); return 1; }
-    bool conn = env_overlapping(st[0], en[0], 0, 1);
-    for (long long y = 1; conn && y < rows; ++y) conn = env_overlapping(st[y - 1], (long long)en[y - 1] + 1, st[y], en[y]);
-    conn = conn && env_overlapping(st[rows - 1], en[rows - 1], I, I + 1);
-    if (!conn) { set_error("Envelope is not connected"); return 1; }
-    for (long long y = 1; y < rows; ++y)
-      if (st[y] < st[y - 1] || en[y] < en[y - 1]) { set_error("Envelope is not monotone"); return 1; }
-    envBase[(size_t)k] = (long long)hSt.size(); diagBase[(size_t)k] = (long long)hLo.size();
-    const size_t d0 = hLo.size();
-    hLo.resize(d0 + (size_t)(I + L + 1), 0); hCnt.resize(d0 + (size_t)(I + L + 1), 0);
-    long long cells = 0;
-    for (long long y = 0; y < rows; ++y) {
-      hSt.push_back(st[y]); hEn.push_back(en[y]); hOff.push_back(cells);
-      cells += en[y] - st[y];
-      // row y puts one cell on each of the diagonals st[y] + y .. en[y] - 1 + y; the rows go upwards, so on a diagonal every
-      // later row holds a smaller i than the rows before it: the last one written is the diagonal's first i
-      for (long long i = st[y]; i < en[y]; ++i) { hLo[d0 + (size_t)(i + y)] = (int)i; ++hCnt[d0 + (size_t)(i + y)]; }
-    }
-    envCells[(size_t)k] = cells;
-    int M = 1;
-    for (size_t d = d0; d < hLo.size(); ++d) M = std::max(M, hCnt[d]);
-    envM[(size_t)k] = M;
-  }
-  if (hSt.empty()) return 0;
-  if (ensure_init()) return 1;
-  auto up = [&](void **dst, const void *src, size_t bytes) {
-    return hip_ok(hipMalloc(dst, std::max<size_t>(bytes, 8)), "hipMalloc(pair envelopes)") && h2d_large(*dst, src, bytes) == 0;
-  };
-  if (!up((void **)&p->d_envStart, hSt.data(), hSt.size() * sizeof(int)) || !up((void **)&p->d_envEnd, hEn.data(), hEn.size() * sizeof(int)) ||
-      !up((void **)&p->d_envOff, hOff.data(), hOff.size() * sizeof(long long)) || !up((void **)&p->d_diagLo, hLo.data(), hLo.size() * sizeof(int)) ||
-      !up((void **)&p->d_diagCnt, hCnt.data(), hCnt.size() * sizeof(int)) || !hip_ok(hipStreamSynchronize(g_stream), "H2D pair envelopes")) { pp_env_free(p); return 1; }
-  p->envBase.swap(envBase); p->diagBase.swap(diagBase); p->envCells.swap(envCells); p->envM.swap(envM);
-  p->h_envStart.swap(hSt); p->h_envEnd.swap(hEn);
-  p->hasEnv = true;
-  return 0;
-}
-
-// nCols > 0: CTC-merged profiles, rows of nCols + 1 doubles and the column map colTok (checked by the caller)
-static mb_profile_pairs *profile_pairs_create(mb_machine *m, int64_t nPairs, const int32_t *inTok, const int64_t *inOff, const double *logP,
-                                              const int64_t *rowOff, int32_t nCols, const int32_t *colTok) {
-  if (!m || nPairs < 0 || (nPairs > 0 && (!rowOff || !inOff))) { set_error("null argument"); return nullptr; }
-  if (ensure_init()) return nullptr;
-  mb_profile_pairs *p = new mb_profile_pairs();
-  p->m = m; p->n = nPairs; p->nCols = nCols;
-  p->rowOff.assign((size_t)nPairs + 1, 0); p->inOff.assign((size_t)nPairs + 1, 0);
-  for (long long k = 0; k < nPairs; ++k) {
-    const long long L = rowOff[k + 1] - rowOff[k], I = inOff[k + 1] - inOff[k];
-    if (L < 0 || L > 0x3fffffff || I < 0 || I > 0x3fffffff) { set_error("bad pair offsets"); delete p; return nullptr; }
-    if ((double)(std::min(I, L) + 1) * m->S * (nCols + 1) > 2147483647.0) { set_error("pair " + std::to_string(k) + ": an anti-diagonal of the lattice has more than 2^31 cells"); delete p; return nullptr; }
-    p->rowOff[(size_t)k + 1] = p->rowOff[(size_t)k] + L;
-    p->inOff[(size_t)k + 1] = p->inOff[(size_t)k] + I;
-  }
-  p->totalRows = p->rowOff.back(); p->totalIn = p->inOff.back();
-  const long long C = nCols ? nCols + 1 : m->nOut + 1, nv = p->totalRows * C;
-  const double *v0 = logP ? logP + (nPairs ? rowOff[0] * C : 0) : nullptr;
-  const int32_t *x0 = inTok ? inTok + (nPairs ? inOff[0] : 0) : nullptr;
-  if ((nv && !v0) || (p->totalIn && !x0)) { set_error("null argument"); delete p; return nullptr; }
-  for (long long k = 0; k < p->totalIn; ++k)
-    if (x0[k] < 1 || x0[k] > m->nIn) {
-      set_error("input token " + std::to_string(x0[k]) + " at position " + std::to_string(k) + " is outside 1..nInTok (" + std::to_string(m->nIn) + ")");
-      delete p; return nullptr;
-    }
-  if (!profile_values_ok(v0, nv)) { delete p; return nullptr; }
-  if (!hip_ok(hipMalloc((void **)&p->d_logP, (size_t)std::max<long long>(nv, 1) * sizeof(double)), "hipMalloc(pair profiles)") ||
-      !hip_ok(hipMalloc((void **)&p->d_in, (size_t)std::max<long long>(p->totalIn, 1) * sizeof(int)), "hipMalloc(pair inputs)")) { mb_profile_pairs_destroy(p); return nullptr; }
-  if (nv && h2d_large(p->d_logP, v0, (size_t)nv * sizeof(double))) { mb_profile_pairs_destroy(p); return nullptr; }
-  if (p->totalIn && h2d_large(p->d_in, x0, (size_t)p->totalIn * sizeof(int))) { mb_profile_pairs_destroy(p); return nullptr; }
-  if (nCols && (!hip_ok(hipMalloc((void **)&p->d_colTok, (size_t)nCols * sizeof(int)), "hipMalloc(column map)") ||
-                !hip_ok(hipMemcpyAsync(p->d_colTok, colTok, (size_t)nCols * sizeof(int), hipMemcpyHostToDevice, g_stream), "H2D column map"))) { mb_profile_pairs_destroy(p); return nullptr; }
-  if (!hip_ok(hipStreamSynchronize(g_stream), "H2D pairs")) { mb_profile_pairs_destroy(p); return nullptr; }
-  return p;
-}
-
-mb_profile_pairs *mb_profile_pairs_create(mb_machine *m, int64_t nPairs, const int32_t *inTok, const int64_t *inOff, const double *logP, const int64_t *rowOff) {
-  ApiGuard guard;
-  return profile_pairs_create(m, nPairs, inTok, inOff, logP, rowOff, 0, nullptr);
-}
-
-mb_profile_pairs *mb_profile_pairs_create_merged(mb_machine *m, int64_t nPairs, const int32_t *inTok, const int64_t *inOff, const double *logP,
-                                                 const int64_t *rowOff, int32_t nCols, const int32_t *colTok) {
-  ApiGuard guard;
-  if (!merge_map_ok(m, nCols, colTok)) return nullptr;
-  return profile_pairs_create(m, nPairs, inTok, inOff, logP, rowOff, nCols, colTok);
-}
-
-void mb_profile_pairs_destroy(mb_profile_pairs *p) {
-  ApiGuard guard;
-  if (!p) return;
-  if (p->d_logP) (void)hipFree(p->d_logP);
-  if (p->d_in) (void)hipFree(p->d_in);
-  if (p->d_colTok) (void)hipFree(p->d_colTok);
-  pp_env_free(p);
-  delete p;
-}
-
-int mb_profile_pairs_set_envelopes(mb_profile_pairs *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
-  ApiGuard guard;
-  if (!p) { set_error("null argument"); return 1; }
-  return profile_pairs_set_envelopes(p, envOff, inStart, inEnd);
-}
-
-int64_t mb_profile_pairs_cells(const mb_profile_pairs *p) {
-  if (!p) return 0;
-  long long c = 0;
-  for (long long k = 0; k < p->n; ++k) c += pp_cells(p, k);
-  return c;
-}
-
-int mb_profile_pairs_forward(mb_profile_pairs *p, int flags, double *loglike) {
-  ApiGuard guard;
-  if (!p || (!loglike && p->n)) { set_error("null argument"); return 1; }
-  if (flags != MB_ROLLING && flags != MB_MATERIALISE) { set_error("unknown flags"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  return pair_profile_scores(p, MB_FORWARD, flags == MB_MATERIALISE, loglike);
-}
-
-int64_t mb_profile_pair_path_bound(const mb_machine *m, int64_t nIn, int64_t nRows) {
-  if (!m || nIn < 0 || nRows < 0) return 0;
-  return profile_pair_path_bound(m->nLevF, nIn, nRows);
-}
-
-int mb_profile_pairs_viterbi(mb_profile_pairs *p, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow, int64_t pathCap) {
-  ApiGuard guard;
-  if (!p || (!loglike && p->n)) { set_error("null argument"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  if (!pathEdges || !pathOff) return pair_profile_scores(p, MB_VITERBI, false, loglike);
-  const mb_machine *m = p->m;
-  long long need = 0;
-  for (long long k = 0; k < p->n; ++k) need += profile_pair_path_bound(m->nLevF, pp_in(p, k), pp_rows(p, k));
-  if (pathCap < need) { set_error("pathCap too small for the Viterbi paths: " + std::to_string((long long)pathCap) + " entries, the path bounds of the pairs sum to " + std::to_string(need)); return 1; }
-  std::vector<Chunk> chunks;
-  auto bytes = [&](long long k) { return pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false) + 8.0 * profile_pair_path_bound(m->nLevF, pp_in(p, k), pp_rows(p, k)); };
-  if (!pair_profile_chunks(p, bytes, chunks)) return 1;
-  double *d_ll = nullptr;
-  long long *d_len = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
-  if (!hip_ok(sm_alloc((void **)&d_len, std::max<long long>(p->n, 1) * sizeof(long long)), "hipMalloc(path lengths)")) { sm_free(d_ll); return 1; }
-  int rc = 0;
-  Timer tm;
-  long long written = 0;
-  pathOff[0] = 0;
-  std::vector<long long> len;
-  std::vector<uint32_t> he;
-  std::vector<int32_t> hr;
-  PairWhere where;
-  for (const Chunk &c : chunks) {
-    PairProfPlan pl;
-    if ((rc = pair_profile_descs(p, c.p0, c.p1, false, pl))) break;
-    where.add(c.p0, pl);
-    const long long np = c.p1 - c.p0, paths = pl.paths;
-    double *pool = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
-    uint32_t *d_e = (uint32_t *)ws_get(3, (size_t)std::max<long long>(paths, 1) * sizeof(uint32_t));
-    int32_t *d_r = (int32_t *)ws_get(4, (size_t)std::max<long long>(paths, 1) * sizeof(int32_t));
-    double *scratch = pl.ring ? (double *)ws_get(1, (size_t)pl.ring * sizeof(double)) : nullptr;
-    if (!pool || !d_e || !d_r || (pl.ring && !scratch)) rc = 1;
-    if (!rc) {
-      tm.start();
-      rc = pp_launch_fwd(p, MB_VITERBI, true, pl, np, pool, scratch, d_ll + c.p0);
-      if (!rc) rc = pp_launch_traceback(p, pl, np, pool, d_e, d_r, d_len + c.p0);
-      g_last_ms += tm.stop();
-      g_last_launches += pp_chunk_launches(pl);
-    }
-    len.resize((size_t)np); he.resize((size_t)std::max<long long>(paths, 1)); hr.resize(he.size());
-    if (!rc && !hip_ok(hipMemcpy(len.data(), d_len + c.p0, np * sizeof(long long), hipMemcpyDeviceToHost), "D2H path lengths")) rc = 1;
-    if (!rc && paths && (d2h_large(he.data(), d_e, paths * sizeof(uint32_t)) || (pathRow && d2h_large(hr.data(), d_r, paths * sizeof(int32_t))))) rc = 1;
-    long long base = 0;
-    for (long long k = 0; k < np && !rc; ++k) {
-      long long n = len[(size_t)pl.slot[(size_t)k]];
-      if (n == -1) n = 0;   // no finite path: an empty one, as mb_profiles_viterbi
-      else if (n < 0) { set_error(n == -2 ? "pair traceback overflowed its bound" : "pair traceback found no matching candidate"); rc = 1; break; }
-      std::memcpy(pathEdges + written, he.data() + base, (size_t)n * sizeof(uint32_t));
-      if (pathRow) std::memcpy(pathRow + written, hr.data() + base, (size_t)n * sizeof(int32_t));
-      written += n;
-      pathOff[c.p0 + k + 1] = written;
-      base += profile_pair_path_bound(m->nLevF, pp_in(p, c.p0 + k), pp_rows(p, c.p0 + k));
-    }
-    if (rc) quiesce_streams();
-    pp_plan_free(pl);
-    if (rc) break;
-  }
-  if (!rc && pp_fetch(loglike, d_ll, p->n, where, "D2H loglike")) rc = 1;
-  sm_free(d_ll); sm_free(d_len);
-  g_last_kernel = pp_fwd_name(p, MB_VITERBI, true);
-  return rc;
-}
-
-int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglikeSum, double *loglike) {
-  ApiGuard guard;
-  if (!p || !counts) { set_error("null argument"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
-  const mb_machine *m = p->m;
-  const long long nT = m->nTrans;
-  std::vector<Chunk> chunks;
-  if (!pair_profile_chunks(p, [&](long long k) { return 2.0 * pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false); }, chunks)) return 1;   // the Forward and the Backward lattice
-  double *d_ll = nullptr, *d_bll = nullptr, *d_cc = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
-  if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
-      !hip_ok(sm_alloc((void **)&d_cc, std::max<long long>(nT, 1) * sizeof(double)), "hipMalloc(counts)")) { sm_free(d_ll); sm_free(d_bll); sm_free(d_cc); return 1; }
-  int rc = 0;
-  Timer tm;
-  std::vector<double> total((size_t)nT, 0.0), hc((size_t)nT);
-  PairWhere where;
-  for (const Chunk &c : chunks) {
-    PairProfPlan pl;
-    if ((rc = pair_profile_descs(p, c.p0, c.p1, false, pl))) break;
-    where.add(c.p0, pl);
-    const long long np = c.p1 - c.p0;
-    double *fwd = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
-    double *bwd = (double *)ws_get(1, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
-    double *scratch = pl.ring ? (double *)ws_get(2, (size_t)pl.ring * sizeof(double)) : nullptr;
-    if (!fwd || !bwd || (pl.ring && !scratch)) rc = 1;
-    long long maxCells = 0;
-    for (long long k = c.p0; k < c.p1; ++k) maxCells = std::max(maxCells, pp_cells(p, k) / 2);
-    const int groups = (int)std::min<long long>(256, std::max<long long>(1, (maxCells + 2047) / 2048));
-    if (!rc && np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); rc = 1; }
-    if (!rc) {
-      tm.start();
-      rc = pp_launch_fwd(p, MB_FORWARD, true, pl, np, fwd, scratch, d_ll + c.p0);      // (merged: the Backward's ring follows the Forward's on the stream, one scratch buffer serves both)
-      if (!rc) rc = pp_launch_bwd(p, pl, np, bwd, scratch, d_bll + c.p0);
-      if (!rc && nT) rc = hip_ok(hipMemsetAsync(d_cc, 0, (size_t)nT * sizeof(double), g_stream), "memset(counts)") ? 0 : 1;
-      if (!rc) rc = pp_launch_counts(p, pl, np, groups, fwd, bwd, d_cc);
-      g_last_ms += tm.stop();
-      g_last_launches += pp_chunk_launches(pl);
-    }
-    if (!rc && nT && !hip_ok(hipMemcpy(hc.data(), d_cc, nT * sizeof(double), hipMemcpyDeviceToHost), "D2H counts")) rc = 1;
-    if (!rc && g_deterministic)
-      for (long long e = 0; e < nT && !rc; ++e) {      // fixed point, 2^-36
-        unsigned long long u; std::memcpy(&u, &hc[(size_t)e], 8);
-        if (!det_to_double(u, hc[(size_t)e])) { set_error("MB_DETERMINISTIC: a posterior count left the fixed-point range (6.7e7 per transition and call): split the batch or use the floating-point mode"); rc = 1; }
-      }
-    if (!rc) for (long long e = 0; e < nT; ++e) total[(size_t)e] += hc[(size_t)e];
-    if (rc) quiesce_streams();
-    pp_plan_free(pl);
-    if (rc) break;
-  }
-  std::vector<double> hll((size_t)p->n);
-  if (!rc && pp_fetch(hll.data(), d_ll, p->n, where, "D2H loglike")) rc = 1;
-  sm_free(d_ll); sm_free(d_bll); sm_free(d_cc);
-  g_last_kernel = p->nCols ? "k_profile_pair_merge_counts" : (p->hasEnv ? "k_profile_pair_env_counts" : "k_profile_pair_counts");
-  if (rc) return rc;
-  for (long long e = 0; e < nT; ++e) counts[e] += total[(size_t)e];
-  double s = 0.0;
-  for (long long k = 0; k < p->n; ++k) { s += hll[(size_t)k]; if (loglike) loglike[k] = hll[(size_t)k]; }
-  if (loglikeSum) *loglikeSum += s;
-  return 0;
-}
-
-// the LDS table of k_profile_pair_rowpost in doubles; MB_ROWPOST_TABLE makes it smaller (the rows-per-block and wide-row paths at small shapes)
-static int pp_rowpost_table() { return std::max(1, std::min(env_int("MB_ROWPOST_TABLE", ROWPOST_LDS_MAX), ROWPOST_LDS_MAX)); }
-static int pp_launch_rowpost(const mb_profile_pairs *p, const PairProfPlan &pl, int groups, int tabMax, const double *fwd, const double *bwd, double *post) {
-  if (launch_profile_pair_rowpost(p->m, pl.d, (int)pl.nPlain, groups, tabMax, p->d_in, p->d_logP, fwd, bwd, post, g_stream)) return 1;
-  return launch_profile_pair_rowpost(p->m, pl.e, pp_env_tables(p), (int)pl.nEnv, groups, tabMax, p->d_in, p->d_logP, fwd, bwd, post, g_stream);
-}
-
-int mb_profile_pairs_row_posteriors(mb_profile_pairs *p, double *post, double *loglike) {
-  ApiGuard guard;
-  if (!p || (!post && p->totalRows)) { set_error("null argument"); return 1; }
-  if (p->nCols) { set_error("row posteriors take plain profiles"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
-  const mb_machine *m = p->m;
-  const long long C = m->nOut + 1, nv = p->totalRows * C;
-  const int tabMax = pp_rowpost_table();
-  std::vector<Chunk> chunks;
-  auto bytes = [&](long long k) { return 2.0 * pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false) + 8.0 * (double)(pp_rows(p, k) * C); };   // both lattices and the pair's bins
-  if (!pair_profile_chunks(p, bytes, chunks)) return 1;
-  double *d_ll = nullptr, *d_bll = nullptr, *d_post = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
-  if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
-      !hip_ok(sm_alloc((void **)&d_post, std::max<long long>(nv, 1) * sizeof(double)), "hipMalloc(row posteriors)")) { sm_free(d_ll); sm_free(d_bll); sm_free(d_post); return 1; }
-  int rc = 0;
-  Timer tm;
-  PairWhere where;
-  for (const Chunk &c : chunks) {
-    PairProfPlan pl;
-    if ((rc = pair_profile_descs(p, c.p0, c.p1, false, pl))) break;
-    where.add(c.p0, pl);
-    const long long np = c.p1 - c.p0;
-    double *fwd = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
-    double *bwd = (double *)ws_get(1, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
-    if (!fwd || !bwd) rc = 1;
-    long long groups = 1;      // the row blocks of the pair that has most (a group past a pair's last block has nothing to do)
-    for (long long k = c.p0; k < c.p1; ++k) {
-      const long long L = pp_rows(p, k), R = profile_pair_rowpost_rows(pp_cells(p, k) / (2 * (long long)m->S), m->S, (int)L, (int)C, tabMax);
-      groups = std::max(groups, (L + R - 1) / R);
-    }
-    groups = std::min<long long>(groups, 1024);
-    if (!rc && np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); rc = 1; }
-    if (!rc) {
-      tm.start();
-      rc = pp_launch_fwd(p, MB_FORWARD, true, pl, np, fwd, nullptr, d_ll + c.p0);
-      if (!rc) rc = pp_launch_bwd(p, pl, np, bwd, nullptr, d_bll + c.p0);
-      if (!rc) rc = pp_launch_rowpost(p, pl, (int)groups, tabMax, fwd, bwd, d_post);
-      g_last_ms += tm.stop();
-      g_last_launches += pp_chunk_launches(pl);
-    }
-    if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "row posteriors")) rc = 1;      // (the next chunk takes the lattices over)
-    if (rc) quiesce_streams();
-    pp_plan_free(pl);
-    if (rc) break;
-  }
-  if (!rc && nv && d2h_large(post, d_post, (size_t)nv * sizeof(double))) rc = 1;
-  if (!rc && g_deterministic)
-    for (long long e = 0; e < nv && !rc; ++e) {      // fixed point, 2^-36 (a posterior is at most 1: far inside the range)
-      unsigned long long u; std::memcpy(&u, &post[e], 8);
-      if (!det_to_double(u, post[e])) { set_error("MB_DETERMINISTIC: a row posterior left the fixed-point range"); rc = 1; }
-    }
-  std::vector<double> hll((size_t)p->n);
-  if (!rc && pp_fetch(hll.data(), d_ll, p->n, where, "D2H loglike")) rc = 1;
-  sm_free(d_ll); sm_free(d_bll); sm_free(d_post);
-  g_last_kernel = p->hasEnv ? "k_profile_pair_env_rowpost" : "k_profile_pair_rowpost";
-  if (rc) return rc;
-  if (loglike) for (long long k = 0; k < p->n; ++k) loglike[k] = hll[(size_t)k];
-  return 0;
-}
-
-int mb_profile_pairs_set_rows(mb_profile_pairs *p, const double *logP) {
-  ApiGuard guard;
-  if (!p) { set_error("null argument"); return 1; }
-  if (p->nCols) { set_error("row posteriors take plain profiles"); return 1; }
-  const long long nv = p->totalRows * (p->m->nOut + 1);
-  if (nv && !logP) { set_error("null argument"); return 1; }
-  if (!profile_values_ok(logP, nv)) return 1;
-  if (nv && h2d_large(p->d_logP, logP, (size_t)nv * sizeof(double))) return 1;
-  return hip_ok(hipStreamSynchronize(g_stream), "H2D pair profiles") ? 0 : 1;
-}
-
-static int profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, int32_t nCols,
-                             const int32_t *colTok, const int32_t *envStart, const int32_t *envEnd, double *cellsOut) {
-  if (!m || !cellsOut || nRows < 0 || nIn < 0 || (nRows && !logP) || (nIn && !inTok)) { set_error("null argument"); return 1; }
-  if (mode != MB_FORWARD && mode != MB_VITERBI && mode != MB_BACKWARD) { set_error("unknown fill mode"); return 1; }
-  if (ensure_init()) return 1;
-  g_last_ms = 0.0; g_last_launches = 0;
-  const int64_t rOff[2] = {0, nRows}, iOff[2] = {0, nIn};
-  mb_profile_pairs *p = profile_pairs_create(m, 1, inTok, iOff, logP, rOff, nCols, colTok);
-  if (!p) return 1;
-  const bool env = envStart && envEnd;
-  if (env) {
-    const int64_t eOff[2] = {0, nRows + 1};
-    if (profile_pairs_set_envelopes(p, eOff, envStart, envEnd)) { mb_profile_pairs_destroy(p); return 1; }
-  }
-  std::vector<Chunk> chunks;
-  if (!pair_profile_chunks(p, [&](long long k) { return pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false); }, chunks)) { mb_profile_pairs_destroy(p); return 1; }
-  PairProfPlan pl;
-  int rc = pair_profile_descs(p, 0, 1, false, pl);
-  double *d_ll = nullptr;
-  if (!rc && !hip_ok(sm_alloc((void **)&d_ll, sizeof(double)), "hipMalloc(loglike)")) rc = 1;
-  double *pool = rc ? nullptr : (double *)ws_get(0, (size_t)pl.cells * sizeof(double));
-  if (!rc && !pool) rc = 1;
-  double *scratch = !rc && pl.ring ? (double *)ws_get(1, (size_t)pl.ring * sizeof(double)) : nullptr;
-  if (!rc && pl.ring && !scratch) rc = 1;
-  if (!rc) {
-    Timer tm;
-    tm.start();
-    rc = mode == MB_BACKWARD ? pp_launch_bwd(p, pl, 1, pool, scratch, d_ll) : pp_launch_fwd(p, mode, true, pl, 1, pool, scratch, d_ll);
-    g_last_ms += tm.stop();
-    g_last_launches = 1;
-  }
-  if (!rc && !env) rc = d2h_large(cellsOut, pool, (size_t)pl.cells * sizeof(double));
-  if (!rc && env) {      // the compact lattice into the full rectangle, -inf outside the envelope
-    std::vector<double> compact((size_t)pl.cells);
-    rc = d2h_large(compact.data(), pool, compact.size() * sizeof(double));
-    const size_t cellD = 2 * (size_t)m->S;
-    if (!rc) std::fill(cellsOut, cellsOut + (size_t)(nIn + 1) * (size_t)(nRows + 1) * cellD, -INFINITY);
-    size_t at = 0;
-    for (int64_t r = 0; !rc && r <= nRows; ++r)
-      for (int64_t i = envStart[r]; i < envEnd[r]; ++i, at += cellD)
-        std::memcpy(cellsOut + ((size_t)i * (size_t)(nRows + 1) + (size_t)r) * cellD, compact.data() + at, cellD * sizeof(double));
-  }
-  if (rc) quiesce_streams();
-  pp_plan_free(pl); sm_free(d_ll);
-  g_last_kernel = mode == MB_BACKWARD ? (nCols ? "k_profile_pair_merge_bwd" : (env ? "k_profile_pair_env_bwd" : "k_profile_pair_bwd")) : pp_fwd_name(p, mode, true);
-  mb_profile_pairs_destroy(p);
-  return rc;
-}
-
-int mb_profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, double *cellsOut) {
-  ApiGuard guard;
-  return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, 0, nullptr, nullptr, nullptr, cellsOut);
-}
-
-int mb_profile_pair_fill_env(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows,
-                             const int32_t *envStart, const int32_t *envEnd, double *cellsOut) {
-  ApiGuard guard;
-  if ((envStart == nullptr) != (envEnd == nullptr)) { set_error("null argument"); return 1; }
-  return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, 0, nullptr, envStart, envEnd, cellsOut);
-}
-
-int mb_profile_pair_fill_merged(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, int32_t nCols,
-                                const int32_t *colTok, double *cellsOut) {
-  ApiGuard guard;
-  if (!merge_map_ok(m, nCols, colTok)) return 1;
-  return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, nCols, colTok, nullptr, nullptr, cellsOut);
-}
-
-// ---- two-profile sweeps: an input profile against an output profile (mb_profile_two.hip, docs/profile_tapes.md "Pairs of profiles") --
-static long long pt_in(const mb_profile_twos *p, long long k) { return p->inOff[k + 1] - p->inOff[k]; }
-static long long pt_rows(const mb_profile_twos *p, long long k) { return p->rowOff[k + 1] - p->rowOff[k]; }
-static double pt_cell_bytes(const mb_profile_twos *p, long long k) { return 8.0 * (double)profile_two_cells(p->m->S, pt_in(p, k), pt_rows(p, k)); }
-// bytes of global scratch the rolling sweep of pair k needs (0: its ring is in LDS)
-static double pt_ring_bytes(const mb_profile_twos *p, long long k) {
-  return profile_two_lds_bytes(p->m->S, pt_in(p, k), pt_rows(p, k)) ? 0.0 : 8.0 * (double)profile_two_ring(p->m->S, pt_in(p, k), pt_rows(p, k));
-}
-static long long pt_path_bound(const mb_profile_twos *p, long long k) { return profile_pair_path_bound(p->m->nLevF, pt_in(p, k), pt_rows(p, k)); }
-
-struct TwoProfPlan {
-  PairProfDesc *d = nullptr;
-  long long cells = 0, paths = 0, ring = 0, maxItems = 0;
-  size_t lds = 0;
-};
-static void pt_plan_free(TwoProfPlan &pl) { sm_free(pl.d); pl.d = nullptr; }
-
-// descriptors of pairs [p0, p1): lattices, traceback slots and (rolling) scratch rings packed from 0
-static int two_profile_descs(const mb_profile_twos *p, long long p0, long long p1, bool rolling, TwoProfPlan &pl) {
-  std::vector<PairProfDesc> h;
-  const int S = p->m->S;
-  for (long long k = p0; k < p1; ++k) {
-    const long long K = pt_in(p, k), L = pt_rows(p, k);
-    PairProfDesc d;
-    d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)K; d.nRows = (int)L;
-    d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = -1;
-    if (rolling) {
-      const size_t lds = profile_two_lds_bytes(S, K, L);
-      if (lds) pl.lds = std::max(pl.lds, lds);
-      else { d.ringBase = pl.ring; pl.ring += profile_two_ring(S, K, L); }
-    }
-    pl.maxItems = std::max(pl.maxItems, (std::min(K, L) + 1) * S);
-    pl.cells += profile_two_cells(S, K, L);
-    pl.paths += pt_path_bound(p, k);
-    h.push_back(d);
-  }
-  MB_HIP(sm_alloc((void **)&pl.d, std::max<size_t>(h.size(), 1) * sizeof(PairProfDesc)));
-  if ((!h.empty() && !hip_ok(hipMemcpyAsync(pl.d, h.data(), h.size() * sizeof(PairProfDesc), hipMemcpyHostToDevice, g_stream), "H2D pair descriptors")) ||
-      !hip_ok(hipStreamSynchronize(g_stream), "H2D pair descriptors")) { pt_plan_free(pl); return 1; }
-  return 0;
-}
-
-static const char *pt_fwd_name(int mode, bool mat) {
-  static const char *const names[2][2] = {{"k_profile_two_fwd<sum,rolling>", "k_profile_two_fwd<sum,mat>"}, {"k_profile_two_fwd<max,rolling>", "k_profile_two_fwd<max,mat>"}};
-  return names[mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
-}
-
-// Forward (MB_FORWARD) or Viterbi scores without paths (MB_VITERBI); mat: through the materialised lattice
-static int two_profile_scores(mb_profile_twos *p, int mode, bool mat, double *loglike) {
-  std::vector<Chunk> chunks;
-  if (!lattice_chunks(p->n, [&](long long k) { return mat ? pt_cell_bytes(p, k) : pt_ring_bytes(p, k); }, chunks)) return 1;
-  double *d_ll = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
-  int rc = 0;
-  Timer tm;
-  for (const Chunk &c : chunks) {
-    TwoProfPlan pl;
-    if ((rc = two_profile_descs(p, c.p0, c.p1, !mat, pl))) break;
-    double *pool = nullptr, *scratch = nullptr;
-    if (mat) { pool = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double)); if (!pool) rc = 1; }
-    if (!rc && pl.ring) { scratch = (double *)ws_get(1, (size_t)pl.ring * sizeof(double)); if (!scratch) rc = 1; }
-    if (!rc) {
-      tm.start();
-      rc = launch_profile_two_fwd(p->m, mode, mat, pl.d, (int)(c.p1 - c.p0), pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, scratch, d_ll + c.p0, g_stream);
-      g_last_ms += tm.stop();
-      g_last_launches += 1;
-    }
-    if (rc) quiesce_streams();
-    pt_plan_free(pl);
-    if (rc) break;
-  }
-  if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
-  sm_free(d_ll);
-  g_last_kernel = pt_fwd_name(mode, mat);
-  return rc;
-}
-
-mb_profile_twos *mb_profile_twos_create(mb_machine *m, int64_t nPairs, const double *logA, const int64_t *inOff, const double *logB, const int64_t *rowOff) {
-  ApiGuard guard;
-  if (!m || nPairs < 0 || (nPairs > 0 && (!rowOff || !inOff))) { set_error("null argument"); return nullptr; }
-  if (!m->nIn) { set_error("two-profile sweeps need a machine with an input alphabet"); return nullptr; }
-  if (ensure_init()) return nullptr;
-  mb_profile_twos *p = new mb_profile_twos();
-  p->m = m; p->n = nPairs;
-  p->rowOff.assign((size_t)nPairs + 1, 0); p->inOff.assign((size_t)nPairs + 1, 0);
-  for (long long k = 0; k < nPairs; ++k) {
-    const long long L = rowOff[k + 1] - rowOff[k], K = inOff[k + 1] - inOff[k];
-    if (L < 0 || L > 0x3fffffff || K < 0 || K > 0x3fffffff) { set_error("bad pair offsets"); delete p; return nullptr; }
-    if ((double)(std::min(K, L) + 1) * m->S > 2147483647.0) { set_error("pair " + std::to_string(k) + ": an anti-diagonal of the lattice has more than 2^31 cells"); delete p; return nullptr; }
-    p->rowOff[(size_t)k + 1] = p->rowOff[(size_t)k] + L;
-    p->inOff[(size_t)k + 1] = p->inOff[(size_t)k] + K;
-  }
-  p->totalRows = p->rowOff.back(); p->totalIn = p->inOff.back();
-  const long long C = m->nOut + 1, CA = m->nIn + 1, nb = p->totalRows * C, na = p->totalIn * CA;
-  const double *b0 = logB ? logB + (nPairs ? rowOff[0] * C : 0) : nullptr;
-  const double *a0 = logA ? logA + (nPairs ? inOff[0] * CA : 0) : nullptr;
-  if ((nb && !b0) || (na && !a0)) { set_error("null argument"); delete p; return nullptr; }
-  if (!profile_values_ok(a0, na) || !profile_values_ok(b0, nb)) { delete p; return nullptr; }
-  if (!hip_ok(hipMalloc((void **)&p->d_logB, (size_t)std::max<long long>(nb, 1) * sizeof(double)), "hipMalloc(output profiles)") ||
-      !hip_ok(hipMalloc((void **)&p->d_logA, (size_t)std::max<long long>(na, 1) * sizeof(double)), "hipMalloc(input profiles)")) { mb_profile_twos_destroy(p); return nullptr; }
-  if ((nb && h2d_large(p->d_logB, b0, (size_t)nb * sizeof(double))) || (na && h2d_large(p->d_logA, a0, (size_t)na * sizeof(double))) ||
-      !hip_ok(hipStreamSynchronize(g_stream), "H2D profiles")) { mb_profile_twos_destroy(p); return nullptr; }
-  return p;
-}
-
-void mb_profile_twos_destroy(mb_profile_twos *p) {
-  ApiGuard guard;
-  if (!p) return;
-  if (p->d_logA) (void)hipFree(p->d_logA);
-  if (p->d_logB) (void)hipFree(p->d_logB);
-  delete p;
-}
-
-int mb_profile_twos_forward(mb_profile_twos *p, int flags, double *loglike) {
-  ApiGuard guard;
-  if (!p || (!loglike && p->n)) { set_error("null argument"); return 1; }
-  if (flags != MB_ROLLING && flags != MB_MATERIALISE) { set_error("unknown flags"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  return two_profile_scores(p, MB_FORWARD, flags == MB_MATERIALISE, loglike);
-}
-
-int mb_profile_twos_viterbi(mb_profile_twos *p, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow, int32_t *pathInRow, int64_t pathCap) {
-  ApiGuard guard;
-  if (!p || (!loglike && p->n)) { set_error("null argument"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  if (!pathEdges || !pathOff) return two_profile_scores(p, MB_VITERBI, false, loglike);
-  long long need = 0;
-  for (long long k = 0; k < p->n; ++k) need += pt_path_bound(p, k);
-  if (pathCap < need) { set_error("pathCap too small for the Viterbi paths: " + std::to_string((long long)pathCap) + " entries, the path bounds of the pairs sum to " + std::to_string(need)); return 1; }
-  std::vector<Chunk> chunks;
-  if (!lattice_chunks(p->n, [&](long long k) { return pt_cell_bytes(p, k) + 12.0 * pt_path_bound(p, k); }, chunks)) return 1;
-  double *d_ll = nullptr;
-  long long *d_len = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
-  if (!hip_ok(sm_alloc((void **)&d_len, std::max<long long>(p->n, 1) * sizeof(long long)), "hipMalloc(path lengths)")) { sm_free(d_ll); return 1; }
-  int rc = 0;
-  Timer tm;
-  long long written = 0;
-  pathOff[0] = 0;
-  std::vector<long long> len;
-  std::vector<uint32_t> he;
-  std::vector<int32_t> hr, hi;
-  for (const Chunk &c : chunks) {
-    TwoProfPlan pl;
-    if ((rc = two_profile_descs(p, c.p0, c.p1, false, pl))) break;
-    const long long np = c.p1 - c.p0, paths = pl.paths;
-    double *pool = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
-    uint32_t *d_e = (uint32_t *)ws_get(3, (size_t)std::max<long long>(paths, 1) * sizeof(uint32_t));
-    int32_t *d_r = (int32_t *)ws_get(4, (size_t)std::max<long long>(paths, 1) * sizeof(int32_t));
-    int32_t *d_i = (int32_t *)ws_get(5, (size_t)std::max<long long>(paths, 1) * sizeof(int32_t));
-    if (!pool || !d_e || !d_r || !d_i) rc = 1;
-    if (!rc) {
-      tm.start();
-      rc = launch_profile_two_fwd(p->m, MB_VITERBI, true, pl.d, (int)np, 0, pl.maxItems, p->d_logA, p->d_logB, pool, nullptr, d_ll + c.p0, g_stream);
-      if (!rc) rc = launch_profile_two_traceback(p->m, pl.d, (int)np, p->d_logA, p->d_logB, pool, d_e, d_r, d_i, d_len + c.p0, g_stream);
-      g_last_ms += tm.stop();
-      g_last_launches += 1;
-    }
-    len.resize((size_t)np); he.resize((size_t)std::max<long long>(paths, 1)); hr.resize(he.size()); hi.resize(he.size());
-    if (!rc && !hip_ok(hipMemcpy(len.data(), d_len + c.p0, np * sizeof(long long), hipMemcpyDeviceToHost), "D2H path lengths")) rc = 1;
-    if (!rc && paths && (d2h_large(he.data(), d_e, paths * sizeof(uint32_t)) || (pathRow && d2h_large(hr.data(), d_r, paths * sizeof(int32_t))) ||
-                         (pathInRow && d2h_large(hi.data(), d_i, paths * sizeof(int32_t))))) rc = 1;
-    long long base = 0;
-    for (long long k = 0; k < np && !rc; ++k) {
-      long long n = len[(size_t)k];
-      if (n == -1) n = 0;   // no finite path: an empty one, as mb_profile_pairs_viterbi
-      else if (n < 0) { set_error(n == -2 ? "pair traceback overflowed its bound" : "pair traceback found no matching candidate"); rc = 1; break; }
-      std::memcpy(pathEdges + written, he.data() + base, (size_t)n * sizeof(uint32_t));
-      if (pathRow) std::memcpy(pathRow + written, hr.data() + base, (size_t)n * sizeof(int32_t));
-      if (pathInRow) std::memcpy(pathInRow + written, hi.data() + base, (size_t)n * sizeof(int32_t));
-      written += n;
-      pathOff[c.p0 + k + 1] = written;
-      base += pt_path_bound(p, c.p0 + k);
-    }
-    if (rc) quiesce_streams();
-    pt_plan_free(pl);
-    if (rc) break;
-  }
-  if (!rc && p->n && !hip_ok(hipMemcpy(loglike, d_ll, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
-  sm_free(d_ll); sm_free(d_len);
-  g_last_kernel = pt_fwd_name(MB_VITERBI, true);
-  return rc;
-}
-
-int mb_profile_twos_counts(mb_profile_twos *p, double *counts, double *loglikeSum, double *loglike) {
-  ApiGuard guard;
-  if (!p || !counts) { set_error("null argument"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
-  const mb_machine *m = p->m;
-  const long long nT = m->nTrans;
-  std::vector<Chunk> chunks;
-  if (!lattice_chunks(p->n, [&](long long k) { return 2.0 * pt_cell_bytes(p, k); }, chunks)) return 1;   // the Forward and the Backward lattice
-  double *d_ll = nullptr, *d_bll = nullptr, *d_cc = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
-  if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
-      !hip_ok(sm_alloc((void **)&d_cc, std::max<long long>(nT, 1) * sizeof(double)), "hipMalloc(counts)")) { sm_free(d_ll); sm_free(d_bll); sm_free(d_cc); return 1; }
-  int rc = 0;
-  Timer tm;
-  std::vector<double> total((size_t)nT, 0.0), hc((size_t)nT);
-  for (const Chunk &c : chunks) {
-    TwoProfPlan pl;
-    if ((rc = two_profile_descs(p, c.p0, c.p1, false, pl))) break;
-    const long long np = c.p1 - c.p0;
-    double *fwd = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
-    double *bwd = (double *)ws_get(1, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
-    if (!fwd || !bwd) rc = 1;
-    long long maxCells = 0;
-    for (long long k = c.p0; k < c.p1; ++k) maxCells = std::max(maxCells, profile_two_cells(m->S, pt_in(p, k), pt_rows(p, k)) / 3);
-    const int groups = (int)std::min<long long>(256, std::max<long long>(1, (maxCells + 2047) / 2048));
-    if (!rc && np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); rc = 1; }
-    if (!rc) {
-      tm.start();
-      rc = launch_profile_two_fwd(m, MB_FORWARD, true, pl.d, (int)np, 0, pl.maxItems, p->d_logA, p->d_logB, fwd, nullptr, d_ll + c.p0, g_stream);
-      if (!rc) rc = launch_profile_two_bwd(m, pl.d, (int)np, pl.maxItems, p->d_logA, p->d_logB, bwd, d_bll + c.p0, g_stream);
-      if (!rc && nT) rc = hip_ok(hipMemsetAsync(d_cc, 0, (size_t)nT * sizeof(double), g_stream), "memset(counts)") ? 0 : 1;
-      if (!rc) rc = launch_profile_two_counts(m, pl.d, (int)np, groups, p->d_logA, p->d_logB, fwd, bwd, d_cc, g_stream);
-      g_last_ms += tm.stop();
-      g_last_launches += 1;
-    }
-    if (!rc && nT && !hip_ok(hipMemcpy(hc.data(), d_cc, nT * sizeof(double), hipMemcpyDeviceToHost), "D2H counts")) rc = 1;
-    if (!rc && g_deterministic)
-      for (long long e = 0; e < nT && !rc; ++e) {      // fixed point, 2^-36
-        unsigned long long u; std::memcpy(&u, &hc[(size_t)e], 8);
-        if (!det_to_double(u, hc[(size_t)e])) { set_error("MB_DETERMINISTIC: a posterior count left the fixed-point range (6.7e7 per transition and call): split the batch or use the floating-point mode"); rc = 1; }
-      }
-    if (!rc) for (long long e = 0; e < nT; ++e) total[(size_t)e] += hc[(size_t)e];
-    if (rc) quiesce_streams();
-    pt_plan_free(pl);
-    if (rc) break;
-  }
-  std::vector<double> hll((size_t)p->n);
-  if (!rc && p->n && !hip_ok(hipMemcpy(hll.data(), d_ll, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
-  sm_free(d_ll); sm_free(d_bll); sm_free(d_cc);
-  g_last_kernel = "k_profile_two_counts";
-  if (rc) return rc;
-  for (long long e = 0; e < nT; ++e) counts[e] += total[(size_t)e];
-  double s = 0.0;
-  for (long long k = 0; k < p->n; ++k) { s += hll[(size_t)k]; if (loglike) loglike[k] = hll[(size_t)k]; }
-  if (loglikeSum) *loglikeSum += s;
-  return 0;
-}
-
-// the line blocks of k_profile_two_rowpost on one axis of the pair that has most among [p0, p1), 1 024 at the most
-static long long pt_rowpost_groups(const mb_profile_twos *p, long long p0, long long p1, int axis, int tabMax) {
-  const int S = p->m->S;
-  const long long NC = (axis ? p->m->nIn : p->m->nOut) + 1;
-  long long groups = 1;
-  for (long long k = p0; k < p1; ++k) {
-    const long long K = pt_in(p, k), L = pt_rows(p, k), NL = axis ? K : L;
-    const long long R = profile_pair_rowpost_rows((K + 1) * (L + 1), S, (int)NL, (int)NC, tabMax);
-    groups = std::max(groups, (NL + R - 1) / R);
-  }
-  return std::min<long long>(groups, 1024);
-}
-
-int mb_profile_twos_row_posteriors(mb_profile_twos *p, double *postA, double *postB, double *loglike) {
-  ApiGuard guard;
-  if (!p) { set_error("null argument"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
-  const mb_machine *m = p->m;
-  const long long C = m->nOut + 1, CA = m->nIn + 1, nb = postB ? p->totalRows * C : 0, na = postA ? p->totalIn * CA : 0;
-  const int tabMax = pp_rowpost_table();
-  std::vector<Chunk> chunks;
-  auto bytes = [&](long long k) { return 2.0 * pt_cell_bytes(p, k) + 8.0 * (double)(pt_rows(p, k) * C + pt_in(p, k) * CA); };   // both lattices and the pair's bins of both tables
-  if (!lattice_chunks(p->n, bytes, chunks)) return 1;
-  double *d_ll = nullptr, *d_bll = nullptr, *d_pa = nullptr, *d_pb = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, std::max<long long>(p->n, 1) * sizeof(double)));
-  if (!hip_ok(sm_alloc((void **)&d_bll, std::max<long long>(p->n, 1) * sizeof(double)), "hipMalloc(loglike)") ||
-      !hip_ok(sm_alloc((void **)&d_pa, std::max<long long>(na, 1) * sizeof(double)), "hipMalloc(row posteriors)") ||
-      !hip_ok(sm_alloc((void **)&d_pb, std::max<long long>(nb, 1) * sizeof(double)), "hipMalloc(row posteriors)")) { sm_free(d_ll); sm_free(d_bll); sm_free(d_pa); sm_free(d_pb); return 1; }
-  int rc = 0;
-  Timer tm;
-  for (const Chunk &c : chunks) {
-    TwoProfPlan pl;
-    if ((rc = two_profile_descs(p, c.p0, c.p1, false, pl))) break;
-    const long long np = c.p1 - c.p0;
-    double *fwd = (double *)ws_get(0, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
-    double *bwd = (double *)ws_get(1, (size_t)std::max<long long>(pl.cells, 1) * sizeof(double));
-    if (!fwd || !bwd) rc = 1;
-    const long long groupsB = pt_rowpost_groups(p, c.p0, c.p1, 0, tabMax), groupsA = pt_rowpost_groups(p, c.p0, c.p1, 1, tabMax);
-    if (!rc && np * std::max(groupsA, groupsB) > 0x7fffffff) { set_error("too many pairs in one chunk"); rc = 1; }
-    if (!rc) {
-      tm.start();
-      rc = launch_profile_two_fwd(m, MB_FORWARD, true, pl.d, (int)np, 0, pl.maxItems, p->d_logA, p->d_logB, fwd, nullptr, d_ll + c.p0, g_stream);
-      if (!rc) rc = launch_profile_two_bwd(m, pl.d, (int)np, pl.maxItems, p->d_logA, p->d_logB, bwd, d_bll + c.p0, g_stream);
-      if (!rc && postB) rc = launch_profile_two_rowpost(m, 0, pl.d, (int)np, (int)groupsB, tabMax, p->d_logA, p->d_logB, fwd, bwd, d_pb, g_stream);
-      if (!rc && postA) rc = launch_profile_two_rowpost(m, 1, pl.d, (int)np, (int)groupsA, tabMax, p->d_logA, p->d_logB, fwd, bwd, d_pa, g_stream);
-      g_last_ms += tm.stop();
-      g_last_launches += 1;
-    }
-    if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "row posteriors")) rc = 1;      // (the next chunk takes the lattices over)
-    if (rc) quiesce_streams();
-    pt_plan_free(pl);
-    if (rc) break;
-  }
-  if (!rc && na && d2h_large(postA, d_pa, (size_t)na * sizeof(double))) rc = 1;
-  if (!rc && nb && d2h_large(postB, d_pb, (size_t)nb * sizeof(double))) rc = 1;
-  if (!rc && g_deterministic)
-    for (int t = 0; t < 2 && !rc; ++t) {      // fixed point, 2^-36 (a posterior is at most 1: far inside the range)
-      double *post = t ? postB : postA;
-      const long long nv = t ? nb : na;
-      for (long long e = 0; e < nv && !rc; ++e) {
-        unsigned long long u; std::memcpy(&u, &post[e], 8);
-        if (!det_to_double(u, post[e])) { set_error("MB_DETERMINISTIC: a posterior count left the fixed-point range (6.7e7 per transition and call): split the batch or use the floating-point mode"); rc = 1; }
-      }
-    }
-  std::vector<double> hll((size_t)p->n);
-  if (!rc && p->n && !hip_ok(hipMemcpy(hll.data(), d_ll, (size_t)p->n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
-  sm_free(d_ll); sm_free(d_bll); sm_free(d_pa); sm_free(d_pb);
-  g_last_kernel = "k_profile_two_rowpost";
-  if (rc) return rc;
-  if (loglike) for (long long k = 0; k < p->n; ++k) loglike[k] = hll[(size_t)k];
-  return 0;
-}
-
-int mb_profile_twos_set_rows(mb_profile_twos *p, const double *logA, const double *logB) {
-  ApiGuard guard;
-  if (!p) { set_error("null argument"); return 1; }
-  const long long na = logA ? p->totalIn * (p->m->nIn + 1) : 0, nb = logB ? p->totalRows * (p->m->nOut + 1) : 0;
-  if (!profile_values_ok(logA, na) || !profile_values_ok(logB, nb)) return 1;      // (before either copy: a refused table leaves both in effect)
-  if ((na && h2d_large(p->d_logA, logA, (size_t)na * sizeof(double))) || (nb && h2d_large(p->d_logB, logB, (size_t)nb * sizeof(double)))) return 1;
-  return hip_ok(hipStreamSynchronize(g_stream), "H2D profiles") ? 0 : 1;
-}
-
-int mb_profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, double *cellsOut) {
-  ApiGuard guard;
-  if (!m || !cellsOut || nRows < 0 || nIn < 0 || (nRows && !logB) || (nIn && !logA)) { set_error("null argument"); return 1; }
-  if (mode != MB_FORWARD && mode != MB_VITERBI && mode != MB_BACKWARD) { set_error("unknown fill mode"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
-  const int64_t rOff[2] = {0, nRows}, iOff[2] = {0, nIn};
-  mb_profile_twos *p = mb_profile_twos_create(m, 1, logA, iOff, logB, rOff);
-  if (!p) return 1;
-  std::vector<Chunk> chunks;
-  if (!lattice_chunks(1, [&](long long k) { return pt_cell_bytes(p, k); }, chunks)) { mb_profile_twos_destroy(p); return 1; }
-  TwoProfPlan pl;
-  int rc = two_profile_descs(p, 0, 1, false, pl);
-  double *d_ll = nullptr;
-  if (!rc && !hip_ok(sm_alloc((void **)&d_ll, sizeof(double)), "hipMalloc(loglike)")) rc = 1;
-  double *pool = rc ? nullptr : (double *)ws_get(0, (size_t)pl.cells * sizeof(double));
-  if (!rc && !pool) rc = 1;
-  if (!rc) {
-    Timer tm;
-    tm.start();
-    rc = mode == MB_BACKWARD ? launch_profile_two_bwd(m, pl.d, 1, pl.maxItems, p->d_logA, p->d_logB, pool, d_ll, g_stream)
-                             : launch_profile_two_fwd(m, mode, true, pl.d, 1, 0, pl.maxItems, p->d_logA, p->d_logB, pool, nullptr, d_ll, g_stream);
-    g_last_ms += tm.stop();
-    g_last_launches = 1;
-  }
-  if (!rc) rc = d2h_large(cellsOut, pool, (size_t)pl.cells * sizeof(double));
-  if (rc) quiesce_streams();
-  pt_plan_free(pl); sm_free(d_ll);
-  g_last_kernel = mode == MB_BACKWARD ? "k_profile_two_bwd" : pt_fwd_name(mode, true);
-  mb_profile_twos_destroy(p);
   return rc;
 }
 

@@ -308,7 +308,7 @@ def batch_case(S, n, maxL):
 
 
 def batch_bytes(em, nCols, profs, levels):
-    """Per profile, the device bytes mb_api.hip charges to the memory budget: (counts(), viterbi() with paths).  The lattice is
+    """Per profile, the device bytes mb_profile_api.hip charges to the memory budget: (counts(), viterbi() with paths).  The lattice is
     (L+1) x 2 x (nCols+1) x S doubles; counts() adds nTrans x (nCols+1) accumulators, viterbi() the path slot of L + (L+1)(levels-1)
     entries at 8 bytes; both add the workgroup's global scratch (the ring of (3 (nCols+1) + nCols) S doubles) when their rolling
     state is beyond LDS -- X (nCols S doubles) for the materialised sweeps, 3 (nCols+1) S for the rolling Backward."""
@@ -322,7 +322,7 @@ def batch_bytes(em, nCols, profs, levels):
 
 
 def greedy_chunks(bytes_, budget):
-    """The chunks profile_chunks (mb_api.hip) cuts: even shares of ceil(total / budget) chunks, 5% slack, never over the budget."""
+    """The chunks lattice_chunks (mb_profile_api.hip) cuts: even shares of ceil(total / budget) chunks, 5% slack, never over the budget."""
     total = float(sum(bytes_))
     share = min(budget, total / max(1.0, np.ceil(total / budget)) * 1.05)
     out, p0, acc = [], 0, 0.0

@@ -272,7 +272,7 @@ def check_env_batch(em, triples, fill=False, live=None):
 
 # ---- a call that mixes plain and enveloped pairs (test_profile_pair_mixed_gpu.py; held to its conditions without a GPU by
 # test_profile_pair_env_host.py) ---------------------------------------------------------------------------------------------------------
-# pair_profile_descs (mb_api.hip) launches a chunk's plain pairs first and its enveloped pairs second and writes the per-pair outputs
+# pair_profile_descs (mb_profile_api.hip) launches a chunk's plain pairs first and its enveloped pairs second and writes the per-pair outputs
 # in that order: slot = rank among the chunk's plain pairs, or nPlain + rank among its enveloped ones.
 MIXED_STATES = (8, 65)
 MIXED_SEED = {8: 208, 65: 265}
@@ -365,7 +365,7 @@ def scratch_ring_bytes(S, x, P, env):
 
 
 def call_bytes(call, em, triples, nLevels=None):
-    """What each call of mb_api.hip tells lattice_chunks a pair costs: the lattice for materialised Forward, the traceback slot on
+    """What each call of mb_profile_api.hip tells lattice_chunks a pair costs: the lattice for materialised Forward, the traceback slot on
     top of it for Viterbi with paths, two lattices for counts, the pair's bins beside them for row posteriors, the scratch ring
     alone for the rolling sweeps."""
     S, C = em.nStates, em.nOutTok + 1
@@ -388,7 +388,7 @@ def chunk_kinds(chunks, envs):
 
 
 def chunk_launches(chunks, envs):
-    """pp_chunk_launches summed: two for a chunk that holds both kinds."""
+    """PairProfPlan::launches summed: two for a chunk that holds both kinds."""
     return sum(2 if len(k) == 2 else 1 for k in chunk_kinds(chunks, envs))
 
 

@@ -1,5 +1,5 @@
-"""GPU tests of the two-tape profile sweeps where one call mixes plain and enveloped pairs (pair_profile_descs, PairWhere and pp_fetch
-in mb_api.hip; docs/profile_tapes.md, "Where a call mixes geometries").  A chunk's plain pairs go through FullGeom in one launch and
+"""GPU tests of the two-tape profile sweeps where one call mixes plain and enveloped pairs (pair_profile_descs, PairWhere and fetch_loglike
+in mb_profile_api.hip; docs/profile_tapes.md, "Where a call mixes geometries").  A chunk's plain pairs go through FullGeom in one launch and
 its enveloped pairs through EnvGeom in a second; the per-pair outputs are written in slot order (plain first) and mapped back to pair
 order, chunk by chunk, while lattices, path slots and scratch rings are packed in pair order.  The references are
 profile.PairProfileDP(env=...) called per pair with that pair's envelope or None, PairProfileDP.rowPosteriors and

@@ -1,4 +1,4 @@
-"""GPU tests of the two-profile sweeps where the host splits one call (mb_api.hip: mb_profile_twos_counts, mb_profile_twos_viterbi,
+"""GPU tests of the two-profile sweeps where the host splits one call (mb_profile_api.hip: mb_profile_twos_counts, mb_profile_twos_viterbi,
 two_profile_descs; docs/profile_tapes.md, "Pairs of profiles"): several count workgroups to a pair around the marks of the group
 rule, counts and Viterbi paths in chunks under a memory budget, and a traceback of more pairs than one block of 64 lanes.  The
 recurrence is pinned by test_profile_two_gpu.py; here it is the strides, the bases and the seams.  The reference is
@@ -61,7 +61,7 @@ def groups():
 @pytest.mark.parametrize("n", range(len(th.GROUP_SHAPES)), ids=["%dx%d" % s for s in th.GROUP_SHAPES])
 def test_counts_of_one_pair_across_groups(groups, n):
     """One pair to a launch at the marks of the group rule -- a workgroup per 2 048 (cell, state) items, restated by
-    th.count_groups and asserted here, so that a change of the rule in mb_api.hip shows instead of moving every shape to one side
+    th.count_groups and asserted here, so that a change of the rule in mb_profile_api.hip shows instead of moving every shape to one side
     of its mark: 2 040 items (one group) against 2 050 (two; the short side found by i, then by r), 4 205 (three; the last stride
     of 768 items is whole for group 0, partial for group 1 and empty for group 2), 10 240 = 5 x 2 048 (five) against 10 400 (six;
     by i, then by r) and 20 800 (eleven).  S = 5 is odd: no stride ends on a cell.  Every transition has a positive count in the

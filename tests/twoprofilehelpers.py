@@ -225,7 +225,7 @@ def count_groups(S, shapes):
 
 
 def lattice_chunks(sizes, budget):
-    """[(p0, p1)]: lattice_chunks of mb_api.hip restated -- chunks of at most ``budget`` bytes, evened out to within a twentieth."""
+    """[(p0, p1)]: lattice_chunks of mb_profile_api.hip restated -- chunks of at most ``budget`` bytes, evened out to within a twentieth."""
     total = float(sum(sizes))
     n = max(1.0, math.ceil(total / budget))
     share = min(float(budget), total / n * 1.05)
