@@ -62,12 +62,9 @@ static int g_api_depth = 0;
 static void ws_begin_call();
 ApiGuard::ApiGuard() { g_api_mutex.lock(); if (g_api_depth++ == 0) ws_begin_call(); }
 ApiGuard::~ApiGuard() { --g_api_depth; g_api_mutex.unlock(); }
-// the same lock without the "a new call begins" bookkeeping: option and introspection entry points (they touch the environment /
-// the planners' process-wide state, which guarded calls of other threads read)
-struct ApiLock {
-  std::lock_guard<std::recursive_mutex> lk;
-  ApiLock() : lk(g_api_mutex) {}
-};
+// the same lock without the "a new call begins" bookkeeping: option and introspection entry points
+ApiLock::ApiLock() { g_api_mutex.lock(); }
+ApiLock::~ApiLock() { g_api_mutex.unlock(); }
 bool g_deterministic = false;
 static int g_device = -1;   // device the library's stream and workspaces live on
 
@@ -345,16 +342,30 @@ static bool plan_chunks(const mb_batch *b, int nMatrices, std::vector<Chunk> &ou
   return true;
 }
 
-// Upload PairDescs of a chunk with cellBase rebased to the chunk's pool.
+// The PairDescs of a chunk with cellBase rebased to the chunk's pool, on the host and (owned) on the device.
+struct DescPlan { SmBuf<PairDesc> d; std::vector<PairDesc> hp; };
 // tbStride > 0: traceback bytes instead of cells -- cellBase = BYTE offset, tbStride bytes per supercell
-static int upload_chunk_descs(const mb_batch *b, const Chunk &c, PairDesc **d_out, std::vector<PairDesc> &tmp, int tbStride = 0) {
-  tmp.assign(b->pairs.begin() + c.p0, b->pairs.begin() + c.p1);
+static int upload_chunk_descs(const mb_batch *b, const Chunk &c, DescPlan &pl, int tbStride = 0) {
+  pl.hp.assign(b->pairs.begin() + c.p0, b->pairs.begin() + c.p1);
   long long base = 0;
-  for (auto &pd : tmp) { pd.cellBase = base; base += (long long)(pd.inLen + 1) * (pd.outLen + 1) * (tbStride > 0 ? tbStride : b->m->S); }
-  MB_HIP(sm_alloc((void **)d_out, tmp.size() * sizeof(PairDesc)));
-  if (!hip_ok(hipMemcpyAsync(*d_out, tmp.data(), tmp.size() * sizeof(PairDesc), hipMemcpyHostToDevice, g_stream), "H2D pair descriptors") ||
-      !hip_ok(hipStreamSynchronize(g_stream), "H2D pair descriptors")) { sm_free(*d_out); *d_out = nullptr; return 1; }
+  for (auto &pd : pl.hp) { pd.cellBase = base; base += (long long)(pd.inLen + 1) * (pd.outLen + 1) * (tbStride > 0 ? tbStride : b->m->S); }
+  MB_HIP(pl.d.alloc((long long)pl.hp.size()));
+  if (!hip_ok(hipMemcpyAsync(pl.d, pl.hp.data(), pl.hp.size() * sizeof(PairDesc), hipMemcpyHostToDevice, g_stream), "H2D pair descriptors") ||
+      !hip_ok(hipStreamSynchronize(g_stream), "H2D pair descriptors")) return 1;
   return 0;
+}
+static auto desc_build(const mb_batch *b, int tbStride = 0) { return [b, tbStride](const Chunk &c, DescPlan &pl) { return upload_chunk_descs(b, c, pl, tbStride); }; }
+
+// launches outside a chunk loop, timed into g_last_ms on a timer of their own
+template <class F> static int timed(F launches) { Timer tm; Timed t(tm, 0); return launches(); }
+static void reset_last() { g_last_ms = 0.0; g_last_launches = 0; g_last_kernel = ""; }
+// the token tape of a one-tape machine's batch
+static const int *tape_of(const mb_batch *b) { return b->m->nOut ? b->d_out : b->d_in; }
+// the batch's envelopes as the tiled family takes them (empty: none)
+static MedEnv med_env(const mb_batch *b) {
+  MedEnv me;
+  if (b->hasEnv) { me.d_start = b->d_envStart; me.d_end = b->d_envEnd; me.h_start = b->h_envStart.data(); me.h_end = b->h_envEnd.data(); }
+  return me;
 }
 
 
@@ -395,7 +406,7 @@ int env_int(const char *name, int dflt) {
 
 // what the closure chooser minimises (fast_state) and what MB_MEDIUM_JIT_VERBOSE prints (mb_debug_jit_source): candidate slots + the
 // price of a round and of a synchronisation point in slots (MB_MEDIUM_ROUND_COST, default 0; MB_MEDIUM_SYNC_COST, default 1)
-static long long medium_program_cost(const MedProgram &P) {
+long long medium_program_cost(const MedProgram &P) {
   const int syncCost = env_int("MB_MEDIUM_SYNC_COST", 1), roundCost = env_int("MB_MEDIUM_ROUND_COST", 0);
   long long c = 0;
   for (const MedRoundInfo &ri : P.roundInfo) c += (long long)ri.slots.size() + roundCost + (ri.sync ? syncCost : 0);
@@ -607,8 +618,7 @@ static int fill_chunk(mb_machine *m, int mode, const PairDesc *d_desc, const std
     const bool exactFwd = mode == MB_VITERBI || (mode == MB_FORWARD && startState != 0);
     MedProgram &P = mode == MB_BACKWARD ? f->bwdSum : (exactFwd ? f->fwdExact : f->fwdSum);
     const MedGeom &geo = mode == MB_BACKWARD ? f->geoBS : (exactFwd ? f->geoFE : f->geoFS);
-    MedEnv me;
-    if (env) { me.d_start = b->d_envStart; me.d_end = b->d_envEnd; me.h_start = b->h_envStart.data(); me.h_end = b->h_envEnd.data(); }
+    const MedEnv me = b ? med_env(b) : MedEnv();
     const int rc = medium_fill_materialised(m, P, geo, mode == MB_VITERBI ? MB_VITERBI : MB_FORWARD,
                                             (mode == MB_FORWARD && startState != 0) ? startState : -1, d_desc, hp, d_in, d_out, pool, g_stream, me);
     if (rc >= 0) {
@@ -666,15 +676,17 @@ static bool small_chunks_plan(const mb_batch *b, const SmallProgram &P, bool wan
   return true;
 }
 
-// buffers of one chunk: aux records uploaded, workspaces sized; fills `sw`
-static int small_prepare(mb_batch *b, const Chunk &c, const SmallProgram &P, bool wantPool, bool wantTb, SmallPlan &pl,
-                         std::vector<PairDesc> &hp, SmAux **d_aux, SmSweep &sw, size_t chunkNo = (size_t)-1) {
+// One chunk of a small-family call: its pairs, their placement, the aux records (owned, on the device) and the sweep's arguments.
+struct SmallChunk { SmallPlan pl; std::vector<PairDesc> hp; SmBuf<SmAux> d_aux; SmSweep sw; };
+// aux records uploaded, workspaces sized; fills k.sw
+static int small_prepare(mb_batch *b, const Chunk &c, const SmallProgram &P, bool wantPool, bool wantTb, SmallChunk &k, size_t chunkNo = (size_t)-1) {
+  SmallPlan &pl = k.pl; std::vector<PairDesc> &hp = k.hp; SmSweep &sw = k.sw;
   hp.assign(b->pairs.begin() + c.p0, b->pairs.begin() + c.p1);
   small_plan(b->m, P, hp.data(), (long long)hp.size(), wantPool, wantTb, pl);
-  MB_HIP(sm_alloc((void **)d_aux, hp.size() * sizeof(SmAux)));   // (the caller frees *d_aux on every path)
-  MB_HIP(hipMemcpyAsync(*d_aux, pl.aux.data(), hp.size() * sizeof(SmAux), hipMemcpyHostToDevice, g_stream));
+  MB_HIP(k.d_aux.alloc((long long)hp.size()));
+  MB_HIP(hipMemcpyAsync(k.d_aux, pl.aux.data(), hp.size() * sizeof(SmAux), hipMemcpyHostToDevice, g_stream));
   sw = SmSweep();
-  sw.d_pairs = b->d_pairs + c.p0; sw.pairs = &hp; sw.d_in = b->d_in; sw.d_out = b->d_out; sw.d_aux = *d_aux;
+  sw.d_pairs = b->d_pairs + c.p0; sw.pairs = &hp; sw.d_in = b->d_in; sw.d_out = b->d_out; sw.d_aux = k.d_aux;
   if (chunkNo != (size_t)-1) {
     if (b->smTiles.size() <= 2 * chunkNo + 1) b->smTiles.resize(2 * chunkNo + 2);
     for (int bw = 0; bw < 2; ++bw) {
@@ -701,32 +713,85 @@ static int small_prepare(mb_batch *b, const Chunk &c, const SmallProgram &P, boo
   return 0;
 }
 
+// the chunk builder of a small-family call (for_chunks); it numbers the chunks for the tile caches
+static auto small_chunk_build(mb_batch *b, const SmallProgram &P, bool wantPool, bool wantTb) {
+  return [=, &P, chunkNo = (size_t)0](const Chunk &c, SmallChunk &k) mutable { return small_prepare(b, c, P, wantPool, wantTb, k, chunkNo++); };
+}
+
 static int small_forward(mb_batch *b, int flags, double *loglike) {
   FastState *f = (FastState *)b->m->fast;
   const bool mat = !(flags & MB_ROLLING);
   std::vector<Chunk> chunks;
   if (!small_chunks_plan(b, f->smF, mat, false, chunks)) return 1;
-  double *d_ll = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, b->nPairs * sizeof(double)));
-  int rc = 0;
-  Timer tm;
-  size_t chunkNo = 0;
-  for (const Chunk &c : chunks) {
-    SmallPlan pl; std::vector<PairDesc> hp; SmAux *d_aux = nullptr; SmSweep sw;
-    if (!(rc = small_prepare(b, c, f->smF, mat, false, pl, hp, &d_aux, sw, chunkNo++))) {
-      sw.d_loglike = d_ll + c.p0;
-      tm.start();
-      rc = small_sweep(f->smF, SM_SUM, mat, sw, g_stream);
-      g_last_ms += tm.stop();
-    }
-    sm_free(d_aux);
-    if (rc) break;
-  }
+  SmBuf<double> d_ll;
+  MB_HIP(d_ll.alloc(b->nPairs));
+  int rc = for_chunks<SmallChunk>(chunks, small_chunk_build(b, f->smF, mat, false), [&](const Chunk &c, SmallChunk &k, Timer &tm) {
+    k.sw.d_loglike = d_ll + c.p0;
+    Timed t(tm, 0);
+    return small_sweep(f->smF, SM_SUM, mat, k.sw, g_stream);
+  });
   g_last_kernel = small_kernel_name(f->smF, SM_SUM, mat);
-  if (!rc && !hip_ok(hipMemcpy(loglike, d_ll, b->nPairs * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
-  sm_free(d_ll);
+  if (!rc) rc = fetch_loglike(loglike, d_ll, b->nPairs);
   return rc;
 }
+
+// ---- the path tail of the Viterbi calls (small family here, viterbi_chunks below) ------------------------------------------------
+// MB_TIMING: the host-side laps of a Viterbi call on stderr
+struct Laps {
+  const bool on = opt_env("MB_TIMING") != nullptr;
+  double tPrev = now();
+  static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  void lap(const char *what) { if (on) { const double t = now(); fprintf(stderr, "[mbhip] viterbi %-28s %7.2f ms\n", what, t - tPrev); tPrev = t; } }
+};
+
+// Where the traceback kernel of a chunk writes: each pair's path into a slot of its worst-case length, the lengths beside them
+// (cached workspaces 3..5: a hipMalloc/hipFree pair per call costs more than the traceback kernel of a small batch).
+struct PathSlots { std::vector<long long> slot; long long *d_slot = nullptr, *d_len = nullptr; uint32_t *d_path = nullptr; };
+static int path_slots(const mb_batch *b, const Chunk &c, PathSlots &s) {
+  const long long np = c.p1 - c.p0;
+  s.slot.assign(np + 1, 0);
+  for (long long p = 0; p < np; ++p)
+    s.slot[p + 1] = s.slot[p] + mb_viterbi_path_bound(b->m, b->pairs[c.p0 + p].inLen, b->pairs[c.p0 + p].outLen);
+  if (!(s.d_slot = (long long *)ws_get(3, (np + 1) * sizeof(long long)))) return 1;
+  if (!(s.d_len = (long long *)ws_get(4, np * sizeof(long long)))) return 1;
+  if (!(s.d_path = (uint32_t *)ws_get(5, std::max<long long>(s.slot[np], 1) * sizeof(uint32_t)))) return 1;
+  return hip_ok(hipMemcpyAsync(s.d_slot, s.slot.data(), (np + 1) * sizeof(long long), hipMemcpyHostToDevice, g_stream), "H2D") ? 0 : 1;
+}
+
+// The caller's path arrays of a Viterbi call, and how much of them the chunks so far have used.
+struct PathOut { int64_t *off; uint32_t *edges; int64_t cap; long long written = 0; };
+
+// The paths of chunk c from their slots to the caller's arrays: lengths checked (-1: no finite path, an empty one; -2 / any other
+// negative: the traceback's two errors, worded by the caller), the chunk's total checked against what is left of pathCap, then
+// packed on the device (slots 6/7) and ONE copy of exactly the used entries (the slots are sized for the worst case,
+// (inLen+outLen+1) x levels edges per pair: 32 MB for 1024 x 1 kb x 1 kb dnapsw pairs, 15 MB used).
+static int pack_paths(PathOut &o, const Chunk &c, const PathSlots &s, const char *overflowText, const char *deadEndText, Laps &laps) {
+  const long long np = c.p1 - c.p0;
+  std::vector<long long> len(np, 0), off(np, -1);
+  if (!hip_ok(hipMemcpy(len.data(), s.d_len, np * sizeof(long long), hipMemcpyDeviceToHost), "D2H path lengths")) return 1;
+  long long total = 0;
+  for (long long p = 0; p < np; ++p) {
+    const long long n = len[p];
+    if (n == -1) continue;   // -inf end cell: no path (src/dpmatrix.defs.h:84)
+    if (n < 0) { set_error(n == -2 ? overflowText : deadEndText); return 1; }
+    off[p] = total; total += n;
+  }
+  if (o.written + total > o.cap) { set_error("pathCap too small for the Viterbi paths of this batch"); return 1; }
+  long long *d_off = (long long *)ws_get(6, np * sizeof(long long));
+  uint32_t *d_packed = (uint32_t *)ws_get(7, std::max<long long>(total, 1) * sizeof(uint32_t));
+  if (!d_off || !d_packed) return 1;
+  if (!hip_ok(hipMemcpyAsync(d_off, off.data(), np * sizeof(long long), hipMemcpyHostToDevice, g_stream), "H2D")) return 1;
+  if (const int rc = launch_compact_paths(s.d_path, s.d_slot, s.d_len, d_off, d_packed, np, g_stream)) return rc;
+  if (total && d2h_large(o.edges + o.written, d_packed, total * sizeof(uint32_t))) return 1;
+  if (!hip_ok(hipStreamSynchronize(g_stream), "path compaction")) return 1;
+  laps.lap("pack + D2H paths");
+  for (long long p = 0; p < np; ++p) {
+    if (len[p] > 0) o.written += len[p];
+    o.off[c.p0 + p + 1] = o.written;
+  }
+  return 0;
+}
+static const char *const PATH_OVERFLOW = "Viterbi traceback exceeded its path bound", *const PATH_DEAD_END = "Viterbi traceback reached a dead end";
 
 // ViterbiMatrix(eval, sp).logLike() / path(): one traceback byte per cell, walked on the device
 static int small_viterbi(mb_batch *b, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int64_t pathCap) {
@@ -734,68 +799,28 @@ static int small_viterbi(mb_batch *b, double *loglike, int64_t *pathOff, uint32_
   const bool wantPaths = pathEdges != nullptr && pathOff != nullptr;
   std::vector<Chunk> chunks;
   if (!small_chunks_plan(b, f->smF, false, true, chunks)) return 1;
-  int rc = 0;
-  Timer tm;
-  long long written = 0;
-  const bool timing = opt_env("MB_TIMING") != nullptr;
-  auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double tPrev = now();
-  auto lap = [&](const char *what) { if (timing) { const double t = now(); fprintf(stderr, "[mbhip] viterbi %-28s %7.2f ms\n", what, t - tPrev); tPrev = t; } };
-  size_t chunkNo = 0;
-  for (const Chunk &c : chunks) {
+  PathOut out{pathOff, pathEdges, pathCap};
+  Laps laps;
+  const int rc = for_chunks<SmallChunk>(chunks, small_chunk_build(b, f->smF, false, true), [&](const Chunk &c, SmallChunk &k, Timer &tm) {
     const long long np = c.p1 - c.p0;
-    SmallPlan pl; std::vector<PairDesc> hp; SmAux *d_aux = nullptr; SmSweep sw;
-    double *d_ll = nullptr;
-    std::vector<long long> slot(np + 1, 0), len(np, 0);
-    do {
-      if ((rc = small_prepare(b, c, f->smF, false, true, pl, hp, &d_aux, sw, chunkNo++))) break;
-      if (!hip_ok(sm_alloc((void **)&d_ll, np * sizeof(double)), "hipMalloc")) { rc = 1; break; }
-      sw.d_loglike = d_ll;
-      lap("chunk set-up");
-      tm.start();
-      if ((rc = small_sweep(f->smF, SM_TB, false, sw, g_stream))) break;
-      lap("fill (traceback bytes)");
-      long long *d_slot = nullptr, *d_len = nullptr; uint32_t *d_path = nullptr;
+    SmBuf<double> d_ll;
+    if (!hip_ok(d_ll.alloc(np), "hipMalloc")) return 1;
+    k.sw.d_loglike = d_ll;
+    laps.lap("chunk set-up");
+    PathSlots ps;
+    {
+      Timed t(tm, 0);
+      if (const int r = small_sweep(f->smF, SM_TB, false, k.sw, g_stream)) return r;
+      laps.lap("fill (traceback bytes)");
       if (wantPaths) {
-        for (long long p = 0; p < np; ++p) slot[p + 1] = slot[p] + mb_viterbi_path_bound(b->m, hp[p].inLen, hp[p].outLen);
-        if (!(d_slot = (long long *)ws_get(3, (np + 1) * sizeof(long long)))) { rc = 1; break; }
-        if (!(d_len = (long long *)ws_get(4, np * sizeof(long long)))) { rc = 1; break; }
-        if (!(d_path = (uint32_t *)ws_get(5, std::max<long long>(slot[np], 1) * sizeof(uint32_t)))) { rc = 1; break; }
-        if (!hip_ok(hipMemcpyAsync(d_slot, slot.data(), (np + 1) * sizeof(long long), hipMemcpyHostToDevice, g_stream), "H2D")) { rc = 1; break; }
-        if ((rc = launch_small_traceback(f->smF, sw.d_pairs, np, b->d_in, b->d_out, sw.d_tb, d_aux, d_ll, d_slot, d_path, d_len, g_stream))) break;
+        if (path_slots(b, c, ps)) return 1;
+        if (const int r = launch_small_traceback(f->smF, k.sw.d_pairs, np, b->d_in, b->d_out, k.sw.d_tb, k.d_aux, d_ll, ps.d_slot, ps.d_path, ps.d_len, g_stream)) return r;
       }
-      g_last_ms += tm.stop();
-      lap("traceback kernel");
-      if (!hip_ok(hipMemcpy(loglike + c.p0, d_ll, np * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) { rc = 1; break; }
-      if (wantPaths) {
-        if (!hip_ok(hipMemcpy(len.data(), d_len, np * sizeof(long long), hipMemcpyDeviceToHost), "D2H path lengths")) { rc = 1; break; }
-        std::vector<long long> off(np, -1);
-        long long total = 0;
-        for (long long p = 0; p < np && !rc; ++p) {
-          const long long n = len[p];
-          if (n == -1) continue;   // -inf end cell: no path (src/dpmatrix.defs.h:84)
-          if (n < 0) { set_error("Viterbi traceback exceeded its path bound"); rc = 1; break; }
-          off[p] = total; total += n;
-        }
-        if (rc) break;
-        if (written + total > pathCap) { set_error("pathCap too small for the Viterbi paths of this batch"); rc = 1; break; }
-        long long *d_off = (long long *)ws_get(6, np * sizeof(long long));
-        uint32_t *d_packed = (uint32_t *)ws_get(7, std::max<long long>(total, 1) * sizeof(uint32_t));
-        if (!d_off || !d_packed) { rc = 1; break; }
-        if (!hip_ok(hipMemcpyAsync(d_off, off.data(), np * sizeof(long long), hipMemcpyHostToDevice, g_stream), "H2D")) { rc = 1; break; }
-        if ((rc = launch_compact_paths(d_path, d_slot, d_len, d_off, d_packed, np, g_stream))) break;
-        if (total && d2h_large(pathEdges + written, d_packed, total * sizeof(uint32_t))) { rc = 1; break; }
-        if (!hip_ok(hipStreamSynchronize(g_stream), "path compaction")) { rc = 1; break; }
-        lap("pack + D2H paths");
-        for (long long p = 0; p < np; ++p) {
-          if (len[p] > 0) written += len[p];
-          pathOff[c.p0 + p + 1] = written;
-        }
-      }
-    } while (0);
-    sm_free(d_aux); sm_free(d_ll);
-    if (rc) break;
-  }
+    }
+    laps.lap("traceback kernel");
+    if (fetch_loglike(loglike + c.p0, d_ll, np)) return 1;
+    return wantPaths ? pack_paths(out, c, ps, PATH_OVERFLOW, PATH_OVERFLOW, laps) : 0;      // (this family's walker reports every failure as the bound's)
+  });
   g_last_kernel = "k_small_tb";
   return rc;
 }
@@ -805,57 +830,38 @@ static int small_viterbi(mb_batch *b, double *loglike, int64_t *pathOff, uint32_
 static const int SMALL_COUNT_REPLICAS = 64;
 static int small_counts(mb_batch *b, double *counts, double *loglikeSum, double *loglike) {
   FastState *f = (FastState *)b->m->fast;
-  const long long nT = b->m->nTrans;
+  const long long nT = b->m->nTrans, nRep = std::max<long long>(nT, 1) * SMALL_COUNT_REPLICAS;
   std::vector<Chunk> chunks;
   if (!small_chunks_plan(b, f->smB, true, false, chunks)) return 1;
-  double *d_rep = nullptr, *d_ll = nullptr, *d_bll = nullptr;
-  int rc = 0;
-  Timer tm;
-  do {
-    if (!hip_ok(sm_alloc((void **)&d_rep, std::max<long long>(nT, 1) * SMALL_COUNT_REPLICAS * sizeof(double)), "hipMalloc")) { rc = 1; break; }
-    if (!hip_ok(sm_alloc((void **)&d_ll, b->nPairs * sizeof(double)), "hipMalloc")) { rc = 1; break; }
-    if (!hip_ok(sm_alloc((void **)&d_bll, b->nPairs * sizeof(double)), "hipMalloc")) { rc = 1; break; }
-    if (!hip_ok(hipMemsetAsync(d_rep, 0, std::max<long long>(nT, 1) * SMALL_COUNT_REPLICAS * sizeof(double), g_stream), "memset")) { rc = 1; break; }
-    size_t chunkNo = 0;
-  for (const Chunk &c : chunks) {
-      SmallPlan pl; std::vector<PairDesc> hp; SmAux *d_aux = nullptr; SmSweep sw;
-      if (!(rc = small_prepare(b, c, f->smB, true, false, pl, hp, &d_aux, sw, chunkNo++))) {
-        tm.start();
-        sw.d_loglike = d_bll + c.p0;
-        rc = small_sweep(f->smB, SM_SUM, true, sw, g_stream);                 // BackwardMatrix::fill, src/backward.cpp:18-46
-        if (!rc) {
-          sw.d_loglike = d_ll + c.p0; sw.d_bwdLL = d_bll + c.p0; sw.d_counts = d_rep; sw.nRep = SMALL_COUNT_REPLICAS;
-          rc = small_sweep(f->smF, SM_COUNT, false, sw, g_stream);            // Forward + getCounts, src/backward.cpp:58-87
-        }
-        g_last_ms += tm.stop();
-      }
-      sm_free(d_aux);
-      if (rc) break;
-    }
-    if (rc) break;
-    std::vector<double> hc((size_t)nT * SMALL_COUNT_REPLICAS), hll(b->nPairs);
-    if (nT && !hip_ok(hipMemcpy(hc.data(), d_rep, hc.size() * sizeof(double), hipMemcpyDeviceToHost), "D2H counts")) { rc = 1; break; }
-    if (!hip_ok(hipMemcpy(hll.data(), d_ll, b->nPairs * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) { rc = 1; break; }
-    for (long long e = 0; e < nT; ++e) {
-      if (g_deterministic) {      // fixed point, 2^-36: the replicas add up as integers
-        unsigned long long tot = 0; bool inRange = true;
-        for (int r = 0; r < SMALL_COUNT_REPLICAS; ++r) { unsigned long long u; std::memcpy(&u, &hc[(size_t)r * nT + e], 8); inRange = inRange && u < (1ull << 62); tot += u; }
-        double c;
-        if (!det_to_double(tot, c) || !inRange) { set_error("MB_DETERMINISTIC: a posterior count left the fixed-point range (6.7e7 per transition and call): split the batch or use the floating-point mode"); rc = 1; break; }
-        counts[e] += c;
-        continue;
-      }
-      double s = 0.0;
-      for (int r = 0; r < SMALL_COUNT_REPLICAS; ++r) s += hc[(size_t)r * nT + e];
-      counts[e] += s;
-    }
-    double s = 0;
-    for (long long p = 0; p < b->nPairs; ++p) { s += hll[p]; if (loglike) loglike[p] = hll[p]; }   // loglike += forward.logLike(), src/counts.cpp:61-62
-    if (loglikeSum) *loglikeSum += s;
-  } while (0);
-  sm_free(d_rep); sm_free(d_ll); sm_free(d_bll);
   g_last_kernel = "k_small_count";
-  return rc;
+  SmBuf<double> d_rep, d_ll, d_bll;
+  if (!hip_ok(d_rep.alloc(nRep), "hipMalloc") || !hip_ok(d_ll.alloc(b->nPairs), "hipMalloc") || !hip_ok(d_bll.alloc(b->nPairs), "hipMalloc")) return 1;
+  if (!hip_ok(hipMemsetAsync(d_rep, 0, nRep * sizeof(double), g_stream), "memset")) return 1;
+  const int rc = for_chunks<SmallChunk>(chunks, small_chunk_build(b, f->smB, true, false), [&](const Chunk &c, SmallChunk &k, Timer &tm) {
+    Timed t(tm, 0);
+    k.sw.d_loglike = d_bll + c.p0;
+    if (const int r = small_sweep(f->smB, SM_SUM, true, k.sw, g_stream)) return r;      // BackwardMatrix::fill, src/backward.cpp:18-46
+    k.sw.d_loglike = d_ll + c.p0; k.sw.d_bwdLL = d_bll + c.p0; k.sw.d_counts = d_rep; k.sw.nRep = SMALL_COUNT_REPLICAS;
+    return small_sweep(f->smF, SM_COUNT, false, k.sw, g_stream);                          // Forward + getCounts, src/backward.cpp:58-87
+  });
+  if (rc) return rc;
+  std::vector<double> hc((size_t)nT * SMALL_COUNT_REPLICAS), hll(b->nPairs);
+  if (nT && !hip_ok(hipMemcpy(hc.data(), d_rep, hc.size() * sizeof(double), hipMemcpyDeviceToHost), "D2H counts")) return 1;
+  if (fetch_loglike(hll.data(), d_ll, b->nPairs)) return 1;
+  CountSum sum(nT);
+  for (long long e = 0; e < nT; ++e) {
+    if (g_deterministic) {      // fixed point, 2^-36: the replicas add up as integers, then the sum is decoded
+      unsigned long long tot = 0; bool inRange = true;
+      for (int r = 0; r < SMALL_COUNT_REPLICAS; ++r) { unsigned long long u; std::memcpy(&u, &hc[(size_t)r * nT + e], 8); inRange = inRange && u < (1ull << 62); tot += u; }
+      if (!det_to_double(tot, sum.total[(size_t)e]) || !inRange) { set_error(COUNT_RANGE_ERROR); return 1; }
+      continue;
+    }
+    double s = 0.0;
+    for (int r = 0; r < SMALL_COUNT_REPLICAS; ++r) s += hc[(size_t)r * nT + e];
+    sum.total[(size_t)e] = s;
+  }
+  sum.finish(hll, counts, loglikeSum, loglike);   // loglike += forward.logLike(), src/counts.cpp:61-62
+  return 0;
 }
 
 // one full matrix in the reference's layout (mb_fill): sweep tile-major, convert on the device, copy out
@@ -864,26 +870,25 @@ static int small_fill(mb_batch *b, int mode, double *cellsOut) {
   SmallProgram &P = mode == MB_BACKWARD ? f->smB : f->smF;
   const PairDesc &pd = b->pairs[0];
   const long long n = (long long)(pd.inLen + 1) * (pd.outLen + 1) * b->m->S;
-  const Chunk c{0, 1, 0};
-  SmallPlan pl; std::vector<PairDesc> hp; SmAux *d_aux = nullptr; SmSweep sw;
-  double *d_ll = nullptr, *d_cells = nullptr;
-  int rc = 0;
-  do {
-    if ((size_t)(small_pair_doubles(P.S, pd.inLen, pd.outLen) + n) * 8 > budget_bytes()) { set_error("matrix exceeds the device memory budget"); rc = 1; break; }
-    if ((rc = small_prepare(b, c, P, true, false, pl, hp, &d_aux, sw))) break;
-    if (!hip_ok(sm_alloc((void **)&d_ll, sizeof(double)), "hipMalloc")) { rc = 1; break; }
-    if (!(d_cells = (double *)ws_get(1, (size_t)std::max<long long>(n, 1) * 8))) { rc = 1; break; }
-    sw.d_loglike = d_ll;
-    if ((rc = small_sweep(P, mode == MB_VITERBI ? SM_MAX : SM_SUM, true, sw, g_stream))) break;
-    if ((rc = launch_fill_neg_inf(d_cells, n, g_stream))) break;
-    if ((rc = launch_small_unpack(sw.d_pool, P.S, pd.inLen, pd.outLen, mode == MB_BACKWARD, d_cells,
-                                  b->hasEnv && pd.envBase >= 0 ? b->d_envStart + pd.envBase : nullptr,
-                                  b->hasEnv && pd.envBase >= 0 ? b->d_envEnd + pd.envBase : nullptr, g_stream))) break;
-    if (!hip_ok(hipStreamSynchronize(g_stream), "fill kernel")) { rc = 1; break; }
-    if (!hip_ok(hipMemcpy(cellsOut, d_cells, n * sizeof(double), hipMemcpyDeviceToHost), "D2H matrix")) { rc = 1; break; }
-  } while (0);
-  sm_free(d_aux); sm_free(d_ll);
-  g_last_kernel = small_kernel_name(P, mode == MB_VITERBI ? SM_MAX : SM_SUM, true);
+  const int smMode = mode == MB_VITERBI ? SM_MAX : SM_SUM;
+  const int rc = [&]() {
+    if ((size_t)(small_pair_doubles(P.S, pd.inLen, pd.outLen) + n) * 8 > budget_bytes()) { set_error("matrix exceeds the device memory budget"); return 1; }
+    SmallChunk k;
+    if (const int r = small_prepare(b, Chunk{0, 1, 0}, P, true, false, k)) return r;
+    SmBuf<double> d_ll;
+    if (!hip_ok(d_ll.alloc(1), "hipMalloc")) return 1;
+    double *d_cells = (double *)ws_get(1, (size_t)std::max<long long>(n, 1) * 8);
+    if (!d_cells) return 1;
+    k.sw.d_loglike = d_ll;
+    if (const int r = small_sweep(P, smMode, true, k.sw, g_stream)) return r;
+    if (const int r = launch_fill_neg_inf(d_cells, n, g_stream)) return r;
+    if (const int r = launch_small_unpack(k.sw.d_pool, P.S, pd.inLen, pd.outLen, mode == MB_BACKWARD, d_cells,
+                                          b->hasEnv && pd.envBase >= 0 ? b->d_envStart + pd.envBase : nullptr,
+                                          b->hasEnv && pd.envBase >= 0 ? b->d_envEnd + pd.envBase : nullptr, g_stream)) return r;
+    if (!hip_ok(hipStreamSynchronize(g_stream), "fill kernel")) return 1;
+    return hip_ok(hipMemcpy(cellsOut, d_cells, n * sizeof(double), hipMemcpyDeviceToHost), "D2H matrix") ? 0 : 1;
+  }();
+  g_last_kernel = small_kernel_name(P, smMode, true);
   return rc;
 }
 
@@ -1164,175 +1169,206 @@ int mb_batch_set_envelopes(mb_batch *b, const int64_t *envOff, const int32_t *in
   return 0;
 }
 
+// ---- two one-tape fills side by side ------------------------------------------------------------------------------------------
+// g_stream and the second stream forked: the second stream starts after what g_stream has queued so far (descriptors), join()
+// makes g_stream wait for what the second one ran since.  The events go on every path.
+struct StreamFork {
+  hipStream_t s2 = second_stream();
+  hipEvent_t evStart = nullptr, evDone = nullptr;
+  bool ok;
+  StreamFork() {
+    ok = s2 && hipEventCreateWithFlags(&evStart, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&evDone, hipEventDisableTiming) == hipSuccess &&
+         hipEventRecord(evStart, g_stream) == hipSuccess && hipStreamWaitEvent(s2, evStart, 0) == hipSuccess;
+  }
+  bool join() { return ok && hipEventRecord(evDone, s2) == hipSuccess && hipStreamWaitEvent(g_stream, evDone, 0) == hipSuccess; }
+  ~StreamFork() { if (evStart) (void)hipEventDestroy(evStart); if (evDone) (void)hipEventDestroy(evDone); }
+};
+
+// A Forward-direction fill (program WF over descriptors d_f / h_f into dstF) and a Backward-direction one (WB, d_b / h_b, dstB) of
+// the same n sequences of a one-tape machine, which are independent: both in ONE launch when the programs share a kernel variant,
+// else two launches on two streams, joined before this returns.  keepColumns: only the last column of each sequence is kept (the
+// split Forward) instead of the matrix.  With CUs to spare each fill runs k workgroups per sequence on half the chip; a machine whose
+// ring lives in L2 and whose parts fit the LDS only when a sweep has the whole chip runs one fill after the other on all of it.
+// Returns 0, an error, or -1 when nothing ran: the programs share no kernel and there is no second stream (a caller that asked for
+// the stream up front never sees that).  forkError / joinError: the texts of the two stream failures.
+static int onetape_fill_pair(mb_machine *m, WideProgram &WF, WideProgram &WB, const PairDesc *d_f, const PairDesc *d_b, const PairDesc *h_f,
+                             const PairDesc *h_b, long long n, const int *tape, double *dstF, double *dstB, bool keepColumns,
+                             const char *forkError, const char *joinError) {
+  hipStream_t s2 = second_stream();
+  const int cus = device_cus();
+  bool parts = s2 && wide_parts_for(m, WF, n, cus / 2, h_f) > 1 && wide_parts_for(m, WB, n, cus / 2, h_b) > 1;
+  const bool oneByOne = s2 && !parts && (WF.retGv || WB.retGv) && wide_parts_for(m, WF, n, cus, h_f) > 1 && wide_parts_for(m, WB, n, cus, h_b) > 1;
+  parts = parts || oneByOne;
+  const int share = oneByOne ? 1 : 2;
+  const int fused = parts ? -1 : wide_fill2(m, WF, WB, d_f, d_b, n, n, tape, dstF, dstB, g_stream, keepColumns);   // both sweeps in ONE launch
+  if (fused >= 0 || !s2) return fused;
+  // (programs of different kernel variants: two launches on two streams)
+  StreamFork fork;
+  if (!fork.ok) { set_error(forkError); return 1; }
+  int rc = wide_fill(m, WF, d_f, n, tape, dstF, nullptr, oneByOne ? g_stream : s2, keepColumns, parts ? h_f : nullptr, cus / share);
+  if (!rc) rc = wide_fill(m, WB, d_b, n, tape, dstB, nullptr, g_stream, keepColumns, parts ? h_b : nullptr, cus / share);
+  if (!fork.join()) { set_error(joinError); rc = 1; }
+  return rc;
+}
+
 // ---- Forward ------------------------------------------------------------------------------------------------
-static bool rolltiles_ok = true;      // (cleared while run_fill_loglike re-enters itself after the matrix-free tile kernel proved unavailable)
+// Each route below leaves the log-likelihoods of the batch in d_ll (device, nPairs entries); run_fill_loglike chooses.
+
+// One-tape machine, fewer sequences than half the CUs (one workgroup per sequence): every sequence is CUT IN TWO -- Forward over
+// the prefix and Backward over the suffix behind the cut run side by side, k_onetape_join sums over the emitting transitions that
+// cross the cut.  Same likelihood (a different summation order: ~1e-12 relative), half the sweep length.
+static int forward_onetape_split(mb_batch *b, WideProgram &W, double *d_ll) {
+  mb_machine *m = b->m;
+  WideProgram *WB = wide_program(m, MB_BACKWARD);
+  const long long n = b->nPairs, S = m->S;
+  std::vector<PairDesc> pre, suf;
+  auto cutAt = [&](double frac) {
+    pre = b->pairs; suf = b->pairs;
+    for (long long p = 0; p < n; ++p) {
+      const int L = m->nOut ? b->pairs[p].outLen : b->pairs[p].inLen, mid = std::min(L - 1, std::max(0, (int)(L * frac)));
+      pre[p].cellBase = suf[p].cellBase = p * S;
+      if (m->nOut) { pre[p].outLen = mid; suf[p].outBase += mid + 1; suf[p].outLen = L - mid - 1; }
+      else { pre[p].inLen = mid; suf[p].inBase += mid + 1; suf[p].inLen = L - mid - 1; }
+    }
+  };
+  cutAt(0.5);
+  // k workgroups per sequence: the two programs' parts are not equally fast (the Backward program of the 5 063-state machine takes 136 ms
+  // where the Forward one takes 120): the cut goes where both halves end together under the planner's model
+  if (WB) {
+    const double cF = wide_parts_cost(m, W, n, device_cus() / 2, pre.data()), cB = wide_parts_cost(m, *WB, n, device_cus() / 2, suf.data());
+    if (cF > 0.0 && cB > 0.0 && env_int("MB_ONETAPE_SPLIT_BALANCE", 1)) cutAt(std::min(0.65, std::max(0.35, cB / (cF + cB))));
+  }
+  if (!WB) return 1;
+  SmBuf<PairDesc> d_pre, d_suf;
+  if (!hip_ok(d_pre.alloc(n), "hipMalloc") || !hip_ok(d_suf.alloc(n), "hipMalloc")) return 1;
+  double *vec = (double *)ws_get(2, (size_t)(2 * n * S) * sizeof(double));
+  if (!vec) return 1;
+  if (!hip_ok(hipMemcpyAsync(d_pre, pre.data(), n * sizeof(PairDesc), hipMemcpyHostToDevice, g_stream), "H2D") ||
+      !hip_ok(hipMemcpyAsync(d_suf, suf.data(), n * sizeof(PairDesc), hipMemcpyHostToDevice, g_stream), "H2D") ||
+      !hip_ok(hipStreamSynchronize(g_stream), "H2D")) { quiesce_streams(); return 1; }   // (pre / suf are pageable host vectors)
+  int rc = timed([&] {
+    if (onetape_fill_pair(m, W, *WB, d_pre, d_suf, pre.data(), suf.data(), n, tape_of(b), vec, vec + n * S, true,
+                          "one-tape split: stream set-up failed", "one-tape split: stream synchronisation failed")) return 1;
+    return wide_join(m, d_pre, n, tape_of(b), vec, vec + n * S, d_ll, g_stream);
+  });
+  if (!rc) { static thread_local std::string nm; nm = std::string(wide_kernel_name(W)) + " x2 + k_onetape_join"; g_last_kernel = nm.c_str(); }
+  if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "one-tape forward kernels")) rc = 1;
+  if (!rc && wide_parts_failed()) rc = 1;
+  if (rc) quiesce_streams();      // (the halves may still read the descriptors freed on return)
+  return rc;
+}
+
+// one-tape machine, log-likelihood only: the two live columns of every sequence stay in LDS, nothing goes to HBM
+static int forward_onetape(mb_batch *b, double *d_ll) {
+  mb_machine *m = b->m;
+  WideProgram *W = wide_program(m, MB_FORWARD);
+  if (!W) return 1;
+  int minLen = 1 << 30;
+  for (const PairDesc &pd : b->pairs) minLen = std::min(minLen, m->nOut ? pd.outLen : pd.inLen);
+  if (env_int("MB_ONETAPE_SPLIT", 1) && 2 * b->nPairs <= device_cus() && minLen >= env_int("MB_ONETAPE_SPLIT_MIN_LEN", 64) && second_stream())
+    return forward_onetape_split(b, *W, d_ll);
+  int rc = timed([&] { return wide_fill(m, *W, b->d_pairs, b->nPairs, tape_of(b), nullptr, d_ll, g_stream, false, b->pairs.data(), device_cus()); });
+  g_last_kernel = wide_kernel_name(*W);
+  if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "one-tape forward kernel")) rc = 1;
+  if (!rc && wide_parts_failed()) rc = 1;
+  return rc;
+}
+
+// tiled family, log-likelihoods only, few pairs or envelopes: the tile pipeline WITHOUT a matrix (halo columns + boundary records).
+// Returns -1 when its kernel is unavailable: nothing was written, another route takes the call.
+static int forward_rolltiles(mb_batch *b, double *d_ll) {
+  FastState *f = fast_state(b->m);
+  std::vector<PairDesc> hp(b->pairs);
+  int rc = launch_fill_neg_inf(d_ll, b->nPairs, g_stream);
+  if (!rc) rc = timed([&] { return medium_forward_rolltiles(b->m, f->fwdSum, f->geoFS, b->d_pairs, hp, b->d_in, b->d_out, d_ll, g_stream, med_env(b)); });
+  if (rc < 0) return -1;
+  g_last_kernel = "k_medium_jit";
+  if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "rolling forward kernels")) rc = 1;
+  return rc;
+}
+
+// tiled family, RollingOutputForwardMatrix: no matrix in HBM, only two halo columns per pair.  It runs ONE workgroup per pair: with
+// fewer pairs than CUs the tile pipeline (which cuts every pair into hundreds of tiles and recycles matrix slots) fills the chip
+// better, and only the log-likelihoods are kept either way (psw2dna, 64 pairs: 229 vs 517 G cells/s) -- see fewPairs in the selector.
+static int forward_rolling_halo(mb_batch *b, double *d_ll) {
+  mb_machine *m = b->m;
+  FastState *f = fast_state(m);
+  std::vector<long long> hb(b->nPairs);
+  long long tot = 0;
+  for (long long p = 0; p < b->nPairs; ++p) { hb[p] = tot; tot += 2ll * (b->pairs[p].outLen + 1) * m->S; }
+  double *d_halo = (double *)ws_get(2, std::max<long long>(tot, 1) * sizeof(double));
+  if (!d_halo) return 1;
+  SmBuf<long long> d_hb;
+  if (!hip_ok(d_hb.alloc(b->nPairs), "hipMalloc")) return 1;
+  if (!hip_ok(hipMemcpyAsync(d_hb, hb.data(), b->nPairs * sizeof(long long), hipMemcpyHostToDevice, g_stream), "H2D")) return 1;
+  int rc = timed([&] { return medium_forward_rolling(m, f->fwdSum, f->geoFS, b->d_pairs, b->pairs, b->d_in, b->d_out, d_halo, d_hb, d_ll, g_stream); });
+  g_last_kernel = (medium_jit_ready(f->fwdSum, MB_FORWARD, MED_MAT_NONE) || medium_jit_ready(f->fwdSum, MB_FORWARD, MED_MAT_ROLL)) ? "k_medium_jit" : "k_medium_tile<0>";
+  if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "rolling forward kernel")) rc = 1;
+  return rc;
+}
+
+// tiled family, the matrices of the batch do not fit the device-memory budget together: ForwardMatrix semantics with only logLike()
+// kept -- a continuous pipeline over recycled matrix slots
+static int forward_pipelined(mb_batch *b, double *d_ll) {
+  mb_machine *m = b->m;
+  FastState *f = fast_state(m);
+  const size_t budget = budget_bytes();
+  const long long want = std::min<long long>(b->totalCells, (long long)(budget / 8));
+  double *pool = (double *)ws_get(0, (size_t)std::max<long long>(want, b->maxPairCells) * sizeof(double));
+  if (!pool) return 1;
+  const long long poolCells = (long long)(ws_bytes(0) / 8);
+  if (poolCells < b->maxPairCells) { set_error("a single DP matrix exceeds the device memory budget"); return 1; }
+  Timer tm;
+  Timed t(tm, 0);
+  int rc = medium_forward_pipelined(m, f->fwdSum, f->geoFS, b->pairs, b->d_in, b->d_out, pool, poolCells, d_ll, g_stream, !m->mediumPersistOff);
+  if (rc == 2) {      // a persistent strip waited longer than MB_MEDIUM_PERSIST_TIMEOUT_S: latched off for this machine, the call runs again launch by launch
+    m->mediumPersistOff = true;
+    fprintf(stderr, "[mbhip] WARNING: a persistent strip of the pipelined Forward waited longer than MB_MEDIUM_PERSIST_TIMEOUT_S for another strip (is the device shared?): the call is run again launch by launch, and so are this machine's later calls\n");
+    rc = medium_forward_pipelined(m, f->fwdSum, f->geoFS, b->pairs, b->d_in, b->d_out, pool, poolCells, d_ll, g_stream, false);
+  }
+  g_last_kernel = (medium_jit_ready(f->fwdSum, MB_FORWARD, MED_MAT_FULL) || medium_jit_ready(f->fwdSum, MB_FORWARD, MED_MAT_PERSIST)) ? "k_medium_jit" : "k_medium_tile<0>";
+  return rc;
+}
+
+// every other case: the matrices of a chunk materialised by fill_chunk, the end cells gathered
+static int forward_chunked(mb_batch *b, int mode, double *d_ll) {
+  std::vector<Chunk> chunks;
+  if (!plan_chunks(b, 1, chunks)) return 1;
+  return for_chunks<DescPlan>(chunks, desc_build(b), [&](const Chunk &c, DescPlan &pl, Timer &tm) {
+    double *pool = (double *)ws_get(0, std::max<long long>(c.cells, 1) * sizeof(double));
+    if (!pool) return 1;
+    {
+      Timed t(tm, 0);
+      if (const int rc = fill_chunk(b->m, mode, pl.d, pl.hp, b->d_in, b->d_out, pool, 0, b)) return rc;
+      if (const int rc = launch_gather_loglike(pl.d, c.p1 - c.p0, pool, b->m->S, 0, d_ll + c.p0, g_stream)) return rc;
+    }
+    if (!hip_ok(hipStreamSynchronize(g_stream), "fill kernel")) return 1;
+    return wide_parts_failed() ? 1 : 0;
+  });
+}
+
 static int run_fill_loglike(mb_batch *b, int mode, int flags, double *loglike) {
-  g_last_ms = 0.0; g_last_launches = 0;
-  g_last_kernel = "";
+  reset_last();
   if (b->nPairs == 0) return 0;
   mb_machine *m = b->m;
-  if (mode == MB_FORWARD && use_small(m) && small_can_run(((FastState *)m->fast)->smF, SM_SUM, !(flags & MB_ROLLING), b->hasEnv)) return small_forward(b, flags, loglike);
-  double *d_ll = nullptr;
-  MB_HIP(sm_alloc((void **)&d_ll, b->nPairs * sizeof(double)));
-  int rc = 0;
-  Timer tm;
-  // The rolling sweep runs ONE workgroup per pair: with fewer pairs than CUs the tile pipeline (which cuts every pair
-  // into hundreds of tiles and recycles matrix slots) fills the chip better, and only the log-likelihoods are kept
-  // either way (psw2dna, 64 pairs: 229 vs 517 G cells/s).
-  const bool fewPairs = b->nPairs < env_int("MB_ROLLING_MIN_PAIRS", 192) &&
-                        (size_t)b->maxPairCells * 8 * 2 <= budget_bytes();
-  if (mode == MB_FORWARD && !b->hasEnv && wide_applicable(m) && g_kernel_choice != 1 &&
-      ((flags & MB_ROLLING) || (size_t)b->totalCells * 8 > budget_bytes())) {
-    // one-tape machine, log-likelihood only: the two live columns of every sequence stay in LDS, nothing goes to HBM
-    WideProgram *W = wide_program(m, MB_FORWARD);
-    // Fewer sequences than half the CUs (one workgroup per sequence): every sequence is CUT IN TWO -- Forward over the prefix
-    // and Backward over the suffix behind the cut run side by side on two streams, k_onetape_join sums over the emitting
-    // transitions that cross the cut.  Same likelihood (a different summation order: ~1e-12 relative), half the sweep length.
-    int minLen = 1 << 30;
-    for (const PairDesc &pd : b->pairs) minLen = std::min(minLen, m->nOut ? pd.outLen : pd.inLen);
-    const bool split = W && env_int("MB_ONETAPE_SPLIT", 1) && 2 * b->nPairs <= device_cus() && minLen >= env_int("MB_ONETAPE_SPLIT_MIN_LEN", 64) && second_stream();
-    if (!W) rc = 1;
-    else if (split) {
-      WideProgram *WB = wide_program(m, MB_BACKWARD);
-      const long long n = b->nPairs, S = m->S;
-      std::vector<PairDesc> pre, suf;
-      auto cutAt = [&](double frac) {
-        pre = b->pairs; suf = b->pairs;
-        for (long long p = 0; p < n; ++p) {
-          const int L = m->nOut ? b->pairs[p].outLen : b->pairs[p].inLen, mid = std::min(L - 1, std::max(0, (int)(L * frac)));
-          pre[p].cellBase = suf[p].cellBase = p * S;
-          if (m->nOut) { pre[p].outLen = mid; suf[p].outBase += mid + 1; suf[p].outLen = L - mid - 1; }
-          else { pre[p].inLen = mid; suf[p].inBase += mid + 1; suf[p].inLen = L - mid - 1; }
-        }
-      };
-      cutAt(0.5);
-      // k workgroups per sequence: the two programs' parts are not equally fast (the Backward program of the 5 063-state machine takes 136 ms
-      // where the Forward one takes 120): the cut goes where both halves end together under the planner's model
-      if (WB) {
-        const double cF = wide_parts_cost(m, *W, n, device_cus() / 2, pre.data()), cB = wide_parts_cost(m, *WB, n, device_cus() / 2, suf.data());
-        if (cF > 0.0 && cB > 0.0 && env_int("MB_ONETAPE_SPLIT_BALANCE", 1)) cutAt(std::min(0.65, std::max(0.35, cB / (cF + cB))));
-      }
-      PairDesc *d_pre = nullptr, *d_suf = nullptr;
-      double *vec = nullptr;
-      hipEvent_t evStart = nullptr, evDone = nullptr;
-      do {
-        if (!WB) { rc = 1; break; }
-        if (!hip_ok(sm_alloc((void **)&d_pre, n * sizeof(PairDesc)), "hipMalloc") || !hip_ok(sm_alloc((void **)&d_suf, n * sizeof(PairDesc)), "hipMalloc")) { rc = 1; break; }
-        if (!(vec = (double *)ws_get(2, (size_t)(2 * n * S) * sizeof(double)))) { rc = 1; break; }
-        if (!hip_ok(hipMemcpyAsync(d_pre, pre.data(), n * sizeof(PairDesc), hipMemcpyHostToDevice, g_stream), "H2D") ||
-            !hip_ok(hipMemcpyAsync(d_suf, suf.data(), n * sizeof(PairDesc), hipMemcpyHostToDevice, g_stream), "H2D") ||
-            !hip_ok(hipStreamSynchronize(g_stream), "H2D")) { rc = 1; break; }   // (pre / suf are pageable host vectors)
-        const int *tape = m->nOut ? b->d_out : b->d_in;
-        hipStream_t s2 = second_stream();
-        tm.start();
-        if (hipEventCreateWithFlags(&evStart, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&evDone, hipEventDisableTiming) != hipSuccess ||
-            hipEventRecord(evStart, g_stream) != hipSuccess || hipStreamWaitEvent(s2, evStart, 0) != hipSuccess) { set_error("one-tape split: stream set-up failed"); rc = 1; break; }
-        // (with CUs to spare both halves run k workgroups per sequence, each launch on a stream of its own)
-        // (a machine whose ring lives in L2 and whose parts fit the LDS only when a sweep has the whole chip: one half after the other)
-        bool parts = wide_parts_for(m, *W, n, device_cus() / 2, pre.data()) > 1 && wide_parts_for(m, *WB, n, device_cus() / 2, suf.data()) > 1;
-        const bool oneByOne = !parts && (W->retGv || WB->retGv) && wide_parts_for(m, *W, n, device_cus(), pre.data()) > 1 && wide_parts_for(m, *WB, n, device_cus(), suf.data()) > 1;
-        parts = parts || oneByOne;
-        const int share = oneByOne ? 1 : 2;
-        const int fusedFill = parts ? -1 : wide_fill2(m, *W, *WB, d_pre, d_suf, n, n, tape, vec, vec + n * S, g_stream, true);   // both sweeps in ONE launch
-        if (fusedFill > 0) { rc = 1; break; }
-        if (fusedFill < 0) {                        // (programs of different kernel variants: two launches on two streams)
-          if ((rc = wide_fill(m, *W, d_pre, n, tape, vec, nullptr, oneByOne ? g_stream : s2, true, parts ? pre.data() : nullptr, device_cus() / share))) break;
-          if ((rc = wide_fill(m, *WB, d_suf, n, tape, vec + n * S, nullptr, g_stream, true, parts ? suf.data() : nullptr, device_cus() / share))) break;
-          if (hipEventRecord(evDone, s2) != hipSuccess || hipStreamWaitEvent(g_stream, evDone, 0) != hipSuccess) { set_error("one-tape split: stream synchronisation failed"); rc = 1; break; }
-        }
-        if ((rc = wide_join(m, d_pre, n, tape, vec, vec + n * S, d_ll, g_stream))) break;
-        { static thread_local std::string nm; nm = std::string(wide_kernel_name(*W)) + " x2 + k_onetape_join"; g_last_kernel = nm.c_str(); }
-        g_last_ms += tm.stop();
-        if (!hip_ok(hipStreamSynchronize(g_stream), "one-tape forward kernels")) rc = 1;
-        if (!rc && wide_parts_failed()) rc = 1;
-      } while (0);
-      if (rc) { (void)hipStreamSynchronize(g_stream); (void)hipStreamSynchronize(second_stream()); }
-      if (evStart) (void)hipEventDestroy(evStart);
-      if (evDone) (void)hipEventDestroy(evDone);
-      sm_free(d_pre); sm_free(d_suf);
-    } else {
-      tm.start();
-      rc = wide_fill(m, *W, b->d_pairs, b->nPairs, m->nOut ? b->d_out : b->d_in, nullptr, d_ll, g_stream, false, b->pairs.data(), device_cus());
-      g_last_kernel = wide_kernel_name(*W);
-      g_last_ms += tm.stop();
-      if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "one-tape forward kernel")) rc = 1;
-      if (!rc && wide_parts_failed()) rc = 1;
-    }
-  } else if (mode == MB_FORWARD && (flags & MB_ROLLING) && use_medium(m) && !wide_applicable(m) && env_int("MB_MEDIUM_ROLLTILES", 1) &&
-             (b->nPairs < env_int("MB_ROLLING_MIN_PAIRS", 192) || b->hasEnv) && rolltiles_ok) {
-    // log-likelihoods only, few pairs or envelopes: the tile pipeline WITHOUT a matrix (halo columns + boundary records)
-    FastState *f = fast_state(m);
-    MedEnv me;
-    if (b->hasEnv) { me.d_start = b->d_envStart; me.d_end = b->d_envEnd; me.h_start = b->h_envStart.data(); me.h_end = b->h_envEnd.data(); }
-    std::vector<PairDesc> hp(b->pairs);
-    rc = launch_fill_neg_inf(d_ll, b->nPairs, g_stream);
-    tm.start();
-    const int r2 = rc ? rc : medium_forward_rolltiles(m, f->fwdSum, f->geoFS, b->d_pairs, hp, b->d_in, b->d_out, d_ll, g_stream, me);
-    g_last_ms += tm.stop();
-    if (r2 < 0) { sm_free(d_ll); rolltiles_ok = false; const int r3 = run_fill_loglike(b, mode, flags, loglike); rolltiles_ok = true; return r3; }   // kernel unavailable: the other paths
-    rc = r2;
-    g_last_kernel = "k_medium_jit";
-    if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "rolling forward kernels")) rc = 1;
-  } else if (mode == MB_FORWARD && (flags & MB_ROLLING) && !fewPairs && !b->hasEnv && use_medium(m)) {
-    // RollingOutputForwardMatrix: no matrix in HBM, only two halo columns per pair
-    FastState *f = fast_state(m);
-    std::vector<long long> hb(b->nPairs);
-    long long tot = 0;
-    for (long long p = 0; p < b->nPairs; ++p) { hb[p] = tot; tot += 2ll * (b->pairs[p].outLen + 1) * m->S; }
-    double *d_halo = nullptr; long long *d_hb = nullptr;
-    do {
-      if (!(d_halo = (double *)ws_get(2, std::max<long long>(tot, 1) * sizeof(double)))) { rc = 1; break; }
-      if (!hip_ok(sm_alloc((void **)&d_hb, b->nPairs * sizeof(long long)), "hipMalloc")) { rc = 1; break; }
-      if (!hip_ok(hipMemcpyAsync(d_hb, hb.data(), b->nPairs * sizeof(long long), hipMemcpyHostToDevice, g_stream), "H2D")) { rc = 1; break; }
-      tm.start();
-      rc = medium_forward_rolling(m, f->fwdSum, f->geoFS, b->d_pairs, b->pairs, b->d_in, b->d_out, d_halo, d_hb, d_ll, g_stream);
-      g_last_kernel = (medium_jit_ready(f->fwdSum, MB_FORWARD, MED_MAT_NONE) || medium_jit_ready(f->fwdSum, MB_FORWARD, MED_MAT_ROLL)) ? "k_medium_jit" : "k_medium_tile<0>";
-      g_last_ms += tm.stop();
-      if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "rolling forward kernel")) rc = 1;
-    } while (0);
-    if (d_hb) sm_free(d_hb);
-  } else if (mode == MB_FORWARD && !b->hasEnv && use_medium(m) && env_int("MB_MEDIUM_PIPELINE", 1) &&
-             (size_t)b->totalCells * 8 > budget_bytes()) {
-    // the matrices of the batch do not fit the device-memory budget together:
-    // ForwardMatrix semantics with only logLike() kept: continuous pipeline over recycled matrix slots
-    FastState *f = fast_state(m);
-    const size_t budget = budget_bytes();
-    const long long want = std::min<long long>(b->totalCells, (long long)(budget / 8));
-    double *pool = (double *)ws_get(0, (size_t)std::max<long long>(want, b->maxPairCells) * sizeof(double));
-    if (!pool) rc = 1;
-    else if ((long long)(g_ws[0].bytes / 8) < b->maxPairCells) { set_error("a single DP matrix exceeds the device memory budget"); rc = 1; }
-    else {
-      tm.start();
-      rc = medium_forward_pipelined(m, f->fwdSum, f->geoFS, b->pairs, b->d_in, b->d_out, pool, (long long)(g_ws[0].bytes / 8), d_ll, g_stream, !m->mediumPersistOff);
-      if (rc == 2) {      // a persistent strip waited longer than MB_MEDIUM_PERSIST_TIMEOUT_S: latched off for this machine, the call runs again launch by launch
-        m->mediumPersistOff = true;
-        fprintf(stderr, "[mbhip] WARNING: a persistent strip of the pipelined Forward waited longer than MB_MEDIUM_PERSIST_TIMEOUT_S for another strip (is the device shared?): the call is run again launch by launch, and so are this machine's later calls\n");
-        rc = medium_forward_pipelined(m, f->fwdSum, f->geoFS, b->pairs, b->d_in, b->d_out, pool, (long long)(g_ws[0].bytes / 8), d_ll, g_stream, false);
-      }
-      g_last_kernel = (medium_jit_ready(f->fwdSum, MB_FORWARD, MED_MAT_FULL) || medium_jit_ready(f->fwdSum, MB_FORWARD, MED_MAT_PERSIST)) ? "k_medium_jit" : "k_medium_tile<0>";
-      g_last_ms += tm.stop();
-    }
-  } else {
-    std::vector<Chunk> chunks;
-    if (!plan_chunks(b, 1, chunks)) { sm_free(d_ll); return 1; }
-    for (const Chunk &c : chunks) {
-      PairDesc *d_desc = nullptr; double *pool = nullptr;
-      std::vector<PairDesc> hp;
-      if ((rc = upload_chunk_descs(b, c, &d_desc, hp))) break;
-      if (!(pool = (double *)ws_get(0, std::max<long long>(c.cells, 1) * sizeof(double)))) { sm_free(d_desc); rc = 1; break; }
-      tm.start();
-      rc = fill_chunk(m, mode, d_desc, hp, b->d_in, b->d_out, pool, 0, b);
-      if (!rc) rc = launch_gather_loglike(d_desc, c.p1 - c.p0, pool, m->S, 0, d_ll + c.p0, g_stream);
-      g_last_ms += tm.stop();
-      if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "fill kernel")) rc = 1;
-      if (!rc && wide_parts_failed()) rc = 1;
-      if (rc) quiesce_streams();      // (a kernel launched before the failure may still read the descriptors)
-      sm_free(d_desc);
-      if (rc) break;
-    }
+  const bool fwd = mode == MB_FORWARD, rolling = (flags & MB_ROLLING) != 0;
+  if (fwd && use_small(m) && small_can_run(((FastState *)m->fast)->smF, SM_SUM, !rolling, b->hasEnv)) return small_forward(b, flags, loglike);
+  SmBuf<double> d_ll;
+  MB_HIP(d_ll.alloc(b->nPairs));
+  const bool belowMinPairs = b->nPairs < env_int("MB_ROLLING_MIN_PAIRS", 192);
+  const bool fewPairs = belowMinPairs && (size_t)b->maxPairCells * 8 * 2 <= budget_bytes();
+  int rc = -1;      // (-1: no route has taken the call yet)
+  if (fwd && !b->hasEnv && wide_applicable(m) && g_kernel_choice != 1 && (rolling || (size_t)b->totalCells * 8 > budget_bytes()))
+    rc = forward_onetape(b, d_ll);
+  else if (fwd && rolling && use_medium(m) && !wide_applicable(m) && env_int("MB_MEDIUM_ROLLTILES", 1) && (belowMinPairs || b->hasEnv))
+    rc = forward_rolltiles(b, d_ll);      // -1: its kernel is unavailable -- the routes below take the call, from a clean slate
+  if (rc < 0) {
+    reset_last();
+    if (fwd && rolling && !fewPairs && !b->hasEnv && use_medium(m)) rc = forward_rolling_halo(b, d_ll);
+    else if (fwd && !b->hasEnv && use_medium(m) && env_int("MB_MEDIUM_PIPELINE", 1) && (size_t)b->totalCells * 8 > budget_bytes()) rc = forward_pipelined(b, d_ll);
+    else rc = forward_chunked(b, mode, d_ll);
   }
-  if (!rc && !hip_ok(hipMemcpy(loglike, d_ll, b->nPairs * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
-  sm_free(d_ll);
+  if (!rc) rc = fetch_loglike(loglike, d_ll, b->nPairs);
   return rc;
 }
 
@@ -1362,115 +1398,74 @@ int64_t mb_viterbi_path_bound(const mb_machine *m, int64_t inLen, int64_t outLen
   return (inLen + outLen + 1) * (int64_t)m->nLevF + 1;
 }
 
-// ViterbiMatrix over a batch on the tiled / generic families.  tb: ONE traceback byte per cell instead of the fp64 matrix (tiled
-// family, run-time specialised kernel; returns -1 before anything was written when that kernel is unavailable).
-// tb: 0 = fp64 Viterbi matrices, 1 = the tiled family's traceback bytes, 2 = the one-tape family's traceback codes
+// ViterbiMatrix over a batch on the tiled / generic / one-tape families.
+// tb: 0 = fp64 Viterbi matrices, 1 = the tiled family's traceback bytes (ONE byte per cell, run-time specialised kernel), 2 = the
+// one-tape family's traceback codes.  tb 1 / 2 return -1 before anything was written when their kernel is unavailable.
 static int viterbi_chunks(mb_batch *b, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int64_t pathCap, int tb) {
+  mb_machine *m = b->m;
   const bool wantPaths = pathEdges != nullptr && pathOff != nullptr;
-  const int Sb = tb == 2 ? wide_tb_stride(b->m->S) : medium_tb_stride(b->m->S);
+  const int Sb = tb == 2 ? wide_tb_stride(m->S) : medium_tb_stride(m->S);
   std::vector<Chunk> chunks;
-  if (!plan_chunks(b, 1, chunks, tb ? (double)Sb / b->m->S + 0.01 : 0.0)) return 1;
-  int rc = 0;
-  Timer tm;
-  long long written = 0;
-  const bool timing = opt_env("MB_TIMING") != nullptr;
-  auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t0 = now(), tPrev = t0;
-  auto lap = [&](const char *what) { if (timing) { const double t = now(); fprintf(stderr, "[mbhip] viterbi %-28s %7.2f ms\n", what, t - tPrev); tPrev = t; } };
-  for (const Chunk &c : chunks) {
+  if (!plan_chunks(b, 1, chunks, tb ? (double)Sb / m->S + 0.01 : 0.0)) return 1;
+  PathOut out{pathOff, pathEdges, pathCap};
+  Laps laps;
+  return for_chunks<DescPlan>(chunks, desc_build(b, tb ? Sb : 0), [&](const Chunk &c, DescPlan &pl, Timer &tm) {
     const long long np = c.p1 - c.p0;
-    PairDesc *d_desc = nullptr; double *pool = nullptr, *d_ll = nullptr;
-    long long *d_slot = nullptr, *d_len = nullptr; uint32_t *d_path = nullptr;
-    std::vector<long long> slot(np + 1, 0), len(np, 0);
-    std::vector<double> hll(np);
-    std::vector<PairDesc> hp;
-    do {
-      if ((rc = upload_chunk_descs(b, c, &d_desc, hp, tb ? Sb : 0))) break;
-      if (!(pool = (double *)ws_get(0, tb ? (size_t)std::max<long long>(c.cells / b->m->S * Sb, 16) : std::max<long long>(c.cells, 1) * sizeof(double)))) { rc = 1; break; }
-      if (!hip_ok(sm_alloc((void **)&d_ll, np * sizeof(double)), "hipMalloc")) { rc = 1; break; }
-      lap("chunk set-up");
-      tm.start();
+    const std::vector<PairDesc> &hp = pl.hp;
+    const PairDesc *d_desc = pl.d;
+    double *pool = (double *)ws_get(0, tb ? (size_t)std::max<long long>(c.cells / m->S * Sb, 16) : std::max<long long>(c.cells, 1) * sizeof(double));
+    if (!pool) return 1;
+    const unsigned char *bytes = (const unsigned char *)pool;      // (tb: the pool holds traceback bytes / codes)
+    SmBuf<double> d_ll;
+    if (!hip_ok(d_ll.alloc(np), "hipMalloc")) return 1;
+    laps.lap("chunk set-up");
+    PathSlots ps;
+    {
+      Timed t(tm, 0);
       if (tb == 2) {
-        WideProgram *W = wide_tb_program(b->m);
-        if (!W) { rc = c.p0 > 0 ? 1 : -1; if (rc > 0) set_error("one-tape traceback-code program became unavailable mid-batch"); break; }
-        if ((rc = wide_fill_tb(b->m, *W, d_desc, np, b->m->nOut ? b->d_out : b->d_in, (unsigned char *)pool, d_ll, g_stream, hp.data(), device_cus()))) break;
+        WideProgram *W = wide_tb_program(m);
+        if (!W && c.p0 == 0) return -1;
+        if (!W) { set_error("one-tape traceback-code program became unavailable mid-batch"); return 1; }
+        if (const int rc = wide_fill_tb(m, *W, d_desc, np, tape_of(b), (unsigned char *)pool, d_ll, g_stream, hp.data(), device_cus())) return rc;
         g_last_kernel = wide_kernel_name(*W);      // (the generated kernel or the interpreter, one workgroup or k: asked after the launch)
       } else if (tb) {
-        MedEnv me;
-        if (b->hasEnv) { me.d_start = b->d_envStart; me.d_end = b->d_envEnd; me.h_start = b->h_envStart.data(); me.h_end = b->h_envEnd.data(); }
-        if ((rc = launch_fill_neg_inf(d_ll, np, g_stream))) break;   // (a pair whose end cell lies in a tile that does not run)
+        if (const int rc = launch_fill_neg_inf(d_ll, np, g_stream)) return rc;   // (a pair whose end cell lies in a tile that does not run)
         MedGeom *tbGeo = nullptr;
-        MedProgram *tbP = medium_tb_program(b->m, &tbGeo);
-        rc = tbP ? medium_viterbi_tb(b->m, *tbP, *tbGeo, d_desc, hp, b->d_in, b->d_out, (unsigned char *)pool, d_ll, g_stream, me) : -1;
+        MedProgram *tbP = medium_tb_program(m, &tbGeo);
+        int rc = tbP ? medium_viterbi_tb(m, *tbP, *tbGeo, d_desc, hp, b->d_in, b->d_out, (unsigned char *)pool, d_ll, g_stream, med_env(b)) : -1;
         if (rc < 0 && c.p0 > 0) { set_error("traceback-byte Viterbi kernel became unavailable mid-batch"); rc = 1; }
-        if (rc) break;
+        if (rc) return rc;
         g_last_kernel = "k_medium_jit";
       } else {
-        if ((rc = fill_chunk(b->m, MB_VITERBI, d_desc, hp, b->d_in, b->d_out, pool, 0, b))) break;
-        if ((rc = launch_gather_loglike(d_desc, np, pool, b->m->S, 0, d_ll, g_stream))) break;
+        if (const int rc = fill_chunk(m, MB_VITERBI, d_desc, hp, b->d_in, b->d_out, pool, 0, b)) return rc;
+        if (const int rc = launch_gather_loglike(d_desc, np, pool, m->S, 0, d_ll, g_stream)) return rc;
       }
       if (wantPaths) {
-        for (long long p = 0; p < np; ++p)
-          slot[p + 1] = slot[p] + mb_viterbi_path_bound(b->m, b->pairs[c.p0 + p].inLen, b->pairs[c.p0 + p].outLen);
-        // cached workspaces: a hipMalloc/hipFree pair per call costs more than the traceback kernel of a small batch
-        if (!(d_slot = (long long *)ws_get(3, (np + 1) * sizeof(long long)))) { rc = 1; break; }
-        if (!(d_len = (long long *)ws_get(4, np * sizeof(long long)))) { rc = 1; break; }
-        if (!(d_path = (uint32_t *)ws_get(5, std::max<long long>(slot[np], 1) * sizeof(uint32_t)))) { rc = 1; break; }
-        if (!hip_ok(hipMemcpyAsync(d_slot, slot.data(), (np + 1) * sizeof(long long), hipMemcpyHostToDevice, g_stream), "H2D")) { rc = 1; break; }
-        if (tb == 2) { if ((rc = wide_traceback_codes(b->m, *wide_tb_program(b->m), d_desc, np, (const unsigned char *)pool, d_ll, d_slot, d_path, d_len, g_stream))) break; }
-        else if (tb) { if ((rc = launch_traceback_bytes(b->m, d_desc, np, b->d_in, b->d_out, (const unsigned char *)pool, Sb, d_ll, d_slot, d_path, d_len, g_stream))) break; }
+        if (path_slots(b, c, ps)) return 1;
+        int rc;
+        if (tb == 2) rc = wide_traceback_codes(m, *wide_tb_program(m), d_desc, np, bytes, d_ll, ps.d_slot, ps.d_path, ps.d_len, g_stream);
+        else if (tb) rc = launch_traceback_bytes(m, d_desc, np, b->d_in, b->d_out, bytes, Sb, d_ll, ps.d_slot, ps.d_path, ps.d_len, g_stream);
         else {
           // one-tape machines beyond the LDS edge tables of the generic walkers: columns in LDS, one trip to memory per step
           WideTbPlan *T = nullptr;
-          if (wide_applicable(b->m) && g_kernel_choice != 1 && b->m->nTrans > env_int("MB_ONETAPE_TRACEBACK_MIN_TRANS", 3584) && !b->hasEnv) {
-            FastState *f = fast_state(b->m);
-            if (!f->wTb.tried) (void)wide_traceback_build(b->m, f->wTb);
+          if (wide_applicable(m) && g_kernel_choice != 1 && m->nTrans > env_int("MB_ONETAPE_TRACEBACK_MIN_TRANS", 3584) && !b->hasEnv) {
+            FastState *f = fast_state(m);
+            if (!f->wTb.tried) (void)wide_traceback_build(m, f->wTb);
             if (f->wTb.ok) T = &f->wTb;
           }
-          if (T) { if ((rc = wide_traceback(b->m, *T, d_desc, np, b->m->nOut ? b->d_out : b->d_in, pool, d_slot, d_path, d_len, g_stream))) break; }
-          else if ((rc = launch_traceback(b->m, d_desc, np, b->d_in, b->d_out, pool, d_slot, d_path, d_len, g_stream))) break;
+          rc = T ? wide_traceback(m, *T, d_desc, np, tape_of(b), pool, ps.d_slot, ps.d_path, ps.d_len, g_stream)
+                 : launch_traceback(m, d_desc, np, b->d_in, b->d_out, pool, ps.d_slot, ps.d_path, ps.d_len, g_stream);
         }
+        if (rc) return rc;
       }
-      lap("launches (host side)");
-      g_last_ms += tm.stop();
-      if (!hip_ok(hipStreamSynchronize(g_stream), "viterbi kernels")) { rc = 1; break; }
-      if (wide_parts_failed()) { rc = 1; break; }
-      lap("kernels");
-      if (!hip_ok(hipMemcpy(hll.data(), d_ll, np * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) { rc = 1; break; }
-      std::memcpy(loglike + c.p0, hll.data(), np * sizeof(double));
-      if (wantPaths) {
-        if (!hip_ok(hipMemcpy(len.data(), d_len, np * sizeof(long long), hipMemcpyDeviceToHost), "D2H path lengths")) { rc = 1; break; }
-        std::vector<long long> off(np, -1);
-        long long total = 0;
-        for (long long p = 0; p < np && !rc; ++p) {
-          const long long n = len[p];
-          if (n == -1) continue;   // -inf end cell: no path (src/dpmatrix.defs.h:84)
-          if (n < 0) { set_error(n == -2 ? "Viterbi traceback exceeded its path bound" : "Viterbi traceback reached a dead end"); rc = 1; break; }
-          off[p] = total; total += n;
-        }
-        if (rc) break;
-        if (written + total > pathCap) { set_error("pathCap too small for the Viterbi paths of this batch"); rc = 1; break; }
-        // packed on the device, then ONE copy of exactly the used bytes into the caller's array (the slots are sized for
-        // the worst case, (inLen+outLen+1) x levels edges per pair: 32 MB for 1024 x 1 kb x 1 kb dnapsw pairs, 15 MB used)
-        long long *d_off = (long long *)ws_get(6, np * sizeof(long long));
-        uint32_t *d_packed = (uint32_t *)ws_get(7, std::max<long long>(total, 1) * sizeof(uint32_t));
-        if (!d_off || !d_packed) { rc = 1; break; }
-        if (!hip_ok(hipMemcpyAsync(d_off, off.data(), np * sizeof(long long), hipMemcpyHostToDevice, g_stream), "H2D")) { rc = 1; break; }
-        if ((rc = launch_compact_paths(d_path, d_slot, d_len, d_off, d_packed, np, g_stream))) break;
-        if (total && d2h_large(pathEdges + written, d_packed, total * sizeof(uint32_t))) { rc = 1; break; }
-        if (!hip_ok(hipStreamSynchronize(g_stream), "path compaction")) { rc = 1; break; }
-        lap("pack + D2H paths");
-        for (long long p = 0; p < np; ++p) {
-          if (len[p] > 0) written += len[p];
-          pathOff[c.p0 + p + 1] = written;
-        }
-      }
-    } while (0);
-    void *ptrs[] = {d_desc, d_ll};
-    for (void *q : ptrs) sm_free(q);
-    if (rc) break;
-  }
-  return rc;
+      laps.lap("launches (host side)");
+    }
+    if (!hip_ok(hipStreamSynchronize(g_stream), "viterbi kernels")) return 1;
+    if (wide_parts_failed()) return 1;
+    laps.lap("kernels");
+    if (fetch_loglike(loglike + c.p0, d_ll, np)) return 1;
+    return wantPaths ? pack_paths(out, c, ps, PATH_OVERFLOW, PATH_DEAD_END, laps) : 0;
+  });
 }
 
 static int batch_viterbi(mb_batch *b, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int64_t pathCap);
@@ -1480,8 +1475,7 @@ int mb_batch_viterbi(mb_batch *b, double *loglike, int64_t *pathOff, uint32_t *p
   return with_parts_retry([&] { return batch_viterbi(b, loglike, pathOff, pathEdges, pathCap); });
 }
 static int batch_viterbi(mb_batch *b, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int64_t pathCap) {
-  g_last_ms = 0.0; g_last_launches = 0;
-  g_last_kernel = "";
+  reset_last();
   if (pathOff) pathOff[0] = 0;
   if (b->nPairs == 0) return 0;
   if (use_small(b->m) && small_can_run(((FastState *)b->m->fast)->smF, SM_TB, false, b->hasEnv)) return small_viterbi(b, loglike, pathOff, pathEdges, pathCap);
@@ -1491,7 +1485,7 @@ static int batch_viterbi(mb_batch *b, double *loglike, int64_t *pathOff, uint32_
       traceback_bytes_lds(b->m, medium_tb_stride(b->m->S))) {
     const int rc = viterbi_chunks(b, loglike, pathOff, pathEdges, pathCap, 1);
     if (rc >= 0) return rc;
-    g_last_ms = 0.0; g_last_launches = 0;
+    reset_last();
     if (pathOff) pathOff[0] = 0;
   }
   // one-tape family: one traceback code per cell when paths are wanted (a fill without paths keeps the leaner fp64 sweep).
@@ -1505,153 +1499,108 @@ static int batch_viterbi(mb_batch *b, double *loglike, int64_t *pathOff, uint32_
   if (pathEdges && pathOff && !b->hasEnv && tbWanted && wide_tb_program(b->m)) {
     const int rc = viterbi_chunks(b, loglike, pathOff, pathEdges, pathCap, 2);
     if (rc >= 0) return rc;
-    g_last_ms = 0.0; g_last_launches = 0;
+    reset_last();
     pathOff[0] = 0;
   }
   return viterbi_chunks(b, loglike, pathOff, pathEdges, pathCap, 0);
 }
 
 // ---- Forward-Backward counts --------------------------------------------------------------------------------
+// One-tape E-step over LONG sequences: the fills carry their log-sum-exp correction term in fp64 (mb_wide.hip, wide_exp64): the
+// fp32 term's per-column error repeats in stationary states and grows linearly with the length (7.6e-5 per transition at 50 000
+// columns).  MB_ONETAPE_COUNT_FP64: 1 always, 0 never, default: sequences of >= MB_ONETAPE_COUNT_FP64_MIN_LEN (10 000) symbols.
+struct AccurateFills { bool on; explicit AccurateFills(bool o) : on(o) { if (on) wide_set_accurate(true); } ~AccurateFills() { if (on) wide_set_accurate(false); } };
+static bool accurate_fills_wanted(const mb_machine *m, const std::vector<PairDesc> &hp) {
+  int longest = 0;
+  for (const PairDesc &pd : hp) longest = std::max(longest, std::max(pd.inLen, pd.outLen));
+  const int accMode = env_int("MB_ONETAPE_COUNT_FP64", -1);
+  return wide_applicable(m) && (accMode == 1 || (accMode != 0 && longest >= env_int("MB_ONETAPE_COUNT_FP64_MIN_LEN", 10000)));
+}
+
 // roll: the tiled family's count sweep WITHOUT a Forward matrix (medium_counts_rolling) -- one matrix per pair instead of two,
 // so twice the pairs per chunk; returns -1 before anything was accumulated when that kernel is unavailable
 // usage3: both matrices materialised by the plain fills, then the dependency-free usage pass of mb_usage.hip (tiled family)
 static int counts_chunks(mb_batch *b, double *counts, double *loglikeSum, double *loglike, bool roll, bool usage3 = false) {
-  const long long nT = b->m->nTrans;
+  mb_machine *m = b->m;
+  const long long nT = m->nTrans;
   std::vector<Chunk> chunks;
   if (!plan_chunks(b, roll ? 1 : 2, chunks)) return 1;
-  double *d_counts = nullptr, *d_ll = nullptr;
-  if (!hip_ok(sm_alloc((void **)&d_counts, std::max<long long>(nT, 1) * sizeof(double)), "hipMalloc(counts)")) return 1;
-  if (!hip_ok(sm_alloc((void **)&d_ll, b->nPairs * sizeof(double)), "hipMalloc(loglike)") ||
-      !hip_ok(hipMemsetAsync(d_counts, 0, std::max<long long>(nT, 1) * sizeof(double), g_stream), "memset(counts)")) {
-    sm_free(d_counts); sm_free(d_ll);
-    return 1;
-  }
-  int rc = 0;
-  Timer tm;
-  for (const Chunk &c : chunks) {
+  SmBuf<double> d_counts, d_ll;
+  if (!hip_ok(d_counts.alloc(nT), "hipMalloc(counts)")) return 1;
+  if (!hip_ok(d_ll.alloc(b->nPairs), "hipMalloc(loglike)") ||
+      !hip_ok(hipMemsetAsync(d_counts, 0, std::max<long long>(nT, 1) * sizeof(double), g_stream), "memset(counts)")) return 1;
+  const int rc = for_chunks<DescPlan>(chunks, desc_build(b), [&](const Chunk &c, DescPlan &pl, Timer &tm) {
     const long long np = c.p1 - c.p0;
-    PairDesc *d_desc = nullptr; double *fwd = nullptr, *bwd = nullptr;
-    std::vector<PairDesc> hp;
-    do {
-      if ((rc = upload_chunk_descs(b, c, &d_desc, hp))) break;
-      { const size_t need = (size_t)std::max<long long>(c.cells, 1) * sizeof(double); const int sl[2] = {1, 0}; const size_t nb[2] = {need, need}; ws_plan(roll ? 1 : 2, sl, nb); }
-      if (!roll && !(fwd = (double *)ws_get(0, std::max<long long>(c.cells, 1) * sizeof(double)))) { rc = 1; break; }
-      if (!(bwd = (double *)ws_get(1, std::max<long long>(c.cells, 1) * sizeof(double)))) { rc = 1; break; }
-      long long maxc = 0;
-      for (long long p = c.p0; p < c.p1; ++p)
-        maxc = std::max(maxc, (long long)(b->pairs[p].inLen + 1) * (b->pairs[p].outLen + 1) * b->m->S);
-      tm.start();
+    const std::vector<PairDesc> &hp = pl.hp;
+    const PairDesc *d_desc = pl.d;
+    double *fwd = nullptr, *bwd = nullptr;
+    { const size_t need = (size_t)std::max<long long>(c.cells, 1) * sizeof(double); const int sl[2] = {1, 0}; const size_t nb[2] = {need, need}; ws_plan(roll ? 1 : 2, sl, nb); }
+    if (!roll && !(fwd = (double *)ws_get(0, std::max<long long>(c.cells, 1) * sizeof(double)))) return 1;
+    if (!(bwd = (double *)ws_get(1, std::max<long long>(c.cells, 1) * sizeof(double)))) return 1;
+    long long maxc = 0;
+    for (long long p = c.p0; p < c.p1; ++p)
+      maxc = std::max(maxc, (long long)(b->pairs[p].inLen + 1) * (b->pairs[p].outLen + 1) * m->S);
+    {
+      Timed t(tm, 0);
+      const AccurateFills accurateFills(accurate_fills_wanted(m, hp));
       // One-tape machine (one workgroup per sequence): the Backward and the Forward fill are independent and a batch of fewer
-      // sequences than CUs leaves most of the chip idle, so the two run side by side on two streams (64 sequences: 64 + 64
-      // CUs); the count kernel waits for both.
+      // sequences than CUs leaves most of the chip idle, so the two run side by side (64 sequences: 64 + 64 CUs); the count kernel
+      // waits for both.  Without a second stream, programs that share no kernel are filled one after the other below.
       bool fwdDone = false;
-      // One-tape E-step over LONG sequences: the fills carry their log-sum-exp correction term in fp64 (mb_wide.hip, wide_exp64): the
-      // fp32 term's per-column error repeats in stationary states and grows linearly with the length (7.6e-5 per transition at 50 000
-      // columns).  MB_ONETAPE_COUNT_FP64: 1 always, 0 never, default: sequences of >= MB_ONETAPE_COUNT_FP64_MIN_LEN (10 000) symbols.
-      struct AccurateFills { bool on; explicit AccurateFills(bool o) : on(o) { if (on) wide_set_accurate(true); } ~AccurateFills() { if (on) wide_set_accurate(false); } };
-      int longest = 0;
-      for (const PairDesc &pd : hp) longest = std::max(longest, std::max(pd.inLen, pd.outLen));
-      const int accMode = env_int("MB_ONETAPE_COUNT_FP64", -1);
-      const AccurateFills accurateFills(wide_applicable(b->m) && (accMode == 1 || (accMode != 0 && longest >= env_int("MB_ONETAPE_COUNT_FP64_MIN_LEN", 10000))));
-      if (!roll && !b->hasEnv && wide_applicable(b->m) && g_kernel_choice != 1 && env_int("MB_ONETAPE_CONCURRENT_FILLS", 1)) {
-        WideProgram *WB = wide_program(b->m, MB_BACKWARD), *WF = wide_program(b->m, MB_FORWARD);
-        hipStream_t s2 = second_stream();
-        if (!WB || !WF) { rc = 1; break; }
-        // (with CUs to spare each fill runs k workgroups per sequence, on a stream of its own)
-        // (a machine whose ring lives in L2 and whose parts fit the LDS only when a fill has the whole chip: one fill after the other)
-        bool parts = s2 && wide_parts_for(b->m, *WF, np, device_cus() / 2, hp.data()) > 1 && wide_parts_for(b->m, *WB, np, device_cus() / 2, hp.data()) > 1;
-        const bool oneByOne = s2 && !parts && (WF->retGv || WB->retGv) && wide_parts_for(b->m, *WF, np, device_cus(), hp.data()) > 1 && wide_parts_for(b->m, *WB, np, device_cus(), hp.data()) > 1;
-        parts = parts || oneByOne;
-        const int share = oneByOne ? 1 : 2;
-        const int fusedFill = parts ? -1 : wide_fill2(b->m, *WF, *WB, d_desc, d_desc, np, np, b->m->nOut ? b->d_out : b->d_in, fwd, bwd, g_stream, false);   // both sweeps in ONE launch
-        if (fusedFill > 0) { rc = 1; break; }
-        if (fusedFill == 0) { fwdDone = true; g_last_kernel = wide_kernel_name(*WF); }
-        else if (s2) {                              // (programs of different kernel variants: two launches on two streams)
-          const int *tape = b->m->nOut ? b->d_out : b->d_in;
-          hipEvent_t evStart = nullptr, evDone = nullptr;
-          bool ok = hipEventCreateWithFlags(&evStart, hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&evDone, hipEventDisableTiming) == hipSuccess;
-          ok = ok && hipEventRecord(evStart, g_stream) == hipSuccess && hipStreamWaitEvent(s2, evStart, 0) == hipSuccess;   // s2 starts after what g_stream has queued (descriptors)
-          if (ok) {
-            rc = wide_fill(b->m, *WF, d_desc, np, tape, fwd, nullptr, oneByOne ? g_stream : s2, false, parts ? hp.data() : nullptr, device_cus() / share);
-            if (!rc) rc = wide_fill(b->m, *WB, d_desc, np, tape, bwd, nullptr, g_stream, false, parts ? hp.data() : nullptr, device_cus() / share);
-            ok = hipEventRecord(evDone, s2) == hipSuccess && hipStreamWaitEvent(g_stream, evDone, 0) == hipSuccess;
-          }
-          if (evStart) (void)hipEventDestroy(evStart);
-          if (evDone) (void)hipEventDestroy(evDone);
-          if (!ok) { set_error("one-tape counts: stream synchronisation failed"); rc = 1; }
-          if (rc) break;
-          fwdDone = true;
-          g_last_kernel = wide_kernel_name(*WF);
-        }
+      if (!roll && !b->hasEnv && wide_applicable(m) && g_kernel_choice != 1 && env_int("MB_ONETAPE_CONCURRENT_FILLS", 1)) {
+        WideProgram *WB = wide_program(m, MB_BACKWARD), *WF = wide_program(m, MB_FORWARD);
+        if (!WB || !WF) return 1;
+        const int rc = onetape_fill_pair(m, *WF, *WB, d_desc, d_desc, hp.data(), hp.data(), np, tape_of(b), fwd, bwd, false,
+                                         "one-tape counts: stream synchronisation failed", "one-tape counts: stream synchronisation failed");
+        if (rc > 0) return rc;
+        if (rc == 0) { fwdDone = true; g_last_kernel = wide_kernel_name(*WF); }
       }
-      if (!fwdDone && (rc = fill_chunk(b->m, MB_BACKWARD, d_desc, hp, b->d_in, b->d_out, bwd, 0, b))) break;
+      if (!fwdDone) if (const int rc = fill_chunk(m, MB_BACKWARD, d_desc, hp, b->d_in, b->d_out, bwd, 0, b)) return rc;
       // fused path: the Forward sweep accumulates the counts while its anti-diagonals are still in LDS
       int fused = -1;
       if (roll) {
-        FastState *f = fast_state(b->m);
-        MedEnv me;
-        if (b->hasEnv) { me.d_start = b->d_envStart; me.d_end = b->d_envEnd; me.h_start = b->h_envStart.data(); me.h_end = b->h_envEnd.data(); }
-        if ((rc = launch_fill_neg_inf(d_ll + c.p0, np, g_stream))) break;   // (a pair whose end cell lies in a tile that does not run)
-        fused = medium_counts_rolling(b->m, f->fwdCnt, f->geoCnt, d_desc, hp, b->d_in, b->d_out, bwd, d_counts, d_ll + c.p0, g_stream, me);
-        if (fused < 0 && c.p0 == 0) { rc = -1; break; }      // kernel unavailable: the caller runs the two-matrix path
-        if (fused) { if (fused < 0) set_error("count sweep kernel became unavailable mid-batch"); rc = 1; break; }
+        FastState *f = fast_state(m);
+        if (const int rc = launch_fill_neg_inf(d_ll + c.p0, np, g_stream)) return rc;   // (a pair whose end cell lies in a tile that does not run)
+        fused = medium_counts_rolling(m, f->fwdCnt, f->geoCnt, d_desc, hp, b->d_in, b->d_out, bwd, d_counts, d_ll + c.p0, g_stream, med_env(b));
+        if (fused < 0 && c.p0 == 0) return -1;      // kernel unavailable: the caller runs the two-matrix path
+        if (fused) { if (fused < 0) set_error("count sweep kernel became unavailable mid-batch"); return 1; }
         g_last_kernel = "k_medium_jit";
       } else if (usage3) {
         // (fused stays -1: Forward fill, log-likelihoods, then the usage pass below)
-      } else if (use_medium(b->m) && fast_state(b->m)->countOk && !(b->hasEnv && wide_applicable(b->m))) {
-        FastState *f = fast_state(b->m);
-        MedEnv me;
-        if (b->hasEnv) {
-          me.d_start = b->d_envStart; me.d_end = b->d_envEnd; me.h_start = b->h_envStart.data(); me.h_end = b->h_envEnd.data();
-          if ((rc = launch_fill_neg_inf(fwd, c.cells, g_stream))) break;      // tiles outside the envelopes do not run
-        }
-        fused = medium_counts_materialised(b->m, f->fwdCnt, f->geoCnt, d_desc, hp, b->d_in, b->d_out, fwd, bwd, d_counts, d_ll + c.p0, g_stream, me);
-        if (fused > 0) { rc = 1; break; }
+      } else if (use_medium(m) && fast_state(m)->countOk && !(b->hasEnv && wide_applicable(m))) {
+        FastState *f = fast_state(m);
+        if (b->hasEnv) if (const int rc = launch_fill_neg_inf(fwd, c.cells, g_stream)) return rc;      // tiles outside the envelopes do not run
+        fused = medium_counts_materialised(m, f->fwdCnt, f->geoCnt, d_desc, hp, b->d_in, b->d_out, fwd, bwd, d_counts, d_ll + c.p0, g_stream, med_env(b));
+        if (fused > 0) return 1;
         if (fused == 0) g_last_kernel = "k_medium_jit";
       }
       if (fused < 0) {
-        if (!fwdDone && (rc = fill_chunk(b->m, MB_FORWARD, d_desc, hp, b->d_in, b->d_out, fwd, 0, b))) break;
-        if ((rc = launch_gather_loglike(d_desc, np, fwd, b->m->S, 0, d_ll + c.p0, g_stream))) break;
+        if (!fwdDone) if (const int rc = fill_chunk(m, MB_FORWARD, d_desc, hp, b->d_in, b->d_out, fwd, 0, b)) return rc;
+        if (const int rc = launch_gather_loglike(d_desc, np, fwd, m->S, 0, d_ll + c.p0, g_stream)) return rc;
         // one-tape machines: a lane owns a transition and walks the columns (mb_wide.hip); two tapes: one thread per cell
-        const bool oneTape = ((b->m->nIn != 0) != (b->m->nOut != 0)) && g_kernel_choice != 1 && env_int("MB_ONETAPE_COUNTS", 1);
+        const bool oneTape = ((m->nIn != 0) != (m->nOut != 0)) && g_kernel_choice != 1 && env_int("MB_ONETAPE_COUNTS", 1);
+        int rc;
         if (usage3) {
-          if ((rc = usage_launch(b->m, fast_state(b->m)->usage, d_desc, hp, b->d_in, b->d_out, fwd, bwd, d_counts, g_stream))) break;
-          g_last_kernel = "k_medium_jit (two fills) + k_medium_usage";
+          rc = usage_launch(m, fast_state(m)->usage, d_desc, hp, b->d_in, b->d_out, fwd, bwd, d_counts, g_stream);
+          if (!rc) g_last_kernel = "k_medium_jit (two fills) + k_medium_usage";
         } else if (oneTape) {
-          FastState *f = fast_state(b->m);
-          if (!f->wCnt.ok && !wide_counts_build(b->m, f->wCnt)) { rc = 1; break; }
-          if ((rc = wide_counts(b->m, f->wCnt, d_desc, hp, b->m->nOut ? b->d_out : b->d_in, fwd, bwd, d_counts, g_stream))) break;
-          g_last_kernel = "k_onetape_counts";
-        } else if ((rc = launch_generic_counts(b->m, d_desc, np, maxc, b->d_in, b->d_out, fwd, bwd, d_counts, g_stream))) break;
+          FastState *f = fast_state(m);
+          if (!f->wCnt.ok && !wide_counts_build(m, f->wCnt)) return 1;
+          rc = wide_counts(m, f->wCnt, d_desc, hp, tape_of(b), fwd, bwd, d_counts, g_stream);
+          if (!rc) g_last_kernel = "k_onetape_counts";
+        } else rc = launch_generic_counts(m, d_desc, np, maxc, b->d_in, b->d_out, fwd, bwd, d_counts, g_stream);
+        if (rc) return rc;
       }
-      g_last_ms += tm.stop();
-      if (!hip_ok(hipStreamSynchronize(g_stream), "counts kernels")) { rc = 1; break; }
-      if (wide_parts_failed()) { rc = 1; break; }
-    } while (0);
-    if (rc) quiesce_streams();      // (the sweep on the second stream may still read the descriptors freed below)
-    sm_free(d_desc);
-    if (rc) break;
-  }
-  if (rc < 0) { (void)hipStreamSynchronize(g_stream); sm_free(d_counts); sm_free(d_ll); return -1; }
-  if (!rc) {
-    std::vector<double> hc(nT), hll(b->nPairs);
-    if (nT && !hip_ok(hipMemcpy(hc.data(), d_counts, nT * sizeof(double), hipMemcpyDeviceToHost), "D2H counts")) rc = 1;
-    if (!rc && !hip_ok(hipMemcpy(hll.data(), d_ll, b->nPairs * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) rc = 1;
-    if (!rc) {
-      if (g_deterministic)
-        for (long long e = 0; e < nT && !rc; ++e) {      // fixed point, 2^-36
-          unsigned long long u; std::memcpy(&u, &hc[e], 8);
-          if (!det_to_double(u, hc[e])) { set_error("MB_DETERMINISTIC: a posterior count left the fixed-point range (6.7e7 per transition and call): split the batch or use the floating-point mode"); rc = 1; }
-        }
-      if (rc) { sm_free(d_counts); sm_free(d_ll); return 1; }
-      for (long long e = 0; e < nT; ++e) counts[e] += hc[e];
-      double s = 0;
-      for (long long p = 0; p < b->nPairs; ++p) { s += hll[p]; if (loglike) loglike[p] = hll[p]; }  // loglike += forward.logLike()
-      if (loglikeSum) *loglikeSum += s;
     }
-  }
-  sm_free(d_counts); sm_free(d_ll);
-  return rc;
+    if (!hip_ok(hipStreamSynchronize(g_stream), "counts kernels")) return 1;
+    return wide_parts_failed() ? 1 : 0;
+  });
+  if (rc) return rc;
+  CountSum sum(nT);
+  std::vector<double> hll((size_t)b->nPairs);
+  if (sum.add(d_counts, g_deterministic) || fetch_loglike(hll.data(), d_ll, b->nPairs)) return 1;
+  sum.finish(hll, counts, loglikeSum, loglike);      // loglike += forward.logLike()
+  return 0;
 }
 
 static int batch_counts(mb_batch *b, double *counts, double *loglikeSum, double *loglike);
@@ -1661,8 +1610,7 @@ int mb_batch_counts(mb_batch *b, double *counts, double *loglikeSum, double *log
   return with_parts_retry([&] { return batch_counts(b, counts, loglikeSum, loglike); });      // (the counts reach the caller's array after the last chunk only: a second run adds nothing twice)
 }
 static int batch_counts(mb_batch *b, double *counts, double *loglikeSum, double *loglike) {
-  g_last_ms = 0.0; g_last_launches = 0;
-  g_last_kernel = "";
+  reset_last();
   g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
   if (b->nPairs == 0) return 0;
   if (use_small(b->m) && small_count_fits(((FastState *)b->m->fast)->smF, b->hasEnv) && small_can_run(((FastState *)b->m->fast)->smB, SM_SUM, true, b->hasEnv))
@@ -1684,7 +1632,7 @@ static int batch_counts(mb_batch *b, double *counts, double *loglikeSum, double 
   if (!wide_applicable(b->m) && use_medium(b->m) && fast_state(b->m)->countOk && env_int("MB_MEDIUM_COUNTS_ROLL", 1)) {
     const int rc = counts_chunks(b, counts, loglikeSum, loglike, true);
     if (rc >= 0) return rc;
-    g_last_ms = 0.0; g_last_launches = 0;
+    reset_last();
   }
   return counts_chunks(b, counts, loglikeSum, loglike, false);
 }
@@ -1744,313 +1692,6 @@ int64_t mb_debug_persist_plan(int64_t nPairs, const int32_t *inLen, const int32_
   for (size_t k = 0; k < tk.size(); ++k) { tickets[2 * k] = tk[k].x; tickets[2 * k + 1] = tk[k].y; }
   for (size_t p = 0; p < w.size(); ++p) { wait[2 * p] = w[p].x; wait[2 * p + 1] = w[p].y; }
   return (int64_t)tk.size();
-}
-
-// ---- introspection: generated source of the run-time specialised tile kernel (host only, no device needed) ------
-int mb_debug_jit_source(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_t nTrans, const uint32_t *src, const uint32_t *dst,
-                        const uint16_t *inTok, const uint16_t *outTok, const double *logWeight, int mode, int backward, int closure,
-                        int G, const char *path) {
-  ApiLock lock;
-  if (nStates <= 0 || nTrans < 0 || !path) { set_error("mb_debug_jit_source: bad argument"); return 1; }
-  if (!medium_valid_G(G)) { set_error("mb_debug_jit_source: G must be a power of two in 1..64"); return 1; }
-  mb_machine m;
-  m.S = nStates; m.nIn = nInTok; m.nOut = nOutTok; m.nTrans = nTrans;
-  m.src.assign(src, src + nTrans); m.dst.assign(dst, dst + nTrans);
-  m.inTok.assign(inTok, inTok + nTrans); m.outTok.assign(outTok, outTok + nTrans);
-  m.logW.assign(logWeight, logWeight + nTrans);
-  std::string err;
-  if (!compile_machine(&m, &err)) { set_error(err); return 1; }
-  // mode: MB_FORWARD sum, MB_VITERBI max, 3 count, 4 max with traceback bytes; + 16: tiles without a matrix (MED_MAT_ROLL; implied by 4);
-  // + 32: the PROGRAM instead of the source (see below); + 128: the persistent-strip matrix kernel (MED_MAT_PERSIST, sum only)
-  const int matKind = (mode & 128) ? MED_MAT_PERSIST : (((mode & 16) || (mode & 15) == MED_MODE_TB) ? MED_MAT_ROLL : MED_MAT_FULL);
-  const bool dumpProgram = (mode & 32) != 0;
-  const bool compactRing = (mode & 64) != 0;      // + 64: the matrix-free kernel with the COMPACT ring (as many wavefronts as its LDS allows, at most 12)
-  mode &= 15;
-  MedProgram P; MedGeom geo;
-  if (matKind == MED_MAT_ROLL) geo.haloSteps = 0;
-  if (mode == MED_MODE_COUNT) {
-    if (!medium_build_count_host(&m, G, P, geo, closure)) { set_error("machine does not qualify for the fused count kernel"); return 1; }
-  } else if (!medium_build_host(&m, backward != 0, closure, G, P, geo)) return 1;
-  if (opt_env("MB_MEDIUM_JIT_VERBOSE")) {
-    const long long c = medium_program_cost(P); int syncs = 0;
-    for (const MedRoundInfo &ri : P.roundInfo) syncs += ri.sync;
-    fprintf(stderr, "[mbhip] program cost %lld (rounds %zu, syncs %d, pairs %d, levels %d)\n", c, P.roundInfo.size(), syncs, P.nPairs, backward ? m.nLevB : m.nLevF);
-  }
-  if (dumpProgram) {
-    // The program as the kernels read it -- descriptors + records, what med_slow_supercell (mb_medium.hip) interprets chunk by chunk
-    // and the run-time generator unrolls --, for a device-free replay (tests/test_tiled_plan.py): 16 int32 (magic 0x4D454431, S, Spad,
-    // LPG, G, nChunks, nIn, nOut, seedOff, dummyOff, records, usage slots of a flat count program, 1 = backward, closure stages,
-    // 1 = counting, flags: 1 flat | 2 emitting usage fused into the fill rounds | 4 two accumulator tables), nChunks x 8 int32
-    // descriptors, the records (fp64 weight, srcOff, dstOff), the usage slots (int32 table, first record, placement), one int32 per
-    // record: the transition it stands for, then int32 fused slots, int32 loop-time accumulators, the fused slots (table, first
-    // record, placement) and the loop-time table's transitions
-    FILE *f = fopen(path, "wb");
-    if (!f) { set_error("mb_debug_jit_source: cannot open output file"); return 1; }
-    // usage slots: (table, first record, placement 2 = VGPRs: summed in a register, set down in the after-the-loop table; else: the
-    // loop-time table) -- the usage pass of a flat count program, then the fused emit slots of its fill rounds (MedProgram::fusedEmit)
-    std::vector<int32_t> flatSlots, fusedSlots;
-    for (const MedRoundInfo &ri : P.roundInfo)
-      for (const MedSlotInfo &sl : ri.slots) {
-        if (ri.flat) { flatSlots.push_back(sl.T); flatSlots.push_back((int32_t)sl.recBase); flatSlots.push_back(sl.place); }
-        else if (ri.fused && sl.T < 3) { fusedSlots.push_back(sl.T); fusedSlots.push_back((int32_t)sl.recBase); fusedSlots.push_back(sl.place); }
-      }
-    const int32_t head[16] = {0x4D454431, m.S, P.Spad, P.LPG, P.G, P.nChunks, m.nIn, m.nOut, (int32_t)P.dev.seedOff, (int32_t)P.dummyOff, (int32_t)P.rec.size(),
-                              (int32_t)(flatSlots.size() / 3), P.backward ? 1 : 0, closure, P.counting ? 1 : 0, (P.flatCount ? 1 : 0) | (P.fusedEmit ? 2 : 0) | (P.accAllEntries ? 4 : 0)};
-    const int32_t tail[2] = {(int32_t)(fusedSlots.size() / 3), (int32_t)P.accMap.size()};
-    const bool ok = fwrite(head, sizeof(head), 1, f) == 1 && fwrite(P.desc.data(), 4, (size_t)P.nChunks * MED_DESC_WORDS, f) == (size_t)P.nChunks * MED_DESC_WORDS &&
-                    fwrite(P.rec.data(), sizeof(MedRec), P.rec.size(), f) == P.rec.size() &&
-                    (flatSlots.empty() || fwrite(flatSlots.data(), 4, flatSlots.size(), f) == flatSlots.size()) &&
-                    fwrite(P.wref.data(), 4, P.wref.size(), f) == P.wref.size() &&      // per record: >= 0 its transition, -1 padding, <= -2 a closure pair
-                    fwrite(tail, sizeof(tail), 1, f) == 1 && (fusedSlots.empty() || fwrite(fusedSlots.data(), 4, fusedSlots.size(), f) == fusedSlots.size()) &&
-                    (P.accMap.empty() || fwrite(P.accMap.data(), 4, P.accMap.size(), f) == P.accMap.size());      // loop-time accumulator entry -> transition
-    fclose(f);
-    if (!ok) { set_error("mb_debug_jit_source: short write"); return 1; }
-    return 0;
-  }
-  if (matKind != MED_MAT_FULL) geo.haloSteps = 0;
-  if (compactRing) {
-    if (matKind != MED_MAT_ROLL || P.recC.empty()) { set_error("mb_debug_jit_source: no compact ring for this kernel kind"); return 1; }
-    geo.compact = true; geo.haloSteps = 0;
-    for (geo.waves = 12; geo.waves > 1; --geo.waves) {
-      geo.C = geo.waves * P.G;
-      if (medium_jit_lds_bytes(P, geo, mode == MED_MODE_TB ? MED_MODE_TB : MB_FORWARD) <= 160 * 1024 - 512) break;
-    }
-  }
-  if (mode == MED_MODE_TB && !medium_tb_eligible(&m, P)) { set_error("machine does not qualify for traceback bytes on the tiled family"); return 1; }
-  if (matKind == MED_MAT_PERSIST && mode != MB_FORWARD) { set_error("mb_debug_jit_source: the persistent-strip kernel is a sum kernel"); return 1; }
-  const std::string code = medium_jit_source(&m, P, geo, mode == MED_MODE_COUNT ? MED_MODE_COUNT : (mode == MED_MODE_TB ? MED_MODE_TB : (mode == MB_VITERBI ? MB_VITERBI : MB_FORWARD)), matKind);
-  FILE *f = fopen(path, "w");
-  if (!f) { set_error("mb_debug_jit_source: cannot open output file"); return 1; }
-  fprintf(f, "// G=%d C=%d waves=%d ldsBytes=%zu ldsRecs=%zu rounds=%zu\n", G, geo.C, geo.waves, medium_jit_lds_bytes(P, geo),
-          P.ldsImageIdx.size(), P.roundInfo.size());
-  fputs(code.c_str(), f);
-  fclose(f);
-  return 0;
-}
-
-// The retimed program of a one-tape machine (mb_wide.hip, k_wide_retimed) as the kernel reads it, written to `path`: 12 int32
-// (magic 0x52455431, lanes, slots per period, ring depth NB, doubles per ring vector, largest lag, penalty row length, penalty
-// entries, period, states, 1 = ring in L2, streams) followed by (NB * slots + 8) * lanes records of 16 bytes.  Host only: the
-// planner can be checked without a device (tests/test_retimed_plan.py simulates the stream and compares with the oracle).
-int mb_debug_wide_retimed(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_t nTrans, const uint32_t *src, const uint32_t *dst,
-                          const uint16_t *inTok, const uint16_t *outTok, const double *logWeight, int mode, int backward, const char *path) {
-  ApiLock lock;
-  if (nStates <= 0 || nTrans < 0 || !path || (nInTok != 0) == (nOutTok != 0)) { set_error("mb_debug_wide_retimed: bad argument (one-tape machines only)"); return 1; }
-  mb_machine m;
-  m.S = nStates; m.nIn = nInTok; m.nOut = nOutTok; m.nTrans = nTrans;
-  m.src.assign(src, src + nTrans); m.dst.assign(dst, dst + nTrans);
-  m.inTok.assign(inTok, inTok + nTrans); m.outTok.assign(outTok, outTok + nTrans);
-  m.logW.assign(logWeight, logWeight + nTrans);
-  std::string err;
-  if (!compile_machine(&m, &err)) { set_error(err); return 1; }
-  WideProgram P;
-  std::vector<WideRec> stream;
-  // mode + 16 (with MB_VITERBI, forward): the program that keeps one traceback CODE per cell; its decode tables and the incoming
-  // view's edge ids follow the record streams: int32 count + tbOff, int32 count + tbEntry, int32 count + inEid
-  const bool tbCodes = (mode & 16) != 0;
-  mode &= 15;
-  if (tbCodes && (mode != MB_VITERBI || backward)) { set_error("mb_debug_wide_retimed: traceback codes belong to the forward max program"); return 1; }
-  if (!wide_ret_host(&m, backward != 0, mode == MB_VITERBI, P, stream, tbCodes)) { set_error("machine has no retimed program"); return 1; }
-  if (tbCodes && !P.tbOk) { set_error("machine does not qualify for traceback codes"); return 1; }
-  FILE *f = fopen(path, "wb");
-  if (!f) { set_error("mb_debug_wide_retimed: cannot open output file"); return 1; }
-  const int32_t head[12] = {0x52455431, P.W, P.ret.nSlots, P.ret.NB, P.ret.NVs, P.ret.kMax, P.ret.rowLen, P.ret.nPen, P.retPeriod, nStates, P.retGv ? 1 : 0, P.ret.NB};
-  bool ok = fwrite(head, sizeof(head), 1, f) == 1 && fwrite(stream.data(), sizeof(WideRec), stream.size(), f) == stream.size();
-  if (ok && tbCodes) {
-    const int32_t n0 = (int32_t)P.h_tbOff.size(), n1 = (int32_t)P.h_tbEntry.size(), n2 = (int32_t)m.inPerm.size();
-    ok = fwrite(&n0, 4, 1, f) == 1 && fwrite(P.h_tbOff.data(), 4, (size_t)n0, f) == (size_t)n0 &&
-         fwrite(&n1, 4, 1, f) == 1 && fwrite(P.h_tbEntry.data(), 4, (size_t)n1, f) == (size_t)n1 &&
-         fwrite(&n2, 4, 1, f) == 1 && fwrite(m.inPerm.data(), 4, (size_t)n2, f) == (size_t)n2;
-  }
-  fclose(f);
-  if (!ok) { set_error("mb_debug_wide_retimed: short write"); return 1; }
-  return 0;
-}
-
-// the k-part form of the retimed program (k workgroups per sequence, WidePartDev), planned on the host only: int32 magic 0x52455432,
-// parts, exchange columns, states; then per part 16 int32 (lanes, slots, NB, NVs, kMax, rowLen, nPen, period, own states, imports,
-// first export entry, first exchange column, exports, result entry, table words, byte offset of the second weights or 0), the table (machine
-// state of every own state, then the exchange column of every import), the record streams as in mb_debug_wide_retimed and -- parts with
-// two-transition candidates -- one double per record: the candidate's second weight
-int mb_debug_wide_parts(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_t nTrans, const uint32_t *src, const uint32_t *dst,
-                        const uint16_t *inTok, const uint16_t *outTok, const double *logWeight, int mode, int backward, int k, int lanes, const char *path) {
-  ApiLock lock;
-  if (nStates <= 0 || nTrans < 0 || !path || (nInTok != 0) == (nOutTok != 0)) { set_error("mb_debug_wide_parts: bad argument (one-tape machines only)"); return 1; }
-  mb_machine m;
-  m.S = nStates; m.nIn = nInTok; m.nOut = nOutTok; m.nTrans = nTrans;
-  m.src.assign(src, src + nTrans); m.dst.assign(dst, dst + nTrans);
-  m.inTok.assign(inTok, inTok + nTrans); m.outTok.assign(outTok, outTok + nTrans);
-  m.logW.assign(logWeight, logWeight + nTrans);
-  std::string err;
-  if (!compile_machine(&m, &err)) { set_error(err); return 1; }
-  const bool tbCodes = (mode & 16) != 0;
-  mode &= 15;
-  std::vector<WidePartHost> parts;
-  int nExpTot = 0;
-  std::vector<int> tbOff; std::vector<uint32_t> tbEntry;
-  if (tbCodes && (mode != MB_VITERBI || backward)) { set_error("mb_debug_wide_parts: traceback codes belong to the forward max program"); return 1; }
-  int lanesChosen = lanes, ringChosen = 8;
-  if (!wide_parts_host(&m, backward != 0, mode == MB_VITERBI, tbCodes, k, lanes, parts, nExpTot, &tbOff, &tbEntry, nullptr, &lanesChosen, &ringChosen)) { set_error("machine has no k-part retimed program"); return 1; }
-  lanes = lanesChosen;
-  FILE *f = fopen(path, "wb");
-  if (!f) { set_error("mb_debug_wide_parts: cannot open output file"); return 1; }
-  const int32_t head[4] = {0x52455432, (int32_t)parts.size(), nExpTot, nStates};
-  bool ok = fwrite(head, sizeof(head), 1, f) == 1;
-  for (const WidePartHost &H : parts) {
-    const int32_t ph[16] = {lanes, H.h.ret.nSlots, H.h.ret.NB, H.h.ret.NVs, H.h.ret.kMax, H.h.ret.rowLen, H.h.ret.nPen, H.period, H.h.Sloc, H.h.nImp,
-                            H.h.expBase, H.h.expIdx0, H.h.nExp, H.h.resultEntry, (int32_t)H.tab.size(), H.h.w2Offset};
-    ok = ok && fwrite(ph, sizeof(ph), 1, f) == 1 && fwrite(H.tab.data(), 4, H.tab.size(), f) == H.tab.size() &&
-         fwrite(H.stream.data(), sizeof(WideRec), H.stream.size(), f) == H.stream.size();
-  }
-  if (ok && tbCodes) {      // the joined decode tables of the parts' candidate lists, and the incoming view's edge ids
-    const int32_t n0 = (int32_t)tbOff.size(), n1 = (int32_t)tbEntry.size(), n2 = (int32_t)m.inPerm.size();
-    ok = fwrite(&n0, 4, 1, f) == 1 && fwrite(tbOff.data(), 4, (size_t)n0, f) == (size_t)n0 &&
-         fwrite(&n1, 4, 1, f) == 1 && fwrite(tbEntry.data(), 4, (size_t)n1, f) == (size_t)n1 &&
-         fwrite(&n2, 4, 1, f) == 1 && fwrite(m.inPerm.data(), 4, (size_t)n2, f) == (size_t)n2;
-  }
-  fclose(f);
-  if (!ok) { set_error("mb_debug_wide_parts: short write"); return 1; }
-  return 0;
-}
-
-// the one-tape sweep GENERATED for this machine (mb_wide_jit.cpp), planned and rendered on the host only: k >= 2: the machine cut for k
-// workgroups per sequence (lanes = 0: searched), k <= 1: the one-workgroup program.  mode: MB_FORWARD / MB_VITERBI, + 16 traceback codes,
-// + 64 the fp64 correction term.  Writes the HIP source to `path` and, to `path`.prog, what the source unrolls -- for the device-free replay
-// of tests/test_retimed_plan.py: int32 magic 0x4A495431, parts, exchange columns, states; per part 24 int32 (lanes, NB, NVs, kMax, rowLen,
-// nPen, nImp, S, expBase, nExp, expIdx0, resultEntry, slots, rounds, NPT, U, penBase, tokBase, ringBase, dummyAddr, ldsBytes, fields,
-// words, 0), per slot 2 int32 (anyPen, anyW2), per round 8 int32 (firstSlot, depth, sync, uniform, gAll, anyMixed, resultLane, mask of the lane-group sizes its switch serves), per
-// field 4 int32 (kind, index, cm, words), then the table [words][lanes] uint32.  compile != 0: the source is also compiled with hiprtc
-// (no device needed) and the call fails when the kernel would use scratch memory.
-int mb_debug_wide_jit(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_t nTrans, const uint32_t *src, const uint32_t *dst,
-                      const uint16_t *inTok, const uint16_t *outTok, const double *logWeight, int mode, int backward, int k, int lanes, int compile, const char *path) {
-  ApiLock lock;
-  if (nStates <= 0 || nTrans < 0 || !path || (nInTok != 0) == (nOutTok != 0)) { set_error("mb_debug_wide_jit: bad argument (one-tape machines only)"); return 1; }
-  mb_machine m;
-  m.S = nStates; m.nIn = nInTok; m.nOut = nOutTok; m.nTrans = nTrans;
-  m.src.assign(src, src + nTrans); m.dst.assign(dst, dst + nTrans);
-  m.inTok.assign(inTok, inTok + nTrans); m.outTok.assign(outTok, outTok + nTrans);
-  m.logW.assign(logWeight, logWeight + nTrans);
-  std::string err;
-  if (!compile_machine(&m, &err)) { set_error(err); return 1; }
-  const bool tbCodes = (mode & 16) != 0, acc = (mode & 64) != 0;
-  mode &= 15;
-  if (tbCodes && (mode != MB_VITERBI || backward)) { set_error("mb_debug_wide_jit: traceback codes belong to the forward max program"); return 1; }
-  std::vector<WidePartHost> parts;
-  std::vector<WideRec> stream;
-  WideProgram P;
-  std::vector<WideJitIn> ins;
-  int nExpTot = 0;
-  if (k >= 2) {
-    int lanesChosen = lanes, mergeFlag = 0;
-    if (!wide_parts_host(&m, backward != 0, mode == MB_VITERBI, tbCodes, k, lanes, parts, nExpTot, nullptr, nullptr, nullptr, &lanesChosen, &mergeFlag)) { set_error("machine has no k-part retimed program"); return 1; }
-    for (const WidePartHost &H : parts) {
-      WideJitIn in;
-      in.ret = H.h.ret; in.W = lanesChosen; in.stream = H.stream.data();
-      in.w2 = H.h.w2Offset ? (const double *)((const char *)H.stream.data() + H.h.w2Offset) : nullptr;
-      in.part = true; in.S = H.h.Sloc; in.Sg = nStates; in.nImp = H.h.nImp; in.expBase = H.h.expBase; in.nExp = H.h.nExp; in.expIdx0 = H.h.expIdx0; in.resultEntry = H.h.resultEntry;
-      in.gmap = H.tab.data();
-      ins.push_back(in);
-    }
-  } else {
-    if (!wide_ret_host(&m, backward != 0, mode == MB_VITERBI, P, stream, tbCodes) || P.retGv) { set_error("machine has no retimed program with its ring in LDS"); return 1; }
-    WideJitIn in;
-    in.ret = P.ret; in.W = P.W; in.stream = stream.data(); in.S = nStates; in.Sg = nStates; in.resultEntry = backward ? 0 : nStates - 1;
-    ins.push_back(in);
-  }
-  WideJitFlags F; F.viterbi = mode == MB_VITERBI; F.tb = tbCodes; F.acc = acc; F.backward = backward != 0; F.inputTape = nOutTok == 0; F.nExpTot = nExpTot;
-  // the plan the library would run: the register estimate's choice, planned again with fewer constants in registers while the compiled
-  // kernel spills (mb_wide_jit.cpp, wide_jit_plan; MB_WIDE_JIT_ATTEMPT: the attempt to start from -- the device-free replays of the later ones)
-  std::vector<WideJitDesc> descs;
-  std::string code, obj;
-  for (int attempt = std::max(0, std::min(env_int("MB_WIDE_JIT_ATTEMPT", 0), WIDE_JIT_ATTEMPTS - 1));; ++attempt) {
-    std::string why;
-    if (!wide_jit_plan(ins, acc != 0, attempt, descs, &why)) { set_error("mb_debug_wide_jit: " + why); return 1; }
-    code = wide_jit_source(descs, F);
-    if (!compile) break;
-    std::string log;
-    if (!jit_compile(code, "mb_wide_jit.hip", obj, &log, nullptr)) { set_error("mb_debug_wide_jit: hiprtc: " + log.substr(0, 2000)); return 1; }
-    const long long scratch = jit_kernel_meta(obj, ".private_segment_fixed_size");
-    if (scratch <= 0) break;
-    if (attempt + 1 >= WIDE_JIT_ATTEMPTS) { set_error("mb_debug_wide_jit: the kernel uses " + std::to_string(scratch) + " bytes of scratch memory"); return 1; }
-  }
-  FILE *f = fopen(path, "w");
-  if (!f) { set_error("mb_debug_wide_jit: cannot open output file"); return 1; }
-  fputs(code.c_str(), f);
-  fclose(f);
-  f = fopen((std::string(path) + ".prog").c_str(), "wb");
-  if (!f) { set_error("mb_debug_wide_jit: cannot open output file"); return 1; }
-  const int32_t head[4] = {0x4A495431, (int32_t)descs.size(), nExpTot, nStates};
-  bool ok = fwrite(head, sizeof(head), 1, f) == 1;
-  for (const WideJitDesc &D : descs) {
-    const WideJitIn &in = D.in;
-    const int32_t ph[24] = {in.W, in.ret.NB, in.ret.NVs, in.ret.kMax, in.ret.rowLen, in.ret.nPen, in.nImp, in.S, in.expBase, in.nExp, in.expIdx0, in.resultEntry,
-                            D.nSlots, (int32_t)D.rounds.size(), D.NPT, D.U, (int32_t)D.penBase, (int32_t)D.tokBase, (int32_t)D.ringBase, (int32_t)D.dummyAddr, (int32_t)D.ldsBytes,
-                            (int32_t)D.fields.size(), D.nWords, D.level | (D.IP << 8) | (D.ring << 20)};
-    ok = ok && fwrite(ph, sizeof(ph), 1, f) == 1;
-    for (const WideJitSlot &sl : D.slots) { const int32_t v[2] = {sl.anyPen, sl.anyW2}; ok = ok && fwrite(v, sizeof(v), 1, f) == 1; }
-    for (const WideJitRound &R : D.rounds) {
-      int32_t mask = 0;      // the lane-group sizes the round's switch has a case for
-      for (int g : R.gWaves) mask |= g;
-      const int32_t v[8] = {R.firstSlot, R.depth, R.sync, R.uniform, R.gAll, R.anyMixed, R.resultLane, mask};
-      ok = ok && fwrite(v, sizeof(v), 1, f) == 1;
-    }
-    for (const WideJitField &fd : D.fields) { const int32_t v[4] = {fd.kind, fd.index, fd.cm, fd.words}; ok = ok && fwrite(v, sizeof(v), 1, f) == 1; }
-    std::vector<uint32_t> tab, stream;
-    wide_jit_table(D, F, tab, &stream);
-    ok = ok && fwrite(tab.data(), 4, tab.size(), f) == tab.size();
-    if (D.level >= 1) ok = ok && fwrite(stream.data(), 4, stream.size(), f) == stream.size();      // [NB][IP][lanes] packed address words
-    if (in.part) ok = ok && fwrite(in.gmap + in.S, 4, (size_t)in.nImp, f) == (size_t)in.nImp;      // the exchange columns of the imports
-  }
-  fclose(f);
-  if (!ok) { set_error("mb_debug_wide_jit: short write"); return 1; }
-  if (compile) {
-    if (FILE *g = fopen((std::string(path) + ".co").c_str(), "wb")) { fwrite(obj.data(), 1, obj.size(), g); fclose(g); }
-  }
-  return 0;
-}
-
-// generated source of the small-machine family's sweep (mode: 0 sum, 1 max, 2 traceback bytes, 3 counts); host only
-int mb_debug_small_source(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_t nTrans, const uint32_t *src, const uint32_t *dst,
-                          const uint16_t *inTok, const uint16_t *outTok, const double *logWeight, int mode, int backward,
-                          int materialise, const char *path) {
-  ApiLock lock;
-  const bool dumpProgram = (mode & 32) != 0;      // the PROGRAM instead of the source (see below)
-  mode &= 31;
-  if (nStates <= 0 || nTrans < 0 || !path || mode < 0 || mode >= SM_NMODE) { set_error("mb_debug_small_source: bad argument"); return 1; }
-  mb_machine m;
-  m.S = nStates; m.nIn = nInTok; m.nOut = nOutTok; m.nTrans = nTrans;
-  m.src.assign(src, src + nTrans); m.dst.assign(dst, dst + nTrans);
-  m.inTok.assign(inTok, inTok + nTrans); m.outTok.assign(outTok, outTok + nTrans);
-  m.logW.assign(logWeight, logWeight + nTrans);
-  std::string err;
-  if (!compile_machine(&m, &err)) { set_error(err); return 1; }
-  SmallProgram P;
-  if (!small_build_host(&m, backward != 0, P)) { set_error("machine does not qualify for the small-machine family"); return 1; }
-  if (dumpProgram) {
-    // what the generator unrolls, for a device-free replay (tests/test_small_plan.py): 20 int32 (magic 0x534D5031, S, nIn, nOut,
-    // backward, seed state, end state, table entries, off[0..3], nTab[0..3], candidates, 3 x 0), the evaluation order [S], decOff
-    // [S + 1], the candidates (T, src, dup, tab) in the reference's enumeration order, then w[] (fp64) and eid[] (int32)
-    FILE *f = fopen(path, "wb");
-    if (!f) { set_error("mb_debug_small_source: cannot open output file"); return 1; }
-    std::vector<int32_t> cands;
-    for (int d = 0; d < P.S; ++d) for (const SmSlot &sl : P.cand[d]) { cands.push_back(sl.T); cands.push_back(sl.src); cands.push_back(sl.dup); cands.push_back(sl.tab); }
-    const int32_t head[20] = {0x534D5031, P.S, P.nIn, P.nOut, P.backward ? 1 : 0, P.seedState, P.endState, (int32_t)P.nEntries, (int32_t)P.off[0], (int32_t)P.off[1],
-                              (int32_t)P.off[2], (int32_t)P.off[3], P.nTab[0], P.nTab[1], P.nTab[2], P.nTab[3], (int32_t)(cands.size() / 4), 0, 0, 0};
-    const bool ok = fwrite(head, sizeof(head), 1, f) == 1 && fwrite(P.order.data(), 4, P.order.size(), f) == P.order.size() &&
-                    fwrite(P.decOff.data(), 4, P.decOff.size(), f) == P.decOff.size() && fwrite(cands.data(), 4, cands.size(), f) == cands.size() &&
-                    fwrite(P.w.data(), 8, P.w.size(), f) == P.w.size() && fwrite(P.eid.data(), 4, P.eid.size(), f) == P.eid.size();
-    fclose(f);
-    if (!ok) { set_error("mb_debug_small_source: short write"); return 1; }
-    return 0;
-  }
-  const std::string code = small_jit_source(P, mode, (materialise & 1) != 0, (materialise & 2) != 0);   // bit 1: the restricted-envelope variant
-  FILE *f = fopen(path, "w");
-  if (!f) { set_error("mb_debug_small_source: cannot open output file"); return 1; }
-  fprintf(f, "// ldsBytes=%zu H=%d NBD=%d tables: silent %d input %d output %d match %d\n", small_jit_lds_bytes(P, mode), P.H, P.NBD,
-          P.nTab[3], P.nTab[1], P.nTab[2], P.nTab[0]);
-  fputs(code.c_str(), f);
-  fclose(f);
-  return 0;
 }
 
 // ---- host-buffer convenience wrappers -------------------------------------------------------------------------
@@ -2234,9 +1875,9 @@ static int prefix_fill(mb_prefix *p, int64_t n, const int64_t *seq, const int64_
     d.outLen = (int)(p->outOff[(size_t)seq[i] + 1] - p->outOff[(size_t)seq[i]]);
     d.inTok = parent[i] >= 0 ? inTok[i] : 0;
   }
-  PrefixDesc *d_desc = nullptr; double *d_res = nullptr;
-  MB_HIP(sm_alloc((void **)&d_desc, h.size() * sizeof(PrefixDesc)));
-  if (!hip_ok(sm_alloc((void **)&d_res, (size_t)n * 2 * sizeof(double)), "hipMalloc(prefix results)")) { sm_free(d_desc); return 1; }
+  SmBuf<PrefixDesc> d_desc; SmBuf<double> d_res;
+  MB_HIP(d_desc.alloc((long long)h.size()));
+  if (!hip_ok(d_res.alloc(n * 2), "hipMalloc(prefix results)")) return 1;
   std::vector<double> res((size_t)n * 2);
   int rc = hip_ok(hipMemcpyAsync(d_desc, h.data(), h.size() * sizeof(PrefixDesc), hipMemcpyHostToDevice, g_stream), "H2D prefix descriptors") ? 0 : 1;
   if (!rc) {
@@ -2252,10 +1893,8 @@ static int prefix_fill(mb_prefix *p, int64_t n, const int64_t *seq, const int64_
   if (!rc && !hip_ok(hipMemcpyAsync(res.data(), d_res, res.size() * sizeof(double), hipMemcpyDeviceToHost, g_stream), "D2H prefix results")) rc = 1;
   const char *kernel = p->nCols ? "k_prefix_fill_merged" : p->profile ? "k_prefix_fill_profile" : "k_prefix_fill";
   if (!rc && !hip_ok(hipStreamSynchronize(g_stream), kernel)) rc = 1;
-  if (rc) quiesce_streams();
-  sm_free(d_desc); sm_free(d_res);
   g_last_kernel = kernel;
-  if (rc) return rc;
+  if (rc) { quiesce_streams(); return rc; }      // (before the descriptors go)
   for (int64_t i = 0; i < n; ++i) {
     p->slotSeq[(size_t)childOut[i]] = seq[i];
     logSeqProb[i] = res[2 * (size_t)i]; logPrefixProb[i] = res[2 * (size_t)i + 1];
@@ -2267,7 +1906,7 @@ static int prefix_fill(mb_prefix *p, int64_t n, const int64_t *seq, const int64_
 int mb_prefix_root(mb_prefix *p, int64_t seq, int64_t *nodeOut, double *logSeqProb, double *logPrefixProb) {
   ApiGuard guard;
   if (!p || !nodeOut || !logSeqProb || !logPrefixProb) { set_error("null argument"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
+  reset_last();
   const int64_t none = -1;
   return prefix_fill(p, 1, &seq, &none, nullptr, nodeOut, logSeqProb, logPrefixProb);
 }
@@ -2276,7 +1915,7 @@ int mb_prefix_extend(mb_prefix *p, int64_t n, const int64_t *seq, const int64_t 
                      double *logSeqProb, double *logPrefixProb) {
   ApiGuard guard;
   if (!p || n < 0 || (n && (!seq || !parent || !inTok || !childOut || !logSeqProb || !logPrefixProb))) { set_error("null argument"); return 1; }
-  g_last_ms = 0.0; g_last_launches = 0;
+  reset_last();
   for (int64_t i = 0; i < n; ++i)
     if (parent[i] < 0) { set_error("prefix fill " + std::to_string(i) + ": parent is not a live node of that search"); return 1; }
   return prefix_fill(p, n, seq, parent, inTok, childOut, logSeqProb, logPrefixProb);

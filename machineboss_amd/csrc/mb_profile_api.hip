@@ -3,8 +3,9 @@
 // (mb_profile_twos).
 //
 // Host orchestration only, like mb_api.hip.  Each family has Forward, Viterbi, counts, row posteriors, set_rows and a single-lattice
-// fill; what those calls share -- the chunk planner and the chunk loop, the call-scoped device buffers, the path copier, the count and
-// posterior tails -- is written once at the top, the per-family parts (descriptors, launches, kernel names) follow.
+// fill; what those calls share with the token batch calls -- the chunk loop, the call-scoped device buffers, the count tail -- is in
+// mb_api_internal.h, what they share among themselves -- the chunk planner, the path copier, the posterior tail -- is written once at
+// the top, the per-family parts (descriptors, launches, kernel names) follow.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -62,52 +63,15 @@ static bool lattice_chunks(long long n, const char *noun, const std::function<do
   return true;
 }
 
-// A call-scoped device buffer of the small-block cache (sm_alloc), one element at the least; it goes back when the scope ends.
-template <class T> struct SmBuf {
-  T *p = nullptr;
-  SmBuf() = default;
-  SmBuf(const SmBuf &) = delete;
-  SmBuf &operator=(const SmBuf &) = delete;
-  ~SmBuf() { sm_free(p); }
-  hipError_t alloc(long long n) { return sm_alloc((void **)&p, (size_t)std::max<long long>(n, 1) * sizeof(T)); }
-  operator T *() const { return p; }
-};
-
-// n elements of a workspace slot (one at the least: a chunk of empty items still gets a pointer)
-template <class T> static T *ws_array(int slot, long long n) { return (T *)ws_get(slot, (size_t)std::max<long long>(n, 1) * sizeof(T)); }
-
-// The launches of one chunk on the library stream: timed into g_last_ms, counted into g_last_launches.
-struct Timed {
-  Timer &tm;
-  Timed(Timer &t, long long launches) : tm(t) { g_last_launches += launches; tm.start(); }
-  ~Timed() { g_last_ms += tm.stop(); }
-};
-
-// The chunk loop of every batch call.  build(c, plan) packs the descriptors of chunk c into a fresh Plan (which frees them when it
-// goes); body(c, plan, timer) takes the workspaces, launches under a Timed and copies the chunk's results out.  A failed body waits
-// for the streams before the descriptors are released, and ends the loop.
-template <class Plan, class Build, class Body>
-static int for_chunks(const std::vector<Chunk> &chunks, Build build, Body body) {
-  Timer tm;
-  for (const Chunk &c : chunks) {
-    Plan pl;
-    if (build(c, pl)) return 1;
-    const int rc = body(c, pl, tm);
-    if (rc) { quiesce_streams(); return rc; }
-  }
-  return 0;
-}
-
 // Where the per-pair device results of mb_profile_pairs landed (PairProfPlan::slot, below): each chunk in the order of its plan's
 // slots, at[k] = the entry of pair k.
 struct PairWhere { std::vector<long long> at; bool permuted = false; };
 
-// per-item log-likelihoods into dst[0..n); where: the permuted fetch of a pair batch that has envelopes
-static int fetch_loglike(double *dst, const double *d_ll, long long n, const PairWhere *where = nullptr) {
-  if (n <= 0) return 0;
-  if (!where || !where->permuted) return hip_ok(hipMemcpy(dst, d_ll, (size_t)n * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike") ? 0 : 1;
+// per-item log-likelihoods of a pair batch into dst[0..n): permuted when the batch has envelopes
+static int fetch_loglike(double *dst, const double *d_ll, long long n, const PairWhere *where) {
+  if (n <= 0 || !where->permuted) return fetch_loglike(dst, d_ll, n);
   std::vector<double> tmp((size_t)n);
-  if (!hip_ok(hipMemcpy(tmp.data(), d_ll, tmp.size() * sizeof(double), hipMemcpyDeviceToHost), "D2H loglike")) return 1;
+  if (fetch_loglike(tmp.data(), d_ll, n)) return 1;
   for (long long k = 0; k < n; ++k) dst[k] = tmp[(size_t)where->at[(size_t)k]];
   return 0;
 }
@@ -150,33 +114,6 @@ static int unpack_paths(PathSink &o, long long k0, long long np, long long paths
   return 0;
 }
 
-// MB_DETERMINISTIC: n global fixed-point accumulators (2^-36) as doubles, in place
-static int decode_fixed_point(double *v, long long n, const char *msg) {
-  for (long long e = 0; e < n; ++e) {
-    unsigned long long u; std::memcpy(&u, &v[e], 8);
-    if (!det_to_double(u, v[e])) { set_error(msg); return 1; }
-  }
-  return 0;
-}
-
-// The transition counts of a call: each chunk's device counts added on the host, then the call's tail.
-struct CountSum {
-  std::vector<double> total, hc;
-  explicit CountSum(long long nT) : total((size_t)nT, 0.0), hc((size_t)nT) {}
-  int add(const double *d_cc, bool fixedPoint) {
-    const long long nT = (long long)total.size();
-    if (nT && !hip_ok(hipMemcpy(hc.data(), d_cc, nT * sizeof(double), hipMemcpyDeviceToHost), "D2H counts")) return 1;
-    if (fixedPoint && decode_fixed_point(hc.data(), nT, "MB_DETERMINISTIC: a posterior count left the fixed-point range (6.7e7 per transition and call): split the batch or use the floating-point mode")) return 1;
-    for (long long e = 0; e < nT; ++e) total[(size_t)e] += hc[(size_t)e];
-    return 0;
-  }
-  void finish(const std::vector<double> &hll, double *counts, double *loglikeSum, double *loglike) const {
-    for (size_t e = 0; e < total.size(); ++e) counts[e] += total[e];
-    double s = 0.0;
-    for (size_t k = 0; k < hll.size(); ++k) { s += hll[k]; if (loglike) loglike[k] = hll[k]; }
-    if (loglikeSum) *loglikeSum += s;
-  }
-};
 // the workgroups per item of the count kernels of the pairs and the two-profile pairs: one per 2 048 cells of the largest lattice, 256 at the most
 template <class Cells> static int count_groups(long long p0, long long p1, Cells cells) {
   long long maxCells = 0;
