@@ -404,9 +404,13 @@ int mb_jit_stats(double *compileMs, int64_t *compiles, int64_t *cacheHits);
  * padding lanes of the kernel family included) -- what the rolling (log-likelihood-only) mode is priced against, since it
  * moves no matrix through HBM.  family: name of the kernel family that would run the sweep. */
 int mb_machine_sweep_ops(mb_machine *m, double *expPerCell, double *logPerCell, const char **family);
-/* Tuning knobs (kernel family thresholds, strip geometry, closure stages ...: DESIGN.md section 4.4).  They are read when
+/* Tuning knobs (kernel family thresholds, strip geometry, closure stages ...: DESIGN.md section 4.7).  They are read when
  * a machine's programs and kernels are built, from the process environment; these calls are the same switchboard for a
- * host that prefers calls.  Names start with "MB_"; value NULL or "" restores the default. */
+ * host that prefers calls: a table inside the library, consulted before the environment.  Value NULL or "" takes the
+ * entry out of that table again (back to the environment's value, or the default).  A name the library does not know, or
+ * a read-only one, is refused: mb_set_option returns non-zero and mb_last_error names the option; mb_get_option returns
+ * NULL for it.  mb_get_option(NULL) returns the list of all options, one per line: name, kind (Int, Real, Text, Present),
+ * default (or "by call", or "-"), class and a note, separated by tabs. */
 int mb_set_option(const char *name, const char *value);
 const char *mb_get_option(const char *name);
 

@@ -227,6 +227,12 @@ def set_option(name: str, value=None):
     _check(load().mb_set_option(name.encode(), None if value is None else str(value).encode()))
 
 
+def options() -> dict:
+    """The library's option table (mb_get_option(NULL)): name -> {kind, default, class, note}."""
+    rows = (line.split("\t") for line in load().mb_get_option(None).decode().splitlines())
+    return {r[0]: {"kind": r[1], "default": r[2], "class": r[3], "note": r[4]} for r in rows}
+
+
 def last_device_ms() -> float:
     return load().mb_last_device_ms()
 

@@ -35,19 +35,6 @@ static bool g_init = false;
 
 void set_error(const std::string &msg) { g_err = msg; }
 
-// the library's own option table (mb_set_option); readers run inside API calls, under the API lock
-static std::map<std::string, std::string> g_options;
-const char *opt_env(const char *name) {
-  if (!g_options.empty()) {
-    auto it = g_options.find(name);
-    if (it != g_options.end()) return it->second.c_str();
-  }
-  return getenv(name);
-}
-void opt_set(const char *name, const char *value) {
-  if (value && *value) g_options[name] = value; else g_options.erase(name);
-}
-
 bool hip_ok(hipError_t e, const char *what) {
   if (e == hipSuccess) return true;
   g_err = std::string(what) + ": " + hipGetErrorString(e);
@@ -66,6 +53,7 @@ ApiGuard::~ApiGuard() { --g_api_depth; g_api_mutex.unlock(); }
 ApiLock::ApiLock() { g_api_mutex.lock(); }
 ApiLock::~ApiLock() { g_api_mutex.unlock(); }
 bool g_deterministic = false;
+void latch_deterministic() { g_deterministic = opt_int<MB_DETERMINISTIC>() != 0; }
 static int g_device = -1;   // device the library's stream and workspaces live on
 
 int ensure_init() {
@@ -248,11 +236,6 @@ static void ws_release() {
   for (int k = 0; k < 2; ++k) if (g_pinned[k]) { (void)hipHostFree(g_pinned[k]); g_pinned[k] = nullptr; }
 }
 
-static int env_flag_default(const char *name, int dflt) {
-  const char *v = opt_env(name);
-  return v && *v ? atoi(v) : dflt;
-}
-
 size_t budget_bytes() {
   if (g_mem_budget) return g_mem_budget;
   size_t freeB = 0, totalB = 0;
@@ -268,9 +251,9 @@ size_t budget_bytes() {
   static size_t sticky = 0;
   static double stickyFrac = 0.0;
   double frac = 0.90;
-  if (const char *e = opt_env("MB_MEM_FRACTION")) { const double f = atof(e); if (f > 0.0 && f <= 0.95) frac = f; }
+  { const double f = opt_real<MB_MEM_FRACTION>(); if (f > 0.0 && f <= 0.95) frac = f; }
   const size_t cur = (size_t)((double)(freeB + reclaimable_bytes()) * frac);
-  if (!sticky || frac != stickyFrac || cur < sticky || cur > sticky + sticky / 8 || !env_flag_default("MB_POOL_STICKY", 1)) { sticky = cur; stickyFrac = frac; }
+  if (!sticky || frac != stickyFrac || cur < sticky || cur > sticky + sticky / 8 || !opt_int<MB_POOL_STICKY>()) { sticky = cur; stickyFrac = frac; }
   return sticky;
 }
 
@@ -399,15 +382,10 @@ struct FastState {
   SmallProgram smF, smB;
 };
 
-int env_int(const char *name, int dflt) {
-  const char *v = opt_env(name);
-  return v && *v ? atoi(v) : dflt;
-}
-
 // what the closure chooser minimises (fast_state) and what MB_MEDIUM_JIT_VERBOSE prints (mb_debug_jit_source): candidate slots + the
 // price of a round and of a synchronisation point in slots (MB_MEDIUM_ROUND_COST, default 0; MB_MEDIUM_SYNC_COST, default 1)
 long long medium_program_cost(const MedProgram &P) {
-  const int syncCost = env_int("MB_MEDIUM_SYNC_COST", 1), roundCost = env_int("MB_MEDIUM_ROUND_COST", 0);
+  const int syncCost = opt_int<MB_MEDIUM_SYNC_COST>(), roundCost = opt_int<MB_MEDIUM_ROUND_COST>();
   long long c = 0;
   for (const MedRoundInfo &ri : P.roundInfo) c += (long long)ri.slots.size() + roundCost + (ri.sync ? syncCost : 0);
   return c;
@@ -419,13 +397,14 @@ static FastState *fast_state(mb_machine *m) {
   if (!f->tried) {
     f->tried = true;
     // tiny machines run with 8 columns per wavefront (8 lanes per supercell); 1-state machines stay generic
-    if (m->S >= env_int("MB_MEDIUM_MIN_STATES", 2) && m->S <= 4096 && !wide_applicable(m)) {
-      int G = env_int("MB_MEDIUM_G", 0);
+    if (m->S >= opt_int<MB_MEDIUM_MIN_STATES>() && m->S <= 4096 && !wide_applicable(m)) {
+      const int wantG = opt_int<MB_MEDIUM_G>();
+      int G = wantG;
       if (!medium_valid_G(G)) G = medium_default_G(m->S);
       f->G = G;
       long long nSilent = 0;
       for (long long e = 0; e < m->nTrans; ++e) nSilent += (m->inTok[e] == 0 && m->outTok[e] == 0);
-      const bool wantClosure = env_int("MB_MEDIUM_CLOSURE", 1) != 0;
+      const bool wantClosure = opt_int<MB_MEDIUM_CLOSURE>() != 0;
       // The silent closure trades synchronisation points (one wave-level LDS round trip per silent level) for
       // candidates.  Closing ALL levels at once is right for psw2dna (10 levels, 146 silent edges -> 360 pairs), but on
       // machines whose silent sub-graph is deep and dense (protpsw.translate.dnapsw: 22 levels, 551 silent edges ->
@@ -441,11 +420,11 @@ static FastState *fast_state(mb_machine *m) {
       auto choose = [&](bool backward, std::vector<int> &cuts) {
         cuts.clear();
         int bestK = 0; long long best = -1;
-        const int forced = env_int("MB_MEDIUM_CLOSURE_STAGES", -1);
+        const int forced = opt_int<MB_MEDIUM_CLOSURE_STAGES>();
         if (forced >= 0) return forced;
         if (!wantClosure) return 0;
         const int nLev = backward ? m->nLevB : m->nLevF;
-        const bool verbose = opt_env("MB_MEDIUM_JIT_VERBOSE") != nullptr;
+        const bool verbose = opt_present<MB_MEDIUM_JIT_VERBOSE>();
         auto tryBuild = [&](int K, const std::vector<int> &cs, long long &c) {
           MedProgram P; MedGeom g;
           medium_set_cuts(cs);
@@ -462,7 +441,7 @@ static FastState *fast_state(mb_machine *m) {
           if (verbose) fprintf(stderr, "[mbhip] %s program, closure stages %d: cost %lld\n", backward ? "backward" : "forward", K, c);
           if (best < 0 || c < best) { best = c; bestK = K; }
         }
-        if (env_int("MB_MEDIUM_CUTS_SEARCH", 1) && nLev > 2 && !opt_env("MB_MEDIUM_CUTS")) {
+        if (opt_int<MB_MEDIUM_CUTS_SEARCH>() && nLev > 2 && !opt_text<MB_MEDIUM_CUTS>()) {
           std::vector<int> cur;
           long long curCost;
           if (tryBuild(1, {}, curCost)) {
@@ -500,9 +479,9 @@ static FastState *fast_state(mb_machine *m) {
       if (ok) ok = buildWith(true, f->bwdSum, f->geoBS);
       f->mediumOk = ok;
       f->exactOk = ok;
-      if (ok && env_int("MB_MEDIUM_COUNTS", 1)) {
-        int Gc = env_int("MB_MEDIUM_COUNT_G", 0);
-        if (!medium_valid_G(Gc)) Gc = env_int("MB_MEDIUM_G", 0) ? G : medium_default_count_G(m->S);
+      if (ok && opt_int<MB_MEDIUM_COUNTS>()) {
+        int Gc = opt_int<MB_MEDIUM_COUNT_G>();
+        if (!medium_valid_G(Gc)) Gc = wantG ? G : medium_default_count_G(m->S);
         f->countOk = medium_build_count(m, Gc, f->fwdCnt, f->geoCnt, KFwd, cutsFwd);
       }
     }
@@ -518,7 +497,7 @@ static bool use_small(mb_machine *m) {
   FastState *f = (FastState *)m->fast;
   if (!f->smallTried) {
     f->smallTried = true;
-    if (env_int("MB_SMALL", 1)) f->smallOk = small_build(m, false, f->smF) && small_build(m, true, f->smB);
+    if (opt_int<MB_SMALL>()) f->smallOk = small_build(m, false, f->smF) && small_build(m, true, f->smB);
   }
   return f->smallOk;
 }
@@ -559,13 +538,13 @@ static WideProgram *wide_program(mb_machine *m, int mode) {
 // update: which edges are -inf decides whether the retimed form exists (they leave the retiming graph), so a machine can gain or
 // lose it.  Callers that never run Viterbi build neither program.
 static bool onetape_tiled_viterbi(mb_machine *m) {
-  if (!wide_applicable(m) || g_kernel_choice == 1 || m->S > env_int("MB_WIDE_VITERBI_MIN_STATES", 2048)) return false;
+  if (!wide_applicable(m) || g_kernel_choice == 1 || m->S > opt_int<MB_WIDE_VITERBI_MIN_STATES>()) return false;
   FastState *f = fast_state(m);
   WideProgram *W = wide_program(m, MB_VITERBI);      // (built on first use, rebuilt when the weights changed)
   if (W && W->retOk) return false;
   if (!f->exactTried) {
     f->exactTried = true;
-    int G = env_int("MB_MEDIUM_G", 0);
+    int G = opt_int<MB_MEDIUM_G>();
     if (!medium_valid_G(G)) G = medium_default_G(m->S);
     f->G = G;
     f->exactOk = medium_build(m, false, 0, G, f->fwdExact, f->geoFE);
@@ -581,7 +560,7 @@ static bool onetape_tiled_viterbi(mb_machine *m) {
 // see onetape_tiled_viterbi): a failed build is retried then, not latched; a program without a retimed form or without codes is
 // freed at once (its column-by-column twin would never run).
 static WideProgram *wide_tb_program(mb_machine *m) {
-  if (g_kernel_choice == 1 || !wide_applicable(m) || !env_int("MB_ONETAPE_TB", 1)) return nullptr;
+  if (g_kernel_choice == 1 || !wide_applicable(m) || !opt_int<MB_ONETAPE_TB>()) return nullptr;
   FastState *f = fast_state(m);
   WideProgram &P = f->wVitTb;
   if (!f->wVitTbTried || P.dirty) {
@@ -738,7 +717,7 @@ static int small_forward(mb_batch *b, int flags, double *loglike) {
 // ---- the path tail of the Viterbi calls (small family here, viterbi_chunks below) ------------------------------------------------
 // MB_TIMING: the host-side laps of a Viterbi call on stderr
 struct Laps {
-  const bool on = opt_env("MB_TIMING") != nullptr;
+  const bool on = opt_present<MB_TIMING>();
   double tPrev = now();
   static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
   void lap(const char *what) { if (on) { const double t = now(); fprintf(stderr, "[mbhip] viterbi %-28s %7.2f ms\n", what, t - tPrev); tPrev = t; } }
@@ -990,24 +969,28 @@ int mb_machine_sweep_ops(mb_machine *m, double *expPerCell, double *logPerCell, 
   return 0;
 }
 
-// Tuning knobs are read from the environment when a machine's programs / kernels are built (DESIGN.md section 4.4 lists
-// them); this is the same switchboard for a host that prefers calls to environment variables.
+// Tuning knobs are read from the environment when a machine's programs / kernels are built (mb_options.h lists them, DESIGN.md
+// section 4.7 the ones for a host); this is the same switchboard for a host that prefers calls to environment variables.
 int mb_set_option(const char *name, const char *value) {
   ApiLock lock;
-  if (!name || strncmp(name, "MB_", 3) != 0) { set_error("mb_set_option: option names start with MB_"); return 1; }
-  opt_set(name, value);      // (the library's table: the process environment is the host's, not ours to write)
+  const int id = opt_find(name);
+  if (id < 0) { set_error(std::string("mb_set_option: unknown option ") + (name ? name : "(null)")); return 1; }
+  if (OPT_TABLE[id].cls == OptClass::info) { set_error(std::string("mb_set_option: ") + name + " is read-only"); return 1; }
+  opt_override((Opt)id, value);      // (the library's table: the process environment is the host's, not ours to write)
   return 0;
 }
 
 const char *mb_get_option(const char *name) {
   ApiLock lock;
-  if (!name || strncmp(name, "MB_", 3) != 0) return nullptr;
-  if (strcmp(name, "MB_INFO_INPLACE_RING_KERNELS") == 0) {      // (read-only: kernel kinds that took the in-place ring so far, for tests)
+  if (!name) return opt_list();
+  const int id = opt_find(name);
+  if (id < 0) return nullptr;
+  if (id == MB_INFO_INPLACE_RING_KERNELS) {      // (read-only: kernel kinds that took the in-place ring so far, for tests)
     static thread_local std::string v;
     v = std::to_string(medium_inplace_kernels());
     return v.c_str();
   }
-  return opt_env(name);
+  return opt_raw((Opt)id);
 }
 
 mb_machine *mb_machine_create(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_t nTrans, const uint32_t *src,
@@ -1236,7 +1219,7 @@ static int forward_onetape_split(mb_batch *b, WideProgram &W, double *d_ll) {
   // where the Forward one takes 120): the cut goes where both halves end together under the planner's model
   if (WB) {
     const double cF = wide_parts_cost(m, W, n, device_cus() / 2, pre.data()), cB = wide_parts_cost(m, *WB, n, device_cus() / 2, suf.data());
-    if (cF > 0.0 && cB > 0.0 && env_int("MB_ONETAPE_SPLIT_BALANCE", 1)) cutAt(std::min(0.65, std::max(0.35, cB / (cF + cB))));
+    if (cF > 0.0 && cB > 0.0 && opt_int<MB_ONETAPE_SPLIT_BALANCE>()) cutAt(std::min(0.65, std::max(0.35, cB / (cF + cB))));
   }
   if (!WB) return 1;
   SmBuf<PairDesc> d_pre, d_suf;
@@ -1265,7 +1248,7 @@ static int forward_onetape(mb_batch *b, double *d_ll) {
   if (!W) return 1;
   int minLen = 1 << 30;
   for (const PairDesc &pd : b->pairs) minLen = std::min(minLen, m->nOut ? pd.outLen : pd.inLen);
-  if (env_int("MB_ONETAPE_SPLIT", 1) && 2 * b->nPairs <= device_cus() && minLen >= env_int("MB_ONETAPE_SPLIT_MIN_LEN", 64) && second_stream())
+  if (opt_int<MB_ONETAPE_SPLIT>() && 2 * b->nPairs <= device_cus() && minLen >= opt_int<MB_ONETAPE_SPLIT_MIN_LEN>() && second_stream())
     return forward_onetape_split(b, *W, d_ll);
   int rc = timed([&] { return wide_fill(m, *W, b->d_pairs, b->nPairs, tape_of(b), nullptr, d_ll, g_stream, false, b->pairs.data(), device_cus()); });
   g_last_kernel = wide_kernel_name(*W);
@@ -1355,17 +1338,17 @@ static int run_fill_loglike(mb_batch *b, int mode, int flags, double *loglike) {
   if (fwd && use_small(m) && small_can_run(((FastState *)m->fast)->smF, SM_SUM, !rolling, b->hasEnv)) return small_forward(b, flags, loglike);
   SmBuf<double> d_ll;
   MB_HIP(d_ll.alloc(b->nPairs));
-  const bool belowMinPairs = b->nPairs < env_int("MB_ROLLING_MIN_PAIRS", 192);
+  const bool belowMinPairs = b->nPairs < opt_int<MB_ROLLING_MIN_PAIRS>();
   const bool fewPairs = belowMinPairs && (size_t)b->maxPairCells * 8 * 2 <= budget_bytes();
   int rc = -1;      // (-1: no route has taken the call yet)
   if (fwd && !b->hasEnv && wide_applicable(m) && g_kernel_choice != 1 && (rolling || (size_t)b->totalCells * 8 > budget_bytes()))
     rc = forward_onetape(b, d_ll);
-  else if (fwd && rolling && use_medium(m) && !wide_applicable(m) && env_int("MB_MEDIUM_ROLLTILES", 1) && (belowMinPairs || b->hasEnv))
+  else if (fwd && rolling && use_medium(m) && !wide_applicable(m) && opt_int<MB_MEDIUM_ROLLTILES>() && (belowMinPairs || b->hasEnv))
     rc = forward_rolltiles(b, d_ll);      // -1: its kernel is unavailable -- the routes below take the call, from a clean slate
   if (rc < 0) {
     reset_last();
     if (fwd && rolling && !fewPairs && !b->hasEnv && use_medium(m)) rc = forward_rolling_halo(b, d_ll);
-    else if (fwd && !b->hasEnv && use_medium(m) && env_int("MB_MEDIUM_PIPELINE", 1) && (size_t)b->totalCells * 8 > budget_bytes()) rc = forward_pipelined(b, d_ll);
+    else if (fwd && !b->hasEnv && use_medium(m) && opt_int<MB_MEDIUM_PIPELINE>() && (size_t)b->totalCells * 8 > budget_bytes()) rc = forward_pipelined(b, d_ll);
     else rc = forward_chunked(b, mode, d_ll);
   }
   if (!rc) rc = fetch_loglike(loglike, d_ll, b->nPairs);
@@ -1448,7 +1431,7 @@ static int viterbi_chunks(mb_batch *b, double *loglike, int64_t *pathOff, uint32
         else {
           // one-tape machines beyond the LDS edge tables of the generic walkers: columns in LDS, one trip to memory per step
           WideTbPlan *T = nullptr;
-          if (wide_applicable(m) && g_kernel_choice != 1 && m->nTrans > env_int("MB_ONETAPE_TRACEBACK_MIN_TRANS", 3584) && !b->hasEnv) {
+          if (wide_applicable(m) && g_kernel_choice != 1 && m->nTrans > opt_int<MB_ONETAPE_TRACEBACK_MIN_TRANS>() && !b->hasEnv) {
             FastState *f = fast_state(m);
             if (!f->wTb.tried) (void)wide_traceback_build(m, f->wTb);
             if (f->wTb.ok) T = &f->wTb;
@@ -1481,7 +1464,7 @@ static int batch_viterbi(mb_batch *b, double *loglike, int64_t *pathOff, uint32_
   if (use_small(b->m) && small_can_run(((FastState *)b->m->fast)->smF, SM_TB, false, b->hasEnv)) return small_viterbi(b, loglike, pathOff, pathEdges, pathCap);
   // tiled family: one traceback byte per cell when the machine's exact program allows it
   MedGeom *tbGeo = nullptr;
-  if (!wide_applicable(b->m) && use_medium(b->m) && env_int("MB_MEDIUM_TB", 1) && medium_tb_program(b->m, &tbGeo) &&
+  if (!wide_applicable(b->m) && use_medium(b->m) && opt_int<MB_MEDIUM_TB>() && medium_tb_program(b->m, &tbGeo) &&
       traceback_bytes_lds(b->m, medium_tb_stride(b->m->S))) {
     const int rc = viterbi_chunks(b, loglike, pathOff, pathEdges, pathCap, 1);
     if (rc >= 0) return rc;
@@ -1495,7 +1478,7 @@ static int batch_viterbi(mb_batch *b, double *loglike, int64_t *pathOff, uint32_
   // 256 x 4 kb 28 vs 42 ms, 64 x 2 kb 13.3 vs 14.2, the whole fn3 composite (L2-resident ring) 158 vs 171 -- and 557 GB of fp64 for
   // that machine at 64 x 50 kb could not be resident at all.  (Until the reduction was split into two butterflies the sweep cost
   // 29 % and the route was taken only when memory asked for it.)
-  const bool tbWanted = env_int("MB_ONETAPE_TB", 1) != 0;
+  const bool tbWanted = opt_int<MB_ONETAPE_TB>() != 0;
   if (pathEdges && pathOff && !b->hasEnv && tbWanted && wide_tb_program(b->m)) {
     const int rc = viterbi_chunks(b, loglike, pathOff, pathEdges, pathCap, 2);
     if (rc >= 0) return rc;
@@ -1513,8 +1496,8 @@ struct AccurateFills { bool on; explicit AccurateFills(bool o) : on(o) { if (on)
 static bool accurate_fills_wanted(const mb_machine *m, const std::vector<PairDesc> &hp) {
   int longest = 0;
   for (const PairDesc &pd : hp) longest = std::max(longest, std::max(pd.inLen, pd.outLen));
-  const int accMode = env_int("MB_ONETAPE_COUNT_FP64", -1);
-  return wide_applicable(m) && (accMode == 1 || (accMode != 0 && longest >= env_int("MB_ONETAPE_COUNT_FP64_MIN_LEN", 10000)));
+  const int accMode = opt_int<MB_ONETAPE_COUNT_FP64>();
+  return wide_applicable(m) && (accMode == 1 || (accMode != 0 && longest >= opt_int<MB_ONETAPE_COUNT_FP64_MIN_LEN>()));
 }
 
 // roll: the tiled family's count sweep WITHOUT a Forward matrix (medium_counts_rolling) -- one matrix per pair instead of two,
@@ -1547,7 +1530,7 @@ static int counts_chunks(mb_batch *b, double *counts, double *loglikeSum, double
       // sequences than CUs leaves most of the chip idle, so the two run side by side (64 sequences: 64 + 64 CUs); the count kernel
       // waits for both.  Without a second stream, programs that share no kernel are filled one after the other below.
       bool fwdDone = false;
-      if (!roll && !b->hasEnv && wide_applicable(m) && g_kernel_choice != 1 && env_int("MB_ONETAPE_CONCURRENT_FILLS", 1)) {
+      if (!roll && !b->hasEnv && wide_applicable(m) && g_kernel_choice != 1 && opt_int<MB_ONETAPE_CONCURRENT_FILLS>()) {
         WideProgram *WB = wide_program(m, MB_BACKWARD), *WF = wide_program(m, MB_FORWARD);
         if (!WB || !WF) return 1;
         const int rc = onetape_fill_pair(m, *WF, *WB, d_desc, d_desc, hp.data(), hp.data(), np, tape_of(b), fwd, bwd, false,
@@ -1578,7 +1561,7 @@ static int counts_chunks(mb_batch *b, double *counts, double *loglikeSum, double
         if (!fwdDone) if (const int rc = fill_chunk(m, MB_FORWARD, d_desc, hp, b->d_in, b->d_out, fwd, 0, b)) return rc;
         if (const int rc = launch_gather_loglike(d_desc, np, fwd, m->S, 0, d_ll + c.p0, g_stream)) return rc;
         // one-tape machines: a lane owns a transition and walks the columns (mb_wide.hip); two tapes: one thread per cell
-        const bool oneTape = ((m->nIn != 0) != (m->nOut != 0)) && g_kernel_choice != 1 && env_int("MB_ONETAPE_COUNTS", 1);
+        const bool oneTape = ((m->nIn != 0) != (m->nOut != 0)) && g_kernel_choice != 1 && opt_int<MB_ONETAPE_COUNTS>();
         int rc;
         if (usage3) {
           rc = usage_launch(m, fast_state(m)->usage, d_desc, hp, b->d_in, b->d_out, fwd, bwd, d_counts, g_stream);
@@ -1611,7 +1594,7 @@ int mb_batch_counts(mb_batch *b, double *counts, double *loglikeSum, double *log
 }
 static int batch_counts(mb_batch *b, double *counts, double *loglikeSum, double *loglike) {
   reset_last();
-  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
+  latch_deterministic();
   if (b->nPairs == 0) return 0;
   if (use_small(b->m) && small_count_fits(((FastState *)b->m->fast)->smF, b->hasEnv) && small_can_run(((FastState *)b->m->fast)->smB, SM_SUM, true, b->hasEnv))
     return small_counts(b, counts, loglikeSum, loglike);
@@ -1622,14 +1605,14 @@ static int batch_counts(mb_batch *b, double *counts, double *loglikeSum, double 
   // where 256 pairs through the pipeline would take 280).  So the fused sweep is the default; MB_MEDIUM_COUNT_PASSES=3 asks for the three
   // passes (a host with few long pairs and memory to spare; the parity tests).
   if (!wide_applicable(b->m) && use_medium(b->m) && !b->hasEnv) {
-    const int passes = env_int("MB_MEDIUM_COUNT_PASSES", 0);
+    const int passes = opt_int<MB_MEDIUM_COUNT_PASSES>();
     FastState *f = fast_state(b->m);
     if (f->mediumOk && passes == 3 && (size_t)b->maxPairCells * 16 <= budget_bytes()) {
       if (!f->usage.tried) usage_build(b->m, f->usage);
       if (f->usage.ok) return counts_chunks(b, counts, loglikeSum, loglike, false, true);
     }
   }
-  if (!wide_applicable(b->m) && use_medium(b->m) && fast_state(b->m)->countOk && env_int("MB_MEDIUM_COUNTS_ROLL", 1)) {
+  if (!wide_applicable(b->m) && use_medium(b->m) && fast_state(b->m)->countOk && opt_int<MB_MEDIUM_COUNTS_ROLL>()) {
     const int rc = counts_chunks(b, counts, loglikeSum, loglike, true);
     if (rc >= 0) return rc;
     reset_last();
@@ -1662,7 +1645,7 @@ int mb_fill_env(mb_machine *m, int mode, const int32_t *in, int64_t inLen, const
   int rc = 0;
   if (n * 8ull > budget_bytes()) { set_error("matrix exceeds the device memory budget"); rc = 1; }
   if (!rc && !(pool = (double *)ws_get(0, n * sizeof(double)))) rc = 1;
-  if (!rc && env_int("MB_DEBUG_POISON", 0)) (void)hipMemsetAsync(pool, 0xFF, n * sizeof(double), g_stream);
+  if (!rc && opt_int<MB_DEBUG_POISON>()) (void)hipMemsetAsync(pool, 0xFF, n * sizeof(double), g_stream);
   for (int attempt = 0; attempt < 2 && !rc; ++attempt) {      // (a second time when the exchange between the parts of a one-tape sweep timed out: see with_parts_retry)
     rc = fill_chunk(m, mode, b->d_pairs, b->pairs, b->d_in, b->d_out, pool, mode == MB_FORWARD ? startState : 0, b);
     if (!rc && !hip_ok(hipStreamSynchronize(g_stream), "fill kernel")) rc = 1;

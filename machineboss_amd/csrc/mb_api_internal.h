@@ -56,7 +56,6 @@ struct Chunk { long long p0, p1, cells; };
 int d2h_large(void *dst, const void *srcDev, size_t bytes);
 // an error path is about to release what launched kernels may still read: wait for both streams
 void quiesce_streams();
-int env_int(const char *name, int dflt);
 
 // ---- what the batch calls of every family share ----------------------------------------------------------------------------------
 // A call-scoped device buffer of the small-block cache (sm_alloc), one element at the least; it goes back when the scope ends.

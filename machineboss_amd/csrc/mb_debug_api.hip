@@ -42,7 +42,7 @@ int mb_debug_jit_source(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_
   if (mode == MED_MODE_COUNT) {
     if (!medium_build_count_host(&m, G, P, geo, closure)) { set_error("machine does not qualify for the fused count kernel"); return 1; }
   } else if (!medium_build_host(&m, backward != 0, closure, G, P, geo)) return 1;
-  if (opt_env("MB_MEDIUM_JIT_VERBOSE")) {
+  if (opt_present<MB_MEDIUM_JIT_VERBOSE>()) {
     const long long c = medium_program_cost(P); int syncs = 0;
     for (const MedRoundInfo &ri : P.roundInfo) syncs += ri.sync;
     fprintf(stderr, "[mbhip] program cost %lld (rounds %zu, syncs %d, pairs %d, levels %d)\n", c, P.roundInfo.size(), syncs, P.nPairs, backward ? m.nLevB : m.nLevF);
@@ -233,7 +233,7 @@ int mb_debug_wide_jit(int32_t nStates, int32_t nInTok, int32_t nOutTok, int64_t 
   // kernel spills (mb_wide_jit.cpp, wide_jit_plan; MB_WIDE_JIT_ATTEMPT: the attempt to start from -- the device-free replays of the later ones)
   std::vector<WideJitDesc> descs;
   std::string code, obj;
-  for (int attempt = std::max(0, std::min(env_int("MB_WIDE_JIT_ATTEMPT", 0), WIDE_JIT_ATTEMPTS - 1));; ++attempt) {
+  for (int attempt = std::max(0, std::min(opt_int<MB_WIDE_JIT_ATTEMPT>(), WIDE_JIT_ATTEMPTS - 1));; ++attempt) {
     std::string why;
     if (!wide_jit_plan(ins, acc != 0, attempt, descs, &why)) { set_error("mb_debug_wide_jit: " + why); return 1; }
     code = wide_jit_source(descs, F);

@@ -13,7 +13,6 @@
 
 namespace mb {
 
-static int env_int_g(const char *name, int dflt) { const char *v = opt_env(name); return v && *v ? atoi(v) : dflt; }
 
 // ---- DPMatrix::accumulate over `incoming` (src/dpmatrix.h:101-115) -----------------------------------------
 template <int MODE>
@@ -627,14 +626,14 @@ int launch_traceback(const mb_machine *m, const PairDesc *d_pairs, long long nPa
   const long long nRows = (long long)m->S * m->K;
   const size_t ldsBytes = (((size_t)(nRows + 1) * 4 + 15) & ~(size_t)15) + (size_t)m->nTrans * sizeof(TbEdge);
   static int useLds = -1;
-  if (useLds < 0) { const char *e = opt_env("MB_TRACEBACK_LDS"); useLds = (e && *e == '0') ? 0 : 1; }
+  if (useLds < 0) { const char *e = opt_text<MB_TRACEBACK_LDS>(); useLds = (e && *e == '0') ? 0 : 1; }
   if (useLds && nRows <= 8192 && m->nTrans <= 2048 && m->S <= 65535 && ldsBytes <= 64 * 1024) {
     hipLaunchKernelGGL(k_traceback_lds<true>, dim3((unsigned)((nPairs + 3) / 4)), dim3(256), ldsBytes, st, m->dev, d_pairs, nPairs,
                        (long long)m->nTrans, d_in, d_out, d_pool, d_slotOff, d_pathBuf, d_pathLen);
     return hip_ok(hipGetLastError(), "traceback launch") ? 0 : 1;
   }
   const size_t scanBytes = (size_t)m->nTrans * sizeof(TbEdgeK) + (size_t)(m->S + 1) * 4;   // edges (<= 56 KB) + one offset per state
-  if (useLds && m->nTrans <= 3584 && m->S <= 8192 && m->K <= 65535 && env_int_g("MB_TRACEBACK_SCAN", 1)) {
+  if (useLds && m->nTrans <= 3584 && m->S <= 8192 && m->K <= 65535 && opt_int<MB_TRACEBACK_SCAN>()) {
     static bool attr = false;   // up to 56 KB + 32 KB: beyond the 64 KB a kernel may use without asking
     if (!attr) { (void)hipFuncSetAttribute((const void *)&k_traceback_scan, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
     hipLaunchKernelGGL(k_traceback_scan, dim3((unsigned)((nPairs + 3) / 4)), dim3(256), scanBytes, st,

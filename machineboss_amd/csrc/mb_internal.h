@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "mbhip.h"
+#include "mb_options.h"
 
 namespace mb {
 
@@ -97,16 +98,13 @@ struct mb_batch {
 
 namespace mb {
 void set_error(const std::string &msg);
-// Tuning knobs: `mb_set_option` keeps them in a table of the LIBRARY -- it does not write the process environment --
-// and every reader asks here: the table first, then the environment (the defaults a host sets before it starts).
-const char *opt_env(const char *name);
-void opt_set(const char *name, const char *value);      // value nullptr / "": back to the environment's (or the built-in) default
 // MB_DETERMINISTIC=1 (read when a count call begins): posterior counts are summed in 64-bit FIXED POINT wherever the order of the
 // additions depends on scheduling (LDS accumulators shared by wavefronts, global accumulators shared by tiles) -- integer addition
 // is associative, so `--counts / --train` reproduce bit for bit from run to run like the reference's serial loop
 // (src/counts.cpp:37-64).  Scales: 2^-44 inside a tile (a tile's partial sum stays below 2^11), 2^-36 in global memory (a count
 // below 6.7e7 per call; beyond it the call fails, det_to_double); lane-private partial sums (registers, fixed shuffle trees) are deterministic as they are.
 extern bool g_deterministic;
+void latch_deterministic();      // every count entry point calls it first
 constexpr double MB_DET_TILE_SCALE = 17592186044416.0;   // 2^44
 constexpr double MB_DET_GLOBAL_SCALE = 68719476736.0;     // 2^36
 // A global fixed-point accumulator as a count.  The device clamps every term to [0, 2^62] before its cast (a NaN, a negative or a

@@ -31,7 +31,7 @@ static std::string g_moreOpts;
 void jit_more_opts(const char *opts) { g_moreOpts = opts ? opts : ""; }
 static std::vector<std::string> extra_opts() {
   std::vector<std::string> v;
-  const char *e = opt_env("MB_JIT_EXTRA_OPTS");
+  const char *e = opt_text<MB_JIT_EXTRA_OPTS>();
   const std::string all = std::string(e ? e : "") + " " + g_moreOpts;
   std::string cur;
   for (const char *p = all.c_str();; ++p) {
@@ -67,12 +67,12 @@ static bool dir_is_private(const std::string &d) {
   return S_ISDIR(st.st_mode) && st.st_uid == getuid() && (st.st_mode & (S_IWGRP | S_IWOTH)) == 0 && access(d.c_str(), W_OK) == 0;
 }
 
-// read on every compile: mb_set_option("MB_JIT_CACHE", "0") or a new MB_JIT_CACHE_DIR takes effect at once
+// read on every compile: MB_JIT_CACHE=0 or a new MB_JIT_CACHE_DIR, through mb_set_option as well, takes effect at once
 static std::string cache_dir() {
-  const char *off = opt_env("MB_JIT_CACHE");
+  const char *off = opt_text<MB_JIT_CACHE>();
   if (off && *off == '0') return "";
   std::string d;
-  if (const char *e = opt_env("MB_JIT_CACHE_DIR")) d = e;
+  if (const char *e = opt_text<MB_JIT_CACHE_DIR>()) d = e;
   else if (const char *x = getenv("XDG_CACHE_HOME")) d = std::string(x) + "/mbhip";
   else if (const char *h = getenv("HOME")) d = std::string(h) + "/.cache/mbhip";
   static std::string validated;      // the last directory that passed (mkdir + ownership check are not repeated for it)

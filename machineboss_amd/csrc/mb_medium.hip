@@ -379,11 +379,6 @@ struct Cand { int src; int wref; };   // src: index into the LDS state vector; w
 std::vector<int> g_medium_cuts;
 void medium_set_cuts(const std::vector<int> &cuts) { g_medium_cuts = cuts; }
 
-static int env_int_m(const char *name, int dflt) {
-  const char *v = opt_env(name);
-  return v && *v ? atoi(v) : dflt;
-}
-
 static double host_lse(double a, double b) {
   if (a == -INFINITY) return b;
   if (b == -INFINITY) return a;
@@ -458,7 +453,7 @@ static void build_program(const mb_machine *m, bool backward, int closure, int G
     // explicit stage boundaries (first silent level of stages 2, 3, ...): set by the chooser (medium_set_cuts) or
     // MB_MEDIUM_CUTS="l1,l2,..." for experiments; levels need not be cut evenly -- a cut belongs where the closure is cheap
     std::vector<int> cuts = g_medium_cuts;
-    if (const char *e = opt_env("MB_MEDIUM_CUTS")) { cuts.clear(); for (const char *q = e; *q;) { cuts.push_back(atoi(q)); while (*q && *q != ',') ++q; if (*q) ++q; } }
+    if (const char *e = opt_text<MB_MEDIUM_CUTS>()) { cuts.clear(); for (const char *q = e; *q;) { cuts.push_back(atoi(q)); while (*q && *q != ',') ++q; if (*q) ++q; } }
     if (!cuts.empty()) {
       std::sort(cuts.begin(), cuts.end());
       for (int s = 0; s < S; ++s)
@@ -511,7 +506,7 @@ static void build_program(const mb_machine *m, bool backward, int closure, int G
   bool anySplit = false, anySplitCur = false;
   int extraStages = 0;
   {
-    const int splitAt = allowSplit ? env_int_m("MB_MEDIUM_SPLIT_DEGREE", 8) : 0, part = std::max(2, env_int_m("MB_MEDIUM_SPLIT_PART", 8));
+    const int splitAt = allowSplit ? opt_int<MB_MEDIUM_SPLIT_DEGREE>() : 0, part = std::max(2, opt_int<MB_MEDIUM_SPLIT_PART>());
     const int seedStage = closure ? 0 : lev[startNode];
     std::vector<Node> outNodes;
     for (Node &n : nodes) {
@@ -645,7 +640,7 @@ static void build_program(const mb_machine *m, bool backward, int closure, int G
       for (int id : rounds[r]) nsT[T] = std::max(nsT[T], sig(nodes[id])[T]);
       total += nsT[T];
     }
-    if (env_int_m("MB_MEDIUM_JIT_VERBOSE", 0) >= 2) {
+    if (opt_int<MB_MEDIUM_JIT_VERBOSE>() >= 2) {
       int used = 0;
       for (int id : rounds[r]) { const auto d = sig(nodes[id]); used += d[0] + d[1] + d[2] + d[3]; }
       fprintf(stderr, "[mbhip]   round %d: stage %d, %zu of %d lanes, slots match/in/out/cur %d/%d/%d/%d, %d of %d lane-slots carry a candidate\n", r, nodes[rounds[r][0]].stage,
@@ -711,7 +706,7 @@ static void build_program(const mb_machine *m, bool backward, int closure, int G
       if (firstSync < 0) { slots0 += (long long)ri.slots.size(); if (ri.sync) firstSync = (int)r; }
     }
     if (firstSync < 0) firstSync = (int)P.roundInfo.size() - 1;
-    P.inPlaceOk = closure != 0 && lastEmit >= 0 && lastEmit <= firstSync && !anyBig && slots0 <= env_int_m("MB_MEDIUM_INPLACE_MAXSLOTS", 48);
+    P.inPlaceOk = closure != 0 && lastEmit >= 0 && lastEmit <= firstSync && !anyBig && slots0 <= opt_int<MB_MEDIUM_INPLACE_MAXSLOTS>();
   }
   P.fusedEmit = fuse;
   if (!fuse) for (MedRoundInfo &ri : P.roundInfo) ri.fused = false;
@@ -815,10 +810,10 @@ bool medium_build_host(const mb_machine *m, bool backward, int closure, int G, M
 // 670 KB per step and CU -- the L1 fill rate, not HBM, bounded the kernel).  Give columns up -- down to half -- until
 // the records that cannot sit in VGPRs fit next to the ring.
 void medium_fit_records(const mb_machine *m, const MedProgram &P, MedGeom &geo) {
-  const char *e = opt_env("MB_MEDIUM_MAXWAVES");
+  const char *e = opt_text<MB_MEDIUM_MAXWAVES>();
   if (e && atoi(e) > 0 && atoi(e) < geo.waves) { geo.waves = atoi(e); geo.C = geo.waves * P.G; }
-  if (opt_env("MB_MEDIUM_FIT_RECORDS") && atoi(opt_env("MB_MEDIUM_FIT_RECORDS")) == 0) return;
-  if (P.counting && env_int_m("MB_MEDIUM_COUNT_FIT", 1) == 0) return;
+  if (const char *fit = opt_text<MB_MEDIUM_FIT_RECORDS>()) if (atoi(fit) == 0) return;
+  if (P.counting && opt_int<MB_MEDIUM_COUNT_FIT>() == 0) return;
   const long long ntokT[4] = {(long long)(m->nIn + 1) * (m->nOut + 1), m->nIn + 1, m->nOut + 1, 1};
   long long slotsT[4] = {0, 0, 0, 0};
   for (const MedRoundInfo &ri : P.roundInfo) for (const MedSlotInfo &sl : ri.slots) ++slotsT[sl.T];
@@ -826,7 +821,7 @@ void medium_fit_records(const mb_machine *m, const MedProgram &P, MedGeom &geo) 
   // machines with a handful of states: a step is shorter than the acknowledgement of the previous step's stores, and on
   // gfx9 any vector load waits for those (one in-order vmcnt) -- so the halo supercells of a whole tile are fetched in
   // the tile's prologue instead (MedGeom::haloSteps), if 32 KB of LDS buy that
-  const bool wantHaloTile = env_int_m("MB_MEDIUM_HALO_TILE", 1) != 0 && !P.counting;
+  const bool wantHaloTile = opt_int<MB_MEDIUM_HALO_TILE>() != 0 && !P.counting;
   auto haloStepsFor = [&](int C) { const long long cap = std::max(C, 128); return (wantHaloTile && cap * m->S * 8 <= 32 * 1024) ? (int)cap : 0; };
   while (true) {
     const int regBudget = std::max(0, std::min(512 / ((geo.waves + 3) / 4), 256) - 84);
@@ -928,10 +923,10 @@ static void append_flat_usage(const mb_machine *m, MedProgram &P) {
 
 // Geometry leaves room for one Backward supercell per column and the count array in LDS, and keeps the workgroup at 8 wavefronts.
 bool medium_build_count_host(const mb_machine *m, int G, MedProgram &P, MedGeom &geo, int closure, const std::vector<int> &cuts) {
-  const bool flat = env_int_m("MB_MEDIUM_COUNT_FLAT", 1) != 0;
+  const bool flat = opt_int<MB_MEDIUM_COUNT_FLAT>() != 0;
   if (flat) {
     medium_set_cuts(cuts);
-    build_program(m, false, closure, G, P, /*allowSplit=*/true, /*countFuse=*/env_int_m("MB_MEDIUM_COUNT_FUSE", 1) != 0);
+    build_program(m, false, closure, G, P, /*allowSplit=*/true, /*countFuse=*/opt_int<MB_MEDIUM_COUNT_FUSE>() != 0);
     medium_set_cuts({});
   } else
     build_program(m, false, 0, G, P, /*allowSplit=*/false);   // counting terms need every candidate beside its real destination
@@ -950,7 +945,7 @@ bool medium_build_count_host(const mb_machine *m, int G, MedProgram &P, MedGeom 
     }
   medium_jit_plan(m, P, geo);
   medium_count_layout(m, P);
-  if (flat && env_int_m("MB_MEDIUM_COUNT_COMPACT", 1)) {
+  if (flat && opt_int<MB_MEDIUM_COUNT_COMPACT>()) {
     // the placement says which usage records are loop-invariant: only the others need an accumulator that lives through the step loop.
     // With that (smaller) table the geometry is taken again -- more columns -- and the placement with it.
     MedGeom geo2;
@@ -973,7 +968,7 @@ bool medium_build_count_host(const mb_machine *m, int G, MedProgram &P, MedGeom 
 // upper half of srcOff.  MB_MEDIUM_COUNT_COMPACT=0: one table of nTrans + LPG entries for both, as in round 4.
 void medium_count_layout(const mb_machine *m, MedProgram &P) {
   if (!P.counting || !P.flatCount) return;
-  const bool compact = env_int_m("MB_MEDIUM_COUNT_COMPACT", 1) != 0;
+  const bool compact = opt_int<MB_MEDIUM_COUNT_COMPACT>() != 0;
   const int LPG = P.LPG;
   const long long ntokT[4] = {(long long)(m->nIn + 1) * (m->nOut + 1), m->nIn + 1, m->nOut + 1, 1};
   std::vector<int> compactOf((size_t)m->nTrans, -1);
@@ -1034,7 +1029,7 @@ bool medium_geometry(const mb_machine *m, const MedProgram &P, MedGeom &geo) {
   if (maxCols < P.G) return false;
   // one or two lanes per supercell (machines with a handful of states): a 512-column strip wastes half its steps on
   // the skewed start/end of a 1 kb sweep; 8 wavefronts (256 columns) measured best on dnapsw / protpsw
-  int waves = (int)std::min<long long>(maxCols / P.G, P.counting ? std::max(1, std::min(16, env_int_m("MB_MEDIUM_COUNT_MAXWAVES", 8))) : (P.LPG <= 2 ? 8 : 16));
+  int waves = (int)std::min<long long>(maxCols / P.G, P.counting ? std::max(1, std::min(16, opt_int<MB_MEDIUM_COUNT_MAXWAVES>())) : (P.LPG <= 2 ? 8 : 16));
   // S must be covered by 4 halo registers per thread
   while (waves < 16 && (long long)waves * 64 * 4 < m->S && (long long)(waves + 1) * P.G <= maxCols) ++waves;
   if ((long long)waves * 64 * 4 < m->S || (long long)waves * P.G > maxCols) return false;
@@ -1124,7 +1119,7 @@ static int launch_wavefront(const mb_machine *m, MedProgram &P, const MedProgDev
     static hipStream_t extra[MAXG - 1] = {nullptr, nullptr, nullptr}; static bool tried = false;
     if (!tried) { tried = true; for (int k = 0; k < MAXG - 1; ++k) if (hipStreamCreateWithFlags(&extra[k], hipStreamNonBlocking) != hipSuccess) extra[k] = nullptr; }
     long long peak = 0;
-    const int want = std::min(MAXG, env_int_m("MB_MEDIUM_STREAMS", 2));
+    const int want = std::min(MAXG, opt_int<MB_MEDIUM_STREAMS>());
     if (twoStreams && want > 1) {
       for (const PairDesc &pd : pairs) peak += (pd.inLen + C) / C;                      // tiles of a launch on the plateau: every strip of every pair
       if (peak < 16 * 256)                                                              // (far more tiles than slots: the tail is noise)
@@ -1204,8 +1199,8 @@ static int launch_wavefront(const mb_machine *m, MedProgram &P, const MedProgDev
 // Round 6: a sweep over FEW pairs is bound by its chain of launches, not by the tiles' prologues, and a chain of 64-step tiles is the
 // shorter one (482-state E-step: 6 pairs 220 -> 180 ms, 12 pairs 297 -> 280 ms; scripts/c4b_scale_probe.py).
 static int tile_steps(int C, size_t nPairs, int maxOut) {
-  int TS = std::max(C, (maxOut >= 4096 && nPairs >= (size_t)env_int_m("MB_MEDIUM_TS_LONG_MIN_PAIRS", 32)) ? 128 : 64);
-  const char *e = opt_env("MB_MEDIUM_TS");
+  int TS = std::max(C, (maxOut >= 4096 && nPairs >= (size_t)opt_int<MB_MEDIUM_TS_LONG_MIN_PAIRS>()) ? 128 : 64);
+  const char *e = opt_text<MB_MEDIUM_TS>();
   if (e && atoi(e) >= C) TS = atoi(e);
   return TS;
 }
@@ -1216,7 +1211,7 @@ MedGeom medium_pick_geometry(const MedProgram &P, const MedGeom &geo, const std:
   // workgroup for the materialised kernels (2 for the rolling one, which has no stores to hide).
   MedGeom best = geo;
   best.level = 0;
-  if (pairs.empty() || env_int_m("MB_MEDIUM_ADAPT_WIDTH", 1) == 0) return best;
+  if (pairs.empty() || opt_int<MB_MEDIUM_ADAPT_WIDTH>() == 0) return best;
   int maxIn = 0;
   for (const PairDesc &pd : pairs) maxIn = std::max(maxIn, pd.inLen);
   const int minWaves = std::min(geo.waves, materialise ? 4 : 2);
@@ -1241,7 +1236,7 @@ long long medium_inplace_kernels() { return g_inplace_kernels; }
 MedGeom medium_roll_geometry(const mb_machine *m, MedProgram &P, const MedGeom &geoIn, const std::vector<PairDesc> &pairs, int mode, int matKind, bool env, bool materialiseRule) {
   const int kind = (3 * medium_jit_index(mode) + matKind) * 2 + (env ? 1 : 0);
   auto plain = [&]() { MedGeom g = medium_pick_geometry(P, geoIn, pairs, materialiseRule); g.env = env; g.haloSteps = 0; return g; };
-  if (matKind == MED_MAT_FULL || mode != MB_FORWARD || P.counting || P.recC.empty() || !P.d_recC || P.LPG <= 2 || env_int_m("MB_MEDIUM_INPLACE_RING", 0) == 0) return plain();      // (off by default: measured, it does not pay -- DESIGN.md 4.1d)
+  if (matKind == MED_MAT_FULL || mode != MB_FORWARD || P.counting || P.recC.empty() || !P.d_recC || P.LPG <= 2 || opt_int<MB_MEDIUM_INPLACE_RING>() == 0) return plain();      // (off by default: measured, it does not pay -- DESIGN.md 4.1d)
   if (P.compactState[kind] < 0) return plain();
   if (P.compactState[kind] == 0) {
     P.compactState[kind] = -1;
@@ -1249,7 +1244,7 @@ MedGeom medium_roll_geometry(const mb_machine *m, MedProgram &P, const MedGeom &
     if ((long long)P.Spad + (long long)P.NS * KC >= (long long)P.NS * P.Spad) return plain();      // nothing to gain (nearly every state is read across columns)
     MedGeom g = geoIn;
     g.compact = true; g.env = env; g.haloSteps = 0; g.level = 0;
-    const int maxWaves = std::min(16, env_int_m("MB_MEDIUM_COMPACT_MAXWAVES", 12));
+    const int maxWaves = std::min(16, opt_int<MB_MEDIUM_COMPACT_MAXWAVES>());
     for (g.waves = maxWaves; g.waves >= geoIn.waves; --g.waves) {      // (the same wavefront count is allowed: the in-place ring also drops an address add per candidate)
       g.C = g.waves * P.G;
       g.ldsBytes = (size_t)(g.C + 1) * (size_t)(P.Spad + P.NS * KC) * sizeof(double);
@@ -1263,14 +1258,14 @@ MedGeom medium_roll_geometry(const mb_machine *m, MedProgram &P, const MedGeom &
     // (9 ... 12 wavefronts leave a wavefront the same 168 registers, 5 ... 8 the same 256: at most two attempts -- the most wavefronts
     //  the LDS allows, then 8 when that is still more than the plain ring's)
     bool ok = medium_jit_get(m, P, g, mode, matKind, /*allowReplan=*/false);
-    if (opt_env("MB_MEDIUM_JIT_VERBOSE")) fprintf(stderr, "[mbhip] in-place ring (mode %d, matrix kind %d%s): %zu of %d states per short vector, %d wavefronts -> %s\n", mode, matKind, env ? ", envelopes" : "",
+    if (opt_present<MB_MEDIUM_JIT_VERBOSE>()) fprintf(stderr, "[mbhip] in-place ring (mode %d, matrix kind %d%s): %zu of %d states per short vector, %d wavefronts -> %s\n", mode, matKind, env ? ", envelopes" : "",
                                                   P.haloStates.size(), m->S, g.waves, ok ? "in use" : "does not fit its registers");
     if (!ok && g.waves > 8 && geoIn.waves < 8) {
       J = MedJit();
       g.waves = 8; g.C = g.waves * P.G;
       g.ldsBytes = (size_t)(g.C + 1) * (size_t)(P.Spad + P.NS * KC) * sizeof(double);
       ok = medium_jit_get(m, P, g, mode, matKind, /*allowReplan=*/false);
-      if (opt_env("MB_MEDIUM_JIT_VERBOSE")) fprintf(stderr, "[mbhip] in-place ring: 8 wavefronts -> %s\n", ok ? "in use" : "does not fit its registers: plain ring");
+      if (opt_present<MB_MEDIUM_JIT_VERBOSE>()) fprintf(stderr, "[mbhip] in-place ring: 8 wavefronts -> %s\n", ok ? "in use" : "does not fit its registers: plain ring");
     }
     if (!ok) { J = MedJit(); return plain(); }
     P.compactState[kind] = 1;
@@ -1463,8 +1458,8 @@ static int forward_persistent(const mb_machine *m, MedProgram &P, const MedGeom 
     A.pairs = d_pairs; A.inTok = d_in; A.outTok = d_out; A.pool = d_pool; A.colHalo = d_halo; A.haloBase = d_hb;
     A.loglike = d_loglike; A.tiles = d_tk; A.C = C; A.TS = maxOut + C + 1; A.rev = P.backward ? 1 : 0; A.materialise = 1; A.det = g_deterministic ? 1 : 0;
     A.psync = d_sync; A.pwait = d_wait; A.ntickets = (int)tickets.size();
-    A.ptimeout = (long long)std::max(1, env_int_m("MB_MEDIUM_PERSIST_TIMEOUT_S", 20)) * 100000000ll;
-    if (const int us = env_int_m("MB_MEDIUM_PERSIST_TIMEOUT_US", 0)) A.ptimeout = (long long)std::max(us, 1) * 100ll;      // (the tests' way to a time-out)
+    A.ptimeout = (long long)std::max(1, opt_int<MB_MEDIUM_PERSIST_TIMEOUT_S>()) * 100000000ll;
+    if (const int us = opt_int<MB_MEDIUM_PERSIST_TIMEOUT_US>()) A.ptimeout = (long long)std::max(us, 1) * 100ll;      // (the tests' way to a time-out)
     // one workgroup per strip; a workgroup takes its ticket when it starts (whatever its blockIdx), so it waits only for started ones
     const long long grid = (long long)tickets.size();
     ++g_last_launches;
@@ -1499,7 +1494,7 @@ int medium_forward_pipelined(const mb_machine *m, MedProgram &P, const MedGeom &
   const size_t ldsPerWg = std::max<size_t>(medium_jit_lds_bytes(P, geo), 1024);
   const int wgPerCU = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>((160 * 1024) / ldsPerWg, 32 / std::max(geo.waves, 1)), 8));
   const int target = 256 * wgPerCU;
-  if (persist && env_int_m("MB_MEDIUM_PERSIST", -1) != 0) {
+  if (persist && opt_int<MB_MEDIUM_PERSIST>() != 0) {
     const int rc = forward_persistent(m, P, geo, pairsIn, slotCells, d_in, d_out, d_pool, poolCells, d_loglike, st);
     if (rc != -1) return rc;
   }

@@ -23,22 +23,13 @@
 
 namespace mb {
 
-static int env_int_early(const char *name, int dflt) {
-  const char *v = opt_env(name);
-  return v && *v ? atoi(v) : dflt;
-}
-static const int JIT_MAX_CANDS = std::max(2, env_int_early("MB_JIT_MAXCANDS", 12));   // candidates evaluated in one straight-line round body
-
-static int env_int(const char *name, int dflt) {
-  const char *v = opt_env(name);
-  return v && *v ? atoi(v) : dflt;
-}
+static const int JIT_MAX_CANDS = std::max(2, opt_int<MB_JIT_MAXCANDS>());   // candidates evaluated in one straight-line round body (read when the library loads)
 int medium_jit_max_cands() { return JIT_MAX_CANDS; }
 // MB_JIT_DEBUG (kernels with switched-off loads: WRONG results by design) exists only in a library built with
 // -DMB_EXPERIMENTS; a product build ignores the variable, so a stray environment cannot corrupt counts or likelihoods
 static int jit_debug_bits() {
 #ifdef MB_EXPERIMENTS
-  const int v = env_int("MB_JIT_DEBUG", 0);
+  const int v = opt_int<MB_JIT_DEBUG>();
   if (v & 3) { static bool told = false; if (!told) { told = true; fprintf(stderr, "[mbhip] WARNING: MB_JIT_DEBUG=%d -- tile kernels skip loads, results are WRONG by design\n", v); } }
   return v;
 #else
@@ -77,7 +68,7 @@ static size_t lds_payload_bytes(const MedProgram &P, const MedGeom &geo, int mod
 }
 size_t medium_jit_lds_bytes(const MedProgram &P, const MedGeom &geo, int mode) { return lds_payload_bytes(P, geo, mode) + 128; }
 // persistent strips (MED_MAT_PERSIST): halo rows of the strip to the left staged ahead, JPAHEAD + 1 rows of JNHP states behind the rest
-static int persist_ahead() { return std::max(1, std::min(env_int("MB_MEDIUM_PERSIST_AHEAD", 16), 256)); }
+static int persist_ahead() { return std::max(1, std::min(opt_int<MB_MEDIUM_PERSIST_AHEAD>(), 256)); }
 static size_t persist_stage_bytes(const MedProgram &P) { return (size_t)(persist_ahead() + 1) * std::max<size_t>(P.haloStates.size(), 1) * sizeof(double); }
 
 // PERSISTENT STRIPS: the matrix kernel (JMAT 1) with the text below at the skeleton's /*@P...@*/ markers (empty for every other kind, whose
@@ -223,7 +214,7 @@ void medium_jit_plan(const mb_machine *m, MedProgram &P, const MedGeom &geoIn) {
     // VGPRs left for loop-invariant records: a wavefront of a W-wave workgroup may use 512 / ceil(W / 4) registers and
     // the specialised kernel needs ~90 of them for everything else; medium_jit_get lowers this if the compiler spills
     const int perWave = std::min(512 / ((geo.waves + 3) / 4), 256);
-    P.regBudget = env_int("MB_JIT_REGBUDGET", std::max(0, perWave - 84));
+    P.regBudget = opt_int<MB_JIT_REGBUDGET>(std::max(0, perWave - 84));
   }
   P.ldsImageIdx.clear();
   P.tokWindow = 64;
@@ -250,7 +241,7 @@ void medium_jit_plan(const mb_machine *m, MedProgram &P, const MedGeom &geoIn) {
     ri.slots[k].place = MED_PLACE_REG; regFree -= cost;
     return true;
   };
-  if (env_int("MB_JIT_PLACE", 1) == 0) {   // legacy placement: token-independent records in LDS, everything else global
+  if (opt_int<MB_JIT_PLACE>() == 0) {   // legacy placement: token-independent records in LDS, everything else global
     for (MedRoundInfo &ri : P.roundInfo) for (MedSlotInfo &sl : ri.slots) if (sl.T == 3) toLds(sl);
     return;
   }
@@ -294,8 +285,8 @@ std::string medium_jit_source(const mb_machine *m, const MedProgram &P, const Me
   const int threads = geo.waves * 64;
   defs << "#define JS " << S << "\n#define JSPAD " << P.Spad << "\n#define JNS " << P.NS << "\n#define JG " << P.G
        << "\n#define JC " << geo.C << "\n#define JWAVES " << geo.waves << "\n#define JMODE " << (maxmode ? 1 : (mode == MED_MODE_COUNT ? 2 : 0))
-       << "\n#define JSTORE2 " << env_int("MB_JIT_STORE2", (S % 2 == 0 && P.LPG <= 8) ? 1 : 0)
-       << "\n#define JSTORENT " << env_int("MB_JIT_STORENT", 0)
+       << "\n#define JSTORE2 " << opt_int<MB_JIT_STORE2>((S % 2 == 0 && P.LPG <= 8) ? 1 : 0)
+       << "\n#define JSTORENT " << opt_int<MB_JIT_STORENT>()
        << "\n#define JENV " << (geo.env ? 1 : 0) << "\n#define JMAT " << (persist ? 1 : matKind) << "\n#define JTB " << (tbmode ? 1 : 0) << "\n#define JTBS " << tb_lds_stride(P) << "\n#define JSB " << medium_tb_stride(S)
        << "\n#define JNH " << P.haloStates.size() << "\n#define JNHP " << std::max<size_t>(P.haloStates.size(), 1)
        << "\n#define JNHR " << std::max<size_t>((P.haloStates.size() + threads - 1) / threads, 1) << "\n#define JHALOT " << (materialise ? geo.haloSteps : 0)
@@ -303,9 +294,9 @@ std::string medium_jit_source(const mb_machine *m, const MedProgram &P, const Me
        // see the skeleton.  Measured on psw2dna 64 x 487 x 2 kb: log-likelihood tiles 1 124 -> 1 188 G cells/s, traceback-byte Viterbi
        // 593 -> 617, the count sweep 224 -> 220 (its step is paced by the Backward loads, not by the barrier): off for that one
        // (round 5: on for the count sweep too when a wavefront is ONE column -- the 482-state machine: 87 -> 90 G lattice-cells/s)
-       << "\n#define JNBSYNC " << ((env_int("MB_JIT_NEIGHBOUR_SYNC", (mode == MED_MODE_COUNT && P.G != 1) ? 0 : 1) && matKind == MED_MAT_ROLL && P.haloStates.size() <= 64 && geo.waves > 1 && geo.waves <= 16) ? 1 : 0)
+       << "\n#define JNBSYNC " << ((opt_int<MB_JIT_NEIGHBOUR_SYNC>((mode == MED_MODE_COUNT && P.G != 1) ? 0 : 1) && matKind == MED_MAT_ROLL && P.haloStates.size() <= 64 && geo.waves > 1 && geo.waves <= 16) ? 1 : 0)
        << "\n#define JFLAGOFF " << lds_payload_bytes(P, geo, mode)
-       << "\n#define JBDIST " << (env_int("MB_JIT_B_DISTANCE", 1) == 2 ? 2 : 1)      // count sweep: steps the Backward supercells are fetched ahead (2: measured 218 vs 221 G lattice-cells/s -- the loads cost issue and LDS writes, not exposed latency)
+       << "\n#define JBDIST " << (opt_int<MB_JIT_B_DISTANCE>() == 2 ? 2 : 1)      // count sweep: steps the Backward supercells are fetched ahead (2: measured 218 vs 221 G lattice-cells/s -- the loads cost issue and LDS writes, not exposed latency)
        << "\n#define JDBG " << jit_debug_bits()      // experiments only (wrong results): 1 = no Backward loads, 2 = no halo loads
        << "\n#define JFLAT " << (P.flatCount ? 1 : 0) << "\n#define JNACC " << P.accEntries << "\n#define JNTRANS " << m->nTrans
        << "\n#define JNALL " << P.accAllEntries << "\n#define JNLOOP " << std::max(0, P.accEntries - P.LPG) << "\n#define JACCOFF " << (P.counting ? acc_offset(P, geo) : 0)
@@ -330,8 +321,8 @@ std::string medium_jit_source(const mb_machine *m, const MedProgram &P, const Me
   // placed in LDS, source values), then the folds, then the stores; rounds too long for that (> JIT_MAX_CANDS candidates) keep
   // their running form and go between the loads and the folds of the others.  MB_JIT_STAGE_LOADS=0: round by round.
   // A stage's loads are issued in batches of at most MB_JIT_STAGE_MAXLOADS source values (two VGPRs each until folded).
-  const bool stageLoads = env_int("MB_JIT_STAGE_LOADS", 1) != 0;
-  const int stageMaxLoads = std::max(1, env_int("MB_JIT_STAGE_MAXLOADS", 32));
+  const bool stageLoads = opt_int<MB_JIT_STAGE_LOADS>() != 0;
+  const int stageMaxLoads = std::max(1, opt_int<MB_JIT_STAGE_MAXLOADS>());
   int stagePending = 0;
   bool firstStageDone = false;
   std::ostringstream sLoad, sBig, sFold;
@@ -370,7 +361,7 @@ std::string medium_jit_source(const mb_machine *m, const MedProgram &P, const Me
       // The slots go in batches of MB_JIT_FLAT_CHUNK (24): the loads of a batch are in flight together, and a program of a hundred
       // slots (16 columns per wavefront on a dense machine) no longer keeps every record and term live at once (600+ spilled VGPRs).
       std::vector<std::string> fn(n);
-      const int chunk = env_int("MB_JIT_FLAT_CHUNK", 24) > 0 ? env_int("MB_JIT_FLAT_CHUNK", 24) : n;
+      const int wantChunk = opt_int<MB_JIT_FLAT_CHUNK>(), chunk = wantChunk > 0 ? wantChunk : n;
       flat << "      if (JINSIDE && !(JDBG & 8)) {  // usage pass: " << n << " slot(s); lanes of columns outside the lattice (stale ring values) sit it out\n";
       for (int k0 = 0; k0 < n; k0 += chunk) {
         const int k1 = std::min(n, k0 + chunk);
@@ -535,8 +526,9 @@ bool medium_jit_get(const mb_machine *m, MedProgram &P, const MedGeom &geoIn, in
   if (J.tried) return J.func != nullptr;
   if ((mode == MED_MODE_COUNT) != P.counting) return false;   // count programs carry packed records: one mode only
   J.tried = true;
-  const char *e = opt_env("MB_MEDIUM_JIT");
+  const char *e = opt_text<MB_MEDIUM_JIT>();
   if (e && *e == '0') return false;
+  const bool verbose = opt_present<MB_MEDIUM_JIT_VERBOSE>();
   long long totalSlots = 0;
   for (const MedRoundInfo &ri : P.roundInfo) {
     if (ri.slots.empty()) return false;
@@ -549,16 +541,16 @@ bool medium_jit_get(const mb_machine *m, MedProgram &P, const MedGeom &geoIn, in
   for (int attempt = 0; attempt < 8; ++attempt) {
     J.ldsBytes = medium_jit_lds_bytes(P, geo, mode) + (matKind == MED_MAT_PERSIST ? persist_stage_bytes(P) : 0);
     if (J.ldsBytes > 160 * 1024) {
-      if (opt_env("MB_MEDIUM_JIT_VERBOSE")) fprintf(stderr, "[mbhip] jit (mode %d, matrix kind %d): %zu bytes of LDS at register budget %d -- ahead-of-time kernel\n", mode, matKind, (size_t)J.ldsBytes, P.regBudget);
+      if (verbose) fprintf(stderr, "[mbhip] jit (mode %d, matrix kind %d): %zu bytes of LDS at register budget %d -- ahead-of-time kernel\n", mode, matKind, (size_t)J.ldsBytes, P.regBudget);
       return false;
     }
     src = medium_jit_source(m, P, geo, mode, matKind);
-    if (const char *dump = opt_env("MB_MEDIUM_JIT_DUMP")) {
+    if (const char *dump = opt_text<MB_MEDIUM_JIT_DUMP>()) {
       if (FILE *f = fopen((std::string(dump) + (mode == MB_VITERBI ? ".vit" : (mode == MED_MODE_COUNT ? ".cnt" : (mode == MED_MODE_TB ? ".tb" : ".sum"))) + (materialise ? ".mat" : (matKind == MED_MAT_ROLL ? ".tiles" : (matKind == MED_MAT_PERSIST ? ".pers" : ".roll"))) + (P.backward ? ".bwd" : ".fwd") + (P.closure ? ".clos" : ".exact") + ".hip").c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
     }
     std::string log;
     if (!jit_compile(src, "mb_medium_jit.hip", code, &log, &fromCache)) {
-      if (opt_env("MB_MEDIUM_JIT_VERBOSE")) fprintf(stderr, "[mbhip] hiprtc failed:\n%s\n", log.c_str());
+      if (verbose) fprintf(stderr, "[mbhip] hiprtc failed:\n%s\n", log.c_str());
       return false;
     }
     // What counts is SCRATCH memory (.private_segment_fixed_size): registers parked in AGPRs (a workgroup of <= 4 wavefronts has 512
@@ -567,7 +559,7 @@ bool medium_jit_get(const mb_machine *m, MedProgram &P, const MedGeom &geoIn, in
     long long spills = medium_jit_spill_count(code);
     if (jit_kernel_meta(code, ".private_segment_fixed_size") == 0) spills = 0;
     if (attempt == 0 && (jit_debug_bits() & 4)) spills = 3;      // experiments: force one re-plan
-    if (opt_env("MB_MEDIUM_JIT_VERBOSE")) fprintf(stderr, "[mbhip] jit %s: register budget %d, %lld spilled VGPRs (scratch %lld bytes)\n", mode == MB_VITERBI ? "max" : (mode == MED_MODE_COUNT ? "count" : (mode == MED_MODE_TB ? "max+tb" : "sum")), P.regBudget, spills, jit_kernel_meta(code, ".private_segment_fixed_size"));
+    if (verbose) fprintf(stderr, "[mbhip] jit %s: register budget %d, %lld spilled VGPRs (scratch %lld bytes)\n", mode == MB_VITERBI ? "max" : (mode == MED_MODE_COUNT ? "count" : (mode == MED_MODE_TB ? "max+tb" : "sum")), P.regBudget, spills, jit_kernel_meta(code, ".private_segment_fixed_size"));
     // (the LAST attempt keeps what it compiled: re-planning behind it would leave the placement -- the LDS image, the record tables
     // the host refreshes -- one step ahead of the code; round 4 found exactly that, counts of 1e19, when a kernel never stopped spilling)
     if (spills > 0 && !allowReplan) return false;      // (a trial build that must not touch the program's placement: medium_roll_geometry)
@@ -593,11 +585,11 @@ bool medium_jit_get(const mb_machine *m, MedProgram &P, const MedGeom &geoIn, in
   // in the ISA the value travels a248 -> a219 through v_accvgpr_mov between its spill and its reload.  The pass is batched now
   // (MB_JIT_FLAT_CHUNK) and no kernel of the test suite or the bench ends here; MB_JIT_AGPR_SPILLS=1 keeps the compiler's default.
   struct MoreOpts { bool on; explicit MoreOpts(bool o) : on(o) { if (on) jit_more_opts("-mllvm -amdgpu-spill-vgpr-to-agpr=0"); } ~MoreOpts() { if (on) jit_more_opts(nullptr); } };
-  const MoreOpts noAgprSpills(jit_kernel_meta(code, ".private_segment_fixed_size") > 0 && env_int("MB_JIT_AGPR_SPILLS", 0) == 0);
+  const MoreOpts noAgprSpills(jit_kernel_meta(code, ".private_segment_fixed_size") > 0 && opt_int<MB_JIT_AGPR_SPILLS>() == 0);
   if (noAgprSpills.on) {
     std::string log;
     if (!jit_compile(src, "mb_medium_jit.hip", code, &log, &fromCache)) return false;
-    if (opt_env("MB_MEDIUM_JIT_VERBOSE")) fprintf(stderr, "[mbhip] jit: scratch memory at the last budget -- compiled again without AGPR spill slots (scratch %lld bytes)\n", jit_kernel_meta(code, ".private_segment_fixed_size"));
+    if (verbose) fprintf(stderr, "[mbhip] jit: scratch memory at the last budget -- compiled again without AGPR spill slots (scratch %lld bytes)\n", jit_kernel_meta(code, ".private_segment_fixed_size"));
   }
   hipModule_t mod = nullptr;
   hipFunction_t fn = nullptr;

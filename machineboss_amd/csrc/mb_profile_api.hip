@@ -122,7 +122,7 @@ template <class Cells> static int count_groups(long long p0, long long p1, Cells
 }
 
 // the LDS table of the row-posterior kernels in doubles; MB_ROWPOST_TABLE makes it smaller (the rows-per-block and wide-row paths at small shapes)
-static int rowpost_table() { return std::max(1, std::min(env_int("MB_ROWPOST_TABLE", ROWPOST_LDS_MAX), ROWPOST_LDS_MAX)); }
+static int rowpost_table() { return std::max(1, std::min(opt_int<MB_ROWPOST_TABLE>(ROWPOST_LDS_MAX), ROWPOST_LDS_MAX)); }
 // the line blocks of the item of [p0, p1) that has most, 1 024 at the most (a group past an item's last block has nothing to do);
 // lines(k): the rows of item k on the axis, blockRows(k): how many of them one block takes
 template <class Lines, class BlockRows> static long long rowpost_groups(long long p0, long long p1, Lines lines, BlockRows blockRows) {
@@ -408,7 +408,7 @@ int mb_profiles_row_posteriors(mb_profiles *p, double *post, double *loglike) {
   ApiGuard guard;
   if (!p || (!post && p->totalRows)) { set_error("null argument"); return 1; }
   g_last_ms = 0.0; g_last_launches = 0;
-  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
+  latch_deterministic();
   const mb_machine *m = p->m;
   const long long PL = pf_planes(p), C = pf_width(p), nv = p->totalRows * C, fScratch = pf_fwd_scratch(p, true);
   const int tabMax = rowpost_table();
@@ -837,7 +837,7 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
   ApiGuard guard;
   if (!p || !counts) { set_error("null argument"); return 1; }
   g_last_ms = 0.0; g_last_launches = 0;
-  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
+  latch_deterministic();
   const long long nT = p->m->nTrans;
   std::vector<Chunk> chunks;
   if (!lattice_chunks(p->n, "pair", [&](long long k) { return 2.0 * pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false); }, chunks)) return 1;   // the Forward and the Backward lattice
@@ -876,7 +876,7 @@ int mb_profile_pairs_row_posteriors(mb_profile_pairs *p, double *post, double *l
   if (!p || (!post && p->totalRows)) { set_error("null argument"); return 1; }
   if (p->nCols) { set_error("row posteriors take plain profiles"); return 1; }
   g_last_ms = 0.0; g_last_launches = 0;
-  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
+  latch_deterministic();
   const mb_machine *m = p->m;
   const long long C = m->nOut + 1, nv = p->totalRows * C;
   const int tabMax = rowpost_table();
@@ -1114,7 +1114,7 @@ int mb_profile_twos_counts(mb_profile_twos *p, double *counts, double *loglikeSu
   ApiGuard guard;
   if (!p || !counts) { set_error("null argument"); return 1; }
   g_last_ms = 0.0; g_last_launches = 0;
-  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
+  latch_deterministic();
   const long long nT = p->m->nTrans;
   std::vector<Chunk> chunks;
   if (!lattice_chunks(p->n, "pair", [&](long long k) { return 2.0 * pt_cell_bytes(p, k); }, chunks)) return 1;   // the Forward and the Backward lattice
@@ -1149,7 +1149,7 @@ int mb_profile_twos_row_posteriors(mb_profile_twos *p, double *postA, double *po
   ApiGuard guard;
   if (!p) { set_error("null argument"); return 1; }
   g_last_ms = 0.0; g_last_launches = 0;
-  g_deterministic = env_int("MB_DETERMINISTIC", 0) != 0;
+  latch_deterministic();
   const mb_machine *m = p->m;
   const long long C = m->nOut + 1, CA = m->nIn + 1, nb = postB ? p->totalRows * C : 0, na = postA ? p->totalIn * CA : 0;
   const int tabMax = rowpost_table();

@@ -47,15 +47,10 @@
 
 namespace mb {
 
-static int env_int_s(const char *name, int dflt) {
-  const char *v = opt_env(name);
-  return v && *v ? atoi(v) : dflt;
-}
-
 static const int SM_MAX_STATES = 16;
 
 bool small_eligible(const mb_machine *m) {
-  if (m->S < 1 || m->S > std::min(env_int_s("MB_SMALL_MAX_STATES", SM_MAX_STATES), SM_MAX_STATES)) return false;   // (the knob can only lower the limit: register tables, traceback words and decode entries are sized for 16)
+  if (m->S < 1 || m->S > std::min(opt_int<MB_SMALL_MAX_STATES>(SM_MAX_STATES), SM_MAX_STATES)) return false;   // (the knob can only lower the limit: register tables, traceback words and decode entries are sized for 16)
   if (m->nIn < 1 || m->nOut < 1) return false;            // one-tape machines: other families
   if (m->nTrans > 8000) return false;                     // the workgroup's count table lives in LDS
   for (long long e = 0; e < m->nTrans; ++e)
@@ -495,7 +490,7 @@ const char *small_kernel_name(const SmallProgram &P, int mode, bool materialise)
 
 // wavefronts per SIMD the kernel is compiled for (register budget 512 / n): the count sweep hides the latency of its
 // Backward loads with occupancy; small_jit_get lowers it until the kernel needs no scratch memory
-int small_default_minwaves(int mode, bool env) { return std::max(1, env_int_s("MB_SMALL_MINWAVES", mode == SM_COUNT ? (env ? 3 : 4) : 1)); }
+int small_default_minwaves(int mode, bool env) { return std::max(1, opt_int<MB_SMALL_MINWAVES>(mode == SM_COUNT ? (env ? 3 : 4) : 1)); }
 
 std::string small_jit_source(const SmallProgram &P, int mode, bool materialise, bool env, int minWaves) {
   std::ostringstream defs, weights, state, loadb, loadd, saveb, flush;
@@ -509,7 +504,7 @@ std::string small_jit_source(const SmallProgram &P, int mode, bool materialise, 
        << "\n#define JNTRANS " << P.nTrans << "\n#define JROWF " << rowF << "\n#define JOUTACC " << outacc_floats(P) << "\n#define JLDSW " << lds_w_doubles(P)
        << "\n#define JLDSWN " << (P.nEntries - P.off[2]) << "\n#define JWAVEDBL " << wave_doubles(P, mode)
        << "\n#define JOFFSIL " << P.off[3] << "\n#define JOFFIN " << P.off[1] << "\n#define JOFFOUT " << P.off[2] << "\n#define JOFFMAT " << P.off[0]
-       << "\n#define JSUB " << std::max(2, std::min(64, env_int_s("MB_SMALL_JSUB", 16) & ~1)) << "\n#define JENDSTATE " << P.endState << "\n#define JLINELANES " << (env_int_s("MB_SMALL_STORE_LINES", 1) ? 128 / CB : 64) << "\n";
+       << "\n#define JSUB " << std::max(2, std::min(64, opt_int<MB_SMALL_JSUB>() & ~1)) << "\n#define JENDSTATE " << P.endState << "\n#define JLINELANES " << (opt_int<MB_SMALL_STORE_LINES>() ? 128 / CB : 64) << "\n";
   for (int k = 0; k < P.nTab[3]; ++k) weights << "    const double wS" << k << " = wc[JOFFSIL + " << k << "];\n";
   for (int k = 0; k < P.nTab[1]; ++k) weights << "    const double wI" << k << " = A.w[JOFFIN + " << (long long)k * (P.nIn + 1) << " + it];\n";
   // persistent state: two sets of cells and of left-neighbour values, alternating by step parity
@@ -553,7 +548,7 @@ std::string small_jit_source(const SmallProgram &P, int mode, bool materialise, 
     b << "          const bool active = colValid && o >= 0 && o <= outLen;\n";
     if (materialise || counting)
       b << "          const bool lineOn = gHi >= max(t - outLen, cLo) && gLo <= min(t, cHi);   // some lane of this lane's 128-byte line holds a cell\n";
-    const bool lateB = env_int_s("MB_SMALL_BLOAD", 0) != 0;
+    const bool lateB = opt_int<MB_SMALL_BLOAD>() != 0;
     auto loadB = [&]() {
       // the Backward supercell of this step's cell: requested at the top of the step, used after its Forward values are done
       b << "          " << (CB == 16 ? "d2" : "double");
@@ -713,23 +708,24 @@ bool small_jit_get(SmallProgram &P, int mode, bool materialise, bool env) {
   // build gave wrong values.  Metadata that cannot be read counts as "spills" (fail closed).
   std::string code, log, src;
   bool fromCache = false;
+  const bool allowScratch = opt_int<MB_SMALL_ALLOW_SCRATCH>() != 0;
   for (int mw = small_default_minwaves(mode, env); mw >= 1; --mw) {
     src = small_jit_source(P, mode, materialise, env, mw);
-    if (const char *dump = opt_env("MB_SMALL_JIT_DUMP")) {
+    if (const char *dump = opt_text<MB_SMALL_JIT_DUMP>()) {
       const std::string fn = std::string(dump) + ".m" + I(mode) + (materialise ? ".mat" : ".roll") + (P.backward ? ".bwd" : ".fwd") + ".hip";
       if (FILE *f = fopen(fn.c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
     }
     if (!jit_compile(src, "mb_small_jit.hip", code, &log, &fromCache)) {
-      if (opt_env("MB_SMALL_JIT_VERBOSE") || opt_env("MB_MEDIUM_JIT_VERBOSE")) fprintf(stderr, "[mbhip] hiprtc failed (small family):\n%s\n", log.c_str());
+      if (opt_present<MB_SMALL_JIT_VERBOSE>() || opt_present<MB_MEDIUM_JIT_VERBOSE>()) fprintf(stderr, "[mbhip] hiprtc failed (small family):\n%s\n", log.c_str());
       set_error("run-time compilation of the small-machine kernel failed: " + log.substr(0, 400));
       return false;
     }
     J.scratch = jit_kernel_meta(code, ".private_segment_fixed_size") != 0;
-    if (opt_env("MB_SMALL_JIT_VERBOSE")) fprintf(stderr, "[mbhip] small family, mode %d: %d wavefront(s) per SIMD, %lld VGPRs, %lld spilled, scratch %lld bytes\n", mode, mw,
+    if (opt_present<MB_SMALL_JIT_VERBOSE>()) fprintf(stderr, "[mbhip] small family, mode %d: %d wavefront(s) per SIMD, %lld VGPRs, %lld spilled, scratch %lld bytes\n", mode, mw,
                                                 jit_kernel_meta(code, ".vgpr_count"), jit_kernel_meta(code, ".vgpr_spill_count"), jit_kernel_meta(code, ".private_segment_fixed_size"));
-    if (!J.scratch || env_int_s("MB_SMALL_ALLOW_SCRATCH", 0)) break;
+    if (!J.scratch || allowScratch) break;
   }
-  if (J.scratch && !env_int_s("MB_SMALL_ALLOW_SCRATCH", 0)) { set_error("small-machine kernel: does not fit the register file (another kernel family takes the machine)"); return false; }
+  if (J.scratch && !allowScratch) { set_error("small-machine kernel: does not fit the register file (another kernel family takes the machine)"); return false; }
   hipModule_t mod = nullptr;
   hipFunction_t fn = nullptr;
   if (hipModuleLoadData(&mod, code.data()) != hipSuccess) {
@@ -766,7 +762,7 @@ struct SmallArgsHost {   // must match SmallArgs in the generated source
 // Steps per tile: the longest tile that still leaves ~12 tiles per CU in an average launch; 64 (the minimum: a tile must
 // not run ahead of the halo rows the strip to its left has produced) when the batch cannot fill the chip anyway.
 static int pick_tile_steps(const std::vector<PairDesc> &pairs) {
-  const int forced = env_int_s("MB_SMALL_TS", 0);
+  const int forced = opt_int<MB_SMALL_TS>();
   if (forced >= 64 && forced % 64 == 0) return forced;
   int best = 64;
   for (int TS : {128, 256, 512}) {
@@ -784,7 +780,7 @@ static int pick_tile_steps(const std::vector<PairDesc> &pairs) {
 int small_sweep(SmallProgram &P, int mode, bool materialise, const SmSweep &sw, hipStream_t st) {
   const std::vector<PairDesc> &pairs = *sw.pairs;
   if (pairs.empty()) return 0;
-  const bool timing = opt_env("MB_TIMING") != nullptr;
+  const bool timing = opt_present<MB_TIMING>();
   auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double tPrev = now();
   auto lap = [&](const char *what) { if (timing) { const double t = now(); fprintf(stderr, "[mbhip]   sweep %-24s %7.2f ms\n", what, t - tPrev); tPrev = t; } };
@@ -803,7 +799,7 @@ int small_sweep(SmallProgram &P, int mode, bool materialise, const SmSweep &sw, 
   // MB_SMALL_ONE_LAUNCH: 0 never, 2 always, 1 the 64-step TILES of a sweep in one grid with done-flags (measured: no faster than the
   // launches), default: the rule above.  A wait that runs out (MB_SMALL_ONE_LAUNCH_TIMEOUT_S; a shared device) latches both forms off.
   static bool oneLaunchOff = false;
-  const int oneWant = env_int_s("MB_SMALL_ONE_LAUNCH", -1);
+  const int oneWant = opt_int<MB_SMALL_ONE_LAUNCH>();
   long long nStrips = 0;
   int chain = 0;      // launches of the tile form (64-step tiles): a pair of one or two tiles has no chain to shorten (config 1's 50 x 50 pair: 85 us per call, 95 through the strips)
   for (const PairDesc &pd : pairs) { nStrips += small_strips(pd.inLen); chain = std::max(chain, 2 * (small_strips(pd.inLen) - 1) + (small_steps(pd.outLen) + 63) / 64); }
@@ -922,13 +918,13 @@ int small_sweep(SmallProgram &P, int mode, bool materialise, const SmSweep &sw, 
     unsigned *flags = (unsigned *)tc.d_flags;      // [nTiles] done words + the error word behind them
     if (!hip_ok(hipMemsetAsync(flags, 0, ((size_t)nTiles + 1) * sizeof(unsigned), st), "memset(tile flags)")) return 1;
     A.deps = (const int4 *)tc.d_deps; A.flags = flags; A.err = flags + nTiles;
-    A.timeoutTicks = (long long)std::max(1, env_int_s("MB_SMALL_ONE_LAUNCH_TIMEOUT_S", 20)) * 100000000ll;
-    if (const int us = env_int_s("MB_SMALL_ONE_LAUNCH_TIMEOUT_US", 0)) A.timeoutTicks = (long long)std::max(us, 1) * 100ll;      // (the tests' way to a time-out: a microsecond)
+    A.timeoutTicks = (long long)std::max(1, opt_int<MB_SMALL_ONE_LAUNCH_TIMEOUT_S>()) * 100000000ll;
+    if (const int us = opt_int<MB_SMALL_ONE_LAUNCH_TIMEOUT_US>()) A.timeoutTicks = (long long)std::max(us, 1) * 100ll;      // (the tests' way to a time-out: a microsecond)
     A.tileBase = 0; A.tileEnd = (int)nTiles;
     void *args[] = {&A};
     ++g_last_launches;
     // (persistent strips: ONE strip per workgroup -- a wavefront alone on its CU issues a Forward step in 0.29 us, four strips sharing a CU in 0.36)
-    const unsigned wpb = persist && env_int_s("MB_SMALL_STRIP_PER_WG", 1) ? 1u : 4u;
+    const unsigned wpb = persist && opt_int<MB_SMALL_STRIP_PER_WG>() ? 1u : 4u;
     ok = hipModuleLaunchKernel((hipFunction_t)J.func, (unsigned)((nTiles + wpb - 1) / wpb), 1, 1, 64 * wpb, 1, 1, (unsigned)J.ldsBytes, st, args, nullptr) == hipSuccess;
     unsigned e = 0;
     ok = ok && hip_ok(hipGetLastError(), "small tile launch") && hip_ok(hipMemcpyAsync(&e, flags + nTiles, sizeof(e), hipMemcpyDeviceToHost, st), "tile status") && hip_ok(hipStreamSynchronize(st), "small tile kernel");

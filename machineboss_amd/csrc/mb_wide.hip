@@ -806,11 +806,6 @@ inline uint32_t CUR(int i) { return (uint32_t)i; }
 inline uint32_t EXTRA(int i) { return (1u << 30) | (uint32_t)i; }
 inline uint32_t PREV(int i) { return (2u << 30) | (uint32_t)i; }
 
-int env_int_w(const char *name, int dflt) {
-  const char *v = opt_env(name);
-  return v && *v ? atoi(v) : dflt;
-}
-
 double host_lse2(double a, double b) {
   if (a == -INFINITY) return b;
   if (b == -INFINITY) return a;
@@ -838,7 +833,7 @@ double plan_stage(const std::vector<const WNode *> &nodes, int nTokTables, int W
   // lane-group reduction, log, store -- 0.30 to 0.58 us, i.e. 1.6-1.9 slots, and the barrier itself next to nothing
   // (the retimed kernel, whose slots are leaner: 0.08 us a slot, 0.37 us a round with its barrier -- cRound = 280)
   const double cSlot = 60.0, cShfl = 3.0, cSync = 10.0;
-  const int maxGroup = std::max(1, std::min(64, env_int_w("MB_WIDE_MAX_GROUP", 64)));
+  const int maxGroup = std::max(1, std::min(64, opt_int<MB_WIDE_MAX_GROUP>()));
   auto groupOf = [&](int L, int d) { return std::min(maxGroup, pow2ceil((L + d - 1) / d)); };
   int bestD = 1; double best = 1e300;
   for (int d = 1; d <= maxLen; ++d) {
@@ -904,10 +899,13 @@ double plan_stage(const std::vector<const WNode *> &nodes, int nTokTables, int W
 }
 }  // namespace
 
+// lanes per workgroup (509 states: 48 G cells/s with 1024 lanes, 35 with 256)
+static int wide_lanes(const mb_machine *m) { return opt_int<MB_WIDE_LANES>(m->S >= 192 ? 1024 : 256); }
+
 bool wide_applicable(const mb_machine *m) {
   if ((m->nIn != 0) == (m->nOut != 0)) return false;      // exactly one tape: a generator (outputs only) or a recogniser (inputs only)
-  if (!env_int_w("MB_WIDE", 1)) return false;
-  return m->S >= env_int_w("MB_WIDE_MIN_STATES", 256) && m->S < (1 << 26);
+  if (!opt_int<MB_WIDE>()) return false;
+  return m->S >= opt_int<MB_WIDE_MIN_STATES>() && m->S < (1 << 26);
 }
 
 void wide_free(WideProgram &P) {
@@ -964,7 +962,7 @@ static void wide_linearise(WideProgram &P, int nTok) {
   }
   P.dev.nA = nA; P.dev.nB = nB; P.dev.strideA = (long long)nA * W;
   // every entry of the workgroup's vectors addressable with 16 bits: both parities' indices precomputed in the record
-  P.fastIdx = 2 * P.NV + P.NX <= 65536 && env_int_w("MB_WIDE_FAST_INDEX", 1);
+  P.fastIdx = 2 * P.NV + P.NX <= 65536 && opt_int<MB_WIDE_FAST_INDEX>();
   if (P.fastIdx) {
     const uint32_t NV = (uint32_t)P.NV;
     auto conv = [&](WideRec &rc) {
@@ -985,7 +983,7 @@ static bool up_w(T *&d, const std::vector<T> &h);
 // only for their record format (16-bit indices for both column parities): the records are re-laid here from P.recs / P.dsts
 static bool wide_vit_build(WideProgram &P, int nTok) {
   P.vitOk = false;
-  if (!P.viterbi || !P.fastIdx || P.vecBytes() > WIDE_LDS_MAX || env_int_w("MB_WIDE_GLOBAL_VECTORS", 0) || !env_int_w("MB_WIDE_VITERBI_PHASES", 1)) return true;
+  if (!P.viterbi || !P.fastIdx || P.vecBytes() > WIDE_LDS_MAX || opt_int<MB_WIDE_GLOBAL_VECTORS>() || !opt_int<MB_WIDE_VITERBI_PHASES>()) return true;
   const int W = P.W, nR = (int)P.rounds.size();
   int lastTok = -1;
   for (int r = 0; r < nR; ++r) if (P.rounds[r].tokStride) lastTok = r;
@@ -1413,7 +1411,7 @@ void ret_merge(std::vector<RetEdge> &edges, int nStates, int nOwn, int seedState
     if (p0 < 0) p0 = p;
     if (p <= target || p > 64) break;
     const std::vector<int> cyc = ret_cycle(edges, nStates, p - 1, 62 * (p - 1) + p - 2);
-    if (verbose && opt_env("MB_WIDE_VERBOSE_MERGE")) fprintf(stderr, "[mbhip]   merge iteration %d: period %d, cycle of %zu edges\n", iter, p, cyc.size());
+    if (verbose && opt_present<MB_WIDE_VERBOSE_MERGE>()) fprintf(stderr, "[mbhip]   merge iteration %d: period %d, cycle of %zu edges\n", iter, p, cyc.size());
     if (cyc.empty()) break;
     int picked = 0;
     for (int k : cyc) {
@@ -1443,12 +1441,12 @@ static bool wide_ret_build(const mb_machine *m, WideProgram &P, const std::vecto
   const int S = part ? part->nOwn + part->nImp + part->nExp : m->S, SC = part ? part->nOwn : m->S;
   const int nImp = part ? part->nImp : 0;
   auto entryOf = [&](int v) { return v < SC ? v : v + 2; };      // (the two constants sit between the own states and the other vertices)
-  const int want = env_int_w("MB_WIDE_RETIMED", 1);
+  const int want = opt_int<MB_WIDE_RETIMED>();
   if (want == 0) return true;
   const int rowLen = nTok + 1;                                 // penalty columns: silent, tokens 1 .. nTok - 1, the seed
   if (S + 2 >= (int)WIDE_RET_NO_DST || rowLen > 64) return true;
   if (part && (hostOut == nullptr || nImp > W)) return true;
-  const bool verbose = opt_env("MB_WIDE_VERBOSE") != nullptr && !g_quiet_search;
+  const bool verbose = opt_present<MB_WIDE_VERBOSE>() && !g_quiet_search;
   // the levelled nodes as a graph over states: t2[tok] = emitting candidates (source in the column before), t3 = silent ones
   std::vector<char> live(S, 0);
   for (const WNode &nd : nodes) live[nd.dst & W_IDX_MASK] = 1;
@@ -1478,7 +1476,7 @@ static bool wide_ret_build(const mb_machine *m, WideProgram &P, const std::vecto
   });
   const int kLimit = WIDE_RET_TOKWIN - 2;                      // largest lag the token window serves
   // parts: two-transition candidates until the period is about half the machine's own (MB_ONETAPE_PART_MERGE=0: none; n > 1: until period n)
-  const int mergeTo = (part && part->useMerge) ? env_int_w("MB_ONETAPE_PART_MERGE", 1) : 0;
+  const int mergeTo = (part && part->useMerge) ? opt_int<MB_ONETAPE_PART_MERGE>() : 0;
   if (mergeTo > 0) {
     int target = mergeTo;
     if (mergeTo == 1 && !part->mergeKnown) {
@@ -1498,7 +1496,7 @@ static bool wide_ret_build(const mb_machine *m, WideProgram &P, const std::vecto
   std::vector<int> tau;
   auto feasible = [&](int period) { return ret_offsets(edges, S, period, kLimit * period + period - 1, tau); };
   // (a weight refresh keeps the period that was chosen: the schedule depends on the machine's structure, not on its weights)
-  const int forced = keepPeriod > 0 ? keepPeriod : env_int_w("MB_WIDE_RETIMED_PERIOD", 0);
+  const int forced = keepPeriod > 0 ? keepPeriod : opt_int<MB_WIDE_RETIMED_PERIOD>();
   int lo = 1, hi = 64;
   if (keepPeriod <= 0) {
     if (!feasible(hi)) return true;
@@ -1507,7 +1505,7 @@ static bool wide_ret_build(const mb_machine *m, WideProgram &P, const std::vecto
   const int pMin = keepPeriod > 0 ? P.retPeriodMin : lo;
   // shape for one period length: ring depth, relays, nodes by residue; cost from the round planner
   struct Shape { int period = 0, NB = 0, NVs = 0, nRelay = 0, kMax = 0, tauMax = 0; bool gv = false; double cost = 1e300; std::vector<WNode> nd; };
-  const bool forceGv = env_int_w("MB_WIDE_GLOBAL_VECTORS", 0) != 0, allowGv = env_int_w("MB_WIDE_RETIMED_L2", 1) != 0;
+  const bool forceGv = opt_int<MB_WIDE_GLOBAL_VECTORS>() != 0, allowGv = opt_int<MB_WIDE_RETIMED_L2>() != 0;
   auto shape = [&](int period, Shape &sh) -> bool {
     if (!feasible(period)) return false;
     int tauMax = 0;
@@ -1691,7 +1689,7 @@ static bool wide_ret_build(const mb_machine *m, WideProgram &P, const std::vecto
 bool wide_ret_host(const mb_machine *m, bool backward, bool viterbi, WideProgram &P, std::vector<WideRec> &stream, bool tbCodes) {
   P = WideProgram();
   P.backward = backward; P.viterbi = viterbi; P.tbCodes = tbCodes;
-  P.W = env_int_w("MB_WIDE_LANES", m->S >= 192 ? 1024 : 256);
+  P.W = wide_lanes(m);
   std::vector<WNode> nodes;
   int nExtra = 0, nStages = 0; long long nPairs = 0;
   if (!wide_nodes(m, backward, 0, P.W, 1ll << 40, nodes, nExtra, nStages, nPairs)) return false;
@@ -1737,7 +1735,7 @@ bool wide_parts_host(const mb_machine *m, bool backward, bool viterbi, bool tbCo
   std::vector<std::vector<uint32_t>> tbOfState(tbCodes ? m->S : 0);
   const int S = m->S, nTok = (m->nOut ? m->nOut : m->nIn) + 1;
   if (k < 2 || S < 2 * k) return false;
-  const bool verbose = opt_env("MB_WIDE_VERBOSE") != nullptr;
+  const bool verbose = opt_present<MB_WIDE_VERBOSE>();
   std::vector<WNode> nodes;
   int nExtra = 0, nStages = 0; long long nPairs = 0;
   if (!wide_nodes(m, backward, 0, 1024, 1ll << 40, nodes, nExtra, nStages, nPairs)) return false;
@@ -1848,8 +1846,8 @@ bool wide_parts_host(const mb_machine *m, bool backward, bool viterbi, bool tbCo
   std::vector<Cand> cand;
   if (hint && hint->valid) cand.push_back({hint->W, hint->ring, hint->merge});
   else {
-    const int ringEnv = env_int_w("MB_ONETAPE_PART_RING", 0);
-    const bool mayMerge = env_int_w("MB_ONETAPE_PART_MERGE", 1) != 0;
+    const int ringEnv = opt_int<MB_ONETAPE_PART_RING>();
+    const bool mayMerge = opt_int<MB_ONETAPE_PART_MERGE>() != 0;
     std::vector<int> Ws;
     if (W > 0) Ws.push_back(W);
     else for (int w : {384, 512, 640, 768, 896, 1024}) Ws.push_back(w);
@@ -1871,8 +1869,8 @@ bool wide_parts_host(const mb_machine *m, bool backward, bool viterbi, bool tbCo
   int bestW = 0, bestRing = 8; double bestCost = 1e300; bool bestMerge = true;
   if (cand.size() == 1) { bestW = cand[0].first; bestRing = cand[0].second; bestMerge = cand[0].merge; }
   else {
-    const bool quiet = opt_env("MB_WIDE_VERBOSE_PARTS") == nullptr;      // (the search's own builds stay silent unless asked)
-    const char *keepVerbose = opt_env("MB_WIDE_VERBOSE");
+    const bool quiet = !opt_present<MB_WIDE_VERBOSE_PARTS>();      // (the search's own builds stay silent unless asked)
+    const bool keepVerbose = opt_present<MB_WIDE_VERBOSE>();
     if (quiet && keepVerbose) g_quiet_search = true;
     struct Res { bool ok = false; double cost = 0.0; int period = 0; };
     std::vector<Res> res(cand.size());
@@ -1952,15 +1950,15 @@ bool wide_build(const mb_machine *m, bool backward, bool viterbi, WideProgram &P
   wide_free(P);
   P.backward = backward; P.viterbi = viterbi; P.tbCodes = keepTb;
   P.partHints = std::move(keepHints);
-  P.W = env_int_w("MB_WIDE_LANES", m->S >= 192 ? 1024 : 256);      // 509 states: 48 G cells/s with 1024 lanes, 35 with 256
+  P.W = wide_lanes(m);
   const int S = m->S, nLev = backward ? m->nLevB : m->nLevF;
   long long nSilent = 0;
   for (long long e = 0; e < m->nTrans; ++e) nSilent += (m->inTok[e] == 0 && m->outTok[e] == 0);
   const long long pairCap = std::max<long long>(64 * (nSilent + S), 1 << 16);
-  const int want32 = env_int_w("MB_WIDE_FP32", -1);
+  const int want32 = opt_int<MB_WIDE_FP32>();
   // The retimed sweep first (from the LEVELLED nodes): a machine that has one needs no column-by-column program, and a
   // weight refresh -- every EM iteration -- then costs one relaxation, one plan and one upload (20-node machine, two programs: 59 -> 5.6 ms on top of a 21 ms E-step; the first build 544 -> 51 ms).
-  if (env_int_w("MB_WIDE_RETIMED", 1) && want32 <= 0) {      // (MB_WIDE_FP32 = 1 asks for the fp32 kernel)
+  if (opt_int<MB_WIDE_RETIMED>() && want32 <= 0) {      // (MB_WIDE_FP32 = 1 asks for the fp32 kernel)
     std::vector<WNode> levelled;
     int xe = 0, xs = 0; long long xp = 0;
     if (wide_nodes(m, backward, 0, P.W, pairCap, levelled, xe, xs, xp)) {
@@ -1979,7 +1977,7 @@ bool wide_build(const mb_machine *m, bool backward, bool viterbi, WideProgram &P
   int nExtra = 0, nStages = 0, bestExtra = 0, bestStages = 0, bestK = 0;
   long long nPairs = 0, bestPairs = 0;
   double best = 1e300;
-  const bool verbose = opt_env("MB_WIDE_VERBOSE") != nullptr;
+  const bool verbose = opt_present<MB_WIDE_VERBOSE>();
   auto consider = [&](int K) {
     if (!wide_nodes(m, backward, K, P.W, pairCap, nodes, nExtra, nStages, nPairs)) return false;
     const double c = wide_plan(nodes, nStages, (m->nOut ? m->nOut : m->nIn) + 1, P.W, false, nullptr);
@@ -1990,7 +1988,7 @@ bool wide_build(const mb_machine *m, bool backward, bool viterbi, WideProgram &P
   if (viterbi) consider(0);
   else {
     // MB_WIDE_CLOSURE_STAGES: K >= 0 uniform level groups (0 = levelled); -n = adaptive stages of at most n slots of candidates
-    const int envK = env_int_w("MB_WIDE_CLOSURE_STAGES", -1000000);
+    const int envK = opt_int<MB_WIDE_CLOSURE_STAGES>();
     if (haveShape) consider(keepStages);
     else if (envK > -1000000) consider(envK >= 0 ? envK : (envK == -999 ? -(int)WIDE_STAGES_DP : envK * P.W));
     else {
@@ -1999,9 +1997,10 @@ bool wide_build(const mb_machine *m, bool backward, bool viterbi, WideProgram &P
         if (!consider(K)) break;
         if (K == 1) break;
       }
-      if (env_int_w("MB_WIDE_ADAPTIVE_STAGES", 1)) consider(-(int)WIDE_STAGES_DP);
-      if (env_int_w("MB_WIDE_ADAPTIVE_STAGES", 1))
+      if (opt_int<MB_WIDE_ADAPTIVE_STAGES>()) {
+        consider(-(int)WIDE_STAGES_DP);
         for (int q = 2; q <= 32; q += (q < 12 ? 1 : (q < 20 ? 2 : 4))) consider(-(q * P.W) / 4);      // 0.5 ... 8 slots of candidates per stage
+      }
     }
   }
   if (best >= 1e300) { set_error("wide program: no feasible shape"); return false; }
@@ -2014,7 +2013,7 @@ bool wide_build(const mb_machine *m, bool backward, bool viterbi, WideProgram &P
   // one each fit the first wavefront, the LDS pipeline already orders that wavefront's store before its next read, so
   // the workgroup barrier between them is dropped; the other wavefronts run ahead to the barrier that ends the run.
   // (LDS columns only: the same-wavefront ordering is not relied upon for the L2 scratch vectors.)
-  if (env_int_w("MB_WIDE_WAVE_LOCAL", 1) && P.vecBytes() <= WIDE_LDS_MAX && !env_int_w("MB_WIDE_GLOBAL_VECTORS", 0) && bestK == 0) {
+  if (opt_int<MB_WIDE_WAVE_LOCAL>() && P.vecBytes() <= WIDE_LDS_MAX && !opt_int<MB_WIDE_GLOBAL_VECTORS>() && bestK == 0) {
     int dropped = 0;
     for (size_t r = 0; r + 1 < P.rounds.size(); ++r)
       if (P.rounds[r].sync && P.rounds[r].pad0 <= 64 && P.rounds[r + 1].pad0 <= 64 && P.rounds[r + 1].sync) { P.rounds[r].sync = 0; ++dropped; }
@@ -2031,7 +2030,7 @@ bool wide_build(const mb_machine *m, bool backward, bool viterbi, WideProgram &P
     // both columns in LDS when they fit; else the current one in LDS and the previous one in L2; else both in L2
     const size_t lds32 = WIDE_LDS_MAX - 64;
     const bool fits2 = (size_t)(2 * P.NV + P.NX) * sizeof(float) <= lds32;
-    const int wantHyb = env_int_w("MB_WIDE_HYBRID", -1);
+    const int wantHyb = opt_int<MB_WIDE_HYBRID>();
     P.hyb = (wantHyb > 0 || (wantHyb < 0 && !fits2)) && (size_t)(P.NV + P.NX) * sizeof(float) <= lds32 &&
             wide_linearise32(P, (m->nOut ? m->nOut : m->nIn) + 1, true, a32, b32, fw);
     if (P.hyb || wide_linearise32(P, (m->nOut ? m->nOut : m->nIn) + 1, false, a32, b32, fw)) {
@@ -2150,17 +2149,17 @@ static bool g_parts_retry = false;
 // states): the parts bring it into LDS -- 16 sequences: Viterbi fill 160 -> 17 ms with 16 parts -- default at most 16.
 static int wide_parts_k(const WideProgram &P, long long nPairs, int cus) {
   if (!P.retOk || nPairs <= 0 || cus <= 0 || P.partsOff) return 1;
-  const int maxK = env_int_w("MB_ONETAPE_PARTS", P.retGv ? 16 : 8);
+  const int maxK = opt_int<MB_ONETAPE_PARTS>(P.retGv ? 16 : 8);
   const long long k = std::min<long long>(maxK, cus / nPairs);
-  if (k < 2 || (k == 2 && P.viterbi && !P.retGv && !opt_env("MB_ONETAPE_PARTS"))) return 1;
+  if (k < 2 || (k == 2 && P.viterbi && !P.retGv && !opt_present<MB_ONETAPE_PARTS>())) return 1;
   return (int)k;
 }
 
 static WidePartSet *wide_parts_get(const mb_machine *m, WideProgram &P, int k) {
   // lanes per part and ring depth: MB_ONETAPE_PART_LANES / MB_ONETAPE_PART_RING, else searched by wide_parts_host (0: its choice)
-  int lanes = env_int_w("MB_ONETAPE_PART_LANES", 0);
+  int lanes = opt_int<MB_ONETAPE_PART_LANES>();
   if (lanes < 64 || lanes > 1024 || lanes % 64) lanes = 0;
-  const int ringAsk = env_int_w("MB_ONETAPE_PART_RING", 0) == 4 ? 4 : (env_int_w("MB_ONETAPE_PART_RING", 0) == 8 ? 8 : 0);
+  const int ring = opt_int<MB_ONETAPE_PART_RING>(), ringAsk = ring == 4 || ring == 8 ? ring : 0;
   for (WidePartSet &ps : P.partSets) if (ps.kWanted == k && ps.lanesAsked == lanes && ps.ringAsked == ringAsk) return ps.ok ? &ps : nullptr;
   P.partSets.emplace_back();
   WidePartSet &ps = P.partSets.back();
@@ -2238,14 +2237,13 @@ static int wide_fill_parts(const mb_machine *m, WideProgram &P, WidePartSet &ps,
   if (!g_parts_pending) MB_HIP(hipMemsetAsync(g_part_err, 0, sizeof(unsigned), st));      // (a second launch of the same call -- the other sweep on the other stream -- shares the word)
   WidePartArgs A{};
   A.parts = ps.d_parts; A.nSeq = (int)nPairs; A.nExpTot = ps.nExpTot; A.X = (double *)(buf + headBytes); A.xOff = (const long long *)buf;
-  { const char *ts = opt_env("MB_ONETAPE_PART_TIMEOUT_S");      // seconds (a fraction is taken: the tests provoke the time-out with microseconds)
-    const double secs = ts && *ts ? atof(ts) : 20.0;
+  { const double secs = opt_real<MB_ONETAPE_PART_TIMEOUT_S>();      // seconds (a fraction is taken: the tests provoke the time-out with microseconds)
     A.err = g_part_err; A.timeoutTicks = std::max<long long>(1, (long long)(secs * 1e8)); }
   if (std::find(g_parts_inflight.begin(), g_parts_inflight.end(), &P) == g_parts_inflight.end()) g_parts_inflight.push_back(&P);
   WideDev dev = P.dev; dev.lastOnly = lastOnly ? 1 : 0; dev.W = ps.W;
   // one workgroup per CU: a part's LDS is padded beyond half a CU's (the parts of a sequence are meant to run side by side on CUs of their own)
   size_t lds = ps.ldsBytes;
-  if (env_int_w("MB_ONETAPE_PART_EXCLUSIVE", 1)) lds = std::max<size_t>(lds, 82 * 1024);
+  if (opt_int<MB_ONETAPE_PART_EXCLUSIVE>()) lds = std::max<size_t>(lds, 82 * 1024);
   if (lds > WIDE_LDS_MAX) { set_error("one-tape parts: LDS"); return 1; }
   const dim3 grid((unsigned)(nPairs * ps.k)), block((unsigned)ps.W);
   // the sweep generated for this machine and this cut (mb_wide_jit.cpp); the interpreter below is the fallback
@@ -2263,7 +2261,7 @@ static int wide_fill_parts(const mb_machine *m, WideProgram &P, WidePartSet &ps,
         in.gmap = ps.h_tab[p].data();
       }
       WideJitFlags F; F.viterbi = P.viterbi; F.tb = tb; F.acc = acc; F.backward = P.backward; F.inputTape = m->nOut == 0; F.nExpTot = ps.nExpTot;
-      if (!wide_jit_build(ins, F, J, &J.why) && opt_env("MB_WIDE_VERBOSE")) fprintf(stderr, "[mbhip] wide jit (%d parts): interpreter kept -- %s\n", ps.k, J.why.c_str());
+      if (!wide_jit_build(ins, F, J, &J.why) && opt_present<MB_WIDE_VERBOSE>()) fprintf(stderr, "[mbhip] wide jit (%d parts): interpreter kept -- %s\n", ps.k, J.why.c_str());
     }
     if (J.mod) {
       for (int p = 0; p < ps.k; ++p) J.args.impIdx[p] = ps.h_parts[p].impIdx;
@@ -2307,7 +2305,7 @@ static bool wide_parts_fit(const mb_machine *m, const WidePartSet &ps, const Pai
 // thousands of columns -- from MB_ONETAPE_PARTS_MIN_LEN (4 096; 64 for a machine whose one-workgroup ring lives in L2, where the
 // parts are 5-17 x faster) symbols in the longest sequence of the launch
 static bool wide_parts_worth(const mb_machine *m, const WideProgram &P, const PairDesc *h_desc, long long nPairs) {
-  const int minLen = env_int_w("MB_ONETAPE_PARTS_MIN_LEN", P.retGv ? 64 : 4096);
+  const int minLen = opt_int<MB_ONETAPE_PARTS_MIN_LEN>(P.retGv ? 64 : 4096);
   for (long long p = 0; p < nPairs; ++p) if ((m->nOut ? h_desc[p].outLen : h_desc[p].inLen) >= minLen) return true;
   return false;
 }
@@ -2339,7 +2337,7 @@ static WideJitKernel *wide_jit_one(const mb_machine *m, WideProgram &P, bool tb,
     WideJitIn &in = ins[0];
     in.ret = P.ret; in.W = P.W; in.stream = P.h_ret.data(); in.S = m->S; in.Sg = m->S; in.resultEntry = P.dev.resultIdx;
     WideJitFlags F; F.viterbi = P.viterbi; F.tb = tb; F.acc = acc; F.backward = P.backward; F.inputTape = m->nOut == 0;
-    if (!wide_jit_build(ins, F, J, &J.why) && opt_env("MB_WIDE_VERBOSE")) fprintf(stderr, "[mbhip] wide jit (one workgroup per sequence): interpreter kept -- %s\n", J.why.c_str());
+    if (!wide_jit_build(ins, F, J, &J.why) && opt_present<MB_WIDE_VERBOSE>()) fprintf(stderr, "[mbhip] wide jit (one workgroup per sequence): interpreter kept -- %s\n", J.why.c_str());
   }
   return J.mod ? &J : nullptr;
 }
@@ -2400,7 +2398,7 @@ int wide_fill(const mb_machine *m, WideProgram &P, const PairDesc *d_desc, long 
     return 0;
   }
   if (P.f32) {
-    const bool gv32 = !P.hyb && (P.vecBytes32() > WIDE_LDS_MAX - 64 || env_int_w("MB_WIDE_GLOBAL_VECTORS", 0));
+    const bool gv32 = !P.hyb && (P.vecBytes32() > WIDE_LDS_MAX - 64 || opt_int<MB_WIDE_GLOBAL_VECTORS>());
     float *scr = nullptr;
     if (gv32 && !(scr = (float *)ws_get(scratchSlot, (size_t)nPairs * P.vecBytes32()))) return 1;
     if (P.hyb && !(scr = (float *)ws_get(scratchSlot, (size_t)nPairs * P.NV * sizeof(float)))) return 1;
@@ -2419,7 +2417,7 @@ int wide_fill(const mb_machine *m, WideProgram &P, const PairDesc *d_desc, long 
     g_last_launches += 1;
     return 0;
   }
-  const bool gv = P.vecBytes() > WIDE_LDS_MAX || env_int_w("MB_WIDE_GLOBAL_VECTORS", 0);
+  const bool gv = P.vecBytes() > WIDE_LDS_MAX || opt_int<MB_WIDE_GLOBAL_VECTORS>();
   double *scratch = nullptr;
   if (gv && !(scratch = (double *)ws_get(scratchSlot, (size_t)nPairs * P.vecBytes()))) return 1;
   int rc;
@@ -2609,7 +2607,7 @@ int wide_traceback_codes(const mb_machine *m, const WideProgram &P, const PairDe
   // the window wants at least 2 x 2 rows; the tables go to LDS when 2 x 4 rows still fit beside them, the fast words (8 bytes per
   // state) when they do too
   if (tabBytes + (size_t)8 * Sb <= budget && tbEntriesN < 65536) Q.tablesInLds = 1;
-  if (Q.tablesInLds && tabBytes + (size_t)S * 8 + 8 + (size_t)8 * Sb <= budget && env_int_w("MB_ONETAPE_TB_FAST", 1) != 0) { Q.fast = 1; tabBytes += (size_t)S * 8 + 8; }
+  if (Q.tablesInLds && tabBytes + (size_t)S * 8 + 8 + (size_t)8 * Sb <= budget && opt_int<MB_ONETAPE_TB_FAST>() != 0) { Q.fast = 1; tabBytes += (size_t)S * 8 + 8; }
   const size_t forRows = budget - (Q.tablesInLds ? tabBytes : 0);
   Q.rowsPerHalf = (int)std::max<size_t>(1, std::min<size_t>(forRows / (2 * (size_t)Sb), 32));
   if ((size_t)2 * Q.rowsPerHalf * Sb > budget) { set_error("one-tape traceback codes: a code row exceeds the LDS"); return 1; }
@@ -2627,8 +2625,9 @@ int wide_fill2(const mb_machine *m, WideProgram &A, WideProgram &B, const PairDe
   if (!A.ok || !B.ok) { set_error("wide program not built"); return 1; }
   if (nA <= 0 || nB <= 0) return -1;
   if (A.viterbi || B.viterbi || A.retOk || B.retOk || A.f32 != B.f32 || A.hyb != B.hyb || A.fastIdx != B.fastIdx || A.W != B.W) return -1;
+  const bool forceGv = opt_int<MB_WIDE_GLOBAL_VECTORS>() != 0;
   if (A.f32) {
-    auto gvOf = [](const WideProgram &Q) { return !Q.hyb && (Q.vecBytes32() > WIDE_LDS_MAX - 64 || env_int_w("MB_WIDE_GLOBAL_VECTORS", 0)); };
+    auto gvOf = [forceGv](const WideProgram &Q) { return !Q.hyb && (Q.vecBytes32() > WIDE_LDS_MAX - 64 || forceGv); };
     if (gvOf(A) != gvOf(B)) return -1;
     const bool gv32 = gvOf(A);
     float *sa = nullptr, *sb = nullptr;
@@ -2640,7 +2639,7 @@ int wide_fill2(const mb_machine *m, WideProgram &A, WideProgram &B, const PairDe
     g_last_launches += 1;
     return rc;
   }
-  auto gvOf = [](const WideProgram &Q) { return Q.vecBytes() > WIDE_LDS_MAX || env_int_w("MB_WIDE_GLOBAL_VECTORS", 0) != 0; };
+  auto gvOf = [forceGv](const WideProgram &Q) { return Q.vecBytes() > WIDE_LDS_MAX || forceGv; };
   if (gvOf(A) != gvOf(B)) return -1;
   const bool gv = gvOf(A);
   double *sa = nullptr, *sb = nullptr;
@@ -2906,7 +2905,7 @@ static void launch_counts_lds(const mb_machine *m, const WideCountPlan &C, const
   if (!attr) { (void)hipFuncSetAttribute((const void *)&k_onetape_counts_lds<EPT, NL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
   hipLaunchKernelGGL((k_onetape_counts_lds<EPT, NL>), dim3((unsigned)nUnits), dim3(512), lds, st, m->dev, (const OtEdge *)C.d_edges,
                      (const unsigned short *)C.d_waveLabel, C.nWaves * 64, d_desc, colSplit, inputTape ? 1 : 0, d_tape, fwd, bwd, d_counts,
-                     env_int_w("MB_ONETAPE_COUNT_NORMALISE", 1), g_deterministic ? 1 : 0);
+                     opt_int<MB_ONETAPE_COUNT_NORMALISE>(), g_deterministic ? 1 : 0);
 }
 
 bool wide_counts_build(const mb_machine *m, WideCountPlan &C) {
@@ -2960,16 +2959,16 @@ int wide_counts(const mb_machine *m, const WideCountPlan &C, const PairDesc *d_d
   int maxLen = 0;
   for (const PairDesc &pd : hp) maxLen = std::max(maxLen, inputTape ? pd.inLen : pd.outLen);
   int colSplit = 1;
-  const int want = env_int_w("MB_ONETAPE_COUNT_UNITS", 32);
+  const int want = opt_int<MB_ONETAPE_COUNT_UNITS>();
   while ((long long)hp.size() * colSplit < want && (maxLen + 1) / (colSplit * 2) >= 64) colSplit *= 2;
   // columns staged in LDS when three state vectors fit and a thread's share of the transitions fits its registers
   const long long nE = (long long)C.nWaves * 64;
-  if ((size_t)3 * m->S * sizeof(double) <= 158 * 1024 && nE <= 32 * 512 && env_int_w("MB_ONETAPE_COUNTS_LDS", 1)) {
+  if ((size_t)3 * m->S * sizeof(double) <= 158 * 1024 && nE <= 32 * 512 && opt_int<MB_ONETAPE_COUNTS_LDS>()) {
     // one workgroup per CU (three state vectors in LDS): the sequences are cut into column parts (>= 64 columns) until the launch fills
     // the chip AND its last round of workgroups is nearly full -- 33 sequences x 8 parts = 264 workgroups on 256 CUs ran two rounds for
     // the work of one (141 ms where 31 x 16 parts took 71; profiles/r06_onetape_estep_trace.txt)
     int cs = 1;
-    const int wantUnits = env_int_w("MB_ONETAPE_COUNT_LDS_UNITS", 256);
+    const int wantUnits = opt_int<MB_ONETAPE_COUNT_LDS_UNITS>();
     int cus = 0;
     { int dev = 0; hipDeviceProp_t prop; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount; (void)hipGetLastError(); }
     auto tailOk = [&](long long units) { if (cus <= 0) return true; const long long rounds = (units + cus - 1) / cus; return (double)units >= 0.9 * (double)(rounds * cus); };
@@ -2991,7 +2990,7 @@ int wide_counts(const mb_machine *m, const WideCountPlan &C, const PairDesc *d_d
   const long long grid = ((nUnits + 7) / 8) * 8 * nEB;
   if (grid > 0x7fffffffll) { set_error("one-tape counts: launch too large"); return 1; }
   float *d_norm = nullptr;
-  if (env_int_w("MB_ONETAPE_COUNT_NORMALISE", 1)) {
+  if (opt_int<MB_ONETAPE_COUNT_NORMALISE>()) {
     long long cols = 0;
     for (const PairDesc &pd : hp) cols = std::max(cols, pd.cellBase / std::max(m->S, 1) + (inputTape ? pd.inLen : pd.outLen) + 1);
     d_norm = (float *)ws_get(13, (size_t)std::max<long long>(cols, 1) * sizeof(float));
@@ -3149,7 +3148,7 @@ __global__ __launch_bounds__(1024) void k_onetape_traceback(DevMachine m, const 
 
 bool wide_traceback_build(const mb_machine *m, WideTbPlan &T) {
   T.tried = true; T.ok = false;
-  if ((m->nIn != 0) == (m->nOut != 0) || !env_int_w("MB_ONETAPE_TRACEBACK", 1)) return false;
+  if ((m->nIn != 0) == (m->nOut != 0) || !opt_int<MB_ONETAPE_TRACEBACK>()) return false;
   const int S = m->S, K = (m->nIn + 1) * (m->nOut + 1);
   T.ldsBytes = 3 * (size_t)S * sizeof(double) + (size_t)(S + 2) * sizeof(int);
   if (T.ldsBytes > WIDE_LDS_MAX - 64 || S > 65535 || K > 65535) return false;

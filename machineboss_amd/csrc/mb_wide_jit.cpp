@@ -20,16 +20,12 @@
 
 namespace mb {
 
-static int jenv(const char *name, int dflt) {
-  const char *v = opt_env(name);
-  return v && *v ? atoi(v) : dflt;
-}
-bool wide_jit_enabled() { return jenv("MB_WIDE_JIT", 1) != 0; }
+bool wide_jit_enabled() { return opt_int<MB_WIDE_JIT>() != 0; }
 // timing experiments with WRONG results (library built with -DMB_EXPERIMENTS only): bits of MB_WIDE_JIT_KNOCKOUT -- 1 no lane-group
 // reduction, 2 no barriers, 4 no per-period bookkeeping (token window, penalty table, imports), 8 no exports / matrix stores
 static int knockout() {
 #ifdef MB_EXPERIMENTS
-  return jenv("MB_WIDE_JIT_KNOCKOUT", 0);
+  return opt_int<MB_WIDE_JIT_KNOCKOUT>();
 #else
   return 0;
 #endif
@@ -289,7 +285,7 @@ struct Gen {
     const WideJitRound &R = D.rounds[r];
     const WideJitIn &in = D.in;
     const unsigned penOff = (unsigned)pt * (unsigned)(in.ret.nPen + in.nImp) * 8u;
-    const bool twoPass = !F.viterbi && jenv("MB_WIDE_JIT_TWOPASS", 1) != 0 && R.depth <= 8;
+    const bool twoPass = !F.viterbi && opt_int<MB_WIDE_JIT_TWOPASS>() != 0 && R.depth <= 8;
     o << "    { // round " << r << ": slots " << R.firstSlot << ".." << R.firstSlot + R.depth - 1 << "\n";
     // the LDS reads of every slot first (a streamed program: its packed words taken from the prefetch ring), then -- in the period's first
     // round -- the bookkeeping of the NEXT period (token window, penalty table, imports: a few lanes' work whose own LDS round trip then
@@ -511,7 +507,7 @@ bool wide_jit_plan(const std::vector<WideJitIn> &ins, bool acc, int attempt, std
   auto fail = [&](const std::string &msg) { if (why) *why = msg; return false; };
   descs.assign(ins.size(), WideJitDesc());
   const int wavesPerSimd = (ins[0].W / 64 + 3) / 4, regs = 512 / wavesPerSimd;
-  const int forceLevel = attempt == 0 ? jenv("MB_WIDE_JIT_LEVEL", -1) : 1;
+  const int forceLevel = attempt == 0 ? opt_int<MB_WIDE_JIT_LEVEL>() : 1;
   const int maxRing = attempt <= 1 ? 17 : (attempt == 2 ? 4 : 2);
   for (size_t p = 0; p < ins.size(); ++p) {
     std::string w;
@@ -543,7 +539,7 @@ bool wide_jit_build(const std::vector<WideJitIn> &ins, const WideJitFlags &F, Wi
     bool spilled = false;
     if (wide_jit_build_one(descs, src, ins, F, K, &lastWhy, &spilled)) return true;
     if (!spilled) break;
-    if (opt_env("MB_WIDE_VERBOSE")) fprintf(stderr, "[mbhip] wide jit: attempt %d spills (%s): planned again with fewer constants in registers\n", attempt, lastWhy.c_str());
+    if (opt_present<MB_WIDE_VERBOSE>()) fprintf(stderr, "[mbhip] wide jit: attempt %d spills (%s): planned again with fewer constants in registers\n", attempt, lastWhy.c_str());
   }
   K.release(); K.tried = true;
   return fail(lastWhy);
@@ -553,7 +549,7 @@ static bool wide_jit_build_one(const std::vector<WideJitDesc> &descs, const std:
   auto fail = [&](const std::string &msg) { if (why) *why = msg; return false; };
   size_t lds = 0;
   for (const WideJitDesc &D : descs) lds = std::max(lds, D.ldsBytes);
-  if (const char *dump = opt_env("MB_WIDE_JIT_DUMP")) {
+  if (const char *dump = opt_text<MB_WIDE_JIT_DUMP>()) {
     const std::string path = std::string(dump) + (F.viterbi ? (F.tb ? ".tb" : ".max") : (F.acc ? ".sum64" : ".sum")) + (F.backward ? ".bwd" : ".fwd") + ".k" + std::to_string(ins.size()) + ".hip";
     if (FILE *f = fopen(path.c_str(), "w")) { fputs(src.c_str(), f); fclose(f); }
   }
@@ -562,13 +558,14 @@ static bool wide_jit_build_one(const std::vector<WideJitDesc> &descs, const std:
   else {
     std::string code, log;
     bool fromCache = false;
+    const bool verbose = opt_present<MB_WIDE_VERBOSE>();
     if (!jit_compile(src, "mb_wide_jit.hip", code, &log, &fromCache)) {
-      if (opt_env("MB_WIDE_VERBOSE")) fprintf(stderr, "[mbhip] wide jit: hiprtc failed:\n%s\n", log.c_str());
+      if (verbose) fprintf(stderr, "[mbhip] wide jit: hiprtc failed:\n%s\n", log.c_str());
       return fail("hiprtc: " + log.substr(0, 400));
     }
     const long long scratch = jit_kernel_meta(code, ".private_segment_fixed_size");
-    if (opt_env("MB_WIDE_VERBOSE")) fprintf(stderr, "[mbhip] wide jit: %zu bytes of source, code object %zu bytes%s, scratch %lld bytes, %lld spilled VGPRs\n", src.size(), code.size(), fromCache ? " (cache)" : "", scratch, jit_kernel_meta(code, ".vgpr_spill_count"));
-    if (scratch > 0 && !jenv("MB_WIDE_JIT_ALLOW_SCRATCH", 0)) { *spilled = true; return fail("the kernel spills to scratch memory (" + std::to_string(scratch) + " bytes)"); }
+    if (verbose) fprintf(stderr, "[mbhip] wide jit: %zu bytes of source, code object %zu bytes%s, scratch %lld bytes, %lld spilled VGPRs\n", src.size(), code.size(), fromCache ? " (cache)" : "", scratch, jit_kernel_meta(code, ".vgpr_spill_count"));
+    if (scratch > 0 && !opt_int<MB_WIDE_JIT_ALLOW_SCRATCH>()) { *spilled = true; return fail("the kernel spills to scratch memory (" + std::to_string(scratch) + " bytes)"); }
     hipModule_t mod = nullptr; hipFunction_t fn = nullptr;
     if (hipModuleLoadData(&mod, code.data()) != hipSuccess) {
       (void)hipGetLastError();
