@@ -284,8 +284,8 @@ int mb_profile_pair_fill_merged(mb_machine *m, int mode, const int32_t *inTok, i
  * blanks on either tape are not edges.  pathCap must hold the sum of mb_profile_pair_path_bound(m, K, rows) over the pairs.  Counts
  * with MB_DETERMINISTIC=1 go through 64-bit fixed point and are the same bits from call to call.  Materialised lattices:
  * cells[(((i*(nRows+1)) + row)*3 + layer)*nStates + state]; mb_profile_two_fill: cellsOut[(nIn+1)*(nRows+1)*3*nStates], mode
- * MB_FORWARD / MB_VITERBI / MB_BACKWARD (Backward: layer 0 = from the arrived stage, 2 = from the committed stage).  There are no
- * envelopes and no CTC-merged form.  Errors, before anything is launched: "two-profile sweeps need a machine with an input
+ * MB_FORWARD / MB_VITERBI / MB_BACKWARD (Backward: layer 0 = from the arrived stage, 2 = from the committed stage).  Envelopes are
+ * below; there is no CTC-merged form.  Errors, before anything is launched: "two-profile sweeps need a machine with an input
  * alphabet", NaN / +inf weights in either table, a pathCap below the bound, a lattice beyond the memory budget on its own. */
 typedef struct mb_profile_twos mb_profile_twos;
 mb_profile_twos *mb_profile_twos_create(mb_machine *m, int64_t nPairs, const double *logA, const int64_t *inOff, const double *logB,
@@ -311,6 +311,24 @@ int mb_profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t nIn
 int mb_profile_twos_row_posteriors(mb_profile_twos *p, double *postA /* [sum K][nInTok+1], may be NULL */,
                                    double *postB /* [sum rows][nOutTok+1], may be NULL */, double *loglike /* [nPairs], may be NULL */);
 int mb_profile_twos_set_rows(mb_profile_twos *p, const double *logA /* NULL: keep */, const double *logB /* NULL: keep */);
+
+/* Pairs of profiles under an envelope (docs/profile_tapes.md, "Pairs of profiles under an envelope"): per output row r = 0..rows the
+ * half-open interval [inStart[r], inEnd[r]) of INPUT-ROW positions i = 0..K whose cells exist -- the orientation and the contract of
+ * mb_profile_pairs_set_envelopes with K for nIn; all three layers (N, W, Z; NB, WB, ZB) of every other cell are -inf, and the input
+ * blank Z[i-1][r] -> Z[i][r] is left out when (i-1, r) lies outside.  Pair k owns rows envOff[k]..envOff[k+1]: rows_k + 1 of them, or
+ * none; envOff == NULL clears every envelope.  No call mixes geometries: if any pair has an envelope EVERY pair of the object runs
+ * through the envelope kernels, a pair that was given none under the full envelope [0, K + 1), whose results are the bits of no
+ * envelope; one launch per kernel and chunk, as for a plain object.  Forward (both flags), Viterbi, counts and both tables of the row
+ * posteriors visit the envelope cells alone; the tie order, the path format and the path bound are unchanged.  Materialised lattices
+ * are compact, cells[((off[r] + i - inStart[r])*3 + layer)*nStates + state] with off[r] the cells of the rows before r;
+ * mb_profile_twos_cells is the doubles of all of them (3 nStates sum(inEnd - inStart) per pair; the memory budget chunks by it).
+ * mb_profile_two_fill_env hands back the full rectangle of mb_profile_two_fill with -inf outside; both pointers NULL = no envelope.
+ * mb_profile_twos_set_rows keeps the envelopes.  Errors, before anything is launched (the pairs are then left without envelopes):
+ * "Envelope/sequence mismatch", "Envelope is not connected", "Envelope is not monotone", as mb_profile_pairs_set_envelopes. */
+int mb_profile_twos_set_envelopes(mb_profile_twos *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd);
+int mb_profile_two_fill_env(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows,
+                            const int32_t *envStart, const int32_t *envEnd, double *cellsOut);
+int64_t mb_profile_twos_cells(const mb_profile_twos *p);   /* doubles of all materialised lattices under the current envelopes */
 
 /* ---- prefix search: imputing the input tape (--prefix-decode / --prefix-encode / --random-encode) -------------------------------
  * The node fill of the reference's PrefixTree (src/ctc.cpp:25-88) on the device, the tree and its heap on the host

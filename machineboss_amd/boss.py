@@ -624,7 +624,8 @@ def _runProfilePairs(args, out, machine: Machine) -> int:
 
 
 def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "device", params=None,
-                     loglike: bool = True, viterbi: bool = False, counts: bool = False, posteriors: bool = False):
+                     loglike: bool = True, viterbi: bool = False, counts: bool = False, posteriors: bool = False,
+                     band: Optional[int] = None):
     """Every input profile (a profile.Profile, read against the machine's input alphabet) as one pair with ``outProfile`` (a
     profile.Profile, read against its output alphabet), all pairs in one batch, on a machine with an input alphabet
     (docs/profile_tapes.md, "Pairs of profiles").  ``backend``: "device" (capi.DeviceProfileTwos) or "numpy"
@@ -633,10 +634,13 @@ def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "d
     summed over the pairs, or None.  ``posteriors``: scores["posteriors"] holds one (postA[K, nInTok + 1], postB[L, nOutTok + 1]) per
     input profile, the posterior probability that each row of either tape was consumed as each of its tokens (column 0: as the
     blank; docs/profile_tapes.md, "Row posteriors of pairs of profiles") -- zeros for a pair that scores -inf; the key is absent
-    when not asked for."""
+    when not asked for.  ``band``: every pair is swept under seqpair.Envelope.band(K, L, band), K the rows of its input profile
+    and L those of ``outProfile``, on both backends (docs/profile_tapes.md, "Pairs of profiles under an envelope"); a width that
+    cannot bridge the slope raises MachineError("Envelope is not connected")."""
     import numpy as np
     from . import dp
     from .profile import TwoProfileDP
+    from .seqpair import Envelope
     ev = EvaluatedMachine.fromMachine(machine, params)
     if not ev.nInTok:
         raise MachineError("two-profile sweeps need a machine with an input alphabet")
@@ -644,20 +648,21 @@ def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "d
     B = outProfile.logRows(ev)
     acc = dp.MachineCounts(ev)
     fwd = vit = post = None
+    envs = [None] * len(As) if band is None else [Envelope.band(len(A), len(B), int(band)) for A in As]
     if backend == "numpy":
         tdp = TwoProfileDP(ev)
-        fwd = [tdp.forward(A, B)[0] for A in As] if loglike else None
+        fwd = [tdp.forward(A, B, env=e)[0] for A, e in zip(As, envs)] if loglike else None
         if counts:
-            for A in As:
-                c, ll = tdp.counts(A, B)
+            for A, e in zip(As, envs):
+                c, ll = tdp.counts(A, B, env=e)
                 acc._flat += c
                 acc.loglike += ll
-        vit = [tdp.forward(A, B, "max")[0] for A in As] if viterbi else None
-        post = [tdp.rowPosteriors(A, B)[:2] for A in As] if posteriors else None
+        vit = [tdp.forward(A, B, "max", env=e)[0] for A, e in zip(As, envs)] if viterbi else None
+        post = [tdp.rowPosteriors(A, B, env=e)[:2] for A, e in zip(As, envs)] if posteriors else None
     else:
         from . import capi
         dm = capi.DeviceMachine(ev)
-        twos = capi.DeviceProfileTwos(dm, As, [B] * len(As))
+        twos = capi.DeviceProfileTwos(dm, As, [B] * len(As), envs=None if band is None else envs)
         try:
             fwd = twos.forward(capi.MB_ROLLING) if loglike else None
             if counts:

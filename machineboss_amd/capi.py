@@ -39,6 +39,7 @@ EXPORTS = [
     "mb_profile_twos_create", "mb_profile_twos_destroy", "mb_profile_twos_forward", "mb_profile_twos_viterbi", "mb_profile_twos_counts",
     "mb_profile_twos_row_posteriors", "mb_profile_twos_set_rows",
     "mb_profile_two_fill",
+    "mb_profile_twos_set_envelopes", "mb_profile_two_fill_env", "mb_profile_twos_cells",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
     "mb_prefix_node_cells", "mb_prefix_create_profiles", "mb_prefix_create_merged",
 ]
@@ -152,6 +153,9 @@ def load():
     L.mb_profile_twos_row_posteriors.argtypes = [vp, dp, dp, dp]
     L.mb_profile_twos_set_rows.argtypes = [vp, dp, dp]
     L.mb_profile_two_fill.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, dp]
+    L.mb_profile_twos_set_envelopes.argtypes = [vp, i64p, i32p, i32p]
+    L.mb_profile_two_fill_env.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, i32p, i32p, dp]
+    L.mb_profile_twos_cells.argtypes = [vp]; L.mb_profile_twos_cells.restype = C.c_int64
     L.mb_prefix_create.restype = vp
     L.mb_prefix_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, C.c_int64]
     L.mb_prefix_create_profiles.restype = vp
@@ -745,23 +749,7 @@ class DeviceProfilePairs:
         """envs: per pair None (full: the pair keeps the sweeps over the whole rectangle), a seqpair.Envelope or an (inStart,
         inEnd) pair of rows + 1 entries each; ``None`` instead of a list clears every envelope (docs/profile_tapes.md, "Pairs
         under an envelope")."""
-        if envs is None:
-            _check(load().mb_profile_pairs_set_envelopes(self.h, None, None, None))
-            return
-        envs = list(envs)
-        if len(envs) != self.nPairs:
-            raise ValueError("one envelope (or None) per pair, please")
-        off = np.zeros(self.nPairs + 1, np.int64)
-        st, en = [], []
-        for k, e in enumerate(envs):
-            n = 0
-            if e is not None:
-                a, b = _env_rows(e)
-                st.append(a); en.append(b); n = len(a)
-            off[k + 1] = off[k] + n
-        cat = lambda xs: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros(1, np.int32), np.int32)
-        a, b = cat(st), cat(en)
-        _check(load().mb_profile_pairs_set_envelopes(self.h, _p(off, C.c_int64), _p(a, C.c_int32), _p(b, C.c_int32)))
+        _set_envelopes(load().mb_profile_pairs_set_envelopes, self.h, self.nPairs, envs)
 
     def cells(self) -> int:
         """Doubles of the materialised lattices of all pairs under the current envelopes."""
@@ -825,6 +813,28 @@ def _env_rows(env):
     return a, b
 
 
+def _set_envelopes(call, h, nPairs, envs):
+    """The envelopes of a pairs object through its set_envelopes entry ``call``: one None, Envelope or (inStart, inEnd) per pair,
+    packed; ``None`` instead of a list clears."""
+    if envs is None:
+        _check(call(h, None, None, None))
+        return
+    envs = list(envs)
+    if len(envs) != nPairs:
+        raise ValueError("one envelope (or None) per pair, please")
+    off = np.zeros(nPairs + 1, np.int64)
+    st, en = [], []
+    for k, e in enumerate(envs):
+        n = 0
+        if e is not None:
+            a, b = _env_rows(e)
+            st.append(a); en.append(b); n = len(a)
+        off[k + 1] = off[k] + n
+    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs) if xs else np.zeros(1, np.int32), np.int32)
+    a, b = cat(st), cat(en)
+    _check(call(h, _p(off, C.c_int64), _p(a, C.c_int32), _p(b, C.c_int32)))
+
+
 def profile_pair_fill(dm: DeviceMachine, mode: int, x, logP, env=None) -> np.ndarray:
     """One pair's lattice [len(x) + 1, rows + 1, 2, nStates] (layer 0 = arrived at (i, row), 1 = after the output-less moves).
     ``env``: a seqpair.Envelope or (inStart, inEnd); the cells outside it are -inf in both layers."""
@@ -858,9 +868,10 @@ class DeviceProfileTwos:
     """Device-resident batch of (input profile, output profile) pairs (mb_profile_twos*) for a machine with an input alphabet: pair k
     is the [rows, nInTok + 1] log weights ``inProfiles[k]`` (profile.Profile.logRowsIn) against the [rows, nOutTok + 1] log weights
     ``outProfiles[k]`` (profile.Profile.logRows), column 0 of either the blank.  The yardstick is profile.TwoProfileDP
-    (docs/profile_tapes.md, "Pairs of profiles")."""
+    (docs/profile_tapes.md, "Pairs of profiles").  ``envs``: what envelopes() takes (docs/profile_tapes.md, "Pairs of profiles
+    under an envelope"); the yardstick is then TwoProfileDP(env=...)."""
 
-    def __init__(self, dm: DeviceMachine, inProfiles, outProfiles):
+    def __init__(self, dm: DeviceMachine, inProfiles, outProfiles, envs=None):
         self.dm = dm
         wa, wb = dm.em.nInTok + 1, dm.em.nOutTok + 1
         As = [np.asarray(p, np.float64).reshape(-1, wa) for p in inProfiles]
@@ -879,6 +890,19 @@ class DeviceProfileTwos:
                                           _p(self.logB, C.c_double), _p(self.rowOff, C.c_int64))
         if not self.h:
             raise MbError(L.mb_last_error().decode())
+        if envs is not None:
+            self.envelopes(envs)
+
+    def envelopes(self, envs):
+        """Replaces the envelopes.  envs: per pair None, a seqpair.Envelope or an (inStart, inEnd) pair of rows + 1 entries each --
+        output row r holds the input-row positions inStart[r] <= i < inEnd[r]; ``None`` instead of a list clears every envelope.
+        If any pair has one, every pair runs the envelope kernels, a pair given None under the full envelope (the same bits as
+        without).  A refused list (MbError) leaves the object without envelopes."""
+        _set_envelopes(load().mb_profile_twos_set_envelopes, self.h, self.nPairs, envs)
+
+    def cells(self) -> int:
+        """Doubles of the materialised lattices of all pairs under the current envelopes."""
+        return int(load().mb_profile_twos_cells(self.h))
 
     def close(self):
         if getattr(self, "h", None) and _lib is not None:
@@ -953,13 +977,21 @@ class DeviceProfileTwos:
             self.logB = logB
 
 
-def profile_two_fill(dm: DeviceMachine, mode: int, logA, logB) -> np.ndarray:
+def profile_two_fill(dm: DeviceMachine, mode: int, logA, logB, env=None) -> np.ndarray:
     """One pair's lattice [rows of A + 1, rows of B + 1, 3, nStates] (layer 0 = arrived at (i, row), 1 = after the output-less
-    moves, 2 = committed to wait for the next input row)."""
+    moves, 2 = committed to wait for the next input row).  ``env``: a seqpair.Envelope or (inStart, inEnd); the cells outside it
+    are -inf in all three layers."""
     A = np.ascontiguousarray(np.asarray(logA, np.float64).reshape(-1, dm.em.nInTok + 1))
     B = np.ascontiguousarray(np.asarray(logB, np.float64).reshape(-1, dm.em.nOutTok + 1))
     cells = np.empty((len(A) + 1, len(B) + 1, 3, dm.nStates), np.float64)
-    _check(load().mb_profile_two_fill(dm.h, mode, _p(A, C.c_double), len(A), _p(B, C.c_double), len(B), _p(cells, C.c_double)))
+    if env is None:
+        _check(load().mb_profile_two_fill(dm.h, mode, _p(A, C.c_double), len(A), _p(B, C.c_double), len(B), _p(cells, C.c_double)))
+        return cells
+    a, b = _env_rows(env)
+    if len(a) != len(B) + 1:
+        raise MbError("Envelope/sequence mismatch")
+    _check(load().mb_profile_two_fill_env(dm.h, mode, _p(A, C.c_double), len(A), _p(B, C.c_double), len(B), _p(a, C.c_int32),
+                                          _p(b, C.c_int32), _p(cells, C.c_double)))
     return cells
 
 

@@ -1,6 +1,6 @@
 // mb_profile_api.hip -- the C-ABI of the profile tapes (include/mbhip.h, docs/profile_tapes.md): one-tape profiles (mb_profiles, plain
 // and CTC-merged), sequence-against-profile pairs (mb_profile_pairs, plain, merged and under envelopes) and two-profile pairs
-// (mb_profile_twos).
+// (mb_profile_twos, plain and under envelopes).
 //
 // Host orchestration only, like mb_api.hip.  Each family has Forward, Viterbi, counts, row posteriors, set_rows and a single-lattice
 // fill; what those calls share with the token batch calls -- the chunk loop, the call-scoped device buffers, the count tail -- is in
@@ -21,6 +21,7 @@
 #include "mb_profile_pair_merge.h"
 #include "mb_profile_post.h"
 #include "mb_profile_two.h"
+#include "mb_profile_two_env.h"
 
 namespace mb {
 
@@ -618,55 +619,68 @@ static void pp_env_free(mb_profile_pairs *p) {
   p->envBase.clear(); p->diagBase.clear(); p->envCells.clear(); p->envM.clear(); p->h_envStart.clear(); p->h_envEnd.clear();
 }
 
-// Checks as mb_batch_set_envelopes (fits, connected) and, new here, that neither bound decreases from one row to the next: the
-// sweeps rest on the envelope cells of an anti-diagonal being consecutive.  A rejected call leaves the pairs without envelopes.
+// The envelopes of a batch on the host, as mb_profile_pairs_set_envelopes and mb_profile_twos_set_envelopes build them: per pair
+// where its rows and its diagonal runs start (-1: none), its cells and its M; the rows, their compact offsets and the runs, packed.
+struct EnvHost {
+  std::vector<long long> envBase, diagBase, envCells, off;
+  std::vector<int> M, st, en, lo, cnt;
+  explicit EnvHost(long long n) : envBase((size_t)n, -1), diagBase((size_t)n, -1), envCells((size_t)n, 0), M((size_t)n, 0) {}
+};
+
+// Pair k's envelope (I input positions, L rows; `rows` entries of st / en) into h.  Checks as mb_batch_set_envelopes (fits,
+// connected) and that neither bound decreases from one row to the next: the sweeps rest on the envelope cells of an anti-diagonal
+// being consecutive.
+static int env_add(EnvHost &h, long long k, long long I, long long L, long long rows, const int32_t *st, const int32_t *en) {
+  if (rows != L + 1) { set_error("Envelope/sequence mismatch"); return 1; }
+  for (long long y = 0; y < rows; ++y)
+    if (st[y] < 0 || en[y] > I + 1 || st[y] > en[y]) { set_error("Envelope/sequence mismatch"); return 1; }
+  bool conn = env_overlapping(st[0], en[0], 0, 1);
+  for (long long y = 1; conn && y < rows; ++y) conn = env_overlapping(st[y - 1], (long long)en[y - 1] + 1, st[y], en[y]);
+  conn = conn && env_overlapping(st[rows - 1], en[rows - 1], I, I + 1);
+  if (!conn) { set_error("Envelope is not connected"); return 1; }
+  for (long long y = 1; y < rows; ++y)
+    if (st[y] < st[y - 1] || en[y] < en[y - 1]) { set_error("Envelope is not monotone"); return 1; }
+  h.envBase[(size_t)k] = (long long)h.st.size(); h.diagBase[(size_t)k] = (long long)h.lo.size();
+  const size_t d0 = h.lo.size();
+  h.lo.resize(d0 + (size_t)(I + L + 1), 0); h.cnt.resize(d0 + (size_t)(I + L + 1), 0);
+  long long cells = 0;
+  for (long long y = 0; y < rows; ++y) {
+    h.st.push_back(st[y]); h.en.push_back(en[y]); h.off.push_back(cells);
+    cells += en[y] - st[y];
+    // row y puts one cell on each of the diagonals st[y] + y .. en[y] - 1 + y; the rows go upwards, so on a diagonal every
+    // later row holds a smaller i than the rows before it: the last one written is the diagonal's first i
+    for (long long i = st[y]; i < en[y]; ++i) { h.lo[d0 + (size_t)(i + y)] = (int)i; ++h.cnt[d0 + (size_t)(i + y)]; }
+  }
+  h.envCells[(size_t)k] = cells;
+  int M = 1;
+  for (size_t d = d0; d < h.lo.size(); ++d) M = std::max(M, h.cnt[d]);
+  h.M[(size_t)k] = M;
+  return 0;
+}
+static bool env_upload(void **dst, const void *src, size_t bytes) {
+  return hip_ok(hipMalloc(dst, std::max<size_t>(bytes, 8)), "hipMalloc(pair envelopes)") && h2d_large(*dst, src, bytes) == 0;
+}
+
+// A rejected call leaves the pairs without envelopes.
 static int profile_pairs_set_envelopes(mb_profile_pairs *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
   pp_env_free(p);
   if (!envOff) return 0;
   const long long total = envOff[p->n] - envOff[0];
   if (total && p->nCols) { set_error("envelopes take plain profiles"); return 1; }
   if (total && (!inStart || !inEnd)) { set_error("null argument"); return 1; }
-  std::vector<long long> envBase((size_t)p->n, -1), diagBase((size_t)p->n, -1), envCells((size_t)p->n, 0), hOff;
-  std::vector<int> envM((size_t)p->n, 0), hSt, hEn, hLo, hCnt;
+  EnvHost h(p->n);
   for (long long k = 0; k < p->n; ++k) {
-    const long long rows = envOff[k + 1] - envOff[k], I = pp_in(p, k), L = pp_rows(p, k);
+    const long long rows = envOff[k + 1] - envOff[k];
     if (rows == 0) continue;   // full: the pair keeps the full geometry of mb_profile_pair.hip
-    if (rows != L + 1) { set_error("Envelope/sequence mismatch"); return 1; }
-    const int32_t *st = inStart + envOff[k], *en = inEnd + envOff[k];
-    for (long long y = 0; y < rows; ++y)
-      if (st[y] < 0 || en[y] > I + 1 || st[y] > en[y]) { set_error("Envelope/sequence mismatch"); return 1; }
-    bool conn = env_overlapping(st[0], en[0], 0, 1);
-    for (long long y = 1; conn && y < rows; ++y) conn = env_overlapping(st[y - 1], (long long)en[y - 1] + 1, st[y], en[y]);
-    conn = conn && env_overlapping(st[rows - 1], en[rows - 1], I, I + 1);
-    if (!conn) { set_error("Envelope is not connected"); return 1; }
-    for (long long y = 1; y < rows; ++y)
-      if (st[y] < st[y - 1] || en[y] < en[y - 1]) { set_error("Envelope is not monotone"); return 1; }
-    envBase[(size_t)k] = (long long)hSt.size(); diagBase[(size_t)k] = (long long)hLo.size();
-    const size_t d0 = hLo.size();
-    hLo.resize(d0 + (size_t)(I + L + 1), 0); hCnt.resize(d0 + (size_t)(I + L + 1), 0);
-    long long cells = 0;
-    for (long long y = 0; y < rows; ++y) {
-      hSt.push_back(st[y]); hEn.push_back(en[y]); hOff.push_back(cells);
-      cells += en[y] - st[y];
-      // row y puts one cell on each of the diagonals st[y] + y .. en[y] - 1 + y; the rows go upwards, so on a diagonal every
-      // later row holds a smaller i than the rows before it: the last one written is the diagonal's first i
-      for (long long i = st[y]; i < en[y]; ++i) { hLo[d0 + (size_t)(i + y)] = (int)i; ++hCnt[d0 + (size_t)(i + y)]; }
-    }
-    envCells[(size_t)k] = cells;
-    int M = 1;
-    for (size_t d = d0; d < hLo.size(); ++d) M = std::max(M, hCnt[d]);
-    envM[(size_t)k] = M;
+    if (env_add(h, k, pp_in(p, k), pp_rows(p, k), rows, inStart + envOff[k], inEnd + envOff[k])) return 1;
   }
-  if (hSt.empty()) return 0;
+  if (h.st.empty()) return 0;
   if (ensure_init()) return 1;
-  auto up = [&](void **dst, const void *src, size_t bytes) {
-    return hip_ok(hipMalloc(dst, std::max<size_t>(bytes, 8)), "hipMalloc(pair envelopes)") && h2d_large(*dst, src, bytes) == 0;
-  };
-  if (!up((void **)&p->d_envStart, hSt.data(), hSt.size() * sizeof(int)) || !up((void **)&p->d_envEnd, hEn.data(), hEn.size() * sizeof(int)) ||
-      !up((void **)&p->d_envOff, hOff.data(), hOff.size() * sizeof(long long)) || !up((void **)&p->d_diagLo, hLo.data(), hLo.size() * sizeof(int)) ||
-      !up((void **)&p->d_diagCnt, hCnt.data(), hCnt.size() * sizeof(int)) || !hip_ok(hipStreamSynchronize(g_stream), "H2D pair envelopes")) { pp_env_free(p); return 1; }
-  p->envBase.swap(envBase); p->diagBase.swap(diagBase); p->envCells.swap(envCells); p->envM.swap(envM);
-  p->h_envStart.swap(hSt); p->h_envEnd.swap(hEn);
+  if (!env_upload((void **)&p->d_envStart, h.st.data(), h.st.size() * sizeof(int)) || !env_upload((void **)&p->d_envEnd, h.en.data(), h.en.size() * sizeof(int)) ||
+      !env_upload((void **)&p->d_envOff, h.off.data(), h.off.size() * sizeof(long long)) || !env_upload((void **)&p->d_diagLo, h.lo.data(), h.lo.size() * sizeof(int)) ||
+      !env_upload((void **)&p->d_diagCnt, h.cnt.data(), h.cnt.size() * sizeof(int)) || !hip_ok(hipStreamSynchronize(g_stream), "H2D pair envelopes")) { pp_env_free(p); return 1; }
+  p->envBase.swap(h.envBase); p->diagBase.swap(h.diagBase); p->envCells.swap(h.envCells); p->envM.swap(h.M);
+  p->h_envStart.swap(h.st); p->h_envEnd.swap(h.en);
   p->hasEnv = true;
   return 0;
 }
@@ -946,16 +960,25 @@ namespace mb {
 
 static long long pt_in(const mb_profile_twos *p, long long k) { return p->inOff[k + 1] - p->inOff[k]; }
 static long long pt_rows(const mb_profile_twos *p, long long k) { return p->rowOff[k + 1] - p->rowOff[k]; }
-static long long pt_cells(const mb_profile_twos *p, long long k) { return profile_two_cells(p->m->S, pt_in(p, k), pt_rows(p, k)); }
+// cells (of three layers of S states) of pair k's materialised lattice: the rectangle, or the compact lattice under the envelopes
+static long long pt_ncells(const mb_profile_twos *p, long long k) { return p->hasEnv ? p->envCells[(size_t)k] : (pt_in(p, k) + 1) * (pt_rows(p, k) + 1); }
+static long long pt_cells(const mb_profile_twos *p, long long k) { return pt_ncells(p, k) * 3 * (long long)p->m->S; }
 static double pt_cell_bytes(const mb_profile_twos *p, long long k) { return 8.0 * (double)pt_cells(p, k); }
-// bytes of global scratch the rolling sweep of pair k needs (0: its ring is in LDS)
-static double pt_ring_bytes(const mb_profile_twos *p, long long k) {
-  return profile_two_lds_bytes(p->m->S, pt_in(p, k), pt_rows(p, k)) ? 0.0 : 8.0 * (double)profile_two_ring(p->m->S, pt_in(p, k), pt_rows(p, k));
+// the ring of pair k's rolling sweep and its dynamic LDS (0: a slice of the global scratch buffer)
+static long long pt_ring(const mb_profile_twos *p, long long k) {
+  return p->hasEnv ? profile_two_env_ring(p->m->S, p->envM[(size_t)k]) : profile_two_ring(p->m->S, pt_in(p, k), pt_rows(p, k));
 }
+static size_t pt_ring_lds(const mb_profile_twos *p, long long k) {
+  return p->hasEnv ? profile_two_env_lds_bytes(p->m->S, p->envM[(size_t)k]) : profile_two_lds_bytes(p->m->S, pt_in(p, k), pt_rows(p, k));
+}
+// bytes of global scratch the rolling sweep of pair k needs (0: its ring is in LDS)
+static double pt_ring_bytes(const mb_profile_twos *p, long long k) { return pt_ring_lds(p, k) ? 0.0 : 8.0 * (double)pt_ring(p, k); }
 static long long pt_path_bound(const mb_profile_twos *p, long long k) { return profile_pair_path_bound(p->m->nLevF, pt_in(p, k), pt_rows(p, k)); }
 
+// No call mixes geometries: without envelopes every pair has a PairProfDesc in d, with them every pair a TwoEnvDesc in e (a pair
+// that was given none runs under the full envelope).  One launch per kernel and chunk either way, the pairs in their order.
 struct TwoProfPlan {
-  SmBuf<PairProfDesc> d;
+  SmBuf<PairProfDesc> d; SmBuf<TwoEnvDesc> e;
   long long cells = 0, paths = 0, ring = 0, maxItems = 0;
   size_t lds = 0;
 };
@@ -963,41 +986,125 @@ struct TwoProfPlan {
 // descriptors of pairs [p0, p1): lattices, traceback slots and (rolling) scratch rings packed from 0
 static int two_profile_descs(const mb_profile_twos *p, long long p0, long long p1, bool rolling, TwoProfPlan &pl) {
   std::vector<PairProfDesc> h;
+  std::vector<TwoEnvDesc> he;
   const int S = p->m->S;
   for (long long k = p0; k < p1; ++k) {
     const long long K = pt_in(p, k), L = pt_rows(p, k);
-    PairProfDesc d;
+    TwoEnvDesc d;      // (without envelopes its PairProfDesc part alone is kept)
     d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)K; d.nRows = (int)L;
     d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = -1;
     if (rolling) {
-      const size_t lds = profile_two_lds_bytes(S, K, L);
+      const size_t lds = pt_ring_lds(p, k);
       if (lds) pl.lds = std::max(pl.lds, lds);
-      else { d.ringBase = pl.ring; pl.ring += profile_two_ring(S, K, L); }
+      else { d.ringBase = pl.ring; pl.ring += pt_ring(p, k); }
     }
-    pl.maxItems = std::max(pl.maxItems, (std::min(K, L) + 1) * S);
     pl.cells += pt_cells(p, k);
     pl.paths += pt_path_bound(p, k);
-    h.push_back(d);
+    if (p->hasEnv) {
+      d.envBase = p->envBase[(size_t)k]; d.diagBase = p->diagBase[(size_t)k]; d.colBase = p->colBase[(size_t)k];
+      d.nCells = p->envCells[(size_t)k]; d.M = p->envM[(size_t)k];
+      pl.maxItems = std::max(pl.maxItems, (long long)d.M * S);
+      he.push_back(d);
+    } else {
+      pl.maxItems = std::max(pl.maxItems, (std::min(K, L) + 1) * S);
+      h.push_back(d);
+    }
   }
   MB_HIP(pl.d.alloc((long long)h.size()));
+  if (!hip_ok(pl.e.alloc((long long)he.size()), "hipMalloc(pair descriptors)")) return 1;
   if ((!h.empty() && !hip_ok(hipMemcpyAsync(pl.d, h.data(), h.size() * sizeof(PairProfDesc), hipMemcpyHostToDevice, g_stream), "H2D pair descriptors")) ||
+      (!he.empty() && !hip_ok(hipMemcpyAsync(pl.e, he.data(), he.size() * sizeof(TwoEnvDesc), hipMemcpyHostToDevice, g_stream), "H2D pair descriptors")) ||
       !hip_ok(hipStreamSynchronize(g_stream), "H2D pair descriptors")) return 1;
   return 0;
 }
 static auto pt_build(const mb_profile_twos *p, bool rolling) {
   return [p, rolling](const Chunk &c, TwoProfPlan &pl) { return two_profile_descs(p, c.p0, c.p1, rolling, pl); };
 }
-// the materialised Forward (or Viterbi) and Backward of a chunk of np pairs
-static int pt_fwd_mat(const mb_profile_twos *p, int mode, const TwoProfPlan &pl, long long np, double *pool, double *ll) {
-  return launch_profile_two_fwd(p->m, mode, true, pl.d.p, (int)np, 0, pl.maxItems, p->d_logA, p->d_logB, pool, nullptr, ll, g_stream);
+static TwoEnvTables pt_env_tables(const mb_profile_twos *p) {
+  TwoEnvTables t;
+  t.envStart = p->d_envStart; t.envEnd = p->d_envEnd; t.envOff = p->d_envOff; t.diagLo = p->d_diagLo; t.diagCnt = p->d_diagCnt;
+  t.colStart = p->d_colStart; t.colEnd = p->d_colEnd; t.colOff = p->d_colOff;
+  return t;
 }
+// The one place where the two geometries part: the launches of a chunk of np pairs and the names they report.
+static int pt_fwd(const mb_profile_twos *p, int mode, bool mat, const TwoProfPlan &pl, long long np, double *pool, double *scratch, double *ll) {
+  if (p->hasEnv) return launch_profile_two_fwd(p->m, mode, mat, pl.e.p, pt_env_tables(p), (int)np, mat ? 0 : pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, mat ? nullptr : scratch, ll, g_stream);
+  return launch_profile_two_fwd(p->m, mode, mat, pl.d.p, (int)np, mat ? 0 : pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, mat ? nullptr : scratch, ll, g_stream);
+}
+static int pt_fwd_mat(const mb_profile_twos *p, int mode, const TwoProfPlan &pl, long long np, double *pool, double *ll) { return pt_fwd(p, mode, true, pl, np, pool, nullptr, ll); }
 static int pt_bwd(const mb_profile_twos *p, const TwoProfPlan &pl, long long np, double *pool, double *ll) {
+  if (p->hasEnv) return launch_profile_two_bwd(p->m, pl.e.p, pt_env_tables(p), (int)np, pl.maxItems, p->d_logA, p->d_logB, pool, ll, g_stream);
   return launch_profile_two_bwd(p->m, pl.d.p, (int)np, pl.maxItems, p->d_logA, p->d_logB, pool, ll, g_stream);
 }
+static int pt_counts(const mb_profile_twos *p, const TwoProfPlan &pl, long long np, int groups, const double *fwd, const double *bwd, double *cc) {
+  if (p->hasEnv) return launch_profile_two_counts(p->m, pl.e.p, pt_env_tables(p), (int)np, groups, p->d_logA, p->d_logB, fwd, bwd, cc, g_stream);
+  return launch_profile_two_counts(p->m, pl.d.p, (int)np, groups, p->d_logA, p->d_logB, fwd, bwd, cc, g_stream);
+}
+static int pt_rowpost(const mb_profile_twos *p, int axis, const TwoProfPlan &pl, long long np, int groups, int tabMax, const double *fwd, const double *bwd, double *post) {
+  if (p->hasEnv) return launch_profile_two_rowpost(p->m, axis, pl.e.p, pt_env_tables(p), (int)np, groups, tabMax, p->d_logA, p->d_logB, fwd, bwd, post, g_stream);
+  return launch_profile_two_rowpost(p->m, axis, pl.d.p, (int)np, groups, tabMax, p->d_logA, p->d_logB, fwd, bwd, post, g_stream);
+}
+static int pt_traceback(const mb_profile_twos *p, const TwoProfPlan &pl, long long np, const double *pool, uint32_t *e, int32_t *r, int32_t *i, long long *len) {
+  if (p->hasEnv) return launch_profile_two_traceback(p->m, pl.e.p, pt_env_tables(p), (int)np, p->d_logA, p->d_logB, pool, e, r, i, len, g_stream);
+  return launch_profile_two_traceback(p->m, pl.d.p, (int)np, p->d_logA, p->d_logB, pool, e, r, i, len, g_stream);
+}
 
-static const char *pt_fwd_name(int mode, bool mat) {
-  static const char *const names[2][2] = {{"k_profile_two_fwd<sum,rolling>", "k_profile_two_fwd<sum,mat>"}, {"k_profile_two_fwd<max,rolling>", "k_profile_two_fwd<max,mat>"}};
-  return names[mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
+static const char *pt_fwd_name(const mb_profile_twos *p, int mode, bool mat) {
+  static const char *const names[2][2][2] = {{{"k_profile_two_fwd<sum,rolling>", "k_profile_two_fwd<sum,mat>"}, {"k_profile_two_fwd<max,rolling>", "k_profile_two_fwd<max,mat>"}},
+                                             {{"k_profile_two_env_fwd<sum,rolling>", "k_profile_two_env_fwd<sum,mat>"}, {"k_profile_two_env_fwd<max,rolling>", "k_profile_two_env_fwd<max,mat>"}}};
+  return names[p->hasEnv ? 1 : 0][mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
+}
+static const char *pt_name(const mb_profile_twos *p, const char *plain, const char *env) { return p->hasEnv ? env : plain; }
+
+// ---- envelopes of the two-profile pairs (mb_profile_two_env.h, docs/profile_tapes.md "Pairs of profiles under an envelope") ----
+static void pt_env_free(mb_profile_twos *p) {
+  for (void *q : {(void *)p->d_envStart, (void *)p->d_envEnd, (void *)p->d_diagLo, (void *)p->d_diagCnt, (void *)p->d_colStart, (void *)p->d_colEnd,
+                  (void *)p->d_envOff, (void *)p->d_colOff})
+    if (q) (void)hipFree(q);
+  p->d_envStart = p->d_envEnd = p->d_diagLo = p->d_diagCnt = p->d_colStart = p->d_colEnd = nullptr; p->d_envOff = p->d_colOff = nullptr;
+  p->hasEnv = false;
+  p->envBase.clear(); p->diagBase.clear(); p->colBase.clear(); p->envCells.clear(); p->envM.clear();
+}
+
+// The checks and the row tables are those of the pairs (env_add).  If any pair has an envelope every pair gets one, the full
+// envelope where none was given; then the transposed envelope: per input row i the run colStart[i] .. colEnd[i] - 1 of output rows
+// whose interval holds i (a run, because neither bound decreases) and colOff[i], the cells of the input rows before.  A rejected
+// call leaves the pairs without envelopes.
+static int profile_twos_set_envelopes(mb_profile_twos *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
+  pt_env_free(p);
+  if (!envOff) return 0;
+  const long long total = envOff[p->n] - envOff[0];
+  if (!total) return 0;
+  if (!inStart || !inEnd) { set_error("null argument"); return 1; }
+  EnvHost h(p->n);
+  std::vector<long long> colBase((size_t)p->n, 0), cOff;
+  std::vector<int> cSt, cEn, fullSt, fullEn;
+  for (long long k = 0; k < p->n; ++k) {
+    const long long rows = envOff[k + 1] - envOff[k], K = pt_in(p, k), L = pt_rows(p, k);
+    if (rows) {
+      if (env_add(h, k, K, L, rows, inStart + envOff[k], inEnd + envOff[k])) return 1;
+    } else {
+      fullSt.assign((size_t)L + 1, 0); fullEn.assign((size_t)L + 1, (int)K + 1);
+      if (env_add(h, k, K, L, L + 1, fullSt.data(), fullEn.data())) return 1;
+    }
+    const int *st = h.st.data() + h.envBase[(size_t)k], *en = h.en.data() + h.envBase[(size_t)k];
+    const size_t c0 = cSt.size();
+    colBase[(size_t)k] = (long long)c0;
+    cSt.resize(c0 + (size_t)K + 1, 0); cEn.resize(c0 + (size_t)K + 1, 0); cOff.resize(c0 + (size_t)K + 1, 0);
+    for (long long r = L; r >= 0; --r)      // (downwards: the last row written to an input row is its first)
+      for (long long i = st[r]; i < en[r]; ++i) { cSt[c0 + (size_t)i] = (int)r; if (!cEn[c0 + (size_t)i]) cEn[c0 + (size_t)i] = (int)r + 1; }
+    long long cells = 0;
+    for (long long i = 0; i <= K; ++i) { cOff[c0 + (size_t)i] = cells; cells += cEn[c0 + (size_t)i] - cSt[c0 + (size_t)i]; }
+  }
+  if (ensure_init()) return 1;
+  if (!env_upload((void **)&p->d_envStart, h.st.data(), h.st.size() * sizeof(int)) || !env_upload((void **)&p->d_envEnd, h.en.data(), h.en.size() * sizeof(int)) ||
+      !env_upload((void **)&p->d_envOff, h.off.data(), h.off.size() * sizeof(long long)) || !env_upload((void **)&p->d_diagLo, h.lo.data(), h.lo.size() * sizeof(int)) ||
+      !env_upload((void **)&p->d_diagCnt, h.cnt.data(), h.cnt.size() * sizeof(int)) || !env_upload((void **)&p->d_colStart, cSt.data(), cSt.size() * sizeof(int)) ||
+      !env_upload((void **)&p->d_colEnd, cEn.data(), cEn.size() * sizeof(int)) || !env_upload((void **)&p->d_colOff, cOff.data(), cOff.size() * sizeof(long long)) ||
+      !hip_ok(hipStreamSynchronize(g_stream), "H2D pair envelopes")) { pt_env_free(p); return 1; }
+  p->envBase.swap(h.envBase); p->diagBase.swap(h.diagBase); p->colBase.swap(colBase); p->envCells.swap(h.envCells); p->envM.swap(h.M);
+  p->hasEnv = true;
+  return 0;
 }
 
 // Forward (MB_FORWARD) or Viterbi scores without paths (MB_VITERBI); mat: through the materialised lattice
@@ -1011,10 +1118,10 @@ static int two_profile_scores(mb_profile_twos *p, int mode, bool mat, double *lo
     if (mat && !(pool = ws_array<double>(0, pl.cells))) return 1;
     if (pl.ring && !(scratch = (double *)ws_get(1, (size_t)pl.ring * sizeof(double)))) return 1;
     Timed t(tm, 1);
-    return launch_profile_two_fwd(p->m, mode, mat, pl.d.p, (int)(c.p1 - c.p0), pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, scratch, d_ll + c.p0, g_stream);
+    return pt_fwd(p, mode, mat, pl, c.p1 - c.p0, pool, scratch, d_ll + c.p0);
   });
   if (!rc) rc = fetch_loglike(loglike, d_ll, p->n);
-  g_last_kernel = pt_fwd_name(mode, mat);
+  g_last_kernel = pt_fwd_name(p, mode, mat);
   return rc;
 }
 
@@ -1023,7 +1130,7 @@ static long long pt_rowpost_groups(const mb_profile_twos *p, long long p0, long 
   const long long NC = (axis ? p->m->nIn : p->m->nOut) + 1;
   auto lines = [&](long long k) { return axis ? pt_in(p, k) : pt_rows(p, k); };
   return rowpost_groups(p0, p1, lines, [&](long long k) {
-    return profile_pair_rowpost_rows((pt_in(p, k) + 1) * (pt_rows(p, k) + 1), p->m->S, (int)lines(k), (int)NC, tabMax);
+    return profile_pair_rowpost_rows(pt_ncells(p, k), p->m->S, (int)lines(k), (int)NC, tabMax);
   });
 }
 
@@ -1064,7 +1171,21 @@ void mb_profile_twos_destroy(mb_profile_twos *p) {
   if (!p) return;
   if (p->d_logA) (void)hipFree(p->d_logA);
   if (p->d_logB) (void)hipFree(p->d_logB);
+  pt_env_free(p);
   delete p;
+}
+
+int mb_profile_twos_set_envelopes(mb_profile_twos *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
+  ApiGuard guard;
+  if (!p) { set_error("null argument"); return 1; }
+  return profile_twos_set_envelopes(p, envOff, inStart, inEnd);
+}
+
+int64_t mb_profile_twos_cells(const mb_profile_twos *p) {
+  if (!p) return 0;
+  long long c = 0;
+  for (long long k = 0; k < p->n; ++k) c += pt_cells(p, k);
+  return c;
 }
 
 int mb_profile_twos_forward(mb_profile_twos *p, int flags, double *loglike) {
@@ -1100,13 +1221,12 @@ int mb_profile_twos_viterbi(mb_profile_twos *p, double *loglike, int64_t *pathOf
     if (!pool || !d_e || !d_r || !d_i) return 1;
     {
       Timed t(tm, 1);
-      if (pt_fwd_mat(p, MB_VITERBI, pl, np, pool, d_ll + c.p0) ||
-          launch_profile_two_traceback(p->m, pl.d.p, (int)np, p->d_logA, p->d_logB, pool, d_e, d_r, d_i, d_len + c.p0, g_stream)) return 1;
+      if (pt_fwd_mat(p, MB_VITERBI, pl, np, pool, d_ll + c.p0) || pt_traceback(p, pl, np, pool, d_e, d_r, d_i, d_len + c.p0)) return 1;
     }
     return unpack_paths(out, c.p0, np, pl.paths, nullptr, d_len + c.p0, d_e, d_r, d_i);
   });
   if (!rc) rc = fetch_loglike(loglike, d_ll, p->n);
-  g_last_kernel = pt_fwd_name(MB_VITERBI, true);
+  g_last_kernel = pt_fwd_name(p, MB_VITERBI, true);
   return rc;
 }
 
@@ -1133,13 +1253,13 @@ int mb_profile_twos_counts(mb_profile_twos *p, double *counts, double *loglikeSu
       Timed t(tm, 1);
       if (pt_fwd_mat(p, MB_FORWARD, pl, np, fwd, d_ll + c.p0) || pt_bwd(p, pl, np, bwd, d_bll + c.p0)) return 1;
       if (nT && !hip_ok(hipMemsetAsync(d_cc, 0, (size_t)nT * sizeof(double), g_stream), "memset(counts)")) return 1;
-      if (launch_profile_two_counts(p->m, pl.d.p, (int)np, groups, p->d_logA, p->d_logB, fwd, bwd, d_cc, g_stream)) return 1;
+      if (pt_counts(p, pl, np, groups, fwd, bwd, d_cc)) return 1;
     }
     return sum.add(d_cc, g_deterministic);
   });
   std::vector<double> hll((size_t)p->n);
   if (!rc) rc = fetch_loglike(hll.data(), d_ll, p->n);
-  g_last_kernel = "k_profile_two_counts";
+  g_last_kernel = pt_name(p, "k_profile_two_counts", "k_profile_two_env_counts");
   if (rc) return rc;
   sum.finish(hll, counts, loglikeSum, loglike);
   return 0;
@@ -1170,15 +1290,15 @@ int mb_profile_twos_row_posteriors(mb_profile_twos *p, double *postA, double *po
     {
       Timed t(tm, 1);
       if (pt_fwd_mat(p, MB_FORWARD, pl, np, fwd, d_ll + c.p0) || pt_bwd(p, pl, np, bwd, d_bll + c.p0)) return 1;
-      if (postB && launch_profile_two_rowpost(m, 0, pl.d.p, (int)np, (int)groupsB, tabMax, p->d_logA, p->d_logB, fwd, bwd, d_pb, g_stream)) return 1;
-      if (postA && launch_profile_two_rowpost(m, 1, pl.d.p, (int)np, (int)groupsA, tabMax, p->d_logA, p->d_logB, fwd, bwd, d_pa, g_stream)) return 1;
+      if (postB && pt_rowpost(p, 0, pl, np, (int)groupsB, tabMax, fwd, bwd, d_pb)) return 1;
+      if (postA && pt_rowpost(p, 1, pl, np, (int)groupsA, tabMax, fwd, bwd, d_pa)) return 1;
     }
     return hip_ok(hipStreamSynchronize(g_stream), "row posteriors") ? 0 : 1;      // (the next chunk takes the lattices over)
   });
   if (!rc) rc = fetch_posteriors(postA, d_pa, na);
   if (!rc) rc = fetch_posteriors(postB, d_pb, nb);
   if (!rc && loglike) rc = fetch_loglike(loglike, d_ll, p->n);
-  g_last_kernel = "k_profile_two_rowpost";
+  g_last_kernel = pt_name(p, "k_profile_two_rowpost", "k_profile_two_env_rowpost");
   return rc;
 }
 
@@ -1191,27 +1311,53 @@ int mb_profile_twos_set_rows(mb_profile_twos *p, const double *logA, const doubl
   return hip_ok(hipStreamSynchronize(g_stream), "H2D profiles") ? 0 : 1;
 }
 
-int mb_profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, double *cellsOut) {
-  ApiGuard guard;
+static int profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, const int32_t *envStart,
+                            const int32_t *envEnd, double *cellsOut) {
   if (!m || !cellsOut || nRows < 0 || nIn < 0 || (nRows && !logB) || (nIn && !logA)) { set_error("null argument"); return 1; }
   if (!fill_mode_ok(mode)) return 1;
   g_last_ms = 0.0; g_last_launches = 0;
   const int64_t rOff[2] = {0, nRows}, iOff[2] = {0, nIn};
   mb_profile_twos *p = mb_profile_twos_create(m, 1, logA, iOff, logB, rOff);
   if (!p) return 1;
+  const bool env = envStart && envEnd;
+  if (env) {
+    const int64_t eOff[2] = {0, nRows + 1};
+    if (profile_twos_set_envelopes(p, eOff, envStart, envEnd)) { mb_profile_twos_destroy(p); return 1; }
+  }
   std::vector<Chunk> chunks;
   if (!lattice_chunks(1, "pair", [&](long long k) { return pt_cell_bytes(p, k); }, chunks)) { mb_profile_twos_destroy(p); return 1; }
   int rc;
   {
     TwoProfPlan pl;
     rc = two_profile_descs(p, 0, 1, false, pl);
-    if (!rc) rc = fill_one(pl.cells, 0, cellsOut, [&](double *pool, double *, double *d_ll) {
+    std::vector<double> compact(!rc && env ? (size_t)pl.cells : 0);      // under an envelope the lattice comes back compact
+    if (!rc) rc = fill_one(pl.cells, 0, env ? compact.data() : cellsOut, [&](double *pool, double *, double *d_ll) {
       return mode == MB_BACKWARD ? pt_bwd(p, pl, 1, pool, d_ll) : pt_fwd_mat(p, mode, pl, 1, pool, d_ll);
     });
+    if (!rc && env) {      // the compact lattice into the full rectangle, -inf outside the envelope
+      const size_t cellD = 3 * (size_t)m->S;
+      std::fill(cellsOut, cellsOut + (size_t)(nIn + 1) * (size_t)(nRows + 1) * cellD, -INFINITY);
+      size_t at = 0;
+      for (int64_t r = 0; r <= nRows; ++r)
+        for (int64_t i = envStart[r]; i < envEnd[r]; ++i, at += cellD)
+          std::memcpy(cellsOut + ((size_t)i * (size_t)(nRows + 1) + (size_t)r) * cellD, compact.data() + at, cellD * sizeof(double));
+    }
   }
-  g_last_kernel = mode == MB_BACKWARD ? "k_profile_two_bwd" : pt_fwd_name(mode, true);
+  g_last_kernel = mode == MB_BACKWARD ? pt_name(p, "k_profile_two_bwd", "k_profile_two_env_bwd") : pt_fwd_name(p, mode, true);
   mb_profile_twos_destroy(p);
   return rc;
+}
+
+int mb_profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, double *cellsOut) {
+  ApiGuard guard;
+  return profile_two_fill(m, mode, logA, nIn, logB, nRows, nullptr, nullptr, cellsOut);
+}
+
+int mb_profile_two_fill_env(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, const int32_t *envStart,
+                            const int32_t *envEnd, double *cellsOut) {
+  ApiGuard guard;
+  if ((envStart == nullptr) != (envEnd == nullptr)) { set_error("null argument"); return 1; }
+  return profile_two_fill(m, mode, logA, nIn, logB, nRows, envStart, envEnd, cellsOut);
 }
 
 }  // extern "C"

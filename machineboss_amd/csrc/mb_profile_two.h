@@ -4,7 +4,8 @@
 // Lattice of one pair: (K+1) input rows x (L+1) output rows x 3 layers x S states.  Layer 0 (N) = "arrived at (i, r)", layer 1 (W) =
 // "after the machine's output-less moves there", layer 2 (Z) = "committed to wait for the next input row"; materialised cells live
 // at cells[(((i*(L+1)) + r)*3 + layer)*S + q].  A pair is described by a PairProfDesc whose inBase is the first row of its input
-// profile in the batch's input row table (rows of nIn+1 doubles, column 0 = blank) and nIn the number of those rows.
+// profile in the batch's input row table (rows of nIn+1 doubles, column 0 = blank) and nIn the number of those rows.  These are the
+// launchers over full rectangles; mb_profile_two_env.h declares their overloads for pairs under an envelope.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -43,4 +44,11 @@ struct mb_profile_twos {
   std::vector<long long> rowOff, inOff;   // [n+1], rebased to 0: rows of the output / the input profiles
   double *d_logB = nullptr;               // [totalRows * (nOut+1)]
   double *d_logA = nullptr;               // [totalIn * (nIn+1)]
+  // envelopes (mb_profile_twos_set_envelopes, mb_profile_two_env.h): with hasEnv EVERY pair runs the envelope geometry, a pair
+  // that was given none under the full envelope
+  bool hasEnv = false;
+  std::vector<long long> envBase, diagBase, colBase, envCells;   // [n]: first envelope row / diagonal entry / input-row entry, envelope cells
+  std::vector<int> envM;                                         // [n]: the largest cell count of a diagonal
+  int *d_envStart = nullptr, *d_envEnd = nullptr, *d_diagLo = nullptr, *d_diagCnt = nullptr, *d_colStart = nullptr, *d_colEnd = nullptr;
+  long long *d_envOff = nullptr, *d_colOff = nullptr;
 };

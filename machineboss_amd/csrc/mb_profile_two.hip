@@ -21,8 +21,13 @@
 // the finished W -- nothing reads Z before the diagonal's last barrier, so the barriers stay at (K + L + 1) nLevF per pair.  The
 // rolling sweeps keep a ring of three diagonals of three layers, 3 * 3 * (min(K, L) + 1) * S doubles, in LDS when that fits 160 KiB,
 // else in the pair's slice of a global scratch buffer.  Cells are fp64, the sums the exact log-sum-exp.
+//
+// Every kernel is written once over a GEOMETRY, which says which cells exist and where they live: TwoGeom, the whole rectangle, or
+// TwoEnvGeom, the cells of an envelope (docs/profile_tapes.md, "Pairs of profiles under an envelope").  All three layers of a cell
+// outside the envelope are -inf, so a neighbour outside is not read -- the input blank Z[i-1][r] -> Z[i][r] is a move along i like
+// any other and is left out when (i-1, r) is outside; the recurrence, the candidate order and the sums are the same text for both.
 #include "mb_profile_common.h"
-#include "mb_profile_two.h"
+#include "mb_profile_two_env.h"
 
 namespace mb {
 
@@ -30,38 +35,104 @@ size_t profile_two_lds_bytes(int S, long long nIn, long long nRows) {
   const double b = (double)profile_two_ring(S, nIn, nRows) * sizeof(double);
   return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
 }
+size_t profile_two_env_lds_bytes(int S, long long M) {
+  const double b = (double)profile_two_env_ring(S, M) * sizeof(double);
+  return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
+}
 
-// Where the cells of a pair live.  MAT: the materialised lattice of mb_profile_two.h at base, else the ring (diagonal (i + r) mod 3,
+struct NoTwoTables {};      // what the full geometry needs beside a pair's descriptor
+
+// The whole rectangle.  MAT: the materialised lattice of mb_profile_two.h at base, else the ring (diagonal (i + r) mod 3,
 // the cell by its coordinate on the short side of the lattice).
 template <bool MAT>
 struct TwoGeom {
+  using Desc = PairProfDesc;
+  using Tables = NoTwoTables;
+  static constexpr bool ENV = false;
   double *base;
   int S, K, L, M, byI;
-  __device__ __forceinline__ TwoGeom(const PairProfDesc &pd, double *base, int S)
+  __device__ __forceinline__ TwoGeom(const Desc &pd, Tables, double *base, int S)
       : base(base), S(S), K(pd.nIn), L(pd.nRows), M(min(pd.nIn, pd.nRows) + 1), byI(pd.nIn <= pd.nRows) {}
   // the cells of diagonal d: i = ilo .. ilo + nCells - 1
   __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = max(0, d - L); nCells = min(K, d) - ilo + 1; }
+  // asked of neighbours the caller has already bounded to the rectangle
+  static constexpr __device__ __forceinline__ bool inside(int, int) { return true; }
   __device__ __forceinline__ double *at(int i, int r, int layer) const {
     if (MAT) return base + ((((long long)i * (L + 1)) + r) * 3 + layer) * S;
     return base + ((((long long)((i + r) % 3) * M) + (byI ? i : r)) * 3 + layer) * S;
   }
   __device__ __forceinline__ long long cells() const { return (long long)(K + 1) * (L + 1); }
   __device__ __forceinline__ void cell(long long c, int &i, int &r) const { i = (int)(c / (L + 1)); r = (int)(c - (long long)i * (L + 1)); }
+  // row posteriors: the cells counted line by line (AXIS 0: output row r holds lineFirst(r) .. lineFirst(r + 1) - 1 by ascending i;
+  // AXIS 1: input row i by ascending r) -- over the rectangle both orders are a division
+  template <int AXIS> __device__ __forceinline__ long long lineFirst(int l) const { return (long long)l * ((AXIS ? L : K) + 1); }
+  template <int AXIS> __device__ __forceinline__ void lineCell(long long c, int &i, int &r) const {
+    const int per = (AXIS ? L : K) + 1, line = (int)(c / per), j = (int)(c - (long long)line * per);
+    i = AXIS ? line : j; r = AXIS ? j : line;
+  }
+};
+
+// The cells of an envelope (mb_profile_two_env.h).  Its bounds never decrease from row to row, so the cells of diagonal d are the
+// run i = diagLo[d] .. diagLo[d] + diagCnt[d] - 1 (the host uploads both).  MAT: the compact three-layer lattice at base, else the
+// ring (diagonal (i + r) mod 3, the cell at i mod M, M the largest diagCnt of the pair: the cells of a diagonal have consecutive i
+// and number at most M, so no two share a slot).
+template <bool MAT>
+struct TwoEnvGeom {
+  using Desc = TwoEnvDesc;
+  using Tables = TwoEnvTables;
+  static constexpr bool ENV = true;
+  double *base;
+  const int *st, *en;         // the pair's envelope rows
+  const long long *off;       // compact index of the first cell of each row
+  const int *dLo, *dCnt;
+  const int *cSt;             // the transposed envelope: first output row of each input row, and
+  const long long *cOff;      // the cells of the input rows before it
+  long long nCells;
+  int S, K, L, M;
+  __device__ __forceinline__ TwoEnvGeom(const Desc &pd, const Tables &t, double *base, int S)
+      : base(base), st(t.envStart + pd.envBase), en(t.envEnd + pd.envBase), off(t.envOff + pd.envBase),
+        dLo(t.diagLo + pd.diagBase), dCnt(t.diagCnt + pd.diagBase), cSt(t.colStart + pd.colBase), cOff(t.colOff + pd.colBase),
+        nCells(pd.nCells), S(S), K(pd.nIn), L(pd.nRows), M(pd.M) {}
+  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = dLo[d]; nCells = dCnt[d]; }
+  // r in -1..L+1, i in -1..K+1
+  __device__ __forceinline__ bool inside(int i, int r) const { return r >= 0 && r <= L && i >= st[r] && i < en[r]; }
+  __device__ __forceinline__ double *at(int i, int r, int layer) const {
+    if (MAT) return base + ((off[r] + (i - st[r])) * 3 + layer) * S;
+    return base + ((((long long)((i + r) % 3) * M) + (i % M)) * 3 + layer) * S;
+  }
+  __device__ __forceinline__ long long cells() const { return nCells; }
+  // the last entry of o[0..n] that is <= c: the lines behind it start past the cell
+  static __device__ __forceinline__ int lastLE(const long long *o, int n, long long c) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (o[mid] <= c) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+  }
+  __device__ __forceinline__ void cell(long long c, int &i, int &r) const { r = lastLE(off, L, c); i = st[r] + (int)(c - off[r]); }
+  // (AXIS 0: the compact index already counts row by row; AXIS 1: column by column through the transposed envelope)
+  template <int AXIS> __device__ __forceinline__ long long lineFirst(int l) const { return AXIS ? cOff[l] : off[l]; }
+  template <int AXIS> __device__ __forceinline__ void lineCell(long long c, int &i, int &r) const {
+    if (AXIS) { i = lastLE(cOff, K, c); r = cSt[i] + (int)(c - cOff[i]); }
+    else cell(c, i, r);
+  }
 };
 
 // Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every cell into pool, else rolling.  Viterbi keeps the FIRST
 // maximum: N takes the output blank first, then the match edges, then the output-only edges; W takes N (no move) first, then the
 // input-only edges, then the silent edges; Z takes W first, then the input blank; edges of a kind in `incoming` order (input token
 // ascending, then output token) -- the order k_profile_two_traceback re-enumerates.
-template <int MODE, bool MAT>
-__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_fwd(DevMachine m, const PairProfDesc *__restrict__ descs, const double *__restrict__ logA,
-                                                                   const double *__restrict__ logB, double *pool, double *scratch, double *__restrict__ loglike) {
+template <int MODE, bool MAT, template <bool> class Geom>
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_fwd(DevMachine m, const typename Geom<MAT>::Desc *__restrict__ descs, typename Geom<MAT>::Tables t,
+                                                                   const double *__restrict__ logA, const double *__restrict__ logB, double *pool, double *scratch,
+                                                                   double *__restrict__ loglike) {
   extern __shared__ double pt_sh[];
-  const PairProfDesc pd = descs[blockIdx.x];
+  const auto pd = descs[blockIdx.x];
   const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, K = pd.nIn, L = pd.nRows;
   const double *A = logA + pd.inBase * CA;
   const double *B = logB + pd.rowBase * C;
-  const TwoGeom<MAT> lat(pd, MAT ? pool + pd.cellBase : (pd.ringBase < 0 ? pt_sh : scratch + pd.ringBase), S);
+  const Geom<MAT> lat(pd, t, MAT ? pool + pd.cellBase : (pd.ringBase < 0 ? pt_sh : scratch + pd.ringBase), S);
   for (int d = 0; d <= K + L; ++d) {
     int ilo, nCells;
     lat.diag(d, ilo, nCells);
@@ -72,8 +143,9 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_fwd(DevMachine m,
       double acc;
       if (r > 0) {
         const double *Br = B + (long long)(r - 1) * C;
-        acc = lat.at(i, r - 1, 0)[q] + Br[0];
-        if (i > 0) {
+        const bool up = lat.inside(i, r - 1);
+        acc = up ? lat.at(i, r - 1, 0)[q] + Br[0] : -INFINITY;
+        if (i > 0 && lat.inside(i - 1, r - 1)) {
           const double *Zd = lat.at(i - 1, r - 1, 2);
           for (int a = 1; a <= m.nIn; ++a) {
             const int row = q * KK + a * C;
@@ -83,15 +155,17 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_fwd(DevMachine m,
               acc = red<MODE>(acc, ((Zd[m.inSrc[e]] + m.inW[e]) + wa) + Br[m.eOutTok[m.inEid[e]]]);
           }
         }
-        const double *Wu = lat.at(i, r - 1, 1);
-        const int e1 = m.inOff[q * KK + C];
-        for (int e = m.inOff[q * KK + 1]; e < e1; ++e)
-          acc = red<MODE>(acc, (Wu[m.inSrc[e]] + m.inW[e]) + Br[m.eOutTok[m.inEid[e]]]);
+        if (up) {
+          const double *Wu = lat.at(i, r - 1, 1);
+          const int e1 = m.inOff[q * KK + C];
+          for (int e = m.inOff[q * KK + 1]; e < e1; ++e)
+            acc = red<MODE>(acc, (Wu[m.inSrc[e]] + m.inW[e]) + Br[m.eOutTok[m.inEid[e]]]);
+        }
       } else {
         acc = (i == 0 && q == 0) ? 0.0 : -INFINITY;
       }
       lat.at(i, r, 0)[q] = acc;
-      if (i > 0) {
+      if (i > 0 && lat.inside(i - 1, r)) {
         const double *Zl = lat.at(i - 1, r, 2);
         for (int a = 1; a <= m.nIn; ++a) {
           const int row = q * KK + a * C;
@@ -121,12 +195,12 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_fwd(DevMachine m,
           acc = red<MODE>(acc, Wc[s] + m.inW[e]);
         }
         Wc[q] = acc;
-        lat.at(i, r, 2)[q] = i > 0 ? red<MODE>(acc, lat.at(i - 1, r, 2)[q] + A[(long long)(i - 1) * CA]) : acc;
+        lat.at(i, r, 2)[q] = (i > 0 && lat.inside(i - 1, r)) ? red<MODE>(acc, lat.at(i - 1, r, 2)[q] + A[(long long)(i - 1) * CA]) : acc;
       }
       __syncthreads();
     }
   }
-  if (threadIdx.x == 0) loglike[blockIdx.x] = lat.at(K, L, 2)[S - 1];
+  if (threadIdx.x == 0) loglike[blockIdx.x] = lat.at(K, L, 2)[S - 1];      // (an envelope is connected: (0, 0) and (K, L) are inside)
 }
 
 // Materialised Backward sweep, layer 0 = NB ("from the arrived stage"), 1 = WB ("from the waiting stage"), 2 = ZB ("from the
@@ -140,13 +214,16 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_fwd(DevMachine m,
 //                 (+) sum_{silent t: s->d, s < d}      w_t + WB[i][r][d]
 //   NB[i][r][s] = WB[i][r][s] (+) (B[r][0] + NB[i][r+1][s])   (r < L);   loglike = NB[0][0][0]
 // Anti-diagonals from K + L down.  A state's WB is final once its backward level has run; the item that finishes it writes its NB.
-__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_bwd(DevMachine m, const PairProfDesc *__restrict__ descs, const double *__restrict__ logA,
-                                                                   const double *__restrict__ logB, double *pool, double *__restrict__ loglike) {
-  const PairProfDesc pd = descs[blockIdx.x];
+// A successor cell outside the geometry contributes nothing.
+template <template <bool> class Geom>
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_bwd(DevMachine m, const typename Geom<true>::Desc *__restrict__ descs, typename Geom<true>::Tables t,
+                                                                   const double *__restrict__ logA, const double *__restrict__ logB, double *pool,
+                                                                   double *__restrict__ loglike) {
+  const auto pd = descs[blockIdx.x];
   const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, K = pd.nIn, L = pd.nRows;
   const double *A = logA + pd.inBase * CA;
   const double *B = logB + pd.rowBase * C;
-  const TwoGeom<true> lat(pd, pool + pd.cellBase, S);
+  const Geom<true> lat(pd, t, pool + pd.cellBase, S);
   for (int d = K + L; d >= 0; --d) {
     int ilo, nCells;
     lat.diag(d, ilo, nCells);
@@ -155,10 +232,11 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_bwd(DevMachine m,
       const int c = it / S, s = it - c * S, i = ilo + c, r = d - i;
       const double *Ai = A + (long long)i * CA;      // read when i < K
       const double *Br = B + (long long)r * C;       // read when r < L
+      const bool right = i < K && lat.inside(i + 1, r), down = r < L && lat.inside(i, r + 1);
       double v = (i == K && r == L && s == S - 1) ? 0.0 : -INFINITY;
       if (i < K) {
-        v = lse2_exact(v, Ai[0] + lat.at(i + 1, r, 2)[s]);
-        if (r < L) {
+        if (right) v = lse2_exact(v, Ai[0] + lat.at(i + 1, r, 2)[s]);
+        if (r < L && lat.inside(i + 1, r + 1)) {
           const double *Nd = lat.at(i + 1, r + 1, 0);
           for (int a = 1; a <= m.nIn; ++a) {
             const int row = s * KK + a * C;
@@ -168,23 +246,25 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_bwd(DevMachine m,
               v = lse2_exact(v, ((m.outW[e] + wa) + Br[m.eOutTok[m.outEid[e]]]) + Nd[m.outDst[e]]);
           }
         }
-        const double *Wl = lat.at(i + 1, r, 1);
-        for (int a = 1; a <= m.nIn; ++a) {
-          const int row = s * KK + a * C;
-          const double wa = Ai[a];
-          const int e1 = m.outOff[row + 1];
-          for (int e = m.outOff[row]; e < e1; ++e) v = lse2_exact(v, (m.outW[e] + wa) + Wl[m.outDst[e]]);
+        if (right) {
+          const double *Wl = lat.at(i + 1, r, 1);
+          for (int a = 1; a <= m.nIn; ++a) {
+            const int row = s * KK + a * C;
+            const double wa = Ai[a];
+            const int e1 = m.outOff[row + 1];
+            for (int e = m.outOff[row]; e < e1; ++e) v = lse2_exact(v, (m.outW[e] + wa) + Wl[m.outDst[e]]);
+          }
         }
       }
       lat.at(i, r, 2)[s] = v;
-      if (r < L) {
+      if (down) {
         const double *Nu = lat.at(i, r + 1, 0);
         const int e1 = m.outOff[s * KK + C];
         for (int e = m.outOff[s * KK + 1]; e < e1; ++e)
           v = lse2_exact(v, (m.outW[e] + Br[m.eOutTok[m.outEid[e]]]) + Nu[m.outDst[e]]);
       }
       lat.at(i, r, 1)[s] = v;
-      lat.at(i, r, 0)[s] = r < L ? lse2_exact(v, Br[0] + lat.at(i, r + 1, 0)[s]) : v;
+      lat.at(i, r, 0)[s] = down ? lse2_exact(v, Br[0] + lat.at(i, r + 1, 0)[s]) : v;
     }
     __syncthreads();
     for (int lev = 1; lev < m.nLevB; ++lev) {
@@ -201,7 +281,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_bwd(DevMachine m,
           v = lse2_exact(v, Wc[t] + m.outW[e]);
         }
         Wc[s] = v;
-        lat.at(i, r, 0)[s] = r < L ? lse2_exact(v, B[(long long)r * C] + lat.at(i, r + 1, 0)[s]) : v;
+        lat.at(i, r, 0)[s] = (r < L && lat.inside(i, r + 1)) ? lse2_exact(v, B[(long long)r * C] + lat.at(i, r + 1, 0)[s]) : v;
       }
       __syncthreads();
     }
@@ -212,18 +292,20 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_bwd(DevMachine m,
 // Posterior counts.  With both lattices in memory every (cell, edge) term is independent:
 //   count[t] += exp(F[i][r][s] - LL + term_t), term_t the edge's summand of ZB (read from Z_F) or WB (read from W_F) above,
 // so the sweep is a flat grid over (pair, group of the pair, (cell, state)), accumulated by CountsAcc (mb_profile_common.h).  A pair
-// whose likelihood is -inf adds nothing; the blanks of either tape are not edges.
-__global__ __launch_bounds__(256) void k_profile_two_counts(DevMachine m, const PairProfDesc *__restrict__ descs, int groupsPerPair, const double *__restrict__ logA,
-                                                            const double *__restrict__ logB, const double *__restrict__ fwdPool,
+// whose likelihood is -inf adds nothing; the blanks of either tape are not edges.  The cells of an envelope are counted through its
+// compact index (a cell finds its row by bisection in off); a term whose destination lies outside is left out.
+template <template <bool> class Geom>
+__global__ __launch_bounds__(256) void k_profile_two_counts(DevMachine m, const typename Geom<true>::Desc *__restrict__ descs, typename Geom<true>::Tables t, int groupsPerPair,
+                                                            const double *__restrict__ logA, const double *__restrict__ logB, const double *__restrict__ fwdPool,
                                                             const double *__restrict__ bwdPool, long long nTrans, double *__restrict__ counts, int det) {
   __shared__ double lcount[COUNTS_LDS_MAX];
   const CountsAcc acc(lcount, counts, nTrans, det);
   const int k = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
-  const PairProfDesc pd = descs[k];
+  const auto pd = descs[k];
   const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, K = pd.nIn, L = pd.nRows;
   const double *A = logA + pd.inBase * CA;
   const double *B = logB + pd.rowBase * C;
-  const TwoGeom<true> F(pd, const_cast<double *>(fwdPool) + pd.cellBase, S), Bk(pd, const_cast<double *>(bwdPool) + pd.cellBase, S);
+  const Geom<true> F(pd, t, const_cast<double *>(fwdPool) + pd.cellBase, S), Bk(pd, t, const_cast<double *>(bwdPool) + pd.cellBase, S);
   const double LL = F.at(K, L, 2)[S - 1];
   if (LL > -INFINITY) {
     const long long nItems = F.cells() * S;
@@ -237,22 +319,24 @@ __global__ __launch_bounds__(256) void k_profile_two_counts(DevMachine m, const 
       const double *Ai = A + (long long)i * CA;
       const double *Br = B + (long long)r * C;
       if (i < K) {
-        const double *Wl = Bk.at(i + 1, r, 1);
+        const bool right = Bk.inside(i + 1, r), across = r < L && Bk.inside(i + 1, r + 1);
+        const double *Wl = right ? Bk.at(i + 1, r, 1) : nullptr, *Nd = across ? Bk.at(i + 1, r + 1, 0) : nullptr;
         for (int a = 1; a <= m.nIn; ++a) {
           const int row = s * KK + a * C;
           const double wa = Ai[a];
-          if (r < L) {
-            const double *Nd = Bk.at(i + 1, r + 1, 0);
+          if (across) {
             const int e1 = m.outOff[row + C];
             for (int e = m.outOff[row + 1]; e < e1; ++e)
               acc.add(m.outEid[e], exp(z + (((m.outW[e] + wa) + Br[m.eOutTok[m.outEid[e]]]) + Nd[m.outDst[e]])));
           }
-          const int e1 = m.outOff[row + 1];
-          for (int e = m.outOff[row]; e < e1; ++e) acc.add(m.outEid[e], exp(z + ((m.outW[e] + wa) + Wl[m.outDst[e]])));
+          if (right) {
+            const int e1 = m.outOff[row + 1];
+            for (int e = m.outOff[row]; e < e1; ++e) acc.add(m.outEid[e], exp(z + ((m.outW[e] + wa) + Wl[m.outDst[e]])));
+          }
         }
       }
       if (!(f > -INFINITY)) continue;
-      if (r < L) {
+      if (r < L && Bk.inside(i, r + 1)) {
         const double *Nu = Bk.at(i, r + 1, 0);
         const int e1 = m.outOff[s * KK + C];
         for (int e = m.outOff[s * KK + 1]; e < e1; ++e)
@@ -286,20 +370,24 @@ __global__ __launch_bounds__(256) void k_profile_two_counts(DevMachine m, const 
 // workgroup, so there is no global atomic and nothing to clear beforehand.  A line of more than tabMax columns is summed in its
 // global bins instead, cleared by the workgroup that owns it.  A pair whose likelihood is -inf gets zeros.  det: post holds 64-bit
 // fixed point at 2^-36.
-template <int AXIS>
-__global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_rowpost(DevMachine m, const PairProfDesc *__restrict__ descs, int groupsPerPair,
-                                                                         const double *__restrict__ logA, const double *__restrict__ logB,
+// Under an envelope the lines are those of the geometry (lineFirst / lineCell): on axis 0 the compact index already counts row by
+// row; on axis 1 the lines are COLUMNS of the envelope -- by monotonicity the cells of input row i are the run r = colStart[i] ..
+// colEnd[i] - 1, an item finds its column by bisection in colOff and its cell through at().  A term whose destination lies outside
+// is left out.
+template <int AXIS, template <bool> class Geom>
+__global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_rowpost(DevMachine m, const typename Geom<true>::Desc *__restrict__ descs, typename Geom<true>::Tables t,
+                                                                         int groupsPerPair, const double *__restrict__ logA, const double *__restrict__ logB,
                                                                          const double *__restrict__ fwdPool, const double *__restrict__ bwdPool,
                                                                          double *post, int tabMax, int det) {
   __shared__ double ltab[ROWPOST_LDS_MAX];
   const int k = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
-  const PairProfDesc pd = descs[k];
+  const auto pd = descs[k];
   const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, K = pd.nIn, L = pd.nRows;
-  const int NL = AXIS ? K : L, NC = AXIS ? CA : C, per = (AXIS ? L : K) + 1;      // lines, bins of a line, cells of a line
+  const int NL = AXIS ? K : L, NC = AXIS ? CA : C;      // lines, bins of a line
   if (NL == 0) return;
   const double *A = logA + pd.inBase * CA;
   const double *B = logB + pd.rowBase * C;
-  const TwoGeom<true> F(pd, const_cast<double *>(fwdPool) + pd.cellBase, S), Bk(pd, const_cast<double *>(bwdPool) + pd.cellBase, S);
+  const Geom<true> F(pd, t, const_cast<double *>(fwdPool) + pd.cellBase, S), Bk(pd, t, const_cast<double *>(bwdPool) + pd.cellBase, S);
   const double LL = F.at(K, L, 2)[S - 1];
   const int R = profile_pair_rowpost_rows(F.cells(), S, NL, NC, tabMax);
   const bool useLds = NC <= tabMax;
@@ -312,30 +400,31 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_rowpost(DevMach
     if (!useLds) __threadfence();
     __syncthreads();
     if (LL > -INFINITY) {
-      const long long nItems = (long long)(l1 - l0) * per * S;
+      const long long c0 = F.template lineFirst<AXIS>(l0), nItems = (F.template lineFirst<AXIS>(l1) - c0) * S;
       for (long long base = threadIdx.x - lane; base < nItems; base += blockDim.x) {      // (a wavefront stays whole in here)
         const long long idx = base + lane;
         const bool valid = idx < nItems;
-        int line = l0, j = 0, s = 0;
+        int i = AXIS ? l0 : 0, r = AXIS ? 0 : l0, s = 0;
         if (valid) {
           const long long cell = idx / S;
           s = (int)(idx - cell * S);
-          line = l0 + (int)(cell / per);
-          j = (int)(cell - (long long)(line - l0) * per);
+          F.template lineCell<AXIS>(c0 + cell, i, r);
         }
-        const int i = AXIS ? line : j, r = AXIS ? j : line;
+        const int line = AXIS ? i : r;
         const double z = valid ? F.at(i, r, 2)[s] - LL : -INFINITY;
         const bool whole = __all(valid && line == __shfl(line, 0));
-        const bool diag = valid && i < K && r < L;      // (the line's own coordinate is inside: r < L on axis 0, i < K on axis 1)
+        // (the line's own coordinate is inside: r < L on axis 0, i < K on axis 1)
+        const bool diag = valid && i < K && r < L && Bk.inside(i + 1, r + 1);
         const double *Ai = A + (long long)i * CA;        // read when i < K
         const double *Br = B + (long long)r * C;         // read when r < L
         const double *Nd = diag ? Bk.at(i + 1, r + 1, 0) : nullptr;
         const int sRow = s * KK, bin0 = (line - l0) * NC;
         if (AXIS == 0) {
           const double f = valid ? F.at(i, r, 1)[s] - LL : -INFINITY, n = valid ? F.at(i, r, 0)[s] - LL : -INFINITY;
-          const double *Nu = Bk.at(i, r + 1, 0);
-          const bool zLive = diag && z > -INFINITY, fLive = f > -INFINITY;
-          rowpost_add(tab, bin0, n > -INFINITY ? exp(n + (Br[0] + Nu[s])) : 0.0, whole, lane, det);
+          const bool up = valid && Bk.inside(i, r + 1);
+          const double *Nu = up ? Bk.at(i, r + 1, 0) : nullptr;
+          const bool zLive = diag && z > -INFINITY, fLive = up && f > -INFINITY;
+          rowpost_add(tab, bin0, (up && n > -INFINITY) ? exp(n + (Br[0] + Nu[s])) : 0.0, whole, lane, det);
           for (int o = 1; o < C; ++o) {      // the out-edges of (s, a) that write o are one CSR row
             double v = 0.0;
             const double po = Br[o];
@@ -353,19 +442,24 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_rowpost(DevMach
             rowpost_add(tab, bin0 + o, v, whole, lane, det);
           }
         } else {
-          const double *Zl = Bk.at(i + 1, r, 2), *Wl = Bk.at(i + 1, r, 1);
+          const bool right = valid && Bk.inside(i + 1, r);
+          const double *Zl = right ? Bk.at(i + 1, r, 2) : nullptr, *Wl = right ? Bk.at(i + 1, r, 1) : nullptr;
           const bool zLive = z > -INFINITY;
-          rowpost_add(tab, bin0, zLive ? exp(z + (Ai[0] + Zl[s])) : 0.0, whole, lane, det);
+          rowpost_add(tab, bin0, (right && zLive) ? exp(z + (Ai[0] + Zl[s])) : 0.0, whole, lane, det);
           for (int a = 1; a < CA; ++a) {      // the out-edges of s that read a: the input-only row, then the rows of the output tokens
             double v = 0.0;
             if (zLive) {
               const int row = sRow + a * C;
               const double wa = Ai[a];
-              int e = m.outOff[row];
-              for (const int e1 = m.outOff[row + 1]; e < e1; ++e) v += exp(z + ((m.outW[e] + wa) + Wl[m.outDst[e]]));
-              if (diag)
-                for (const int e1 = m.outOff[row + C]; e < e1; ++e)
+              if (right) {
+                const int e1 = m.outOff[row + 1];
+                for (int e = m.outOff[row]; e < e1; ++e) v += exp(z + ((m.outW[e] + wa) + Wl[m.outDst[e]]));
+              }
+              if (diag) {
+                const int e1 = m.outOff[row + C];
+                for (int e = m.outOff[row + 1]; e < e1; ++e)
                   v += exp(z + (((m.outW[e] + wa) + Br[m.eOutTok[m.outEid[e]]]) + Nd[m.outDst[e]]));
+              }
             }
             rowpost_add(tab, bin0 + a, v, whole, lane, det);
           }
@@ -385,16 +479,18 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_rowpost(DevMach
 // (profile_pair_path_bound entries) with both coordinates at which each fired: an emitting edge the output row it consumed, an
 // output-less edge the number of output rows consumed before it, and the same on the input tape.  len = -1: no finite path, -2: the
 // slot was too small, -3: no candidate matched (a corrupt matrix).
-__global__ void k_profile_two_traceback(DevMachine m, const PairProfDesc *__restrict__ descs, int n, const double *__restrict__ logA,
-                                        const double *__restrict__ logB, const double *__restrict__ pool, uint32_t *edges, int32_t *rows,
-                                        int32_t *inRows, long long *len) {
+// A candidate whose source cell lies outside the geometry is left out: it is -inf, and the cells on the path are finite.
+template <template <bool> class Geom>
+__global__ void k_profile_two_traceback(DevMachine m, const typename Geom<true>::Desc *__restrict__ descs, typename Geom<true>::Tables t, int n,
+                                        const double *__restrict__ logA, const double *__restrict__ logB, const double *__restrict__ pool, uint32_t *edges,
+                                        int32_t *rows, int32_t *inRows, long long *len) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
-  const PairProfDesc pd = descs[k];
+  const auto pd = descs[k];
   const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, K = pd.nIn, L = pd.nRows;
   const double *A = logA + pd.inBase * CA;
   const double *B = logB + pd.rowBase * C;
-  const TwoGeom<true> lat(pd, const_cast<double *>(pool) + pd.cellBase, S);
+  const Geom<true> lat(pd, t, const_cast<double *>(pool) + pd.cellBase, S);
   uint32_t *pe = edges + pd.pathBase;
   int32_t *pr = rows + pd.pathBase, *pi = inRows + pd.pathBase;
   int i = K, r = L, q = S - 1, layer = 2;
@@ -407,14 +503,14 @@ __global__ void k_profile_two_traceback(DevMachine m, const PairProfDesc *__rest
     if (layer == 2) {
       const double cur = lat.at(i, r, 2)[q];
       if (lat.at(i, r, 1)[q] == cur) { layer = 1; continue; }
-      if (i > 0 && lat.at(i - 1, r, 2)[q] + Ai[0] == cur) { --i; continue; }
+      if (i > 0 && lat.inside(i - 1, r) && lat.at(i - 1, r, 2)[q] + Ai[0] == cur) { --i; continue; }
       len[k] = -3; return;
     } else if (layer == 1) {
       const double *W = lat.at(i, r, 1);
       const double cur = W[q];
       if (lat.at(i, r, 0)[q] == cur) { layer = 0; continue; }
       int ni = i, nl = 1;
-      if (i > 0) {
+      if (i > 0 && lat.inside(i - 1, r)) {
         const double *Zl = lat.at(i - 1, r, 2);
         for (int a = 1; a <= m.nIn && found < 0; ++a) {
           const int row = q * KK + a * C;
@@ -439,9 +535,10 @@ __global__ void k_profile_two_traceback(DevMachine m, const PairProfDesc *__rest
       if (r == 0) { if (i != 0 || q != 0) { len[k] = -3; return; } break; }
       const double *Br = B + (long long)(r - 1) * C;
       const double cur = lat.at(i, r, 0)[q];
-      if (lat.at(i, r - 1, 0)[q] + Br[0] == cur) { --r; continue; }
+      const bool up = lat.inside(i, r - 1);
+      if (up && lat.at(i, r - 1, 0)[q] + Br[0] == cur) { --r; continue; }
       int ni = i, nl = 1;
-      if (i > 0) {
+      if (i > 0 && lat.inside(i - 1, r - 1)) {
         const double *Zd = lat.at(i - 1, r - 1, 2);
         for (int a = 1; a <= m.nIn && found < 0; ++a) {
           const int row = q * KK + a * C;
@@ -451,7 +548,7 @@ __global__ void k_profile_two_traceback(DevMachine m, const PairProfDesc *__rest
             if (((Zd[m.inSrc[e]] + m.inW[e]) + wa) + Br[m.eOutTok[m.inEid[e]]] == cur) { found = (int)m.inSrc[e]; ni = i - 1; nl = 2; break; }
         }
       }
-      if (found < 0) {
+      if (found < 0 && up) {
         const double *Wu = lat.at(i, r - 1, 1);
         e = m.inOff[q * KK + 1];
         for (const int e1 = m.inOff[q * KK + C]; e < e1; ++e)
@@ -472,58 +569,105 @@ __global__ void k_profile_two_traceback(DevMachine m, const PairProfDesc *__rest
   len[k] = cnt;
 }
 
-int launch_profile_two_fwd(const mb_machine *m, int mode, bool mat, const PairProfDesc *d, int n, size_t lds, long long maxItems, const double *logA,
-                           const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st) {
+// The launchers: each sweep once over a geometry, and the two overloads of the headers that name one.
+template <template <bool> class Geom>
+static int two_fwd(const mb_machine *m, int mode, bool mat, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, size_t lds, long long maxItems,
+                   const double *logA, const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  constexpr bool ENV = Geom<true>::ENV;
   if (n <= 0) return 0;
   if (mat) lds = 0;
   static size_t ldsAllowed = 64 * 1024;      // beyond the default the kernels must be told; asked for once, and only when a ring needs it
   if (lds > ldsAllowed) {
-    const char *what = "k_profile_two_fwd: raising the LDS limit";
-    if (!hip_ok(hipFuncSetAttribute((const void *)&k_profile_two_fwd<MB_FORWARD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what) ||
-        !hip_ok(hipFuncSetAttribute((const void *)&k_profile_two_fwd<MB_VITERBI, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what)) return 1;
+    const char *what = ENV ? "k_profile_two_env_fwd: raising the LDS limit" : "k_profile_two_fwd: raising the LDS limit";
+    if (!hip_ok(hipFuncSetAttribute((const void *)&k_profile_two_fwd<MB_FORWARD, false, Geom>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what) ||
+        !hip_ok(hipFuncSetAttribute((const void *)&k_profile_two_fwd<MB_VITERBI, false, Geom>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what)) return 1;
     ldsAllowed = SWEEP_LDS_MAX;
   }
   const dim3 g(n), b(sweep_threads(maxItems));
   if (mode == MB_VITERBI) {
-    if (mat) k_profile_two_fwd<MB_VITERBI, true><<<g, b, 0, st>>>(m->dev, d, logA, logB, pool, scratch, loglike);
-    else k_profile_two_fwd<MB_VITERBI, false><<<g, b, lds, st>>>(m->dev, d, logA, logB, pool, scratch, loglike);
+    if (mat) k_profile_two_fwd<MB_VITERBI, true, Geom><<<g, b, 0, st>>>(m->dev, d, t, logA, logB, pool, scratch, loglike);
+    else k_profile_two_fwd<MB_VITERBI, false, Geom><<<g, b, lds, st>>>(m->dev, d, t, logA, logB, pool, scratch, loglike);
   } else {
-    if (mat) k_profile_two_fwd<MB_FORWARD, true><<<g, b, 0, st>>>(m->dev, d, logA, logB, pool, scratch, loglike);
-    else k_profile_two_fwd<MB_FORWARD, false><<<g, b, lds, st>>>(m->dev, d, logA, logB, pool, scratch, loglike);
+    if (mat) k_profile_two_fwd<MB_FORWARD, true, Geom><<<g, b, 0, st>>>(m->dev, d, t, logA, logB, pool, scratch, loglike);
+    else k_profile_two_fwd<MB_FORWARD, false, Geom><<<g, b, lds, st>>>(m->dev, d, t, logA, logB, pool, scratch, loglike);
   }
-  return hip_ok(hipGetLastError(), "k_profile_two_fwd") ? 0 : 1;
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_two_env_fwd" : "k_profile_two_fwd") ? 0 : 1;
+}
+int launch_profile_two_fwd(const mb_machine *m, int mode, bool mat, const PairProfDesc *d, int n, size_t lds, long long maxItems, const double *logA,
+                           const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  return two_fwd<TwoGeom>(m, mode, mat, d, {}, n, lds, maxItems, logA, logB, pool, scratch, loglike, st);
+}
+int launch_profile_two_fwd(const mb_machine *m, int mode, bool mat, const TwoEnvDesc *d, const TwoEnvTables &t, int n, size_t lds, long long maxItems,
+                           const double *logA, const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  return two_fwd<TwoEnvGeom>(m, mode, mat, d, t, n, lds, maxItems, logA, logB, pool, scratch, loglike, st);
 }
 
+template <template <bool> class Geom>
+static int two_bwd(const mb_machine *m, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, long long maxItems, const double *logA,
+                   const double *logB, double *pool, double *loglike, hipStream_t st) {
+  if (n <= 0) return 0;
+  k_profile_two_bwd<Geom><<<dim3(n), dim3(sweep_threads(maxItems)), 0, st>>>(m->dev, d, t, logA, logB, pool, loglike);
+  return hip_ok(hipGetLastError(), Geom<true>::ENV ? "k_profile_two_env_bwd" : "k_profile_two_bwd") ? 0 : 1;
+}
 int launch_profile_two_bwd(const mb_machine *m, const PairProfDesc *d, int n, long long maxItems, const double *logA, const double *logB, double *pool,
                            double *loglike, hipStream_t st) {
-  if (n <= 0) return 0;
-  k_profile_two_bwd<<<dim3(n), dim3(sweep_threads(maxItems)), 0, st>>>(m->dev, d, logA, logB, pool, loglike);
-  return hip_ok(hipGetLastError(), "k_profile_two_bwd") ? 0 : 1;
+  return two_bwd<TwoGeom>(m, d, {}, n, maxItems, logA, logB, pool, loglike, st);
+}
+int launch_profile_two_bwd(const mb_machine *m, const TwoEnvDesc *d, const TwoEnvTables &t, int n, long long maxItems, const double *logA, const double *logB,
+                           double *pool, double *loglike, hipStream_t st) {
+  return two_bwd<TwoEnvGeom>(m, d, t, n, maxItems, logA, logB, pool, loglike, st);
 }
 
+template <template <bool> class Geom>
+static int two_counts(const mb_machine *m, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, int groupsPerPair, const double *logA,
+                      const double *logB, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
+  if (n <= 0 || m->nTrans <= 0) return 0;
+  k_profile_two_counts<Geom><<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(m->dev, d, t, groupsPerPair, logA, logB, fwdPool, bwdPool, m->nTrans, counts,
+                                                                                                g_deterministic ? 1 : 0);
+  return hip_ok(hipGetLastError(), Geom<true>::ENV ? "k_profile_two_env_counts" : "k_profile_two_counts") ? 0 : 1;
+}
 int launch_profile_two_counts(const mb_machine *m, const PairProfDesc *d, int n, int groupsPerPair, const double *logA, const double *logB,
                               const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
-  if (n <= 0 || m->nTrans <= 0) return 0;
-  k_profile_two_counts<<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(m->dev, d, groupsPerPair, logA, logB, fwdPool, bwdPool, m->nTrans, counts,
-                                                                                         g_deterministic ? 1 : 0);
-  return hip_ok(hipGetLastError(), "k_profile_two_counts") ? 0 : 1;
+  return two_counts<TwoGeom>(m, d, {}, n, groupsPerPair, logA, logB, fwdPool, bwdPool, counts, st);
+}
+int launch_profile_two_counts(const mb_machine *m, const TwoEnvDesc *d, const TwoEnvTables &t, int n, int groupsPerPair, const double *logA, const double *logB,
+                              const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
+  return two_counts<TwoEnvGeom>(m, d, t, n, groupsPerPair, logA, logB, fwdPool, bwdPool, counts, st);
 }
 
-int launch_profile_two_rowpost(const mb_machine *m, int axis, const PairProfDesc *d, int n, int groupsPerPair, int tabMax, const double *logA,
-                               const double *logB, const double *fwdPool, const double *bwdPool, double *post, hipStream_t st) {
+template <template <bool> class Geom>
+static int two_rowpost(const mb_machine *m, int axis, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, int groupsPerPair, int tabMax,
+                       const double *logA, const double *logB, const double *fwdPool, const double *bwdPool, double *post, hipStream_t st) {
   if (n <= 0) return 0;
   const dim3 g((unsigned)((long long)n * groupsPerPair)), b(ROWPOST_THREADS);
   const int det = g_deterministic ? 1 : 0;
-  if (axis) k_profile_two_rowpost<1><<<g, b, 0, st>>>(m->dev, d, groupsPerPair, logA, logB, fwdPool, bwdPool, post, tabMax, det);
-  else k_profile_two_rowpost<0><<<g, b, 0, st>>>(m->dev, d, groupsPerPair, logA, logB, fwdPool, bwdPool, post, tabMax, det);
-  return hip_ok(hipGetLastError(), "k_profile_two_rowpost") ? 0 : 1;
+  if (axis) k_profile_two_rowpost<1, Geom><<<g, b, 0, st>>>(m->dev, d, t, groupsPerPair, logA, logB, fwdPool, bwdPool, post, tabMax, det);
+  else k_profile_two_rowpost<0, Geom><<<g, b, 0, st>>>(m->dev, d, t, groupsPerPair, logA, logB, fwdPool, bwdPool, post, tabMax, det);
+  return hip_ok(hipGetLastError(), Geom<true>::ENV ? "k_profile_two_env_rowpost" : "k_profile_two_rowpost") ? 0 : 1;
+}
+int launch_profile_two_rowpost(const mb_machine *m, int axis, const PairProfDesc *d, int n, int groupsPerPair, int tabMax, const double *logA,
+                               const double *logB, const double *fwdPool, const double *bwdPool, double *post, hipStream_t st) {
+  return two_rowpost<TwoGeom>(m, axis, d, {}, n, groupsPerPair, tabMax, logA, logB, fwdPool, bwdPool, post, st);
+}
+int launch_profile_two_rowpost(const mb_machine *m, int axis, const TwoEnvDesc *d, const TwoEnvTables &t, int n, int groupsPerPair, int tabMax, const double *logA,
+                               const double *logB, const double *fwdPool, const double *bwdPool, double *post, hipStream_t st) {
+  return two_rowpost<TwoEnvGeom>(m, axis, d, t, n, groupsPerPair, tabMax, logA, logB, fwdPool, bwdPool, post, st);
 }
 
+template <template <bool> class Geom>
+static int two_traceback(const mb_machine *m, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, const double *logA, const double *logB,
+                         const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, hipStream_t st) {
+  if (n <= 0) return 0;
+  k_profile_two_traceback<Geom><<<(n + 63) / 64, 64, 0, st>>>(m->dev, d, t, n, logA, logB, pool, edges, rows, inRows, len);
+  return hip_ok(hipGetLastError(), Geom<true>::ENV ? "k_profile_two_env_traceback" : "k_profile_two_traceback") ? 0 : 1;
+}
 int launch_profile_two_traceback(const mb_machine *m, const PairProfDesc *d, int n, const double *logA, const double *logB, const double *pool,
                                  uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, hipStream_t st) {
-  if (n <= 0) return 0;
-  k_profile_two_traceback<<<(n + 63) / 64, 64, 0, st>>>(m->dev, d, n, logA, logB, pool, edges, rows, inRows, len);
-  return hip_ok(hipGetLastError(), "k_profile_two_traceback") ? 0 : 1;
+  return two_traceback<TwoGeom>(m, d, {}, n, logA, logB, pool, edges, rows, inRows, len, st);
+}
+int launch_profile_two_traceback(const mb_machine *m, const TwoEnvDesc *d, const TwoEnvTables &t, int n, const double *logA, const double *logB, const double *pool,
+                                 uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, hipStream_t st) {
+  return two_traceback<TwoEnvGeom>(m, d, t, n, logA, logB, pool, edges, rows, inRows, len, st);
 }
 
 }  // namespace mb

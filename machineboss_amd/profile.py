@@ -1079,7 +1079,13 @@ class TwoProfileDP(PairProfileDP):
     there: after a blank only input-reading edges follow (Z feeds the match and the input-only edges alone).  The output blank reads
     N, never W.  Viterbi keeps the FIRST maximum -- N: the output blank, then the match edges, then the output-only edges; W: "no
     move", then the input-only edges, then the silent edges; Z: W, then the input blank; edges of a kind in `incoming` order, which
-    is ascending input token first, then ascending output token.  Lattices are [K + 1, L + 1, S]."""
+    is ascending input token first, then ascending output token.  Lattices are [K + 1, L + 1, S].
+
+    ``env`` (forward, backward, counts, rowPosteriors, viterbi): a seqpair.Envelope or an (inStart, inEnd) pair -- output row r
+    holds the input-row positions inStart[r] <= i < inEnd[r]; all three layers of every other cell are -inf, so the input blank
+    Z[i-1][r] -> Z[i][r] is left out when (i-1, r) is outside like any other move along i (docs/profile_tapes.md, "Pairs of
+    profiles under an envelope").  The sweeps visit the envelope cells alone and read a cell outside as the -inf it is.  Without it
+    not one operation differs."""
 
     def __init__(self, em: EvaluatedMachine):
         super().__init__(em)
@@ -1100,7 +1106,7 @@ class TwoProfileDP(PairProfileDP):
             raise MachineError("profile weight is NaN or +infinity")
         return A, self._check(B)
 
-    def forward(self, A, B, mode: str = "exact") -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
+    def forward(self, A, B, mode: str = "exact", env=None) -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
         """(loglike, N, W, Z), each [K+1][L+1][S]; mode "exact" or "max"."""
         A, B = self._checkTwo(A, B)
         fold = _max_fold if mode == "max" else _lse_fold
@@ -1108,8 +1114,9 @@ class TwoProfileDP(PairProfileDP):
         N = np.full((K + 1, L + 1, S), _NEG); W = np.full((K + 1, L + 1, S), _NEG); Z = np.full((K + 1, L + 1, S), _NEG)
         _, mS, mD, mW, mA, mO = self.mAll
         _, iS, iD, iW, iA, _ = self.iAll
+        inside = self.envelopeRows(env, K, L)
         for i in range(K + 1):
-            for r in range(L + 1):
+            for r in (range(L + 1) if inside is None else inside[i]):      # (a cell outside stays -inf and is read as such)
                 base = np.full(S, _NEG)
                 if i == 0 and r == 0:
                     base[0] = 0.0
@@ -1128,7 +1135,7 @@ class TwoProfileDP(PairProfileDP):
                 Z[i, r] = fold(w_, self._all, Z[i - 1, r] + A[i - 1][0]) if i else w_
         return float(Z[K, L, S - 1]), N, W, Z
 
-    def backward(self, A, B) -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
+    def backward(self, A, B, env=None) -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
         """(loglike, NB, WB, ZB), exact log-sum-exp; loglike = NB[0][0][0].  ZB[i][r][s] is the mass from the committed stage of
         (i, r, s) to the end, WB from the waiting stage, NB from the arrived stage."""
         A, B = self._checkTwo(A, B)
@@ -1136,8 +1143,9 @@ class TwoProfileDP(PairProfileDP):
         NB = np.full((K + 1, L + 1, S), _NEG); WB = np.full((K + 1, L + 1, S), _NEG); ZB = np.full((K + 1, L + 1, S), _NEG)
         _, mS, mD, mW, mA, mO = self.mAll
         _, iS, iD, iW, iA, _ = self.iAll
+        inside = self.envelopeRows(env, K, L)
         for i in range(K, -1, -1):
-            for r in range(L, -1, -1):
+            for r in (range(L, -1, -1) if inside is None else reversed(inside[i])):
                 base = np.full(S, _NEG)
                 if i == K and r == L:
                     base[S - 1] = 0.0
@@ -1155,16 +1163,17 @@ class TwoProfileDP(PairProfileDP):
                 NB[i, r] = np.logaddexp(base, B[r][0] + NB[i, r + 1]) if r < L else base
         return float(NB[0, 0, 0]), NB, WB, ZB
 
-    def counts(self, A, B, blanks: Optional[list] = None) -> Tuple[np.ndarray, float]:
+    def counts(self, A, B, blanks: Optional[list] = None, env=None) -> Tuple[np.ndarray, float]:
         """(posterior expected use of every transition, Forward loglike); nothing for a -inf pair.  Blanks are not edges;
         ``blanks`` (a list) receives (mass of the output blanks, mass of the input blanks), summed over the lattice."""
         A, B = self._checkTwo(A, B)
-        ll, NF, WF, ZF = self.forward(A, B)
+        ll, NF, WF, ZF = self.forward(A, B) if env is None else self.forward(A, B, env=env)
         out = np.zeros(self.em.nTransitions)
         if not ll > _NEG:
             return out, ll
-        _, NB, WB, ZB = self.backward(A, B)
+        _, NB, WB, ZB = self.backward(A, B) if env is None else self.backward(A, B, env=env)
         K, L = len(A), len(B)
+        inside = self.envelopeRows(env, K, L)
         mE, mS, mD, mW, mA, mO = self.mAll
         iE, iS, iD, iW, iA, _ = self.iAll
         outBlank = inBlank = 0.0
@@ -1173,7 +1182,7 @@ class TwoProfileDP(PairProfileDP):
             return float(np.exp(b[b > _NEG]).sum())
         with np.errstate(invalid="ignore"):
             for i in range(K + 1):
-                for r in range(L + 1):
+                for r in (range(L + 1) if inside is None else inside[i]):
                     f, z = WF[i, r] - ll, ZF[i, r] - ll
                     if r < L:
                         if i < K:
@@ -1188,19 +1197,20 @@ class TwoProfileDP(PairProfileDP):
             blanks.append((outBlank, inBlank))
         return out, ll
 
-    def rowPosteriors(self, A, B) -> Tuple[np.ndarray, np.ndarray, float]:
+    def rowPosteriors(self, A, B, env=None) -> Tuple[np.ndarray, np.ndarray, float]:
         """(postA[K, nInTok + 1], postB[L, nOutTok + 1], Forward loglike): postB[r][o] is the posterior probability that output
         row r was consumed as output token o, postA[i][a] that input row i was consumed as input token a (column 0 of either: as
         its blank) -- the terms of counts() and its two blank masses, binned by (row, column) of either tape instead of by
         transition, which are the gradients of loglike in B[r][o] and in A[i][a] (docs/profile_tapes.md, "Row posteriors of pairs
         of profiles").  Every row of either table sums to 1; zeros for a -inf pair; exactly 0 where the weight is -inf."""
         A, B = self._checkTwo(A, B)
-        ll, NF, WF, ZF = self.forward(A, B)
+        ll, NF, WF, ZF = self.forward(A, B) if env is None else self.forward(A, B, env=env)
         K, L = len(A), len(B)
         postA = np.zeros((K, self.em.nInTok + 1)); postB = np.zeros((L, self.em.nOutTok + 1))
         if not ll > _NEG:
             return postA, postB, ll
-        _, NB, WB, ZB = self.backward(A, B)
+        _, NB, WB, ZB = self.backward(A, B) if env is None else self.backward(A, B, env=env)
+        inside = self.envelopeRows(env, K, L)
         _, mS, mD, mW, mA, mO = self.mAll
         _, iS, iD, iW, iA, _ = self.iAll
         eO = np.asarray(self.eO)
@@ -1209,7 +1219,7 @@ class TwoProfileDP(PairProfileDP):
             return float(np.exp(b[b > _NEG]).sum())
         with np.errstate(invalid="ignore"):
             for i in range(K + 1):
-                for r in range(L + 1):
+                for r in (range(L + 1) if inside is None else inside[i]):
                     f, z = WF[i, r] - ll, ZF[i, r] - ll
                     if r < L:
                         if i < K:
@@ -1226,15 +1236,16 @@ class TwoProfileDP(PairProfileDP):
                         postA[i, 0] += mass(z + (A[i][0] + ZB[i + 1, r]))
         return postA, postB, ll
 
-    def viterbi(self, A, B, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
+    def viterbi(self, A, B, census: Optional[dict] = None, env=None) -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
         """(score, global edge ids start -> end, output row, input row at which each fired); the first maximum in the fill's
         candidate order.  The output row of an emitting edge is the row it consumed, of an output-less edge the number of rows
         consumed before it; the input row likewise on the input tape -- input blanks advance it without an edge, so it does not
         follow from counting edges.  ``census``: per step at which two or more candidates equal the cell, a count under the tuple
         of the kinds that tie, in candidate order ("blank", "match", "emit" at an N cell; "stay", "ins", "silent" at a W cell;
-        "wait", "inblank" at a Z cell)."""
+        "wait", "inblank" at a Z cell).  Under ``env`` a candidate whose source cell lies outside the envelope is -inf and loses
+        to the finite cell it is compared with."""
         A, B = self._checkTwo(A, B)
-        v, N, W, Z = self.forward(A, B, "max")
+        v, N, W, Z = self.forward(A, B, "max") if env is None else self.forward(A, B, "max", env=env)
         edges: List[int] = []; rows: List[int] = []; ins: List[int] = []
         if not v > _NEG:
             return v, np.zeros(0, np.uint32), np.zeros(0, np.int32), np.zeros(0, np.int32)

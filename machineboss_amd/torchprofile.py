@@ -79,7 +79,7 @@ def pair_profile_loglike(machine_or_dm, inputs, logP, rowOff, envs=None, backend
     return _PairProfileLoglike.apply(logP, machine_or_dm, inputs, rowOff, envs, backend)
 
 
-def _two_row_posteriors(machine_or_dm, A, inOff, B, rowOff, wantA, wantB, backend):
+def _two_row_posteriors(machine_or_dm, A, inOff, B, rowOff, wantA, wantB, envs, backend):
     """(postA[sumK, CA] or None, postB[sumRows, C] or None, loglike[nPairs]) in numpy, on the device or by the numpy yardstick."""
     n = len(rowOff) - 1
     As = [A[inOff[k]:inOff[k + 1]] for k in range(n)]
@@ -91,29 +91,31 @@ def _two_row_posteriors(machine_or_dm, A, inOff, B, rowOff, wantA, wantB, backen
         postA, postB = np.zeros(A.shape, np.float64), np.zeros(B.shape, np.float64)
         ll = np.empty(n, np.float64)
         for k in range(n):
-            postA[inOff[k]:inOff[k + 1]], postB[rowOff[k]:rowOff[k + 1]], ll[k] = dp.rowPosteriors(As[k], Bs[k])
+            postA[inOff[k]:inOff[k + 1]], postB[rowOff[k]:rowOff[k + 1]], ll[k] = dp.rowPosteriors(As[k], Bs[k], env=None if envs is None else envs[k])
         return (postA if wantA else None), (postB if wantB else None), ll
     if backend != "device":
         raise ValueError('backend is "device" or "numpy"')
     from . import capi
     own = not isinstance(machine_or_dm, capi.DeviceMachine)
     dm = capi.DeviceMachine(machine_or_dm) if own else machine_or_dm
-    twos = capi.DeviceProfileTwos(dm, As, Bs)
+    twos = None
     try:
+        twos = capi.DeviceProfileTwos(dm, As, Bs, envs=envs)
         return twos.row_posteriors(inputs=wantA, outputs=wantB)
     finally:
-        twos.close()
+        if twos is not None:
+            twos.close()
         if own:
             dm.close()
 
 
 class _TwoProfileLoglike(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logA, logB, machine_or_dm, inOff, rowOff, backend):
+    def forward(ctx, logA, logB, machine_or_dm, inOff, rowOff, envs, backend):
         A = np.ascontiguousarray(logA.detach().cpu().numpy(), np.float64)
         B = np.ascontiguousarray(logB.detach().cpu().numpy(), np.float64)
         wantA, wantB = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        postA, postB, ll = _two_row_posteriors(machine_or_dm, A, inOff, B, rowOff, wantA, wantB, backend)
+        postA, postB, ll = _two_row_posteriors(machine_or_dm, A, inOff, B, rowOff, wantA, wantB, envs, backend)
         ctx.inOff, ctx.rowOff = inOff, rowOff
         ctx.save_for_backward(None if postA is None else torch.from_numpy(postA).to(logA.device),
                               None if postB is None else torch.from_numpy(postB).to(logB.device))
@@ -127,16 +129,18 @@ class _TwoProfileLoglike(torch.autograd.Function):
             rows = torch.as_tensor(np.diff(off), device=post.device)
             return torch.repeat_interleave(grad_out.to(device=post.device, dtype=post.dtype), rows).unsqueeze(1) * post
         postA, postB = ctx.saved_tensors
-        return grad(postA, ctx.inOff), grad(postB, ctx.rowOff), None, None, None, None
+        return grad(postA, ctx.inOff), grad(postB, ctx.rowOff), None, None, None, None, None
 
 
-def two_profile_loglike(machine_or_dm, logA, inOff, logB, rowOff, backend="device"):
+def two_profile_loglike(machine_or_dm, logA, inOff, logB, rowOff, envs=None, backend="device"):
     """tensor[nPairs] of log-likelihoods: pair k is the rows inOff[k]..inOff[k + 1] of ``logA``, a float64 [sumK, nInTok + 1] tensor
     of log weights on the input tape, against the rows rowOff[k]..rowOff[k + 1] of ``logB``, a float64 [sumRows, nOutTok + 1] tensor
     on the output tape; column 0 of either is its blank (docs/profile_tapes.md, "Row posteriors of pairs of profiles").
     Differentiable in both tables: the gradient is grad_out[k] times the row posteriors of pair k on that tape, zeros for a pair
     that scores -inf, computed only for the tables that require one.  ``machine_or_dm``: an EvaluatedMachine or a
-    capi.DeviceMachine (kept open for the caller).  ``backend``: "device" (one capi.DeviceProfileTwos.row_posteriors() call) or
+    capi.DeviceMachine (kept open for the caller).  ``envs``: per pair None, a seqpair.Envelope or (inStart, inEnd) over the input
+    rows per output row (docs/profile_tapes.md, "Pairs of profiles under an envelope"); the posteriors are then summed over the
+    envelope cells.  ``backend``: "device" (one capi.DeviceProfileTwos.row_posteriors() call) or
     "numpy" (profile.TwoProfileDP.rowPosteriors, no GPU needed).  Tensors go through host memory, as pair_profile_loglike's do."""
     if logA.dtype != torch.float64 or logA.dim() != 2:
         raise ValueError("logA is a float64 [sumK, nInTok + 1] tensor")
@@ -148,7 +152,9 @@ def two_profile_loglike(machine_or_dm, logA, inOff, logB, rowOff, backend="devic
         raise ValueError("inOff has one entry per pair and one more, from 0 up to the rows of logA")
     if len(rowOff) != len(inOff) or rowOff[0] != 0 or rowOff[-1] != logB.shape[0] or (np.diff(rowOff) < 0).any():
         raise ValueError("rowOff has one entry per pair and one more, from 0 up to the rows of logB")
-    return _TwoProfileLoglike.apply(logA, logB, machine_or_dm, inOff, rowOff, backend)
+    if envs is not None and len(envs) != len(inOff) - 1:
+        raise ValueError("one envelope (or None) per pair, please")
+    return _TwoProfileLoglike.apply(logA, logB, machine_or_dm, inOff, rowOff, envs, backend)
 
 
 def _one_row_posteriors(machine_or_dm, P, rowOff, colTok, backend):
