@@ -269,6 +269,21 @@ mb_profile_pairs *mb_profile_pairs_create_merged(mb_machine *m, int64_t nPairs, 
 int mb_profile_pair_fill_merged(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows,
                                 int32_t nCols, const int32_t *colTok, double *cellsOut);
 
+/* Row posteriors of pairs against merged profiles (k_profile_pair_merge_rowpost; docs/profile_tapes.md, "Row posteriors of pairs
+ * against a merged profile"): post[(rowOff[k] - rowOff[0] + r)*(nCols+1) + c] = the posterior probability that row r of pair k was
+ * consumed as column c (column 0: as the blank) -- the blank out of every plane, the repeat of column c, and the match and
+ * output-only edges that write colTok[c] out of every plane other than c -- which is the gradient of the pair's log-likelihood in
+ * logP at that entry.  Every row of a pair with a finite likelihood sums to 1; a pair whose likelihood is -inf gets zeros and an
+ * entry whose weight is -inf is exactly 0; post less the repeats, summed over rows and over the columns of a token, is the
+ * mb_profile_pairs_counts of the transitions that write that token.  MB_DETERMINISTIC=1 as mb_profile_pairs_row_posteriors.
+ * mb_profile_pairs_set_rows_merged replaces the whole row table (same shapes, checked as create checks it; a refused table leaves
+ * the old one in effect) and launches nothing.  Both refuse a plain pairs object before anything is launched: "merged row
+ * posteriors take merged profiles"; a pair whose lattices exceed the memory budget on its own is the error of
+ * mb_profile_pairs_counts. */
+int mb_profile_pairs_row_posteriors_merged(mb_profile_pairs *p, double *post /* [sum rows][nCols+1], overwritten */,
+                                           double *loglike /* [nPairs] or NULL */);
+int mb_profile_pairs_set_rows_merged(mb_profile_pairs *p, const double *logP);
+
 /* Pairs of profiles (`--generate-csv A.csv` beside `--recognize-csv B.csv`): a machine WITH an input alphabet between an input
  * profile and an output profile -- the semantics of compose(A.machine(), compose(M, transpose(B.machine()))) with both tapes empty,
  * swept natively over (K + 1) x (rows + 1) x 3 x nStates along anti-diagonals (mb_profile_two.hip; docs/profile_tapes.md, "Pairs

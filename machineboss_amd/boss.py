@@ -589,6 +589,44 @@ def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device"
     return scores, (acc.paramCounts(machine, params) if counts else None)
 
 
+def mergedPairPosteriors(machine: Machine, inputs, profile, backend: str = "device", params=None):
+    """Every input sequence (a list of symbols) as one pair with ``profile`` read CTC-merged (a profile.Profile, or a pair
+    (logP[L, nCols + 1], colTok) as Profile.mergeRows returns), all pairs in one batch: (posteriors, loglike), one [L, nCols + 1]
+    array and one float per input -- the posterior probability that each row was consumed as each column (column 0: as the blank),
+    the gradient of the pair's log-likelihood in the merged rows (docs/profile_tapes.md, "Row posteriors of pairs against a merged
+    profile").  An input that cannot be tokenised scores -inf; it and an input that scores -inf get zeros.  ``backend``: "device"
+    (capi.DeviceProfilePairs.merged_row_posteriors) or "numpy" (profile.PairMergedProfileDP.rowPosteriors)."""
+    import numpy as np
+    from .profile import PairMergedProfileDP
+    if backend not in ("device", "numpy"):
+        raise MachineError('backend is "device" or "numpy"')
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    if not ev.nOutTok:
+        raise MachineError("--recognize-merge-csv needs a machine with an output alphabet")
+    P, colTok = _mergedRows(profile, ev) if hasattr(profile, "mergeRows") else profile
+    P = np.asarray(P, np.float64).reshape(-1, len(colTok) + 1)
+    ok = [ev.inputTokenizer.canTokenize(seq) for seq in inputs]
+    xs = [np.asarray(ev.inputTokenizer.tokenize(seq), np.int64).reshape(-1) for seq, k in zip(inputs, ok) if k]
+    if backend == "numpy":
+        pdp = PairMergedProfileDP(ev, colTok)
+        res = [pdp.rowPosteriors(x, P) for x in xs]
+        post, ll = [r[0] for r in res], [r[1] for r in res]
+    else:
+        from . import capi
+        dm = capi.DeviceMachine(ev)
+        pairs = None
+        try:
+            pairs = capi.DeviceProfilePairs(dm, xs, [P] * len(xs), colTok)
+            flat, ll = pairs.merged_row_posteriors()
+            post = [flat[k * len(P):(k + 1) * len(P)] for k in range(len(xs))]
+        finally:
+            if pairs is not None:
+                pairs.close()
+            dm.close()
+    ip, il = iter(post), iter(ll)
+    return [np.array(next(ip)) if k else np.zeros(P.shape) for k in ok], [float(next(il)) if k else -math.inf for k in ok]
+
+
 def _runProfilePairs(args, out, machine: Machine) -> int:
     """--recognize-csv beside --input-chars / --input-fasta / --input-json on a machine with an input alphabet: every input
     sequence is one pair with the profile (docs/profile_tapes.md, "Pairs"), all pairs in one batch.  -L and -V print one

@@ -36,6 +36,7 @@ EXPORTS = [
     "mb_profile_pairs_create_merged", "mb_profile_pair_fill_merged",
     "mb_profile_pairs_set_envelopes", "mb_profile_pair_fill_env", "mb_profile_pairs_cells",
     "mb_profile_pairs_row_posteriors", "mb_profile_pairs_set_rows",
+    "mb_profile_pairs_row_posteriors_merged", "mb_profile_pairs_set_rows_merged",
     "mb_profile_twos_create", "mb_profile_twos_destroy", "mb_profile_twos_forward", "mb_profile_twos_viterbi", "mb_profile_twos_counts",
     "mb_profile_twos_row_posteriors", "mb_profile_twos_set_rows",
     "mb_profile_two_fill",
@@ -144,6 +145,8 @@ def load():
     L.mb_profile_pairs_cells.argtypes = [vp]; L.mb_profile_pairs_cells.restype = C.c_int64
     L.mb_profile_pairs_row_posteriors.argtypes = [vp, dp, dp]
     L.mb_profile_pairs_set_rows.argtypes = [vp, dp]
+    L.mb_profile_pairs_row_posteriors_merged.argtypes = [vp, dp, dp]
+    L.mb_profile_pairs_set_rows_merged.argtypes = [vp, dp]
     L.mb_profile_twos_create.restype = vp
     L.mb_profile_twos_create.argtypes = [vp, C.c_int64, dp, i64p, dp, i64p]
     L.mb_profile_twos_destroy.argtypes = [vp]; L.mb_profile_twos_destroy.restype = None
@@ -792,16 +795,34 @@ class DeviceProfilePairs:
         _check(load().mb_profile_pairs_row_posteriors(self.h, _p(post, C.c_double), _p(ll, C.c_double)))
         return post, ll
 
-    def set_profiles(self, profiles):
-        """New rows for every pair, of the shapes the object was created with; the inputs and the envelopes stay.  A refused
-        table (NaN, +inf) leaves the old rows in effect."""
+    def _set_rows(self, call, profiles):
         width = self.logP.shape[1]
         rows = [np.asarray(q, np.float64).reshape(-1, width) for q in profiles]
         if len(rows) != self.nPairs or any(len(r) != n for r, n in zip(rows, np.diff(self.rowOff))):
             raise ValueError("one profile per pair with the rows it was created with, please")
         logP = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((1, width)), np.float64)
-        _check(load().mb_profile_pairs_set_rows(self.h, _p(logP, C.c_double)))
+        _check(call(self.h, _p(logP, C.c_double)))
         self.logP = logP
+
+    def set_profiles(self, profiles):
+        """New rows for every pair, of the shapes the object was created with; the inputs and the envelopes stay.  A refused
+        table (NaN, +inf) leaves the old rows in effect."""
+        self._set_rows(load().mb_profile_pairs_set_rows, profiles)
+
+    def merged_row_posteriors(self):
+        """Returns (post[sumRows, nCols + 1], loglike[nPairs]) of an object created with ``colTok``: post[rowOff[k] + r][c] is the
+        posterior probability that row r of pair k was consumed as column c (column 0: as the blank) -- the blank out of every
+        plane, the repeat of column c, and the emissions of colTok[c - 1] out of every other plane -- the gradient of loglike[k]
+        in that entry of the merged profile; zeros for a pair whose likelihood is -inf (docs/profile_tapes.md, "Row posteriors
+        of pairs against a merged profile").  The yardstick is profile.PairMergedProfileDP.rowPosteriors."""
+        post = np.zeros((int(self.rowOff[-1]), self.logP.shape[1]), np.float64)
+        ll = np.empty(self.nPairs, np.float64)
+        _check(load().mb_profile_pairs_row_posteriors_merged(self.h, _p(post, C.c_double), _p(ll, C.c_double)))
+        return post, ll
+
+    def set_merged_profiles(self, profiles):
+        """set_profiles for an object created with ``colTok``: new [rows, nCols + 1] rows for every pair."""
+        self._set_rows(load().mb_profile_pairs_set_rows_merged, profiles)
 
 
 def _env_rows(env):

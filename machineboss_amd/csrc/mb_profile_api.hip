@@ -934,6 +934,58 @@ int mb_profile_pairs_set_rows(mb_profile_pairs *p, const double *logP) {
   return hip_ok(hipStreamSynchronize(g_stream), "H2D pair profiles") ? 0 : 1;
 }
 
+// The merged pairs' own entry: mb_profile_pairs_counts on a merged object chunk for chunk -- the materialised merged Forward and
+// Backward, whose X / T rings share one scratch buffer -- then the flat k_profile_pair_merge_rowpost over the two lattices.
+int mb_profile_pairs_row_posteriors_merged(mb_profile_pairs *p, double *post, double *loglike) {
+  ApiGuard guard;
+  if (!p || (!post && p->totalRows)) { set_error("null argument"); return 1; }
+  if (!p->nCols) { set_error("merged row posteriors take merged profiles"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  latch_deterministic();
+  const mb_machine *m = p->m;
+  const long long PL = p->nCols + 1, nv = p->totalRows * PL;
+  const int tabMax = rowpost_table();
+  std::vector<Chunk> chunks;
+  auto bytes = [&](long long k) { return 2.0 * pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false) + 8.0 * (double)(pp_rows(p, k) * PL); };   // both lattices, the X / T ring and the pair's bins
+  if (!lattice_chunks(p->n, "pair", bytes, chunks)) return 1;
+  SmBuf<double> d_ll, d_bll, d_post;
+  MB_HIP(d_ll.alloc(p->n));
+  if (!hip_ok(d_bll.alloc(p->n), "hipMalloc(loglike)") || !hip_ok(d_post.alloc(nv), "hipMalloc(row posteriors)")) return 1;
+  PairWhere where;
+  int rc = for_chunks<PairProfPlan>(chunks, pp_build(p, false, where), [&](const Chunk &c, PairProfPlan &pl, Timer &tm) {
+    const long long np = c.p1 - c.p0;
+    double *fwd = ws_array<double>(0, pl.cells);
+    double *bwd = ws_array<double>(1, pl.cells);
+    double *scratch = pl.ring ? (double *)ws_get(2, (size_t)pl.ring * sizeof(double)) : nullptr;
+    if (!fwd || !bwd || (pl.ring && !scratch)) return 1;
+    const long long groups = rowpost_groups(c.p0, c.p1, [&](long long k) { return pp_rows(p, k); }, [&](long long k) {
+      return profile_pair_rowpost_rows(pp_cells(p, k) / (2 * (long long)m->S), m->S, (int)pp_rows(p, k), (int)PL, tabMax);
+    });
+    if (np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); return 1; }
+    {
+      Timed t(tm, pl.launches());
+      if (pp_launch_fwd(p, MB_FORWARD, true, pl, np, fwd, scratch, d_ll + c.p0) || pp_launch_bwd(p, pl, np, bwd, scratch, d_bll + c.p0) ||
+          launch_profile_pair_merge_rowpost(m, pp_map(p), pl.d.p, (int)np, (int)groups, tabMax, p->d_in, p->d_logP, fwd, bwd, d_ll + c.p0, d_post, g_stream)) return 1;
+    }
+    return hip_ok(hipStreamSynchronize(g_stream), "row posteriors") ? 0 : 1;      // (the next chunk takes the lattices over)
+  });
+  if (!rc) rc = fetch_posteriors(post, d_post, nv);
+  if (!rc && loglike) rc = fetch_loglike(loglike, d_ll, p->n, &where);
+  g_last_kernel = "k_profile_pair_merge_rowpost";
+  return rc;
+}
+
+int mb_profile_pairs_set_rows_merged(mb_profile_pairs *p, const double *logP) {
+  ApiGuard guard;
+  if (!p) { set_error("null argument"); return 1; }
+  if (!p->nCols) { set_error("merged row posteriors take merged profiles"); return 1; }
+  const long long nv = p->totalRows * (p->nCols + 1);
+  if (nv && !logP) { set_error("null argument"); return 1; }
+  if (!profile_values_ok(logP, nv)) return 1;
+  if (nv && h2d_large(p->d_logP, logP, (size_t)nv * sizeof(double))) return 1;
+  return hip_ok(hipStreamSynchronize(g_stream), "H2D pair profiles") ? 0 : 1;
+}
+
 int mb_profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, double *cellsOut) {
   ApiGuard guard;
   return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, 0, nullptr, nullptr, nullptr, cellsOut);

@@ -54,7 +54,7 @@ struct CountsAcc {
   }
 };
 
-// One lane sum into bin `bin` of a row-posterior table (k_profile_pair_rowpost, k_profile_two_rowpost, k_profile_rowpost), every lane of the wavefront
+// One lane sum into bin `bin` of a row-posterior table (k_profile_pair_rowpost, k_profile_pair_merge_rowpost, k_profile_two_rowpost, k_profile_rowpost), every lane of the wavefront
 // together.  whole: all 64 lanes hold items of one line, so the sums are reduced across the lanes and lane 0 alone adds; else every
 // lane adds its own.  det: the lane sum becomes 64-bit fixed point at 2^-36 (mb_internal.h) before it meets another.
 __device__ __forceinline__ void rowpost_add(double *tab, int bin, double v, bool whole, int lane, int det) {

@@ -36,6 +36,12 @@ int launch_profile_pair_merge_bwd(const mb_machine *m, MergeMap mm, const PairPr
 // counts[nTrans] += posteriors of the n pairs (fwdPool / bwdPool: their materialised lattices); det: 64-bit fixed point at 2^-36
 int launch_profile_pair_merge_counts(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, int groupsPerPair, const int *inTok,
                                      const double *logP, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
+// post[(rowBase + r) * (nCols + 1) + c] = the row posteriors of the n pairs, every bin of every row written (nothing to clear);
+// groupsPerPair: at least the row blocks (profile_pair_rowpost_rows over rows of (I + 1)(nCols + 1) S items) of the pair that has
+// most, 1 024 at the most; loglike: the Forward's, per pair; det: post holds 64-bit fixed point at 2^-36
+int launch_profile_pair_merge_rowpost(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, int groupsPerPair, int tabMax,
+                                      const int *inTok, const double *logP, const double *fwdPool, const double *bwdPool,
+                                      const double *loglike, double *post, hipStream_t st);
 int launch_profile_pair_merge_traceback(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, const int *inTok,
                                         const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len,
                                         hipStream_t st);

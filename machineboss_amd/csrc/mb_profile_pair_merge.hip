@@ -1,6 +1,7 @@
-// mb_profile_pair_merge.hip -- Forward / Backward / Viterbi / posterior counts of a machine WITH an input alphabet, run on a known
-// input sequence x[1..I] against a CTC-MERGED profile of L rows: the semantics of compose(M, transpose(CSVProfile::mergingMachine()))
-// on input x with an empty output, restated in docs/profile_tapes.md ("Pairs against a merged profile"):
+// mb_profile_pair_merge.hip -- Forward / Backward / Viterbi / posterior counts / row posteriors of a machine WITH an input alphabet,
+// run on a known input sequence x[1..I] against a CTC-MERGED profile of L rows: the semantics of
+// compose(M, transpose(CSVProfile::mergingMachine())) on input x with an empty output, restated in docs/profile_tapes.md ("Pairs
+// against a merged profile"):
 //
 //   X[i][r][c][s] = (+)_{k != c} W[i][r][k][s]                                                          (the exclusion vector)
 //   N[i][r][0][d] = [i = 0, r = 0, d = 0]  (+)  (+)_p (N[i][r-1][p][d] + P[r-1][0])                      (blank; r > 0)
@@ -302,6 +303,105 @@ __global__ __launch_bounds__(256) void k_profile_pair_merge_counts(DevMachine m,
   acc.flush();
 }
 
+// Row posteriors: post[(rowBase + r) * (nCols + 1) + c] = the posterior probability that row r of the pair's merged profile was
+// consumed as column c (0: the blank), the gradient of the log-likelihood in P[r][c] (docs/profile_tapes.md, "Row posteriors of
+// pairs against a merged profile"):
+//   post[r][0] = sum_i sum_p sum_s exp((N_F[i][r][p][s] - LL) + (P[r][0] + NB[i][r+1][0][s]))
+//   post[r][c] = sum_i sum_s exp((N_F[i][r][c][s] - LL) + (P[r][c] + NB[i][r+1][c][s]))                     (the repeat)
+//              + the emitting terms of k_profile_pair_merge_counts above, binned by (row, column) instead of by transition.
+// The scheme is the one of k_profile_pair_rowpost (mb_profile_pair.hip) with the plane axis of k_profile_rowpost<true>
+// (mb_profile_post.hip).  The work items are (row, cell of the row, plane, state) in that order and a workgroup owns whole rows:
+// blocks of profile_pair_rowpost_rows rows, dealt round robin to the pair's groups.  An item (r, i, k, s) adds the blank term out of
+// its plane, at k >= 1 the repeat term into column k, and at every other column c whose P[r][c] is finite the match edges of
+// (s, x_{i+1}, colTok[c]) into NB[i+1][r+1][c] and the output-only edges of (s, colTok[c]) into NB[i][r+1][c], one CSR row each,
+// summed in a register: the sum over k != c runs over the items, the exclusion vector of the Forward sweep is not needed.  Where all
+// 64 lanes of the wavefront hold items of one row the lane sums are reduced across the lanes and one lane adds the result to the
+// workgroup's LDS table (rows of the block x (nCols + 1)), else every lane adds its own (rowpost_add, mb_profile_common.h).  The
+// table is then stored with plain stores: every bin has one writing workgroup, so there is no global atomic and nothing to clear
+// beforehand.  A row of more than tabMax columns is summed in its global bins instead, cleared by the workgroup that owns it.  A pair
+// whose likelihood is -inf gets zeros by the same stores.  loglike: the Forward sweep's, per pair of the launch.
+// det: a lane sum is turned into 64-bit fixed point at 2^-36 (mb_internal.h) before it meets another; post then holds the integers.
+__global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_merge_rowpost(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+                                                                                int groupsPerPair, const int *__restrict__ inTok,
+                                                                                const double *__restrict__ logP, const double *__restrict__ fwdPool,
+                                                                                const double *__restrict__ bwdPool, const double *__restrict__ loglike,
+                                                                                double *post, int tabMax, int det) {
+  __shared__ double ltab[ROWPOST_LDS_MAX];
+  const int pair = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
+  const PairProfDesc pd = descs[pair];
+  const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
+  if (L == 0) return;
+  const int *x = inTok + pd.inBase;
+  const double *P = logP + pd.rowBase * PL;
+  const PairMergeLattice<true> F{const_cast<double *>(fwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0},
+      B{const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  const double LL = loglike[pair];
+  const long long PS = (long long)PL * S, perRow = (long long)(I + 1) * PS;
+  const int R = profile_pair_rowpost_rows((long long)(I + 1) * (L + 1) * PL, S, L, PL, tabMax);
+  const bool useLds = PL <= tabMax;
+  const int lane = threadIdx.x & 63;
+  for (long long rb = (long long)group * R; rb < L; rb += (long long)groupsPerPair * R) {
+    const int r0 = (int)rb, r1 = (int)min((long long)L, rb + R), nBins = (r1 - r0) * PL;
+    double *out = post + (pd.rowBase + r0) * PL;
+    double *tab = useLds ? ltab : out;
+    for (int e = threadIdx.x; e < nBins; e += blockDim.x) tab[e] = 0.0;      // (the fixed point's zero has the same bits)
+    if (!useLds) __threadfence();
+    __syncthreads();
+    if (LL > -INFINITY) {
+      const long long nItems = (long long)(r1 - r0) * perRow;
+      for (long long base = threadIdx.x - lane; base < nItems; base += blockDim.x) {      // (a wavefront stays whole in here)
+        const long long idx = base + lane;
+        const bool valid = idx < nItems;
+        int r = r0, i = 0, k = 0, s = 0, ks = 0;
+        double f = -INFINITY, n = -INFINITY;
+        if (valid) {
+          const long long row = idx / perRow, rem = idx - row * perRow;
+          r = r0 + (int)row;
+          i = (int)(rem / PS);
+          ks = (int)(rem - (long long)i * PS);
+          k = ks / S;
+          s = ks - k * S;
+          n = F.nw(i, r, 0)[ks] - LL;
+          f = F.nw(i, r, 1)[ks] - LL;
+        }
+        const bool whole = __all(valid && r == __shfl(r, 0));
+        const bool across = valid && i < I;
+        const double *Pr = P + (long long)r * PL;
+        const double *Nu = B.nw(i, r + 1, 0), *Nd = across ? B.nw(i + 1, r + 1, 0) : nullptr;
+        const int sRow = s * K, xRow = across ? sRow + x[i] * C : 0;
+        const bool nLive = n > -INFINITY, fLive = f > -INFINITY;
+        const int bin0 = (r - r0) * PL;
+        rowpost_add(tab, bin0, nLive ? exp(n + (Pr[0] + Nu[s])) : 0.0, whole, lane, det);
+        for (int c = 1; c < PL; ++c) {      // the out-edges of (s, input token) that write the column's token are one CSR row
+          double v = 0.0;
+          if (valid && c == k) {
+            if (nLive) v = exp(n + (Pr[c] + Nu[ks]));
+          } else if (fLive) {
+            const double pc = Pr[c];
+            if (pc > -INFINITY) {
+              const int tok = mm.colTok[c - 1];
+              if (across) {
+                const double *Ndc = Nd + (long long)c * S;
+                const int a1 = m.outOff[xRow + tok + 1];
+                for (int a = m.outOff[xRow + tok]; a < a1; ++a) v += exp(f + ((m.outW[a] + pc) + Ndc[m.outDst[a]]));
+              }
+              const double *Nuc = Nu + (long long)c * S;
+              const int a1 = m.outOff[sRow + tok + 1];
+              for (int a = m.outOff[sRow + tok]; a < a1; ++a) v += exp(f + ((m.outW[a] + pc) + Nuc[m.outDst[a]]));
+            }
+          }
+          rowpost_add(tab, bin0 + c, v, whole, lane, det);
+        }
+      }
+    }
+    __syncthreads();
+    if (useLds) {
+      for (int e = threadIdx.x; e < nBins; e += blockDim.x) out[e] = tab[e];
+      __syncthreads();
+    }
+  }
+}
+
 // Viterbi traceback over a materialised max lattice, one lane per pair: from the first plane that attains the score at
 // W[I][L][.][S-1] back to N[0][0][0][0], taking at every cell the first candidate (in the fill's order) whose value equals the cell;
 // an emitting edge comes from the lowest plane k != c whose W equals the edge's X.  Blank and repeat rows are not edges.  Edges go
@@ -450,6 +550,15 @@ int launch_profile_pair_merge_counts(const mb_machine *m, MergeMap mm, const Pai
   k_profile_pair_merge_counts<<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(
       m->dev, mm, d, groupsPerPair, inTok, logP, fwdPool, bwdPool, m->nTrans, counts, g_deterministic ? 1 : 0);
   return hip_ok(hipGetLastError(), "k_profile_pair_merge_counts") ? 0 : 1;
+}
+
+int launch_profile_pair_merge_rowpost(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, int groupsPerPair, int tabMax,
+                                      const int *inTok, const double *logP, const double *fwdPool, const double *bwdPool,
+                                      const double *loglike, double *post, hipStream_t st) {
+  if (n <= 0) return 0;
+  k_profile_pair_merge_rowpost<<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(ROWPOST_THREADS), 0, st>>>(
+      m->dev, mm, d, groupsPerPair, inTok, logP, fwdPool, bwdPool, loglike, post, tabMax, g_deterministic ? 1 : 0);
+  return hip_ok(hipGetLastError(), "k_profile_pair_merge_rowpost") ? 0 : 1;
 }
 
 int launch_profile_pair_merge_traceback(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, const int *inTok,

@@ -989,6 +989,45 @@ class PairMergedProfileDP(PairProfileDP):
             blanks.append(blank)
         return out, ll
 
+    def rowPosteriors(self, x, P, repeats: Optional[list] = None) -> Tuple[np.ndarray, float]:
+        """(post[L, nCols + 1], Forward loglike): post[r][c] is the posterior probability that row r was consumed as column c
+        (column 0: as the blank), the gradient of loglike in P[r][c] (docs/profile_tapes.md, "Row posteriors of pairs against a
+        merged profile"): the blank out of every plane of every cell of the row, and for a column its repeat (plane c stays) plus
+        the match and output-only edges of colTok[c - 1] out of every plane k != c -- the emitting terms of counts(), taken plane
+        by plane off W instead of through X, binned by (row, column).  ``repeats``, if a list, receives the [L, nCols + 1] repeat
+        part, so that post - repeats sums per token to the counts.  Every row sums to 1; zeros for a -inf pair; exactly 0 where
+        P[r][c] is -inf."""
+        x, P = self._checkPair(x, P)
+        ll, NF, WF = self.forward(x, P)
+        I, L, PL = len(x), len(P), self.PL
+        post = np.zeros((L, PL)); rep = np.zeros((L, PL))
+        if repeats is not None:
+            repeats.append(rep)
+        if not ll > _NEG:
+            return post, ll
+        _, NB, _ = self.backward(x, P)
+        planes = np.arange(PL)
+
+        def emit(row, f, tab, NBn):
+            """the edges of ``tab`` (column-major) out of plane k into column c != k of the cell whose arrived Backward is NBn"""
+            _, s, d, w, c = tab
+            t = f[:, s] + ((w + P[r][c]) + NBn[c, d])[None, :]
+            keep = (c[None, :] != planes[:, None]) & (t > _NEG)
+            np.add.at(row, np.broadcast_to(c, t.shape)[keep], np.exp(t[keep]))
+        with np.errstate(invalid="ignore"):
+            for i in range(I + 1):
+                for r in range(L):
+                    n, f = NF[i, r] - ll, WF[i, r] - ll
+                    b = n + (P[r][0] + NB[i, r + 1][0])
+                    post[r, 0] += float(np.exp(b[b > _NEG]).sum())
+                    b = n[1:] + (P[r][1:, None] + NB[i, r + 1][1:])
+                    rep[r, 1:] += np.where(b > _NEG, np.exp(b), 0.0).sum(axis=1)
+                    if i < I:
+                        emit(post[r], f, self.matchCol[x[i]], NB[i + 1, r + 1])
+                    emit(post[r], f, self.emitCol, NB[i, r + 1])
+        post += rep
+        return post, ll
+
     def viterbi(self, x, P, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray]:
         """(score, global edge ids start -> end, row at which each fired); the first maximum in the fill's candidate order.  Rows as
         PairProfileDP.viterbi; blank and repeat rows are not edges.  ``census`` counts, by the candidate taken, the steps at which

@@ -13,40 +13,45 @@ import numpy as np
 import torch
 
 
-def _row_posteriors(machine_or_dm, inputs, P, rowOff, envs, backend):
-    """(post[sumRows, C], loglike[nPairs]) in numpy, on the device or by the numpy yardstick."""
+def _row_posteriors(machine_or_dm, inputs, P, rowOff, envs, backend, colTok=None):
+    """(post[sumRows, width], loglike[nPairs]) in numpy, on the device or by the numpy yardstick; colTok: CTC-merged profiles."""
     n = len(rowOff) - 1
     profiles = [P[rowOff[k]:rowOff[k + 1]] for k in range(n)]
     if backend == "numpy":
-        from .profile import PairProfileDP
+        from .profile import PairMergedProfileDP, PairProfileDP
         em = getattr(machine_or_dm, "em", machine_or_dm)
-        dp = PairProfileDP(em)
+        dp = PairProfileDP(em) if colTok is None else PairMergedProfileDP(em, colTok)
         post = np.zeros(P.shape, np.float64)
         ll = np.empty(n, np.float64)
         for k in range(n):
-            post[rowOff[k]:rowOff[k + 1]], ll[k] = dp.rowPosteriors(inputs[k], profiles[k], env=None if envs is None else envs[k])
+            if colTok is None:
+                post[rowOff[k]:rowOff[k + 1]], ll[k] = dp.rowPosteriors(inputs[k], profiles[k], env=None if envs is None else envs[k])
+            else:
+                post[rowOff[k]:rowOff[k + 1]], ll[k] = dp.rowPosteriors(inputs[k], profiles[k])
         return post, ll
     if backend != "device":
         raise ValueError('backend is "device" or "numpy"')
     from . import capi
     own = not isinstance(machine_or_dm, capi.DeviceMachine)
     dm = capi.DeviceMachine(machine_or_dm) if own else machine_or_dm
-    pairs = capi.DeviceProfilePairs(dm, inputs, profiles)
+    pairs = None
     try:
+        pairs = capi.DeviceProfilePairs(dm, inputs, profiles, colTok)
         if envs is not None:
             pairs.set_envelopes(envs)
-        return pairs.row_posteriors()
+        return pairs.row_posteriors() if colTok is None else pairs.merged_row_posteriors()
     finally:
-        pairs.close()
+        if pairs is not None:
+            pairs.close()
         if own:
             dm.close()
 
 
 class _PairProfileLoglike(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logP, machine_or_dm, inputs, rowOff, envs, backend):
+    def forward(ctx, logP, machine_or_dm, inputs, rowOff, envs, backend, colTok=None):
         P = np.ascontiguousarray(logP.detach().cpu().numpy(), np.float64)
-        post, ll = _row_posteriors(machine_or_dm, inputs, P, rowOff, envs, backend)
+        post, ll = _row_posteriors(machine_or_dm, inputs, P, rowOff, envs, backend, colTok)
         ctx.rowOff = rowOff
         ctx.save_for_backward(torch.from_numpy(post).to(logP.device))
         return torch.from_numpy(ll).to(logP.device)
@@ -55,16 +60,22 @@ class _PairProfileLoglike(torch.autograd.Function):
     def backward(ctx, grad_out):
         post, = ctx.saved_tensors
         rows = torch.as_tensor(np.diff(ctx.rowOff), device=post.device)
-        return torch.repeat_interleave(grad_out.to(post.dtype), rows).unsqueeze(1) * post, None, None, None, None, None
+        return torch.repeat_interleave(grad_out.to(post.dtype), rows).unsqueeze(1) * post, None, None, None, None, None, None
 
 
-def pair_profile_loglike(machine_or_dm, inputs, logP, rowOff, envs=None, backend="device"):
+def pair_profile_loglike(machine_or_dm, inputs, logP, rowOff, envs=None, backend="device", colTok=None):
     """tensor[nPairs] of log-likelihoods: pair k is the token sequence ``inputs[k]`` (1..nInTok) against the rows
     rowOff[k]..rowOff[k + 1] of ``logP``, a float64 [sumRows, nOutTok + 1] tensor of log weights with column 0 the blank.
     Differentiable in ``logP``: the gradient is grad_out[k] times the row posteriors of pair k, zeros for a pair that scores -inf
     (like zero_infinity of a CTC loss).  ``machine_or_dm``: an EvaluatedMachine or a capi.DeviceMachine (kept open for the
     caller).  ``envs``: per pair None, a seqpair.Envelope or (inStart, inEnd).  ``backend``: "device" (one
     capi.DeviceProfilePairs.row_posteriors() call) or "numpy" (profile.PairProfileDP.rowPosteriors, no GPU needed).
+
+    With ``colTok`` the profiles are CTC-merged frames: ``logP`` is [sumRows, nCols + 1], column c a frame's log weight of the
+    output token colTok[c - 1], repeats collapse and a blank separates equal symbols (docs/profile_tapes.md, "Row posteriors of
+    pairs against a merged profile").  Both backends take the merged route (capi.DeviceProfilePairs.merged_row_posteriors,
+    profile.PairMergedProfileDP.rowPosteriors); with a one-state echo transducer the result is -ctc_loss(logP, x) per pair.
+    Envelopes take plain profiles.
 
     Tensors of any device go through host memory (``.detach().cpu().numpy()``) and the results come back to the tensor's device;
     a zero-copy entry that takes device pointers is out of scope here."""
@@ -75,8 +86,14 @@ def pair_profile_loglike(machine_or_dm, inputs, logP, rowOff, envs=None, backend
         raise ValueError("rowOff has one entry per pair and one more, from 0 up to the rows of logP")
     if envs is not None and len(envs) != len(inputs):
         raise ValueError("one envelope (or None) per pair, please")
+    if colTok is not None:
+        if envs is not None:
+            raise ValueError("envelopes take plain profiles")
+        colTok = np.asarray(colTok, np.int64).reshape(-1)
+        if logP.shape[1] != len(colTok) + 1:
+            raise ValueError("merged profiles: logP has one column per entry of colTok and the blank in front")
     inputs = [np.asarray(x, np.int64).reshape(-1) for x in inputs]
-    return _PairProfileLoglike.apply(logP, machine_or_dm, inputs, rowOff, envs, backend)
+    return _PairProfileLoglike.apply(logP, machine_or_dm, inputs, rowOff, envs, backend, colTok)
 
 
 def _two_row_posteriors(machine_or_dm, A, inOff, B, rowOff, wantA, wantB, envs, backend):
