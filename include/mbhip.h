@@ -345,6 +345,24 @@ int mb_profile_two_fill_env(mb_machine *m, int mode, const double *logA, int64_t
                             const int32_t *envStart, const int32_t *envEnd, double *cellsOut);
 int64_t mb_profile_twos_cells(const mb_profile_twos *p);   /* doubles of all materialised lattices under the current envelopes */
 
+/* Pairs of profiles against a CTC-merged output profile (mb_profile_two_merge.hip; docs/profile_tapes.md, "Pairs of profiles
+ * against a merged profile"): the input profile as above, the output rows those of mb_profiles_create_merged -- logB rows of
+ * nCols + 1 doubles, column 0 the blank, column c the CSV column whose output token is colTok[c - 1], one column map per batch
+ * (checked as mb_profiles_create_merged checks it).  The semantics are those of
+ * compose(A.machine(), compose(M, transpose(mergingMachine()))) with both tapes empty.  mb_profile_twos_forward / _viterbi / _counts
+ * / _cells / _destroy and the path cap work on the object unchanged (paths in the two-profile format: edge, output row, input
+ * row; blanks of either tape and repeat rows are not edges); mb_profile_twos_set_rows takes logB rows of nCols + 1 doubles.  The
+ * lattice of a pair has nCols + 1 planes of the plain one -- cells[((((i*(nRows+1)) + row)*3 + layer)*(nCols+1) + plane)*nStates +
+ * state], plane 0 = the last row took the blank (or no row yet), plane c = it took column c; mb_profile_two_fill_merged:
+ * cellsOut[(nIn+1)*(nRows+1)*3*(nCols+1)*nStates], mode MB_FORWARD, MB_VITERBI or MB_BACKWARD.  The memory budget chunks by the
+ * lattices, the scratch rings of the pairs whose ring does not fit LDS, and the path slots; an anti-diagonal of more than 2^31
+ * (cell, plane, state) items is an error at create.  mb_profile_twos_set_envelopes fails on the object with "envelopes take plain
+ * profiles", mb_profile_twos_row_posteriors with "row posteriors take plain profiles". */
+mb_profile_twos *mb_profile_twos_create_merged(mb_machine *m, int64_t nPairs, const double *logA, const int64_t *inOff, const double *logB,
+                                               const int64_t *rowOff, int32_t nCols, const int32_t *colTok);
+int mb_profile_two_fill_merged(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, int32_t nCols,
+                               const int32_t *colTok, double *cellsOut);
+
 /* ---- prefix search: imputing the input tape (--prefix-decode / --prefix-encode / --random-encode) -------------------------------
  * The node fill of the reference's PrefixTree (src/ctc.cpp:25-88) on the device, the tree and its heap on the host
  * (docs/decoding.md).  An mb_prefix holds nSeq searches (output sequence k = outTok[outOff[k]..outOff[k+1]), tokens 1..nOutTok)

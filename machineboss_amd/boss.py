@@ -663,7 +663,7 @@ def _runProfilePairs(args, out, machine: Machine) -> int:
 
 def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "device", params=None,
                      loglike: bool = True, viterbi: bool = False, counts: bool = False, posteriors: bool = False,
-                     band: Optional[int] = None):
+                     band: Optional[int] = None, merge: bool = False):
     """Every input profile (a profile.Profile, read against the machine's input alphabet) as one pair with ``outProfile`` (a
     profile.Profile, read against its output alphabet), all pairs in one batch, on a machine with an input alphabet
     (docs/profile_tapes.md, "Pairs of profiles").  ``backend``: "device" (capi.DeviceProfileTwos) or "numpy"
@@ -674,20 +674,37 @@ def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "d
     blank; docs/profile_tapes.md, "Row posteriors of pairs of profiles") -- zeros for a pair that scores -inf; the key is absent
     when not asked for.  ``band``: every pair is swept under seqpair.Envelope.band(K, L, band), K the rows of its input profile
     and L those of ``outProfile``, on both backends (docs/profile_tapes.md, "Pairs of profiles under an envelope"); a width that
-    cannot bridge the slope raises MachineError("Envelope is not connected")."""
+    cannot bridge the slope raises MachineError("Envelope is not connected").  ``merge``: ``outProfile`` is read CTC-merged, as
+    --recognize-merge-csv reads it (docs/profile_tapes.md, "Pairs of profiles against a merged profile"; capi.DeviceProfileTwos
+    with colTok / profile.TwoMergedProfileDP); plain profiles only for ``band`` and ``posteriors``."""
     import numpy as np
     from . import dp
-    from .profile import TwoProfileDP
+    from .profile import TwoMergedProfileDP, TwoProfileDP
     from .seqpair import Envelope
     ev = EvaluatedMachine.fromMachine(machine, params)
     if not ev.nInTok:
         raise MachineError("two-profile sweeps need a machine with an input alphabet")
+    if merge and not ev.nOutTok:
+        raise MachineError("--recognize-merge-csv needs a machine with an output alphabet")
+    if band is not None and merge:
+        raise MachineError("envelopes take plain profiles")
+    if posteriors and merge:
+        raise MachineError("row posteriors take plain profiles")
     As = [a.logRowsIn(ev) for a in inProfiles]
-    B = outProfile.logRows(ev)
+    B, colTok = _mergedRows(outProfile, ev) if merge else (outProfile.logRows(ev), None)
     acc = dp.MachineCounts(ev)
     fwd = vit = post = None
     envs = [None] * len(As) if band is None else [Envelope.band(len(A), len(B), int(band)) for A in As]
-    if backend == "numpy":
+    if backend == "numpy" and merge:
+        tdp = TwoMergedProfileDP(ev, colTok)
+        fwd = [tdp.forward(A, B)[0] for A in As] if loglike else None
+        if counts:
+            for A in As:
+                c, ll = tdp.counts(A, B)
+                acc._flat += c
+                acc.loglike += ll
+        vit = [tdp.forward(A, B, "max")[0] for A in As] if viterbi else None
+    elif backend == "numpy":
         tdp = TwoProfileDP(ev)
         fwd = [tdp.forward(A, B, env=e)[0] for A, e in zip(As, envs)] if loglike else None
         if counts:
@@ -700,7 +717,7 @@ def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "d
     else:
         from . import capi
         dm = capi.DeviceMachine(ev)
-        twos = capi.DeviceProfileTwos(dm, As, [B] * len(As), envs=None if band is None else envs)
+        twos = capi.DeviceProfileTwos(dm, As, [B] * len(As), envs=None if band is None else envs, colTok=colTok)
         try:
             fwd = twos.forward(capi.MB_ROLLING) if loglike else None
             if counts:

@@ -41,6 +41,7 @@ EXPORTS = [
     "mb_profile_twos_row_posteriors", "mb_profile_twos_set_rows",
     "mb_profile_two_fill",
     "mb_profile_twos_set_envelopes", "mb_profile_two_fill_env", "mb_profile_twos_cells",
+    "mb_profile_twos_create_merged", "mb_profile_two_fill_merged",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
     "mb_prefix_node_cells", "mb_prefix_create_profiles", "mb_prefix_create_merged",
 ]
@@ -159,6 +160,9 @@ def load():
     L.mb_profile_twos_set_envelopes.argtypes = [vp, i64p, i32p, i32p]
     L.mb_profile_two_fill_env.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, i32p, i32p, dp]
     L.mb_profile_twos_cells.argtypes = [vp]; L.mb_profile_twos_cells.restype = C.c_int64
+    L.mb_profile_twos_create_merged.restype = vp
+    L.mb_profile_twos_create_merged.argtypes = [vp, C.c_int64, dp, i64p, dp, i64p, C.c_int32, i32p]
+    L.mb_profile_two_fill_merged.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int32, i32p, dp]
     L.mb_prefix_create.restype = vp
     L.mb_prefix_create.argtypes = [vp, C.c_int64, i32p, i64p, dp, C.c_int64]
     L.mb_prefix_create_profiles.restype = vp
@@ -890,11 +894,18 @@ class DeviceProfileTwos:
     is the [rows, nInTok + 1] log weights ``inProfiles[k]`` (profile.Profile.logRowsIn) against the [rows, nOutTok + 1] log weights
     ``outProfiles[k]`` (profile.Profile.logRows), column 0 of either the blank.  The yardstick is profile.TwoProfileDP
     (docs/profile_tapes.md, "Pairs of profiles").  ``envs``: what envelopes() takes (docs/profile_tapes.md, "Pairs of profiles
-    under an envelope"); the yardstick is then TwoProfileDP(env=...)."""
+    under an envelope"); the yardstick is then TwoProfileDP(env=...).  With ``colTok`` the output profiles are CTC-merged
+    (mb_profile_twos_create_merged): per pair a [rows, nCols + 1] array, column 0 the blank and column c a CSV column whose output
+    token is colTok[c - 1] (profile.Profile.mergeRows); forward, viterbi, counts, cells and set_profiles work the same and the
+    yardstick is profile.TwoMergedProfileDP (docs/profile_tapes.md, "Pairs of profiles against a merged profile").  Envelopes and
+    row posteriors take plain profiles."""
 
-    def __init__(self, dm: DeviceMachine, inProfiles, outProfiles, envs=None):
+    def __init__(self, dm: DeviceMachine, inProfiles, outProfiles, envs=None, colTok=None):
         self.dm = dm
-        wa, wb = dm.em.nInTok + 1, dm.em.nOutTok + 1
+        self.colTok = None if colTok is None else np.ascontiguousarray(np.asarray(colTok).reshape(-1), np.int32)
+        if self.colTok is not None and envs is not None:
+            raise MbError("envelopes take plain profiles")
+        wa, wb = dm.em.nInTok + 1, dm.em.nOutTok + 1 if colTok is None else len(self.colTok) + 1
         As = [np.asarray(p, np.float64).reshape(-1, wa) for p in inProfiles]
         Bs = [np.asarray(p, np.float64).reshape(-1, wb) for p in outProfiles]
         if len(As) != len(Bs):
@@ -907,8 +918,13 @@ class DeviceProfileTwos:
         self.logA = np.ascontiguousarray(np.concatenate(As + [np.zeros((1, wa))]), np.float64)
         self.logB = np.ascontiguousarray(np.concatenate(Bs + [np.zeros((1, wb))]), np.float64)
         L = load()
-        self.h = L.mb_profile_twos_create(dm.h, self.nPairs, _p(self.logA, C.c_double), _p(self.inOff, C.c_int64),
-                                          _p(self.logB, C.c_double), _p(self.rowOff, C.c_int64))
+        if self.colTok is None:
+            self.h = L.mb_profile_twos_create(dm.h, self.nPairs, _p(self.logA, C.c_double), _p(self.inOff, C.c_int64),
+                                              _p(self.logB, C.c_double), _p(self.rowOff, C.c_int64))
+        else:
+            self.h = L.mb_profile_twos_create_merged(dm.h, self.nPairs, _p(self.logA, C.c_double), _p(self.inOff, C.c_int64),
+                                                     _p(self.logB, C.c_double), _p(self.rowOff, C.c_int64), len(self.colTok),
+                                                     _p(self.colTok, C.c_int32))
         if not self.h:
             raise MbError(L.mb_last_error().decode())
         if envs is not None:
@@ -1013,6 +1029,18 @@ def profile_two_fill(dm: DeviceMachine, mode: int, logA, logB, env=None) -> np.n
         raise MbError("Envelope/sequence mismatch")
     _check(load().mb_profile_two_fill_env(dm.h, mode, _p(A, C.c_double), len(A), _p(B, C.c_double), len(B), _p(a, C.c_int32),
                                           _p(b, C.c_int32), _p(cells, C.c_double)))
+    return cells
+
+
+def profile_two_fill_merged(dm: DeviceMachine, mode: int, logA, logB, colTok) -> np.ndarray:
+    """One pair's lattice against a merged output profile, [rows of A + 1, rows of B + 1, 3, nCols + 1, nStates] (layers as
+    profile_two_fill; plane 0 = the last row took the blank, plane c = it took column c)."""
+    ct = np.ascontiguousarray(np.asarray(colTok).reshape(-1), np.int32)
+    A = np.ascontiguousarray(np.asarray(logA, np.float64).reshape(-1, dm.em.nInTok + 1))
+    B = np.ascontiguousarray(np.asarray(logB, np.float64).reshape(-1, len(ct) + 1))
+    cells = np.empty((len(A) + 1, len(B) + 1, 3, len(ct) + 1, dm.nStates), np.float64)
+    _check(load().mb_profile_two_fill_merged(dm.h, mode, _p(A, C.c_double), len(A), _p(B, C.c_double), len(B), len(ct),
+                                             _p(ct, C.c_int32), _p(cells, C.c_double)))
     return cells
 
 

@@ -1,6 +1,6 @@
 // mb_profile_api.hip -- the C-ABI of the profile tapes (include/mbhip.h, docs/profile_tapes.md): one-tape profiles (mb_profiles, plain
 // and CTC-merged), sequence-against-profile pairs (mb_profile_pairs, plain, merged and under envelopes) and two-profile pairs
-// (mb_profile_twos, plain and under envelopes).
+// (mb_profile_twos, plain, merged and under envelopes).
 //
 // Host orchestration only, like mb_api.hip.  Each family has Forward, Viterbi, counts, row posteriors, set_rows and a single-lattice
 // fill; what those calls share with the token batch calls -- the chunk loop, the call-scoped device buffers, the count tail -- is in
@@ -22,6 +22,7 @@
 #include "mb_profile_post.h"
 #include "mb_profile_two.h"
 #include "mb_profile_two_env.h"
+#include "mb_profile_two_merge.h"
 
 namespace mb {
 
@@ -1014,17 +1015,24 @@ static long long pt_in(const mb_profile_twos *p, long long k) { return p->inOff[
 static long long pt_rows(const mb_profile_twos *p, long long k) { return p->rowOff[k + 1] - p->rowOff[k]; }
 // cells (of three layers of S states) of pair k's materialised lattice: the rectangle, or the compact lattice under the envelopes
 static long long pt_ncells(const mb_profile_twos *p, long long k) { return p->hasEnv ? p->envCells[(size_t)k] : (pt_in(p, k) + 1) * (pt_rows(p, k) + 1); }
-static long long pt_cells(const mb_profile_twos *p, long long k) { return pt_ncells(p, k) * 3 * (long long)p->m->S; }
+static long long pt_cells(const mb_profile_twos *p, long long k) { return pt_ncells(p, k) * 3 * (long long)p->m->S * (p->nCols + 1); }
 static double pt_cell_bytes(const mb_profile_twos *p, long long k) { return 8.0 * (double)pt_cells(p, k); }
-// the ring of pair k's rolling sweep and its dynamic LDS (0: a slice of the global scratch buffer)
-static long long pt_ring(const mb_profile_twos *p, long long k) {
+// The ring of pair k's sweep and its dynamic LDS (0: a slice of the global scratch buffer).  Plain profiles: the rolling sweep alone
+// has one.  Merged: the materialised sweeps keep their exclusion vectors in one too (mb_profile_two_merge.h).
+static long long pt_ring(const mb_profile_twos *p, long long k, bool rolling) {
+  if (p->nCols) return profile_two_merge_ring(p->m->S, p->nCols, pt_in(p, k), pt_rows(p, k), !rolling);
+  if (!rolling) return 0;
   return p->hasEnv ? profile_two_env_ring(p->m->S, p->envM[(size_t)k]) : profile_two_ring(p->m->S, pt_in(p, k), pt_rows(p, k));
 }
-static size_t pt_ring_lds(const mb_profile_twos *p, long long k) {
+static size_t pt_ring_lds(const mb_profile_twos *p, long long k, bool rolling) {
+  if (p->nCols) return profile_two_merge_lds_bytes(p->m->S, p->nCols, pt_in(p, k), pt_rows(p, k), !rolling);
+  if (!rolling) return 0;
   return p->hasEnv ? profile_two_env_lds_bytes(p->m->S, p->envM[(size_t)k]) : profile_two_lds_bytes(p->m->S, pt_in(p, k), pt_rows(p, k));
 }
-// bytes of global scratch the rolling sweep of pair k needs (0: its ring is in LDS)
-static double pt_ring_bytes(const mb_profile_twos *p, long long k) { return pt_ring_lds(p, k) ? 0.0 : 8.0 * (double)pt_ring(p, k); }
+// bytes of global scratch the sweep of pair k needs (0: its ring is in LDS, or it has none)
+static double pt_ring_bytes(const mb_profile_twos *p, long long k, bool rolling) { return pt_ring_lds(p, k, rolling) ? 0.0 : 8.0 * (double)pt_ring(p, k, rolling); }
+static long long pt_width(const mb_profile_twos *p) { return p->nCols ? p->nCols + 1 : p->m->nOut + 1; }   // doubles of an output row
+static MergeMap pt_map(const mb_profile_twos *p) { return MergeMap{p->nCols, p->d_colTok}; }
 static long long pt_path_bound(const mb_profile_twos *p, long long k) { return profile_pair_path_bound(p->m->nLevF, pt_in(p, k), pt_rows(p, k)); }
 
 // No call mixes geometries: without envelopes every pair has a PairProfDesc in d, with them every pair a TwoEnvDesc in e (a pair
@@ -1035,7 +1043,7 @@ struct TwoProfPlan {
   size_t lds = 0;
 };
 
-// descriptors of pairs [p0, p1): lattices, traceback slots and (rolling) scratch rings packed from 0
+// descriptors of pairs [p0, p1): lattices, traceback slots and scratch rings (rolling; merged: the materialised sweeps' too) packed from 0
 static int two_profile_descs(const mb_profile_twos *p, long long p0, long long p1, bool rolling, TwoProfPlan &pl) {
   std::vector<PairProfDesc> h;
   std::vector<TwoEnvDesc> he;
@@ -1045,10 +1053,10 @@ static int two_profile_descs(const mb_profile_twos *p, long long p0, long long p
     TwoEnvDesc d;      // (without envelopes its PairProfDesc part alone is kept)
     d.inBase = p->inOff[k]; d.rowBase = p->rowOff[k]; d.nIn = (int)K; d.nRows = (int)L;
     d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = -1;
-    if (rolling) {
-      const size_t lds = pt_ring_lds(p, k);
+    if (pt_ring(p, k, rolling)) {
+      const size_t lds = pt_ring_lds(p, k, rolling);
       if (lds) pl.lds = std::max(pl.lds, lds);
-      else { d.ringBase = pl.ring; pl.ring += pt_ring(p, k); }
+      else { d.ringBase = pl.ring; pl.ring += pt_ring(p, k, rolling); }
     }
     pl.cells += pt_cells(p, k);
     pl.paths += pt_path_bound(p, k);
@@ -1058,7 +1066,7 @@ static int two_profile_descs(const mb_profile_twos *p, long long p0, long long p
       pl.maxItems = std::max(pl.maxItems, (long long)d.M * S);
       he.push_back(d);
     } else {
-      pl.maxItems = std::max(pl.maxItems, (std::min(K, L) + 1) * S);
+      pl.maxItems = std::max(pl.maxItems, (std::min(K, L) + 1) * S * (p->nCols + 1));
       h.push_back(d);
     }
   }
@@ -1078,17 +1086,21 @@ static TwoEnvTables pt_env_tables(const mb_profile_twos *p) {
   t.colStart = p->d_colStart; t.colEnd = p->d_colEnd; t.colOff = p->d_colOff;
   return t;
 }
-// The one place where the two geometries part: the launches of a chunk of np pairs and the names they report.
+// The one place where the two geometries and the merged kernels part: the launches of a chunk of np pairs and the names they
+// report.  scratch: the chunk's rings that did not fit LDS (plain: the rolling sweep's alone).
 static int pt_fwd(const mb_profile_twos *p, int mode, bool mat, const TwoProfPlan &pl, long long np, double *pool, double *scratch, double *ll) {
+  if (p->nCols) return launch_profile_two_merge_fwd(p->m, pt_map(p), mode, mat, pl.d.p, (int)np, pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, scratch, ll, g_stream);
   if (p->hasEnv) return launch_profile_two_fwd(p->m, mode, mat, pl.e.p, pt_env_tables(p), (int)np, mat ? 0 : pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, mat ? nullptr : scratch, ll, g_stream);
   return launch_profile_two_fwd(p->m, mode, mat, pl.d.p, (int)np, mat ? 0 : pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, mat ? nullptr : scratch, ll, g_stream);
 }
-static int pt_fwd_mat(const mb_profile_twos *p, int mode, const TwoProfPlan &pl, long long np, double *pool, double *ll) { return pt_fwd(p, mode, true, pl, np, pool, nullptr, ll); }
-static int pt_bwd(const mb_profile_twos *p, const TwoProfPlan &pl, long long np, double *pool, double *ll) {
+static int pt_fwd_mat(const mb_profile_twos *p, int mode, const TwoProfPlan &pl, long long np, double *pool, double *scratch, double *ll) { return pt_fwd(p, mode, true, pl, np, pool, scratch, ll); }
+static int pt_bwd(const mb_profile_twos *p, const TwoProfPlan &pl, long long np, double *pool, double *scratch, double *ll) {
+  if (p->nCols) return launch_profile_two_merge_bwd(p->m, pt_map(p), pl.d.p, (int)np, pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, scratch, ll, g_stream);
   if (p->hasEnv) return launch_profile_two_bwd(p->m, pl.e.p, pt_env_tables(p), (int)np, pl.maxItems, p->d_logA, p->d_logB, pool, ll, g_stream);
   return launch_profile_two_bwd(p->m, pl.d.p, (int)np, pl.maxItems, p->d_logA, p->d_logB, pool, ll, g_stream);
 }
 static int pt_counts(const mb_profile_twos *p, const TwoProfPlan &pl, long long np, int groups, const double *fwd, const double *bwd, double *cc) {
+  if (p->nCols) return launch_profile_two_merge_counts(p->m, pt_map(p), pl.d.p, (int)np, groups, p->d_logA, p->d_logB, fwd, bwd, cc, g_stream);
   if (p->hasEnv) return launch_profile_two_counts(p->m, pl.e.p, pt_env_tables(p), (int)np, groups, p->d_logA, p->d_logB, fwd, bwd, cc, g_stream);
   return launch_profile_two_counts(p->m, pl.d.p, (int)np, groups, p->d_logA, p->d_logB, fwd, bwd, cc, g_stream);
 }
@@ -1097,6 +1109,7 @@ static int pt_rowpost(const mb_profile_twos *p, int axis, const TwoProfPlan &pl,
   return launch_profile_two_rowpost(p->m, axis, pl.d.p, (int)np, groups, tabMax, p->d_logA, p->d_logB, fwd, bwd, post, g_stream);
 }
 static int pt_traceback(const mb_profile_twos *p, const TwoProfPlan &pl, long long np, const double *pool, uint32_t *e, int32_t *r, int32_t *i, long long *len) {
+  if (p->nCols) return launch_profile_two_merge_traceback(p->m, pt_map(p), pl.d.p, (int)np, p->d_logA, p->d_logB, pool, e, r, i, len, g_stream);
   if (p->hasEnv) return launch_profile_two_traceback(p->m, pl.e.p, pt_env_tables(p), (int)np, p->d_logA, p->d_logB, pool, e, r, i, len, g_stream);
   return launch_profile_two_traceback(p->m, pl.d.p, (int)np, p->d_logA, p->d_logB, pool, e, r, i, len, g_stream);
 }
@@ -1104,9 +1117,11 @@ static int pt_traceback(const mb_profile_twos *p, const TwoProfPlan &pl, long lo
 static const char *pt_fwd_name(const mb_profile_twos *p, int mode, bool mat) {
   static const char *const names[2][2][2] = {{{"k_profile_two_fwd<sum,rolling>", "k_profile_two_fwd<sum,mat>"}, {"k_profile_two_fwd<max,rolling>", "k_profile_two_fwd<max,mat>"}},
                                              {{"k_profile_two_env_fwd<sum,rolling>", "k_profile_two_env_fwd<sum,mat>"}, {"k_profile_two_env_fwd<max,rolling>", "k_profile_two_env_fwd<max,mat>"}}};
+  static const char *const merged[2][2] = {{"k_profile_two_merge_fwd<sum,rolling>", "k_profile_two_merge_fwd<sum,mat>"}, {"k_profile_two_merge_fwd<max,rolling>", "k_profile_two_merge_fwd<max,mat>"}};
+  if (p->nCols) return merged[mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
   return names[p->hasEnv ? 1 : 0][mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
 }
-static const char *pt_name(const mb_profile_twos *p, const char *plain, const char *env) { return p->hasEnv ? env : plain; }
+static const char *pt_name(const mb_profile_twos *p, const char *plain, const char *env, const char *merged) { return p->nCols ? merged : (p->hasEnv ? env : plain); }
 
 // ---- envelopes of the two-profile pairs (mb_profile_two_env.h, docs/profile_tapes.md "Pairs of profiles under an envelope") ----
 static void pt_env_free(mb_profile_twos *p) {
@@ -1127,6 +1142,7 @@ static int profile_twos_set_envelopes(mb_profile_twos *p, const int64_t *envOff,
   if (!envOff) return 0;
   const long long total = envOff[p->n] - envOff[0];
   if (!total) return 0;
+  if (p->nCols) { set_error("envelopes take plain profiles"); return 1; }
   if (!inStart || !inEnd) { set_error("null argument"); return 1; }
   EnvHost h(p->n);
   std::vector<long long> colBase((size_t)p->n, 0), cOff;
@@ -1162,7 +1178,7 @@ static int profile_twos_set_envelopes(mb_profile_twos *p, const int64_t *envOff,
 // Forward (MB_FORWARD) or Viterbi scores without paths (MB_VITERBI); mat: through the materialised lattice
 static int two_profile_scores(mb_profile_twos *p, int mode, bool mat, double *loglike) {
   std::vector<Chunk> chunks;
-  if (!lattice_chunks(p->n, "pair", [&](long long k) { return mat ? pt_cell_bytes(p, k) : pt_ring_bytes(p, k); }, chunks)) return 1;
+  if (!lattice_chunks(p->n, "pair", [&](long long k) { return (mat ? pt_cell_bytes(p, k) : 0.0) + pt_ring_bytes(p, k, !mat); }, chunks)) return 1;
   SmBuf<double> d_ll;
   MB_HIP(d_ll.alloc(p->n));
   int rc = for_chunks<TwoProfPlan>(chunks, pt_build(p, !mat), [&](const Chunk &c, TwoProfPlan &pl, Timer &tm) {
@@ -1190,32 +1206,47 @@ static long long pt_rowpost_groups(const mb_profile_twos *p, long long p0, long 
 
 extern "C" {
 
-mb_profile_twos *mb_profile_twos_create(mb_machine *m, int64_t nPairs, const double *logA, const int64_t *inOff, const double *logB, const int64_t *rowOff) {
-  ApiGuard guard;
+// nCols > 0: CTC-merged output profiles, rows of nCols + 1 doubles and the column map colTok (checked by the caller)
+static mb_profile_twos *profile_twos_create(mb_machine *m, int64_t nPairs, const double *logA, const int64_t *inOff, const double *logB, const int64_t *rowOff,
+                                            int32_t nCols, const int32_t *colTok) {
   if (!m || nPairs < 0 || (nPairs > 0 && (!rowOff || !inOff))) { set_error("null argument"); return nullptr; }
   if (!m->nIn) { set_error("two-profile sweeps need a machine with an input alphabet"); return nullptr; }
   if (ensure_init()) return nullptr;
   mb_profile_twos *p = new mb_profile_twos();
-  p->m = m; p->n = nPairs;
+  p->m = m; p->n = nPairs; p->nCols = nCols;
   p->rowOff.assign((size_t)nPairs + 1, 0); p->inOff.assign((size_t)nPairs + 1, 0);
   for (long long k = 0; k < nPairs; ++k) {
     const long long L = rowOff[k + 1] - rowOff[k], K = inOff[k + 1] - inOff[k];
     if (L < 0 || L > 0x3fffffff || K < 0 || K > 0x3fffffff) { set_error("bad pair offsets"); delete p; return nullptr; }
-    if ((double)(std::min(K, L) + 1) * m->S > 2147483647.0) { set_error("pair " + std::to_string(k) + ": an anti-diagonal of the lattice has more than 2^31 cells"); delete p; return nullptr; }
+    if ((double)(std::min(K, L) + 1) * m->S * (nCols + 1) > 2147483647.0) { set_error("pair " + std::to_string(k) + ": an anti-diagonal of the lattice has more than 2^31 cells"); delete p; return nullptr; }
     p->rowOff[(size_t)k + 1] = p->rowOff[(size_t)k] + L;
     p->inOff[(size_t)k + 1] = p->inOff[(size_t)k] + K;
   }
   p->totalRows = p->rowOff.back(); p->totalIn = p->inOff.back();
-  const long long C = m->nOut + 1, CA = m->nIn + 1, nb = p->totalRows * C, na = p->totalIn * CA;
+  const long long C = pt_width(p), CA = m->nIn + 1, nb = p->totalRows * C, na = p->totalIn * CA;
   const double *b0 = logB ? logB + (nPairs ? rowOff[0] * C : 0) : nullptr;
   const double *a0 = logA ? logA + (nPairs ? inOff[0] * CA : 0) : nullptr;
   if ((nb && !b0) || (na && !a0)) { set_error("null argument"); delete p; return nullptr; }
   if (!profile_values_ok(a0, na) || !profile_values_ok(b0, nb)) { delete p; return nullptr; }
   if (!hip_ok(hipMalloc((void **)&p->d_logB, (size_t)std::max<long long>(nb, 1) * sizeof(double)), "hipMalloc(output profiles)") ||
       !hip_ok(hipMalloc((void **)&p->d_logA, (size_t)std::max<long long>(na, 1) * sizeof(double)), "hipMalloc(input profiles)")) { mb_profile_twos_destroy(p); return nullptr; }
+  if (nCols && (!hip_ok(hipMalloc((void **)&p->d_colTok, (size_t)nCols * sizeof(int)), "hipMalloc(column map)") ||
+                !hip_ok(hipMemcpyAsync(p->d_colTok, colTok, (size_t)nCols * sizeof(int), hipMemcpyHostToDevice, g_stream), "H2D column map"))) { mb_profile_twos_destroy(p); return nullptr; }
   if ((nb && h2d_large(p->d_logB, b0, (size_t)nb * sizeof(double))) || (na && h2d_large(p->d_logA, a0, (size_t)na * sizeof(double))) ||
       !hip_ok(hipStreamSynchronize(g_stream), "H2D profiles")) { mb_profile_twos_destroy(p); return nullptr; }
   return p;
+}
+
+mb_profile_twos *mb_profile_twos_create(mb_machine *m, int64_t nPairs, const double *logA, const int64_t *inOff, const double *logB, const int64_t *rowOff) {
+  ApiGuard guard;
+  return profile_twos_create(m, nPairs, logA, inOff, logB, rowOff, 0, nullptr);
+}
+
+mb_profile_twos *mb_profile_twos_create_merged(mb_machine *m, int64_t nPairs, const double *logA, const int64_t *inOff, const double *logB, const int64_t *rowOff,
+                                               int32_t nCols, const int32_t *colTok) {
+  ApiGuard guard;
+  if (!merge_map_ok(m, nCols, colTok)) return nullptr;
+  return profile_twos_create(m, nPairs, logA, inOff, logB, rowOff, nCols, colTok);
 }
 
 void mb_profile_twos_destroy(mb_profile_twos *p) {
@@ -1223,6 +1254,7 @@ void mb_profile_twos_destroy(mb_profile_twos *p) {
   if (!p) return;
   if (p->d_logA) (void)hipFree(p->d_logA);
   if (p->d_logB) (void)hipFree(p->d_logB);
+  if (p->d_colTok) (void)hipFree(p->d_colTok);
   pt_env_free(p);
   delete p;
 }
@@ -1257,7 +1289,7 @@ int mb_profile_twos_viterbi(mb_profile_twos *p, double *loglike, int64_t *pathOf
   for (long long k = 0; k < p->n; ++k) need += pt_path_bound(p, k);
   if (pathCap < need) { set_error("pathCap too small for the Viterbi paths: " + std::to_string((long long)pathCap) + " entries, the path bounds of the pairs sum to " + std::to_string(need)); return 1; }
   std::vector<Chunk> chunks;
-  if (!lattice_chunks(p->n, "pair", [&](long long k) { return pt_cell_bytes(p, k) + 12.0 * pt_path_bound(p, k); }, chunks)) return 1;
+  if (!lattice_chunks(p->n, "pair", [&](long long k) { return pt_cell_bytes(p, k) + pt_ring_bytes(p, k, false) + 12.0 * pt_path_bound(p, k); }, chunks)) return 1;
   SmBuf<double> d_ll;
   SmBuf<long long> d_len;
   MB_HIP(d_ll.alloc(p->n));
@@ -1270,10 +1302,11 @@ int mb_profile_twos_viterbi(mb_profile_twos *p, double *loglike, int64_t *pathOf
     uint32_t *d_e = ws_array<uint32_t>(3, pl.paths);
     int32_t *d_r = ws_array<int32_t>(4, pl.paths);
     int32_t *d_i = ws_array<int32_t>(5, pl.paths);
-    if (!pool || !d_e || !d_r || !d_i) return 1;
+    double *scratch = pl.ring ? (double *)ws_get(1, (size_t)pl.ring * sizeof(double)) : nullptr;
+    if (!pool || !d_e || !d_r || !d_i || (pl.ring && !scratch)) return 1;
     {
       Timed t(tm, 1);
-      if (pt_fwd_mat(p, MB_VITERBI, pl, np, pool, d_ll + c.p0) || pt_traceback(p, pl, np, pool, d_e, d_r, d_i, d_len + c.p0)) return 1;
+      if (pt_fwd_mat(p, MB_VITERBI, pl, np, pool, scratch, d_ll + c.p0) || pt_traceback(p, pl, np, pool, d_e, d_r, d_i, d_len + c.p0)) return 1;
     }
     return unpack_paths(out, c.p0, np, pl.paths, nullptr, d_len + c.p0, d_e, d_r, d_i);
   });
@@ -1289,7 +1322,7 @@ int mb_profile_twos_counts(mb_profile_twos *p, double *counts, double *loglikeSu
   latch_deterministic();
   const long long nT = p->m->nTrans;
   std::vector<Chunk> chunks;
-  if (!lattice_chunks(p->n, "pair", [&](long long k) { return 2.0 * pt_cell_bytes(p, k); }, chunks)) return 1;   // the Forward and the Backward lattice
+  if (!lattice_chunks(p->n, "pair", [&](long long k) { return 2.0 * pt_cell_bytes(p, k) + pt_ring_bytes(p, k, false); }, chunks)) return 1;   // the Forward and the Backward lattice
   SmBuf<double> d_ll, d_bll, d_cc;
   MB_HIP(d_ll.alloc(p->n));
   if (!hip_ok(d_bll.alloc(p->n), "hipMalloc(loglike)") || !hip_ok(d_cc.alloc(nT), "hipMalloc(counts)")) return 1;
@@ -1298,12 +1331,14 @@ int mb_profile_twos_counts(mb_profile_twos *p, double *counts, double *loglikeSu
     const long long np = c.p1 - c.p0;
     double *fwd = ws_array<double>(0, pl.cells);
     double *bwd = ws_array<double>(1, pl.cells);
-    if (!fwd || !bwd) return 1;
+    double *scratch = pl.ring ? (double *)ws_get(2, (size_t)pl.ring * sizeof(double)) : nullptr;
+    if (!fwd || !bwd || (pl.ring && !scratch)) return 1;
     const int groups = count_groups(c.p0, c.p1, [&](long long k) { return pt_cells(p, k) / 3; });
     if (np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); return 1; }
     {
       Timed t(tm, 1);
-      if (pt_fwd_mat(p, MB_FORWARD, pl, np, fwd, d_ll + c.p0) || pt_bwd(p, pl, np, bwd, d_bll + c.p0)) return 1;
+      // (merged: the Backward's ring follows the Forward's on the stream, one scratch buffer serves both)
+      if (pt_fwd_mat(p, MB_FORWARD, pl, np, fwd, scratch, d_ll + c.p0) || pt_bwd(p, pl, np, bwd, scratch, d_bll + c.p0)) return 1;
       if (nT && !hip_ok(hipMemsetAsync(d_cc, 0, (size_t)nT * sizeof(double), g_stream), "memset(counts)")) return 1;
       if (pt_counts(p, pl, np, groups, fwd, bwd, d_cc)) return 1;
     }
@@ -1311,7 +1346,7 @@ int mb_profile_twos_counts(mb_profile_twos *p, double *counts, double *loglikeSu
   });
   std::vector<double> hll((size_t)p->n);
   if (!rc) rc = fetch_loglike(hll.data(), d_ll, p->n);
-  g_last_kernel = pt_name(p, "k_profile_two_counts", "k_profile_two_env_counts");
+  g_last_kernel = pt_name(p, "k_profile_two_counts", "k_profile_two_env_counts", "k_profile_two_merge_counts");
   if (rc) return rc;
   sum.finish(hll, counts, loglikeSum, loglike);
   return 0;
@@ -1320,6 +1355,7 @@ int mb_profile_twos_counts(mb_profile_twos *p, double *counts, double *loglikeSu
 int mb_profile_twos_row_posteriors(mb_profile_twos *p, double *postA, double *postB, double *loglike) {
   ApiGuard guard;
   if (!p) { set_error("null argument"); return 1; }
+  if (p->nCols) { set_error("row posteriors take plain profiles"); return 1; }
   g_last_ms = 0.0; g_last_launches = 0;
   latch_deterministic();
   const mb_machine *m = p->m;
@@ -1341,7 +1377,7 @@ int mb_profile_twos_row_posteriors(mb_profile_twos *p, double *postA, double *po
     if (np * std::max(groupsA, groupsB) > 0x7fffffff) { set_error("too many pairs in one chunk"); return 1; }
     {
       Timed t(tm, 1);
-      if (pt_fwd_mat(p, MB_FORWARD, pl, np, fwd, d_ll + c.p0) || pt_bwd(p, pl, np, bwd, d_bll + c.p0)) return 1;
+      if (pt_fwd_mat(p, MB_FORWARD, pl, np, fwd, nullptr, d_ll + c.p0) || pt_bwd(p, pl, np, bwd, nullptr, d_bll + c.p0)) return 1;
       if (postB && pt_rowpost(p, 0, pl, np, (int)groupsB, tabMax, fwd, bwd, d_pb)) return 1;
       if (postA && pt_rowpost(p, 1, pl, np, (int)groupsA, tabMax, fwd, bwd, d_pa)) return 1;
     }
@@ -1350,26 +1386,26 @@ int mb_profile_twos_row_posteriors(mb_profile_twos *p, double *postA, double *po
   if (!rc) rc = fetch_posteriors(postA, d_pa, na);
   if (!rc) rc = fetch_posteriors(postB, d_pb, nb);
   if (!rc && loglike) rc = fetch_loglike(loglike, d_ll, p->n);
-  g_last_kernel = pt_name(p, "k_profile_two_rowpost", "k_profile_two_env_rowpost");
+  g_last_kernel = p->hasEnv ? "k_profile_two_env_rowpost" : "k_profile_two_rowpost";
   return rc;
 }
 
 int mb_profile_twos_set_rows(mb_profile_twos *p, const double *logA, const double *logB) {
   ApiGuard guard;
   if (!p) { set_error("null argument"); return 1; }
-  const long long na = logA ? p->totalIn * (p->m->nIn + 1) : 0, nb = logB ? p->totalRows * (p->m->nOut + 1) : 0;
+  const long long na = logA ? p->totalIn * (p->m->nIn + 1) : 0, nb = logB ? p->totalRows * pt_width(p) : 0;
   if (!profile_values_ok(logA, na) || !profile_values_ok(logB, nb)) return 1;      // (before either copy: a refused table leaves both in effect)
   if ((na && h2d_large(p->d_logA, logA, (size_t)na * sizeof(double))) || (nb && h2d_large(p->d_logB, logB, (size_t)nb * sizeof(double)))) return 1;
   return hip_ok(hipStreamSynchronize(g_stream), "H2D profiles") ? 0 : 1;
 }
 
-static int profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, const int32_t *envStart,
-                            const int32_t *envEnd, double *cellsOut) {
+static int profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, int32_t nCols,
+                            const int32_t *colTok, const int32_t *envStart, const int32_t *envEnd, double *cellsOut) {
   if (!m || !cellsOut || nRows < 0 || nIn < 0 || (nRows && !logB) || (nIn && !logA)) { set_error("null argument"); return 1; }
   if (!fill_mode_ok(mode)) return 1;
   g_last_ms = 0.0; g_last_launches = 0;
   const int64_t rOff[2] = {0, nRows}, iOff[2] = {0, nIn};
-  mb_profile_twos *p = mb_profile_twos_create(m, 1, logA, iOff, logB, rOff);
+  mb_profile_twos *p = profile_twos_create(m, 1, logA, iOff, logB, rOff, nCols, colTok);
   if (!p) return 1;
   const bool env = envStart && envEnd;
   if (env) {
@@ -1377,14 +1413,14 @@ static int profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t
     if (profile_twos_set_envelopes(p, eOff, envStart, envEnd)) { mb_profile_twos_destroy(p); return 1; }
   }
   std::vector<Chunk> chunks;
-  if (!lattice_chunks(1, "pair", [&](long long k) { return pt_cell_bytes(p, k); }, chunks)) { mb_profile_twos_destroy(p); return 1; }
+  if (!lattice_chunks(1, "pair", [&](long long k) { return pt_cell_bytes(p, k) + pt_ring_bytes(p, k, false); }, chunks)) { mb_profile_twos_destroy(p); return 1; }
   int rc;
   {
     TwoProfPlan pl;
     rc = two_profile_descs(p, 0, 1, false, pl);
     std::vector<double> compact(!rc && env ? (size_t)pl.cells : 0);      // under an envelope the lattice comes back compact
-    if (!rc) rc = fill_one(pl.cells, 0, env ? compact.data() : cellsOut, [&](double *pool, double *, double *d_ll) {
-      return mode == MB_BACKWARD ? pt_bwd(p, pl, 1, pool, d_ll) : pt_fwd_mat(p, mode, pl, 1, pool, d_ll);
+    if (!rc) rc = fill_one(pl.cells, pl.ring, env ? compact.data() : cellsOut, [&](double *pool, double *scratch, double *d_ll) {
+      return mode == MB_BACKWARD ? pt_bwd(p, pl, 1, pool, scratch, d_ll) : pt_fwd_mat(p, mode, pl, 1, pool, scratch, d_ll);
     });
     if (!rc && env) {      // the compact lattice into the full rectangle, -inf outside the envelope
       const size_t cellD = 3 * (size_t)m->S;
@@ -1395,21 +1431,28 @@ static int profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t
           std::memcpy(cellsOut + ((size_t)i * (size_t)(nRows + 1) + (size_t)r) * cellD, compact.data() + at, cellD * sizeof(double));
     }
   }
-  g_last_kernel = mode == MB_BACKWARD ? pt_name(p, "k_profile_two_bwd", "k_profile_two_env_bwd") : pt_fwd_name(p, mode, true);
+  g_last_kernel = mode == MB_BACKWARD ? pt_name(p, "k_profile_two_bwd", "k_profile_two_env_bwd", "k_profile_two_merge_bwd") : pt_fwd_name(p, mode, true);
   mb_profile_twos_destroy(p);
   return rc;
 }
 
 int mb_profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, double *cellsOut) {
   ApiGuard guard;
-  return profile_two_fill(m, mode, logA, nIn, logB, nRows, nullptr, nullptr, cellsOut);
+  return profile_two_fill(m, mode, logA, nIn, logB, nRows, 0, nullptr, nullptr, nullptr, cellsOut);
+}
+
+int mb_profile_two_fill_merged(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, int32_t nCols,
+                               const int32_t *colTok, double *cellsOut) {
+  ApiGuard guard;
+  if (!merge_map_ok(m, nCols, colTok)) return 1;
+  return profile_two_fill(m, mode, logA, nIn, logB, nRows, nCols, colTok, nullptr, nullptr, cellsOut);
 }
 
 int mb_profile_two_fill_env(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, const int32_t *envStart,
                             const int32_t *envEnd, double *cellsOut) {
   ApiGuard guard;
   if ((envStart == nullptr) != (envEnd == nullptr)) { set_error("null argument"); return 1; }
-  return profile_two_fill(m, mode, logA, nIn, logB, nRows, envStart, envEnd, cellsOut);
+  return profile_two_fill(m, mode, logA, nIn, logB, nRows, 0, nullptr, envStart, envEnd, cellsOut);
 }
 
 }  // extern "C"

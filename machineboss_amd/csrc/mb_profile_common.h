@@ -1,5 +1,5 @@
 // mb_profile_common.h -- what the profile sweeps share (mb_profile.hip, mb_profile_merge.hip, mb_profile_pair.hip,
-// mb_profile_pair_merge.hip, mb_profile_two.hip, mb_profile_post.hip): the reduction of a sweep's mode, the LDS a ring may take, the lanes of a workgroup, the
+// mb_profile_pair_merge.hip, mb_profile_two.hip, mb_profile_two_merge.hip, mb_profile_post.hip): the reduction of a sweep's mode, the LDS a ring may take, the lanes of a workgroup, the
 // accumulator of the posterior counts and the add of the row posteriors.  Device code: included by .hip files only.
 #pragma once
 #include <algorithm>

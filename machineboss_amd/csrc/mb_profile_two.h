@@ -42,8 +42,10 @@ struct mb_profile_twos {
   mb_machine *m = nullptr;
   long long n = 0, totalRows = 0, totalIn = 0;
   std::vector<long long> rowOff, inOff;   // [n+1], rebased to 0: rows of the output / the input profiles
-  double *d_logB = nullptr;               // [totalRows * (nOut+1)]
+  double *d_logB = nullptr;               // [totalRows * (nOut+1)]; merged: [totalRows * (nCols+1)]
   double *d_logA = nullptr;               // [totalIn * (nIn+1)]
+  int nCols = 0;                          // > 0: CTC-merged output profiles (mb_profile_two_merge.h); they take no envelopes
+  int *d_colTok = nullptr;                // [nCols] output token of column c at [c - 1]
   // envelopes (mb_profile_twos_set_envelopes, mb_profile_two_env.h): with hasEnv EVERY pair runs the envelope geometry, a pair
   // that was given none under the full envelope
   bool hasEnv = false;

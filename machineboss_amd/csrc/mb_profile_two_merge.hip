@@ -1,0 +1,522 @@
+// mb_profile_two_merge.hip -- Forward / Backward / Viterbi / posterior counts of a machine WITH an input alphabet between an input
+// PROFILE A of K rows and a CTC-MERGED output profile B of L rows: the semantics of
+// compose(A.machine(), compose(M, transpose(CSVProfile::mergingMachine()))) with both tapes empty, restated in docs/profile_tapes.md
+// ("Pairs of profiles against a merged profile"):
+//
+//   XW[i][r][c][s] = (+)_{k != c} W[i][r][k][s]          XZ[i][r][c][s] = (+)_{k != c} Z[i][r][k][s]      (the exclusion vectors)
+//   N[i][r][0][d]  = [i = 0, r = 0, d = 0]  (+)  (+)_p (N[i][r-1][p][d] + B[r-1][0])                        (output blank; r > 0)
+//   N[i][r][c][d]  = (N[i][r-1][c][d] + B[r-1][c])                                                          (repeat; r > 0)
+//                    (+) sum_{t: s->d, in = a,   out = colTok[c]} ((XZ[i-1][r-1][c][s] + w_t) + A[i-1][a]) + B[r-1][c]   (match)
+//                    (+) sum_{t: s->d, in = eps, out = colTok[c]} (XW[i][r-1][c][s] + w_t) + B[r-1][c]                   (output-only)
+//   W[i][r][p][d]  = N[i][r][p][d]
+//                    (+) sum_{t: in = a, out = eps} (Z[i-1][r][p][s] + w_t) + A[i-1][a]                     (input-only; same plane)
+//                    (+) sum_{silent t, s < d}      W[i][r][p][s] + w_t                                     (silent levels, per plane)
+//   Z[i][r][p][d]  = W[i][r][p][d]  (+)  Z[i-1][r][p][d] + A[i-1][0]                                        (input blank; same plane)
+//   loglike        = (+)_p Z[K][L][p][S-1]
+//
+// The anti-diagonal sweep of mb_profile_pair_merge.hip with the third layer and the all-input-token edge loops of mb_profile_two.hip
+// (for a destination q the CSR rows q*K + a*C + o) and two exclusion vectors: the match edges leave the committed stage (XZ), the
+// output-only edges the waiting stage (XW).  One workgroup per pair; the work items of a diagonal are (cell, plane, state).  Per
+// diagonal: one phase for N and the non-silent part of W -- the item that finishes a state's W writes its Z -- and a barrier, one
+// barrier per silent level, and one phase and barrier that forms XW and XZ, so that no edge loop runs over planes --
+// (K + L + 1)(nLevF + 1) barriers per pair.  The rolling sweeps keep a ring of three diagonals of N, W, Z, XW and XZ,
+// 3 (5 nCols + 3)(min(K, L) + 1) S doubles, in LDS when that fits 160 KiB, else in the pair's slice of a global scratch buffer; the
+// materialised ones keep only XW and XZ there.  Cells are fp64, the sums the exact log-sum-exp.
+#include "mb_profile_common.h"
+#include "mb_profile_two_merge.h"
+
+namespace mb {
+
+size_t profile_two_merge_lds_bytes(int S, int nCols, long long nIn, long long nRows, bool mat) {
+  const double b = (double)profile_two_merge_ring(S, nCols, nIn, nRows, mat) * sizeof(double);
+  return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
+}
+
+// Where cell (i, r) lives.  at(i, r, layer): its N (0), W (1) or Z (2), nCols + 1 planes of S states -- the materialised lattice, or
+// the ring (diagonal (i + r) mod 3, the cell by its coordinate on the short side of the lattice).  xw(i, r) / xz(i, r): its exclusion
+// vectors over W / over Z, column c at (c - 1) * S -- always in the ring, beside the three layers when rolling.
+template <bool MAT>
+struct TwoMergeLattice {
+  double *cells, *ring;
+  int S, PL, L, M, byI;
+  __device__ __forceinline__ long long slot(int i, int r) const { return (long long)((i + r) % 3) * M + (byI ? i : r); }
+  __device__ __forceinline__ double *at(int i, int r, int layer) const {
+    if (MAT) return cells + ((((long long)i * (L + 1)) + r) * 3 + layer) * PL * S;
+    return ring + (slot(i, r) * (5 * PL - 2) + layer * PL) * S;
+  }
+  __device__ __forceinline__ double *xw(int i, int r) const {
+    if (MAT) return ring + slot(i, r) * 2 * (PL - 1) * S;
+    return ring + (slot(i, r) * (5 * PL - 2) + 3 * PL) * S;
+  }
+  __device__ __forceinline__ double *xz(int i, int r) const { return xw(i, r) + (PL - 1) * S; }
+};
+
+// Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every N, W and Z cell into pool (layout of
+// mb_profile_two_merge.h) and only XW, XZ in the ring, else rolling.  Viterbi keeps the FIRST maximum: N[.][.][0] takes the planes
+// ascending; N[.][.][c] the repeat first, then the match edges in `incoming` order (input token ascending), then the output-only
+// edges; W takes N (no move) first, then the input-only edges, then the silent edges; Z takes W, then the input blank; XW, XZ and the
+// end the planes ascending -- the order k_profile_two_merge_traceback re-enumerates.
+template <int MODE, bool MAT>
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_fwd(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+                                                                         const double *__restrict__ logA, const double *__restrict__ logB,
+                                                                         double *pool, double *scratch, double *__restrict__ loglike) {
+  extern __shared__ double ptm_sh[];
+  const PairProfDesc pd = descs[blockIdx.x];
+  const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, nC = mm.nCols, PL = nC + 1, K = pd.nIn, L = pd.nRows;
+  const double *A = logA + pd.inBase * CA;
+  const double *B = logB + pd.rowBase * PL;
+  const TwoMergeLattice<MAT> lat{MAT ? pool + pd.cellBase : nullptr, pd.ringBase < 0 ? ptm_sh : scratch + pd.ringBase, S, PL, L,
+                                 min(K, L) + 1, K <= L};
+  const int PS = PL * S;
+  for (int d = 0; d <= K + L; ++d) {
+    const int ilo = max(0, d - L), nCells = min(K, d) - ilo + 1;
+    const int nItems = nCells * PS;
+    for (int it = threadIdx.x; it < nItems; it += blockDim.x) {
+      const int c = it / PS, pq = it - c * PS, p = pq / S, q = pq - p * S, i = ilo + c, r = d - i;
+      const double *Ai = A + (long long)max(i - 1, 0) * CA;      // row i - 1; read when i > 0
+      double acc = (d == 0 && pq == 0) ? 0.0 : -INFINITY;
+      if (r > 0) {
+        const double w = B[(long long)(r - 1) * PL + p];
+        const double *Np = lat.at(i, r - 1, 0);
+        if (p == 0) {
+          acc = Np[q] + w;
+          for (int k = 1; k < PL; ++k) acc = red<MODE>(acc, Np[k * S + q] + w);
+        } else if (w > -INFINITY) {                          // (a column the row rules out is skipped as a whole)
+          const int tok = mm.colTok[p - 1];
+          acc = Np[p * S + q] + w;
+          if (i > 0) {
+            const double *Xd = lat.xz(i - 1, r - 1) + (p - 1) * S;
+            for (int a = 1; a <= m.nIn; ++a) {
+              const int row = q * KK + a * C + tok;
+              const double wa = Ai[a];
+              const int e1 = m.inOff[row + 1];
+              for (int e = m.inOff[row]; e < e1; ++e) acc = red<MODE>(acc, ((Xd[m.inSrc[e]] + m.inW[e]) + wa) + w);
+            }
+          }
+          const double *Xu = lat.xw(i, r - 1) + (p - 1) * S;
+          const int e1 = m.inOff[q * KK + tok + 1];
+          for (int e = m.inOff[q * KK + tok]; e < e1; ++e) acc = red<MODE>(acc, (Xu[m.inSrc[e]] + m.inW[e]) + w);
+        }
+      }
+      lat.at(i, r, 0)[pq] = acc;
+      if (i > 0) {
+        const double *Zl = lat.at(i - 1, r, 2) + p * S;
+        for (int a = 1; a <= m.nIn; ++a) {
+          const int row = q * KK + a * C;
+          const double wa = Ai[a];
+          const int e1 = m.inOff[row + 1];
+          for (int e = m.inOff[row]; e < e1; ++e) acc = red<MODE>(acc, (Zl[m.inSrc[e]] + m.inW[e]) + wa);
+        }
+        lat.at(i, r, 1)[pq] = acc;
+        lat.at(i, r, 2)[pq] = red<MODE>(acc, Zl[q] + Ai[0]);
+      } else {
+        lat.at(i, r, 1)[pq] = acc;
+        lat.at(i, r, 2)[pq] = acc;
+      }
+    }
+    __syncthreads();
+    for (int lev = 1; lev < m.nLevF; ++lev) {      // (level 0 has no silent edge coming in: its W and Z are complete)
+      const int l0 = m.levFOff[lev], ns = m.levFOff[lev + 1] - l0;
+      const int PN = PL * ns, nLevItems = nCells * PN;
+      for (int it = threadIdx.x; it < nLevItems; it += blockDim.x) {
+        const int c = it / PN, pj = it - c * PN, p = pj / ns, q = m.levFState[l0 + (pj - p * ns)], i = ilo + c, r = d - i;
+        double *Wc = lat.at(i, r, 1) + p * S;
+        double acc = Wc[q];
+        const int e1 = m.inOff[q * KK + 1];
+        for (int e = m.inOff[q * KK]; e < e1; ++e) {
+          const int s = (int)m.inSrc[e];
+          if (s >= q) continue;                       // as the token sweeps: a silent self-loop never fires
+          acc = red<MODE>(acc, Wc[s] + m.inW[e]);
+        }
+        Wc[q] = acc;
+        lat.at(i, r, 2)[p * S + q] = i > 0 ? red<MODE>(acc, lat.at(i - 1, r, 2)[p * S + q] + A[(long long)(i - 1) * CA]) : acc;
+      }
+      __syncthreads();
+    }
+    if (d < K + L) {
+      const int XS = nC * S, nXItems = nCells * XS;
+      for (int it = threadIdx.x; it < nXItems; it += blockDim.x) {
+        const int c = it / XS, cs = it - c * XS, col = cs / S + 1, s = cs - (col - 1) * S, i = ilo + c;
+        const double *Wc = lat.at(i, d - i, 1) + s, *Zc = lat.at(i, d - i, 2) + s;
+        double aw = Wc[0], az = Zc[0];                   // plane 0 is never the excluded one
+        for (int k = 1; k < PL; ++k)
+          if (k != col) { aw = red<MODE>(aw, Wc[k * S]); az = red<MODE>(az, Zc[k * S]); }
+        lat.xw(i, d - i)[cs] = aw;
+        lat.xz(i, d - i)[cs] = az;
+      }
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x == 0) {
+    const double *Ze = lat.at(K, L, 2) + S - 1;
+    double acc = Ze[0];
+    for (int p = 1; p < PL; ++p) acc = red<MODE>(acc, Ze[p * S]);
+    loglike[blockIdx.x] = acc;
+  }
+}
+
+// Materialised Backward sweep, layer 0 = NB ("from the arrived stage"), 1 = WB ("from the waiting stage"), 2 = ZB ("from the
+// committed stage"):
+//   TZ[i][r][c][s] = sum_{t: s->d, in = a,   out = colTok[c]} ((w_t + A[i][a]) + B[r][c]) + NB[i+1][r+1][c][d]     (i < K, r < L)
+//   TW[i][r][c][s] = sum_{t: s->d, in = eps, out = colTok[c]} (w_t + B[r][c]) + NB[i][r+1][c][d]                   (r < L)
+//   ZB[i][r][k][s] = [i = K, r = L, s = S-1]  (+)  A[i][0] + ZB[i+1][r][k][s]  (+)  (+)_{c != k} TZ[i][r][c][s]
+//                    (+) sum_{t: in = a, out = eps} (w_t + A[i][a]) + WB[i+1][r][k][d]                              (i < K)
+//   WB[i][r][k][s] = ZB[i][r][k][s]  (+)  (+)_{c != k} TW[i][r][c][s]  (+)  sum_{silent t, s < d} w_t + WB[i][r][k][d]
+//   NB[i][r][k][s] = WB[i][r][k][s] (+) (B[r][0] + NB[i][r+1][0][s]) (+) [k >= 1](B[r][k] + NB[i][r+1][k][s])       (r < L)
+//   loglike        = NB[0][0][0][0]
+// Anti-diagonals from K + L down.  TZ and TW, everything that leaves (i, r, s) through column c from the committed and from the
+// waiting stage, are formed once per diagonal over (cell, column, state) -- the mirror of the Forward's XZ and XW -- so the edge
+// loops do not run over planes; they live in the ring (one diagonal of them, the cell by its place on the diagonal, TZ then TW).  A
+// state's WB is final once its backward level has run; the item that finishes it writes its NB.
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_bwd(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+                                                                         const double *__restrict__ logA, const double *__restrict__ logB,
+                                                                         double *pool, double *scratch, double *__restrict__ loglike) {
+  extern __shared__ double ptm_sh[];
+  const PairProfDesc pd = descs[blockIdx.x];
+  const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, nC = mm.nCols, PL = nC + 1, K = pd.nIn, L = pd.nRows;
+  const double *A = logA + pd.inBase * CA;
+  const double *B = logB + pd.rowBase * PL;
+  const TwoMergeLattice<true> lat{pool + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  double *T = pd.ringBase < 0 ? ptm_sh : scratch + pd.ringBase;       // T[((cell on the diagonal * 2 + (0: TZ, 1: TW)) * nCols + c - 1) * S + s]
+  const int PS = PL * S, XS = nC * S;
+  for (int d = K + L; d >= 0; --d) {
+    const int ilo = max(0, d - L), nCells = min(K, d) - ilo + 1;
+    if (d < K + L) {
+      const int nTItems = nCells * XS;
+      for (int it = threadIdx.x; it < nTItems; it += blockDim.x) {
+        const int c = it / XS, cs = it - c * XS, col = cs / S + 1, s = cs - (col - 1) * S, i = ilo + c, r = d - i;
+        double tz = -INFINITY, tw = -INFINITY;
+        if (r < L) {
+          const double pc = B[(long long)r * PL + col];
+          if (pc > -INFINITY) {
+            const int tok = mm.colTok[col - 1];
+            if (i < K) {
+              const double *Nd = lat.at(i + 1, r + 1, 0) + col * S;
+              const double *Ai = A + (long long)i * CA;
+              for (int a = 1; a <= m.nIn; ++a) {
+                const int row = s * KK + a * C + tok;
+                const double wa = Ai[a];
+                const int e1 = m.outOff[row + 1];
+                for (int e = m.outOff[row]; e < e1; ++e) tz = lse2_exact(tz, ((m.outW[e] + wa) + pc) + Nd[m.outDst[e]]);
+              }
+            }
+            const double *Nu = lat.at(i, r + 1, 0) + col * S;
+            const int e1 = m.outOff[s * KK + tok + 1];
+            for (int e = m.outOff[s * KK + tok]; e < e1; ++e) tw = lse2_exact(tw, (m.outW[e] + pc) + Nu[m.outDst[e]]);
+          }
+        }
+        T[(long long)c * 2 * XS + cs] = tz;
+        T[(long long)c * 2 * XS + XS + cs] = tw;
+      }
+      __syncthreads();
+    }
+    const int nItems = nCells * PS;
+    for (int it = threadIdx.x; it < nItems; it += blockDim.x) {
+      const int c = it / PS, ks = it - c * PS, k = ks / S, s = ks - k * S, i = ilo + c, r = d - i;
+      const double *Tc = T + (long long)c * 2 * XS + s;
+      double v = (d == K + L && s == S - 1) ? 0.0 : -INFINITY;
+      if (i < K) {
+        const double *Ai = A + (long long)i * CA;
+        v = lse2_exact(v, Ai[0] + lat.at(i + 1, r, 2)[ks]);
+        if (r < L)
+          for (int col = 1; col < PL; ++col)
+            if (col != k) v = lse2_exact(v, Tc[(col - 1) * S]);
+        const double *Wl = lat.at(i + 1, r, 1) + k * S;
+        for (int a = 1; a <= m.nIn; ++a) {
+          const int row = s * KK + a * C;
+          const double wa = Ai[a];
+          const int e1 = m.outOff[row + 1];
+          for (int e = m.outOff[row]; e < e1; ++e) v = lse2_exact(v, (m.outW[e] + wa) + Wl[m.outDst[e]]);
+        }
+      }
+      lat.at(i, r, 2)[ks] = v;
+      if (r < L)
+        for (int col = 1; col < PL; ++col)
+          if (col != k) v = lse2_exact(v, Tc[XS + (col - 1) * S]);
+      lat.at(i, r, 1)[ks] = v;
+      if (r < L) {
+        const double *Nn = lat.at(i, r + 1, 0), *Br = B + (long long)r * PL;
+        v = lse2_exact(v, Br[0] + Nn[s]);
+        if (k) v = lse2_exact(v, Br[k] + Nn[ks]);
+      }
+      lat.at(i, r, 0)[ks] = v;
+    }
+    __syncthreads();
+    for (int lev = 1; lev < m.nLevB; ++lev) {
+      const int l0 = m.levBOff[lev], ns = m.levBOff[lev + 1] - l0;
+      const int PN = PL * ns, nLevItems = nCells * PN;
+      for (int it = threadIdx.x; it < nLevItems; it += blockDim.x) {
+        const int c = it / PN, kj = it - c * PN, k = kj / ns, s = m.levBState[l0 + (kj - k * ns)], i = ilo + c, r = d - i;
+        double *Wc = lat.at(i, r, 1) + k * S;
+        double v = Wc[s];
+        const int e1 = m.outOff[s * KK + 1];
+        for (int e = m.outOff[s * KK]; e < e1; ++e) {
+          const int t = (int)m.outDst[e];
+          if (t <= s) continue;
+          v = lse2_exact(v, Wc[t] + m.outW[e]);
+        }
+        Wc[s] = v;
+        if (r < L) {
+          const double *Nn = lat.at(i, r + 1, 0), *Br = B + (long long)r * PL;
+          v = lse2_exact(v, Br[0] + Nn[s]);
+          if (k) v = lse2_exact(v, Br[k] + Nn[k * S + s]);
+        }
+        lat.at(i, r, 0)[k * S + s] = v;
+      }
+      __syncthreads();
+    }
+  }
+  if (threadIdx.x == 0) loglike[blockIdx.x] = lat.at(0, 0, 0)[0];
+}
+
+// Posterior counts.  With both lattices in memory every (cell, plane, edge) term is independent:
+//   count[t] += exp(F[i][r][k][s] - LL + term_t), term_t the edge's summand of ZB (read from Z_F: the input-reading edges) or of WB
+//   (read from W_F: the others) above, through TZ / TW for the emitting edges: every column c != k,
+// so the sweep is a flat grid over (pair, group of the pair, (cell, plane, state)), accumulated by CountsAcc (mb_profile_common.h).
+// A pair whose likelihood is -inf adds nothing; the blanks of either tape and the repeat rows are not edges.
+__global__ __launch_bounds__(256) void k_profile_two_merge_counts(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+                                                                  int groupsPerPair, const double *__restrict__ logA,
+                                                                  const double *__restrict__ logB, const double *__restrict__ fwdPool,
+                                                                  const double *__restrict__ bwdPool, long long nTrans,
+                                                                  double *__restrict__ counts, int det) {
+  __shared__ double lcount[COUNTS_LDS_MAX];
+  const CountsAcc acc(lcount, counts, nTrans, det);
+  const int pair = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
+  const PairProfDesc pd = descs[pair];
+  const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, nC = mm.nCols, PL = nC + 1, K = pd.nIn, L = pd.nRows;
+  const double *A = logA + pd.inBase * CA;
+  const double *B = logB + pd.rowBase * PL;
+  const TwoMergeLattice<true> F{const_cast<double *>(fwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0},
+      Bk{const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  double LL;
+  {
+    const double *Ze = F.at(K, L, 2) + S - 1;
+    LL = Ze[0];
+    for (int p = 1; p < PL; ++p) LL = lse2_exact(LL, Ze[p * S]);
+  }
+  if (LL > -INFINITY) {
+    const long long PS = (long long)PL * S, nItems = (long long)(K + 1) * (L + 1) * PS;
+    for (long long idx = (long long)group * blockDim.x + threadIdx.x; idx < nItems; idx += (long long)groupsPerPair * blockDim.x) {
+      const long long cell = idx / PS;
+      const int ks = (int)(idx - cell * PS), k = ks / S, s = ks - k * S, i = (int)(cell / (L + 1)), r = (int)(cell - (long long)i * (L + 1));
+      const double f = F.at(i, r, 1)[ks] - LL, z = F.at(i, r, 2)[ks] - LL;
+      if (!(z > -INFINITY)) continue;                 // (Z holds W: a dead Z is a dead W)
+      const double *Br = B + (long long)r * PL;       // read when r < L
+      if (i < K) {
+        const double *Ai = A + (long long)i * CA;
+        const double *Wl = Bk.at(i + 1, r, 1) + k * S;
+        for (int a = 1; a <= m.nIn; ++a) {
+          const int row = s * KK + a * C;
+          const double wa = Ai[a];
+          if (r < L) {
+            const double *Nd = Bk.at(i + 1, r + 1, 0);
+            for (int col = 1; col < PL; ++col) {
+              const double pc = Br[col];
+              if (col == k || !(pc > -INFINITY)) continue;
+              const int tok = mm.colTok[col - 1];
+              const int e1 = m.outOff[row + tok + 1];
+              for (int e = m.outOff[row + tok]; e < e1; ++e)
+                acc.add(m.outEid[e], exp(z + (((m.outW[e] + wa) + pc) + Nd[col * S + m.outDst[e]])));
+            }
+          }
+          const int e1 = m.outOff[row + 1];
+          for (int e = m.outOff[row]; e < e1; ++e) acc.add(m.outEid[e], exp(z + ((m.outW[e] + wa) + Wl[m.outDst[e]])));
+        }
+      }
+      if (!(f > -INFINITY)) continue;
+      if (r < L) {
+        const double *Nu = Bk.at(i, r + 1, 0);
+        for (int col = 1; col < PL; ++col) {
+          const double pc = Br[col];
+          if (col == k || !(pc > -INFINITY)) continue;
+          const int tok = mm.colTok[col - 1];
+          const int e1 = m.outOff[s * KK + tok + 1];
+          for (int e = m.outOff[s * KK + tok]; e < e1; ++e) acc.add(m.outEid[e], exp(f + ((m.outW[e] + pc) + Nu[col * S + m.outDst[e]])));
+        }
+      }
+      const double *Wc = Bk.at(i, r, 1) + k * S;
+      const int e1 = m.outOff[s * KK + 1];
+      for (int e = m.outOff[s * KK]; e < e1; ++e) {
+        const int t = (int)m.outDst[e];
+        if (t <= s) continue;
+        acc.add(m.outEid[e], exp(f + (Wc[t] + m.outW[e])));
+      }
+    }
+  }
+  acc.flush();
+}
+
+// Viterbi traceback over a materialised max lattice, one lane per pair: from the first plane that attains the score at
+// Z[K][L][.][S-1] back to N[0][0][0][0], taking at every cell the first candidate (in the fill's order) whose value equals the cell;
+// an emitting edge comes from the lowest plane k != c whose Z (match) or W (output-only) equals the edge's XZ / XW.  Blanks of
+// either tape and repeat rows are not edges.  Edges go start -> end into the pair's slot (profile_pair_path_bound entries) with
+// both coordinates at which each fired, as k_profile_two_traceback.  len = -1: no finite path, -2: the slot was too small, -3: no
+// candidate matched (a corrupt matrix).
+__global__ void k_profile_two_merge_traceback(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs, int n,
+                                              const double *__restrict__ logA, const double *__restrict__ logB,
+                                              const double *__restrict__ pool, uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len) {
+  const int pair = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pair >= n) return;
+  const PairProfDesc pd = descs[pair];
+  const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, nC = mm.nCols, PL = nC + 1, K = pd.nIn, L = pd.nRows;
+  const double *A = logA + pd.inBase * CA;
+  const double *B = logB + pd.rowBase * PL;
+  const TwoMergeLattice<true> lat{const_cast<double *>(pool) + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  uint32_t *pe = edges + pd.pathBase;
+  int32_t *pr = rows + pd.pathBase, *pi = inRows + pd.pathBase;
+  int i = K, r = L, q = S - 1, layer = 2, p = 0;
+  const long long cap = K + L + (long long)(K + L + 1) * (m.nLevF - 1);
+  long long cnt = 0;
+  {
+    const double *Ze = lat.at(K, L, 2) + q;
+    double best = Ze[0];
+    for (int k = 1; k < PL; ++k)
+      if (best < Ze[k * S]) { best = Ze[k * S]; p = k; }
+    if (!(best > -INFINITY)) { len[pair] = -1; return; }
+  }
+  for (;;) {
+    const double *Ai = A + (long long)max(i - 1, 0) * CA;      // row i - 1; read when i > 0
+    int e = 0, found = -1, ni = i, nl = 1;
+    if (layer == 2) {
+      const double cur = lat.at(i, r, 2)[p * S + q];
+      if (lat.at(i, r, 1)[p * S + q] == cur) { layer = 1; continue; }
+      if (i > 0 && lat.at(i - 1, r, 2)[p * S + q] + Ai[0] == cur) { --i; continue; }
+      len[pair] = -3; return;
+    } else if (layer == 1) {
+      const double *W = lat.at(i, r, 1) + p * S;
+      const double cur = W[q];
+      if (lat.at(i, r, 0)[p * S + q] == cur) { layer = 0; continue; }
+      if (i > 0) {
+        const double *Zl = lat.at(i - 1, r, 2) + p * S;
+        for (int a = 1; a <= m.nIn && found < 0; ++a) {
+          const int row = q * KK + a * C;
+          const double wa = Ai[a];
+          e = m.inOff[row];
+          for (const int e1 = m.inOff[row + 1]; e < e1; ++e)
+            if ((Zl[m.inSrc[e]] + m.inW[e]) + wa == cur) { found = (int)m.inSrc[e]; ni = i - 1; nl = 2; break; }
+        }
+      }
+      if (found < 0) {
+        e = m.inOff[q * KK];
+        for (const int e1 = m.inOff[q * KK + 1]; e < e1; ++e) {
+          const int s = (int)m.inSrc[e];
+          if (s < q && W[s] + m.inW[e] == cur) { found = s; break; }
+        }
+      }
+      if (found < 0) { len[pair] = -3; return; }
+      if (cnt >= cap) { len[pair] = -2; return; }
+      pe[cnt] = m.inEid[e]; pr[cnt] = r; pi[cnt] = ni; ++cnt;
+      i = ni; q = found; layer = nl;
+    } else {
+      if (r == 0) { if (i != 0 || q != 0 || p != 0) { len[pair] = -3; return; } break; }
+      const double *Np = lat.at(i, r - 1, 0);
+      const double cur = lat.at(i, r, 0)[p * S + q], w = B[(long long)(r - 1) * PL + p];
+      if (p == 0) {
+        int k = 0;
+        while (k < PL && !(Np[k * S + q] + w == cur)) ++k;
+        if (k == PL) { len[pair] = -3; return; }
+        p = k; --r;
+        continue;
+      }
+      if (Np[p * S + q] + w == cur) { --r; continue; }
+      const int tok = mm.colTok[p - 1];
+      int from = -1;
+      // the edge's exclusion value over the planes of V and the lowest plane that attains it
+      auto excl = [&](const double *V, int s, int &kx) {
+        double xs = V[s];
+        kx = 0;
+        for (int k = 1; k < PL; ++k)
+          if (k != p && xs < V[k * S + s]) { xs = V[k * S + s]; kx = k; }
+        return xs;
+      };
+      if (i > 0) {
+        const double *Zd = lat.at(i - 1, r - 1, 2);
+        for (int a = 1; a <= m.nIn && found < 0; ++a) {
+          const int row = q * KK + a * C + tok;
+          const double wa = Ai[a];
+          e = m.inOff[row];
+          for (const int e1 = m.inOff[row + 1]; e < e1; ++e) {
+            int kx;
+            const double xs = excl(Zd, (int)m.inSrc[e], kx);
+            if (((xs + m.inW[e]) + wa) + w == cur) { found = (int)m.inSrc[e]; from = kx; ni = i - 1; nl = 2; break; }
+          }
+        }
+      }
+      if (found < 0) {
+        const double *Wu = lat.at(i, r - 1, 1);
+        e = m.inOff[q * KK + tok];
+        for (const int e1 = m.inOff[q * KK + tok + 1]; e < e1; ++e) {
+          int kx;
+          const double xs = excl(Wu, (int)m.inSrc[e], kx);
+          if ((xs + m.inW[e]) + w == cur) { found = (int)m.inSrc[e]; from = kx; break; }
+        }
+      }
+      if (found < 0) { len[pair] = -3; return; }
+      if (cnt >= cap) { len[pair] = -2; return; }
+      --r;
+      pe[cnt] = m.inEid[e]; pr[cnt] = r; pi[cnt] = ni; ++cnt;
+      i = ni; q = found; p = from; layer = nl;
+    }
+  }
+  for (long long u = 0, v = cnt - 1; u < v; ++u, --v) {
+    const uint32_t e = pe[u]; pe[u] = pe[v]; pe[v] = e;
+    const int32_t w = pr[u]; pr[u] = pr[v]; pr[v] = w;
+    const int32_t x = pi[u]; pi[u] = pi[v]; pi[v] = x;
+  }
+  len[pair] = cnt;
+}
+
+// beyond the default 64 KiB the kernels must be told; asked for once, and only when a ring needs it
+static bool ptm_allow_lds(size_t lds) {
+  static size_t ldsAllowed = 64 * 1024;
+  if (lds <= ldsAllowed) return true;
+  const void *ks[] = {(const void *)&k_profile_two_merge_fwd<MB_FORWARD, false>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, false>,
+                      (const void *)&k_profile_two_merge_fwd<MB_FORWARD, true>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, true>,
+                      (const void *)&k_profile_two_merge_bwd};
+  for (const void *k : ks)
+    if (!hip_ok(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), "k_profile_two_merge: raising the LDS limit")) return false;
+  ldsAllowed = SWEEP_LDS_MAX;
+  return true;
+}
+
+int launch_profile_two_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const PairProfDesc *d, int n, size_t lds,
+                                 long long maxItems, const double *logA, const double *logB, double *pool, double *scratch,
+                                 double *loglike, hipStream_t st) {
+  if (n <= 0) return 0;
+  if (!ptm_allow_lds(lds)) return 1;
+  const dim3 g(n), b(sweep_threads(maxItems));
+  if (mode == MB_VITERBI) {
+    if (mat) k_profile_two_merge_fwd<MB_VITERBI, true><<<g, b, lds, st>>>(m->dev, mm, d, logA, logB, pool, scratch, loglike);
+    else k_profile_two_merge_fwd<MB_VITERBI, false><<<g, b, lds, st>>>(m->dev, mm, d, logA, logB, pool, scratch, loglike);
+  } else {
+    if (mat) k_profile_two_merge_fwd<MB_FORWARD, true><<<g, b, lds, st>>>(m->dev, mm, d, logA, logB, pool, scratch, loglike);
+    else k_profile_two_merge_fwd<MB_FORWARD, false><<<g, b, lds, st>>>(m->dev, mm, d, logA, logB, pool, scratch, loglike);
+  }
+  return hip_ok(hipGetLastError(), "k_profile_two_merge_fwd") ? 0 : 1;
+}
+
+int launch_profile_two_merge_bwd(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, size_t lds, long long maxItems,
+                                 const double *logA, const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  if (n <= 0) return 0;
+  if (!ptm_allow_lds(lds)) return 1;
+  k_profile_two_merge_bwd<<<dim3(n), dim3(sweep_threads(maxItems)), lds, st>>>(m->dev, mm, d, logA, logB, pool, scratch, loglike);
+  return hip_ok(hipGetLastError(), "k_profile_two_merge_bwd") ? 0 : 1;
+}
+
+int launch_profile_two_merge_counts(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, int groupsPerPair, const double *logA,
+                                    const double *logB, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
+  if (n <= 0 || m->nTrans <= 0) return 0;
+  k_profile_two_merge_counts<<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(
+      m->dev, mm, d, groupsPerPair, logA, logB, fwdPool, bwdPool, m->nTrans, counts, g_deterministic ? 1 : 0);
+  return hip_ok(hipGetLastError(), "k_profile_two_merge_counts") ? 0 : 1;
+}
+
+int launch_profile_two_merge_traceback(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, const double *logA,
+                                       const double *logB, const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows,
+                                       long long *len, hipStream_t st) {
+  if (n <= 0) return 0;
+  k_profile_two_merge_traceback<<<(n + 63) / 64, 64, 0, st>>>(m->dev, mm, d, n, logA, logB, pool, edges, rows, inRows, len);
+  return hip_ok(hipGetLastError(), "k_profile_two_merge_traceback") ? 0 : 1;
+}
+
+}  // namespace mb

@@ -1340,3 +1340,271 @@ class TwoProfileDP(PairProfileDP):
                 r -= 1; i -= 1
                 edges.append(e); rows.append(r); ins.append(i); q = s; layer = 2
         return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32), np.array(ins[::-1], np.int32)
+
+
+class TwoMergedProfileDP(TwoProfileDP):
+    """A machine WITH an input alphabet between an input profile and a CTC-MERGED output profile, in numpy -- the yardstick of
+    mb_profile_two_merge.hip (docs/profile_tapes.md, "Pairs of profiles against a merged profile"): the semantics of
+    compose(A.machine(), compose(M, mergingRecogniserMachine())) with both tapes empty.  The lattice of TwoProfileDP with the plane
+    axis of MergedProfileDP: plane 0 = the last row took the blank (or no row yet), plane c = the last row took column c, whose
+    output token is colTok[c - 1].  XW and XZ are the exclusion vectors over W and over Z:
+
+        XW[i][r][c][s] = (+)_{k != c} W[i][r][k][s]          XZ[i][r][c][s] = (+)_{k != c} Z[i][r][k][s]
+        N[i][r][0][d]  = [i = 0, r = 0, d = 0]  (+)  (+)_p (N[i][r-1][p][d] + B[r-1][0])                      (output blank; r > 0)
+        N[i][r][c][d]  = (N[i][r-1][c][d] + B[r-1][c])                                                        (repeat; r > 0)
+                         (+) sum_{t: s->d, in = a,   out = colTok[c]} ((XZ[i-1][r-1][c][s] + w_t) + A[i-1][a]) + B[r-1][c]   (match)
+                         (+) sum_{t: s->d, in = eps, out = colTok[c]} (XW[i][r-1][c][s] + w_t) + B[r-1][c]                   (output-only)
+        W[i][r][p][d]  = N[i][r][p][d]
+                         (+) sum_{t: in = a, out = eps} (Z[i-1][r][p][s] + w_t) + A[i-1][a]                   (input-only; same plane)
+                         (+) sum_{silent t, s < d}      W[i][r][p][s] + w_t                                   (silent levels, per plane)
+        Z[i][r][p][d]  = W[i][r][p][d]  (+)  Z[i-1][r][p][d] + A[i-1][0]                                      (input blank; same plane)
+        loglike        = (+)_p Z[K][L][p][S-1]
+
+    The output blank and the repeat read N, never W.  Viterbi keeps the FIRST maximum -- N[.][.][0]: planes ascending; N[.][.][c]:
+    the repeat, then the match edges in `incoming` order (input token ascending), then the output-only edges, each from the lowest
+    plane k != c that attains its XZ / XW; W: "no move", then the input-only edges, then the silent edges; Z: W, then the input
+    blank; the end: planes ascending.  Every method takes (A, B): A the [K, nInTok + 1] log rows of Profile.logRowsIn, B the
+    [L, nCols + 1] log rows of Profile.mergeRows.  Lattices are [K + 1, L + 1, nCols + 1, S]; every sweep is vectorised over planes
+    and states."""
+
+    def __init__(self, em: EvaluatedMachine, colTok: Sequence[int]):
+        super().__init__(em)
+        self.colTok = np.asarray(colTok, np.int64).reshape(-1)
+        self.nCols = len(self.colTok)
+        if self.nCols < 1:
+            raise MachineError("merged profiles need at least one column")
+        if self.colTok.min() < 1 or self.colTok.max() > em.nOutTok:
+            raise MachineError("column token outside 1..nOutTok")
+        self.PL = self.nCols + 1
+
+        def by_column(o):
+            """(indices into a table whose out tokens are ``o``, column) of its edges whose token heads a column: column-major,
+            `incoming` order within"""
+            sel = [np.nonzero(o == t)[0] for t in self.colTok]
+            col = np.concatenate([np.full(len(k), c + 1, np.int64) for c, k in enumerate(sel)])
+            return np.concatenate(sel).astype(np.int64), col
+        mE, mS, mD, mW, mA, mO = self.mAll
+        k, col = by_column(mO)
+        self.mCol = (mE[k], mS[k], mD[k], mW[k], mA[k], col)       # (edge id, src, dst, w, in token, column)
+        k, col = by_column(np.asarray(self.eO))
+        self.emitCol = (self.eId[k], self.eS[k], self.eD[k], self.eW[k], col)
+
+    def _check(self, P) -> np.ndarray:
+        P = np.asarray(P, np.float64).reshape(-1, self.PL)
+        if np.isnan(P).any() or (P == math.inf).any():
+            raise MachineError("profile weight is NaN or +infinity")
+        return P
+
+    def _planes(self, fold, base: np.ndarray, d: np.ndarray, vals: np.ndarray) -> np.ndarray:
+        """fold over (plane, state) at once: vals[PL, n] into base[PL, S] at column d[n] of every plane"""
+        S = self.S
+        idx = (np.arange(self.PL)[:, None] * S + d[None, :]).ravel()
+        return fold(base.ravel(), idx, vals.ravel()).reshape(self.PL, S)
+
+    def forward(self, A, B, mode: str = "exact"):
+        """(loglike, N, W, Z), each [K+1][L+1][nCols+1][S]; mode "exact" or "max"."""
+        return self._sweep(A, B, mode)[:4]
+
+    def _sweep(self, A, B, mode: str):
+        """forward() and the exclusion vectors XW, XZ [K+1][L+1][nCols+1][S] (plane 0 of either is not read)"""
+        A, B = self._checkTwo(A, B)
+        mx = mode == "max"
+        fold = _max_fold if mx else _lse_fold
+        K, L, S, PL = len(A), len(B), self.S, self.PL
+        shape = (K + 1, L + 1, PL, S)
+        N = np.full(shape, _NEG); W = np.full(shape, _NEG); Z = np.full(shape, _NEG)
+        XW = np.full(shape, _NEG); XZ = np.full(shape, _NEG)
+        _, mS, mD, mW, mA, mC = self.mCol
+        _, eS, eD, eW, eC = self.emitCol
+        _, iS, iD, iW, iA, _ = self.iAll
+        for i in range(K + 1):
+            for r in range(L + 1):
+                base = np.full((PL, S), _NEG)
+                if i == 0 and r == 0:
+                    base[0, 0] = 0.0
+                if r:
+                    Br = B[r - 1]
+                    base[0] = _red_planes(N[i, r - 1] + Br[0], mx)
+                    flat = (N[i, r - 1] + Br[:, None]).ravel()
+                    flat[:S] = base[0]
+                    idx, vals = [], []
+                    if i:
+                        idx.append(mC * S + mD); vals.append(((XZ[i - 1, r - 1][mC, mS] + mW) + A[i - 1][mA]) + Br[mC])
+                    idx.append(eC * S + eD); vals.append((XW[i, r - 1][eC, eS] + eW) + Br[eC])
+                    base = fold(flat, np.concatenate(idx), np.concatenate(vals)).reshape(PL, S)
+                N[i, r] = base
+                w_ = base.copy()
+                if i:
+                    w_ = self._planes(fold, w_, iD, (Z[i - 1, r][:, iS] + iW) + A[i - 1][iA])
+                for lv in self.fLevels:
+                    w_ = self._planes(fold, w_, self.sD[lv], w_[:, self.sS[lv]] + self.sW[lv])
+                W[i, r] = w_
+                z_ = self._planes(fold, w_, self._all, Z[i - 1, r] + A[i - 1][0]) if i else w_
+                Z[i, r] = z_
+                XW[i, r] = _excl_planes(w_, mx)
+                XZ[i, r] = _excl_planes(z_, mx)
+        return float(_red_planes(Z[K, L, :, S - 1:S], mx)[0]), N, W, Z, XW, XZ
+
+    def backward(self, A, B):
+        """(loglike, NB, WB, ZB), each [K+1][L+1][nCols+1][S], exact log-sum-exp; loglike = NB[0][0][0][0]."""
+        A, B = self._checkTwo(A, B)
+        K, L, S, PL = len(A), len(B), self.S, self.PL
+        shape = (K + 1, L + 1, PL, S)
+        NB = np.full(shape, _NEG); WB = np.full(shape, _NEG); ZB = np.full(shape, _NEG)
+        _, mS, mD, mW, mA, mC = self.mCol
+        _, eS, eD, eW, eC = self.emitCol
+        _, iS, iD, iW, iA, _ = self.iAll
+        neg = np.full(PL * S, _NEG)
+        for i in range(K, -1, -1):
+            for r in range(L, -1, -1):
+                base = np.full((PL, S), _NEG)
+                if i == K and r == L:
+                    base[:, S - 1] = 0.0
+                if i < K:
+                    base = np.logaddexp(base, A[i][0] + ZB[i + 1, r])
+                    if r < L:
+                        # TZ[c][s]: everything that leaves the committed s through column c; ZB[k] takes the columns other than k
+                        TZ = _lse_fold(neg, mC * S + mS, ((mW + A[i][mA]) + B[r][mC]) + NB[i + 1, r + 1][mC, mD]).reshape(PL, S)
+                        base = np.logaddexp(base, _excl_planes(TZ, False))
+                    base = self._planes(_lse_fold, base, iS, (iW + A[i][iA]) + WB[i + 1, r][:, iD])
+                ZB[i, r] = base
+                if r < L:
+                    TW = _lse_fold(neg, eC * S + eS, (eW + B[r][eC]) + NB[i, r + 1][eC, eD]).reshape(PL, S)
+                    base = np.logaddexp(base, _excl_planes(TW, False))
+                for lv in self.bLevels:
+                    base = self._planes(_lse_fold, base, self.sS[lv], base[:, self.sD[lv]] + self.sW[lv])
+                WB[i, r] = base
+                if r < L:
+                    nb = np.logaddexp(base, B[r][0] + NB[i, r + 1][0])
+                    nb[1:] = np.logaddexp(nb[1:], B[r][1:, None] + NB[i, r + 1][1:])
+                    NB[i, r] = nb
+                else:
+                    NB[i, r] = base
+        return float(NB[0, 0, 0, 0]), NB, WB, ZB
+
+    def counts(self, A, B, blanks: Optional[list] = None) -> Tuple[np.ndarray, float]:
+        """(posterior expected use of every transition, Forward loglike); nothing for a -inf pair.  Blanks of either tape and
+        repeat rows are not edges; ``blanks`` (a list) receives (mass of the output blanks, mass of the repeats, mass of the input
+        blanks), summed over the lattice."""
+        A, B = self._checkTwo(A, B)
+        ll, NF, WF, ZF, XW, XZ = self._sweep(A, B, "exact")
+        out = np.zeros(self.em.nTransitions)
+        if not ll > _NEG:
+            return out, ll
+        _, NB, WB, ZB = self.backward(A, B)
+        K, L = len(A), len(B)
+        mE, mS, mD, mW, mA, mC = self.mCol
+        eE, eS, eD, eW, eC = self.emitCol
+        iE, iS, iD, iW, iA, _ = self.iAll
+        outBlank = repeat = inBlank = 0.0
+
+        def mass(b):
+            return float(np.exp(b[b > _NEG]).sum())
+        with np.errstate(invalid="ignore"):
+            for i in range(K + 1):
+                for r in range(L + 1):
+                    f, z = WF[i, r] - ll, ZF[i, r] - ll
+                    fx, zx = XW[i, r] - ll, XZ[i, r] - ll
+                    if r < L:
+                        if i < K:
+                            np.add.at(out, mE, np.exp(zx[mC, mS] + (((mW + A[i][mA]) + B[r][mC]) + NB[i + 1, r + 1][mC, mD])))
+                        np.add.at(out, eE, np.exp(fx[eC, eS] + ((eW + B[r][eC]) + NB[i, r + 1][eC, eD])))
+                        n = NF[i, r] - ll
+                        outBlank += mass(n + (B[r][0] + NB[i, r + 1][0]))
+                        repeat += mass(n[1:] + (B[r][1:, None] + NB[i, r + 1][1:]))
+                    if i < K:
+                        np.add.at(out, iE, np.exp(z[:, iS] + ((iW + A[i][iA]) + WB[i + 1, r][:, iD])).sum(axis=0))
+                        inBlank += mass(z + (A[i][0] + ZB[i + 1, r]))
+                    np.add.at(out, self.sId, np.exp(f[:, self.sS] + (WB[i, r][:, self.sD] + self.sW)).sum(axis=0))
+        if blanks is not None:
+            blanks.append((outBlank, repeat, inBlank))
+        return out, ll
+
+    def rowPosteriors(self, A, B, env=None):
+        raise MachineError("row posteriors take plain profiles")
+
+    def viterbi(self, A, B, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
+        """(score, global edge ids start -> end, output row, input row at which each fired); the first maximum in the fill's
+        candidate order, rows as TwoProfileDP.viterbi; blanks of either tape and repeat rows are not edges.  ``census``: per step
+        at which two or more candidates equal the cell, a count under the tuple of the kinds that tie, in candidate order ("repeat",
+        "match", "emit" at N[.][.][c]; "stay", "ins", "silent" at a W cell; "wait", "inblank" at a Z cell); under ("blank",) the
+        steps at N[.][.][0] that two planes attain, under ("plane",) the emitting edges whose XZ / XW two planes attain, under
+        ("end",) an end that two planes attain."""
+        A, B = self._checkTwo(A, B)
+        v, N, W, Z = self.forward(A, B, "max")
+        edges: List[int] = []; rows: List[int] = []; ins: List[int] = []
+        if not v > _NEG:
+            return v, np.zeros(0, np.uint32), np.zeros(0, np.int32), np.zeros(0, np.int32)
+
+        def tie(kinds, n: int = 2):
+            if census is not None and n > 1:
+                census[kinds] = census.get(kinds, 0) + 1
+        mE, mS, mD, mW, mA, mO = self.mAll
+        iE, iS, iD, iW, iA, _ = self.iAll
+        i, r, q, layer = len(A), len(B), self.S - 1, 2
+        ends = [p for p in range(self.PL) if Z[i, r, p, q] == v]
+        tie(("end",), len(ends))
+        p = ends[0]
+        while True:
+            cand = []          # (kind, edge id or -1, source state, exclusion value or None, attains the cell)
+            if layer == 2:
+                cur = Z[i, r, p, q]
+                cand.append(("wait", -1, q, None, W[i, r, p, q] == cur))
+                if i:
+                    cand.append(("inblank", -1, q, None, Z[i - 1, r, p, q] + A[i - 1][0] == cur))
+            elif layer == 1:
+                cur = W[i, r, p, q]
+                cand.append(("stay", -1, q, None, N[i, r, p, q] == cur))
+                if i:
+                    cand += [("ins", int(iE[k]), int(iS[k]), None, (Z[i - 1, r, p, iS[k]] + iW[k]) + A[i - 1][iA[k]] == cur)
+                             for k in np.nonzero(iD == q)[0]]
+                cand += [("silent", int(self.sId[k]), int(self.sS[k]), None, W[i, r, p, self.sS[k]] + self.sW[k] == cur) for k in self.inSil[q]]
+            else:
+                if r == 0:
+                    assert i == 0 and q == 0 and p == 0
+                    break
+                Br, cur = B[r - 1], N[i, r, p, q]
+                if p == 0:
+                    hit = [N[i, r - 1, k, q] + Br[0] == cur for k in range(self.PL)]
+                    tie(("blank",), sum(hit))
+                    p = hit.index(True)
+                    r -= 1
+                    continue
+                oth = [k for k in range(self.PL) if k != p]
+                tok = self.colTok[p - 1]
+                cand.append(("repeat", -1, q, None, N[i, r - 1, p, q] + Br[p] == cur))
+                if i:
+                    for k in np.nonzero((mD == q) & (mO == tok))[0]:
+                        xv = max(Z[i - 1, r - 1, o_, mS[k]] for o_ in oth)
+                        cand.append(("match", int(mE[k]), int(mS[k]), xv, ((xv + mW[k]) + A[i - 1][mA[k]]) + Br[p] == cur))
+                for k in self.inEmit[q]:
+                    if self.eO[k] == tok:
+                        xv = max(W[i, r - 1, o_, self.eS[k]] for o_ in oth)
+                        cand.append(("emit", int(self.eId[k]), int(self.eS[k]), xv, (xv + self.eW[k]) + Br[p] == cur))
+            hits = [c for c in cand if c[4]]
+            if len(hits) > 1:
+                tie(tuple(dict.fromkeys(c[0] for c in hits)))
+            kind, e, s, xv, _ = hits[0]
+            if kind == "wait":
+                layer = 1
+            elif kind == "inblank":
+                i -= 1
+            elif kind == "stay":
+                layer = 0
+            elif kind == "repeat":
+                r -= 1
+            elif kind == "silent":
+                edges.append(e); rows.append(r); ins.append(i); q = s
+            elif kind == "ins":
+                i -= 1
+                edges.append(e); rows.append(r); ins.append(i); q = s; layer = 2
+            else:
+                r -= 1
+                if kind == "match":
+                    i -= 1
+                V = Z if kind == "match" else W
+                src = [k for k in oth if V[i, r, k, s] == xv]
+                tie(("plane",), len(src))
+                edges.append(e); rows.append(r); ins.append(i); q = s; p = src[0]
+                layer = 2 if kind == "match" else 1
+        return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32), np.array(ins[::-1], np.int32)
