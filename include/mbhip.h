@@ -232,7 +232,7 @@ int mb_profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int64_t 
  * NULL = no envelope.  Errors, before anything is launched (the pairs are then left without envelopes): "Envelope/sequence mismatch"
  * (a row count other than rows + 1, inEnd > nIn + 1, inStart < 0 or > inEnd), "Envelope is not connected" (the rule of
  * Envelope::connected; (0, 0) and (nIn, rows) lie inside), "Envelope is not monotone" (inStart or inEnd decreases from a row to the
- * next), "envelopes take plain profiles" (a merged pairs object). */
+ * next), "envelopes take plain profiles" (a merged pairs object: its entry is mb_profile_pairs_set_envelopes_merged, below). */
 int mb_profile_pairs_set_envelopes(mb_profile_pairs *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd);
 int mb_profile_pair_fill_env(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows,
                              const int32_t *envStart, const int32_t *envEnd, double *cellsOut);
@@ -283,6 +283,21 @@ int mb_profile_pair_fill_merged(mb_machine *m, int mode, const int32_t *inTok, i
 int mb_profile_pairs_row_posteriors_merged(mb_profile_pairs *p, double *post /* [sum rows][nCols+1], overwritten */,
                                            double *loglike /* [nPairs] or NULL */);
 int mb_profile_pairs_set_rows_merged(mb_profile_pairs *p, const double *logP);
+
+/* Pairs against merged profiles under an envelope (docs/profile_tapes.md, "Pairs against a merged profile under an envelope"): the
+ * envelopes of mb_profile_pairs_set_envelopes -- same arguments, same checks, same three messages -- on a merged pairs object.  Cell
+ * (i, r) exists iff inStart[r] <= i < inEnd[r], in every plane; N, W and the exclusion vectors of every other cell are -inf.  A pair
+ * without an envelope runs the kernels of the rectangle, in a launch of their own when the batch holds both kinds.  Materialised
+ * lattices are compact, cells[(((off[r] + i - inStart[r])*2 + layer)*(nCols+1) + plane)*nStates + state], and
+ * mb_profile_pairs_cells counts them.  mb_profile_pairs_forward / _viterbi / _counts / _row_posteriors_merged then sweep the envelope
+ * cells alone; mb_profile_pairs_set_rows_merged leaves the envelopes in place.  envOff == NULL clears.  A plain pairs object is
+ * refused with "merged envelopes take merged profiles"; a rejected call leaves the pairs without envelopes and launches nothing.
+ * (mb_profile_pairs_set_envelopes keeps refusing a merged object.)  mb_profile_pair_fill_merged_env hands back the full rectangle of
+ * mb_profile_pair_fill_merged with -inf outside; both envelope pointers NULL = no envelope. */
+int mb_profile_pairs_set_envelopes_merged(mb_profile_pairs *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd);
+int mb_profile_pair_fill_merged_env(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows,
+                                    int32_t nCols, const int32_t *colTok, const int32_t *envStart, const int32_t *envEnd,
+                                    double *cellsOut);
 
 /* Pairs of profiles (`--generate-csv A.csv` beside `--recognize-csv B.csv`): a machine WITH an input alphabet between an input
  * profile and an output profile -- the semantics of compose(A.machine(), compose(M, transpose(B.machine()))) with both tapes empty,

@@ -518,9 +518,9 @@ def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device"
     float per input, or None where not asked for -- a sequence that cannot be tokenised scores -inf and adds nothing to the counts,
     as the --loglike loop (dp.loglikeBatch); paramCounts is the posterior count of every parameter summed over the pairs, or None.
     ``band``: every tokenisable input is swept under seqpair.Envelope.band(len(x), len(profile), band) (docs/profile_tapes.md,
-    "Pairs under an envelope"); plain profiles only.  ``posteriors``: scores["posteriors"] holds one [rows, nOutTok + 1] array per
+    "Pairs under an envelope"); plain profiles only here -- scoreMergedPairs bands a merged profile.  ``posteriors``: scores["posteriors"] holds one [rows, nOutTok + 1] array per
     input, the posterior probability that each row was consumed as each output token (column 0: as the blank; docs/profile_tapes.md,
-    "Row posteriors") -- zeros for an input that cannot be tokenised or scores -inf; plain profiles only; the key is absent when not
+    "Row posteriors") -- zeros for an input that cannot be tokenised or scores -inf; plain profiles only (merged: scoreMergedPairs); the key is absent when not
     asked for."""
     import numpy as np
     from . import dp
@@ -589,15 +589,19 @@ def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device"
     return scores, (acc.paramCounts(machine, params) if counts else None)
 
 
-def mergedPairPosteriors(machine: Machine, inputs, profile, backend: str = "device", params=None):
-    """Every input sequence (a list of symbols) as one pair with ``profile`` read CTC-merged (a profile.Profile, or a pair
-    (logP[L, nCols + 1], colTok) as Profile.mergeRows returns), all pairs in one batch: (posteriors, loglike), one [L, nCols + 1]
-    array and one float per input -- the posterior probability that each row was consumed as each column (column 0: as the blank),
-    the gradient of the pair's log-likelihood in the merged rows (docs/profile_tapes.md, "Row posteriors of pairs against a merged
-    profile").  An input that cannot be tokenised scores -inf; it and an input that scores -inf get zeros.  ``backend``: "device"
-    (capi.DeviceProfilePairs.merged_row_posteriors) or "numpy" (profile.PairMergedProfileDP.rowPosteriors)."""
+def scoreMergedPairs(machine: Machine, inputs, profile, backend: str = "device", params=None, loglike: bool = True,
+                     viterbi: bool = False, counts: bool = False, posteriors: bool = False, band: Optional[int] = None):
+    """scoreProfilePairs for a profile read CTC-merged (a profile.Profile, or a pair (logP[L, nCols + 1], colTok) as
+    Profile.mergeRows returns), with everything the merged pairs have: the same return shape, (scores, paramCounts).  ``band``:
+    every tokenisable input is swept under seqpair.Envelope.band(len(x), rows, band) (docs/profile_tapes.md, "Pairs against a merged
+    profile under an envelope").  ``posteriors``: scores["posteriors"] holds one [rows, nCols + 1] array per input, the posterior
+    probability that each row was consumed as each column (column 0: as the blank) -- zeros for an input that cannot be tokenised
+    or scores -inf; the key is absent when not asked for.  ``backend``: "device" (capi.DeviceProfilePairs with colTok) or "numpy"
+    (profile.PairMergedProfileDP)."""
     import numpy as np
+    from . import dp
     from .profile import PairMergedProfileDP
+    from .seqpair import Envelope
     if backend not in ("device", "numpy"):
         raise MachineError('backend is "device" or "numpy"')
     ev = EvaluatedMachine.fromMachine(machine, params)
@@ -607,9 +611,77 @@ def mergedPairPosteriors(machine: Machine, inputs, profile, backend: str = "devi
     P = np.asarray(P, np.float64).reshape(-1, len(colTok) + 1)
     ok = [ev.inputTokenizer.canTokenize(seq) for seq in inputs]
     xs = [np.asarray(ev.inputTokenizer.tokenize(seq), np.int64).reshape(-1) for seq, k in zip(inputs, ok) if k]
+    envs = [None] * len(xs) if band is None else [Envelope.band(len(x), len(P), int(band)) for x in xs]
+    acc = dp.MachineCounts(ev)
+    fwd = vit = post = None
     if backend == "numpy":
         pdp = PairMergedProfileDP(ev, colTok)
-        res = [pdp.rowPosteriors(x, P) for x in xs]
+        fwd = [pdp.forward(x, P, env=e)[0] for x, e in zip(xs, envs)] if loglike else None
+        if counts:
+            for x, e in zip(xs, envs):
+                c, ll = pdp.counts(x, P, env=e)
+                acc._flat += c
+                acc.loglike += ll
+        vit = [pdp.forward(x, P, "max", env=e)[0] for x, e in zip(xs, envs)] if viterbi else None
+        post = [pdp.rowPosteriors(x, P, env=e)[0] for x, e in zip(xs, envs)] if posteriors else None
+    else:
+        from . import capi
+        dm = capi.DeviceMachine(ev)
+        pairs = None
+        try:
+            pairs = capi.DeviceProfilePairs(dm, xs, [P] * len(xs), colTok)
+            if band is not None:
+                pairs.set_merged_envelopes(envs)
+            fwd = pairs.forward(capi.MB_ROLLING) if loglike else None
+            if counts:
+                _, s, _ = pairs.counts(acc._flat)
+                acc.loglike += s
+            vit = pairs.viterbi(paths=False)[0] if viterbi else None
+            if posteriors:
+                flat = pairs.merged_row_posteriors()[0]
+                post = [flat[k * len(P):(k + 1) * len(P)] for k in range(len(xs))]
+        finally:
+            if pairs is not None:
+                pairs.close()
+            dm.close()
+
+    def spread(v):
+        if v is None:
+            return None
+        it = iter(v)
+        return [float(next(it)) if k else -math.inf for k in ok]
+    scores = {"loglike": spread(fwd), "viterbi": spread(vit)}
+    if posteriors:
+        it = iter(post)
+        scores["posteriors"] = [np.array(next(it)) if k else np.zeros(P.shape) for k in ok]
+    return scores, (acc.paramCounts(machine, params) if counts else None)
+
+
+def mergedPairPosteriors(machine: Machine, inputs, profile, backend: str = "device", params=None, band: Optional[int] = None):
+    """Every input sequence (a list of symbols) as one pair with ``profile`` read CTC-merged (a profile.Profile, or a pair
+    (logP[L, nCols + 1], colTok) as Profile.mergeRows returns), all pairs in one batch: (posteriors, loglike), one [L, nCols + 1]
+    array and one float per input -- the posterior probability that each row was consumed as each column (column 0: as the blank),
+    the gradient of the pair's log-likelihood in the merged rows (docs/profile_tapes.md, "Row posteriors of pairs against a merged
+    profile").  An input that cannot be tokenised scores -inf; it and an input that scores -inf get zeros.  ``backend``: "device"
+    (capi.DeviceProfilePairs.merged_row_posteriors) or "numpy" (profile.PairMergedProfileDP.rowPosteriors).  ``band``: every
+    tokenisable input is swept under seqpair.Envelope.band(len(x), L, band) (docs/profile_tapes.md, "Pairs against a merged profile
+    under an envelope")."""
+    import numpy as np
+    from .profile import PairMergedProfileDP
+    from .seqpair import Envelope
+    if backend not in ("device", "numpy"):
+        raise MachineError('backend is "device" or "numpy"')
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    if not ev.nOutTok:
+        raise MachineError("--recognize-merge-csv needs a machine with an output alphabet")
+    P, colTok = _mergedRows(profile, ev) if hasattr(profile, "mergeRows") else profile
+    P = np.asarray(P, np.float64).reshape(-1, len(colTok) + 1)
+    ok = [ev.inputTokenizer.canTokenize(seq) for seq in inputs]
+    xs = [np.asarray(ev.inputTokenizer.tokenize(seq), np.int64).reshape(-1) for seq, k in zip(inputs, ok) if k]
+    envs = None if band is None else [Envelope.band(len(x), len(P), int(band)) for x in xs]
+    if backend == "numpy":
+        pdp = PairMergedProfileDP(ev, colTok)
+        res = [pdp.rowPosteriors(x, P) for x in xs] if envs is None else [pdp.rowPosteriors(x, P, env=e) for x, e in zip(xs, envs)]
         post, ll = [r[0] for r in res], [r[1] for r in res]
     else:
         from . import capi
@@ -617,6 +689,8 @@ def mergedPairPosteriors(machine: Machine, inputs, profile, backend: str = "devi
         pairs = None
         try:
             pairs = capi.DeviceProfilePairs(dm, xs, [P] * len(xs), colTok)
+            if envs is not None:
+                pairs.set_merged_envelopes(envs)
             flat, ll = pairs.merged_row_posteriors()
             post = [flat[k * len(P):(k + 1) * len(P)] for k in range(len(xs))]
         finally:

@@ -37,6 +37,7 @@ EXPORTS = [
     "mb_profile_pairs_set_envelopes", "mb_profile_pair_fill_env", "mb_profile_pairs_cells",
     "mb_profile_pairs_row_posteriors", "mb_profile_pairs_set_rows",
     "mb_profile_pairs_row_posteriors_merged", "mb_profile_pairs_set_rows_merged",
+    "mb_profile_pairs_set_envelopes_merged", "mb_profile_pair_fill_merged_env",
     "mb_profile_twos_create", "mb_profile_twos_destroy", "mb_profile_twos_forward", "mb_profile_twos_viterbi", "mb_profile_twos_counts",
     "mb_profile_twos_row_posteriors", "mb_profile_twos_set_rows",
     "mb_profile_two_fill",
@@ -148,6 +149,8 @@ def load():
     L.mb_profile_pairs_set_rows.argtypes = [vp, dp]
     L.mb_profile_pairs_row_posteriors_merged.argtypes = [vp, dp, dp]
     L.mb_profile_pairs_set_rows_merged.argtypes = [vp, dp]
+    L.mb_profile_pairs_set_envelopes_merged.argtypes = [vp, i64p, i32p, i32p]
+    L.mb_profile_pair_fill_merged_env.argtypes = [vp, C.c_int, i32p, C.c_int64, dp, C.c_int64, C.c_int32, i32p, i32p, i32p, dp]
     L.mb_profile_twos_create.restype = vp
     L.mb_profile_twos_create.argtypes = [vp, C.c_int64, dp, i64p, dp, i64p]
     L.mb_profile_twos_destroy.argtypes = [vp]; L.mb_profile_twos_destroy.restype = None
@@ -755,8 +758,14 @@ class DeviceProfilePairs:
     def set_envelopes(self, envs):
         """envs: per pair None (full: the pair keeps the sweeps over the whole rectangle), a seqpair.Envelope or an (inStart,
         inEnd) pair of rows + 1 entries each; ``None`` instead of a list clears every envelope (docs/profile_tapes.md, "Pairs
-        under an envelope")."""
+        under an envelope").  Plain profiles; an object created with ``colTok`` takes set_merged_envelopes."""
         _set_envelopes(load().mb_profile_pairs_set_envelopes, self.h, self.nPairs, envs)
+
+    def set_merged_envelopes(self, envs):
+        """set_envelopes for an object created with ``colTok``: a cell outside is -inf in every plane, and the sweeps, the counts and
+        merged_row_posteriors visit the envelope cells alone (docs/profile_tapes.md, "Pairs against a merged profile under an
+        envelope").  The yardstick is profile.PairMergedProfileDP with ``env``."""
+        _set_envelopes(load().mb_profile_pairs_set_envelopes_merged, self.h, self.nPairs, envs)
 
     def cells(self) -> int:
         """Doubles of the materialised lattices of all pairs under the current envelopes."""
@@ -877,15 +886,23 @@ def profile_pair_fill(dm: DeviceMachine, mode: int, x, logP, env=None) -> np.nda
     return cells
 
 
-def profile_pair_fill_merged(dm: DeviceMachine, mode: int, x, logP, colTok) -> np.ndarray:
+def profile_pair_fill_merged(dm: DeviceMachine, mode: int, x, logP, colTok, env=None) -> np.ndarray:
     """One pair's lattice against a merged profile, [len(x) + 1, rows + 1, 2, nCols + 1, nStates] (layer 0 = arrived at (i, row),
-    1 = after the output-less moves; plane 0 = the last row took the blank, plane c = it took column c)."""
+    1 = after the output-less moves; plane 0 = the last row took the blank, plane c = it took column c).  ``env``: a
+    seqpair.Envelope or (inStart, inEnd); the cells outside it are -inf in both layers and all planes."""
     ct = np.ascontiguousarray(np.asarray(colTok).reshape(-1), np.int32)
     P = np.ascontiguousarray(np.asarray(logP, np.float64).reshape(-1, len(ct) + 1))
     xs = np.ascontiguousarray(np.asarray(x, np.int64).reshape(-1), np.int32)
     cells = np.empty((len(xs) + 1, len(P) + 1, 2, len(ct) + 1, dm.nStates), np.float64)
-    _check(load().mb_profile_pair_fill_merged(dm.h, mode, _p(xs, C.c_int32), len(xs), _p(P, C.c_double), len(P), len(ct),
-                                              _p(ct, C.c_int32), _p(cells, C.c_double)))
+    if env is None:
+        _check(load().mb_profile_pair_fill_merged(dm.h, mode, _p(xs, C.c_int32), len(xs), _p(P, C.c_double), len(P), len(ct),
+                                                  _p(ct, C.c_int32), _p(cells, C.c_double)))
+        return cells
+    a, b = _env_rows(env)
+    if len(a) != len(P) + 1:
+        raise MbError("Envelope/sequence mismatch")
+    _check(load().mb_profile_pair_fill_merged_env(dm.h, mode, _p(xs, C.c_int32), len(xs), _p(P, C.c_double), len(P), len(ct),
+                                                  _p(ct, C.c_int32), _p(a, C.c_int32), _p(b, C.c_int32), _p(cells, C.c_double)))
     return cells
 
 

@@ -473,7 +473,7 @@ static long long pp_rows(const mb_profile_pairs *p, long long k) { return p->row
 static bool pp_env(const mb_profile_pairs *p, long long k) { return p->hasEnv && p->envBase[(size_t)k] >= 0; }
 // doubles of pair k's materialised lattice: the rectangle, or the compact lattice of its envelope
 static long long pp_cells(const mb_profile_pairs *p, long long k) {
-  if (pp_env(p, k)) return p->envCells[(size_t)k] * 2 * (long long)p->m->S;
+  if (pp_env(p, k)) return p->envCells[(size_t)k] * 2 * (long long)p->m->S * (p->nCols + 1);
   return profile_pair_cells(p->m->S, pp_in(p, k), pp_rows(p, k)) * (p->nCols + 1);
 }
 static double pp_cell_bytes(const mb_profile_pairs *p, long long k) { return 8.0 * (double)pp_cells(p, k); }
@@ -481,11 +481,13 @@ static long long pp_path_bound(const mb_profile_pairs *p, long long k) { return 
 // The ring of pair k's sweep and its dynamic LDS (0: a slice of the global scratch buffer).  Plain profiles: the rolling sweep alone
 // has one.  Merged: the materialised sweeps keep their exclusion vectors in one too (mb_profile_pair_merge.h).
 static long long pp_ring(const mb_profile_pairs *p, long long k, bool rolling) {
+  if (p->nCols && pp_env(p, k)) return profile_pair_merge_env_ring(p->m->S, p->nCols, p->envM[(size_t)k], !rolling);
   if (p->nCols) return profile_pair_merge_ring(p->m->S, p->nCols, pp_in(p, k), pp_rows(p, k), !rolling);
   if (pp_env(p, k)) return rolling ? profile_pair_env_ring(p->m->S, p->envM[(size_t)k]) : 0;
   return rolling ? profile_pair_ring(p->m->S, pp_in(p, k), pp_rows(p, k)) : 0;
 }
 static size_t pp_ring_lds(const mb_profile_pairs *p, long long k, bool rolling) {
+  if (p->nCols && pp_env(p, k)) return profile_pair_merge_env_lds_bytes(p->m->S, p->nCols, p->envM[(size_t)k], !rolling);
   if (p->nCols) return profile_pair_merge_lds_bytes(p->m->S, p->nCols, pp_in(p, k), pp_rows(p, k), !rolling);
   if (pp_env(p, k)) return rolling ? profile_pair_env_lds_bytes(p->m->S, p->envM[(size_t)k]) : 0;
   return rolling ? profile_pair_lds_bytes(p->m->S, pp_in(p, k), pp_rows(p, k)) : 0;
@@ -526,7 +528,7 @@ static int pair_profile_descs(const mb_profile_pairs *p, long long p0, long long
     d.cellBase = pl.cells; d.pathBase = pl.paths; d.ringBase = ringBase;
     if (pp_env(p, k)) {
       d.envBase = p->envBase[(size_t)k]; d.diagBase = p->diagBase[(size_t)k]; d.nCells = p->envCells[(size_t)k]; d.M = p->envM[(size_t)k];
-      pl.maxItemsEnv = std::max(pl.maxItemsEnv, (long long)d.M * S);
+      pl.maxItemsEnv = std::max(pl.maxItemsEnv, (long long)d.M * S * (p->nCols + 1));
       he.push_back(d); envPairs.push_back(k);
     } else {
       pl.maxItems = std::max(pl.maxItems, (std::min(I, L) + 1) * S * (p->nCols + 1));
@@ -555,25 +557,40 @@ static auto pp_build(const mb_profile_pairs *p, bool rolling, PairWhere &where) 
 static PairEnvTables pp_env_tables(const mb_profile_pairs *p) { return PairEnvTables{p->d_envStart, p->d_envEnd, p->d_envOff, p->d_diagLo, p->d_diagCnt}; }
 
 // The one place where the plain and the merged kernels part: the launches of a chunk and the names they report.  The plain kernels
-// take the chunk's full pairs, then its pairs under an envelope, through the two overloads of one launcher.
-static int pp_launch_fwd(const mb_profile_pairs *p, int mode, bool mat, const PairProfPlan &pl, long long n, double *pool, double *scratch, double *ll) {
-  if (p->nCols) return launch_profile_pair_merge_fwd(p->m, pp_map(p), mode, mat, pl.d.p, (int)n, pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, ll, g_stream);
+// and the merged ones alike take the chunk's full pairs, then its pairs under an envelope, through the two overloads of one launcher;
+// the second launch's per-pair outputs (ll, len) follow the first's, at + nPlain.
+static int pp_launch_fwd(const mb_profile_pairs *p, int mode, bool mat, const PairProfPlan &pl, double *pool, double *scratch, double *ll) {
+  if (p->nCols) {
+    if (launch_profile_pair_merge_fwd(p->m, pp_map(p), mode, mat, pl.d.p, (int)pl.nPlain, pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, ll, g_stream)) return 1;
+    return launch_profile_pair_merge_fwd(p->m, pp_map(p), mode, mat, pl.e.p, pp_env_tables(p), (int)pl.nEnv, pl.ldsEnv, pl.maxItemsEnv, p->d_in, p->d_logP, pool, scratch,
+                                         ll + pl.nPlain, g_stream);
+  }
   if (launch_profile_pair_fwd(p->m, mode, mat, pl.d.p, (int)pl.nPlain, mat ? 0 : pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, mat ? nullptr : scratch, ll, g_stream)) return 1;
   return launch_profile_pair_fwd(p->m, mode, mat, pl.e.p, pp_env_tables(p), (int)pl.nEnv, mat ? 0 : pl.ldsEnv, pl.maxItemsEnv, p->d_in, p->d_logP, pool,
                                  mat ? nullptr : scratch, ll + pl.nPlain, g_stream);
 }
-static int pp_launch_bwd(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, double *pool, double *scratch, double *ll) {
-  if (p->nCols) return launch_profile_pair_merge_bwd(p->m, pp_map(p), pl.d.p, (int)n, pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, ll, g_stream);
+static int pp_launch_bwd(const mb_profile_pairs *p, const PairProfPlan &pl, double *pool, double *scratch, double *ll) {
+  if (p->nCols) {
+    if (launch_profile_pair_merge_bwd(p->m, pp_map(p), pl.d.p, (int)pl.nPlain, pl.lds, pl.maxItems, p->d_in, p->d_logP, pool, scratch, ll, g_stream)) return 1;
+    return launch_profile_pair_merge_bwd(p->m, pp_map(p), pl.e.p, pp_env_tables(p), (int)pl.nEnv, pl.ldsEnv, pl.maxItemsEnv, p->d_in, p->d_logP, pool, scratch,
+                                         ll + pl.nPlain, g_stream);
+  }
   if (launch_profile_pair_bwd(p->m, pl.d.p, (int)pl.nPlain, pl.maxItems, p->d_in, p->d_logP, pool, ll, g_stream)) return 1;
   return launch_profile_pair_bwd(p->m, pl.e.p, pp_env_tables(p), (int)pl.nEnv, pl.maxItemsEnv, p->d_in, p->d_logP, pool, ll + pl.nPlain, g_stream);
 }
-static int pp_launch_traceback(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, const double *pool, uint32_t *e, int32_t *r, long long *len) {
-  if (p->nCols) return launch_profile_pair_merge_traceback(p->m, pp_map(p), pl.d.p, (int)n, p->d_in, p->d_logP, pool, e, r, len, g_stream);
+static int pp_launch_traceback(const mb_profile_pairs *p, const PairProfPlan &pl, const double *pool, uint32_t *e, int32_t *r, long long *len) {
+  if (p->nCols) {
+    if (launch_profile_pair_merge_traceback(p->m, pp_map(p), pl.d.p, (int)pl.nPlain, p->d_in, p->d_logP, pool, e, r, len, g_stream)) return 1;
+    return launch_profile_pair_merge_traceback(p->m, pp_map(p), pl.e.p, pp_env_tables(p), (int)pl.nEnv, p->d_in, p->d_logP, pool, e, r, len + pl.nPlain, g_stream);
+  }
   if (launch_profile_pair_traceback(p->m, pl.d.p, (int)pl.nPlain, p->d_in, p->d_logP, pool, e, r, len, g_stream)) return 1;
   return launch_profile_pair_traceback(p->m, pl.e.p, pp_env_tables(p), (int)pl.nEnv, p->d_in, p->d_logP, pool, e, r, len + pl.nPlain, g_stream);
 }
-static int pp_launch_counts(const mb_profile_pairs *p, const PairProfPlan &pl, long long n, int groups, const double *fwd, const double *bwd, double *cc) {
-  if (p->nCols) return launch_profile_pair_merge_counts(p->m, pp_map(p), pl.d.p, (int)n, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
+static int pp_launch_counts(const mb_profile_pairs *p, const PairProfPlan &pl, int groups, const double *fwd, const double *bwd, double *cc) {
+  if (p->nCols) {
+    if (launch_profile_pair_merge_counts(p->m, pp_map(p), pl.d.p, (int)pl.nPlain, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream)) return 1;
+    return launch_profile_pair_merge_counts(p->m, pp_map(p), pl.e.p, pp_env_tables(p), (int)pl.nEnv, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
+  }
   if (launch_profile_pair_counts(p->m, pl.d.p, (int)pl.nPlain, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream)) return 1;
   return launch_profile_pair_counts(p->m, pl.e.p, pp_env_tables(p), (int)pl.nEnv, groups, p->d_in, p->d_logP, fwd, bwd, cc, g_stream);
 }
@@ -581,11 +598,18 @@ static int pp_launch_rowpost(const mb_profile_pairs *p, const PairProfPlan &pl, 
   if (launch_profile_pair_rowpost(p->m, pl.d.p, (int)pl.nPlain, groups, tabMax, p->d_in, p->d_logP, fwd, bwd, post, g_stream)) return 1;
   return launch_profile_pair_rowpost(p->m, pl.e.p, pp_env_tables(p), (int)pl.nEnv, groups, tabMax, p->d_in, p->d_logP, fwd, bwd, post, g_stream);
 }
+// the merged row posteriors; ll: the chunk's Forward log-likelihoods, in the order of the plan's slots
+static int pp_launch_merge_rowpost(const mb_profile_pairs *p, const PairProfPlan &pl, int groups, int tabMax, const double *fwd, const double *bwd, const double *ll, double *post) {
+  if (launch_profile_pair_merge_rowpost(p->m, pp_map(p), pl.d.p, (int)pl.nPlain, groups, tabMax, p->d_in, p->d_logP, fwd, bwd, ll, post, g_stream)) return 1;
+  return launch_profile_pair_merge_rowpost(p->m, pp_map(p), pl.e.p, pp_env_tables(p), (int)pl.nEnv, groups, tabMax, p->d_in, p->d_logP, fwd, bwd, ll + pl.nPlain, post, g_stream);
+}
 static const char *pp_fwd_name(const mb_profile_pairs *p, int mode, bool mat) {
   static const char *const names[2][2][2] = {{{"k_profile_pair_fwd<sum,rolling>", "k_profile_pair_fwd<sum,mat>"}, {"k_profile_pair_fwd<max,rolling>", "k_profile_pair_fwd<max,mat>"}},
                                              {{"k_profile_pair_merge_fwd<sum,rolling>", "k_profile_pair_merge_fwd<sum,mat>"}, {"k_profile_pair_merge_fwd<max,rolling>", "k_profile_pair_merge_fwd<max,mat>"}}};
   static const char *const envNames[2][2] = {{"k_profile_pair_env_fwd<sum,rolling>", "k_profile_pair_env_fwd<sum,mat>"}, {"k_profile_pair_env_fwd<max,rolling>", "k_profile_pair_env_fwd<max,mat>"}};
-  if (p->hasEnv) return envNames[mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];      // (a batch that mixes both kinds reports the envelope kernel)
+  static const char *const mergeEnvNames[2][2] = {{"k_profile_pair_merge_env_fwd<sum,rolling>", "k_profile_pair_merge_env_fwd<sum,mat>"},
+                                                  {"k_profile_pair_merge_env_fwd<max,rolling>", "k_profile_pair_merge_env_fwd<max,mat>"}};
+  if (p->hasEnv) return (p->nCols ? mergeEnvNames : envNames)[mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];      // (a batch that mixes both kinds reports the envelope kernel)
   return names[p->nCols ? 1 : 0][mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
 }
 
@@ -601,7 +625,7 @@ static int pair_profile_scores(mb_profile_pairs *p, int mode, bool mat, double *
     if (mat && !(pool = ws_array<double>(0, pl.cells))) return 1;
     if (pl.ring && !(scratch = (double *)ws_get(1, (size_t)pl.ring * sizeof(double)))) return 1;
     Timed t(tm, pl.launches());
-    return pp_launch_fwd(p, mode, mat, pl, c.p1 - c.p0, pool, scratch, d_ll + c.p0);
+    return pp_launch_fwd(p, mode, mat, pl, pool, scratch, d_ll + c.p0);
   });
   if (!rc) rc = fetch_loglike(loglike, d_ll, p->n, &where);
   g_last_kernel = pp_fwd_name(p, mode, mat);
@@ -662,12 +686,13 @@ static bool env_upload(void **dst, const void *src, size_t bytes) {
   return hip_ok(hipMalloc(dst, std::max<size_t>(bytes, 8)), "hipMalloc(pair envelopes)") && h2d_large(*dst, src, bytes) == 0;
 }
 
-// A rejected call leaves the pairs without envelopes.
-static int profile_pairs_set_envelopes(mb_profile_pairs *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
+// A rejected call leaves the pairs without envelopes.  merged: the call came through the merged pairs' own entry.
+static int profile_pairs_set_envelopes(mb_profile_pairs *p, bool merged, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
   pp_env_free(p);
+  if (merged && !p->nCols) { set_error("merged envelopes take merged profiles"); return 1; }
   if (!envOff) return 0;
   const long long total = envOff[p->n] - envOff[0];
-  if (total && p->nCols) { set_error("envelopes take plain profiles"); return 1; }
+  if (total && p->nCols && !merged) { set_error("envelopes take plain profiles"); return 1; }
   if (total && (!inStart || !inEnd)) { set_error("null argument"); return 1; }
   EnvHost h(p->n);
   for (long long k = 0; k < p->n; ++k) {
@@ -734,7 +759,7 @@ static int profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int6
   const bool env = envStart && envEnd;
   if (env) {
     const int64_t eOff[2] = {0, nRows + 1};
-    if (profile_pairs_set_envelopes(p, eOff, envStart, envEnd)) { mb_profile_pairs_destroy(p); return 1; }
+    if (profile_pairs_set_envelopes(p, nCols > 0, eOff, envStart, envEnd)) { mb_profile_pairs_destroy(p); return 1; }
   }
   std::vector<Chunk> chunks;
   if (!lattice_chunks(p->n, "pair", [&](long long k) { return pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false); }, chunks)) { mb_profile_pairs_destroy(p); return 1; }
@@ -744,10 +769,10 @@ static int profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int6
     rc = pair_profile_descs(p, 0, 1, false, pl);
     std::vector<double> compact(!rc && env ? (size_t)pl.cells : 0);      // under an envelope the lattice comes back compact
     if (!rc) rc = fill_one(pl.cells, pl.ring, env ? compact.data() : cellsOut, [&](double *pool, double *scratch, double *d_ll) {
-      return mode == MB_BACKWARD ? pp_launch_bwd(p, pl, 1, pool, scratch, d_ll) : pp_launch_fwd(p, mode, true, pl, 1, pool, scratch, d_ll);
+      return mode == MB_BACKWARD ? pp_launch_bwd(p, pl, pool, scratch, d_ll) : pp_launch_fwd(p, mode, true, pl, pool, scratch, d_ll);
     });
     if (!rc && env) {      // the compact lattice into the full rectangle, -inf outside the envelope
-      const size_t cellD = 2 * (size_t)m->S;
+      const size_t cellD = 2 * (size_t)m->S * (size_t)(nCols + 1);
       std::fill(cellsOut, cellsOut + (size_t)(nIn + 1) * (size_t)(nRows + 1) * cellD, -INFINITY);
       size_t at = 0;
       for (int64_t r = 0; r <= nRows; ++r)
@@ -755,7 +780,8 @@ static int profile_pair_fill(mb_machine *m, int mode, const int32_t *inTok, int6
           std::memcpy(cellsOut + ((size_t)i * (size_t)(nRows + 1) + (size_t)r) * cellD, compact.data() + at, cellD * sizeof(double));
     }
   }
-  g_last_kernel = mode == MB_BACKWARD ? (nCols ? "k_profile_pair_merge_bwd" : (env ? "k_profile_pair_env_bwd" : "k_profile_pair_bwd")) : pp_fwd_name(p, mode, true);
+  g_last_kernel = mode == MB_BACKWARD ? (nCols ? (env ? "k_profile_pair_merge_env_bwd" : "k_profile_pair_merge_bwd") : (env ? "k_profile_pair_env_bwd" : "k_profile_pair_bwd"))
+                                      : pp_fwd_name(p, mode, true);
   mb_profile_pairs_destroy(p);
   return rc;
 }
@@ -789,7 +815,13 @@ void mb_profile_pairs_destroy(mb_profile_pairs *p) {
 int mb_profile_pairs_set_envelopes(mb_profile_pairs *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
   ApiGuard guard;
   if (!p) { set_error("null argument"); return 1; }
-  return profile_pairs_set_envelopes(p, envOff, inStart, inEnd);
+  return profile_pairs_set_envelopes(p, false, envOff, inStart, inEnd);
+}
+
+int mb_profile_pairs_set_envelopes_merged(mb_profile_pairs *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
+  ApiGuard guard;
+  if (!p) { set_error("null argument"); return 1; }
+  return profile_pairs_set_envelopes(p, true, envOff, inStart, inEnd);
 }
 
 int64_t mb_profile_pairs_cells(const mb_profile_pairs *p) {
@@ -839,7 +871,7 @@ int mb_profile_pairs_viterbi(mb_profile_pairs *p, double *loglike, int64_t *path
     if (!pool || !d_e || !d_r || (pl.ring && !scratch)) return 1;
     {
       Timed t(tm, pl.launches());
-      if (pp_launch_fwd(p, MB_VITERBI, true, pl, np, pool, scratch, d_ll + c.p0) || pp_launch_traceback(p, pl, np, pool, d_e, d_r, d_len + c.p0)) return 1;
+      if (pp_launch_fwd(p, MB_VITERBI, true, pl, pool, scratch, d_ll + c.p0) || pp_launch_traceback(p, pl, pool, d_e, d_r, d_len + c.p0)) return 1;
     }
     return unpack_paths(out, c.p0, np, pl.paths, &pl.slot, d_len + c.p0, d_e, d_r);
   });
@@ -871,16 +903,16 @@ int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglike
     if (np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); return 1; }
     {
       Timed t(tm, pl.launches());
-      if (pp_launch_fwd(p, MB_FORWARD, true, pl, np, fwd, scratch, d_ll + c.p0)) return 1;      // (merged: the Backward's ring follows the Forward's on the stream, one scratch buffer serves both)
-      if (pp_launch_bwd(p, pl, np, bwd, scratch, d_bll + c.p0)) return 1;
+      if (pp_launch_fwd(p, MB_FORWARD, true, pl, fwd, scratch, d_ll + c.p0)) return 1;      // (merged: the Backward's ring follows the Forward's on the stream, one scratch buffer serves both)
+      if (pp_launch_bwd(p, pl, bwd, scratch, d_bll + c.p0)) return 1;
       if (nT && !hip_ok(hipMemsetAsync(d_cc, 0, (size_t)nT * sizeof(double), g_stream), "memset(counts)")) return 1;
-      if (pp_launch_counts(p, pl, np, groups, fwd, bwd, d_cc)) return 1;
+      if (pp_launch_counts(p, pl, groups, fwd, bwd, d_cc)) return 1;
     }
     return sum.add(d_cc, g_deterministic);
   });
   std::vector<double> hll((size_t)p->n);
   if (!rc) rc = fetch_loglike(hll.data(), d_ll, p->n, &where);
-  g_last_kernel = p->nCols ? "k_profile_pair_merge_counts" : (p->hasEnv ? "k_profile_pair_env_counts" : "k_profile_pair_counts");
+  g_last_kernel = p->nCols ? (p->hasEnv ? "k_profile_pair_merge_env_counts" : "k_profile_pair_merge_counts") : (p->hasEnv ? "k_profile_pair_env_counts" : "k_profile_pair_counts");
   if (rc) return rc;
   sum.finish(hll, counts, loglikeSum, loglike);
   return 0;
@@ -913,7 +945,7 @@ int mb_profile_pairs_row_posteriors(mb_profile_pairs *p, double *post, double *l
     if (np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); return 1; }
     {
       Timed t(tm, pl.launches());
-      if (pp_launch_fwd(p, MB_FORWARD, true, pl, np, fwd, nullptr, d_ll + c.p0) || pp_launch_bwd(p, pl, np, bwd, nullptr, d_bll + c.p0) ||
+      if (pp_launch_fwd(p, MB_FORWARD, true, pl, fwd, nullptr, d_ll + c.p0) || pp_launch_bwd(p, pl, bwd, nullptr, d_bll + c.p0) ||
           pp_launch_rowpost(p, pl, (int)groups, tabMax, fwd, bwd, d_post)) return 1;
     }
     return hip_ok(hipStreamSynchronize(g_stream), "row posteriors") ? 0 : 1;      // (the next chunk takes the lattices over)
@@ -965,14 +997,14 @@ int mb_profile_pairs_row_posteriors_merged(mb_profile_pairs *p, double *post, do
     if (np * groups > 0x7fffffff) { set_error("too many pairs in one chunk"); return 1; }
     {
       Timed t(tm, pl.launches());
-      if (pp_launch_fwd(p, MB_FORWARD, true, pl, np, fwd, scratch, d_ll + c.p0) || pp_launch_bwd(p, pl, np, bwd, scratch, d_bll + c.p0) ||
-          launch_profile_pair_merge_rowpost(m, pp_map(p), pl.d.p, (int)np, (int)groups, tabMax, p->d_in, p->d_logP, fwd, bwd, d_ll + c.p0, d_post, g_stream)) return 1;
+      if (pp_launch_fwd(p, MB_FORWARD, true, pl, fwd, scratch, d_ll + c.p0) || pp_launch_bwd(p, pl, bwd, scratch, d_bll + c.p0) ||
+          pp_launch_merge_rowpost(p, pl, (int)groups, tabMax, fwd, bwd, d_ll + c.p0, d_post)) return 1;
     }
     return hip_ok(hipStreamSynchronize(g_stream), "row posteriors") ? 0 : 1;      // (the next chunk takes the lattices over)
   });
   if (!rc) rc = fetch_posteriors(post, d_post, nv);
   if (!rc && loglike) rc = fetch_loglike(loglike, d_ll, p->n, &where);
-  g_last_kernel = "k_profile_pair_merge_rowpost";
+  g_last_kernel = p->hasEnv ? "k_profile_pair_merge_env_rowpost" : "k_profile_pair_merge_rowpost";
   return rc;
 }
 
@@ -1004,6 +1036,14 @@ int mb_profile_pair_fill_merged(mb_machine *m, int mode, const int32_t *inTok, i
   ApiGuard guard;
   if (!merge_map_ok(m, nCols, colTok)) return 1;
   return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, nCols, colTok, nullptr, nullptr, cellsOut);
+}
+
+int mb_profile_pair_fill_merged_env(mb_machine *m, int mode, const int32_t *inTok, int64_t nIn, const double *logP, int64_t nRows, int32_t nCols,
+                                    const int32_t *colTok, const int32_t *envStart, const int32_t *envEnd, double *cellsOut) {
+  ApiGuard guard;
+  if ((envStart == nullptr) != (envEnd == nullptr)) { set_error("null argument"); return 1; }
+  if (!merge_map_ok(m, nCols, colTok)) return 1;
+  return profile_pair_fill(m, mode, inTok, nIn, logP, nRows, nCols, colTok, envStart, envEnd, cellsOut);
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 // are a run of consecutive i.
 //
 // Materialised lattices are COMPACT: cells[((off[r] + i - inStart[r]) * 2 + layer) * S + q], off[r] = the cells of the rows < r.
+// The pairs against CTC-merged profiles take the same envelopes, descriptors and tables (mb_profile_pair_merge.h), with nCols + 1
+// planes in every cell.
 #pragma once
 #include "mb_profile_pair.h"
 

@@ -8,9 +8,14 @@
 // output-less moves there"; plane 0 = "the last row took the blank, or no row yet", plane c = "the last row took column c".
 // PairProfDesc is shared with the plain pair sweeps: rowBase counts rows of nCols + 1 doubles, cellBase doubles of this layout,
 // ringBase the pair's slice of the global scratch buffer (-1: its ring is in LDS).
+//
+// Under an ENVELOPE (mb_profile_pair_env.h; docs/profile_tapes.md, "Pairs against a merged profile under an envelope") cell (i, r)
+// exists iff inStart[r] <= i < inEnd[r], in every plane; everything else is -inf.  Materialised lattices are then COMPACT:
+// cells[(((off[r] + i - inStart[r]) * 2 + layer) * (nCols + 1) + p) * S + q], off[r] = the cells of the rows < r.  The descriptor
+// and the tables are those of the plain pairs under an envelope, PairEnvDesc and PairEnvTables.
 #pragma once
 #include "mb_profile_merge.h"
-#include "mb_profile_pair.h"
+#include "mb_profile_pair_env.h"
 
 namespace mb {
 
@@ -25,6 +30,11 @@ inline long long profile_pair_merge_ring(int S, int nCols, long long nIn, long l
 }
 // dynamic LDS of a pair's ring when it fits 160 KiB (0: a slice of the global scratch buffer)
 size_t profile_pair_merge_lds_bytes(int S, int nCols, long long nIn, long long nRows, bool mat);
+// the same under an envelope: three anti-diagonals of M cells, M the largest cell count of a diagonal; a cell lives at i mod M
+inline long long profile_pair_merge_env_ring(int S, int nCols, long long M, bool mat) {
+  return 3 * (mat ? (long long)nCols : 3LL * nCols + 2) * M * (long long)S;
+}
+size_t profile_pair_merge_env_lds_bytes(int S, int nCols, long long M, bool mat);
 
 // lds: the dynamic LDS of the launch (the largest ring among the pairs whose ringBase is -1); maxItems: the most (cell, plane,
 // state) items on one diagonal of the batch
@@ -43,6 +53,21 @@ int launch_profile_pair_merge_rowpost(const mb_machine *m, MergeMap mm, const Pa
                                       const int *inTok, const double *logP, const double *fwdPool, const double *bwdPool,
                                       const double *loglike, double *post, hipStream_t st);
 int launch_profile_pair_merge_traceback(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, const int *inTok,
+                                        const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len,
+                                        hipStream_t st);
+
+// the launchers above over pairs under an envelope (lds, maxItems: of the envelope rings and diagonals)
+int launch_profile_pair_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const PairEnvDesc *d, const PairEnvTables &t, int n, size_t lds,
+                                  long long maxItems, const int *inTok, const double *logP, double *pool, double *scratch,
+                                  double *loglike, hipStream_t st);
+int launch_profile_pair_merge_bwd(const mb_machine *m, MergeMap mm, const PairEnvDesc *d, const PairEnvTables &t, int n, size_t lds, long long maxItems,
+                                  const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st);
+int launch_profile_pair_merge_counts(const mb_machine *m, MergeMap mm, const PairEnvDesc *d, const PairEnvTables &t, int n, int groupsPerPair, const int *inTok,
+                                     const double *logP, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
+int launch_profile_pair_merge_rowpost(const mb_machine *m, MergeMap mm, const PairEnvDesc *d, const PairEnvTables &t, int n, int groupsPerPair, int tabMax,
+                                      const int *inTok, const double *logP, const double *fwdPool, const double *bwdPool,
+                                      const double *loglike, double *post, hipStream_t st);
+int launch_profile_pair_merge_traceback(const mb_machine *m, MergeMap mm, const PairEnvDesc *d, const PairEnvTables &t, int n, const int *inTok,
                                         const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len,
                                         hipStream_t st);
 

@@ -19,6 +19,11 @@
 // edge loop runs over planes -- (I + L + 1)(nLevF + 1) barriers per pair.  The rolling sweeps keep a ring of three diagonals of N, W
 // and X, 3 (3 nCols + 2)(min(I, L) + 1) S doubles, in LDS when that fits 160 KiB, else in the pair's slice of a global scratch
 // buffer; the materialised ones keep only X there.  Cells are fp64, the sums the exact log-sum-exp.
+//
+// Every kernel is written once over PairMergeLattice, which says which cells exist and where they live: its full form, the whole
+// rectangle, or its envelope form, the cells of an envelope (docs/profile_tapes.md, "Pairs against a merged profile under an
+// envelope").  Every plane of both layers of a cell outside the envelope is -inf, and so are its X and T, so a neighbour outside is
+// not read; the recurrence, the candidate order and the sums are the same text for both.
 #include "mb_profile_common.h"
 #include "mb_profile_pair_merge.h"
 
@@ -29,13 +34,33 @@ size_t profile_pair_merge_lds_bytes(int S, int nCols, long long nIn, long long n
   return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
 }
 
-// Where cell (i, r) lives.  nw(i, r, layer): its N (layer 0) or W (layer 1), nCols + 1 planes of S states -- the materialised
-// lattice, or the ring (diagonal (i + r) mod 3, the cell by its coordinate on the short side of the lattice).  xv(i, r): its
-// exclusion vectors, column c at (c - 1) * S -- always in the ring, beside N and W when rolling.
+size_t profile_pair_merge_env_lds_bytes(int S, int nCols, long long M, bool mat) {
+  const double b = (double)profile_pair_merge_env_ring(S, nCols, M, mat) * sizeof(double);
+  return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
+}
+
+struct NoMergeTables {};      // what the full form needs beside a pair's descriptor
+
+// Where cell (i, r) lives and whether it exists.  nw(i, r, layer): its N (layer 0) or W (layer 1), nCols + 1 planes of S states --
+// the materialised lattice, or the ring.  xv(i, r): its exclusion vectors, column c at (c - 1) * S -- always in the ring, beside N
+// and W when rolling.  diag(d): the cells of anti-diagonal d, i = ilo .. ilo + nCells - 1.  cell / rowCell: the c-th cell of the
+// pair as the counts and the row posteriors enumerate them (row r holds the cells rowFirst(r) .. rowFirst(r + 1) - 1, ascending i).
+template <bool MAT, bool ENV>
+struct PairMergeLattice;
+
+// The whole rectangle: the lattice of mb_profile_pair_merge.h; in the ring diagonal (i + r) mod 3, the cell by its coordinate on the
+// short side of the lattice.
 template <bool MAT>
-struct PairMergeLattice {
+struct PairMergeLattice<MAT, false> {
+  using Desc = PairProfDesc;
+  using Tables = NoMergeTables;
   double *cells, *ring;
-  int S, PL, L, M, byI;
+  int S, PL, I, L, M, byI;
+  __device__ __forceinline__ PairMergeLattice(const Desc &pd, Tables, double *cells, double *ring, int S, int PL)
+      : cells(cells), ring(ring), S(S), PL(PL), I(pd.nIn), L(pd.nRows), M(min(pd.nIn, pd.nRows) + 1), byI(pd.nIn <= pd.nRows) {}
+  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = max(0, d - L); nCells = min(I, d) - ilo + 1; }
+  // asked of neighbours the caller has already bounded to the rectangle
+  static constexpr __device__ __forceinline__ bool inside(int, int) { return true; }
   __device__ __forceinline__ long long slot(int i, int r) const { return (long long)((i + r) % 3) * M + (byI ? i : r); }
   __device__ __forceinline__ double *nw(int i, int r, int layer) const {
     if (MAT) return cells + ((((long long)i * (L + 1)) + r) * 2 + layer) * PL * S;
@@ -45,27 +70,77 @@ struct PairMergeLattice {
     if (MAT) return ring + slot(i, r) * (PL - 1) * S;
     return ring + (slot(i, r) * (3 * PL - 1) + 2 * PL) * S;
   }
+  __device__ __forceinline__ long long nCells() const { return (long long)(I + 1) * (L + 1); }
+  __device__ __forceinline__ void cell(long long c, int &i, int &r) const { i = (int)(c / (L + 1)); r = (int)(c - (long long)i * (L + 1)); }
+  __device__ __forceinline__ long long rowFirst(int r) const { return (long long)r * (I + 1); }
+  __device__ __forceinline__ void rowCell(long long c, int &i, int &r) const { r = (int)(c / (I + 1)); i = (int)(c - (long long)r * (I + 1)); }
+};
+
+// The cells of an envelope (mb_profile_pair_env.h): the compact lattice cells[(((off[r] + i - inStart[r]) * 2 + layer) * (nCols + 1)
+// + p) * S + q]; in the ring diagonal (i + r) mod 3, the cell at i mod M, M the largest cell count of a diagonal of the pair -- the
+// cells of a diagonal have consecutive i and number at most M, so no two share a slot.  A slot may hold a stale cell of another
+// row; it is never read, because inside() is asked first.
+template <bool MAT>
+struct PairMergeLattice<MAT, true> {
+  using Desc = PairEnvDesc;
+  using Tables = PairEnvTables;
+  double *cells, *ring;
+  const int *st, *en;         // the pair's envelope rows
+  const long long *off;       // compact index of the first cell of each row
+  const int *dLo, *dCnt;
+  long long nEnv;
+  int S, PL, L, M;
+  __device__ __forceinline__ PairMergeLattice(const Desc &pd, const Tables &t, double *cells, double *ring, int S, int PL)
+      : cells(cells), ring(ring), st(t.envStart + pd.envBase), en(t.envEnd + pd.envBase), off(t.envOff + pd.envBase),
+        dLo(t.diagLo + pd.diagBase), dCnt(t.diagCnt + pd.diagBase), nEnv(pd.nCells), S(S), PL(PL), L(pd.nRows), M(pd.M) {}
+  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = dLo[d]; nCells = dCnt[d]; }
+  // r in -1..L+1, i in -1..I+1
+  __device__ __forceinline__ bool inside(int i, int r) const { return r >= 0 && r <= L && i >= st[r] && i < en[r]; }
+  __device__ __forceinline__ long long slot(int i, int r) const { return (long long)((i + r) % 3) * M + (i % M); }
+  __device__ __forceinline__ double *nw(int i, int r, int layer) const {
+    if (MAT) return cells + ((off[r] + (i - st[r])) * 2 + layer) * PL * S;
+    return ring + (slot(i, r) * (3 * PL - 1) + layer * PL) * S;
+  }
+  __device__ __forceinline__ double *xv(int i, int r) const {
+    if (MAT) return ring + slot(i, r) * (PL - 1) * S;
+    return ring + (slot(i, r) * (3 * PL - 1) + 2 * PL) * S;
+  }
+  __device__ __forceinline__ long long nCells() const { return nEnv; }
+  __device__ __forceinline__ void cell(long long c, int &i, int &r) const {
+    int lo = 0, hi = L;                        // the last row whose offset is <= c: rows behind it start past the cell
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (off[mid] <= c) lo = mid; else hi = mid - 1;
+    }
+    r = lo; i = st[r] + (int)(c - off[r]);
+  }
+  // (the compact index already counts row by row; r <= L)
+  __device__ __forceinline__ long long rowFirst(int r) const { return off[r]; }
+  __device__ __forceinline__ void rowCell(long long c, int &i, int &r) const { cell(c, i, r); }
 };
 
 // Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every N and W cell into pool (layout of mb_profile_pair_merge.h)
 // and only X in the ring, else rolling.  Viterbi keeps the FIRST maximum: N[.][.][0] takes the planes ascending; N[.][.][c] the
 // repeat first, then the match edges in `incoming` order, then the output-only edges in `incoming` order; W takes N (no move)
 // first, then the input-only edges, then the silent edges, each in `incoming` order; X and the end the planes ascending -- the
-// order k_profile_pair_merge_traceback re-enumerates.
-template <int MODE, bool MAT>
-__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_fwd(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+// order k_profile_pair_merge_traceback re-enumerates.  A neighbour outside the lattice is -inf and is not read: (i, r - 1) feeds the
+// blank over all planes, the repeat and X of the output-only edges, (i - 1, r - 1) X of the match edges, (i - 1, r) W of the
+// input-only edges.
+template <int MODE, bool MAT, bool ENV>
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_fwd(DevMachine m, MergeMap mm, const typename PairMergeLattice<MAT, ENV>::Desc *__restrict__ descs,
+                                                                          typename PairMergeLattice<MAT, ENV>::Tables t,
                                                                           const int *__restrict__ inTok, const double *__restrict__ logP,
                                                                           double *pool, double *scratch, double *__restrict__ loglike) {
   extern __shared__ double ppm_sh[];
-  const PairProfDesc pd = descs[blockIdx.x];
+  const auto pd = descs[blockIdx.x];
   const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
   const int *x = inTok + pd.inBase;
   const double *P = logP + pd.rowBase * PL;
-  const PairMergeLattice<MAT> lat{MAT ? pool + pd.cellBase : nullptr, pd.ringBase < 0 ? ppm_sh : scratch + pd.ringBase, S, PL, L,
-                                  min(I, L) + 1, I <= L};
+  const PairMergeLattice<MAT, ENV> lat(pd, t, MAT ? pool + pd.cellBase : nullptr, pd.ringBase < 0 ? ppm_sh : scratch + pd.ringBase, S, PL);
   const int PS = PL * S;
   for (int d = 0; d <= I + L; ++d) {
-    const int ilo = max(0, d - L), nCells = min(I, d) - ilo + 1;
+    int ilo, nCells;
+    lat.diag(d, ilo, nCells);
     const int nItems = nCells * PS;
     for (int it = threadIdx.x; it < nItems; it += blockDim.x) {
       const int c = it / PS, pq = it - c * PS, p = pq / S, q = pq - p * S, i = ilo + c, r = d - i;
@@ -73,25 +148,30 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_fwd(DevMac
       double acc = (d == 0 && pq == 0) ? 0.0 : -INFINITY;
       if (r > 0) {
         const double w = P[(long long)(r - 1) * PL + p];
-        const double *Np = lat.nw(i, r - 1, 0);
+        const bool up = lat.inside(i, r - 1);
+        const double *Np = lat.nw(i, r - 1, 0);      // (an address alone: read only where the cell is inside)
         if (p == 0) {
-          acc = Np[q] + w;
-          for (int k = 1; k < PL; ++k) acc = red<MODE>(acc, Np[k * S + q] + w);
+          if (up) {
+            acc = Np[q] + w;
+            for (int k = 1; k < PL; ++k) acc = red<MODE>(acc, Np[k * S + q] + w);
+          }
         } else if (w > -INFINITY) {                          // (a column the row rules out is skipped as a whole)
           const int tok = mm.colTok[p - 1];
-          acc = Np[p * S + q] + w;
-          if (i > 0) {
+          if (up) acc = Np[p * S + q] + w;
+          if (i > 0 && lat.inside(i - 1, r - 1)) {
             const double *Xd = lat.xv(i - 1, r - 1) + (p - 1) * S;
             const int a1 = m.inOff[xRow + tok + 1];
             for (int a = m.inOff[xRow + tok]; a < a1; ++a) acc = red<MODE>(acc, (Xd[m.inSrc[a]] + m.inW[a]) + w);
           }
-          const double *Xu = lat.xv(i, r - 1) + (p - 1) * S;
-          const int a1 = m.inOff[q * K + tok + 1];
-          for (int a = m.inOff[q * K + tok]; a < a1; ++a) acc = red<MODE>(acc, (Xu[m.inSrc[a]] + m.inW[a]) + w);
+          if (up) {
+            const double *Xu = lat.xv(i, r - 1) + (p - 1) * S;
+            const int a1 = m.inOff[q * K + tok + 1];
+            for (int a = m.inOff[q * K + tok]; a < a1; ++a) acc = red<MODE>(acc, (Xu[m.inSrc[a]] + m.inW[a]) + w);
+          }
         }
       }
       lat.nw(i, r, 0)[pq] = acc;
-      if (i > 0) {
+      if (i > 0 && lat.inside(i - 1, r)) {
         const double *Wl = lat.nw(i - 1, r, 1) + p * S;
         const int a1 = m.inOff[xRow + 1];
         for (int a = m.inOff[xRow]; a < a1; ++a) acc = red<MODE>(acc, Wl[m.inSrc[a]] + m.inW[a]);
@@ -130,7 +210,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_fwd(DevMac
     }
   }
   if (threadIdx.x == 0) {
-    const double *We = lat.nw(I, L, 1) + S - 1;
+    const double *We = lat.nw(I, L, 1) + S - 1;      // (an envelope is connected: (0, 0) and (I, L) are inside)
     double acc = We[0];
     for (int p = 1; p < PL; ++p) acc = red<MODE>(acc, We[p * S]);
     loglike[blockIdx.x] = acc;
@@ -148,20 +228,23 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_fwd(DevMac
 // Anti-diagonals from I + L down.  T, everything that leaves (i, r, s) through column c, is formed once per diagonal over (cell,
 // column, state) -- the mirror of the Forward's X -- so the edge loops do not run over planes; it lives in the ring (one diagonal of
 // it, the cell by its place on the diagonal).  A state's WB is final once its backward level has run; the item that finishes it
-// writes its NB.
-__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_bwd(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+// writes its NB.  A successor cell outside the lattice contributes nothing.
+template <bool ENV>
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_bwd(DevMachine m, MergeMap mm, const typename PairMergeLattice<true, ENV>::Desc *__restrict__ descs,
+                                                                          typename PairMergeLattice<true, ENV>::Tables t,
                                                                           const int *__restrict__ inTok, const double *__restrict__ logP,
                                                                           double *pool, double *scratch, double *__restrict__ loglike) {
   extern __shared__ double ppm_sh[];
-  const PairProfDesc pd = descs[blockIdx.x];
+  const auto pd = descs[blockIdx.x];
   const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
   const int *x = inTok + pd.inBase;
   const double *P = logP + pd.rowBase * PL;
-  const PairMergeLattice<true> lat{pool + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  const PairMergeLattice<true, ENV> lat(pd, t, pool + pd.cellBase, nullptr, S, PL);
   double *T = pd.ringBase < 0 ? ppm_sh : scratch + pd.ringBase;       // T[(cell on the diagonal * nCols + c - 1) * S + s]
   const int PS = PL * S, XS = nC * S;
   for (int d = I + L; d >= 0; --d) {
-    const int ilo = max(0, d - L), nCells = min(I, d) - ilo + 1;
+    int ilo, nCells;
+    lat.diag(d, ilo, nCells);
     if (d < I + L) {
       const int nTItems = nCells * XS;
       for (int it = threadIdx.x; it < nTItems; it += blockDim.x) {
@@ -171,15 +254,17 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_bwd(DevMac
           const double pc = P[(long long)r * PL + col];
           if (pc > -INFINITY) {
             const int tok = mm.colTok[col - 1];
-            if (i < I) {
+            if (i < I && lat.inside(i + 1, r + 1)) {
               const double *Nd = lat.nw(i + 1, r + 1, 0) + col * S;
               const int xRow = s * K + x[i] * C;
               const int a1 = m.outOff[xRow + tok + 1];
               for (int a = m.outOff[xRow + tok]; a < a1; ++a) v = lse2_exact(v, (m.outW[a] + pc) + Nd[m.outDst[a]]);
             }
-            const double *Nu = lat.nw(i, r + 1, 0) + col * S;
-            const int a1 = m.outOff[s * K + tok + 1];
-            for (int a = m.outOff[s * K + tok]; a < a1; ++a) v = lse2_exact(v, (m.outW[a] + pc) + Nu[m.outDst[a]]);
+            if (lat.inside(i, r + 1)) {
+              const double *Nu = lat.nw(i, r + 1, 0) + col * S;
+              const int a1 = m.outOff[s * K + tok + 1];
+              for (int a = m.outOff[s * K + tok]; a < a1; ++a) v = lse2_exact(v, (m.outW[a] + pc) + Nu[m.outDst[a]]);
+            }
           }
         }
         T[it] = v;
@@ -195,14 +280,14 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_bwd(DevMac
         for (int col = 1; col < PL; ++col)
           if (col != k) v = lse2_exact(v, Tc[(col - 1) * S]);
       }
-      if (i < I) {
+      if (i < I && lat.inside(i + 1, r)) {
         const double *Wl = lat.nw(i + 1, r, 1) + k * S;
         const int xRow = s * K + x[i] * C;
         const int a1 = m.outOff[xRow + 1];
         for (int a = m.outOff[xRow]; a < a1; ++a) v = lse2_exact(v, Wl[m.outDst[a]] + m.outW[a]);
       }
       lat.nw(i, r, 1)[ks] = v;
-      if (r < L) {
+      if (r < L && lat.inside(i, r + 1)) {
         const double *Nn = lat.nw(i, r + 1, 0), *Pr = P + (long long)r * PL;
         v = lse2_exact(v, Pr[0] + Nn[s]);
         if (k) v = lse2_exact(v, Pr[k] + Nn[ks]);
@@ -224,7 +309,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_bwd(DevMac
           v = lse2_exact(v, Wc[t] + m.outW[a]);
         }
         Wc[s] = v;
-        if (r < L) {
+        if (r < L && lat.inside(i, r + 1)) {
           const double *Nn = lat.nw(i, r + 1, 0), *Pr = P + (long long)r * PL;
           v = lse2_exact(v, Pr[0] + Nn[s]);
           if (k) v = lse2_exact(v, Pr[k] + Nn[k * S + s]);
@@ -241,21 +326,23 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_pair_merge_bwd(DevMac
 //   count[t] += exp(W_F[i][r][k][s] - LL + term_t), term_t the edge's summand of WB[i][r][k][s] above (through T for the emitting
 //   edges: every column c != k),
 // so the sweep is a flat grid over (pair, group of the pair, (cell, plane, state)), accumulated by CountsAcc (mb_profile_common.h).
-// A pair whose likelihood is -inf adds nothing.
-__global__ __launch_bounds__(256) void k_profile_pair_merge_counts(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
-                                                                   int groupsPerPair, const int *__restrict__ inTok,
+// A pair whose likelihood is -inf adds nothing.  The cells are the lattice's own count (under an envelope the compact index, its row
+// found by bisection).
+template <bool ENV>
+__global__ __launch_bounds__(256) void k_profile_pair_merge_counts(DevMachine m, MergeMap mm, const typename PairMergeLattice<true, ENV>::Desc *__restrict__ descs,
+                                                                   typename PairMergeLattice<true, ENV>::Tables t, int groupsPerPair, const int *__restrict__ inTok,
                                                                    const double *__restrict__ logP, const double *__restrict__ fwdPool,
                                                                    const double *__restrict__ bwdPool, long long nTrans,
                                                                    double *__restrict__ counts, int det) {
   __shared__ double lcount[COUNTS_LDS_MAX];
   const CountsAcc acc(lcount, counts, nTrans, det);
   const int pair = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
-  const PairProfDesc pd = descs[pair];
+  const auto pd = descs[pair];
   const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
   const int *x = inTok + pd.inBase;
   const double *P = logP + pd.rowBase * PL;
-  const PairMergeLattice<true> F{const_cast<double *>(fwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0},
-      B{const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  const PairMergeLattice<true, ENV> F(pd, t, const_cast<double *>(fwdPool) + pd.cellBase, nullptr, S, PL),
+      B(pd, t, const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL);
   double LL;
   {
     const double *We = F.nw(I, L, 1) + S - 1;
@@ -263,30 +350,35 @@ __global__ __launch_bounds__(256) void k_profile_pair_merge_counts(DevMachine m,
     for (int p = 1; p < PL; ++p) LL = lse2_exact(LL, We[p * S]);
   }
   if (LL > -INFINITY) {
-    const long long PS = (long long)PL * S, nItems = (long long)(I + 1) * (L + 1) * PS;
+    const long long PS = (long long)PL * S, nItems = F.nCells() * PS;
     for (long long idx = (long long)group * blockDim.x + threadIdx.x; idx < nItems; idx += (long long)groupsPerPair * blockDim.x) {
       const long long cell = idx / PS;
-      const int ks = (int)(idx - cell * PS), k = ks / S, s = ks - k * S, i = (int)(cell / (L + 1)), r = (int)(cell - (long long)i * (L + 1));
+      const int ks = (int)(idx - cell * PS), k = ks / S, s = ks - k * S;
+      int i, r;
+      F.cell(cell, i, r);
       const double f = F.nw(i, r, 1)[ks] - LL;
       if (!(f > -INFINITY)) continue;
       const int xRow = i < I ? s * K + x[i] * C : 0;
       if (r < L) {
         const double *Pr = P + (long long)r * PL;
+        const bool across = i < I && B.inside(i + 1, r + 1), up = B.inside(i, r + 1);
         for (int col = 1; col < PL; ++col) {
           const double pc = Pr[col];
           if (col == k || !(pc > -INFINITY)) continue;
           const int tok = mm.colTok[col - 1];
-          if (i < I) {
+          if (across) {
             const double *Nd = B.nw(i + 1, r + 1, 0) + col * S;
             const int a1 = m.outOff[xRow + tok + 1];
             for (int a = m.outOff[xRow + tok]; a < a1; ++a) acc.add(m.outEid[a], exp(f + ((m.outW[a] + pc) + Nd[m.outDst[a]])));
           }
-          const double *Nu = B.nw(i, r + 1, 0) + col * S;
-          const int a1 = m.outOff[s * K + tok + 1];
-          for (int a = m.outOff[s * K + tok]; a < a1; ++a) acc.add(m.outEid[a], exp(f + ((m.outW[a] + pc) + Nu[m.outDst[a]])));
+          if (up) {
+            const double *Nu = B.nw(i, r + 1, 0) + col * S;
+            const int a1 = m.outOff[s * K + tok + 1];
+            for (int a = m.outOff[s * K + tok]; a < a1; ++a) acc.add(m.outEid[a], exp(f + ((m.outW[a] + pc) + Nu[m.outDst[a]])));
+          }
         }
       }
-      if (i < I) {
+      if (i < I && B.inside(i + 1, r)) {
         const double *Wl = B.nw(i + 1, r, 1) + k * S;
         const int a1 = m.outOff[xRow + 1];
         for (int a = m.outOff[xRow]; a < a1; ++a) acc.add(m.outEid[a], exp(f + (Wl[m.outDst[a]] + m.outW[a])));
@@ -321,23 +413,27 @@ __global__ __launch_bounds__(256) void k_profile_pair_merge_counts(DevMachine m,
 // beforehand.  A row of more than tabMax columns is summed in its global bins instead, cleared by the workgroup that owns it.  A pair
 // whose likelihood is -inf gets zeros by the same stores.  loglike: the Forward sweep's, per pair of the launch.
 // det: a lane sum is turned into 64-bit fixed point at 2^-36 (mb_internal.h) before it meets another; post then holds the integers.
-__global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_merge_rowpost(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
-                                                                                int groupsPerPair, const int *__restrict__ inTok,
+// The rows are walked through the lattice's rowFirst / rowCell: under an envelope row r has (inEnd[r] - inStart[r]) (nCols + 1) S
+// items, and the cells (i, r + 1) and (i + 1, r + 1) are asked inside() before they are read.  Every bin of every row is still
+// written, so a row all of whose terms are dead gets zeros.
+template <bool ENV>
+__global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_merge_rowpost(DevMachine m, MergeMap mm, const typename PairMergeLattice<true, ENV>::Desc *__restrict__ descs,
+                                                                                typename PairMergeLattice<true, ENV>::Tables t, int groupsPerPair, const int *__restrict__ inTok,
                                                                                 const double *__restrict__ logP, const double *__restrict__ fwdPool,
                                                                                 const double *__restrict__ bwdPool, const double *__restrict__ loglike,
                                                                                 double *post, int tabMax, int det) {
   __shared__ double ltab[ROWPOST_LDS_MAX];
   const int pair = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
-  const PairProfDesc pd = descs[pair];
+  const auto pd = descs[pair];
   const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
   if (L == 0) return;
   const int *x = inTok + pd.inBase;
   const double *P = logP + pd.rowBase * PL;
-  const PairMergeLattice<true> F{const_cast<double *>(fwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0},
-      B{const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  const PairMergeLattice<true, ENV> F(pd, t, const_cast<double *>(fwdPool) + pd.cellBase, nullptr, S, PL),
+      B(pd, t, const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL);
   const double LL = loglike[pair];
-  const long long PS = (long long)PL * S, perRow = (long long)(I + 1) * PS;
-  const int R = profile_pair_rowpost_rows((long long)(I + 1) * (L + 1) * PL, S, L, PL, tabMax);
+  const long long PS = (long long)PL * S;
+  const int R = profile_pair_rowpost_rows(F.nCells() * PL, S, L, PL, tabMax);
   const bool useLds = PL <= tabMax;
   const int lane = threadIdx.x & 63;
   for (long long rb = (long long)group * R; rb < L; rb += (long long)groupsPerPair * R) {
@@ -348,28 +444,27 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_merge_rowpost(
     if (!useLds) __threadfence();
     __syncthreads();
     if (LL > -INFINITY) {
-      const long long nItems = (long long)(r1 - r0) * perRow;
+      const long long c0 = F.rowFirst(r0), nItems = (F.rowFirst(r1) - c0) * PS;
       for (long long base = threadIdx.x - lane; base < nItems; base += blockDim.x) {      // (a wavefront stays whole in here)
         const long long idx = base + lane;
         const bool valid = idx < nItems;
         int r = r0, i = 0, k = 0, s = 0, ks = 0;
         double f = -INFINITY, n = -INFINITY;
         if (valid) {
-          const long long row = idx / perRow, rem = idx - row * perRow;
-          r = r0 + (int)row;
-          i = (int)(rem / PS);
-          ks = (int)(rem - (long long)i * PS);
+          const long long cell = idx / PS;
+          ks = (int)(idx - cell * PS);
+          F.rowCell(c0 + cell, i, r);
           k = ks / S;
           s = ks - k * S;
           n = F.nw(i, r, 0)[ks] - LL;
           f = F.nw(i, r, 1)[ks] - LL;
         }
         const bool whole = __all(valid && r == __shfl(r, 0));
-        const bool across = valid && i < I;
+        const bool up = valid && B.inside(i, r + 1), across = valid && i < I && B.inside(i + 1, r + 1);
         const double *Pr = P + (long long)r * PL;
-        const double *Nu = B.nw(i, r + 1, 0), *Nd = across ? B.nw(i + 1, r + 1, 0) : nullptr;
+        const double *Nu = B.nw(i, r + 1, 0), *Nd = across ? B.nw(i + 1, r + 1, 0) : nullptr;      // (Nu: an address alone, read only where `up`)
         const int sRow = s * K, xRow = across ? sRow + x[i] * C : 0;
-        const bool nLive = n > -INFINITY, fLive = f > -INFINITY;
+        const bool nLive = up && n > -INFINITY, fLive = f > -INFINITY;
         const int bin0 = (r - r0) * PL;
         rowpost_add(tab, bin0, nLive ? exp(n + (Pr[0] + Nu[s])) : 0.0, whole, lane, det);
         for (int c = 1; c < PL; ++c) {      // the out-edges of (s, input token) that write the column's token are one CSR row
@@ -385,9 +480,11 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_merge_rowpost(
                 const int a1 = m.outOff[xRow + tok + 1];
                 for (int a = m.outOff[xRow + tok]; a < a1; ++a) v += exp(f + ((m.outW[a] + pc) + Ndc[m.outDst[a]]));
               }
-              const double *Nuc = Nu + (long long)c * S;
-              const int a1 = m.outOff[sRow + tok + 1];
-              for (int a = m.outOff[sRow + tok]; a < a1; ++a) v += exp(f + ((m.outW[a] + pc) + Nuc[m.outDst[a]]));
+              if (up) {
+                const double *Nuc = Nu + (long long)c * S;
+                const int a1 = m.outOff[sRow + tok + 1];
+                for (int a = m.outOff[sRow + tok]; a < a1; ++a) v += exp(f + ((m.outW[a] + pc) + Nuc[m.outDst[a]]));
+              }
             }
           }
           rowpost_add(tab, bin0 + c, v, whole, lane, det);
@@ -406,17 +503,21 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_merge_rowpost(
 // W[I][L][.][S-1] back to N[0][0][0][0], taking at every cell the first candidate (in the fill's order) whose value equals the cell;
 // an emitting edge comes from the lowest plane k != c whose W equals the edge's X.  Blank and repeat rows are not edges.  Edges go
 // start -> end into the pair's slot (profile_pair_path_bound entries) with the row each fired at, as k_profile_pair_traceback.
-// len = -1: no finite path, -2: the slot was too small, -3: no candidate matched (a corrupt matrix).
-__global__ void k_profile_pair_merge_traceback(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs, int n,
+// len = -1: no finite path, -2: the slot was too small, -3: no candidate matched (a corrupt matrix).  A candidate whose source cell
+// lies outside the lattice is left out: it is -inf, and the cells on the path are finite, so a live cell always has a live source
+// inside.
+template <bool ENV>
+__global__ void k_profile_pair_merge_traceback(DevMachine m, MergeMap mm, const typename PairMergeLattice<true, ENV>::Desc *__restrict__ descs,
+                                               typename PairMergeLattice<true, ENV>::Tables t, int n,
                                                const int *__restrict__ inTok, const double *__restrict__ logP,
                                                const double *__restrict__ pool, uint32_t *edges, int32_t *rows, long long *len) {
   const int pair = blockIdx.x * blockDim.x + threadIdx.x;
   if (pair >= n) return;
-  const PairProfDesc pd = descs[pair];
+  const auto pd = descs[pair];
   const int S = m.S, K = m.K, C = m.nOut + 1, nC = mm.nCols, PL = nC + 1, I = pd.nIn, L = pd.nRows;
   const int *x = inTok + pd.inBase;
   const double *P = logP + pd.rowBase * PL;
-  const PairMergeLattice<true> lat{const_cast<double *>(pool) + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  const PairMergeLattice<true, ENV> lat(pd, t, const_cast<double *>(pool) + pd.cellBase, nullptr, S, PL);
   uint32_t *pe = edges + pd.pathBase;
   int32_t *pr = rows + pd.pathBase;
   int i = I, r = L, q = S - 1, layer = 1, p = 0;
@@ -436,7 +537,7 @@ __global__ void k_profile_pair_merge_traceback(DevMachine m, MergeMap mm, const 
       const double *W = lat.nw(i, r, 1) + p * S;
       const double cur = W[q];
       if (lat.nw(i, r, 0)[p * S + q] == cur) { layer = 0; continue; }
-      if (i > 0) {
+      if (i > 0 && lat.inside(i - 1, r)) {
         const double *Wl = lat.nw(i - 1, r, 1) + p * S;
         a = m.inOff[xRow];
         for (const int a1 = m.inOff[xRow + 1]; a < a1; ++a)
@@ -455,16 +556,17 @@ __global__ void k_profile_pair_merge_traceback(DevMachine m, MergeMap mm, const 
       i = ni; q = found;
     } else {
       if (r == 0) { if (i != 0 || q != 0 || p != 0) { len[pair] = -3; return; } break; }
-      const double *Np = lat.nw(i, r - 1, 0);
+      const bool up = lat.inside(i, r - 1);
+      const double *Np = up ? lat.nw(i, r - 1, 0) : nullptr;
       const double cur = lat.nw(i, r, 0)[p * S + q], w = P[(long long)(r - 1) * PL + p];
       if (p == 0) {
-        int k = 0;
+        int k = up ? 0 : PL;
         while (k < PL && !(Np[k * S + q] + w == cur)) ++k;
         if (k == PL) { len[pair] = -3; return; }
         p = k; --r;
         continue;
       }
-      if (Np[p * S + q] + w == cur) { --r; continue; }
+      if (up && Np[p * S + q] + w == cur) { --r; continue; }
       const int tok = mm.colTok[p - 1];
       int from = -1;
       // the edge's X and the lowest plane that attains it
@@ -475,7 +577,7 @@ __global__ void k_profile_pair_merge_traceback(DevMachine m, MergeMap mm, const 
           if (k != p && xs < Wv[k * S + s]) { xs = Wv[k * S + s]; kx = k; }
         return xs;
       };
-      if (i > 0) {
+      if (i > 0 && lat.inside(i - 1, r - 1)) {
         const double *Wd = lat.nw(i - 1, r - 1, 1);
         a = m.inOff[xRow + tok];
         for (const int a1 = m.inOff[xRow + tok + 1]; a < a1; ++a) {
@@ -484,7 +586,7 @@ __global__ void k_profile_pair_merge_traceback(DevMachine m, MergeMap mm, const 
           if ((xs + m.inW[a]) + w == cur) { found = (int)m.inSrc[a]; from = kx; ni = i - 1; break; }
         }
       }
-      if (found < 0) {
+      if (found < 0 && up) {
         const double *Wu = lat.nw(i, r - 1, 1);
         a = m.inOff[q * K + tok];
         for (const int a1 = m.inOff[q * K + tok + 1]; a < a1; ++a) {
@@ -511,62 +613,115 @@ __global__ void k_profile_pair_merge_traceback(DevMachine m, MergeMap mm, const 
 static bool ppm_allow_lds(size_t lds) {
   static size_t ldsAllowed = 64 * 1024;
   if (lds <= ldsAllowed) return true;
-  const void *ks[] = {(const void *)&k_profile_pair_merge_fwd<MB_FORWARD, false>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, false>,
-                      (const void *)&k_profile_pair_merge_fwd<MB_FORWARD, true>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, true>,
-                      (const void *)&k_profile_pair_merge_bwd};
+  const void *ks[] = {(const void *)&k_profile_pair_merge_fwd<MB_FORWARD, false, false>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, false, false>,
+                      (const void *)&k_profile_pair_merge_fwd<MB_FORWARD, true, false>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, true, false>,
+                      (const void *)&k_profile_pair_merge_bwd<false>,
+                      (const void *)&k_profile_pair_merge_fwd<MB_FORWARD, false, true>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, false, true>,
+                      (const void *)&k_profile_pair_merge_fwd<MB_FORWARD, true, true>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, true, true>,
+                      (const void *)&k_profile_pair_merge_bwd<true>};
   for (const void *k : ks)
     if (!hip_ok(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), "k_profile_pair_merge: raising the LDS limit")) return false;
   ldsAllowed = SWEEP_LDS_MAX;
   return true;
 }
 
-int launch_profile_pair_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const PairProfDesc *d, int n, size_t lds,
-                                  long long maxItems, const int *inTok, const double *logP, double *pool, double *scratch,
-                                  double *loglike, hipStream_t st) {
+// The launchers: each sweep once over a form of the lattice, and the two overloads of the header that name one.
+template <bool ENV>
+static int ppm_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const typename PairMergeLattice<true, ENV>::Desc *d, typename PairMergeLattice<true, ENV>::Tables t,
+                   int n, size_t lds, long long maxItems, const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st) {
   if (n <= 0) return 0;
   if (!ppm_allow_lds(lds)) return 1;
   const dim3 g(n), b(sweep_threads(maxItems));
   if (mode == MB_VITERBI) {
-    if (mat) k_profile_pair_merge_fwd<MB_VITERBI, true><<<g, b, lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
-    else k_profile_pair_merge_fwd<MB_VITERBI, false><<<g, b, lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
+    if (mat) k_profile_pair_merge_fwd<MB_VITERBI, true, ENV><<<g, b, lds, st>>>(m->dev, mm, d, t, inTok, logP, pool, scratch, loglike);
+    else k_profile_pair_merge_fwd<MB_VITERBI, false, ENV><<<g, b, lds, st>>>(m->dev, mm, d, t, inTok, logP, pool, scratch, loglike);
   } else {
-    if (mat) k_profile_pair_merge_fwd<MB_FORWARD, true><<<g, b, lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
-    else k_profile_pair_merge_fwd<MB_FORWARD, false><<<g, b, lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
+    if (mat) k_profile_pair_merge_fwd<MB_FORWARD, true, ENV><<<g, b, lds, st>>>(m->dev, mm, d, t, inTok, logP, pool, scratch, loglike);
+    else k_profile_pair_merge_fwd<MB_FORWARD, false, ENV><<<g, b, lds, st>>>(m->dev, mm, d, t, inTok, logP, pool, scratch, loglike);
   }
-  return hip_ok(hipGetLastError(), "k_profile_pair_merge_fwd") ? 0 : 1;
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_pair_merge_env_fwd" : "k_profile_pair_merge_fwd") ? 0 : 1;
+}
+int launch_profile_pair_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const PairProfDesc *d, int n, size_t lds,
+                                  long long maxItems, const int *inTok, const double *logP, double *pool, double *scratch,
+                                  double *loglike, hipStream_t st) {
+  return ppm_fwd<false>(m, mm, mode, mat, d, {}, n, lds, maxItems, inTok, logP, pool, scratch, loglike, st);
+}
+int launch_profile_pair_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const PairEnvDesc *d, const PairEnvTables &t, int n, size_t lds,
+                                  long long maxItems, const int *inTok, const double *logP, double *pool, double *scratch,
+                                  double *loglike, hipStream_t st) {
+  return ppm_fwd<true>(m, mm, mode, mat, d, t, n, lds, maxItems, inTok, logP, pool, scratch, loglike, st);
 }
 
-int launch_profile_pair_merge_bwd(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, size_t lds, long long maxItems,
-                                  const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st) {
+template <bool ENV>
+static int ppm_bwd(const mb_machine *m, MergeMap mm, const typename PairMergeLattice<true, ENV>::Desc *d, typename PairMergeLattice<true, ENV>::Tables t, int n, size_t lds,
+                   long long maxItems, const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st) {
   if (n <= 0) return 0;
   if (!ppm_allow_lds(lds)) return 1;
-  k_profile_pair_merge_bwd<<<dim3(n), dim3(sweep_threads(maxItems)), lds, st>>>(m->dev, mm, d, inTok, logP, pool, scratch, loglike);
-  return hip_ok(hipGetLastError(), "k_profile_pair_merge_bwd") ? 0 : 1;
+  k_profile_pair_merge_bwd<ENV><<<dim3(n), dim3(sweep_threads(maxItems)), lds, st>>>(m->dev, mm, d, t, inTok, logP, pool, scratch, loglike);
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_pair_merge_env_bwd" : "k_profile_pair_merge_bwd") ? 0 : 1;
+}
+int launch_profile_pair_merge_bwd(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, size_t lds, long long maxItems,
+                                  const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  return ppm_bwd<false>(m, mm, d, {}, n, lds, maxItems, inTok, logP, pool, scratch, loglike, st);
+}
+int launch_profile_pair_merge_bwd(const mb_machine *m, MergeMap mm, const PairEnvDesc *d, const PairEnvTables &t, int n, size_t lds, long long maxItems,
+                                  const int *inTok, const double *logP, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  return ppm_bwd<true>(m, mm, d, t, n, lds, maxItems, inTok, logP, pool, scratch, loglike, st);
 }
 
+template <bool ENV>
+static int ppm_counts(const mb_machine *m, MergeMap mm, const typename PairMergeLattice<true, ENV>::Desc *d, typename PairMergeLattice<true, ENV>::Tables t, int n,
+                      int groupsPerPair, const int *inTok, const double *logP, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
+  if (n <= 0 || m->nTrans <= 0) return 0;
+  k_profile_pair_merge_counts<ENV><<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(
+      m->dev, mm, d, t, groupsPerPair, inTok, logP, fwdPool, bwdPool, m->nTrans, counts, g_deterministic ? 1 : 0);
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_pair_merge_env_counts" : "k_profile_pair_merge_counts") ? 0 : 1;
+}
 int launch_profile_pair_merge_counts(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, int groupsPerPair, const int *inTok,
                                      const double *logP, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
-  if (n <= 0 || m->nTrans <= 0) return 0;
-  k_profile_pair_merge_counts<<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(
-      m->dev, mm, d, groupsPerPair, inTok, logP, fwdPool, bwdPool, m->nTrans, counts, g_deterministic ? 1 : 0);
-  return hip_ok(hipGetLastError(), "k_profile_pair_merge_counts") ? 0 : 1;
+  return ppm_counts<false>(m, mm, d, {}, n, groupsPerPair, inTok, logP, fwdPool, bwdPool, counts, st);
+}
+int launch_profile_pair_merge_counts(const mb_machine *m, MergeMap mm, const PairEnvDesc *d, const PairEnvTables &t, int n, int groupsPerPair, const int *inTok,
+                                     const double *logP, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
+  return ppm_counts<true>(m, mm, d, t, n, groupsPerPair, inTok, logP, fwdPool, bwdPool, counts, st);
 }
 
+template <bool ENV>
+static int ppm_rowpost(const mb_machine *m, MergeMap mm, const typename PairMergeLattice<true, ENV>::Desc *d, typename PairMergeLattice<true, ENV>::Tables t, int n,
+                       int groupsPerPair, int tabMax, const int *inTok, const double *logP, const double *fwdPool, const double *bwdPool,
+                       const double *loglike, double *post, hipStream_t st) {
+  if (n <= 0) return 0;
+  k_profile_pair_merge_rowpost<ENV><<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(ROWPOST_THREADS), 0, st>>>(
+      m->dev, mm, d, t, groupsPerPair, inTok, logP, fwdPool, bwdPool, loglike, post, tabMax, g_deterministic ? 1 : 0);
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_pair_merge_env_rowpost" : "k_profile_pair_merge_rowpost") ? 0 : 1;
+}
 int launch_profile_pair_merge_rowpost(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, int groupsPerPair, int tabMax,
                                       const int *inTok, const double *logP, const double *fwdPool, const double *bwdPool,
                                       const double *loglike, double *post, hipStream_t st) {
-  if (n <= 0) return 0;
-  k_profile_pair_merge_rowpost<<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(ROWPOST_THREADS), 0, st>>>(
-      m->dev, mm, d, groupsPerPair, inTok, logP, fwdPool, bwdPool, loglike, post, tabMax, g_deterministic ? 1 : 0);
-  return hip_ok(hipGetLastError(), "k_profile_pair_merge_rowpost") ? 0 : 1;
+  return ppm_rowpost<false>(m, mm, d, {}, n, groupsPerPair, tabMax, inTok, logP, fwdPool, bwdPool, loglike, post, st);
+}
+int launch_profile_pair_merge_rowpost(const mb_machine *m, MergeMap mm, const PairEnvDesc *d, const PairEnvTables &t, int n, int groupsPerPair, int tabMax,
+                                      const int *inTok, const double *logP, const double *fwdPool, const double *bwdPool,
+                                      const double *loglike, double *post, hipStream_t st) {
+  return ppm_rowpost<true>(m, mm, d, t, n, groupsPerPair, tabMax, inTok, logP, fwdPool, bwdPool, loglike, post, st);
 }
 
+template <bool ENV>
+static int ppm_traceback(const mb_machine *m, MergeMap mm, const typename PairMergeLattice<true, ENV>::Desc *d, typename PairMergeLattice<true, ENV>::Tables t, int n,
+                         const int *inTok, const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len, hipStream_t st) {
+  if (n <= 0) return 0;
+  k_profile_pair_merge_traceback<ENV><<<(n + 63) / 64, 64, 0, st>>>(m->dev, mm, d, t, n, inTok, logP, pool, edges, rows, len);
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_pair_merge_env_traceback" : "k_profile_pair_merge_traceback") ? 0 : 1;
+}
 int launch_profile_pair_merge_traceback(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, const int *inTok,
                                         const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len,
                                         hipStream_t st) {
-  if (n <= 0) return 0;
-  k_profile_pair_merge_traceback<<<(n + 63) / 64, 64, 0, st>>>(m->dev, mm, d, n, inTok, logP, pool, edges, rows, len);
-  return hip_ok(hipGetLastError(), "k_profile_pair_merge_traceback") ? 0 : 1;
+  return ppm_traceback<false>(m, mm, d, {}, n, inTok, logP, pool, edges, rows, len, st);
+}
+int launch_profile_pair_merge_traceback(const mb_machine *m, MergeMap mm, const PairEnvDesc *d, const PairEnvTables &t, int n, const int *inTok,
+                                        const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len,
+                                        hipStream_t st) {
+  return ppm_traceback<true>(m, mm, d, t, n, inTok, logP, pool, edges, rows, len, st);
 }
 
 }  // namespace mb

@@ -849,7 +849,12 @@ class PairMergedProfileDP(PairProfileDP):
     repeat, then match edges in `incoming` order, then output-only edges in `incoming` order, each from the lowest plane k != c
     that attains its X; W: "no move", then input-only edges, then silent edges, each in `incoming` order; the end: planes
     ascending.  Every method takes (x, P): P the [L, nCols + 1] log weights of Profile.mergeRows.  Lattices are
-    [I + 1, L + 1, nCols + 1, S]."""
+    [I + 1, L + 1, nCols + 1, S].
+
+    ``env`` (forward, backward, counts, rowPosteriors, viterbi): as PairProfileDP's, checked by envelopeRows -- cell (i, r) exists
+    iff inStart[r] <= i < inEnd[r], in every plane; N, W and X (NB, WB and T) of every other cell are -inf (docs/profile_tapes.md,
+    "Pairs against a merged profile under an envelope").  The sweeps visit the envelope cells alone.  Without it not one operation
+    differs."""
 
     def __init__(self, em: EvaluatedMachine, colTok: Sequence[int]):
         super().__init__(em)
@@ -883,11 +888,11 @@ class PairMergedProfileDP(PairProfileDP):
         idx = (np.arange(self.PL)[:, None] * S + d[None, :]).ravel()
         return fold(base.ravel(), idx, vals.ravel()).reshape(self.PL, S)
 
-    def forward(self, x, P, mode: str = "exact") -> Tuple[float, np.ndarray, np.ndarray]:
+    def forward(self, x, P, mode: str = "exact", env=None) -> Tuple[float, np.ndarray, np.ndarray]:
         """(loglike, N[I+1][L+1][nCols+1][S], W[I+1][L+1][nCols+1][S]); mode "exact" or "max"."""
-        return self._sweep(x, P, mode)[:3]
+        return self._sweep(x, P, mode, env)[:3]
 
-    def _sweep(self, x, P, mode: str):
+    def _sweep(self, x, P, mode: str, env=None):
         """forward() and the exclusion vectors X[I+1][L+1][nCols+1][S] (plane 0 of X is not read)"""
         x, P = self._checkPair(x, P)
         mx = mode == "max"
@@ -895,8 +900,9 @@ class PairMergedProfileDP(PairProfileDP):
         I, L, S, PL = len(x), len(P), self.S, self.PL
         N = np.full((I + 1, L + 1, PL, S), _NEG); W = np.full((I + 1, L + 1, PL, S), _NEG)
         X = np.full((I + 1, L + 1, PL, S), _NEG)
+        inside = self.envelopeRows(env, I, L)
         for i in range(I + 1):
-            for r in range(L + 1):
+            for r in (range(L + 1) if inside is None else inside[i]):      # (a cell outside stays -inf and is read as such)
                 base = np.full((PL, S), _NEG)
                 if i == 0 and r == 0:
                     base[0, 0] = 0.0
@@ -923,13 +929,14 @@ class PairMergedProfileDP(PairProfileDP):
                 X[i, r] = _excl_planes(w_, mx)
         return float(_red_planes(W[I, L, :, S - 1:S], mx)[0]), N, W, X
 
-    def backward(self, x, P) -> Tuple[float, np.ndarray, np.ndarray]:
+    def backward(self, x, P, env=None) -> Tuple[float, np.ndarray, np.ndarray]:
         """(loglike, NB[I+1][L+1][nCols+1][S], WB[I+1][L+1][nCols+1][S]), exact log-sum-exp; loglike = NB[0][0][0][0]."""
         x, P = self._checkPair(x, P)
         I, L, S, PL = len(x), len(P), self.S, self.PL
         NB = np.full((I + 1, L + 1, PL, S), _NEG); WB = np.full((I + 1, L + 1, PL, S), _NEG)
+        inside = self.envelopeRows(env, I, L)
         for i in range(I, -1, -1):
-            for r in range(L, -1, -1):
+            for r in (range(L, -1, -1) if inside is None else reversed(inside[i])):
                 base = np.full((PL, S), _NEG)
                 if r < L:
                     # T[c][s]: everything that leaves s through column c; WB[k] takes the columns other than k
@@ -957,20 +964,21 @@ class PairMergedProfileDP(PairProfileDP):
                     NB[i, r] = base
         return float(NB[0, 0, 0, 0]), NB, WB
 
-    def counts(self, x, P, blanks: Optional[list] = None) -> Tuple[np.ndarray, float]:
+    def counts(self, x, P, blanks: Optional[list] = None, env=None) -> Tuple[np.ndarray, float]:
         """(posterior expected use of every transition, Forward loglike); nothing for a -inf pair.  Blank and repeat rows are not
         edges; ``blanks`` (a list) receives their posterior mass, summed over the lattice."""
         x, P = self._checkPair(x, P)
-        ll, NF, WF, XF = self._sweep(x, P, "exact")
+        ll, NF, WF, XF = self._sweep(x, P, "exact", env)
         out = np.zeros(self.em.nTransitions)
         if not ll > _NEG:
             return out, ll
-        _, NB, WB = self.backward(x, P)
+        _, NB, WB = self.backward(x, P) if env is None else self.backward(x, P, env=env)
         I, L = len(x), len(P)
+        inside = self.envelopeRows(env, I, L)
         blank = 0.0
         with np.errstate(invalid="ignore"):
             for i in range(I + 1):
-                for r in range(L + 1):
+                for r in (range(L + 1) if inside is None else inside[i]):
                     f, fx = WF[i, r] - ll, XF[i, r] - ll
                     if r < L:
                         if i < I:
@@ -989,7 +997,7 @@ class PairMergedProfileDP(PairProfileDP):
             blanks.append(blank)
         return out, ll
 
-    def rowPosteriors(self, x, P, repeats: Optional[list] = None) -> Tuple[np.ndarray, float]:
+    def rowPosteriors(self, x, P, repeats: Optional[list] = None, env=None) -> Tuple[np.ndarray, float]:
         """(post[L, nCols + 1], Forward loglike): post[r][c] is the posterior probability that row r was consumed as column c
         (column 0: as the blank), the gradient of loglike in P[r][c] (docs/profile_tapes.md, "Row posteriors of pairs against a
         merged profile"): the blank out of every plane of every cell of the row, and for a column its repeat (plane c stays) plus
@@ -998,14 +1006,15 @@ class PairMergedProfileDP(PairProfileDP):
         part, so that post - repeats sums per token to the counts.  Every row sums to 1; zeros for a -inf pair; exactly 0 where
         P[r][c] is -inf."""
         x, P = self._checkPair(x, P)
-        ll, NF, WF = self.forward(x, P)
+        ll, NF, WF = self.forward(x, P) if env is None else self.forward(x, P, env=env)
         I, L, PL = len(x), len(P), self.PL
         post = np.zeros((L, PL)); rep = np.zeros((L, PL))
         if repeats is not None:
             repeats.append(rep)
         if not ll > _NEG:
             return post, ll
-        _, NB, _ = self.backward(x, P)
+        _, NB, _ = self.backward(x, P) if env is None else self.backward(x, P, env=env)
+        inside = self.envelopeRows(env, I, L)
         planes = np.arange(PL)
 
         def emit(row, f, tab, NBn):
@@ -1016,7 +1025,9 @@ class PairMergedProfileDP(PairProfileDP):
             np.add.at(row, np.broadcast_to(c, t.shape)[keep], np.exp(t[keep]))
         with np.errstate(invalid="ignore"):
             for i in range(I + 1):
-                for r in range(L):
+                for r in (range(L) if inside is None else inside[i]):
+                    if r == L:
+                        continue
                     n, f = NF[i, r] - ll, WF[i, r] - ll
                     b = n + (P[r][0] + NB[i, r + 1][0])
                     post[r, 0] += float(np.exp(b[b > _NEG]).sum())
@@ -1028,13 +1039,16 @@ class PairMergedProfileDP(PairProfileDP):
         post += rep
         return post, ll
 
-    def viterbi(self, x, P, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray]:
+    def viterbi(self, x, P, census: Optional[dict] = None, env=None) -> Tuple[float, np.ndarray, np.ndarray]:
         """(score, global edge ids start -> end, row at which each fired); the first maximum in the fill's candidate order.  Rows as
         PairProfileDP.viterbi; blank and repeat rows are not edges.  ``census`` counts, by the candidate taken, the steps at which
         two or more candidates equal the cell: "end"; "stay" / "input" / "silent" at a W cell; "blank" at N[.][.][0]; "repeat" /
-        "match" / "emit" at N[.][.][c]; "plane" for an emitting edge whose X two planes attain."""
+        "match" / "emit" at N[.][.][c]; "plane" for an emitting edge whose X two planes attain.  Under ``env`` a candidate whose
+        source cell lies outside the envelope is -inf and loses; the census counts, under ("outside", kind), the steps that had
+        such a candidate of that kind."""
         x, P = self._checkPair(x, P)
-        v, N, W = self.forward(x, P, "max")
+        v, N, W = self.forward(x, P, "max") if env is None else self.forward(x, P, "max", env=env)
+        inside = self.envelopeRows(env, len(x), len(P))
         edges: List[int] = []; rows: List[int] = []
         if not v > _NEG:
             return v, np.zeros(0, np.uint32), np.zeros(0, np.int32)
@@ -1042,6 +1056,16 @@ class PairMergedProfileDP(PairProfileDP):
         def tie(kind: str, n: int):
             if census is not None and n > 1:
                 census[kind] = census.get(kind, 0) + 1
+
+        def outside(cand):
+            """the census of the candidates (kind, ..., input position of the source at [3]) of a cell whose sources lie outside"""
+            if census is None or inside is None:
+                return
+            for kind in dict.fromkeys(c[0] for c in cand if c[0] != "stay" and c[0] != "silent"):
+                si = i - (kind in ("input", "match"))
+                sr = r - (kind != "input")
+                if sr not in inside[si]:
+                    census[("outside", kind)] = census.get(("outside", kind), 0) + 1
         i, r, q, layer = len(x), len(P), self.S - 1, 1
         ends = [p for p in range(self.PL) if W[i, r, p, q] == v]
         tie("end", len(ends))
@@ -1055,6 +1079,7 @@ class PairMergedProfileDP(PairProfileDP):
                     e, s, d, w, _o = self.ins[x[i - 1]]
                     cand += [("input", int(e[k]), int(s[k]), i - 1, W[i - 1, r, p, s[k]] + w[k] == cur) for k in np.nonzero(d == q)[0]]
                 cand += [("silent", int(self.sId[k]), int(self.sS[k]), i, W[i, r, p, self.sS[k]] + self.sW[k] == cur) for k in self.inSil[q]]
+                outside(cand)
                 hits = [c for c in cand if c[4]]
                 kind, e, s, ni, _ = hits[0]
                 tie(kind, len(hits))
@@ -1068,6 +1093,7 @@ class PairMergedProfileDP(PairProfileDP):
                 break
             Pr, cur = P[r - 1], N[i, r, p, q]
             if p == 0:
+                outside([("blank",)])
                 hit = [N[i, r - 1, k, q] + Pr[0] == cur for k in range(self.PL)]
                 tie("blank", sum(hit))
                 p = hit.index(True)
@@ -1085,6 +1111,7 @@ class PairMergedProfileDP(PairProfileDP):
                 if self.eO[k] == tok:
                     xv = max(W[i, r - 1, o_, self.eS[k]] for o_ in oth)
                     cand.append(("emit", int(self.eId[k]), int(self.eS[k]), i, xv, (xv + self.eW[k]) + Pr[p] == cur))
+            outside(cand)
             hits = [c for c in cand if c[5]]
             kind, e, s, ni, xv, _ = hits[0]
             tie(kind, len(hits))

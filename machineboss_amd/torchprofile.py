@@ -26,8 +26,10 @@ def _row_posteriors(machine_or_dm, inputs, P, rowOff, envs, backend, colTok=None
         for k in range(n):
             if colTok is None:
                 post[rowOff[k]:rowOff[k + 1]], ll[k] = dp.rowPosteriors(inputs[k], profiles[k], env=None if envs is None else envs[k])
-            else:
+            elif envs is None or envs[k] is None:
                 post[rowOff[k]:rowOff[k + 1]], ll[k] = dp.rowPosteriors(inputs[k], profiles[k])
+            else:
+                post[rowOff[k]:rowOff[k + 1]], ll[k] = dp.rowPosteriors(inputs[k], profiles[k], env=envs[k])
         return post, ll
     if backend != "device":
         raise ValueError('backend is "device" or "numpy"')
@@ -37,8 +39,10 @@ def _row_posteriors(machine_or_dm, inputs, P, rowOff, envs, backend, colTok=None
     pairs = None
     try:
         pairs = capi.DeviceProfilePairs(dm, inputs, profiles, colTok)
-        if envs is not None:
+        if envs is not None and colTok is None:
             pairs.set_envelopes(envs)
+        elif envs is not None:
+            pairs.set_merged_envelopes(envs)
         return pairs.row_posteriors() if colTok is None else pairs.merged_row_posteriors()
     finally:
         if pairs is not None:
@@ -75,7 +79,7 @@ def pair_profile_loglike(machine_or_dm, inputs, logP, rowOff, envs=None, backend
     output token colTok[c - 1], repeats collapse and a blank separates equal symbols (docs/profile_tapes.md, "Row posteriors of
     pairs against a merged profile").  Both backends take the merged route (capi.DeviceProfilePairs.merged_row_posteriors,
     profile.PairMergedProfileDP.rowPosteriors); with a one-state echo transducer the result is -ctc_loss(logP, x) per pair.
-    Envelopes take plain profiles.
+    Envelopes take plain profiles here; merged_pair_profile_loglike takes both.
 
     Tensors of any device go through host memory (``.detach().cpu().numpy()``) and the results come back to the tensor's device;
     a zero-copy entry that takes device pointers is out of scope here."""
@@ -92,6 +96,28 @@ def pair_profile_loglike(machine_or_dm, inputs, logP, rowOff, envs=None, backend
         colTok = np.asarray(colTok, np.int64).reshape(-1)
         if logP.shape[1] != len(colTok) + 1:
             raise ValueError("merged profiles: logP has one column per entry of colTok and the blank in front")
+    inputs = [np.asarray(x, np.int64).reshape(-1) for x in inputs]
+    return _PairProfileLoglike.apply(logP, machine_or_dm, inputs, rowOff, envs, backend, colTok)
+
+
+def merged_pair_profile_loglike(machine_or_dm, inputs, logP, rowOff, colTok, envs=None, backend="device"):
+    """pair_profile_loglike against CTC-merged frames, with envelopes: tensor[nPairs] of log-likelihoods, pair k the token sequence
+    ``inputs[k]`` against the rows rowOff[k]..rowOff[k + 1] of ``logP``, a float64 [sumRows, nCols + 1] tensor with column 0 the blank
+    and column c a frame's log weight of the output token colTok[c - 1].  ``envs``: per pair None, a seqpair.Envelope or (inStart,
+    inEnd); a pair under one is summed over the alignments inside it alone (docs/profile_tapes.md, "Pairs against a merged profile
+    under an envelope"), so its value is never above the unbanded one.  Differentiable in ``logP``: the gradient is grad_out[k] times
+    the merged row posteriors of pair k under its envelope, zeros for a pair that scores -inf.  ``backend``: "device"
+    (capi.DeviceProfilePairs.set_merged_envelopes, merged_row_posteriors) or "numpy" (profile.PairMergedProfileDP.rowPosteriors)."""
+    if logP.dtype != torch.float64 or logP.dim() != 2:
+        raise ValueError("logP is a float64 [sumRows, nCols + 1] tensor")
+    rowOff = np.asarray(rowOff, np.int64).reshape(-1)
+    if len(rowOff) != len(inputs) + 1 or rowOff[0] != 0 or rowOff[-1] != logP.shape[0] or (np.diff(rowOff) < 0).any():
+        raise ValueError("rowOff has one entry per pair and one more, from 0 up to the rows of logP")
+    if envs is not None and len(envs) != len(inputs):
+        raise ValueError("one envelope (or None) per pair, please")
+    colTok = np.asarray(colTok, np.int64).reshape(-1)
+    if logP.shape[1] != len(colTok) + 1:
+        raise ValueError("merged profiles: logP has one column per entry of colTok and the blank in front")
     inputs = [np.asarray(x, np.int64).reshape(-1) for x in inputs]
     return _PairProfileLoglike.apply(logP, machine_or_dm, inputs, rowOff, envs, backend, colTok)
 
