@@ -378,6 +378,22 @@ mb_profile_twos *mb_profile_twos_create_merged(mb_machine *m, int64_t nPairs, co
 int mb_profile_two_fill_merged(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, int32_t nCols,
                                const int32_t *colTok, double *cellsOut);
 
+/* Row posteriors of pairs of profiles against merged profiles (k_profile_two_merge_rowpost; docs/profile_tapes.md, "Row posteriors
+ * of pairs of profiles against a merged profile"): postB[(rowOff[k] - rowOff[0] + r)*(nCols+1) + c] = the posterior probability
+ * that output row r of pair k was consumed as column c (column 0: as the blank) -- the blank out of every plane, the repeat of
+ * column c, and the match and output-only edges that write colTok[c] out of every plane other than c;
+ * postA[(inOff[k] - inOff[0] + i)*(nInTok+1) + a] = that input row i was consumed as input token a (column 0: as the input blank)
+ * -- the gradients of the pair's log-likelihood in logB and in logA at those entries.  Either table has the layout of its row
+ * table and is overwritten; either may be NULL, and its kernel is then not launched.  Every row of a pair with a finite likelihood
+ * sums to 1; a pair whose likelihood is -inf gets zeros in both tables and an entry whose weight is -inf is exactly 0; postB less
+ * the repeats, summed over rows and over the columns of a token, is the mb_profile_twos_counts of the transitions that write that
+ * token, the column sums of postA those of the transitions that read the column's token.  MB_DETERMINISTIC=1 as
+ * mb_profile_twos_row_posteriors; mb_profile_twos_set_rows replaces the row tables between calls.  A plain object is refused before
+ * anything is launched: "merged row posteriors take merged profiles"; a pair whose lattices exceed the memory budget on its own is
+ * the error of mb_profile_twos_counts. */
+int mb_profile_twos_row_posteriors_merged(mb_profile_twos *p, double *postA /* [sum K][nInTok+1], may be NULL */,
+                                          double *postB /* [sum rows][nCols+1], may be NULL */, double *loglike /* may be NULL */);
+
 /* ---- prefix search: imputing the input tape (--prefix-decode / --prefix-encode / --random-encode) -------------------------------
  * The node fill of the reference's PrefixTree (src/ctc.cpp:25-88) on the device, the tree and its heap on the host
  * (docs/decoding.md).  An mb_prefix holds nSeq searches (output sequence k = outTok[outOff[k]..outOff[k+1]), tokens 1..nOutTok)

@@ -812,6 +812,45 @@ def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "d
     return scores, (acc.paramCounts(machine, params) if counts else None)
 
 
+def mergedTwoPosteriors(machine: Machine, inProfiles, outProfile, backend: str = "device", params=None):
+    """Every input profile (a profile.Profile read against the machine's input alphabet, or its [K, nInTok + 1] log rows) as one
+    pair with ``outProfile`` read CTC-merged, as --recognize-merge-csv reads it (a profile.Profile, or a pair
+    (logB[L, nCols + 1], colTok) as Profile.mergeRows returns), all pairs in one batch: (posteriors, loglike), one
+    (postA[K, nInTok + 1], postB[L, nCols + 1]) and one float per input profile -- the posterior probability that each input row was
+    consumed as each input token and each output row as each column (column 0 of either: as its blank), the gradients of the pair's
+    log-likelihood in the two profiles (docs/profile_tapes.md, "Row posteriors of pairs of profiles against a merged profile").  A
+    pair that scores -inf gets zeros.  ``backend``: "device" (capi.DeviceProfileTwos.merged_row_posteriors) or "numpy"
+    (profile.TwoMergedProfileDP.mergedRowPosteriors)."""
+    import numpy as np
+    from .profile import TwoMergedProfileDP
+    if backend not in ("device", "numpy"):
+        raise MachineError('backend is "device" or "numpy"')
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    if not ev.nInTok:
+        raise MachineError("two-profile sweeps need a machine with an input alphabet")
+    if not ev.nOutTok:
+        raise MachineError("--recognize-merge-csv needs a machine with an output alphabet")
+    As = [a.logRowsIn(ev) if hasattr(a, "logRowsIn") else np.asarray(a, np.float64).reshape(-1, ev.nInTok + 1) for a in inProfiles]
+    B, colTok = _mergedRows(outProfile, ev) if hasattr(outProfile, "mergeRows") else outProfile
+    B = np.asarray(B, np.float64).reshape(-1, len(colTok) + 1)
+    if backend == "numpy":
+        tdp = TwoMergedProfileDP(ev, colTok)
+        res = [tdp.mergedRowPosteriors(A, B) for A in As]
+        return [(r[0], r[1]) for r in res], [float(r[2]) for r in res]
+    from . import capi
+    dm = capi.DeviceMachine(ev)
+    twos = None
+    try:
+        twos = capi.DeviceProfileTwos(dm, As, [B] * len(As), colTok=colTok)
+        pa, pb, ll = twos.merged_row_posteriors()
+        post = [(np.array(pa[twos.inOff[k]:twos.inOff[k + 1]]), np.array(pb[k * len(B):(k + 1) * len(B)])) for k in range(len(As))]
+    finally:
+        if twos is not None:
+            twos.close()
+        dm.close()
+    return post, [float(x) for x in ll]
+
+
 def _runTwoProfiles(args, out, machine: Machine) -> int:
     """--generate-csv beside --recognize-csv on a machine with an input alphabet: one pair of profiles (docs/profile_tapes.md,
     "Pairs of profiles").  -L and -V print [the --generate-csv argument, "", score], -C the counts, --profile-posteriors after them

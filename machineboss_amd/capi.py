@@ -42,7 +42,7 @@ EXPORTS = [
     "mb_profile_twos_row_posteriors", "mb_profile_twos_set_rows",
     "mb_profile_two_fill",
     "mb_profile_twos_set_envelopes", "mb_profile_two_fill_env", "mb_profile_twos_cells",
-    "mb_profile_twos_create_merged", "mb_profile_two_fill_merged",
+    "mb_profile_twos_create_merged", "mb_profile_two_fill_merged", "mb_profile_twos_row_posteriors_merged",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
     "mb_prefix_node_cells", "mb_prefix_create_profiles", "mb_prefix_create_merged",
 ]
@@ -158,6 +158,7 @@ def load():
     L.mb_profile_twos_viterbi.argtypes = [vp, dp, i64p, u32p, i32p, i32p, C.c_int64]
     L.mb_profile_twos_counts.argtypes = [vp, dp, dp, dp]
     L.mb_profile_twos_row_posteriors.argtypes = [vp, dp, dp, dp]
+    L.mb_profile_twos_row_posteriors_merged.argtypes = [vp, dp, dp, dp]
     L.mb_profile_twos_set_rows.argtypes = [vp, dp, dp]
     L.mb_profile_two_fill.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, dp]
     L.mb_profile_twos_set_envelopes.argtypes = [vp, i64p, i32p, i32p]
@@ -915,7 +916,7 @@ class DeviceProfileTwos:
     (mb_profile_twos_create_merged): per pair a [rows, nCols + 1] array, column 0 the blank and column c a CSV column whose output
     token is colTok[c - 1] (profile.Profile.mergeRows); forward, viterbi, counts, cells and set_profiles work the same and the
     yardstick is profile.TwoMergedProfileDP (docs/profile_tapes.md, "Pairs of profiles against a merged profile").  Envelopes and
-    row posteriors take plain profiles."""
+    row_posteriors take plain profiles; the row posteriors of a merged object are merged_row_posteriors."""
 
     def __init__(self, dm: DeviceMachine, inProfiles, outProfiles, envs=None, colTok=None):
         self.dm = dm
@@ -1011,6 +1012,19 @@ class DeviceProfileTwos:
         postB = np.zeros((int(self.rowOff[-1]), self.logB.shape[1]), np.float64) if outputs else None
         ll = np.empty(self.nPairs, np.float64)
         _check(load().mb_profile_twos_row_posteriors(self.h, _p(postA, C.c_double), _p(postB, C.c_double), _p(ll, C.c_double)))
+        return postA, postB, ll
+
+    def merged_row_posteriors(self, inputs: bool = True, outputs: bool = True):
+        """Of a merged object: returns (postA[sumK, nInTok + 1], postB[sumRows, nCols + 1], loglike[nPairs]).  postB[rowOff[k] + r][c]
+        is the posterior probability that output row r of pair k was consumed as column c (0: the blank; a column holds its repeats
+        and its fresh emissions), postA[inOff[k] + i][a] that input row i was consumed as input token a (0: the input blank) -- the
+        gradients of loglike[k] in those entries of the two profiles; zeros for a pair whose likelihood is -inf
+        (docs/profile_tapes.md, "Row posteriors of pairs of profiles against a merged profile").  ``inputs=False`` /
+        ``outputs=False``: that table is None and its kernel is not launched."""
+        postA = np.zeros((int(self.inOff[-1]), self.logA.shape[1]), np.float64) if inputs else None
+        postB = np.zeros((int(self.rowOff[-1]), self.logB.shape[1]), np.float64) if outputs else None
+        ll = np.empty(self.nPairs, np.float64)
+        _check(load().mb_profile_twos_row_posteriors_merged(self.h, _p(postA, C.c_double), _p(postB, C.c_double), _p(ll, C.c_double)))
         return postA, postB, ll
 
     def set_profiles(self, inProfiles=None, outProfiles=None):

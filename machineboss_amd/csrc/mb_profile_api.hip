@@ -1241,6 +1241,15 @@ static long long pt_rowpost_groups(const mb_profile_twos *p, long long p0, long 
     return profile_pair_rowpost_rows(pt_ncells(p, k), p->m->S, (int)lines(k), (int)NC, tabMax);
   });
 }
+// the same for k_profile_two_merge_rowpost: lines of (K + 1)(nCols + 1) S items and nCols + 1 bins on axis 0, of (L + 1)(nCols + 1) S
+// items and nIn + 1 bins on axis 1
+static long long pt_merge_rowpost_groups(const mb_profile_twos *p, long long p0, long long p1, int axis, int tabMax) {
+  const long long NC = axis ? p->m->nIn + 1 : p->nCols + 1;
+  auto lines = [&](long long k) { return axis ? pt_in(p, k) : pt_rows(p, k); };
+  return rowpost_groups(p0, p1, lines, [&](long long k) {
+    return profile_pair_rowpost_rows(pt_ncells(p, k) * (p->nCols + 1), p->m->S, (int)lines(k), (int)NC, tabMax);
+  });
+}
 
 }  // namespace mb
 
@@ -1427,6 +1436,49 @@ int mb_profile_twos_row_posteriors(mb_profile_twos *p, double *postA, double *po
   if (!rc) rc = fetch_posteriors(postB, d_pb, nb);
   if (!rc && loglike) rc = fetch_loglike(loglike, d_ll, p->n);
   g_last_kernel = p->hasEnv ? "k_profile_two_env_rowpost" : "k_profile_two_rowpost";
+  return rc;
+}
+
+// The merged object's own entry: mb_profile_twos_counts on a merged object chunk for chunk -- the materialised merged Forward and
+// Backward, whose X / T rings share one scratch buffer -- then the flat k_profile_two_merge_rowpost over the two lattices, once per
+// table that was asked for.
+int mb_profile_twos_row_posteriors_merged(mb_profile_twos *p, double *postA, double *postB, double *loglike) {
+  ApiGuard guard;
+  if (!p) { set_error("null argument"); return 1; }
+  if (!p->nCols) { set_error("merged row posteriors take merged profiles"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  latch_deterministic();
+  const long long PL = p->nCols + 1, CA = p->m->nIn + 1, nb = postB ? p->totalRows * PL : 0, na = postA ? p->totalIn * CA : 0;
+  const int tabMax = rowpost_table();
+  std::vector<Chunk> chunks;
+  auto bytes = [&](long long k) {      // both lattices, the X / T ring and the pair's bins of both tables
+    return 2.0 * pt_cell_bytes(p, k) + pt_ring_bytes(p, k, false) + 8.0 * (double)(pt_rows(p, k) * PL + pt_in(p, k) * CA);
+  };
+  if (!lattice_chunks(p->n, "pair", bytes, chunks)) return 1;
+  SmBuf<double> d_ll, d_bll, d_pa, d_pb;
+  MB_HIP(d_ll.alloc(p->n));
+  if (!hip_ok(d_bll.alloc(p->n), "hipMalloc(loglike)") || !hip_ok(d_pa.alloc(na), "hipMalloc(row posteriors)") ||
+      !hip_ok(d_pb.alloc(nb), "hipMalloc(row posteriors)")) return 1;
+  int rc = for_chunks<TwoProfPlan>(chunks, pt_build(p, false), [&](const Chunk &c, TwoProfPlan &pl, Timer &tm) {
+    const long long np = c.p1 - c.p0;
+    double *fwd = ws_array<double>(0, pl.cells);
+    double *bwd = ws_array<double>(1, pl.cells);
+    double *scratch = pl.ring ? (double *)ws_get(2, (size_t)pl.ring * sizeof(double)) : nullptr;
+    if (!fwd || !bwd || (pl.ring && !scratch)) return 1;
+    const long long groupsB = pt_merge_rowpost_groups(p, c.p0, c.p1, 0, tabMax), groupsA = pt_merge_rowpost_groups(p, c.p0, c.p1, 1, tabMax);
+    if (np * std::max(groupsA, groupsB) > 0x7fffffff) { set_error("too many pairs in one chunk"); return 1; }
+    {
+      Timed t(tm, 1);
+      if (pt_fwd_mat(p, MB_FORWARD, pl, np, fwd, scratch, d_ll + c.p0) || pt_bwd(p, pl, np, bwd, scratch, d_bll + c.p0)) return 1;
+      if (postB && launch_profile_two_merge_rowpost(p->m, pt_map(p), 0, pl.d.p, (int)np, (int)groupsB, tabMax, p->d_logA, p->d_logB, fwd, bwd, d_ll + c.p0, d_pb, g_stream)) return 1;
+      if (postA && launch_profile_two_merge_rowpost(p->m, pt_map(p), 1, pl.d.p, (int)np, (int)groupsA, tabMax, p->d_logA, p->d_logB, fwd, bwd, d_ll + c.p0, d_pa, g_stream)) return 1;
+    }
+    return hip_ok(hipStreamSynchronize(g_stream), "row posteriors") ? 0 : 1;      // (the next chunk takes the lattices over)
+  });
+  if (!rc) rc = fetch_posteriors(postA, d_pa, na);
+  if (!rc) rc = fetch_posteriors(postB, d_pb, nb);
+  if (!rc && loglike) rc = fetch_loglike(loglike, d_ll, p->n);
+  g_last_kernel = "k_profile_two_merge_rowpost";
   return rc;
 }
 

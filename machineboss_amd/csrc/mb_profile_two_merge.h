@@ -38,6 +38,13 @@ int launch_profile_two_merge_bwd(const mb_machine *m, MergeMap mm, const PairPro
 // counts[nTrans] += posteriors of the n pairs (fwdPool / bwdPool: their materialised lattices); det: 64-bit fixed point at 2^-36
 int launch_profile_two_merge_counts(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, int groupsPerPair, const double *logA,
                                     const double *logB, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
+// post = the row posteriors of the n pairs on one axis (0: post[(rowBase + r) * (nCols + 1) + c], 1: post[(inBase + i) * (nIn + 1) + a]),
+// every bin of every line written (nothing to clear); groupsPerPair: at least the line blocks (profile_pair_rowpost_rows over lines
+// of (K + 1)(nCols + 1) S items on axis 0, (L + 1)(nCols + 1) S on axis 1) of the pair that has most, 1 024 at the most; loglike: the
+// Forward sweep's, per pair of the launch; det: post holds 64-bit fixed point at 2^-36
+int launch_profile_two_merge_rowpost(const mb_machine *m, MergeMap mm, int axis, const PairProfDesc *d, int n, int groupsPerPair, int tabMax,
+                                     const double *logA, const double *logB, const double *fwdPool, const double *bwdPool,
+                                     const double *loglike, double *post, hipStream_t st);
 int launch_profile_two_merge_traceback(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, const double *logA,
                                        const double *logB, const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows,
                                        long long *len, hipStream_t st);

@@ -1,4 +1,4 @@
-// mb_profile_two_merge.hip -- Forward / Backward / Viterbi / posterior counts of a machine WITH an input alphabet between an input
+// mb_profile_two_merge.hip -- Forward / Backward / Viterbi / posterior counts / row posteriors of a machine WITH an input alphabet between an input
 // PROFILE A of K rows and a CTC-MERGED output profile B of L rows: the semantics of
 // compose(A.machine(), compose(M, transpose(CSVProfile::mergingMachine()))) with both tapes empty, restated in docs/profile_tapes.md
 // ("Pairs of profiles against a merged profile"):
@@ -346,6 +346,141 @@ __global__ __launch_bounds__(256) void k_profile_two_merge_counts(DevMachine m, 
   acc.flush();
 }
 
+// Row posteriors of both tapes (docs/profile_tapes.md, "Row posteriors of pairs of profiles against a merged profile"): the terms of
+// k_profile_two_merge_counts, the blank masses of either tape and the repeats, binned by (line, column) instead of by transition.
+// AXIS 0 bins output rows -- post[(rowBase + r) * (nCols + 1) + c] is the gradient of the log-likelihood in B[r][c]:
+//   post[r][0] = sum_i sum_p sum_s exp((N_F[i][r][p][s] - LL) + (B[r][0] + NB[i][r+1][0][s]))
+//   post[r][c] = sum_i sum_s exp((N_F[i][r][c][s] - LL) + (B[r][c] + NB[i][r+1][c][s]))                     (the repeat)
+//              + the match terms (read from Z_F) and the output-only terms (read from W_F) of every plane k != c
+// AXIS 1 bins input rows -- post[(inBase + i) * (nIn + 1) + a] is the gradient in A[i][a]:
+//   post[i][0] = sum_r sum_p sum_s exp((Z_F[i][r][p][s] - LL) + (A[i][0] + ZB[i+1][r][p][s]))
+//   post[i][a] = the input-only terms (into WB[i+1][r], same plane) and the match terms of every column c != k, all read from Z_F
+// The scheme is the one of k_profile_pair_merge_rowpost (mb_profile_pair_merge.hip) once per axis, as k_profile_two_rowpost
+// (mb_profile_two.hip) applies k_profile_pair_rowpost: the work items are (line, cell of the line, plane, state) in that order and a
+// workgroup owns whole lines, blocks of profile_pair_rowpost_rows lines dealt round robin to the pair's groups.  A lane sums its
+// terms of one column in a register, in CSR order (axis 0, column c: the rows s*K + a*C + colTok[c] for a = 1..nIn, then
+// s*K + colTok[c]; axis 1, column a: the row s*K + a*C, then the rows s*K + a*C + colTok[c] for c ascending): the sum over k != c runs
+// over the items, neither exclusion vector of the Forward sweep is needed.  rowpost_add reduces the lane sums of a wavefront that
+// lies in one line and adds to the workgroup's LDS table, which is then stored: every bin has one writing workgroup, so there is no
+// global atomic and nothing to clear beforehand.  A line of more than tabMax columns is summed in its global bins instead, cleared
+// by the workgroup that owns it.  A pair whose likelihood is -inf gets zeros by the same stores.  loglike: the Forward sweep's, per
+// pair of the launch.  det: post holds 64-bit fixed point at 2^-36.
+template <int AXIS>
+__global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_merge_rowpost(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+                                                                               int groupsPerPair, const double *__restrict__ logA,
+                                                                               const double *__restrict__ logB, const double *__restrict__ fwdPool,
+                                                                               const double *__restrict__ bwdPool, const double *__restrict__ loglike,
+                                                                               double *post, int tabMax, int det) {
+  __shared__ double ltab[ROWPOST_LDS_MAX];
+  const int pair = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
+  const PairProfDesc pd = descs[pair];
+  const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, nC = mm.nCols, PL = nC + 1, K = pd.nIn, L = pd.nRows;
+  const int NL = AXIS ? K : L, NC = AXIS ? CA : PL, NX = AXIS ? L + 1 : K + 1;      // lines, bins of a line, cells of a line
+  if (NL == 0) return;
+  const double *A = logA + pd.inBase * CA;
+  const double *B = logB + pd.rowBase * PL;
+  const TwoMergeLattice<true> F{const_cast<double *>(fwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0},
+      Bk{const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  const double LL = loglike[pair];
+  const long long PS = (long long)PL * S, lineItems = NX * PS;
+  const int R = profile_pair_rowpost_rows((long long)(K + 1) * (L + 1) * PL, S, NL, NC, tabMax);
+  const bool useLds = NC <= tabMax;
+  const int lane = threadIdx.x & 63;
+  for (long long lb = (long long)group * R; lb < NL; lb += (long long)groupsPerPair * R) {
+    const int l0 = (int)lb, l1 = (int)min((long long)NL, lb + R), nBins = (l1 - l0) * NC;
+    double *out = post + ((AXIS ? pd.inBase : pd.rowBase) + l0) * NC;
+    double *tab = useLds ? ltab : out;
+    for (int e = threadIdx.x; e < nBins; e += blockDim.x) tab[e] = 0.0;      // (the fixed point's zero has the same bits)
+    if (!useLds) __threadfence();
+    __syncthreads();
+    if (LL > -INFINITY) {
+      const long long nItems = (l1 - l0) * lineItems;
+      for (long long base = threadIdx.x - lane; base < nItems; base += blockDim.x) {      // (a wavefront stays whole in here)
+        const long long idx = base + lane;
+        const bool valid = idx < nItems;
+        int line = l0, x = 0, k = 0, s = 0, ks = 0;
+        if (valid) {
+          const long long ln = idx / lineItems, rem = idx - ln * lineItems;
+          line = l0 + (int)ln;
+          x = (int)(rem / PS);
+          ks = (int)(rem - x * PS);
+          k = ks / S;
+          s = ks - k * S;
+        }
+        const int i = AXIS ? line : x, r = AXIS ? x : line;
+        const double z = valid ? F.at(i, r, 2)[ks] - LL : -INFINITY;
+        const bool whole = __all(valid && line == __shfl(line, 0));
+        // (the line's own coordinate is inside: r < L on axis 0, i < K on axis 1)
+        const bool diag = valid && i < K && r < L;
+        const double *Ai = A + (long long)i * CA;        // read when i < K
+        const double *Br = B + (long long)r * PL;        // read when r < L
+        const double *Nd = diag ? Bk.at(i + 1, r + 1, 0) : nullptr;
+        const int sRow = s * KK, bin0 = (line - l0) * NC;
+        const bool zLive = z > -INFINITY;
+        if (AXIS == 0) {
+          const double f = valid ? F.at(i, r, 1)[ks] - LL : -INFINITY, n = valid ? F.at(i, r, 0)[ks] - LL : -INFINITY;
+          const double *Nu = Bk.at(i, r + 1, 0);         // (an address alone where the item is not valid: read only where f or n lives)
+          const bool nLive = n > -INFINITY, fLive = f > -INFINITY, dLive = diag && zLive;
+          rowpost_add(tab, bin0, nLive ? exp(n + (Br[0] + Nu[s])) : 0.0, whole, lane, det);
+          for (int c = 1; c < PL; ++c) {      // the out-edges of (s, a) that write the column's token are one CSR row
+            double v = 0.0;
+            if (valid && c == k) {
+              if (nLive) v = exp(n + (Br[c] + Nu[ks]));
+            } else if (fLive || dLive) {
+              const double pc = Br[c];
+              if (pc > -INFINITY) {
+                const int tok = mm.colTok[c - 1];
+                if (dLive) {
+                  const double *Ndc = Nd + (long long)c * S;
+                  for (int a = 1; a <= m.nIn; ++a) {
+                    const int row = sRow + a * C + tok;
+                    const double wa = Ai[a];
+                    const int e1 = m.outOff[row + 1];
+                    for (int e = m.outOff[row]; e < e1; ++e) v += exp(z + (((m.outW[e] + wa) + pc) + Ndc[m.outDst[e]]));
+                  }
+                }
+                if (fLive) {
+                  const double *Nuc = Nu + (long long)c * S;
+                  const int e1 = m.outOff[sRow + tok + 1];
+                  for (int e = m.outOff[sRow + tok]; e < e1; ++e) v += exp(f + ((m.outW[e] + pc) + Nuc[m.outDst[e]]));
+                }
+              }
+            }
+            rowpost_add(tab, bin0 + c, v, whole, lane, det);
+          }
+        } else {
+          const double *Zl = Bk.at(i + 1, r, 2), *Wl = Bk.at(i + 1, r, 1) + (long long)k * S;      // (i < K: the cell is inside)
+          rowpost_add(tab, bin0, zLive ? exp(z + (Ai[0] + Zl[ks])) : 0.0, whole, lane, det);
+          for (int a = 1; a < CA; ++a) {      // the out-edges of s that read a: the input-only row, then the rows of the columns' tokens
+            double v = 0.0;
+            if (zLive) {
+              const int row = sRow + a * C;
+              const double wa = Ai[a];
+              const int e1 = m.outOff[row + 1];
+              for (int e = m.outOff[row]; e < e1; ++e) v += exp(z + ((m.outW[e] + wa) + Wl[m.outDst[e]]));
+              if (diag)
+                for (int c = 1; c < PL; ++c) {
+                  const double pc = Br[c];
+                  if (c == k || !(pc > -INFINITY)) continue;
+                  const int tok = mm.colTok[c - 1];
+                  const double *Ndc = Nd + (long long)c * S;
+                  const int t1 = m.outOff[row + tok + 1];
+                  for (int e = m.outOff[row + tok]; e < t1; ++e) v += exp(z + (((m.outW[e] + wa) + pc) + Ndc[m.outDst[e]]));
+                }
+            }
+            rowpost_add(tab, bin0 + a, v, whole, lane, det);
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (useLds) {
+      for (int e = threadIdx.x; e < nBins; e += blockDim.x) out[e] = tab[e];
+      __syncthreads();
+    }
+  }
+}
+
 // Viterbi traceback over a materialised max lattice, one lane per pair: from the first plane that attains the score at
 // Z[K][L][.][S-1] back to N[0][0][0][0], taking at every cell the first candidate (in the fill's order) whose value equals the cell;
 // an emitting edge comes from the lowest plane k != c whose Z (match) or W (output-only) equals the edge's XZ / XW.  Blanks of
@@ -509,6 +644,17 @@ int launch_profile_two_merge_counts(const mb_machine *m, MergeMap mm, const Pair
   k_profile_two_merge_counts<<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(
       m->dev, mm, d, groupsPerPair, logA, logB, fwdPool, bwdPool, m->nTrans, counts, g_deterministic ? 1 : 0);
   return hip_ok(hipGetLastError(), "k_profile_two_merge_counts") ? 0 : 1;
+}
+
+int launch_profile_two_merge_rowpost(const mb_machine *m, MergeMap mm, int axis, const PairProfDesc *d, int n, int groupsPerPair, int tabMax,
+                                     const double *logA, const double *logB, const double *fwdPool, const double *bwdPool,
+                                     const double *loglike, double *post, hipStream_t st) {
+  if (n <= 0) return 0;
+  const dim3 g((unsigned)((long long)n * groupsPerPair)), b(ROWPOST_THREADS);
+  const int det = g_deterministic ? 1 : 0;
+  if (axis) k_profile_two_merge_rowpost<1><<<g, b, 0, st>>>(m->dev, mm, d, groupsPerPair, logA, logB, fwdPool, bwdPool, loglike, post, tabMax, det);
+  else k_profile_two_merge_rowpost<0><<<g, b, 0, st>>>(m->dev, mm, d, groupsPerPair, logA, logB, fwdPool, bwdPool, loglike, post, tabMax, det);
+  return hip_ok(hipGetLastError(), "k_profile_two_merge_rowpost") ? 0 : 1;
 }
 
 int launch_profile_two_merge_traceback(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, const double *logA,

@@ -1550,6 +1550,56 @@ class TwoMergedProfileDP(TwoProfileDP):
     def rowPosteriors(self, A, B, env=None):
         raise MachineError("row posteriors take plain profiles")
 
+    def mergedRowPosteriors(self, A, B, repeats: Optional[list] = None) -> Tuple[np.ndarray, np.ndarray, float]:
+        """(postA[K, nInTok + 1], postB[L, nCols + 1], Forward loglike): postB[r][c] is the posterior probability that output row r
+        was consumed as column c (column 0: as the blank), postA[i][a] that input row i was consumed as input token a (column 0:
+        as the input blank) -- the gradients of loglike in B[r][c] and in A[i][a] (docs/profile_tapes.md, "Row posteriors of pairs
+        of profiles against a merged profile").  The terms of counts() and of its three masses, the emitting ones taken plane by
+        plane off Z and W instead of through XZ and XW, binned by (row, column) of either tape; a match term goes to both tables.
+        ``repeats``, if a list, receives the [L, nCols + 1] repeat part of postB, so that postB - repeats sums per token to the
+        counts.  Every row of either table sums to 1; zeros for a -inf pair; exactly 0 where the weight is -inf."""
+        A, B = self._checkTwo(A, B)
+        ll, NF, WF, ZF = self.forward(A, B)
+        K, L, PL = len(A), len(B), self.PL
+        postA = np.zeros((K, self.em.nInTok + 1)); postB = np.zeros((L, PL)); rep = np.zeros((L, PL))
+        if repeats is not None:
+            repeats.append(rep)
+        if not ll > _NEG:
+            return postA, postB, ll
+        _, NB, WB, ZB = self.backward(A, B)
+        _, mS, mD, mW, mA, mC = self.mCol
+        _, eS, eD, eW, eC = self.emitCol
+        _, iS, iD, iW, iA, _ = self.iAll
+        planes = np.arange(PL)[:, None]
+        mKeep, eKeep = mC[None, :] != planes, eC[None, :] != planes      # [plane k, edge]: the edge's column is another than k
+
+        def mass(b):
+            return float(np.exp(b[b > _NEG]).sum())
+        with np.errstate(invalid="ignore"):
+            for i in range(K + 1):
+                for r in range(L + 1):
+                    f, z = WF[i, r] - ll, ZF[i, r] - ll
+                    if r < L:
+                        if i < K:
+                            t = z[:, mS] + (((mW + A[i][mA]) + B[r][mC]) + NB[i + 1, r + 1][mC, mD])[None, :]
+                            live = mKeep & (t > _NEG)
+                            np.add.at(postB[r], np.broadcast_to(mC, t.shape)[live], np.exp(t[live]))
+                            np.add.at(postA[i], np.broadcast_to(mA, t.shape)[live], np.exp(t[live]))
+                        t = f[:, eS] + ((eW + B[r][eC]) + NB[i, r + 1][eC, eD])[None, :]
+                        live = eKeep & (t > _NEG)
+                        np.add.at(postB[r], np.broadcast_to(eC, t.shape)[live], np.exp(t[live]))
+                        n = NF[i, r] - ll
+                        postB[r, 0] += mass(n + (B[r][0] + NB[i, r + 1][0]))
+                        b = n[1:] + (B[r][1:, None] + NB[i, r + 1][1:])
+                        rep[r, 1:] += np.where(b > _NEG, np.exp(b), 0.0).sum(axis=1)
+                    if i < K:
+                        t = z[:, iS] + ((iW + A[i][iA]) + WB[i + 1, r][:, iD])
+                        live = t > _NEG
+                        np.add.at(postA[i], np.broadcast_to(iA, t.shape)[live], np.exp(t[live]))
+                        postA[i, 0] += mass(z + (A[i][0] + ZB[i + 1, r]))
+        postB += rep
+        return postA, postB, ll
+
     def viterbi(self, A, B, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
         """(score, global edge ids start -> end, output row, input row at which each fired); the first maximum in the fill's
         candidate order, rows as TwoProfileDP.viterbi; blanks of either tape and repeat rows are not edges.  ``census``: per step

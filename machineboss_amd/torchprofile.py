@@ -200,6 +200,78 @@ def two_profile_loglike(machine_or_dm, logA, inOff, logB, rowOff, envs=None, bac
     return _TwoProfileLoglike.apply(logA, logB, machine_or_dm, inOff, rowOff, envs, backend)
 
 
+def _two_merged_row_posteriors(machine_or_dm, A, inOff, B, rowOff, colTok, wantA, wantB, backend):
+    """_two_row_posteriors against CTC-merged output rows: postB is [sumRows, nCols + 1]."""
+    n = len(rowOff) - 1
+    As = [A[inOff[k]:inOff[k + 1]] for k in range(n)]
+    Bs = [B[rowOff[k]:rowOff[k + 1]] for k in range(n)]
+    if backend == "numpy":
+        from .profile import TwoMergedProfileDP
+        em = getattr(machine_or_dm, "em", machine_or_dm)
+        dp = TwoMergedProfileDP(em, colTok)
+        postA, postB = np.zeros(A.shape, np.float64), np.zeros(B.shape, np.float64)
+        ll = np.empty(n, np.float64)
+        for k in range(n):
+            postA[inOff[k]:inOff[k + 1]], postB[rowOff[k]:rowOff[k + 1]], ll[k] = dp.mergedRowPosteriors(As[k], Bs[k])
+        return (postA if wantA else None), (postB if wantB else None), ll
+    if backend != "device":
+        raise ValueError('backend is "device" or "numpy"')
+    from . import capi
+    own = not isinstance(machine_or_dm, capi.DeviceMachine)
+    dm = capi.DeviceMachine(machine_or_dm) if own else machine_or_dm
+    twos = None
+    try:
+        twos = capi.DeviceProfileTwos(dm, As, Bs, colTok=colTok)
+        return twos.merged_row_posteriors(inputs=wantA, outputs=wantB)
+    finally:
+        if twos is not None:
+            twos.close()
+        if own:
+            dm.close()
+
+
+class _TwoMergedProfileLoglike(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logA, logB, machine_or_dm, inOff, rowOff, colTok, backend):
+        A = np.ascontiguousarray(logA.detach().cpu().numpy(), np.float64)
+        B = np.ascontiguousarray(logB.detach().cpu().numpy(), np.float64)
+        wantA, wantB = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        postA, postB, ll = _two_merged_row_posteriors(machine_or_dm, A, inOff, B, rowOff, colTok, wantA, wantB, backend)
+        ctx.inOff, ctx.rowOff = inOff, rowOff
+        ctx.save_for_backward(None if postA is None else torch.from_numpy(postA).to(logA.device),
+                              None if postB is None else torch.from_numpy(postB).to(logB.device))
+        return torch.from_numpy(ll).to(logB.device)
+
+    backward = staticmethod(_TwoProfileLoglike.backward)      # (the same seven inputs: two tables, five constants)
+
+
+def merged_two_profile_loglike(machine_or_dm, logA, inOff, logB, rowOff, colTok, backend="device"):
+    """two_profile_loglike against CTC-merged frames on the output tape: tensor[nPairs] of log-likelihoods, pair k the rows
+    inOff[k]..inOff[k + 1] of ``logA``, a float64 [sumK, nInTok + 1] tensor (column 0 the input blank), against the rows
+    rowOff[k]..rowOff[k + 1] of ``logB``, a float64 [sumRows, nCols + 1] tensor with column 0 the blank and column c a frame's log
+    weight of the output token colTok[c - 1]; repeats collapse and a blank separates equal symbols (docs/profile_tapes.md, "Row
+    posteriors of pairs of profiles against a merged profile").  Differentiable in both tables: the gradient is grad_out[k] times
+    the merged row posteriors of pair k on that tape, zeros for a pair that scores -inf, computed only for the tables that require
+    one.  With a one-hot ``logA`` and a one-state echo transducer the result is -ctc_loss(logB, x) per pair.  ``machine_or_dm``: an
+    EvaluatedMachine or a capi.DeviceMachine (kept open for the caller).  ``backend``: "device" (one
+    capi.DeviceProfileTwos.merged_row_posteriors() call) or "numpy" (profile.TwoMergedProfileDP.mergedRowPosteriors, no GPU
+    needed).  Tensors go through host memory, as pair_profile_loglike's do."""
+    if logA.dtype != torch.float64 or logA.dim() != 2:
+        raise ValueError("logA is a float64 [sumK, nInTok + 1] tensor")
+    if logB.dtype != torch.float64 or logB.dim() != 2:
+        raise ValueError("logB is a float64 [sumRows, nCols + 1] tensor")
+    inOff = np.asarray(inOff, np.int64).reshape(-1)
+    rowOff = np.asarray(rowOff, np.int64).reshape(-1)
+    if len(inOff) < 1 or inOff[0] != 0 or inOff[-1] != logA.shape[0] or (np.diff(inOff) < 0).any():
+        raise ValueError("inOff has one entry per pair and one more, from 0 up to the rows of logA")
+    if len(rowOff) != len(inOff) or rowOff[0] != 0 or rowOff[-1] != logB.shape[0] or (np.diff(rowOff) < 0).any():
+        raise ValueError("rowOff has one entry per pair and one more, from 0 up to the rows of logB")
+    colTok = np.asarray(colTok, np.int64).reshape(-1)
+    if logB.shape[1] != len(colTok) + 1:
+        raise ValueError("merged profiles: logB has one column per entry of colTok and the blank in front")
+    return _TwoMergedProfileLoglike.apply(logA, logB, machine_or_dm, inOff, rowOff, colTok, backend)
+
+
 def _one_row_posteriors(machine_or_dm, P, rowOff, colTok, backend):
     """(post[sumRows, width], loglike[nProfiles]) in numpy, on the device or by the numpy yardstick."""
     n = len(rowOff) - 1
