@@ -314,8 +314,8 @@ int mb_profile_pair_fill_merged_env(mb_machine *m, int mode, const int32_t *inTo
  * blanks on either tape are not edges.  pathCap must hold the sum of mb_profile_pair_path_bound(m, K, rows) over the pairs.  Counts
  * with MB_DETERMINISTIC=1 go through 64-bit fixed point and are the same bits from call to call.  Materialised lattices:
  * cells[(((i*(nRows+1)) + row)*3 + layer)*nStates + state]; mb_profile_two_fill: cellsOut[(nIn+1)*(nRows+1)*3*nStates], mode
- * MB_FORWARD / MB_VITERBI / MB_BACKWARD (Backward: layer 0 = from the arrived stage, 2 = from the committed stage).  Envelopes are
- * below; there is no CTC-merged form.  Errors, before anything is launched: "two-profile sweeps need a machine with an input
+ * MB_FORWARD / MB_VITERBI / MB_BACKWARD (Backward: layer 0 = from the arrived stage, 2 = from the committed stage).  Envelopes and
+ * the CTC-merged form are below.  Errors, before anything is launched: "two-profile sweeps need a machine with an input
  * alphabet", NaN / +inf weights in either table, a pathCap below the bound, a lattice beyond the memory budget on its own. */
 typedef struct mb_profile_twos mb_profile_twos;
 mb_profile_twos *mb_profile_twos_create(mb_machine *m, int64_t nPairs, const double *logA, const int64_t *inOff, const double *logB,
@@ -372,7 +372,8 @@ int64_t mb_profile_twos_cells(const mb_profile_twos *p);   /* doubles of all mat
  * cellsOut[(nIn+1)*(nRows+1)*3*(nCols+1)*nStates], mode MB_FORWARD, MB_VITERBI or MB_BACKWARD.  The memory budget chunks by the
  * lattices, the scratch rings of the pairs whose ring does not fit LDS, and the path slots; an anti-diagonal of more than 2^31
  * (cell, plane, state) items is an error at create.  mb_profile_twos_set_envelopes fails on the object with "envelopes take plain
- * profiles", mb_profile_twos_row_posteriors with "row posteriors take plain profiles". */
+ * profiles" (its entry is mb_profile_twos_set_envelopes_merged, below), mb_profile_twos_row_posteriors with "row posteriors take
+ * plain profiles". */
 mb_profile_twos *mb_profile_twos_create_merged(mb_machine *m, int64_t nPairs, const double *logA, const int64_t *inOff, const double *logB,
                                                const int64_t *rowOff, int32_t nCols, const int32_t *colTok);
 int mb_profile_two_fill_merged(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, int32_t nCols,
@@ -393,6 +394,24 @@ int mb_profile_two_fill_merged(mb_machine *m, int mode, const double *logA, int6
  * the error of mb_profile_twos_counts. */
 int mb_profile_twos_row_posteriors_merged(mb_profile_twos *p, double *postA /* [sum K][nInTok+1], may be NULL */,
                                           double *postB /* [sum rows][nCols+1], may be NULL */, double *loglike /* may be NULL */);
+
+/* Pairs of profiles against merged profiles under an envelope (docs/profile_tapes.md, "Pairs of profiles against a merged profile
+ * under an envelope"): the envelopes of mb_profile_twos_set_envelopes -- same arguments, same checks, same three messages -- on a
+ * merged two-profile object.  Cell (i, r) exists iff inStart[r] <= i < inEnd[r], in every plane; N, W, Z, the exclusion vectors XW
+ * and XZ and, in the Backward, NB, WB, ZB, TZ and TW of every other cell are -inf.  No call mixes geometries, as for the plain
+ * object: if any pair has an envelope EVERY pair runs the envelope kernels, a pair that was given none under the full envelope,
+ * whose results are the bits of no envelope; one launch per kernel and chunk.  Materialised lattices are compact,
+ * cells[(((off[r] + i - inStart[r])*3 + layer)*(nCols+1) + plane)*nStates + state], and mb_profile_twos_cells counts them
+ * (3 nStates (nCols+1) sum(inEnd - inStart) doubles per pair; the memory budget chunks by it).  mb_profile_twos_forward / _viterbi /
+ * _counts / _row_posteriors_merged then sweep the envelope cells alone, with the tie order, the path format and the path bound of
+ * the rectangle; mb_profile_twos_set_rows leaves the envelopes in place.  envOff == NULL clears.  A plain object is refused with
+ * "merged envelopes take merged profiles"; a rejected call leaves the pairs without envelopes and launches nothing.
+ * (mb_profile_twos_set_envelopes keeps refusing a merged object.)  mb_profile_two_fill_merged_env hands back the full rectangle of
+ * mb_profile_two_fill_merged with -inf outside in all layers and planes; both envelope pointers NULL = no envelope. */
+int mb_profile_twos_set_envelopes_merged(mb_profile_twos *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd);
+int mb_profile_two_fill_merged_env(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows,
+                                   int32_t nCols, const int32_t *colTok, const int32_t *envStart, const int32_t *envEnd,
+                                   double *cellsOut);
 
 /* ---- prefix search: imputing the input tape (--prefix-decode / --prefix-encode / --random-encode) -------------------------------
  * The node fill of the reference's PrefixTree (src/ctc.cpp:25-88) on the device, the tree and its heap on the host

@@ -812,17 +812,21 @@ def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "d
     return scores, (acc.paramCounts(machine, params) if counts else None)
 
 
-def mergedTwoPosteriors(machine: Machine, inProfiles, outProfile, backend: str = "device", params=None):
-    """Every input profile (a profile.Profile read against the machine's input alphabet, or its [K, nInTok + 1] log rows) as one
-    pair with ``outProfile`` read CTC-merged, as --recognize-merge-csv reads it (a profile.Profile, or a pair
-    (logB[L, nCols + 1], colTok) as Profile.mergeRows returns), all pairs in one batch: (posteriors, loglike), one
-    (postA[K, nInTok + 1], postB[L, nCols + 1]) and one float per input profile -- the posterior probability that each input row was
-    consumed as each input token and each output row as each column (column 0 of either: as its blank), the gradients of the pair's
-    log-likelihood in the two profiles (docs/profile_tapes.md, "Row posteriors of pairs of profiles against a merged profile").  A
-    pair that scores -inf gets zeros.  ``backend``: "device" (capi.DeviceProfileTwos.merged_row_posteriors) or "numpy"
-    (profile.TwoMergedProfileDP.mergedRowPosteriors)."""
+def scoreMergedTwos(machine: Machine, inProfiles, outProfile, backend: str = "device", params=None, loglike: bool = True,
+                    viterbi: bool = False, counts: bool = False, posteriors: bool = False, band: Optional[int] = None):
+    """scoreTwoProfiles(merge=True) with everything the merged two-profile pairs have: every input profile (a profile.Profile read
+    against the machine's input alphabet, or its [K, nInTok + 1] log rows) as one pair with ``outProfile`` read CTC-merged (a
+    profile.Profile, or a pair (logB[L, nCols + 1], colTok) as Profile.mergeRows returns); the same return shape, (scores,
+    paramCounts).  ``band``: every pair is swept under seqpair.Envelope.band(K, L, band), K the rows of its input profile, on both
+    backends (docs/profile_tapes.md, "Pairs of profiles against a merged profile under an envelope"); a width that cannot bridge
+    the slope raises MachineError("Envelope is not connected").  ``posteriors``: scores["posteriors"] holds one
+    (postA[K, nInTok + 1], postB[L, nCols + 1]) per input profile, as mergedTwoPosteriors returns them -- zeros for a pair that
+    scores -inf; the key is absent when not asked for.  ``backend``: "device" (capi.DeviceProfileTwos with colTok) or "numpy"
+    (profile.TwoMergedProfileDP)."""
     import numpy as np
+    from . import dp
     from .profile import TwoMergedProfileDP
+    from .seqpair import Envelope
     if backend not in ("device", "numpy"):
         raise MachineError('backend is "device" or "numpy"')
     ev = EvaluatedMachine.fromMachine(machine, params)
@@ -833,15 +837,79 @@ def mergedTwoPosteriors(machine: Machine, inProfiles, outProfile, backend: str =
     As = [a.logRowsIn(ev) if hasattr(a, "logRowsIn") else np.asarray(a, np.float64).reshape(-1, ev.nInTok + 1) for a in inProfiles]
     B, colTok = _mergedRows(outProfile, ev) if hasattr(outProfile, "mergeRows") else outProfile
     B = np.asarray(B, np.float64).reshape(-1, len(colTok) + 1)
+    envs = [None] * len(As) if band is None else [Envelope.band(len(A), len(B), int(band)) for A in As]
+    acc = dp.MachineCounts(ev)
+    fwd = vit = post = None
     if backend == "numpy":
         tdp = TwoMergedProfileDP(ev, colTok)
-        res = [tdp.mergedRowPosteriors(A, B) for A in As]
+        fwd = [tdp.forward(A, B, env=e)[0] for A, e in zip(As, envs)] if loglike else None
+        if counts:
+            for A, e in zip(As, envs):
+                c, ll = tdp.counts(A, B, env=e)
+                acc._flat += c
+                acc.loglike += ll
+        vit = [tdp.forward(A, B, "max", env=e)[0] for A, e in zip(As, envs)] if viterbi else None
+        post = [tdp.mergedRowPosteriors(A, B, env=e)[:2] for A, e in zip(As, envs)] if posteriors else None
+    else:
+        from . import capi
+        dm = capi.DeviceMachine(ev)
+        twos = None
+        try:
+            twos = capi.DeviceProfileTwos(dm, As, [B] * len(As), colTok=colTok, mergedEnvs=None if band is None else envs)
+            fwd = twos.forward(capi.MB_ROLLING) if loglike else None
+            if counts:
+                _, s, _ = twos.counts(acc._flat)
+                acc.loglike += s
+            vit = twos.viterbi(paths=False)[0] if viterbi else None
+            if posteriors:
+                pa, pb, _ = twos.merged_row_posteriors()
+                post = [(np.array(pa[twos.inOff[k]:twos.inOff[k + 1]]), np.array(pb[k * len(B):(k + 1) * len(B)])) for k in range(len(As))]
+        finally:
+            if twos is not None:
+                twos.close()
+            dm.close()
+
+    def floats(v):
+        return None if v is None else [float(x) for x in v]
+    scores = {"loglike": floats(fwd), "viterbi": floats(vit)}
+    if posteriors:
+        scores["posteriors"] = post
+    return scores, (acc.paramCounts(machine, params) if counts else None)
+
+
+def mergedTwoPosteriors(machine: Machine, inProfiles, outProfile, backend: str = "device", params=None, band: Optional[int] = None):
+    """Every input profile (a profile.Profile read against the machine's input alphabet, or its [K, nInTok + 1] log rows) as one
+    pair with ``outProfile`` read CTC-merged, as --recognize-merge-csv reads it (a profile.Profile, or a pair
+    (logB[L, nCols + 1], colTok) as Profile.mergeRows returns), all pairs in one batch: (posteriors, loglike), one
+    (postA[K, nInTok + 1], postB[L, nCols + 1]) and one float per input profile -- the posterior probability that each input row was
+    consumed as each input token and each output row as each column (column 0 of either: as its blank), the gradients of the pair's
+    log-likelihood in the two profiles (docs/profile_tapes.md, "Row posteriors of pairs of profiles against a merged profile").  A
+    pair that scores -inf gets zeros.  ``backend``: "device" (capi.DeviceProfileTwos.merged_row_posteriors) or "numpy"
+    (profile.TwoMergedProfileDP.mergedRowPosteriors).  ``band``: every pair is swept under seqpair.Envelope.band(K, L, band)
+    (docs/profile_tapes.md, "Pairs of profiles against a merged profile under an envelope")."""
+    import numpy as np
+    from .profile import TwoMergedProfileDP
+    from .seqpair import Envelope
+    if backend not in ("device", "numpy"):
+        raise MachineError('backend is "device" or "numpy"')
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    if not ev.nInTok:
+        raise MachineError("two-profile sweeps need a machine with an input alphabet")
+    if not ev.nOutTok:
+        raise MachineError("--recognize-merge-csv needs a machine with an output alphabet")
+    As = [a.logRowsIn(ev) if hasattr(a, "logRowsIn") else np.asarray(a, np.float64).reshape(-1, ev.nInTok + 1) for a in inProfiles]
+    B, colTok = _mergedRows(outProfile, ev) if hasattr(outProfile, "mergeRows") else outProfile
+    B = np.asarray(B, np.float64).reshape(-1, len(colTok) + 1)
+    envs = None if band is None else [Envelope.band(len(A), len(B), int(band)) for A in As]
+    if backend == "numpy":
+        tdp = TwoMergedProfileDP(ev, colTok)
+        res = [tdp.mergedRowPosteriors(A, B) for A in As] if envs is None else [tdp.mergedRowPosteriors(A, B, env=e) for A, e in zip(As, envs)]
         return [(r[0], r[1]) for r in res], [float(r[2]) for r in res]
     from . import capi
     dm = capi.DeviceMachine(ev)
     twos = None
     try:
-        twos = capi.DeviceProfileTwos(dm, As, [B] * len(As), colTok=colTok)
+        twos = capi.DeviceProfileTwos(dm, As, [B] * len(As), colTok=colTok, mergedEnvs=envs)
         pa, pb, ll = twos.merged_row_posteriors()
         post = [(np.array(pa[twos.inOff[k]:twos.inOff[k + 1]]), np.array(pb[k * len(B):(k + 1) * len(B)])) for k in range(len(As))]
     finally:

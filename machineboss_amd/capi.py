@@ -42,6 +42,7 @@ EXPORTS = [
     "mb_profile_twos_row_posteriors", "mb_profile_twos_set_rows",
     "mb_profile_two_fill",
     "mb_profile_twos_set_envelopes", "mb_profile_two_fill_env", "mb_profile_twos_cells",
+    "mb_profile_twos_set_envelopes_merged", "mb_profile_two_fill_merged_env",
     "mb_profile_twos_create_merged", "mb_profile_two_fill_merged", "mb_profile_twos_row_posteriors_merged",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
     "mb_prefix_node_cells", "mb_prefix_create_profiles", "mb_prefix_create_merged",
@@ -163,6 +164,8 @@ def load():
     L.mb_profile_two_fill.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, dp]
     L.mb_profile_twos_set_envelopes.argtypes = [vp, i64p, i32p, i32p]
     L.mb_profile_two_fill_env.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, i32p, i32p, dp]
+    L.mb_profile_twos_set_envelopes_merged.argtypes = [vp, i64p, i32p, i32p]
+    L.mb_profile_two_fill_merged_env.argtypes = [vp, C.c_int, dp, C.c_int64, dp, C.c_int64, C.c_int32, i32p, i32p, i32p, dp]
     L.mb_profile_twos_cells.argtypes = [vp]; L.mb_profile_twos_cells.restype = C.c_int64
     L.mb_profile_twos_create_merged.restype = vp
     L.mb_profile_twos_create_merged.argtypes = [vp, C.c_int64, dp, i64p, dp, i64p, C.c_int32, i32p]
@@ -915,10 +918,12 @@ class DeviceProfileTwos:
     under an envelope"); the yardstick is then TwoProfileDP(env=...).  With ``colTok`` the output profiles are CTC-merged
     (mb_profile_twos_create_merged): per pair a [rows, nCols + 1] array, column 0 the blank and column c a CSV column whose output
     token is colTok[c - 1] (profile.Profile.mergeRows); forward, viterbi, counts, cells and set_profiles work the same and the
-    yardstick is profile.TwoMergedProfileDP (docs/profile_tapes.md, "Pairs of profiles against a merged profile").  Envelopes and
-    row_posteriors take plain profiles; the row posteriors of a merged object are merged_row_posteriors."""
+    yardstick is profile.TwoMergedProfileDP (docs/profile_tapes.md, "Pairs of profiles against a merged profile").  ``envs``,
+    envelopes() and row_posteriors take plain profiles; the envelopes of a merged object are ``mergedEnvs`` / merged_envelopes()
+    (docs/profile_tapes.md, "Pairs of profiles against a merged profile under an envelope"; the yardstick is then
+    TwoMergedProfileDP with ``env``), its row posteriors merged_row_posteriors."""
 
-    def __init__(self, dm: DeviceMachine, inProfiles, outProfiles, envs=None, colTok=None):
+    def __init__(self, dm: DeviceMachine, inProfiles, outProfiles, envs=None, colTok=None, mergedEnvs=None):
         self.dm = dm
         self.colTok = None if colTok is None else np.ascontiguousarray(np.asarray(colTok).reshape(-1), np.int32)
         if self.colTok is not None and envs is not None:
@@ -947,6 +952,8 @@ class DeviceProfileTwos:
             raise MbError(L.mb_last_error().decode())
         if envs is not None:
             self.envelopes(envs)
+        if mergedEnvs is not None:
+            self.merged_envelopes(mergedEnvs)
 
     def envelopes(self, envs):
         """Replaces the envelopes.  envs: per pair None, a seqpair.Envelope or an (inStart, inEnd) pair of rows + 1 entries each --
@@ -954,6 +961,13 @@ class DeviceProfileTwos:
         If any pair has one, every pair runs the envelope kernels, a pair given None under the full envelope (the same bits as
         without).  A refused list (MbError) leaves the object without envelopes."""
         _set_envelopes(load().mb_profile_twos_set_envelopes, self.h, self.nPairs, envs)
+
+    def merged_envelopes(self, envs):
+        """envelopes() for an object created with ``colTok``: a cell outside is -inf in every plane of every layer, and the sweeps,
+        the counts and merged_row_posteriors visit the envelope cells alone (docs/profile_tapes.md, "Pairs of profiles against a
+        merged profile under an envelope").  As there, no call mixes geometries: a pair given None runs under the full envelope,
+        with the bits it has without.  A refused list (MbError) leaves the object without envelopes."""
+        _set_envelopes(load().mb_profile_twos_set_envelopes_merged, self.h, self.nPairs, envs)
 
     def cells(self) -> int:
         """Doubles of the materialised lattices of all pairs under the current envelopes."""
@@ -1063,15 +1077,23 @@ def profile_two_fill(dm: DeviceMachine, mode: int, logA, logB, env=None) -> np.n
     return cells
 
 
-def profile_two_fill_merged(dm: DeviceMachine, mode: int, logA, logB, colTok) -> np.ndarray:
+def profile_two_fill_merged(dm: DeviceMachine, mode: int, logA, logB, colTok, env=None) -> np.ndarray:
     """One pair's lattice against a merged output profile, [rows of A + 1, rows of B + 1, 3, nCols + 1, nStates] (layers as
-    profile_two_fill; plane 0 = the last row took the blank, plane c = it took column c)."""
+    profile_two_fill; plane 0 = the last row took the blank, plane c = it took column c).  ``env``: a seqpair.Envelope or
+    (inStart, inEnd); the cells outside it are -inf in all layers and planes."""
     ct = np.ascontiguousarray(np.asarray(colTok).reshape(-1), np.int32)
     A = np.ascontiguousarray(np.asarray(logA, np.float64).reshape(-1, dm.em.nInTok + 1))
     B = np.ascontiguousarray(np.asarray(logB, np.float64).reshape(-1, len(ct) + 1))
     cells = np.empty((len(A) + 1, len(B) + 1, 3, len(ct) + 1, dm.nStates), np.float64)
-    _check(load().mb_profile_two_fill_merged(dm.h, mode, _p(A, C.c_double), len(A), _p(B, C.c_double), len(B), len(ct),
-                                             _p(ct, C.c_int32), _p(cells, C.c_double)))
+    if env is None:
+        _check(load().mb_profile_two_fill_merged(dm.h, mode, _p(A, C.c_double), len(A), _p(B, C.c_double), len(B), len(ct),
+                                                 _p(ct, C.c_int32), _p(cells, C.c_double)))
+        return cells
+    a, b = _env_rows(env)
+    if len(a) != len(B) + 1:
+        raise MbError("Envelope/sequence mismatch")
+    _check(load().mb_profile_two_fill_merged_env(dm.h, mode, _p(A, C.c_double), len(A), _p(B, C.c_double), len(B), len(ct),
+                                                 _p(ct, C.c_int32), _p(a, C.c_int32), _p(b, C.c_int32), _p(cells, C.c_double)))
     return cells
 
 

@@ -1060,11 +1060,13 @@ static double pt_cell_bytes(const mb_profile_twos *p, long long k) { return 8.0 
 // The ring of pair k's sweep and its dynamic LDS (0: a slice of the global scratch buffer).  Plain profiles: the rolling sweep alone
 // has one.  Merged: the materialised sweeps keep their exclusion vectors in one too (mb_profile_two_merge.h).
 static long long pt_ring(const mb_profile_twos *p, long long k, bool rolling) {
+  if (p->nCols && p->hasEnv) return profile_two_merge_env_ring(p->m->S, p->nCols, p->envM[(size_t)k], !rolling);
   if (p->nCols) return profile_two_merge_ring(p->m->S, p->nCols, pt_in(p, k), pt_rows(p, k), !rolling);
   if (!rolling) return 0;
   return p->hasEnv ? profile_two_env_ring(p->m->S, p->envM[(size_t)k]) : profile_two_ring(p->m->S, pt_in(p, k), pt_rows(p, k));
 }
 static size_t pt_ring_lds(const mb_profile_twos *p, long long k, bool rolling) {
+  if (p->nCols && p->hasEnv) return profile_two_merge_env_lds_bytes(p->m->S, p->nCols, p->envM[(size_t)k], !rolling);
   if (p->nCols) return profile_two_merge_lds_bytes(p->m->S, p->nCols, pt_in(p, k), pt_rows(p, k), !rolling);
   if (!rolling) return 0;
   return p->hasEnv ? profile_two_env_lds_bytes(p->m->S, p->envM[(size_t)k]) : profile_two_lds_bytes(p->m->S, pt_in(p, k), pt_rows(p, k));
@@ -1103,7 +1105,7 @@ static int two_profile_descs(const mb_profile_twos *p, long long p0, long long p
     if (p->hasEnv) {
       d.envBase = p->envBase[(size_t)k]; d.diagBase = p->diagBase[(size_t)k]; d.colBase = p->colBase[(size_t)k];
       d.nCells = p->envCells[(size_t)k]; d.M = p->envM[(size_t)k];
-      pl.maxItems = std::max(pl.maxItems, (long long)d.M * S);
+      pl.maxItems = std::max(pl.maxItems, (long long)d.M * S * (p->nCols + 1));
       he.push_back(d);
     } else {
       pl.maxItems = std::max(pl.maxItems, (std::min(K, L) + 1) * S * (p->nCols + 1));
@@ -1129,17 +1131,20 @@ static TwoEnvTables pt_env_tables(const mb_profile_twos *p) {
 // The one place where the two geometries and the merged kernels part: the launches of a chunk of np pairs and the names they
 // report.  scratch: the chunk's rings that did not fit LDS (plain: the rolling sweep's alone).
 static int pt_fwd(const mb_profile_twos *p, int mode, bool mat, const TwoProfPlan &pl, long long np, double *pool, double *scratch, double *ll) {
+  if (p->nCols && p->hasEnv) return launch_profile_two_merge_fwd(p->m, pt_map(p), mode, mat, pl.e.p, pt_env_tables(p), (int)np, pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, scratch, ll, g_stream);
   if (p->nCols) return launch_profile_two_merge_fwd(p->m, pt_map(p), mode, mat, pl.d.p, (int)np, pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, scratch, ll, g_stream);
   if (p->hasEnv) return launch_profile_two_fwd(p->m, mode, mat, pl.e.p, pt_env_tables(p), (int)np, mat ? 0 : pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, mat ? nullptr : scratch, ll, g_stream);
   return launch_profile_two_fwd(p->m, mode, mat, pl.d.p, (int)np, mat ? 0 : pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, mat ? nullptr : scratch, ll, g_stream);
 }
 static int pt_fwd_mat(const mb_profile_twos *p, int mode, const TwoProfPlan &pl, long long np, double *pool, double *scratch, double *ll) { return pt_fwd(p, mode, true, pl, np, pool, scratch, ll); }
 static int pt_bwd(const mb_profile_twos *p, const TwoProfPlan &pl, long long np, double *pool, double *scratch, double *ll) {
+  if (p->nCols && p->hasEnv) return launch_profile_two_merge_bwd(p->m, pt_map(p), pl.e.p, pt_env_tables(p), (int)np, pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, scratch, ll, g_stream);
   if (p->nCols) return launch_profile_two_merge_bwd(p->m, pt_map(p), pl.d.p, (int)np, pl.lds, pl.maxItems, p->d_logA, p->d_logB, pool, scratch, ll, g_stream);
   if (p->hasEnv) return launch_profile_two_bwd(p->m, pl.e.p, pt_env_tables(p), (int)np, pl.maxItems, p->d_logA, p->d_logB, pool, ll, g_stream);
   return launch_profile_two_bwd(p->m, pl.d.p, (int)np, pl.maxItems, p->d_logA, p->d_logB, pool, ll, g_stream);
 }
 static int pt_counts(const mb_profile_twos *p, const TwoProfPlan &pl, long long np, int groups, const double *fwd, const double *bwd, double *cc) {
+  if (p->nCols && p->hasEnv) return launch_profile_two_merge_counts(p->m, pt_map(p), pl.e.p, pt_env_tables(p), (int)np, groups, p->d_logA, p->d_logB, fwd, bwd, cc, g_stream);
   if (p->nCols) return launch_profile_two_merge_counts(p->m, pt_map(p), pl.d.p, (int)np, groups, p->d_logA, p->d_logB, fwd, bwd, cc, g_stream);
   if (p->hasEnv) return launch_profile_two_counts(p->m, pl.e.p, pt_env_tables(p), (int)np, groups, p->d_logA, p->d_logB, fwd, bwd, cc, g_stream);
   return launch_profile_two_counts(p->m, pl.d.p, (int)np, groups, p->d_logA, p->d_logB, fwd, bwd, cc, g_stream);
@@ -1148,7 +1153,13 @@ static int pt_rowpost(const mb_profile_twos *p, int axis, const TwoProfPlan &pl,
   if (p->hasEnv) return launch_profile_two_rowpost(p->m, axis, pl.e.p, pt_env_tables(p), (int)np, groups, tabMax, p->d_logA, p->d_logB, fwd, bwd, post, g_stream);
   return launch_profile_two_rowpost(p->m, axis, pl.d.p, (int)np, groups, tabMax, p->d_logA, p->d_logB, fwd, bwd, post, g_stream);
 }
+// the merged row posteriors; ll: the chunk's Forward log-likelihoods
+static int pt_merge_rowpost(const mb_profile_twos *p, int axis, const TwoProfPlan &pl, long long np, int groups, int tabMax, const double *fwd, const double *bwd, const double *ll, double *post) {
+  if (p->hasEnv) return launch_profile_two_merge_rowpost(p->m, pt_map(p), axis, pl.e.p, pt_env_tables(p), (int)np, groups, tabMax, p->d_logA, p->d_logB, fwd, bwd, ll, post, g_stream);
+  return launch_profile_two_merge_rowpost(p->m, pt_map(p), axis, pl.d.p, (int)np, groups, tabMax, p->d_logA, p->d_logB, fwd, bwd, ll, post, g_stream);
+}
 static int pt_traceback(const mb_profile_twos *p, const TwoProfPlan &pl, long long np, const double *pool, uint32_t *e, int32_t *r, int32_t *i, long long *len) {
+  if (p->nCols && p->hasEnv) return launch_profile_two_merge_traceback(p->m, pt_map(p), pl.e.p, pt_env_tables(p), (int)np, p->d_logA, p->d_logB, pool, e, r, i, len, g_stream);
   if (p->nCols) return launch_profile_two_merge_traceback(p->m, pt_map(p), pl.d.p, (int)np, p->d_logA, p->d_logB, pool, e, r, i, len, g_stream);
   if (p->hasEnv) return launch_profile_two_traceback(p->m, pl.e.p, pt_env_tables(p), (int)np, p->d_logA, p->d_logB, pool, e, r, i, len, g_stream);
   return launch_profile_two_traceback(p->m, pl.d.p, (int)np, p->d_logA, p->d_logB, pool, e, r, i, len, g_stream);
@@ -1158,10 +1169,14 @@ static const char *pt_fwd_name(const mb_profile_twos *p, int mode, bool mat) {
   static const char *const names[2][2][2] = {{{"k_profile_two_fwd<sum,rolling>", "k_profile_two_fwd<sum,mat>"}, {"k_profile_two_fwd<max,rolling>", "k_profile_two_fwd<max,mat>"}},
                                              {{"k_profile_two_env_fwd<sum,rolling>", "k_profile_two_env_fwd<sum,mat>"}, {"k_profile_two_env_fwd<max,rolling>", "k_profile_two_env_fwd<max,mat>"}}};
   static const char *const merged[2][2] = {{"k_profile_two_merge_fwd<sum,rolling>", "k_profile_two_merge_fwd<sum,mat>"}, {"k_profile_two_merge_fwd<max,rolling>", "k_profile_two_merge_fwd<max,mat>"}};
-  if (p->nCols) return merged[mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
+  static const char *const mergedEnv[2][2] = {{"k_profile_two_merge_env_fwd<sum,rolling>", "k_profile_two_merge_env_fwd<sum,mat>"},
+                                              {"k_profile_two_merge_env_fwd<max,rolling>", "k_profile_two_merge_env_fwd<max,mat>"}};
+  if (p->nCols) return (p->hasEnv ? mergedEnv : merged)[mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
   return names[p->hasEnv ? 1 : 0][mode == MB_VITERBI ? 1 : 0][mat ? 1 : 0];
 }
-static const char *pt_name(const mb_profile_twos *p, const char *plain, const char *env, const char *merged) { return p->nCols ? merged : (p->hasEnv ? env : plain); }
+static const char *pt_name(const mb_profile_twos *p, const char *plain, const char *env, const char *merged, const char *mergedEnv) {
+  return p->nCols ? (p->hasEnv ? mergedEnv : merged) : (p->hasEnv ? env : plain);
+}
 
 // ---- envelopes of the two-profile pairs (mb_profile_two_env.h, docs/profile_tapes.md "Pairs of profiles under an envelope") ----
 static void pt_env_free(mb_profile_twos *p) {
@@ -1176,13 +1191,15 @@ static void pt_env_free(mb_profile_twos *p) {
 // The checks and the row tables are those of the pairs (env_add).  If any pair has an envelope every pair gets one, the full
 // envelope where none was given; then the transposed envelope: per input row i the run colStart[i] .. colEnd[i] - 1 of output rows
 // whose interval holds i (a run, because neither bound decreases) and colOff[i], the cells of the input rows before.  A rejected
-// call leaves the pairs without envelopes.
-static int profile_twos_set_envelopes(mb_profile_twos *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
+// call leaves the pairs without envelopes.  merged: the call came through the merged pairs' own entry; the merged kernels take the
+// same tables.
+static int profile_twos_set_envelopes(mb_profile_twos *p, bool merged, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
   pt_env_free(p);
+  if (merged && !p->nCols) { set_error("merged envelopes take merged profiles"); return 1; }
   if (!envOff) return 0;
   const long long total = envOff[p->n] - envOff[0];
   if (!total) return 0;
-  if (p->nCols) { set_error("envelopes take plain profiles"); return 1; }
+  if (p->nCols && !merged) { set_error("envelopes take plain profiles"); return 1; }
   if (!inStart || !inEnd) { set_error("null argument"); return 1; }
   EnvHost h(p->n);
   std::vector<long long> colBase((size_t)p->n, 0), cOff;
@@ -1195,6 +1212,7 @@ static int profile_twos_set_envelopes(mb_profile_twos *p, const int64_t *envOff,
       fullSt.assign((size_t)L + 1, 0); fullEn.assign((size_t)L + 1, (int)K + 1);
       if (env_add(h, k, K, L, L + 1, fullSt.data(), fullEn.data())) return 1;
     }
+    if ((double)h.M[(size_t)k] * p->m->S * (p->nCols + 1) > 2147483647.0) { set_error("pair " + std::to_string(k) + ": an anti-diagonal of the lattice has more than 2^31 cells"); return 1; }
     const int *st = h.st.data() + h.envBase[(size_t)k], *en = h.en.data() + h.envBase[(size_t)k];
     const size_t c0 = cSt.size();
     colBase[(size_t)k] = (long long)c0;
@@ -1311,7 +1329,13 @@ void mb_profile_twos_destroy(mb_profile_twos *p) {
 int mb_profile_twos_set_envelopes(mb_profile_twos *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
   ApiGuard guard;
   if (!p) { set_error("null argument"); return 1; }
-  return profile_twos_set_envelopes(p, envOff, inStart, inEnd);
+  return profile_twos_set_envelopes(p, false, envOff, inStart, inEnd);
+}
+
+int mb_profile_twos_set_envelopes_merged(mb_profile_twos *p, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
+  ApiGuard guard;
+  if (!p) { set_error("null argument"); return 1; }
+  return profile_twos_set_envelopes(p, true, envOff, inStart, inEnd);
 }
 
 int64_t mb_profile_twos_cells(const mb_profile_twos *p) {
@@ -1395,7 +1419,7 @@ int mb_profile_twos_counts(mb_profile_twos *p, double *counts, double *loglikeSu
   });
   std::vector<double> hll((size_t)p->n);
   if (!rc) rc = fetch_loglike(hll.data(), d_ll, p->n);
-  g_last_kernel = pt_name(p, "k_profile_two_counts", "k_profile_two_env_counts", "k_profile_two_merge_counts");
+  g_last_kernel = pt_name(p, "k_profile_two_counts", "k_profile_two_env_counts", "k_profile_two_merge_counts", "k_profile_two_merge_env_counts");
   if (rc) return rc;
   sum.finish(hll, counts, loglikeSum, loglike);
   return 0;
@@ -1470,15 +1494,15 @@ int mb_profile_twos_row_posteriors_merged(mb_profile_twos *p, double *postA, dou
     {
       Timed t(tm, 1);
       if (pt_fwd_mat(p, MB_FORWARD, pl, np, fwd, scratch, d_ll + c.p0) || pt_bwd(p, pl, np, bwd, scratch, d_bll + c.p0)) return 1;
-      if (postB && launch_profile_two_merge_rowpost(p->m, pt_map(p), 0, pl.d.p, (int)np, (int)groupsB, tabMax, p->d_logA, p->d_logB, fwd, bwd, d_ll + c.p0, d_pb, g_stream)) return 1;
-      if (postA && launch_profile_two_merge_rowpost(p->m, pt_map(p), 1, pl.d.p, (int)np, (int)groupsA, tabMax, p->d_logA, p->d_logB, fwd, bwd, d_ll + c.p0, d_pa, g_stream)) return 1;
+      if (postB && pt_merge_rowpost(p, 0, pl, np, (int)groupsB, tabMax, fwd, bwd, d_ll + c.p0, d_pb)) return 1;
+      if (postA && pt_merge_rowpost(p, 1, pl, np, (int)groupsA, tabMax, fwd, bwd, d_ll + c.p0, d_pa)) return 1;
     }
     return hip_ok(hipStreamSynchronize(g_stream), "row posteriors") ? 0 : 1;      // (the next chunk takes the lattices over)
   });
   if (!rc) rc = fetch_posteriors(postA, d_pa, na);
   if (!rc) rc = fetch_posteriors(postB, d_pb, nb);
   if (!rc && loglike) rc = fetch_loglike(loglike, d_ll, p->n);
-  g_last_kernel = "k_profile_two_merge_rowpost";
+  g_last_kernel = p->hasEnv ? "k_profile_two_merge_env_rowpost" : "k_profile_two_merge_rowpost";
   return rc;
 }
 
@@ -1502,7 +1526,7 @@ static int profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t
   const bool env = envStart && envEnd;
   if (env) {
     const int64_t eOff[2] = {0, nRows + 1};
-    if (profile_twos_set_envelopes(p, eOff, envStart, envEnd)) { mb_profile_twos_destroy(p); return 1; }
+    if (profile_twos_set_envelopes(p, nCols > 0, eOff, envStart, envEnd)) { mb_profile_twos_destroy(p); return 1; }
   }
   std::vector<Chunk> chunks;
   if (!lattice_chunks(1, "pair", [&](long long k) { return pt_cell_bytes(p, k) + pt_ring_bytes(p, k, false); }, chunks)) { mb_profile_twos_destroy(p); return 1; }
@@ -1515,7 +1539,7 @@ static int profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t
       return mode == MB_BACKWARD ? pt_bwd(p, pl, 1, pool, scratch, d_ll) : pt_fwd_mat(p, mode, pl, 1, pool, scratch, d_ll);
     });
     if (!rc && env) {      // the compact lattice into the full rectangle, -inf outside the envelope
-      const size_t cellD = 3 * (size_t)m->S;
+      const size_t cellD = 3 * (size_t)m->S * (size_t)(nCols + 1);
       std::fill(cellsOut, cellsOut + (size_t)(nIn + 1) * (size_t)(nRows + 1) * cellD, -INFINITY);
       size_t at = 0;
       for (int64_t r = 0; r <= nRows; ++r)
@@ -1523,7 +1547,7 @@ static int profile_two_fill(mb_machine *m, int mode, const double *logA, int64_t
           std::memcpy(cellsOut + ((size_t)i * (size_t)(nRows + 1) + (size_t)r) * cellD, compact.data() + at, cellD * sizeof(double));
     }
   }
-  g_last_kernel = mode == MB_BACKWARD ? pt_name(p, "k_profile_two_bwd", "k_profile_two_env_bwd", "k_profile_two_merge_bwd") : pt_fwd_name(p, mode, true);
+  g_last_kernel = mode == MB_BACKWARD ? pt_name(p, "k_profile_two_bwd", "k_profile_two_env_bwd", "k_profile_two_merge_bwd", "k_profile_two_merge_env_bwd") : pt_fwd_name(p, mode, true);
   mb_profile_twos_destroy(p);
   return rc;
 }
@@ -1545,6 +1569,14 @@ int mb_profile_two_fill_env(mb_machine *m, int mode, const double *logA, int64_t
   ApiGuard guard;
   if ((envStart == nullptr) != (envEnd == nullptr)) { set_error("null argument"); return 1; }
   return profile_two_fill(m, mode, logA, nIn, logB, nRows, 0, nullptr, envStart, envEnd, cellsOut);
+}
+
+int mb_profile_two_fill_merged_env(mb_machine *m, int mode, const double *logA, int64_t nIn, const double *logB, int64_t nRows, int32_t nCols,
+                                   const int32_t *colTok, const int32_t *envStart, const int32_t *envEnd, double *cellsOut) {
+  ApiGuard guard;
+  if (!merge_map_ok(m, nCols, colTok)) return 1;
+  if ((envStart == nullptr) != (envEnd == nullptr)) { set_error("null argument"); return 1; }
+  return profile_two_fill(m, mode, logA, nIn, logB, nRows, nCols, colTok, envStart, envEnd, cellsOut);
 }
 
 }  // extern "C"

@@ -9,9 +9,14 @@
 // plane 0 = "the last row took the blank, or no row yet", plane c = "the last row took column c".  PairProfDesc is shared with the
 // plain sweeps: rowBase counts rows of nCols + 1 doubles, cellBase doubles of this layout, ringBase the pair's slice of the global
 // scratch buffer (-1: its ring is in LDS).
+//
+// Under an ENVELOPE (mb_profile_two_env.h; docs/profile_tapes.md, "Pairs of profiles against a merged profile under an envelope")
+// cell (i, r) exists iff inStart[r] <= i < inEnd[r], in every plane of every layer; everything else is -inf.  Materialised lattices
+// are then COMPACT: cells[(((off[r] + i - inStart[r]) * 3 + layer) * (nCols + 1) + p) * S + q], off[r] = the cells of the rows < r.
+// The descriptor and the tables are those of the plain two-profile pairs under an envelope, TwoEnvDesc and TwoEnvTables.
 #pragma once
 #include "mb_profile_merge.h"
-#include "mb_profile_two.h"
+#include "mb_profile_two_env.h"
 
 namespace mb {
 
@@ -27,6 +32,12 @@ inline long long profile_two_merge_ring(int S, int nCols, long long nIn, long lo
 }
 // dynamic LDS of a pair's ring when it fits 160 KiB (0: a slice of the global scratch buffer)
 size_t profile_two_merge_lds_bytes(int S, int nCols, long long nIn, long long nRows, bool mat);
+// the same under an envelope: three anti-diagonals of M cells, M the largest cell count of a diagonal; a cell lives at i mod M
+// (the Backward's TZ and TW: the cell by its place on the diagonal, at most M places)
+inline long long profile_two_merge_env_ring(int S, int nCols, long long M, bool mat) {
+  return 3 * (mat ? 2LL * nCols : 5LL * nCols + 3) * M * (long long)S;
+}
+size_t profile_two_merge_env_lds_bytes(int S, int nCols, long long M, bool mat);
 
 // lds: the dynamic LDS of the launch (the largest ring among the pairs whose ringBase is -1); maxItems: the most (cell, plane,
 // state) items on one diagonal of the batch
@@ -46,6 +57,21 @@ int launch_profile_two_merge_rowpost(const mb_machine *m, MergeMap mm, int axis,
                                      const double *logA, const double *logB, const double *fwdPool, const double *bwdPool,
                                      const double *loglike, double *post, hipStream_t st);
 int launch_profile_two_merge_traceback(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, const double *logA,
+                                       const double *logB, const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows,
+                                       long long *len, hipStream_t st);
+
+// the launchers above over pairs under an envelope (lds, maxItems: of the envelope rings and diagonals)
+int launch_profile_two_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const TwoEnvDesc *d, const TwoEnvTables &t, int n, size_t lds,
+                                 long long maxItems, const double *logA, const double *logB, double *pool, double *scratch,
+                                 double *loglike, hipStream_t st);
+int launch_profile_two_merge_bwd(const mb_machine *m, MergeMap mm, const TwoEnvDesc *d, const TwoEnvTables &t, int n, size_t lds, long long maxItems,
+                                 const double *logA, const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st);
+int launch_profile_two_merge_counts(const mb_machine *m, MergeMap mm, const TwoEnvDesc *d, const TwoEnvTables &t, int n, int groupsPerPair, const double *logA,
+                                    const double *logB, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
+int launch_profile_two_merge_rowpost(const mb_machine *m, MergeMap mm, int axis, const TwoEnvDesc *d, const TwoEnvTables &t, int n, int groupsPerPair, int tabMax,
+                                     const double *logA, const double *logB, const double *fwdPool, const double *bwdPool,
+                                     const double *loglike, double *post, hipStream_t st);
+int launch_profile_two_merge_traceback(const mb_machine *m, MergeMap mm, const TwoEnvDesc *d, const TwoEnvTables &t, int n, const double *logA,
                                        const double *logB, const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows,
                                        long long *len, hipStream_t st);
 

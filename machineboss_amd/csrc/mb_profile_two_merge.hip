@@ -22,6 +22,11 @@
 // (K + L + 1)(nLevF + 1) barriers per pair.  The rolling sweeps keep a ring of three diagonals of N, W, Z, XW and XZ,
 // 3 (5 nCols + 3)(min(K, L) + 1) S doubles, in LDS when that fits 160 KiB, else in the pair's slice of a global scratch buffer; the
 // materialised ones keep only XW and XZ there.  Cells are fp64, the sums the exact log-sum-exp.
+//
+// Every kernel is written once over TwoMergeLattice, which says which cells exist and where they live: its full form, the whole
+// rectangle, or its envelope form, the cells of an envelope (docs/profile_tapes.md, "Pairs of profiles against a merged profile
+// under an envelope").  Every plane of all three layers of a cell outside the envelope is -inf, and so are its XW, XZ, TZ and TW,
+// so a neighbour outside is not read; the recurrence, the candidate order and the sums are the same text for both.
 #include "mb_profile_common.h"
 #include "mb_profile_two_merge.h"
 
@@ -32,13 +37,34 @@ size_t profile_two_merge_lds_bytes(int S, int nCols, long long nIn, long long nR
   return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
 }
 
-// Where cell (i, r) lives.  at(i, r, layer): its N (0), W (1) or Z (2), nCols + 1 planes of S states -- the materialised lattice, or
-// the ring (diagonal (i + r) mod 3, the cell by its coordinate on the short side of the lattice).  xw(i, r) / xz(i, r): its exclusion
-// vectors over W / over Z, column c at (c - 1) * S -- always in the ring, beside the three layers when rolling.
+size_t profile_two_merge_env_lds_bytes(int S, int nCols, long long M, bool mat) {
+  const double b = (double)profile_two_merge_env_ring(S, nCols, M, mat) * sizeof(double);
+  return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
+}
+
+struct NoTwoMergeTables {};      // what the full form needs beside a pair's descriptor
+
+// Where cell (i, r) lives and whether it exists.  at(i, r, layer): its N (0), W (1) or Z (2), nCols + 1 planes of S states -- the
+// materialised lattice, or the ring.  xw(i, r) / xz(i, r): its exclusion vectors over W / over Z, column c at (c - 1) * S -- always
+// in the ring, beside the three layers when rolling.  diag(d): the cells of anti-diagonal d, i = ilo .. ilo + nCells - 1.  cell: the
+// c-th cell of the pair as the counts enumerate them; lineFirst / lineCell: the cells counted line by line as the row posteriors
+// do (AXIS 0: output row r holds lineFirst(r) .. lineFirst(r + 1) - 1 by ascending i; AXIS 1: input row i by ascending r).
+template <bool MAT, bool ENV>
+struct TwoMergeLattice;
+
+// The whole rectangle: the lattice of mb_profile_two_merge.h; in the ring diagonal (i + r) mod 3, the cell by its coordinate on the
+// short side of the lattice.
 template <bool MAT>
-struct TwoMergeLattice {
+struct TwoMergeLattice<MAT, false> {
+  using Desc = PairProfDesc;
+  using Tables = NoTwoMergeTables;
   double *cells, *ring;
-  int S, PL, L, M, byI;
+  int S, PL, K, L, M, byI;
+  __device__ __forceinline__ TwoMergeLattice(const Desc &pd, Tables, double *cells, double *ring, int S, int PL)
+      : cells(cells), ring(ring), S(S), PL(PL), K(pd.nIn), L(pd.nRows), M(min(pd.nIn, pd.nRows) + 1), byI(pd.nIn <= pd.nRows) {}
+  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = max(0, d - L); nCells = min(K, d) - ilo + 1; }
+  // asked of neighbours the caller has already bounded to the rectangle
+  static constexpr __device__ __forceinline__ bool inside(int, int) { return true; }
   __device__ __forceinline__ long long slot(int i, int r) const { return (long long)((i + r) % 3) * M + (byI ? i : r); }
   __device__ __forceinline__ double *at(int i, int r, int layer) const {
     if (MAT) return cells + ((((long long)i * (L + 1)) + r) * 3 + layer) * PL * S;
@@ -49,27 +75,91 @@ struct TwoMergeLattice {
     return ring + (slot(i, r) * (5 * PL - 2) + 3 * PL) * S;
   }
   __device__ __forceinline__ double *xz(int i, int r) const { return xw(i, r) + (PL - 1) * S; }
+  __device__ __forceinline__ long long nCells() const { return (long long)(K + 1) * (L + 1); }
+  __device__ __forceinline__ void cell(long long c, int &i, int &r) const { i = (int)(c / (L + 1)); r = (int)(c - (long long)i * (L + 1)); }
+  // (over the rectangle both line orders are a division)
+  template <int AXIS> __device__ __forceinline__ long long lineFirst(int l) const { return (long long)l * ((AXIS ? L : K) + 1); }
+  template <int AXIS> __device__ __forceinline__ void lineCell(long long c, int &i, int &r) const {
+    const int per = (AXIS ? L : K) + 1, line = (int)(c / per), j = (int)(c - (long long)line * per);
+    i = AXIS ? line : j; r = AXIS ? j : line;
+  }
+};
+
+// The cells of an envelope (mb_profile_two_env.h): the compact lattice cells[(((off[r] + i - inStart[r]) * 3 + layer) * (nCols + 1)
+// + p) * S + q]; in the ring diagonal (i + r) mod 3, the cell at i mod M, M the largest cell count of a diagonal of the pair -- the
+// cells of a diagonal have consecutive i and number at most M, so no two share a slot.  A slot may hold a stale cell of another
+// row; it is never read, because inside() is asked first.
+template <bool MAT>
+struct TwoMergeLattice<MAT, true> {
+  using Desc = TwoEnvDesc;
+  using Tables = TwoEnvTables;
+  double *cells, *ring;
+  const int *st, *en;         // the pair's envelope rows
+  const long long *off;       // compact index of the first cell of each row
+  const int *dLo, *dCnt;
+  const int *cSt;             // the transposed envelope: first output row of each input row, and
+  const long long *cOff;      // the cells of the input rows before it
+  long long nEnv;
+  int S, PL, K, L, M;
+  __device__ __forceinline__ TwoMergeLattice(const Desc &pd, const Tables &t, double *cells, double *ring, int S, int PL)
+      : cells(cells), ring(ring), st(t.envStart + pd.envBase), en(t.envEnd + pd.envBase), off(t.envOff + pd.envBase),
+        dLo(t.diagLo + pd.diagBase), dCnt(t.diagCnt + pd.diagBase), cSt(t.colStart + pd.colBase), cOff(t.colOff + pd.colBase),
+        nEnv(pd.nCells), S(S), PL(PL), K(pd.nIn), L(pd.nRows), M(pd.M) {}
+  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = dLo[d]; nCells = dCnt[d]; }
+  // r in -1..L+1, i in -1..K+1
+  __device__ __forceinline__ bool inside(int i, int r) const { return r >= 0 && r <= L && i >= st[r] && i < en[r]; }
+  __device__ __forceinline__ long long slot(int i, int r) const { return (long long)((i + r) % 3) * M + (i % M); }
+  // (MAT: r in 0..L; the address of a cell outside is formed in places, and read nowhere)
+  __device__ __forceinline__ double *at(int i, int r, int layer) const {
+    if (MAT) return cells + ((off[r] + (i - st[r])) * 3 + layer) * PL * S;
+    return ring + (slot(i, r) * (5 * PL - 2) + layer * PL) * S;
+  }
+  __device__ __forceinline__ double *xw(int i, int r) const {
+    if (MAT) return ring + slot(i, r) * 2 * (PL - 1) * S;
+    return ring + (slot(i, r) * (5 * PL - 2) + 3 * PL) * S;
+  }
+  __device__ __forceinline__ double *xz(int i, int r) const { return xw(i, r) + (PL - 1) * S; }
+  __device__ __forceinline__ long long nCells() const { return nEnv; }
+  // the last entry of o[0..n] that is <= c: the lines behind it start past the cell
+  static __device__ __forceinline__ int lastLE(const long long *o, int n, long long c) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (o[mid] <= c) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+  }
+  __device__ __forceinline__ void cell(long long c, int &i, int &r) const { r = lastLE(off, L, c); i = st[r] + (int)(c - off[r]); }
+  // (AXIS 0: the compact index already counts row by row, l <= L; AXIS 1: column by column through the transposed envelope, l <= K)
+  template <int AXIS> __device__ __forceinline__ long long lineFirst(int l) const { return AXIS ? cOff[l] : off[l]; }
+  template <int AXIS> __device__ __forceinline__ void lineCell(long long c, int &i, int &r) const {
+    if (AXIS) { i = lastLE(cOff, K, c); r = cSt[i] + (int)(c - cOff[i]); }
+    else cell(c, i, r);
+  }
 };
 
 // Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every N, W and Z cell into pool (layout of
 // mb_profile_two_merge.h) and only XW, XZ in the ring, else rolling.  Viterbi keeps the FIRST maximum: N[.][.][0] takes the planes
 // ascending; N[.][.][c] the repeat first, then the match edges in `incoming` order (input token ascending), then the output-only
 // edges; W takes N (no move) first, then the input-only edges, then the silent edges; Z takes W, then the input blank; XW, XZ and the
-// end the planes ascending -- the order k_profile_two_merge_traceback re-enumerates.
-template <int MODE, bool MAT>
-__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_fwd(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+// end the planes ascending -- the order k_profile_two_merge_traceback re-enumerates.  A neighbour outside the lattice is -inf and
+// is not read: (i, r - 1) feeds the output blank over all planes, the repeat and XW of the output-only edges, (i - 1, r - 1) XZ of
+// the match edges, (i - 1, r) Z of the input-only edges and of the input blank.
+template <int MODE, bool MAT, bool ENV>
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_fwd(DevMachine m, MergeMap mm, const typename TwoMergeLattice<MAT, ENV>::Desc *__restrict__ descs,
+                                                                         typename TwoMergeLattice<MAT, ENV>::Tables t,
                                                                          const double *__restrict__ logA, const double *__restrict__ logB,
                                                                          double *pool, double *scratch, double *__restrict__ loglike) {
   extern __shared__ double ptm_sh[];
-  const PairProfDesc pd = descs[blockIdx.x];
+  const auto pd = descs[blockIdx.x];
   const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, nC = mm.nCols, PL = nC + 1, K = pd.nIn, L = pd.nRows;
   const double *A = logA + pd.inBase * CA;
   const double *B = logB + pd.rowBase * PL;
-  const TwoMergeLattice<MAT> lat{MAT ? pool + pd.cellBase : nullptr, pd.ringBase < 0 ? ptm_sh : scratch + pd.ringBase, S, PL, L,
-                                 min(K, L) + 1, K <= L};
+  const TwoMergeLattice<MAT, ENV> lat(pd, t, MAT ? pool + pd.cellBase : nullptr, pd.ringBase < 0 ? ptm_sh : scratch + pd.ringBase, S, PL);
   const int PS = PL * S;
   for (int d = 0; d <= K + L; ++d) {
-    const int ilo = max(0, d - L), nCells = min(K, d) - ilo + 1;
+    int ilo, nCells;
+    lat.diag(d, ilo, nCells);
     const int nItems = nCells * PS;
     for (int it = threadIdx.x; it < nItems; it += blockDim.x) {
       const int c = it / PS, pq = it - c * PS, p = pq / S, q = pq - p * S, i = ilo + c, r = d - i;
@@ -77,14 +167,17 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_fwd(DevMach
       double acc = (d == 0 && pq == 0) ? 0.0 : -INFINITY;
       if (r > 0) {
         const double w = B[(long long)(r - 1) * PL + p];
-        const double *Np = lat.at(i, r - 1, 0);
+        const bool up = lat.inside(i, r - 1);
+        const double *Np = lat.at(i, r - 1, 0);      // (an address alone: read only where the cell is inside)
         if (p == 0) {
-          acc = Np[q] + w;
-          for (int k = 1; k < PL; ++k) acc = red<MODE>(acc, Np[k * S + q] + w);
+          if (up) {
+            acc = Np[q] + w;
+            for (int k = 1; k < PL; ++k) acc = red<MODE>(acc, Np[k * S + q] + w);
+          }
         } else if (w > -INFINITY) {                          // (a column the row rules out is skipped as a whole)
           const int tok = mm.colTok[p - 1];
-          acc = Np[p * S + q] + w;
-          if (i > 0) {
+          if (up) acc = Np[p * S + q] + w;
+          if (i > 0 && lat.inside(i - 1, r - 1)) {
             const double *Xd = lat.xz(i - 1, r - 1) + (p - 1) * S;
             for (int a = 1; a <= m.nIn; ++a) {
               const int row = q * KK + a * C + tok;
@@ -93,13 +186,15 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_fwd(DevMach
               for (int e = m.inOff[row]; e < e1; ++e) acc = red<MODE>(acc, ((Xd[m.inSrc[e]] + m.inW[e]) + wa) + w);
             }
           }
-          const double *Xu = lat.xw(i, r - 1) + (p - 1) * S;
-          const int e1 = m.inOff[q * KK + tok + 1];
-          for (int e = m.inOff[q * KK + tok]; e < e1; ++e) acc = red<MODE>(acc, (Xu[m.inSrc[e]] + m.inW[e]) + w);
+          if (up) {
+            const double *Xu = lat.xw(i, r - 1) + (p - 1) * S;
+            const int e1 = m.inOff[q * KK + tok + 1];
+            for (int e = m.inOff[q * KK + tok]; e < e1; ++e) acc = red<MODE>(acc, (Xu[m.inSrc[e]] + m.inW[e]) + w);
+          }
         }
       }
       lat.at(i, r, 0)[pq] = acc;
-      if (i > 0) {
+      if (i > 0 && lat.inside(i - 1, r)) {
         const double *Zl = lat.at(i - 1, r, 2) + p * S;
         for (int a = 1; a <= m.nIn; ++a) {
           const int row = q * KK + a * C;
@@ -129,7 +224,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_fwd(DevMach
           acc = red<MODE>(acc, Wc[s] + m.inW[e]);
         }
         Wc[q] = acc;
-        lat.at(i, r, 2)[p * S + q] = i > 0 ? red<MODE>(acc, lat.at(i - 1, r, 2)[p * S + q] + A[(long long)(i - 1) * CA]) : acc;
+        lat.at(i, r, 2)[p * S + q] = (i > 0 && lat.inside(i - 1, r)) ? red<MODE>(acc, lat.at(i - 1, r, 2)[p * S + q] + A[(long long)(i - 1) * CA]) : acc;
       }
       __syncthreads();
     }
@@ -148,7 +243,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_fwd(DevMach
     }
   }
   if (threadIdx.x == 0) {
-    const double *Ze = lat.at(K, L, 2) + S - 1;
+    const double *Ze = lat.at(K, L, 2) + S - 1;      // (an envelope is connected: (0, 0) and (K, L) are inside)
     double acc = Ze[0];
     for (int p = 1; p < PL; ++p) acc = red<MODE>(acc, Ze[p * S]);
     loglike[blockIdx.x] = acc;
@@ -167,20 +262,25 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_fwd(DevMach
 // Anti-diagonals from K + L down.  TZ and TW, everything that leaves (i, r, s) through column c from the committed and from the
 // waiting stage, are formed once per diagonal over (cell, column, state) -- the mirror of the Forward's XZ and XW -- so the edge
 // loops do not run over planes; they live in the ring (one diagonal of them, the cell by its place on the diagonal, TZ then TW).  A
-// state's WB is final once its backward level has run; the item that finishes it writes its NB.
-__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_bwd(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+// state's WB is final once its backward level has run; the item that finishes it writes its NB.  A successor cell outside the
+// lattice contributes nothing: (i + 1, r + 1) is asked before TZ reads it, (i, r + 1) before TW, the output blank and the repeat do,
+// (i + 1, r) before the input blank and the input-only edges do.
+template <bool ENV>
+__global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_bwd(DevMachine m, MergeMap mm, const typename TwoMergeLattice<true, ENV>::Desc *__restrict__ descs,
+                                                                         typename TwoMergeLattice<true, ENV>::Tables t,
                                                                          const double *__restrict__ logA, const double *__restrict__ logB,
                                                                          double *pool, double *scratch, double *__restrict__ loglike) {
   extern __shared__ double ptm_sh[];
-  const PairProfDesc pd = descs[blockIdx.x];
+  const auto pd = descs[blockIdx.x];
   const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, nC = mm.nCols, PL = nC + 1, K = pd.nIn, L = pd.nRows;
   const double *A = logA + pd.inBase * CA;
   const double *B = logB + pd.rowBase * PL;
-  const TwoMergeLattice<true> lat{pool + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  const TwoMergeLattice<true, ENV> lat(pd, t, pool + pd.cellBase, nullptr, S, PL);
   double *T = pd.ringBase < 0 ? ptm_sh : scratch + pd.ringBase;       // T[((cell on the diagonal * 2 + (0: TZ, 1: TW)) * nCols + c - 1) * S + s]
   const int PS = PL * S, XS = nC * S;
   for (int d = K + L; d >= 0; --d) {
-    const int ilo = max(0, d - L), nCells = min(K, d) - ilo + 1;
+    int ilo, nCells;
+    lat.diag(d, ilo, nCells);
     if (d < K + L) {
       const int nTItems = nCells * XS;
       for (int it = threadIdx.x; it < nTItems; it += blockDim.x) {
@@ -190,7 +290,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_bwd(DevMach
           const double pc = B[(long long)r * PL + col];
           if (pc > -INFINITY) {
             const int tok = mm.colTok[col - 1];
-            if (i < K) {
+            if (i < K && lat.inside(i + 1, r + 1)) {
               const double *Nd = lat.at(i + 1, r + 1, 0) + col * S;
               const double *Ai = A + (long long)i * CA;
               for (int a = 1; a <= m.nIn; ++a) {
@@ -200,9 +300,11 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_bwd(DevMach
                 for (int e = m.outOff[row]; e < e1; ++e) tz = lse2_exact(tz, ((m.outW[e] + wa) + pc) + Nd[m.outDst[e]]);
               }
             }
-            const double *Nu = lat.at(i, r + 1, 0) + col * S;
-            const int e1 = m.outOff[s * KK + tok + 1];
-            for (int e = m.outOff[s * KK + tok]; e < e1; ++e) tw = lse2_exact(tw, (m.outW[e] + pc) + Nu[m.outDst[e]]);
+            if (lat.inside(i, r + 1)) {
+              const double *Nu = lat.at(i, r + 1, 0) + col * S;
+              const int e1 = m.outOff[s * KK + tok + 1];
+              for (int e = m.outOff[s * KK + tok]; e < e1; ++e) tw = lse2_exact(tw, (m.outW[e] + pc) + Nu[m.outDst[e]]);
+            }
           }
         }
         T[(long long)c * 2 * XS + cs] = tz;
@@ -217,16 +319,19 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_bwd(DevMach
       double v = (d == K + L && s == S - 1) ? 0.0 : -INFINITY;
       if (i < K) {
         const double *Ai = A + (long long)i * CA;
-        v = lse2_exact(v, Ai[0] + lat.at(i + 1, r, 2)[ks]);
-        if (r < L)
+        const bool right = lat.inside(i + 1, r);
+        if (right) v = lse2_exact(v, Ai[0] + lat.at(i + 1, r, 2)[ks]);
+        if (r < L)      // (TZ of a target outside is -inf)
           for (int col = 1; col < PL; ++col)
             if (col != k) v = lse2_exact(v, Tc[(col - 1) * S]);
-        const double *Wl = lat.at(i + 1, r, 1) + k * S;
-        for (int a = 1; a <= m.nIn; ++a) {
-          const int row = s * KK + a * C;
-          const double wa = Ai[a];
-          const int e1 = m.outOff[row + 1];
-          for (int e = m.outOff[row]; e < e1; ++e) v = lse2_exact(v, (m.outW[e] + wa) + Wl[m.outDst[e]]);
+        if (right) {
+          const double *Wl = lat.at(i + 1, r, 1) + k * S;
+          for (int a = 1; a <= m.nIn; ++a) {
+            const int row = s * KK + a * C;
+            const double wa = Ai[a];
+            const int e1 = m.outOff[row + 1];
+            for (int e = m.outOff[row]; e < e1; ++e) v = lse2_exact(v, (m.outW[e] + wa) + Wl[m.outDst[e]]);
+          }
         }
       }
       lat.at(i, r, 2)[ks] = v;
@@ -234,7 +339,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_bwd(DevMach
         for (int col = 1; col < PL; ++col)
           if (col != k) v = lse2_exact(v, Tc[XS + (col - 1) * S]);
       lat.at(i, r, 1)[ks] = v;
-      if (r < L) {
+      if (r < L && lat.inside(i, r + 1)) {
         const double *Nn = lat.at(i, r + 1, 0), *Br = B + (long long)r * PL;
         v = lse2_exact(v, Br[0] + Nn[s]);
         if (k) v = lse2_exact(v, Br[k] + Nn[ks]);
@@ -256,7 +361,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_bwd(DevMach
           v = lse2_exact(v, Wc[t] + m.outW[e]);
         }
         Wc[s] = v;
-        if (r < L) {
+        if (r < L && lat.inside(i, r + 1)) {
           const double *Nn = lat.at(i, r + 1, 0), *Br = B + (long long)r * PL;
           v = lse2_exact(v, Br[0] + Nn[s]);
           if (k) v = lse2_exact(v, Br[k] + Nn[k * S + s]);
@@ -273,8 +378,12 @@ __global__ __launch_bounds__(SWEEP_THREADS) void k_profile_two_merge_bwd(DevMach
 //   count[t] += exp(F[i][r][k][s] - LL + term_t), term_t the edge's summand of ZB (read from Z_F: the input-reading edges) or of WB
 //   (read from W_F: the others) above, through TZ / TW for the emitting edges: every column c != k,
 // so the sweep is a flat grid over (pair, group of the pair, (cell, plane, state)), accumulated by CountsAcc (mb_profile_common.h).
-// A pair whose likelihood is -inf adds nothing; the blanks of either tape and the repeat rows are not edges.
-__global__ __launch_bounds__(256) void k_profile_two_merge_counts(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
+// A pair whose likelihood is -inf adds nothing; the blanks of either tape and the repeat rows are not edges.  The cells of an
+// envelope are counted through its compact index (a cell finds its row by bisection in off); a term whose destination lies outside
+// is left out.
+template <bool ENV>
+__global__ __launch_bounds__(256) void k_profile_two_merge_counts(DevMachine m, MergeMap mm, const typename TwoMergeLattice<true, ENV>::Desc *__restrict__ descs,
+                                                                  typename TwoMergeLattice<true, ENV>::Tables t,
                                                                   int groupsPerPair, const double *__restrict__ logA,
                                                                   const double *__restrict__ logB, const double *__restrict__ fwdPool,
                                                                   const double *__restrict__ bwdPool, long long nTrans,
@@ -282,12 +391,12 @@ __global__ __launch_bounds__(256) void k_profile_two_merge_counts(DevMachine m, 
   __shared__ double lcount[COUNTS_LDS_MAX];
   const CountsAcc acc(lcount, counts, nTrans, det);
   const int pair = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
-  const PairProfDesc pd = descs[pair];
+  const auto pd = descs[pair];
   const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, nC = mm.nCols, PL = nC + 1, K = pd.nIn, L = pd.nRows;
   const double *A = logA + pd.inBase * CA;
   const double *B = logB + pd.rowBase * PL;
-  const TwoMergeLattice<true> F{const_cast<double *>(fwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0},
-      Bk{const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  const TwoMergeLattice<true, ENV> F(pd, t, const_cast<double *>(fwdPool) + pd.cellBase, nullptr, S, PL),
+      Bk(pd, t, const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL);
   double LL;
   {
     const double *Ze = F.at(K, L, 2) + S - 1;
@@ -295,20 +404,23 @@ __global__ __launch_bounds__(256) void k_profile_two_merge_counts(DevMachine m, 
     for (int p = 1; p < PL; ++p) LL = lse2_exact(LL, Ze[p * S]);
   }
   if (LL > -INFINITY) {
-    const long long PS = (long long)PL * S, nItems = (long long)(K + 1) * (L + 1) * PS;
+    const long long PS = (long long)PL * S, nItems = F.nCells() * PS;
     for (long long idx = (long long)group * blockDim.x + threadIdx.x; idx < nItems; idx += (long long)groupsPerPair * blockDim.x) {
       const long long cell = idx / PS;
-      const int ks = (int)(idx - cell * PS), k = ks / S, s = ks - k * S, i = (int)(cell / (L + 1)), r = (int)(cell - (long long)i * (L + 1));
+      const int ks = (int)(idx - cell * PS), k = ks / S, s = ks - k * S;
+      int i, r;
+      F.cell(cell, i, r);
       const double f = F.at(i, r, 1)[ks] - LL, z = F.at(i, r, 2)[ks] - LL;
       if (!(z > -INFINITY)) continue;                 // (Z holds W: a dead Z is a dead W)
       const double *Br = B + (long long)r * PL;       // read when r < L
       if (i < K) {
         const double *Ai = A + (long long)i * CA;
-        const double *Wl = Bk.at(i + 1, r, 1) + k * S;
+        const bool right = Bk.inside(i + 1, r), across = r < L && Bk.inside(i + 1, r + 1);
+        const double *Wl = Bk.at(i + 1, r, 1) + k * S;      // (an address alone: read only where the cell is inside)
         for (int a = 1; a <= m.nIn; ++a) {
           const int row = s * KK + a * C;
           const double wa = Ai[a];
-          if (r < L) {
+          if (across) {
             const double *Nd = Bk.at(i + 1, r + 1, 0);
             for (int col = 1; col < PL; ++col) {
               const double pc = Br[col];
@@ -319,12 +431,14 @@ __global__ __launch_bounds__(256) void k_profile_two_merge_counts(DevMachine m, 
                 acc.add(m.outEid[e], exp(z + (((m.outW[e] + wa) + pc) + Nd[col * S + m.outDst[e]])));
             }
           }
-          const int e1 = m.outOff[row + 1];
-          for (int e = m.outOff[row]; e < e1; ++e) acc.add(m.outEid[e], exp(z + ((m.outW[e] + wa) + Wl[m.outDst[e]])));
+          if (right) {
+            const int e1 = m.outOff[row + 1];
+            for (int e = m.outOff[row]; e < e1; ++e) acc.add(m.outEid[e], exp(z + ((m.outW[e] + wa) + Wl[m.outDst[e]])));
+          }
         }
       }
       if (!(f > -INFINITY)) continue;
-      if (r < L) {
+      if (r < L && Bk.inside(i, r + 1)) {
         const double *Nu = Bk.at(i, r + 1, 0);
         for (int col = 1; col < PL; ++col) {
           const double pc = Br[col];
@@ -365,25 +479,29 @@ __global__ __launch_bounds__(256) void k_profile_two_merge_counts(DevMachine m, 
 // global atomic and nothing to clear beforehand.  A line of more than tabMax columns is summed in its global bins instead, cleared
 // by the workgroup that owns it.  A pair whose likelihood is -inf gets zeros by the same stores.  loglike: the Forward sweep's, per
 // pair of the launch.  det: post holds 64-bit fixed point at 2^-36.
-template <int AXIS>
-__global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_merge_rowpost(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs,
-                                                                               int groupsPerPair, const double *__restrict__ logA,
+// Under an envelope the lines are those of the lattice (lineFirst / lineCell): on axis 0 the compact index already counts row by row;
+// on axis 1 the lines are COLUMNS of the envelope -- by monotonicity the cells of input row i are the run r = colStart[i] ..
+// colEnd[i] - 1, an item finds its column by bisection in colOff and its cell through at().  A term whose destination lies outside
+// is left out, the match terms to (i + 1, r + 1) independently of the input-only and input-blank terms to (i + 1, r).
+template <int AXIS, bool ENV>
+__global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_merge_rowpost(DevMachine m, MergeMap mm, const typename TwoMergeLattice<true, ENV>::Desc *__restrict__ descs,
+                                                                               typename TwoMergeLattice<true, ENV>::Tables t, int groupsPerPair, const double *__restrict__ logA,
                                                                                const double *__restrict__ logB, const double *__restrict__ fwdPool,
                                                                                const double *__restrict__ bwdPool, const double *__restrict__ loglike,
                                                                                double *post, int tabMax, int det) {
   __shared__ double ltab[ROWPOST_LDS_MAX];
   const int pair = blockIdx.x / groupsPerPair, group = blockIdx.x % groupsPerPair;
-  const PairProfDesc pd = descs[pair];
+  const auto pd = descs[pair];
   const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, nC = mm.nCols, PL = nC + 1, K = pd.nIn, L = pd.nRows;
-  const int NL = AXIS ? K : L, NC = AXIS ? CA : PL, NX = AXIS ? L + 1 : K + 1;      // lines, bins of a line, cells of a line
+  const int NL = AXIS ? K : L, NC = AXIS ? CA : PL;      // lines, bins of a line
   if (NL == 0) return;
   const double *A = logA + pd.inBase * CA;
   const double *B = logB + pd.rowBase * PL;
-  const TwoMergeLattice<true> F{const_cast<double *>(fwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0},
-      Bk{const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  const TwoMergeLattice<true, ENV> F(pd, t, const_cast<double *>(fwdPool) + pd.cellBase, nullptr, S, PL),
+      Bk(pd, t, const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL);
   const double LL = loglike[pair];
-  const long long PS = (long long)PL * S, lineItems = NX * PS;
-  const int R = profile_pair_rowpost_rows((long long)(K + 1) * (L + 1) * PL, S, NL, NC, tabMax);
+  const long long PS = (long long)PL * S;
+  const int R = profile_pair_rowpost_rows(F.nCells() * PL, S, NL, NC, tabMax);
   const bool useLds = NC <= tabMax;
   const int lane = threadIdx.x & 63;
   for (long long lb = (long long)group * R; lb < NL; lb += (long long)groupsPerPair * R) {
@@ -394,24 +512,23 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_merge_rowpost(D
     if (!useLds) __threadfence();
     __syncthreads();
     if (LL > -INFINITY) {
-      const long long nItems = (l1 - l0) * lineItems;
+      const long long c0 = F.template lineFirst<AXIS>(l0), nItems = (F.template lineFirst<AXIS>(l1) - c0) * PS;
       for (long long base = threadIdx.x - lane; base < nItems; base += blockDim.x) {      // (a wavefront stays whole in here)
         const long long idx = base + lane;
         const bool valid = idx < nItems;
-        int line = l0, x = 0, k = 0, s = 0, ks = 0;
+        int i = AXIS ? l0 : 0, r = AXIS ? 0 : l0, k = 0, s = 0, ks = 0;
         if (valid) {
-          const long long ln = idx / lineItems, rem = idx - ln * lineItems;
-          line = l0 + (int)ln;
-          x = (int)(rem / PS);
-          ks = (int)(rem - x * PS);
+          const long long cell = idx / PS;
+          ks = (int)(idx - cell * PS);
           k = ks / S;
           s = ks - k * S;
+          F.template lineCell<AXIS>(c0 + cell, i, r);
         }
-        const int i = AXIS ? line : x, r = AXIS ? x : line;
+        const int line = AXIS ? i : r;
         const double z = valid ? F.at(i, r, 2)[ks] - LL : -INFINITY;
         const bool whole = __all(valid && line == __shfl(line, 0));
         // (the line's own coordinate is inside: r < L on axis 0, i < K on axis 1)
-        const bool diag = valid && i < K && r < L;
+        const bool diag = valid && i < K && r < L && Bk.inside(i + 1, r + 1);
         const double *Ai = A + (long long)i * CA;        // read when i < K
         const double *Br = B + (long long)r * PL;        // read when r < L
         const double *Nd = diag ? Bk.at(i + 1, r + 1, 0) : nullptr;
@@ -419,8 +536,9 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_merge_rowpost(D
         const bool zLive = z > -INFINITY;
         if (AXIS == 0) {
           const double f = valid ? F.at(i, r, 1)[ks] - LL : -INFINITY, n = valid ? F.at(i, r, 0)[ks] - LL : -INFINITY;
-          const double *Nu = Bk.at(i, r + 1, 0);         // (an address alone where the item is not valid: read only where f or n lives)
-          const bool nLive = n > -INFINITY, fLive = f > -INFINITY, dLive = diag && zLive;
+          const bool up = Bk.inside(i, r + 1);
+          const double *Nu = Bk.at(i, r + 1, 0);         // (an address alone where the item is not valid or the cell outside: read only where f or n lives)
+          const bool nLive = up && n > -INFINITY, fLive = up && f > -INFINITY, dLive = diag && zLive;
           rowpost_add(tab, bin0, nLive ? exp(n + (Br[0] + Nu[s])) : 0.0, whole, lane, det);
           for (int c = 1; c < PL; ++c) {      // the out-edges of (s, a) that write the column's token are one CSR row
             double v = 0.0;
@@ -449,15 +567,18 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_merge_rowpost(D
             rowpost_add(tab, bin0 + c, v, whole, lane, det);
           }
         } else {
-          const double *Zl = Bk.at(i + 1, r, 2), *Wl = Bk.at(i + 1, r, 1) + (long long)k * S;      // (i < K: the cell is inside)
-          rowpost_add(tab, bin0, zLive ? exp(z + (Ai[0] + Zl[ks])) : 0.0, whole, lane, det);
+          const bool right = Bk.inside(i + 1, r);      // (i < K: the cell is inside the rectangle)
+          const double *Zl = Bk.at(i + 1, r, 2), *Wl = Bk.at(i + 1, r, 1) + (long long)k * S;
+          rowpost_add(tab, bin0, (right && zLive) ? exp(z + (Ai[0] + Zl[ks])) : 0.0, whole, lane, det);
           for (int a = 1; a < CA; ++a) {      // the out-edges of s that read a: the input-only row, then the rows of the columns' tokens
             double v = 0.0;
             if (zLive) {
               const int row = sRow + a * C;
               const double wa = Ai[a];
-              const int e1 = m.outOff[row + 1];
-              for (int e = m.outOff[row]; e < e1; ++e) v += exp(z + ((m.outW[e] + wa) + Wl[m.outDst[e]]));
+              if (right) {
+                const int e1 = m.outOff[row + 1];
+                for (int e = m.outOff[row]; e < e1; ++e) v += exp(z + ((m.outW[e] + wa) + Wl[m.outDst[e]]));
+              }
               if (diag)
                 for (int c = 1; c < PL; ++c) {
                   const double pc = Br[c];
@@ -486,17 +607,20 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_merge_rowpost(D
 // an emitting edge comes from the lowest plane k != c whose Z (match) or W (output-only) equals the edge's XZ / XW.  Blanks of
 // either tape and repeat rows are not edges.  Edges go start -> end into the pair's slot (profile_pair_path_bound entries) with
 // both coordinates at which each fired, as k_profile_two_traceback.  len = -1: no finite path, -2: the slot was too small, -3: no
-// candidate matched (a corrupt matrix).
-__global__ void k_profile_two_merge_traceback(DevMachine m, MergeMap mm, const PairProfDesc *__restrict__ descs, int n,
+// candidate matched (a corrupt matrix).  A candidate whose source cell lies outside the lattice is left out: it is -inf, and the
+// cells on the path are finite.
+template <bool ENV>
+__global__ void k_profile_two_merge_traceback(DevMachine m, MergeMap mm, const typename TwoMergeLattice<true, ENV>::Desc *__restrict__ descs,
+                                              typename TwoMergeLattice<true, ENV>::Tables t, int n,
                                               const double *__restrict__ logA, const double *__restrict__ logB,
                                               const double *__restrict__ pool, uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len) {
   const int pair = blockIdx.x * blockDim.x + threadIdx.x;
   if (pair >= n) return;
-  const PairProfDesc pd = descs[pair];
+  const auto pd = descs[pair];
   const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, nC = mm.nCols, PL = nC + 1, K = pd.nIn, L = pd.nRows;
   const double *A = logA + pd.inBase * CA;
   const double *B = logB + pd.rowBase * PL;
-  const TwoMergeLattice<true> lat{const_cast<double *>(pool) + pd.cellBase, nullptr, S, PL, L, 0, 0};
+  const TwoMergeLattice<true, ENV> lat(pd, t, const_cast<double *>(pool) + pd.cellBase, nullptr, S, PL);
   uint32_t *pe = edges + pd.pathBase;
   int32_t *pr = rows + pd.pathBase, *pi = inRows + pd.pathBase;
   int i = K, r = L, q = S - 1, layer = 2, p = 0;
@@ -515,13 +639,13 @@ __global__ void k_profile_two_merge_traceback(DevMachine m, MergeMap mm, const P
     if (layer == 2) {
       const double cur = lat.at(i, r, 2)[p * S + q];
       if (lat.at(i, r, 1)[p * S + q] == cur) { layer = 1; continue; }
-      if (i > 0 && lat.at(i - 1, r, 2)[p * S + q] + Ai[0] == cur) { --i; continue; }
+      if (i > 0 && lat.inside(i - 1, r) && lat.at(i - 1, r, 2)[p * S + q] + Ai[0] == cur) { --i; continue; }
       len[pair] = -3; return;
     } else if (layer == 1) {
       const double *W = lat.at(i, r, 1) + p * S;
       const double cur = W[q];
       if (lat.at(i, r, 0)[p * S + q] == cur) { layer = 0; continue; }
-      if (i > 0) {
+      if (i > 0 && lat.inside(i - 1, r)) {
         const double *Zl = lat.at(i - 1, r, 2) + p * S;
         for (int a = 1; a <= m.nIn && found < 0; ++a) {
           const int row = q * KK + a * C;
@@ -544,16 +668,17 @@ __global__ void k_profile_two_merge_traceback(DevMachine m, MergeMap mm, const P
       i = ni; q = found; layer = nl;
     } else {
       if (r == 0) { if (i != 0 || q != 0 || p != 0) { len[pair] = -3; return; } break; }
-      const double *Np = lat.at(i, r - 1, 0);
+      const bool up = lat.inside(i, r - 1);
+      const double *Np = lat.at(i, r - 1, 0);      // (an address alone: read only where the cell is inside)
       const double cur = lat.at(i, r, 0)[p * S + q], w = B[(long long)(r - 1) * PL + p];
       if (p == 0) {
-        int k = 0;
+        int k = up ? 0 : PL;
         while (k < PL && !(Np[k * S + q] + w == cur)) ++k;
         if (k == PL) { len[pair] = -3; return; }
         p = k; --r;
         continue;
       }
-      if (Np[p * S + q] + w == cur) { --r; continue; }
+      if (up && Np[p * S + q] + w == cur) { --r; continue; }
       const int tok = mm.colTok[p - 1];
       int from = -1;
       // the edge's exclusion value over the planes of V and the lowest plane that attains it
@@ -564,7 +689,7 @@ __global__ void k_profile_two_merge_traceback(DevMachine m, MergeMap mm, const P
           if (k != p && xs < V[k * S + s]) { xs = V[k * S + s]; kx = k; }
         return xs;
       };
-      if (i > 0) {
+      if (i > 0 && lat.inside(i - 1, r - 1)) {
         const double *Zd = lat.at(i - 1, r - 1, 2);
         for (int a = 1; a <= m.nIn && found < 0; ++a) {
           const int row = q * KK + a * C + tok;
@@ -577,7 +702,7 @@ __global__ void k_profile_two_merge_traceback(DevMachine m, MergeMap mm, const P
           }
         }
       }
-      if (found < 0) {
+      if (found < 0 && up) {
         const double *Wu = lat.at(i, r - 1, 1);
         e = m.inOff[q * KK + tok];
         for (const int e1 = m.inOff[q * KK + tok + 1]; e < e1; ++e) {
@@ -601,68 +726,122 @@ __global__ void k_profile_two_merge_traceback(DevMachine m, MergeMap mm, const P
   len[pair] = cnt;
 }
 
-// beyond the default 64 KiB the kernels must be told; asked for once, and only when a ring needs it
+// beyond the default 64 KiB the kernels must be told; asked for once, for the full and the envelope instantiations together, and only
+// when a ring needs it
 static bool ptm_allow_lds(size_t lds) {
   static size_t ldsAllowed = 64 * 1024;
   if (lds <= ldsAllowed) return true;
-  const void *ks[] = {(const void *)&k_profile_two_merge_fwd<MB_FORWARD, false>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, false>,
-                      (const void *)&k_profile_two_merge_fwd<MB_FORWARD, true>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, true>,
-                      (const void *)&k_profile_two_merge_bwd};
+  const void *ks[] = {(const void *)&k_profile_two_merge_fwd<MB_FORWARD, false, false>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, false, false>,
+                      (const void *)&k_profile_two_merge_fwd<MB_FORWARD, true, false>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, true, false>,
+                      (const void *)&k_profile_two_merge_bwd<false>,
+                      (const void *)&k_profile_two_merge_fwd<MB_FORWARD, false, true>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, false, true>,
+                      (const void *)&k_profile_two_merge_fwd<MB_FORWARD, true, true>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, true, true>,
+                      (const void *)&k_profile_two_merge_bwd<true>};
   for (const void *k : ks)
     if (!hip_ok(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), "k_profile_two_merge: raising the LDS limit")) return false;
   ldsAllowed = SWEEP_LDS_MAX;
   return true;
 }
 
-int launch_profile_two_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const PairProfDesc *d, int n, size_t lds,
-                                 long long maxItems, const double *logA, const double *logB, double *pool, double *scratch,
-                                 double *loglike, hipStream_t st) {
+// The launchers: each sweep once over a form of the lattice, and the two overloads of the header that name one.
+template <bool ENV>
+static int ptm_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const typename TwoMergeLattice<true, ENV>::Desc *d, typename TwoMergeLattice<true, ENV>::Tables t,
+                   int n, size_t lds, long long maxItems, const double *logA, const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st) {
   if (n <= 0) return 0;
   if (!ptm_allow_lds(lds)) return 1;
   const dim3 g(n), b(sweep_threads(maxItems));
   if (mode == MB_VITERBI) {
-    if (mat) k_profile_two_merge_fwd<MB_VITERBI, true><<<g, b, lds, st>>>(m->dev, mm, d, logA, logB, pool, scratch, loglike);
-    else k_profile_two_merge_fwd<MB_VITERBI, false><<<g, b, lds, st>>>(m->dev, mm, d, logA, logB, pool, scratch, loglike);
+    if (mat) k_profile_two_merge_fwd<MB_VITERBI, true, ENV><<<g, b, lds, st>>>(m->dev, mm, d, t, logA, logB, pool, scratch, loglike);
+    else k_profile_two_merge_fwd<MB_VITERBI, false, ENV><<<g, b, lds, st>>>(m->dev, mm, d, t, logA, logB, pool, scratch, loglike);
   } else {
-    if (mat) k_profile_two_merge_fwd<MB_FORWARD, true><<<g, b, lds, st>>>(m->dev, mm, d, logA, logB, pool, scratch, loglike);
-    else k_profile_two_merge_fwd<MB_FORWARD, false><<<g, b, lds, st>>>(m->dev, mm, d, logA, logB, pool, scratch, loglike);
+    if (mat) k_profile_two_merge_fwd<MB_FORWARD, true, ENV><<<g, b, lds, st>>>(m->dev, mm, d, t, logA, logB, pool, scratch, loglike);
+    else k_profile_two_merge_fwd<MB_FORWARD, false, ENV><<<g, b, lds, st>>>(m->dev, mm, d, t, logA, logB, pool, scratch, loglike);
   }
-  return hip_ok(hipGetLastError(), "k_profile_two_merge_fwd") ? 0 : 1;
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_two_merge_env_fwd" : "k_profile_two_merge_fwd") ? 0 : 1;
+}
+int launch_profile_two_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const PairProfDesc *d, int n, size_t lds,
+                                 long long maxItems, const double *logA, const double *logB, double *pool, double *scratch,
+                                 double *loglike, hipStream_t st) {
+  return ptm_fwd<false>(m, mm, mode, mat, d, {}, n, lds, maxItems, logA, logB, pool, scratch, loglike, st);
+}
+int launch_profile_two_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const TwoEnvDesc *d, const TwoEnvTables &t, int n, size_t lds,
+                                 long long maxItems, const double *logA, const double *logB, double *pool, double *scratch,
+                                 double *loglike, hipStream_t st) {
+  return ptm_fwd<true>(m, mm, mode, mat, d, t, n, lds, maxItems, logA, logB, pool, scratch, loglike, st);
 }
 
-int launch_profile_two_merge_bwd(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, size_t lds, long long maxItems,
-                                 const double *logA, const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st) {
+template <bool ENV>
+static int ptm_bwd(const mb_machine *m, MergeMap mm, const typename TwoMergeLattice<true, ENV>::Desc *d, typename TwoMergeLattice<true, ENV>::Tables t, int n, size_t lds,
+                   long long maxItems, const double *logA, const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st) {
   if (n <= 0) return 0;
   if (!ptm_allow_lds(lds)) return 1;
-  k_profile_two_merge_bwd<<<dim3(n), dim3(sweep_threads(maxItems)), lds, st>>>(m->dev, mm, d, logA, logB, pool, scratch, loglike);
-  return hip_ok(hipGetLastError(), "k_profile_two_merge_bwd") ? 0 : 1;
+  k_profile_two_merge_bwd<ENV><<<dim3(n), dim3(sweep_threads(maxItems)), lds, st>>>(m->dev, mm, d, t, logA, logB, pool, scratch, loglike);
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_two_merge_env_bwd" : "k_profile_two_merge_bwd") ? 0 : 1;
+}
+int launch_profile_two_merge_bwd(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, size_t lds, long long maxItems,
+                                 const double *logA, const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  return ptm_bwd<false>(m, mm, d, {}, n, lds, maxItems, logA, logB, pool, scratch, loglike, st);
+}
+int launch_profile_two_merge_bwd(const mb_machine *m, MergeMap mm, const TwoEnvDesc *d, const TwoEnvTables &t, int n, size_t lds, long long maxItems,
+                                 const double *logA, const double *logB, double *pool, double *scratch, double *loglike, hipStream_t st) {
+  return ptm_bwd<true>(m, mm, d, t, n, lds, maxItems, logA, logB, pool, scratch, loglike, st);
 }
 
+template <bool ENV>
+static int ptm_counts(const mb_machine *m, MergeMap mm, const typename TwoMergeLattice<true, ENV>::Desc *d, typename TwoMergeLattice<true, ENV>::Tables t, int n,
+                      int groupsPerPair, const double *logA, const double *logB, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
+  if (n <= 0 || m->nTrans <= 0) return 0;
+  k_profile_two_merge_counts<ENV><<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(
+      m->dev, mm, d, t, groupsPerPair, logA, logB, fwdPool, bwdPool, m->nTrans, counts, g_deterministic ? 1 : 0);
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_two_merge_env_counts" : "k_profile_two_merge_counts") ? 0 : 1;
+}
 int launch_profile_two_merge_counts(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, int groupsPerPair, const double *logA,
                                     const double *logB, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
-  if (n <= 0 || m->nTrans <= 0) return 0;
-  k_profile_two_merge_counts<<<dim3((unsigned)((long long)n * groupsPerPair)), dim3(256), 0, st>>>(
-      m->dev, mm, d, groupsPerPair, logA, logB, fwdPool, bwdPool, m->nTrans, counts, g_deterministic ? 1 : 0);
-  return hip_ok(hipGetLastError(), "k_profile_two_merge_counts") ? 0 : 1;
+  return ptm_counts<false>(m, mm, d, {}, n, groupsPerPair, logA, logB, fwdPool, bwdPool, counts, st);
+}
+int launch_profile_two_merge_counts(const mb_machine *m, MergeMap mm, const TwoEnvDesc *d, const TwoEnvTables &t, int n, int groupsPerPair, const double *logA,
+                                    const double *logB, const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st) {
+  return ptm_counts<true>(m, mm, d, t, n, groupsPerPair, logA, logB, fwdPool, bwdPool, counts, st);
 }
 
-int launch_profile_two_merge_rowpost(const mb_machine *m, MergeMap mm, int axis, const PairProfDesc *d, int n, int groupsPerPair, int tabMax,
-                                     const double *logA, const double *logB, const double *fwdPool, const double *bwdPool,
-                                     const double *loglike, double *post, hipStream_t st) {
+template <bool ENV>
+static int ptm_rowpost(const mb_machine *m, MergeMap mm, int axis, const typename TwoMergeLattice<true, ENV>::Desc *d, typename TwoMergeLattice<true, ENV>::Tables t, int n,
+                       int groupsPerPair, int tabMax, const double *logA, const double *logB, const double *fwdPool, const double *bwdPool,
+                       const double *loglike, double *post, hipStream_t st) {
   if (n <= 0) return 0;
   const dim3 g((unsigned)((long long)n * groupsPerPair)), b(ROWPOST_THREADS);
   const int det = g_deterministic ? 1 : 0;
-  if (axis) k_profile_two_merge_rowpost<1><<<g, b, 0, st>>>(m->dev, mm, d, groupsPerPair, logA, logB, fwdPool, bwdPool, loglike, post, tabMax, det);
-  else k_profile_two_merge_rowpost<0><<<g, b, 0, st>>>(m->dev, mm, d, groupsPerPair, logA, logB, fwdPool, bwdPool, loglike, post, tabMax, det);
-  return hip_ok(hipGetLastError(), "k_profile_two_merge_rowpost") ? 0 : 1;
+  if (axis) k_profile_two_merge_rowpost<1, ENV><<<g, b, 0, st>>>(m->dev, mm, d, t, groupsPerPair, logA, logB, fwdPool, bwdPool, loglike, post, tabMax, det);
+  else k_profile_two_merge_rowpost<0, ENV><<<g, b, 0, st>>>(m->dev, mm, d, t, groupsPerPair, logA, logB, fwdPool, bwdPool, loglike, post, tabMax, det);
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_two_merge_env_rowpost" : "k_profile_two_merge_rowpost") ? 0 : 1;
+}
+int launch_profile_two_merge_rowpost(const mb_machine *m, MergeMap mm, int axis, const PairProfDesc *d, int n, int groupsPerPair, int tabMax,
+                                     const double *logA, const double *logB, const double *fwdPool, const double *bwdPool,
+                                     const double *loglike, double *post, hipStream_t st) {
+  return ptm_rowpost<false>(m, mm, axis, d, {}, n, groupsPerPair, tabMax, logA, logB, fwdPool, bwdPool, loglike, post, st);
+}
+int launch_profile_two_merge_rowpost(const mb_machine *m, MergeMap mm, int axis, const TwoEnvDesc *d, const TwoEnvTables &t, int n, int groupsPerPair, int tabMax,
+                                     const double *logA, const double *logB, const double *fwdPool, const double *bwdPool,
+                                     const double *loglike, double *post, hipStream_t st) {
+  return ptm_rowpost<true>(m, mm, axis, d, t, n, groupsPerPair, tabMax, logA, logB, fwdPool, bwdPool, loglike, post, st);
 }
 
+template <bool ENV>
+static int ptm_traceback(const mb_machine *m, MergeMap mm, const typename TwoMergeLattice<true, ENV>::Desc *d, typename TwoMergeLattice<true, ENV>::Tables t, int n,
+                         const double *logA, const double *logB, const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, hipStream_t st) {
+  if (n <= 0) return 0;
+  k_profile_two_merge_traceback<ENV><<<(n + 63) / 64, 64, 0, st>>>(m->dev, mm, d, t, n, logA, logB, pool, edges, rows, inRows, len);
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_two_merge_env_traceback" : "k_profile_two_merge_traceback") ? 0 : 1;
+}
 int launch_profile_two_merge_traceback(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, const double *logA,
                                        const double *logB, const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows,
                                        long long *len, hipStream_t st) {
-  if (n <= 0) return 0;
-  k_profile_two_merge_traceback<<<(n + 63) / 64, 64, 0, st>>>(m->dev, mm, d, n, logA, logB, pool, edges, rows, inRows, len);
-  return hip_ok(hipGetLastError(), "k_profile_two_merge_traceback") ? 0 : 1;
+  return ptm_traceback<false>(m, mm, d, {}, n, logA, logB, pool, edges, rows, inRows, len, st);
+}
+int launch_profile_two_merge_traceback(const mb_machine *m, MergeMap mm, const TwoEnvDesc *d, const TwoEnvTables &t, int n, const double *logA,
+                                       const double *logB, const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows,
+                                       long long *len, hipStream_t st) {
+  return ptm_traceback<true>(m, mm, d, t, n, logA, logB, pool, edges, rows, inRows, len, st);
 }
 
 }  // namespace mb

@@ -1392,7 +1392,12 @@ class TwoMergedProfileDP(TwoProfileDP):
     plane k != c that attains its XZ / XW; W: "no move", then the input-only edges, then the silent edges; Z: W, then the input
     blank; the end: planes ascending.  Every method takes (A, B): A the [K, nInTok + 1] log rows of Profile.logRowsIn, B the
     [L, nCols + 1] log rows of Profile.mergeRows.  Lattices are [K + 1, L + 1, nCols + 1, S]; every sweep is vectorised over planes
-    and states."""
+    and states.
+
+    ``env`` (forward, backward, counts, mergedRowPosteriors, viterbi): as TwoProfileDP's, checked by envelopeRows with K for I --
+    cell (i, r) exists iff inStart[r] <= i < inEnd[r], in every plane; N, W, Z, XW, XZ and NB, WB, ZB of every other cell are -inf
+    (docs/profile_tapes.md, "Pairs of profiles against a merged profile under an envelope").  The sweeps visit the envelope cells
+    alone and read a cell outside as the -inf it is.  Without it not one operation differs."""
 
     def __init__(self, em: EvaluatedMachine, colTok: Sequence[int]):
         super().__init__(em)
@@ -1428,11 +1433,11 @@ class TwoMergedProfileDP(TwoProfileDP):
         idx = (np.arange(self.PL)[:, None] * S + d[None, :]).ravel()
         return fold(base.ravel(), idx, vals.ravel()).reshape(self.PL, S)
 
-    def forward(self, A, B, mode: str = "exact"):
+    def forward(self, A, B, mode: str = "exact", env=None):
         """(loglike, N, W, Z), each [K+1][L+1][nCols+1][S]; mode "exact" or "max"."""
-        return self._sweep(A, B, mode)[:4]
+        return self._sweep(A, B, mode, env)[:4]
 
-    def _sweep(self, A, B, mode: str):
+    def _sweep(self, A, B, mode: str, env=None):
         """forward() and the exclusion vectors XW, XZ [K+1][L+1][nCols+1][S] (plane 0 of either is not read)"""
         A, B = self._checkTwo(A, B)
         mx = mode == "max"
@@ -1444,8 +1449,9 @@ class TwoMergedProfileDP(TwoProfileDP):
         _, mS, mD, mW, mA, mC = self.mCol
         _, eS, eD, eW, eC = self.emitCol
         _, iS, iD, iW, iA, _ = self.iAll
+        inside = self.envelopeRows(env, K, L)
         for i in range(K + 1):
-            for r in range(L + 1):
+            for r in (range(L + 1) if inside is None else inside[i]):      # (a cell outside stays -inf and is read as such)
                 base = np.full((PL, S), _NEG)
                 if i == 0 and r == 0:
                     base[0, 0] = 0.0
@@ -1472,7 +1478,7 @@ class TwoMergedProfileDP(TwoProfileDP):
                 XZ[i, r] = _excl_planes(z_, mx)
         return float(_red_planes(Z[K, L, :, S - 1:S], mx)[0]), N, W, Z, XW, XZ
 
-    def backward(self, A, B):
+    def backward(self, A, B, env=None):
         """(loglike, NB, WB, ZB), each [K+1][L+1][nCols+1][S], exact log-sum-exp; loglike = NB[0][0][0][0]."""
         A, B = self._checkTwo(A, B)
         K, L, S, PL = len(A), len(B), self.S, self.PL
@@ -1482,8 +1488,9 @@ class TwoMergedProfileDP(TwoProfileDP):
         _, eS, eD, eW, eC = self.emitCol
         _, iS, iD, iW, iA, _ = self.iAll
         neg = np.full(PL * S, _NEG)
+        inside = self.envelopeRows(env, K, L)
         for i in range(K, -1, -1):
-            for r in range(L, -1, -1):
+            for r in (range(L, -1, -1) if inside is None else reversed(inside[i])):
                 base = np.full((PL, S), _NEG)
                 if i == K and r == L:
                     base[:, S - 1] = 0.0
@@ -1509,17 +1516,18 @@ class TwoMergedProfileDP(TwoProfileDP):
                     NB[i, r] = base
         return float(NB[0, 0, 0, 0]), NB, WB, ZB
 
-    def counts(self, A, B, blanks: Optional[list] = None) -> Tuple[np.ndarray, float]:
+    def counts(self, A, B, blanks: Optional[list] = None, env=None) -> Tuple[np.ndarray, float]:
         """(posterior expected use of every transition, Forward loglike); nothing for a -inf pair.  Blanks of either tape and
         repeat rows are not edges; ``blanks`` (a list) receives (mass of the output blanks, mass of the repeats, mass of the input
         blanks), summed over the lattice."""
         A, B = self._checkTwo(A, B)
-        ll, NF, WF, ZF, XW, XZ = self._sweep(A, B, "exact")
+        ll, NF, WF, ZF, XW, XZ = self._sweep(A, B, "exact", env)
         out = np.zeros(self.em.nTransitions)
         if not ll > _NEG:
             return out, ll
-        _, NB, WB, ZB = self.backward(A, B)
+        _, NB, WB, ZB = self.backward(A, B) if env is None else self.backward(A, B, env=env)
         K, L = len(A), len(B)
+        inside = self.envelopeRows(env, K, L)
         mE, mS, mD, mW, mA, mC = self.mCol
         eE, eS, eD, eW, eC = self.emitCol
         iE, iS, iD, iW, iA, _ = self.iAll
@@ -1529,7 +1537,7 @@ class TwoMergedProfileDP(TwoProfileDP):
             return float(np.exp(b[b > _NEG]).sum())
         with np.errstate(invalid="ignore"):
             for i in range(K + 1):
-                for r in range(L + 1):
+                for r in (range(L + 1) if inside is None else inside[i]):      # (a term into a cell outside is exp(-inf))
                     f, z = WF[i, r] - ll, ZF[i, r] - ll
                     fx, zx = XW[i, r] - ll, XZ[i, r] - ll
                     if r < L:
@@ -1550,7 +1558,7 @@ class TwoMergedProfileDP(TwoProfileDP):
     def rowPosteriors(self, A, B, env=None):
         raise MachineError("row posteriors take plain profiles")
 
-    def mergedRowPosteriors(self, A, B, repeats: Optional[list] = None) -> Tuple[np.ndarray, np.ndarray, float]:
+    def mergedRowPosteriors(self, A, B, repeats: Optional[list] = None, env=None) -> Tuple[np.ndarray, np.ndarray, float]:
         """(postA[K, nInTok + 1], postB[L, nCols + 1], Forward loglike): postB[r][c] is the posterior probability that output row r
         was consumed as column c (column 0: as the blank), postA[i][a] that input row i was consumed as input token a (column 0:
         as the input blank) -- the gradients of loglike in B[r][c] and in A[i][a] (docs/profile_tapes.md, "Row posteriors of pairs
@@ -1559,14 +1567,15 @@ class TwoMergedProfileDP(TwoProfileDP):
         ``repeats``, if a list, receives the [L, nCols + 1] repeat part of postB, so that postB - repeats sums per token to the
         counts.  Every row of either table sums to 1; zeros for a -inf pair; exactly 0 where the weight is -inf."""
         A, B = self._checkTwo(A, B)
-        ll, NF, WF, ZF = self.forward(A, B)
+        ll, NF, WF, ZF = self.forward(A, B) if env is None else self.forward(A, B, env=env)
         K, L, PL = len(A), len(B), self.PL
         postA = np.zeros((K, self.em.nInTok + 1)); postB = np.zeros((L, PL)); rep = np.zeros((L, PL))
         if repeats is not None:
             repeats.append(rep)
         if not ll > _NEG:
             return postA, postB, ll
-        _, NB, WB, ZB = self.backward(A, B)
+        _, NB, WB, ZB = self.backward(A, B) if env is None else self.backward(A, B, env=env)
+        inside = self.envelopeRows(env, K, L)
         _, mS, mD, mW, mA, mC = self.mCol
         _, eS, eD, eW, eC = self.emitCol
         _, iS, iD, iW, iA, _ = self.iAll
@@ -1577,7 +1586,7 @@ class TwoMergedProfileDP(TwoProfileDP):
             return float(np.exp(b[b > _NEG]).sum())
         with np.errstate(invalid="ignore"):
             for i in range(K + 1):
-                for r in range(L + 1):
+                for r in (range(L + 1) if inside is None else inside[i]):      # (a term into a cell outside is dead)
                     f, z = WF[i, r] - ll, ZF[i, r] - ll
                     if r < L:
                         if i < K:
@@ -1600,15 +1609,18 @@ class TwoMergedProfileDP(TwoProfileDP):
         postB += rep
         return postA, postB, ll
 
-    def viterbi(self, A, B, census: Optional[dict] = None) -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
+    def viterbi(self, A, B, census: Optional[dict] = None, env=None) -> Tuple[float, np.ndarray, np.ndarray, np.ndarray]:
         """(score, global edge ids start -> end, output row, input row at which each fired); the first maximum in the fill's
         candidate order, rows as TwoProfileDP.viterbi; blanks of either tape and repeat rows are not edges.  ``census``: per step
         at which two or more candidates equal the cell, a count under the tuple of the kinds that tie, in candidate order ("repeat",
         "match", "emit" at N[.][.][c]; "stay", "ins", "silent" at a W cell; "wait", "inblank" at a Z cell); under ("blank",) the
         steps at N[.][.][0] that two planes attain, under ("plane",) the emitting edges whose XZ / XW two planes attain, under
-        ("end",) an end that two planes attain."""
+        ("end",) an end that two planes attain.  Under ``env`` a candidate whose source cell lies outside the envelope is -inf and
+        loses; the census counts, under ("outside", kind), the steps that had such a candidate of that kind ("blank" for the
+        step at N[.][.][0])."""
         A, B = self._checkTwo(A, B)
-        v, N, W, Z = self.forward(A, B, "max")
+        v, N, W, Z = self.forward(A, B, "max") if env is None else self.forward(A, B, "max", env=env)
+        inside = self.envelopeRows(env, len(A), len(B))
         edges: List[int] = []; rows: List[int] = []; ins: List[int] = []
         if not v > _NEG:
             return v, np.zeros(0, np.uint32), np.zeros(0, np.int32), np.zeros(0, np.int32)
@@ -1616,6 +1628,16 @@ class TwoMergedProfileDP(TwoProfileDP):
         def tie(kinds, n: int = 2):
             if census is not None and n > 1:
                 census[kinds] = census.get(kinds, 0) + 1
+
+        def outside(kinds):
+            """the census of the candidate kinds of cell (i, r) whose sources lie outside"""
+            if census is None or inside is None:
+                return
+            for kind in dict.fromkeys(k for k in kinds if k not in ("wait", "stay", "silent")):
+                si = i - (kind in ("inblank", "ins", "match"))
+                sr = r - (kind in ("blank", "repeat", "match", "emit"))
+                if sr not in inside[si]:
+                    census[("outside", kind)] = census.get(("outside", kind), 0) + 1
         mE, mS, mD, mW, mA, mO = self.mAll
         iE, iS, iD, iW, iA, _ = self.iAll
         i, r, q, layer = len(A), len(B), self.S - 1, 2
@@ -1642,6 +1664,7 @@ class TwoMergedProfileDP(TwoProfileDP):
                     break
                 Br, cur = B[r - 1], N[i, r, p, q]
                 if p == 0:
+                    outside(["blank"])
                     hit = [N[i, r - 1, k, q] + Br[0] == cur for k in range(self.PL)]
                     tie(("blank",), sum(hit))
                     p = hit.index(True)
@@ -1658,6 +1681,7 @@ class TwoMergedProfileDP(TwoProfileDP):
                     if self.eO[k] == tok:
                         xv = max(W[i, r - 1, o_, self.eS[k]] for o_ in oth)
                         cand.append(("emit", int(self.eId[k]), int(self.eS[k]), xv, (xv + self.eW[k]) + Br[p] == cur))
+            outside(c[0] for c in cand)
             hits = [c for c in cand if c[4]]
             if len(hits) > 1:
                 tie(tuple(dict.fromkeys(c[0] for c in hits)))

@@ -200,7 +200,7 @@ def two_profile_loglike(machine_or_dm, logA, inOff, logB, rowOff, envs=None, bac
     return _TwoProfileLoglike.apply(logA, logB, machine_or_dm, inOff, rowOff, envs, backend)
 
 
-def _two_merged_row_posteriors(machine_or_dm, A, inOff, B, rowOff, colTok, wantA, wantB, backend):
+def _two_merged_row_posteriors(machine_or_dm, A, inOff, B, rowOff, colTok, wantA, wantB, backend, envs=None):
     """_two_row_posteriors against CTC-merged output rows: postB is [sumRows, nCols + 1]."""
     n = len(rowOff) - 1
     As = [A[inOff[k]:inOff[k + 1]] for k in range(n)]
@@ -212,7 +212,8 @@ def _two_merged_row_posteriors(machine_or_dm, A, inOff, B, rowOff, colTok, wantA
         postA, postB = np.zeros(A.shape, np.float64), np.zeros(B.shape, np.float64)
         ll = np.empty(n, np.float64)
         for k in range(n):
-            postA[inOff[k]:inOff[k + 1]], postB[rowOff[k]:rowOff[k + 1]], ll[k] = dp.mergedRowPosteriors(As[k], Bs[k])
+            postA[inOff[k]:inOff[k + 1]], postB[rowOff[k]:rowOff[k + 1]], ll[k] = (
+                dp.mergedRowPosteriors(As[k], Bs[k]) if envs is None or envs[k] is None else dp.mergedRowPosteriors(As[k], Bs[k], env=envs[k]))
         return (postA if wantA else None), (postB if wantB else None), ll
     if backend != "device":
         raise ValueError('backend is "device" or "numpy"')
@@ -221,7 +222,7 @@ def _two_merged_row_posteriors(machine_or_dm, A, inOff, B, rowOff, colTok, wantA
     dm = capi.DeviceMachine(machine_or_dm) if own else machine_or_dm
     twos = None
     try:
-        twos = capi.DeviceProfileTwos(dm, As, Bs, colTok=colTok)
+        twos = capi.DeviceProfileTwos(dm, As, Bs, colTok=colTok, mergedEnvs=envs)
         return twos.merged_row_posteriors(inputs=wantA, outputs=wantB)
     finally:
         if twos is not None:
@@ -232,20 +233,22 @@ def _two_merged_row_posteriors(machine_or_dm, A, inOff, B, rowOff, colTok, wantA
 
 class _TwoMergedProfileLoglike(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logA, logB, machine_or_dm, inOff, rowOff, colTok, backend):
+    def forward(ctx, logA, logB, machine_or_dm, inOff, rowOff, colTok, backend, envs):
         A = np.ascontiguousarray(logA.detach().cpu().numpy(), np.float64)
         B = np.ascontiguousarray(logB.detach().cpu().numpy(), np.float64)
         wantA, wantB = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        postA, postB, ll = _two_merged_row_posteriors(machine_or_dm, A, inOff, B, rowOff, colTok, wantA, wantB, backend)
+        postA, postB, ll = _two_merged_row_posteriors(machine_or_dm, A, inOff, B, rowOff, colTok, wantA, wantB, backend, envs)
         ctx.inOff, ctx.rowOff = inOff, rowOff
         ctx.save_for_backward(None if postA is None else torch.from_numpy(postA).to(logA.device),
                               None if postB is None else torch.from_numpy(postB).to(logB.device))
         return torch.from_numpy(ll).to(logB.device)
 
-    backward = staticmethod(_TwoProfileLoglike.backward)      # (the same seven inputs: two tables, five constants)
+    @staticmethod
+    def backward(ctx, grad_out):      # (two tables, six constants)
+        return _TwoProfileLoglike.backward(ctx, grad_out) + (None,)
 
 
-def merged_two_profile_loglike(machine_or_dm, logA, inOff, logB, rowOff, colTok, backend="device"):
+def merged_two_profile_loglike(machine_or_dm, logA, inOff, logB, rowOff, colTok, envs=None, backend="device"):
     """two_profile_loglike against CTC-merged frames on the output tape: tensor[nPairs] of log-likelihoods, pair k the rows
     inOff[k]..inOff[k + 1] of ``logA``, a float64 [sumK, nInTok + 1] tensor (column 0 the input blank), against the rows
     rowOff[k]..rowOff[k + 1] of ``logB``, a float64 [sumRows, nCols + 1] tensor with column 0 the blank and column c a frame's log
@@ -253,7 +256,9 @@ def merged_two_profile_loglike(machine_or_dm, logA, inOff, logB, rowOff, colTok,
     posteriors of pairs of profiles against a merged profile").  Differentiable in both tables: the gradient is grad_out[k] times
     the merged row posteriors of pair k on that tape, zeros for a pair that scores -inf, computed only for the tables that require
     one.  With a one-hot ``logA`` and a one-state echo transducer the result is -ctc_loss(logB, x) per pair.  ``machine_or_dm``: an
-    EvaluatedMachine or a capi.DeviceMachine (kept open for the caller).  ``backend``: "device" (one
+    EvaluatedMachine or a capi.DeviceMachine (kept open for the caller).  ``envs``: per pair None, a seqpair.Envelope or (inStart,
+    inEnd) over the input rows per output row (docs/profile_tapes.md, "Pairs of profiles against a merged profile under an
+    envelope"); the likelihood and the posteriors are then summed over the envelope cells.  ``backend``: "device" (one
     capi.DeviceProfileTwos.merged_row_posteriors() call) or "numpy" (profile.TwoMergedProfileDP.mergedRowPosteriors, no GPU
     needed).  Tensors go through host memory, as pair_profile_loglike's do."""
     if logA.dtype != torch.float64 or logA.dim() != 2:
@@ -269,7 +274,9 @@ def merged_two_profile_loglike(machine_or_dm, logA, inOff, logB, rowOff, colTok,
     colTok = np.asarray(colTok, np.int64).reshape(-1)
     if logB.shape[1] != len(colTok) + 1:
         raise ValueError("merged profiles: logB has one column per entry of colTok and the blank in front")
-    return _TwoMergedProfileLoglike.apply(logA, logB, machine_or_dm, inOff, rowOff, colTok, backend)
+    if envs is not None and len(envs) != len(inOff) - 1:
+        raise ValueError("one envelope (or None) per pair, please")
+    return _TwoMergedProfileLoglike.apply(logA, logB, machine_or_dm, inOff, rowOff, colTok, backend, envs)
 
 
 def _one_row_posteriors(machine_or_dm, P, rowOff, colTok, backend):
