@@ -252,6 +252,25 @@ int mb_profile_pairs_row_posteriors(mb_profile_pairs *p, double *post /* [sum ro
                                     double *loglike /* [nPairs] or NULL */);
 int mb_profile_pairs_set_rows(mb_profile_pairs *p, const double *logP);
 
+/* Posterior path samples of the pairs (docs/profile_tapes.md, "Posterior path samples"): nSamples alignments per pair, each drawn with
+ * its posterior probability by a stochastic traceback over the pair's materialised Forward lattice, on the device -- the reference's
+ * ForwardMatrix::samplePath, without the lattice crossing to the host.  Path k * nSamples + j is sample j of pair k, in the format of
+ * mb_profile_pairs_viterbi (global edge ids start -> end, pathRow as there, may be NULL; blank rows are not edges);
+ * pathLogProb[k * nSamples + j] (may be NULL) is the log posterior probability of that path: its own log weight minus loglike[k].  From
+ * W[I][L][S-1] back to N[0][0][0] every visit of a W cell, or of an N cell with row > 0, is one decision among the terms of the fill in
+ * the fill's order (the Viterbi candidate order above): p_c = exp(term_c - cell), the first c whose running sum exceeds u, else the
+ * last c with p_c > 0.  The uniform u of decision t of sample j of pair k is Philox4x32-10 with key (seed & 0xffffffff, seed >> 32)
+ * and counter (t, j, k & 0xffffffff, k >> 32), u = ((x0 >> 5) * 2^26 + (x1 >> 6)) * 2^-53: a sample depends on nothing but (seed,
+ * k, j), not on chunking, the pairs beside it or nSamples.  A pair whose likelihood is -inf gets empty paths and -inf.  Pairs under
+ * an envelope are sampled over its cells.  The call runs one materialised Forward sweep and one sample launch per kind of pair and
+ * chunk; it chunks under the memory budget by a pair's lattice plus nSamples * (8 * bound + 16) bytes.  Errors, before anything is
+ * launched: nSamples < 1, NULL pathOff or pathEdges, a pathCap below nSamples times the sum of mb_profile_pair_path_bound over the
+ * pairs, a merged pairs object ("sampling takes plain profiles"), more than 2^31 - 1 (pair, sample) lanes in one chunk, a pair beyond
+ * the memory budget on its own. */
+int mb_profile_pairs_sample(mb_profile_pairs *p, int64_t nSamples, uint64_t seed, double *loglike /* [nPairs] or NULL */,
+                            int64_t *pathOff /* [nPairs*nSamples + 1] */, uint32_t *pathEdges, int32_t *pathRow,
+                            double *pathLogProb /* [nPairs*nSamples] or NULL */, int64_t pathCap);
+
 /* Pairs against CTC-merged profiles: a known input sequence against the rows of `--recognize-merge-csv` -- the semantics of
  * compose(M, transpose(CSVProfile::mergingMachine())) on input x[1..I] with an empty output, swept natively over
  * (I + 1) x (rows + 1) x 2 x (nCols + 1) x nStates along anti-diagonals (mb_profile_pair_merge.hip; docs/profile_tapes.md, "Pairs

@@ -589,6 +589,55 @@ def scoreProfilePairs(machine: Machine, inputs, profile, backend: str = "device"
     return scores, (acc.paramCounts(machine, params) if counts else None)
 
 
+def sampleProfilePairs(machine: Machine, inputs, profile, nSamples: int, seed: int = 0, backend: str = "device", params=None,
+                       band: Optional[int] = None):
+    """``nSamples`` alignments of every input sequence with ``profile`` drawn from the posterior (docs/profile_tapes.md,
+    "Posterior path samples"), the pairs of scoreProfilePairs in one batch.  Returns (paths, logq, loglike): paths[k][j] is sample j
+    of input k as a MachinePath (dp.edgesToPath), logq[k][j] its log posterior probability -- the path's own log weight minus
+    loglike[k] -- and loglike[k] the Forward log-likelihood.  An input that cannot be tokenised, or scores -inf, gets empty paths
+    and logq = -inf.  A sample depends on (seed, the input's index among the tokenisable ones, j) alone.  ``backend``: "device"
+    (capi.DeviceProfilePairs.sample_paths) or "numpy" (profile.PairProfileDP.samplePaths).  ``band``: as scoreProfilePairs."""
+    import numpy as np
+    from . import dp
+    from .profile import PairProfileDP
+    from .seqpair import Envelope
+    if backend not in ("device", "numpy"):
+        raise MachineError('backend is "device" or "numpy"')
+    nSamples = int(nSamples)
+    if nSamples < 1:
+        raise MachineError("nSamples must be at least 1")
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    ok = [ev.inputTokenizer.canTokenize(seq) for seq in inputs]
+    xs = [np.asarray(ev.inputTokenizer.tokenize(seq), np.int64).reshape(-1) for seq, k in zip(inputs, ok) if k]
+    P = profile.logRows(ev)
+    envs = None if band is None else [Envelope.band(len(x), len(P), int(band)) for x in xs]
+    if backend == "numpy":
+        pdp = PairProfileDP(ev)
+        ll, got = [], []
+        for k, x in enumerate(xs):
+            l, samples = pdp.samplePaths(x, P, nSamples, seed=seed, pair=k, env=None if envs is None else envs[k])
+            ll.append(l); got.append([(e, q) for e, _r, q in samples])
+    else:
+        from . import capi
+        dm = capi.DeviceMachine(ev)
+        pairs = capi.DeviceProfilePairs(dm, xs, [P] * len(xs))
+        try:
+            if envs is not None:
+                pairs.set_envelopes(envs)
+            ll, off, edges, _rows, lq = pairs.sample_paths(nSamples, seed=seed)
+        finally:
+            pairs.close(); dm.close()
+        got = [[(edges[off[k * nSamples + j]:off[k * nSamples + j + 1]], lq[k * nSamples + j]) for j in range(nSamples)] for k in range(len(xs))]
+    it = iter(zip(ll, got))
+    paths, logq, loglike = [], [], []
+    for good in ok:
+        l, samples = next(it) if good else (-math.inf, [(np.zeros(0, np.uint32), -math.inf)] * nSamples)
+        paths.append([dp.edgesToPath(ev, machine, e) for e, _q in samples])
+        logq.append([float(q) for _e, q in samples])
+        loglike.append(float(l))
+    return paths, logq, loglike
+
+
 def scoreMergedPairs(machine: Machine, inputs, profile, backend: str = "device", params=None, loglike: bool = True,
                      viterbi: bool = False, counts: bool = False, posteriors: bool = False, band: Optional[int] = None):
     """scoreProfilePairs for a profile read CTC-merged (a profile.Profile, or a pair (logP[L, nCols + 1], colTok) as

@@ -880,6 +880,84 @@ int mb_profile_pairs_viterbi(mb_profile_pairs *p, double *loglike, int64_t *path
   return rc;
 }
 
+int mb_profile_pairs_sample(mb_profile_pairs *p, int64_t nSamples, uint64_t seed, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow,
+                            double *pathLogProb, int64_t pathCap) {
+  ApiGuard guard;
+  if (!p || !pathOff || !pathEdges) { set_error("null argument"); return 1; }
+  g_last_ms = 0.0; g_last_launches = 0;
+  if (p->nCols) { set_error("sampling takes plain profiles"); return 1; }
+  if (nSamples < 1) { set_error("nSamples must be at least 1"); return 1; }
+  double need = 0.0;
+  for (long long k = 0; k < p->n; ++k) need += (double)pp_path_bound(p, k);
+  need *= (double)nSamples;
+  if ((double)pathCap < need) {
+    set_error("pathCap too small for the sampled paths: " + std::to_string((long long)pathCap) + " entries, nSamples times the path bounds of the pairs is " +
+              std::to_string((long long)need));
+    return 1;
+  }
+  // a pair costs its lattice, and per sample a path slot (an edge and a row per entry), a length and a log probability
+  std::vector<Chunk> chunks;
+  auto bytes = [&](long long k) { return pp_cell_bytes(p, k) + (double)nSamples * (8.0 * (double)pp_path_bound(p, k) + 16.0); };
+  if (!lattice_chunks(p->n, "pair", bytes, chunks)) return 1;
+  for (const Chunk &c : chunks)
+    if ((double)(c.p1 - c.p0) * (double)nSamples > 2147483647.0) { set_error("too many samples in one chunk: pairs times nSamples exceeds 2^31 - 1 lanes"); return 1; }
+  SmBuf<double> d_ll;
+  MB_HIP(d_ll.alloc(p->n));
+  const int nS = (int)nSamples;
+  std::vector<long long> hlen, hidx;
+  std::vector<double> hlq;
+  std::vector<uint32_t> he;
+  std::vector<int32_t> hr;
+  long long written = 0;
+  pathOff[0] = 0;
+  PairWhere where;
+  int rc = for_chunks<PairProfPlan>(chunks, pp_build(p, false, where), [&](const Chunk &c, PairProfPlan &pl, Timer &tm) {
+    const long long np = c.p1 - c.p0, lanes = np * nS, entries = pl.paths * nS;
+    double *pool = ws_array<double>(0, pl.cells);
+    uint32_t *d_e = ws_array<uint32_t>(3, entries);
+    int32_t *d_r = ws_array<int32_t>(4, entries);
+    long long *d_len = ws_array<long long>(5, lanes);
+    double *d_lq = ws_array<double>(6, lanes);
+    SmBuf<long long> d_idx;
+    if (!pool || !d_e || !d_r || !d_len || !d_lq || !hip_ok(d_idx.alloc(np), "hipMalloc(pair indices)")) return 1;
+    hidx.assign((size_t)np, 0);
+    for (long long k = 0; k < np; ++k) hidx[(size_t)pl.slot[(size_t)k]] = c.p0 + k;      // the kernels see the pairs in slot order
+    if (np && (!hip_ok(hipMemcpyAsync(d_idx.p, hidx.data(), (size_t)np * sizeof(long long), hipMemcpyHostToDevice, g_stream), "H2D pair indices") ||
+               !hip_ok(hipStreamSynchronize(g_stream), "H2D pair indices"))) return 1;
+    {
+      Timed t(tm, pl.launches());
+      if (pp_launch_fwd(p, MB_FORWARD, true, pl, pool, nullptr, d_ll + c.p0)) return 1;
+      if (launch_profile_pair_sample(p->m, pl.d.p, (int)pl.nPlain, nS, d_idx.p, seed, p->d_in, p->d_logP, pool, d_e, d_r, d_len, d_lq, g_stream)) return 1;
+      if (launch_profile_pair_sample(p->m, pl.e.p, pp_env_tables(p), (int)pl.nEnv, nS, d_idx.p + pl.nPlain, seed, p->d_in, p->d_logP, pool, d_e, d_r,
+                                     d_len + pl.nPlain * nS, d_lq + pl.nPlain * nS, g_stream)) return 1;
+    }
+    // lengths and log probabilities landed in slot order, the path slots are packed in pair order
+    hlen.resize((size_t)std::max<long long>(lanes, 1)); hlq.resize(hlen.size());
+    he.resize((size_t)std::max<long long>(entries, 1)); hr.resize(pathRow ? he.size() : 0);
+    if (lanes && (d2h_large(hlen.data(), d_len, (size_t)lanes * sizeof(long long)) || d2h_large(hlq.data(), d_lq, (size_t)lanes * sizeof(double)))) return 1;
+    if (!lanes && !hip_ok(hipStreamSynchronize(g_stream), "sample launch")) return 1;
+    if (entries && (d2h_large(he.data(), d_e, (size_t)entries * sizeof(uint32_t)) || (pathRow && d2h_large(hr.data(), d_r, (size_t)entries * sizeof(int32_t))))) return 1;
+    long long base = 0;
+    for (long long k = 0; k < np; ++k) {
+      const long long bound = pp_path_bound(p, c.p0 + k), at = pl.slot[(size_t)k] * nS;
+      for (long long j = 0; j < nS; ++j, base += bound) {
+        long long n = hlen[(size_t)(at + j)];
+        if (n == -1) n = 0;      // a dead pair: empty paths, logq = -inf
+        else if (n < 0) { set_error(n == -2 ? "pair sample overflowed its bound" : "pair sample found no candidate with a positive probability"); return 1; }
+        std::memcpy(pathEdges + written, he.data() + base, (size_t)n * sizeof(uint32_t));
+        if (pathRow) std::memcpy(pathRow + written, hr.data() + base, (size_t)n * sizeof(int32_t));
+        written += n;
+        pathOff[(c.p0 + k) * nS + j + 1] = written;
+        if (pathLogProb) pathLogProb[(c.p0 + k) * nS + j] = hlq[(size_t)(at + j)];
+      }
+    }
+    return 0;
+  });
+  if (!rc && loglike) rc = fetch_loglike(loglike, d_ll, p->n, &where);
+  g_last_kernel = p->hasEnv ? "k_profile_pair_env_sample" : "k_profile_pair_sample";
+  return rc;
+}
+
 int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglikeSum, double *loglike) {
   ApiGuard guard;
   if (!p || !counts) { set_error("null argument"); return 1; }

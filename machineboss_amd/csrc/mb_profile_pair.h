@@ -56,6 +56,11 @@ int launch_profile_pair_counts(const mb_machine *m, const PairProfDesc *d, int n
                                const double *fwdPool, const double *bwdPool, double *counts, hipStream_t st);
 int launch_profile_pair_traceback(const mb_machine *m, const PairProfDesc *d, int n, const int *inTok, const double *logP, const double *pool,
                                   uint32_t *edges, int32_t *rows, long long *len, hipStream_t st);
+// Posterior path samples over the n pairs' materialised sum lattices (k_profile_pair_sample): nSamples lanes per pair, n * nSamples
+// <= 2^31 - 1.  pairIdx[n]: each pair's index in the object, the `k` of the generator's counter.  Sample j of the pair at d[s] writes
+// len / logq at s * nSamples + j and its path at (d[s].pathBase * nSamples + j * bound), bound = profile_pair_path_bound of the pair.
+int launch_profile_pair_sample(const mb_machine *m, const PairProfDesc *d, int n, int nSamples, const long long *pairIdx, unsigned long long seed, const int *inTok,
+                               const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len, double *logq, hipStream_t st);
 // post[(rowBase + r) * C + o] = the row posteriors of the n pairs, every bin of every row written (nothing to clear); groupsPerPair:
 // at least the row blocks of the pair that has most; det: post holds 64-bit fixed point at 2^-36
 int launch_profile_pair_rowpost(const mb_machine *m, const PairProfDesc *d, int n, int groupsPerPair, int tabMax, const int *inTok, const double *logP,

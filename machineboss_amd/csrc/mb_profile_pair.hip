@@ -470,6 +470,127 @@ __global__ void k_profile_pair_traceback(DevMachine m, const typename Geom<true>
   len[k] = cnt;
 }
 
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11) and the 53-bit uniform of its first two words,
+// the recipe of the Mt19937 variates: ((x0 >> 5) * 2^26 + (x1 >> 6)) * 2^-53.  profile.philox4x32 / sample_uniform are the same text
+// in numpy.
+__device__ __forceinline__ double philox_uniform(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0, hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return ((double)(c0 >> 5) * 67108864.0 + (double)(c1 >> 6)) * (1.0 / 9007199254740992.0);
+}
+
+// One candidate of a sampling decision: p = exp(term - cur) joins the running sum; the first candidate whose sum passes u is taken,
+// and the last one with p > 0 is remembered for the draw that rounding left above the total.
+struct SampleDraw {
+  double u, cur, acc = 0.0, term = 0.0;
+  int a = -1, src = -1, kind = -1;      // the taken candidate: its CSR entry, source state and kind (the caller's numbering)
+  bool done = false;
+  __device__ __forceinline__ SampleDraw(double u, double cur) : u(u), cur(cur) {}
+  __device__ __forceinline__ void offer(double t, int kind_, int a_, int src_) {
+    if (done) return;
+    const double p = exp(t - cur);
+    acc += p;
+    if (p > 0.0) { term = t; kind = kind_; a = a_; src = src_; }
+    done = u < acc;      // (p > 0 here: the sum has just grown past u)
+  }
+};
+
+// Posterior path samples over a materialised SUM lattice (docs/profile_tapes.md, "Posterior path samples"), one lane per (pair slot,
+// sample): lane id serves slot id / nSamples, sample id % nSamples, so the lanes of a wavefront walk the same lattice.  From
+// W[I][L][S-1] back to N[0][0][0]; at every W cell and every N cell with r > 0 one decision among the terms of the fill, in the
+// fill's order and parenthesisation -- the list k_profile_pair_traceback enumerates -- each with probability exp(term - cell).  The
+// uniform of decision t of sample j of pair k (pairIdx[slot]: the pair's index in the object, not in the chunk) is
+// philox_uniform(t, j, k, seed), so a sample depends on nothing else.  logq: the sum of term - cell over the decisions, the log
+// posterior probability of the path.  Edges go into the sample's slot, at (pathBase * nSamples + j * bound) with bound the pair's
+// profile_pair_path_bound, backwards and are reversed at the end.  len = -1: a dead pair (logq = -inf), -2: the slot was too small,
+// -3: no candidate with p > 0 (a corrupt lattice).  A candidate whose source cell lies outside the geometry is left out.
+template <template <bool> class Geom>
+__global__ __launch_bounds__(64) void k_profile_pair_sample(DevMachine m, const typename Geom<true>::Desc *__restrict__ descs, typename Geom<true>::Tables t, long long nLanes,
+                                                            int nSamples, const long long *__restrict__ pairIdx, unsigned long long seed,
+                                                            const int *__restrict__ inTok, const double *__restrict__ logP, const double *__restrict__ pool,
+                                                            uint32_t *edges, int32_t *rows, long long *len, double *logq) {
+  const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= nLanes) return;
+  const int slot = (int)(id / nSamples), j = (int)(id - (long long)slot * nSamples);
+  const auto pd = descs[slot];
+  const unsigned long long k = (unsigned long long)pairIdx[slot];
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), c2 = (uint32_t)k, c3 = (uint32_t)(k >> 32);
+  const int S = m.S, K = m.K, C = m.nOut + 1, I = pd.nIn, L = pd.nRows;
+  const int *x = inTok + pd.inBase;
+  const double *P = logP + pd.rowBase * C;
+  const Geom<true> lat(pd, t, const_cast<double *>(pool) + pd.cellBase, S);
+  const long long cap = I + L + (long long)(I + L + 1) * (m.nLevF - 1);
+  uint32_t *pe = edges + pd.pathBase * nSamples + (long long)j * cap;
+  int32_t *pr = rows + pd.pathBase * nSamples + (long long)j * cap;
+  int i = I, r = L, q = S - 1, layer = 1;
+  long long cnt = 0;
+  uint32_t dec = 0;
+  double lq = 0.0;
+  if (!(lat.at(i, r, 1)[q] > -INFINITY)) { len[id] = -1; logq[id] = -INFINITY; return; }
+  for (;;) {
+    const int xRow = i > 0 ? q * K + x[i - 1] * C : 0;
+    if (layer == 1) {
+      const double *W = lat.at(i, r, 1);
+      SampleDraw d(philox_uniform(dec++, (uint32_t)j, c2, c3, k0, k1), W[q]);
+      d.offer(lat.at(i, r, 0)[q], 0, 0, q);
+      if (i > 0 && lat.inside(i - 1, r)) {
+        const double *Wl = lat.at(i - 1, r, 1);
+        const int a1 = m.inOff[xRow + 1];
+        for (int a = m.inOff[xRow]; a < a1 && !d.done; ++a) d.offer(Wl[m.inSrc[a]] + m.inW[a], 1, a, (int)m.inSrc[a]);
+      }
+      const int a1 = m.inOff[q * K + 1];
+      for (int a = m.inOff[q * K]; a < a1 && !d.done; ++a) {
+        const int s = (int)m.inSrc[a];
+        if (s < q) d.offer(W[s] + m.inW[a], 2, a, s);
+      }
+      if (d.kind < 0) { len[id] = -3; logq[id] = lq; return; }
+      lq += d.term - d.cur;
+      if (d.kind == 0) { layer = 0; continue; }
+      if (cnt >= cap) { len[id] = -2; logq[id] = lq; return; }
+      pe[cnt] = m.inEid[d.a]; pr[cnt] = r; ++cnt;
+      if (d.kind == 1) --i;
+      q = d.src;
+    } else {
+      if (r == 0) { if (i != 0 || q != 0) { len[id] = -3; logq[id] = lq; return; } break; }
+      const double *Pr = P + (long long)(r - 1) * C;
+      SampleDraw d(philox_uniform(dec++, (uint32_t)j, c2, c3, k0, k1), lat.at(i, r, 0)[q]);
+      const bool up = lat.inside(i, r - 1);
+      if (up) d.offer(lat.at(i, r - 1, 0)[q] + Pr[0], 0, 0, q);
+      if (i > 0 && lat.inside(i - 1, r - 1)) {
+        const double *Wd = lat.at(i - 1, r - 1, 1);
+        const int a1 = m.inOff[xRow + C];
+        for (int a = m.inOff[xRow + 1]; a < a1 && !d.done; ++a)
+          d.offer((Wd[m.inSrc[a]] + m.inW[a]) + Pr[m.eOutTok[m.inEid[a]]], 1, a, (int)m.inSrc[a]);
+      }
+      if (up) {
+        const double *Wu = lat.at(i, r - 1, 1);
+        const int a1 = m.inOff[q * K + C];
+        for (int a = m.inOff[q * K + 1]; a < a1 && !d.done; ++a)
+          d.offer((Wu[m.inSrc[a]] + m.inW[a]) + Pr[m.eOutTok[m.inEid[a]]], 2, a, (int)m.inSrc[a]);
+      }
+      if (d.kind < 0) { len[id] = -3; logq[id] = lq; return; }
+      lq += d.term - d.cur;
+      --r;
+      if (d.kind == 0) continue;
+      if (cnt >= cap) { len[id] = -2; logq[id] = lq; return; }
+      pe[cnt] = m.inEid[d.a]; pr[cnt] = r; ++cnt;
+      if (d.kind == 1) --i;
+      q = d.src; layer = 1;
+    }
+  }
+  for (long long u = 0, v = cnt - 1; u < v; ++u, --v) {
+    const uint32_t e = pe[u]; pe[u] = pe[v]; pe[v] = e;
+    const int32_t w = pr[u]; pr[u] = pr[v]; pr[v] = w;
+  }
+  len[id] = cnt;
+  logq[id] = lq;
+}
+
 // The launchers: each sweep once over a geometry, and the two overloads of the headers that name one.
 template <template <bool> class Geom>
 static int pair_fwd(const mb_machine *m, int mode, bool mat, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, size_t lds, long long maxItems,
@@ -567,6 +688,25 @@ int launch_profile_pair_traceback(const mb_machine *m, const PairProfDesc *d, in
 int launch_profile_pair_traceback(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, const int *inTok, const double *logP, const double *pool,
                                   uint32_t *edges, int32_t *rows, long long *len, hipStream_t st) {
   return pair_traceback<EnvGeom>(m, d, t, n, inTok, logP, pool, edges, rows, len, st);
+}
+
+template <template <bool> class Geom>
+static int pair_sample(const mb_machine *m, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, int nSamples, const long long *pairIdx,
+                       unsigned long long seed, const int *inTok, const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len,
+                       double *logq, hipStream_t st) {
+  if (n <= 0) return 0;
+  const long long nLanes = (long long)n * nSamples;      // (the caller keeps it within 2^31 - 1)
+  k_profile_pair_sample<Geom><<<(unsigned)((nLanes + 63) / 64), 64, 0, st>>>(m->dev, d, t, nLanes, nSamples, pairIdx, seed, inTok, logP, pool, edges, rows, len, logq);
+  return hip_ok(hipGetLastError(), Geom<true>::ENV ? "k_profile_pair_env_sample" : "k_profile_pair_sample") ? 0 : 1;
+}
+int launch_profile_pair_sample(const mb_machine *m, const PairProfDesc *d, int n, int nSamples, const long long *pairIdx, unsigned long long seed, const int *inTok,
+                               const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len, double *logq, hipStream_t st) {
+  return pair_sample<FullGeom>(m, d, {}, n, nSamples, pairIdx, seed, inTok, logP, pool, edges, rows, len, logq, st);
+}
+int launch_profile_pair_sample(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, int nSamples, const long long *pairIdx, unsigned long long seed,
+                               const int *inTok, const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len, double *logq,
+                               hipStream_t st) {
+  return pair_sample<EnvGeom>(m, d, t, n, nSamples, pairIdx, seed, inTok, logP, pool, edges, rows, len, logq, st);
 }
 
 }  // namespace mb

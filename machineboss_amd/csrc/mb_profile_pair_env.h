@@ -43,5 +43,8 @@ int launch_profile_pair_rowpost(const mb_machine *m, const PairEnvDesc *d, const
                                 const double *logP, const double *fwdPool, const double *bwdPool, double *post, hipStream_t st);
 int launch_profile_pair_traceback(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, const int *inTok, const double *logP, const double *pool,
                                   uint32_t *edges, int32_t *rows, long long *len, hipStream_t st);
+int launch_profile_pair_sample(const mb_machine *m, const PairEnvDesc *d, const PairEnvTables &t, int n, int nSamples, const long long *pairIdx, unsigned long long seed,
+                               const int *inTok, const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len, double *logq,
+                               hipStream_t st);
 
 }  // namespace mb

@@ -189,6 +189,29 @@ def table_log_sum_exp(a: float, b: float) -> float:
     return mx + (f0 + (f1 - f0) * ((d - n * 1e-4) / 1e-4))
 
 
+_M32 = 0xffffffff
+
+
+def philox4x32(counter: Sequence[int], key: Sequence[int]) -> Tuple[int, int, int, int]:
+    """Philox4x32-10 (Salmon et al., SC'11): four 32-bit counter words and two key words to four output words.  The restatement of
+    philox_uniform's rounds in mb_profile_pair.hip (docs/profile_tapes.md, "Posterior path samples")."""
+    c0, c1, c2, c3 = (int(c) & _M32 for c in counter)
+    k0, k1 = (int(k) & _M32 for k in key)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _M32, (p0 >> 32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0, c1, c2, c3
+
+
+def sample_uniform(seed: int, k: int, j: int, t: int) -> float:
+    """The uniform in [0, 1) of decision ``t`` of sample ``j`` of pair ``k``: key (seed & 0xffffffff, seed >> 32), counter
+    (t, j, k & 0xffffffff, k >> 32), and the 53-bit recipe of the Mt19937 variates on the first two output words."""
+    seed, k = int(seed) & 0xffffffffffffffff, int(k) & 0xffffffffffffffff
+    x0, x1, _, _ = philox4x32((t, j, k & _M32, k >> 32), (seed & _M32, seed >> 32))
+    return ((x0 >> 5) * 67108864 + (x1 >> 6)) * (1.0 / 9007199254740992.0)
+
+
 def _lse_fold(base: np.ndarray, idx: np.ndarray, vals: np.ndarray) -> np.ndarray:
     """out[q] = log(exp(base[q]) + sum_{k: idx[k] = q} exp(vals[k])), exactly (max-shifted); out[q] = base[q] where no term."""
     if len(idx) == 0:
@@ -814,6 +837,88 @@ class PairProfileDP(ProfileDP):
                 edges.append(e); rows.append(r); q = s; layer = 1
                 i -= kind == "match"
         return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32)
+
+    def sampleCandidates(self, x, P, N, W, inside, i: int, r: int, q: int, layer: int):
+        """The candidates of the sampling decision at cell (i, r, q) of ``layer`` (1: W, 0: N with r > 0) over the sum lattice
+        (N, W): (kind, edge id or -1, source state, term) in the fill's order, the list viterbi() enumerates.  ``inside``:
+        envelopeRows(); a candidate whose source cell lies outside is left out."""
+        ok = (lambda si, sr: True) if inside is None else (lambda si, sr: sr in inside[si])
+        cand = []
+        if layer == 1:
+            cand.append(("stay", -1, q, float(N[i, r, q])))
+            if i and ok(i - 1, r):
+                e, s, d, w, _o = self.ins[x[i - 1]]
+                cand += [("ins", int(e[k]), int(s[k]), float(W[i - 1, r, s[k]] + w[k])) for k in np.nonzero(d == q)[0]]
+            cand += [("silent", int(self.sId[k]), int(self.sS[k]), float(W[i, r, self.sS[k]] + self.sW[k])) for k in self.inSil[q]]
+        else:
+            Pr = P[r - 1]
+            up = ok(i, r - 1)
+            if up:
+                cand.append(("blank", -1, q, float(N[i, r - 1, q] + Pr[0])))
+            if i and ok(i - 1, r - 1):
+                e, s, d, w, o = self.match[x[i - 1]]
+                cand += [("match", int(e[k]), int(s[k]), float((W[i - 1, r - 1, s[k]] + w[k]) + Pr[o[k]])) for k in np.nonzero(d == q)[0]]
+            if up:
+                cand += [("emit", int(self.eId[k]), int(self.eS[k]), float((W[i, r - 1, self.eS[k]] + self.eW[k]) + Pr[self.eO[k]]))
+                         for k in self.inEmit[q]]
+        return cand
+
+    def samplePaths(self, x, P, nSamples: int, seed: int = 0, pair: int = 0, env=None, margins: Optional[list] = None):
+        """(loglike, [(edges, rows, logq), ...]): ``nSamples`` paths drawn from the posterior by a stochastic traceback over
+        forward(x, P, env=env) -- the yardstick of k_profile_pair_sample (docs/profile_tapes.md, "Posterior path samples").  From
+        W[I][L][S-1] back to N[0][0][0]; every visit of a W cell, or of an N cell with r > 0, is one decision among
+        sampleCandidates(): p_c = exp(term_c - cell), acc adds them in order from 0.0, the first c with u < acc is taken, else the
+        last c with p_c > 0.  u = sample_uniform(seed, pair, j, t) for decision t of sample j.  logq sums term - cell over the
+        decisions: the path's log posterior probability.  Paths are as viterbi()'s; a -inf pair gives empty paths and logq = -inf.
+        ``margins`` (a list) receives per decision the least |u - acc_c| over all partial sums acc_c of the decision."""
+        x, P = self._checkPair(x, P)
+        ll, N, W = self.forward(x, P) if env is None else self.forward(x, P, env=env)
+        inside = self.envelopeRows(env, len(x), len(P))
+        if inside is not None:
+            inside = [set(rs) for rs in inside]
+        out = []
+        for j in range(int(nSamples)):
+            edges: List[int] = []; rows: List[int] = []
+            if not ll > _NEG:
+                out.append((np.zeros(0, np.uint32), np.zeros(0, np.int32), _NEG))
+                continue
+            i, r, q, layer, t, logq = len(x), len(P), self.S - 1, 1, 0, 0.0
+            while layer == 1 or r > 0:
+                cur = float(W[i, r, q] if layer == 1 else N[i, r, q])
+                cand = self.sampleCandidates(x, P, N, W, inside, i, r, q, layer)
+                u = sample_uniform(seed, pair, j, t)
+                t += 1
+                acc, pick, last, margin = 0.0, None, None, math.inf
+                for c in cand:
+                    p = math.exp(c[3] - cur) if c[3] > _NEG else 0.0
+                    acc += p
+                    margin = min(margin, abs(u - acc))
+                    if p > 0.0:
+                        last = c
+                    if pick is None and u < acc:
+                        pick = c
+                if pick is None:
+                    pick = last
+                if pick is None:
+                    raise MachineError("samplePaths: no candidate with a positive probability")
+                if margins is not None:
+                    margins.append(margin)
+                kind, e, s, term = pick
+                logq += term - cur
+                if kind == "stay":
+                    layer = 0
+                elif kind == "blank":
+                    r -= 1
+                elif kind in ("ins", "silent"):
+                    edges.append(e); rows.append(r); q = s
+                    i -= kind == "ins"
+                else:
+                    r -= 1
+                    edges.append(e); rows.append(r); q = s; layer = 1
+                    i -= kind == "match"
+            assert i == 0 and q == 0
+            out.append((np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32), logq))
+        return ll, out
 
 
 def _excl_planes(A: np.ndarray, mx: bool) -> np.ndarray:
