@@ -318,6 +318,27 @@ int mb_profile_pair_fill_merged_env(mb_machine *m, int mode, const int32_t *inTo
                                     int32_t nCols, const int32_t *colTok, const int32_t *envStart, const int32_t *envEnd,
                                     double *cellsOut);
 
+/* Posterior path samples of pairs against merged profiles (docs/profile_tapes.md, "Posterior path samples of pairs against a merged
+ * profile"): mb_profile_pairs_sample for a merged pairs object, with or without envelopes.  A sample is a LATTICE path: its edges in
+ * the format of mb_profile_pairs_viterbi and the column every row took, rowCol[(rowOff[k] - rowOff[0]) * nSamples + j * L_k + r] for
+ * row r of sample j of pair k (0: the blank; c: column c, fresh or repeated; may be NULL) -- the edge list alone does not say whether
+ * a row no edge consumed was a blank or a repeat.  pathLogProb is the log weight of that lattice path (its edges plus P[r][rowCol[r]]
+ * of every row) minus loglike[k].  Decision 0 picks the end plane among W[I][L][.][S-1], planes ascending, against loglike; then at a
+ * W cell: N ("stay"), the input-only edges, the silent edges, on the cell's plane; at N[.][r][0]: the blank out of every plane
+ * ascending; at N[.][r][c]: the repeat, then the match and then the output-only edges of colTok[c] in `incoming` order, every edge
+ * once per source plane k != c ascending.  The draw rule and the uniforms are those of mb_profile_pairs_sample: a sample depends on
+ * nothing but (seed, k, j).  A pair whose likelihood is -inf gets empty paths, -inf and rowCol = -1 in every row.  The call runs one
+ * materialised Forward sweep and one sample launch per kind of pair and chunk; it chunks under the memory budget by a pair's lattice
+ * (and the ring of its fill, where that lives in global memory) plus nSamples * (8 * bound + 16 + 4 * rows) bytes.  Errors, before
+ * anything is launched: nSamples < 1, NULL pathOff or pathEdges, a pathCap below nSamples times the sum of
+ * mb_profile_pair_path_bound over the pairs, a plain pairs object ("merged sampling takes merged profiles"), more than 2^31 - 1
+ * (pair, sample) lanes in one chunk, a pair beyond the memory budget on its own.  (mb_profile_pairs_sample keeps refusing a merged
+ * object.) */
+int mb_profile_pairs_sample_merged(mb_profile_pairs *p, int64_t nSamples, uint64_t seed, double *loglike /* [nPairs] or NULL */,
+                                   int64_t *pathOff /* [nPairs*nSamples + 1] */, uint32_t *pathEdges, int32_t *pathRow /* or NULL */,
+                                   int32_t *rowCol /* [nSamples * sum rows] or NULL */, double *pathLogProb /* [nPairs*nSamples] or NULL */,
+                                   int64_t pathCap);
+
 /* Pairs of profiles (`--generate-csv A.csv` beside `--recognize-csv B.csv`): a machine WITH an input alphabet between an input
  * profile and an output profile -- the semantics of compose(A.machine(), compose(M, transpose(B.machine()))) with both tapes empty,
  * swept natively over (K + 1) x (rows + 1) x 3 x nStates along anti-diagonals (mb_profile_two.hip; docs/profile_tapes.md, "Pairs

@@ -706,6 +706,68 @@ def scoreMergedPairs(machine: Machine, inputs, profile, backend: str = "device",
     return scores, (acc.paramCounts(machine, params) if counts else None)
 
 
+def sampleMergedPairs(machine: Machine, inputs, profile, nSamples: int, seed: int = 0, backend: str = "device", params=None,
+                      band: Optional[int] = None):
+    """sampleProfilePairs for a profile read CTC-merged (a profile.Profile, or a pair (logP[L, nCols + 1], colTok) as
+    Profile.mergeRows returns): ``nSamples`` lattice paths of every input sequence drawn from the posterior (docs/profile_tapes.md,
+    "Posterior path samples of pairs against a merged profile").  Returns (paths, rowCols, logq, loglike): paths[k][j] is sample j of
+    input k as a MachinePath (dp.edgesToPath), rowCols[k][j] the column each of the L rows took in it (0: the blank; c: column c,
+    fresh or repeated) -- the frame labelling, which with the path determines the lattice path -- logq[k][j] that lattice path's log
+    weight minus loglike[k], and loglike[k] the Forward log-likelihood.  An input that cannot be tokenised, or scores -inf, gets empty
+    paths, rowCols of -1 and logq = -inf.  A sample depends on (seed, the input's index among the tokenisable ones, j) alone.
+    ``backend``: "device" (capi.DeviceProfilePairs.merged_sample_paths) or "numpy" (profile.PairMergedProfileDP.samplePaths).
+    ``band``: as scoreMergedPairs."""
+    import numpy as np
+    from . import dp
+    from .profile import PairMergedProfileDP
+    from .seqpair import Envelope
+    if backend not in ("device", "numpy"):
+        raise MachineError('backend is "device" or "numpy"')
+    nSamples = int(nSamples)
+    if nSamples < 1:
+        raise MachineError("nSamples must be at least 1")
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    if not ev.nOutTok:
+        raise MachineError("--recognize-merge-csv needs a machine with an output alphabet")
+    P, colTok = _mergedRows(profile, ev) if hasattr(profile, "mergeRows") else profile
+    P = np.asarray(P, np.float64).reshape(-1, len(colTok) + 1)
+    L = len(P)
+    ok = [ev.inputTokenizer.canTokenize(seq) for seq in inputs]
+    xs = [np.asarray(ev.inputTokenizer.tokenize(seq), np.int64).reshape(-1) for seq, k in zip(inputs, ok) if k]
+    envs = None if band is None else [Envelope.band(len(x), L, int(band)) for x in xs]
+    if backend == "numpy":
+        pdp = PairMergedProfileDP(ev, colTok)
+        ll, got = [], []
+        for k, x in enumerate(xs):
+            l, samples = pdp.samplePaths(x, P, nSamples, seed=seed, pair=k, env=None if envs is None else envs[k])
+            ll.append(l); got.append([(e, c, q) for e, _r, c, q in samples])
+    else:
+        from . import capi
+        dm = capi.DeviceMachine(ev)
+        pairs = None
+        try:
+            pairs = capi.DeviceProfilePairs(dm, xs, [P] * len(xs), colTok)
+            if envs is not None:
+                pairs.set_merged_envelopes(envs)
+            ll, off, edges, _rows, rc, lq = pairs.merged_sample_paths(nSamples, seed=seed)
+        finally:
+            if pairs is not None:
+                pairs.close()
+            dm.close()
+        rc = rc.reshape(len(xs), nSamples, L)
+        got = [[(edges[off[k * nSamples + j]:off[k * nSamples + j + 1]], rc[k, j].copy(), lq[k * nSamples + j]) for j in range(nSamples)]
+               for k in range(len(xs))]
+    it = iter(zip(ll, got))
+    paths, rowCols, logq, loglike = [], [], [], []
+    for good in ok:
+        l, samples = next(it) if good else (-math.inf, [(np.zeros(0, np.uint32), np.full(L, -1, np.int32), -math.inf)] * nSamples)
+        paths.append([dp.edgesToPath(ev, machine, e) for e, _c, _q in samples])
+        rowCols.append([np.asarray(c, np.int32) for _e, c, _q in samples])
+        logq.append([float(q) for _e, _c, q in samples])
+        loglike.append(float(l))
+    return paths, rowCols, logq, loglike
+
+
 def mergedPairPosteriors(machine: Machine, inputs, profile, backend: str = "device", params=None, band: Optional[int] = None):
     """Every input sequence (a list of symbols) as one pair with ``profile`` read CTC-merged (a profile.Profile, or a pair
     (logP[L, nCols + 1], colTok) as Profile.mergeRows returns), all pairs in one batch: (posteriors, loglike), one [L, nCols + 1]

@@ -37,7 +37,7 @@ EXPORTS = [
     "mb_profile_pairs_set_envelopes", "mb_profile_pair_fill_env", "mb_profile_pairs_cells",
     "mb_profile_pairs_row_posteriors", "mb_profile_pairs_set_rows", "mb_profile_pairs_sample",
     "mb_profile_pairs_row_posteriors_merged", "mb_profile_pairs_set_rows_merged",
-    "mb_profile_pairs_set_envelopes_merged", "mb_profile_pair_fill_merged_env",
+    "mb_profile_pairs_set_envelopes_merged", "mb_profile_pair_fill_merged_env", "mb_profile_pairs_sample_merged",
     "mb_profile_twos_create", "mb_profile_twos_destroy", "mb_profile_twos_forward", "mb_profile_twos_viterbi", "mb_profile_twos_counts",
     "mb_profile_twos_row_posteriors", "mb_profile_twos_set_rows",
     "mb_profile_two_fill",
@@ -149,6 +149,7 @@ def load():
     L.mb_profile_pairs_row_posteriors.argtypes = [vp, dp, dp]
     L.mb_profile_pairs_set_rows.argtypes = [vp, dp]
     L.mb_profile_pairs_sample.argtypes = [vp, C.c_int64, C.c_uint64, dp, i64p, u32p, i32p, dp, C.c_int64]
+    L.mb_profile_pairs_sample_merged.argtypes = [vp, C.c_int64, C.c_uint64, dp, i64p, u32p, i32p, i32p, dp, C.c_int64]
     L.mb_profile_pairs_row_posteriors_merged.argtypes = [vp, dp, dp]
     L.mb_profile_pairs_set_rows_merged.argtypes = [vp, dp]
     L.mb_profile_pairs_set_envelopes_merged.argtypes = [vp, i64p, i32p, i32p]
@@ -809,6 +810,24 @@ class DeviceProfilePairs:
         _check(load().mb_profile_pairs_sample(self.h, nSamples, int(seed) & 0xffffffffffffffff, _p(ll, C.c_double), _p(off, C.c_int64),
                                               _p(edges, C.c_uint32), _p(rows, C.c_int32), _p(logq, C.c_double), cap))
         return ll, off, edges[:off[-1]].copy(), rows[:off[-1]].copy(), logq
+
+    def merged_sample_paths(self, nSamples: int, seed: int = 0, cap: Optional[int] = None):
+        """sample_paths() for an object created with ``colTok`` (mb_profile_pairs_sample_merged; docs/profile_tapes.md, "Posterior
+        path samples of pairs against a merged profile").  Returns (loglike[nPairs], off[nPairs * nSamples + 1], edges, rows,
+        rowCol[nSamples * sumRows], logq[nPairs * nSamples]): rowCol[rowOff[k] * nSamples + j * L_k + r] is the column row r of
+        sample j of pair k took (0: the blank; c: column c, fresh or repeated; -1 in every row of a -inf pair), which with the edges
+        determines the lattice path whose log posterior probability logq is.  The yardstick is
+        profile.PairMergedProfileDP.samplePaths with ``pair=k``."""
+        nSamples = int(nSamples)
+        cap = self.path_cap() * max(nSamples, 0) if cap is None else int(cap)
+        n = self.nPairs * max(nSamples, 0)
+        ll = np.empty(self.nPairs, np.float64)
+        off = np.zeros(n + 1, np.int64); logq = np.empty(n, np.float64)
+        edges = np.empty(max(cap, 1), np.uint32); rows = np.empty(max(cap, 1), np.int32)
+        rowCol = np.full(max(int(self.rowOff[-1]) * max(nSamples, 0), 1), -1, np.int32)
+        _check(load().mb_profile_pairs_sample_merged(self.h, nSamples, int(seed) & 0xffffffffffffffff, _p(ll, C.c_double), _p(off, C.c_int64),
+                                                     _p(edges, C.c_uint32), _p(rows, C.c_int32), _p(rowCol, C.c_int32), _p(logq, C.c_double), cap))
+        return ll, off, edges[:off[-1]].copy(), rows[:off[-1]].copy(), rowCol[:int(self.rowOff[-1]) * nSamples], logq
 
     def counts(self, counts: Optional[np.ndarray] = None):
         """Returns (counts[nTrans], loglikeSum, loglike[nPairs]); accumulates into ``counts`` if given."""

@@ -880,12 +880,14 @@ int mb_profile_pairs_viterbi(mb_profile_pairs *p, double *loglike, int64_t *path
   return rc;
 }
 
-int mb_profile_pairs_sample(mb_profile_pairs *p, int64_t nSamples, uint64_t seed, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow,
-                            double *pathLogProb, int64_t pathCap) {
-  ApiGuard guard;
+// The two sample calls: plain pairs (merged = false, rowCol unused) and pairs against merged profiles, whose lanes also write the
+// column every row took.  Lengths and log probabilities arrive in slot order; path slots and rowCol are packed in pair order.
+static int pair_profile_sample(mb_profile_pairs *p, bool merged, int64_t nSamples, uint64_t seed, double *loglike, int64_t *pathOff, uint32_t *pathEdges,
+                               int32_t *pathRow, int32_t *rowCol, double *pathLogProb, int64_t pathCap) {
   if (!p || !pathOff || !pathEdges) { set_error("null argument"); return 1; }
   g_last_ms = 0.0; g_last_launches = 0;
-  if (p->nCols) { set_error("sampling takes plain profiles"); return 1; }
+  if (!merged && p->nCols) { set_error("sampling takes plain profiles"); return 1; }
+  if (merged && !p->nCols) { set_error("merged sampling takes merged profiles"); return 1; }
   if (nSamples < 1) { set_error("nSamples must be at least 1"); return 1; }
   double need = 0.0;
   for (long long k = 0; k < p->n; ++k) need += (double)pp_path_bound(p, k);
@@ -897,7 +899,10 @@ int mb_profile_pairs_sample(mb_profile_pairs *p, int64_t nSamples, uint64_t seed
   }
   // a pair costs its lattice, and per sample a path slot (an edge and a row per entry), a length and a log probability
   std::vector<Chunk> chunks;
-  auto bytes = [&](long long k) { return pp_cell_bytes(p, k) + (double)nSamples * (8.0 * (double)pp_path_bound(p, k) + 16.0); };
+  // (merged: also the ring of the fill's exclusion vectors where it does not fit LDS, and per sample a column for every row)
+  auto bytes = [&](long long k) {
+    return pp_cell_bytes(p, k) + pp_ring_bytes(p, k, false) + (double)nSamples * (8.0 * (double)pp_path_bound(p, k) + 16.0 + (merged ? 4.0 * (double)pp_rows(p, k) : 0.0));
+  };
   if (!lattice_chunks(p->n, "pair", bytes, chunks)) return 1;
   for (const Chunk &c : chunks)
     if ((double)(c.p1 - c.p0) * (double)nSamples > 2147483647.0) { set_error("too many samples in one chunk: pairs times nSamples exceeds 2^31 - 1 lanes"); return 1; }
@@ -913,7 +918,11 @@ int mb_profile_pairs_sample(mb_profile_pairs *p, int64_t nSamples, uint64_t seed
   PairWhere where;
   int rc = for_chunks<PairProfPlan>(chunks, pp_build(p, false, where), [&](const Chunk &c, PairProfPlan &pl, Timer &tm) {
     const long long np = c.p1 - c.p0, lanes = np * nS, entries = pl.paths * nS;
+    const long long row0 = p->rowOff[(size_t)c.p0], colEntries = merged ? (p->rowOff[(size_t)c.p1] - row0) * nS : 0;
     double *pool = ws_array<double>(0, pl.cells);
+    double *scratch = pl.ring ? (double *)ws_get(1, (size_t)pl.ring * sizeof(double)) : nullptr;
+    int32_t *d_rc = merged ? ws_array<int32_t>(7, colEntries) : nullptr;
+    if ((pl.ring && !scratch) || (merged && !d_rc)) return 1;
     uint32_t *d_e = ws_array<uint32_t>(3, entries);
     int32_t *d_r = ws_array<int32_t>(4, entries);
     long long *d_len = ws_array<long long>(5, lanes);
@@ -926,10 +935,17 @@ int mb_profile_pairs_sample(mb_profile_pairs *p, int64_t nSamples, uint64_t seed
                !hip_ok(hipStreamSynchronize(g_stream), "H2D pair indices"))) return 1;
     {
       Timed t(tm, pl.launches());
-      if (pp_launch_fwd(p, MB_FORWARD, true, pl, pool, nullptr, d_ll + c.p0)) return 1;
-      if (launch_profile_pair_sample(p->m, pl.d.p, (int)pl.nPlain, nS, d_idx.p, seed, p->d_in, p->d_logP, pool, d_e, d_r, d_len, d_lq, g_stream)) return 1;
-      if (launch_profile_pair_sample(p->m, pl.e.p, pp_env_tables(p), (int)pl.nEnv, nS, d_idx.p + pl.nPlain, seed, p->d_in, p->d_logP, pool, d_e, d_r,
-                                     d_len + pl.nPlain * nS, d_lq + pl.nPlain * nS, g_stream)) return 1;
+      if (pp_launch_fwd(p, MB_FORWARD, true, pl, pool, scratch, d_ll + c.p0)) return 1;
+      if (merged) {
+        if (launch_profile_pair_merge_sample(p->m, pp_map(p), pl.d.p, (int)pl.nPlain, nS, d_idx.p, seed, p->d_in, p->d_logP, pool, row0, d_e, d_r, d_rc, d_len, d_lq,
+                                             g_stream)) return 1;
+        if (launch_profile_pair_merge_sample(p->m, pp_map(p), pl.e.p, pp_env_tables(p), (int)pl.nEnv, nS, d_idx.p + pl.nPlain, seed, p->d_in, p->d_logP, pool, row0, d_e,
+                                             d_r, d_rc, d_len + pl.nPlain * nS, d_lq + pl.nPlain * nS, g_stream)) return 1;
+      } else {
+        if (launch_profile_pair_sample(p->m, pl.d.p, (int)pl.nPlain, nS, d_idx.p, seed, p->d_in, p->d_logP, pool, d_e, d_r, d_len, d_lq, g_stream)) return 1;
+        if (launch_profile_pair_sample(p->m, pl.e.p, pp_env_tables(p), (int)pl.nEnv, nS, d_idx.p + pl.nPlain, seed, p->d_in, p->d_logP, pool, d_e, d_r,
+                                       d_len + pl.nPlain * nS, d_lq + pl.nPlain * nS, g_stream)) return 1;
+      }
     }
     // lengths and log probabilities landed in slot order, the path slots are packed in pair order
     hlen.resize((size_t)std::max<long long>(lanes, 1)); hlq.resize(hlen.size());
@@ -937,6 +953,8 @@ int mb_profile_pairs_sample(mb_profile_pairs *p, int64_t nSamples, uint64_t seed
     if (lanes && (d2h_large(hlen.data(), d_len, (size_t)lanes * sizeof(long long)) || d2h_large(hlq.data(), d_lq, (size_t)lanes * sizeof(double)))) return 1;
     if (!lanes && !hip_ok(hipStreamSynchronize(g_stream), "sample launch")) return 1;
     if (entries && (d2h_large(he.data(), d_e, (size_t)entries * sizeof(uint32_t)) || (pathRow && d2h_large(hr.data(), d_r, (size_t)entries * sizeof(int32_t))))) return 1;
+    // (the chunk's block of rowCol is already in pair order: rows of the object from row0 on, nSamples lines per pair)
+    if (rowCol && colEntries && d2h_large(rowCol + (row0 - p->rowOff[0]) * nS, d_rc, (size_t)colEntries * sizeof(int32_t))) return 1;
     long long base = 0;
     for (long long k = 0; k < np; ++k) {
       const long long bound = pp_path_bound(p, c.p0 + k), at = pl.slot[(size_t)k] * nS;
@@ -954,8 +972,21 @@ int mb_profile_pairs_sample(mb_profile_pairs *p, int64_t nSamples, uint64_t seed
     return 0;
   });
   if (!rc && loglike) rc = fetch_loglike(loglike, d_ll, p->n, &where);
-  g_last_kernel = p->hasEnv ? "k_profile_pair_env_sample" : "k_profile_pair_sample";
+  if (merged) g_last_kernel = p->hasEnv ? "k_profile_pair_merge_env_sample" : "k_profile_pair_merge_sample";
+  else g_last_kernel = p->hasEnv ? "k_profile_pair_env_sample" : "k_profile_pair_sample";
   return rc;
+}
+
+int mb_profile_pairs_sample(mb_profile_pairs *p, int64_t nSamples, uint64_t seed, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow,
+                            double *pathLogProb, int64_t pathCap) {
+  ApiGuard guard;
+  return pair_profile_sample(p, false, nSamples, seed, loglike, pathOff, pathEdges, pathRow, nullptr, pathLogProb, pathCap);
+}
+
+int mb_profile_pairs_sample_merged(mb_profile_pairs *p, int64_t nSamples, uint64_t seed, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow,
+                                   int32_t *rowCol, double *pathLogProb, int64_t pathCap) {
+  ApiGuard guard;
+  return pair_profile_sample(p, true, nSamples, seed, loglike, pathOff, pathEdges, pathRow, rowCol, pathLogProb, pathCap);
 }
 
 int mb_profile_pairs_counts(mb_profile_pairs *p, double *counts, double *loglikeSum, double *loglike) {

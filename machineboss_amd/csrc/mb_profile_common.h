@@ -1,6 +1,7 @@
 // mb_profile_common.h -- what the profile sweeps share (mb_profile.hip, mb_profile_merge.hip, mb_profile_pair.hip,
 // mb_profile_pair_merge.hip, mb_profile_two.hip, mb_profile_two_merge.hip, mb_profile_post.hip): the reduction of a sweep's mode, the LDS a ring may take, the lanes of a workgroup, the
-// accumulator of the posterior counts and the add of the row posteriors.  Device code: included by .hip files only.
+// accumulator of the posterior counts, the add of the row posteriors, and the generator and the draw of the path samplers
+// (k_profile_pair_sample, k_profile_pair_merge_sample).  Device code: included by .hip files only.
 #pragma once
 #include <algorithm>
 
@@ -73,5 +74,35 @@ __device__ __forceinline__ void rowpost_add(double *tab, int bin, double v, bool
     if (v != 0.0) atomicAdd(&tab[bin], v);
   }
 }
+
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11) and the 53-bit uniform of its first two words,
+// the recipe of the Mt19937 variates: ((x0 >> 5) * 2^26 + (x1 >> 6)) * 2^-53.  profile.philox4x32 / sample_uniform are the same text
+// in numpy.
+__device__ __forceinline__ double philox_uniform(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0, hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return ((double)(c0 >> 5) * 67108864.0 + (double)(c1 >> 6)) * (1.0 / 9007199254740992.0);
+}
+
+// One candidate of a sampling decision: p = exp(term - cur) joins the running sum; the first candidate whose sum passes u is taken,
+// and the last one with p > 0 is remembered for the draw that rounding left above the total.
+struct SampleDraw {
+  double u, cur, acc = 0.0, term = 0.0;
+  int a = -1, src = -1, kind = -1;      // the taken candidate: its CSR entry, source state and kind (the caller's numbering)
+  bool done = false;
+  __device__ __forceinline__ SampleDraw(double u, double cur) : u(u), cur(cur) {}
+  __device__ __forceinline__ void offer(double t, int kind_, int a_, int src_) {
+    if (done) return;
+    const double p = exp(t - cur);
+    acc += p;
+    if (p > 0.0) { term = t; kind = kind_; a = a_; src = src_; }
+    done = u < acc;      // (p > 0 here: the sum has just grown past u)
+  }
+};
 
 }  // namespace mb

@@ -56,6 +56,14 @@ int launch_profile_pair_merge_traceback(const mb_machine *m, MergeMap mm, const 
                                         const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len,
                                         hipStream_t st);
 
+// Posterior path samples over the n pairs' materialised sum lattices (k_profile_pair_merge_sample): nSamples lanes per pair, n *
+// nSamples <= 2^31 - 1.  pairIdx[n]: each pair's index in the object, the `k` of the generator's counter.  Sample j of the pair at
+// d[s] writes len / logq at s * nSamples + j, its path at (d[s].pathBase * nSamples + j * bound), bound = profile_pair_path_bound of
+// the pair, and the column every row took at rowCol[(d[s].rowBase - rowBase0) * nSamples + j * nRows + r].
+int launch_profile_pair_merge_sample(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, int nSamples, const long long *pairIdx, unsigned long long seed,
+                                     const int *inTok, const double *logP, const double *pool, long long rowBase0, uint32_t *edges, int32_t *rows, int32_t *rowCol,
+                                     long long *len, double *logq, hipStream_t st);
+
 // the launchers above over pairs under an envelope (lds, maxItems: of the envelope rings and diagonals)
 int launch_profile_pair_merge_fwd(const mb_machine *m, MergeMap mm, int mode, bool mat, const PairEnvDesc *d, const PairEnvTables &t, int n, size_t lds,
                                   long long maxItems, const int *inTok, const double *logP, double *pool, double *scratch,
@@ -70,5 +78,8 @@ int launch_profile_pair_merge_rowpost(const mb_machine *m, MergeMap mm, const Pa
 int launch_profile_pair_merge_traceback(const mb_machine *m, MergeMap mm, const PairEnvDesc *d, const PairEnvTables &t, int n, const int *inTok,
                                         const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len,
                                         hipStream_t st);
+int launch_profile_pair_merge_sample(const mb_machine *m, MergeMap mm, const PairEnvDesc *d, const PairEnvTables &t, int n, int nSamples, const long long *pairIdx,
+                                     unsigned long long seed, const int *inTok, const double *logP, const double *pool, long long rowBase0, uint32_t *edges,
+                                     int32_t *rows, int32_t *rowCol, long long *len, double *logq, hipStream_t st);
 
 }  // namespace mb

@@ -609,6 +609,135 @@ __global__ void k_profile_pair_merge_traceback(DevMachine m, MergeMap mm, const 
   len[pair] = cnt;
 }
 
+// Posterior path samples over a materialised SUM lattice (docs/profile_tapes.md, "Posterior path samples of pairs against a merged
+// profile"), one lane per (pair slot, sample) as k_profile_pair_sample (mb_profile_pair.hip): lane id serves slot id / nSamples,
+// sample id % nSamples.  Decision 0 takes the end plane among W[I][L][.][S-1], planes ascending, against the likelihood folded as
+// k_profile_pair_merge_fwd folds it.  Then back to N[0][0][0][0]: at a W cell "stay" (N), the input-only edges, the silent edges, all
+// on the cell's plane; at N[.][r][0], r > 0, the blank out of every plane ascending; at N[.][r][c] the repeat, then the match edges
+// and then the output-only edges of colTok[c] in `incoming` order, every edge once per source plane k != c ascending -- the lattice
+// holds W, not the fill's X, so the (edge, plane) pairs are the candidates and their p sum to 1 up to the rounding of that
+// regrouping; the last candidate with p > 0 takes what is left.  SampleDraw's kind carries the candidate's kind in its low two bits
+// and the source plane above them.  rowCol[(rowBase - rowBase0) * nSamples + j * L + r]: the column row r took (0: the blank), -1 in
+// every row of a dead pair.  The uniform of decision t of sample j of pair k (pairIdx[slot]) is philox_uniform(t, j, k, seed).
+// Paths, len and logq are k_profile_pair_sample's; a candidate whose source cell lies outside the lattice is left out.
+template <bool ENV>
+__global__ __launch_bounds__(64) void k_profile_pair_merge_sample(DevMachine m, MergeMap mm, const typename PairMergeLattice<true, ENV>::Desc *__restrict__ descs,
+                                                                  typename PairMergeLattice<true, ENV>::Tables t, long long nLanes, int nSamples,
+                                                                  const long long *__restrict__ pairIdx, unsigned long long seed, const int *__restrict__ inTok,
+                                                                  const double *__restrict__ logP, const double *__restrict__ pool, long long rowBase0,
+                                                                  uint32_t *edges, int32_t *rows, int32_t *rowCol, long long *len, double *logq) {
+  const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= nLanes) return;
+  const int slot = (int)(id / nSamples), j = (int)(id - (long long)slot * nSamples);
+  const auto pd = descs[slot];
+  const unsigned long long k = (unsigned long long)pairIdx[slot];
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), c2 = (uint32_t)k, c3 = (uint32_t)(k >> 32);
+  const int S = m.S, K = m.K, C = m.nOut + 1, PL = mm.nCols + 1, I = pd.nIn, L = pd.nRows;
+  const int *x = inTok + pd.inBase;
+  const double *P = logP + pd.rowBase * PL;
+  const PairMergeLattice<true, ENV> lat(pd, t, const_cast<double *>(pool) + pd.cellBase, nullptr, S, PL);
+  const long long cap = I + L + (long long)(I + L + 1) * (m.nLevF - 1);
+  uint32_t *pe = edges + pd.pathBase * nSamples + (long long)j * cap;
+  int32_t *pr = rows + pd.pathBase * nSamples + (long long)j * cap;
+  int32_t *rc = rowCol + (pd.rowBase - rowBase0) * nSamples + (long long)j * L;
+  int i = I, r = L, q = S - 1, layer = 1, p = 0;
+  long long cnt = 0;
+  uint32_t dec = 0;
+  double lq = 0.0;
+  {
+    const double *We = lat.nw(I, L, 1) + q;
+    double LL = We[0];
+    for (int pl = 1; pl < PL; ++pl) LL = lse2_exact(LL, We[pl * S]);
+    if (!(LL > -INFINITY)) {
+      for (int e = 0; e < L; ++e) rc[e] = -1;
+      len[id] = -1; logq[id] = -INFINITY;
+      return;
+    }
+    SampleDraw d(philox_uniform(dec++, (uint32_t)j, c2, c3, k0, k1), LL);
+    for (int pl = 0; pl < PL && !d.done; ++pl) d.offer(We[pl * S], 0, 0, pl);
+    if (d.kind < 0) { len[id] = -3; logq[id] = lq; return; }
+    lq += d.term - d.cur;
+    p = d.src;
+  }
+  for (;;) {
+    const int xRow = i > 0 ? q * K + x[i - 1] * C : 0;
+    if (layer == 1) {
+      const double *W = lat.nw(i, r, 1) + p * S;
+      SampleDraw d(philox_uniform(dec++, (uint32_t)j, c2, c3, k0, k1), W[q]);
+      d.offer(lat.nw(i, r, 0)[p * S + q], 0, 0, q);
+      if (i > 0 && lat.inside(i - 1, r)) {
+        const double *Wl = lat.nw(i - 1, r, 1) + p * S;
+        const int a1 = m.inOff[xRow + 1];
+        for (int a = m.inOff[xRow]; a < a1 && !d.done; ++a) d.offer(Wl[m.inSrc[a]] + m.inW[a], 1, a, (int)m.inSrc[a]);
+      }
+      const int a1 = m.inOff[q * K + 1];
+      for (int a = m.inOff[q * K]; a < a1 && !d.done; ++a) {
+        const int s = (int)m.inSrc[a];
+        if (s < q) d.offer(W[s] + m.inW[a], 2, a, s);
+      }
+      if (d.kind < 0) { len[id] = -3; logq[id] = lq; return; }
+      lq += d.term - d.cur;
+      if (d.kind == 0) { layer = 0; continue; }
+      if (cnt >= cap) { len[id] = -2; logq[id] = lq; return; }
+      pe[cnt] = m.inEid[d.a]; pr[cnt] = r; ++cnt;
+      if (d.kind == 1) --i;
+      q = d.src;
+    } else {
+      if (r == 0) { if (i != 0 || q != 0 || p != 0) { len[id] = -3; logq[id] = lq; return; } break; }
+      const double *Pr = P + (long long)(r - 1) * PL;
+      SampleDraw d(philox_uniform(dec++, (uint32_t)j, c2, c3, k0, k1), lat.nw(i, r, 0)[p * S + q]);
+      const bool up = lat.inside(i, r - 1);
+      const double *Np = lat.nw(i, r - 1, 0);      // (an address alone: read only where the cell is inside)
+      if (p == 0) {
+        if (up)
+          for (int pl = 0; pl < PL && !d.done; ++pl) d.offer(Np[pl * S + q] + Pr[0], 0, 0, pl);
+        if (d.kind < 0) { len[id] = -3; logq[id] = lq; return; }
+        lq += d.term - d.cur;
+        --r;
+        rc[r] = 0;
+        p = d.src;
+        continue;
+      }
+      const double w = Pr[p];
+      const int tok = mm.colTok[p - 1];
+      if (up) d.offer(Np[p * S + q] + w, 0, 0, q);
+      if (i > 0 && lat.inside(i - 1, r - 1)) {
+        const double *Wd = lat.nw(i - 1, r - 1, 1);
+        const int a1 = m.inOff[xRow + tok + 1];
+        for (int a = m.inOff[xRow + tok]; a < a1 && !d.done; ++a) {
+          const int s = (int)m.inSrc[a];
+          for (int pl = 0; pl < PL && !d.done; ++pl)
+            if (pl != p) d.offer((Wd[pl * S + s] + m.inW[a]) + w, 1 | (pl << 2), a, s);
+        }
+      }
+      if (up) {
+        const double *Wu = lat.nw(i, r - 1, 1);
+        const int a1 = m.inOff[q * K + tok + 1];
+        for (int a = m.inOff[q * K + tok]; a < a1 && !d.done; ++a) {
+          const int s = (int)m.inSrc[a];
+          for (int pl = 0; pl < PL && !d.done; ++pl)
+            if (pl != p) d.offer((Wu[pl * S + s] + m.inW[a]) + w, 2 | (pl << 2), a, s);
+        }
+      }
+      if (d.kind < 0) { len[id] = -3; logq[id] = lq; return; }
+      lq += d.term - d.cur;
+      --r;
+      rc[r] = p;
+      if (d.kind == 0) continue;      // the repeat: the walk stays in N on its plane
+      if (cnt >= cap) { len[id] = -2; logq[id] = lq; return; }
+      pe[cnt] = m.inEid[d.a]; pr[cnt] = r; ++cnt;
+      if ((d.kind & 3) == 1) --i;
+      q = d.src; p = d.kind >> 2; layer = 1;
+    }
+  }
+  for (long long u = 0, v = cnt - 1; u < v; ++u, --v) {
+    const uint32_t e = pe[u]; pe[u] = pe[v]; pe[v] = e;
+    const int32_t w = pr[u]; pr[u] = pr[v]; pr[v] = w;
+  }
+  len[id] = cnt;
+  logq[id] = lq;
+}
+
 // beyond the default 64 KiB the kernels must be told; asked for once, and only when a ring needs it
 static bool ppm_allow_lds(size_t lds) {
   static size_t ldsAllowed = 64 * 1024;
@@ -722,6 +851,27 @@ int launch_profile_pair_merge_traceback(const mb_machine *m, MergeMap mm, const 
                                         const double *logP, const double *pool, uint32_t *edges, int32_t *rows, long long *len,
                                         hipStream_t st) {
   return ppm_traceback<true>(m, mm, d, t, n, inTok, logP, pool, edges, rows, len, st);
+}
+
+template <bool ENV>
+static int ppm_sample(const mb_machine *m, MergeMap mm, const typename PairMergeLattice<true, ENV>::Desc *d, typename PairMergeLattice<true, ENV>::Tables t, int n,
+                      int nSamples, const long long *pairIdx, unsigned long long seed, const int *inTok, const double *logP, const double *pool, long long rowBase0,
+                      uint32_t *edges, int32_t *rows, int32_t *rowCol, long long *len, double *logq, hipStream_t st) {
+  if (n <= 0) return 0;
+  const long long nLanes = (long long)n * nSamples;      // (the caller keeps it within 2^31 - 1)
+  k_profile_pair_merge_sample<ENV><<<(unsigned)((nLanes + 63) / 64), 64, 0, st>>>(m->dev, mm, d, t, nLanes, nSamples, pairIdx, seed, inTok, logP, pool, rowBase0, edges,
+                                                                                rows, rowCol, len, logq);
+  return hip_ok(hipGetLastError(), ENV ? "k_profile_pair_merge_env_sample" : "k_profile_pair_merge_sample") ? 0 : 1;
+}
+int launch_profile_pair_merge_sample(const mb_machine *m, MergeMap mm, const PairProfDesc *d, int n, int nSamples, const long long *pairIdx, unsigned long long seed,
+                                     const int *inTok, const double *logP, const double *pool, long long rowBase0, uint32_t *edges, int32_t *rows, int32_t *rowCol,
+                                     long long *len, double *logq, hipStream_t st) {
+  return ppm_sample<false>(m, mm, d, {}, n, nSamples, pairIdx, seed, inTok, logP, pool, rowBase0, edges, rows, rowCol, len, logq, st);
+}
+int launch_profile_pair_merge_sample(const mb_machine *m, MergeMap mm, const PairEnvDesc *d, const PairEnvTables &t, int n, int nSamples, const long long *pairIdx,
+                                     unsigned long long seed, const int *inTok, const double *logP, const double *pool, long long rowBase0, uint32_t *edges,
+                                     int32_t *rows, int32_t *rowCol, long long *len, double *logq, hipStream_t st) {
+  return ppm_sample<true>(m, mm, d, t, n, nSamples, pairIdx, seed, inTok, logP, pool, rowBase0, edges, rows, rowCol, len, logq, st);
 }
 
 }  // namespace mb

@@ -194,7 +194,7 @@ _M32 = 0xffffffff
 
 def philox4x32(counter: Sequence[int], key: Sequence[int]) -> Tuple[int, int, int, int]:
     """Philox4x32-10 (Salmon et al., SC'11): four 32-bit counter words and two key words to four output words.  The restatement of
-    philox_uniform's rounds in mb_profile_pair.hip (docs/profile_tapes.md, "Posterior path samples")."""
+    philox_uniform's rounds in mb_profile_common.h (docs/profile_tapes.md, "Posterior path samples")."""
     c0, c1, c2, c3 = (int(c) & _M32 for c in counter)
     k0, k1 = (int(k) & _M32 for k in key)
     for _ in range(10):
@@ -1227,6 +1227,160 @@ class PairMergedProfileDP(PairProfileDP):
             tie("plane", len(src))
             edges.append(e); rows.append(r); q = s; i = ni; p = src[0]; layer = 1
         return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32)
+
+    def sampleCandidates(self, x, P, N, W, inside, i: int, r: int, p: int, q: int, layer: int):
+        """The candidates of the sampling decision at (i, r, plane p, state q) of ``layer`` over the sum lattice (N, W), as
+        (kind, edge id or -1, source state, source plane, term), in the order of docs/profile_tapes.md, "Posterior path samples of
+        pairs against a merged profile".  layer 2, the end: W[I][L][k][S-1], planes ascending.  layer 1, a W cell: "stay" (N), the
+        input-only edges, the silent edges, each in `incoming` order, all on plane p.  layer 0, an N cell with r > 0: on plane 0 the
+        blank out of every plane k ascending; on plane c the repeat, then the match edges in `incoming` order, then the output-only
+        edges in `incoming` order, every edge once per source plane k != c ascending -- the fill's X taken apart.  ``inside``:
+        envelopeRows() as sets; a candidate whose source cell lies outside is left out."""
+        ok = (lambda si, sr: True) if inside is None else (lambda si, sr: sr in inside[si])
+        cand = []
+        if layer == 2:
+            return [("end", -1, q, k, float(W[i, r, k, q])) for k in range(self.PL)]
+        if layer == 1:
+            cand.append(("stay", -1, q, p, float(N[i, r, p, q])))
+            if i and ok(i - 1, r):
+                e, s, d, w, _o = self.ins[x[i - 1]]
+                cand += [("ins", int(e[k]), int(s[k]), p, float(W[i - 1, r, p, s[k]] + w[k])) for k in np.nonzero(d == q)[0]]
+            cand += [("silent", int(self.sId[k]), int(self.sS[k]), p, float(W[i, r, p, self.sS[k]] + self.sW[k])) for k in self.inSil[q]]
+            return cand
+        Pr = P[r - 1]
+        up = ok(i, r - 1)
+        if p == 0:
+            if up:
+                cand += [("blank", -1, q, k, float(N[i, r - 1, k, q] + Pr[0])) for k in range(self.PL)]
+            return cand
+        oth = [k for k in range(self.PL) if k != p]
+        tok = self.colTok[p - 1]
+        if up:
+            cand.append(("repeat", -1, q, p, float(N[i, r - 1, p, q] + Pr[p])))
+        if i and ok(i - 1, r - 1):
+            e, s, d, w, o = self.match[x[i - 1]]
+            for a in np.nonzero((d == q) & (o == tok))[0]:
+                cand += [("match", int(e[a]), int(s[a]), k, float((W[i - 1, r - 1, k, s[a]] + w[a]) + Pr[p])) for k in oth]
+        if up:
+            for a in self.inEmit[q]:
+                if self.eO[a] == tok:
+                    cand += [("emit", int(self.eId[a]), int(self.eS[a]), k, float((W[i, r - 1, k, self.eS[a]] + self.eW[a]) + Pr[p])) for k in oth]
+        return cand
+
+    def samplePaths(self, x, P, nSamples: int, seed: int = 0, pair: int = 0, env=None, margins: Optional[list] = None):
+        """(loglike, [(edges, rows, rowCol, logq), ...]): ``nSamples`` lattice paths drawn from the posterior by a stochastic
+        traceback over forward(x, P, env=env) -- the yardstick of k_profile_pair_merge_sample (docs/profile_tapes.md, "Posterior
+        path samples of pairs against a merged profile").  Decision 0 picks the end plane among W[I][L][.][S-1] against loglike;
+        then every visit of a W cell, or of an N cell with r > 0, is one decision among sampleCandidates(): p_c = exp(term_c -
+        cell), acc adds them in order from 0.0, the first c with u < acc is taken, else the last c with p_c > 0.  u =
+        sample_uniform(seed, pair, j, t) for decision t of sample j.  logq sums term - cell over the decisions: the lattice path's
+        log weight minus loglike.  edges and rows are as viterbi()'s; rowCol[r] is the column row r took (0: the blank; c: column
+        c, fresh or repeated), which with the edges determines the lattice path.  A -inf pair gives empty paths, rowCol = -1 and
+        logq = -inf.  ``margins`` (a list) receives per decision the least |u - acc_c| over all partial sums acc_c of the decision."""
+        x, P = self._checkPair(x, P)
+        ll, N, W = self.forward(x, P) if env is None else self.forward(x, P, env=env)
+        inside = self.envelopeRows(env, len(x), len(P))
+        if inside is not None:
+            inside = [set(rs) for rs in inside]
+        out = []
+        for j in range(int(nSamples)):
+            edges: List[int] = []; rows: List[int] = []
+            rowCol = np.full(len(P), -1, np.int32)
+            if not ll > _NEG:
+                out.append((np.zeros(0, np.uint32), np.zeros(0, np.int32), rowCol, _NEG))
+                continue
+            i, r, p, q, layer, t, logq = len(x), len(P), 0, self.S - 1, 2, 0, 0.0
+            while layer or r > 0:
+                cur = ll if layer == 2 else float(W[i, r, p, q] if layer == 1 else N[i, r, p, q])
+                cand = self.sampleCandidates(x, P, N, W, inside, i, r, p, q, layer)
+                u = sample_uniform(seed, pair, j, t)
+                t += 1
+                acc, pick, last, margin = 0.0, None, None, math.inf
+                for c in cand:
+                    pc = math.exp(c[4] - cur) if c[4] > _NEG else 0.0
+                    acc += pc
+                    margin = min(margin, abs(u - acc))
+                    if pc > 0.0:
+                        last = c
+                    if pick is None and u < acc:
+                        pick = c
+                if pick is None:
+                    pick = last
+                if pick is None:
+                    raise MachineError("samplePaths: no candidate with a positive probability")
+                if margins is not None:
+                    margins.append(margin)
+                kind, e, s, k, term = pick
+                logq += term - cur
+                if kind == "end":
+                    p = k; layer = 1
+                elif kind == "stay":
+                    layer = 0
+                elif kind in ("ins", "silent"):
+                    edges.append(e); rows.append(r); q = s
+                    i -= kind == "ins"
+                else:
+                    r -= 1
+                    rowCol[r] = p
+                    if kind in ("match", "emit"):
+                        edges.append(e); rows.append(r); q = s; layer = 1
+                        i -= kind == "match"
+                    p = k
+            assert i == 0 and q == 0 and p == 0
+            out.append((np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32), rowCol, logq))
+        return ll, out
+
+    def pathWeight(self, x, P, edges, rows, rowCol) -> float:
+        """The log weight of the lattice path (edges, rows, rowCol) replayed from the definition, without a lattice: the weights of
+        its edges plus P[r][rowCol[r]] of every row; -inf where it is no lattice path of (x, P).  The edges chain from state 0 to
+        S - 1 and read x in order; silent edges climb (s < d); rows[k] is the row an emitting edge consumed, else the rows consumed
+        when the edge fired, so the stamps never fall.  A row no edge consumed was taken on arrival (the blank and the repeat read
+        N, never W): once an output-less edge has fired at a stamp, the next edge carries the same stamp, and the walk ends there
+        only at L.
+        The labels: a row with label c >= 1 that an edge consumed needs the edge to write colTok[c - 1] and the row before it
+        ("no row yet" counts as 0) a label other than c; one that no edge consumed needs the row before it to carry c; label 0 goes
+        with no edge."""
+        x, P = self._checkPair(x, P)
+        em = self.em
+        I, L = len(x), len(P)
+        edges = [int(e) for e in np.asarray(edges).reshape(-1)]
+        rows = [int(v) for v in np.asarray(rows).reshape(-1)]
+        rowCol = [int(v) for v in np.asarray(rowCol).reshape(-1)]
+        if len(rows) != len(edges) or len(rowCol) != L or any(c < 0 or c > self.nCols for c in rowCol):
+            return _NEG
+        # at: the rows consumed so far; waiting: the walk has left N for W there, so the next row needs an edge
+        w, q, i, at, waiting = 0.0, 0, 0, 0, False
+        by: List[Optional[int]] = [None] * L    # the edge that consumed each row
+        for e, r in zip(edges, rows):
+            if e < 0 or e >= em.nTransitions or int(em.src[e]) != q:
+                return _NEG
+            it, ot, d = int(em.inTok[e]), int(em.outTok[e]), int(em.dst[e])
+            if r < at or (waiting and r != at) or r > L - (1 if ot else 0):      # (the rows at..r-1 were taken on arrival)
+                return _NEG
+            if it:
+                if i >= I or x[i] != it:
+                    return _NEG
+                i += 1
+            elif not ot and not q < d:
+                return _NEG
+            if ot:
+                by[r] = e
+            at, waiting = (r + 1, False) if ot else (r, True)
+            w += float(em.logWeight[e])
+            q = d
+        if q != self.S - 1 or i != I or (waiting and at != L):
+            return _NEG
+        prev = 0
+        for r in range(L):
+            c = rowCol[r]
+            if by[r] is None:
+                if c and prev != c:
+                    return _NEG
+            elif c == 0 or int(em.outTok[by[r]]) != int(self.colTok[c - 1]) or prev == c:
+                return _NEG
+            w += float(P[r][c])
+            prev = c
+        return w if w > _NEG else _NEG
 
 
 class TwoProfileDP(PairProfileDP):
