@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "mb_internal.h"
+#include "mb_profile_lattice.h"      // env_overlapping
 
 namespace mb {
 
@@ -128,8 +129,6 @@ struct CountSum {
     if (loglikeSum) *loglikeSum += s;
   }
 };
-
-inline bool env_overlapping(long long s1, long long e1, long long s2, long long e2) { return !(s1 >= e2 || s2 >= e1); }
 
 // argument checks of the profile entry points (mb_profile_api.hip), shared with the prefix search
 bool profile_values_ok(const double *v, long long n);

@@ -644,43 +644,11 @@ static void pp_env_free(mb_profile_pairs *p) {
   p->envBase.clear(); p->diagBase.clear(); p->envCells.clear(); p->envM.clear(); p->h_envStart.clear(); p->h_envEnd.clear();
 }
 
-// The envelopes of a batch on the host, as mb_profile_pairs_set_envelopes and mb_profile_twos_set_envelopes build them: per pair
-// where its rows and its diagonal runs start (-1: none), its cells and its M; the rows, their compact offsets and the runs, packed.
-struct EnvHost {
-  std::vector<long long> envBase, diagBase, envCells, off;
-  std::vector<int> M, st, en, lo, cnt;
-  explicit EnvHost(long long n) : envBase((size_t)n, -1), diagBase((size_t)n, -1), envCells((size_t)n, 0), M((size_t)n, 0) {}
-};
-
-// Pair k's envelope (I input positions, L rows; `rows` entries of st / en) into h.  Checks as mb_batch_set_envelopes (fits,
-// connected) and that neither bound decreases from one row to the next: the sweeps rest on the envelope cells of an anti-diagonal
-// being consecutive.
-static int env_add(EnvHost &h, long long k, long long I, long long L, long long rows, const int32_t *st, const int32_t *en) {
-  if (rows != L + 1) { set_error("Envelope/sequence mismatch"); return 1; }
-  for (long long y = 0; y < rows; ++y)
-    if (st[y] < 0 || en[y] > I + 1 || st[y] > en[y]) { set_error("Envelope/sequence mismatch"); return 1; }
-  bool conn = env_overlapping(st[0], en[0], 0, 1);
-  for (long long y = 1; conn && y < rows; ++y) conn = env_overlapping(st[y - 1], (long long)en[y - 1] + 1, st[y], en[y]);
-  conn = conn && env_overlapping(st[rows - 1], en[rows - 1], I, I + 1);
-  if (!conn) { set_error("Envelope is not connected"); return 1; }
-  for (long long y = 1; y < rows; ++y)
-    if (st[y] < st[y - 1] || en[y] < en[y - 1]) { set_error("Envelope is not monotone"); return 1; }
-  h.envBase[(size_t)k] = (long long)h.st.size(); h.diagBase[(size_t)k] = (long long)h.lo.size();
-  const size_t d0 = h.lo.size();
-  h.lo.resize(d0 + (size_t)(I + L + 1), 0); h.cnt.resize(d0 + (size_t)(I + L + 1), 0);
-  long long cells = 0;
-  for (long long y = 0; y < rows; ++y) {
-    h.st.push_back(st[y]); h.en.push_back(en[y]); h.off.push_back(cells);
-    cells += en[y] - st[y];
-    // row y puts one cell on each of the diagonals st[y] + y .. en[y] - 1 + y; the rows go upwards, so on a diagonal every
-    // later row holds a smaller i than the rows before it: the last one written is the diagonal's first i
-    for (long long i = st[y]; i < en[y]; ++i) { h.lo[d0 + (size_t)(i + y)] = (int)i; ++h.cnt[d0 + (size_t)(i + y)]; }
-  }
-  h.envCells[(size_t)k] = cells;
-  int M = 1;
-  for (size_t d = d0; d < h.lo.size(); ++d) M = std::max(M, h.cnt[d]);
-  h.M[(size_t)k] = M;
-  return 0;
+// EnvHost and env_add, which checks a pair's envelope and builds its tables, are mb_profile_lattice.h's.  A message of env_add: the
+// call is rejected with it.
+static bool env_rejected(const char *msg) {
+  if (msg) set_error(msg);
+  return msg != nullptr;
 }
 static bool env_upload(void **dst, const void *src, size_t bytes) {
   return hip_ok(hipMalloc(dst, std::max<size_t>(bytes, 8)), "hipMalloc(pair envelopes)") && h2d_large(*dst, src, bytes) == 0;
@@ -698,7 +666,7 @@ static int profile_pairs_set_envelopes(mb_profile_pairs *p, bool merged, const i
   for (long long k = 0; k < p->n; ++k) {
     const long long rows = envOff[k + 1] - envOff[k];
     if (rows == 0) continue;   // full: the pair keeps the full geometry of mb_profile_pair.hip
-    if (env_add(h, k, pp_in(p, k), pp_rows(p, k), rows, inStart + envOff[k], inEnd + envOff[k])) return 1;
+    if (env_rejected(env_add(h, k, pp_in(p, k), pp_rows(p, k), rows, inStart + envOff[k], inEnd + envOff[k], false))) return 1;
   }
   if (h.st.empty()) return 0;
   if (ensure_init()) return 1;
@@ -1297,9 +1265,8 @@ static void pt_env_free(mb_profile_twos *p) {
   p->envBase.clear(); p->diagBase.clear(); p->colBase.clear(); p->envCells.clear(); p->envM.clear();
 }
 
-// The checks and the row tables are those of the pairs (env_add).  If any pair has an envelope every pair gets one, the full
-// envelope where none was given; then the transposed envelope: per input row i the run colStart[i] .. colEnd[i] - 1 of output rows
-// whose interval holds i (a run, because neither bound decreases) and colOff[i], the cells of the input rows before.  A rejected
+// The checks and the row tables are those of the pairs (env_add), with the transposed envelope (colStart, colEnd, colOff) as well.
+// If any pair has an envelope every pair gets one, the full envelope where none was given.  A rejected
 // call leaves the pairs without envelopes.  merged: the call came through the merged pairs' own entry; the merged kernels take the
 // same tables.
 static int profile_twos_set_envelopes(mb_profile_twos *p, bool merged, const int64_t *envOff, const int32_t *inStart, const int32_t *inEnd) {
@@ -1311,33 +1278,24 @@ static int profile_twos_set_envelopes(mb_profile_twos *p, bool merged, const int
   if (p->nCols && !merged) { set_error("envelopes take plain profiles"); return 1; }
   if (!inStart || !inEnd) { set_error("null argument"); return 1; }
   EnvHost h(p->n);
-  std::vector<long long> colBase((size_t)p->n, 0), cOff;
-  std::vector<int> cSt, cEn, fullSt, fullEn;
+  std::vector<int> fullSt, fullEn;
   for (long long k = 0; k < p->n; ++k) {
     const long long rows = envOff[k + 1] - envOff[k], K = pt_in(p, k), L = pt_rows(p, k);
     if (rows) {
-      if (env_add(h, k, K, L, rows, inStart + envOff[k], inEnd + envOff[k])) return 1;
+      if (env_rejected(env_add(h, k, K, L, rows, inStart + envOff[k], inEnd + envOff[k], true))) return 1;
     } else {
       fullSt.assign((size_t)L + 1, 0); fullEn.assign((size_t)L + 1, (int)K + 1);
-      if (env_add(h, k, K, L, L + 1, fullSt.data(), fullEn.data())) return 1;
+      if (env_rejected(env_add(h, k, K, L, L + 1, fullSt.data(), fullEn.data(), true))) return 1;
     }
     if ((double)h.M[(size_t)k] * p->m->S * (p->nCols + 1) > 2147483647.0) { set_error("pair " + std::to_string(k) + ": an anti-diagonal of the lattice has more than 2^31 cells"); return 1; }
-    const int *st = h.st.data() + h.envBase[(size_t)k], *en = h.en.data() + h.envBase[(size_t)k];
-    const size_t c0 = cSt.size();
-    colBase[(size_t)k] = (long long)c0;
-    cSt.resize(c0 + (size_t)K + 1, 0); cEn.resize(c0 + (size_t)K + 1, 0); cOff.resize(c0 + (size_t)K + 1, 0);
-    for (long long r = L; r >= 0; --r)      // (downwards: the last row written to an input row is its first)
-      for (long long i = st[r]; i < en[r]; ++i) { cSt[c0 + (size_t)i] = (int)r; if (!cEn[c0 + (size_t)i]) cEn[c0 + (size_t)i] = (int)r + 1; }
-    long long cells = 0;
-    for (long long i = 0; i <= K; ++i) { cOff[c0 + (size_t)i] = cells; cells += cEn[c0 + (size_t)i] - cSt[c0 + (size_t)i]; }
   }
   if (ensure_init()) return 1;
   if (!env_upload((void **)&p->d_envStart, h.st.data(), h.st.size() * sizeof(int)) || !env_upload((void **)&p->d_envEnd, h.en.data(), h.en.size() * sizeof(int)) ||
       !env_upload((void **)&p->d_envOff, h.off.data(), h.off.size() * sizeof(long long)) || !env_upload((void **)&p->d_diagLo, h.lo.data(), h.lo.size() * sizeof(int)) ||
-      !env_upload((void **)&p->d_diagCnt, h.cnt.data(), h.cnt.size() * sizeof(int)) || !env_upload((void **)&p->d_colStart, cSt.data(), cSt.size() * sizeof(int)) ||
-      !env_upload((void **)&p->d_colEnd, cEn.data(), cEn.size() * sizeof(int)) || !env_upload((void **)&p->d_colOff, cOff.data(), cOff.size() * sizeof(long long)) ||
+      !env_upload((void **)&p->d_diagCnt, h.cnt.data(), h.cnt.size() * sizeof(int)) || !env_upload((void **)&p->d_colStart, h.cSt.data(), h.cSt.size() * sizeof(int)) ||
+      !env_upload((void **)&p->d_colEnd, h.cEn.data(), h.cEn.size() * sizeof(int)) || !env_upload((void **)&p->d_colOff, h.cOff.data(), h.cOff.size() * sizeof(long long)) ||
       !hip_ok(hipStreamSynchronize(g_stream), "H2D pair envelopes")) { pt_env_free(p); return 1; }
-  p->envBase.swap(h.envBase); p->diagBase.swap(h.diagBase); p->colBase.swap(colBase); p->envCells.swap(h.envCells); p->envM.swap(h.M);
+  p->envBase.swap(h.envBase); p->diagBase.swap(h.diagBase); p->colBase.swap(h.colBase); p->envCells.swap(h.envCells); p->envM.swap(h.M);
   p->hasEnv = true;
   return 0;
 }

@@ -1,9 +1,11 @@
 // mb_profile_common.h -- what the profile sweeps share (mb_profile.hip, mb_profile_merge.hip, mb_profile_pair.hip,
-// mb_profile_pair_merge.hip, mb_profile_two.hip, mb_profile_two_merge.hip, mb_profile_post.hip): the reduction of a sweep's mode, the LDS a ring may take, the lanes of a workgroup, the
+// mb_profile_pair_merge.hip, mb_profile_two.hip, mb_profile_two_merge.hip, mb_profile_post.hip): the reduction of a sweep's mode, the LDS a ring may take and the raising of its limit, the lanes of a workgroup, the reversal of a path, the
 // accumulator of the posterior counts, the add of the row posteriors, and the generator and the draw of the path samplers
 // (k_profile_pair_sample, k_profile_pair_merge_sample).  Device code: included by .hip files only.
 #pragma once
 #include <algorithm>
+#include <initializer_list>
+#include <type_traits>
 
 #include "mb_device_math.h"
 #include "mb_internal.h"
@@ -19,6 +21,25 @@ __device__ __forceinline__ double red(double a, double b) { return MODE == MB_VI
 
 // lanes of a workgroup whose busiest phase has maxItems work items: whole wavefronts, at least one
 inline int sweep_threads(long long maxItems) { return (int)std::min<long long>(SWEEP_THREADS, std::max<long long>(64, (maxItems + 63) / 64 * 64)); }
+
+// Beyond the default 64 KiB of dynamic LDS the kernels must be told: asked for once, and only when a ring needs it.  allowed: the
+// caller's static, 64 KiB at first; kernels: every kernel of the caller that may get a ring that large; what: the error's context.
+inline bool allow_sweep_lds(size_t &allowed, size_t lds, std::initializer_list<const void *> kernels, const char *what) {
+  if (lds <= allowed) return true;
+  for (const void *k : kernels)
+    if (!hip_ok(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what)) return false;
+  allowed = SWEEP_LDS_MAX;
+  return true;
+}
+
+template <class T>
+__device__ __forceinline__ void swap_entries(T *a, long long u, long long v) { const T e = a[u]; a[u] = a[v]; a[v] = e; }
+// A path that a traceback or a sampler wrote from its end, turned round in place: its edges, the rows they fired at and, where the
+// input is a profile too, the input rows.
+template <class... T>
+__device__ __forceinline__ void reverse_path(long long cnt, T *...arrays) {
+  for (long long u = 0, v = cnt - 1; u < v; ++u, --v) (swap_entries(arrays, u, v), ...);
+}
 
 // Posterior counts of one workgroup.  Partial counts are kept in the workgroup's LDS table (lds[COUNTS_LDS_MAX]) when the
 // transition table is small and flushed once with atomics; beyond, every term goes to the global table.  det: both tables hold

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "mb_internal.h"
+#include "mb_profile_lattice.h"
 
 namespace mb {
 
@@ -19,6 +20,9 @@ struct PairProfDesc {
   long long ringBase;   // rolling sweeps: offset (doubles) of this pair's ring in the global scratch buffer, -1 = the ring is in LDS
   int nIn, nRows;
 };
+
+// which cells of the pair's lattice exist and where they live (mb_profile_lattice.h)
+MB_LATTICE_FN RectCells lattice_cells(const PairProfDesc &pd, NoTables) { return RectCells(pd.nIn, pd.nRows); }
 
 inline long long profile_pair_cells(int S, long long nIn, long long nRows) { return (nIn + 1) * (nRows + 1) * 2 * (long long)S; }
 // traceback slot: at most nIn input-consuming and nRows output-only edges, and nLevF - 1 silent edges at each of the at most

@@ -18,8 +18,9 @@
 // when that fits 160 KiB, else in the pair's slice of a global scratch buffer.  Cells are fp64, the sums the exact log-sum-exp.
 //
 // Every kernel is written once over a GEOMETRY, which says which cells exist and where they live: FullGeom, the whole rectangle, or
-// EnvGeom, the cells of an envelope (docs/profile_tapes.md, "Pairs under an envelope").  Both layers of a cell outside the envelope
-// are -inf, so a neighbour outside is not read; the recurrence, the candidate order and the sums are the same text for both.
+// EnvGeom, the cells of an envelope (docs/profile_tapes.md, "Pairs under an envelope").  The index rules of both are those of
+// mb_profile_lattice.h; PairLattice below adds the two layers.  Both layers of a cell outside the envelope are -inf, so a neighbour
+// outside is not read; the recurrence, the candidate order and the sums are the same text for both.
 #include "mb_profile_common.h"
 #include "mb_profile_pair_env.h"
 
@@ -34,73 +35,19 @@ size_t profile_pair_env_lds_bytes(int S, long long M) {
   return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
 }
 
-struct NoPairTables {};      // what the full geometry needs beside a pair's descriptor
-
-// The whole rectangle.  MAT: the materialised lattice of mb_profile_pair.h at base, else the ring (diagonal (i + r) mod 3, the cell
-// by its coordinate on the short side of the lattice).
-template <bool MAT>
-struct FullGeom {
-  using Desc = PairProfDesc;
-  using Tables = NoPairTables;
-  static constexpr bool ENV = false;
+// A pair's lattice: the cells of mb_profile_lattice.h, RectCells or EnvCells, with two layers of S doubles in each.  MAT: the
+// materialised lattice of mb_profile_pair.h (the compact one of mb_profile_pair_env.h) at base, else the ring.
+template <class Cells, bool MAT>
+struct PairLattice : Cells {
+  using Desc = std::conditional_t<Cells::ENV, PairEnvDesc, PairProfDesc>;
+  using Tables = std::conditional_t<Cells::ENV, PairEnvTables, NoTables>;
   double *base;
-  int S, I, L, M, byI;
-  __device__ __forceinline__ FullGeom(const Desc &pd, Tables, double *base, int S)
-      : base(base), S(S), I(pd.nIn), L(pd.nRows), M(min(pd.nIn, pd.nRows) + 1), byI(pd.nIn <= pd.nRows) {}
-  // the cells of diagonal d: i = ilo .. ilo + nCells - 1
-  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = max(0, d - L); nCells = min(I, d) - ilo + 1; }
-  // asked of neighbours the caller has already bounded to the rectangle
-  static constexpr __device__ __forceinline__ bool inside(int, int) { return true; }
-  __device__ __forceinline__ double *at(int i, int r, int layer) const {
-    if (MAT) return base + ((((long long)i * (L + 1)) + r) * 2 + layer) * S;
-    return base + ((((long long)((i + r) % 3) * M) + (byI ? i : r)) * 2 + layer) * S;
-  }
-  // counts: the cells of the pair and the c-th of them
-  __device__ __forceinline__ long long cells() const { return (long long)(I + 1) * (L + 1); }
-  __device__ __forceinline__ void cell(long long c, int &i, int &r) const { i = (int)(c / (L + 1)); r = (int)(c - (long long)i * (L + 1)); }
-  // row posteriors: the cells counted row by row (row r holds the cells rowFirst(r) .. rowFirst(r + 1) - 1, by ascending i)
-  __device__ __forceinline__ long long rowFirst(int r) const { return (long long)r * (I + 1); }
-  __device__ __forceinline__ void rowCell(long long c, int &i, int &r) const { r = (int)(c / (I + 1)); i = (int)(c - (long long)r * (I + 1)); }
+  int S;
+  __device__ __forceinline__ PairLattice(const Desc &pd, const Tables &t, double *base, int S) : Cells(lattice_cells(pd, t)), base(base), S(S) {}
+  __device__ __forceinline__ double *at(int i, int r, int layer) const { return base + ((MAT ? this->index(i, r) : this->slot(i, r)) * 2 + layer) * S; }
 };
-
-// The cells of an envelope (mb_profile_pair_env.h).  Its bounds never decrease from row to row, so the cells of diagonal d are the
-// run i = diagLo[d] .. diagLo[d] + diagCnt[d] - 1 (the host uploads both).  MAT: the compact lattice at base, else the ring
-// (diagonal (i + r) mod 3, the cell at i mod M, M the largest diagCnt of the pair: the cells of a diagonal have consecutive i and
-// number at most M, so no two share a slot).
-template <bool MAT>
-struct EnvGeom {
-  using Desc = PairEnvDesc;
-  using Tables = PairEnvTables;
-  static constexpr bool ENV = true;
-  double *base;
-  const int *st, *en;         // the pair's envelope rows
-  const long long *off;       // compact index of the first cell of each row
-  const int *dLo, *dCnt;
-  long long nCells;
-  int S, L, M;
-  __device__ __forceinline__ EnvGeom(const Desc &pd, const Tables &t, double *base, int S)
-      : base(base), st(t.envStart + pd.envBase), en(t.envEnd + pd.envBase), off(t.envOff + pd.envBase),
-        dLo(t.diagLo + pd.diagBase), dCnt(t.diagCnt + pd.diagBase), nCells(pd.nCells), S(S), L(pd.nRows), M(pd.M) {}
-  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = dLo[d]; nCells = dCnt[d]; }
-  // r in -1..L+1, i in -1..I+1
-  __device__ __forceinline__ bool inside(int i, int r) const { return r >= 0 && r <= L && i >= st[r] && i < en[r]; }
-  __device__ __forceinline__ double *at(int i, int r, int layer) const {
-    if (MAT) return base + ((off[r] + (i - st[r])) * 2 + layer) * S;
-    return base + ((((long long)((i + r) % 3) * M) + (i % M)) * 2 + layer) * S;
-  }
-  __device__ __forceinline__ long long cells() const { return nCells; }
-  __device__ __forceinline__ void cell(long long c, int &i, int &r) const {
-    int lo = 0, hi = L;                        // the last row whose offset is <= c: rows behind it start past the cell
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (off[mid] <= c) lo = mid; else hi = mid - 1;
-    }
-    r = lo; i = st[r] + (int)(c - off[r]);
-  }
-  // (the compact index already counts row by row; r <= L)
-  __device__ __forceinline__ long long rowFirst(int r) const { return off[r]; }
-  __device__ __forceinline__ void rowCell(long long c, int &i, int &r) const { cell(c, i, r); }
-};
+template <bool MAT> using FullGeom = PairLattice<RectCells, MAT>;
+template <bool MAT> using EnvGeom = PairLattice<EnvCells, MAT>;
 
 // Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every cell into pool (the geometry's layout), else rolling.
 // Viterbi keeps the FIRST maximum: N takes the blank first, then the match edges in `incoming` order, then the output-only edges in
@@ -344,7 +291,7 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_rowpost(DevMac
     if (!useLds) __threadfence();
     __syncthreads();
     if (LL > -INFINITY) {
-      const long long c0 = F.rowFirst(r0), nItems = (F.rowFirst(r1) - c0) * S;
+      const long long c0 = F.template lineFirst<0>(r0), nItems = (F.template lineFirst<0>(r1) - c0) * S;
       for (long long base = threadIdx.x - lane; base < nItems; base += blockDim.x) {      // (a wavefront stays whole in here)
         const long long idx = base + lane;
         const bool valid = idx < nItems;
@@ -353,7 +300,7 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_rowpost(DevMac
         if (valid) {
           const long long cell = idx / S;
           s = (int)(idx - cell * S);
-          F.rowCell(c0 + cell, i, r);
+          F.template lineCell<0>(c0 + cell, i, r);
           f = F.at(i, r, 1)[s] - LL;
           n = F.at(i, r, 0)[s] - LL;
         }
@@ -463,10 +410,7 @@ __global__ void k_profile_pair_traceback(DevMachine m, const typename Geom<true>
       i = ni; q = found; layer = 1;
     }
   }
-  for (long long u = 0, v = cnt - 1; u < v; ++u, --v) {
-    const uint32_t e = pe[u]; pe[u] = pe[v]; pe[v] = e;
-    const int32_t w = pr[u]; pr[u] = pr[v]; pr[v] = w;
-  }
+  reverse_path(cnt, pe, pr);
   len[k] = cnt;
 }
 
@@ -553,10 +497,7 @@ __global__ __launch_bounds__(64) void k_profile_pair_sample(DevMachine m, const 
       q = d.src; layer = 1;
     }
   }
-  for (long long u = 0, v = cnt - 1; u < v; ++u, --v) {
-    const uint32_t e = pe[u]; pe[u] = pe[v]; pe[v] = e;
-    const int32_t w = pr[u]; pr[u] = pr[v]; pr[v] = w;
-  }
+  reverse_path(cnt, pe, pr);
   len[id] = cnt;
   logq[id] = lq;
 }
@@ -568,13 +509,9 @@ static int pair_fwd(const mb_machine *m, int mode, bool mat, const typename Geom
   constexpr bool ENV = Geom<true>::ENV;
   if (n <= 0) return 0;
   if (mat) lds = 0;
-  static size_t ldsAllowed = 64 * 1024;      // beyond the default the kernels must be told; asked for once, and only when a ring needs it
-  if (lds > ldsAllowed) {
-    const char *what = ENV ? "k_profile_pair_env_fwd: raising the LDS limit" : "k_profile_pair_fwd: raising the LDS limit";
-    if (!hip_ok(hipFuncSetAttribute((const void *)&k_profile_pair_fwd<MB_FORWARD, false, Geom>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what) ||
-        !hip_ok(hipFuncSetAttribute((const void *)&k_profile_pair_fwd<MB_VITERBI, false, Geom>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what)) return 1;
-    ldsAllowed = SWEEP_LDS_MAX;
-  }
+  static size_t ldsAllowed = 64 * 1024;
+  if (!allow_sweep_lds(ldsAllowed, lds, {(const void *)&k_profile_pair_fwd<MB_FORWARD, false, Geom>, (const void *)&k_profile_pair_fwd<MB_VITERBI, false, Geom>},
+                       ENV ? "k_profile_pair_env_fwd: raising the LDS limit" : "k_profile_pair_fwd: raising the LDS limit")) return 1;
   const dim3 g(n), b(sweep_threads(maxItems));
   if (mode == MB_VITERBI) {
     if (mat) k_profile_pair_fwd<MB_VITERBI, true, Geom><<<g, b, 0, st>>>(m->dev, d, t, inTok, logP, pool, scratch, loglike);

@@ -26,6 +26,10 @@ struct PairEnvTables {
   const int *diagLo, *diagCnt;    // [diagonals] first i and cell count of each anti-diagonal
 };
 
+MB_LATTICE_FN EnvCells lattice_cells(const PairEnvDesc &pd, const PairEnvTables &t) {
+  return EnvCells(pd.nIn, pd.nRows, t.envStart + pd.envBase, t.envEnd + pd.envBase, t.envOff + pd.envBase, t.diagLo + pd.diagBase, t.diagCnt + pd.diagBase, pd.nCells, pd.M);
+}
+
 // the rolling ring: three anti-diagonals of both layers, each of M cells; a cell lives at i mod M
 inline long long profile_pair_env_ring(int S, long long M) { return 3 * 2 * M * (long long)S; }
 // dynamic LDS of the ring when it fits (0: a slice of the global scratch buffer)

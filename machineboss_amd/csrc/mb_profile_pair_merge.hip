@@ -22,8 +22,9 @@
 //
 // Every kernel is written once over PairMergeLattice, which says which cells exist and where they live: its full form, the whole
 // rectangle, or its envelope form, the cells of an envelope (docs/profile_tapes.md, "Pairs against a merged profile under an
-// envelope").  Every plane of both layers of a cell outside the envelope is -inf, and so are its X and T, so a neighbour outside is
-// not read; the recurrence, the candidate order and the sums are the same text for both.
+// envelope"); the index rules of both are those of mb_profile_lattice.h.  Every plane of both layers of a cell outside the envelope
+// is -inf, and so are its X and T, so a neighbour outside is not read; the recurrence, the candidate order and the sums are the same
+// text for both.
 #include "mb_profile_common.h"
 #include "mb_profile_pair_merge.h"
 
@@ -39,85 +40,29 @@ size_t profile_pair_merge_env_lds_bytes(int S, int nCols, long long M, bool mat)
   return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
 }
 
-struct NoMergeTables {};      // what the full form needs beside a pair's descriptor
-
-// Where cell (i, r) lives and whether it exists.  nw(i, r, layer): its N (layer 0) or W (layer 1), nCols + 1 planes of S states --
-// the materialised lattice, or the ring.  xv(i, r): its exclusion vectors, column c at (c - 1) * S -- always in the ring, beside N
-// and W when rolling.  diag(d): the cells of anti-diagonal d, i = ilo .. ilo + nCells - 1.  cell / rowCell: the c-th cell of the
-// pair as the counts and the row posteriors enumerate them (row r holds the cells rowFirst(r) .. rowFirst(r + 1) - 1, ascending i).
+// Where cell (i, r) lives: the cells of mb_profile_lattice.h, RectCells or EnvCells, and this family's layout.  nw(i, r, layer): its
+// N (layer 0) or W (layer 1), nCols + 1 planes of S states -- the materialised lattice of mb_profile_pair_merge.h (under an envelope
+// the compact one, cells[(((off[r] + i - inStart[r]) * 2 + layer) * (nCols + 1) + p) * S + q]), or the ring.  xv(i, r): its exclusion
+// vectors, column c at (c - 1) * S -- always in the ring, beside N and W when rolling.
+template <class Cells, bool MAT>
+struct PairMergeStore : Cells {
+  using Desc = std::conditional_t<Cells::ENV, PairEnvDesc, PairProfDesc>;
+  using Tables = std::conditional_t<Cells::ENV, PairEnvTables, NoTables>;
+  double *pool, *ring;
+  int S, PL;
+  __device__ __forceinline__ PairMergeStore(const Desc &pd, const Tables &t, double *pool, double *ring, int S, int PL)
+      : Cells(lattice_cells(pd, t)), pool(pool), ring(ring), S(S), PL(PL) {}
+  __device__ __forceinline__ double *nw(int i, int r, int layer) const {
+    if (MAT) return pool + (this->index(i, r) * 2 + layer) * PL * S;
+    return ring + (this->slot(i, r) * (3 * PL - 1) + layer * PL) * S;
+  }
+  __device__ __forceinline__ double *xv(int i, int r) const {
+    if (MAT) return ring + this->slot(i, r) * (PL - 1) * S;
+    return ring + (this->slot(i, r) * (3 * PL - 1) + 2 * PL) * S;
+  }
+};
 template <bool MAT, bool ENV>
-struct PairMergeLattice;
-
-// The whole rectangle: the lattice of mb_profile_pair_merge.h; in the ring diagonal (i + r) mod 3, the cell by its coordinate on the
-// short side of the lattice.
-template <bool MAT>
-struct PairMergeLattice<MAT, false> {
-  using Desc = PairProfDesc;
-  using Tables = NoMergeTables;
-  double *cells, *ring;
-  int S, PL, I, L, M, byI;
-  __device__ __forceinline__ PairMergeLattice(const Desc &pd, Tables, double *cells, double *ring, int S, int PL)
-      : cells(cells), ring(ring), S(S), PL(PL), I(pd.nIn), L(pd.nRows), M(min(pd.nIn, pd.nRows) + 1), byI(pd.nIn <= pd.nRows) {}
-  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = max(0, d - L); nCells = min(I, d) - ilo + 1; }
-  // asked of neighbours the caller has already bounded to the rectangle
-  static constexpr __device__ __forceinline__ bool inside(int, int) { return true; }
-  __device__ __forceinline__ long long slot(int i, int r) const { return (long long)((i + r) % 3) * M + (byI ? i : r); }
-  __device__ __forceinline__ double *nw(int i, int r, int layer) const {
-    if (MAT) return cells + ((((long long)i * (L + 1)) + r) * 2 + layer) * PL * S;
-    return ring + (slot(i, r) * (3 * PL - 1) + layer * PL) * S;
-  }
-  __device__ __forceinline__ double *xv(int i, int r) const {
-    if (MAT) return ring + slot(i, r) * (PL - 1) * S;
-    return ring + (slot(i, r) * (3 * PL - 1) + 2 * PL) * S;
-  }
-  __device__ __forceinline__ long long nCells() const { return (long long)(I + 1) * (L + 1); }
-  __device__ __forceinline__ void cell(long long c, int &i, int &r) const { i = (int)(c / (L + 1)); r = (int)(c - (long long)i * (L + 1)); }
-  __device__ __forceinline__ long long rowFirst(int r) const { return (long long)r * (I + 1); }
-  __device__ __forceinline__ void rowCell(long long c, int &i, int &r) const { r = (int)(c / (I + 1)); i = (int)(c - (long long)r * (I + 1)); }
-};
-
-// The cells of an envelope (mb_profile_pair_env.h): the compact lattice cells[(((off[r] + i - inStart[r]) * 2 + layer) * (nCols + 1)
-// + p) * S + q]; in the ring diagonal (i + r) mod 3, the cell at i mod M, M the largest cell count of a diagonal of the pair -- the
-// cells of a diagonal have consecutive i and number at most M, so no two share a slot.  A slot may hold a stale cell of another
-// row; it is never read, because inside() is asked first.
-template <bool MAT>
-struct PairMergeLattice<MAT, true> {
-  using Desc = PairEnvDesc;
-  using Tables = PairEnvTables;
-  double *cells, *ring;
-  const int *st, *en;         // the pair's envelope rows
-  const long long *off;       // compact index of the first cell of each row
-  const int *dLo, *dCnt;
-  long long nEnv;
-  int S, PL, L, M;
-  __device__ __forceinline__ PairMergeLattice(const Desc &pd, const Tables &t, double *cells, double *ring, int S, int PL)
-      : cells(cells), ring(ring), st(t.envStart + pd.envBase), en(t.envEnd + pd.envBase), off(t.envOff + pd.envBase),
-        dLo(t.diagLo + pd.diagBase), dCnt(t.diagCnt + pd.diagBase), nEnv(pd.nCells), S(S), PL(PL), L(pd.nRows), M(pd.M) {}
-  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = dLo[d]; nCells = dCnt[d]; }
-  // r in -1..L+1, i in -1..I+1
-  __device__ __forceinline__ bool inside(int i, int r) const { return r >= 0 && r <= L && i >= st[r] && i < en[r]; }
-  __device__ __forceinline__ long long slot(int i, int r) const { return (long long)((i + r) % 3) * M + (i % M); }
-  __device__ __forceinline__ double *nw(int i, int r, int layer) const {
-    if (MAT) return cells + ((off[r] + (i - st[r])) * 2 + layer) * PL * S;
-    return ring + (slot(i, r) * (3 * PL - 1) + layer * PL) * S;
-  }
-  __device__ __forceinline__ double *xv(int i, int r) const {
-    if (MAT) return ring + slot(i, r) * (PL - 1) * S;
-    return ring + (slot(i, r) * (3 * PL - 1) + 2 * PL) * S;
-  }
-  __device__ __forceinline__ long long nCells() const { return nEnv; }
-  __device__ __forceinline__ void cell(long long c, int &i, int &r) const {
-    int lo = 0, hi = L;                        // the last row whose offset is <= c: rows behind it start past the cell
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (off[mid] <= c) lo = mid; else hi = mid - 1;
-    }
-    r = lo; i = st[r] + (int)(c - off[r]);
-  }
-  // (the compact index already counts row by row; r <= L)
-  __device__ __forceinline__ long long rowFirst(int r) const { return off[r]; }
-  __device__ __forceinline__ void rowCell(long long c, int &i, int &r) const { cell(c, i, r); }
-};
+using PairMergeLattice = PairMergeStore<std::conditional_t<ENV, EnvCells, RectCells>, MAT>;
 
 // Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every N and W cell into pool (layout of mb_profile_pair_merge.h)
 // and only X in the ring, else rolling.  Viterbi keeps the FIRST maximum: N[.][.][0] takes the planes ascending; N[.][.][c] the
@@ -350,7 +295,7 @@ __global__ __launch_bounds__(256) void k_profile_pair_merge_counts(DevMachine m,
     for (int p = 1; p < PL; ++p) LL = lse2_exact(LL, We[p * S]);
   }
   if (LL > -INFINITY) {
-    const long long PS = (long long)PL * S, nItems = F.nCells() * PS;
+    const long long PS = (long long)PL * S, nItems = F.cells() * PS;
     for (long long idx = (long long)group * blockDim.x + threadIdx.x; idx < nItems; idx += (long long)groupsPerPair * blockDim.x) {
       const long long cell = idx / PS;
       const int ks = (int)(idx - cell * PS), k = ks / S, s = ks - k * S;
@@ -413,7 +358,7 @@ __global__ __launch_bounds__(256) void k_profile_pair_merge_counts(DevMachine m,
 // beforehand.  A row of more than tabMax columns is summed in its global bins instead, cleared by the workgroup that owns it.  A pair
 // whose likelihood is -inf gets zeros by the same stores.  loglike: the Forward sweep's, per pair of the launch.
 // det: a lane sum is turned into 64-bit fixed point at 2^-36 (mb_internal.h) before it meets another; post then holds the integers.
-// The rows are walked through the lattice's rowFirst / rowCell: under an envelope row r has (inEnd[r] - inStart[r]) (nCols + 1) S
+// The rows are walked through the lattice's lineFirst<0> / lineCell<0>: under an envelope row r has (inEnd[r] - inStart[r]) (nCols + 1) S
 // items, and the cells (i, r + 1) and (i + 1, r + 1) are asked inside() before they are read.  Every bin of every row is still
 // written, so a row all of whose terms are dead gets zeros.
 template <bool ENV>
@@ -433,7 +378,7 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_merge_rowpost(
       B(pd, t, const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL);
   const double LL = loglike[pair];
   const long long PS = (long long)PL * S;
-  const int R = profile_pair_rowpost_rows(F.nCells() * PL, S, L, PL, tabMax);
+  const int R = profile_pair_rowpost_rows(F.cells() * PL, S, L, PL, tabMax);
   const bool useLds = PL <= tabMax;
   const int lane = threadIdx.x & 63;
   for (long long rb = (long long)group * R; rb < L; rb += (long long)groupsPerPair * R) {
@@ -444,7 +389,7 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_merge_rowpost(
     if (!useLds) __threadfence();
     __syncthreads();
     if (LL > -INFINITY) {
-      const long long c0 = F.rowFirst(r0), nItems = (F.rowFirst(r1) - c0) * PS;
+      const long long c0 = F.template lineFirst<0>(r0), nItems = (F.template lineFirst<0>(r1) - c0) * PS;
       for (long long base = threadIdx.x - lane; base < nItems; base += blockDim.x) {      // (a wavefront stays whole in here)
         const long long idx = base + lane;
         const bool valid = idx < nItems;
@@ -453,7 +398,7 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_pair_merge_rowpost(
         if (valid) {
           const long long cell = idx / PS;
           ks = (int)(idx - cell * PS);
-          F.rowCell(c0 + cell, i, r);
+          F.template lineCell<0>(c0 + cell, i, r);
           k = ks / S;
           s = ks - k * S;
           n = F.nw(i, r, 0)[ks] - LL;
@@ -602,10 +547,7 @@ __global__ void k_profile_pair_merge_traceback(DevMachine m, MergeMap mm, const 
       i = ni; q = found; p = from; layer = 1;
     }
   }
-  for (long long u = 0, v = cnt - 1; u < v; ++u, --v) {
-    const uint32_t e = pe[u]; pe[u] = pe[v]; pe[v] = e;
-    const int32_t w = pr[u]; pr[u] = pr[v]; pr[v] = w;
-  }
+  reverse_path(cnt, pe, pr);
   len[pair] = cnt;
 }
 
@@ -730,28 +672,22 @@ __global__ __launch_bounds__(64) void k_profile_pair_merge_sample(DevMachine m, 
       q = d.src; p = d.kind >> 2; layer = 1;
     }
   }
-  for (long long u = 0, v = cnt - 1; u < v; ++u, --v) {
-    const uint32_t e = pe[u]; pe[u] = pe[v]; pe[v] = e;
-    const int32_t w = pr[u]; pr[u] = pr[v]; pr[v] = w;
-  }
+  reverse_path(cnt, pe, pr);
   len[id] = cnt;
   logq[id] = lq;
 }
 
-// beyond the default 64 KiB the kernels must be told; asked for once, and only when a ring needs it
+// every kernel that may get a ring in dynamic LDS (allow_sweep_lds, mb_profile_common.h)
 static bool ppm_allow_lds(size_t lds) {
   static size_t ldsAllowed = 64 * 1024;
-  if (lds <= ldsAllowed) return true;
-  const void *ks[] = {(const void *)&k_profile_pair_merge_fwd<MB_FORWARD, false, false>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, false, false>,
-                      (const void *)&k_profile_pair_merge_fwd<MB_FORWARD, true, false>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, true, false>,
-                      (const void *)&k_profile_pair_merge_bwd<false>,
-                      (const void *)&k_profile_pair_merge_fwd<MB_FORWARD, false, true>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, false, true>,
-                      (const void *)&k_profile_pair_merge_fwd<MB_FORWARD, true, true>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, true, true>,
-                      (const void *)&k_profile_pair_merge_bwd<true>};
-  for (const void *k : ks)
-    if (!hip_ok(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), "k_profile_pair_merge: raising the LDS limit")) return false;
-  ldsAllowed = SWEEP_LDS_MAX;
-  return true;
+  return allow_sweep_lds(ldsAllowed, lds,
+                         {(const void *)&k_profile_pair_merge_fwd<MB_FORWARD, false, false>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, false, false>,
+                          (const void *)&k_profile_pair_merge_fwd<MB_FORWARD, true, false>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, true, false>,
+                          (const void *)&k_profile_pair_merge_bwd<false>,
+                          (const void *)&k_profile_pair_merge_fwd<MB_FORWARD, false, true>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, false, true>,
+                          (const void *)&k_profile_pair_merge_fwd<MB_FORWARD, true, true>, (const void *)&k_profile_pair_merge_fwd<MB_VITERBI, true, true>,
+                          (const void *)&k_profile_pair_merge_bwd<true>},
+                         "k_profile_pair_merge: raising the LDS limit");
 }
 
 // The launchers: each sweep once over a form of the lattice, and the two overloads of the header that name one.

@@ -23,9 +23,10 @@
 // else in the pair's slice of a global scratch buffer.  Cells are fp64, the sums the exact log-sum-exp.
 //
 // Every kernel is written once over a GEOMETRY, which says which cells exist and where they live: TwoGeom, the whole rectangle, or
-// TwoEnvGeom, the cells of an envelope (docs/profile_tapes.md, "Pairs of profiles under an envelope").  All three layers of a cell
-// outside the envelope are -inf, so a neighbour outside is not read -- the input blank Z[i-1][r] -> Z[i][r] is a move along i like
-// any other and is left out when (i-1, r) is outside; the recurrence, the candidate order and the sums are the same text for both.
+// TwoEnvGeom, the cells of an envelope (docs/profile_tapes.md, "Pairs of profiles under an envelope").  The index rules of both are
+// those of mb_profile_lattice.h; TwoLattice below adds the three layers.  All three layers of a cell outside the envelope are -inf,
+// so a neighbour outside is not read -- the input blank Z[i-1][r] -> Z[i][r] is a move along i like any other and is left out when
+// (i-1, r) is outside; the recurrence, the candidate order and the sums are the same text for both.
 #include "mb_profile_common.h"
 #include "mb_profile_two_env.h"
 
@@ -40,84 +41,19 @@ size_t profile_two_env_lds_bytes(int S, long long M) {
   return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
 }
 
-struct NoTwoTables {};      // what the full geometry needs beside a pair's descriptor
-
-// The whole rectangle.  MAT: the materialised lattice of mb_profile_two.h at base, else the ring (diagonal (i + r) mod 3,
-// the cell by its coordinate on the short side of the lattice).
-template <bool MAT>
-struct TwoGeom {
-  using Desc = PairProfDesc;
-  using Tables = NoTwoTables;
-  static constexpr bool ENV = false;
+// A pair's lattice: the cells of mb_profile_lattice.h, RectCells or EnvCells, with three layers of S doubles in each.  MAT: the
+// materialised lattice of mb_profile_two.h (the compact one of mb_profile_two_env.h) at base, else the ring.
+template <class Cells, bool MAT>
+struct TwoLattice : Cells {
+  using Desc = std::conditional_t<Cells::ENV, TwoEnvDesc, PairProfDesc>;
+  using Tables = std::conditional_t<Cells::ENV, TwoEnvTables, NoTables>;
   double *base;
-  int S, K, L, M, byI;
-  __device__ __forceinline__ TwoGeom(const Desc &pd, Tables, double *base, int S)
-      : base(base), S(S), K(pd.nIn), L(pd.nRows), M(min(pd.nIn, pd.nRows) + 1), byI(pd.nIn <= pd.nRows) {}
-  // the cells of diagonal d: i = ilo .. ilo + nCells - 1
-  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = max(0, d - L); nCells = min(K, d) - ilo + 1; }
-  // asked of neighbours the caller has already bounded to the rectangle
-  static constexpr __device__ __forceinline__ bool inside(int, int) { return true; }
-  __device__ __forceinline__ double *at(int i, int r, int layer) const {
-    if (MAT) return base + ((((long long)i * (L + 1)) + r) * 3 + layer) * S;
-    return base + ((((long long)((i + r) % 3) * M) + (byI ? i : r)) * 3 + layer) * S;
-  }
-  __device__ __forceinline__ long long cells() const { return (long long)(K + 1) * (L + 1); }
-  __device__ __forceinline__ void cell(long long c, int &i, int &r) const { i = (int)(c / (L + 1)); r = (int)(c - (long long)i * (L + 1)); }
-  // row posteriors: the cells counted line by line (AXIS 0: output row r holds lineFirst(r) .. lineFirst(r + 1) - 1 by ascending i;
-  // AXIS 1: input row i by ascending r) -- over the rectangle both orders are a division
-  template <int AXIS> __device__ __forceinline__ long long lineFirst(int l) const { return (long long)l * ((AXIS ? L : K) + 1); }
-  template <int AXIS> __device__ __forceinline__ void lineCell(long long c, int &i, int &r) const {
-    const int per = (AXIS ? L : K) + 1, line = (int)(c / per), j = (int)(c - (long long)line * per);
-    i = AXIS ? line : j; r = AXIS ? j : line;
-  }
+  int S;
+  __device__ __forceinline__ TwoLattice(const Desc &pd, const Tables &t, double *base, int S) : Cells(lattice_cells(pd, t)), base(base), S(S) {}
+  __device__ __forceinline__ double *at(int i, int r, int layer) const { return base + ((MAT ? this->index(i, r) : this->slot(i, r)) * 3 + layer) * S; }
 };
-
-// The cells of an envelope (mb_profile_two_env.h).  Its bounds never decrease from row to row, so the cells of diagonal d are the
-// run i = diagLo[d] .. diagLo[d] + diagCnt[d] - 1 (the host uploads both).  MAT: the compact three-layer lattice at base, else the
-// ring (diagonal (i + r) mod 3, the cell at i mod M, M the largest diagCnt of the pair: the cells of a diagonal have consecutive i
-// and number at most M, so no two share a slot).
-template <bool MAT>
-struct TwoEnvGeom {
-  using Desc = TwoEnvDesc;
-  using Tables = TwoEnvTables;
-  static constexpr bool ENV = true;
-  double *base;
-  const int *st, *en;         // the pair's envelope rows
-  const long long *off;       // compact index of the first cell of each row
-  const int *dLo, *dCnt;
-  const int *cSt;             // the transposed envelope: first output row of each input row, and
-  const long long *cOff;      // the cells of the input rows before it
-  long long nCells;
-  int S, K, L, M;
-  __device__ __forceinline__ TwoEnvGeom(const Desc &pd, const Tables &t, double *base, int S)
-      : base(base), st(t.envStart + pd.envBase), en(t.envEnd + pd.envBase), off(t.envOff + pd.envBase),
-        dLo(t.diagLo + pd.diagBase), dCnt(t.diagCnt + pd.diagBase), cSt(t.colStart + pd.colBase), cOff(t.colOff + pd.colBase),
-        nCells(pd.nCells), S(S), K(pd.nIn), L(pd.nRows), M(pd.M) {}
-  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = dLo[d]; nCells = dCnt[d]; }
-  // r in -1..L+1, i in -1..K+1
-  __device__ __forceinline__ bool inside(int i, int r) const { return r >= 0 && r <= L && i >= st[r] && i < en[r]; }
-  __device__ __forceinline__ double *at(int i, int r, int layer) const {
-    if (MAT) return base + ((off[r] + (i - st[r])) * 3 + layer) * S;
-    return base + ((((long long)((i + r) % 3) * M) + (i % M)) * 3 + layer) * S;
-  }
-  __device__ __forceinline__ long long cells() const { return nCells; }
-  // the last entry of o[0..n] that is <= c: the lines behind it start past the cell
-  static __device__ __forceinline__ int lastLE(const long long *o, int n, long long c) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (o[mid] <= c) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-  }
-  __device__ __forceinline__ void cell(long long c, int &i, int &r) const { r = lastLE(off, L, c); i = st[r] + (int)(c - off[r]); }
-  // (AXIS 0: the compact index already counts row by row; AXIS 1: column by column through the transposed envelope)
-  template <int AXIS> __device__ __forceinline__ long long lineFirst(int l) const { return AXIS ? cOff[l] : off[l]; }
-  template <int AXIS> __device__ __forceinline__ void lineCell(long long c, int &i, int &r) const {
-    if (AXIS) { i = lastLE(cOff, K, c); r = cSt[i] + (int)(c - cOff[i]); }
-    else cell(c, i, r);
-  }
-};
+template <bool MAT> using TwoGeom = TwoLattice<RectCells, MAT>;
+template <bool MAT> using TwoEnvGeom = TwoLattice<EnvCells, MAT>;
 
 // Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every cell into pool, else rolling.  Viterbi keeps the FIRST
 // maximum: N takes the output blank first, then the match edges, then the output-only edges; W takes N (no move) first, then the
@@ -561,11 +497,7 @@ __global__ void k_profile_two_traceback(DevMachine m, const typename Geom<true>:
       i = ni; q = found; layer = nl;
     }
   }
-  for (long long u = 0, v = cnt - 1; u < v; ++u, --v) {
-    const uint32_t e = pe[u]; pe[u] = pe[v]; pe[v] = e;
-    const int32_t w = pr[u]; pr[u] = pr[v]; pr[v] = w;
-    const int32_t x = pi[u]; pi[u] = pi[v]; pi[v] = x;
-  }
+  reverse_path(cnt, pe, pr, pi);
   len[k] = cnt;
 }
 
@@ -576,13 +508,9 @@ static int two_fwd(const mb_machine *m, int mode, bool mat, const typename Geom<
   constexpr bool ENV = Geom<true>::ENV;
   if (n <= 0) return 0;
   if (mat) lds = 0;
-  static size_t ldsAllowed = 64 * 1024;      // beyond the default the kernels must be told; asked for once, and only when a ring needs it
-  if (lds > ldsAllowed) {
-    const char *what = ENV ? "k_profile_two_env_fwd: raising the LDS limit" : "k_profile_two_fwd: raising the LDS limit";
-    if (!hip_ok(hipFuncSetAttribute((const void *)&k_profile_two_fwd<MB_FORWARD, false, Geom>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what) ||
-        !hip_ok(hipFuncSetAttribute((const void *)&k_profile_two_fwd<MB_VITERBI, false, Geom>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), what)) return 1;
-    ldsAllowed = SWEEP_LDS_MAX;
-  }
+  static size_t ldsAllowed = 64 * 1024;
+  if (!allow_sweep_lds(ldsAllowed, lds, {(const void *)&k_profile_two_fwd<MB_FORWARD, false, Geom>, (const void *)&k_profile_two_fwd<MB_VITERBI, false, Geom>},
+                       ENV ? "k_profile_two_env_fwd: raising the LDS limit" : "k_profile_two_fwd: raising the LDS limit")) return 1;
   const dim3 g(n), b(sweep_threads(maxItems));
   if (mode == MB_VITERBI) {
     if (mat) k_profile_two_fwd<MB_VITERBI, true, Geom><<<g, b, 0, st>>>(m->dev, d, t, logA, logB, pool, scratch, loglike);

@@ -20,6 +20,11 @@ struct TwoEnvTables : PairEnvTables {
   const long long *colOff;        // [input rows] cells of the input rows before, per pair from 0
 };
 
+MB_LATTICE_FN EnvCells lattice_cells(const TwoEnvDesc &pd, const TwoEnvTables &t) {
+  return EnvCells(pd.nIn, pd.nRows, t.envStart + pd.envBase, t.envEnd + pd.envBase, t.envOff + pd.envBase, t.diagLo + pd.diagBase, t.diagCnt + pd.diagBase, pd.nCells, pd.M,
+                  t.colStart + pd.colBase, t.colOff + pd.colBase);
+}
+
 // the rolling ring: three anti-diagonals of three layers, each of M cells; a cell lives at i mod M
 inline long long profile_two_env_ring(int S, long long M) { return 3 * 3 * M * (long long)S; }
 // dynamic LDS of the ring when it fits (0: a slice of the global scratch buffer)

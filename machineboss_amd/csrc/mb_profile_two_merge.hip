@@ -25,8 +25,9 @@
 //
 // Every kernel is written once over TwoMergeLattice, which says which cells exist and where they live: its full form, the whole
 // rectangle, or its envelope form, the cells of an envelope (docs/profile_tapes.md, "Pairs of profiles against a merged profile
-// under an envelope").  Every plane of all three layers of a cell outside the envelope is -inf, and so are its XW, XZ, TZ and TW,
-// so a neighbour outside is not read; the recurrence, the candidate order and the sums are the same text for both.
+// under an envelope"); the index rules of both are those of mb_profile_lattice.h.  Every plane of all three layers of a cell
+// outside the envelope is -inf, and so are its XW, XZ, TZ and TW, so a neighbour outside is not read; the recurrence, the candidate
+// order and the sums are the same text for both.
 #include "mb_profile_common.h"
 #include "mb_profile_two_merge.h"
 
@@ -42,101 +43,30 @@ size_t profile_two_merge_env_lds_bytes(int S, int nCols, long long M, bool mat) 
   return b <= (double)SWEEP_LDS_MAX ? (size_t)b : 0;
 }
 
-struct NoTwoMergeTables {};      // what the full form needs beside a pair's descriptor
-
-// Where cell (i, r) lives and whether it exists.  at(i, r, layer): its N (0), W (1) or Z (2), nCols + 1 planes of S states -- the
-// materialised lattice, or the ring.  xw(i, r) / xz(i, r): its exclusion vectors over W / over Z, column c at (c - 1) * S -- always
-// in the ring, beside the three layers when rolling.  diag(d): the cells of anti-diagonal d, i = ilo .. ilo + nCells - 1.  cell: the
-// c-th cell of the pair as the counts enumerate them; lineFirst / lineCell: the cells counted line by line as the row posteriors
-// do (AXIS 0: output row r holds lineFirst(r) .. lineFirst(r + 1) - 1 by ascending i; AXIS 1: input row i by ascending r).
+// Where cell (i, r) lives: the cells of mb_profile_lattice.h, RectCells or EnvCells, and this family's layout.  at(i, r, layer): its
+// N (0), W (1) or Z (2), nCols + 1 planes of S states -- the materialised lattice of mb_profile_two_merge.h (under an envelope the
+// compact one, cells[(((off[r] + i - inStart[r]) * 3 + layer) * (nCols + 1) + p) * S + q]), or the ring.  xw(i, r) / xz(i, r): its
+// exclusion vectors over W / over Z, column c at (c - 1) * S -- always in the ring, beside the three layers when rolling.
+template <class Cells, bool MAT>
+struct TwoMergeStore : Cells {
+  using Desc = std::conditional_t<Cells::ENV, TwoEnvDesc, PairProfDesc>;
+  using Tables = std::conditional_t<Cells::ENV, TwoEnvTables, NoTables>;
+  double *pool, *ring;
+  int S, PL;
+  __device__ __forceinline__ TwoMergeStore(const Desc &pd, const Tables &t, double *pool, double *ring, int S, int PL)
+      : Cells(lattice_cells(pd, t)), pool(pool), ring(ring), S(S), PL(PL) {}
+  __device__ __forceinline__ double *at(int i, int r, int layer) const {
+    if (MAT) return pool + (this->index(i, r) * 3 + layer) * PL * S;
+    return ring + (this->slot(i, r) * (5 * PL - 2) + layer * PL) * S;
+  }
+  __device__ __forceinline__ double *xw(int i, int r) const {
+    if (MAT) return ring + this->slot(i, r) * 2 * (PL - 1) * S;
+    return ring + (this->slot(i, r) * (5 * PL - 2) + 3 * PL) * S;
+  }
+  __device__ __forceinline__ double *xz(int i, int r) const { return xw(i, r) + (PL - 1) * S; }
+};
 template <bool MAT, bool ENV>
-struct TwoMergeLattice;
-
-// The whole rectangle: the lattice of mb_profile_two_merge.h; in the ring diagonal (i + r) mod 3, the cell by its coordinate on the
-// short side of the lattice.
-template <bool MAT>
-struct TwoMergeLattice<MAT, false> {
-  using Desc = PairProfDesc;
-  using Tables = NoTwoMergeTables;
-  double *cells, *ring;
-  int S, PL, K, L, M, byI;
-  __device__ __forceinline__ TwoMergeLattice(const Desc &pd, Tables, double *cells, double *ring, int S, int PL)
-      : cells(cells), ring(ring), S(S), PL(PL), K(pd.nIn), L(pd.nRows), M(min(pd.nIn, pd.nRows) + 1), byI(pd.nIn <= pd.nRows) {}
-  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = max(0, d - L); nCells = min(K, d) - ilo + 1; }
-  // asked of neighbours the caller has already bounded to the rectangle
-  static constexpr __device__ __forceinline__ bool inside(int, int) { return true; }
-  __device__ __forceinline__ long long slot(int i, int r) const { return (long long)((i + r) % 3) * M + (byI ? i : r); }
-  __device__ __forceinline__ double *at(int i, int r, int layer) const {
-    if (MAT) return cells + ((((long long)i * (L + 1)) + r) * 3 + layer) * PL * S;
-    return ring + (slot(i, r) * (5 * PL - 2) + layer * PL) * S;
-  }
-  __device__ __forceinline__ double *xw(int i, int r) const {
-    if (MAT) return ring + slot(i, r) * 2 * (PL - 1) * S;
-    return ring + (slot(i, r) * (5 * PL - 2) + 3 * PL) * S;
-  }
-  __device__ __forceinline__ double *xz(int i, int r) const { return xw(i, r) + (PL - 1) * S; }
-  __device__ __forceinline__ long long nCells() const { return (long long)(K + 1) * (L + 1); }
-  __device__ __forceinline__ void cell(long long c, int &i, int &r) const { i = (int)(c / (L + 1)); r = (int)(c - (long long)i * (L + 1)); }
-  // (over the rectangle both line orders are a division)
-  template <int AXIS> __device__ __forceinline__ long long lineFirst(int l) const { return (long long)l * ((AXIS ? L : K) + 1); }
-  template <int AXIS> __device__ __forceinline__ void lineCell(long long c, int &i, int &r) const {
-    const int per = (AXIS ? L : K) + 1, line = (int)(c / per), j = (int)(c - (long long)line * per);
-    i = AXIS ? line : j; r = AXIS ? j : line;
-  }
-};
-
-// The cells of an envelope (mb_profile_two_env.h): the compact lattice cells[(((off[r] + i - inStart[r]) * 3 + layer) * (nCols + 1)
-// + p) * S + q]; in the ring diagonal (i + r) mod 3, the cell at i mod M, M the largest cell count of a diagonal of the pair -- the
-// cells of a diagonal have consecutive i and number at most M, so no two share a slot.  A slot may hold a stale cell of another
-// row; it is never read, because inside() is asked first.
-template <bool MAT>
-struct TwoMergeLattice<MAT, true> {
-  using Desc = TwoEnvDesc;
-  using Tables = TwoEnvTables;
-  double *cells, *ring;
-  const int *st, *en;         // the pair's envelope rows
-  const long long *off;       // compact index of the first cell of each row
-  const int *dLo, *dCnt;
-  const int *cSt;             // the transposed envelope: first output row of each input row, and
-  const long long *cOff;      // the cells of the input rows before it
-  long long nEnv;
-  int S, PL, K, L, M;
-  __device__ __forceinline__ TwoMergeLattice(const Desc &pd, const Tables &t, double *cells, double *ring, int S, int PL)
-      : cells(cells), ring(ring), st(t.envStart + pd.envBase), en(t.envEnd + pd.envBase), off(t.envOff + pd.envBase),
-        dLo(t.diagLo + pd.diagBase), dCnt(t.diagCnt + pd.diagBase), cSt(t.colStart + pd.colBase), cOff(t.colOff + pd.colBase),
-        nEnv(pd.nCells), S(S), PL(PL), K(pd.nIn), L(pd.nRows), M(pd.M) {}
-  __device__ __forceinline__ void diag(int d, int &ilo, int &nCells) const { ilo = dLo[d]; nCells = dCnt[d]; }
-  // r in -1..L+1, i in -1..K+1
-  __device__ __forceinline__ bool inside(int i, int r) const { return r >= 0 && r <= L && i >= st[r] && i < en[r]; }
-  __device__ __forceinline__ long long slot(int i, int r) const { return (long long)((i + r) % 3) * M + (i % M); }
-  // (MAT: r in 0..L; the address of a cell outside is formed in places, and read nowhere)
-  __device__ __forceinline__ double *at(int i, int r, int layer) const {
-    if (MAT) return cells + ((off[r] + (i - st[r])) * 3 + layer) * PL * S;
-    return ring + (slot(i, r) * (5 * PL - 2) + layer * PL) * S;
-  }
-  __device__ __forceinline__ double *xw(int i, int r) const {
-    if (MAT) return ring + slot(i, r) * 2 * (PL - 1) * S;
-    return ring + (slot(i, r) * (5 * PL - 2) + 3 * PL) * S;
-  }
-  __device__ __forceinline__ double *xz(int i, int r) const { return xw(i, r) + (PL - 1) * S; }
-  __device__ __forceinline__ long long nCells() const { return nEnv; }
-  // the last entry of o[0..n] that is <= c: the lines behind it start past the cell
-  static __device__ __forceinline__ int lastLE(const long long *o, int n, long long c) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (o[mid] <= c) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-  }
-  __device__ __forceinline__ void cell(long long c, int &i, int &r) const { r = lastLE(off, L, c); i = st[r] + (int)(c - off[r]); }
-  // (AXIS 0: the compact index already counts row by row, l <= L; AXIS 1: column by column through the transposed envelope, l <= K)
-  template <int AXIS> __device__ __forceinline__ long long lineFirst(int l) const { return AXIS ? cOff[l] : off[l]; }
-  template <int AXIS> __device__ __forceinline__ void lineCell(long long c, int &i, int &r) const {
-    if (AXIS) { i = lastLE(cOff, K, c); r = cSt[i] + (int)(c - cOff[i]); }
-    else cell(c, i, r);
-  }
-};
+using TwoMergeLattice = TwoMergeStore<std::conditional_t<ENV, EnvCells, RectCells>, MAT>;
 
 // Forward (MODE = MB_FORWARD) or Viterbi (MB_VITERBI) sweep.  MAT: every N, W and Z cell into pool (layout of
 // mb_profile_two_merge.h) and only XW, XZ in the ring, else rolling.  Viterbi keeps the FIRST maximum: N[.][.][0] takes the planes
@@ -404,7 +334,7 @@ __global__ __launch_bounds__(256) void k_profile_two_merge_counts(DevMachine m, 
     for (int p = 1; p < PL; ++p) LL = lse2_exact(LL, Ze[p * S]);
   }
   if (LL > -INFINITY) {
-    const long long PS = (long long)PL * S, nItems = F.nCells() * PS;
+    const long long PS = (long long)PL * S, nItems = F.cells() * PS;
     for (long long idx = (long long)group * blockDim.x + threadIdx.x; idx < nItems; idx += (long long)groupsPerPair * blockDim.x) {
       const long long cell = idx / PS;
       const int ks = (int)(idx - cell * PS), k = ks / S, s = ks - k * S;
@@ -501,7 +431,7 @@ __global__ __launch_bounds__(ROWPOST_THREADS) void k_profile_two_merge_rowpost(D
       Bk(pd, t, const_cast<double *>(bwdPool) + pd.cellBase, nullptr, S, PL);
   const double LL = loglike[pair];
   const long long PS = (long long)PL * S;
-  const int R = profile_pair_rowpost_rows(F.nCells() * PL, S, NL, NC, tabMax);
+  const int R = profile_pair_rowpost_rows(F.cells() * PL, S, NL, NC, tabMax);
   const bool useLds = NC <= tabMax;
   const int lane = threadIdx.x & 63;
   for (long long lb = (long long)group * R; lb < NL; lb += (long long)groupsPerPair * R) {
@@ -718,29 +648,21 @@ __global__ void k_profile_two_merge_traceback(DevMachine m, MergeMap mm, const t
       i = ni; q = found; p = from; layer = nl;
     }
   }
-  for (long long u = 0, v = cnt - 1; u < v; ++u, --v) {
-    const uint32_t e = pe[u]; pe[u] = pe[v]; pe[v] = e;
-    const int32_t w = pr[u]; pr[u] = pr[v]; pr[v] = w;
-    const int32_t x = pi[u]; pi[u] = pi[v]; pi[v] = x;
-  }
+  reverse_path(cnt, pe, pr, pi);
   len[pair] = cnt;
 }
 
-// beyond the default 64 KiB the kernels must be told; asked for once, for the full and the envelope instantiations together, and only
-// when a ring needs it
+// every kernel that may get a ring in dynamic LDS (allow_sweep_lds, mb_profile_common.h)
 static bool ptm_allow_lds(size_t lds) {
   static size_t ldsAllowed = 64 * 1024;
-  if (lds <= ldsAllowed) return true;
-  const void *ks[] = {(const void *)&k_profile_two_merge_fwd<MB_FORWARD, false, false>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, false, false>,
-                      (const void *)&k_profile_two_merge_fwd<MB_FORWARD, true, false>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, true, false>,
-                      (const void *)&k_profile_two_merge_bwd<false>,
-                      (const void *)&k_profile_two_merge_fwd<MB_FORWARD, false, true>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, false, true>,
-                      (const void *)&k_profile_two_merge_fwd<MB_FORWARD, true, true>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, true, true>,
-                      (const void *)&k_profile_two_merge_bwd<true>};
-  for (const void *k : ks)
-    if (!hip_ok(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SWEEP_LDS_MAX), "k_profile_two_merge: raising the LDS limit")) return false;
-  ldsAllowed = SWEEP_LDS_MAX;
-  return true;
+  return allow_sweep_lds(ldsAllowed, lds,
+                         {(const void *)&k_profile_two_merge_fwd<MB_FORWARD, false, false>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, false, false>,
+                          (const void *)&k_profile_two_merge_fwd<MB_FORWARD, true, false>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, true, false>,
+                          (const void *)&k_profile_two_merge_bwd<false>,
+                          (const void *)&k_profile_two_merge_fwd<MB_FORWARD, false, true>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, false, true>,
+                          (const void *)&k_profile_two_merge_fwd<MB_FORWARD, true, true>, (const void *)&k_profile_two_merge_fwd<MB_VITERBI, true, true>,
+                          (const void *)&k_profile_two_merge_bwd<true>},
+                         "k_profile_two_merge: raising the LDS limit");
 }
 
 // The launchers: each sweep once over a form of the lattice, and the two overloads of the header that name one.
