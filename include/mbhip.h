@@ -400,6 +400,26 @@ int mb_profile_two_fill_env(mb_machine *m, int mode, const double *logA, int64_t
                             const int32_t *envStart, const int32_t *envEnd, double *cellsOut);
 int64_t mb_profile_twos_cells(const mb_profile_twos *p);   /* doubles of all materialised lattices under the current envelopes */
 
+/* Posterior path samples of the pairs of profiles (docs/profile_tapes.md, "Posterior path samples of pairs of profiles"): nSamples
+ * alignments per pair, each drawn with its posterior probability by a stochastic traceback over the pair's materialised Forward
+ * lattice, on the device.  Path k * nSamples + j is sample j of pair k, in the format of mb_profile_twos_viterbi (global edge ids
+ * start -> end, pathRow and pathInRow as there, either may be NULL; blanks on either tape are not edges);
+ * pathLogProb[k * nSamples + j] (may be NULL) is the log posterior probability of that path: its own log weight, the blank of every
+ * row of either tape that no edge consumed included, minus loglike[k].  From Z[K][rows][S-1] back to N[0][0][0] every visit of a Z
+ * cell with i > 0, of a W cell, or of an N cell with row > 0 is one decision among the terms of the fill in the fill's order (the
+ * Viterbi candidate order above; a Z cell with i = 0 holds its W and is none): p_c = exp(term_c - cell), the first c whose running
+ * sum exceeds u, else the last c with p_c > 0.  A decision takes one counter value however many of its candidates exist.  The
+ * uniforms are those of mb_profile_pairs_sample -- Philox4x32-10 under (seed; t, j, k) with k the pair's index in the object --, so
+ * a sample depends on nothing but (seed, k, j), not on chunking, the pairs beside it or nSamples.  A pair whose likelihood is -inf
+ * gets empty paths and -inf.  Under envelopes the samples are drawn over their cells.  The call runs one materialised Forward sweep
+ * and one sample launch per chunk; it chunks under the memory budget by a pair's lattice plus nSamples * (12 * bound + 16) bytes.
+ * Errors, before anything is launched: nSamples < 1, NULL pathOff or pathEdges, a pathCap below nSamples times the sum of
+ * mb_profile_pair_path_bound over the pairs, a merged object ("sampling takes plain profiles"), more than 2^31 - 1 (pair, sample)
+ * lanes in one chunk, a pair beyond the memory budget on its own. */
+int mb_profile_twos_sample(mb_profile_twos *p, int64_t nSamples, uint64_t seed, double *loglike /* [nPairs] or NULL */,
+                           int64_t *pathOff /* [nPairs*nSamples + 1] */, uint32_t *pathEdges, int32_t *pathRow /* or NULL */,
+                           int32_t *pathInRow /* or NULL */, double *pathLogProb /* [nPairs*nSamples] or NULL */, int64_t pathCap);
+
 /* Pairs of profiles against a CTC-merged output profile (mb_profile_two_merge.hip; docs/profile_tapes.md, "Pairs of profiles
  * against a merged profile"): the input profile as above, the output rows those of mb_profiles_create_merged -- logB rows of
  * nCols + 1 doubles, column 0 the blank, column c the CSV column whose output token is colTok[c - 1], one column map per batch

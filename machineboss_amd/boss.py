@@ -923,6 +923,48 @@ def scoreTwoProfiles(machine: Machine, inProfiles, outProfile, backend: str = "d
     return scores, (acc.paramCounts(machine, params) if counts else None)
 
 
+def sampleTwoProfiles(machine: Machine, inProfiles, outProfile, nSamples: int, seed: int = 0, backend: str = "device", params=None,
+                      band: Optional[int] = None):
+    """``nSamples`` alignments of every input profile with ``outProfile`` drawn from the posterior (docs/profile_tapes.md,
+    "Posterior path samples of pairs of profiles"), the pairs of scoreTwoProfiles in one batch.  Returns (paths, logq, loglike):
+    paths[k][j] is sample j of input profile k as a MachinePath (dp.edgesToPath), logq[k][j] its log posterior probability -- the
+    path's own log weight with the blanks of both tapes, minus loglike[k] -- and loglike[k] the Forward log-likelihood.  A pair that
+    scores -inf gets empty paths and logq = -inf.  A sample depends on (seed, k, j) alone.  ``backend``: "device"
+    (capi.DeviceProfileTwos.sample_paths) or "numpy" (profile.TwoProfileDP.samplePaths).  ``band``: as scoreTwoProfiles."""
+    import numpy as np
+    from . import dp
+    from .profile import TwoProfileDP
+    from .seqpair import Envelope
+    if backend not in ("device", "numpy"):
+        raise MachineError('backend is "device" or "numpy"')
+    nSamples = int(nSamples)
+    if nSamples < 1:
+        raise MachineError("nSamples must be at least 1")
+    ev = EvaluatedMachine.fromMachine(machine, params)
+    if not ev.nInTok:
+        raise MachineError("two-profile sweeps need a machine with an input alphabet")
+    As = [a.logRowsIn(ev) for a in inProfiles]
+    B = outProfile.logRows(ev)
+    envs = None if band is None else [Envelope.band(len(A), len(B), int(band)) for A in As]
+    if backend == "numpy":
+        tdp = TwoProfileDP(ev)
+        ll, got = [], []
+        for k, A in enumerate(As):
+            l, samples = tdp.samplePaths(A, B, nSamples, seed=seed, pair=k, env=None if envs is None else envs[k])
+            ll.append(l); got.append([(s[0], s[3]) for s in samples])
+    else:
+        from . import capi
+        dm = capi.DeviceMachine(ev)
+        twos = capi.DeviceProfileTwos(dm, As, [B] * len(As), envs=envs)
+        try:
+            ll, off, edges, _rows, _ins, lq = twos.sample_paths(nSamples, seed=seed)
+        finally:
+            twos.close(); dm.close()
+        got = [[(edges[off[k * nSamples + j]:off[k * nSamples + j + 1]], lq[k * nSamples + j]) for j in range(nSamples)] for k in range(len(As))]
+    paths = [[dp.edgesToPath(ev, machine, e) for e, _q in samples] for samples in got]
+    return paths, [[float(q) for _e, q in samples] for samples in got], [float(l) for l in ll]
+
+
 def scoreMergedTwos(machine: Machine, inProfiles, outProfile, backend: str = "device", params=None, loglike: bool = True,
                     viterbi: bool = False, counts: bool = False, posteriors: bool = False, band: Optional[int] = None):
     """scoreTwoProfiles(merge=True) with everything the merged two-profile pairs have: every input profile (a profile.Profile read

@@ -41,7 +41,7 @@ EXPORTS = [
     "mb_profile_twos_create", "mb_profile_twos_destroy", "mb_profile_twos_forward", "mb_profile_twos_viterbi", "mb_profile_twos_counts",
     "mb_profile_twos_row_posteriors", "mb_profile_twos_set_rows",
     "mb_profile_two_fill",
-    "mb_profile_twos_set_envelopes", "mb_profile_two_fill_env", "mb_profile_twos_cells",
+    "mb_profile_twos_set_envelopes", "mb_profile_two_fill_env", "mb_profile_twos_cells", "mb_profile_twos_sample",
     "mb_profile_twos_set_envelopes_merged", "mb_profile_two_fill_merged_env",
     "mb_profile_twos_create_merged", "mb_profile_two_fill_merged", "mb_profile_twos_row_posteriors_merged",
     "mb_prefix_create", "mb_prefix_destroy", "mb_prefix_root", "mb_prefix_extend", "mb_prefix_release", "mb_prefix_free_nodes",
@@ -159,6 +159,7 @@ def load():
     L.mb_profile_twos_destroy.argtypes = [vp]; L.mb_profile_twos_destroy.restype = None
     L.mb_profile_twos_forward.argtypes = [vp, C.c_int, dp]
     L.mb_profile_twos_viterbi.argtypes = [vp, dp, i64p, u32p, i32p, i32p, C.c_int64]
+    L.mb_profile_twos_sample.argtypes = [vp, C.c_int64, C.c_uint64, dp, i64p, u32p, i32p, i32p, dp, C.c_int64]
     L.mb_profile_twos_counts.argtypes = [vp, dp, dp, dp]
     L.mb_profile_twos_row_posteriors.argtypes = [vp, dp, dp, dp]
     L.mb_profile_twos_row_posteriors_merged.argtypes = [vp, dp, dp, dp]
@@ -1041,6 +1042,23 @@ class DeviceProfileTwos:
         _check(load().mb_profile_twos_viterbi(self.h, _p(ll, C.c_double), _p(off, C.c_int64), _p(edges, C.c_uint32), _p(rows, C.c_int32),
                                               _p(ins, C.c_int32), cap))
         return ll, off, edges[:off[-1]].copy(), rows[:off[-1]].copy(), ins[:off[-1]].copy()
+
+    def sample_paths(self, nSamples: int, seed: int = 0, cap: Optional[int] = None):
+        """``nSamples`` alignments per pair drawn from the posterior on the device (mb_profile_twos_sample; docs/profile_tapes.md,
+        "Posterior path samples of pairs of profiles").  Returns (loglike[nPairs], off[nPairs * nSamples + 1], edges, rows, inRows,
+        logq[nPairs * nSamples]): path k * nSamples + j is sample j of pair k in the format of viterbi(), logq its log posterior
+        probability.  A sample depends on (seed, k, j) alone.  ``cap``: the size of the path buffers (default: nSamples times
+        path_cap()).  Plain profiles only, with or without envelopes.  The yardstick is profile.TwoProfileDP.samplePaths with
+        ``pair=k``."""
+        nSamples = int(nSamples)
+        cap = self.path_cap() * max(nSamples, 0) if cap is None else int(cap)
+        n = self.nPairs * max(nSamples, 0)
+        ll = np.empty(self.nPairs, np.float64)
+        off = np.zeros(n + 1, np.int64); logq = np.empty(n, np.float64)
+        edges = np.empty(max(cap, 1), np.uint32); rows = np.empty(max(cap, 1), np.int32); ins = np.empty(max(cap, 1), np.int32)
+        _check(load().mb_profile_twos_sample(self.h, nSamples, int(seed) & 0xffffffffffffffff, _p(ll, C.c_double), _p(off, C.c_int64),
+                                             _p(edges, C.c_uint32), _p(rows, C.c_int32), _p(ins, C.c_int32), _p(logq, C.c_double), cap))
+        return ll, off, edges[:off[-1]].copy(), rows[:off[-1]].copy(), ins[:off[-1]].copy(), logq
 
     def counts(self, counts: Optional[np.ndarray] = None):
         """Returns (counts[nTrans], loglikeSum, loglike[nPairs]); accumulates into ``counts`` if given."""

@@ -116,6 +116,49 @@ static int unpack_paths(PathSink &o, long long k0, long long np, long long paths
   return 0;
 }
 
+// The caller's arrays of a sample call (nS samples per item) and the host staging of one chunk; inRow: the third array of the
+// two-profile pairs.
+struct SampleSink {
+  int64_t *off; uint32_t *edges; int32_t *row, *inRow; double *logProb;
+  long long nS;
+  std::function<long long(long long)> bound;
+  long long written = 0;
+  std::vector<long long> len;
+  std::vector<double> lq;
+  std::vector<uint32_t> he;
+  std::vector<int32_t> hr, hi;
+};
+
+// The sampled paths of chunk items [k0, k0 + np) from the device to the caller's arrays, packed: path (k0 + k) * nS + j is sample j
+// of item k.  Lengths and log probabilities lie where the item's lanes were (slot: in which place of the chunk each item ran,
+// nullptr = in order); the path slots (entries: all of the chunk's) are packed in item order, bound(k) entries per sample.
+static int unpack_samples(SampleSink &o, long long k0, long long np, long long entries, const std::vector<long long> *slot, const long long *d_len, const double *d_lq,
+                          const uint32_t *d_e, const int32_t *d_r, const int32_t *d_i = nullptr) {
+  const long long lanes = np * o.nS;
+  o.len.resize((size_t)std::max<long long>(lanes, 1)); o.lq.resize(o.len.size());
+  o.he.resize((size_t)std::max<long long>(entries, 1)); o.hr.resize(o.row ? o.he.size() : 0); o.hi.resize(o.inRow ? o.he.size() : 0);
+  if (lanes && (d2h_large(o.len.data(), d_len, (size_t)lanes * sizeof(long long)) || d2h_large(o.lq.data(), d_lq, (size_t)lanes * sizeof(double)))) return 1;
+  if (!lanes && !hip_ok(hipStreamSynchronize(g_stream), "sample launch")) return 1;
+  if (entries && (d2h_large(o.he.data(), d_e, (size_t)entries * sizeof(uint32_t)) || (o.row && d2h_large(o.hr.data(), d_r, (size_t)entries * sizeof(int32_t))) ||
+                  (o.inRow && d2h_large(o.hi.data(), d_i, (size_t)entries * sizeof(int32_t))))) return 1;
+  long long base = 0;
+  for (long long k = 0; k < np; ++k) {
+    const long long bound = o.bound(k0 + k), at = (slot ? (*slot)[(size_t)k] : k) * o.nS;
+    for (long long j = 0; j < o.nS; ++j, base += bound) {
+      long long n = o.len[(size_t)(at + j)];
+      if (n == -1) n = 0;      // a dead pair: empty paths, logq = -inf
+      else if (n < 0) { set_error(n == -2 ? "pair sample overflowed its bound" : "pair sample found no candidate with a positive probability"); return 1; }
+      std::memcpy(o.edges + o.written, o.he.data() + base, (size_t)n * sizeof(uint32_t));
+      if (o.row) std::memcpy(o.row + o.written, o.hr.data() + base, (size_t)n * sizeof(int32_t));
+      if (o.inRow) std::memcpy(o.inRow + o.written, o.hi.data() + base, (size_t)n * sizeof(int32_t));
+      o.written += n;
+      o.off[(k0 + k) * o.nS + j + 1] = o.written;
+      if (o.logProb) o.logProb[(k0 + k) * o.nS + j] = o.lq[(size_t)(at + j)];
+    }
+  }
+  return 0;
+}
+
 // the workgroups per item of the count kernels of the pairs and the two-profile pairs: one per 2 048 cells of the largest lattice, 256 at the most
 template <class Cells> static int count_groups(long long p0, long long p1, Cells cells) {
   long long maxCells = 0;
@@ -877,11 +920,8 @@ static int pair_profile_sample(mb_profile_pairs *p, bool merged, int64_t nSample
   SmBuf<double> d_ll;
   MB_HIP(d_ll.alloc(p->n));
   const int nS = (int)nSamples;
-  std::vector<long long> hlen, hidx;
-  std::vector<double> hlq;
-  std::vector<uint32_t> he;
-  std::vector<int32_t> hr;
-  long long written = 0;
+  std::vector<long long> hidx;
+  SampleSink out{pathOff, pathEdges, pathRow, nullptr, pathLogProb, nSamples, [&](long long k) { return pp_path_bound(p, k); }};
   pathOff[0] = 0;
   PairWhere where;
   int rc = for_chunks<PairProfPlan>(chunks, pp_build(p, false, where), [&](const Chunk &c, PairProfPlan &pl, Timer &tm) {
@@ -916,28 +956,9 @@ static int pair_profile_sample(mb_profile_pairs *p, bool merged, int64_t nSample
       }
     }
     // lengths and log probabilities landed in slot order, the path slots are packed in pair order
-    hlen.resize((size_t)std::max<long long>(lanes, 1)); hlq.resize(hlen.size());
-    he.resize((size_t)std::max<long long>(entries, 1)); hr.resize(pathRow ? he.size() : 0);
-    if (lanes && (d2h_large(hlen.data(), d_len, (size_t)lanes * sizeof(long long)) || d2h_large(hlq.data(), d_lq, (size_t)lanes * sizeof(double)))) return 1;
-    if (!lanes && !hip_ok(hipStreamSynchronize(g_stream), "sample launch")) return 1;
-    if (entries && (d2h_large(he.data(), d_e, (size_t)entries * sizeof(uint32_t)) || (pathRow && d2h_large(hr.data(), d_r, (size_t)entries * sizeof(int32_t))))) return 1;
+    if (unpack_samples(out, c.p0, np, entries, &pl.slot, d_len, d_lq, d_e, d_r)) return 1;
     // (the chunk's block of rowCol is already in pair order: rows of the object from row0 on, nSamples lines per pair)
-    if (rowCol && colEntries && d2h_large(rowCol + (row0 - p->rowOff[0]) * nS, d_rc, (size_t)colEntries * sizeof(int32_t))) return 1;
-    long long base = 0;
-    for (long long k = 0; k < np; ++k) {
-      const long long bound = pp_path_bound(p, c.p0 + k), at = pl.slot[(size_t)k] * nS;
-      for (long long j = 0; j < nS; ++j, base += bound) {
-        long long n = hlen[(size_t)(at + j)];
-        if (n == -1) n = 0;      // a dead pair: empty paths, logq = -inf
-        else if (n < 0) { set_error(n == -2 ? "pair sample overflowed its bound" : "pair sample found no candidate with a positive probability"); return 1; }
-        std::memcpy(pathEdges + written, he.data() + base, (size_t)n * sizeof(uint32_t));
-        if (pathRow) std::memcpy(pathRow + written, hr.data() + base, (size_t)n * sizeof(int32_t));
-        written += n;
-        pathOff[(c.p0 + k) * nS + j + 1] = written;
-        if (pathLogProb) pathLogProb[(c.p0 + k) * nS + j] = hlq[(size_t)(at + j)];
-      }
-    }
-    return 0;
+    return rowCol && colEntries && d2h_large(rowCol + (row0 - p->rowOff[0]) * nS, d_rc, (size_t)colEntries * sizeof(int32_t)) ? 1 : 0;
   });
   if (!rc && loglike) rc = fetch_loglike(loglike, d_ll, p->n, &where);
   if (merged) g_last_kernel = p->hasEnv ? "k_profile_pair_merge_env_sample" : "k_profile_pair_merge_sample";
@@ -1452,6 +1473,56 @@ int mb_profile_twos_viterbi(mb_profile_twos *p, double *loglike, int64_t *pathOf
   });
   if (!rc) rc = fetch_loglike(loglike, d_ll, p->n);
   g_last_kernel = pt_fwd_name(p, MB_VITERBI, true);
+  return rc;
+}
+
+// Per chunk one materialised Forward launch and one sample launch.  The pairs of a chunk run in their order (TwoProfPlan), so the
+// index in the object of the pair a lane serves is c.p0 plus its place in the chunk.
+int mb_profile_twos_sample(mb_profile_twos *p, int64_t nSamples, uint64_t seed, double *loglike, int64_t *pathOff, uint32_t *pathEdges, int32_t *pathRow,
+                           int32_t *pathInRow, double *pathLogProb, int64_t pathCap) {
+  ApiGuard guard;
+  g_last_ms = 0.0; g_last_launches = 0;
+  if (!p || !pathOff || !pathEdges) { set_error("null argument"); return 1; }
+  if (p->nCols) { set_error("sampling takes plain profiles"); return 1; }
+  if (nSamples < 1) { set_error("nSamples must be at least 1"); return 1; }
+  double need = 0.0;
+  for (long long k = 0; k < p->n; ++k) need += (double)pt_path_bound(p, k);
+  need *= (double)nSamples;
+  if ((double)pathCap < need) {
+    set_error("pathCap too small for the sampled paths: " + std::to_string((long long)pathCap) + " entries, nSamples times the path bounds of the pairs is " +
+              std::to_string((long long)need));
+    return 1;
+  }
+  // a pair costs its lattice, and per sample a path slot (an edge and both rows per entry), a length and a log probability
+  std::vector<Chunk> chunks;
+  auto bytes = [&](long long k) { return pt_cell_bytes(p, k) + pt_ring_bytes(p, k, false) + (double)nSamples * (12.0 * (double)pt_path_bound(p, k) + 16.0); };
+  if (!lattice_chunks(p->n, "pair", bytes, chunks)) return 1;
+  for (const Chunk &c : chunks)
+    if ((double)(c.p1 - c.p0) * (double)nSamples > 2147483647.0) { set_error("too many samples in one chunk: pairs times nSamples exceeds 2^31 - 1 lanes"); return 1; }
+  SmBuf<double> d_ll;
+  MB_HIP(d_ll.alloc(p->n));
+  const int nS = (int)nSamples;
+  SampleSink out{pathOff, pathEdges, pathRow, pathInRow, pathLogProb, nSamples, [&](long long k) { return pt_path_bound(p, k); }};
+  pathOff[0] = 0;
+  int rc = for_chunks<TwoProfPlan>(chunks, pt_build(p, false), [&](const Chunk &c, TwoProfPlan &pl, Timer &tm) {
+    const long long np = c.p1 - c.p0, lanes = np * nS, entries = pl.paths * nS;
+    double *pool = ws_array<double>(0, pl.cells);
+    uint32_t *d_e = ws_array<uint32_t>(3, entries);
+    int32_t *d_r = ws_array<int32_t>(4, entries);
+    int32_t *d_i = ws_array<int32_t>(5, entries);
+    long long *d_len = ws_array<long long>(6, lanes);
+    double *d_lq = ws_array<double>(7, lanes);
+    if (!pool || !d_e || !d_r || !d_i || !d_len || !d_lq) return 1;
+    {
+      Timed t(tm, 1);
+      if (pt_fwd_mat(p, MB_FORWARD, pl, np, pool, nullptr, d_ll + c.p0)) return 1;
+      if (p->hasEnv ? launch_profile_two_sample(p->m, pl.e.p, pt_env_tables(p), (int)np, nS, c.p0, seed, p->d_logA, p->d_logB, pool, d_e, d_r, d_i, d_len, d_lq, g_stream)
+                    : launch_profile_two_sample(p->m, pl.d.p, (int)np, nS, c.p0, seed, p->d_logA, p->d_logB, pool, d_e, d_r, d_i, d_len, d_lq, g_stream)) return 1;
+    }
+    return unpack_samples(out, c.p0, np, entries, nullptr, d_len, d_lq, d_e, d_r, d_i);
+  });
+  if (!rc && loglike) rc = fetch_loglike(loglike, d_ll, p->n);
+  g_last_kernel = p->hasEnv ? "k_profile_two_env_sample" : "k_profile_two_sample";
   return rc;
 }
 

@@ -1,7 +1,7 @@
 // mb_profile_common.h -- what the profile sweeps share (mb_profile.hip, mb_profile_merge.hip, mb_profile_pair.hip,
 // mb_profile_pair_merge.hip, mb_profile_two.hip, mb_profile_two_merge.hip, mb_profile_post.hip): the reduction of a sweep's mode, the LDS a ring may take and the raising of its limit, the lanes of a workgroup, the reversal of a path, the
 // accumulator of the posterior counts, the add of the row posteriors, and the generator and the draw of the path samplers
-// (k_profile_pair_sample, k_profile_pair_merge_sample).  Device code: included by .hip files only.
+// (k_profile_pair_sample, k_profile_pair_merge_sample, k_profile_two_sample).  Device code: included by .hip files only.
 #pragma once
 #include <algorithm>
 #include <initializer_list>

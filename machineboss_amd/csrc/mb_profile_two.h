@@ -35,6 +35,11 @@ int launch_profile_two_rowpost(const mb_machine *m, int axis, const PairProfDesc
                                const double *logB, const double *fwdPool, const double *bwdPool, double *post, hipStream_t st);
 int launch_profile_two_traceback(const mb_machine *m, const PairProfDesc *d, int n, const double *logA, const double *logB, const double *pool,
                                  uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, hipStream_t st);
+// Posterior path samples over the n pairs' materialised sum lattices (k_profile_two_sample): nSamples lanes per pair, n * nSamples
+// at most 2^31 - 1.  pair0: the index in the object of the chunk's first pair (the counter of the uniforms).  The slot of sample j of
+// a pair is at (pathBase * nSamples + j * bound) of edges / rows / inRows; len and logq are [n * nSamples], pair-major.
+int launch_profile_two_sample(const mb_machine *m, const PairProfDesc *d, int n, int nSamples, long long pair0, unsigned long long seed, const double *logA,
+                              const double *logB, const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, double *logq, hipStream_t st);
 
 }  // namespace mb
 

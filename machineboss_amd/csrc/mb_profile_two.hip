@@ -501,6 +501,104 @@ __global__ void k_profile_two_traceback(DevMachine m, const typename Geom<true>:
   len[k] = cnt;
 }
 
+// Posterior path samples over a materialised SUM lattice (docs/profile_tapes.md, "Posterior path samples of pairs of profiles"), one
+// lane per (pair, sample) as k_profile_pair_sample (mb_profile_pair.hip): lane id serves pair id / nSamples of the chunk, sample
+// id % nSamples.  From Z[K][L][S-1] back to N[0][0][0]; every Z cell with i > 0, every W cell and every N cell with r > 0 is one
+// decision among the terms of the fill, in the fill's order and parenthesisation -- the list k_profile_two_traceback enumerates --
+// each with probability exp(term - cell).  A Z cell with i = 0 holds its W and draws nothing; a Z cell whose input blank lies
+// outside the geometry has one candidate and still takes a counter value.  The uniform of decision t of sample j of pair k
+// (pair0 + the pair's place in the chunk: its index in the object) is philox_uniform(t, j, k, seed).  SampleDraw's kind: 0 the
+// candidate without an edge (wait, stay, the output blank; at a Z cell 1 is the input blank), 1 an edge that reads an input row
+// (its source is a Z cell), 2 an edge that reads none (its source is a W cell).  Edges and both coordinates go into the sample's
+// slot, at (pathBase * nSamples + j * bound), backwards and are reversed at the end; len and logq are k_profile_pair_sample's.
+template <template <bool> class Geom>
+__global__ __launch_bounds__(64) void k_profile_two_sample(DevMachine m, const typename Geom<true>::Desc *__restrict__ descs, typename Geom<true>::Tables t, long long nLanes,
+                                                           int nSamples, long long pair0, unsigned long long seed, const double *__restrict__ logA,
+                                                           const double *__restrict__ logB, const double *__restrict__ pool, uint32_t *edges, int32_t *rows,
+                                                           int32_t *inRows, long long *len, double *logq) {
+  const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= nLanes) return;
+  const int slot = (int)(id / nSamples), j = (int)(id - (long long)slot * nSamples);
+  const auto pd = descs[slot];
+  const unsigned long long k = (unsigned long long)(pair0 + slot);
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32), c2 = (uint32_t)k, c3 = (uint32_t)(k >> 32);
+  const int S = m.S, KK = m.K, C = m.nOut + 1, CA = m.nIn + 1, K = pd.nIn, L = pd.nRows;
+  const double *A = logA + pd.inBase * CA;
+  const double *B = logB + pd.rowBase * C;
+  const Geom<true> lat(pd, t, const_cast<double *>(pool) + pd.cellBase, S);
+  const long long cap = K + L + (long long)(K + L + 1) * (m.nLevF - 1);
+  const long long at = pd.pathBase * nSamples + (long long)j * cap;
+  uint32_t *pe = edges + at;
+  int32_t *pr = rows + at, *pi = inRows + at;
+  int i = K, r = L, q = S - 1, layer = 2;
+  long long cnt = 0;
+  uint32_t dec = 0;
+  double lq = 0.0;
+  if (!(lat.at(i, r, 2)[q] > -INFINITY)) { len[id] = -1; logq[id] = -INFINITY; return; }
+  for (;;) {
+    if (layer == 2 && i == 0) layer = 1;      // (Z[0][r] is W[0][r]: nothing to decide)
+    if (layer == 0 && r == 0) { if (i != 0 || q != 0) { len[id] = -3; logq[id] = lq; return; } break; }
+    const double *Ai = A + (long long)max(i - 1, 0) * CA;      // row i - 1; read when i > 0
+    const double *Br = B + (long long)max(r - 1, 0) * C;       // row r - 1; read at an N cell
+    SampleDraw d(philox_uniform(dec++, (uint32_t)j, c2, c3, k0, k1), lat.at(i, r, layer)[q]);
+    if (layer == 2) {
+      d.offer(lat.at(i, r, 1)[q], 0, 0, q);
+      if (lat.inside(i - 1, r)) d.offer(lat.at(i - 1, r, 2)[q] + Ai[0], 1, 0, q);
+    } else if (layer == 1) {
+      const double *W = lat.at(i, r, 1);
+      d.offer(lat.at(i, r, 0)[q], 0, 0, q);
+      if (i > 0 && lat.inside(i - 1, r)) {
+        const double *Zl = lat.at(i - 1, r, 2);
+        for (int a = 1; a <= m.nIn && !d.done; ++a) {
+          const int row = q * KK + a * C;
+          const double wa = Ai[a];
+          const int e1 = m.inOff[row + 1];
+          for (int e = m.inOff[row]; e < e1 && !d.done; ++e) d.offer((Zl[m.inSrc[e]] + m.inW[e]) + wa, 1, e, (int)m.inSrc[e]);
+        }
+      }
+      const int e1 = m.inOff[q * KK + 1];
+      for (int e = m.inOff[q * KK]; e < e1 && !d.done; ++e) {
+        const int s = (int)m.inSrc[e];
+        if (s < q) d.offer(W[s] + m.inW[e], 2, e, s);
+      }
+    } else {
+      const bool up = lat.inside(i, r - 1);
+      if (up) d.offer(lat.at(i, r - 1, 0)[q] + Br[0], 0, 0, q);
+      if (i > 0 && lat.inside(i - 1, r - 1)) {
+        const double *Zd = lat.at(i - 1, r - 1, 2);
+        for (int a = 1; a <= m.nIn && !d.done; ++a) {
+          const int row = q * KK + a * C;
+          const double wa = Ai[a];
+          const int e1 = m.inOff[row + C];
+          for (int e = m.inOff[row + 1]; e < e1 && !d.done; ++e)
+            d.offer(((Zd[m.inSrc[e]] + m.inW[e]) + wa) + Br[m.eOutTok[m.inEid[e]]], 1, e, (int)m.inSrc[e]);
+        }
+      }
+      if (up) {
+        const double *Wu = lat.at(i, r - 1, 1);
+        const int e1 = m.inOff[q * KK + C];
+        for (int e = m.inOff[q * KK + 1]; e < e1 && !d.done; ++e)
+          d.offer((Wu[m.inSrc[e]] + m.inW[e]) + Br[m.eOutTok[m.inEid[e]]], 2, e, (int)m.inSrc[e]);
+      }
+    }
+    if (d.kind < 0) { len[id] = -3; logq[id] = lq; return; }
+    lq += d.term - d.cur;
+    if (layer == 2) {      // wait, or the input blank: no edge
+      if (d.kind == 0) layer = 1; else --i;
+      continue;
+    }
+    if (layer == 0) --r;
+    if (d.kind == 0) { layer = 0; continue; }      // (stay: W -> N; the output blank: N -> N)
+    if (cnt >= cap) { len[id] = -2; logq[id] = lq; return; }
+    if (d.kind == 1) --i;
+    pe[cnt] = m.inEid[d.a]; pr[cnt] = r; pi[cnt] = i; ++cnt;
+    q = d.src; layer = d.kind == 1 ? 2 : 1;
+  }
+  reverse_path(cnt, pe, pr, pi);
+  len[id] = cnt;
+  logq[id] = lq;
+}
+
 // The launchers: each sweep once over a geometry, and the two overloads of the headers that name one.
 template <template <bool> class Geom>
 static int two_fwd(const mb_machine *m, int mode, bool mat, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, size_t lds, long long maxItems,
@@ -596,6 +694,25 @@ int launch_profile_two_traceback(const mb_machine *m, const PairProfDesc *d, int
 int launch_profile_two_traceback(const mb_machine *m, const TwoEnvDesc *d, const TwoEnvTables &t, int n, const double *logA, const double *logB, const double *pool,
                                  uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, hipStream_t st) {
   return two_traceback<TwoEnvGeom>(m, d, t, n, logA, logB, pool, edges, rows, inRows, len, st);
+}
+
+template <template <bool> class Geom>
+static int two_sample(const mb_machine *m, const typename Geom<true>::Desc *d, typename Geom<true>::Tables t, int n, int nSamples, long long pair0, unsigned long long seed,
+                      const double *logA, const double *logB, const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, double *logq,
+                      hipStream_t st) {
+  if (n <= 0) return 0;
+  const long long nLanes = (long long)n * nSamples;
+  k_profile_two_sample<Geom><<<(unsigned)((nLanes + 63) / 64), 64, 0, st>>>(m->dev, d, t, nLanes, nSamples, pair0, seed, logA, logB, pool, edges, rows, inRows, len, logq);
+  return hip_ok(hipGetLastError(), Geom<true>::ENV ? "k_profile_two_env_sample" : "k_profile_two_sample") ? 0 : 1;
+}
+int launch_profile_two_sample(const mb_machine *m, const PairProfDesc *d, int n, int nSamples, long long pair0, unsigned long long seed, const double *logA,
+                              const double *logB, const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, double *logq, hipStream_t st) {
+  return two_sample<TwoGeom>(m, d, {}, n, nSamples, pair0, seed, logA, logB, pool, edges, rows, inRows, len, logq, st);
+}
+int launch_profile_two_sample(const mb_machine *m, const TwoEnvDesc *d, const TwoEnvTables &t, int n, int nSamples, long long pair0, unsigned long long seed,
+                              const double *logA, const double *logB, const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len,
+                              double *logq, hipStream_t st) {
+  return two_sample<TwoEnvGeom>(m, d, t, n, nSamples, pair0, seed, logA, logB, pool, edges, rows, inRows, len, logq, st);
 }
 
 }  // namespace mb

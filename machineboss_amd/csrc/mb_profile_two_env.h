@@ -41,5 +41,8 @@ int launch_profile_two_rowpost(const mb_machine *m, int axis, const TwoEnvDesc *
                                const double *logB, const double *fwdPool, const double *bwdPool, double *post, hipStream_t st);
 int launch_profile_two_traceback(const mb_machine *m, const TwoEnvDesc *d, const TwoEnvTables &t, int n, const double *logA, const double *logB, const double *pool,
                                  uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len, hipStream_t st);
+int launch_profile_two_sample(const mb_machine *m, const TwoEnvDesc *d, const TwoEnvTables &t, int n, int nSamples, long long pair0, unsigned long long seed,
+                              const double *logA, const double *logB, const double *pool, uint32_t *edges, int32_t *rows, int32_t *inRows, long long *len,
+                              double *logq, hipStream_t st);
 
 }  // namespace mb

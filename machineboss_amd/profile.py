@@ -1627,6 +1627,155 @@ class TwoProfileDP(PairProfileDP):
                 edges.append(e); rows.append(r); ins.append(i); q = s; layer = 2
         return v, np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32), np.array(ins[::-1], np.int32)
 
+    def sampleCandidates(self, A, B, N, W, Z, inside, i: int, r: int, q: int, layer: int):
+        """The candidates of the sampling decision at cell (i, r, q) of ``layer`` (2: Z with i > 0, 1: W, 0: N with r > 0) over the
+        sum lattice (N, W, Z): (kind, edge id or -1, source state, term) in the fill's order, the list viterbi() enumerates.
+        ``inside``: per input row the set of its output rows, or None; a candidate whose source cell lies outside is left out."""
+        ok = (lambda si, sr: True) if inside is None else (lambda si, sr: sr in inside[si])
+        mE, mS, mD, mW, mA, mO = self.mAll
+        iE, iS, iD, iW, iA, _ = self.iAll
+        cand = []
+        if layer == 2:
+            cand.append(("wait", -1, q, float(W[i, r, q])))
+            if ok(i - 1, r):
+                cand.append(("inblank", -1, q, float(Z[i - 1, r, q] + A[i - 1][0])))
+        elif layer == 1:
+            cand.append(("stay", -1, q, float(N[i, r, q])))
+            if i and ok(i - 1, r):
+                cand += [("ins", int(iE[k]), int(iS[k]), float((Z[i - 1, r, iS[k]] + iW[k]) + A[i - 1][iA[k]])) for k in np.nonzero(iD == q)[0]]
+            cand += [("silent", int(self.sId[k]), int(self.sS[k]), float(W[i, r, self.sS[k]] + self.sW[k])) for k in self.inSil[q]]
+        else:
+            Br = B[r - 1]
+            up = ok(i, r - 1)
+            if up:
+                cand.append(("blank", -1, q, float(N[i, r - 1, q] + Br[0])))
+            if i and ok(i - 1, r - 1):
+                cand += [("match", int(mE[k]), int(mS[k]), float(((Z[i - 1, r - 1, mS[k]] + mW[k]) + A[i - 1][mA[k]]) + Br[mO[k]]))
+                         for k in np.nonzero(mD == q)[0]]
+            if up:
+                cand += [("emit", int(self.eId[k]), int(self.eS[k]), float((W[i, r - 1, self.eS[k]] + self.eW[k]) + Br[self.eO[k]]))
+                         for k in self.inEmit[q]]
+        return cand
+
+    @staticmethod
+    def _sampleMove(kind: str, e: int, s: int, i: int, r: int, q: int, layer: int, edges: list, rows: list, ins: list):
+        """One taken candidate: the cell it leads back to, its edge (if it is one) appended with both coordinates."""
+        if kind == "wait":
+            return i, r, q, 1
+        if kind == "inblank":
+            return i - 1, r, q, 2
+        if kind == "stay":
+            return i, r, q, 0
+        if kind == "blank":
+            return i, r - 1, q, 0
+        if kind in ("match", "emit"):
+            r -= 1
+        if kind in ("match", "ins"):
+            i -= 1
+        edges.append(e); rows.append(r); ins.append(i)
+        return i, r, s, 2 if kind in ("match", "ins") else 1
+
+    def _sampleLattice(self, A, B, env):
+        A, B = self._checkTwo(A, B)
+        ll, N, W, Z = self.forward(A, B) if env is None else self.forward(A, B, env=env)
+        inside = self.envelopeRows(env, len(A), len(B))
+        if inside is not None:
+            inside = [set(rs) for rs in inside]
+        return A, B, ll, N, W, Z, inside
+
+    def samplePaths(self, A, B, nSamples: int, seed: int = 0, pair: int = 0, env=None, margins: Optional[list] = None):
+        """(loglike, [(edges, rows, inRows, logq), ...]): ``nSamples`` paths drawn from the posterior by a stochastic traceback over
+        forward(A, B, env=env) -- the yardstick of k_profile_two_sample (docs/profile_tapes.md, "Posterior path samples of pairs of
+        profiles").  From Z[K][L][S-1] back to N[0][0][0]; every visit of a Z cell with i > 0, of a W cell, or of an N cell with
+        r > 0 is one decision among sampleCandidates() and takes one counter value t, however many candidates it has; a Z cell with
+        i = 0 moves to its W without one.  The draw is PairProfileDP.samplePaths': p_c = exp(term_c - cell), acc adds them in order
+        from 0.0, the first c with u < acc is taken, else the last c with p_c > 0; u = sample_uniform(seed, pair, j, t).  logq sums
+        term - cell over the decisions: the path's log posterior probability.  Paths are as viterbi()'s; a -inf pair gives empty
+        paths and logq = -inf.  ``margins`` (a list) receives per decision the least |u - acc_c| over all partial sums acc_c of
+        the decision."""
+        A, B, ll, N, W, Z, inside = self._sampleLattice(A, B, env)
+        layers = (N, W, Z)
+        out = []
+        for j in range(int(nSamples)):
+            edges: List[int] = []; rows: List[int] = []; ins: List[int] = []
+            if not ll > _NEG:
+                out.append((np.zeros(0, np.uint32), np.zeros(0, np.int32), np.zeros(0, np.int32), _NEG))
+                continue
+            i, r, q, layer, t, logq = len(A), len(B), self.S - 1, 2, 0, 0.0
+            while layer or r > 0:
+                if layer == 2 and i == 0:
+                    layer = 1
+                    continue
+                cur = float(layers[layer][i, r, q])
+                cand = self.sampleCandidates(A, B, N, W, Z, inside, i, r, q, layer)
+                u = sample_uniform(seed, pair, j, t)
+                t += 1
+                acc, pick, last, margin = 0.0, None, None, math.inf
+                for c in cand:
+                    p = math.exp(c[3] - cur) if c[3] > _NEG else 0.0
+                    acc += p
+                    margin = min(margin, abs(u - acc))
+                    if p > 0.0:
+                        last = c
+                    if pick is None and u < acc:
+                        pick = c
+                if pick is None:
+                    pick = last
+                if pick is None:
+                    raise MachineError("samplePaths: no candidate with a positive probability")
+                if margins is not None:
+                    margins.append(margin)
+                kind, e, s, term = pick
+                logq += term - cur
+                i, r, q, layer = self._sampleMove(kind, e, s, i, r, q, layer, edges, rows, ins)
+            assert i == 0 and q == 0
+            out.append((np.array(edges[::-1], np.uint32), np.array(rows[::-1], np.int32), np.array(ins[::-1], np.int32), logq))
+        return ll, out
+
+    def pathProbability(self, A, B, edges, rows, inRows, env=None) -> float:
+        """The log posterior probability of one path (in the format of viterbi()): the path replayed backwards through the
+        decisions of samplePaths() over forward(A, B, env=env), the sum of term - cell over them.  The edges with both coordinates
+        fix every decision: an edge arrives at the input row it read plus one (at inRows, if it read none) and likewise on the
+        output tape, so at a Z cell the input blank is taken while the cell lies past the arrival of the edge before it, then at the
+        W cell that edge if it wrote nothing, else "stay", and at the N cell the output blank while the cell lies past the arrival.
+        Raises MachineError where the path leaves the lattice (or the envelope); -inf for a pair whose likelihood is -inf."""
+        A, B, ll, N, W, Z, inside = self._sampleLattice(A, B, env)
+        if not ll > _NEG:
+            return _NEG
+        layers = (N, W, Z)
+        em = self.em
+        edges = [int(e) for e in edges]; rows = [int(v) for v in rows]; inRows = [int(v) for v in inRows]
+        if not len(edges) == len(rows) == len(inRows):
+            raise MachineError("pathProbability: edges, rows and inRows differ in length")
+        p = len(edges) - 1
+        i, r, q, layer, logq = len(A), len(B), self.S - 1, 2, 0.0
+        sink: List[int] = []
+        while layer or r > 0:
+            if layer == 2 and i == 0:
+                layer = 1
+                continue
+            e = edges[p] if p >= 0 else -1
+            reads, writes = (bool(em.inTok[e]), bool(em.outTok[e])) if p >= 0 else (False, False)
+            ai, ar = (inRows[p] + reads, rows[p] + writes) if p >= 0 else (0, 0)      # where the edge before arrives
+            if layer == 2:
+                want = ("wait", -1) if ai == i else ("inblank", -1)
+            elif layer == 1:
+                want = (("ins" if reads else "silent"), e) if p >= 0 and not writes and (ai, ar) == (i, r) else ("stay", -1)
+            else:
+                want = (("match" if reads else "emit"), e) if p >= 0 and writes and (ai, ar) == (i, r) else ("blank", -1)
+            cur = float(layers[layer][i, r, q])
+            hit = [c for c in self.sampleCandidates(A, B, N, W, Z, inside, i, r, q, layer) if (c[0], c[1]) == want]
+            if len(hit) != 1 or not hit[0][3] > _NEG:
+                raise MachineError("pathProbability: the path leaves the lattice at (%d, %d, %d)" % (i, r, q))
+            kind, e, s, term = hit[0]
+            logq += term - cur
+            if e >= 0:
+                p -= 1
+            i, r, q, layer = self._sampleMove(kind, e, s, i, r, q, layer, sink, sink, sink)
+        if i != 0 or q != 0 or p >= 0:
+            raise MachineError("pathProbability: the path does not reach the start")
+        return logq
+
 
 class TwoMergedProfileDP(TwoProfileDP):
     """A machine WITH an input alphabet between an input profile and a CTC-MERGED output profile, in numpy -- the yardstick of
@@ -1691,6 +1840,12 @@ class TwoMergedProfileDP(TwoProfileDP):
         S = self.S
         idx = (np.arange(self.PL)[:, None] * S + d[None, :]).ravel()
         return fold(base.ravel(), idx, vals.ravel()).reshape(self.PL, S)
+
+    def sampleCandidates(self, *args, **kwargs):
+        """Merged pairs of profiles are not sampled (mb_profile_twos_sample refuses them): the plain rule knows no planes."""
+        raise MachineError("sampling takes plain profiles")
+
+    samplePaths = pathProbability = sampleCandidates
 
     def forward(self, A, B, mode: str = "exact", env=None):
         """(loglike, N, W, Z), each [K+1][L+1][nCols+1][S]; mode "exact" or "max"."""
